@@ -145,6 +145,9 @@ typedef struct mmf_skinny_problem {
 int mmf_skinny_linear_fwd(const mmf_skinny_problem* problems, int num_problems, int flags, int out_f32, void* stream);
 int mmf_skinny_linear_dgrad(const mmf_skinny_problem* problems, int num_problems, int flags, float alpha, int out_f32,
                             void* stream);
+/* the strip width of the calling thread's last dgrad launch (mmf_skinny_linear_dgrad[_ex]): 4, 2 or 1 sixteen-column tiles of K
+ * per workgroup (4 when the launch has >= 128 64-column strips in all, 2 from 48, else 1); 0 before any call. */
+int mmf_skinny_last_strip(void);
 /* Round 4: the launches AROUND a (B, d)-row linear folded into it — these rows cost a launch (~5 us) per kernel, not bandwidth
  * (models/fusion_layers.py:21-28,304-327,395-412,471-476: every Linear there is followed by ReLU and / or Dropout and fed by a cat
  * or a pooled f32 tensor).
@@ -259,6 +262,10 @@ int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num_problems, 
 size_t mmf_layernorm_bwd_workspace_bytes(int d);
 int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num_problems, int d,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* the form the calling thread's last mmf_layernorm_fwd_grouped / _bwd_grouped call dispatched to (tests assert the form they
+ * target): 1-4 = the chunk form ln_*_kernel<NCH> (NCH 512-column chunks per row); 100 + 10 NV + H8 = the lane form
+ * ln_*_lane_kernel<NV, H8> (d = 512 NV + 256 H8: 110 / 111 / 101 / 120 for d = 512 / 768 / 256 / 1024); 0 before any call. */
+int mmf_layernorm_last_form(void);
 
 /* ------------------------------------------------------------------------------------------
  * Streaming helpers (HBM-bound, 16-byte vector accesses)

@@ -434,6 +434,10 @@ void ln_bwd_finalize_kernel(const LnArgs a) {
   atomicAdd(a.p[pi].dbeta + col, (sb[0] + sb[1]) + (sb[2] + sb[3]));
 }
 
+// the form and instantiation the calling thread's last forward / backward launch took (mmf_layernorm_last_form)
+thread_local int t_last_form = 0;
+constexpr int lane_form_id(int nv, int h8) { return 100 + 10 * nv + h8; }
+
 int check_common(const char* who, const mmf_ln_problem* p, int n, int d) {
   if (!p || n <= 0 || n > MMF_LN_MAX_PROBLEMS) MMF_FAIL(MMF_E_SHAPE, "%s: num_problems=%d out of range", who, n);
   if (d <= 0 || (d & 7) || d > MAX_CH * 512) MMF_FAIL(MMF_E_SHAPE, "%s: d=%d must be a multiple of 8, <= 2048", who, d);
@@ -441,6 +445,8 @@ int check_common(const char* who, const mmf_ln_problem* p, int n, int d) {
 }
 
 }  // namespace
+
+extern "C" int mmf_layernorm_last_form(void) { return t_last_form; }
 
 extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num_problems, int d,
                                          float eps, void* stream) {
@@ -481,6 +487,7 @@ extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num
     else if (d == 512)  hipLaunchKernelGGL((ln_fwd_lane_kernel<1, 0>), dim3(t2), dim3(256), 0, s, a);
     else if (d == 256)  hipLaunchKernelGGL((ln_fwd_lane_kernel<0, 1>), dim3(t2), dim3(256), 0, s, a);
     else                hipLaunchKernelGGL((ln_fwd_lane_kernel<2, 0>), dim3(t2), dim3(256), 0, s, a);
+    t_last_form = lane_form_id(d / 512, (d / 256) & 1);
     MMF_CHECK_LAUNCH("mmf_layernorm_fwd_grouped(lane)");
     return MMF_OK;
   }
@@ -491,6 +498,7 @@ extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num
     case 3: hipLaunchKernelGGL(ln_fwd_kernel<3>, dim3(total), dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL(ln_fwd_kernel<4>, dim3(total), dim3(256), 0, s, a); break;
   }
+  t_last_form = nch;
   MMF_CHECK_LAUNCH("mmf_layernorm_fwd_grouped");
   return MMF_OK;
 }
@@ -540,6 +548,7 @@ extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num
     else if (d == 512)  hipLaunchKernelGGL((ln_bwd_lane_kernel<1, 0>), dim3(total), dim3(256), 0, s, a);
     else if (d == 256)  hipLaunchKernelGGL((ln_bwd_lane_kernel<0, 1>), dim3(total), dim3(256), 0, s, a);
     else                hipLaunchKernelGGL((ln_bwd_lane_kernel<2, 0>), dim3(total), dim3(256), 0, s, a);
+    t_last_form = lane_form_id(d / 512, (d / 256) & 1);
     MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(lane)");
     hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((d + 255) / 256, num_problems, FIN_SLICES), dim3(256), 0, s, a);
     MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(finalize)");
@@ -551,6 +560,7 @@ extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num
     case 3: hipLaunchKernelGGL(ln_bwd_kernel<3>, dim3(total), dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(total), dim3(256), 0, s, a); break;
   }
+  t_last_form = nch;
   MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped");
   hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((d + 255) / 256, num_problems, FIN_SLICES), dim3(256), 0, s, a);
   MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(finalize)");

@@ -369,12 +369,16 @@ int launch_fwd(SkinnyArgs& a, const mmf_skinny_problem* problems, int num_proble
   return MMF_OK;
 }
 
+// the strip width (ct) of the calling thread's last dgrad launch (mmf_skinny_last_strip)
+thread_local int t_last_strip = 0;
+
 int launch_dgrad(SkinnyArgs& a, const mmf_skinny_problem* problems, int num_problems, int out_f32, void* stream) {
   int wide = 0;
   for (int i = 0; i < num_problems; ++i) wide += (problems[i].K + 63) / 64;
   // strip width: 64 columns when that already gives the chip a workgroup per two CUs, else 32, else 16 (MMF_SKINNY_CT pins it)
   static const int pin = [] { const char* e = getenv("MMF_SKINNY_CT"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 0; }();
   const int ct = pin ? pin : wide >= 128 ? 4 : wide >= 48 ? 2 : 1;
+  t_last_strip = ct;
   int total = 0;
   for (int i = 0; i < num_problems; ++i) { a.blk_start[i] = total; total += (problems[i].K + 16 * ct - 1) / (16 * ct); a.p[i] = problems[i]; }
   a.blk_start[num_problems] = total;
@@ -393,6 +397,8 @@ int launch_dgrad(SkinnyArgs& a, const mmf_skinny_problem* problems, int num_prob
 }
 
 }  // namespace
+
+extern "C" int mmf_skinny_last_strip(void) { return t_last_strip; }
 
 extern "C" int mmf_skinny_linear_fwd(const mmf_skinny_problem* problems, int num_problems, int flags, int out_f32,
                                      void* stream) {

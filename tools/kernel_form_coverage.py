@@ -1,0 +1,88 @@
+"""Which device kernel instantiations of libmmfusion.so a profiled run launched, and which it never did.
+
+    python tools/kernel_form_coverage.py LIB STATS.csv [STATS.csv ...] [--only REGEX]
+
+LIB is the built libmmfusion.so; each STATS.csv is the kernel-stats file of a `rocprofv3 --kernel-trace --stats` run (its
+`Name` column; several files are merged).  The instantiations are read off the `.kd` (kernel descriptor) symbols of the
+embedded code objects with `strings` and `c++filt`, so this runs on a machine without a GPU; it reads files only.
+--only keeps the instantiations whose name matches REGEX (the families a run targets, e.g. 'ln_|skinny_dgrad').
+Exit status 1 if an instantiation outside DELIBERATELY_UNLAUNCHED was never launched.
+"""
+import argparse
+import csv
+import re
+import subprocess
+import sys
+
+# forms no default dispatch reaches, kept on purpose (each with the switch that selects it)
+DELIBERATELY_UNLAUNCHED = {
+    # MMF_GEMM6_CFG=1 / 2: the 32-deep x 5-stage and 64-deep x 2-stage rings of generation 6, A/B ablations of its
+    # default 32 x 4 (csrc/gemm6.hip)
+    r"gemm6_grouped_kernel<(true|false), (true|false), 32, 5, (true|false)>",
+    r"gemm6_grouped_kernel<(true|false), (true|false), 64, 2, (true|false)>",
+}
+
+
+def key(name: str) -> str:
+    """kernel name with its template arguments, without return type, namespaces or parameter list:
+    'void (anonymous namespace)::ln_fwd_kernel<1>((anonymous namespace)::LnArgs) [clone .kd]' -> 'ln_fwd_kernel<1>'"""
+    n = name.replace("(anonymous namespace)::", "").replace(" [clone .kd]", "").strip()
+    if n.startswith("void "):
+        n = n[5:]
+    depth = 0
+    for i, ch in enumerate(n):          # cut at the parameter list: the first '(' outside template brackets
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0:
+            n = n[:i]
+            break
+    return re.sub(r"\s+", " ", n).strip()
+
+
+def instantiations(lib_path: str) -> set:
+    out = subprocess.run(["strings", "-a", lib_path], check=True, capture_output=True, text=True).stdout
+    # strings can glue a length byte in front of a name: match the mangled symbol itself
+    mangled = sorted(set(re.findall(r"_Z\w+\.kd", out)))
+    demangled = subprocess.run(["c++filt"], input="\n".join(mangled), check=True, capture_output=True, text=True).stdout
+    return {key(line) for line in demangled.splitlines() if line.strip()}
+
+
+def launched(stats_paths) -> set:
+    names = set()
+    for path in stats_paths:
+        with open(path, newline="") as f:
+            rows = [line for line in f if not line.startswith("#")]
+        for row in csv.DictReader(rows):
+            if row.get("Name"):
+                names.add(key(row["Name"]))
+    return names
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("lib")
+    ap.add_argument("stats", nargs="+")
+    ap.add_argument("--only", default=None, help="regex: report only the instantiations it matches")
+    a = ap.parse_args(argv)
+    forms = instantiations(a.lib)
+    if a.only:
+        forms = {k for k in forms if re.search(a.only, k)}
+    ran = launched(a.stats)
+    deliberate = {k for k in forms if any(re.fullmatch(p, k) for p in DELIBERATELY_UNLAUNCHED)}
+    hit = sorted(forms & ran)
+    missed = sorted(forms - ran - deliberate)
+    print(f"{len(forms)} instantiations{' matching ' + repr(a.only) if a.only else ''}; {len(hit)} launched, "
+          f"{len(missed)} never launched, {len(deliberate - ran)} deliberately unlaunched")
+    for k in hit:
+        print(f"  launched    {k}")
+    for k in sorted(deliberate - ran):
+        print(f"  deliberate  {k}")
+    for k in missed:
+        print(f"  NEVER       {k}")
+    return 1 if missed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
