@@ -104,22 +104,24 @@ typedef struct mmf_gemm_extra {
 int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue,
                         int out_f32, const mmf_gemm_extra* extra, void* stream);
 
-/* Tuning hook: which kernel mmf_gemm_grouped dispatches to (0 automatic [default]; 2 LDS-DMA ring 256x128; 4 LDS-DMA ring
- * 256x256; 5 256x128 with a 32-deep k-step and two workgroups per CU; 6 256x256 on one wave per SIMD with 128x128 wave tiles
- * [gemm6.hip: any K for TN, K % 32 == 0 for NT / NN, no aux epilogue with f32 output — otherwise the automatic choice]).
- * Automatic: 6 for TN (wgrad) and for NT / NN launches with K >= 512 that give at least half of the CUs a tile, else per launch
- * from the tile count and K (gemm.hip auto_impl); 7: see mmf_gemm_set_persistent_workgroups below.  1 and 3 (rounds 1-2: register-staged 128x128, persistent ring) were
- * removed in round 3 and are refused with MMF_E_SHAPE.  Results are identical up to f32 summation order; exists so that A/B
- * timings can be interleaved inside one process. */
+/* Tuning hook: which kernel mmf_gemm_grouped dispatches to.  0 = automatic [default]; 2 = LDS-DMA ring 256x128; 6 = 256x256 on
+ * one wave per SIMD with 128x128 wave tiles [gemm6.hip: any K for TN, K % 32 == 0 for NT / NN, no aux epilogue with f32 output];
+ * 7 = generation 6 on persistent workgroups (below).  Automatic (gemm.hip auto_impl): 6 when the launch has 256x256 tiles for at
+ * least half of the CUs (TN, wgrad) or a quarter of them (NT / NN) and generation 6 takes its shapes, else 2; a launch that
+ * gets 6 is promoted to 7 whenever generation 7 takes it (MMF_GEMM_PERSIST=0: never).  A pinned generation is used for every
+ * launch it takes; the others fall back 7 -> 6 -> 2.  Any other value (1 / 3 left in round 3, 4 / 5 in round 4) is refused
+ * with MMF_E_UNSUPPORTED.  Results are identical up to f32 summation order (and, with a bias, one bf16 ulp between 6 and 7);
+ * exists so that A/B timings can be interleaved inside one process.  A process-wide setting, not synchronised between threads. */
 int mmf_gemm_select_impl(int impl);
 /* the kernel generation the calling thread's last mmf_gemm_grouped[_ex] call dispatched to (profiling labels) */
 int mmf_gemm_last_impl(void);
 /* Round 4, generation 7 (gemm7.hip): generation 6's tile on PERSISTENT workgroups — one per CU, each walking the tiles w, w + grid,
  * ... of the launch with its LDS ring running on across tile boundaries (no ring fill and no idle matrix pipe between tiles).  NT /
- * NN with bf16 output, K % 32 == 0 and K >= 160; the automatic choice takes it for every such launch generation 6 would get that
- * has more tiles than CUs (MMF_GEMM_PERSIST=0: off).  Results are bit-identical to generation 6.
+ * NN with bf16 output, K % 32 == 0, K >= 160, N and the leading dimensions of C / aux multiples of 8, and the flag sets of the
+ * fusion step.  Bit-identical to generation 6 without a bias; with one the accumulators start from the bias, so outputs may
+ * differ by one bf16 ulp.
  * mmf_gemm_set_persistent_workgroups(n): grid size of generation 7 (0 = the CU count [default]); a test / tuning hook: with a
- * small n a small problem exercises many tiles per workgroup. */
+ * small n a small problem exercises many tiles per workgroup.  Process-wide, not synchronised between threads. */
 int mmf_gemm_set_persistent_workgroups(int n);
 
 /* ------------------------------------------------------------------------------------------
@@ -227,7 +229,7 @@ int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_problems, int
 int mmf_attn_fwd_grouped_ex(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
                             float dropout_p, const uint64_t* rng_state, uint32_t site, void* stream);
 /* Tuning hook kept for ABI stability: 0 (automatic) and 2 select attention2.hip, the only implementation since round 3
- * (LDS-DMA ring, 128 query rows per workgroup, XCD-aware order); any other value is refused with MMF_E_SHAPE. */
+ * (LDS-DMA ring, 128 query rows per workgroup, XCD-aware order); any other value is refused with MMF_E_UNSUPPORTED. */
 int mmf_attn_select_impl(int impl);
 int mmf_attn_bwd_grouped_ex(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
                             float dropout_p, const uint64_t* rng_state, uint32_t site, void* stream);

@@ -207,15 +207,12 @@ class BackwardExchange:
     # -- overridable: how a round's GEMMs are issued (the CPU logic test substitutes torch arithmetic) -----------------
     def _issue(self, problems) -> None:
         from . import ops
-        if self.arena.grads.is_cuda:
-            ops._issue_wgrad_side(problems, all_streams=True)      # on the wgrad stream, behind every producer stream
-        else:
-            ops.issue_wgrad(problems)
+        ops.issue_wgrad(problems, side=self.arena.grads.is_cuda)      # on the wgrad stream, behind every producer stream
 
     def _stream(self):
         from . import ops
-        if self.arena.grads.is_cuda and ops._wgrad_stream is not None:
-            return torch.cuda.stream(ops._wgrad_stream)
+        if self.arena.grads.is_cuda and ops.wgrad_stream() is not None:
+            return torch.cuda.stream(ops.wgrad_stream())
         import contextlib
         return contextlib.nullcontext()
 
@@ -287,8 +284,8 @@ class BackwardExchange:
         """Call after backward AND ``arena.finalize_grads()``: exchange what no round sent, then wait for everything."""
         if self.arena.grads.is_cuda:
             from . import ops
-            if ops._wgrad_stream is not None:            # the final round's GEMMs ran on the wgrad stream
-                torch.cuda.current_stream().wait_stream(ops._wgrad_stream)
+            if ops.wgrad_stream() is not None:           # the final round's GEMMs ran on the wgrad stream
+                torch.cuda.current_stream().wait_stream(ops.wgrad_stream())
         plan = self._plan or []
         for i in range(self._sent_rounds, len(plan)):    # planned rounds this rank did not reach: same collectives, only later
             self._send(plan[i])

@@ -248,17 +248,13 @@ def dropout(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
 # block's wgrads are ~100 tiles, far fewer than 256 CUs.  Nothing downstream in the backward pass
 # reads dW, so every Function only *queues* its wgrad problems and one autograd end-of-backward
 # callback issues them all as grouped launches (>= 1000 tiles for MulT), bias gradients included.
+#
+# What the end-of-backward callback (_flush_wgrad) does with the queue is one of three modes:
+#   automatic   issue everything on the current stream (what is left after the optional early launch, below);
+#   manual      park it for the caller (set_manual_wgrad_flush: bench.py's overlapped data-parallel step);
+#   round hook  hand it to a hook in rounds, the first ones during backward (set_wgrad_rounds: mmfusion.dp.BackwardExchange).
 import os as _os
 
-DEFER_WGRAD = _os.environ.get("MMF_DEFER_WGRAD", "1") != "0"
-_SKINNY = _os.environ.get("MMF_SKINNY", "1") != "0"          # skinny-M kernels for problems with <= 64 rows
-_pending_wgrad: List[tuple] = []
-# Side-stream wgrad (MMF_WGRAD_SIDE=1, experimental A/B): instead of one flush at the end of backward, the queued
-# wgrad problems are issued on a second stream whenever MMF_WGRAD_CHUNK output tiles have accumulated, so the long
-# wgrad GEMMs fill the CUs the dgrad / attention / LayerNorm chain leaves idle (launch tails, latency-bound kernels).
-_WGRAD_SIDE = _os.environ.get("MMF_WGRAD_SIDE", "0") == "1"
-_WGRAD_CHUNK = int(_os.environ.get("MMF_WGRAD_CHUNK", "800"))
-_wgrad_stream: Optional[torch.cuda.Stream] = None
 # Early flush (MMF_WGRAD_EARLY=1; measured +0.4 % and left OFF by default — with it the dominant kernel shares the chip with
 # the input-gradient sums, so its duration in a profile of the timed steps no longer equals its stand-alone duration, which
 # is what bench.py's roofline is built on): the number of weight-gradient problems a backward queues is the same every
@@ -268,10 +264,25 @@ _wgrad_stream: Optional[torch.cuda.Stream] = None
 # then runs beside the wgrad launch instead of in front of it.  A backward that queues more, or fewer, than the last one
 # is still complete: whatever is pending when the callback runs is issued there, and the callback joins the stream.
 _WGRAD_EARLY = _os.environ.get("MMF_WGRAD_EARLY", "0") == "1"
-_expected_wgrad = 0
-_early_issued = 0
-_callback_queued = False
-_pending_tiles = 0
+_pending_wgrad: List[tuple] = []
+_wgrad_stream: Optional[torch.cuda.Stream] = None
+
+
+class _Backward:
+    """Bookkeeping of the backward pass in progress.  The end-of-backward callback replaces it with a fresh one that carries
+    over what this backward taught: how many problems it queued and which gradient regions it wrote more than once."""
+
+    def __init__(self, expected: int = 0):
+        self.expected = expected                  # problems the previous backward queued (0: unknown)
+        self.multi_writer: set = set()            # gradient pointers the previous backward wrote twice (round hook only)
+        self.callback_queued = False
+        self.early = 0                            # problems issued by the early launch
+        self.round_issued = 0                     # problems handed to the round hook before the end of backward
+        self.rounds_cut = 0                       # rounds handed over so far
+        self.round_ptrs: List[int] = []           # gradient pointers handed over in those rounds
+
+
+_bw = _Backward()
 
 
 _branch_streams: List[torch.cuda.Stream] = []
@@ -279,7 +290,7 @@ _branch_streams: List[torch.cuda.Stream] = []
 
 def branch_stream(i: int = 0) -> torch.cuda.Stream:
     """Extra stream i for work that runs beside the main chain (HierarchicalFusion's small branches, the concurrent
-    halves of MulT's cross blocks).  The deferred wgrad flush and anything else that consumes its results on the
+    half of MulT's cross blocks).  The deferred wgrad flush and anything else that consumes its results on the
     main stream joins every branch stream first (``join_branch_streams``)."""
     while len(_branch_streams) <= i:
         _branch_streams.append(torch.cuda.Stream())
@@ -290,9 +301,6 @@ def join_branch_streams() -> None:
     cur = torch.cuda.current_stream()
     for s in _branch_streams:
         cur.wait_stream(s)
-
-
-_WGRAD_SORT = _os.environ.get("MMF_WGRAD_SORT", "k")
 
 
 def _wgrad_rounds(pend: List[tuple]) -> List[List[tuple]]:
@@ -337,28 +345,36 @@ def _issue_wgrad(pend: List[tuple]) -> None:
         # kernel hands tiles to the CUs in this order, so the tail of the launch is made of the short tiles.
         # Overwrite groups before accumulate groups.
         for (has_bias, overwrite), group in sorted(groups.items(), key=lambda kv: (not kv[0][1], not kv[0][0])):
-            if _WGRAD_SORT == "k":
-                group.sort(key=lambda t: (-t[0].shape[0], -(t[2].shape[0] * t[2].shape[1])))
-            else:
-                group.sort(key=lambda t: -(t[2].shape[0] * t[2].shape[1] * t[0].shape[0]))
+            group.sort(key=lambda t: (-t[0].shape[0], -(t[2].shape[0] * t[2].shape[1])))
             gemm_group(GEMM_TN, group, (0 if overwrite else EPI_ACCUM) | (EPI_COLSUM_A if has_bias else 0))
 
 
-def _issue_wgrad_side(pend: List[tuple], all_streams: bool = False) -> None:
+def issue_wgrad(pend: List[tuple], side: bool = False) -> None:
+    """Issue queued wgrad problems now, as grouped launches (as the automatic flush does): on the current stream, or with
+    ``side`` on the wgrad stream (``wgrad_stream()``) behind the current stream and every branch stream."""
     global _wgrad_stream
+    if not pend:
+        return
+    if not side:
+        _issue_wgrad(pend)
+        return
     if _wgrad_stream is None:
         _wgrad_stream = torch.cuda.Stream()
     cur = torch.cuda.current_stream()
     _wgrad_stream.wait_stream(cur)                       # the queued dy / x are complete on the main stream
-    if all_streams:                                      # ... and on the branch streams other backward nodes ran on
-        for st in _branch_streams:
-            if st != cur:
-                _wgrad_stream.wait_stream(st)
+    for st in _branch_streams:                           # ... and on the branch streams other backward nodes ran on
+        if st != cur:
+            _wgrad_stream.wait_stream(st)
     with torch.cuda.stream(_wgrad_stream):
         _issue_wgrad(pend)
     for q in pend:                                       # keep the operands' memory until the side kernels ran
         q[0].record_stream(_wgrad_stream)
         q[1].record_stream(_wgrad_stream)
+
+
+def wgrad_stream() -> Optional[torch.cuda.Stream]:
+    """The stream ``issue_wgrad(..., side=True)`` launches on; None until the first such launch."""
+    return _wgrad_stream
 
 
 # Manual flush (data-parallel overlap, bench.py / mmfusion.dp): the end-of-backward callback only parks the queued
@@ -370,8 +386,6 @@ _parked_wgrad: List[tuple] = []
 
 def set_manual_wgrad_flush(on: bool) -> None:
     global _MANUAL_FLUSH
-    if not DEFER_WGRAD and on:
-        raise RuntimeError("manual wgrad flush needs the deferred wgrad queue (MMF_DEFER_WGRAD=1)")
     _MANUAL_FLUSH = bool(on)
 
 
@@ -412,12 +426,6 @@ def split_wgrad_by_offset(pend: List[tuple], nparts: int = 2) -> Tuple[List[List
     return parts, bounds
 
 
-def issue_wgrad(pend: List[tuple]) -> None:
-    """Issue queued wgrad problems now, on the current stream (grouped launches, as the automatic flush does)."""
-    if pend:
-        _issue_wgrad(pend)
-
-
 # Round flush (data-parallel exchange INSIDE backward, SURVEY 8e / VERDICT r2 item 5a): with a hook installed, the backward
 # hands its queued weight-gradient problems over in `n` rounds in reverse-autograd order — round i as soon as i/n of the
 # problems the PREVIOUS backward queued have been queued again — and whatever is left from the end-of-backward callback
@@ -428,55 +436,46 @@ def issue_wgrad(pend: List[tuple]) -> None:
 # installing the hook has nothing to learn from and delivers everything in the final round.
 _ROUND_HOOK = None
 _ROUND_N = 0
-_round_issued = 0
-_multi_writer: set = set()
-_round_ptrs: List[int] = []          # gradient pointers handed over in this backward's earlier rounds
-_rounds_cut = 0                      # rounds handed over so far in this backward
 
 
 def set_wgrad_rounds(n: int, hook) -> None:
-    """hook(problems, final) or None to remove.  Needs the deferred queue (MMF_DEFER_WGRAD=1); excludes the manual flush."""
-    global _ROUND_HOOK, _ROUND_N, _round_issued, _expected_wgrad
-    if hook is not None and (not DEFER_WGRAD or _MANUAL_FLUSH or n < 1):
-        raise RuntimeError("wgrad rounds need the deferred wgrad queue, no manual flush, n >= 1")
-    _ROUND_HOOK, _ROUND_N, _round_issued = hook, int(n), 0
-    _expected_wgrad = 0
+    """hook(problems, final) or None to remove.  Excludes the manual flush."""
+    global _ROUND_HOOK, _ROUND_N
+    if hook is not None and (_MANUAL_FLUSH or n < 1):
+        raise RuntimeError("wgrad rounds need no manual flush and n >= 1")
+    _ROUND_HOOK, _ROUND_N = hook, int(n)
+    _bw.expected = 0
 
 
 def _maybe_cut_round() -> None:
     """queue_wgrad: hand over a round when its share of the expected problems has been queued."""
-    global _pending_wgrad, _round_issued
-    if _ROUND_HOOK is None or not _expected_wgrad or _ROUND_N < 2:
+    global _pending_wgrad
+    if _ROUND_HOOK is None or not _bw.expected or _ROUND_N < 2:
         return
-    global _rounds_cut
-    done = _round_issued + len(_pending_wgrad)
-    k = _rounds_cut + 1                                                # the round being filled, 1-based
-    if k >= _ROUND_N or done * _ROUND_N < k * _expected_wgrad:
+    done = _bw.round_issued + len(_pending_wgrad)
+    k = _bw.rounds_cut + 1                                             # the round being filled, 1-based
+    if k >= _ROUND_N or done * _ROUND_N < k * _bw.expected:
         return                                                         # (the last round is the end-of-backward callback's)
-    _rounds_cut = k
-    ready = [q for q in _pending_wgrad if q[2].data_ptr() not in _multi_writer]
+    _bw.rounds_cut = k
+    ready = [q for q in _pending_wgrad if q[2].data_ptr() not in _bw.multi_writer]
     if not ready:
         return
-    _pending_wgrad = [q for q in _pending_wgrad if q[2].data_ptr() in _multi_writer]
-    _round_issued += len(ready)
-    _round_ptrs.extend(q[2].data_ptr() for q in ready)
+    _pending_wgrad = [q for q in _pending_wgrad if q[2].data_ptr() in _bw.multi_writer]
+    _bw.round_issued += len(ready)
+    _bw.round_ptrs.extend(q[2].data_ptr() for q in ready)
     _ROUND_HOOK(ready, False)
 
 
 def _flush_wgrad() -> None:
-    global _pending_wgrad, _callback_queued, _pending_tiles, _expected_wgrad, _early_issued, _round_issued, _multi_writer
-    pend, _pending_wgrad = _pending_wgrad, []
-    _callback_queued, _pending_tiles = False, 0
-    early, _early_issued = _early_issued, 0
-    global _rounds_cut
-    rounds_done, _round_issued, _rounds_cut = _round_issued, 0, 0
-    _expected_wgrad = early + rounds_done + len(pend)    # what the next backward is expected to queue
+    """The end-of-backward callback: what is still queued goes to the flush mode in force."""
+    global _bw, _pending_wgrad
+    bw, pend, _pending_wgrad = _bw, _pending_wgrad, []
+    _bw = _Backward(expected=bw.early + bw.round_issued + len(pend))    # what the next backward is expected to queue
     if _ROUND_HOOK is not None:
         seen: dict = {}
-        for ptr in _round_ptrs + [q[2].data_ptr() for q in pend]:
+        for ptr in bw.round_ptrs + [q[2].data_ptr() for q in pend]:
             seen[ptr] = seen.get(ptr, 0) + 1
-        _multi_writer = {ptr for ptr, c in seen.items() if c > 1}
-        _round_ptrs.clear()
+        _bw.multi_writer = {ptr for ptr, c in seen.items() if c > 1}
         _ROUND_HOOK(pend, True)
         return
     if _branch_streams:                                  # operands queued by backward nodes that ran on a branch stream
@@ -488,51 +487,33 @@ def _flush_wgrad() -> None:
     if _MANUAL_FLUSH:
         _parked_wgrad.extend(pend)
         return
-    if _WGRAD_SIDE:
-        if pend:
-            _issue_wgrad_side(pend)
-        if _wgrad_stream is not None:
-            torch.cuda.current_stream().wait_stream(_wgrad_stream)      # gradients complete when backward returns
-        return
-    if early and _wgrad_stream is not None:
+    if bw.early:
         # gradients complete when backward returns — and BEFORE any left-over problem is issued here: a left-over may
         # accumulate into a region the early launch is still writing (a weight used twice)
         torch.cuda.current_stream().wait_stream(_wgrad_stream)
-    if pend:
-        _issue_wgrad(pend)
+    issue_wgrad(pend)
 
 
 def queue_wgrad(dy: torch.Tensor, x: torch.Tensor, wgrad: torch.Tensor, bgrad: Optional[torch.Tensor]) -> None:
     """wgrad (f32, [N_out, K_in]) += dy^T x ;  bgrad (f32 [N_out]) += column sums of dy.
     If the gradient lives in an arena that was zeroed lazily this step and nothing has written it yet, the
     GEMM overwrites instead (``ParamArena.take_first_touch``)."""
-    global _callback_queued, _pending_tiles, _pending_wgrad
+    global _pending_wgrad
     overwrite = False
     from .arena import arena_of
     ar = arena_of(wgrad)
     if ar is not None:
         overwrite = ar.take_first_touch(wgrad)
-    if not DEFER_WGRAD:
-        gemm_group(GEMM_TN, [(dy, x, wgrad, bgrad, None)],
-                   (0 if overwrite else EPI_ACCUM) | (EPI_COLSUM_A if bgrad is not None else 0))
-        return
-    if not _callback_queued:
+    if not _bw.callback_queued:
         torch.autograd.Variable._execution_engine.queue_callback(_flush_wgrad)
-        _callback_queued = True
+        _bw.callback_queued = True
     _pending_wgrad.append((dy, x, wgrad, bgrad, None, overwrite))
     _maybe_cut_round()
-    global _early_issued
-    if (_WGRAD_EARLY and not _WGRAD_SIDE and not _MANUAL_FLUSH and _ROUND_HOOK is None and _expected_wgrad and not _early_issued
-            and len(_pending_wgrad) == _expected_wgrad):
+    if (_WGRAD_EARLY and not _MANUAL_FLUSH and _ROUND_HOOK is None and _bw.expected and not _bw.early
+            and len(_pending_wgrad) == _bw.expected):
         pend, _pending_wgrad = _pending_wgrad, []
-        _early_issued = len(pend)
-        _issue_wgrad_side(pend, all_streams=True)
-    if _WGRAD_SIDE:
-        _pending_tiles += ((wgrad.shape[0] + 255) // 256) * ((wgrad.shape[1] + 127) // 128)
-        if _pending_tiles >= _WGRAD_CHUNK:
-            pend, _pending_wgrad = _pending_wgrad, []
-            _pending_tiles = 0
-            _issue_wgrad_side(pend)
+        _bw.early = len(pend)
+        issue_wgrad(pend, side=True)
 
 
 # --------------------------------------------------------------------------------------------
@@ -643,7 +624,7 @@ class _GroupedLinear(torch.autograd.Function):
             probs.append((x, w16, y, bias, res))
             xs.append(x), ress.append(res), outs.append(y)
         epi = (EPI_BIAS if has_bias else 0) | (EPI_RELU if relu else 0) | (EPI_ADD_AUX if has_res else 0)
-        skinny = _SKINNY and not has_res and all(x.shape[0] <= lib.SKINNY_MAX_M and x.shape[1] % 8 == 0 for x in xs)
+        skinny = not has_res and all(x.shape[0] <= lib.SKINNY_MAX_M and x.shape[1] % 8 == 0 for x in xs)
         if skinny:          # (B, d)-row problems: weight-streaming kernels instead of the 256-row tile
             lib.skinny_fwd([lib.SkinnyProblem(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                                               b.data_ptr() if b is not None else None, None,
@@ -728,7 +709,7 @@ class _GroupedLinear(torch.autograd.Function):
             if s.has_residual:
                 grads[4 * i + 1] = g
         if dgrad:
-            if _SKINNY and all(g.shape[0] <= lib.SKINNY_MAX_M for (g, _, _, _, _) in dgrad):
+            if all(g.shape[0] <= lib.SKINNY_MAX_M for (g, _, _, _, _) in dgrad):
                 lib.skinny_dgrad([lib.SkinnyProblem(g.data_ptr(), w.data_ptr(), dx.data_ptr(), None, None,
                                                     g.shape[0], w.shape[0], w.shape[1], _ld(g), _ld(w), _ld(dx), 0)
                                   for (g, w, dx, _, _) in dgrad], 0, 1.0, ctx.f32_in)
@@ -849,7 +830,7 @@ class _RowLinear(torch.autograd.Function):
 
 def row_linear_ok(items: Sequence[tuple]) -> bool:
     """whether a linear group can take the fused (B, d)-row form: bf16 mode, <= 64 rows, no residual, one launch"""
-    if _PRECISION == "fp32" or not _SKINNY or len(items) > lib.SKINNY_MAX_PROBLEMS:
+    if _PRECISION == "fp32" or len(items) > lib.SKINNY_MAX_PROBLEMS:
         return False
     for x, spec, res in items:
         if res is not None or x.dim() != 2 or x.shape[0] > lib.SKINNY_MAX_M or x.shape[1] % 8 or spec.w.w16.shape[0] % 4:

@@ -33,8 +33,6 @@ from mmfusion.ops import AttnSpec, LinearSpec, W
 _depth = 0          # >0 while inside an outer fusion forward: the arena was already ensured
 import os as _os
 _BRANCH_STREAM = _os.environ.get("MMF_HIER_STREAMS", "1") != "0"   # HierarchicalFusion: small branches beside MulT
-_MULT_NESTED = _os.environ.get("MMF_MULT_NESTED", "0") == "1"      # A/B: the two groups also when MulT runs inside HierarchicalFusion
-_INTERLEAVE = _os.environ.get("MMF_HIER_INTERLEAVE", "1") != "0"    # HierarchicalFusion: side branches issued BETWEEN MulT's stages
 # Side-branch thunks of an enclosing HierarchicalFusion, run one per stage of the MulT cross blocks (`_tick`).  A captured graph's nodes
 # are submitted in the order they were created: with the four (B, d)-row branches (~100 launches) created in front of MulT their forward
 # ran BEFORE MulT's first GEMM and — autograd executes in reverse creation order — their backward AFTER MulT's last, 250 + 300 us of
@@ -50,13 +48,13 @@ def _tick() -> None:
         if fn is not None:
             fn()
 _RECAST = _os.environ.get("MMF_RECAST_EACH_STEP", "0") == "1"        # fp32 -> bf16 weight cast in every training forward
-_MULT_STREAMS = int(_os.environ.get("MMF_MULT_STREAMS", "2"))       # MulT's cross blocks as this many concurrent groups (1, 2, 3)
-# How the two groups are cut (round 3): "modality" = by QUERY modality — {t<-a, t<-v} + the text self-attention on one
-# stream, {a<-t, a<-v, v<-t, v<-a} + the audio / video self-attentions on the other, joined only in front of the pooled
-# projections — so the self-attention section (in-projection, cores, their backward: ~400 us of single-stream,
-# partly-filled launches per step in rounds 1-2) also runs two streams wide; "size" = rounds 1-2: {t<-a, a<-v, v<-t} /
-# {t<-v, a<-t, v<-a}, joined after the cross blocks.
-_MULT_GROUPING = _os.environ.get("MMF_MULT_GROUPING", "modality")
+# MulT as the root module: 2 = its blocks cut by QUERY modality over two streams (round 3) — {t<-a, t<-v} + the text
+# self-attention on one, {a<-t, a<-v, v<-t, v<-a} + the audio / video self-attentions on the other, joined only in front of the
+# pooled projections, so the self-attention section (in-projection, cores, their backward: ~400 us of single-stream,
+# partly-filled launches per step in rounds 1-2) also runs two streams wide; 1 = everything on the current stream.
+_MULT_STREAMS = int(_os.environ.get("MMF_MULT_STREAMS", "2"))
+if _MULT_STREAMS not in (1, 2):
+    raise ValueError(f"MMF_MULT_STREAMS must be 1 or 2, got {_MULT_STREAMS}")
 
 
 class _FusionBase(nn.Module):
@@ -340,68 +338,31 @@ class MultimodalTransformer(_FusionBase):
         Tqs, Tks = [Tt, Tt, Ta, Ta, Tv, Tv], [Ta, Tv, Tt, Tv, Tt, Ta]
         t, a, v = tf[6], af[6], vf[6]
         mhas = [self.text_self_attn, self.audio_self_attn, self.video_self_attn]
-        streams = _MULT_STREAMS > 1 and (_depth == 1 or _MULT_NESTED) and t.is_cuda and not ops.fp32_mode()
-        # (as the root module only: nested in HierarchicalFusion the branch stream already fills the holes, and a third
-        # stream measured slower: hier-seq 2.90 -> 3.24 ms)
-
-        def run_blocks(g):
-            return _cross_blocks([blocks[i] for i in g], [qs[i] for i in g], [kvs[i] for i in g], B,
-                                 [Tqs[i] for i in g], [Tks[i] for i in g], p, [ress[i] for i in g])
-
-        if streams and _MULT_STREAMS == 2 and _MULT_GROUPING in ("modality", "tv_a"):
-            # Two independent chains up to the pooled projections, cut by QUERY modality; autograd replays each node's backward
-            # on its forward stream, so the backward is two chains wide as well.  "modality": text on the current stream, audio +
-            # video on the side stream.  "tv_a" (MMF_MULT_GROUPING=tv_a): text + video | audio — tried because the audio + video stream finishes its
-            # backward ~110 us after the text stream (its 30-row attention problems are one-wave chains): level, 2.163 vs 2.165 ms.
-            mods = {"modality": ([0], [1, 2]), "tv_a": ([0, 2], [1])}[_MULT_GROUPING]
+        streams = _MULT_STREAMS > 1 and _depth == 1 and t.is_cuda and not ops.fp32_mode()
+        # (as the root module only: nested in HierarchicalFusion the branch stream already fills the holes, and the cut
+        # there measured slower: hier-seq 2.90 -> 3.24 ms)
+        if streams:
+            # Two independent chains up to the pooled projections, text on the current stream, audio + video on the side
+            # stream; autograd replays each node's backward on its forward stream, so the backward is two chains wide as well.
             xs3, Ts3 = [t, a, v], [Tt, Ta, Tv]
 
             def chain(ms):          # query modalities ms: their two cross blocks each, the three-way sums, the self-attentions
-                outs = run_blocks([2 * m + j for m in ms for j in (0, 1)])
+                g = [2 * m + j for m in ms for j in (0, 1)]
+                outs = _cross_blocks([blocks[i] for i in g], [qs[i] for i in g], [kvs[i] for i in g], B,
+                                     [Tqs[i] for i in g], [Tks[i] for i in g], p, [ress[i] for i in g])
                 es = ops.add3_group([(xs3[m], outs[2 * i], outs[2 * i + 1]) for i, m in enumerate(ms)])   # :156-158
                 return _self_attention_core([mhas[m] for m in ms], es, B, [Ts3[m] for m in ms], p)
             main = torch.cuda.current_stream()
             side = ops.branch_stream(1)                     # stream 0 belongs to HierarchicalFusion's small branches
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                att_side = chain(mods[1])
-            att_main = chain(mods[0])
-            att = [None, None, None]
-            for m, x in zip(mods[0], att_main):
-                att[m] = x
-            for m, x in zip(mods[1], att_side):
-                att[m] = x
+                att_side = chain([1, 2])
+            att = [*chain([0]), *att_side]
             main.wait_stream(side)
             for x in att_side:
                 x.record_stream(main)
         else:
-            if streams:
-                # The six blocks are independent: as balanced groups on concurrent streams, one group's HBM- / latency-bound
-                # launches (attention, LayerNorm, residual adds, the partly filled last round of every GEMM launch) run
-                # beside another group's GEMMs.  Forward here; autograd replays each node's backward on its forward stream.
-                groups = {2: ([0, 3, 4], [1, 2, 5]),           # {t<-a, a<-v, v<-t} / {t<-v, a<-t, v<-a}: one query size each
-                          3: ([0, 4], [1, 5], [2, 3])}[_MULT_STREAMS]
-                main = torch.cuda.current_stream()
-                outs = [None] * 6
-                sides = []
-                for gi, g in enumerate(groups[1:]):
-                    side = ops.branch_stream(1 + gi)
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        r = run_blocks(g)
-                    for i, x in zip(g, r):
-                        outs[i] = x
-                    sides.append((side, g))
-                g = groups[0]
-                for i, x in zip(g, run_blocks(g)):
-                    outs[i] = x
-                for side, g in sides:
-                    main.wait_stream(side)
-                    for i in g:
-                        outs[i].record_stream(main)
-                t_a, t_v, a_t, a_v, v_t, v_a = outs
-            else:
-                t_a, t_v, a_t, a_v, v_t, v_a = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress)    # :146-153
+            t_a, t_v, a_t, a_v, v_t, v_a = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress)    # :146-153
             et, ea, ev = ops.add3_group([(t, t_a, t_v), (a, a_t, a_v), (v, v_t, v_a)])         # :156-158, one launch
             att = _self_attention_core(mhas, [et, ea, ev], B, [Tt, Ta, Tv], p)
         # :161-168.  The self-attention outputs are only ever used through their mean over T, and the
@@ -627,7 +588,7 @@ class HierarchicalFusion(_FusionBase):
                       None,                                                                      # (LayerNorm 1)
                       on_side("graph", lambda: self.graph_fusion(*tav))]    # ... the FFN: the longest branch chain (3 GAT layers)
             # backward runs beside the FFN's two dgrads, the first big launches of MulT's backward
-            if _INTERLEAVE and not rows_only:       # (with (B, d) inputs every launch is a few us: interleaving only adds cross-stream
+            if not rows_only:                       # (with (B, d) inputs every launch is a few us: interleaving only adds cross-stream
                 _between[:] = thunks                # hand-offs — MELD-shaped step 1.02 -> 1.06 ms)
             else:
                 for fn in (thunks[2], thunks[4], thunks[1], thunks[0]):

@@ -97,3 +97,107 @@ def test_wgrad_rounds_separate_writers_of_one_region():
     rounds = ops._wgrad_rounds([a, b, c, d, e])
     assert [len(r) for r in rounds] == [2, 1, 2]          # d and e touch disjoint memory: one round
     assert rounds[0] == [a, b] and rounds[1] == [c] and rounds[2] == [d, e]
+
+
+# --- the deferred wgrad queue (ops.queue_wgrad) driven by a backward pass on the CPU, ops.gemm_group recorded ---------------
+class _FirstTouchArena:
+    """What ops.queue_wgrad needs of a ParamArena: the gradient buffer, and lazy zeroing's first-touch answer (the first
+    writer of a region overwrites, every later one accumulates)."""
+
+    def __init__(self, numel):
+        self.numel = numel
+        self.grads = torch.zeros(numel)
+        self.touched = set()
+
+    def take_first_touch(self, g):
+        first = g.data_ptr() not in self.touched
+        self.touched.add(g.data_ptr())
+        return first
+
+
+class _QueueWgrad(torch.autograd.Function):
+    """Queues the given (dy, x, wgrad, bgrad) problems from its backward, as the product Functions do."""
+
+    @staticmethod
+    def forward(ctx, x, probs):
+        ctx.probs = probs
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        from mmfusion import ops
+        for dy, x, wg, bg in ctx.probs:
+            ops.queue_wgrad(dy, x, wg, bg)
+        return g, None
+
+
+def _run_queue(monkeypatch):
+    """One backward that queues seven problems; -> (names by id of the weight gradient, queued problems, gemm_group calls).
+    Arena regions: W1 (+ bias b1), W2, W3, W4; `loose` lives outside every arena (always accumulated)."""
+    from mmfusion import arena as arena_mod, ops
+    calls = []
+    monkeypatch.setattr(ops, "gemm_group", lambda layout, probs, epi, *a, **k: calls.append((layout, list(probs), epi)))
+    ar = _FirstTouchArena(256)
+    monkeypatch.setattr(arena_mod, "_ARENAS", {ar})
+    W1, W2, W3, W4 = (ar.grads[0:32].view(4, 8), ar.grads[64:112].view(6, 8), ar.grads[128:160].view(4, 8),
+                      ar.grads[160:176].view(2, 8))
+    b1, loose = ar.grads[192:196], torch.zeros(2, 8)
+    names = {id(W1): "W1", id(W2): "W2", id(W3): "W3", id(W4): "W4", id(loose): "loose"}
+
+    def prob(k, w, b=None):
+        return torch.randn(k, w.shape[0]), torch.randn(k, w.shape[1]), w, b
+    # queue order = backward order: W1 and W3 are written twice (a weight used twice in one forward)
+    probs = [prob(5, W1, b1), prob(9, W2), prob(11, W4), prob(11, W3), prob(7, loose), prob(3, W1, b1), prob(12, W3)]
+    _QueueWgrad.apply(torch.ones(1, requires_grad=True), probs).sum().backward()
+    return names, probs, calls
+
+
+def test_wgrad_queue_automatic_flush_order(monkeypatch):
+    """The end-of-backward flush: writers of one region in separate launches, overwrite groups before accumulate groups,
+    K (the rows of dy) descending then output size inside a group, the fused bias gradient only where a bias is set."""
+    from mmfusion import lib, ops
+    names, probs, calls = _run_queue(monkeypatch)
+    got = [(layout, [names[id(q[2])] for q in group], epi) for layout, group, epi in calls]
+    TN, ACC, COLSUM = lib.GEMM_TN, lib.EPI_ACCUM, lib.EPI_COLSUM_A
+    assert got == [(TN, ["W1"], COLSUM),                  # round 1: overwrite + bias
+                   (TN, ["W3", "W4", "W2"], 0),           # ... overwrite: K 11, 11, 9; W4 (2 x 8) after W3 (4 x 8)
+                   (TN, ["loose"], ACC),                  # ... accumulate
+                   (TN, ["W1"], ACC | COLSUM),            # round 2: the second writers of W1 and W3
+                   (TN, ["W3"], ACC)]
+    for _, group, epi in calls:
+        assert all((q[3] is not None) == bool(epi & COLSUM) for q in group)
+        assert all(len(q) == 5 for q in group)
+    issued = [q for _, group, _ in calls for q in group]
+    assert sorted(id(q[2]) for q in issued) == sorted(id(p[2]) for p in probs)          # each problem exactly once
+    assert ops.take_pending_wgrad() == []
+
+
+def test_wgrad_queue_manual_park(monkeypatch):
+    """Manual flush (bench.py, N > 1): the backward parks its problems, in queue order with their overwrite flags, and
+    issues nothing; issue_wgrad on the parked list then launches what the automatic flush would have."""
+    from mmfusion import ops
+    ops.set_manual_wgrad_flush(True)
+    try:
+        names, probs, calls = _run_queue(monkeypatch)
+        assert calls == []
+        pend = ops.take_pending_wgrad()
+    finally:
+        ops.set_manual_wgrad_flush(False)
+    assert [(names[id(q[2])], q[5]) for q in pend] == [("W1", True), ("W2", True), ("W4", True), ("W3", True),
+                                                       ("loose", False), ("W1", False), ("W3", False)]
+    assert all(q[0] is p[0] and q[1] is p[1] and q[3] is p[3] and q[4] is None for q, p in zip(pend, probs))
+    assert ops.take_pending_wgrad() == []                # handed over
+    ops.issue_wgrad(pend)
+    assert [[names[id(q[2])] for q in group] for _, group, _ in calls] == [["W1"], ["W3", "W4", "W2"], ["loose"], ["W1"], ["W3"]]
+
+
+def test_wgrad_rounds_exclude_manual_flush():
+    """The round hook (dp.BackwardExchange) and the manual flush exclude each other: installing rounds under a manual flush raises."""
+    import pytest
+    from mmfusion import ops
+    ops.set_manual_wgrad_flush(True)
+    try:
+        with pytest.raises(RuntimeError):
+            ops.set_wgrad_rounds(2, lambda problems, final: None)
+    finally:
+        ops.set_manual_wgrad_flush(False)
