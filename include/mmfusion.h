@@ -198,6 +198,25 @@ int mmf_modality_dropout(const float* const* x, float* const* y, float* keep, in
                          const uint64_t* rng_state, uint32_t site, int draw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Knowledge distillation loss (csrc/loss.hip).
+ * mmf_distill_kl: replaces models/multimodal_model.py:250-256 —
+ *   loss = T^2 * (1 / B) sum_b KL(softmax(teacher[b] / T) || softmax(student[b] / T))   (F.kl_div(..., "batchmean") * T^2)
+ * over (B, C <= 64) f32 logits with row strides lds, ldt >= C (the teacher's logits may be a view), B unbounded, and writes
+ * dstudent[b][c] = (T / B) (softmax(student[b] / T)_c - softmax(teacher[b] / T)_c) (f32 dense [B][C], may be NULL: value only).
+ * The teacher gets no gradient.  A teacher probability that underflows to 0 contributes 0 (torch's xlogy).
+ * mmf_fusion_loss_kd: mmf_fusion_loss + kd_weight * mmf_distill_kl(logits, teacher) in ONE launch — the distillation training
+ * step's loss (training/advanced_trainer.py:139-166 with its 0.5 x distillation term): value and d/dlogits.
+ * Both refuse (MMF_E_SHAPE, nothing launched) a null student / teacher / loss, C outside 1..64, a row stride below C, a
+ * temperature that is not finite and > 0; mmf_fusion_loss_kd also everything mmf_fusion_loss refuses and a non-finite kd_weight.
+ * ------------------------------------------------------------------------------------------ */
+int mmf_distill_kl(const float* student, int lds, const float* teacher, int ldt, int B, int C, float temperature,
+                   float* loss, float* dstudent, void* stream);
+int mmf_fusion_loss_kd(const float* logits, int ldl, const int64_t* targets, int B, int C, float label_smoothing,
+                       const float* const* extra, const float* extra_w, int n_extra,
+                       const float* teacher, int ldt, float temperature, float kd_weight,
+                       float* loss, float* dlogits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Grouped fused attention (flash-style: no (Tq,Tk) score matrix in HBM).
  * Replaces q*scale, QK^T, softmax, P.V of F.multi_head_attention_forward as called at
  * models/fusion_layers.py:161-163,204 (six cross blocks + three self blocks of MulT in ONE

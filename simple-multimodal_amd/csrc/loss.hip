@@ -11,6 +11,11 @@
 //                             three (B, d) tensors scaled in the same launch (torch: rand, compare, randint, one_hot, where, any
 //                             and three strided copies in front of three row-mask launches).  The same kernel applies a given mask
 //                             (backward).
+//   kd_loss_kernel<false>     reference models/multimodal_model.py:250-256 (mmf_distill_kl): T^2 * KL(softmax(t / T) || softmax(s / T)),
+//                             batchmean, value and d/d(student) in one launch (torch: the two scaled log_softmax / softmax, kl_div,
+//                             the T^2 scale and their backward: 20 launches, counted by tools/distill_bench.py).
+//   kd_loss_kernel<true>      (mmf_fusion_loss_kd) fusion_loss_kernel's CE + sum_j w_j extra_j plus kd_weight * KD as ONE launch, the
+//                             gradient with respect to the student logits summed in registers (the distillation step's loss tail).
 #include "mmf_internal.h"
 
 namespace {
@@ -61,6 +66,110 @@ void fusion_loss_kernel(const LossArgs a) {
     t *= invB;
     for (int j = 0; j < a.n_extra; ++j) t += a.extra_w[j] * a.extra[j][0];
     a.loss[0] = t;
+  }
+}
+
+// ---- knowledge distillation (reference models/multimodal_model.py:222-262) ------------------------------------------------------
+// Arithmetic: the KD terms use the ACCURATE expf / logf (OCML, <= 1 ulp each), not __expf / __logf — whose error grows with the
+// argument (|x| * 2^-22 relative for the exp of a scaled logit) and which T^2 would then amplify; C <= 64 exps per row cost
+// nothing here.  Everything is evaluated from max-subtracted, temperature-scaled logits, z_c = (x_c - max x) / T (one rounded
+// difference, one correctly-rounded division, z <= 0), and with Z = sum_c exp(z_c):
+//   KL_b = sum_c p_c (zt_c - zs_c) - log(Zt / Zs),   p = softmax(t / T) = exp(zt) / Zt,   q = softmax(s / T) = exp(zs) / Zs
+// (sum_c p_c log p_c - sum_c p_c log q_c with the two log-sum-exps folded into one log of a ratio in [1/64, 64]).  A teacher
+// probability that underflows to 0 multiplies a finite difference and adds exactly 0 (torch's xlogy); teacher == student gives
+// exactly 0.  Error model (worst case; tests/distill_ref.py evaluates exactly this one per test case), u = 2^-24, C <= 64,
+// R = the widest (max - min) of a row of s or t, r = R / T: the scaled differences z carry 2u|z|, exp / log 1 ulp, the C-term
+// sums C u of their magnitude, the probabilities (C + 4) u relative (the sum Z) plus u |z| absolute (the exponent's argument):
+//   |d KL_b| <= u ((4 + 2C) r + 2 r min(r, C) + 2C + 8)
+//   |d loss| <= T^2 max_b |d KL_b| + (B / 256 + 10) u |loss|                    (the f32 batch sum: B / 256 terms per thread)
+//   |d dstudent[b][c]| <= kd_weight (T / B) (2C + 10) u
+// The CE part of kd_loss_kernel<true> is fusion_loss_kernel's arithmetic to the operation (__expf / __logf), so the combined
+// kernel equals mmf_fusion_loss + kd_weight * mmf_distill_kl up to the order of the f32 additions.
+struct KdArgs {
+  const float* student;           // (B, lds) — the CE logits too
+  const float* teacher;           // (B, ldt)
+  const long long* targets;       // null: KD only
+  float* loss;
+  float* dstudent;                // dense (B, C), nullable
+  const float* extra[LOSS_MAX_EXTRA];
+  float extra_w[LOSS_MAX_EXTRA];
+  int B, C, lds, ldt, n_extra;
+  float smoothing, T, kd_weight;
+};
+
+// one row's max-subtracted, temperature-scaled statistics; KL(p || q) of the row
+struct KdRow { float ms, mt, rZs, rZt, kl; };
+
+__device__ __forceinline__ KdRow kd_row(const float* s, const float* t, int C, float T) {
+  KdRow r;
+  r.ms = -INFINITY; r.mt = -INFINITY;
+  for (int c = 0; c < C; ++c) { r.ms = fmaxf(r.ms, s[c]); r.mt = fmaxf(r.mt, t[c]); }
+  float Zs = 0.f, Zt = 0.f;
+  for (int c = 0; c < C; ++c) { Zs += expf((s[c] - r.ms) / T); Zt += expf((t[c] - r.mt) / T); }
+  r.rZs = 1.f / Zs; r.rZt = 1.f / Zt;
+  float kl = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float zs = (s[c] - r.ms) / T, zt = (t[c] - r.mt) / T;
+    kl += (expf(zt) * r.rZt) * (zt - zs);
+  }
+  r.kl = kl - logf(Zt / Zs);
+  return r;
+}
+
+// q_c - p_c of a row from its statistics (recomputed rather than held: a 64-float array indexed by c would live in scratch)
+__device__ __forceinline__ float kd_grad(const KdRow& r, float s, float t, float T) {
+  return expf((s - r.ms) / T) * r.rZs - expf((t - r.mt) / T) * r.rZt;
+}
+
+template <bool CE>
+__global__ __launch_bounds__(LOSS_THREADS)
+void kd_loss_kernel(const KdArgs a) {
+  __shared__ float part[2][LOSS_THREADS / 64];
+  const int tid = threadIdx.x;
+  const float eps = a.smoothing, invB = 1.f / (float)a.B, invC = 1.f / (float)a.C;
+  const float gk = a.kd_weight * a.T * invB;                 // d(kd_weight * T^2 * mean_b KL_b) / ds = kd_weight (T / B) (q - p)
+  float acc_ce = 0.f, acc_kl = 0.f;
+  for (int b = tid; b < a.B; b += LOSS_THREADS) {            // one sample per thread: C <= 64 logits
+    const float* l = a.student + (size_t)b * a.lds;
+    const float* t = a.teacher + (size_t)b * a.ldt;
+    const KdRow r = kd_row(l, t, a.C, a.T);
+    acc_kl += r.kl;
+    float lse = 0.f;
+    int y = 0;
+    if (CE) {                                                // fusion_loss_kernel's row, operation for operation
+      float mx = -INFINITY;
+      for (int c = 0; c < a.C; ++c) mx = fmaxf(mx, l[c]);
+      float se = 0.f, sl = 0.f;
+      for (int c = 0; c < a.C; ++c) { se += __expf(l[c] - mx); sl += l[c]; }
+      lse = mx + __logf(se);
+      y = (int)a.targets[b];
+      const float nll = lse - l[y];
+      const float smooth = lse - sl * invC;
+      acc_ce += (1.f - eps) * nll + eps * smooth;
+    }
+    if (a.dstudent) {
+      float* d = a.dstudent + (size_t)b * a.C;
+      for (int c = 0; c < a.C; ++c) {
+        float v = gk * kd_grad(r, l[c], t[c], a.T);
+        if (CE) v += (__expf(l[c] - lse) - ((c == y ? 1.f - eps : 0.f) + eps * invC)) * invB;
+        d[c] = v;
+      }
+    }
+  }
+  acc_ce = wave_sum(acc_ce);
+  acc_kl = wave_sum(acc_kl);
+  if ((tid & 63) == 0) { part[0][tid >> 6] = acc_ce; part[1][tid >> 6] = acc_kl; }
+  __syncthreads();
+  if (tid == 0) {
+    float ce = 0.f, kl = 0.f;
+    for (int w = 0; w < LOSS_THREADS / 64; ++w) { ce += part[0][w]; kl += part[1][w]; }
+    float out = a.kd_weight * (a.T * a.T) * (kl * invB);
+    if (CE) {
+      float t = ce * invB;
+      for (int j = 0; j < a.n_extra; ++j) t += a.extra_w[j] * a.extra[j][0];
+      out += t;
+    }
+    a.loss[0] = out;
   }
 }
 
@@ -138,5 +247,45 @@ extern "C" int mmf_modality_dropout(const float* const* x, float* const* y, floa
   a.thresh = draw ? mmf_drop_thresh(p) : 0u; a.site = site; a.B = B; a.d = d; a.draw = draw;
   hipLaunchKernelGGL(modality_dropout_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   MMF_CHECK_LAUNCH("mmf_modality_dropout");
+  return MMF_OK;
+}
+
+static bool kd_temperature_ok(float T) { return __builtin_isfinite(T) && T > 0.f; }
+
+extern "C" int mmf_distill_kl(const float* student, int lds, const float* teacher, int ldt, int B, int C, float temperature,
+                              float* loss, float* dstudent, void* stream) {
+  if (!student || !teacher || !loss || B <= 0 || C <= 0 || C > 64 || lds < C || ldt < C)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_distill_kl: B=%d C=%d (1..64) lds=%d ldt=%d, student / teacher / loss non-null", B, C, lds, ldt);
+  if (!kd_temperature_ok(temperature)) MMF_FAIL(MMF_E_SHAPE, "mmf_distill_kl: temperature must be finite and > 0");
+  KdArgs a = {};
+  a.student = student; a.teacher = teacher; a.loss = loss; a.dstudent = dstudent;
+  a.B = B; a.C = C; a.lds = lds; a.ldt = ldt; a.T = temperature; a.kd_weight = 1.f;
+  hipLaunchKernelGGL(kd_loss_kernel<false>, dim3(1), dim3(LOSS_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  MMF_CHECK_LAUNCH("mmf_distill_kl");
+  return MMF_OK;
+}
+
+extern "C" int mmf_fusion_loss_kd(const float* logits, int ldl, const int64_t* targets, int B, int C, float label_smoothing,
+                                  const float* const* extra, const float* extra_w, int n_extra,
+                                  const float* teacher, int ldt, float temperature, float kd_weight,
+                                  float* loss, float* dlogits, void* stream) {
+  if (!logits || !targets || !loss || B <= 0 || C <= 0 || C > 64 || ldl < C)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: B=%d C=%d (1..64) ldl=%d", B, C, ldl);
+  if (n_extra < 0 || n_extra > LOSS_MAX_EXTRA || (n_extra && (!extra || !extra_w)))
+    MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: n_extra=%d out of range [0,%d]", n_extra, LOSS_MAX_EXTRA);
+  if (!(label_smoothing >= 0.f) || label_smoothing >= 1.f) MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: label_smoothing must be in [0, 1)");
+  if (!teacher || ldt < C) MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: teacher null or ldt=%d < C=%d", ldt, C);
+  if (!kd_temperature_ok(temperature)) MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: temperature must be finite and > 0");
+  if (!__builtin_isfinite(kd_weight)) MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: kd_weight must be finite");
+  KdArgs a = {};
+  a.student = logits; a.teacher = teacher; a.targets = reinterpret_cast<const long long*>(targets); a.loss = loss; a.dstudent = dlogits;
+  a.B = B; a.C = C; a.lds = ldl; a.ldt = ldt; a.n_extra = n_extra; a.smoothing = label_smoothing;
+  a.T = temperature; a.kd_weight = kd_weight;
+  for (int j = 0; j < n_extra; ++j) {
+    if (!extra[j]) MMF_FAIL(MMF_E_SHAPE, "mmf_fusion_loss_kd: extra[%d] is null", j);
+    a.extra[j] = extra[j]; a.extra_w[j] = extra_w[j];
+  }
+  hipLaunchKernelGGL(kd_loss_kernel<true>, dim3(1), dim3(LOSS_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  MMF_CHECK_LAUNCH("mmf_fusion_loss_kd");
   return MMF_OK;
 }

@@ -311,8 +311,16 @@ int lstm_spin_limit() {
   return v;
 }
 
+// The barrier counters start at zero.  Zeroed by a kernel, not hipMemsetAsync: replayed from a captured graph, a memset node
+// was not reliably ordered against the persistent kernel behind it (counters reset under running workgroups -> timed-out
+// barriers -> NaN gradients; or left over from the previous launch -> barriers passed early), a kernel node is.
+__global__ void lstm_counters_zero_kernel(int* c) {
+  if (threadIdx.x < 16) c[threadIdx.x] = 0;
+}
+
 template <typename K>
 void launch_lstm(K kernel, const LstmArgs& a, int H, hipStream_t s) {
+  hipLaunchKernelGGL(lstm_counters_zero_kernel, dim3(1), dim3(64), 0, s, a.counters);
   hipLaunchKernelGGL(kernel, dim3(8 * (H / 16)), dim3(LSTM_THREADS), 0, s, a);
 }
 
@@ -323,7 +331,6 @@ extern "C" size_t mmf_bilstm_workspace_bytes(void) { return 64; }
 extern "C" int mmf_bilstm_layer_fwd(const mmf_bilstm_args* args, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_lstm("mmf_bilstm_layer_fwd", args, workspace, workspace_bytes, false)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(workspace, 0, 64, s) != hipSuccess) MMF_FAIL(MMF_E_LAUNCH, "mmf_bilstm_layer_fwd: workspace memset failed");
   LstmArgs a; a.p = *args; a.counters = static_cast<int*>(workspace); a.spin_limit = lstm_spin_limit();
   switch (args->H) {
     case 384: launch_lstm(bilstm_fwd_kernel<384>, a, 384, s); break;
@@ -337,7 +344,6 @@ extern "C" int mmf_bilstm_layer_fwd(const mmf_bilstm_args* args, void* workspace
 extern "C" int mmf_bilstm_layer_bwd(const mmf_bilstm_args* args, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_lstm("mmf_bilstm_layer_bwd", args, workspace, workspace_bytes, true)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(workspace, 0, 64, s) != hipSuccess) MMF_FAIL(MMF_E_LAUNCH, "mmf_bilstm_layer_bwd: workspace memset failed");
   LstmArgs a; a.p = *args; a.counters = static_cast<int*>(workspace); a.spin_limit = lstm_spin_limit();
   switch (args->H) {
     case 384: launch_lstm(bilstm_bwd_kernel<384>, a, 384, s); break;

@@ -211,6 +211,27 @@ def next_site() -> int:
     return _site
 
 
+class dropout_state:
+    """Within: dropout masks come from ``state`` (a device int64 [1]) with a site numbering of their own, and the outer
+    state tensor and site counter are untouched — ``begin_training_forward`` advances ``state``, not the outer one.  For a
+    second root module run between another root's forward and its backward (the distillation teacher): the outer root's
+    backward regenerates its masks from the live outer state, which must not have moved.  The swap is host-side and names
+    another device tensor, so it holds under graph capture too."""
+
+    def __init__(self, state: torch.Tensor):
+        self.state = state
+
+    def __enter__(self):
+        global _rng_state, _site
+        self.saved = (rng_state(), _site)
+        _rng_state, _site = self.state, 0
+        return self.state
+
+    def __exit__(self, *exc):
+        global _rng_state, _site
+        _rng_state, _site = self.saved
+
+
 class _Dropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, site):

@@ -446,3 +446,52 @@ class FusionTrainStep:
         self.opt.advance()
         self.opt.launch()
         return loss
+
+
+class DistillTrainStep(FusionTrainStep):
+    """The training step of a ``KnowledgeDistillationModel`` (reference ``--mode distillation``: train_advanced.py:230-273
+    through advanced_trainer.py:118-188), as one callable ``step(text, audio, video, targets) -> loss``:
+
+      1. zero the student's gradient arena;
+      2. student forward (``compute_contrastive_loss=contrastive``);
+      3. teacher forward under ``no_grad`` with the same arguments, its dropout on a state of its own
+         (``KnowledgeDistillationModel.teacher_forward``) — the reference order, teacher between the student's forward and
+         its backward;
+      4. ONE ``mmf_fusion_loss_kd`` launch: CE(ls=0.1) + 0.1 * sum of the contrastive losses + 0.5 * T^2 KL, value and
+         d/d(student logits);
+      5. ``backward_from``; 6. the gradient exchange of ``FusionTrainStep`` at world size > 1;
+      7. ``FusedAdamW`` over the STUDENT's arena only: the teacher's weights are in an arena of their own that no optimiser
+         touches (no weight decay on frozen weights).
+
+    Everything after the constructor is graph-capturable (capture single-stream, ``bench.single_stream``)."""
+
+    def __init__(self, kd_model: torch.nn.Module, *, lr: float = 1e-4, weight_decay: float = 1e-5, max_grad_norm: float = 1.0,
+                 total_steps: int = 1000, contrastive: bool = True, allreduce: Optional[str] = "bf16",
+                 shard_optimizer: bool = False, exchange: str = "after", exchange_rounds: int = 4,
+                 label_smoothing: float = 0.1, kd_weight: float = 0.5):
+        from . import arena as arena_mod
+        student, teacher = kd_model.student, kd_model.teacher
+        # The teacher gets an arena of its own because every fusion module runs from one (its bf16 shadow is what the MFMA
+        # kernels read).  That arena also has an fp32 gradient buffer the size of the teacher: nothing writes it (the
+        # teacher runs under no_grad), it stays zero, and it is the price of not giving ParamArena a gradient-free form.
+        s_arena, t_arena = arena_mod.ensure(student), arena_mod.ensure(teacher)
+        if s_arena is t_arena or any(getattr(p, "_mmf_arena", None) is s_arena for p in teacher.parameters()):
+            raise ValueError("DistillTrainStep: teacher weights in the student's arena (was the wrapper made an arena root?)")
+        kd_model.teacher_rng_state()                     # the teacher's dropout state exists before any capture
+        super().__init__(student, None, s_arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         total_steps=total_steps, contrastive=contrastive, allreduce=allreduce,
+                         shard_optimizer=shard_optimizer, exchange=exchange, exchange_rounds=exchange_rounds)
+        self.kd, self.label_smoothing, self.kd_weight = kd_model, float(label_smoothing), float(kd_weight)
+
+    def fwd_bwd(self, text, audio, video, targets) -> torch.Tensor:
+        from . import small_ops
+        self.arena.zero_grad(overlap=True, lazy=True)
+        kw = {"compute_contrastive_loss": True} if self.contrastive else {}
+        out = self.model(text, audio, video, **kw)
+        teacher_logits = self.kd.teacher_forward(text, audio, video, **kw)["emotion_logits"]
+        cl = out.get("contrastive_losses") or {}
+        loss = small_ops.fusion_loss_kd(out["emotion_logits"], targets, self.label_smoothing, list(cl.values()),
+                                        [0.1] * len(cl), teacher_logits, self.kd.temperature, self.kd_weight)
+        backward_from(loss)
+        self.arena.finalize_grads()
+        return loss

@@ -8,9 +8,11 @@ keys (reference :159-181), ``fusion_type`` dispatch incl. the ``ValueError`` (:2
 classifier's d -> d/2 layer on the skinny MFMA kernel, the 7-class / 1-unit output layers (classifier, valence,
 arousal, uncertainty) on the narrow-linear kernel (f32 masters); the softmaxes over 7 logits are torch glue.
 
-Research wrappers (``KnowledgeDistillationModel``, ``FewShotModel``, ``RobustMultimodalModel``,
-reference :222-450) are outside the hot path: the names exist so that
-``train_advanced.py:21-25`` imports, constructing them raises ``NotImplementedError``.
+``KnowledgeDistillationModel`` (reference :222-262, ``create_model(config, "distillation")``): a frozen teacher and a
+student ``MultimodalEmotionModel``, each in its own parameter arena, the distillation loss on the fused KD kernel
+(``csrc/loss.hip``); the teacher's dropout draws from a state of its own (see the class).  The two other research
+wrappers (``FewShotModel``, ``RobustMultimodalModel``, reference :265-450) are outside the hot path (SURVEY.md section 2
+row 5): the names exist so that ``train_advanced.py:21-25`` imports, constructing them raises ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -138,7 +140,62 @@ def _out_of_scope(name: str):
     return _Stub
 
 
-KnowledgeDistillationModel = _out_of_scope("KnowledgeDistillationModel")
+class KnowledgeDistillationModel(nn.Module):
+    """Reference :222-262: ``teacher`` (frozen: ``requires_grad=False``, ``eval()``) and ``student =
+    MultimodalEmotionModel(student_config)``; ``forward`` returns the student's outputs plus ``distillation_loss`` =
+    T^2 * KL(softmax(t / T) || softmax(s / T)) (batchmean, ``small_ops.distill_kl``) and ``teacher_logits``.  ``alpha`` is
+    stored and unused, as in the reference (its trainer weights the term 0.5).
+
+    Not an arena root: teacher and student each become the root of their own arena at their first forward, so an
+    optimiser over ``student``'s arena never sees a teacher weight.  Modes follow ``nn.Module``: ``kd.train()`` reaches the
+    teacher too (the reference trainer does that, advanced_trainer.py:118), and the teacher then runs its dropout.  Its
+    forward runs between the student's forward and the student's backward, whose dropout sites regenerate their masks
+    from the LIVE device state (mmfusion.ops: dropout section), so the teacher draws from a state tensor of its own
+    (``ops.dropout_state``) and leaves the student's state and site numbering where the student's forward left them."""
+
+    def __init__(self, teacher_model: "MultimodalEmotionModel", student_config,
+                 backbones: Optional[Dict[str, nn.Module]] = None):
+        super().__init__()
+        tcfg = getattr(teacher_model, "config", None)
+        if tcfg is not None:
+            if int(tcfg.num_emotions) != int(student_config.num_emotions):
+                raise ValueError(f"KnowledgeDistillationModel: teacher has {tcfg.num_emotions} emotions, "
+                                 f"the student config {student_config.num_emotions}")
+            if bool(getattr(tcfg, "feature_inputs", False)) != bool(getattr(student_config, "feature_inputs", False)):
+                raise ValueError("KnowledgeDistillationModel: teacher and student disagree on feature_inputs "
+                                 "(both must take the same inputs)")
+        self.teacher = teacher_model
+        self.student = MultimodalEmotionModel(student_config, backbones=backbones)
+        self.temperature = student_config.distill_temperature
+        self.alpha = student_config.distill_alpha
+        for param in self.teacher.parameters():
+            param.requires_grad = False
+        self.teacher.eval()
+        self._teacher_rng: Optional[torch.Tensor] = None
+
+    def teacher_rng_state(self) -> torch.Tensor:
+        """The teacher's dropout state (device int64 [1]): the student's state at first use with the high word flipped, so
+        the two never draw the same masks.  Created outside any capture by the first call (a training step's warm-up)."""
+        st = ops.rng_state()
+        if self._teacher_rng is None or self._teacher_rng.device != st.device:
+            self._teacher_rng = st.clone() ^ (0x7EAC4E12 << 32)
+        return self._teacher_rng
+
+    def teacher_forward(self, *args, **kwargs) -> Dict[str, torch.Tensor]:
+        """The teacher's forward without gradients, its dropout isolated from the student's (see the class)."""
+        with torch.no_grad(), ops.dropout_state(self.teacher_rng_state()):
+            return self.teacher(*args, **kwargs)
+
+    def forward(self, *args, **kwargs) -> Dict[str, torch.Tensor]:
+        student_output = self.student(*args, **kwargs)
+        teacher_output = self.teacher_forward(*args, **kwargs)
+        student_logits = student_output["emotion_logits"]
+        teacher_logits = teacher_output["emotion_logits"]
+        student_output["distillation_loss"] = sops.distill_kl(student_logits, teacher_logits, self.temperature)
+        student_output["teacher_logits"] = teacher_logits
+        return student_output
+
+
 FewShotModel = _out_of_scope("FewShotModel")
 RobustMultimodalModel = _out_of_scope("RobustMultimodalModel")
 
@@ -146,7 +203,11 @@ RobustMultimodalModel = _out_of_scope("RobustMultimodalModel")
 def create_model(config, model_type: str = "standard") -> nn.Module:
     if model_type == "standard":
         return MultimodalEmotionModel(config)
-    if model_type in ("few_shot", "robust", "distillation"):
+    if model_type == "distillation":
+        # reference :465-468: teacher and student from the same config (train_advanced.py:247-250 builds a half-size student
+        # itself and calls KnowledgeDistillationModel directly); the teacher is expected to be loaded afterwards
+        return KnowledgeDistillationModel(MultimodalEmotionModel(config), config)
+    if model_type in ("few_shot", "robust"):
         raise NotImplementedError(f"model_type '{model_type}' wraps the fusion path and is out of scope here")
     raise ValueError(f"Unknown model type: {model_type}")
 
