@@ -217,6 +217,35 @@ int mmf_fusion_loss_kd(const float* logits, int ldl, const int64_t* targets, int
                        float* loss, float* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Robust head of RobustMultimodalModel (csrc/small.hip).  Replaces models/multimodal_model.py:404-440 after the
+ * predictor's hidden layer h = relu(W1 [f_t; f_a; f_v] + b1) (which stays on the row linear).  Per sample b:
+ *   a    = sigmoid(W2 h + b2)                       [B][3]   "modality_availability"
+ *   p_m  = W_m f_m + b_m,  m = t, a, v              [B][C]   "individual_predictions"
+ *   w    = a (avail = -1), or the constant mask bits of avail in 0..7 (bit 0 text, 1 audio, 2 video; no gradient to a)
+ *   wn_m = w_m / ((w_t + w_a + w_v) + 1e-8)         [B][3]   "modality_weights" (f32, the reference's order: a given mask
+ *                                                             yields exactly 1, 1/2, 1/3 or 0)
+ *   y    = wn_t p_t + wn_a p_a + wn_v p_v           [B][C]   "robust_prediction"
+ * f_m, h: f32 dense [B][d]; W2 [3][d], b2 [3], W_m [C][d], b_m [C]: the f32 masters.  Forward: one workgroup per sample.
+ * Backward (one launch, no atomics: eager and replayed runs are bit-identical), given g = dL/dy and the optional direct
+ * gradients dP_m [B][C], dA [B][3], dN [B][3] (NULL: none; dP itself may be NULL):
+ *   dwn_m = g . p_m + dN_m,  dp_m = wn_m g + dP_m
+ *   predicted: dz_m = (dA_m + (dwn_m - sum_k wn_k dwn_k) / (S + 1e-8)) a_m (1 - a_m);   given: dz_m = dA_m a_m (1 - a_m)
+ *   df_m = W_m^T dp_m, dh = W2^T dz (written; NULL: not needed, df itself may be NULL);
+ *   dW_m += dp_m^T f_m, db_m += sum_b dp_m, dW2 += dz^T h, db2 += sum_b dz (accumulated into the gradient arena).
+ * a, p_m, wn are the forward's outputs.  Limits: B <= 256 (the backward holds B (3C + 3) floats of per-sample scalars in
+ * LDS, <= 51 KiB), C <= 16, d a multiple of 4, features / h / W2 / W_m 16-byte aligned.  Refused, nothing launched:
+ * MMF_E_SHAPE for a null operand, output or parameter gradient, B, C or d out of range, avail outside -1..7;
+ * MMF_E_ALIGN for a misaligned operand.
+ * ------------------------------------------------------------------------------------------ */
+int mmf_robust_head_fwd(const float* const f[3], const float* h, const float* W2, const float* b2,
+                        const float* const Wm[3], const float* const bm[3], int avail, float* a, float* const p[3],
+                        float* wn, float* y, int B, int d, int C, void* stream);
+int mmf_robust_head_bwd(const float* const f[3], const float* h, const float* W2, const float* const Wm[3],
+                        const float* a, const float* const p[3], const float* wn, int avail, const float* g,
+                        const float* const dP[3], const float* dA, const float* dN, float* const df[3], float* dh,
+                        float* dW2, float* db2, float* const dWm[3], float* const dbm[3], int B, int d, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Grouped fused attention (flash-style: no (Tq,Tk) score matrix in HBM).
  * Replaces q*scale, QK^T, softmax, P.V of F.multi_head_attention_forward as called at
  * models/fusion_layers.py:161-163,204 (six cross blocks + three self blocks of MulT in ONE

@@ -652,6 +652,177 @@ int fill_gat(Gat3Args& a, const mmf_gat3_params* p) {
   return MMF_OK;
 }
 
+// ================================================================================================
+// Robust head of RobustMultimodalModel (reference models/multimodal_model.py:365-450), per sample b:
+//   a    = sigmoid(W2 h + b2)                    (3)      modality_predictor.2 + Sigmoid; h = relu(W1 [f_t; f_a; f_v] + b1)
+//                                                         comes from the row linear (mmfusion.ops)
+//   p_m  = W_m f_m + b_m, m = t, a, v            (3 x C)  the modality-only classifiers
+//   w    = a (avail < 0) or the 3-bit mask (avail in 0..7: bit 0 text, 1 audio, 2 video)
+//   wn_m = w_m / ((w_t + w_a + w_v) + 1e-8),  y = wn_t p_t + wn_a p_a + wn_v p_v
+// Forward: one workgroup per sample (float4 loads, d % 4 == 0), 3 + 3C dot products reduced in one pass.
+// Backward: every workgroup first recomputes the per-sample scalars dp [B][3][C] and dz [B][3] into LDS, then one thread
+// per input column k of [f_t | f_a | f_v | h] (4d columns) writes df_m / dh and adds its column of dW_m / dW2; block 0 adds
+// the biases.  Every gradient element has exactly one writer: no atomics, so eager and replayed runs are bit-identical.
+// ================================================================================================
+constexpr int ROBUST_MAXC = NARROW_MAXN;
+constexpr int ROBUST_MAXB = 256;                // LDS prologue: B (3 C + 3) floats <= 51 KiB at C = 16
+constexpr int ROBUST_NP = 3 + 3 * ROBUST_MAXC;
+struct RobustArgs {
+  const float* f[3]; const float* h; const float* W2; const float* b2; const float* Wm[3]; const float* bm[3];
+  float* a; float* p[3]; float* wn; float* y;                                    // forward outputs / backward saved
+  const float* g; const float* dP[3]; const float* dA; const float* dN;          // backward gradient inputs
+  float* df[3]; float* dh; float* dW2; float* db2; float* dWm[3]; float* dbm[3];  // backward outputs
+  int B, d, C, avail;
+};
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float dot4(const float4 x, const float4 w) { return x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w; }
+
+__global__ __launch_bounds__(SM_THREADS)
+void robust_fwd_kernel(const RobustArgs a) {
+  __shared__ float red[ROBUST_NP], scratch[SM_WAVES * ROBUST_NP];
+  const int b = blockIdx.x, d = a.d, C = a.C, tid = threadIdx.x;
+  float part[ROBUST_NP];
+#pragma unroll
+  for (int n = 0; n < ROBUST_NP; ++n) part[n] = 0.f;
+  for (int k = 4 * tid; k < d; k += 4 * SM_THREADS) {
+    const float4 hv = ld4(a.h + (size_t)b * d + k);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) part[i] += dot4(hv, ld4(a.W2 + (size_t)i * d + k));
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      const float4 fv = ld4(a.f[m] + (size_t)b * d + k);
+#pragma unroll
+      for (int c = 0; c < ROBUST_MAXC; ++c)
+        if (c < C) part[3 + m * ROBUST_MAXC + c] += dot4(fv, ld4(a.Wm[m] + (size_t)c * d + k));
+    }
+  }
+  block_sum<ROBUST_NP>(part, red, scratch);
+  __shared__ float wn_s[3];
+  if (tid == 0) {
+    float av[3], w[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      av[i] = 1.f / (1.f + __expf(-(red[i] + a.b2[i])));
+      w[i] = a.avail < 0 ? av[i] : (float)((a.avail >> i) & 1);
+      a.a[b * 3 + i] = av[i];
+    }
+    const float den = ((w[0] + w[1]) + w[2]) + 1e-8f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { wn_s[i] = w[i] / den; a.wn[b * 3 + i] = wn_s[i]; }
+  }
+  __syncthreads();
+  if (tid < C) {
+    float pm[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      pm[m] = red[3 + m * ROBUST_MAXC + tid] + a.bm[m][tid];
+      a.p[m][(size_t)b * C + tid] = pm[m];
+    }
+    a.y[(size_t)b * C + tid] = (wn_s[0] * pm[0] + wn_s[1] * pm[1]) + wn_s[2] * pm[2];
+  }
+}
+
+__global__ __launch_bounds__(SM_THREADS)
+void robust_bwd_kernel(const RobustArgs a) {
+  extern __shared__ float rb_lds[];              // dp [B][3][C], then dz [B][3]
+  const int B = a.B, d = a.d, C = a.C, tid = threadIdx.x;
+  float* dp_s = rb_lds;
+  float* dz_s = rb_lds + (size_t)B * 3 * C;
+  for (int b = tid; b < B; b += SM_THREADS) {
+    float wn[3], dwn[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      wn[m] = a.wn[b * 3 + m];
+      dwn[m] = a.dN ? a.dN[b * 3 + m] : 0.f;
+    }
+    for (int c = 0; c < C; ++c) {
+      const float g = a.g[(size_t)b * C + c];
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        dwn[m] += g * a.p[m][(size_t)b * C + c];
+        dp_s[((size_t)b * 3 + m) * C + c] = wn[m] * g + (a.dP[m] ? a.dP[m][(size_t)b * C + c] : 0.f);
+      }
+    }
+    float av[3], dw[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { av[m] = a.a[b * 3 + m]; dw[m] = a.dA ? a.dA[b * 3 + m] : 0.f; }
+    if (a.avail < 0) {                           // weights = a: d/dw of w / (sum w + eps)
+      const float den = ((av[0] + av[1]) + av[2]) + 1e-8f;
+      const float dot = (wn[0] * dwn[0] + wn[1] * dwn[1]) + wn[2] * dwn[2];
+#pragma unroll
+      for (int m = 0; m < 3; ++m) dw[m] += (dwn[m] - dot) / den;
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) dz_s[b * 3 + m] = dw[m] * av[m] * (1.f - av[m]);
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && tid < 3 * C + 3) {
+    float s = 0.f;
+    if (tid < 3 * C) {
+      const int m = tid / C, c = tid % C;
+      for (int b = 0; b < B; ++b) s += dp_s[((size_t)b * 3 + m) * C + c];
+      a.dbm[m][c] += s;
+    } else {
+      const int i = tid - 3 * C;
+      for (int b = 0; b < B; ++b) s += dz_s[b * 3 + i];
+      a.db2[i] += s;
+    }
+  }
+  const int j = blockIdx.x * SM_THREADS + tid;
+  if (j >= 4 * d) return;
+  const int m = j / d, k = j - m * d;
+  if (m < 3) {                                   // column k of f_m: df_m[:, k], dW_m[:, k]
+    const float* W = a.Wm[m];
+    const float* x = a.f[m];
+    float* dx = a.df[m];
+    float w[ROBUST_MAXC], dw[ROBUST_MAXC];
+#pragma unroll
+    for (int c = 0; c < ROBUST_MAXC; ++c) { w[c] = c < C ? W[(size_t)c * d + k] : 0.f; dw[c] = 0.f; }
+    for (int b = 0; b < B; ++b) {
+      const float xv = x[(size_t)b * d + k];
+      const float* dpb = dp_s + ((size_t)b * 3 + m) * C;
+      float gx = 0.f;
+#pragma unroll
+      for (int c = 0; c < ROBUST_MAXC; ++c)
+        if (c < C) { const float g = dpb[c]; gx += g * w[c]; dw[c] += g * xv; }
+      if (dx) dx[(size_t)b * d + k] = gx;
+    }
+#pragma unroll
+    for (int c = 0; c < ROBUST_MAXC; ++c)
+      if (c < C) a.dWm[m][(size_t)c * d + k] += dw[c];
+  } else {                                       // column k of h: dh[:, k], dW2[:, k]
+    float w[3], dw[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w[i] = a.W2[(size_t)i * d + k];
+    for (int b = 0; b < B; ++b) {
+      const float xv = a.h[(size_t)b * d + k];
+      float gx = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { const float g = dz_s[b * 3 + i]; gx += g * w[i]; dw[i] += g * xv; }
+      if (a.dh) a.dh[(size_t)b * d + k] = gx;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a.dW2[(size_t)i * d + k] += dw[i];
+  }
+}
+
+int fill_robust(RobustArgs& a, const char* who, const float* const f[3], const float* h, const float* W2,
+                const float* const Wm[3], int avail, int B, int d, int C) {
+  if (!f || !Wm || !h || !W2) MMF_FAIL(MMF_E_SHAPE, "%s: null operand", who);
+  for (int m = 0; m < 3; ++m)
+    if (!f[m] || !Wm[m]) MMF_FAIL(MMF_E_SHAPE, "%s: null feature / classifier weight %d", who, m);
+  if (B <= 0 || B > ROBUST_MAXB || d <= 0 || d % 4 || C <= 0 || C > ROBUST_MAXC)
+    MMF_FAIL(MMF_E_SHAPE, "%s: B=%d (1..%d) d=%d (multiple of 4) C=%d (1..%d)", who, B, ROBUST_MAXB, d, C, ROBUST_MAXC);
+  if (avail < -1 || avail > 7) MMF_FAIL(MMF_E_SHAPE, "%s: avail=%d (-1: predicted, 0..7: mask)", who, avail);
+  if (!mmf_aligned16(h) || !mmf_aligned16(W2)) MMF_FAIL(MMF_E_ALIGN, "%s: h / W2 not 16-byte aligned", who);
+  for (int m = 0; m < 3; ++m)
+    if (!mmf_aligned16(f[m]) || !mmf_aligned16(Wm[m])) MMF_FAIL(MMF_E_ALIGN, "%s: feature / weight %d not 16-byte aligned", who, m);
+  for (int m = 0; m < 3; ++m) { a.f[m] = f[m]; a.Wm[m] = Wm[m]; }
+  a.h = h; a.W2 = W2; a.B = B; a.d = d; a.C = C; a.avail = avail;
+  return MMF_OK;
+}
+
 }  // namespace
 
 extern "C" int mmf_gat3_dense_fwd(const float* h, const float* att_src, const float* att_dst, const float* bias,
@@ -821,5 +992,46 @@ extern "C" int mmf_adaptive_attn_weights(const void* qkv_bf16, float* w, int B, 
   hipLaunchKernelGGL(ada_attn_weights_kernel, dim3(B), dim3(SM_THREADS), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(qkv_bf16), w, heads, head_dim, 1.f / sqrtf((float)head_dim));
   MMF_CHECK_LAUNCH("mmf_adaptive_attn_weights");
+  return MMF_OK;
+}
+
+extern "C" int mmf_robust_head_fwd(const float* const f[3], const float* h, const float* W2, const float* b2,
+                                   const float* const Wm[3], const float* const bm[3], int avail, float* a_out,
+                                   float* const p[3], float* wn, float* y, int B, int d, int C, void* stream) {
+  RobustArgs a = {};
+  const int rc = fill_robust(a, "mmf_robust_head_fwd", f, h, W2, Wm, avail, B, d, C);
+  if (rc != MMF_OK) return rc;
+  if (!b2 || !bm || !p || !a_out || !wn || !y) MMF_FAIL(MMF_E_SHAPE, "mmf_robust_head_fwd: null bias / output");
+  for (int m = 0; m < 3; ++m) {
+    if (!bm[m] || !p[m]) MMF_FAIL(MMF_E_SHAPE, "mmf_robust_head_fwd: null bias / prediction %d", m);
+    a.bm[m] = bm[m]; a.p[m] = p[m];
+  }
+  a.b2 = b2; a.a = a_out; a.wn = wn; a.y = y;
+  hipLaunchKernelGGL(robust_fwd_kernel, dim3(B), dim3(SM_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  MMF_CHECK_LAUNCH("mmf_robust_head_fwd");
+  return MMF_OK;
+}
+
+extern "C" int mmf_robust_head_bwd(const float* const f[3], const float* h, const float* W2, const float* const Wm[3],
+                                   const float* a_sv, const float* const p[3], const float* wn, int avail, const float* g,
+                                   const float* const dP[3], const float* dA, const float* dN, float* const df[3], float* dh,
+                                   float* dW2, float* db2, float* const dWm[3], float* const dbm[3], int B, int d, int C,
+                                   void* stream) {
+  RobustArgs a = {};
+  const int rc = fill_robust(a, "mmf_robust_head_bwd", f, h, W2, Wm, avail, B, d, C);
+  if (rc != MMF_OK) return rc;
+  if (!a_sv || !p || !wn || !g || !dW2 || !db2 || !dWm || !dbm)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_robust_head_bwd: null saved tensor, output gradient or parameter gradient");
+  for (int m = 0; m < 3; ++m) {
+    if (!p[m] || !dWm[m] || !dbm[m]) MMF_FAIL(MMF_E_SHAPE, "mmf_robust_head_bwd: null prediction / parameter gradient %d", m);
+    a.p[m] = const_cast<float*>(p[m]); a.dWm[m] = dWm[m]; a.dbm[m] = dbm[m];
+    a.dP[m] = dP ? dP[m] : nullptr; a.df[m] = df ? df[m] : nullptr;
+  }
+  a.a = const_cast<float*>(a_sv); a.wn = const_cast<float*>(wn); a.g = g; a.dA = dA; a.dN = dN;
+  a.dh = dh; a.dW2 = dW2; a.db2 = db2;
+  const size_t lds = (size_t)B * (3 * C + 3) * sizeof(float);
+  hipLaunchKernelGGL(robust_bwd_kernel, dim3((4 * d + SM_THREADS - 1) / SM_THREADS), dim3(SM_THREADS), lds,
+                     static_cast<hipStream_t>(stream), a);
+  MMF_CHECK_LAUNCH("mmf_robust_head_bwd");
   return MMF_OK;
 }

@@ -32,7 +32,7 @@ SYMBOLS = (
     "mmf_stack3_embed_bwd", "mmf_rowmask_apply", "mmf_zero_ranges_f32", "mmf_fusion_loss", "mmf_modality_dropout",
     "mmf_attn_weights_mean", "mmf_gemm_f32_grouped", "mmf_gemm_f32_batched", "mmf_softmax_rows_f32", "mmf_softmax_bwd_rows_f32",
     "mmf_layernorm_f32_fwd", "mmf_layernorm_f32_bwd", "mmf_bilstm_workspace_bytes", "mmf_bilstm_layer_fwd", "mmf_bilstm_layer_bwd", "mmf_swap01",
-    "mmf_distill_kl", "mmf_fusion_loss_kd",
+    "mmf_distill_kl", "mmf_fusion_loss_kd", "mmf_robust_head_fwd", "mmf_robust_head_bwd",
 )
 
 
@@ -161,6 +161,10 @@ def load() -> C.CDLL:
     lib.mmf_modality_dropout.argtypes = [C.POINTER(vp), C.POINTER(vp), vp, i32, i32, f32, vp, C.c_uint32, i32, vp]
     lib.mmf_distill_kl.argtypes = [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp]
     lib.mmf_fusion_loss_kd.argtypes = [vp, i32, vp, i32, i32, f32, C.POINTER(vp), C.POINTER(f32), i32, vp, i32, f32, f32, vp, vp, vp]
+    pp = C.POINTER(vp)
+    lib.mmf_robust_head_fwd.argtypes = [pp, vp, vp, vp, pp, pp, i32, vp, pp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_robust_head_bwd.argtypes = [pp, vp, vp, pp, vp, pp, vp, i32, vp, pp, vp, vp, pp, vp, vp, vp, pp, pp,
+                                        i32, i32, i32, vp]
     lib.mmf_skinny_linear_fwd_ex.argtypes = [C.POINTER(SkinnyProblemEx), i32, i32, i32, C.POINTER(SkinnyExtra), vp]
     lib.mmf_skinny_linear_dgrad_ex.argtypes = [C.POINTER(SkinnyProblemEx), i32, i32, f32, i32, C.POINTER(SkinnyExtra), vp]
     lib.mmf_sqnorm_f32.argtypes = [vp, i64, vp, vp]

@@ -520,3 +520,94 @@ def fusion_loss_kd(logits: torch.Tensor, targets: torch.Tensor, smoothing: float
         targets = targets.long()
     return _FusionLossKD.apply(logits, targets.contiguous(), float(smoothing), list(weights), teacher_logits,
                                float(temperature), float(kd_weight), *extras)
+
+
+# --------------------------------------------------------------------------------------------
+# robust head of RobustMultimodalModel (csrc/small.hip mmf_robust_head_*)
+# --------------------------------------------------------------------------------------------
+ROBUST_MAX_B = 256
+_MODALITIES = ("text", "audio", "video")
+
+
+def availability_mask(available) -> int:
+    """``available_modalities`` -> the kernels' argument: None -> -1 (predicted weights), a list of names -> the 3-bit mask
+    (bit 0 text, 1 audio, 2 video; unknown names are ignored, [] gives 0), an int passes through."""
+    if available is None:
+        return -1
+    if isinstance(available, int):
+        return available
+    return sum(1 << i for i, m in enumerate(_MODALITIES) if m in available)
+
+
+class _RobustHead(torch.autograd.Function):
+    """(f_t, f_a, f_v, h) -> (a, p_t, p_a, p_v, wn, y) in one launch, all six gradients back in one (see include/mmfusion.h).
+    Outputs the loss ignores arrive as None (``set_materialize_grads(False)``) and cost nothing."""
+
+    @staticmethod
+    def forward(ctx, ft, fa, fv, h, avail, w2, b2, wt, bt, wa, ba, wv, bv):
+        fs = [x.float().contiguous() for x in (ft, fa, fv)]
+        h = h.float().contiguous()
+        for x in (*fs, h):
+            _req(x, F32)
+        B, d = fs[0].shape
+        Cn = wt.shape[0]
+        if any(tuple(x.shape) != (B, d) for x in (*fs, h)):
+            raise ValueError(f"robust_head: features {[tuple(x.shape) for x in fs]} / hidden {tuple(h.shape)} differ")
+        dev = h.device
+        a = torch.empty((B, 3), dtype=F32, device=dev)
+        ps = [torch.empty((B, Cn), dtype=F32, device=dev) for _ in range(3)]
+        wn = torch.empty((B, 3), dtype=F32, device=dev)
+        y = torch.empty((B, Cn), dtype=F32, device=dev)
+        wm, bm = (wt, wa, wv), (bt, ba, bv)
+        lib.check(lib.load().mmf_robust_head_fwd(_ptr3(fs), h.data_ptr(), w2.data_ptr(), b2.data_ptr(), _ptr3(wm), _ptr3(bm),
+                                                 int(avail), a.data_ptr(), _ptr3(ps), wn.data_ptr(), y.data_ptr(), B, d, Cn,
+                                                 lib.stream_ptr()))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*fs, h, a, *ps, wn)
+        ctx.params, ctx.avail = (w2, b2, wm, bm), int(avail)
+        if avail >= 0:
+            ctx.mark_non_differentiable(wn)              # constant weights: nothing flows back through them
+        return a, ps[0], ps[1], ps[2], wn, y
+
+    @staticmethod
+    def backward(ctx, ga, gpt, gpa, gpv, gwn, gy):
+        ft, fa, fv, h, a, pt, pa, pv, wn = ctx.saved_tensors
+        w2, b2, wm, bm = ctx.params
+        B, d = h.shape
+        Cn = pt.shape[1]
+        if ga is None and gpt is None and gpa is None and gpv is None and gwn is None and gy is None:
+            return (None,) * 13
+
+        def rows(g):
+            return None if g is None else g.float().contiguous()
+        g = rows(gy) if gy is not None else torch.zeros((B, Cn), dtype=F32, device=h.device)
+        dps = [rows(x) for x in (gpt, gpa, gpv)]
+        ga, gwn = rows(ga), (rows(gwn) if ctx.avail < 0 else None)
+        need = ctx.needs_input_grad
+        dfs = [torch.empty((B, d), dtype=F32, device=h.device) if need[i] else None for i in range(3)]
+        # with a given mask only a direct gradient of the availability reaches the predictor
+        dh = torch.empty((B, d), dtype=F32, device=h.device) if need[3] and (ctx.avail < 0 or ga is not None) else None
+        dP = (_C.c_void_p * 3)(*[_ptr(x) for x in dps])
+        dF = (_C.c_void_p * 3)(*[_ptr(x) for x in dfs])
+        lib.check(lib.load().mmf_robust_head_bwd(_ptr3((ft, fa, fv)), h.data_ptr(), w2.data_ptr(), _ptr3(wm), a.data_ptr(),
+                                                 _ptr3((pt, pa, pv)), wn.data_ptr(), ctx.avail, g.data_ptr(), dP, _ptr(ga),
+                                                 _ptr(gwn), dF, _ptr(dh), _grad_of(w2).data_ptr(), _grad_of(b2).data_ptr(),
+                                                 _ptr3([_grad_of(w) for w in wm]), _ptr3([_grad_of(b) for b in bm]),
+                                                 B, d, Cn, lib.stream_ptr()))
+        return (dfs[0], dfs[1], dfs[2], dh) + (None,) * 9
+
+
+def robust_head(f_t: torch.Tensor, f_a: torch.Tensor, f_v: torch.Tensor, h: torch.Tensor, module, available=None):
+    """The robust head of ``RobustMultimodalModel`` after its predictor's hidden layer ``h`` (f32 (B, d)): -> (availability
+    (B, 3), text / audio / video predictions (B, C) each, normalised weights (B, 3), robust prediction (B, C)), f32.
+    ``module`` holds ``modality_predictor`` and the three ``*_only_classifier`` layers (f32 masters in an arena);
+    ``available``: None (predicted weights), a list of modality names or a 3-bit mask.  B <= 256, C <= 16, d % 4 == 0."""
+    avail = availability_mask(available)
+    if not 0 <= avail + 1 <= 8:
+        raise ValueError(f"robust_head: availability mask {avail} (-1 or 0..7)")
+    lin2 = module.modality_predictor[2]
+    heads = (module.text_only_classifier, module.audio_only_classifier, module.video_only_classifier)
+    if heads[0].weight.shape[0] > NARROW_MAX_N or f_t.shape[0] > ROBUST_MAX_B:
+        raise ValueError(f"robust_head: C = {heads[0].weight.shape[0]} (<= {NARROW_MAX_N}), B = {f_t.shape[0]} (<= {ROBUST_MAX_B})")
+    return _RobustHead.apply(f_t, f_a, f_v, h, avail, lin2.weight, lin2.bias,
+                             *[t for l in heads for t in (l.weight, l.bias)])

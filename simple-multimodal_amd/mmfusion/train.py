@@ -20,13 +20,28 @@ array, so the whole step (forward, backward, optimiser) can be replayed from one
 from __future__ import annotations
 
 import math
-from typing import Dict, Iterable, Optional
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import dp, lib
-from .arena import ParamArena
+from .arena import ALIGN as ARENA_ALIGN, ParamArena
+
+
+def coalesce_ranges(spans: Iterable[Tuple[int, int]], align: int = ARENA_ALIGN) -> List[Tuple[int, int]]:
+    """(arena offset, numel) of some parameters -> sorted, disjoint (start, end) element ranges covering them.  Two
+    parameters that are arena neighbours (the second starts where the first ends, rounded up to ``align``: the arena's
+    layout) share one range; the padding between them holds zeros that an AdamW step leaves zero.  A gap that holds
+    another parameter splits the range."""
+    out: List[Tuple[int, int]] = []
+    for s0, n in sorted(spans):
+        e0 = s0 + n
+        if out and s0 <= -(-out[-1][1] // align) * align:
+            out[-1] = (out[-1][0], max(out[-1][1], e0))
+        else:
+            out.append((s0, e0))
+    return out
 
 
 def one_cycle(step: int, total_steps: int, max_lr: float, pct_start: float = 0.1, div_factor: float = 25.0,
@@ -70,13 +85,31 @@ class FusedAdamW:
     _RING = 32
 
     def __init__(self, arena: ParamArena, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-5, max_grad_norm: Optional[float] = 1.0, shard: bool = False, group=None):
+                 weight_decay: float = 1e-5, max_grad_norm: Optional[float] = 1.0, shard: bool = False, group=None,
+                 params: Optional[Iterable[torch.nn.Parameter]] = None):
         """``shard=True`` under an initialised process group of N > 1 ranks: the ZeRO-1 form of the step (``launch`` then
         runs ``launch_sharded``): reduce-scatter of the gradient arena instead of an all-reduce, clip + AdamW on this
         rank's 1/N of the arena only (the moments exist for that shard only), all-gather of the bf16 shadow the forward
         reads, plus the fp32 masters of the small parameters (the arena's tail).  The fp32 masters of the big matrices of the
-        OTHER shards go stale: ``gather_masters()`` refreshes them (checkpoints do).  Not for the fp32 parity mode."""
+        OTHER shards go stale: ``gather_masters()`` refreshes them (checkpoints do).  Not for the fp32 parity mode.
+
+        ``params``: step only these arena parameters, as torch's AdamW skips those whose ``.grad`` is None — the norm and
+        the update run over their coalesced arena ranges (``coalesce_ranges``: one launch per range), the moments stay
+        indexed by the arena offset, every other parameter and its moments are left alone.  ``None``: the whole arena in
+        one launch.  Not with ``shard``."""
         self.arena, self.lr, self.betas, self.eps = arena, lr, betas, eps
+        self.ranges: Optional[List[Tuple[int, int]]] = None
+        if params is not None:
+            if shard:
+                raise ValueError("FusedAdamW: params= (a parameter subset) and shard=True exclude each other")
+            where = {id(p): i for i, p in enumerate(arena.params)}
+            spans = []
+            for p in params:
+                if id(p) not in where:
+                    raise ValueError("FusedAdamW: params= names a parameter outside the arena")
+                i = where[id(p)]
+                spans.append((arena.offsets[i], p.numel()))
+            self.ranges = coalesce_ranges(spans)
         self.weight_decay, self.max_grad_norm = weight_decay, max_grad_norm
         dev = arena.master.device
         self.group = group
@@ -178,8 +211,9 @@ class FusedAdamW:
 
     def _adamw_range(self, s: int, n: int, use_norm: bool) -> None:
         a = self.arena
+        mo = 4 * (s - self.shard_start)
         lib.check(lib.load().mmf_adamw_step(a.master_full.data_ptr() + 4 * s, a.grads_full.data_ptr() + 4 * s,
-                                            self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                            self.exp_avg.data_ptr() + mo, self.exp_avg_sq.data_ptr() + mo,
                                             a.shadow_full.data_ptr() + 2 * s, n, self.hparams.data_ptr(),
                                             self.gnorm_sq.data_ptr() if use_norm else None, lib.stream_ptr()))
 
@@ -189,10 +223,13 @@ class FusedAdamW:
             self.launch_sharded()
             return
         a = self.arena
+        ranges = [(0, a.numel)] if self.ranges is None else self.ranges
         if self.max_grad_norm:
             self.gnorm_sq.zero_()
-            self._sqnorm_range(0, a.numel)
-        self._adamw_range(0, a.numel, bool(self.max_grad_norm))
+            for s0, e0 in ranges:
+                self._sqnorm_range(s0, e0 - s0)
+        for s0, e0 in ranges:
+            self._adamw_range(s0, e0 - s0, bool(self.max_grad_norm))
         a.mark_shadow_fresh()
 
     def launch_sharded(self, compress: Optional[str] = None) -> None:
@@ -413,8 +450,7 @@ class FusionTrainStep:
         runs inside backward in ``exchange_rounds`` reverse-autograd rounds (``dp.BackwardExchange``; replicated optimiser
         only)."""
         self.model, self.head, self.arena = model, head, arena
-        self.opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard_optimizer)
-        self.opt.set_schedule(lr, total_steps)            # OneCycleLR evaluated on the device, per step
+        self.opt = self._optimizer(arena, lr, weight_decay, max_grad_norm, total_steps, shard_optimizer)
         self.max_lr, self.total_steps, self.contrastive, self.allreduce = lr, total_steps, contrastive, allreduce
         self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
         if exchange not in ("after", "backward"):
@@ -424,6 +460,11 @@ class FusionTrainStep:
             if shard_optimizer:
                 raise ValueError("the in-backward all-reduce and the sharded optimiser (reduce-scatter) exclude each other")
             self._bx = dp.BackwardExchange(arena, exchange_rounds, None if allreduce == "fp32" else "bf16").install()
+
+    def _optimizer(self, arena, lr, weight_decay, max_grad_norm, total_steps, shard) -> FusedAdamW:
+        opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard)
+        opt.set_schedule(lr, total_steps)                 # OneCycleLR evaluated on the device, per step
+        return opt
 
     def fwd_bwd(self, text, audio, video, targets) -> torch.Tensor:
         self.arena.zero_grad(overlap=True, lazy=True)
@@ -495,3 +536,77 @@ class DistillTrainStep(FusionTrainStep):
         backward_from(loss)
         self.arena.finalize_grads()
         return loss
+
+
+class RobustTrainStep(FusionTrainStep):
+    """The training step of a ``RobustMultimodalModel`` (reference ``--mode robust``: ``RobustnessTrainer.
+    train_with_missing_modalities``, advanced_trainer.py:564-605), as one callable ``step(text, audio, video, targets,
+    missing_modalities=None) -> loss``, reproducing what that loop does:
+
+      1. zero the gradient arena;
+      2. forward of the wrapper with ``missing_modalities`` (no ``available_modalities``: the weights are the predicted
+         availability), in training mode, so ``ModalityDropout`` runs;
+      3. CE with label smoothing 0.1 on ``robust_prediction``: ONE ``small_ops.fusion_loss`` launch, no contrastive term
+         (the loop does not ask for it);
+      4. ``backward_from``; 5. the gradient exchange of ``FusionTrainStep`` at world size > 1;
+      6. ``FusedAdamW`` at a constant lr = ``lr / 25`` with betas (0.95, 0.999) — what ``OneCycleLR``'s constructor
+         leaves on the optimiser (initial_lr = max_lr / div_factor, beta1 = max_momentum); the loop never steps the
+         scheduler — without clipping (the loop never clips), over the parameters the loss reaches only
+         (``reached_parameters``): torch's AdamW skips the ones whose ``.grad`` is None, weight decay included.
+
+    ``missing_modalities`` is fixed per captured graph, like every other host-side argument: everything after the constructor
+    is graph-capturable for one scenario (capture single-stream, ``bench.single_stream``)."""
+
+    def __init__(self, model: torch.nn.Module, *, lr: float = 1e-4, weight_decay: float = 1e-5,
+                 allreduce: Optional[str] = "bf16", exchange: str = "after", exchange_rounds: int = 4,
+                 label_smoothing: float = 0.1):
+        from . import arena as arena_mod
+        arena = arena_mod.ensure(model)
+        self.reached = self.reached_parameters(model)
+        super().__init__(model, None, arena, lr=lr, weight_decay=weight_decay, max_grad_norm=None, contrastive=False,
+                         allreduce=allreduce, shard_optimizer=False, exchange=exchange, exchange_rounds=exchange_rounds)
+        self.label_smoothing = float(label_smoothing)
+
+    @staticmethod
+    def reached_parameters(model: torch.nn.Module):
+        """The parameters a loss on ``robust_prediction`` gives a gradient: the encoders without their adapters and prompt
+        embeddings (the forward runs with ``use_adapter = use_prompt = False``), the modality-only classifiers and the
+        availability predictor.  The fusion layer, the ``EmotionClassifier`` and the valence / arousal / uncertainty heads
+        run (their outputs are returned) but do not reach the loss."""
+        out = []
+        for n, p in model.named_parameters():
+            if n.startswith("base_model."):
+                parts = n.split(".")
+                if parts[1] not in ("text_encoder", "audio_encoder", "video_encoder"):
+                    continue
+                if parts[2] in ("adapter", "prompt_embeddings"):
+                    continue
+            out.append(p)
+        return out
+
+    def _optimizer(self, arena, lr, weight_decay, max_grad_norm, total_steps, shard) -> FusedAdamW:
+        # schedule mode 0 (set_schedule is not called): advance() keeps the uploaded lr and beta1, and derives the bias
+        # corrections from the device step counter
+        return FusedAdamW(arena, lr=lr / 25.0, betas=(0.95, 0.999), weight_decay=weight_decay, max_grad_norm=None,
+                          params=self.reached)
+
+    def fwd_bwd(self, text, audio, video, targets, missing_modalities=None) -> torch.Tensor:
+        from . import small_ops
+        self.arena.zero_grad(overlap=True, lazy=True)
+        out = self.model(text, audio, video, missing_modalities=missing_modalities)
+        loss = small_ops.fusion_loss(out["robust_prediction"], targets, self.label_smoothing, [], [])
+        backward_from(loss)
+        self.arena.finalize_grads()
+        return loss
+
+    def __call__(self, text, audio, video, targets, missing_modalities=None) -> torch.Tensor:
+        loss = self.fwd_bwd(text, audio, video, targets, missing_modalities)
+        if self._bx is not None:
+            self._bx.finish()
+        elif self.world > 1:
+            dp.allreduce_grads(self.arena, compress=None if self.allreduce == "fp32" else "bf16")
+        self.opt.advance()
+        self.opt.launch()
+        return loss
+
+    step = __call__

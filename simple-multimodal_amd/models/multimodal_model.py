@@ -10,9 +10,14 @@ arousal, uncertainty) on the narrow-linear kernel (f32 masters); the softmaxes o
 
 ``KnowledgeDistillationModel`` (reference :222-262, ``create_model(config, "distillation")``): a frozen teacher and a
 student ``MultimodalEmotionModel``, each in its own parameter arena, the distillation loss on the fused KD kernel
-(``csrc/loss.hip``); the teacher's dropout draws from a state of its own (see the class).  The two other research
-wrappers (``FewShotModel``, ``RobustMultimodalModel``, reference :265-450) are outside the hot path (SURVEY.md section 2
-row 5): the names exist so that ``train_advanced.py:21-25`` imports, constructing them raises ``NotImplementedError``.
+(``csrc/loss.hip``); the teacher's dropout draws from a state of its own (see the class).
+
+``RobustMultimodalModel`` (reference :365-450): the base model, three modality-only classifiers and an availability
+predictor in ONE arena; the head after the predictor's hidden layer is one HIP launch each way (``small_ops.robust_head``).
+``create_model(config, "robust")`` still raises ``NotImplementedError``: construct ``RobustMultimodalModel(config)``.
+
+``FewShotModel`` (reference :265-362) is outside the hot path: the name exists so that
+``train_advanced.py:21-25`` imports, constructing it raises ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -197,7 +202,56 @@ class KnowledgeDistillationModel(nn.Module):
 
 
 FewShotModel = _out_of_scope("FewShotModel")
-RobustMultimodalModel = _out_of_scope("RobustMultimodalModel")
+
+
+class RobustMultimodalModel(_FusionBase):
+    """Reference :365-450: ``base_model = MultimodalEmotionModel(config)``, ``{text,audio,video}_only_classifier``
+    (d -> C) and ``modality_predictor`` (Linear(3d, d), ReLU, Linear(d, 3), Sigmoid); state_dict keys and shapes are the
+    reference's.  ``forward`` returns the base model's outputs plus ``robust_prediction``, ``modality_availability``,
+    ``individual_predictions`` {text, audio, video} and ``modality_weights``, computed from the base model's returned
+    features (after ``ModalityDropout`` in training mode).  The weights are the predicted availability, or with
+    ``available_modalities`` the constant indicator of the named modalities (unknown names ignored), normalised by their
+    sum + 1e-8.
+
+    Deliberate deviation: ``missing_modalities`` is accepted and passed to ``base_model`` (which zeroes those inputs).  The
+    reference trainer calls the wrapper that way (advanced_trainer.py:583-588) and the reference class rejects it with a
+    TypeError.  It does not select the weights: those still come from
+    ``available_modalities`` or the predictor.
+
+    An arena root (``_FusionBase``): the base model and the head share one parameter arena, hence one optimiser.  The
+    predictor's hidden layer runs on the row linear (``ops.linear``, ReLU epilogue) over the concatenated features; the
+    rest of the head is ``small_ops.robust_head``."""
+
+    def __init__(self, config, backbones: Optional[Dict[str, nn.Module]] = None):
+        super().__init__()
+        self.base_model = MultimodalEmotionModel(config, backbones)
+        self.config = config
+        d, C = config.fusion_hidden_size, config.num_emotions
+        self.text_only_classifier = nn.Linear(d, C)
+        self.audio_only_classifier = nn.Linear(d, C)
+        self.video_only_classifier = nn.Linear(d, C)
+        self.modality_predictor = nn.Sequential(nn.Linear(d * 3, d), nn.ReLU(), nn.Linear(d, 3), nn.Sigmoid())
+
+    def head(self, text_features: torch.Tensor, audio_features: torch.Tensor, video_features: torch.Tensor,
+             available_modalities: Optional[List[str]] = None):
+        """-> (modality_availability, text_pred, audio_pred, video_pred, modality_weights, robust_prediction)"""
+        if not text_features.is_cuda:
+            raise RuntimeError("mmfusion: the robust head runs on the GPU only (no CPU fallback)")
+        cat = torch.cat([text_features.float(), audio_features.float(), video_features.float()], dim=-1)
+        l0 = self.modality_predictor[0]
+        h = ops.linear(cat, W(l0.weight), W(l0.bias), relu=True, out_f32=True)
+        return sops.robust_head(text_features, audio_features, video_features, h, self, available_modalities)
+
+    def forward(self, text_input: Dict[str, torch.Tensor], audio_input: torch.Tensor, video_input: torch.Tensor,
+                available_modalities: Optional[List[str]] = None,
+                missing_modalities: Optional[List[str]] = None) -> Dict[str, torch.Tensor]:
+        output = self.base_model(text_input=text_input, audio_input=audio_input, video_input=video_input,
+                                 missing_modalities=missing_modalities)
+        a, pt, pa, pv, wn, y = self.head(output["text_features"], output["audio_features"], output["video_features"],
+                                         available_modalities)
+        output.update({"robust_prediction": y, "modality_availability": a,
+                       "individual_predictions": {"text": pt, "audio": pa, "video": pv}, "modality_weights": wn})
+        return output
 
 
 def create_model(config, model_type: str = "standard") -> nn.Module:
@@ -207,7 +261,11 @@ def create_model(config, model_type: str = "standard") -> nn.Module:
         # reference :465-468: teacher and student from the same config (train_advanced.py:247-250 builds a half-size student
         # itself and calls KnowledgeDistillationModel directly); the teacher is expected to be loaded afterwards
         return KnowledgeDistillationModel(MultimodalEmotionModel(config), config)
-    if model_type in ("few_shot", "robust"):
+    if model_type == "robust":
+        # the reference factory returns RobustMultimodalModel(config) here; this factory keeps refusing as before (callers
+        # and tests rely on it), the class itself is constructed directly
+        raise NotImplementedError("model_type 'robust': construct RobustMultimodalModel(config) directly")
+    if model_type == "few_shot":
         raise NotImplementedError(f"model_type '{model_type}' wraps the fusion path and is out of scope here")
     raise ValueError(f"Unknown model type: {model_type}")
 
