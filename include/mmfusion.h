@@ -246,6 +246,31 @@ int mmf_robust_head_bwd(const float* const f[3], const float* h, const float* W2
                         float* dW2, float* db2, float* const dWm[3], float* const dbm[3], int B, int d, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Episode head of FewShotModel (csrc/fewshot.hip).  Replaces models/multimodal_model.py:286-362 around the prototype MLP
+ * (which stays on the row linear).  Support rows are class-major: row r = c * n_shot + s, S = n_way * n_shot.
+ *   proto_fwd:  sf[r] = (t[r] + a[r]) + v[r]               [S][d]      "support_features" (the reference's order)
+ *               mean[c] = (sum_s sf[c * n_shot + s]) / n_shot [n_way][d]  summed in shot order, f32
+ *   proto_bwd:  ds[r] = dmean[c] / n_shot + dsf[r]           [S][d]      dsf may be NULL; ds is the gradient of t, a and v
+ *   dist_fwd:   qf[i] = (t[i] + a[i]) + v[i]                 [Nq][d]     "query_features"
+ *               dist[i][j] = sqrt(sum_k (qf[i][k] - P[j][k])^2) [Nq][n_way] direct differences (torch.cdist at these sizes)
+ *               pred[i] = softmax(-dist[i])                   [Nq][n_way] accurate expf on max-subtracted values
+ *   dist_bwd:   given gdist = dL/ddist and gpred = dL/dpred (either may be NULL: none),
+ *               g_ij = gdist_ij - pred_ij (gpred_ij - sum_k pred_ik gpred_ik),  c_ij = g_ij / dist_ij, 0 where dist_ij = 0
+ *               (torch's cdist backward: a query on a prototype sends it no gradient);
+ *               dq[i] = sum_j c_ij (qf[i] - P[j]),  dp[j] = -sum_i c_ij (qf[i] - P[j])   (written; either may be NULL)
+ *               One launch: a workgroup per query row for dq and per prototype for dp, no atomics (bit-deterministic).
+ * All tensors f32 dense.  Limits: d a multiple of 4 and <= 1024, 1 <= n_way <= 64, 1 <= n_shot <= 64, 1 <= Nq <= 1024;
+ * feature rows, P, dq, dp 16-byte aligned.  Refused, nothing launched: MMF_E_SHAPE for a null required pointer or a size
+ * out of range, MMF_E_ALIGN for a misaligned row operand.
+ * ------------------------------------------------------------------------------------------ */
+int mmf_fewshot_proto_fwd(const float* const s[3], float* sf, float* mean, int n_way, int n_shot, int d, void* stream);
+int mmf_fewshot_proto_bwd(const float* dmean, const float* dsf, float* ds, int n_way, int n_shot, int d, void* stream);
+int mmf_fewshot_dist_fwd(const float* const q[3], const float* P, float* qf, float* dist, float* pred, int Nq, int n_way,
+                         int d, void* stream);
+int mmf_fewshot_dist_bwd(const float* qf, const float* P, const float* dist, const float* pred, const float* gdist,
+                         const float* gpred, float* dq, float* dp, int Nq, int n_way, int d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Grouped fused attention (flash-style: no (Tq,Tk) score matrix in HBM).
  * Replaces q*scale, QK^T, softmax, P.V of F.multi_head_attention_forward as called at
  * models/fusion_layers.py:161-163,204 (six cross blocks + three self blocks of MulT in ONE

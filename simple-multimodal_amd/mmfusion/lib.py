@@ -33,6 +33,7 @@ SYMBOLS = (
     "mmf_attn_weights_mean", "mmf_gemm_f32_grouped", "mmf_gemm_f32_batched", "mmf_softmax_rows_f32", "mmf_softmax_bwd_rows_f32",
     "mmf_layernorm_f32_fwd", "mmf_layernorm_f32_bwd", "mmf_bilstm_workspace_bytes", "mmf_bilstm_layer_fwd", "mmf_bilstm_layer_bwd", "mmf_swap01",
     "mmf_distill_kl", "mmf_fusion_loss_kd", "mmf_robust_head_fwd", "mmf_robust_head_bwd",
+    "mmf_fewshot_proto_fwd", "mmf_fewshot_proto_bwd", "mmf_fewshot_dist_fwd", "mmf_fewshot_dist_bwd",
 )
 
 
@@ -165,6 +166,10 @@ def load() -> C.CDLL:
     lib.mmf_robust_head_fwd.argtypes = [pp, vp, vp, vp, pp, pp, i32, vp, pp, vp, vp, i32, i32, i32, vp]
     lib.mmf_robust_head_bwd.argtypes = [pp, vp, vp, pp, vp, pp, vp, i32, vp, pp, vp, vp, pp, vp, vp, vp, pp, pp,
                                         i32, i32, i32, vp]
+    lib.mmf_fewshot_proto_fwd.argtypes = [pp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_fewshot_proto_bwd.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_fewshot_dist_fwd.argtypes = [pp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_fewshot_dist_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mmf_skinny_linear_fwd_ex.argtypes = [C.POINTER(SkinnyProblemEx), i32, i32, i32, C.POINTER(SkinnyExtra), vp]
     lib.mmf_skinny_linear_dgrad_ex.argtypes = [C.POINTER(SkinnyProblemEx), i32, i32, f32, i32, C.POINTER(SkinnyExtra), vp]
     lib.mmf_sqnorm_f32.argtypes = [vp, i64, vp, vp]

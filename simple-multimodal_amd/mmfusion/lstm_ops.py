@@ -117,9 +117,11 @@ class _BiLSTMLayer(torch.autograd.Function):
             ops.gemm(GEMM_NN, dgd[1], ops.shadow(w_ih[1]), dx, aux=dx, epilogue=EPI_ADD_AUX)
         # h_{t-1} as the steps saw it: direction 0 reads the row block before, direction 1 the one after (zeros at the ends)
         hprev = [ybuf[0:T * B, 0:H], ybuf[2 * B:(T + 2) * B, H:2 * H]]
-        for d in range(2):
-            ops.queue_wgrad(dgd[d], x_tb, W(w_ih[d]).grad, W(b_ih[d]).grad)
-            ops.queue_wgrad(dgd[d], hprev[d], W(w_hh[d]).grad, W(b_hh[d]).grad)
+        for d in range(2):                               # (none for a frozen weight: its bias gradient is skipped with it)
+            if w_ih[d].requires_grad:
+                ops.queue_wgrad(dgd[d], x_tb, W(w_ih[d]).grad, W(b_ih[d]).grad)
+            if w_hh[d].requires_grad:
+                ops.queue_wgrad(dgd[d], hprev[d], W(w_hh[d]).grad, W(b_hh[d]).grad)
         return (dx, None, None) + (None,) * len(params)
 
 

@@ -284,6 +284,9 @@ import os as _os
 # N-way input-gradient sums of the fan-outs: three HBM-bound kernels, 40 us + launch gaps at the MulT bench shapes)
 # then runs beside the wgrad launch instead of in front of it.  A backward that queues more, or fewer, than the last one
 # is still complete: whatever is pending when the callback runs is issued there, and the callback joins the stream.
+# A weight with requires_grad = False (few-shot training freezes everything but the adapters, the prompt and the prototype
+# network) queues nothing, its bias gradient included; the input gradient still flows through it.  Its arena gradient then
+# stays as zero_grad left it (lazy zeroing: ParamArena.finalize_grads clears it).
 _WGRAD_EARLY = _os.environ.get("MMF_WGRAD_EARLY", "0") == "1"
 _pending_wgrad: List[tuple] = []
 _wgrad_stream: Optional[torch.cuda.Stream] = None
@@ -725,8 +728,9 @@ class _GroupedLinear(torch.autograd.Function):
                     dx = torch.empty(xs[i].shape, dtype=torch.float32 if ctx.f32_in else BF16, device=g.device)
                 dgrad.append((g, s.w.w16, dx, None, None))
                 grads[4 * i] = dx
-            # wgrad; the bias gradient (column sums of dy) rides along in the same kernel
-            queue_wgrad(g, xs[i], s.w.grad, s.b.grad if has_bias else None)
+            # wgrad; the bias gradient (column sums of dy) rides along in the same kernel (none for a frozen weight)
+            if s.w.p.requires_grad:
+                queue_wgrad(g, xs[i], s.w.grad, s.b.grad if has_bias else None)
             if s.has_residual:
                 grads[4 * i + 1] = g
         if dgrad:
@@ -838,7 +842,8 @@ class _RowLinear(torch.autograd.Function):
                     None, y.data_ptr() if y is not None else None, dz.data_ptr() if dz is not g else None,
                     0, _ld(y) if y is not None else 0, _ld(dz) if dz is not g else 0, 0))
                 dxs.append(dx)
-                queue_wgrad(dz, x16s[i], specs[i].w.grad, specs[i].b.grad if has_bias else None)
+                if specs[i].w.p.requires_grad:               # a frozen weight: input gradient only
+                    queue_wgrad(dz, x16s[i], specs[i].w.grad, specs[i].b.grad if has_bias else None)
                 if ctx.x_needs[i]:
                     grads[3 * i] = dx
             regen = p > 0.0 and not relu                      # dropout without ReLU: the mask is drawn again from (state, site)
@@ -946,8 +951,9 @@ class _GroupedFFN(torch.autograd.Function):
                    alpha=ctx.keep_scale)
         gemm_group(GEMM_NN, [(dhs[i], shadow(layers[i][0].weight), dxs[i], None, dys[i]) for i in idx], EPI_ADD_AUX)
         for i in idx:
-            queue_wgrad(dys[i], hs[i], layers[i][1].weight.grad, layers[i][1].bias.grad)
-            queue_wgrad(dhs[i], xs[i], layers[i][0].weight.grad, layers[i][0].bias.grad)
+            for l, dy_, x_ in ((layers[i][1], dys[i], hs[i]), (layers[i][0], dhs[i], xs[i])):
+                if l.weight.requires_grad:
+                    queue_wgrad(dy_, x_, l.weight.grad, l.bias.grad)
         grads: List[Optional[torch.Tensor]] = [None] * (5 * n)
         for i in idx:
             grads[5 * i] = dxs[i]

@@ -611,3 +611,116 @@ def robust_head(f_t: torch.Tensor, f_a: torch.Tensor, f_v: torch.Tensor, h: torc
         raise ValueError(f"robust_head: C = {heads[0].weight.shape[0]} (<= {NARROW_MAX_N}), B = {f_t.shape[0]} (<= {ROBUST_MAX_B})")
     return _RobustHead.apply(f_t, f_a, f_v, h, avail, lin2.weight, lin2.bias,
                              *[t for l in heads for t in (l.weight, l.bias)])
+
+
+# --------------------------------------------------------------------------------------------
+# episode head of FewShotModel (csrc/fewshot.hip mmf_fewshot_*)
+# --------------------------------------------------------------------------------------------
+FEWSHOT_MAX_D, FEWSHOT_MAX_WAY, FEWSHOT_MAX_SHOT, FEWSHOT_MAX_Q = 1024, 64, 64, 1024
+
+
+def _feat3(xs, who: str):
+    fs = [x.float().contiguous() for x in xs]
+    for x in fs:
+        _req(x, F32)
+    if any(x.dim() != 2 or x.shape != fs[0].shape for x in fs):
+        raise ValueError(f"{who}: the three feature tensors must share one (rows, d) shape, got {[tuple(x.shape) for x in fs]}")
+    return fs
+
+
+class _FewShotPrototypes(torch.autograd.Function):
+    """(t, a, v) support rows (class-major, n_way * n_shot) -> (support_features = (t + a) + v, class means) in one launch;
+    the backward is one launch too, and its result is the gradient of all three inputs."""
+
+    @staticmethod
+    def forward(ctx, t, a, v, n_way, n_shot):
+        fs = _feat3((t, a, v), "fewshot_prototypes")
+        S, d = fs[0].shape
+        sf = torch.empty((S, d), dtype=F32, device=fs[0].device)
+        mean = torch.empty((n_way, d), dtype=F32, device=fs[0].device)
+        lib.check(lib.load().mmf_fewshot_proto_fwd(_ptr3(fs), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d, lib.stream_ptr()))
+        ctx.set_materialize_grads(False)
+        ctx.dims = (n_way, n_shot, d)
+        return sf, mean
+
+    @staticmethod
+    def backward(ctx, gsf, gmean):
+        n_way, n_shot, d = ctx.dims
+        need = ctx.needs_input_grad[:3]
+        if not any(need) or (gsf is None and gmean is None):
+            return (None,) * 5
+        dev = (gsf if gsf is not None else gmean).device
+        gm = gmean.float().contiguous() if gmean is not None else torch.zeros((n_way, d), dtype=F32, device=dev)
+        gs = gsf.float().contiguous() if gsf is not None else None
+        ds = torch.empty((n_way * n_shot, d), dtype=F32, device=dev)
+        lib.check(lib.load().mmf_fewshot_proto_bwd(gm.data_ptr(), _ptr(gs), ds.data_ptr(), n_way, n_shot, d, lib.stream_ptr()))
+        return tuple(ds if n else None for n in need) + (None, None)
+
+
+class _FewShotScores(torch.autograd.Function):
+    """(t, a, v) query rows, prototypes P -> (query_features = (t + a) + v, distances, softmax(-distances)) in one launch;
+    dQ and dP in one launch back (the gradient of query_features, if any, is added to dQ)."""
+
+    @staticmethod
+    def forward(ctx, t, a, v, P):
+        fs = _feat3((t, a, v), "fewshot_scores")
+        P = P.float().contiguous()
+        _req(P, F32)
+        Nq, d = fs[0].shape
+        n_way = P.shape[0]
+        if P.dim() != 2 or P.shape[1] != d:
+            raise ValueError(f"fewshot_scores: prototypes {tuple(P.shape)} against query features (.., {d})")
+        dev = P.device
+        qf = torch.empty((Nq, d), dtype=F32, device=dev)
+        dist = torch.empty((Nq, n_way), dtype=F32, device=dev)
+        pred = torch.empty((Nq, n_way), dtype=F32, device=dev)
+        lib.check(lib.load().mmf_fewshot_dist_fwd(_ptr3(fs), P.data_ptr(), qf.data_ptr(), dist.data_ptr(), pred.data_ptr(),
+                                                  Nq, n_way, d, lib.stream_ptr()))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(qf, P, dist, pred)
+        return qf, dist, pred
+
+    @staticmethod
+    def backward(ctx, gqf, gdist, gpred):
+        qf, P, dist, pred = ctx.saved_tensors
+        need_q, need_p = any(ctx.needs_input_grad[:3]), ctx.needs_input_grad[3]
+        Nq, d = qf.shape
+        n_way = P.shape[0]
+        dq = dp = None
+        if gdist is not None or gpred is not None:
+            dq = torch.empty((Nq, d), dtype=F32, device=qf.device) if need_q else None
+            dp = torch.empty((n_way, d), dtype=F32, device=qf.device) if need_p else None
+            gd = gdist.float().contiguous() if gdist is not None else None
+            gp = gpred.float().contiguous() if gpred is not None else None
+            lib.check(lib.load().mmf_fewshot_dist_bwd(qf.data_ptr(), P.data_ptr(), dist.data_ptr(), pred.data_ptr(), _ptr(gd),
+                                                      _ptr(gp), _ptr(dq), _ptr(dp), Nq, n_way, d, lib.stream_ptr()))
+        if need_q and gqf is not None:
+            dq = gqf.float() if dq is None else dq + gqf.float()
+        return tuple(dq if n else None for n in ctx.needs_input_grad[:3]) + (dp,)
+
+
+def _fewshot_check(rows: int, d: int, who: str, n_way: int, n_shot: int = 1) -> None:
+    if d % 4 or d > FEWSHOT_MAX_D or not 1 <= n_way <= FEWSHOT_MAX_WAY or not 1 <= n_shot <= FEWSHOT_MAX_SHOT:
+        raise ValueError(f"{who}: d = {d} (multiple of 4, <= {FEWSHOT_MAX_D}), n_way = {n_way} (1..{FEWSHOT_MAX_WAY}), "
+                         f"n_shot = {n_shot} (1..{FEWSHOT_MAX_SHOT})")
+    if not 1 <= rows <= FEWSHOT_MAX_Q * FEWSHOT_MAX_SHOT:
+        raise ValueError(f"{who}: {rows} rows")
+
+
+def fewshot_prototypes(t: torch.Tensor, a: torch.Tensor, v: torch.Tensor, n_way: int, n_shot: int):
+    """Support features (f32 (n_way * n_shot, d) each, class-major: row c * n_shot + s) -> (support_features (t + a) + v,
+    class means (n_way, d)), f32.  d % 4 == 0, d <= 1024, n_way and n_shot in 1..64."""
+    n_way, n_shot = int(n_way), int(n_shot)
+    _fewshot_check(t.shape[0], t.shape[-1], "fewshot_prototypes", n_way, n_shot)
+    if t.shape[0] != n_way * n_shot:
+        raise ValueError(f"fewshot_prototypes: {t.shape[0]} support rows, n_way * n_shot = {n_way * n_shot}")
+    return _FewShotPrototypes.apply(t, a, v, n_way, n_shot)
+
+
+def fewshot_scores(t: torch.Tensor, a: torch.Tensor, v: torch.Tensor, prototypes: torch.Tensor):
+    """Query features (f32 (Nq, d) each) and prototypes (n_way, d) -> (query_features (t + a) + v, distances (Nq, n_way)
+    = cdist(query_features, prototypes), predictions = softmax(-distances)), f32.  Nq <= 1024, n_way <= 64."""
+    _fewshot_check(t.shape[0], t.shape[-1], "fewshot_scores", prototypes.shape[0])
+    if t.shape[0] > FEWSHOT_MAX_Q:
+        raise ValueError(f"fewshot_scores: {t.shape[0]} query rows (<= {FEWSHOT_MAX_Q})")
+    return _FewShotScores.apply(t, a, v, prototypes)

@@ -610,3 +610,83 @@ class RobustTrainStep(FusionTrainStep):
         return loss
 
     step = __call__
+
+
+FEWSHOT_TRAINABLE = ("adapter", "prompt_embeddings", "prototype_network")
+
+
+class FewShotTrainStep(FusionTrainStep):
+    """The training step of a ``FewShotModel`` (reference ``--mode few_shot``: ``FewShotTrainer.train_few_shot_episode``,
+    advanced_trainer.py:488-557), as one callable ``step(support, query, targets) -> loss`` over ``(text, audio, video)``
+    triples with ``n_way`` / ``n_shot`` fixed at construction (support rows class-major), reproducing what that loop does:
+
+      1. the constructor sets ``requires_grad`` by name, as the reference trainer does: True for a parameter whose name
+         contains ``adapter``, ``prompt_embeddings`` or ``prototype_network``, False for every other one — the backward
+         then queues no weight gradient for a frozen weight (mmfusion.ops: the deferred wgrad queue);
+      2. zero the gradient arena (lazily); forward of the wrapper in training mode (dropout, ``ModalityDropout``);
+      3. ``nn.CrossEntropyLoss()`` on ``predictions`` — probabilities already, the reference's double softmax — as ONE
+         ``small_ops.fusion_loss`` launch without label smoothing;
+      4. ``backward_from``, ``finalize_grads``; the gradient exchange of ``FusionTrainStep`` at world size > 1;
+      5. ``FusedAdamW`` with torch's AdamW defaults (lr constant: schedule mode 0, betas (0.9, 0.999), eps 1e-8, weight
+         decay 0.01), no clipping, over ``reached_parameters`` only: torch's AdamW skips a parameter whose ``.grad`` is
+         None, weight decay included.
+
+    Everything after the constructor is graph-capturable (capture single-stream, ``bench.single_stream``)."""
+
+    def __init__(self, model: torch.nn.Module, n_way: int, n_shot: int, *, lr: float = 1e-4, weight_decay: float = 0.01,
+                 allreduce: Optional[str] = "bf16", exchange: str = "after", exchange_rounds: int = 4):
+        from . import arena as arena_mod
+        for name, p in model.named_parameters():
+            p.requires_grad_(any(k in name for k in FEWSHOT_TRAINABLE))
+        arena = arena_mod.ensure(model)
+        self.n_way, self.n_shot = int(n_way), int(n_shot)
+        self.reached = self.reached_parameters(model)
+        super().__init__(model, None, arena, lr=lr, weight_decay=weight_decay, max_grad_norm=None, contrastive=False,
+                         allreduce=allreduce, shard_optimizer=False, exchange=exchange, exchange_rounds=exchange_rounds)
+
+    @staticmethod
+    def reached_parameters(model: torch.nn.Module):
+        """The trainable-by-name parameters a loss on ``predictions`` gives a gradient: the three encoders' adapters and
+        ``prototype_network``, and ``prompt_embeddings`` only when the text encoder has a backbone (feature inputs bypass
+        the prompt, so torch leaves its ``.grad`` None).  ``support_encoder`` / ``query_encoder`` never run."""
+        text_backbone = getattr(model.base_model.text_encoder, "model", None) is not None
+        out = []
+        for n, p in model.named_parameters():
+            if n.startswith("prototype_network.") or ".adapter." in n:
+                out.append(p)
+            elif n.endswith("prompt_embeddings") and text_backbone:
+                out.append(p)
+        return out
+
+    def _optimizer(self, arena, lr, weight_decay, max_grad_norm, total_steps, shard) -> FusedAdamW:
+        # schedule mode 0 (set_schedule is not called): advance() keeps the uploaded lr and beta1
+        return FusedAdamW(arena, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, max_grad_norm=None,
+                          params=self.reached)
+
+    @staticmethod
+    def _data(x) -> Dict[str, torch.Tensor]:
+        if isinstance(x, dict):
+            return x
+        text, audio, video = x
+        return {"text": text, "audio": audio, "video": video}
+
+    def fwd_bwd(self, support, query, targets) -> torch.Tensor:
+        from . import small_ops
+        self.arena.zero_grad(overlap=True, lazy=True)
+        out = self.model(self._data(support), self._data(query), self.n_way, self.n_shot)
+        loss = small_ops.fusion_loss(out["predictions"], targets, 0.0, [], [])
+        backward_from(loss)
+        self.arena.finalize_grads()
+        return loss
+
+    def __call__(self, support, query, targets) -> torch.Tensor:
+        loss = self.fwd_bwd(support, query, targets)
+        if self._bx is not None:
+            self._bx.finish()
+        elif self.world > 1:
+            dp.allreduce_grads(self.arena, compress=None if self.allreduce == "fp32" else "bf16")
+        self.opt.advance()
+        self.opt.launch()
+        return loss
+
+    step = __call__

@@ -16,12 +16,14 @@ student ``MultimodalEmotionModel``, each in its own parameter arena, the distill
 predictor in ONE arena; the head after the predictor's hidden layer is one HIP launch each way (``small_ops.robust_head``).
 ``create_model(config, "robust")`` still raises ``NotImplementedError``: construct ``RobustMultimodalModel(config)``.
 
-``FewShotModel`` (reference :265-362) is outside the hot path: the name exists so that
-``train_advanced.py:21-25`` imports, constructing it raises ``NotImplementedError``.
+``FewShotModel`` (reference :265-362): the base model, the (unused) support / query LSTMs and the prototype network in ONE
+arena; the features come from ``MultimodalEmotionModel.encode`` (no fusion layer, no heads), the class means and the
+distance / softmax tail are one HIP launch each way (``small_ops.fewshot_prototypes`` / ``fewshot_scores``).
+``create_model(config, "few_shot")`` still raises ``NotImplementedError``: construct ``FewShotModel(base_model, config)``.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -88,9 +90,11 @@ class MultimodalEmotionModel(_FusionBase):
         self.arousal_regressor = nn.Linear(d, 1)
         self.uncertainty_head = nn.Linear(d, config.num_emotions)
 
-    def forward(self, text_input: Dict[str, torch.Tensor], audio_input: torch.Tensor, video_input: torch.Tensor,
-                use_adapter: bool = False, use_prompt: bool = False, compute_contrastive_loss: bool = False,
-                missing_modalities: Optional[List[str]] = None) -> Dict[str, torch.Tensor]:
+    def encode(self, text_input: Dict[str, torch.Tensor], audio_input: torch.Tensor, video_input: torch.Tensor,
+               use_adapter: bool = False, use_prompt: bool = False,
+               missing_modalities: Optional[List[str]] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The three encoders and, in training mode, ``ModalityDropout``: -> (text, audio, video) features, exactly the
+        ``*_features`` outputs of ``forward``, without the fusion layer and the heads (``FewShotModel`` needs only these)."""
         if missing_modalities:                                                   # reference :77-86
             if "text" in missing_modalities:
                 text_input = {"input_ids": torch.zeros_like(text_input["input_ids"]),
@@ -105,6 +109,12 @@ class MultimodalEmotionModel(_FusionBase):
         vf = self.video_encoder(video_input, use_adapter=use_adapter)["features"]
         if self.training:                                                        # reference :104-107
             tf, af, vf = self.modality_dropout(tf, af, vf, training=True)
+        return tf, af, vf
+
+    def forward(self, text_input: Dict[str, torch.Tensor], audio_input: torch.Tensor, video_input: torch.Tensor,
+                use_adapter: bool = False, use_prompt: bool = False, compute_contrastive_loss: bool = False,
+                missing_modalities: Optional[List[str]] = None) -> Dict[str, torch.Tensor]:
+        tf, af, vf = self.encode(text_input, audio_input, video_input, use_adapter, use_prompt, missing_modalities)
 
         individual_logits = fusion_weights = None
         if self.fusion_type == "late":
@@ -132,17 +142,6 @@ class MultimodalEmotionModel(_FusionBase):
                 if k != "fused_features":
                     out[k] = v
         return out
-
-
-def _out_of_scope(name: str):
-    class _Stub(nn.Module):
-        def __init__(self, *a, **k):
-            super().__init__()
-            raise NotImplementedError(
-                f"{name} is a research wrapper around the fusion path (reference models/multimodal_model.py) "
-                f"and is outside the MI355X hot-path scope (SURVEY.md section 2 row 5).")
-    _Stub.__name__ = _Stub.__qualname__ = name
-    return _Stub
 
 
 class KnowledgeDistillationModel(nn.Module):
@@ -201,7 +200,66 @@ class KnowledgeDistillationModel(nn.Module):
         return student_output
 
 
-FewShotModel = _out_of_scope("FewShotModel")
+class FewShotModel(_FusionBase):
+    """Reference :265-362: ``base_model`` (a ``MultimodalEmotionModel``), ``support_encoder`` / ``query_encoder``
+    (``nn.LSTM(d, d / 2, bidirectional)``: constructed, never run, as in the reference; they keep its state_dict keys) and
+    ``prototype_network`` (Linear(d, d), ReLU, Linear(d, d)).  ``forward(support_data, query_data, n_way, n_shot)`` takes
+    the reference's dicts (``text`` {input_ids, attention_mask}, ``audio``, ``video``) and returns ``predictions`` =
+    softmax(-distances), ``distances`` = cdist(query_features, prototypes), ``prototypes`` = prototype_network(class means
+    of the support features), ``support_features`` and ``query_features`` (text + audio + video features of the base
+    model with adapters and prompt, after ``ModalityDropout`` in training mode).  Support rows are class-major: row
+    c * n_shot + s is shot s of class c; any other row count than n_way * n_shot raises ``ValueError``.
+
+    Deliberate deviation in cost only: the features come from ``base_model.encode`` (encoders + ModalityDropout); the
+    reference also runs the fusion layer and the heads and throws their outputs away (no gradient reaches them).
+
+    An arena root (``_FusionBase``): the base model and the head share one parameter arena (a ``base_model`` that had an
+    arena of its own moves into this one).  The class means, the sums of the three modalities and the distance / softmax
+    tail are HIP launches (``small_ops.fewshot_prototypes`` / ``fewshot_scores``); the prototype MLP runs on the row linear."""
+
+    def __init__(self, base_model: MultimodalEmotionModel, config):
+        super().__init__()
+        self.base_model = base_model
+        self.config = config
+        d = config.fusion_hidden_size
+        self.support_encoder = nn.LSTM(d, d // 2, batch_first=True, bidirectional=True)
+        self.query_encoder = nn.LSTM(d, d // 2, batch_first=True, bidirectional=True)
+        self.prototype_network = nn.Sequential(nn.Linear(d, d), nn.ReLU(), nn.Linear(d, d))
+
+    def _encode(self, data: Dict[str, torch.Tensor]):
+        return self.base_model.encode(data["text"], data["audio"], data["video"], use_adapter=True, use_prompt=True)
+
+    def head(self, support: Tuple[torch.Tensor, ...], query: Tuple[torch.Tensor, ...], n_way: int, n_shot: int):
+        """(text, audio, video) support and query features -> (support_features, prototypes, query_features, distances,
+        predictions)"""
+        if not support[0].is_cuda:
+            raise RuntimeError("mmfusion: the few-shot head runs on the GPU only (no CPU fallback)")
+        sf, mean = sops.fewshot_prototypes(*support, n_way, n_shot)
+        l0, l2 = self.prototype_network[0], self.prototype_network[2]
+        h = ops.linear(mean, W(l0.weight), W(l0.bias), relu=True, out_f32=True)
+        prototypes = ops.linear(h, W(l2.weight), W(l2.bias), out_f32=True)
+        qf, distances, predictions = sops.fewshot_scores(*query, prototypes)
+        return sf, prototypes, qf, distances, predictions
+
+    @staticmethod
+    def _check_rows(support_data: Dict[str, torch.Tensor], n_way: int, n_shot: int) -> None:
+        rows = support_data["audio"].shape[0]
+        if rows != int(n_way) * int(n_shot):
+            raise ValueError(f"FewShotModel: {rows} support rows, n_way * n_shot = {n_way} * {n_shot} (class-major)")
+
+    def __call__(self, support_data, query_data, n_way, n_shot):
+        self._check_rows(support_data, n_way, n_shot)            # before the arena is touched (the reference's view fails)
+        return super().__call__(support_data, query_data, n_way, n_shot)
+
+    def forward(self, support_data: Dict[str, torch.Tensor], query_data: Dict[str, torch.Tensor], n_way: int,
+                n_shot: int) -> Dict[str, torch.Tensor]:
+        n_way, n_shot = int(n_way), int(n_shot)
+        self._check_rows(support_data, n_way, n_shot)
+        support = self._encode(support_data)
+        query = self._encode(query_data)
+        sf, prototypes, qf, distances, predictions = self.head(support, query, n_way, n_shot)
+        return {"predictions": predictions, "distances": distances, "prototypes": prototypes,
+                "support_features": sf, "query_features": qf}
 
 
 class RobustMultimodalModel(_FusionBase):
@@ -266,7 +324,9 @@ def create_model(config, model_type: str = "standard") -> nn.Module:
         # and tests rely on it), the class itself is constructed directly
         raise NotImplementedError("model_type 'robust': construct RobustMultimodalModel(config) directly")
     if model_type == "few_shot":
-        raise NotImplementedError(f"model_type '{model_type}' wraps the fusion path and is out of scope here")
+        # the reference factory returns FewShotModel(MultimodalEmotionModel(config), config); this one keeps refusing as
+        # before (callers and tests rely on it): construct the class directly
+        raise NotImplementedError(f"model_type '{model_type}': construct FewShotModel(base_model, config) directly")
     raise ValueError(f"Unknown model type: {model_type}")
 
 
