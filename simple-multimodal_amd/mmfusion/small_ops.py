@@ -410,116 +410,71 @@ def _resident_scalar(v: float, device) -> torch.Tensor:
     return _SCALARS[key]
 
 
-class _FusionLoss(torch.autograd.Function):
-    """mean CE(label_smoothing) over (B, C) logits + sum_j w_j * extra_j (device scalars): value and d/d(logits) in one launch."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, smoothing, weights, *extras):
-        logits = logits.float()
-        if logits.stride(1) != 1:
-            logits = logits.contiguous()
-        B, Cn = logits.shape
-        ex = [e.float().reshape(1) for e in extras]
-        loss = torch.empty((), dtype=F32, device=logits.device)
-        dlog = torch.empty((B, Cn), dtype=F32, device=logits.device)
-        n = len(ex)
-        pe = (_C.c_void_p * max(n, 1))(*[e.data_ptr() for e in ex])
-        pw = (_C.c_float * max(n, 1))(*[float(w) for w in weights])
-        lib.check(lib.load().mmf_fusion_loss(logits.data_ptr(), logits.stride(0), targets.data_ptr(), B, Cn, float(smoothing),
-                                             pe, pw, n, loss.data_ptr(), dlog.data_ptr(), lib.stream_ptr()))
-        ctx.save_for_backward(dlog)
-        ctx.weights = [float(w) for w in weights]
-        ctx.wt = [_resident_scalar(float(w), logits.device) for w in weights]
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        dlog, = ctx.saved_tensors
-        if g.data_ptr() == loss_seed(g.device).data_ptr():       # started by backward_from: the gradient IS one
-            return (dlog, None, None, None, *ctx.wt)
-        return (dlog * g, None, None, None, *[g * w for w in ctx.weights])
-
-
-def fusion_loss(logits: torch.Tensor, targets: torch.Tensor, smoothing: float, extras, weights) -> torch.Tensor:
-    if targets.dtype != torch.int64:
-        targets = targets.long()
-    return _FusionLoss.apply(logits, targets.contiguous(), float(smoothing), list(weights), *extras)
-
-
 def _rows_f32(x: torch.Tensor) -> torch.Tensor:
     """(B, C) f32 rows with unit column stride (a row-strided view passes as is: the kernels take its leading dimension)"""
     x = x.float()
     return x if x.stride(1) == 1 else x.contiguous()
 
 
-class _DistillKL(torch.autograd.Function):
-    """T^2 * KL(softmax(t / T) || softmax(s / T)), batchmean (reference models/multimodal_model.py:250-256): value and
-    d/d(student) in one launch; the teacher's logits get no gradient."""
+class _LossTail(torch.autograd.Function):
+    """The fused loss tail of ``csrc/loss.hip``, value and d/d(logits) in one launch: with ``targets``, mean CE(label
+    smoothing) over (B, C) logits + sum_j w_j * extra_j (device scalars); with ``teacher``, + kd_weight * T^2 *
+    KL(softmax(teacher / T) || softmax(logits / T)), batchmean (reference models/multimodal_model.py:250-256).  The
+    teacher's logits get no gradient."""
 
     @staticmethod
-    def forward(ctx, student, teacher, temperature):
-        s, t = _rows_f32(student), _rows_f32(teacher.detach())
+    def forward(ctx, logits, targets, teacher, smoothing, temperature, kd_weight, weights, *extras):
+        s = _rows_f32(logits)
         B, Cn = s.shape
-        if tuple(t.shape) != (B, Cn):
-            raise ValueError(f"distill_kl: student {tuple(s.shape)} vs teacher {tuple(t.shape)}")
+        if teacher is not None:
+            t = _rows_f32(teacher.detach())
+            if tuple(t.shape) != (B, Cn):
+                raise ValueError(f"{'distill_kl' if targets is None else 'fusion_loss_kd'}: logits {tuple(s.shape)} vs "
+                                 f"teacher {tuple(t.shape)}")
         loss = torch.empty((), dtype=F32, device=s.device)
-        ds = torch.empty((B, Cn), dtype=F32, device=s.device) if ctx.needs_input_grad[0] else None
-        lib.check(lib.load().mmf_distill_kl(s.data_ptr(), s.stride(0), t.data_ptr(), t.stride(0), B, Cn, float(temperature),
-                                            loss.data_ptr(), _ptr(ds), lib.stream_ptr()))
-        ctx.save_for_backward(ds)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        ds, = ctx.saved_tensors
-        if g.data_ptr() == loss_seed(g.device).data_ptr():       # started by backward_from: the gradient IS one
-            return ds, None, None
-        return ds * g, None, None
-
-
-def distill_kl(student_logits: torch.Tensor, teacher_logits: torch.Tensor, temperature: float) -> torch.Tensor:
-    """-> 0-d f32 ``F.kl_div(log_softmax(s / T), softmax(t / T), reduction="batchmean") * T**2`` (C <= 64)"""
-    return _DistillKL.apply(student_logits, teacher_logits, float(temperature))
-
-
-class _FusionLossKD(torch.autograd.Function):
-    """``_FusionLoss`` + kd_weight * ``_DistillKL`` of the same logits: value and d/d(logits) in ONE launch."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, smoothing, weights, teacher, temperature, kd_weight, *extras):
-        s, t = _rows_f32(logits), _rows_f32(teacher.detach())
-        B, Cn = s.shape
-        if tuple(t.shape) != (B, Cn):
-            raise ValueError(f"fusion_loss_kd: logits {tuple(s.shape)} vs teacher {tuple(t.shape)}")
-        ex = [e.float().reshape(1) for e in extras]
-        loss = torch.empty((), dtype=F32, device=s.device)
-        dlog = torch.empty((B, Cn), dtype=F32, device=s.device)
-        n = len(ex)
-        pe = (_C.c_void_p * max(n, 1))(*[e.data_ptr() for e in ex])
-        pw = (_C.c_float * max(n, 1))(*[float(w) for w in weights])
-        lib.check(lib.load().mmf_fusion_loss_kd(s.data_ptr(), s.stride(0), targets.data_ptr(), B, Cn, float(smoothing),
-                                                pe, pw, n, t.data_ptr(), t.stride(0), float(temperature), float(kd_weight),
-                                                loss.data_ptr(), dlog.data_ptr(), lib.stream_ptr()))
+        dlog = torch.empty((B, Cn), dtype=F32, device=s.device) if ctx.needs_input_grad[0] else None
+        L, rows, out = lib.load(), (s.data_ptr(), s.stride(0)), (loss.data_ptr(), _ptr(dlog), lib.stream_ptr())
+        if targets is None:
+            rc = L.mmf_distill_kl(*rows, t.data_ptr(), t.stride(0), B, Cn, temperature, *out)
+        else:
+            ex = [e.float().reshape(1) for e in extras]
+            ce = (*rows, targets.data_ptr(), B, Cn, smoothing, (_C.c_void_p * max(len(ex), 1))(*[e.data_ptr() for e in ex]),
+                  (_C.c_float * max(len(ex), 1))(*weights), len(ex))
+            rc = (L.mmf_fusion_loss(*ce, *out) if teacher is None
+                  else L.mmf_fusion_loss_kd(*ce, t.data_ptr(), t.stride(0), temperature, kd_weight, *out))
+        lib.check(rc)
         ctx.save_for_backward(dlog)
-        ctx.weights = [float(w) for w in weights]
-        ctx.wt = [_resident_scalar(float(w), s.device) for w in weights]
+        ctx.weights = weights
+        ctx.wt = [_resident_scalar(w, s.device) for w in weights]
         return loss
 
     @staticmethod
     def backward(ctx, g):
         dlog, = ctx.saved_tensors
-        if g.data_ptr() == loss_seed(g.device).data_ptr():
+        if g.data_ptr() == loss_seed(g.device).data_ptr():       # started by backward_from: the gradient IS one
             return (dlog, None, None, None, None, None, None, *ctx.wt)
-        return (dlog * g, None, None, None, None, None, None, *[g * w for w in ctx.weights])
+        return (None if dlog is None else dlog * g, None, None, None, None, None, None, *[g * w for w in ctx.weights])
+
+
+def _targets(targets: torch.Tensor) -> torch.Tensor:
+    return (targets if targets.dtype == torch.int64 else targets.long()).contiguous()
+
+
+def fusion_loss(logits: torch.Tensor, targets: torch.Tensor, smoothing: float, extras, weights) -> torch.Tensor:
+    """-> 0-d f32 CE(logits, targets, label_smoothing) + sum_j weights[j] * extras[j] (C <= 64)"""
+    return _LossTail.apply(logits, _targets(targets), None, float(smoothing), 1.0, 1.0, [float(w) for w in weights], *extras)
+
+
+def distill_kl(student_logits: torch.Tensor, teacher_logits: torch.Tensor, temperature: float) -> torch.Tensor:
+    """-> 0-d f32 ``F.kl_div(log_softmax(s / T), softmax(t / T), reduction="batchmean") * T**2`` (C <= 64)"""
+    return _LossTail.apply(student_logits, None, teacher_logits, 0.0, float(temperature), 1.0, [])
 
 
 def fusion_loss_kd(logits: torch.Tensor, targets: torch.Tensor, smoothing: float, extras, weights,
                    teacher_logits: torch.Tensor, temperature: float, kd_weight: float) -> torch.Tensor:
     """``fusion_loss`` + kd_weight * ``distill_kl(logits, teacher_logits, temperature)``, one launch forward, none backward"""
-    if targets.dtype != torch.int64:
-        targets = targets.long()
-    return _FusionLossKD.apply(logits, targets.contiguous(), float(smoothing), list(weights), teacher_logits,
-                               float(temperature), float(kd_weight), *extras)
+    return _LossTail.apply(logits, _targets(targets), teacher_logits, float(smoothing), float(temperature), float(kd_weight),
+                           [float(w) for w in weights], *extras)
 
 
 # --------------------------------------------------------------------------------------------

@@ -440,17 +440,24 @@ class FusionTrainStep:
     """fusion module + classifier head + loss + (RCCL all-reduce) + fused AdamW, as one callable.
 
     ``model(text, audio, video, compute_contrastive_loss=...)`` must return a dict with
-    ``fused_features``; ``head`` maps them to emotion logits (reference ``EmotionClassifier``)."""
+    ``fused_features``; ``head`` maps them to emotion logits (reference ``EmotionClassifier``).
 
-    def __init__(self, model: torch.nn.Module, head: torch.nn.Module, arena: ParamArena, *, lr: float = 1e-4,
-                 weight_decay: float = 1e-5, max_grad_norm: float = 1.0, total_steps: int = 1000,
+    The step loop is this class's for every training mode: a subclass overrides ``loss`` (its forward and loss) and
+    passes the optimiser of its recipe to the constructor."""
+
+    def __init__(self, model: torch.nn.Module, head: Optional[torch.nn.Module], arena: ParamArena, *, lr: float = 1e-4,
+                 weight_decay: float = 1e-5, max_grad_norm: Optional[float] = 1.0, total_steps: int = 1000,
                  contrastive: bool = True, allreduce: Optional[str] = "bf16", shard_optimizer: bool = False,
-                 exchange: str = "after", exchange_rounds: int = 4):
+                 exchange: str = "after", exchange_rounds: int = 4, opt: Optional[FusedAdamW] = None):
         """exchange: "after" = one bucketed all-reduce of the gradient arena after backward; "backward" = the exchange
         runs inside backward in ``exchange_rounds`` reverse-autograd rounds (``dp.BackwardExchange``; replicated optimiser
-        only)."""
+        only).  opt: the optimiser over ``arena``; None builds the fusion recipe's (AdamW, OneCycleLR evaluated on the
+        device per step, clipping at ``max_grad_norm``)."""
         self.model, self.head, self.arena = model, head, arena
-        self.opt = self._optimizer(arena, lr, weight_decay, max_grad_norm, total_steps, shard_optimizer)
+        if opt is None:
+            opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard_optimizer)
+            opt.set_schedule(lr, total_steps)
+        self.opt = opt
         self.max_lr, self.total_steps, self.contrastive, self.allreduce = lr, total_steps, contrastive, allreduce
         self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
         if exchange not in ("after", "backward"):
@@ -461,25 +468,24 @@ class FusionTrainStep:
                 raise ValueError("the in-backward all-reduce and the sharded optimiser (reduce-scatter) exclude each other")
             self._bx = dp.BackwardExchange(arena, exchange_rounds, None if allreduce == "fp32" else "bf16").install()
 
-    def _optimizer(self, arena, lr, weight_decay, max_grad_norm, total_steps, shard) -> FusedAdamW:
-        opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard)
-        opt.set_schedule(lr, total_steps)                 # OneCycleLR evaluated on the device, per step
-        return opt
-
-    def fwd_bwd(self, text, audio, video, targets) -> torch.Tensor:
-        self.arena.zero_grad(overlap=True, lazy=True)
+    def loss(self, text, audio, video, targets) -> torch.Tensor:
+        """the forward and the loss of one step"""
         kw = {"compute_contrastive_loss": True} if self.contrastive else {}
         out = self.model(text, audio, video, **kw)
         fused = out["fused_features"] if isinstance(out, dict) else out
         outputs = dict(out) if isinstance(out, dict) else {}
         outputs["emotion_logits"] = self.head(fused)
-        loss = fusion_loss(outputs, targets)
+        return fusion_loss(outputs, targets)
+
+    def fwd_bwd(self, *inputs, **kw) -> torch.Tensor:
+        self.arena.zero_grad(overlap=True, lazy=True)
+        loss = self.loss(*inputs, **kw)
         backward_from(loss)
         self.arena.finalize_grads()
         return loss
 
-    def __call__(self, text, audio, video, targets) -> torch.Tensor:
-        loss = self.fwd_bwd(text, audio, video, targets)
+    def __call__(self, *inputs, **kw) -> torch.Tensor:
+        loss = self.fwd_bwd(*inputs, **kw)
         if self._bx is not None:                             # most of the arena is already on the wire
             self._bx.finish()
         elif self.world > 1 and not self.opt.sharded:        # (the sharded step reduce-scatters the gradients itself)
@@ -487,6 +493,8 @@ class FusionTrainStep:
         self.opt.advance()
         self.opt.launch()
         return loss
+
+    step = __call__
 
 
 class DistillTrainStep(FusionTrainStep):
@@ -524,18 +532,14 @@ class DistillTrainStep(FusionTrainStep):
                          shard_optimizer=shard_optimizer, exchange=exchange, exchange_rounds=exchange_rounds)
         self.kd, self.label_smoothing, self.kd_weight = kd_model, float(label_smoothing), float(kd_weight)
 
-    def fwd_bwd(self, text, audio, video, targets) -> torch.Tensor:
+    def loss(self, text, audio, video, targets) -> torch.Tensor:
         from . import small_ops
-        self.arena.zero_grad(overlap=True, lazy=True)
         kw = {"compute_contrastive_loss": True} if self.contrastive else {}
         out = self.model(text, audio, video, **kw)
         teacher_logits = self.kd.teacher_forward(text, audio, video, **kw)["emotion_logits"]
         cl = out.get("contrastive_losses") or {}
-        loss = small_ops.fusion_loss_kd(out["emotion_logits"], targets, self.label_smoothing, list(cl.values()),
+        return small_ops.fusion_loss_kd(out["emotion_logits"], targets, self.label_smoothing, list(cl.values()),
                                         [0.1] * len(cl), teacher_logits, self.kd.temperature, self.kd_weight)
-        backward_from(loss)
-        self.arena.finalize_grads()
-        return loss
 
 
 class RobustTrainStep(FusionTrainStep):
@@ -563,8 +567,12 @@ class RobustTrainStep(FusionTrainStep):
         from . import arena as arena_mod
         arena = arena_mod.ensure(model)
         self.reached = self.reached_parameters(model)
+        # schedule mode 0 (set_schedule is not called): advance() keeps the uploaded lr and beta1, and derives the bias
+        # corrections from the device step counter
+        opt = FusedAdamW(arena, lr=lr / 25.0, betas=(0.95, 0.999), weight_decay=weight_decay, max_grad_norm=None,
+                         params=self.reached)
         super().__init__(model, None, arena, lr=lr, weight_decay=weight_decay, max_grad_norm=None, contrastive=False,
-                         allreduce=allreduce, shard_optimizer=False, exchange=exchange, exchange_rounds=exchange_rounds)
+                         allreduce=allreduce, exchange=exchange, exchange_rounds=exchange_rounds, opt=opt)
         self.label_smoothing = float(label_smoothing)
 
     @staticmethod
@@ -584,32 +592,10 @@ class RobustTrainStep(FusionTrainStep):
             out.append(p)
         return out
 
-    def _optimizer(self, arena, lr, weight_decay, max_grad_norm, total_steps, shard) -> FusedAdamW:
-        # schedule mode 0 (set_schedule is not called): advance() keeps the uploaded lr and beta1, and derives the bias
-        # corrections from the device step counter
-        return FusedAdamW(arena, lr=lr / 25.0, betas=(0.95, 0.999), weight_decay=weight_decay, max_grad_norm=None,
-                          params=self.reached)
-
-    def fwd_bwd(self, text, audio, video, targets, missing_modalities=None) -> torch.Tensor:
+    def loss(self, text, audio, video, targets, missing_modalities=None) -> torch.Tensor:
         from . import small_ops
-        self.arena.zero_grad(overlap=True, lazy=True)
         out = self.model(text, audio, video, missing_modalities=missing_modalities)
-        loss = small_ops.fusion_loss(out["robust_prediction"], targets, self.label_smoothing, [], [])
-        backward_from(loss)
-        self.arena.finalize_grads()
-        return loss
-
-    def __call__(self, text, audio, video, targets, missing_modalities=None) -> torch.Tensor:
-        loss = self.fwd_bwd(text, audio, video, targets, missing_modalities)
-        if self._bx is not None:
-            self._bx.finish()
-        elif self.world > 1:
-            dp.allreduce_grads(self.arena, compress=None if self.allreduce == "fp32" else "bf16")
-        self.opt.advance()
-        self.opt.launch()
-        return loss
-
-    step = __call__
+        return small_ops.fusion_loss(out["robust_prediction"], targets, self.label_smoothing, [], [])
 
 
 FEWSHOT_TRAINABLE = ("adapter", "prompt_embeddings", "prototype_network")
@@ -641,8 +627,10 @@ class FewShotTrainStep(FusionTrainStep):
         arena = arena_mod.ensure(model)
         self.n_way, self.n_shot = int(n_way), int(n_shot)
         self.reached = self.reached_parameters(model)
+        # schedule mode 0 (set_schedule is not called): advance() keeps the uploaded lr and beta1
+        opt = FusedAdamW(arena, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, max_grad_norm=None, params=self.reached)
         super().__init__(model, None, arena, lr=lr, weight_decay=weight_decay, max_grad_norm=None, contrastive=False,
-                         allreduce=allreduce, shard_optimizer=False, exchange=exchange, exchange_rounds=exchange_rounds)
+                         allreduce=allreduce, exchange=exchange, exchange_rounds=exchange_rounds, opt=opt)
 
     @staticmethod
     def reached_parameters(model: torch.nn.Module):
@@ -658,11 +646,6 @@ class FewShotTrainStep(FusionTrainStep):
                 out.append(p)
         return out
 
-    def _optimizer(self, arena, lr, weight_decay, max_grad_norm, total_steps, shard) -> FusedAdamW:
-        # schedule mode 0 (set_schedule is not called): advance() keeps the uploaded lr and beta1
-        return FusedAdamW(arena, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, max_grad_norm=None,
-                          params=self.reached)
-
     @staticmethod
     def _data(x) -> Dict[str, torch.Tensor]:
         if isinstance(x, dict):
@@ -670,23 +653,7 @@ class FewShotTrainStep(FusionTrainStep):
         text, audio, video = x
         return {"text": text, "audio": audio, "video": video}
 
-    def fwd_bwd(self, support, query, targets) -> torch.Tensor:
+    def loss(self, support, query, targets) -> torch.Tensor:
         from . import small_ops
-        self.arena.zero_grad(overlap=True, lazy=True)
         out = self.model(self._data(support), self._data(query), self.n_way, self.n_shot)
-        loss = small_ops.fusion_loss(out["predictions"], targets, 0.0, [], [])
-        backward_from(loss)
-        self.arena.finalize_grads()
-        return loss
-
-    def __call__(self, support, query, targets) -> torch.Tensor:
-        loss = self.fwd_bwd(support, query, targets)
-        if self._bx is not None:
-            self._bx.finish()
-        elif self.world > 1:
-            dp.allreduce_grads(self.arena, compress=None if self.allreduce == "fp32" else "bf16")
-        self.opt.advance()
-        self.opt.launch()
-        return loss
-
-    step = __call__
+        return small_ops.fusion_loss(out["predictions"], targets, 0.0, [], [])

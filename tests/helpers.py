@@ -1,4 +1,6 @@
-"""Shared test helpers: golden-fixture loading and oracle dispatch (test infrastructure)."""
+"""Shared test helpers: golden-fixture loading and oracle dispatch, raw entry-point plumbing, error-bound checks and the
+graph-replay check of the training steps (test infrastructure)."""
+import ctypes as C
 import json
 import os
 from types import SimpleNamespace
@@ -158,3 +160,81 @@ def masked_hierarchical_fusion(config):
             return h
 
     return MaskedHierarchicalFusion(config)
+
+
+def hip_lib():
+    """(the loaded libmmfusion, the current stream) for calling entry points directly"""
+    from mmfusion import lib
+    return lib.load(), lib.stream_ptr()
+
+
+def ptr3(ts):
+    """a void*[3] of three tensors (or raw addresses, or None)"""
+    return (C.c_void_p * 3)(*[None if t is None else (t if isinstance(t, int) else t.data_ptr()) for t in ts])
+
+
+def within_bound(got, want, bound, label, worst):
+    """assert |got - want| <= bound elementwise (want, bound float64 on the CPU); worst = [ratio, label] keeps the largest
+    error / bound seen"""
+    e = (got.double().cpu() - want).abs()
+    r = float((e / bound.clamp_min(1e-300)).max())
+    if r > worst[0]:
+        worst[0], worst[1] = r, label
+    assert bool((e <= bound).all()), f"{label}: error {float(e.max()):.3e}, worst / bound {r:.3f}"
+
+
+def check_graph_replay_matches_eager(step, arena, opt, extra_state=()):
+    """Three steps of ``step()`` captured as one single-chain graph (``bench.single_stream``) and replayed, against three
+    eager steps from the same state: the arena (masters, bf16 shadow, gradients), the optimiser (moments, step counter,
+    hyper-parameters, gradient norm), the dropout state and ``extra_state``, restored before each run.  Asserted per step:
+    no NaN, the loss to 1e-6 relative, the whole gradient arena to 1e-6 of its max, the parameters to 1e-6; then that the
+    eager losses differ (new dropout masks every step) and that the parameters moved.
+    Returns (eager, replay, worst gradient diff, worst parameter diff, parameter movement); eager / replay hold
+    (loss, gradient arena, parameters) per step."""
+    import bench
+    from mmfusion import ops
+    state = [arena.master_full, arena.shadow_full, arena.grads_full, opt.exp_avg, opt.exp_avg_sq, opt.step_dev, opt.hparams,
+             opt.gnorm_sq, ops.rng_state(), *extra_state]
+
+    def restore(saved):
+        for x, v in zip(state, saved):
+            x.copy_(v)
+        torch.cuda.synchronize()
+
+    def trace(fn):
+        out = []
+        for _ in range(3):
+            loss = fn()
+            torch.cuda.synchronize()
+            out.append((float(loss.detach()), arena.grads.clone(), arena.master.clone()))
+        return out
+
+    s0 = [x.clone() for x in state]
+    with bench.single_stream():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            static_loss = step()
+        restore(s0)
+        eager = trace(step)
+        restore(s0)
+        replay = trace(lambda: (g.replay(), static_loss)[1])
+    worst_g = worst_p = 0.0
+    for k, ((le, ge, pe), (lr_, gr, pr)) in enumerate(zip(eager, replay)):
+        assert not bool(gr.isnan().any()) and not bool(pr.isnan().any()), f"step {k + 1}: NaN in the replayed step"
+        assert abs(le - lr_) <= 1e-6 * max(1.0, abs(le)), f"step {k + 1}: loss eager {le} vs replay {lr_}"
+        eg = float((ge - gr).abs().max()) / float(ge.abs().max())
+        ep = float((pe - pr).abs().max())
+        worst_g, worst_p = max(worst_g, eg), max(worst_p, ep)
+        assert eg <= 1e-6, f"step {k + 1}: gradient arena differs by {eg:.3e} of its max"
+        assert ep <= 1e-6, f"step {k + 1}: parameters differ by {ep:.3e}"
+    assert len({e[0] for e in eager}) == 3                    # new dropout masks every step
+    moved = float((eager[-1][2] - s0[0][:arena.numel]).abs().max())
+    assert moved > 0
+    return eager, replay, worst_g, worst_p, moved

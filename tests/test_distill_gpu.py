@@ -9,20 +9,15 @@ import torch
 import torch.nn.functional as F
 
 from distill_ref import kd_grad_bound, kd_loss_bound, kd_value_grad
-from helpers import l2_rel
+from helpers import check_graph_replay_matches_eager, hip_lib, l2_rel
 
 pytestmark = pytest.mark.gpu
 
 MMF_E_SHAPE = -1
 
 
-def _lib():
-    from mmfusion import lib
-    return lib.load(), lib.stream_ptr()
-
-
 def _kl(s, t, T, grad=True):
-    L, st = _lib()
+    L, st = hip_lib()
     B, Cn = s.shape
     loss = torch.full((), float("nan"), device="cuda")
     ds = torch.full((B, Cn), float("nan"), device="cuda") if grad else None
@@ -37,7 +32,7 @@ def _ptrs(extras, weights):
 
 
 def _fl(s, y, eps, extras, weights):
-    L, st = _lib()
+    L, st = hip_lib()
     B, Cn = s.shape
     loss = torch.full((), float("nan"), device="cuda")
     d = torch.full((B, Cn), float("nan"), device="cuda")
@@ -48,7 +43,7 @@ def _fl(s, y, eps, extras, weights):
 
 
 def _flkd(s, y, eps, extras, weights, t, T, w, ldt=None, B=None, Cn=None):
-    L, st = _lib()
+    L, st = hip_lib()
     B = s.shape[0] if B is None else B
     Cn = s.shape[1] if Cn is None else Cn
     loss = torch.full((), float("nan"), device="cuda")
@@ -148,7 +143,7 @@ def test_kd_entry_points_refuse_bad_arguments():
     s = torch.randn(B, 80, device="cuda")          # every buffer large enough that a wrongly accepted call stays in bounds
     t = torch.randn(B, 80, device="cuda")
     y = torch.zeros(B, dtype=torch.int64, device="cuda")
-    L, st = _lib()
+    L, st = hip_lib()
     bad_kl = [dict(T=0.0), dict(T=-1.0), dict(T=float("nan")), dict(T=float("inf")), dict(teacher=None), dict(ldt=6),
               dict(lds=6), dict(C=0), dict(C=65), dict(B=0), dict(loss=None)]
     for case in bad_kl:
@@ -371,60 +366,12 @@ def test_distill_step_graph_replay_matches_eager():
     student parameters.  The learning rate is small on purpose: the GAT backward accumulates with atomics (last-bit
     nondeterminism, ~1e-7 of a gradient) and Adam turns a sign flip of a near-zero gradient into a 2 x lr parameter step,
     so at lr = 1e-3 two EAGER runs drift apart by ~1e-3 within three steps; at lr = 1e-7 that stays under 1e-6."""
-    import bench
-    from mmfusion import ops
     from mmfusion.train import DistillTrainStep
     _, _, kd, B = _pair("small", dropout=0.1, modality_dropout=0.1)
     assert kd.teacher.training
     ti, au, vi, labels = _cuda_inputs(B)
     ts = DistillTrainStep(kd, lr=1e-7, weight_decay=1e-2, total_steps=10)
-    ar, opt = ts.arena, ts.opt
-    state = [ar.master_full, ar.shadow_full, ar.grads_full, opt.exp_avg, opt.exp_avg_sq, opt.step_dev, opt.hparams,
-             opt.gnorm_sq, ops.rng_state(), kd.teacher_rng_state()]
-
-    def snap():
-        return [x.clone() for x in state]
-
-    def restore(saved):
-        for x, v in zip(state, saved):
-            x.copy_(v)
-        torch.cuda.synchronize()
-
-    def trace(fn):
-        out = []
-        for _ in range(3):
-            loss = fn()
-            torch.cuda.synchronize()
-            out.append((float(loss.detach()), ar.grads.clone(), ar.master.clone()))
-        return out
-
-    s0 = snap()
-    with bench.single_stream():
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                ts(ti, au, vi, labels)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            static_loss = ts(ti, au, vi, labels)
-        restore(s0)
-        eager = trace(lambda: ts(ti, au, vi, labels))
-        restore(s0)
-        replay = trace(lambda: (g.replay(), static_loss)[1])
-    worst_g = worst_p = 0.0
-    for k, ((le, ge, pe), (lr_, gr, pr)) in enumerate(zip(eager, replay)):
-        assert not bool(gr.isnan().any()) and not bool(pr.isnan().any()), f"step {k + 1}: NaN in the replayed step"
-        assert le == lr_ or abs(le - lr_) <= 1e-6 * max(1.0, abs(le)), f"step {k + 1}: loss eager {le} vs replay {lr_}"
-        eg = float((ge - gr).abs().max()) / float(ge.abs().max())
-        ep = float((pe - pr).abs().max())
-        worst_g, worst_p = max(worst_g, eg), max(worst_p, ep)
-        assert eg <= 1e-6, f"step {k + 1}: gradient arena differs by {eg:.3e} of its max"
-        assert ep <= 1e-6, f"step {k + 1}: student parameters differ by {ep:.3e}"
-    assert len({e[0] for e in eager}) == 3                    # new dropout masks every step
-    moved = float((eager[-1][2] - s0[0][:ar.numel]).abs().max())
-    assert moved > 0
+    eager, replay, worst_g, worst_p, moved = check_graph_replay_matches_eager(lambda: ts(ti, au, vi, labels), ts.arena, ts.opt,
+                                                                              [kd.teacher_rng_state()])
     print(f"graph replay: losses {[r[0] for r in replay]} (eager {[e[0] for e in eager]}); worst gradient diff "
           f"{worst_g:.2e} of max, worst parameter diff {worst_p:.2e} (parameters moved up to {moved:.2e})")

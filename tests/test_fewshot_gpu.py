@@ -3,27 +3,17 @@ tests/fewshot_ref.py (per-element f32 error bounds, worst error reported as a fr
 determinism and refusals, the head in the fp32 parity mode, the wrapper in eval mode against the base model, and
 ``mmfusion.train.FewShotTrainStep`` (gradients against the torch formulation of the head, which parameters it steps and
 which weight gradients it queues, graph replay, checkpoints)."""
-import ctypes as C
 
 import pytest
 import torch
 
 from fewshot_ref import dist_bwd_bound, dist_fwd, pred_bound, proto_bwd_bound, proto_fwd, query_features
-from helpers import l2_rel
+from helpers import check_graph_replay_matches_eager, hip_lib, l2_rel, ptr3, within_bound
 
 pytestmark = pytest.mark.gpu
 
 MMF_E_SHAPE, MMF_E_ALIGN = -1, -3
 NAN = float("nan")
-
-
-def _lib():
-    from mmfusion import lib
-    return lib.load(), lib.stream_ptr()
-
-
-def _p3(ts):
-    return (C.c_void_p * 3)(*[None if t is None else (t if isinstance(t, int) else t.data_ptr()) for t in ts])
 
 
 def _ptr(t):
@@ -35,15 +25,15 @@ def _nan(*s):
 
 
 def _proto_fwd(s3, n_way, n_shot, d=None):
-    L, st = _lib()
+    L, st = hip_lib()
     S, d0 = s3[0].shape
     sf, mean = _nan(S, d0), _nan(n_way, d0)
-    rc = L.mmf_fewshot_proto_fwd(_p3(s3), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d0 if d is None else d, st)
+    rc = L.mmf_fewshot_proto_fwd(ptr3(s3), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d0 if d is None else d, st)
     return rc, sf, mean
 
 
 def _proto_bwd(dmean, dsf, n_way, n_shot, d=None):
-    L, st = _lib()
+    L, st = hip_lib()
     d0 = dmean.shape[1]
     ds = _nan(n_way * n_shot, d0)
     rc = L.mmf_fewshot_proto_bwd(dmean.data_ptr(), _ptr(dsf), ds.data_ptr(), n_way, n_shot, d0 if d is None else d, st)
@@ -51,17 +41,17 @@ def _proto_bwd(dmean, dsf, n_way, n_shot, d=None):
 
 
 def _dist_fwd(q3, P, Nq=None, n_way=None, d=None):
-    L, st = _lib()
+    L, st = hip_lib()
     Nq0, d0 = q3[0].shape
     nw = P.shape[0]
     qf, dist, pred = _nan(Nq0, d0), _nan(Nq0, nw), _nan(Nq0, nw)
-    rc = L.mmf_fewshot_dist_fwd(_p3(q3), _ptr(P), qf.data_ptr(), dist.data_ptr(), pred.data_ptr(), Nq0 if Nq is None else Nq,
+    rc = L.mmf_fewshot_dist_fwd(ptr3(q3), _ptr(P), qf.data_ptr(), dist.data_ptr(), pred.data_ptr(), Nq0 if Nq is None else Nq,
                                 nw if n_way is None else n_way, d0 if d is None else d, st)
     return rc, qf, dist, pred
 
 
 def _dist_bwd(qf, P, dist, pred, gd, gp, want_q=True, want_p=True, Nq=None, n_way=None, d=None):
-    L, st = _lib()
+    L, st = hip_lib()
     Nq0, d0 = qf.shape
     nw = P.shape[0]
     dq = _nan(Nq0, d0) if want_q else None
@@ -69,14 +59,6 @@ def _dist_bwd(qf, P, dist, pred, gd, gp, want_q=True, want_p=True, Nq=None, n_wa
     rc = L.mmf_fewshot_dist_bwd(qf.data_ptr(), P.data_ptr(), dist.data_ptr(), pred.data_ptr(), _ptr(gd), _ptr(gp), _ptr(dq),
                                 _ptr(dP), Nq0 if Nq is None else Nq, nw if n_way is None else n_way, d0 if d is None else d, st)
     return rc, dq, dP
-
-
-def _within(got, want, bound, label, worst):
-    e = (got.double().cpu() - want).abs()
-    r = float((e / bound.clamp_min(1e-300)).max())
-    if r > worst[0]:
-        worst[0], worst[1] = r, label
-    assert bool((e <= bound).all()), f"{label}: error {float(e.max()):.3e}, worst / bound {r:.3f}"
 
 
 def _episode(n_way, n_shot, Nq, d, seed):
@@ -103,17 +85,17 @@ def test_fewshot_kernels_against_float64():
         torch.cuda.synchronize()
         assert rc == 0, label
         ref = proto_fwd(s3, n_way, n_shot)
-        _within(sf, ref["sf"], ref["e_sf"], label + " support_features", worst_f)
-        _within(mean, ref["mean"], ref["e_mean"], label + " mean", worst_f)
+        within_bound(sf, ref["sf"], ref["e_sf"], label + " support_features", worst_f)
+        within_bound(mean, ref["mean"], ref["e_mean"], label + " mean", worst_f)
         rc, qf, dist, pred = _dist_fwd(q3, P)
         torch.cuda.synchronize()
         assert rc == 0, label
         rq, e_q = query_features(q3)
-        _within(qf, rq, e_q, label + " query_features", worst_f)
+        within_bound(qf, rq, e_q, label + " query_features", worst_f)
         rd = dist_fwd(qf, P)
-        _within(dist, rd["dist"], rd["e_dist"], label + " distances", worst_f)
+        within_bound(dist, rd["dist"], rd["e_dist"], label + " distances", worst_f)
         rp = torch.softmax(-dist.double().cpu(), dim=-1)            # from the kernel's own f32 distances
-        _within(pred, rp, pred_bound(dist, rp), label + " predictions", worst_f)
+        within_bound(pred, rp, pred_bound(dist, rp), label + " predictions", worst_f)
         # backward, with each upstream gradient alone and both
         for which in ("pred", "dist", "both"):
             gd = torch.randn(Nq, n_way, generator=g).cuda() if which in ("dist", "both") else None
@@ -122,15 +104,15 @@ def test_fewshot_kernels_against_float64():
             torch.cuda.synchronize()
             assert rc == 0, label
             rq_, rP_, e_dq, e_dP = dist_bwd_bound(qf, P, dist, pred, gd, gp)
-            _within(dq, rq_, e_dq, f"{label} grads={which} dq", worst_b)
-            _within(dP, rP_, e_dP, f"{label} grads={which} dP", worst_b)
+            within_bound(dq, rq_, e_dq, f"{label} grads={which} dq", worst_b)
+            within_bound(dP, rP_, e_dP, f"{label} grads={which} dP", worst_b)
         dmean = torch.randn(n_way, d, generator=g).cuda()
         for dsf in (None, torch.randn(n_way * n_shot, d, generator=g).cuda()):
             rc, ds = _proto_bwd(dmean, dsf, n_way, n_shot)
             torch.cuda.synchronize()
             assert rc == 0, label
             want, bound = proto_bwd_bound(dmean, dsf, n_shot)
-            _within(ds, want, bound, f"{label} ds dsf={dsf is not None}", worst_b)
+            within_bound(ds, want, bound, f"{label} ds dsf={dsf is not None}", worst_b)
     print(f"fewshot head: {len(CASES)} episodes; worst error / bound: forward {worst_f[0]:.3e} ({worst_f[1]}), "
           f"backward {worst_b[0]:.3e} ({worst_b[1]})")
 
@@ -175,7 +157,7 @@ def test_backward_is_bit_deterministic():
 def test_every_limit_refuses():
     n_way, n_shot, Nq, d = 4, 2, 8, 256
     s3, q3, P, g = _episode(n_way, n_shot, Nq, d, 3)
-    L, st = _lib()
+    L, st = hip_lib()
     # every operand and output of a refused call lives in a buffer large enough for the largest size asked for, so a call
     # accepted by mistake would stay in bounds; the outputs keep their NaN sentinel
     big_n = 65 * 65 * 1028 + 64
@@ -183,14 +165,14 @@ def test_every_limit_refuses():
     outs = [_nan(big_n) for _ in range(3)]
     for case in [dict(d=254), dict(d=0), dict(d=1028), dict(n_way=0), dict(n_way=65), dict(n_shot=0), dict(n_shot=65)]:
         nw, ns, dd = case.get("n_way", n_way), case.get("n_shot", n_shot), case.get("d", d)
-        rc = L.mmf_fewshot_proto_fwd(_p3([src] * 3), outs[0].data_ptr(), outs[1].data_ptr(), nw, ns, dd, st)
+        rc = L.mmf_fewshot_proto_fwd(ptr3([src] * 3), outs[0].data_ptr(), outs[1].data_ptr(), nw, ns, dd, st)
         rc2 = L.mmf_fewshot_proto_bwd(src.data_ptr(), None, outs[2].data_ptr(), nw, ns, dd, st)
         torch.cuda.synchronize()
         assert rc == MMF_E_SHAPE and rc2 == MMF_E_SHAPE, case
         assert all(bool(o.isnan().all()) for o in outs), case
     for case in [dict(d=254), dict(d=1028), dict(n_way=0), dict(n_way=65), dict(Nq=0), dict(Nq=1025)]:
         nq, nw, dd = case.get("Nq", Nq), case.get("n_way", n_way), case.get("d", d)
-        rc = L.mmf_fewshot_dist_fwd(_p3([src] * 3), src.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+        rc = L.mmf_fewshot_dist_fwd(ptr3([src] * 3), src.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
                                     nq, nw, dd, st)
         rc2 = L.mmf_fewshot_dist_bwd(src.data_ptr(), src.data_ptr(), src.data_ptr(), src.data_ptr(), None, src.data_ptr(),
                                      outs[0].data_ptr(), outs[1].data_ptr(), nq, nw, dd, st)
@@ -199,20 +181,20 @@ def test_every_limit_refuses():
         assert all(bool(o.isnan().all()) for o in outs), case
     # null required pointers
     sf, mean = _nan(n_way * n_shot, d), _nan(n_way, d)
-    assert L.mmf_fewshot_proto_fwd(_p3([s3[0], None, s3[2]]), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d, st) == MMF_E_SHAPE
+    assert L.mmf_fewshot_proto_fwd(ptr3([s3[0], None, s3[2]]), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d, st) == MMF_E_SHAPE
     assert L.mmf_fewshot_proto_fwd(None, sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d, st) == MMF_E_SHAPE
-    assert L.mmf_fewshot_proto_fwd(_p3(s3), sf.data_ptr(), None, n_way, n_shot, d, st) == MMF_E_SHAPE
+    assert L.mmf_fewshot_proto_fwd(ptr3(s3), sf.data_ptr(), None, n_way, n_shot, d, st) == MMF_E_SHAPE
     assert L.mmf_fewshot_proto_bwd(None, None, sf.data_ptr(), n_way, n_shot, d, st) == MMF_E_SHAPE
     rc, qf, dist, pred = _dist_fwd(q3, P)
     assert rc == 0
     qf2, d2, p2 = _nan(Nq, d), _nan(Nq, n_way), _nan(Nq, n_way)
-    assert L.mmf_fewshot_dist_fwd(_p3(q3), None, qf2.data_ptr(), d2.data_ptr(), p2.data_ptr(), Nq, n_way, d, st) == MMF_E_SHAPE
-    assert L.mmf_fewshot_dist_fwd(_p3(q3), P.data_ptr(), qf2.data_ptr(), None, p2.data_ptr(), Nq, n_way, d, st) == MMF_E_SHAPE
+    assert L.mmf_fewshot_dist_fwd(ptr3(q3), None, qf2.data_ptr(), d2.data_ptr(), p2.data_ptr(), Nq, n_way, d, st) == MMF_E_SHAPE
+    assert L.mmf_fewshot_dist_fwd(ptr3(q3), P.data_ptr(), qf2.data_ptr(), None, p2.data_ptr(), Nq, n_way, d, st) == MMF_E_SHAPE
     dq = _nan(Nq, d)
     assert L.mmf_fewshot_dist_bwd(qf.data_ptr(), P.data_ptr(), None, pred.data_ptr(), None, pred.data_ptr(), dq.data_ptr(),
                                   None, Nq, n_way, d, st) == MMF_E_SHAPE
     # misaligned feature rows
-    assert L.mmf_fewshot_proto_fwd(_p3([s3[0], src.data_ptr() + 4, s3[2]]), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d,
+    assert L.mmf_fewshot_proto_fwd(ptr3([s3[0], src.data_ptr() + 4, s3[2]]), sf.data_ptr(), mean.data_ptr(), n_way, n_shot, d,
                                    st) == MMF_E_ALIGN
     torch.cuda.synchronize()
     assert all(bool(t.isnan().all()) for t in (sf, mean, qf2, d2, p2, dq))
@@ -448,57 +430,11 @@ def test_step_updates_reached_parameters_only_and_queues_no_frozen_wgrad():
 def test_fewshot_step_graph_replay_matches_eager():
     """Three FewShotTrainStep steps (dropout and ModalityDropout on) captured as one single-chain graph and replayed,
     against three eager steps from the same state: loss, gradient arena, parameters."""
-    import bench
-    from mmfusion import ops
     from mmfusion.train import FewShotTrainStep
     model = _model(256, 4, dropout=0.1, modality_dropout=0.1)
     sup, qry, y = _episode_data(7, 5, 16)
     ts = FewShotTrainStep(model, 7, 5, lr=1e-3)
-    ar, opt = ts.arena, ts.opt
-    state = [ar.master_full, ar.shadow_full, ar.grads_full, opt.exp_avg, opt.exp_avg_sq, opt.step_dev, opt.hparams,
-             opt.gnorm_sq, ops.rng_state()]
-
-    def step():
-        return ts(_triple(sup), _triple(qry), y)
-
-    def restore(saved):
-        for x, v in zip(state, saved):
-            x.copy_(v)
-        torch.cuda.synchronize()
-
-    def trace(fn):
-        out = []
-        for _ in range(3):
-            loss = fn()
-            torch.cuda.synchronize()
-            out.append((float(loss.detach()), ar.grads.clone(), ar.master.clone()))
-        return out
-
-    s0 = [x.clone() for x in state]
-    with bench.single_stream():
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            static_loss = step()
-        restore(s0)
-        eager = trace(step)
-        restore(s0)
-        replay = trace(lambda: (g.replay(), static_loss)[1])
-    for k, ((le, ge, pe), (lr_, gr, pr)) in enumerate(zip(eager, replay)):
-        assert not bool(gr.isnan().any()) and not bool(pr.isnan().any()), f"step {k + 1}: NaN in the replayed step"
-        assert abs(le - lr_) <= 1e-6 * max(1.0, abs(le)), f"step {k + 1}: loss eager {le} vs replay {lr_}"
-        eg = float((ge - gr).abs().max()) / float(ge.abs().max())
-        ep = float((pe - pr).abs().max())
-        assert eg <= 1e-6, f"step {k + 1}: gradient arena differs by {eg:.3e} of its max"
-        assert ep <= 1e-6, f"step {k + 1}: parameters differ by {ep:.3e}"
-    assert len({e[0] for e in eager}) == 3
-    assert float((eager[-1][2] - s0[0][:ar.numel]).abs().max()) > 0
+    check_graph_replay_matches_eager(lambda: ts(_triple(sup), _triple(qry), y), ts.arena, ts.opt)
 
 
 def test_checkpoint_round_trip(tmp_path):

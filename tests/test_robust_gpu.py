@@ -2,27 +2,17 @@
 tests/robust_ref.py (per-element f32 error bounds, worst error reported as a fraction of its bound), their refusals, the
 head in the fp32 parity mode, the wrapper in eval mode against the plain base model, and ``mmfusion.train.RobustTrainStep``
 (gradients against the torch formulation of the head, which parameters it steps, graph replay, checkpoints)."""
-import ctypes as C
 
 import pytest
 import torch
 
-from helpers import l2_rel
+from helpers import check_graph_replay_matches_eager, hip_lib, l2_rel, ptr3, within_bound
 from robust_ref import head_bwd, head_fwd, torch_head
 
 pytestmark = pytest.mark.gpu
 
 MMF_E_SHAPE, MMF_E_ALIGN = -1, -3
 NAMES = ("text", "audio", "video")
-
-
-def _lib():
-    from mmfusion import lib
-    return lib.load(), lib.stream_ptr()
-
-
-def _p3(ts):
-    return (C.c_void_p * 3)(*[None if t is None else (t if isinstance(t, int) else t.data_ptr()) for t in ts])
 
 
 def _operands(B, d, Cn, seed):
@@ -37,41 +27,33 @@ def _operands(B, d, Cn, seed):
 
 
 def _fwd(f, h, W2, b2, Wm, bm, avail, B=None, d=None, Cn=None):
-    L, st = _lib()
+    L, st = hip_lib()
     B0, d0 = h.shape
     C0 = Wm[0].shape[0]
     a = torch.full((B0, 3), float("nan"), device="cuda")
     p = [torch.full((B0, C0), float("nan"), device="cuda") for _ in range(3)]
     wn = torch.full((B0, 3), float("nan"), device="cuda")
     y = torch.full((B0, C0), float("nan"), device="cuda")
-    rc = L.mmf_robust_head_fwd(_p3(f), h.data_ptr() if h is not None else None, W2.data_ptr(), b2.data_ptr(), _p3(Wm), _p3(bm),
-                               avail, a.data_ptr(), _p3(p), wn.data_ptr(), y.data_ptr(),
+    rc = L.mmf_robust_head_fwd(ptr3(f), h.data_ptr() if h is not None else None, W2.data_ptr(), b2.data_ptr(), ptr3(Wm), ptr3(bm),
+                               avail, a.data_ptr(), ptr3(p), wn.data_ptr(), y.data_ptr(),
                                B0 if B is None else B, d0 if d is None else d, C0 if Cn is None else Cn, st)
     return rc, a, p, wn, y
 
 
 def _bwd(f, h, W2, Wm, a, p, wn, avail, g, dP, dA, dN, want_df, want_dh, init, B=None, Cn=None):
-    L, st = _lib()
+    L, st = hip_lib()
     B0, d = h.shape
     C0 = Wm[0].shape[0]
     df = [torch.full((B0, d), float("nan"), device="cuda") if want_df[m] else None for m in range(3)]
     dh = torch.full((B0, d), float("nan"), device="cuda") if want_dh else None
     dW2, db2 = init["dW2"].clone(), init["db2"].clone()
     dWm, dbm = [x.clone() for x in init["dWm"]], [x.clone() for x in init["dbm"]]
-    rc = L.mmf_robust_head_bwd(_p3(f), h.data_ptr(), W2.data_ptr(), _p3(Wm), a.data_ptr(), _p3(p), wn.data_ptr(), avail,
-                               g.data_ptr() if g is not None else None, _p3(dP) if dP is not None else None,
+    rc = L.mmf_robust_head_bwd(ptr3(f), h.data_ptr(), W2.data_ptr(), ptr3(Wm), a.data_ptr(), ptr3(p), wn.data_ptr(), avail,
+                               g.data_ptr() if g is not None else None, ptr3(dP) if dP is not None else None,
                                dA.data_ptr() if dA is not None else None, dN.data_ptr() if dN is not None else None,
-                               _p3(df), dh.data_ptr() if dh is not None else None, dW2.data_ptr(), db2.data_ptr(),
-                               _p3(dWm), _p3(dbm), B0 if B is None else B, d, C0 if Cn is None else Cn, st)
+                               ptr3(df), dh.data_ptr() if dh is not None else None, dW2.data_ptr(), db2.data_ptr(),
+                               ptr3(dWm), ptr3(dbm), B0 if B is None else B, d, C0 if Cn is None else Cn, st)
     return rc, {"df": df, "dh": dh, "dW2": dW2, "db2": db2, "dWm": dWm, "dbm": dbm}
-
-
-def _within(got, want, bound, label, worst):
-    e = (got.double().cpu() - want).abs()
-    r = float((e / bound.clamp_min(1e-300)).max())
-    if r > worst[0]:
-        worst[0], worst[1] = r, label
-    assert bool((e <= bound).all()), f"{label}: error {float(e.max()):.3e}, worst / bound {r:.3f}"
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -94,11 +76,11 @@ def test_robust_head_kernels_against_float64():
                     torch.cuda.synchronize()
                     assert rc == 0, label
                     ref = head_fwd(f, h, W2, b2, Wm, bm, avail)
-                    _within(a, ref["a"], ref["ea"], label + " a", worst_f)
+                    within_bound(a, ref["a"], ref["ea"], label + " a", worst_f)
                     for m in range(3):
-                        _within(p[m], ref["p"][m], ref["ep"][m], label + f" p{m}", worst_f)
-                    _within(wn, ref["wn"], ref["ewn"], label + " wn", worst_f)
-                    _within(y, ref["y"], ref["ey"], label + " y", worst_f)
+                        within_bound(p[m], ref["p"][m], ref["ep"][m], label + f" p{m}", worst_f)
+                    within_bound(wn, ref["wn"], ref["ewn"], label + " wn", worst_f)
+                    within_bound(y, ref["y"], ref["ey"], label + " y", worst_f)
                     if avail >= 0:
                         n = bin(avail).count("1")
                         want = torch.tensor([[((avail >> i) & 1) / n if n else 0.0 for i in range(3)]], dtype=torch.float32)
@@ -122,16 +104,16 @@ def test_robust_head_kernels_against_float64():
                         U = 2.0 ** -24
                         for m in range(3):
                             if want_df[m]:
-                                _within(out["df"][m], rb["df"][m], rb["e_df"][m], lab + f" df{m}", worst_b)
+                                within_bound(out["df"][m], rb["df"][m], rb["e_df"][m], lab + f" df{m}", worst_b)
                             acc = init["dWm"][m].double().cpu() + rb["dWm"][m]
-                            _within(out["dWm"][m], acc, rb["e_dWm"][m] + U * acc.abs(), lab + f" dW{m}", worst_b)
+                            within_bound(out["dWm"][m], acc, rb["e_dWm"][m] + U * acc.abs(), lab + f" dW{m}", worst_b)
                             acc = init["dbm"][m].double().cpu() + rb["dbm"][m]
-                            _within(out["dbm"][m], acc, rb["e_dbm"][m] + U * acc.abs(), lab + f" db{m}", worst_b)
-                        _within(out["dh"], rb["dh"], rb["e_dh"], lab + " dh", worst_b)
+                            within_bound(out["dbm"][m], acc, rb["e_dbm"][m] + U * acc.abs(), lab + f" db{m}", worst_b)
+                        within_bound(out["dh"], rb["dh"], rb["e_dh"], lab + " dh", worst_b)
                         acc = init["dW2"].double().cpu() + rb["dW2"]
-                        _within(out["dW2"], acc, rb["e_dW2"] + U * acc.abs(), lab + " dW2", worst_b)
+                        within_bound(out["dW2"], acc, rb["e_dW2"] + U * acc.abs(), lab + " dW2", worst_b)
                         acc = init["db2"].double().cpu() + rb["db2"]
-                        _within(out["db2"], acc, rb["e_db2"] + U * acc.abs(), lab + " db2", worst_b)
+                        within_bound(out["db2"], acc, rb["e_db2"] + U * acc.abs(), lab + " db2", worst_b)
                         if avail >= 0 and dA is None:
                             assert not bool(out["dh"].any()), f"{lab}: a given mask sent gradient to the predictor"
                         cases += 1
@@ -172,25 +154,25 @@ def test_robust_head_refuses_bad_arguments():
         if case.get("W") == "mis":
             Ww = [Wm[0], big.data_ptr() + 8, Wm[2]]
         hh = None if "h" in case else h
-        L, st = _lib()
+        L, st = hip_lib()
         a = torch.full((B, 3), float("nan"), device="cuda")
         p = [torch.full((B, Cn), float("nan"), device="cuda") for _ in range(3)]
         wn = torch.full((B, 3), float("nan"), device="cuda")
         y = torch.full((B, Cn), float("nan"), device="cuda")
-        rc = L.mmf_robust_head_fwd(_p3(ff), hh.data_ptr() if hh is not None else None, W2.data_ptr(), b2.data_ptr(), _p3(Ww),
-                                   _p3(bm), case.get("avail", -1), a.data_ptr(), _p3(p), wn.data_ptr(), y.data_ptr(),
+        rc = L.mmf_robust_head_fwd(ptr3(ff), hh.data_ptr() if hh is not None else None, W2.data_ptr(), b2.data_ptr(), ptr3(Ww),
+                                   ptr3(bm), case.get("avail", -1), a.data_ptr(), ptr3(p), wn.data_ptr(), y.data_ptr(),
                                    case.get("B", B), case.get("d", d), case.get("Cn", Cn), st)
         torch.cuda.synchronize()
         assert rc == case["rc"], case
         assert all(bool(t.isnan().all()) for t in (a, *p, wn, y)), case
     # null outputs / biases in the forward
-    L, st = _lib()
+    L, st = hip_lib()
     for which in ("a", "y", "b2"):
         a, y = torch.full((B, 3), float("nan"), device="cuda"), torch.full((B, Cn), float("nan"), device="cuda")
         p = [torch.full((B, Cn), float("nan"), device="cuda") for _ in range(3)]
         wn = torch.full((B, 3), float("nan"), device="cuda")
-        rc = L.mmf_robust_head_fwd(_p3(f), h.data_ptr(), W2.data_ptr(), None if which == "b2" else b2.data_ptr(), _p3(Wm), _p3(bm),
-                                   -1, None if which == "a" else a.data_ptr(), _p3(p), wn.data_ptr(),
+        rc = L.mmf_robust_head_fwd(ptr3(f), h.data_ptr(), W2.data_ptr(), None if which == "b2" else b2.data_ptr(), ptr3(Wm), ptr3(bm),
+                                   -1, None if which == "a" else a.data_ptr(), ptr3(p), wn.data_ptr(),
                                    None if which == "y" else y.data_ptr(), B, d, Cn, st)
         torch.cuda.synchronize()
         assert rc == MMF_E_SHAPE and all(bool(t.isnan().all()) for t in (a, *p, wn, y)), which
@@ -211,9 +193,9 @@ def test_robust_head_refuses_bad_arguments():
     # a null parameter gradient is refused too
     dW2 = nan(3, d)
     dh = nan(B, d)
-    rc = L.mmf_robust_head_bwd(_p3(f), h.data_ptr(), W2.data_ptr(), _p3(Wm), a.data_ptr(), _p3(p), wn.data_ptr(), -1,
+    rc = L.mmf_robust_head_bwd(ptr3(f), h.data_ptr(), W2.data_ptr(), ptr3(Wm), a.data_ptr(), ptr3(p), wn.data_ptr(), -1,
                                g.data_ptr(), None, None, None, None, dh.data_ptr(), dW2.data_ptr(), None,
-                               _p3(init["dWm"]), _p3(init["dbm"]), B, d, Cn, st)
+                               ptr3(init["dWm"]), ptr3(init["dbm"]), B, d, Cn, st)
     torch.cuda.synchronize()
     assert rc == MMF_E_SHAPE and bool(dh.isnan().all()) and bool(dW2.isnan().all())
 
@@ -425,57 +407,11 @@ def test_step_updates_reached_parameters_only():
 def test_robust_step_graph_replay_matches_eager():
     """Three RobustTrainStep steps (missing_modalities=["audio"], dropout and ModalityDropout on) captured as one
     single-chain graph and replayed, against three eager steps from the same state: loss, gradient arena, parameters."""
-    import bench
-    from mmfusion import ops
     from mmfusion.train import RobustTrainStep
     model = _model(256, 4, dropout=0.1, modality_dropout=0.1)
     ti, au, vi, labels = _cuda_inputs(16)
     ts = RobustTrainStep(model, lr=1e-5, weight_decay=1e-2)
-    ar, opt = ts.arena, ts.opt
-    state = [ar.master_full, ar.shadow_full, ar.grads_full, opt.exp_avg, opt.exp_avg_sq, opt.step_dev, opt.hparams,
-             opt.gnorm_sq, ops.rng_state()]
-
-    def step():
-        return ts(ti, au, vi, labels, missing_modalities=["audio"])
-
-    def restore(saved):
-        for x, v in zip(state, saved):
-            x.copy_(v)
-        torch.cuda.synchronize()
-
-    def trace(fn):
-        out = []
-        for _ in range(3):
-            loss = fn()
-            torch.cuda.synchronize()
-            out.append((float(loss.detach()), ar.grads.clone(), ar.master.clone()))
-        return out
-
-    s0 = [x.clone() for x in state]
-    with bench.single_stream():
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            static_loss = step()
-        restore(s0)
-        eager = trace(step)
-        restore(s0)
-        replay = trace(lambda: (g.replay(), static_loss)[1])
-    for k, ((le, ge, pe), (lr_, gr, pr)) in enumerate(zip(eager, replay)):
-        assert not bool(gr.isnan().any()) and not bool(pr.isnan().any()), f"step {k + 1}: NaN in the replayed step"
-        assert abs(le - lr_) <= 1e-6 * max(1.0, abs(le)), f"step {k + 1}: loss eager {le} vs replay {lr_}"
-        eg = float((ge - gr).abs().max()) / float(ge.abs().max())
-        ep = float((pe - pr).abs().max())
-        assert eg <= 1e-6, f"step {k + 1}: gradient arena differs by {eg:.3e} of its max"
-        assert ep <= 1e-6, f"step {k + 1}: parameters differ by {ep:.3e}"
-    assert len({e[0] for e in eager}) == 3
-    assert float((eager[-1][2] - s0[0][:ar.numel]).abs().max()) > 0
+    check_graph_replay_matches_eager(lambda: ts(ti, au, vi, labels, missing_modalities=["audio"]), ts.arena, ts.opt)
 
 
 def test_checkpoint_round_trip(tmp_path):
