@@ -271,6 +271,32 @@ int mmf_fewshot_dist_bwd(const float* qf, const float* P, const float* dist, con
                          const float* gpred, float* dq, float* dp, int Nq, int n_way, int d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation metrics, one launch per batch (csrc/metrics.hip).  Replaces the per-batch tail of training/advanced_trainer.py:
+ * 209-263 (validate), :607-660 (evaluate_robustness) and evaluate_model.py:55-203 (evaluate_dataset): CrossEntropyLoss,
+ * softmax, argmax and the host copies behind sklearn.  Adds one batch to device-resident accumulators:
+ *   counts (int64, n_heads * C * C + 2):  [h][t][p] += #rows of head h with target t and prediction p  (row = target,
+ *                                         column = prediction; prediction = argmax with torch's rule: the lowest index
+ *                                         among equal maxima, the first NaN if the row holds one);
+ *                                         [n_heads C C] += #rows whose target is < 0 or >= C (never used as an index:
+ *                                         the caller raises), [n_heads C C + 1] += 1 (the batch count);
+ *   sums (f64, MMF_EVAL_NSUMS), head 0 only: [0] += mean_b CE_ls(logits[b], t[b]) (torch's label smoothing, rows with an
+ *                                         invalid target adding 0), [1] += sum_b pmax_b, [2] += sum_b pmax_b^2,
+ *                                         [3] += sum_b pmax_b over the rows predicted correctly;  pmax_b = max_c softmax_c.
+ * logits[h]: f32 (B, C) with row stride ld[h] >= C, h < n_heads <= MMF_EVAL_MAX_HEADS (the main head, then e.g. late
+ * fusion's text / audio / video logits); targets int64 (B).  Optional outputs (NULL: not written), rows row0 .. row0 + B - 1
+ * of caller buffers with `capacity` rows: pred_out int64 (head 0's argmax), target_out int64 (the targets as given),
+ * prob_out f32 dense (capacity, C) (head 0's softmax).  One workgroup, no atomics to global memory: the same inputs give
+ * the same bits on every run.  Refused, nothing launched: MMF_E_SHAPE for B <= 0, C outside 1..64, n_heads outside
+ * 1..MMF_EVAL_MAX_HEADS, a null operand, a row stride < C, label_smoothing outside [0, 1), output rows beyond capacity;
+ * MMF_E_ALIGN for logits / prob_out not 4-byte or targets / counts / sums / pred_out / target_out not 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define MMF_EVAL_MAX_HEADS 4
+#define MMF_EVAL_NSUMS 4
+int mmf_eval_accumulate(const float* const* logits, const int* ld, int n_heads, const int64_t* targets, int B, int C,
+                        float label_smoothing, int64_t* counts, double* sums, int64_t* pred_out, int64_t* target_out,
+                        float* prob_out, int64_t row0, int64_t capacity, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Grouped fused attention (flash-style: no (Tq,Tk) score matrix in HBM).
  * Replaces q*scale, QK^T, softmax, P.V of F.multi_head_attention_forward as called at
  * models/fusion_layers.py:161-163,204 (six cross blocks + three self blocks of MulT in ONE

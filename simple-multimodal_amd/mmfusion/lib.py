@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmfusion.so
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_BIAS, EPI_RELU, EPI_MASK_AUX, EPI_ADD_AUX, EPI_ACCUM, EPI_COLSUM_A, EPI_DROPOUT = 1, 2, 4, 8, 16, 32, 64
 GEMM_MAX_PROBLEMS, ATTN_MAX_PROBLEMS, LN_MAX_PROBLEMS, COLSUM_MAX_PROBLEMS = 48, 12, 8, 24
+EVAL_MAX_HEADS, EVAL_NSUMS = 4, 4
 
 # every symbol include/mmfusion.h declares (tests check the .so exports all of them)
 SYMBOLS = (
@@ -34,6 +35,7 @@ SYMBOLS = (
     "mmf_layernorm_f32_fwd", "mmf_layernorm_f32_bwd", "mmf_bilstm_workspace_bytes", "mmf_bilstm_layer_fwd", "mmf_bilstm_layer_bwd", "mmf_swap01",
     "mmf_distill_kl", "mmf_fusion_loss_kd", "mmf_robust_head_fwd", "mmf_robust_head_bwd",
     "mmf_fewshot_proto_fwd", "mmf_fewshot_proto_bwd", "mmf_fewshot_dist_fwd", "mmf_fewshot_dist_bwd",
+    "mmf_eval_accumulate",
 )
 
 
@@ -170,6 +172,7 @@ def load() -> C.CDLL:
     lib.mmf_fewshot_proto_bwd.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     lib.mmf_fewshot_dist_fwd.argtypes = [pp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mmf_fewshot_dist_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_eval_accumulate.argtypes = [pp, C.POINTER(C.c_int), i32, vp, i32, i32, f32, vp, vp, vp, vp, vp, i64, i64, vp]
     lib.mmf_skinny_linear_fwd_ex.argtypes = [C.POINTER(SkinnyProblemEx), i32, i32, i32, C.POINTER(SkinnyExtra), vp]
     lib.mmf_skinny_linear_dgrad_ex.argtypes = [C.POINTER(SkinnyProblemEx), i32, i32, f32, i32, C.POINTER(SkinnyExtra), vp]
     lib.mmf_sqnorm_f32.argtypes = [vp, i64, vp, vp]
