@@ -108,21 +108,33 @@ int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_problems, int 
  * one wave per SIMD with 128x128 wave tiles [gemm6.hip: any K for TN, K % 32 == 0 for NT / NN, no aux epilogue with f32 output];
  * 7 = generation 6 on persistent workgroups (below).  Automatic (gemm.hip auto_impl): 6 when the launch has 256x256 tiles for at
  * least half of the CUs (TN, wgrad) or a quarter of them (NT / NN) and generation 6 takes its shapes, else 2; a launch that
- * gets 6 is promoted to 7 whenever generation 7 takes it (MMF_GEMM_PERSIST=0: never).  A pinned generation is used for every
- * launch it takes; the others fall back 7 -> 6 -> 2.  Any other value (1 / 3 left in round 3, 4 / 5 in round 4) is refused
- * with MMF_E_UNSUPPORTED.  Results are identical up to f32 summation order (and, with a bias, one bf16 ulp between 6 and 7);
- * exists so that A/B timings can be interleaved inside one process.  A process-wide setting, not synchronised between threads. */
+ * gets 6 is promoted to 7 whenever generation 7 takes it (MMF_GEMM_PERSIST=0: never), whatever its tile count.  A pinned
+ * generation is used for every launch it takes; the others fall back 7 -> 6 -> 2.  Any other value (1 / 3 left in round 3, 4 / 5
+ * in round 4) is refused with MMF_E_UNSUPPORTED.  Results are identical up to f32 summation order (and, with a bias, one bf16 ulp
+ * between 6 and 7); exists so that A/B timings can be interleaved inside one process.  A process-wide setting, not synchronised
+ * between threads. */
 int mmf_gemm_select_impl(int impl);
 /* the kernel generation the calling thread's last mmf_gemm_grouped[_ex] call dispatched to (profiling labels) */
 int mmf_gemm_last_impl(void);
-/* Round 4, generation 7 (gemm7.hip): generation 6's tile on PERSISTENT workgroups — one per CU, each walking the tiles w, w + grid,
- * ... of the launch with its LDS ring running on across tile boundaries (no ring fill and no idle matrix pipe between tiles).  NT /
- * NN with bf16 output, K % 32 == 0, K >= 160, N and the leading dimensions of C / aux multiples of 8, and the flag sets of the
- * fusion step.  Bit-identical to generation 6 without a bias; with one the accumulators start from the bias, so outputs may
- * differ by one bf16 ulp.
+/* Generation 7 (gemm7.hip): generation 6's tile on PERSISTENT workgroups — one per CU, each walking the tiles w, w + grid, ... of
+ * the launch with its LDS ring running on across tile boundaries (no ring fill and no idle matrix pipe between tiles).  NT / NN
+ * with bf16 output, K % 32 == 0, K >= 160, N and the leading dimensions of C / aux multiples of 8, a 16-byte aligned aux, and the
+ * flag sets of the fusion step.  Without a bias bit-identical to generation 6; with one the accumulators start from the bias, so
+ * outputs may differ from generation 6 by one bf16 ulp on a small fraction of the elements.
+ * Tile width: 256 x 256 or 256 x 192, per launch.  Automatic: 192 exactly when the launch's makespan — the longest workgroup's
+ * sum of K x width over the tiles the persistent walk gives it — is strictly shorter at 192 than at 256.  Both widths give every
+ * output element the same MFMA chain: the results are bit-identical between them.
  * mmf_gemm_set_persistent_workgroups(n): grid size of generation 7 (0 = the CU count [default]); a test / tuning hook: with a
- * small n a small problem exercises many tiles per workgroup.  Process-wide, not synchronised between threads. */
+ * small n a small problem exercises many tiles per workgroup.
+ * mmf_gemm7_set_tile_n(n): tile width of every generation-7 launch (0 = automatic [default], 256, 192); a test / tuning hook.
+ * Both hooks are process-wide and not synchronised between threads. */
 int mmf_gemm_set_persistent_workgroups(int n);
+int mmf_gemm7_set_tile_n(int n);
+/* the tile width (256 / 192) of the calling thread's last generation-7 launch */
+int mmf_gemm7_last_tile_n(void);
+/* the width the automatic rule gives a launch of these problems on `workgroups` persistent workgroups (0 = the grid the launch
+ * would get); host only, launches nothing */
+int mmf_gemm7_tile_n(const mmf_gemm_problem* problems, int num_problems, int workgroups);
 
 /* ------------------------------------------------------------------------------------------
  * Skinny-M linear layers (1 <= M <= 64 rows): the (B, d) MLPs of the Early / Contrastive / Adaptive /

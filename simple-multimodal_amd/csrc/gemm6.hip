@@ -105,8 +105,10 @@ __device__ __forceinline__ void gemm6_body(const GemmArgs& args, const int total
       __builtin_amdgcn_sched_barrier(0);
       return;
     }
-    if (I < PPO) asm volatile("s_add_i32 m0, %0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(ring_base), "v"(voff[I]), "s"(dA), "n"(OFF) : "memory");
-    else         asm volatile("s_add_i32 m0, %0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(ring_base), "v"(voff[I]), "s"(dB), "n"(OFF) : "memory");
+    // (M0, which the LDS-DMA reads, as the statement's output: a clobber of a reserved register is not honoured by the compiler)
+    int m0w;
+    if (I < PPO) asm volatile("s_add_i32 %0, %1, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds" : "={m0}"(m0w) : "s"(ring_base), "v"(voff[I]), "s"(dA), "n"(OFF) : "memory");
+    else         asm volatile("s_add_i32 %0, %1, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds" : "={m0}"(m0w) : "s"(ring_base), "v"(voff[I]), "s"(dB), "n"(OFF) : "memory");
     __builtin_amdgcn_sched_barrier(0);
   };
 

@@ -41,11 +41,13 @@ __device__ __forceinline__ u32x2_t lds_read_tr(unsigned addr) {
   return r;
 }
 
-// One operand's four fragments of a k-substep.  KC: lane (r = l & 31, h = l >> 5) reads chunk 2 G + h of tile row 32 D + r;
-// KR: two transposed reads give it rows 16 G + 8 h + 0..7 of tile column 32 D + r (the standard MFMA k order).
-template <bool KR> struct Frag4;
-template <> struct Frag4<false> {
-  u32x4_t v[4];
+// One operand's NF fragments of a k-substep (4: a 128-row / 128-column wave quadrant; 3: gemm7's 96-column n-operand).  KC: lane
+// (r = l & 31, h = l >> 5) reads chunk 2 G + h of tile row 32 D + r; KR: two transposed reads give it rows 16 G + 8 h + 0..7 of tile
+// column 32 D + r (the standard MFMA k order).
+template <bool KR, int NF = 4> struct Frag4;
+template <int NF> struct Frag4<false, NF> {
+  static_assert(NF == 3 || NF == 4, "three or four fragments");
+  u32x4_t v[NF];
   // lane parts of the address for even / odd G
   static __device__ __forceinline__ void lane_parts(int W, int lane, unsigned& a0, unsigned& a1) {
     const int r = lane & 31, h = lane >> 5, s = (r >> 2) & 3;
@@ -60,7 +62,7 @@ template <> struct Frag4<false> {
     v[0] = lds_read_b128<S * (D0 + 0) + 512 * (G >> 1)>(t);
     v[1] = lds_read_b128<S * (D0 + 1) + 512 * (G >> 1)>(t);
     v[2] = lds_read_b128<S * (D0 + 2) + 512 * (G >> 1)>(t);
-    v[3] = lds_read_b128<S * (D0 + 3) + 512 * (G >> 1)>(t);
+    if constexpr (NF > 3) v[3] = lds_read_b128<S * (D0 + 3) + 512 * (G >> 1)>(t);
   }
   template <int W, int G, int D0, int I>
   __device__ __forceinline__ void issue1(unsigned t0, unsigned t1) {
@@ -68,24 +70,27 @@ template <> struct Frag4<false> {
   }
   __device__ __forceinline__ bf16x8_t get(int i) const { return __builtin_bit_cast(bf16x8_t, v[i]); }
 };
-template <> struct Frag4<true> {
-  u32x2_t lo[4], hi[4];
-  static __device__ __forceinline__ void lane_parts(int, int lane, unsigned& a0, unsigned& a1) {
+// KR tiles are [BK][W]: 8 tile rows are (W / 32) * 512 bytes (4096 at W = 256, 3072 at gemm7's W = 192)
+template <int NF> struct Frag4<true, NF> {
+  static_assert(NF == 3 || NF == 4, "three or four fragments");
+  u32x2_t lo[NF], hi[NF];
+  static __device__ __forceinline__ void lane_parts(int W, int lane, unsigned& a0, unsigned& a1) {
     const int h = lane >> 5, g = (lane >> 4) & 1, q = (lane >> 2) & 3, p = lane & 3;
-    const unsigned c = (unsigned)(2 * g + (p >> 1));
-    a0 = (unsigned)(4096 * h + 64 * q) + 16u * (c ^ (unsigned)(2 * h)) + 8u * (unsigned)(p & 1);
-    a1 = (unsigned)(4096 * h + 64 * (4 + q)) + 16u * (c ^ (unsigned)(2 * h + 1)) + 8u * (unsigned)(p & 1);
+    const unsigned c = (unsigned)(2 * g + (p >> 1)), r8 = (unsigned)((W / 32) * 512);
+    a0 = r8 * (unsigned)h + (unsigned)(64 * q) + 16u * (c ^ (unsigned)(2 * h)) + 8u * (unsigned)(p & 1);
+    a1 = r8 * (unsigned)h + (unsigned)(64 * (4 + q)) + 16u * (c ^ (unsigned)(2 * h + 1)) + 8u * (unsigned)(p & 1);
   }
   template <int W, int G, int D0>
   __device__ __forceinline__ void issue(unsigned t0, unsigned t1) {          // t0 / t1: tile base + lane part of the lo / hi read
-    lo[0] = lds_read_tr<8192 * G + 512 * (D0 + 0)>(t0); hi[0] = lds_read_tr<8192 * G + 512 * (D0 + 0)>(t1);
-    lo[1] = lds_read_tr<8192 * G + 512 * (D0 + 1)>(t0); hi[1] = lds_read_tr<8192 * G + 512 * (D0 + 1)>(t1);
-    lo[2] = lds_read_tr<8192 * G + 512 * (D0 + 2)>(t0); hi[2] = lds_read_tr<8192 * G + 512 * (D0 + 2)>(t1);
-    lo[3] = lds_read_tr<8192 * G + 512 * (D0 + 3)>(t0); hi[3] = lds_read_tr<8192 * G + 512 * (D0 + 3)>(t1);
+    constexpr int R16 = (W / 32) * 1024 * G;                                 // 16 tile rows per G
+    lo[0] = lds_read_tr<R16 + 512 * (D0 + 0)>(t0); hi[0] = lds_read_tr<R16 + 512 * (D0 + 0)>(t1);
+    lo[1] = lds_read_tr<R16 + 512 * (D0 + 1)>(t0); hi[1] = lds_read_tr<R16 + 512 * (D0 + 1)>(t1);
+    lo[2] = lds_read_tr<R16 + 512 * (D0 + 2)>(t0); hi[2] = lds_read_tr<R16 + 512 * (D0 + 2)>(t1);
+    if constexpr (NF > 3) { lo[3] = lds_read_tr<R16 + 512 * (D0 + 3)>(t0); hi[3] = lds_read_tr<R16 + 512 * (D0 + 3)>(t1); }
   }
   template <int W, int G, int D0, int I>
   __device__ __forceinline__ void issue1(unsigned t0, unsigned t1) {
-    lo[I] = lds_read_tr<8192 * G + 512 * (D0 + I)>(t0); hi[I] = lds_read_tr<8192 * G + 512 * (D0 + I)>(t1);
+    lo[I] = lds_read_tr<(W / 32) * 1024 * G + 512 * (D0 + I)>(t0); hi[I] = lds_read_tr<(W / 32) * 1024 * G + 512 * (D0 + I)>(t1);
   }
   __device__ __forceinline__ bf16x8_t get(int i) const {
     const u32x4_t w = {lo[i][0], lo[i][1], hi[i][0], hi[i][1]};
@@ -104,19 +109,30 @@ __device__ __forceinline__ void frag_wait(Frag4<true>& a, Frag4<true>& b) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.lo[0]), "+v"(a.lo[1]), "+v"(a.lo[2]), "+v"(a.lo[3]), "+v"(a.hi[0]), "+v"(a.hi[1]), "+v"(a.hi[2]), "+v"(a.hi[3]),
                "+v"(b.lo[0]), "+v"(b.lo[1]), "+v"(b.lo[2]), "+v"(b.lo[3]), "+v"(b.hi[0]), "+v"(b.hi[1]), "+v"(b.hi[2]), "+v"(b.hi[3]));
 }
+// (gemm7's 96-column form: three n-fragments)
+__device__ __forceinline__ void frag_wait(Frag4<false>& a, Frag4<false, 3>& b) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(a.v[3]), "+v"(b.v[0]), "+v"(b.v[1]), "+v"(b.v[2]));
+}
+__device__ __forceinline__ void frag_wait(Frag4<false>& a, Frag4<true, 3>& b) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(a.v[3]), "+v"(b.lo[0]), "+v"(b.lo[1]), "+v"(b.lo[2]),
+               "+v"(b.hi[0]), "+v"(b.hi[1]), "+v"(b.hi[2]));
+}
 
-// per-lane source offset (bytes, relative to the operand tile's first element at k = 0) of 1-KiB piece p: the inverse of the image
-template <bool KR, int BK>
+// per-lane source offset (bytes, relative to the operand tile's first element at k = 0) of 1-KiB piece p: the inverse of the image.
+// W: a KR tile's width (its n or m extent: 256, or 192 for gemm7's 96-column form)
+template <bool KR, int BK, int W = 256>
 __device__ __forceinline__ unsigned piece_voff(int p, int ld, int lane) {
-  constexpr int NC = (KR ? 256 : BK) / 32;
+  constexpr int NC = (KR ? W : BK) / 32;
   const int st = 2 * p + (lane >> 5), rg = st / NC, cc = st % NC;
   const int w = lane & 31, row = 8 * rg + (w >> 2), ch = 4 * cc + ((w & 3) ^ ((row >> 2) & 3));
   return (unsigned)(row * ld * 2 + ch * 16);
 }
 
-// tile t of problem P -> (m0, n0): super-rows of 8 m-tiles, n fastest across a super-row (gemm4.hip)
+// tile t of problem P -> (m0, n0): super-rows of 8 m-tiles, n fastest across a super-row (gemm4.hip).  TBN: the tile width (gemm7:
+// 256 or 192)
+template <int TBN = BN>
 __device__ __forceinline__ void tile_origin(const mmf_gemm_problem& P, const int t, int& m0, int& n0) {
-  const int tiles_m = (P.M + BM - 1) / BM, tiles_n = (P.N + BN - 1) / BN;
+  const int tiles_m = (P.M + BM - 1) / BM, tiles_n = (P.N + TBN - 1) / TBN;
   // super-rows of 8 m-tiles.  (Round 4 tried the height that makes an XCD's 32 concurrent tiles touch the fewest operand panels — 32 / tiles_n
   // for narrow outputs, 11 x 3 instead of 8 x 3 + 8 x 1 at N = 768: the step got SLOWER, 2.027 -> 2.052 ms same box.)  MMF_GEMM_GROUPM
   // (build-time) pins another height for A/Bs.
@@ -128,7 +144,7 @@ __device__ __forceinline__ void tile_origin(const mmf_gemm_problem& P, const int
   const int grp = t / (GROUP_M * tiles_n), rem = t % (GROUP_M * tiles_n);
   const int gm = min(GROUP_M, tiles_m - grp * GROUP_M);
   m0 = (grp * GROUP_M + rem % gm) * BM;
-  n0 = (rem / gm) * BN;
+  n0 = (rem / gm) * TBN;
 }
 
 // epilogue: lane owns C[m][n .. n+3] for m = m_base + 32 tm + (l & 31), n = n_base + 32 tn + 8 g + 4 (l >> 5).

@@ -14,13 +14,26 @@
 //     hand-overs keep their piece-only vmcnt counts: with stores in flight they wait for MORE than they need, never for less —
 //     vmcnt counts loads and stores together) and drain under the next tile's k-loop.
 // NT and NN, bf16 output, every K a multiple of 32 and >= (NS + 1) * 32; everything else stays on gemm6 (gemm.hip).
+//
+// Two tile widths (TN: n-fragments per wave).  TN = 4 is gemm6's 256 x 256 tile (wave tile 128 x 128); TN = 3 a 256 x 192 tile (wave
+// tile 128 x 96).  Every N of the fusion step is a multiple of 768 = 3 x 256 = 4 x 192, and a launch of 354 tiles on 256 CUs ends on a
+// round of 98 tiles with 158 CUs idle; at 192 the same launch is 472 tiles of three quarters the work.  The host (pick_tile_n) takes
+// the narrower form only where the walk's makespan is strictly shorter.  Both forms give every output element the same MFMA chain
+// (bias start, then the k-substeps in order) and no K split: the results are bit-identical.
 #include <algorithm>
+#include <vector>
 #include "gemm6_parts.h"
 
 namespace {
 
 constexpr int BK = 32, NS = 4;
-constexpr int TILE = 256 * BK * 2, STAGE = 2 * TILE, PPO = BK / 8, PPW = 2 * PPO;   // 16 KiB per operand tile, 8 pieces per wave and stage
+constexpr int TILE = 256 * BK * 2, PPO = BK / 8;             // the m-operand tile: 16 KiB, 4 pieces per wave and stage
+// the n-operand tile of the TN form: TN * 64 columns, TN * 4 KiB (TN pieces per wave); a stage holds both tiles
+template <int TN> struct Form {
+  static constexpr int BNT = 64 * TN, TILE_B = BNT * BK * 2, STAGE = TILE + TILE_B, PPB = TN, PPW = PPO + PPB;
+  static constexpr int LDS = NS * STAGE + 4 * 8192;          // the ring and the four waves' output staging regions
+};
+static_assert(Form<4>::LDS == 160 * 1024 && Form<3>::LDS == 144 * 1024, "LDS of the two forms");
 
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
@@ -49,14 +62,14 @@ __device__ __forceinline__ int to_sgpr(int x) {
   return r;
 }
 
-template <bool B_KR>
+template <bool B_KR, int TN>
 __device__ __forceinline__ void locate_tile(const GemmArgs& args, const int total_tiles, const int orig, TileSrc& s, TileDst& d, int& lda, int& ldb) {
   const int bid = to_sgpr(mmf_xcd_tile(orig, total_tiles, args.xcd_granule));
   int pi = 0;
   while (pi + 1 < args.nprob && bid >= args.tile_start[pi + 1]) ++pi;
   const mmf_gemm_problem& P = args.p[pi];
   int m0, n0;
-  tile_origin(P, bid - args.tile_start[pi], m0, n0);
+  tile_origin<Form<TN>::BNT>(P, bid - args.tile_start[pi], m0, n0);
   m0 = to_sgpr(m0);
   n0 = to_sgpr(n0);
   d.pi = pi; d.m0 = m0; d.n0 = n0;
@@ -83,10 +96,11 @@ __device__ __forceinline__ void locate_tile(const GemmArgs& args, const int tota
 //        stores of 4 rows x 256 B.
 // LDS operations of one wave execute in order, so the region needs no barrier and no wait between a write and the read behind it.
 // CT: the epilogue's flag set (compile time; alpha = 1, no dropout).  The bias is not added here: it is what the tile's accumulators
-// START from (bias_init below).
-template <int CT>
+// START from (bias_init below).  TN = 3: the wave tile is 96 columns, 12 of a row's 16 chunks; the lanes of chunks 12..15 get the
+// out-of-range offset (their aux loads read zeros into region chunks nobody reads back, their stores are dropped).
+template <int CT, int TN>
 __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, const mmf_gemm_problem& P, const int mb, const int nb,
-                                           f32x16_t (&acc)[4][4], char* region, const int lane) {
+                                           f32x16_t (&acc)[TN][4], char* region, const int lane) {
   constexpr bool AUX = (CT & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX)) != 0;
   constexpr bool DROP = (CT & MMF_EPI_DROPOUT) != 0;
   // dropout on the (activated) outputs, the mask of gemm6's epilogue: element m * N + n of the caller's problem `orig[pi]`
@@ -101,7 +115,7 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
   auto row_at = [&](int it) { return region + it * 1024 + (rd_base ^ (unsigned)((it & 3) << 6)); };
   // global side: lane's column chunk is fixed (8 bf16 at nb + 8 cq), its row walks 32 tm + 4 it + q.  Range-checked buffer accesses
   // against [base, last valid element]: rows past M fall outside; columns past N get an out-of-range offset.
-  const bool col_ok = nb + 8 * cq < P.N;
+  const bool col_ok = cq < 4 * TN && nb + 8 * cq < P.N;
   const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(P.C, 0, (int)((((long)P.M - 1) * P.ldc + P.N) * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(AUX ? P.aux : P.C), 0,
                                                                        AUX ? (int)((((long)P.M - 1) * P.ldaux + P.N) * 2) : 0, 0x00020000);
@@ -120,12 +134,12 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
   // head and spills what it cannot hold — accumulators included)
 #pragma unroll
   for (int tm = 0; tm < 4; ++tm) {
-    u32x2_t axv[4][4];
+    u32x2_t axv[TN][4];
     if constexpr (AUX) {
 #pragma unroll
       for (int it = 0; it < 8; ++it) *reinterpret_cast<u32x4_t*>(row_at(it)) = auxr[tm & 1][it];
 #pragma unroll
-      for (int tn = 0; tn < 4; ++tn)
+      for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
         for (int g = 0; g < 4; ++g) axv[tn][g] = *reinterpret_cast<const u32x2_t*>(acc_at(4 * tn + g));
       __builtin_amdgcn_sched_barrier(0);
@@ -133,7 +147,7 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
+    for (int tn = 0; tn < TN; ++tn) {
       // (the tile passes through an opaque statement HERE: its sixteen accumulator reads cannot be hoisted to the head of the drain,
       // where hipcc otherwise reads 160-250 accumulator registers into vector registers at once and spills the aux pieces in flight)
       asm volatile("" : "+a"(acc[tn][tm]));
@@ -184,14 +198,16 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
 //     the instruction stream (and in the hand-overs' counts) but touch no memory — the range check answers them with zeros;
 //   * the ring fill fetches NS - 1 stages and the late half of the NS-th, so the very first stage already finds its early pieces
 //     to issue.
-template <bool B_KR, int CT>
+template <bool B_KR, int CT, int TN>
 __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total_tiles, char* smem) {
   constexpr bool A_KR = false;
-  constexpr int WA = BK, WB = B_KR ? 256 : BK;
+  using F = Form<TN>;
+  constexpr int BNT = F::BNT, STAGE = F::STAGE, PPW = F::PPW, NMF = 4 * TN, NRD = 4 + TN;   // MFMAs / fragment reads per k-substep
+  constexpr int WA = BK, WB = B_KR ? BNT : BK;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;                   // this wave's 128 x 128 quadrant
+  const int wm = wave >> 1, wn = wave & 1;                   // this wave's 128 x (32 TN) part of the tile
   const int nwg = gridDim.x;
   // The walk: round r hands ids r * nwg .. to the workgroups in ascending order when r is even and in DESCENDING order when it is odd.
   // The host sorts the problems by K, longest first, so ids run from the longest tiles to the shortest; the snake gives whoever got the
@@ -205,17 +221,17 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   TileSrc ns;
   TileDst cd, nd;
   int KT, lda, ldb;
-  locate_tile<B_KR>(args, total_tiles, orig, ns, cd, lda, ldb);
+  locate_tile<B_KR, TN>(args, total_tiles, orig, ns, cd, lda, ldb);
   KT = ns.KT;
 
-  // ---- LDS-DMA: this wave's PPW pieces of a stage, per-lane source offsets for the tile being FETCHED -----------------------------
+  // ---- LDS-DMA: this wave's PPW pieces of a stage (PPO of the m-operand, TN of the n-operand), per-lane source offsets for the tile
+  // being FETCHED ----------------------------------------------------------------------------------------------------------------------
   unsigned voff[PPW], voffn[PPW];
   auto set_voff = [&](unsigned (&v)[PPW], int la, int lb) {
 #pragma unroll
-    for (int i = 0; i < PPO; ++i) {
-      v[i] = piece_voff<A_KR, BK>(wave + 4 * i, la, lane);
-      v[PPO + i] = piece_voff<B_KR, BK>(wave + 4 * i, lb, lane);
-    }
+    for (int i = 0; i < PPO; ++i) v[i] = piece_voff<A_KR, BK>(wave + 4 * i, la, lane);
+#pragma unroll
+    for (int i = 0; i < TN; ++i) v[PPO + i] = piece_voff<B_KR, BK, BNT>(wave + 4 * i, lb, lane);
   };
   set_voff(voff, lda, ldb);
   char* const my_pieces = smem + wave * 1024;
@@ -246,7 +262,11 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     constexpr int I = decltype(ic)::value, OFF = I < PPO ? I * 4096 : TILE + (I - PPO) * 4096;
     const Desc& d = I < PPO ? dA : dB;
     const i32x4_t q = {d.lo, d.hi, d.rec, 0x00020000};
-    asm volatile("s_add_i32 m0, %0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(ring_base), "v"(voff[I]), "s"(q), "n"(OFF) : "memory");
+    // M0 (which the LDS-DMA reads) is the statement's output: a clobber of a reserved register is not honoured by the compiler.  One
+    // wait state between the M0 write and the LDS-DMA that reads it, the s_nop (the hardware does not interlock them); it does not
+    // depend on the number of pieces per stage.
+    int m0w;
+    asm volatile("s_add_i32 %0, %1, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds" : "={m0}"(m0w) : "s"(ring_base), "v"(voff[I]), "s"(q), "n"(OFF) : "memory");
     __builtin_amdgcn_sched_barrier(0);
   };
 
@@ -259,7 +279,8 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     hot_piece(std::integral_constant<int, 2>{}, rb); hot_piece(std::integral_constant<int, 3>{}, rb);
     if (s + 1 < NS) {
       hot_piece(std::integral_constant<int, 4>{}, rb); hot_piece(std::integral_constant<int, 5>{}, rb);
-      hot_piece(std::integral_constant<int, 6>{}, rb); hot_piece(std::integral_constant<int, 7>{}, rb);
+      hot_piece(std::integral_constant<int, 6>{}, rb);
+      if constexpr (TN == 4) hot_piece(std::integral_constant<int, 7>{}, rb);
       advance(dA, stepA); advance(dB, stepB);                // afterwards: stage NS - 1, the one being fetched
     }
   }
@@ -268,7 +289,7 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   nd = cd;
   if (has_next) {
     int la, lb;
-    locate_tile<B_KR>(args, total_tiles, walk(1), ns, nd, la, lb);
+    locate_tile<B_KR, TN>(args, total_tiles, walk(1), ns, nd, la, lb);
     set_voff(voffn, la, lb);
   } else {
     ns.recA = 0; ns.recB = 0; ns.stepB = 0;
@@ -282,26 +303,26 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   Frag4<B_KR>::lane_parts(WB, lane, lb0, lb1);
   const unsigned smem_base = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
   const unsigned qa = (unsigned)((WA / 32) * 2048 * 4 * wm);
-  const unsigned qb = (unsigned)(B_KR ? 512 * 4 * wn : (WB / 32) * 2048 * 4 * wn);
+  const unsigned qb = (unsigned)(B_KR ? 512 * TN * wn : (WB / 32) * 2048 * TN * wn);   // column blocks / row blocks TN wn ..
   la0 += smem_base + qa; la1 += smem_base + qa;
   lb0 += smem_base + TILE + qb; lb1 += smem_base + TILE + qb;
 
-  f32x16_t acc[4][4];                 // [tn][tm]; set to the bias (or to zero) by bias_init in front of every tile
+  f32x16_t acc[TN][4];                // [tn][tm]; set to the bias (or to zero) by bias_init in front of every tile
 
   // Bias.  In the accumulator layout a lane would hold 64 bias values per tile (columns nb + 32 tn + 8 g + 4 h + e) through the
   // drain, on top of the aux pieces in flight: with them the drain spills.  Instead the tile's accumulators START from the bias: lane
   // r keeps ONE value per 32-column block tn (bias[nb + 32 tn + r], loaded a tile ahead: at the head of the previous tile's drain) and
-  // sixteen MFMAs spread them as outer products with a ones fragment,
+  // 4 TN MFMAs spread them as outer products with a ones fragment,
   //     D[n][m] = sum_k A[n][k] B[k][m],  A[n][0..2] = the exact three-way bf16 split of bias[n],  B[0..2][m] = 1
   // (exact in f32: 8 + 8 + 8 mantissa bits; attention2.hip does the same with its row statistics).  16 of a K = 768 tile's 784 MFMAs.
   constexpr bool use_bias = (CT & MMF_EPI_BIAS) != 0;
-  float bcur[4] = {0.f, 0.f, 0.f, 0.f};
-  auto load_bias = [&](float (&b)[4], const TileDst& d) {
+  float bcur[TN] = {};
+  auto load_bias = [&](float (&b)[TN], const TileDst& d) {
     const mmf_gemm_problem& P = args.p[d.pi];
     const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.bias), 0, P.N * 4, 0x00020000);
-    const unsigned off = (unsigned)((d.n0 + 128 * wn + (lane & 31)) * 4);
+    const unsigned off = (unsigned)((d.n0 + 32 * TN * wn + (lane & 31)) * 4);
 #pragma unroll
-    for (int tn = 0; tn < 4; ++tn)                              // (the builtin returns the 32 bits as an integer)   past N: 0
+    for (int tn = 0; tn < TN; ++tn)                              // (the builtin returns the 32 bits as an integer)   past N: 0
       b[tn] = __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b32(brs, off + (unsigned)(32 * tn * 4), 0, 0));
   };
   auto split3 = [&](float x) {
@@ -314,16 +335,16 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     const u32x4_t w = {lo ? ((hh >> 16) | mm) : 0u, lo ? (ll >> 16) : 0u, 0u, 0u};
     return __builtin_bit_cast(bf16x8_t, w);
   };
-  auto bias_init = [&](const float (&b)[4]) {
+  auto bias_init = [&](const float (&b)[TN]) {
     const f32x16_t zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const u32x4_t ow = {lane < 32 ? 0x3f803f80u : 0u, lane < 32 ? 0x00003f80u : 0u, 0u, 0u};
-    // one opaque copy of the ones fragment per row block: sixteen MFMAs with the same operands would be merged into four (or, without
+    // one opaque copy of the ones fragment per row block: 4 TN MFMAs with the same operands would be merged into four (or, without
     // a bias, into ONE) and their results copied into the other accumulator tiles register by register
     u32x4_t ones[4] = {ow, ow, ow, ow};
 #pragma unroll
     for (int tm = 0; tm < 4; ++tm) asm volatile("" : "+v"(ones[tm]));
 #pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
+    for (int tn = 0; tn < TN; ++tn) {
       u32x4_t bw = __builtin_bit_cast(u32x4_t, use_bias ? split3(b[tn]) : __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u}));
       asm volatile("" : "+v"(bw));
 #pragma unroll
@@ -335,16 +356,28 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   };
   if constexpr (use_bias) load_bias(bcur, cd);
 
-  vm_wait<PPW * (NS - 2) + 4>();      // stage 0 landed (with the bias loads behind the pieces this waits for more: once per workgroup)
+  // The vmcnt counts (hand-counted: the pieces are inline asm, the compiler counts none of them).  Per wave a stage is PPW = 4 + TN
+  // pieces: PPO = 4 "late" ones of the m-operand and TN "early" ones of the n-operand (8 at TN = 4, 7 at TN = 3).  In issue order:
+  //   ring fill:        stages 0 .. NS - 2 whole (PPW each), then the late PPO of stage NS - 1;
+  //   stage g, step 0:  the early TN of stage g + NS - 1;     stage g, step 1 behind the hand-over: the late PPO of stage g + NS.
+  // First wait, stage 0 complete: younger than its last piece are stages 1 .. NS - 2 and the late part of NS - 1,
+  //   PPW * (NS - 2) + PPO  (20 at TN = 4, 18 at TN = 3).
+  // Hand-over in stage g (needs stage g + 1): the last piece of stage g + 1 is its early part, issued in step 0 of stage g - NS + 2 (in
+  // the ring fill while that is negative).  Younger, up to the hand-over in step 1 of stage g: the late parts of stages g + 2 ..
+  // g + NS - 1 and their early parts, NS - 2 of each,
+  //   (NS - 2) * (PPO + TN) = PPW * (NS - 2)  (16 at TN = 4, 14 at TN = 3).
+  // Anything else the wave issues (bias, aux loads and stores of a drain) is younger than the pieces it is counted with: the wait
+  // then covers more than it needs, never less.
+  vm_wait<PPW * (NS - 2) + PPO>();    // stage 0 landed (with the bias loads behind the pieces this waits for more: once per workgroup)
   __builtin_amdgcn_s_barrier();
   Frag4<A_KR> fa[2];
-  Frag4<B_KR> fb[2];
+  Frag4<B_KR, TN> fb[2];
   fa[0].template issue<WA, 0, 0>(la0, la1);
   fb[0].template issue<WB, 0, 0>(lb0, lb1);
   frag_wait(fa[0], fb[0]);
 
-  auto mf = [&](const Frag4<A_KR>& a, const Frag4<B_KR>& b, int i) {
-    const int tm = i >> 2, tn = i & 3;
+  auto mf = [&](const Frag4<A_KR>& a, const Frag4<B_KR, TN>& b, int i) {
+    const int tm = i / TN, tn = i % TN;
     acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b.get(tn), a.get(tm), acc[tn][tm], 0, 0, 0);
     // an empty statement that "uses" the tile: the MFMA builtin has no side effect, and in this kernel instruction selection sank the
     // sixteen MFMAs of a substep below the reads and pieces that are written between them (each down to its next use, the same
@@ -361,11 +394,11 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     if ((u) == 4) dstB.template issue1<WB, G, 0, 0>(lb0 + (so), lb1 + (so));                            \
     if ((u) == 5) dstB.template issue1<WB, G, 0, 1>(lb0 + (so), lb1 + (so));                            \
     if ((u) == 6) dstB.template issue1<WB, G, 0, 2>(lb0 + (so), lb1 + (so));                            \
-    if ((u) == 7) dstB.template issue1<WB, G, 0, 3>(lb0 + (so), lb1 + (so));                            \
+    if constexpr (TN == 4) { if ((u) == 7) dstB.template issue1<WB, G, 0, TN - 1>(lb0 + (so), lb1 + (so)); } \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
   } while (0)
 
-  // One stage (gemm6.hip's schedule, BK = 32: two k-substeps of sixteen MFMAs).  g: the workgroup's running stage count (ring slot
+  // One stage (gemm6.hip's schedule, BK = 32: two k-substeps of NMF = 4 TN MFMAs and NRD = 4 + TN fragment reads).  g: the workgroup's running stage count (ring slot
   // g % NS).  kt == ksw: this is stage KT - NS of its tile — from its hand-over on the refills fetch the NEXT tile (or nothing).
   // The hand-over counts PIECES only.  Stores, aux and bias loads of a drain may be younger than the pieces waited for: the wait
   // then covers more than it needs (safe whether or not the hardware retires loads and stores in one order), never less.
@@ -374,20 +407,20 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     const Desc nA = mkdesc(ns.Ab, ns.recA), nB = mkdesc(ns.Bb, ns.recB);
     const unsigned so = (g % NS) * STAGE;
     const unsigned ring_cur = lds_pieces + so, ring_prev = lds_pieces + ((g + NS - 1) % NS) * STAGE;
-    // substep 0: MFMA i (i < 8) is followed by one read of substep 1's fragments; the early pieces (second half of the stage whose
-    // late half went out at the end of the previous stage) ride behind MFMAs 8, 10, 12, 14
+    // substep 0: MFMA i (i < NRD) is followed by one read of substep 1's fragments; the early pieces (the n-operand part of the stage
+    // whose m-operand part went out at the end of the previous stage) ride behind MFMAs NRD, NRD + 2, .. (8, 10, 12, 14 | 7, 9, 11)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
+    for (int i = 0; i < NMF; ++i) {
       mf(fa[0], fb[0], i);
-      if (i < 8) MMF_G7_READ(fa[1], fb[1], 1, i, so);
-      if (i == 8)  hot_piece(std::integral_constant<int, 4>{}, ring_prev);
-      if (i == 10) hot_piece(std::integral_constant<int, 5>{}, ring_prev);
-      if (i == 12) hot_piece(std::integral_constant<int, 6>{}, ring_prev);
-      if (i == 14) hot_piece(std::integral_constant<int, 7>{}, ring_prev);
+      if (i < NRD) MMF_G7_READ(fa[1], fb[1], 1, i, so);
+      if (i == NRD)     hot_piece(std::integral_constant<int, 4>{}, ring_prev);
+      if (i == NRD + 2) hot_piece(std::integral_constant<int, 5>{}, ring_prev);
+      if (i == NRD + 4) hot_piece(std::integral_constant<int, 6>{}, ring_prev);
+      if constexpr (TN == 4) { if (i == NRD + 6) hot_piece(std::integral_constant<int, 7>{}, ring_prev); }
     }
     frag_wait(fa[1], fb[1]);
-    // substep 1: four MFMAs, the stage hand-over, then MFMAs 4..11 each followed by one read of the next stage's first fragments and
-    // MFMAs 12..15 by the late pieces
+    // substep 1: four MFMAs, the stage hand-over, then MFMAs 4 .. NRD + 3 each followed by one read of the next stage's first fragments
+    // and the last four MFMAs by the late pieces (12..15 | 8..11: at TN = 3 the last three carry a read and a piece)
     const unsigned sn = ((g + 1) % NS) * STAGE;
 #pragma unroll
     for (int i = 0; i < 4; ++i) mf(fa[1], fb[1], i);
@@ -401,9 +434,9 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     // (hipcc re-derived the condition per portion: 45 instructions), and left to itself it computes all of it between the vmcnt
     // wait and the barrier, in front of an idle matrix pipe.
 #pragma unroll
-    for (int i = 4; i < 16; ++i) {
+    for (int i = 4; i < NMF; ++i) {
       mf(fa[1], fb[1], i);
-      if (i < 12) MMF_G7_READ(fa[0], fb[0], 0, i - 4, sn);
+      if (i < 4 + NRD) MMF_G7_READ(fa[0], fb[0], 0, i - 4, sn);
       if (i == 4) {                                            // both descriptors one stage on (eight scalar instructions)
         advance(dA, stepA);
         advance(dB, stepB);
@@ -428,16 +461,22 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
         __builtin_amdgcn_sched_barrier(0);
       }
       if (i == 7) {
-        asm volatile("v_cndmask_b32_e64 %0, %0, %4, %8\n\tv_cndmask_b32_e64 %1, %1, %5, %8\n\t"
-                     "v_cndmask_b32_e64 %2, %2, %6, %8\n\tv_cndmask_b32_e64 %3, %3, %7, %8"
-                     : "+v"(voff[4]), "+v"(voff[5]), "+v"(voff[6]), "+v"(voff[7])
-                     : "v"(voffn[4]), "v"(voffn[5]), "v"(voffn[6]), "v"(voffn[7]), "s"(swmask));
+        if constexpr (TN == 4)
+          asm volatile("v_cndmask_b32_e64 %0, %0, %4, %8\n\tv_cndmask_b32_e64 %1, %1, %5, %8\n\t"
+                       "v_cndmask_b32_e64 %2, %2, %6, %8\n\tv_cndmask_b32_e64 %3, %3, %7, %8"
+                       : "+v"(voff[4]), "+v"(voff[5]), "+v"(voff[6]), "+v"(voff[7])
+                       : "v"(voffn[4]), "v"(voffn[5]), "v"(voffn[6]), "v"(voffn[7]), "s"(swmask));
+        else
+          asm volatile("v_cndmask_b32_e64 %0, %0, %3, %6\n\tv_cndmask_b32_e64 %1, %1, %4, %6\n\t"
+                       "v_cndmask_b32_e64 %2, %2, %5, %6"
+                       : "+v"(voff[4]), "+v"(voff[5]), "+v"(voff[6])
+                       : "v"(voffn[4]), "v"(voffn[5]), "v"(voffn[6]), "s"(swmask));
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (i == 12) hot_piece(std::integral_constant<int, 0>{}, ring_cur);
-      if (i == 13) hot_piece(std::integral_constant<int, 1>{}, ring_cur);
-      if (i == 14) hot_piece(std::integral_constant<int, 2>{}, ring_cur);
-      if (i == 15) hot_piece(std::integral_constant<int, 3>{}, ring_cur);
+      if (i == NMF - 4) hot_piece(std::integral_constant<int, 0>{}, ring_cur);
+      if (i == NMF - 3) hot_piece(std::integral_constant<int, 1>{}, ring_cur);
+      if (i == NMF - 2) hot_piece(std::integral_constant<int, 2>{}, ring_cur);
+      if (i == NMF - 1) hot_piece(std::integral_constant<int, 3>{}, ring_cur);
     }
     frag_wait(fa[0], fb[0]);
   };
@@ -450,10 +489,10 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     for (int kt = 0; kt < KT; ++kt, ++g) stage(g, kt, ksw);
     // ---- the tile's outputs ----------------------------------------------------------------------------------------------------------
     const mmf_gemm_problem& P = args.p[cd.pi];
-    const int mb = cd.m0 + 128 * wm, nb = cd.n0 + 128 * wn;
+    const int mb = cd.m0 + 128 * wm, nb = cd.n0 + 32 * TN * wn;
     if constexpr (use_bias) { if (has_next) load_bias(bcur, nd); }   // the NEXT tile's bias: the drain covers the round trip
 #ifndef MMF_G7_NODRAIN
-    drain_tile<CT & ~MMF_EPI_BIAS>(args, cd.pi, P, mb, nb, acc, region, lane);
+    drain_tile<CT & ~MMF_EPI_BIAS, TN>(args, cd.pi, P, mb, nb, acc, region, lane);
 #else
     if (lane == 0 && mb == -1) static_cast<volatile unsigned short*>(P.C)[0] = (unsigned short)acc[0][0][0];   // (ablation: the tile is not stored)
 #endif
@@ -465,7 +504,7 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     has_next = walk(round + 1) < total_tiles;
     if (has_next) {
       int la, lb;
-      locate_tile<B_KR>(args, total_tiles, walk(round + 1), ns, nd, la, lb);
+      locate_tile<B_KR, TN>(args, total_tiles, walk(round + 1), ns, nd, la, lb);
       set_voff(voffn, la, lb);
     } else {
       ns.recA = 0; ns.recB = 0; ns.stepB = 0;
@@ -475,34 +514,36 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
 #undef MMF_G7_READ
 }
 
-template <bool B_KR, int CT>
+template <bool B_KR, int CT, int TN>
 __global__ __launch_bounds__(NTHREADS, 1)
 void gemm7_persistent_kernel(const GemmArgs args, const int total_tiles) {
-  // the ring and, behind it, one 8-KiB output staging region per wave: all 160 KiB of the CU
-  __shared__ __attribute__((aligned(1024))) char smem[NS * STAGE + 4 * 8192];
-  gemm7_body<B_KR, CT>(args, total_tiles, smem);
+  // the ring and, behind it, one 8-KiB output staging region per wave: all 160 KiB of the CU at TN = 4, 144 KiB at TN = 3
+  __shared__ __attribute__((aligned(1024))) char smem[Form<TN>::LDS];
+  gemm7_body<B_KR, CT, TN>(args, total_tiles, smem);
 }
 
 // the (layout, flag set) pairs of the fusion step's NT / NN launches: in-projections (NT, bias), FFN1 (NT, bias + ReLU), out-projection
 // and FFN2 (NT, bias + residual), plain NT, dgrads (NN, none), dH (NN, ReLU mask), dX (NN, residual gradient)
 template <bool B_KR, int CT>
-void launch7(const GemmArgs& a, int total, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
+void launch7(const GemmArgs& a, int total, int grid, int tile_n, hipStream_t s) {
+  if (tile_n == 192) hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT, 3>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
+  else               hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT, 4>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
 }
-bool launch7_select(int layout, int eflags, const GemmArgs* a, int total, int grid, hipStream_t s) {   // a == nullptr: only ask
+// a == nullptr: only ask
+bool launch7_select(int layout, int eflags, const GemmArgs* a, int total, int grid, hipStream_t s, int tile_n = 256) {
   if (layout == MMF_GEMM_NT) {
-    if (eflags == 0)                                      { if (a) launch7<false, 0>(*a, total, grid, s); return true; }
-    if (eflags == MMF_EPI_BIAS)                           { if (a) launch7<false, MMF_EPI_BIAS>(*a, total, grid, s); return true; }
-    if (eflags == (MMF_EPI_BIAS | MMF_EPI_RELU))          { if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU>(*a, total, grid, s); return true; }
-    if (eflags == (MMF_EPI_BIAS | MMF_EPI_ADD_AUX))       { if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_ADD_AUX>(*a, total, grid, s); return true; }
+    if (eflags == 0)                                      { if (a) launch7<false, 0>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == MMF_EPI_BIAS)                           { if (a) launch7<false, MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == (MMF_EPI_BIAS | MMF_EPI_RELU))          { if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == (MMF_EPI_BIAS | MMF_EPI_ADD_AUX))       { if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
     if (eflags == (MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT)) {       // FFN hidden layer in training mode
-      if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT>(*a, total, grid, s);
+      if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s);
       return true;
     }
   } else if (layout == MMF_GEMM_NN) {
-    if (eflags == 0)                                      { if (a) launch7<true, 0>(*a, total, grid, s); return true; }
-    if (eflags == MMF_EPI_MASK_AUX)                       { if (a) launch7<true, MMF_EPI_MASK_AUX>(*a, total, grid, s); return true; }
-    if (eflags == MMF_EPI_ADD_AUX)                        { if (a) launch7<true, MMF_EPI_ADD_AUX>(*a, total, grid, s); return true; }
+    if (eflags == 0)                                      { if (a) launch7<true, 0>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == MMF_EPI_MASK_AUX)                       { if (a) launch7<true, MMF_EPI_MASK_AUX>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == MMF_EPI_ADD_AUX)                        { if (a) launch7<true, MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
   }
   return false;
 }
@@ -514,6 +555,80 @@ extern "C" int mmf_gemm_set_persistent_workgroups(int n) {
   g_persistent_wgs = n;
   return MMF_OK;
 }
+static int g_tile_n = 0;                                       // 0: automatic (pick_tile_n), else 256 / 192 for every launch
+static thread_local int t_last_tile_n = 0;
+extern "C" int mmf_gemm7_set_tile_n(int n) {
+  if (n != 0 && n != 256 && n != 192) MMF_FAIL(MMF_E_SHAPE, "mmf_gemm7_set_tile_n: %d is not 0, 256 or 192", n);
+  g_tile_n = n;
+  return MMF_OK;
+}
+extern "C" int mmf_gemm7_last_tile_n(void) { return t_last_tile_n; }
+
+namespace {
+int persistent_grid_cap() {
+  static const int cus = [] { int c = mmf_device_cu_count(); return c > 0 ? c : 256; }();
+  return g_persistent_wgs > 0 ? g_persistent_wgs : cus;
+}
+// order: the problems longest K first (the kernel's problem order)
+int tiles_of(const mmf_gemm_problem& p, int bn) { return ((p.M + BM - 1) / BM) * ((p.N + bn - 1) / bn); }
+// The launch's makespan on min(tiles, cap) workgroups at tile width bn, in units of K x bn per tile: the kernel's walk (snake rounds
+// over the XCD-aware tile order, gemm7_body / mmf_xcd_tile) replayed on the host, the longest workgroup's sum.
+long long walk_makespan(const mmf_gemm_problem* problems, const int* order, int n, int bn, int cap, int granule) {
+  int start[MMF_GEMM_MAX_PROBLEMS + 1];
+  start[0] = 0;
+  for (int i = 0; i < n; ++i) start[i + 1] = start[i] + tiles_of(problems[order[i]], bn);
+  const int total = start[n], grid = total < cap ? total : cap;
+  if (total == 0) return 0;
+  static thread_local std::vector<long long> load;
+  load.assign(grid, 0);
+  for (int o = 0; o < total; ++o) {
+    const int round = o / grid, pos = o % grid, wid = (round & 1) ? grid - 1 - pos : pos;
+    const int bid = mmf_xcd_tile(o, total, granule);
+    const int pi = (int)(std::upper_bound(start, start + n + 1, bid) - start) - 1;
+    load[wid] += (long long)problems[order[pi]].K * bn;
+  }
+  return *std::max_element(load.begin(), load.end());
+}
+// Tile width of a launch: 192 only where its makespan is strictly shorter than at 256 (a tie keeps 256: fewer, larger tiles).
+// Replaying the walk costs 15-55 us of host time for the step's launches (one pass per tile and width), which an eager step would
+// pay per launch; the answers are remembered per thread for the last 16 launch shapes (the step has ten).
+struct TileNMemo {
+  int cap, granule, n, width;
+  int mnk[3 * MMF_GEMM_MAX_PROBLEMS];
+};
+int pick_tile_n(const mmf_gemm_problem* problems, const int* order, int n, int cap) {
+  const int granule = mmf_xcd_granule();
+  static thread_local TileNMemo memo[16];
+  static thread_local int used = 0, next = 0;
+  TileNMemo key;
+  key.cap = cap; key.granule = granule; key.n = n;
+  for (int i = 0; i < n; ++i) {
+    const mmf_gemm_problem& p = problems[order[i]];
+    key.mnk[3 * i] = p.M; key.mnk[3 * i + 1] = p.N; key.mnk[3 * i + 2] = p.K;
+  }
+  for (int e = 0; e < used; ++e) {
+    const TileNMemo& m = memo[e];
+    if (m.cap == cap && m.granule == granule && m.n == n && std::equal(key.mnk, key.mnk + 3 * n, m.mnk)) return m.width;
+  }
+  key.width = walk_makespan(problems, order, n, 192, cap, granule) < walk_makespan(problems, order, n, 256, cap, granule) ? 192 : 256;
+  memo[next] = key;
+  next = (next + 1) % 16;
+  if (used < 16) ++used;
+  return key.width;
+}
+void sort_by_k(const mmf_gemm_problem* problems, int n, int* order) {      // longest reduction first (see the walk in gemm7_body)
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order, order + n, [&](int x, int y) { return problems[x].K > problems[y].K; });
+}
+}  // namespace
+
+extern "C" int mmf_gemm7_tile_n(const mmf_gemm_problem* problems, int num_problems, int workgroups) {
+  if (!problems || num_problems < 1 || num_problems > MMF_GEMM_MAX_PROBLEMS || workgroups < 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_gemm7_tile_n: %d problems, %d workgroups", num_problems, workgroups);
+  int order[MMF_GEMM_MAX_PROBLEMS];
+  sort_by_k(problems, num_problems, order);
+  return pick_tile_n(problems, order, num_problems, workgroups > 0 ? workgroups : persistent_grid_cap());
+}
 
 // whether the persistent kernel can take this launch (gemm.hip asks before selecting it)
 bool mmf_gemm7_supports(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue, int out_f32, const mmf_gemm_extra* extra) {
@@ -522,7 +637,7 @@ bool mmf_gemm7_supports(const mmf_gemm_problem* problems, int num_problems, int 
   if ((epilogue & MMF_EPI_DROPOUT) && !(extra && extra->rng_state)) return false;
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[i];
-    if (p.K % BK || p.K < (NS + 1) * BK || (p.N & 7) || (p.ldc & 7) || (p.aux && (p.ldaux & 7))) return false;
+    if (p.K % BK || p.K < (NS + 1) * BK || (p.N & 7) || (p.ldc & 7) || (p.aux && ((p.ldaux & 7) || !mmf_aligned16(p.aux)))) return false;
   }
   return true;
 }
@@ -541,9 +656,10 @@ int mmf_gemm7_launch(const mmf_gemm_problem* problems, int num_problems, int lay
   a.site = extra ? extra->site : 0u;
   a.rng_state = extra ? reinterpret_cast<const unsigned long long*>(extra->rng_state) : nullptr;
   int total = 0;
-  int order[MMF_GEMM_MAX_PROBLEMS];                            // longest reduction first (see the walk in gemm7_body)
-  for (int i = 0; i < num_problems; ++i) order[i] = i;
-  std::stable_sort(order, order + num_problems, [&](int x, int y) { return problems[x].K > problems[y].K; });
+  int order[MMF_GEMM_MAX_PROBLEMS];
+  sort_by_k(problems, num_problems, order);
+  const int cap = persistent_grid_cap();
+  const int tile_n = g_tile_n ? g_tile_n : pick_tile_n(problems, order, num_problems, cap);
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[order[i]];
     const size_t a_bytes = (size_t)p.M * p.lda * 2;
@@ -552,15 +668,14 @@ int mmf_gemm7_launch(const mmf_gemm_problem* problems, int num_problems, int lay
     if (a_bytes >= 0x7fffffffull || b_bytes >= 0x7fffffffull || c_bytes >= 0x7fffffffull || x_bytes >= 0x7fffffffull)
       MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped[%d]: operand larger than 2 GiB", i);
     a.tile_start[i] = total;
-    total += ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+    total += tiles_of(p, tile_n);
     a.p[i] = p;
     a.orig[i] = (short)order[i];
   }
   a.tile_start[num_problems] = total;
-  static const int cus = [] { int c = mmf_device_cu_count(); return c > 0 ? c : 256; }();
-  const int want = g_persistent_wgs > 0 ? g_persistent_wgs : cus;
-  const int grid = total < want ? total : want;
-  launch7_select(layout, epilogue, &a, total, grid, s);
+  const int grid = total < cap ? total : cap;
+  t_last_tile_n = tile_n;
+  launch7_select(layout, epilogue, &a, total, grid, s, tile_n);
   MMF_CHECK_LAUNCH("mmf_gemm_grouped(v7)");
   return MMF_OK;
 }

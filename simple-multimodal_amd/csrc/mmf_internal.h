@@ -64,7 +64,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // problems.  One contiguous range per XCD (G = 0, the first form) is only balanced when all tiles take equally
 // long: with the problems ordered by K descending it gave XCD 0 nothing but the longest tiles and the launch
 // ended when XCD 0 did.  The last (< 8 G) tiles, and launches smaller than that, keep one range per XCD.
-__device__ __forceinline__ int mmf_xcd_tile(int orig, int total, int G) {
+__host__ __device__ __forceinline__ int mmf_xcd_tile(int orig, int total, int G) {   // (host: gemm7.hip's tile-width choice)
   const int xcd = orig & 7;
   const int full = G > 0 ? (total / (8 * G)) * (8 * G) : 0;
   if (orig < full) {

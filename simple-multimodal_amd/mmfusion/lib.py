@@ -23,6 +23,7 @@ EVAL_MAX_HEADS, EVAL_NSUMS = 4, 4
 # every symbol include/mmfusion.h declares (tests check the .so exports all of them)
 SYMBOLS = (
     "mmf_version", "mmf_last_error", "mmf_device_cu_count", "mmf_gemm_grouped", "mmf_gemm_grouped_ex", "mmf_gemm_select_impl", "mmf_gemm_last_impl", "mmf_gemm_set_persistent_workgroups",
+    "mmf_gemm7_set_tile_n", "mmf_gemm7_last_tile_n", "mmf_gemm7_tile_n",
     "mmf_attn_fwd_grouped_ex", "mmf_attn_bwd_grouped_ex", "mmf_dropout", "mmf_attn_select_impl",
     "mmf_attn_fwd_grouped", "mmf_attn_bwd_grouped", "mmf_layernorm_fwd_grouped",
     "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
@@ -132,6 +133,7 @@ def load() -> C.CDLL:
     vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
     lib.mmf_gemm_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, i32, vp]
     lib.mmf_gemm_grouped_ex.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, i32, C.POINTER(GemmExtra), vp]
+    lib.mmf_gemm7_tile_n.argtypes = [C.POINTER(GemmProblem), i32, i32]
     lib.mmf_attn_fwd_grouped_ex.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, vp]
     lib.mmf_attn_bwd_grouped_ex.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, vp]
     lib.mmf_dropout.argtypes = [vp, vp, i64, i32, f32, vp, C.c_uint32, vp]

@@ -109,35 +109,36 @@ def gemm6_row_read_cycles(W, rows=256):
     return worst
 
 
-def gemm6_tr_read_ok(G_count):
+def gemm6_tr_read_ok(G_count, W=256):
     """Frag4<true>: the two ds_read_b64_tr_b16 of fragment (G, D) address rows 16 G + 8 h + q (+ 4) of columns 32 D + 16 g + 4 p ..;
-    returns (addresses match img_off, worst LDS cycles per read)."""
-    W, worst, ok = 256, 0, True
+    returns (addresses match img_off, worst LDS cycles per read).  W: the tile width (256; gemm7's 96-column form: 192)."""
+    worst, ok = 0, True
+    R8 = (W // 32) * 512                       # bytes of 8 tile rows
     for G in range(G_count):
-        for D in range(8):
+        for D in range(W // 32):
             for hi in (0, 1):
                 addrs = []
                 for l in range(64):
                     h, g, q, p = l >> 5, (l >> 4) & 1, (l >> 2) & 3, l & 3
                     c = 2 * g + (p >> 1)
                     if hi:
-                        lane_part = 4096 * h + 64 * (4 + q) + 16 * (c ^ (2 * h + 1)) + 8 * (p & 1)
+                        lane_part = R8 * h + 64 * (4 + q) + 16 * (c ^ (2 * h + 1)) + 8 * (p & 1)
                     else:
-                        lane_part = 4096 * h + 64 * q + 16 * (c ^ (2 * h)) + 8 * (p & 1)
-                    a = lane_part + 8192 * G + 512 * D
+                        lane_part = R8 * h + 64 * q + 16 * (c ^ (2 * h)) + 8 * (p & 1)
+                    a = lane_part + 2 * R8 * G + 512 * D
                     ok = ok and a == off_new(W, 16 * G + 8 * h + q + 4 * hi, 4 * D + c) + 8 * (p & 1)
                     addrs.append(a)
                 worst = max(worst, cycles(addrs, 8, TR_GROUPS))
     return ok, worst
 
 
-def gemm6_piece_map_ok(KR, BK):
+def gemm6_piece_map_ok(KR, BK, width=256):
     """piece_voff: piece p, lane L -> (tile row, 16-byte chunk); its LDS position 1024 p + 16 L must be img_off(row, chunk) and
-    the pieces must cover the tile exactly once."""
-    W = 256 if KR else BK
-    rows = BK if KR else 256
+    the pieces must cover the tile exactly once.  width: the tile's m / n extent (256; gemm7's 96-column form: 192)."""
+    W = width if KR else BK
+    rows = BK if KR else width
     NC, seen = W // 32, set()
-    for p in range(BK // 2):
+    for p in range(rows * W * 2 // 1024):
         for L in range(64):
             st = 2 * p + (L >> 5)
             rg, cc = st // NC, st % NC
