@@ -479,7 +479,8 @@ int mmf_gat3_dense_bwd(const float* h, const float* att_src, const float* att_ds
 /* n_m = z_m / max(||z_m||, 1e-12) for three (B, D) projections and, if losses != NULL, the symmetric InfoNCE of
  * the pairs (0,1) (0,2) (1,2): (CE(n_a n_b^T / T, arange) + CE(transposed, arange)) / 2 — ContrastiveFusion,
  * models/fusion_layers.py:338-347, 361-375.  B <= 64 (per-rank batch), D a multiple of 4.  inv_norm [3][B] and
- * lse [3][2][B] are saved for the backward; dn[m] / dloss[p] may be NULL (no gradient from that output). */
+ * lse [3][2][B] are saved for the backward; dn[m] / dloss[p] may be NULL (no gradient from that output).  A row whose
+ * norm is clamped (||z|| <= 1e-12: a row of zeros) gets a zero gradient row, not dn * 1e12. */
 int mmf_infonce_fwd(const float* const z[3], float* const n[3], float* inv_norm, float* losses, float* lse,
                     int B, int D, float temperature, void* stream);
 int mmf_infonce_bwd(const float* const n[3], const float* inv_norm, const float* lse, const float* const dn[3],

@@ -225,6 +225,14 @@ struct NceArgs {
 };
 
 __device__ __forceinline__ void nce_pair(int p, int& ma, int& mb) { ma = p == 2 ? 1 : 0; mb = p == 0 ? 1 : 2; }
+// 1 / max(||z||, 1e-12).  A row whose norm is clamped (all zeros, in practice) has no direction: its normalised row is
+// z * 1e12 and the derivative of that is I * 1e12, which would put gradients of ~1e10 into the step for a row that carries
+// no information.  The backward gives such a row a ZERO gradient instead (the other rows are untouched: n = 0 adds
+// nothing to their similarities' gradients).  torch's F.normalize backward returns dn * 1e12 there.
+// The test on the saved 1 / norm is deliberately inclusive: the 0.999999 keeps a last-bit difference of the division from
+// deciding it, at the price of also zeroing a non-zero row with ||z|| <= 1.000001e-12.
+__device__ __forceinline__ float nce_inv_norm(float norm) { return 1.f / fmaxf(norm, 1e-12f); }
+__device__ __forceinline__ bool nce_clamped(float inv) { return inv >= 0.999999f * nce_inv_norm(0.f); }
 
 constexpr int NCE_THREADS = 1024, NCE_WAVES = NCE_THREADS / 64;
 
@@ -264,7 +272,7 @@ void nce_fwd_kernel(const NceArgs a) {
       ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
     }
     ss = wave_sum(ss);
-    const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+    const float inv = nce_inv_norm(sqrtf(ss));
     if (lane == 0) a.inv_norm[m * B + i] = inv;
     float* n = a.n[m] + (size_t)i * D;
     for (int c = lane * 4; c < D; c += 256)
@@ -358,9 +366,10 @@ void nce_bwd_kernel(const NceArgs a) {
   }
   dot = wave_sum(dot);
   const float inv = a.inv_norm[m * B + i];
+  const bool clamped = nce_clamped(inv);                  // wave-uniform: a row without a direction gets no gradient
   for (int c = lane * 4; c < D; c += 256) {
     const f32x4_t g = *reinterpret_cast<const f32x4_t*>(dz + c), nv = *reinterpret_cast<const f32x4_t*>(n + c);
-    *reinterpret_cast<f32x4_t*>(dz + c) = (g - nv * dot) * inv;
+    *reinterpret_cast<f32x4_t*>(dz + c) = clamped ? f32x4_t{0.f, 0.f, 0.f, 0.f} : (g - nv * dot) * inv;
   }
 }
 

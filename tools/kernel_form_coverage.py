@@ -6,6 +6,8 @@ LIB is the built libmmfusion.so; each STATS.csv is the kernel-stats file of a `r
 `Name` column; several files are merged).  The instantiations are read off the `.kd` (kernel descriptor) symbols of the
 embedded code objects with `strings` and `c++filt`, so this runs on a machine without a GPU; it reads files only.
 --only keeps the instantiations whose name matches REGEX (the families a run targets, e.g. 'ln_|skinny_dgrad').
+For a trace of tests/test_streaming_small_gpu.py (the kernels of elementwise.hip, small.hip and optim.hip it pins):
+    --only '^(cast_|add3|addn_|relu_bwd|dropout_kernel|meanpool|colsum|zero_ranges|gat3_|nce_|ada_|attn_weights_mean|narrow_|stack3_|rowmask|sqnorm|adamw)'
 Exit status 1 if an instantiation outside DELIBERATELY_UNLAUNCHED was never launched.
 """
 import argparse
