@@ -590,6 +590,23 @@ int mmf_bilstm_layer_bwd(const mmf_bilstm_args* args, void* workspace, size_t wo
  * ((B, T, d) <-> (T, B, d)); in_f32 selects an f32 source, the destination is bf16 unless out_f32. d % 8 == 0. */
 int mmf_swap01(const void* in, void* out, int n0, int n1, int d, int in_f32, int out_f32, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frozen ViT backbone (mmfusion/vit.py; the reference runs HuggingFace's ViTModel at models/encoders.py:179,216-226).
+ * The linears, the attention and the LayerNorms of a ViT layer are the grouped kernels above; these are the three
+ * streaming pieces a ViT has beside them.  All pointers 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+/* pixels (N, C, H, W) f32 -> patches (N * (H/P) * (W/P), C*P*P) bf16, row = (n, gy, gx), column = (c, py, px): the A operand of
+ * ONE NT GEMM against the Conv2d(C, hidden, P, stride P) weight viewed as (hidden, C*P*P).  H % P == 0, W % P == 0, P % 8 == 0,
+ * N <= 65535; anything else is MMF_E_UNSUPPORTED. */
+int mmf_vit_patchify(const float* pixels, void* patches_bf16, int N, int C, int H, int W, int P, void* stream);
+/* tokens (N*T, d) bf16: row n*T = cls + pos[0], row n*T + 1 + p = patch_emb[n*(T-1) + p] + pos[1 + p]; cls f32 [d], pos f32
+ * [T][d], patch_emb bf16 (N*(T-1), d); the add is f32 with one rounding to bf16.  d % 8 == 0, N <= 65535. */
+int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls, const float* pos, void* tokens_bf16, int N, int T, int d,
+                         void* stream);
+/* x <- gelu(x + bias) in place on a bf16 (rows, cols) block with row stride ld: the exact form 0.5 v (1 + erf(v / sqrt 2)) in
+ * f32 (HuggingFace hidden_act = "gelu"), one rounding to bf16.  bias f32 [cols] or NULL.  cols % 8 == 0, ld % 8 == 0. */
+int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows, int cols, int ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

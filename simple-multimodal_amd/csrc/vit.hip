@@ -1,0 +1,146 @@
+// The pieces a ViT forward has and the fusion path did not (mmfusion/vit.py): patch extraction for the patch-embedding
+// GEMM, CLS / position tokens, exact (erf) GELU.  All three are HBM-bound streaming kernels: one 16-byte bf16 access
+// (8 elements) per lane on the bf16 side, two 16-byte accesses on the f32 side, grid-stride loops capped at 2048
+// workgroups per grid row like elementwise.hip's.
+#include "mmf_internal.h"
+
+namespace {
+
+constexpr int VIT_THREADS = 256;
+inline int vit_grid(int64_t nvec) {
+  int64_t g = (nvec + VIT_THREADS - 1) / VIT_THREADS;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+__device__ __forceinline__ u32x4_t pack8(const f32x4_t a, const f32x4_t b) {
+  return u32x4_t{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
+}
+
+// (N, C, H, W) f32 -> (N * gh * gw, C * P * P) bf16, column (c, py, px).  blockIdx.y = image; inside an image the lanes
+// walk the OUTPUT in order (every wave store covers 1 KiB contiguous); a lane's 8 output columns are 8 consecutive px of
+// one pixel row (P % 8 == 0), i.e. 32 contiguous input bytes, and the P / 8 lanes of one patch row read P * 4 contiguous
+// bytes.  The other patches of the same pixel row are C * P * P / 8 lanes further on, so the rest of each input cache line is
+// fetched by the same or a neighbouring workgroup.
+__global__ __launch_bounds__(VIT_THREADS)
+void vit_patchify_kernel(const float* __restrict__ pix, unsigned short* __restrict__ out, int C, int H, int W, int P,
+                         int gw, unsigned kv /* C*P*P/8 */, unsigned nvec /* gh*gw*kv */) {
+  const unsigned pv = (unsigned)P >> 3, ppv = pv * (unsigned)P;      // vectors per patch row / per patch channel
+  const float* __restrict__ img = pix + (size_t)blockIdx.y * C * H * W;
+  unsigned short* __restrict__ dst = out + (size_t)blockIdx.y * nvec * 8;
+  const unsigned stride = gridDim.x * VIT_THREADS;
+  for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const unsigned patch = v / kv, k = v - patch * kv;
+    const unsigned gy = patch / (unsigned)gw, gx = patch - gy * (unsigned)gw;
+    const unsigned c = k / ppv, r = k - c * ppv;
+    const unsigned py = r / pv, px = (r - py * pv) << 3;
+    const float* __restrict__ src = img + ((size_t)c * H + (gy * P + py)) * W + (gx * P + px);
+    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(src);
+    const f32x4_t b = *reinterpret_cast<const f32x4_t*>(src + 4);
+    *reinterpret_cast<u32x4_t*>(dst + (size_t)v * 8) = pack8(a, b);
+  }
+}
+
+// tokens[n][0] = cls + pos[0]; tokens[n][1 + p] = patch_emb[n][p] + pos[1 + p]; f32 add, one rounding.  blockIdx.y = image;
+// inside an image the flat element index of tokens IS the index into pos, and the one into patch_emb shifted by d.
+__global__ __launch_bounds__(VIT_THREADS)
+void vit_embed_tokens_kernel(const unsigned short* __restrict__ pe, const float* __restrict__ cls, const float* __restrict__ pos,
+                             unsigned short* __restrict__ tok, int T, int d) {
+  const unsigned dv = (unsigned)d >> 3, nvec = (unsigned)T * dv;
+  const unsigned short* __restrict__ src = pe + (size_t)blockIdx.y * (T - 1) * d;
+  unsigned short* __restrict__ dst = tok + (size_t)blockIdx.y * T * d;
+  const unsigned stride = gridDim.x * VIT_THREADS;
+  for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const f32x4_t p0 = *reinterpret_cast<const f32x4_t*>(pos + (size_t)v * 8);
+    const f32x4_t p1 = *reinterpret_cast<const f32x4_t*>(pos + (size_t)v * 8 + 4);
+    f32x4_t a, b;
+    if (v < dv) {
+      a = *reinterpret_cast<const f32x4_t*>(cls + v * 8);
+      b = *reinterpret_cast<const f32x4_t*>(cls + v * 8 + 4);
+    } else {
+      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(src + (size_t)(v - dv) * 8);
+      a = f32x4_t{bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
+      b = f32x4_t{bf16lo(w[2]), bf16hi(w[2]), bf16lo(w[3]), bf16hi(w[3])};
+    }
+    *reinterpret_cast<u32x4_t*>(dst + (size_t)v * 8) = pack8(a + p0, b + p1);
+  }
+}
+
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// x <- gelu(x + bias) in place, rows x cols with row stride ld.  nvec = rows * cols / 8 < 2^31 (the host splits longer inputs).
+template <bool HAS_BIAS>
+__global__ __launch_bounds__(VIT_THREADS)
+void bias_gelu_kernel(unsigned short* __restrict__ x, const float* __restrict__ bias, unsigned nvec, unsigned cv /* cols/8 */, int ld) {
+  const unsigned stride = gridDim.x * VIT_THREADS;
+  for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const unsigned r = v / cv, j = (v - r * cv) << 3;
+    unsigned short* p = x + (size_t)r * ld + j;
+    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(p);
+    f32x4_t a = f32x4_t{bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
+    f32x4_t b = f32x4_t{bf16lo(w[2]), bf16hi(w[2]), bf16lo(w[3]), bf16hi(w[3])};
+    if (HAS_BIAS) {
+      a += *reinterpret_cast<const f32x4_t*>(bias + j);
+      b += *reinterpret_cast<const f32x4_t*>(bias + j + 4);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { a[e] = gelu_erf(a[e]); b[e] = gelu_erf(b[e]); }
+    *reinterpret_cast<u32x4_t*>(p) = pack8(a, b);
+  }
+}
+
+}  // namespace
+
+extern "C" int mmf_vit_patchify(const float* pixels, void* patches_bf16, int N, int C, int H, int W, int P, void* stream) {
+  if (!pixels || !patches_bf16 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || P <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_vit_patchify: null operand or N=%d C=%d H=%d W=%d P=%d", N, C, H, W, P);
+  if ((P & 7) || H % P || W % P)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_patchify: H=%d W=%d P=%d (needs P %% 8 == 0, H %% P == 0, W %% P == 0)", H, W, P);
+  if (N > 65535) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_patchify: N=%d images in one call (at most 65535)", N);
+  if (!mmf_aligned16(pixels) || !mmf_aligned16(patches_bf16))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_vit_patchify: pointers must be 16-byte aligned");
+  const int64_t per_image = (int64_t)C * H * W / 8;                   // = gh * gw * C * P * P / 8 output vectors
+  if (per_image >= (int64_t)1 << 31) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_patchify: image of %lld elements", (long long)per_image * 8);
+  const unsigned kv = (unsigned)((int64_t)C * P * P / 8);
+  hipLaunchKernelGGL(vit_patchify_kernel, dim3(vit_grid(per_image), N), dim3(VIT_THREADS), 0, static_cast<hipStream_t>(stream),
+                     pixels, static_cast<unsigned short*>(patches_bf16), C, H, W, P, W / P, kv, (unsigned)per_image);
+  MMF_CHECK_LAUNCH("mmf_vit_patchify");
+  return MMF_OK;
+}
+
+extern "C" int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls, const float* pos, void* tokens_bf16,
+                                    int N, int T, int d, void* stream) {
+  if (!patch_emb_bf16 || !cls || !pos || !tokens_bf16 || N <= 0 || T < 2 || d <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_vit_embed_tokens: null operand or N=%d T=%d d=%d", N, T, d);
+  if (d & 7) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_embed_tokens: d=%d must be a multiple of 8", d);
+  if (N > 65535 || (int64_t)T * d >= (int64_t)1 << 31)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_embed_tokens: N=%d (at most 65535), T*d=%lld (below 2^31)", N, (long long)T * d);
+  if (!mmf_aligned16(patch_emb_bf16) || !mmf_aligned16(cls) || !mmf_aligned16(pos) || !mmf_aligned16(tokens_bf16))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_vit_embed_tokens: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(vit_embed_tokens_kernel, dim3(vit_grid((int64_t)T * d / 8), N), dim3(VIT_THREADS), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(patch_emb_bf16), cls, pos,
+                     static_cast<unsigned short*>(tokens_bf16), T, d);
+  MMF_CHECK_LAUNCH("mmf_vit_embed_tokens");
+  return MMF_OK;
+}
+
+extern "C" int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows, int cols, int ld, void* stream) {
+  if (!x_bf16 || rows <= 0 || cols <= 0) MMF_FAIL(MMF_E_SHAPE, "mmf_bias_gelu_bf16: null operand or rows=%lld cols=%d", (long long)rows, cols);
+  if ((cols & 7) || (ld & 7) || ld < cols)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_bias_gelu_bf16: cols=%d ld=%d (multiples of 8, ld >= cols)", cols, ld);
+  if (!mmf_aligned16(x_bf16) || (bias && !mmf_aligned16(bias)))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_bias_gelu_bf16: pointers must be 16-byte aligned");
+  const unsigned cv = (unsigned)cols >> 3;
+  const int64_t max_rows = (((int64_t)1 << 31) - 1) / cv;             // rows of one launch: 32-bit vector index
+  unsigned short* x = static_cast<unsigned short*>(x_bf16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int64_t r0 = 0; r0 < rows; r0 += max_rows) {
+    const int64_t nr = rows - r0 < max_rows ? rows - r0 : max_rows;
+    const unsigned nvec = (unsigned)(nr * cv);
+    if (bias) hipLaunchKernelGGL(bias_gelu_kernel<true>, dim3(vit_grid(nvec)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
+    else      hipLaunchKernelGGL(bias_gelu_kernel<false>, dim3(vit_grid(nvec)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
+    MMF_CHECK_LAUNCH("mmf_bias_gelu_bf16");
+  }
+  return MMF_OK;
+}

@@ -37,6 +37,7 @@ SYMBOLS = (
     "mmf_distill_kl", "mmf_fusion_loss_kd", "mmf_robust_head_fwd", "mmf_robust_head_bwd",
     "mmf_fewshot_proto_fwd", "mmf_fewshot_proto_bwd", "mmf_fewshot_dist_fwd", "mmf_fewshot_dist_bwd",
     "mmf_eval_accumulate",
+    "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16",
 )
 
 
@@ -199,6 +200,9 @@ def load() -> C.CDLL:
     lib.mmf_bilstm_layer_fwd.argtypes = [C.POINTER(BiLstmArgs), vp, C.c_size_t, vp]
     lib.mmf_bilstm_layer_bwd.argtypes = [C.POINTER(BiLstmArgs), vp, C.c_size_t, vp]
     lib.mmf_swap01.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_vit_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_vit_embed_tokens.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_bias_gelu_bf16.argtypes = [vp, vp, i64, i32, i32, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -333,3 +337,31 @@ def skinny_dgrad(problems: Sequence[SkinnyProblem], flags: int, alpha: float, ou
         chunk = problems[i:i + SKINNY_MAX_PROBLEMS]
         arr = (SkinnyProblem * len(chunk))(*chunk)
         check(load().mmf_skinny_linear_dgrad(arr, len(chunk), flags, alpha, int(out_f32), stream_ptr()))
+
+
+# ---- ViT streaming kernels (csrc/vit.hip); tensors, not pointers: the shapes are checked here ---------------
+def vit_patchify(pixels, patches, N: int, C: int, H: int, W: int, P: int) -> None:
+    """pixels (N, C, H, W) f32 contiguous -> patches (N * (H/P) * (W/P), C*P*P) bf16 contiguous"""
+    if pixels.numel() != N * C * H * W or not pixels.is_contiguous() or not patches.is_contiguous() \
+            or patches.numel() != pixels.numel():
+        raise ValueError("vit_patchify: pixels / patches do not hold N x C x H x W contiguous elements")
+    with _Timed("vit_patchify_kernel", 0.0, [(N, C * H * W)]):
+        check(load().mmf_vit_patchify(pixels.data_ptr(), patches.data_ptr(), N, C, H, W, P, stream_ptr()))
+
+
+def vit_embed_tokens(patch_emb, cls, pos, tokens, N: int, T: int, d: int) -> None:
+    if patch_emb.numel() != N * (T - 1) * d or not patch_emb.is_contiguous() or cls.numel() != d or pos.numel() != T * d \
+            or tokens.numel() < N * T * d or not tokens.is_contiguous():
+        raise ValueError("vit_embed_tokens: operand sizes do not match N, T, d")
+    with _Timed("vit_embed_tokens_kernel", 0.0, [(N * T, d)]):
+        check(load().mmf_vit_embed_tokens(patch_emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), tokens.data_ptr(), N, T, d,
+                                          stream_ptr()))
+
+
+def bias_gelu(x, bias=None) -> None:
+    """x (rows, cols) bf16, row-strided allowed, in place: gelu(x + bias), exact (erf) form"""
+    if x.dim() != 2 or x.stride(1) != 1 or (bias is not None and (bias.numel() != x.shape[1] or not bias.is_contiguous())):
+        raise ValueError("bias_gelu: x must be 2-D with contiguous rows and bias one value per column")
+    with _Timed("bias_gelu_kernel", 0.0, [tuple(x.shape)]):
+        check(load().mmf_bias_gelu_bf16(x.data_ptr(), bias.data_ptr() if bias is not None else None, x.shape[0], x.shape[1],
+                                        x.stride(0), stream_ptr()))

@@ -393,7 +393,10 @@ def load_checkpoint(path: str, module: torch.nn.Module, optimizer: Optional["Fus
     """Restore ``module`` (and the fused optimiser's moments / step count) from a checkpoint in the reference's
     layout, read with the safe loader (``models.multimodal_model.load_checkpoint_file``).  The parameters live in
     the arena's fp32 master, which ``load_state_dict`` writes in place; the bf16 shadow is re-cast.  Returns the
-    checkpoint dict (epoch, metrics, scheduler_state_dict, config)."""
+    checkpoint dict (epoch, metrics, scheduler_state_dict, config).
+    ``video_encoder.vit.*`` keys of either HuggingFace generation (transformers 5.x ``layers.N.attention.q_proj`` or the 4.x
+    ``encoder.layer.N.attention.attention.query`` of published checkpoints and reference ``.pth`` files) load into a native
+    backbone: ``mmfusion.vit.NativeViT`` renames and fuses them in its own ``load_state_dict`` hook."""
     from models.multimodal_model import load_checkpoint_file
     ckpt = load_checkpoint_file(path)
     module.load_state_dict(ckpt["model_state_dict"])

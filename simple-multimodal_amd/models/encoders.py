@@ -11,6 +11,8 @@ They are third-party pretrained models fetched by name; there is no network here
 therefore take a ``backbone`` argument:
   * ``backbone=None`` (default) reproduces the reference: ``from_pretrained(config.*_model_name)``;
   * any ``nn.Module`` returning an object with ``.last_hidden_state`` is used as is;
+  * ``config.video_backbone = "native"`` (dynamic attribute, ``VideoEncoder`` only) builds ``mmfusion.vit.NativeViT``: the
+    frozen, forward-only ViT on the HIP kernels, which takes HuggingFace ``state_dict``s and needs no network;
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -41,6 +43,20 @@ def _load_backbone(kind: str, name: str):
     from transformers import AutoModel, ViTModel, Wav2Vec2Model
     cls = {"text": AutoModel, "audio": Wav2Vec2Model, "video": ViTModel}[kind]
     return cls.from_pretrained(name)
+
+
+def _native_vit(config):
+    """``config.video_backbone = "native"``: the ViT of ``mmfusion.vit`` on the HIP kernels, built from
+    ``config.video_hidden_size`` / ``config.video_frame_size`` with ViT-base's other sizes (``config.video_backbone_kwargs``,
+    a dict, overrides any of them); weights come from ``load_state_dict`` / a checkpoint, nothing is fetched."""
+    from mmfusion.vit import NativeViT
+    size = config.video_frame_size
+    size = size if isinstance(size, int) else size[0]
+    if not isinstance(config.video_frame_size, int) and len(set(config.video_frame_size)) != 1:
+        raise ValueError(f"the native ViT backbone takes square frames, not {tuple(config.video_frame_size)}")
+    kw = dict(hidden_size=config.video_hidden_size, image_size=size)
+    kw.update(getattr(config, "video_backbone_kwargs", None) or {})
+    return NativeViT(**kw)
 
 
 class AdapterLayer(_FusionBase):
@@ -168,6 +184,9 @@ class VideoEncoder(_FusionBase):
         self.config = config
         if _feature_mode(config):
             self.vit, self.hidden_size = None, config.video_hidden_size
+        elif backbone is None and getattr(config, "video_backbone", None) == "native":
+            self.vit = _native_vit(config)
+            self.hidden_size = self.vit.config.hidden_size
         else:
             self.vit = backbone if backbone is not None else _load_backbone("video", config.video_model_name)
             self.hidden_size = self.vit.config.hidden_size
@@ -183,7 +202,11 @@ class VideoEncoder(_FusionBase):
             frame_features = video_frames
         else:
             B, n, c, h, w = video_frames.shape
-            cls = self.vit(pixel_values=video_frames.view(-1, c, h, w)).last_hidden_state[:, 0]
+            if hasattr(self.vit, "cls_features"):        # the native backbone: frozen, and its last layer runs for the CLS rows only
+                with torch.no_grad():
+                    cls = self.vit.cls_features(video_frames.reshape(-1, c, h, w))
+            else:
+                cls = self.vit(pixel_values=video_frames.view(-1, c, h, w)).last_hidden_state[:, 0]
             frame_features = cls.view(B, n, -1)
         if use_adapter and self.adapter is not None:
             frame_features = self.adapter(frame_features)
