@@ -607,6 +607,36 @@ int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls, const flo
  * f32 (HuggingFace hidden_act = "gelu"), one rounding to bf16.  bias f32 [cols] or NULL.  cols % 8 == 0, ld % 8 == 0. */
 int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows, int cols, int ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frozen Wav2Vec2 backbone (mmfusion/wav2vec2.py; the reference runs HuggingFace's Wav2Vec2Model at models/encoders.py:116,144).
+ * Activations are channel-last (time, channels) bf16.  The inner feature-extractor convolutions, the projection and the
+ * transformer layers are the grouped kernels above; these are the pieces a Wav2Vec2 has beside them.  Every function
+ * validates first and launches nothing on an error.
+ * ------------------------------------------------------------------------------------------ */
+#define MMF_W2V_STATS_SLOTS 128
+/* Layer 0, pass 1: Conv1d(1 -> C0, k0, stride s0, no bias) of wave (N, L) f32 against weight (C0, k0) f32, recomputed and
+ * reduced (Welford per lane, merged in a fixed order: deterministic) to stats (N, 2, C0) f32: row 0 the mean, row 1 the biased
+ * variance over the T0 = (L - k0) / s0 + 1 frames of each (clip, channel).  partial: N * MMF_W2V_STATS_SLOTS * 2 * C0 floats of
+ * scratch.  C0 % 8 == 0, C0 <= 2048, k0 <= 16, N <= 65535; stats / partial 16-byte aligned. */
+int mmf_w2v_conv0_stats(const float* wave, const float* weight, float* stats, float* partial, int N, int L, int C0, int k0, int s0,
+                        void* stream);
+/* Layer 0, pass 2: the same convolution recomputed, GroupNorm with one group per channel (stats, gamma, beta f32 [C0], eps),
+ * exact GELU, one rounding to bf16, stored in the window form of the NEXT conv layer (kernel k1, stride s1):
+ * out (N, T1, k1*C0) bf16 with out[n][t][j*C0 + c] = frame s1*t + j, T1 = (T0 - k1) / s1 + 1. */
+int mmf_w2v_conv0_norm_gelu(const float* wave, const float* weight, const float* stats, const float* gamma, const float* beta,
+                            void* out_bf16, int N, int L, int C0, int k0, int s0, int k1, int s1, float eps, void* stream);
+/* x (N, T_in, C) bf16, a raw convolution output -> out (N, T_out, k*C) bf16, out[n][t][j*C + c] = gelu(x[n][s*t + j][c]) (exact
+ * form, f32, one rounding), T_out = (T_in - k) / s + 1: the A operand of the next conv layer as ONE NT GEMM against its weight
+ * repacked to (C_out, k*C), column (j, c).  C % 8 == 0, N <= 65535, out must not be x. */
+int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, int T_in, int C, int k, int s, void* stream);
+/* The positional convolution with its residual: y = x + gelu(conv(x) + bias), x / y (N, T, C) bf16, Conv1d(C -> C, kernel k,
+ * padding k/2, `groups` groups; for an even k the extra last frame is dropped) on the MFMA units with f32 accumulation.
+ * w_bf16: (groups, cg, Kp) with cg = C / groups, Kp = k*cg rounded up to a multiple of 32, w[g][co][j*cg + ci] = the
+ * convolution weight [g*cg + co][ci][j] and zeros in the padding columns.  bias f32 [C].  cg in {16, 32, 48, 64},
+ * (127 cg + Kp) * 2 <= 65536 bytes of LDS, N and groups <= 65535, y must not be x. */
+int mmf_w2v_posconv(const void* x_bf16, const void* w_bf16, const float* bias, void* y_bf16, int N, int T, int C, int groups, int k,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

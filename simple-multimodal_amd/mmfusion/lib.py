@@ -38,6 +38,7 @@ SYMBOLS = (
     "mmf_fewshot_proto_fwd", "mmf_fewshot_proto_bwd", "mmf_fewshot_dist_fwd", "mmf_fewshot_dist_bwd",
     "mmf_eval_accumulate",
     "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16",
+    "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
 )
 
 
@@ -203,6 +204,10 @@ def load() -> C.CDLL:
     lib.mmf_vit_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_vit_embed_tokens.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mmf_bias_gelu_bf16.argtypes = [vp, vp, i64, i32, i32, vp]
+    lib.mmf_w2v_conv0_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_conv0_norm_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.mmf_w2v_gelu_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_posconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -365,3 +370,76 @@ def bias_gelu(x, bias=None) -> None:
     with _Timed("bias_gelu_kernel", 0.0, [tuple(x.shape)]):
         check(load().mmf_bias_gelu_bf16(x.data_ptr(), bias.data_ptr() if bias is not None else None, x.shape[0], x.shape[1],
                                         x.stride(0), stream_ptr()))
+
+
+# ---- Wav2Vec2 kernels (csrc/wav2vec2.hip); tensors, not pointers: the shapes are checked here --------------
+W2V_STATS_SLOTS = 128            # MMF_W2V_STATS_SLOTS of include/mmfusion.h (tests/test_w2v_cpu.py compares the two)
+
+
+def _w2v_f32(*ts) -> None:
+    import torch
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("w2v kernels run on the GPU only (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("w2v: the f32 operands must be contiguous float32 tensors")
+
+
+def _w2v_bf16(*ts) -> None:
+    import torch
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("w2v kernels run on the GPU only (no CPU fallback)")
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"w2v: expected a bfloat16 operand, got {t.dtype}")
+
+
+def w2v_conv0_stats(wave, weight, stats, partial, k0: int, s0: int) -> None:
+    """wave (N, L) f32, weight (C0, 1, k0) f32 -> stats (N, 2, C0) f32: mean and biased variance of the layer-0 convolution
+    per (clip, channel); partial: N * W2V_STATS_SLOTS * 2 * C0 floats of scratch"""
+    _w2v_f32(wave, weight, stats, partial)
+    N, L = wave.shape
+    C0 = weight.shape[0]
+    if weight.numel() != C0 * k0 or stats.numel() < N * 2 * C0 or partial.numel() < N * W2V_STATS_SLOTS * 2 * C0:
+        raise ValueError("w2v_conv0_stats: operand sizes do not match N, C0, k0")
+    with _Timed("w2v_conv0_stats_kernels", 2.0 * N * ((L - k0) // s0 + 1) * C0 * k0, [(N, L)]):
+        check(load().mmf_w2v_conv0_stats(wave.data_ptr(), weight.data_ptr(), stats.data_ptr(), partial.data_ptr(), N, L, C0, k0, s0,
+                                         stream_ptr()))
+
+
+def w2v_conv0_norm_gelu(wave, weight, stats, gamma, beta, out, k0: int, s0: int, k1: int, s1: int, eps: float) -> None:
+    """-> out (N, T1, k1 * C0) bf16: gelu(groupnorm(conv0(wave))) in the window form of the next conv layer"""
+    _w2v_f32(wave, weight, stats, gamma, beta)
+    _w2v_bf16(out)
+    N, L = wave.shape
+    C0 = weight.shape[0]
+    T1 = (((L - k0) // s0 + 1) - k1) // s1 + 1
+    if weight.numel() != C0 * k0 or stats.numel() < N * 2 * C0 or gamma.numel() != C0 or beta.numel() != C0 \
+            or T1 < 1 or out.numel() < N * T1 * k1 * C0 or not out.is_contiguous():
+        raise ValueError("w2v_conv0_norm_gelu: operand sizes do not match N, L, C0 and the two kernels")
+    with _Timed("w2v_conv0_norm_gelu_kernel", 2.0 * N * ((L - k0) // s0 + 1) * C0 * k0, [(N, L)]):
+        check(load().mmf_w2v_conv0_norm_gelu(wave.data_ptr(), weight.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                             out.data_ptr(), N, L, C0, k0, s0, k1, s1, eps, stream_ptr()))
+
+
+def w2v_gelu_window(x, out, N: int, T_in: int, C: int, k: int, s: int) -> None:
+    """x (N, T_in, C) bf16 -> out (N, T_out, k * C) bf16, out[n][t][j*C + c] = gelu(x[n][s*t + j][c])"""
+    _w2v_bf16(x, out)
+    T_out = (T_in - k) // s + 1
+    if x.numel() < N * T_in * C or not x.is_contiguous() or T_out < 1 or out.numel() < N * T_out * k * C or not out.is_contiguous():
+        raise ValueError("w2v_gelu_window: operand sizes do not match N, T_in, C, k, s")
+    with _Timed("w2v_gelu_window_kernel", 0.0, [(N * T_out, k * C)]):
+        check(load().mmf_w2v_gelu_window(x.data_ptr(), out.data_ptr(), N, T_in, C, k, s, stream_ptr()))
+
+
+def w2v_posconv(x, w, bias, y, N: int, T: int, C: int, groups: int, k: int) -> None:
+    """y = x + gelu(grouped_conv(x) + bias) on (N, T, C) bf16; w (groups, C / groups, Kp) bf16 repacked (include/mmfusion.h)"""
+    _w2v_bf16(x, w, y)
+    _w2v_f32(bias)
+    cg = C // max(groups, 1)
+    Kp = (k * cg + 31) // 32 * 32
+    if x.numel() < N * T * C or y.numel() < N * T * C or w.numel() != C * Kp or bias.numel() != C or not (
+            x.is_contiguous() and y.is_contiguous() and w.is_contiguous() and bias.is_contiguous()):
+        raise ValueError("w2v_posconv: operand sizes do not match N, T, C, groups, k")
+    with _Timed("w2v_posconv_kernel", 2.0 * N * T * C * cg * k, [(N * T, C, k * cg)]):
+        check(load().mmf_w2v_posconv(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N, T, C, groups, k, stream_ptr()))

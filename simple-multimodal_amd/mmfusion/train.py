@@ -396,7 +396,9 @@ def load_checkpoint(path: str, module: torch.nn.Module, optimizer: Optional["Fus
     checkpoint dict (epoch, metrics, scheduler_state_dict, config).
     ``video_encoder.vit.*`` keys of either HuggingFace generation (transformers 5.x ``layers.N.attention.q_proj`` or the 4.x
     ``encoder.layer.N.attention.attention.query`` of published checkpoints and reference ``.pth`` files) load into a native
-    backbone: ``mmfusion.vit.NativeViT`` renames and fuses them in its own ``load_state_dict`` hook."""
+    backbone: ``mmfusion.vit.NativeViT`` renames and fuses them in its own ``load_state_dict`` hook.  ``audio_encoder.model.*``
+    keys load into a native ``mmfusion.wav2vec2.NativeWav2Vec2`` the same way, with the positional convolution's weight norm in
+    either spelling (``parametrizations.weight.original0/1`` or ``weight_g`` / ``weight_v``)."""
     from models.multimodal_model import load_checkpoint_file
     ckpt = load_checkpoint_file(path)
     module.load_state_dict(ckpt["model_state_dict"])

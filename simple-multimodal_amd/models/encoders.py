@@ -6,13 +6,15 @@ pool -> optional ``AdapterLayer`` -> ``projection`` Linear(hidden -> fusion_hidd
 ``ModalityDropout`` (:280-321).  The projections, the adapter GEMMs and the temporal / facial
 self-attention heads run on the HIP kernels (``mmfusion.ops``).
 
-Out of scope: the HuggingFace backbones themselves (DeBERTa-v3 / Wav2Vec2 / ViT, reference :20,116,179).
-They are third-party pretrained models fetched by name; there is no network here.  The encoders
-therefore take a ``backbone`` argument:
+The HuggingFace backbones themselves (DeBERTa-v3 / Wav2Vec2 / ViT, reference :20,116,179) are third-party pretrained
+models fetched by name.  ViT and Wav2Vec2 have native, frozen, forward-only forms on the HIP kernels that need no
+network (below); DeBERTa-v3 has none.  The encoders take a ``backbone`` argument:
   * ``backbone=None`` (default) reproduces the reference: ``from_pretrained(config.*_model_name)``;
   * any ``nn.Module`` returning an object with ``.last_hidden_state`` is used as is;
   * ``config.video_backbone = "native"`` (dynamic attribute, ``VideoEncoder`` only) builds ``mmfusion.vit.NativeViT``: the
     frozen, forward-only ViT on the HIP kernels, which takes HuggingFace ``state_dict``s and needs no network;
+  * ``config.audio_backbone = "native"`` (dynamic attribute, ``AudioEncoder`` only) builds ``mmfusion.wav2vec2.NativeWav2Vec2``
+    the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers);
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -57,6 +59,16 @@ def _native_vit(config):
     kw = dict(hidden_size=config.video_hidden_size, image_size=size)
     kw.update(getattr(config, "video_backbone_kwargs", None) or {})
     return NativeViT(**kw)
+
+
+def _native_wav2vec2(config):
+    """``config.audio_backbone = "native"``: the Wav2Vec2 of ``mmfusion.wav2vec2`` on the HIP kernels, built from
+    ``config.audio_hidden_size`` with wav2vec2-base's other sizes (``config.audio_backbone_kwargs``, a dict, overrides any of
+    them); weights come from ``load_state_dict`` / a checkpoint, nothing is fetched."""
+    from mmfusion.wav2vec2 import NativeWav2Vec2
+    kw = dict(hidden_size=config.audio_hidden_size)
+    kw.update(getattr(config, "audio_backbone_kwargs", None) or {})
+    return NativeWav2Vec2(**kw)
 
 
 class AdapterLayer(_FusionBase):
@@ -158,8 +170,12 @@ class AudioEncoder(_FusionBase):
     def __init__(self, config, backbone: Optional[nn.Module] = None):
         super().__init__()
         self.config = config
+        self._native = False
         if _feature_mode(config):
             self.model, self.hidden_size = None, config.audio_hidden_size
+        elif backbone is None and getattr(config, "audio_backbone", None) == "native":
+            self.model, self._native = _native_wav2vec2(config), True
+            self.hidden_size = self.model.config.hidden_size
         else:
             self.model = backbone if backbone is not None else _load_backbone("audio", config.audio_model_name)
             self.hidden_size = self.model.config.hidden_size
@@ -169,7 +185,13 @@ class AudioEncoder(_FusionBase):
         self.dropout = nn.Dropout(config.fusion_dropout)
 
     def forward(self, waveform, use_adapter: bool = False) -> Dict[str, torch.Tensor]:
-        seq = waveform if self.model is None else self.model(waveform).last_hidden_state
+        if self.model is None:                       # feature mode: waveform holds (B, T, hidden)
+            seq = waveform
+        elif self._native:                           # the native backbone: frozen
+            with torch.no_grad():
+                seq = self.model(waveform).last_hidden_state
+        else:
+            seq = self.model(waveform).last_hidden_state
         if use_adapter and self.adapter is not None:
             seq = self.adapter(seq)
         projected, attended, weights = _mha_mean_project(self.temporal_attention, self.projection, seq,

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Cost of the native frozen Wav2Vec2 backbone (mmfusion.wav2vec2.NativeWav2Vec2, wav2vec2-base) on one batch of clips
+(default 16 clips of 160000 samples = 10 s, what the reference pushes through its backbone per step):
+
+  * ms per batch, clips/s and TFLOP/s (by operation count, printed as gflop_per_clip: feature-extractor convolutions,
+    positional convolution, 12 layers at T = 499) of ``forward``, per chunk size;
+  * the yardstick: tests/w2v_ref.py run in bf16 through stock torch (rocBLAS + torch's attention) on the same inputs with the
+    same timing loop and the same chunking;
+  * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE): time, share,
+    TFLOP/s where the wrapper counts operations.
+
+    python tools/w2v_bench.py [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--no-torch]
+Prints one JSON line (the table, when asked for, on the lines before it)."""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
+import torch
+
+
+def gflop_per_clip(cfg, L: int) -> dict:
+    from mmfusion.wav2vec2 import feat_lengths
+    Ts = feat_lengths(L, cfg.conv_kernel, cfg.conv_stride)
+    dims, ks, d, I, T = cfg.conv_dim, cfg.conv_kernel, cfg.hidden_size, cfg.intermediate_size, Ts[-1]
+    conv = 2.0 * Ts[0] * dims[0] * ks[0] + sum(2.0 * Ts[i] * dims[i] * dims[i - 1] * ks[i] for i in range(1, len(dims)))
+    pos = 2.0 * T * d * (d // cfg.num_conv_pos_embedding_groups) * cfg.num_conv_pos_embeddings
+    layers = cfg.num_hidden_layers * (2.0 * T * (4 * d * d + 2 * d * I) + 4.0 * T * T * d) + 2.0 * T * d * dims[-1]
+    return {"conv": round(conv / 1e9, 2), "posconv": round(pos / 1e9, 2), "layers": round(layers / 1e9, 2),
+            "total": round((conv + pos + layers) / 1e9, 2)}
+
+
+def time_eager(fn, steps, warmup) -> float:
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def kernel_table(fn) -> list:
+    from mmfusion import lib
+    fn()
+    torch.cuda.synchronize()
+    lib.PROFILE = []
+    try:
+        fn()
+        torch.cuda.synchronize()
+        recs = lib.PROFILE
+    finally:
+        lib.PROFILE = None
+    agg = {}
+    for label, flops, e0, e1, detail in recs:
+        key = label
+        if label.startswith("gemm") and detail:
+            key = f"{label} N={detail[0][1]} K={detail[0][2]}" + (" (+1)" if len(detail) > 1 else "")
+        row = agg.setdefault(key, {"kernel": key, "calls": 0, "ms": 0.0, "flops": 0.0})
+        row["calls"] += 1
+        row["ms"] += e0.elapsed_time(e1)
+        row["flops"] += flops
+    total = sum(r["ms"] for r in agg.values())
+    rows = sorted(agg.values(), key=lambda r: -r["ms"])
+    for r in rows:
+        r["share"] = round(r["ms"] / total, 4)
+        r["tflops"] = round(r.pop("flops") / r["ms"] / 1e9, 1) if r["flops"] else None
+        r["ms"] = round(r["ms"], 4)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=16)
+    ap.add_argument("--samples", type=int, default=160000)
+    ap.add_argument("--chunks", default="")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--table", action="store_true")
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    import w2v_ref
+    from mmfusion import wav2vec2
+    cfg = w2v_ref.base_config()
+    sd = w2v_ref.seeded_weights(cfg, seed=0)
+    model = wav2vec2.NativeWav2Vec2(**w2v_ref.config_kwargs(cfg))
+    model.load_state_dict(sd)
+    model = model.cuda().eval()
+    N, L = args.clips, args.samples
+    x = (0.5 * torch.randn(N, L, generator=torch.Generator().manual_seed(1))).cuda()
+    gf = gflop_per_clip(cfg, L)
+
+    def rate(ms: float) -> dict:
+        return {"ms": round(ms, 3), "clips_per_s": round(N / ms * 1e3, 1), "tflops": round(gf["total"] * N / ms, 1)}
+
+    res = {"model": "wav2vec2-base, frozen, bf16 storage", "clips": N, "samples": L, "frames": model.frames(L), "gflop_per_clip": gf,
+           "default_chunk": wav2vec2.DEFAULT_CHUNK, "workspace_mb_per_clip": round(model.workspace_bytes_per_clip(L) / 2 ** 20, 2)}
+    chunks = [int(c) for c in args.chunks.split(",") if c] or [wav2vec2.DEFAULT_CHUNK]
+    for c in chunks:
+        model.chunk, model._ws = c, None
+        res[f"forward_chunk{c}"] = rate(time_eager(lambda: model(x), args.steps, args.warmup))
+    model.chunk, model._ws = wav2vec2.DEFAULT_CHUNK, None
+    if args.table:
+        rows = kernel_table(lambda: model(x))
+        print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s}")
+        for r in rows:
+            print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} {r['tflops'] if r['tflops'] is not None else '':>8}")
+        res["kernels"] = rows
+    model._ws = None
+    torch.cuda.empty_cache()
+    if not args.no_torch:
+        # the yardstick: the restatement itself in bf16 through stock torch, in chunks of the same size (the same memory bound)
+        sd16 = {k: v.cuda().to(torch.bfloat16) for k, v in sd.items()}
+        x16 = x.to(torch.bfloat16)
+        c = wav2vec2.DEFAULT_CHUNK
+
+        def stock():
+            with torch.no_grad():
+                return torch.cat([w2v_ref.w2v_forward(sd16, x16[i:i + c], cfg, dtype=torch.bfloat16, sdpa=True) for i in range(0, N, c)]).float()
+        res["torch_bf16_forward"] = rate(time_eager(stock, args.steps, args.warmup))
+        res["native_over_torch"] = round(res["torch_bf16_forward"]["ms"] / res[f"forward_chunk{c}"]["ms"], 3) if f"forward_chunk{c}" in res else None
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
