@@ -314,8 +314,11 @@ int mmf_eval_accumulate(const float* const* logits, const int* ld, int n_heads, 
  * models/fusion_layers.py:161-163,204 (six cross blocks + three self blocks of MulT in ONE
  * launch) and models/encoders.py:152-154,236-238.
  * Row r = b*T + t of Q/K/V/O holds head h at columns [h*head_dim, (h+1)*head_dim).
- * head_dim in {64, 96}.  LSE (f32, [B][H][Tq]) = log sum_k exp(scale * q.k) is saved for backward.
- * Backward recomputes the probabilities; `delta` is a caller-provided f32 [B][H][Tq] workspace.
+ * head_dim in {64, 96}.  LSE[(b*H + h)*Tq + q] (f32) = ln sum_k exp(scale * q.k): the NATURAL logarithm of the sum over
+ * the keys of the exponentials of the SCALED scores (undropped under dropout), written by the forward, read by the backward.
+ * Backward recomputes the probabilities p = exp(scale * q.k - LSE).  delta[(b*H + h)*Tq + q] (f32) = sum_c O[q][c] * dO[q][c]
+ * over the head's columns, from the bf16 O and dO the backward is given: the dQ kernel writes it and the dK/dV kernel, launched
+ * behind it, reads it (dS = p * (dP - delta)); the caller provides the buffer and may read it afterwards.
  * ------------------------------------------------------------------------------------------ */
 #define MMF_ATTN_MAX_PROBLEMS 12
 typedef struct mmf_attn_problem {
@@ -324,7 +327,7 @@ typedef struct mmf_attn_problem {
   float* LSE;                                    /* f32 [B*H*Tq] */
   /* backward only (NULL in forward) */
   const void* dO;                                /* bf16, same layout as O */
-  float* delta;                                  /* f32 [B*H*Tq] workspace */
+  float* delta;                                  /* f32 [B*H*Tq], written by the backward (see above) */
   void* dQ; void* dK; void* dV;                  /* bf16, same layouts/strides as Q, K, V */
   int32_t B, H, Tq, Tk;
   int32_t ldq, ldk, ldv, ldo;                    /* row strides (elements) of Q,K,V,O (and grads) */
@@ -336,7 +339,10 @@ int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_problems, int
                          float scale, void* stream);
 /* With attention-probability dropout (nn.MultiheadAttention(dropout=p) in training mode): the
  * probabilities are dropped/rescaled before P.V, the softmax normaliser uses the undropped row sums;
- * the backward kernels regenerate the same mask from (*rng_state, site, problem, b, h, q, key). */
+ * the backward kernels regenerate the same mask from (*rng_state, site, problem, b, h, q, key): stream id
+ * problem * 4096 + b*H + h (problem = the index in `problems`, whatever order the launch works in), element q*Tk + key.
+ * A problem with B*H > 4096 would share streams with its successor, so dropout_p > 0 with B*H > 4096 is refused
+ * (MMF_E_SHAPE), in the forward and in the backward. */
 int mmf_attn_fwd_grouped_ex(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
                             float dropout_p, const uint64_t* rng_state, uint32_t site, void* stream);
 /* Tuning hook kept for ABI stability: 0 (automatic) and 2 select attention2.hip, the only implementation since round 3

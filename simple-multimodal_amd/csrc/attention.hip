@@ -30,6 +30,16 @@ int validate(const char* who, const mmf_attn_problem* p, int n, int head_dim, bo
   return MMF_OK;
 }
 
+// the dropout stream id is problem * 4096 + b*H + h: past 4096 (b, h) pairs a problem would draw its successor's masks
+int validate_dropout(const char* who, const mmf_attn_problem* p, int n, float dropout_p, const uint64_t* rng_state) {
+  if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !rng_state))
+    MMF_FAIL(MMF_E_SHAPE, "%s: dropout needs 0 <= p < 1 and an rng_state", who);
+  for (int i = 0; dropout_p > 0.f && i < n; ++i)
+    if ((long long)p[i].B * p[i].H > 4096)
+      MMF_FAIL(MMF_E_SHAPE, "%s[%d]: dropout needs B*H <= 4096 (B=%d H=%d)", who, i, p[i].B, p[i].H);
+  return MMF_OK;
+}
+
 }  // namespace
 
 int mmf_attn_fwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
@@ -48,8 +58,7 @@ extern "C" int mmf_attn_fwd_grouped_ex(const mmf_attn_problem* problems, int num
                                        float scale, float dropout_p, const uint64_t* rng_state, uint32_t site,
                                        void* stream) {
   if (int rc = validate("mmf_attn_fwd_grouped", problems, num_problems, head_dim, false)) return rc;
-  if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !rng_state))
-    MMF_FAIL(MMF_E_SHAPE, "mmf_attn_fwd_grouped_ex: dropout needs 0 <= p < 1 and an rng_state");
+  if (int rc = validate_dropout("mmf_attn_fwd_grouped_ex", problems, num_problems, dropout_p, rng_state)) return rc;
   return mmf_attn_fwd2_launch(problems, num_problems, head_dim, scale, dropout_p, rng_state, site,
                               static_cast<hipStream_t>(stream));
 }
@@ -58,8 +67,7 @@ extern "C" int mmf_attn_bwd_grouped_ex(const mmf_attn_problem* problems, int num
                                        float scale, float dropout_p, const uint64_t* rng_state, uint32_t site,
                                        void* stream) {
   if (int rc = validate("mmf_attn_bwd_grouped", problems, num_problems, head_dim, true)) return rc;
-  if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !rng_state))
-    MMF_FAIL(MMF_E_SHAPE, "mmf_attn_bwd_grouped_ex: dropout needs 0 <= p < 1 and an rng_state");
+  if (int rc = validate_dropout("mmf_attn_bwd_grouped_ex", problems, num_problems, dropout_p, rng_state)) return rc;
   return mmf_attn_bwd2_launch(problems, num_problems, head_dim, scale, dropout_p, rng_state, site,
                               static_cast<hipStream_t>(stream));
 }

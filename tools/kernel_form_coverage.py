@@ -8,6 +8,9 @@ embedded code objects with `strings` and `c++filt`, so this runs on a machine wi
 --only keeps the instantiations whose name matches REGEX (the families a run targets, e.g. 'ln_|skinny_dgrad').
 For a trace of tests/test_streaming_small_gpu.py (the kernels of elementwise.hip, small.hip and optim.hip it pins):
     --only '^(cast_|add3|addn_|relu_bwd|dropout_kernel|meanpool|colsum|zero_ranges|gat3_|nce_|ada_|attn_weights_mean|narrow_|stack3_|rowmask|sqnorm|adamw)'
+For a trace of tests/test_attention_paths_gpu.py (the twelve instantiations of attention2.hip: forward, dQ and dK/dV, each at
+head_dim 64 and 96, each with and without dropout; profiles/attention_form_coverage.txt):
+    --only '^attn_(fwd|bwd)'    (attn_weights_mean_kernel of small.hip belongs to the streaming file's list above)
 Exit status 1 if an instantiation outside DELIBERATELY_UNLAUNCHED was never launched.
 """
 import argparse
