@@ -1,0 +1,206 @@
+"""What the frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2``) share: the table of frozen
+parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, and the launches of a transformer layer.
+
+A layer is two blocks on ``rows = n * T`` tokens of a chunk of ``n`` items (bf16 residual stream like MulT's); where its
+LayerNorms go around them is the subclass's ``_layer``:
+
+    _attention(src, resid):
+      fused Q/K/V linear + bias     mmf_gemm_grouped NT, BIAS            src -> qkv (rows, 3 d)
+      attention, H heads of 64/96   mmf_attn_fwd_grouped                 qkv -> att
+      out-projection + bias + resid mmf_gemm_grouped NT, BIAS | ADD_AUX  att -> y
+    _ffn(src, resid, out):
+      fc1                           mmf_gemm_grouped NT                  src -> h (rows, intermediate)
+      + bias, exact GELU            mmf_bias_gelu_bf16 (in place)        h
+      fc2 + bias + resid            mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> out
+    _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
+    _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
+
+Parameters are stored as the kernels read them (Q/K/V fused, a subclass may store a weight with its last two dims swapped)
+and ``_hf`` maps every HuggingFace key to its view of them, in HuggingFace's order, so ``state_dict()`` and
+``load_state_dict`` speak HuggingFace's names and shapes.  A subclass declares its workspace as a table of
+(name, elements per chunk item, dtype); the allocation and the bytes-per-item figure are both read from that table.
+
+Forward only and frozen: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  bf16
+storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
+Nothing synchronises with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import lib, ops
+from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NT, AttnProblem, LnProblem
+
+BF16 = torch.bfloat16
+LN_WIDTHS = (256, 512, 768, 1024)          # the lane forms of layernorm.hip
+WsTable = List[Tuple[str, int, torch.dtype]]
+
+
+class BackboneOutput:
+    """What the encoders read from a backbone's result."""
+
+    def __init__(self, last_hidden_state: torch.Tensor):
+        self.last_hidden_state = last_hidden_state
+        self.pooler_output = None
+
+
+class FrozenBackbone(nn.Module):
+    """Base of the native backbones.  A subclass sets ``self.config`` (``hidden_size``, ``num_attention_heads``,
+    ``intermediate_size``, ``layer_norm_eps``), registers its parameters with ``_add`` / ``_add_qkv`` in HuggingFace's
+    order, and names its layer parameters ``l{i}_{qkv,o,fc1,fc2}_{w,b}``."""
+
+    def __init__(self, hidden_size: int, num_attention_heads: int, chunk: int):
+        super().__init__()
+        d, H, who = hidden_size, num_attention_heads, type(self).__name__
+        if H <= 0 or d % H or d // H not in (64, 96):
+            raise ValueError(f"{who}: hidden_size {d} / num_attention_heads {H} must give a head_dim of 64 or 96 "
+                             "(the fused attention kernel's forms)")
+        if d not in LN_WIDTHS:
+            raise ValueError(f"{who}: hidden_size {d} is not one of the LayerNorm kernel's widths {LN_WIDTHS}")
+        self.chunk = int(chunk)
+        self.head_dim = d // H
+        # HuggingFace key -> (parameter, row range | None, stored with the last two dims swapped)
+        self._hf: Dict[str, Tuple[str, Optional[Tuple[int, int]], bool]] = {}
+        self._ws: Optional[dict] = None
+
+    # -- parameter table --------------------------------------------------------------------------------
+    def _add(self, name: str, shape, key: Optional[str] = None, *, ones: bool = False, std: float = 0.02, swapped: bool = False):
+        p = nn.Parameter(torch.empty(shape), requires_grad=False)
+        if ones:
+            nn.init.ones_(p)
+        elif std > 0:
+            nn.init.normal_(p, std=std)
+        else:
+            nn.init.zeros_(p)
+        self.register_parameter(name, p)
+        if key is not None:
+            self._hf[key] = (name, None, swapped)
+
+    def _add_qkv(self, i: int, prefix: str, order: str, d: int) -> None:
+        """layer ``i``'s fused (3 d, d) projection, rows q | k | v; ``order`` is the order of HuggingFace's three keys"""
+        for n in order:
+            r = "qkv".index(n)
+            self._hf[f"{prefix}{n}_proj.weight"] = (f"l{i}_qkv_w", (r * d, r * d + d), False)
+            self._hf[f"{prefix}{n}_proj.bias"] = (f"l{i}_qkv_b", (r * d, r * d + d), False)
+        self._add(f"l{i}_qkv_w", (3 * d, d))
+        self._add(f"l{i}_qkv_b", (3 * d,), std=0.0)
+
+    # -- HuggingFace state_dict surface ----------------------------------------------------------------
+    def _canonical_key(self, key: str) -> str:
+        """a checkpoint's key in the spelling of ``_hf`` (a subclass that reads older spellings overrides this)"""
+        return key
+
+    def _view(self, name: str, rows, swapped: bool, keep_vars: bool = False) -> torch.Tensor:
+        p = getattr(self, name)
+        t = p if keep_vars else p.detach()
+        if rows is not None:
+            t = t[rows[0]:rows[1]]
+        return t.permute(0, 2, 1) if swapped else t
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        for key, (name, rows, swapped) in self._hf.items():
+            destination[prefix + key] = self._view(name, rows, swapped, keep_vars)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        found = {}
+        for key in list(state_dict.keys()):
+            if not key.startswith(prefix):
+                continue
+            k = self._canonical_key(key[len(prefix):])
+            if k in self._hf:
+                found[k] = state_dict[key]
+            elif strict:
+                unexpected_keys.append(key)
+        with torch.no_grad():
+            for k, (name, rows, swapped) in self._hf.items():
+                if k not in found:
+                    missing_keys.append(prefix + k)
+                    continue
+                dst, src = self._view(name, rows, swapped), found[k]
+                if tuple(src.shape) != tuple(dst.shape):
+                    error_msgs.append(f"size mismatch for {prefix + k}: copying a param with shape {tuple(src.shape)} from "
+                                      f"checkpoint, the shape in current model is {tuple(dst.shape)}.")
+                    continue
+                dst.copy_(src)                 # in place: the version counter moves, so what was derived from the old value is rebuilt
+
+    # -- workspace --------------------------------------------------------------------------------------
+    def _token_table(self, T: int, h: int) -> WsTable:
+        """the layers' buffers for one item of ``T`` tokens; ``h`` elements for the MLP's hidden activations"""
+        d, H = self.config.hidden_size, self.config.num_attention_heads
+        return [("x", T * d, BF16), ("y", T * d, BF16), ("ln", T * d, BF16), ("att", T * d, BF16), ("qkv", T * 3 * d, BF16),
+                ("h", h, BF16), ("mean", T, torch.float32), ("rstd", T, torch.float32), ("lse", H * T, torch.float32)]
+
+    @staticmethod
+    def _bytes_per_item(table: WsTable) -> int:
+        return sum(numel * dtype.itemsize for _, numel, dtype in table)
+
+    def _allocate(self, dev, table: WsTable, **keys) -> dict:
+        """a new workspace of ``self.chunk`` items; ``keys``: what else the subclass's cache-validity rule reads"""
+        ws = {"dev": dev, "chunk": self.chunk, **keys}
+        for name, numel, dtype in table:
+            ws[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
+        self._ws = ws
+        return ws
+
+    @staticmethod
+    def _rows(ws, name: str, rows: int, width: int) -> torch.Tensor:
+        """the leading (rows, width) of a workspace buffer"""
+        return ws[name][:rows * width].view(rows, width)
+
+    # -- launches ---------------------------------------------------------------------------------------
+    def _check_input(self, x, name: str) -> None:
+        who = type(self).__name__
+        if ops.fp32_mode():
+            raise RuntimeError(f"{who} runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback)")
+        if x.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be float32, got {x.dtype}")
+
+    def _w(self, name: str) -> torch.Tensor:
+        return ops.shadow(getattr(self, name))
+
+    def _f(self, name: str) -> torch.Tensor:
+        return getattr(self, name).detach()
+
+    def _ln(self, ws, src: torch.Tensor, dst: torch.Tensor, gamma: str, beta: str) -> None:
+        rows, width = src.shape
+        with lib._Timed("ln_fwd_kernel", 0.0, [(rows, width)]):
+            lib.layernorm_fwd_grouped([LnProblem(src.data_ptr(), dst.data_ptr(), self._f(gamma).data_ptr(), self._f(beta).data_ptr(),
+                                                 ws["mean"].data_ptr(), ws["rstd"].data_ptr(), None, None, None, None, rows)],
+                                      width, self.config.layer_norm_eps)
+
+    def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
+        """attention of ``Tq`` queries per item over its ``T`` keys, read from the fused ``qkv`` rows; ``Tq == 1`` takes the
+        query of each item's first row"""
+        c, d = self.config, self.config.hidden_size
+        base = qkv.data_ptr()
+        lib.attn_fwd_grouped([AttnProblem(base, base + 2 * d, base + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), None, None, None,
+                                          None, None, n, c.num_attention_heads, Tq, T, 3 * d if Tq == T else T * 3 * d, 3 * d, 3 * d, d)],
+                             self.head_dim, self.head_dim ** -0.5)
+
+    def _out_proj(self, i: int, att: torch.Tensor, resid: torch.Tensor, y: torch.Tensor) -> None:
+        ops.gemm(GEMM_NT, att, self._w(f"l{i}_o_w"), y, bias=self._f(f"l{i}_o_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
+
+    def _attention(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, n: int, T: int) -> torch.Tensor:
+        """-> y = resid + out_proj(attention(qkv(src))) on the ``n * T`` rows of a chunk"""
+        rows, d = n * T, self.config.hidden_size
+        qkv, att, y = self._rows(ws, "qkv", rows, 3 * d), self._rows(ws, "att", rows, d), self._rows(ws, "y", rows, d)
+        ops.gemm(GEMM_NT, src, self._w(f"l{i}_qkv_w"), qkv, bias=self._f(f"l{i}_qkv_b"), epilogue=EPI_BIAS)
+        self._attn(ws, qkv, att, n, T, T)
+        self._out_proj(i, att, resid, y)
+        return y
+
+    def _ffn(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, out: torch.Tensor) -> None:
+        """out = resid + fc2(gelu(fc1(src) + b1)) + b2 on the rows of ``src``"""
+        h = self._rows(ws, "h", src.shape[0], self.config.intermediate_size)
+        ops.gemm(GEMM_NT, src, self._w(f"l{i}_fc1_w"), h)
+        lib.bias_gelu(h, self._f(f"l{i}_fc1_b"))
+        ops.gemm(GEMM_NT, h, self._w(f"l{i}_fc2_w"), out, bias=self._f(f"l{i}_fc2_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
+
+    @staticmethod
+    def _widen(src: torch.Tensor, dst: torch.Tensor) -> None:
+        lib.check(lib.load().mmf_cast_bf16_to_f32(src.data_ptr(), dst.data_ptr(), src.numel(), lib.stream_ptr()))

@@ -6,7 +6,7 @@ surface, so published checkpoints and the reference's ``.pth`` files load.  Only
 feature extractor without conv biases, post-LN encoder.
 
 Activations are channel-last ``(time, channels)`` bf16, so a convolution over time is one GEMM over a window form and the
-transformer needs no transpose.  Launch list for a chunk of ``n`` clips:
+transformer needs no transpose.  Launch list for a chunk of ``n`` clips (the layer's two blocks: mmfusion/backbone.py):
 
     conv layer 0 statistics       mmf_w2v_conv0_stats                  wave -> mean / variance per (clip, channel)
     conv 0 + GroupNorm + GELU     mmf_w2v_conv0_norm_gelu              wave -> window form of layer 1
@@ -18,20 +18,15 @@ transformer needs no transpose.  Launch list for a chunk of ``n`` clips:
     x + gelu(pos_conv(x) + b)     mmf_w2v_posconv                      x -> y
     LayerNorm                                                          y -> x
     per post-LN layer:
-      fused Q/K/V linear + bias   mmf_gemm_grouped NT, BIAS            x   -> qkv
-      attention                   mmf_attn_fwd_grouped                 qkv -> att
-      out-projection + bias + x   mmf_gemm_grouped NT, BIAS | ADD_AUX  att -> y
-      LayerNorm                                                        y   -> ln
-      fc1                         mmf_gemm_grouped NT                  ln  -> h
-      + bias, exact GELU          mmf_bias_gelu_bf16 (in place)        h
-      fc2 + bias + ln             mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> y
-      LayerNorm                                                        y   -> x
-    widening cast                 mmf_cast_bf16_to_f32                 x   -> result
+      _attention(x, + x)                                               x  -> qkv -> att -> y
+      LayerNorm                                                        y  -> ln
+      _ffn(ln, + ln)                                                   ln -> h -> y
+      LayerNorm                                                        y  -> x
+    widening cast                 mmf_cast_bf16_to_f32                 x  -> result
 
 Clips are processed in chunks of ``chunk`` through one workspace sized by the chunk and the longest waveform seen so far
-(a longer one reallocates it once; shorter ones use its leading part).  Nothing synchronises
-with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.  Forward only and frozen; bf16 storage only: in
-the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
+(a longer one reallocates it once; shorter ones use its leading part).  Forward only, frozen, bf16 storage only, nothing
+synchronises with the host (mmfusion/backbone.py).
 """
 from __future__ import annotations
 
@@ -39,17 +34,15 @@ import types
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import arena as _arena
 from . import lib, ops
-from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NT, AttnProblem, LnProblem
+from .backbone import BF16, LN_WIDTHS, BackboneOutput, FrozenBackbone, WsTable
+from .lib import EPI_BIAS, GEMM_NT
 
-BF16 = torch.bfloat16
 # clips per pass through the workspace.  NOT chosen by measurement yet: 8 clips keep the workspace at 0.57 GB for 10 s clips
 # and give the layer GEMMs 3992 rows; tools/w2v_bench.py --chunks is the sweep that should decide it
 DEFAULT_CHUNK = 16
-LN_WIDTHS = (256, 512, 768, 1024)          # the lane forms of layernorm.hip
 POS_GROUP_WIDTHS = (16, 32, 48, 64)        # the forms of mmf_w2v_posconv
 
 _WN = "encoder.pos_conv_embed.conv."
@@ -57,13 +50,6 @@ _WN_NEW = (_WN + "parametrizations.weight.original0", _WN + "parametrizations.we
 _WN_OLD = (_WN + "weight_g", _WN + "weight_v")
 _WN_TO_NEW = dict(zip(_WN_OLD, _WN_NEW))
 _WN_TO_OLD = dict(zip(_WN_NEW, _WN_OLD))
-
-
-class Wav2Vec2Output:
-    """What the encoders read from a backbone's result."""
-
-    def __init__(self, last_hidden_state: torch.Tensor):
-        self.last_hidden_state = last_hidden_state
 
 
 def feat_lengths(L: int, kernels: Sequence[int], strides: Sequence[int]) -> List[int]:
@@ -75,7 +61,7 @@ def feat_lengths(L: int, kernels: Sequence[int], strides: Sequence[int]) -> List
     return out
 
 
-class NativeWav2Vec2(nn.Module):
+class NativeWav2Vec2(FrozenBackbone):
     """HuggingFace ``Wav2Vec2Model`` (inference, no mask), defaults = wav2vec2-base.
 
     ``forward(input_values)`` -> ``.last_hidden_state`` (N, T, hidden) f32; ``input_values``: (N, L) f32 on the GPU.
@@ -89,7 +75,6 @@ class NativeWav2Vec2(nn.Module):
                  conv_bias: bool = False, num_conv_pos_embeddings: int = 128, num_conv_pos_embedding_groups: int = 16,
                  layer_norm_eps: float = 1e-5, feat_extract_norm: str = "group", do_stable_layer_norm: bool = False,
                  in_channels: int = 1, chunk: int = DEFAULT_CHUNK):
-        super().__init__()
         d, H, I = int(hidden_size), int(num_attention_heads), int(intermediate_size)
         dims, ks, ss = tuple(int(v) for v in conv_dim), tuple(int(v) for v in conv_kernel), tuple(int(v) for v in conv_stride)
         pk, pg = int(num_conv_pos_embeddings), int(num_conv_pos_embedding_groups)
@@ -100,13 +85,11 @@ class NativeWav2Vec2(nn.Module):
             raise ValueError(f"{who}: do_stable_layer_norm=True (the large-lv60 family) is not built")
         if conv_bias:
             raise ValueError(f"{who}: conv_bias=True is not built (the base family has no conv biases)")
-        if H <= 0 or d % H or d // H not in (64, 96):
-            raise ValueError(f"{who}: hidden_size {d} / num_attention_heads {H} must give a head_dim of 64 or 96 "
-                             "(the fused attention kernel's forms)")
         if not (len(dims) == len(ks) == len(ss)) or len(dims) < 2 or min(dims + ks + ss) < 1:
             raise ValueError(f"{who}: conv_dim, conv_kernel and conv_stride must be positive and of one length of at least 2")
-        if d not in LN_WIDTHS or dims[-1] not in LN_WIDTHS:
+        if d not in LN_WIDTHS or dims[-1] not in LN_WIDTHS:        # (ahead of the base's check of d alone: this one names both)
             raise ValueError(f"{who}: hidden_size {d} and conv_dim[-1] {dims[-1]} must be among the LayerNorm kernel's widths {LN_WIDTHS}")
+        super().__init__(d, H, chunk)
         if in_channels != 1:
             raise ValueError(f"{who}: the first conv layer takes one input channel (a waveform), not {in_channels}")
         if ks[0] > 16 or dims[0] > 2048:
@@ -131,23 +114,8 @@ class NativeWav2Vec2(nn.Module):
             conv_kernel=ks, conv_stride=ss, conv_bias=False, num_conv_pos_embeddings=pk, num_conv_pos_embedding_groups=pg,
             layer_norm_eps=float(layer_norm_eps), feat_extract_norm="group", do_stable_layer_norm=False, hidden_act="gelu",
             feat_extract_activation="gelu", num_feat_extract_layers=len(dims), model_type="wav2vec2")
-        self.chunk = int(chunk)
-        self.head_dim, self.pos_cg, self.pos_kp = d // H, cg, kp
-        # HuggingFace key -> (parameter, row range | None, stored with the last two dims swapped)
-        self._hf: Dict[str, Tuple[str, Optional[Tuple[int, int]], bool]] = {}
-
-        def add(name: str, shape, key: Optional[str], ones: bool = False, std: float = 0.02, swapped: bool = False):
-            p = nn.Parameter(torch.empty(shape), requires_grad=False)
-            if ones:
-                nn.init.ones_(p)
-            elif std > 0:
-                nn.init.normal_(p, std=std)
-            else:
-                nn.init.zeros_(p)
-            self.register_parameter(name, p)
-            if key is not None:
-                self._hf[key] = (name, None, swapped)
-
+        self.pos_cg, self.pos_kp = cg, kp
+        add = self._add
         add("masked_spec_embed", (d,), "masked_spec_embed", std=1.0)
         fe = "feature_extractor.conv_layers."
         add("conv0_w", (dims[0], 1, ks[0]), fe + "0.conv.weight", std=0.3)
@@ -169,11 +137,7 @@ class NativeWav2Vec2(nn.Module):
         for i in range(num_hidden_layers):
             a = f"encoder.layers.{i}."
             # HuggingFace's order inside a layer: k, v, q, out_proj, layer_norm, intermediate, output, final_layer_norm
-            for n, r in (("k", (d, 2 * d)), ("v", (2 * d, 3 * d)), ("q", (0, d))):
-                self._hf[f"{a}attention.{n}_proj.weight"] = (f"l{i}_qkv_w", r, False)
-                self._hf[f"{a}attention.{n}_proj.bias"] = (f"l{i}_qkv_b", r, False)
-            add(f"l{i}_qkv_w", (3 * d, d), None)
-            add(f"l{i}_qkv_b", (3 * d,), None, std=0.0)
+            self._add_qkv(i, a + "attention.", "kvq", d)
             add(f"l{i}_o_w", (d, d), a + "attention.out_proj.weight")
             add(f"l{i}_o_b", (d,), a + "attention.out_proj.bias", std=0.0)
             add(f"l{i}_ln1_w", (d,), a + "layer_norm.weight", ones=True)
@@ -184,43 +148,12 @@ class NativeWav2Vec2(nn.Module):
             add(f"l{i}_fc2_b", (d,), a + "feed_forward.output_dense.bias", std=0.0)
             add(f"l{i}_ln2_w", (d,), a + "final_layer_norm.weight", ones=True)
             add(f"l{i}_ln2_b", (d,), a + "final_layer_norm.bias", std=0.0)
-        self._ws: Optional[dict] = None
         self._pos_w16: Optional[torch.Tensor] = None
         self._pos_stamp = None
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
-    def _view(self, name: str, rows, swapped: bool, keep_vars: bool = False) -> torch.Tensor:
-        p = getattr(self, name)
-        t = p if keep_vars else p.detach()
-        if rows is not None:
-            t = t[rows[0]:rows[1]]
-        return t.permute(0, 2, 1) if swapped else t
-
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        for key, (name, rows, swapped) in self._hf.items():
-            destination[prefix + key] = self._view(name, rows, swapped, keep_vars)
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        found = {}
-        for key in list(state_dict.keys()):
-            if not key.startswith(prefix):
-                continue
-            k = _WN_TO_NEW.get(key[len(prefix):], key[len(prefix):])
-            if k in self._hf:
-                found[k] = state_dict[key]
-            elif strict:
-                unexpected_keys.append(key)
-        with torch.no_grad():
-            for k, (name, rows, swapped) in self._hf.items():
-                if k not in found:
-                    missing_keys.append(prefix + k)
-                    continue
-                dst, src = self._view(name, rows, swapped), found[k]
-                if tuple(src.shape) != tuple(dst.shape):
-                    error_msgs.append(f"size mismatch for {prefix + k}: copying a param with shape {tuple(src.shape)} from "
-                                      f"checkpoint, the shape in current model is {tuple(dst.shape)}.")
-                    continue
-                dst.copy_(src)                 # in place: the version counter moves, so the shadow is re-cast and the weight norm re-folded
+    def _canonical_key(self, key: str) -> str:
+        return _WN_TO_NEW.get(key, key)
 
     def hf_state_dict(self, legacy_weight_norm: bool = False) -> Dict[str, torch.Tensor]:
         """``state_dict()`` with the positional convolution's weight norm spelled as current torch does
@@ -242,38 +175,23 @@ class NativeWav2Vec2(nn.Module):
         raw = max(Ts[i] * c.conv_dim[i] for i in range(1, n))
         return win, raw
 
-    def workspace_bytes_per_clip(self, L: int) -> int:
-        c = self.config
-        T, d = self.frames(L), c.hidden_size
+    def _ws_table(self, L: int) -> WsTable:
+        """per clip of ``L`` samples"""
+        c, T = self.config, self.frames(L)
         win, raw = self._conv_elements(L)
-        return 2 * (win + raw + T * (4 * d + 3 * d + c.intermediate_size)) \
-            + 4 * (2 * T + c.num_attention_heads * T + (2 + 2 * lib.W2V_STATS_SLOTS) * c.conv_dim[0])
+        return [("win", win, BF16), ("raw", raw, BF16)] + self._token_table(T, T * c.intermediate_size) \
+            + [("stats", 2 * c.conv_dim[0], torch.float32), ("partial", lib.W2V_STATS_SLOTS * 2 * c.conv_dim[0], torch.float32)]
+
+    def workspace_bytes_per_clip(self, L: int) -> int:
+        return self._bytes_per_item(self._ws_table(L))
 
     def _workspace(self, dev, L: int) -> dict:
         ws = self._ws
         if ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk and ws["L"] >= L:
             return ws                                        # every buffer grows with L: a shorter clip uses the leading part
-        c, n, d = self.config, self.chunk, self.config.hidden_size
-        rows = n * self.frames(L)
-        win, raw = self._conv_elements(L)
-
-        def buf(numel, dtype=BF16):
-            return torch.empty(numel, dtype=dtype, device=dev)
-        ws = {"dev": dev, "chunk": n, "L": L, "win": buf(n * win), "raw": buf(n * raw), "x": buf(rows * d), "y": buf(rows * d),
-              "ln": buf(rows * d), "att": buf(rows * d), "qkv": buf(rows * 3 * d), "h": buf(rows * c.intermediate_size),
-              "mean": buf(rows, torch.float32), "rstd": buf(rows, torch.float32),
-              "lse": buf(rows * c.num_attention_heads, torch.float32), "stats": buf(n * 2 * c.conv_dim[0], torch.float32),
-              "partial": buf(n * lib.W2V_STATS_SLOTS * 2 * c.conv_dim[0], torch.float32)}
-        self._ws = ws
-        return ws
+        return self._allocate(dev, self._ws_table(L), L=L)
 
     # -- weights ----------------------------------------------------------------------------------------
-    def _w(self, name: str) -> torch.Tensor:
-        return ops.shadow(getattr(self, name))
-
-    def _f(self, name: str) -> torch.Tensor:
-        return getattr(self, name).detach()
-
     def _pos_weight(self) -> torch.Tensor:
         """The positional convolution's effective weight g v / ||v|| (norm over dims (0, 1) per tap, ``weight_norm(dim=2)``),
         folded in f32, repacked to (groups, cg, Kp) column (tap, channel) and rounded to bf16 once per weight version."""
@@ -289,13 +207,6 @@ class NativeWav2Vec2(nn.Module):
         return self._pos_w16
 
     # -- launches ---------------------------------------------------------------------------------------
-    def _ln(self, ws, src: torch.Tensor, dst: torch.Tensor, gamma: str, beta: str) -> None:
-        rows, width = src.shape
-        with lib._Timed("ln_fwd_kernel", 0.0, [(rows, width)]):
-            lib.layernorm_fwd_grouped([LnProblem(src.data_ptr(), dst.data_ptr(), self._f(gamma).data_ptr(), self._f(beta).data_ptr(),
-                                                 ws["mean"].data_ptr(), ws["rstd"].data_ptr(), None, None, None, None, rows)],
-                                      width, self.config.layer_norm_eps)
-
     def _features(self, ws, wave: torch.Tensor, n: int, Ts: List[int]) -> torch.Tensor:
         """the feature extractor: wave (n, L) f32 -> (n * T, conv_dim[-1]) bf16 after the last layer's GELU"""
         c = self.config
@@ -307,8 +218,7 @@ class NativeWav2Vec2(nn.Module):
         last = len(dims) - 1
         for i in range(1, last + 1):
             rows, K = n * Ts[i], ks[i] * dims[i - 1]
-            win = ws["win"][:rows * K].view(rows, K)
-            raw = ws["raw"][:rows * dims[i]].view(rows, dims[i])
+            win, raw = self._rows(ws, "win", rows, K), self._rows(ws, "raw", rows, dims[i])
             ops.gemm(GEMM_NT, win, self._w(f"conv{i}_w").view(dims[i], K), raw)
             if i < last:
                 lib.w2v_gelu_window(ws["raw"], ws["win"], n, Ts[i], dims[i], ks[i + 1], ss[i + 1])
@@ -317,32 +227,18 @@ class NativeWav2Vec2(nn.Module):
         return raw
 
     def _layer(self, i: int, ws, n: int, T: int) -> None:
-        c, d, I = self.config, self.config.hidden_size, self.config.intermediate_size
-        rows = n * T
-        x, y, ln, att = (ws[k][:rows * d].view(rows, d) for k in ("x", "y", "ln", "att"))
-        qkv, h = ws["qkv"][:rows * 3 * d].view(rows, 3 * d), ws["h"][:rows * I].view(rows, I)
-        ops.gemm(GEMM_NT, x, self._w(f"l{i}_qkv_w"), qkv, bias=self._f(f"l{i}_qkv_b"), epilogue=EPI_BIAS)
-        base = qkv.data_ptr()
-        lib.attn_fwd_grouped([AttnProblem(base, base + 2 * d, base + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), None, None, None,
-                                          None, None, n, c.num_attention_heads, T, T, 3 * d, 3 * d, 3 * d, d)],
-                             self.head_dim, self.head_dim ** -0.5)
-        ops.gemm(GEMM_NT, att, self._w(f"l{i}_o_w"), y, bias=self._f(f"l{i}_o_b"), aux=x, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        rows, d = n * T, self.config.hidden_size
+        x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
+        y = self._attention(i, ws, x, x, n, T)
         self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        ops.gemm(GEMM_NT, ln, self._w(f"l{i}_fc1_w"), h)
-        lib.bias_gelu(h, self._f(f"l{i}_fc1_b"))
-        ops.gemm(GEMM_NT, h, self._w(f"l{i}_fc2_w"), y, bias=self._f(f"l{i}_fc2_b"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        self._ffn(i, ws, ln, ln, y)
         self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
 
-    def forward(self, input_values: torch.Tensor, attention_mask=None) -> Wav2Vec2Output:
+    def forward(self, input_values: torch.Tensor, attention_mask=None) -> BackboneOutput:
         c = self.config
         if attention_mask is not None:
             raise NotImplementedError("NativeWav2Vec2: attention_mask is not implemented (the reference never passes one)")
-        if ops.fp32_mode():
-            raise RuntimeError("NativeWav2Vec2 runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
-        if not isinstance(input_values, torch.Tensor) or not input_values.is_cuda:
-            raise RuntimeError("NativeWav2Vec2 runs on the GPU only (no CPU fallback)")
-        if input_values.dtype != torch.float32:
-            raise TypeError(f"NativeWav2Vec2: input_values must be float32, got {input_values.dtype}")
+        self._check_input(input_values, "input_values")
         if input_values.dim() != 2:
             raise ValueError(f"NativeWav2Vec2: input_values {tuple(input_values.shape)} is not (N, L)")
         N, L = input_values.shape
@@ -359,13 +255,13 @@ class NativeWav2Vec2(nn.Module):
             n = min(self.chunk, N - n0)
             rows = n * T
             feat = self._features(ws, wave[n0:n0 + n], n, Ts)
-            x, y = (ws[k][:rows * d].view(rows, d) for k in ("x", "y"))
-            fln = ws["win"][:rows * feat.shape[1]].view(rows, feat.shape[1])
+            x, y = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d)
+            fln = self._rows(ws, "win", rows, feat.shape[1])
             self._ln(ws, feat, fln, "fp_ln_w", "fp_ln_b")
             ops.gemm(GEMM_NT, fln, self._w("fp_w"), x, bias=self._f("fp_b"), epilogue=EPI_BIAS)
             lib.w2v_posconv(x, pos_w, self._f("pos_b"), y, n, T, d, c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings)
             self._ln(ws, y, x, "enc_ln_w", "enc_ln_b")
             for i in range(c.num_hidden_layers):
                 self._layer(i, ws, n, T)
-            lib.check(lib.load().mmf_cast_bf16_to_f32(x.data_ptr(), out[n0:n0 + n].data_ptr(), rows * d, lib.stream_ptr()))
-        return Wav2Vec2Output(out)
+            self._widen(x, out[n0:n0 + n])
+        return BackboneOutput(out)

@@ -1,0 +1,143 @@
+"""GPU: the launch sequence of the two frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2``)
+is the one their module docstrings list: every launch that ``mmfusion.lib`` records while ``lib.PROFILE`` is a list, in
+order, with the shapes it records.
+
+The expected lists are written out here from the configuration's sizes alone; nothing below asks the modules under test
+for a size.  GEMM labels are reduced to layout and output dtype (which kernel generation the dispatch chose is not this
+test's business).  Launches that are not recorded (the widening cast into the result, the bf16 shadow cast of the
+weights) are not expected.  One full chunk and one short chunk each."""
+import re
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import vit_ref  # noqa: E402
+import w2v_ref  # noqa: E402
+
+N, CHUNK, SAMPLES = 3, 2, 4000
+_GEMM = re.compile(r"^gemm\d*_grouped_kernel<(\w+),(\w+)>$")
+
+
+def _recorded(fn):
+    from mmfusion import lib
+    fn()                                                                              # warm-up: workspace, shadow casts
+    torch.cuda.synchronize()
+    lib.PROFILE = []
+    try:
+        fn()
+        torch.cuda.synchronize()
+        recs = lib.PROFILE
+    finally:
+        lib.PROFILE = None
+    out = []
+    for label, _flops, _e0, _e1, detail in recs:
+        m = _GEMM.match(label)
+        out.append((f"gemm<{m.group(1)},{m.group(2)}>" if m else label, tuple(tuple(int(v) for v in d) for d in detail)))
+    return out
+
+
+def _assert_same(got, want):
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"launch {i}: recorded {g}, expected {w}"
+    k = min(len(got), len(want))
+    assert len(got) == len(want), f"{len(got)} launches recorded, {len(want)} expected; the first one over: {(got[k:] + want[k:])[0]}"
+
+
+def gemm(*mnk):
+    return ("gemm<NT,bf16>", tuple(mnk))
+
+
+def ln(rows, width):
+    return ("ln_fwd_kernel", ((rows, width),))
+
+
+def gelu(rows, cols):
+    return ("bias_gelu_kernel", ((rows, cols),))
+
+
+def attn(head_dim, Tq, Tk):
+    return (f"attn_fwd_kernel<{head_dim}>", ((Tq, Tk),))
+
+
+def _chunks():
+    return [min(CHUNK, N - n0) for n0 in range(0, N, CHUNK)]
+
+
+# ---- ViT ---------------------------------------------------------------------------------------------------
+def _vit_expected(cfg, cls_only):
+    d, I, H, C, S, P = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_channels, cfg.image_size, cfg.patch_size
+    NP = (S // P) ** 2
+    T, hd = NP + 1, d // H
+    want = []
+    for n in _chunks():
+        rows = n * T
+        want += [("vit_patchify_kernel", ((n, C * S * S),)), gemm((n * NP, d, C * P * P)), ("vit_embed_tokens_kernel", ((rows, d),))]
+        full = [ln(rows, d), gemm((rows, 3 * d, d)), attn(hd, T, T), gemm((rows, d, d)),
+                ln(rows, d), gemm((rows, I, d)), gelu(rows, I), gemm((rows, d, I))]
+        if not cls_only:
+            want += full * cfg.num_hidden_layers + [ln(rows, d)]
+            continue
+        want += full * (cfg.num_hidden_layers - 1)
+        # the last layer: K / V for every token and Q for row 0 of each image in one grouped launch, the rest on n rows
+        want += [ln(rows, d), gemm((rows, 2 * d, d), (n, d, d)), attn(hd, 1, T), gemm((n, d, d)),
+                 ln(n, d), gemm((n, I, d)), gelu(n, I), gemm((n, d, I)), ln(n, d)]
+    return want
+
+
+@pytest.fixture(scope="module")
+def vit_case():
+    from mmfusion.vit import NativeViT
+    cfg = vit_ref.tiny_config()
+    m = NativeViT(**vit_ref.config_kwargs(cfg), chunk=CHUNK)
+    m.load_state_dict(vit_ref.seeded_weights(cfg, seed=21))
+    x = torch.rand(N, cfg.num_channels, cfg.image_size, cfg.image_size, generator=torch.Generator().manual_seed(22))
+    return cfg, m.cuda().eval(), x.cuda()
+
+
+def test_vit_forward_launches_are_the_documented_sequence(vit_case):
+    cfg, m, x = vit_case
+    _assert_same(_recorded(lambda: m(x)), _vit_expected(cfg, cls_only=False))
+
+
+def test_vit_cls_features_launches_are_the_documented_sequence(vit_case):
+    cfg, m, x = vit_case
+    _assert_same(_recorded(lambda: m.cls_features(x)), _vit_expected(cfg, cls_only=True))
+
+
+# ---- Wav2Vec2 ----------------------------------------------------------------------------------------------
+def _w2v_expected(cfg, L):
+    d, I, H = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+    dims, ks, ss = cfg.conv_dim, cfg.conv_kernel, cfg.conv_stride
+    Ts, t = [], L
+    for k, s in zip(ks, ss):
+        t = (t - k) // s + 1
+        Ts.append(t)
+    T, hd, last = Ts[-1], d // H, len(dims) - 1
+    cg = d // cfg.num_conv_pos_embedding_groups
+    want = []
+    for n in _chunks():
+        rows = n * T
+        want += [("w2v_conv0_stats_kernels", ((n, L),)), ("w2v_conv0_norm_gelu_kernel", ((n, L),))]
+        for i in range(1, last + 1):
+            want.append(gemm((n * Ts[i], dims[i], ks[i] * dims[i - 1])))
+            if i < last:
+                want.append(("w2v_gelu_window_kernel", ((n * Ts[i + 1], ks[i + 1] * dims[i]),)))
+            else:
+                want.append(gelu(rows, dims[i]))
+        want += [ln(rows, dims[-1]), gemm((rows, d, dims[-1])),
+                 ("w2v_posconv_kernel", ((rows, d, cfg.num_conv_pos_embeddings * cg),)), ln(rows, d)]
+        want += [gemm((rows, 3 * d, d)), attn(hd, T, T), gemm((rows, d, d)), ln(rows, d),
+                 gemm((rows, I, d)), gelu(rows, I), gemm((rows, d, I)), ln(rows, d)] * cfg.num_hidden_layers
+    return want
+
+
+def test_w2v_forward_launches_are_the_documented_sequence():
+    from mmfusion.wav2vec2 import NativeWav2Vec2
+    cfg = w2v_ref.tiny_config()
+    m = NativeWav2Vec2(**w2v_ref.config_kwargs(cfg), chunk=CHUNK)
+    m.load_state_dict(w2v_ref.seeded_weights(cfg, seed=21))
+    m = m.cuda().eval()
+    x = (0.5 * torch.randn(N, SAMPLES, generator=torch.Generator().manual_seed(22))).cuda()
+    _assert_same(_recorded(lambda: m(x)), _w2v_expected(cfg, SAMPLES))

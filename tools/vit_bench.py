@@ -23,20 +23,9 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
 import torch
 
+from backbone_bench import kernel_table, time_eager
+
 GFLOP_PER_FRAME = 35.1
-
-
-def time_eager(fn, steps, warmup) -> float:
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
 
 
 def _rate(ms: float, frames: int) -> dict:
@@ -57,38 +46,6 @@ def _bytes(label: str, detail) -> float:
     if label == "ln_fwd_kernel":
         return a * b * 4 + a * 8
     return 0.0
-
-
-def kernel_table(fn) -> list:
-    from mmfusion import lib
-    fn()
-    torch.cuda.synchronize()
-    lib.PROFILE = []
-    try:
-        fn()
-        torch.cuda.synchronize()
-        recs = lib.PROFILE
-    finally:
-        lib.PROFILE = None
-    agg = {}
-    for label, flops, e0, e1, detail in recs:
-        key = label
-        if label.startswith("gemm") and detail:
-            key = f"{label} N={detail[0][1]} K={detail[0][2]}" + (" (+1)" if len(detail) > 1 else "")
-        row = agg.setdefault(key, {"kernel": key, "calls": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0})
-        row["calls"] += 1
-        row["ms"] += e0.elapsed_time(e1)
-        row["flops"] += flops
-        row["bytes"] += _bytes(label, detail) if detail else 0.0
-    total = sum(r["ms"] for r in agg.values())
-    rows = sorted(agg.values(), key=lambda r: -r["ms"])
-    for r in rows:
-        r["share"] = round(r["ms"] / total, 4)
-        r["tflops"] = round(r.pop("flops") / r["ms"] / 1e9, 1) if r["flops"] else None
-        r["tb_per_s"] = round(r.pop("bytes") / r["ms"] / 1e9, 2) if r["bytes"] else None
-        r["ms"] = round(r["ms"], 4)
-        r.pop("flops", None), r.pop("bytes", None)
-    return rows
 
 
 def main():
@@ -119,7 +76,7 @@ def main():
     model.chunk = vit.DEFAULT_CHUNK
     model._ws = None
     if args.table:
-        rows = kernel_table(lambda: model.cls_features(x))
+        rows = kernel_table(lambda: model.cls_features(x), bytes_of=_bytes)
         print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s} {'TB/s':>6s}")
         for r in rows:
             print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} "

@@ -23,6 +23,8 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
 import torch
 
+from backbone_bench import kernel_table, time_eager
+
 
 def gflop_per_clip(cfg, L: int) -> dict:
     from mmfusion.wav2vec2 import feat_lengths
@@ -33,48 +35,6 @@ def gflop_per_clip(cfg, L: int) -> dict:
     layers = cfg.num_hidden_layers * (2.0 * T * (4 * d * d + 2 * d * I) + 4.0 * T * T * d) + 2.0 * T * d * dims[-1]
     return {"conv": round(conv / 1e9, 2), "posconv": round(pos / 1e9, 2), "layers": round(layers / 1e9, 2),
             "total": round((conv + pos + layers) / 1e9, 2)}
-
-
-def time_eager(fn, steps, warmup) -> float:
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
-
-
-def kernel_table(fn) -> list:
-    from mmfusion import lib
-    fn()
-    torch.cuda.synchronize()
-    lib.PROFILE = []
-    try:
-        fn()
-        torch.cuda.synchronize()
-        recs = lib.PROFILE
-    finally:
-        lib.PROFILE = None
-    agg = {}
-    for label, flops, e0, e1, detail in recs:
-        key = label
-        if label.startswith("gemm") and detail:
-            key = f"{label} N={detail[0][1]} K={detail[0][2]}" + (" (+1)" if len(detail) > 1 else "")
-        row = agg.setdefault(key, {"kernel": key, "calls": 0, "ms": 0.0, "flops": 0.0})
-        row["calls"] += 1
-        row["ms"] += e0.elapsed_time(e1)
-        row["flops"] += flops
-    total = sum(r["ms"] for r in agg.values())
-    rows = sorted(agg.values(), key=lambda r: -r["ms"])
-    for r in rows:
-        r["share"] = round(r["ms"] / total, 4)
-        r["tflops"] = round(r.pop("flops") / r["ms"] / 1e9, 1) if r["flops"] else None
-        r["ms"] = round(r["ms"], 4)
-    return rows
 
 
 def main():
