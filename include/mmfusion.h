@@ -643,6 +643,30 @@ int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, int T_in, int
 int mmf_w2v_posconv(const void* x_bf16, const void* w_bf16, const float* bias, void* y_bf16, int N, int T, int C, int groups, int k,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frozen DeBERTa-v3 backbone (mmfusion/deberta.py; the reference runs HuggingFace's DebertaV2Model at models/encoders.py:20).
+ * The linears, the LayerNorms and the MLP of a layer are the grouped kernels above; these are the two pieces a DeBERTa has
+ * beside them.  Both validate first and launch nothing on an error.  A mask is (n, T) as f32 (mask_kind 1, nonzero = keep) or
+ * u8 (mask_kind 2), or NULL with mask_kind 0 for all ones.
+ * ------------------------------------------------------------------------------------------ */
+/* rows of table[ids[row]] (ids int64 [rows], table f32 (vocab, d); an id outside the table reads its nearest row) or, with
+ * ids NULL, of embeds f32 (rows, d) -> LayerNorm(gamma, beta, eps) in f32 -> * mask[row] -> out (rows, d) bf16, one rounding.
+ * Exactly one of ids / embeds.  d % 4 == 0, d <= 1024; table / embeds / gamma / beta / out 16-byte aligned. */
+int mmf_deberta_embed(const int64_t* ids, const float* embeds, const float* table, const float* gamma, const float* beta, float eps,
+                      const void* mask, int mask_kind, void* out_bf16, int64_t rows, int d, int vocab, void* stream);
+/* Disentangled self-attention forward for head_dim 64, H heads, n items of T tokens:
+ *   s[i][j] = (Q_i.K_j + Q_i.posK[idx(i-j)] + K_j.posQ[idx(i-j)]) / scale,  out = softmax_j(s) V
+ * qkv_bf16: fused rows (n*T, 3 H 64), q | k | v.  posq / posk: bf16 (2S, H 64) with row stride ld_pos (elements): the layer's
+ * query / key projections of the normalised relative embeddings.  idx: int32 [2T - 1], idx[delta + T - 1] in [0, 2S) for
+ * delta = i - j, NON-DECREASING WITH STEPS OF AT MOST 1 (the kernel forms only the run of rows a tile can reach; values are
+ * clamped to [0, 2S), so a table that breaks this gives wrong numbers, not a stray access).  A pair (i, j) with mask[i] *
+ * mask[j] == 0 scores the lowest finite f32: masked keys get probability exactly 0 and a masked query row attends uniformly
+ * over all T keys, as HuggingFace's masked_fill + softmax does.  out_bf16 (n*T, H 64).  Scores, bias and probabilities are never
+ * written to memory.  1 <= T <= 1024, 1 <= S <= 256, n and H <= 65535; head_dim other than 64 is MMF_E_UNSUPPORTED. */
+int mmf_deberta_attn_fwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                         const void* mask, int mask_kind, void* out_bf16, int n, int H, int T, int S, int head_dim, float scale,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,307 @@
+// The pieces a DeBERTa-v3 forward has and the fusion path did not (mmfusion/deberta.py).
+//   embed   word_embeddings[ids] (or f32 inputs_embeds rows) -> LayerNorm in f32 -> * mask -> bf16 rows, one pass
+//   attn    fused disentangled attention forward, head_dim 64:
+//             s[i][j] = (Q_i.K_j + Q_i.posK[idx(i-j)] + K_j.posQ[idx(i-j)]) / scale, masked softmax over j, @ V
+//           Scores, bias and probabilities live in registers and LDS only.
+#include <float.h>
+#include "mmf_internal.h"
+
+namespace {
+
+constexpr int DB_THREADS = 256;
+
+// mask element `i` of a (n, T) mask given as f32 (kind 1) or u8 (kind 2); kind 0: all ones
+__device__ __forceinline__ float db_mask(const void* __restrict__ mask, int kind, size_t i) {
+  if (kind == 1) return static_cast<const float*>(mask)[i];
+  if (kind == 2) return static_cast<const unsigned char*>(mask)[i] ? 1.0f : 0.0f;
+  return 1.0f;
+}
+
+// ---- embeddings ---------------------------------------------------------------------------------------------
+// One wave per row; lane l owns columns 4 l + 256 k (k < 4, so d <= 1024), kept in registers between the two statistics
+// passes (mean, then the centred second moment: what torch's LayerNorm computes) and the store.
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_embed_kernel(const long long* __restrict__ ids, const float* __restrict__ embeds, const float* __restrict__ table,
+                          const float* __restrict__ gamma, const float* __restrict__ beta, const void* __restrict__ mask,
+                          int mask_kind, unsigned short* __restrict__ out, int rows, int d, int vocab, float eps) {
+  const int row = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* __restrict__ src;
+  if (ids) {
+    long long id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);              // an id outside the table reads its nearest row, never past it
+    src = table + (size_t)id * d;
+  } else {
+    src = embeds + (size_t)row * d;
+  }
+  f32x4_t v[4];
+  float sum = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 4 * lane + 256 * k;
+    v[k] = c < d ? *reinterpret_cast<const f32x4_t*>(src + c) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    sum += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+  }
+  const float mean = wave_sum(sum) / (float)d;
+  float sq = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (4 * lane + 256 * k < d) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float c = v[k][e] - mean; sq = fmaf(c, c, sq); }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+  const float m = db_mask(mask, mask_kind, (size_t)row);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 4 * lane + 256 * k;
+    if (c < d) {
+      const f32x4_t g = *reinterpret_cast<const f32x4_t*>(gamma + c), b = *reinterpret_cast<const f32x4_t*>(beta + c);
+      float y[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[e] = (fmaf((v[k][e] - mean) * rstd, g[e], b[e])) * m;
+      *reinterpret_cast<u32x2_t*>(out + (size_t)row * d + c) = u32x2_t{pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3])};
+    }
+  }
+}
+
+// ---- disentangled attention ------------------------------------------------------------------------------------
+// One workgroup = (64 queries, head, item): 4 waves of 16 queries each, walking the keys in tiles of 32.
+// v_mfma_f32_16x16x32_bf16 throughout: lane (q = lane >> 4, r = lane & 15) holds A[row r][k 8q..8q+7], B[k 8q..8q+7][col r]
+// and D[row 4q + e][col r].  Every product is formed TRANSPOSED, with the wave's 16 queries as the columns:
+//   S^T   [key][query]     A = K tile rows (LDS)           B = Q fragment (registers, loaded once)
+//   C2P^T [pos row][query] A = posK rows (global, L2)      B = Q fragment
+//   P2C^T [pos row][key]   A = posQ rows (global, L2)      B = K tile rows (LDS)  -- the same LDS fragment as S^T's A
+//   O^T   [dh][query]      A = V^T tile rows (LDS)         B = P^T = the softmax of S^T's own D registers, packed to bf16
+// so a lane ends with the scores of ONE query (its column) and the row statistics need two shuffles, and the
+// probabilities are a B operand without leaving their registers.  S^T's D holds, per 32-key tile, keys 4q..4q+3 of chunk 0
+// and 16 + 4q..16 + 4q+3 of chunk 1; the MFMA's k index is only a summation index, so V^T is stored with its keys permuted
+// to that order (db_slot) and both operands are one 16-byte read.
+//
+// The relative-position terms.  idx is non-decreasing in delta = i - j with steps of at most 1 (the caller's contract:
+// mmfusion/deberta.py checks the table it builds), so a tile touches a short run of consecutive posK / posQ rows:
+//   a wave's 16 queries x 32 keys: 47 deltas -> at most 47 rows from lo_c = idx(smallest delta): 3 row chunks of 16 (C2P)
+//   the block's 64 queries x 32 keys: 95 deltas -> at most 95 rows from lo_p: 6 row chunks (P2C, shared by the 4 waves,
+//   each forming a quarter of its (row chunk, key chunk) tiles)
+// Only the chunks up to idx(largest delta) are formed: far from the diagonal the log buckets make that one or two.  Both
+// products are parked in LDS as f32 and each lane gathers its 8 (query, key) entries at idx(delta) - lo.  Every gather
+// offset and every row index is clamped, so a table that breaks the contract gives wrong numbers, not a stray access.
+//
+// LDS: K tile 32 x 72 bf16 (4608 B), V^T 64 x 40 bf16 (5120 B), C2P 4 waves x 16 x 49 f32 (12544 B), P2C 32 x 97 f32
+// (12416 B), the tile's 95 idx values and 32 key-mask values: 35.1 KB, four workgroups per CU by LDS.
+constexpr int DB_BQ = 64, DB_BK = 32, DB_DH = 64;
+constexpr int DB_KLD = 72, DB_VLD = 40, DB_CLD = 49, DB_PLD = 97;
+constexpr int DB_CROWS = 48, DB_PROWS = 96, DB_NIDX = DB_BQ + DB_BK - 1;      // 95
+
+__device__ __forceinline__ int db_slot(int key) {            // key of a 32-key tile -> its k slot in the PV product
+  const int c = key >> 4, k = key & 15;
+  return 8 * (k >> 2) + 4 * c + (k & 3);
+}
+
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ posq,
+                             const unsigned short* __restrict__ posk, int ld_pos, const int* __restrict__ idx,
+                             const void* __restrict__ mask, int mask_kind, unsigned short* __restrict__ out,
+                             int H, int T, int S2 /* 2 S */, float inv_scale) {
+  __shared__ __attribute__((aligned(16))) unsigned short sK[DB_BK * DB_KLD];
+  __shared__ __attribute__((aligned(16))) unsigned short sVt[DB_DH * DB_VLD];
+  __shared__ float sC[4 * 16 * DB_CLD];
+  __shared__ float sP[DB_BK * DB_PLD];
+  __shared__ int sIdx[DB_NIDX + 1];
+  __shared__ float sKm[DB_BK];
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, r = lane & 15;
+  const int i0 = blockIdx.x * DB_BQ, h = blockIdx.y, item = blockIdx.z;
+  const int d = H * DB_DH, ld = 3 * d;
+  const unsigned short* __restrict__ base = qkv + (size_t)item * T * ld + h * DB_DH;
+  const size_t mrow = (size_t)item * T;
+
+  // this lane's query (column r of every product of this wave) and its Q fragment
+  const int iq = i0 + wave * 16 + r, iqc = iq < T ? iq : T - 1;
+  bf16x8_t qf[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) qf[ks] = *reinterpret_cast<const bf16x8_t*>(base + (size_t)iqc * ld + ks * 32 + q * 8);
+  const bool q_on = db_mask(mask, mask_kind, mrow + iqc) != 0.0f;
+
+  f32x4_t o[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) o[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.0f;
+  float* __restrict__ cw = sC + wave * 16 * DB_CLD;
+  const unsigned short* __restrict__ pq = posq + h * DB_DH + q * 8;
+  const unsigned short* __restrict__ pk = posk + h * DB_DH + q * 8;
+
+  for (int j0 = 0; j0 < T; j0 += DB_BK) {
+    __syncthreads();                                             // the previous tile's readers are done
+    {
+      // K rows as they are; V transposed with its keys in db_slot order.  Keys past T read row T - 1: they get probability 0.
+      const int key = tid >> 3, c8 = (tid & 7) * 8;
+      const int j = j0 + key < T ? j0 + key : T - 1;
+      const unsigned short* __restrict__ src = base + (size_t)j * ld + c8;
+      *reinterpret_cast<u32x4_t*>(sK + key * DB_KLD + c8) = *reinterpret_cast<const u32x4_t*>(src + d);
+      const u32x4_t vv = *reinterpret_cast<const u32x4_t*>(src + 2 * d);
+      const int slot = db_slot(key);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sVt[(c8 + 2 * e) * DB_VLD + slot] = (unsigned short)(vv[e] & 0xffffu);
+        sVt[(c8 + 2 * e + 1) * DB_VLD + slot] = (unsigned short)(vv[e] >> 16);
+      }
+      if (tid < DB_NIDX) {                                       // idx of delta = dmin + tid, delta clamped to the table
+        int dl = i0 - j0 - (DB_BK - 1) + tid;
+        dl = dl < -(T - 1) ? -(T - 1) : (dl > T - 1 ? T - 1 : dl);
+        int v = idx[dl + T - 1];
+        sIdx[tid] = v < 0 ? 0 : (v > S2 - 1 ? S2 - 1 : v);
+      }
+      if (tid < DB_BK) sKm[tid] = j0 + tid < T ? db_mask(mask, mask_kind, mrow + j0 + tid) : 0.0f;
+    }
+    __syncthreads();
+
+    const int lo_p = sIdx[0], hi_p = sIdx[DB_NIDX - 1];
+    const int lo_c = sIdx[16 * wave], hi_c = sIdx[16 * wave + 46];
+    int npc = (hi_p - lo_p) / 16 + 1;
+    npc = npc < 1 ? 1 : (npc > DB_PROWS / 16 ? DB_PROWS / 16 : npc);
+    int ncc = (hi_c - lo_c) / 16 + 1;
+    ncc = ncc < 1 ? 1 : (ncc > DB_CROWS / 16 ? DB_CROWS / 16 : ncc);
+
+    // the K fragments of this tile: A of S^T and B of P2C^T
+    bf16x8_t kf[2][2];
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) kf[kc][ks] = *reinterpret_cast<const bf16x8_t*>(sK + (kc * 16 + r) * DB_KLD + ks * 32 + q * 8);
+
+    // P2C^T: this wave's share of the (row chunk, key chunk) tiles -> sP[key][pos row - lo_p]
+    for (int t = wave; t < npc * 2; t += 4) {
+      const int rc = t >> 1, kc = t & 1;
+      int prow = lo_p + rc * 16 + r;
+      prow = prow > S2 - 1 ? S2 - 1 : prow;
+      const unsigned short* __restrict__ a = pq + (size_t)prow * ld_pos;
+      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), kc ? kf[1][0] : kf[0][0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), kc ? kf[1][1] : kf[0][1], acc, 0, 0, 0);
+      float* __restrict__ dst = sP + (kc * 16 + r) * DB_PLD + rc * 16 + q * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dst[e] = acc[e];
+    }
+    // C2P^T: this wave's own rows -> cw[query][pos row - lo_c]
+    for (int c = 0; c < ncc; ++c) {
+      int prow = lo_c + c * 16 + r;
+      prow = prow > S2 - 1 ? S2 - 1 : prow;
+      const unsigned short* __restrict__ a = pk + (size_t)prow * ld_pos;
+      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), qf[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), qf[1], acc, 0, 0, 0);
+      float* __restrict__ dst = cw + r * DB_CLD + c * 16 + q * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dst[e] = acc[e];
+    }
+    // S^T
+    f32x4_t s[2];
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc) {
+      s[kc] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) s[kc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kc][ks], qf[ks], s[kc], 0, 0, 0);
+    }
+    __syncthreads();                                             // sP (all waves) and cw are complete
+
+    // gather the two bias terms, mask, online softmax; lane (q, r): keys kc * 16 + 4 q + e of query r
+    float p[2][4], tmax = -INFINITY;
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int key = kc * 16 + q * 4 + e;
+        const int ix = sIdx[16 * wave + r - key + (DB_BK - 1)];
+        int oc = ix - lo_c, op = ix - lo_p;
+        oc = oc < 0 ? 0 : (oc > DB_CROWS - 1 ? DB_CROWS - 1 : oc);
+        op = op < 0 ? 0 : (op > DB_PROWS - 1 ? DB_PROWS - 1 : op);
+        float v = (s[kc][e] + cw[r * DB_CLD + oc] + sP[key * DB_PLD + op]) * inv_scale;
+        if (!(q_on && sKm[key] != 0.0f)) v = -FLT_MAX;          // a masked pair: HuggingFace's masked_fill(finfo.min)
+        if (j0 + key >= T) v = -INFINITY;                        // no such key
+        p[kc][e] = v;
+        tmax = fmaxf(tmax, v);
+      }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m_run, tmax);                      // finite: every tile has at least one key below T
+    const float alpha = __expf(m_run - m_new);
+    float psum = 0.0f;
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        p[kc][e] = __expf(p[kc][e] - m_new);                     // a fully masked row: exp(0) = 1 on every key, the uniform row
+        psum += p[kc][e];
+      }
+    l_run = l_run * alpha + psum;                                // this lane's keys only; the four q groups are summed at the end
+    m_run = m_new;
+    const u32x4_t pw = {pack_bf16x2(p[0][0], p[0][1]), pack_bf16x2(p[0][2], p[0][3]), pack_bf16x2(p[1][0], p[1][1]), pack_bf16x2(p[1][2], p[1][3])};
+    const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pw);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(sVt + (t * 16 + r) * DB_VLD + q * 8);
+      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[t] * alpha, 0, 0, 0);
+    }
+  }
+  l_run += __shfl_xor(l_run, 16, 64);
+  l_run += __shfl_xor(l_run, 32, 64);
+  if (iq < T) {
+    const float inv = 1.0f / l_run;
+    unsigned short* __restrict__ dst = out + ((size_t)item * T + iq) * d + h * DB_DH + q * 4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      *reinterpret_cast<u32x2_t*>(dst + t * 16) = u32x2_t{pack_bf16x2(o[t][0] * inv, o[t][1] * inv), pack_bf16x2(o[t][2] * inv, o[t][3] * inv)};
+  }
+}
+
+int db_mask_check(const char* fn, const void* mask, int mask_kind) {
+  if (mask_kind < 0 || mask_kind > 2 || (mask_kind == 0) != (mask == nullptr))
+    MMF_FAIL(MMF_E_SHAPE, "%s: mask_kind=%d (0 none, 1 f32, 2 u8) does not match the mask pointer", fn, mask_kind);
+  if (mask_kind == 1 && (reinterpret_cast<uintptr_t>(mask) & 3u)) MMF_FAIL(MMF_E_ALIGN, "%s: an f32 mask must be 4-byte aligned", fn);
+  return MMF_OK;
+}
+
+}  // namespace
+
+extern "C" int mmf_deberta_embed(const int64_t* ids, const float* embeds, const float* table, const float* gamma, const float* beta,
+                                 float eps, const void* mask, int mask_kind, void* out_bf16, int64_t rows, int d, int vocab,
+                                 void* stream) {
+  if ((ids == nullptr) == (embeds == nullptr)) MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_embed: exactly one of ids / embeds");
+  if (!gamma || !beta || !out_bf16 || (ids && !table) || rows <= 0 || d <= 0 || (ids && vocab <= 0))
+    MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_embed: null operand or rows=%lld d=%d vocab=%d", (long long)rows, d, vocab);
+  if ((d & 3) || d > 1024 || rows > ((int64_t)1 << 31) - 4)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_deberta_embed: d=%d (multiple of 4, at most 1024), rows=%lld (below 2^31)", d, (long long)rows);
+  if (int rc = db_mask_check("mmf_deberta_embed", mask, mask_kind)) return rc;
+  if (!mmf_aligned16(gamma) || !mmf_aligned16(beta) || !mmf_aligned16(out_bf16) || (ids && !mmf_aligned16(table)) || (embeds && !mmf_aligned16(embeds))
+      || (reinterpret_cast<uintptr_t>(ids) & 7u))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_deberta_embed: table / embeds / gamma / beta / out must be 16-byte aligned, ids 8-byte aligned");
+  const int per = DB_THREADS / MMF_WAVE;
+  hipLaunchKernelGGL(deberta_embed_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const long long*>(ids), embeds, table, gamma, beta, mask, mask_kind, static_cast<unsigned short*>(out_bf16),
+                     (int)rows, d, vocab, eps);
+  MMF_CHECK_LAUNCH("mmf_deberta_embed");
+  return MMF_OK;
+}
+
+extern "C" int mmf_deberta_attn_fwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                                    const void* mask, int mask_kind, void* out_bf16, int n, int H, int T, int S, int head_dim,
+                                    float scale, void* stream) {
+  if (!qkv_bf16 || !posq_bf16 || !posk_bf16 || !idx || !out_bf16 || n <= 0 || H <= 0 || T <= 0 || S <= 0 || head_dim <= 0 || !(scale > 0.0f))
+    MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_attn_fwd: null operand or n=%d H=%d T=%d S=%d head_dim=%d scale=%g", n, H, T, S, head_dim, (double)scale);
+  if (head_dim == DB_DH && ld_pos < H * DB_DH) MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_attn_fwd: ld_pos=%d is less than H * 64 = %d", ld_pos, H * DB_DH);
+  if (head_dim != DB_DH || T > 1024 || S > 256 || n > 65535 || H > 65535)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_deberta_attn_fwd: head_dim=%d (64 only), T=%d (at most 1024), S=%d (at most 256), n=%d H=%d (at most 65535)",
+             head_dim, T, S, n, H);
+  if (int rc = db_mask_check("mmf_deberta_attn_fwd", mask, mask_kind)) return rc;
+  if (!mmf_aligned16(qkv_bf16) || !mmf_aligned16(posq_bf16) || !mmf_aligned16(posk_bf16) || !mmf_aligned16(out_bf16) || (ld_pos & 7)
+      || (reinterpret_cast<uintptr_t>(idx) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_deberta_attn_fwd: qkv / posq / posk / out must be 16-byte aligned, ld_pos a multiple of 8, idx 4-byte aligned");
+  hipLaunchKernelGGL(deberta_attn_fwd_kernel, dim3((T + DB_BQ - 1) / DB_BQ, H, n), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(qkv_bf16), static_cast<const unsigned short*>(posq_bf16),
+                     static_cast<const unsigned short*>(posk_bf16), ld_pos, idx, mask, mask_kind, static_cast<unsigned short*>(out_bf16),
+                     H, T, 2 * S, 1.0f / scale);
+  MMF_CHECK_LAUNCH("mmf_deberta_attn_fwd");
+  return MMF_OK;
+}

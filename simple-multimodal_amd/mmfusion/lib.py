@@ -39,6 +39,7 @@ SYMBOLS = (
     "mmf_eval_accumulate",
     "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
+    "mmf_deberta_embed", "mmf_deberta_attn_fwd",
 )
 
 
@@ -208,6 +209,8 @@ def load() -> C.CDLL:
     lib.mmf_w2v_conv0_norm_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_w2v_gelu_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_posconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_deberta_embed.argtypes = [vp, vp, vp, vp, vp, f32, vp, i32, vp, i64, i32, i32, vp]
+    lib.mmf_deberta_attn_fwd.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -443,3 +446,60 @@ def w2v_posconv(x, w, bias, y, N: int, T: int, C: int, groups: int, k: int) -> N
         raise ValueError("w2v_posconv: operand sizes do not match N, T, C, groups, k")
     with _Timed("w2v_posconv_kernel", 2.0 * N * T * C * cg * k, [(N * T, C, k * cg)]):
         check(load().mmf_w2v_posconv(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N, T, C, groups, k, stream_ptr()))
+
+
+# ---- DeBERTa kernels (csrc/deberta.hip) ------------------------------------------------------------------------
+def _deberta_mask(mask, numel: int):
+    """-> (pointer | None, mask_kind): an f32 mask as it is, a bool / uint8 one as bytes"""
+    import torch
+    if mask is None:
+        return None, 0
+    if not mask.is_cuda:
+        raise RuntimeError("deberta kernels run on the GPU only (no CPU fallback)")
+    if mask.dtype not in (torch.float32, torch.uint8, torch.bool) or not mask.is_contiguous() or mask.numel() != numel:
+        raise ValueError("deberta: the mask must be a contiguous float32 / uint8 / bool tensor with one value per token")
+    return mask.data_ptr(), 1 if mask.dtype == torch.float32 else 2
+
+
+def deberta_embed(out, table, gamma, beta, eps: float, ids=None, embeds=None, mask=None) -> None:
+    """out (rows, d) bf16 = LayerNorm(table[ids] | embeds) * mask: ids int64 (rows,), table f32 (vocab, d) or embeds f32 (rows, d)"""
+    import torch
+    _w2v_bf16(out)
+    _w2v_f32(gamma, beta)
+    if (ids is None) == (embeds is None):
+        raise ValueError("deberta_embed: exactly one of ids / embeds")
+    rows, d = out.shape
+    if ids is not None:
+        _w2v_f32(table)
+        if not ids.is_cuda:
+            raise RuntimeError("deberta kernels run on the GPU only (no CPU fallback)")
+        if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != rows or table.dim() != 2 or table.shape[1] != d:
+            raise ValueError("deberta_embed: ids must be contiguous int64, one per output row, and table (vocab, d)")
+    else:
+        _w2v_f32(embeds)
+        if embeds.numel() != rows * d:
+            raise ValueError("deberta_embed: embeds must hold (rows, d) values")
+    if not out.is_contiguous() or gamma.numel() != d or beta.numel() != d:
+        raise ValueError("deberta_embed: out must be contiguous and gamma / beta one value per column")
+    mp, kind = _deberta_mask(mask, rows)
+    with _Timed("deberta_embed_kernel", 0.0, [(rows, d)]):
+        check(load().mmf_deberta_embed(ids.data_ptr() if ids is not None else None, embeds.data_ptr() if embeds is not None else None,
+                                       table.data_ptr() if ids is not None else None, gamma.data_ptr(), beta.data_ptr(), eps, mp, kind,
+                                       out.data_ptr(), rows, d, table.shape[0] if ids is not None else 0, stream_ptr()))
+
+
+def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S: int, scale: float, head_dim: int = 64) -> None:
+    """out (n T, H 64) bf16 = disentangled attention of the fused qkv rows (n T, 3 H 64); posq / posk (2S, H 64) bf16 views with a
+    common row stride; idx int32 (2T - 1,) (include/mmfusion.h states its contract); mask (n, T) or None"""
+    import torch
+    _w2v_bf16(qkv, posq, posk, out)
+    d = H * head_dim
+    if not idx.is_cuda or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != 2 * T - 1:
+        raise ValueError("deberta_attn_fwd: idx must be a contiguous int32 GPU tensor of 2 T - 1 values")
+    if (qkv.numel() < n * T * 3 * d or out.numel() < n * T * d or not qkv.is_contiguous() or not out.is_contiguous()
+            or tuple(posq.shape) != (2 * S, d) or tuple(posk.shape) != (2 * S, d) or posq.stride() != posk.stride() or posq.stride(1) != 1):
+        raise ValueError("deberta_attn_fwd: operand sizes do not match n, H, T, S")
+    mp, kind = _deberta_mask(mask, n * T)
+    with _Timed(f"deberta_attn_fwd_kernel<{head_dim}>", 12.0 * n * H * T * T * head_dim, [(T, T)]):
+        check(load().mmf_deberta_attn_fwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
+                                          out.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))

@@ -7,14 +7,17 @@ pool -> optional ``AdapterLayer`` -> ``projection`` Linear(hidden -> fusion_hidd
 self-attention heads run on the HIP kernels (``mmfusion.ops``).
 
 The HuggingFace backbones themselves (DeBERTa-v3 / Wav2Vec2 / ViT, reference :20,116,179) are third-party pretrained
-models fetched by name.  ViT and Wav2Vec2 have native, frozen, forward-only forms on the HIP kernels that need no
-network (below); DeBERTa-v3 has none.  The encoders take a ``backbone`` argument:
+models fetched by name.  All three have native, frozen, forward-only forms on the HIP kernels that need no network
+(below).  The encoders take a ``backbone`` argument:
   * ``backbone=None`` (default) reproduces the reference: ``from_pretrained(config.*_model_name)``;
   * any ``nn.Module`` returning an object with ``.last_hidden_state`` is used as is;
   * ``config.video_backbone = "native"`` (dynamic attribute, ``VideoEncoder`` only) builds ``mmfusion.vit.NativeViT``: the
     frozen, forward-only ViT on the HIP kernels, which takes HuggingFace ``state_dict``s and needs no network;
   * ``config.audio_backbone = "native"`` (dynamic attribute, ``AudioEncoder`` only) builds ``mmfusion.wav2vec2.NativeWav2Vec2``
     the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers);
+  * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
+    same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
+    on the prompt route, from input embeddings;
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -69,6 +72,16 @@ def _native_wav2vec2(config):
     kw = dict(hidden_size=config.audio_hidden_size)
     kw.update(getattr(config, "audio_backbone_kwargs", None) or {})
     return NativeWav2Vec2(**kw)
+
+
+def _native_deberta(config):
+    """``config.text_backbone = "native"``: the DeBERTa-v3 of ``mmfusion.deberta`` on the HIP kernels, built from
+    ``config.text_hidden_size`` with deberta-v3-base's other sizes (``config.text_backbone_kwargs``, a dict, overrides any of
+    them); weights come from ``load_state_dict`` / a checkpoint, nothing is fetched."""
+    from mmfusion.deberta import NativeDeberta
+    kw = dict(hidden_size=config.text_hidden_size)
+    kw.update(getattr(config, "text_backbone_kwargs", None) or {})
+    return NativeDeberta(**kw)
 
 
 class AdapterLayer(_FusionBase):
@@ -126,8 +139,12 @@ class TextEncoder(_FusionBase):
     def __init__(self, config, backbone: Optional[nn.Module] = None):
         super().__init__()
         self.config = config
+        self._native = False
         if _feature_mode(config):
             self.model, self.hidden_size = None, config.text_hidden_size
+        elif backbone is None and getattr(config, "text_backbone", None) == "native":
+            self.model, self._native = _native_deberta(config), True
+            self.hidden_size = self.model.config.hidden_size
         else:
             self.model = backbone if backbone is not None else _load_backbone("text", config.text_model_name)
             self.hidden_size = self.model.config.hidden_size
@@ -149,9 +166,14 @@ class TextEncoder(_FusionBase):
                 emb = self.model.embeddings.word_embeddings(input_ids)
                 pm = torch.ones(B, self.config.prompt_length, device=attention_mask.device, dtype=attention_mask.dtype)
                 attention_mask = torch.cat([pm, attention_mask], dim=1)
-                outputs = self.model(inputs_embeds=torch.cat([pe, emb], dim=1), attention_mask=attention_mask)
+                kw = dict(inputs_embeds=torch.cat([pe, emb], dim=1), attention_mask=attention_mask)
             else:
-                outputs = self.model(input_ids=input_ids, attention_mask=attention_mask)
+                kw = dict(input_ids=input_ids, attention_mask=attention_mask)
+            if self._native:                         # the native backbone: frozen
+                with torch.no_grad():
+                    outputs = self.model(**kw)
+            else:
+                outputs = self.model(**kw)
             sequence_output = outputs.last_hidden_state
             cls_pool = "bert" in getattr(self.model.config, "model_type", "")     # reference :87
         if use_adapter and self.adapter is not None:

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Cost of the native frozen DeBERTa-v3 backbone (mmfusion.deberta.NativeDeberta, deberta-v3-base) on one batch of token ids
+(default 16 items of 512 tokens, the last 32 of every second item padded):
+
+  * ms per batch, tokens/s and TFLOP/s (by operation count: 12 layers of linears, the four attention products counted as
+    12 T^2 d per layer: QK^T, PV, and the two relative-position products at their bias-free size) of ``forward``, per chunk size;
+  * the disentangled attention kernel alone beside ``mmf_attn_fwd_grouped`` on the same fused qkv rows: the bias-free, mask-free
+    floor, and the ratio of the two (there is no pass mark: the new kernel forms two more products and gathers);
+  * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE).
+
+    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table]
+Prints one JSON line (the table, when asked for, on the lines before it)."""
+import argparse
+import json
+import math
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
+import torch
+
+from backbone_bench import kernel_table, time_eager
+
+
+def gflop_per_item(cfg, T: int) -> float:
+    d, I = cfg.hidden_size, cfg.intermediate_size
+    return cfg.num_hidden_layers * (2.0 * T * (4 * d * d + 2 * d * I) + 12.0 * T * T * d) / 1e9
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--items", type=int, default=16)
+    ap.add_argument("--tokens", type=int, default=512)
+    ap.add_argument("--chunks", default="")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--table", action="store_true")
+    args = ap.parse_args()
+    import deberta_ref
+    from mmfusion import deberta, lib
+    from mmfusion.lib import AttnProblem
+    cfg = deberta_ref.base_config()
+    model = deberta.NativeDeberta(**deberta_ref.config_kwargs(cfg))
+    model.load_state_dict(deberta_ref.seeded_weights(cfg, seed=0))
+    model = model.cuda().eval()
+    N, T, d, H = args.items, args.tokens, cfg.hidden_size, cfg.num_attention_heads
+    g = torch.Generator().manual_seed(1)
+    ids = torch.randint(1, cfg.vocab_size, (N, T), generator=g).cuda()
+    mask = torch.ones(N, T, dtype=torch.int64)
+    mask[1::2, max(T - 32, 1):] = 0
+    mask = mask.cuda()
+    gf = gflop_per_item(cfg, T)
+
+    def rate(ms: float) -> dict:
+        return {"ms": round(ms, 3), "tokens_per_s": round(N * T / ms * 1e3, 0), "tflops": round(gf * N / ms, 1)}
+
+    res = {"model": "deberta-v3-base, frozen, bf16 storage", "items": N, "tokens": T, "gflop_per_item": round(gf, 2),
+           "default_chunk": deberta.DEFAULT_CHUNK, "workspace_mb_per_item": round(model.workspace_bytes_per_item(T) / 2 ** 20, 2)}
+    fwd = lambda: model(input_ids=ids, attention_mask=mask)
+    chunks = [int(c) for c in args.chunks.split(",") if c] or [deberta.DEFAULT_CHUNK]
+    for c in chunks:
+        model.chunk, model._ws = c, None
+        res[f"forward_chunk{c}"] = rate(time_eager(fwd, args.steps, args.warmup))
+    model.chunk, model._ws = deberta.DEFAULT_CHUNK, None
+    if args.table:
+        rows = kernel_table(fwd)
+        print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s}")
+        for r in rows:
+            print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} {r['tflops'] if r['tflops'] is not None else '':>8}")
+        res["kernels"] = rows
+    # the attention kernel alone against the bias-free, mask-free fused attention on the same rows
+    n = min(N, deberta.DEFAULT_CHUNK)
+    qkv = torch.randn(n * T, 3 * d, generator=g).to(torch.bfloat16).cuda()
+    att = torch.empty(n * T, d, dtype=torch.bfloat16, device="cuda")
+    lse = torch.empty(n * H * T, dtype=torch.float32, device="cuda")
+    posq, posk = model._pos_tables(ids.device)[0]
+    idx = model._index(T, ids.device)
+    m32 = mask[:n].float().contiguous()
+    scale = math.sqrt(3.0 * 64)
+    base = qkv.data_ptr()
+    floor = lambda: lib.attn_fwd_grouped([AttnProblem(base, base + 2 * d, base + 4 * d, att.data_ptr(), lse.data_ptr(), None, None, None,
+                                                      None, None, n, H, T, T, 3 * d, 3 * d, 3 * d, d)], 64, 1.0 / scale)
+    ours = lambda: lib.deberta_attn_fwd(qkv, posq, posk, idx, m32, att, n, H, T, cfg.position_buckets, scale)
+    t_ours, t_floor = time_eager(ours, 20, 5), time_eager(floor, 20, 5)
+    res["attention"] = {"items": n, "deberta_attn_fwd_ms": round(t_ours, 4), "attn_fwd_grouped_ms": round(t_floor, 4),
+                        "ratio": round(t_ours / t_floor, 2), "deberta_tflops_4_products": round(12.0 * n * H * T * T * 64 / t_ours / 1e9, 1),
+                        "eager_bias_mb_per_layer": round(n * H * T * T * 4 / 1e6, 1)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
