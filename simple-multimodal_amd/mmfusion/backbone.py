@@ -1,12 +1,14 @@
-"""What the frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2``) share: the table of frozen
-parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, and the launches of a transformer layer.
+"""What the frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2``, ``mmfusion.deberta.NativeDeberta``)
+share: the table of frozen parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, what is derived from
+the weights once per weight version, and the launches of a transformer layer.
 
-A layer is two blocks on ``rows = n * T`` tokens of a chunk of ``n`` items (bf16 residual stream like MulT's); where its
-LayerNorms go around them is the subclass's ``_layer``:
+A layer is two blocks on ``rows = n * T`` tokens of a chunk of ``n`` items (bf16 residual stream like MulT's).  Where the
+LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subclass's own ``_layer`` (ViT, pre-LN):
 
-    _attention(src, resid):
+    _attention(src, resid, attend):
       fused Q/K/V linear + bias     mmf_gemm_grouped NT, BIAS            src -> qkv (rows, 3 d)
-      attention, H heads of 64/96   mmf_attn_fwd_grouped                 qkv -> att
+      attend(qkv, att)              mmf_attn_fwd_grouped by default      qkv -> att   (H heads of 64 / 96; a subclass hands in
+                                                                                       its own attention: DeBERTa's disentangled one)
       out-projection + bias + resid mmf_gemm_grouped NT, BIAS | ADD_AUX  att -> y
     _ffn(src, resid, out):
       fc1                           mmf_gemm_grouped NT                  src -> h (rows, intermediate)
@@ -17,8 +19,10 @@ LayerNorms go around them is the subclass's ``_layer``:
 
 Parameters are stored as the kernels read them (Q/K/V fused, a subclass may store a weight with its last two dims swapped)
 and ``_hf`` maps every HuggingFace key to its view of them, in HuggingFace's order, so ``state_dict()`` and
-``load_state_dict`` speak HuggingFace's names and shapes.  A subclass declares its workspace as a table of
-(name, elements per chunk item, dtype); the allocation and the bytes-per-item figure are both read from that table.
+``load_state_dict`` speak HuggingFace's names and shapes; ``_add_layer`` registers one layer from a table of HuggingFace's
+names.  A subclass declares its workspace as a table of (name, elements per chunk item, dtype), ``_ws_table(size)``; the
+allocation and the bytes-per-item figure are both read from that table.  A forward pass writes no attribute of the module
+but that workspace and the ``_derived`` cache: what a launch needs beyond the buffers travels as arguments.
 
 Forward only and frozen: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  bf16
 storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
@@ -26,7 +30,7 @@ Nothing synchronises with the host: a fixed-shape call can be captured by ``torc
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -37,6 +41,7 @@ from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NT, AttnProblem, LnProblem
 BF16 = torch.bfloat16
 LN_WIDTHS = (256, 512, 768, 1024)          # the lane forms of layernorm.hip
 WsTable = List[Tuple[str, int, torch.dtype]]
+Attend = Callable[[torch.Tensor, torch.Tensor], None]          # (qkv rows, att rows): launches one chunk's attention
 
 
 class BackboneOutput:
@@ -48,23 +53,27 @@ class BackboneOutput:
 
 
 class FrozenBackbone(nn.Module):
-    """Base of the native backbones.  A subclass sets ``self.config`` (``hidden_size``, ``num_attention_heads``,
-    ``intermediate_size``, ``layer_norm_eps``), registers its parameters with ``_add`` / ``_add_qkv`` in HuggingFace's
-    order, and names its layer parameters ``l{i}_{qkv,o,fc1,fc2}_{w,b}``."""
+    """Base of the native backbones.  A subclass declares its limits to ``__init__`` (``head_dims``: the head widths its
+    attention has a form for; ``ln_widths``: further named sizes that go through the LayerNorm kernel), sets ``self.config``
+    (``hidden_size``, ``num_attention_heads``, ``intermediate_size``, ``layer_norm_eps``), registers its parameters with ``_add``
+    / ``_add_layer`` in HuggingFace's order, and defines ``_ws_table(size)``."""
 
-    def __init__(self, hidden_size: int, num_attention_heads: int, chunk: int):
+    def __init__(self, hidden_size: int, num_attention_heads: int, chunk: int, head_dims: Sequence[int] = (64, 96),
+                 ln_widths: Optional[Dict[str, int]] = None):
         super().__init__()
         d, H, who = hidden_size, num_attention_heads, type(self).__name__
-        if H <= 0 or d % H or d // H not in (64, 96):
-            raise ValueError(f"{who}: hidden_size {d} / num_attention_heads {H} must give a head_dim of 64 or 96 "
-                             "(the fused attention kernel's forms)")
-        if d not in LN_WIDTHS:
-            raise ValueError(f"{who}: hidden_size {d} is not one of the LayerNorm kernel's widths {LN_WIDTHS}")
+        if H <= 0 or d % H or d // H not in head_dims:
+            raise ValueError(f"{who}: hidden_size {d} / num_attention_heads {H} must give a head_dim of "
+                             f"{' or '.join(str(v) for v in head_dims)} (its attention kernel's forms)")
+        for name, width in {"hidden_size": d, **(ln_widths or {})}.items():
+            if width not in LN_WIDTHS:
+                raise ValueError(f"{who}: {name} {width} is not one of the LayerNorm kernel's widths {LN_WIDTHS}")
         self.chunk = int(chunk)
         self.head_dim = d // H
         # HuggingFace key -> (parameter, row range | None, stored with the last two dims swapped)
         self._hf: Dict[str, Tuple[str, Optional[Tuple[int, int]], bool]] = {}
         self._ws: Optional[dict] = None
+        self._cache: Dict[str, tuple] = {}             # _derived: slot -> (stamp of the parameters it was built from, value)
 
     # -- parameter table --------------------------------------------------------------------------------
     def _add(self, name: str, shape, key: Optional[str] = None, *, ones: bool = False, std: float = 0.02, swapped: bool = False):
@@ -79,14 +88,27 @@ class FrozenBackbone(nn.Module):
         if key is not None:
             self._hf[key] = (name, None, swapped)
 
-    def _add_qkv(self, i: int, prefix: str, order: str, d: int) -> None:
-        """layer ``i``'s fused (3 d, d) projection, rows q | k | v; ``order`` is the order of HuggingFace's three keys"""
-        for n in order:
-            r = "qkv".index(n)
-            self._hf[f"{prefix}{n}_proj.weight"] = (f"l{i}_qkv_w", (r * d, r * d + d), False)
-            self._hf[f"{prefix}{n}_proj.bias"] = (f"l{i}_qkv_b", (r * d, r * d + d), False)
+    def _add_qkv(self, i: int, d: int, keys: Dict[str, str]) -> None:
+        """layer ``i``'s fused (3 d, d) projection, rows q | k | v; ``keys``: "q" / "k" / "v" -> HuggingFace's name of that
+        linear, in HuggingFace's order"""
+        for role, key in keys.items():
+            r = "qkv".index(role)
+            self._hf[key + ".weight"] = (f"l{i}_qkv_w", (r * d, r * d + d), False)
+            self._hf[key + ".bias"] = (f"l{i}_qkv_b", (r * d, r * d + d), False)
         self._add(f"l{i}_qkv_w", (3 * d, d))
         self._add(f"l{i}_qkv_b", (3 * d,), std=0.0)
+
+    def _add_layer(self, i: int, d: int, I: int, keys: Dict[str, str]) -> None:
+        """layer ``i``: ``l{i}_{qkv,o,fc1,fc2}_{w,b}`` and ``l{i}_ln{1,2}_{w,b}``.  ``keys``: "q", "k", "v", "o", "ln1", "fc1",
+        "fc2", "ln2" -> HuggingFace's name of that module (without ``.weight`` / ``.bias``), IN HUGGINGFACE'S ORDER for the
+        model, the three projections first: that order is ``state_dict()``'s"""
+        roles = list(keys)
+        assert sorted(roles[:3]) == ["k", "q", "v"] and sorted(roles[3:]) == ["fc1", "fc2", "ln1", "ln2", "o"], roles
+        self._add_qkv(i, d, {r: keys[r] for r in roles[:3]})
+        shapes = {"o": (d, d), "fc1": (I, d), "fc2": (d, I), "ln1": (d,), "ln2": (d,)}
+        for r in roles[3:]:
+            self._add(f"l{i}_{r}_w", shapes[r], keys[r] + ".weight", ones=r.startswith("ln"))
+            self._add(f"l{i}_{r}_b", shapes[r][:1], keys[r] + ".bias", std=0.0)
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _canonical_key(self, key: str) -> str:
@@ -137,10 +159,14 @@ class FrozenBackbone(nn.Module):
     def _bytes_per_item(table: WsTable) -> int:
         return sum(numel * dtype.itemsize for _, numel, dtype in table)
 
-    def _allocate(self, dev, table: WsTable, **keys) -> dict:
-        """a new workspace of ``self.chunk`` items; ``keys``: what else the subclass's cache-validity rule reads"""
-        ws = {"dev": dev, "chunk": self.chunk, **keys}
-        for name, numel, dtype in table:
+    def _workspace(self, dev, size=None) -> dict:
+        """the workspace of ``self.chunk`` items of ``size`` (samples, tokens; None where the model fixes it).  Every buffer
+        grows with ``size``, so a smaller item uses the leading part of what a larger one allocated"""
+        ws = self._ws
+        if ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk and (size is None or ws["size"] >= size):
+            return ws
+        ws = {"dev": dev, "chunk": self.chunk, "size": size}
+        for name, numel, dtype in self._ws_table(size):
             ws[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
         self._ws = ws
         return ws
@@ -150,15 +176,29 @@ class FrozenBackbone(nn.Module):
         """the leading (rows, width) of a workspace buffer"""
         return ws[name][:rows * width].view(rows, width)
 
+    # -- what is derived from the weights ---------------------------------------------------------------
+    def _derived(self, slot: str, names: Sequence[str], build: Callable[[], object]):
+        """``build()`` of the parameters ``names``, made once per weight version: again when one of them was written in place
+        (``load_state_dict``) or replaced (``.cuda()``)"""
+        stamp = tuple((p.data_ptr(), p._version) for p in (getattr(self, n) for n in names))
+        hit = self._cache.get(slot)
+        if hit is None or hit[0] != stamp:
+            with torch.no_grad():
+                hit = self._cache[slot] = (stamp, build())
+        return hit[1]
+
     # -- launches ---------------------------------------------------------------------------------------
-    def _check_input(self, x, name: str) -> None:
+    def _check_input(self, x, name: str, dtype: torch.dtype = torch.float32, ndim: Optional[int] = None) -> None:
         who = type(self).__name__
         if ops.fp32_mode():
             raise RuntimeError(f"{who} runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback)")
-        if x.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32, got {x.dtype}")
+        want = str(dtype).rpartition(".")[2]
+        if ndim is not None and (x.dtype != dtype or x.dim() != ndim):
+            raise TypeError(f"{who}: {name} must be {ndim}-d {want}, got {tuple(x.shape)} {x.dtype}")
+        if x.dtype != dtype:
+            raise TypeError(f"{who}: {name} must be {want}, got {x.dtype}")
 
     def _w(self, name: str) -> torch.Tensor:
         return ops.shadow(getattr(self, name))
@@ -185,12 +225,16 @@ class FrozenBackbone(nn.Module):
     def _out_proj(self, i: int, att: torch.Tensor, resid: torch.Tensor, y: torch.Tensor) -> None:
         ops.gemm(GEMM_NT, att, self._w(f"l{i}_o_w"), y, bias=self._f(f"l{i}_o_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
 
-    def _attention(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, n: int, T: int) -> torch.Tensor:
-        """-> y = resid + out_proj(attention(qkv(src))) on the ``n * T`` rows of a chunk"""
+    def _attention(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, n: int, T: int, attend: Optional[Attend] = None) -> torch.Tensor:
+        """-> y = resid + out_proj(attention(qkv(src))) on the ``n * T`` rows of a chunk; ``attend(qkv, att)`` launches the
+        attention, None: the fused one (``_attn``)"""
         rows, d = n * T, self.config.hidden_size
         qkv, att, y = self._rows(ws, "qkv", rows, 3 * d), self._rows(ws, "att", rows, d), self._rows(ws, "y", rows, d)
         ops.gemm(GEMM_NT, src, self._w(f"l{i}_qkv_w"), qkv, bias=self._f(f"l{i}_qkv_b"), epilogue=EPI_BIAS)
-        self._attn(ws, qkv, att, n, T, T)
+        if attend is None:
+            self._attn(ws, qkv, att, n, T, T)
+        else:
+            attend(qkv, att)
         self._out_proj(i, att, resid, y)
         return y
 
@@ -200,6 +244,15 @@ class FrozenBackbone(nn.Module):
         ops.gemm(GEMM_NT, src, self._w(f"l{i}_fc1_w"), h)
         lib.bias_gelu(h, self._f(f"l{i}_fc1_b"))
         ops.gemm(GEMM_NT, h, self._w(f"l{i}_fc2_w"), out, bias=self._f(f"l{i}_fc2_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
+
+    def _post_ln_layer(self, i: int, ws, n: int, T: int, attend: Optional[Attend] = None) -> None:
+        """x = LayerNorm(ln + ffn(ln)), ln = LayerNorm(x + attention(x)) on the ``n * T`` rows of ``x``"""
+        rows, d = n * T, self.config.hidden_size
+        x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
+        y = self._attention(i, ws, x, x, n, T, attend)
+        self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
+        self._ffn(i, ws, ln, ln, y)
+        self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
 
     @staticmethod
     def _widen(src: torch.Tensor, dst: torch.Tensor) -> None:

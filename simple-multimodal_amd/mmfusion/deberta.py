@@ -45,7 +45,7 @@ import torch
 
 from . import arena as _arena
 from . import lib, ops
-from .backbone import BF16, LN_WIDTHS, BackboneOutput, FrozenBackbone, WsTable
+from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
 from .lib import EPI_BIAS, GEMM_NT
 
 # items per pass through the workspace.  NOT chosen by measurement yet: 16 items of 512 tokens give the layer GEMMs 8192 rows
@@ -126,11 +126,7 @@ class NativeDeberta(FrozenBackbone):
             raise ValueError(f"{who}: hidden_act={hidden_act!r}: only the exact 'gelu' is built")
         if embedding_size is not None and int(embedding_size) != d:
             raise ValueError(f"{who}: embedding_size={embedding_size} differs from hidden_size {d}: embed_proj is not built")
-        if H <= 0 or d % H or d // H != 64:                    # (ahead of the base's 64 / 96 check: the fused kernel has the one form)
-            raise ValueError(f"{who}: hidden_size {d} / num_attention_heads {H} must give a head_dim of 64 (the disentangled "
-                             "attention kernel's only form; every published v3 size has it)")
-        if d not in LN_WIDTHS:
-            raise ValueError(f"{who}: hidden_size {d} is not one of the LayerNorm kernel's widths {LN_WIDTHS}")
+        super().__init__(d, H, chunk, head_dims=(64,))         # (the disentangled attention kernel's only form; every published v3 size has it)
         if not 1 <= S <= 256:
             raise ValueError(f"{who}: position_buckets {S} must be in 1 .. 256 (the attention kernel takes up to 512 relative rows)")
         if max_position_embeddings < 2 or vocab_size < 1 or I % 8 or I < 8:
@@ -138,7 +134,6 @@ class NativeDeberta(FrozenBackbone):
                              f"intermediate_size {I} (a multiple of 8)")
         if num_hidden_layers < 1 or chunk < 1:
             raise ValueError(f"{who}: layers and chunk at least 1")
-        super().__init__(d, H, chunk)
         self.config = types.SimpleNamespace(
             vocab_size=int(vocab_size), hidden_size=d, num_hidden_layers=int(num_hidden_layers), num_attention_heads=H,
             intermediate_size=I, max_position_embeddings=int(max_position_embeddings), position_buckets=S,
@@ -150,34 +145,15 @@ class NativeDeberta(FrozenBackbone):
         add("emb_ln_w", (d,), "embeddings.LayerNorm.weight", ones=True)
         add("emb_ln_b", (d,), "embeddings.LayerNorm.bias", std=0.0)
         for i in range(num_hidden_layers):
-            a = f"encoder.layer.{i}."
-            self._add_qkv(i, a + "attention.self.", "qkv", d)
-            self._rename_qkv(a + "attention.self.")
-            add(f"l{i}_o_w", (d, d), a + "attention.output.dense.weight")
-            add(f"l{i}_o_b", (d,), a + "attention.output.dense.bias", std=0.0)
-            add(f"l{i}_ln1_w", (d,), a + "attention.output.LayerNorm.weight", ones=True)
-            add(f"l{i}_ln1_b", (d,), a + "attention.output.LayerNorm.bias", std=0.0)
-            add(f"l{i}_fc1_w", (I, d), a + "intermediate.dense.weight")
-            add(f"l{i}_fc1_b", (I,), a + "intermediate.dense.bias", std=0.0)
-            add(f"l{i}_fc2_w", (d, I), a + "output.dense.weight")
-            add(f"l{i}_fc2_b", (d,), a + "output.dense.bias", std=0.0)
-            add(f"l{i}_ln2_w", (d,), a + "output.LayerNorm.weight", ones=True)
-            add(f"l{i}_ln2_b", (d,), a + "output.LayerNorm.bias", std=0.0)
+            a, att = f"encoder.layer.{i}.", f"encoder.layer.{i}.attention."
+            self._add_layer(i, d, I, {"q": att + "self.query_proj", "k": att + "self.key_proj", "v": att + "self.value_proj",
+                                      "o": att + "output.dense", "ln1": att + "output.LayerNorm", "fc1": a + "intermediate.dense",
+                                      "fc2": a + "output.dense", "ln2": a + "output.LayerNorm"})
         add("rel_emb", (2 * S, d), "encoder.rel_embeddings.weight")
         add("enc_ln_w", (d,), "encoder.LayerNorm.weight", ones=True)
         add("enc_ln_b", (d,), "encoder.LayerNorm.bias", std=0.0)
         self.embeddings = types.SimpleNamespace(word_embeddings=_WordEmbeddings(self))
-        self._pos: Optional[list] = None               # per layer (posQ, posK): bf16 (2S, d) views of one (2S, 2d) GEMM output
-        self._pos_stamp = None
         self._idx: Dict[Tuple, torch.Tensor] = {}      # (T, S, max position, device) -> the int32 table on that device
-        self._call: dict = {}                          # what the running forward hands to _attn
-
-    def _rename_qkv(self, prefix: str) -> None:
-        """``_add_qkv`` names the three keys ``{q,k,v}_proj``; DeBERTa spells them ``{query,key,value}_proj`` (same order)"""
-        for short, full in (("q", "query"), ("k", "key"), ("v", "value")):
-            for leaf in ("weight", "bias"):
-                self._hf[f"{prefix}{full}_proj.{leaf}"] = self._hf.pop(f"{prefix}{short}_proj.{leaf}")
-        # pop + insert keeps q, k, v each as (weight, bias) at the end of the table, in HuggingFace's order
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -191,12 +167,6 @@ class NativeDeberta(FrozenBackbone):
 
     def workspace_bytes_per_item(self, T: int) -> int:
         return self._bytes_per_item(self._ws_table(T))
-
-    def _workspace(self, dev, T: int) -> dict:
-        ws = self._ws
-        if ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk and ws["T"] >= T:
-            return ws                                        # every buffer grows with T: a shorter sequence uses the leading part
-        return self._allocate(dev, self._ws_table(T), T=T)
 
     def _index(self, T: int, dev) -> torch.Tensor:
         c = self.config
@@ -214,41 +184,32 @@ class NativeDeberta(FrozenBackbone):
 
     # -- weights ----------------------------------------------------------------------------------------
     def _pos_tables(self, dev) -> list:
-        """per layer (posQ, posK) = the layer's q / k projection (bias included) of LayerNorm(rel_embeddings), bf16, computed on
-        the HIP kernels once per weight version"""
+        """per layer (posQ, posK) = the layer's q / k projection (bias included) of LayerNorm(rel_embeddings): bf16 (2S, d) views
+        of one (2S, 2d) GEMM output, computed on the HIP kernels once per weight version"""
         c = self.config
+        d, rows = c.hidden_size, 2 * c.position_buckets
+
+        def build():
+            rel = torch.empty((rows, d), dtype=BF16, device=dev)
+            lib.deberta_embed(rel, None, self._f("enc_ln_w"), self._f("enc_ln_b"), c.layer_norm_eps, embeds=self._f("rel_emb"))
+            pos = []
+            for i in range(c.num_hidden_layers):
+                qk = torch.empty((rows, 2 * d), dtype=BF16, device=dev)
+                ops.gemm(GEMM_NT, rel, self._w(f"l{i}_qkv_w")[:2 * d], qk, bias=self._f(f"l{i}_qkv_b")[:2 * d], epilogue=EPI_BIAS)
+                pos.append((qk[:, :d], qk[:, d:]))
+            return pos
         names = ["rel_emb", "enc_ln_w", "enc_ln_b"] + [f"l{i}_qkv_{s}" for i in range(c.num_hidden_layers) for s in "wb"]
-        stamp = tuple((p.data_ptr(), p._version) for p in (getattr(self, n) for n in names))
-        if self._pos is None or stamp != self._pos_stamp:
-            d, rows = c.hidden_size, 2 * c.position_buckets
-            with torch.no_grad():
-                rel = torch.empty((rows, d), dtype=BF16, device=dev)
-                lib.deberta_embed(rel, None, self._f("enc_ln_w"), self._f("enc_ln_b"), c.layer_norm_eps, embeds=self._f("rel_emb"))
-                pos = []
-                for i in range(c.num_hidden_layers):
-                    qk = torch.empty((rows, 2 * d), dtype=BF16, device=dev)
-                    ops.gemm(GEMM_NT, rel, self._w(f"l{i}_qkv_w")[:2 * d], qk, bias=self._f(f"l{i}_qkv_b")[:2 * d], epilogue=EPI_BIAS)
-                    pos.append((qk[:, :d], qk[:, d:]))
-            self._pos, self._pos_stamp = pos, stamp
-        return self._pos
+        return self._derived("pos", names, build)
 
     # -- launches ---------------------------------------------------------------------------------------
-    def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
-        """the disentangled attention in place of the base's: ``self._call`` carries this layer's (posQ, posK), the index table
-        and the chunk's mask"""
-        c, call = self.config, self._call
-        posq, posk = call["pos"]
-        lib.deberta_attn_fwd(qkv, posq, posk, call["idx"], call["mask"], att, n, c.num_attention_heads, T, c.position_buckets,
-                             math.sqrt(3.0 * self.head_dim), self.head_dim)
+    def _layer(self, i: int, ws, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor]) -> None:
+        """a post-LN layer around the disentangled attention: ``pos`` = this layer's (posQ, posK), ``idx`` the index table,
+        ``mask`` the chunk's (n, T) mask or None"""
+        c, scale = self.config, math.sqrt(3.0 * self.head_dim)
 
-    def _layer(self, i: int, ws, n: int, T: int) -> None:
-        rows, d = n * T, self.config.hidden_size
-        x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
-        self._call["pos"] = self._pos[i]
-        y = self._attention(i, ws, x, x, n, T)
-        self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        self._ffn(i, ws, ln, ln, y)
-        self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
+        def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
+            lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, n, c.num_attention_heads, T, c.position_buckets, scale, self.head_dim)
+        self._post_ln_layer(i, ws, n, T, attend)
 
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None) -> BackboneOutput:
         c, who = self.config, "NativeDeberta"
@@ -256,12 +217,7 @@ class NativeDeberta(FrozenBackbone):
             raise ValueError(f"{who}: exactly one of input_ids / inputs_embeds")
         d = c.hidden_size
         if input_ids is not None:
-            if ops.fp32_mode():
-                raise RuntimeError(f"{who} runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
-            if not isinstance(input_ids, torch.Tensor) or not input_ids.is_cuda:
-                raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback)")
-            if input_ids.dtype != torch.int64 or input_ids.dim() != 2:
-                raise TypeError(f"{who}: input_ids must be (N, T) int64, got {tuple(input_ids.shape)} {input_ids.dtype}")
+            self._check_input(input_ids, "input_ids", torch.int64, ndim=2)
             src = input_ids.contiguous()
         else:
             self._check_input(inputs_embeds, "inputs_embeds")
@@ -279,21 +235,19 @@ class NativeDeberta(FrozenBackbone):
             mask = attention_mask if attention_mask.dtype in (torch.float32, torch.uint8, torch.bool) else attention_mask.to(torch.float32)
             mask = mask.contiguous()
         _arena.ensure(self)
-        self._pos_tables(dev)
+        pos, idx = self._pos_tables(dev), self._index(T, dev)
         ws = self._workspace(dev, T)
-        call = self._call = {"idx": self._index(T, dev), "mask": None, "pos": None}
         out = torch.empty((N, T, d), dtype=torch.float32, device=dev)
         table, gamma, beta = self._f("word_emb"), self._f("emb_ln_w"), self._f("emb_ln_b")
         for n0 in range(0, N, self.chunk):
             n = min(self.chunk, N - n0)
             x = self._rows(ws, "x", n * T, d)
-            call["mask"] = None if mask is None else mask[n0:n0 + n]
-            part = src[n0:n0 + n]
+            part, m = src[n0:n0 + n], None if mask is None else mask[n0:n0 + n]
             if input_ids is not None:
-                lib.deberta_embed(x, table, gamma, beta, c.layer_norm_eps, ids=part.reshape(-1), mask=call["mask"])
+                lib.deberta_embed(x, table, gamma, beta, c.layer_norm_eps, ids=part.reshape(-1), mask=m)
             else:
-                lib.deberta_embed(x, None, gamma, beta, c.layer_norm_eps, embeds=part, mask=call["mask"])
+                lib.deberta_embed(x, None, gamma, beta, c.layer_norm_eps, embeds=part, mask=m)
             for i in range(c.num_hidden_layers):
-                self._layer(i, ws, n, T)
+                self._layer(i, ws, n, T, pos[i], idx, m)
             self._widen(x, out[n0:n0 + n])
         return BackboneOutput(out)

@@ -98,18 +98,9 @@ class NativeViT(FrozenBackbone):
         add("patch_bias", (d,), "embeddings.patch_embeddings.projection.bias", std=0.0)
         for i in range(num_hidden_layers):
             a = f"layers.{i}."
-            # HuggingFace's order inside a layer: q, k, v, o, layernorm_before, layernorm_after, fc1, fc2
-            self._add_qkv(i, a + "attention.", "qkv", d)
-            add(f"l{i}_o_w", (d, d), a + "attention.o_proj.weight")
-            add(f"l{i}_o_b", (d,), a + "attention.o_proj.bias", std=0.0)
-            add(f"l{i}_ln1_w", (d,), a + "layernorm_before.weight", ones=True)
-            add(f"l{i}_ln1_b", (d,), a + "layernorm_before.bias", std=0.0)
-            add(f"l{i}_ln2_w", (d,), a + "layernorm_after.weight", ones=True)
-            add(f"l{i}_ln2_b", (d,), a + "layernorm_after.bias", std=0.0)
-            add(f"l{i}_fc1_w", (I, d), a + "mlp.fc1.weight")
-            add(f"l{i}_fc1_b", (I,), a + "mlp.fc1.bias", std=0.0)
-            add(f"l{i}_fc2_w", (d, I), a + "mlp.fc2.weight")
-            add(f"l{i}_fc2_b", (d,), a + "mlp.fc2.bias", std=0.0)
+            self._add_layer(i, d, I, {"q": a + "attention.q_proj", "k": a + "attention.k_proj", "v": a + "attention.v_proj",
+                                      "o": a + "attention.o_proj", "ln1": a + "layernorm_before", "ln2": a + "layernorm_after",
+                                      "fc1": a + "mlp.fc1", "fc2": a + "mlp.fc2"})
         add("ln_w", (d,), "layernorm.weight", ones=True)
         add("ln_b", (d,), "layernorm.bias", std=0.0)
         add("pooler_w", (d, d), "pooler.dense.weight")
@@ -127,19 +118,13 @@ class NativeViT(FrozenBackbone):
         return sd if generation == 5 else {hf_key_to_v4(k): v for k, v in sd.items()}
 
     # -- workspace --------------------------------------------------------------------------------------
-    def _ws_table(self) -> WsTable:
-        """per image; ``h`` also holds the patches and their embeddings in front of the layers"""
+    def _ws_table(self, size=None) -> WsTable:
+        """per image (the model fixes its size); ``h`` also holds the patches and their embeddings in front of the layers"""
         c = self.config
         return self._token_table(self.T, max(self.T * c.intermediate_size, self.num_patches * (self.patch_dim + c.hidden_size)))
 
     def workspace_bytes_per_image(self) -> int:
         return self._bytes_per_item(self._ws_table())
-
-    def _workspace(self, dev) -> dict:
-        ws = self._ws
-        if ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk:
-            return ws
-        return self._allocate(dev, self._ws_table())
 
     # -- launches ---------------------------------------------------------------------------------------
     def _layer(self, i: int, ws, n: int) -> None:

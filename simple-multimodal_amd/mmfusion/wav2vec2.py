@@ -31,13 +31,13 @@ synchronises with the host (mmfusion/backbone.py).
 from __future__ import annotations
 
 import types
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
 from . import arena as _arena
 from . import lib, ops
-from .backbone import BF16, LN_WIDTHS, BackboneOutput, FrozenBackbone, WsTable
+from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
 from .lib import EPI_BIAS, GEMM_NT
 
 # clips per pass through the workspace.  NOT chosen by measurement yet: 8 clips keep the workspace at 0.57 GB for 10 s clips
@@ -87,9 +87,7 @@ class NativeWav2Vec2(FrozenBackbone):
             raise ValueError(f"{who}: conv_bias=True is not built (the base family has no conv biases)")
         if not (len(dims) == len(ks) == len(ss)) or len(dims) < 2 or min(dims + ks + ss) < 1:
             raise ValueError(f"{who}: conv_dim, conv_kernel and conv_stride must be positive and of one length of at least 2")
-        if d not in LN_WIDTHS or dims[-1] not in LN_WIDTHS:        # (ahead of the base's check of d alone: this one names both)
-            raise ValueError(f"{who}: hidden_size {d} and conv_dim[-1] {dims[-1]} must be among the LayerNorm kernel's widths {LN_WIDTHS}")
-        super().__init__(d, H, chunk)
+        super().__init__(d, H, chunk, ln_widths={"conv_dim[-1]": dims[-1]})
         if in_channels != 1:
             raise ValueError(f"{who}: the first conv layer takes one input channel (a waveform), not {in_channels}")
         if ks[0] > 16 or dims[0] > 2048:
@@ -136,20 +134,9 @@ class NativeWav2Vec2(FrozenBackbone):
         add("enc_ln_b", (d,), "encoder.layer_norm.bias", std=0.0)
         for i in range(num_hidden_layers):
             a = f"encoder.layers.{i}."
-            # HuggingFace's order inside a layer: k, v, q, out_proj, layer_norm, intermediate, output, final_layer_norm
-            self._add_qkv(i, a + "attention.", "kvq", d)
-            add(f"l{i}_o_w", (d, d), a + "attention.out_proj.weight")
-            add(f"l{i}_o_b", (d,), a + "attention.out_proj.bias", std=0.0)
-            add(f"l{i}_ln1_w", (d,), a + "layer_norm.weight", ones=True)
-            add(f"l{i}_ln1_b", (d,), a + "layer_norm.bias", std=0.0)
-            add(f"l{i}_fc1_w", (I, d), a + "feed_forward.intermediate_dense.weight")
-            add(f"l{i}_fc1_b", (I,), a + "feed_forward.intermediate_dense.bias", std=0.0)
-            add(f"l{i}_fc2_w", (d, I), a + "feed_forward.output_dense.weight")
-            add(f"l{i}_fc2_b", (d,), a + "feed_forward.output_dense.bias", std=0.0)
-            add(f"l{i}_ln2_w", (d,), a + "final_layer_norm.weight", ones=True)
-            add(f"l{i}_ln2_b", (d,), a + "final_layer_norm.bias", std=0.0)
-        self._pos_w16: Optional[torch.Tensor] = None
-        self._pos_stamp = None
+            self._add_layer(i, d, I, {"k": a + "attention.k_proj", "v": a + "attention.v_proj", "q": a + "attention.q_proj",
+                                      "o": a + "attention.out_proj", "ln1": a + "layer_norm", "fc1": a + "feed_forward.intermediate_dense",
+                                      "fc2": a + "feed_forward.output_dense", "ln2": a + "final_layer_norm"})
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _canonical_key(self, key: str) -> str:
@@ -185,26 +172,18 @@ class NativeWav2Vec2(FrozenBackbone):
     def workspace_bytes_per_clip(self, L: int) -> int:
         return self._bytes_per_item(self._ws_table(L))
 
-    def _workspace(self, dev, L: int) -> dict:
-        ws = self._ws
-        if ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk and ws["L"] >= L:
-            return ws                                        # every buffer grows with L: a shorter clip uses the leading part
-        return self._allocate(dev, self._ws_table(L), L=L)
-
     # -- weights ----------------------------------------------------------------------------------------
     def _pos_weight(self) -> torch.Tensor:
         """The positional convolution's effective weight g v / ||v|| (norm over dims (0, 1) per tap, ``weight_norm(dim=2)``),
         folded in f32, repacked to (groups, cg, Kp) column (tap, channel) and rounded to bf16 once per weight version."""
-        g, v = self.pos_g, self.pos_v
-        stamp = (g.data_ptr(), g._version, v.data_ptr(), v._version)
-        if self._pos_w16 is None or stamp != self._pos_stamp:
-            with torch.no_grad():
-                w = g.detach() * v.detach() / v.detach().norm(dim=(0, 1), keepdim=True)          # (C, cg, k)
-                C, cg, k = w.shape
-                packed = torch.zeros(C, self.pos_kp, dtype=BF16, device=w.device)
-                packed[:, :k * cg] = w.permute(0, 2, 1).reshape(C, k * cg).to(BF16)
-            self._pos_w16, self._pos_stamp = packed, stamp
-        return self._pos_w16
+        def build():
+            g, v = self._f("pos_g"), self._f("pos_v")
+            w = g * v / v.norm(dim=(0, 1), keepdim=True)                                          # (C, cg, k)
+            C, cg, k = w.shape
+            packed = torch.zeros(C, self.pos_kp, dtype=BF16, device=w.device)
+            packed[:, :k * cg] = w.permute(0, 2, 1).reshape(C, k * cg).to(BF16)
+            return packed
+        return self._derived("pos_w16", ("pos_g", "pos_v"), build)
 
     # -- launches ---------------------------------------------------------------------------------------
     def _features(self, ws, wave: torch.Tensor, n: int, Ts: List[int]) -> torch.Tensor:
@@ -225,14 +204,6 @@ class NativeWav2Vec2(FrozenBackbone):
             else:
                 lib.bias_gelu(raw)
         return raw
-
-    def _layer(self, i: int, ws, n: int, T: int) -> None:
-        rows, d = n * T, self.config.hidden_size
-        x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
-        y = self._attention(i, ws, x, x, n, T)
-        self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        self._ffn(i, ws, ln, ln, y)
-        self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
 
     def forward(self, input_values: torch.Tensor, attention_mask=None) -> BackboneOutput:
         c = self.config
@@ -262,6 +233,6 @@ class NativeWav2Vec2(FrozenBackbone):
             lib.w2v_posconv(x, pos_w, self._f("pos_b"), y, n, T, d, c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings)
             self._ln(ws, y, x, "enc_ln_w", "enc_ln_b")
             for i in range(c.num_hidden_layers):
-                self._layer(i, ws, n, T)
+                self._post_ln_layer(i, ws, n, T)
             self._widen(x, out[n0:n0 + n])
         return BackboneOutput(out)

@@ -29,13 +29,17 @@ The audio / video heads return the head-averaged ``attention_weights`` (B, T, T)
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from mmfusion import ops
+from mmfusion.deberta import NativeDeberta
 from mmfusion.ops import AttnSpec, W
+from mmfusion.vit import NativeViT
+from mmfusion.wav2vec2 import NativeWav2Vec2
 from .fusion_layers import _FusionBase, _MHAParams, _as_rows, _p, _wb
 
 
@@ -50,38 +54,40 @@ def _load_backbone(kind: str, name: str):
     return cls.from_pretrained(name)
 
 
-def _native_vit(config):
-    """``config.video_backbone = "native"``: the ViT of ``mmfusion.vit`` on the HIP kernels, built from
-    ``config.video_hidden_size`` / ``config.video_frame_size`` with ViT-base's other sizes (``config.video_backbone_kwargs``,
-    a dict, overrides any of them); weights come from ``load_state_dict`` / a checkpoint, nothing is fetched."""
-    from mmfusion.vit import NativeViT
-    size = config.video_frame_size
-    size = size if isinstance(size, int) else size[0]
-    if not isinstance(config.video_frame_size, int) and len(set(config.video_frame_size)) != 1:
-        raise ValueError(f"the native ViT backbone takes square frames, not {tuple(config.video_frame_size)}")
-    kw = dict(hidden_size=config.video_hidden_size, image_size=size)
-    kw.update(getattr(config, "video_backbone_kwargs", None) or {})
-    return NativeViT(**kw)
+def _square(size) -> int:
+    if not isinstance(size, int) and len(set(size)) != 1:
+        raise ValueError(f"the native ViT backbone takes square frames, not {tuple(size)}")
+    return size if isinstance(size, int) else size[0]
 
 
-def _native_wav2vec2(config):
-    """``config.audio_backbone = "native"``: the Wav2Vec2 of ``mmfusion.wav2vec2`` on the HIP kernels, built from
-    ``config.audio_hidden_size`` with wav2vec2-base's other sizes (``config.audio_backbone_kwargs``, a dict, overrides any of
-    them); weights come from ``load_state_dict`` / a checkpoint, nothing is fetched."""
-    from mmfusion.wav2vec2 import NativeWav2Vec2
-    kw = dict(hidden_size=config.audio_hidden_size)
-    kw.update(getattr(config, "audio_backbone_kwargs", None) or {})
-    return NativeWav2Vec2(**kw)
+# kind -> (its native class, the sizes it takes from the config).  ``config.<kind>_backbone = "native"`` builds the class with its
+# family's base sizes otherwise (``config.<kind>_backbone_kwargs``, a dict, overrides any of them); weights come from
+# ``load_state_dict`` / a checkpoint, nothing is fetched.
+_NATIVE = {
+    "text": (NativeDeberta, lambda c: dict(hidden_size=c.text_hidden_size)),
+    "audio": (NativeWav2Vec2, lambda c: dict(hidden_size=c.audio_hidden_size)),
+    "video": (NativeViT, lambda c: dict(hidden_size=c.video_hidden_size, image_size=_square(c.video_frame_size))),
+}
 
 
-def _native_deberta(config):
-    """``config.text_backbone = "native"``: the DeBERTa-v3 of ``mmfusion.deberta`` on the HIP kernels, built from
-    ``config.text_hidden_size`` with deberta-v3-base's other sizes (``config.text_backbone_kwargs``, a dict, overrides any of
-    them); weights come from ``load_state_dict`` / a checkpoint, nothing is fetched."""
-    from mmfusion.deberta import NativeDeberta
-    kw = dict(hidden_size=config.text_hidden_size)
-    kw.update(getattr(config, "text_backbone_kwargs", None) or {})
-    return NativeDeberta(**kw)
+def _backbone(config, kind: str, given: Optional[nn.Module]):
+    """-> (module | None, hidden_size, native).  ``feature_inputs`` beats everything (no backbone); an explicit ``backbone=`` beats
+    the config switch and is never ``native``; then ``config.<kind>_backbone == "native"``; else the reference's ``from_pretrained``."""
+    if _feature_mode(config):
+        return None, getattr(config, kind + "_hidden_size"), False
+    native = given is None and getattr(config, kind + "_backbone", None) == "native"
+    if native:
+        cls, sizes = _NATIVE[kind]
+        given = cls(**{**sizes(config), **(getattr(config, kind + "_backbone_kwargs", None) or {})})
+    elif given is None:
+        given = _load_backbone(kind, getattr(config, kind + "_model_name"))
+    return given, given.config.hidden_size, native
+
+
+def _run_backbone(fn, native: bool, *args, **kw):
+    """``fn(*args, **kw)``, under ``no_grad`` iff the backbone is the native one: that one is frozen"""
+    with torch.no_grad() if native else contextlib.nullcontext():
+        return fn(*args, **kw)
 
 
 class AdapterLayer(_FusionBase):
@@ -139,15 +145,7 @@ class TextEncoder(_FusionBase):
     def __init__(self, config, backbone: Optional[nn.Module] = None):
         super().__init__()
         self.config = config
-        self._native = False
-        if _feature_mode(config):
-            self.model, self.hidden_size = None, config.text_hidden_size
-        elif backbone is None and getattr(config, "text_backbone", None) == "native":
-            self.model, self._native = _native_deberta(config), True
-            self.hidden_size = self.model.config.hidden_size
-        else:
-            self.model = backbone if backbone is not None else _load_backbone("text", config.text_model_name)
-            self.hidden_size = self.model.config.hidden_size
+        self.model, self.hidden_size, self._native = _backbone(config, "text", backbone)
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.prompt_embeddings = nn.Parameter(torch.randn(config.prompt_length, self.hidden_size)) \
             if hasattr(config, "prompt_length") else None
@@ -169,12 +167,7 @@ class TextEncoder(_FusionBase):
                 kw = dict(inputs_embeds=torch.cat([pe, emb], dim=1), attention_mask=attention_mask)
             else:
                 kw = dict(input_ids=input_ids, attention_mask=attention_mask)
-            if self._native:                         # the native backbone: frozen
-                with torch.no_grad():
-                    outputs = self.model(**kw)
-            else:
-                outputs = self.model(**kw)
-            sequence_output = outputs.last_hidden_state
+            sequence_output = _run_backbone(self.model, self._native, **kw).last_hidden_state
             cls_pool = "bert" in getattr(self.model.config, "model_type", "")     # reference :87
         if use_adapter and self.adapter is not None:
             sequence_output = self.adapter(sequence_output)
@@ -192,15 +185,7 @@ class AudioEncoder(_FusionBase):
     def __init__(self, config, backbone: Optional[nn.Module] = None):
         super().__init__()
         self.config = config
-        self._native = False
-        if _feature_mode(config):
-            self.model, self.hidden_size = None, config.audio_hidden_size
-        elif backbone is None and getattr(config, "audio_backbone", None) == "native":
-            self.model, self._native = _native_wav2vec2(config), True
-            self.hidden_size = self.model.config.hidden_size
-        else:
-            self.model = backbone if backbone is not None else _load_backbone("audio", config.audio_model_name)
-            self.hidden_size = self.model.config.hidden_size
+        self.model, self.hidden_size, self._native = _backbone(config, "audio", backbone)
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.temporal_attention = _MHAParams(self.hidden_size, 8)
         self.projection = nn.Linear(self.hidden_size, config.fusion_hidden_size)
@@ -209,11 +194,8 @@ class AudioEncoder(_FusionBase):
     def forward(self, waveform, use_adapter: bool = False) -> Dict[str, torch.Tensor]:
         if self.model is None:                       # feature mode: waveform holds (B, T, hidden)
             seq = waveform
-        elif self._native:                           # the native backbone: frozen
-            with torch.no_grad():
-                seq = self.model(waveform).last_hidden_state
         else:
-            seq = self.model(waveform).last_hidden_state
+            seq = _run_backbone(self.model, self._native, waveform).last_hidden_state
         if use_adapter and self.adapter is not None:
             seq = self.adapter(seq)
         projected, attended, weights = _mha_mean_project(self.temporal_attention, self.projection, seq,
@@ -226,14 +208,10 @@ class VideoEncoder(_FusionBase):
     def __init__(self, config, backbone: Optional[nn.Module] = None):
         super().__init__()
         self.config = config
-        if _feature_mode(config):
-            self.vit, self.hidden_size = None, config.video_hidden_size
-        elif backbone is None and getattr(config, "video_backbone", None) == "native":
-            self.vit = _native_vit(config)
-            self.hidden_size = self.vit.config.hidden_size
-        else:
-            self.vit = backbone if backbone is not None else _load_backbone("video", config.video_model_name)
-            self.hidden_size = self.vit.config.hidden_size
+        self.vit, self.hidden_size, native = _backbone(config, "video", backbone)
+        # the frozen route that runs the last layer for the CLS rows only.  Deliberately also for a NativeViT handed in as
+        # ``backbone=`` (it always was): the one case where a given backbone is treated like the native one
+        self._cls_route = native or isinstance(self.vit, NativeViT)
         self.temporal_lstm = nn.LSTM(self.hidden_size, self.hidden_size // 2, num_layers=2, batch_first=True,
                                      bidirectional=True, dropout=config.fusion_dropout)
         self.facial_attention = _MHAParams(self.hidden_size, 8)
@@ -246,9 +224,8 @@ class VideoEncoder(_FusionBase):
             frame_features = video_frames
         else:
             B, n, c, h, w = video_frames.shape
-            if hasattr(self.vit, "cls_features"):        # the native backbone: frozen, and its last layer runs for the CLS rows only
-                with torch.no_grad():
-                    cls = self.vit.cls_features(video_frames.reshape(-1, c, h, w))
+            if self._cls_route:
+                cls = _run_backbone(self.vit.cls_features, True, video_frames.reshape(-1, c, h, w))
             else:
                 cls = self.vit(pixel_values=video_frames.view(-1, c, h, w)).last_hidden_state[:, 0]
             frame_features = cls.view(B, n, -1)

@@ -30,6 +30,8 @@ import types
 
 import torch
 
+from backbone_ref import _r, config_kwargs, gelu_erf, layer_norm  # noqa: F401  (the tests read them from here)
+
 
 def tiny_config():
     return types.SimpleNamespace(vocab_size=300, hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=512,
@@ -39,10 +41,6 @@ def tiny_config():
 def base_config():
     return types.SimpleNamespace(vocab_size=128100, hidden_size=768, num_hidden_layers=12, num_attention_heads=12,
                                  intermediate_size=3072, max_position_embeddings=512, position_buckets=256, layer_norm_eps=1e-7)
-
-
-def config_kwargs(cfg):
-    return dict(vars(cfg))
 
 
 def hf_config_kwargs(cfg):
@@ -89,20 +87,6 @@ def seeded_weights(cfg, seed: int = 0):
             t = t / math.sqrt(shape[1]) * (1.5 if ("query_proj" in k or "key_proj" in k) else 1.0)
         sd[k] = t
     return sd
-
-
-def _r(t, on, dtype):
-    return t.to(torch.bfloat16).to(dtype) if on else t
-
-
-def layer_norm(x, gamma, beta, eps):
-    mean = x.mean(dim=-1, keepdim=True)
-    var = ((x - mean) ** 2).mean(dim=-1, keepdim=True)
-    return (x - mean) / torch.sqrt(var + eps) * gamma + beta
-
-
-def gelu_erf(x):
-    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
 def log_bucket(delta: torch.Tensor, bucket_size: int, max_position: int) -> torch.Tensor:

@@ -12,6 +12,7 @@ from mmfusion import synth
 from oracle import ref_cpu
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+BOUND_A = 2e-2           # relative L2 of a kernel against an oracle with the same storage format (the backbones' bound (a))
 
 
 def load_fixture(name):
@@ -160,6 +161,17 @@ def masked_hierarchical_fusion(config):
             return h
 
     return MaskedHierarchicalFusion(config)
+
+
+def _lib():
+    from mmfusion import lib
+    return lib
+
+
+def _bf16_ulp(v: torch.Tensor) -> torch.Tensor:
+    """spacing of bf16 (8 significant bits) at |v|, never below the smallest normal's"""
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
+    return torch.pow(2.0, e - 7)
 
 
 def hip_lib():

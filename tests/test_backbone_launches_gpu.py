@@ -1,5 +1,5 @@
-"""GPU: the launch sequence of the two frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2``)
-is the one their module docstrings list: every launch that ``mmfusion.lib`` records while ``lib.PROFILE`` is a list, in
+"""GPU: the launch sequence of the three frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2``,
+``mmfusion.deberta.NativeDeberta``) is the one their module docstrings list: every launch that ``mmfusion.lib`` records while ``lib.PROFILE`` is a list, in
 order, with the shapes it records.
 
 The expected lists are written out here from the configuration's sizes alone; nothing below asks the modules under test
@@ -13,6 +13,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import deberta_ref  # noqa: E402
 import vit_ref  # noqa: E402
 import w2v_ref  # noqa: E402
 
@@ -141,3 +142,28 @@ def test_w2v_forward_launches_are_the_documented_sequence():
     m = m.cuda().eval()
     x = (0.5 * torch.randn(N, SAMPLES, generator=torch.Generator().manual_seed(22))).cuda()
     _assert_same(_recorded(lambda: m(x)), _w2v_expected(cfg, SAMPLES))
+
+
+# ---- DeBERTa -----------------------------------------------------------------------------------------------
+def test_deberta_forward_launches_are_the_documented_sequence():
+    """the widening cast and the once-per-weight-version position tables are not recorded in a warmed-up forward"""
+    from mmfusion.deberta import NativeDeberta
+    T = 70
+    cfg = deberta_ref.tiny_config()
+    m = NativeDeberta(**deberta_ref.config_kwargs(cfg), chunk=CHUNK)
+    m.load_state_dict(deberta_ref.seeded_weights(cfg, seed=21))
+    m = m.cuda().eval()
+    ids = torch.randint(1, cfg.vocab_size, (N, T), generator=torch.Generator().manual_seed(22))
+    mask = torch.ones(N, T, dtype=torch.int64)
+    ids[N - 1, 50:], mask[N - 1, 50:] = 0, 0
+    i, k = ids.cuda(), mask.cuda()
+    got = _recorded(lambda: m(input_ids=i, attention_mask=k))
+    d, I = cfg.hidden_size, cfg.intermediate_size
+    want = []
+    for n in (2, 1):
+        rows = n * T
+        want.append(("deberta_embed_kernel", ((rows, d),)))
+        want += [gemm((rows, 3 * d, d)), ("deberta_attn_fwd_kernel<64>", ((T, T),)), gemm((rows, d, d)), ln(rows, d),
+                 gemm((rows, I, d)), gelu(rows, I), gemm((rows, d, I)), ln(rows, d)] * cfg.num_hidden_layers
+    _assert_same(got, want)
+    assert len(got) == len(want) == 2 * (1 + 8 * cfg.num_hidden_layers)

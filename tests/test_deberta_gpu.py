@@ -8,7 +8,6 @@ L-layer bf16 residual stream is modelled by the storage format, not by the code 
 order (tests/test_w2v_gpu.py's rule)."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,23 +16,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import deberta_ref  # noqa: E402
-from helpers import l2_rel  # noqa: E402
+from helpers import BOUND_A, _bf16_ulp, _lib, l2_rel  # noqa: E402
 
-BOUND_A = 2e-2
 BF16 = torch.bfloat16
 E_SHAPE, E_ALIGN, E_UNSUPPORTED = -1, -3, -5
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "deberta_tiny.npz")
-
-
-def _lib():
-    from mmfusion import lib
-    return lib
-
-
-def _bf16_ulp(v: torch.Tensor) -> torch.Tensor:
-    """spacing of bf16 (8 significant bits) at |v|, never below the smallest normal's (tests/test_vit_gpu.py's formula)"""
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
 
 
 # ---- the attention kernel ------------------------------------------------------------------------------------
@@ -389,41 +376,3 @@ def test_text_encoder_native_backbone_against_restatement_backbone(use_prompt):
         err = l2_rel(got[k], want[k])
         print(f"TextEncoder native vs restatement backbone (use_prompt={use_prompt}), {k}: rel L2 {err:.3e} (bound {BOUND_A})")
         assert got[k].shape == want[k].shape and err <= BOUND_A, k
-
-
-# ---- launch list ---------------------------------------------------------------------------------------------
-_GEMM = re.compile(r"^gemm\d*_grouped_kernel<(\w+),(\w+)>$")
-
-
-def test_forward_launches_are_the_documented_sequence():
-    """every launch ``mmfusion.lib`` records, in order, against the list in mmfusion/deberta.py's docstring written out from the
-    configuration's sizes (tests/test_backbone_launches_gpu.py's method); the widening cast and the once-per-weight-version
-    position tables are not recorded in a warmed-up forward"""
-    lib = _lib()
-    N, CHUNK, T = 3, 2, 70
-    cfg, sd, m, ids, mask = _setup(N, T, chunk=CHUNK, pad_from=50)
-    i, k = ids.cuda(), mask.cuda()
-    m(input_ids=i, attention_mask=k)
-    torch.cuda.synchronize()
-    lib.PROFILE = []
-    try:
-        m(input_ids=i, attention_mask=k)
-        torch.cuda.synchronize()
-        recs = lib.PROFILE
-    finally:
-        lib.PROFILE = None
-    got = []
-    for label, _flops, _e0, _e1, detail in recs:
-        mm = _GEMM.match(label)
-        got.append((f"gemm<{mm.group(1)},{mm.group(2)}>" if mm else label, tuple(tuple(int(v) for v in d) for d in detail)))
-    d, I = cfg.hidden_size, cfg.intermediate_size
-    gemm = lambda *mnk: ("gemm<NT,bf16>", (tuple(mnk),))
-    want = []
-    for n in (2, 1):
-        rows = n * T
-        want.append(("deberta_embed_kernel", ((rows, d),)))
-        want += [gemm(rows, 3 * d, d), ("deberta_attn_fwd_kernel<64>", ((T, T),)), gemm(rows, d, d), ("ln_fwd_kernel", ((rows, d),)),
-                 gemm(rows, I, d), ("bias_gelu_kernel", ((rows, I),)), gemm(rows, d, I), ("ln_fwd_kernel", ((rows, d),))] * cfg.num_hidden_layers
-    for j, (g, w) in enumerate(zip(got, want)):
-        assert g == w, f"launch {j}: recorded {g}, expected {w}"
-    assert len(got) == len(want) == 2 * (1 + 8 * cfg.num_hidden_layers)

@@ -13,15 +13,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import vit_ref  # noqa: E402
-from helpers import l2_rel  # noqa: E402
+from helpers import BOUND_A, _bf16_ulp, _lib, l2_rel  # noqa: E402
 
-BOUND_A = 2e-2
 BF16 = torch.bfloat16
-
-
-def _lib():
-    from mmfusion import lib
-    return lib
 
 
 # ---- kernels -----------------------------------------------------------------------------------------------
@@ -59,12 +53,6 @@ def test_embed_tokens_is_f32_add_with_one_rounding(N, T, d):
     lib.vit_embed_tokens(pe.cuda(), cls.cuda(), pos.cuda(), tok, N, T, d)
     want = (torch.cat([cls.expand(N, 1, d), pe.float().view(N, T - 1, d)], dim=1) + pos).to(BF16).view(N * T, d)
     assert torch.equal(tok.cpu().view(torch.int16), want.view(torch.int16))
-
-
-def _bf16_ulp(v: torch.Tensor) -> torch.Tensor:
-    """spacing of bf16 (8 significant bits) at |v|, never below the smallest normal's"""
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
 
 
 @pytest.mark.parametrize("rows,cols,ld,bias", [(37, 1024, 1024, True), (301, 72, 128, True), (5, 3072, 3080, False)])

@@ -13,22 +13,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import w2v_ref  # noqa: E402
-from helpers import l2_rel  # noqa: E402
+from helpers import BOUND_A, _bf16_ulp, _lib, l2_rel  # noqa: E402
 
-BOUND_A = 2e-2
 BF16 = torch.bfloat16
 E_SHAPE, E_ALIGN, E_UNSUPPORTED = -1, -3, -5
-
-
-def _lib():
-    from mmfusion import lib
-    return lib
-
-
-def _bf16_ulp(v: torch.Tensor) -> torch.Tensor:
-    """spacing of bf16 (8 significant bits) at |v|, never below the smallest normal's (tests/test_vit_gpu.py's formula)"""
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
 
 
 # ---- kernels -----------------------------------------------------------------------------------------------

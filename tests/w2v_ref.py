@@ -18,6 +18,8 @@ import types
 
 import torch
 
+from backbone_ref import _r, config_kwargs, gelu_erf, layer_norm  # noqa: F401  (the tests read them from here)
+
 GN_EPS = 1e-5            # nn.GroupNorm's default, which HuggingFace's group-norm conv layer keeps
 
 
@@ -33,10 +35,6 @@ def base_config():
                                  conv_dim=(512,) * 7, conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2),
                                  conv_bias=False, num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16,
                                  layer_norm_eps=1e-5, feat_extract_norm="group", do_stable_layer_norm=False)
-
-
-def config_kwargs(cfg):
-    return dict(vars(cfg))
 
 
 WN = "encoder.pos_conv_embed.conv."
@@ -93,20 +91,6 @@ def seeded_weights(cfg, seed: int = 0, legacy_weight_norm: bool = False):
             t = t / math.sqrt(shape[1]) * (1.5 if ("q_proj" in k or "k_proj" in k) else 1.0)
         sd[k] = t
     return sd
-
-
-def _r(t, on, dtype):
-    return t.to(torch.bfloat16).to(dtype) if on else t
-
-
-def layer_norm(x, gamma, beta, eps):
-    mean = x.mean(dim=-1, keepdim=True)
-    var = ((x - mean) ** 2).mean(dim=-1, keepdim=True)
-    return (x - mean) / torch.sqrt(var + eps) * gamma + beta
-
-
-def gelu_erf(x):
-    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
 def window(x, k, s):

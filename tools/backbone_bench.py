@@ -1,6 +1,37 @@
-"""What tools/vit_bench.py and tools/w2v_bench.py share: the event-timed loop and the per-kernel table read from
-mmfusion.lib.PROFILE.  Imported by those two (which set up ``sys.path``); not a command of its own."""
-import torch
+"""What tools/vit_bench.py, tools/w2v_bench.py and tools/deberta_bench.py share: the import path, the common arguments, the
+event-timed loop, the chunk sweep and the per-kernel table read from mmfusion.lib.PROFILE.  Imported by those three ahead of
+anything of the project's; not a command of its own."""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
+import torch  # noqa: E402
+
+
+def parser(steps: int, warmup: int, torch_yardstick: bool = False) -> argparse.ArgumentParser:
+    """--chunks --steps --warmup --table (and --no-torch where the script has a stock-torch yardstick); the script adds its inputs' sizes"""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chunks", default="")
+    ap.add_argument("--steps", type=int, default=steps)
+    ap.add_argument("--warmup", type=int, default=warmup)
+    ap.add_argument("--table", action="store_true")
+    if torch_yardstick:
+        ap.add_argument("--no-torch", action="store_true")
+    return ap
+
+
+def sweep(model, default_chunk: int, chunks: str, measure) -> None:
+    """``measure(c)`` with ``model.chunk = c`` and a fresh workspace for every ``c`` of the comma-separated ``chunks`` (none: the
+    default alone); leaves the model at its default chunk without a workspace"""
+    for c in [int(v) for v in chunks.split(",") if v] or [default_chunk]:
+        model.chunk, model._ws = c, None
+        measure(c)
+    model.chunk, model._ws = default_chunk, None
 
 
 def time_eager(fn, steps, warmup) -> float:
@@ -51,3 +82,12 @@ def kernel_table(fn, bytes_of=None) -> list:
             r["tb_per_s"] = round(nbytes / r["ms"] / 1e9, 2) if nbytes else None
         r["ms"] = round(r["ms"], 4)
     return rows
+
+
+def print_table(rows: list) -> None:
+    """``kernel_table``'s rows as text (the TB/s column where the rows carry it)"""
+    tb = bool(rows) and "tb_per_s" in rows[0]
+    show = lambda v, w: f"{v if v is not None else '':>{w}}"
+    print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s}" + (f" {'TB/s':>6s}" if tb else ""))
+    for r in rows:
+        print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} {show(r['tflops'], 8)}" + (f" {show(r['tb_per_s'], 6)}" if tb else ""))

@@ -10,20 +10,11 @@
 
     python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
-import argparse
 import json
 import math
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
+from backbone_bench import kernel_table, parser, print_table, sweep, time_eager  # (first: it sets the import path)
 import torch
-
-from backbone_bench import kernel_table, time_eager
 
 
 def gflop_per_item(cfg, T: int) -> float:
@@ -32,13 +23,9 @@ def gflop_per_item(cfg, T: int) -> float:
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = parser(steps=5, warmup=2)
     ap.add_argument("--items", type=int, default=16)
     ap.add_argument("--tokens", type=int, default=512)
-    ap.add_argument("--chunks", default="")
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--table", action="store_true")
     args = ap.parse_args()
     import deberta_ref
     from mmfusion import deberta, lib
@@ -61,17 +48,13 @@ def main():
     res = {"model": "deberta-v3-base, frozen, bf16 storage", "items": N, "tokens": T, "gflop_per_item": round(gf, 2),
            "default_chunk": deberta.DEFAULT_CHUNK, "workspace_mb_per_item": round(model.workspace_bytes_per_item(T) / 2 ** 20, 2)}
     fwd = lambda: model(input_ids=ids, attention_mask=mask)
-    chunks = [int(c) for c in args.chunks.split(",") if c] or [deberta.DEFAULT_CHUNK]
-    for c in chunks:
-        model.chunk, model._ws = c, None
+
+    def measure(c):
         res[f"forward_chunk{c}"] = rate(time_eager(fwd, args.steps, args.warmup))
-    model.chunk, model._ws = deberta.DEFAULT_CHUNK, None
+    sweep(model, deberta.DEFAULT_CHUNK, args.chunks, measure)
     if args.table:
-        rows = kernel_table(fwd)
-        print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s}")
-        for r in rows:
-            print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} {r['tflops'] if r['tflops'] is not None else '':>8}")
-        res["kernels"] = rows
+        res["kernels"] = kernel_table(fwd)
+        print_table(res["kernels"])
     # the attention kernel alone against the bias-free, mask-free fused attention on the same rows
     n = min(N, deberta.DEFAULT_CHUNK)
     qkv = torch.randn(n * T, 3 * d, generator=g).to(torch.bfloat16).cuda()

@@ -11,19 +11,10 @@
 
     python tools/vit_bench.py [--frames 480] [--chunks 32,96,160,480] [--steps 10] [--warmup 3] [--table] [--no-torch]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
-import argparse
 import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
+from backbone_bench import kernel_table, parser, print_table, sweep, time_eager  # (first: it sets the import path)
 import torch
-
-from backbone_bench import kernel_table, time_eager
 
 GFLOP_PER_FRAME = 35.1
 
@@ -49,13 +40,8 @@ def _bytes(label: str, detail) -> float:
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = parser(steps=10, warmup=3, torch_yardstick=True)
     ap.add_argument("--frames", type=int, default=480)
-    ap.add_argument("--chunks", default="")
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--table", action="store_true")
-    ap.add_argument("--no-torch", action="store_true")
     args = ap.parse_args()
     import vit_ref
     from mmfusion import vit
@@ -68,20 +54,14 @@ def main():
     x = torch.rand(N, 3, cfg.image_size, cfg.image_size, generator=torch.Generator().manual_seed(1)).cuda()
     res = {"model": "ViT-base/16-224, frozen, bf16 storage", "frames": N, "gflop_per_frame": GFLOP_PER_FRAME,
            "default_chunk": vit.DEFAULT_CHUNK, "workspace_mb_per_image": round(model.workspace_bytes_per_image() / 2 ** 20, 2)}
-    chunks = [int(c) for c in args.chunks.split(",") if c] or [vit.DEFAULT_CHUNK]
-    for c in chunks:
-        model.chunk = c
+
+    def measure(c):
         res[f"cls_features_chunk{c}"] = _rate(time_eager(lambda: model.cls_features(x), args.steps, args.warmup), N)
         res[f"forward_chunk{c}"] = _rate(time_eager(lambda: model(x), args.steps, args.warmup), N)
-    model.chunk = vit.DEFAULT_CHUNK
-    model._ws = None
+    sweep(model, vit.DEFAULT_CHUNK, args.chunks, measure)
     if args.table:
-        rows = kernel_table(lambda: model.cls_features(x), bytes_of=_bytes)
-        print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s} {'TB/s':>6s}")
-        for r in rows:
-            print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} "
-                  f"{r['tflops'] if r['tflops'] is not None else '':>8} {r['tb_per_s'] if r['tb_per_s'] is not None else '':>6}")
-        res["kernels"] = rows
+        res["kernels"] = kernel_table(lambda: model.cls_features(x), bytes_of=_bytes)
+        print_table(res["kernels"])
     if not args.no_torch:
         # the yardstick: the restatement itself in bf16 through stock torch, in chunks of the same size (the same memory bound)
         sd16 = {k: v.cuda().to(torch.bfloat16) for k, v in sd.items()}

@@ -11,19 +11,10 @@
 
     python tools/w2v_bench.py [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--no-torch]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
-import argparse
 import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-os.environ.setdefault("MMFUSION_CONFIG_MKDIRS", "0")
+from backbone_bench import kernel_table, parser, print_table, sweep, time_eager  # (first: it sets the import path)
 import torch
-
-from backbone_bench import kernel_table, time_eager
 
 
 def gflop_per_clip(cfg, L: int) -> dict:
@@ -38,14 +29,9 @@ def gflop_per_clip(cfg, L: int) -> dict:
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = parser(steps=5, warmup=2, torch_yardstick=True)
     ap.add_argument("--clips", type=int, default=16)
     ap.add_argument("--samples", type=int, default=160000)
-    ap.add_argument("--chunks", default="")
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--table", action="store_true")
-    ap.add_argument("--no-torch", action="store_true")
     args = ap.parse_args()
     import w2v_ref
     from mmfusion import wav2vec2
@@ -63,17 +49,13 @@ def main():
 
     res = {"model": "wav2vec2-base, frozen, bf16 storage", "clips": N, "samples": L, "frames": model.frames(L), "gflop_per_clip": gf,
            "default_chunk": wav2vec2.DEFAULT_CHUNK, "workspace_mb_per_clip": round(model.workspace_bytes_per_clip(L) / 2 ** 20, 2)}
-    chunks = [int(c) for c in args.chunks.split(",") if c] or [wav2vec2.DEFAULT_CHUNK]
-    for c in chunks:
-        model.chunk, model._ws = c, None
+
+    def measure(c):
         res[f"forward_chunk{c}"] = rate(time_eager(lambda: model(x), args.steps, args.warmup))
-    model.chunk, model._ws = wav2vec2.DEFAULT_CHUNK, None
+    sweep(model, wav2vec2.DEFAULT_CHUNK, args.chunks, measure)
     if args.table:
-        rows = kernel_table(lambda: model(x))
-        print(f"{'kernel':58s} {'calls':>5s} {'ms':>9s} {'share':>7s} {'TFLOP/s':>8s}")
-        for r in rows:
-            print(f"{r['kernel']:58s} {r['calls']:5d} {r['ms']:9.4f} {r['share']:7.2%} {r['tflops'] if r['tflops'] is not None else '':>8}")
-        res["kernels"] = rows
+        res["kernels"] = kernel_table(lambda: model(x))
+        print_table(res["kernels"])
     model._ws = None
     torch.cuda.empty_cache()
     if not args.no_torch:
