@@ -1,18 +1,20 @@
-// Grouped bf16 GEMM on the gfx950 matrix cores (v_mfma_f32_16x16x32_bf16), f32 accumulate: C-ABI entry points,
-// validation and the choice of kernel generation.
+// Grouped bf16 GEMM on the gfx950 matrix cores (v_mfma_f32_16x16x32_bf16 in gemm2, v_mfma_f32_32x32x16_bf16 in gemm6 / gemm7), f32
+// accumulate: C-ABI entry points, validation and the choice of kernel generation.
 //
 // One launch = up to MMF_GEMM_MAX_PROBLEMS independent problems (the six cross-modal blocks'
 // projections / FFNs of MulT, models/fusion_layers.py:146-153, are issued together so the grid
 // has >> 256 workgroups even though each problem is small).  The problem table travels by value
 // in the kernel arguments, so a launch is self-contained and hipGraph-capturable.
 //
-// Kernels (round 4: three are left): gemm2.hip (LDS-DMA ring, 256 x 128 tile, eight waves: the general kernel — any K, small launches),
-// gemm6.hip (256 x 256 tile, one wave per SIMD with 128 x 128 wave tiles: wgrad, and NT / NN launches the persistent form has no flag set
-// for) and gemm7.hip (gemm6's tile walked by persistent workgroups, outputs through LDS: the NT / NN launches of the fusion step).  Earlier
-// generations — the register-staged 128 x 128 kernel and gemm3 (rounds 1-2), gemm4 (256 x 256 ring, eight waves; stream-K) and gemm5
-// (32-deep ring, two workgroups per CU) (rounds 2-3) — are in git history with their measurements in DESIGN.md section 5; the last two
-// left when a same-box A/B of the selection rule without them came out level or ahead on all four workloads (MulT 2.116 -> 2.088 ms,
-// hierarchical 2.75 = 2.75, training step 3.33 -> 3.34, MELD-shaped 1.076 -> 1.070).
+// Kernels (three): gemm2.hip (LDS-DMA ring, 256 x 128 tile, eight waves: the general kernel — any K, small launches),
+// gemm6.hip (256 x 256 tile, one wave per SIMD with 128 x 128 wave tiles, a 32-deep x 4-stage LDS ring, one tile per workgroup: wgrad,
+// and every NT / NN launch the persistent form refuses — f32 output, a flag set it does not instantiate, K < 160, N or a leading
+// dimension of C / aux no multiple of 8) and gemm7.hip (gemm6's tile and ring walked by persistent workgroups, outputs through LDS: the NT / NN
+// launches of the fusion step); gemm6_parts.h holds what the last two share.  Earlier generations — the register-staged 128 x 128
+// kernel and gemm3 (rounds 1-2), gemm4 (256 x 256 ring, eight waves; stream-K) and gemm5 (32-deep ring, two workgroups per CU)
+// (rounds 2-3) — are in git history with their measurements in DESIGN.md section 5; the last two left in round 4, when a same-box
+// A/B of the selection rule without them came out level or ahead on all four workloads (MulT 2.116 -> 2.088 ms, hierarchical
+// 2.75 = 2.75, training step 3.33 -> 3.34, MELD-shaped 1.076 -> 1.070).
 #include "mmf_internal.h"
 #include <stdlib.h>
 

@@ -10,6 +10,9 @@ namespace {
 
 constexpr int BM = 256, BN = 256;
 constexpr int NTHREADS = 256;
+// the LDS ring of both kernels: NS stages of BK k-columns (a stage is BK / 16 = 2 k-substeps of the 32x32x16 MFMA).  A fifth stage
+// and a 64-deep x 2-stage ring measured level or worse and left with their template axes.
+constexpr int BK = 32, NS = 4;
 
 struct GemmArgs {
   int nprob;
@@ -24,6 +27,7 @@ struct GemmArgs {
 };
 
 typedef __attribute__((address_space(3))) void lds_void_t;
+typedef int i32x4_t __attribute__((ext_vector_type(4)));      // a buffer descriptor as the "s" operand of an LDS-DMA statement
 
 template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -117,10 +121,27 @@ __device__ __forceinline__ void frag_wait(Frag4<false>& a, Frag4<true, 3>& b) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(a.v[3]), "+v"(b.lo[0]), "+v"(b.lo[1]), "+v"(b.lo[2]),
                "+v"(b.hi[0]), "+v"(b.hi[1]), "+v"(b.hi[2]));
 }
+// Read unit u of a k-substep, one per MFMA slot: u = 0..3 the m-operand's fragments, u = 4..3 + NF the n-operand's NF (4; 3 for
+// gemm7's 96-column wave tile), of substep G of the stage at byte offset so.  u is the index of an unrolled loop: one arm is
+// left.  A macro, the form it had in both kernels: it is used inside their stage lambdas and takes WA / WB (tile widths) and
+// la0 / la1 / lb0 / lb1 (the lane's fragment addresses) from there by name; moved here as text, it left both kernels' generated code
+// as it was (tools/kernel_isa_diff.py).
+#define MMF_G6_READ(NF, dstA, dstB, G, u, so)                                                          \
+  do {                                                                                                 \
+    if ((u) == 0) dstA.template issue1<WA, G, 0, 0>(la0 + (so), la1 + (so));                            \
+    if ((u) == 1) dstA.template issue1<WA, G, 0, 1>(la0 + (so), la1 + (so));                            \
+    if ((u) == 2) dstA.template issue1<WA, G, 0, 2>(la0 + (so), la1 + (so));                            \
+    if ((u) == 3) dstA.template issue1<WA, G, 0, 3>(la0 + (so), la1 + (so));                            \
+    if ((u) == 4) dstB.template issue1<WB, G, 0, 0>(lb0 + (so), lb1 + (so));                            \
+    if ((u) == 5) dstB.template issue1<WB, G, 0, 1>(lb0 + (so), lb1 + (so));                            \
+    if ((u) == 6) dstB.template issue1<WB, G, 0, 2>(lb0 + (so), lb1 + (so));                            \
+    if constexpr ((NF) == 4) { if ((u) == 7) dstB.template issue1<WB, G, 0, (NF) - 1>(lb0 + (so), lb1 + (so)); } \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
 
 // per-lane source offset (bytes, relative to the operand tile's first element at k = 0) of 1-KiB piece p: the inverse of the image.
 // W: a KR tile's width (its n or m extent: 256, or 192 for gemm7's 96-column form)
-template <bool KR, int BK, int W = 256>
+template <bool KR, int W = 256>
 __device__ __forceinline__ unsigned piece_voff(int p, int ld, int lane) {
   constexpr int NC = (KR ? W : BK) / 32;
   const int st = 2 * p + (lane >> 5), rg = st / NC, cc = st % NC;
@@ -128,19 +149,14 @@ __device__ __forceinline__ unsigned piece_voff(int p, int ld, int lane) {
   return (unsigned)(row * ld * 2 + ch * 16);
 }
 
-// tile t of problem P -> (m0, n0): super-rows of 8 m-tiles, n fastest across a super-row (gemm4.hip).  TBN: the tile width (gemm7:
+// tile t of problem P -> (m0, n0): super-rows of GROUP_M m-tiles, n fastest across a super-row.  TBN: the tile width (gemm7:
 // 256 or 192)
 template <int TBN = BN>
 __device__ __forceinline__ void tile_origin(const mmf_gemm_problem& P, const int t, int& m0, int& n0) {
   const int tiles_m = (P.M + BM - 1) / BM, tiles_n = (P.N + TBN - 1) / TBN;
   // super-rows of 8 m-tiles.  (Round 4 tried the height that makes an XCD's 32 concurrent tiles touch the fewest operand panels — 32 / tiles_n
-  // for narrow outputs, 11 x 3 instead of 8 x 3 + 8 x 1 at N = 768: the step got SLOWER, 2.027 -> 2.052 ms same box.)  MMF_GEMM_GROUPM
-  // (build-time) pins another height for A/Bs.
-#ifdef MMF_GEMM_GROUPM
-  constexpr int GROUP_M = MMF_GEMM_GROUPM;
-#else
+  // for narrow outputs, 11 x 3 instead of 8 x 3 + 8 x 1 at N = 768: the step got SLOWER, 2.027 -> 2.052 ms same box.)
   constexpr int GROUP_M = 8;
-#endif
   const int grp = t / (GROUP_M * tiles_n), rem = t % (GROUP_M * tiles_n);
   const int gm = min(GROUP_M, tiles_m - grp * GROUP_M);
   m0 = (grp * GROUP_M + rem % gm) * BM;
@@ -153,8 +169,9 @@ __device__ __forceinline__ void tile_origin(const mmf_gemm_problem& P, const int
 // round trips.  Everything it reads is therefore requested up front: the bias once, and per 32-row block tm the aux row pieces /
 // old C values of block tm + 1 before block tm is finished and stored.
 // CT: the epilogue flags as a compile-time mask (alpha = 1, no dropout), or -1: every flag tested at run time.  One wave per SIMD
-// walks the 64 register groups alone: with the flags tested per group the epilogue of a 256 x 256 tile took 10.7 us (ablation
-// -DMMF_G6_DBG=64), ~4 of which are the CU's store path; the step's flag sets are instantiated (tile_epilogue below).
+// walks the 64 register groups alone: with the flags tested per group the epilogue of a 256 x 256 tile took 10.7 us (measured
+// against a build without the epilogue; gemm6's ablation builds are in git history, as of the parent of the commit that removed them),
+// ~4 of which are the CU's store path; the step's flag sets are instantiated (tile_epilogue below).
 template <bool OUT_F32, int CT>
 __device__ __forceinline__ void tile_epilogue_mode(const GemmArgs& args, const mmf_gemm_problem& P, const int pi, const int mb, const int nb,
                                                    f32x16_t (&acc)[4][4], const int lane, const int epi_all) {

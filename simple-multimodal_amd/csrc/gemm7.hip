@@ -3,8 +3,8 @@
 //
 // Why.  A K = 768 tile of gemm6 is 2.7 us of prologue (the ring fill: 128 KiB per CU requested by all 256 CUs at once), 15.4 us of
 // k-loop and 4-5 us of epilogue, and in a launch of one to three rounds every CU is in the same phase at the same time: the
-// prologue is an HBM burst with the matrix pipe idle, the epilogue a store burst (rounds 2-3; ablation
-// -DMMF_G6_DBG=64).  Here
+// prologue is an HBM burst with the matrix pipe idle, the epilogue a store burst (rounds 2-3; measured with
+// gemm6's no-epilogue ablation build, in git history as of the parent of the commit that removed the ablation builds).  Here
 //   * workgroup w (one per CU, grid = min(tiles, CUs)) takes the tiles w, w + grid, ... of the launch's XCD-aware tile order
 //     (mmf_xcd_tile: an XCD's 32 workgroups still share A / B panels in its L2);
 //   * the LDS-DMA stream never stops: while tile j's last NS stages are multiplied, the refills of the ring fetch the first NS
@@ -26,7 +26,6 @@
 
 namespace {
 
-constexpr int BK = 32, NS = 4;
 constexpr int TILE = 256 * BK * 2, PPO = BK / 8;             // the m-operand tile: 16 KiB, 4 pieces per wave and stage
 // the n-operand tile of the TN form: TN * 64 columns, TN * 4 KiB (TN pieces per wave); a stage holds both tiles
 template <int TN> struct Form {
@@ -34,8 +33,6 @@ template <int TN> struct Form {
   static constexpr int LDS = NS * STAGE + 4 * 8192;          // the ring and the four waves' output staging regions
 };
 static_assert(Form<4>::LDS == 160 * 1024 && Form<3>::LDS == 144 * 1024, "LDS of the two forms");
-
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 // what the fetch side needs of the NEXT tile (wave-uniform): first element of each operand tile, bytes from there to the operand's
 // last valid element (< 2 GiB: host), bytes per stage of the n-operand, stages
@@ -229,9 +226,9 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   unsigned voff[PPW], voffn[PPW];
   auto set_voff = [&](unsigned (&v)[PPW], int la, int lb) {
 #pragma unroll
-    for (int i = 0; i < PPO; ++i) v[i] = piece_voff<A_KR, BK>(wave + 4 * i, la, lane);
+    for (int i = 0; i < PPO; ++i) v[i] = piece_voff<A_KR>(wave + 4 * i, la, lane);
 #pragma unroll
-    for (int i = 0; i < TN; ++i) v[PPO + i] = piece_voff<B_KR, BK, BNT>(wave + 4 * i, lb, lane);
+    for (int i = 0; i < TN; ++i) v[PPO + i] = piece_voff<B_KR, BNT>(wave + 4 * i, lb, lane);
   };
   set_voff(voff, lda, ldb);
   char* const my_pieces = smem + wave * 1024;
@@ -385,18 +382,6 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     asm volatile("" ::"a"(acc[tn][tm]));
     __builtin_amdgcn_sched_barrier(0);
   };
-#define MMF_G7_READ(dstA, dstB, G, u, so)                                                              \
-  do {                                                                                                 \
-    if ((u) == 0) dstA.template issue1<WA, G, 0, 0>(la0 + (so), la1 + (so));                            \
-    if ((u) == 1) dstA.template issue1<WA, G, 0, 1>(la0 + (so), la1 + (so));                            \
-    if ((u) == 2) dstA.template issue1<WA, G, 0, 2>(la0 + (so), la1 + (so));                            \
-    if ((u) == 3) dstA.template issue1<WA, G, 0, 3>(la0 + (so), la1 + (so));                            \
-    if ((u) == 4) dstB.template issue1<WB, G, 0, 0>(lb0 + (so), lb1 + (so));                            \
-    if ((u) == 5) dstB.template issue1<WB, G, 0, 1>(lb0 + (so), lb1 + (so));                            \
-    if ((u) == 6) dstB.template issue1<WB, G, 0, 2>(lb0 + (so), lb1 + (so));                            \
-    if constexpr (TN == 4) { if ((u) == 7) dstB.template issue1<WB, G, 0, TN - 1>(lb0 + (so), lb1 + (so)); } \
-    __builtin_amdgcn_sched_barrier(0);                                                                 \
-  } while (0)
 
   // One stage (gemm6.hip's schedule, BK = 32: two k-substeps of NMF = 4 TN MFMAs and NRD = 4 + TN fragment reads).  g: the workgroup's running stage count (ring slot
   // g % NS).  kt == ksw: this is stage KT - NS of its tile — from its hand-over on the refills fetch the NEXT tile (or nothing).
@@ -412,7 +397,7 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
 #pragma unroll
     for (int i = 0; i < NMF; ++i) {
       mf(fa[0], fb[0], i);
-      if (i < NRD) MMF_G7_READ(fa[1], fb[1], 1, i, so);
+      if (i < NRD) MMF_G6_READ(TN, fa[1], fb[1], 1, i, so);
       if (i == NRD)     hot_piece(std::integral_constant<int, 4>{}, ring_prev);
       if (i == NRD + 2) hot_piece(std::integral_constant<int, 5>{}, ring_prev);
       if (i == NRD + 4) hot_piece(std::integral_constant<int, 6>{}, ring_prev);
@@ -436,7 +421,7 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
 #pragma unroll
     for (int i = 4; i < NMF; ++i) {
       mf(fa[1], fb[1], i);
-      if (i < 4 + NRD) MMF_G7_READ(fa[0], fb[0], 0, i - 4, sn);
+      if (i < 4 + NRD) MMF_G6_READ(TN, fa[0], fb[0], 0, i - 4, sn);
       if (i == 4) {                                            // both descriptors one stage on (eight scalar instructions)
         advance(dA, stepA);
         advance(dB, stepB);
@@ -511,7 +496,6 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     }
   }
   vm_wait<0>();                       // the zero-range refills behind the last tile
-#undef MMF_G7_READ
 }
 
 template <bool B_KR, int CT, int TN>

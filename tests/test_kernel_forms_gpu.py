@@ -339,6 +339,45 @@ def test_gemm_f32_layouts_and_epilogues(layout, M, N, K):
         assert rel(db, host(A).sum(0) + db0) < F32_TOL
 
 
+# ---------------------------------------------------------------------------------------- gemm6: every stage form
+# The one-wave-per-SIMD kernel's stage body is instantiated per role (csrc/gemm6.hip, `stage`): the lone stage of a one-step
+# sweep, a sweep's first stage, the steady loop (both refills, no condition), the stages around it with the ring running dry, and
+# the last.  At 32 k-columns per stage, K = 32 is the lone stage, 64 and 128 never reach the steady loop (2 and 4 steps: the ring of
+# four stages is filled once and runs dry), 160 enters it exactly once and 320 runs it six times; TN's K = 72 leaves a
+# zero-filled tail in its third stage.  300 x 264 (TN: 296, its m extent is the operands' contiguous one: a multiple of 8) is two
+# tiles each way with a boundary tile in M and in N.
+G6_CASES = [(lay, K) for lay in (GEMM_NT, GEMM_NN, GEMM_TN) for K in (32, 64, 128, 160, 320)] + [(GEMM_TN, 72)]
+
+
+@pytest.mark.parametrize("layout,K", G6_CASES, ids=[f"{'NT NN TN'.split()[lay]}-K{K}" for lay, K in G6_CASES])
+def test_gemm6_stage_forms(layout, K):
+    """generation 6 pinned, both output types (all six kernels of gemm6.hip), every output pre-filled with NaN; TN also with the
+    fused bias gradient, whose extra MFMAs ride in every stage form"""
+    L = lib.load()
+    M, N = (296 if layout == GEMM_TN else 300), 264
+    a16 = bf(rnd(*((K, M) if layout == GEMM_TN else (M, K)), seed=600 + K))
+    b16 = bf(rnd(*((N, K) if layout == GEMM_NT else (K, N)), seed=700 + K, scale=K ** -0.5))
+    ref = f32_gemm_ref(layout, a16, b16)
+    lib.check(L.mmf_gemm_select_impl(6))
+    try:
+        c32, c16 = nan_like((M, N)), nan_like((M, N), torch.bfloat16)
+        ops.gemm(layout, a16, b16, c32)
+        assert L.mmf_gemm_last_impl() == 6
+        ops.gemm(layout, a16, b16, c16)
+        assert L.mmf_gemm_last_impl() == 6
+        assert rel(c32, ref) < F32_TOL, rel(c32, ref)
+        assert rel(c16, ref) < BF16_TOL, rel(c16, ref)
+        if layout == GEMM_TN:
+            db0 = rnd(M, seed=800 + K).float().double()
+            db, cw = f32(db0), nan_like((M, N))
+            ops.gemm(layout, a16, b16, cw, bias=db, epilogue=EPI_COLSUM_A)
+            assert L.mmf_gemm_last_impl() == 6
+            assert rel(cw, ref) < F32_TOL, rel(cw, ref)
+            assert rel(db, host(a16).sum(0) + db0) < F32_TOL, rel(db, host(a16).sum(0) + db0)
+    finally:
+        lib.check(L.mmf_gemm_select_impl(0))
+
+
 def test_gemm_f32_max_problem_count():
     """MMF_GEMM_MAX_PROBLEMS problems of ragged shapes in one launch (NT, bias + ReLU)"""
     L = lib.load()

@@ -11,22 +11,13 @@ For a trace of tests/test_streaming_small_gpu.py (the kernels of elementwise.hip
 For a trace of tests/test_attention_paths_gpu.py (the twelve instantiations of attention2.hip: forward, dQ and dK/dV, each at
 head_dim 64 and 96, each with and without dropout; profiles/attention_form_coverage.txt):
     --only '^attn_(fwd|bwd)'    (attn_weights_mean_kernel of small.hip belongs to the streaming file's list above)
-Exit status 1 if an instantiation outside DELIBERATELY_UNLAUNCHED was never launched.
+Exit status 1 if an instantiation was never launched.
 """
 import argparse
 import csv
 import re
 import subprocess
 import sys
-
-# forms no default dispatch reaches, kept on purpose (each with the switch that selects it)
-DELIBERATELY_UNLAUNCHED = {
-    # MMF_GEMM6_CFG=1 / 2: the 32-deep x 5-stage and 64-deep x 2-stage rings of generation 6, A/B ablations of its
-    # default 32 x 4 (csrc/gemm6.hip)
-    r"gemm6_grouped_kernel<(true|false), (true|false), 32, 5, (true|false)>",
-    r"gemm6_grouped_kernel<(true|false), (true|false), 64, 2, (true|false)>",
-}
-
 
 def key(name: str) -> str:
     """kernel name with its template arguments, without return type, namespaces or parameter list:
@@ -75,15 +66,12 @@ def main(argv=None) -> int:
     if a.only:
         forms = {k for k in forms if re.search(a.only, k)}
     ran = launched(a.stats)
-    deliberate = {k for k in forms if any(re.fullmatch(p, k) for p in DELIBERATELY_UNLAUNCHED)}
     hit = sorted(forms & ran)
-    missed = sorted(forms - ran - deliberate)
+    missed = sorted(forms - ran)
     print(f"{len(forms)} instantiations{' matching ' + repr(a.only) if a.only else ''}; {len(hit)} launched, "
-          f"{len(missed)} never launched, {len(deliberate - ran)} deliberately unlaunched")
+          f"{len(missed)} never launched")
     for k in hit:
         print(f"  launched    {k}")
-    for k in sorted(deliberate - ran):
-        print(f"  deliberate  {k}")
     for k in missed:
         print(f"  NEVER       {k}")
     return 1 if missed else 0
