@@ -108,7 +108,7 @@ int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_problems, int 
  * one wave per SIMD with 128x128 wave tiles [gemm6.hip: any K for TN, K % 32 == 0 for NT / NN, no aux epilogue with f32 output];
  * 7 = generation 6 on persistent workgroups (below).  Automatic (gemm.hip auto_impl): 6 when the launch has 256x256 tiles for at
  * least half of the CUs (TN, wgrad) or a quarter of them (NT / NN) and generation 6 takes its shapes, else 2; a launch that
- * gets 6 is promoted to 7 whenever generation 7 takes it (MMF_GEMM_PERSIST=0: never), whatever its tile count.  A pinned
+ * gets 6 is promoted to 7 whenever generation 7 takes it, whatever its tile count.  A pinned
  * generation is used for every launch it takes; the others fall back 7 -> 6 -> 2.  Any other value (1 / 3 left in round 3, 4 / 5
  * in round 4) is refused with MMF_E_UNSUPPORTED.  Results are identical up to f32 summation order (and, with a bias, one bf16 ulp
  * between 6 and 7); exists so that A/B timings can be interleaved inside one process.  A process-wide setting, not synchronised

@@ -1,6 +1,6 @@
 // Grouped fused attention (forward, dQ, dK/dV): fat workgroups, LDS-DMA ring, one dual-use LDS image.
 //
-// Structure (rounds 1-2; measurements behind each choice in DESIGN.md section 5):
+// Structure (measurements behind each choice in DESIGN.md section 5 and profiles/r03_attn_*):
 //   * all attention problems of a stage (the six cross blocks, or the three self-attentions, of a MulT pass — unequal
 //     Tq / Tk) go out as ONE launch; workgroup ids are remapped so that the chunks of one (b, h) (and neighbouring heads
 //     of one batch row) run on the SAME XCD (blockIdx % 8) and share its L2;
@@ -12,8 +12,7 @@
 //     next tile in flight under the current tile's MFMAs; rows past T come back as zeros from the buffer range check;
 //   * softmax on raw scores, p = exp2(fma(s, c, -m)); the running maximum is raised only when a row's block maximum
 //     exceeds it by 2^DEFER (guide T13), 32-key blocks, blocks that hold only padding are skipped;
-//   * transposed operands by asm ds_read_b64_tr_b16 with counted lgkmcnt waits.
-// Round 3 (each from a measurement, profiles/r03_attn_*):
+//   * transposed operands by asm ds_read_b64_tr_b16 with counted lgkmcnt waits;
 //   * ONE LDS image for row reads and transposed reads (attn_helpers.h: 8-row x 32-column subtiles, XOR swizzle) instead
 //     of 16-byte padded rows: the transposed reads were 2-way bank-conflicted, and the LDS port is as busy as the matrix
 //     pipe in these kernels (~1 KiB of fragment reads per MFMA);
@@ -83,10 +82,7 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
   for (int j = 0; j < ntiles; ++j) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces of tile j have landed
-    __builtin_amdgcn_s_barrier();                          // ... everyone's; the stage of tile j-1 is free
-    asm volatile("" ::: "memory");
-    if (j + 1 < ntiles) issue(j + 1);
+    ring_handover(j, ntiles, issue, [](int) {});
     if constexpr (ACTIVE) {
       const char* sK = smem + (j & 1) * STAGE_B;
       const TrBase vaV = tr_base(smem_lds + (j & 1) * STAGE_B + TILE_B, tlo, thi);
@@ -99,7 +95,6 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
         f32x16_t s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        mfma_prio(1);
         // all KS fragment reads in flight before the first MFMA: one exposed LDS latency per block instead of KS / 2
         bf16x8_t kf[KS];
 #pragma unroll
@@ -108,8 +103,7 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);                 // the asm V^T reads below are invisible to the compiler's lgkmcnt count
-        mfma_prio(0);
-        constexpr int TD = 2;                              // the first two V^T fragments land under the softmax
+        constexpr int TD = FWD_TRDEPTH;
         s16x4_t lo[2 * DT], hi[2 * DT];
         PvStepD<DH, KT, TD, 0>::prime(vaV, lo, hi);
         if (k0 + 32 > Tk) {                                // ragged block
@@ -179,13 +173,7 @@ __global__ __launch_bounds__(NT, 3)
 void attn_fwd2n_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_B];
-  const int bid = blockIdx.x;
-  int pi = 0;
-  while (pi + 1 < a.nprob && bid >= a.blk_start[pi + 1]) ++pi;
-  // XCD x (= blockIdx % 8; blk_start is a multiple of 8) walks a contiguous range of the problem's work
-  // items, so the chunks of one (b, h) and the heads of one batch row share that XCD's L2
-  const int loc = bid - a.blk_start[pi], n8 = (a.blk_start[pi + 1] - a.blk_start[pi]) >> 3;
-  const int item = (loc & 7) * n8 + (loc >> 3);
+  const auto [pi, item] = work_item(a);
   if (item >= a.nwg[pi]) return;
   const mmf_attn_problem& P = a.p[pi];
   const int nchunk = a.nchunk[pi], rpc = a.rpc[pi];         // rpc <= 128 here
@@ -198,16 +186,10 @@ void attn_fwd2n_kernel(const AttnArgs2 a) {
 }
 
 // ================================================================================================
-// backward, second generation.  Same arithmetic as attention.hip's two kernels (dQ + delta, then dK/dV; recompute
-// from LSE; no atomics, deterministic); what changes is how the swept tiles reach the MFMAs:
-//   * K/V (dQ kernel) and Q/dO (+ LSE, delta; dK/dV kernel) tiles arrive by LDS-DMA into a 2-stage ring, the next
-//     tile in flight under the current tile's MFMAs.  The first generation fetched through registers and, in the
-//     dK/dV kernel, only AFTER the MFMAs: one exposed HBM/L2 latency per tile, which made the x30 problems
-//     (one active wave walking 8 tiles) cost 37-41 us each;
-//   * XCD-aware work order, heaviest problem first (see the forward);
-//   * 32-row blocks that hold only padding are skipped;
-//   * transposed operands by asm ds_read_b64_tr_b16 with counted waits, the next fragment in flight under the
-//     current MFMAs.
+// Backward: the dQ kernel (which also writes delta), then the dK/dV kernel; P is recomputed from LSE; no atomics,
+// deterministic.  The swept tiles — K/V in the dQ kernel, Q/dO (+ LSE, delta) in the dK/dV kernel — ride the same 2-stage
+// LDS-DMA ring as the forward's: fetched through registers, and in the dK/dV kernel only AFTER the MFMAs, every tile
+// cost one exposed HBM/L2 latency, which made the x30 problems (one active wave walking 8 tiles) 37-41 us each.
 // ================================================================================================
 
 // dQ^T += K^T . dS^T for block KT: PvStep with the K tile as the transposed operand.
@@ -264,22 +246,17 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
   const float c = a.scale * LOG2E;
   const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh)) : 0u;
   const unsigned qidx = (unsigned)qrow * (unsigned)Tk;
-  f32x16_t dq[1][DT];
+  f32x16_t dq[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dq[0][dt][r] = 0.f;
+    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
   if constexpr (ACTIVE) BSTAMP(0);
   for (int j = 0; j < ntiles; ++j) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (ACTIVE) BSTAMP(1);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if constexpr (ACTIVE) BSTAMP(2);
-    if (j + 1 < ntiles) issue(j + 1);
+    ring_handover(j, ntiles, issue, [&](int i) { if constexpr (ACTIVE) BSTAMP(i); });
     if constexpr (ACTIVE) BSTAMP(3);
     if constexpr (ACTIVE) {
       const char* sK = smem + (j & 1) * STAGE_B;
@@ -292,19 +269,17 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
         f32x16_t s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-        mfma_prio(1);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sK, 32 * KT, ks, lane), qf[ks], s, 0, 0, 0);
           dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sV, 32 * KT, ks, lane), dof[ks], dp, 0, 0, 0);
         }
-        mfma_prio(0);
         BSTAMP(4);
-        constexpr int TD = MMF_DQ_TRDEPTH;
+        constexpr int TD = DQ_TRDEPTH;
         s16x4_t lo[2 * DT], hi[2 * DT];
         PvStepD<DH, KT, TD, 0>::prime(vaK, lo, hi);         // the first K^T fragments land under the dS arithmetic
         const bool ragged = k0 + 32 > Tk;
-        f32x16_t ds[1];
+        f32x16_t ds;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float p = fast_exp2(__builtin_fmaf(s[r], c, -lse2));
@@ -312,11 +287,11 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
           if (ragged) p = key < Tk ? p : 0.f;
           float dpv = dp[r];                                // d(P_dropped) -> dP through the same mask
           if (DROP) dpv = mmf_keep(dkey, qidx + (unsigned)key, a.drop_thresh) ? dpv * a.inv_keep : 0.f;
-          ds[0][r] = p * (dpv - delta);                     // dS^T (scale applied at the store)
+          ds[r] = p * (dpv - delta);                        // dS^T (scale applied at the store)
         }
         BSTAMP(5);
         bf16x8_t pf;
-        PvStepD<DH, KT, TD, 0>::run(vaK, lo, hi, ds[0], pf, dq[0]);
+        PvStepD<DH, KT, TD, 0>::run(vaK, lo, hi, ds, pf, dq);
         BSTAMP(6);
       };
       block(std::integral_constant<int, 0>{});
@@ -329,7 +304,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
     // sweep, so the lane id is read again here (guide: "recompute per block (v_mbcnt)")
     int lane_e;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-    store_rows_lds<DH>(dq[0], a.scale, static_cast<unsigned short*>(P.dQ) + qoff, P.ldq, qs, Tq, lane_e, oslice);
+    store_rows_lds<DH>(dq, a.scale, static_cast<unsigned short*>(P.dQ) + qoff, P.ldq, qs, Tq, lane_e, oslice);
     BSTAMP(7);
     BSTAMP_STORE(0);
   }
@@ -340,15 +315,11 @@ __global__ __launch_bounds__(NT, DQ_WAVES_PER_SIMD)
 void attn_bwd_dq2_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_B];
-  const int bid = blockIdx.x;
-  int pi = 0;
-  while (pi + 1 < a.nprob && bid >= a.blk_start[pi + 1]) ++pi;
-  const int loc = bid - a.blk_start[pi], n8 = (a.blk_start[pi + 1] - a.blk_start[pi]) >> 3;
-  const int item = (loc & 7) * n8 + (loc >> 3);
+  const auto [pi, item] = work_item(a);
   if (item >= a.nwg[pi]) return;
   const mmf_attn_problem& P = a.p[pi];
   const int nchunk = a.nchunk[pi];
-  const int bh = item / nchunk, q0 = (item % nchunk) * 128;
+  const int bh = item / nchunk, q0 = (item % nchunk) * ROWS_PER_WG;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int qs = q0 + 32 * wave, pidx = a.orig[pi];
   if (qs < P.Tq) dq2_wave<DH, DROP, true>(a, P, pidx, bh, qs, smem);
@@ -366,8 +337,8 @@ void attn_bwd_dq2_kernel(const AttnArgs2 a) {
 // exact in f32 (8 + 8 + 8 mantissa bits, f32 accumulate).  With D as the initial accumulator of the S (and, without
 // dropout, the dP) chain the subtraction is free:  S' = Q.K^T - LSE / scale,  p = exp2(c S');  dP' = dO.V^T - delta,
 // dS = p dP'.
-// Sweep split as in dq2_wave: a problem with <= 32 keys gives them to waves 0 and 1, wave w works on 32-row query
-// block w of every tile; wave 1's partial dK^T, dV^T are added to wave 0's through LDS at the end.
+// Sweep split (split_wg; sel = the wave's half, -1 without the split): a problem with <= 32 keys gives them to waves 0 and 1,
+// wave w works on 32-row query block w of every tile; wave 1's partial dK^T, dV^T are added to wave 0's through LDS at the end.
 template <int DH, bool DROP, bool ACTIVE>
 __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_problem& P, const int pidx, const int bh,
                                           const int k0, char* smem, const bool split_wg, const int sel) {
@@ -426,12 +397,7 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
 
   if constexpr (ACTIVE) BSTAMP(0);
   for (int j = 0; j < ntiles; ++j) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (ACTIVE) BSTAMP(1);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if constexpr (ACTIVE) BSTAMP(2);
-    if (j + 1 < ntiles) issue(j + 1);
+    ring_handover(j, ntiles, issue, [&](int i) { if constexpr (ACTIVE) BSTAMP(i); });
     if constexpr (ACTIVE) BSTAMP(3);
     if constexpr (ACTIVE) {
       const char* sQ = smem + (j & 1) * STAGE_B;
@@ -450,7 +416,6 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
         f32x16_t s, dp, z;
 #pragma unroll
         for (int r = 0; r < 16; ++r) z[r] = 0.f;
-        mfma_prio(1);
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cl[QS], half == 0), one3, z, 0, 0, 0);   // S' starts at -LSE / scale
         f32x16_t dm;                                                                      // -delta[q] in every key column
         dm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cd[QS], half == 0), one3, z, 0, 0, 0);
@@ -460,9 +425,8 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sQ, 32 * QS, ks, lane), kf[ks], s, 0, 0, 0);
           dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sdO, 32 * QS, ks, lane), vf[ks], dp, 0, 0, 0);
         }
-        mfma_prio(0);
         BSTAMP(4);
-        constexpr int TD = MMF_DKV_TRDEPTH;
+        constexpr int TD = DKV_TRDEPTH;
         s16x4_t lo[4 * DT], hi[4 * DT];
         DkvStepD<DH, QS, TD, 0>::prime(vaQ, vadO, lo, hi);  // the first fragments land under the P / dS arithmetic
         f32x16_t ds;
@@ -531,18 +495,14 @@ __global__ __launch_bounds__(NT, 2)      // dK^T, dV^T, K and V fragments alone 
 void attn_bwd_dkv2_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_B];
-  const int bid = blockIdx.x;
-  int pi = 0;
-  while (pi + 1 < a.nprob && bid >= a.blk_start[pi + 1]) ++pi;
-  const int loc = bid - a.blk_start[pi], n8 = (a.blk_start[pi + 1] - a.blk_start[pi]) >> 3;
-  const int item = (loc & 7) * n8 + (loc >> 3);
+  const auto [pi, item] = work_item(a);
   if (item >= a.nwg[pi]) return;
   const mmf_attn_problem& P = a.p[pi];
   const int nchunk = a.nchunk[pi];
-  const int bh = item / nchunk, kc0 = (item % nchunk) * 128;
+  const int bh = item / nchunk, kc0 = (item % nchunk) * ROWS_PER_WG;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int k0 = kc0 + 32 * wave, pidx = a.orig[pi];
-  const bool split = a.split && P.Tk <= 32;                 // workgroup-uniform
+  const bool split = P.Tk <= 32;                            // workgroup-uniform: the sweep split (dkv2_wave)
   const bool act = split ? wave < 2 : k0 < P.Tk;
   if (act) dkv2_wave<DH, DROP, true>(a, P, pidx, bh, split ? kc0 : k0, smem, split, split ? wave : -1);
   else     dkv2_wave<DH, DROP, false>(a, P, pidx, bh, k0, smem, split, -1);
@@ -577,13 +537,13 @@ int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, 
   if (int rc = check_ranges("mmf_attn_bwd_grouped", problems, n)) return rc;
   AttnArgs2 a;
   if (!(g_attn_stub & 2)) {
-    const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, 128, false, false);   // dQ (+ delta) first
+    const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false);   // dQ (+ delta) first
     launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dq2_kernel<96, true>, attn_bwd_dq2_kernel<96, false>, attn_bwd_dq2_kernel<64, true>,
             attn_bwd_dq2_kernel<64, false>, total, a, s);
     MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dq, v2)");
   }
   if (g_attn_stub & 4) return MMF_OK;
-  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, 128, true, false);        // then dK/dV (reads delta)
+  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, true, false);        // then dK/dV (reads delta)
   launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dkv2_kernel<96, true>, attn_bwd_dkv2_kernel<96, false>, attn_bwd_dkv2_kernel<64, true>,
           attn_bwd_dkv2_kernel<64, false>, total, a, s);
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dkv, v2)");
@@ -596,7 +556,7 @@ int mmf_attn_fwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, 
   if (int rc = check_ranges("mmf_attn_fwd_grouped", problems, n)) return rc;
   if (g_attn_stub & 1) return MMF_OK;
   AttnArgs2 a;
-  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, 128, false, true);
+  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, true);
   launch4(head_dim, a.drop_thresh != 0u, attn_fwd2n_kernel<96, true>, attn_fwd2n_kernel<96, false>, attn_fwd2n_kernel<64, true>,
           attn_fwd2n_kernel<64, false>, total, a, s);
   MMF_CHECK_LAUNCH("mmf_attn_fwd_grouped");

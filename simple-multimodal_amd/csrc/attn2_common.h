@@ -2,35 +2,14 @@
 // LDS image of attn_helpers.h, asm transposed reads with counted waits, and the host-side table fill.
 #pragma once
 #include "mmf_internal.h"
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 #include "attn_helpers.h"
 
 namespace {
 
-#ifndef DQ_WAVES_PER_SIMD
-#define DQ_WAVES_PER_SIMD 3            // dQ kernel at <= 168 registers: three 4-wave workgroups per CU (3 x 52 KiB of LDS)
-#endif
-#ifndef MMF_DKV_TRDEPTH
-#define MMF_DKV_TRDEPTH 3              // transposed fragments in flight ahead of the dV^T / dK^T MFMA chain (DkvStepD)
-#endif
-#ifndef MMF_DQ_TRDEPTH
-#define MMF_DQ_TRDEPTH 1               // ... ahead of the dQ^T chain (PvStepD): the dQ kernel is at its 168-register budget
-#endif
 constexpr float DEFER = 6.0f;          // log2 domain: P <= 64 before a rescale is forced
-// MMF_ATTN_SETPRIO=1 (build-time A/B): raise the wave's issue priority around its MFMA clusters (guide T5), so that of the
-// two waves sharing a SIMD the one entering a matrix phase is not held behind the other's softmax VALU stream
-#ifndef MMF_ATTN_SETPRIO
-#define MMF_ATTN_SETPRIO 0
-#endif
-__device__ __forceinline__ void mfma_prio(int on) {
-#if MMF_ATTN_SETPRIO
-  if (on) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#else
-  (void)on;
-#endif
-}
+constexpr int ROWS_PER_WG = 128;       // rows of the partitioned axis per workgroup: one 32-row block per wave
 
 struct AttnArgs2 {
   int nprob;
@@ -38,7 +17,6 @@ struct AttnArgs2 {
   unsigned drop_thresh, site;
   float inv_keep;
   const unsigned long long* rng_state;
-  int split;      // sweep split of the <= 32-row problems in the backward kernels (MMF_ATTN_SPLIT=0: off)
   int blk_start[MMF_ATTN_MAX_PROBLEMS + 1];   // multiples of 8 (XCD alignment)
   int nwg[MMF_ATTN_MAX_PROBLEMS];             // real workgroups of the problem = B*H*nchunk
   short nchunk[MMF_ATTN_MAX_PROBLEMS];        // query chunks per (b, h)
@@ -46,6 +24,18 @@ struct AttnArgs2 {
   short orig[MMF_ATTN_MAX_PROBLEMS];          // caller's problem index (dropout stream id)
   mmf_attn_problem p[MMF_ATTN_MAX_PROBLEMS];
 };
+
+// A workgroup's problem and its work item in it (item >= nwg[pi]: padding, nothing to do).  XCD x (= blockIdx % 8; blk_start is
+// a multiple of 8) walks a contiguous range of the problem's work items, so the chunks of one (b, h) and the heads of one batch
+// row share that XCD's L2.
+struct WorkItem { int pi, item; };
+__device__ __forceinline__ WorkItem work_item(const AttnArgs2& a) {
+  const int bid = blockIdx.x;
+  int pi = 0;
+  while (pi + 1 < a.nprob && bid >= a.blk_start[pi + 1]) ++pi;
+  const int loc = bid - a.blk_start[pi], n8 = (a.blk_start[pi + 1] - a.blk_start[pi]) >> 3;
+  return {pi, (loc & 7) * n8 + (loc >> 3)};
+}
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -87,6 +77,10 @@ __device__ __forceinline__ bf16x8_t join(const s16x4_t& lo, const s16x4_t& hi) {
 // three waves per SIMD the partner waves cover one wave's LDS latency, what the kernels lacked was LDS bandwidth.
 template <int NF, int D, int N>
 constexpr int tr_pending() { return 2 * ((N + D < NF - 1 ? N + D : NF - 1) - N); }
+constexpr int FWD_TRDEPTH = 2;         // forward, O^T chain (PvStepD): the first two V^T fragments land under the softmax
+constexpr int DKV_TRDEPTH = 3;         // dK/dV kernel, dV^T / dK^T chain (DkvStepD)
+constexpr int DQ_TRDEPTH = 1;          // dQ kernel, dQ^T chain (PvStepD): the kernel is at its 168-register budget
+constexpr int DQ_WAVES_PER_SIMD = 3;   // dQ kernel at <= 168 registers: three 4-wave workgroups per CU (3 x 52 KiB of LDS)
 
 // O^T += V^T . P^T (forward) and dQ^T += K^T . dS^T (dQ kernel) for the 32 keys of block KT of the tile at `va`:
 // fragment n = (k-substep n / DT, d-tile n % DT)
@@ -104,12 +98,10 @@ struct PvStepD {
                                              bf16x8_t& pf, f32x16_t (&o)[DT]) {
     if constexpr (N + D < NF) issue<N + D>(va, lo, hi);
     tr_wait<tr_pending<NF, D, N>()>(lo[N], hi[N]);
-    if constexpr (N == 0) mfma_prio(1);
     const bf16x8_t vf = join(lo[N], hi[N]);
     if constexpr (N % DT == 0) pf = acc_frag(s, N / DT);
     o[N % DT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[N % DT], 0, 0, 0);
     if constexpr (N + 1 < NF) PvStepD<DH, KT, D, N + 1>::run(va, lo, hi, s, pf, o);
-    else mfma_prio(0);
   }
 };
 
@@ -130,14 +122,12 @@ struct DkvStepD {
                                              f32x16_t (&dv)[DT], f32x16_t (&dk)[DT]) {
     if constexpr (N + D < NF) issue<N + D>(vaQ, vadO, lo, hi);
     tr_wait<tr_pending<NF, D, N>()>(lo[N], hi[N]);
-    if constexpr (N == 0) mfma_prio(1);
     const bf16x8_t f = join(lo[N], hi[N]);
     if constexpr (N % (2 * DT) == 0) { pf = acc_frag(pm, N / (2 * DT)); dsf = acc_frag(dsm, N / (2 * DT)); }
     constexpr int dt = (N / 2) % DT;
     if constexpr ((N & 1) == 0) dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, pf, dv[dt], 0, 0, 0);
     else                        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, dsf, dk[dt], 0, 0, 0);
     if constexpr (N + 1 < NF) DkvStepD<DH, QS, D, N + 1>::run(vaQ, vadO, lo, hi, pm, dsm, pf, dsf, dv, dk);
-    else mfma_prio(0);
   }
 };
 
@@ -193,20 +183,28 @@ struct TileDma {
   }
 };
 
-}  // namespace
+// Ring hand-over at the top of tile j's iteration: this wave's pieces of tile j have landed (vmcnt), after the barrier everyone's
+// have and the stage of tile j - 1 is free, so tile j + 1 is issued into it.  stamp(1) / stamp(2): the MMF_ATTN_STAMPS build's
+// segment marks of attention2.hip (nothing in the default build).
+template <typename Issue, typename Stamp>
+__device__ __forceinline__ void ring_handover(int j, int ntiles, const Issue& issue, const Stamp& stamp) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  stamp(1);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  stamp(2);
+  if (j + 1 < ntiles) issue(j + 1);
+}
 
-namespace {
-// Work table: problems heaviest first; rows_per_wg rows of the partitioned axis (queries, or keys for the dK/dV
-// kernel) per workgroup, balanced over the chunks; workgroup ranges padded to multiples of 8 for the XCD map.
+// Work table: problems heaviest first; ROWS_PER_WG rows of the partitioned axis (queries, or keys for the dK/dV
+// kernel) per workgroup, with `balance` spread evenly over the chunks; workgroup ranges padded to multiples of 8 for the XCD map.
 int fill_args2(AttnArgs2& a, const mmf_attn_problem* problems, int n, float scale, float drop_p, const uint64_t* rng_state,
-               uint32_t site, int rows_per_wg, bool by_keys, bool balance) {
+               uint32_t site, bool by_keys, bool balance) {
   a.nprob = n; a.scale = scale;
   a.drop_thresh = (drop_p > 0.f && rng_state) ? mmf_drop_thresh(drop_p) : 0u;
   a.inv_keep = a.drop_thresh ? 1.f / (1.f - (float)a.drop_thresh * (1.f / 4294967296.f)) : 1.f;
   a.site = site;
   a.rng_state = reinterpret_cast<const unsigned long long*>(rng_state);
-  static const int split = [] { const char* e = getenv("MMF_ATTN_SPLIT"); return e ? atoi(e) : 1; }();
-  a.split = split;
   int order[MMF_ATTN_MAX_PROBLEMS];
   for (int i = 0; i < n; ++i) order[i] = i;
   // Launch order = longest per-workgroup chain first: a workgroup's duration is set by the length of its sweep
@@ -215,15 +213,15 @@ int fill_args2(AttnArgs2& a, const mmf_attn_problem* problems, int n, float scal
   // wide problems instead of trailing them on an empty chip.
   auto key = [&](const mmf_attn_problem& q) {
     const int part = by_keys ? q.Tk : q.Tq, sweep = by_keys ? q.Tq : q.Tk;
-    return (long long)((sweep + 63) / 64) * 4096 - std::min(part, rows_per_wg);
+    return (long long)((sweep + 63) / 64) * 4096 - std::min(part, ROWS_PER_WG);
   };
   std::stable_sort(order, order + n, [&](int x, int y) { return key(problems[x]) > key(problems[y]); });
   int total = 0;
   for (int k = 0; k < n; ++k) {
     const mmf_attn_problem& q = problems[order[k]];
     const int part = by_keys ? q.Tk : q.Tq;
-    const int nchunk = (part + rows_per_wg - 1) / rows_per_wg;
-    const int rpc = balance ? (((part + nchunk - 1) / nchunk) + 31) / 32 * 32 : rows_per_wg;
+    const int nchunk = (part + ROWS_PER_WG - 1) / ROWS_PER_WG;
+    const int rpc = balance ? (((part + nchunk - 1) / nchunk) + 31) / 32 * 32 : ROWS_PER_WG;
     a.blk_start[k] = total;
     a.nwg[k] = q.B * q.H * nchunk;
     a.nchunk[k] = (short)nchunk; a.rpc[k] = (short)rpc; a.orig[k] = (short)order[k];

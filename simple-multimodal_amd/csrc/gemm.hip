@@ -36,8 +36,6 @@ static int g_gemm_impl = [] {
   const int v = (e && e[0] >= '0' && e[0] <= '9') ? e[0] - '0' : 0;
   return impl_built(v) ? v : 0;
 }();
-// MMF_GEMM_PERSIST=0: NT / NN launches stay on gemm6 (one tile per workgroup) instead of its persistent form
-static const int g_persist = [] { const char* e = getenv("MMF_GEMM_PERSIST"); return e ? atoi(e) : 1; }();
 
 // The automatic choice: the 256 x 256 one-wave-per-SIMD tile for every launch it supports that gives at least a quarter of the CUs a
 // tile (wgrad: half — a single layer's weight gradient keeps the 256 x 128 ring and its twice as many tiles), gemm2 for the rest.
@@ -84,7 +82,7 @@ extern "C" int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_pro
   const bool pinned = impl != 0;
   if (impl == 0) impl = auto_impl(problems, num_problems, layout);
   const bool ok6 = mmf_gemm6_supports(problems, num_problems, layout) && mmf_gemm6_supports_epi(epilogue, out_f32);
-  if (impl == 6 && !pinned && g_persist && mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 7;
+  if (impl == 6 && !pinned && mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 7;
   if (impl == 7 && !mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 6;
   if (impl == 6 && !ok6) impl = 2;
   t_last_impl = impl;

@@ -3,23 +3,21 @@
 // f32 statistics by wave butterfly reduction, no LDS in the forward.
 // Algorithmic bytes per row: forward 2 x 2d (x in, y out) + 8; backward 3 x 2d (x, dy in; dx out).
 #include "mmf_internal.h"
-#include <stdlib.h>
 
 namespace {
 
 constexpr int ROWS_PER_BLOCK = 4;      // 4 waves, one row each
 constexpr int MAX_CH = 4;              // 4 chunks x 64 lanes x 8 elements = 2048 columns
 
-constexpr int BWD_BLOCK_BUDGET = 2048;  // upper bound of workgroups of a grouped backward launch (workspace rows)
-// workgroups actually used (MMF_LN_BWD_BLOCKS, default below): enough rows in flight per CU to cover the HBM latency
-static int bwd_blocks(bool lane_form) {
-  // the lane form keeps its next row in flight, so two workgroups per CU already cover the HBM latency, and fewer partial
-  // rows are left for the finalize pass (round 3, same box: 2048 / 1024 / 512 workgroups 23.5 / 20.5 / 19.9 us per
-  // three-problem launch, finalize included; the chunk form 25.1 / 24.1 / 23.8)
-  static const int v = [] { const char* e = getenv("MMF_LN_BWD_BLOCKS"); return e ? atoi(e) : 0; }();
-  const int b = v > 0 ? v : (lane_form ? 512 : 2048);
-  return b < 64 ? 64 : (b > BWD_BLOCK_BUDGET ? BWD_BLOCK_BUDGET : b);
-}
+// Workgroups of a launch (round 3, same box, profiles/r03_layernorm.txt).  Forward, chunk form / lane form: three problems of
+// 15,072 rows 13.0 / 9.6 us with 1024 workgroups; all six, 30,144 rows, 20.7 / 16.4 us with 2048.
+constexpr int FWD_BLOCKS = 1024, FWD_BLOCKS_LARGE = 2048;
+constexpr long long FWD_LARGE_ROWS = 20000;            // more rows than this in one launch: FWD_BLOCKS_LARGE
+// Backward: enough rows in flight per CU to cover the HBM latency.  The lane form keeps its next row in flight, so two workgroups
+// per CU already do, and fewer partial rows are left for the finalize pass (2048 / 1024 / 512 workgroups 23.5 / 20.5 / 19.9 us per
+// three-problem launch, finalize included; the chunk form 25.1 / 24.1 / 23.8).
+constexpr int BWD_BLOCKS_LANE = 512;
+constexpr int BWD_BLOCKS_CHUNK = 2048;                 // also the bound the workspace is sized for
 
 struct LnArgs {
   int nprob;
@@ -96,13 +94,74 @@ void ln_fwd_kernel(const LnArgs a) {
   if (lane == 0) { P.mean[row] = mean; P.rstd[row] = rstd; }
 }
 
-// Round 3: the forward in the lane form of ln_bwd_lane_kernel below (lane l owns columns [8 l, +8) of every 512-column block and
-// [512 NV + 4 l, +4) of the last 256; gamma / beta in registers instead of 6 KB of L2 reads per row; a workgroup's waves walk
-// strided rows with the next row's load in flight).
+// Column ownership of the lane form, for d = 512 NV + 256 H8: lane l owns columns [512 c + 8 l, +8) of each of the NV 512-column
+// blocks (16-byte bf16 loads) and [512 NV + 4 l, +4) of the last 256 (8-byte loads), so every lane is busy at d = 768 and a lane's
+// EP values of a per-column vector (gamma, beta, the dgamma / dbeta sums) stay in registers across rows.  Element 8 c + e of a
+// lane is column 512 c + 8 l + e; the last four are columns 512 NV + 4 l + e.
+template <int NV, int H8>
+struct LaneCols {
+  static constexpr int EP = 8 * NV + 4 * H8, D = 512 * NV + 256 * H8;
+  struct Bf16 { u32x4_t v[NV > 0 ? NV : 1]; u32x2_t t; };      // a lane's share of one bf16 row, as loaded
+  static __device__ __forceinline__ void load(const unsigned short* row, int lane, Bf16& r) {
+#pragma unroll
+    for (int c = 0; c < NV; ++c) r.v[c] = *reinterpret_cast<const u32x4_t*>(row + 512 * c + 8 * lane);
+    if (H8) r.t = *reinterpret_cast<const u32x2_t*>(row + 512 * NV + 4 * lane);
+  }
+  static __device__ __forceinline__ void unpack(const Bf16& r, float (&f)[EP]) {
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      float t[8];
+      unpack8(r.v[c], t);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[8 * c + e] = t[e];
+    }
+    if (H8) { f[8 * NV] = bf16lo(r.t[0]); f[8 * NV + 1] = bf16hi(r.t[0]); f[8 * NV + 2] = bf16lo(r.t[1]); f[8 * NV + 3] = bf16hi(r.t[1]); }
+  }
+  static __device__ __forceinline__ void store(unsigned short* row, int lane, const float (&o)[EP]) {
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      const u32x4_t w = {pack_bf16x2(o[8 * c], o[8 * c + 1]), pack_bf16x2(o[8 * c + 2], o[8 * c + 3]),
+                         pack_bf16x2(o[8 * c + 4], o[8 * c + 5]), pack_bf16x2(o[8 * c + 6], o[8 * c + 7])};
+      *reinterpret_cast<u32x4_t*>(row + 512 * c + 8 * lane) = w;
+    }
+    if (H8) {
+      const u32x2_t w = {pack_bf16x2(o[8 * NV], o[8 * NV + 1]), pack_bf16x2(o[8 * NV + 2], o[8 * NV + 3])};
+      *reinterpret_cast<u32x2_t*>(row + 512 * NV + 4 * lane) = w;
+    }
+  }
+  static __device__ __forceinline__ void load_f32(const float* p, int lane, float (&f)[EP]) {
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x4_t g = *reinterpret_cast<const f32x4_t*>(p + 512 * c + 8 * lane + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[8 * c + 4 * h + e] = g[e];
+      }
+    if (H8) {
+      const f32x4_t g = *reinterpret_cast<const f32x4_t*>(p + 512 * NV + 4 * lane);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[8 * NV + e] = g[e];
+    }
+  }
+  static __device__ __forceinline__ void store_f32(float* p, int lane, const float (&f)[EP]) {
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        *reinterpret_cast<f32x4_t*>(p + 512 * c + 8 * lane + 4 * h) =
+            f32x4_t{f[8 * c + 4 * h], f[8 * c + 4 * h + 1], f[8 * c + 4 * h + 2], f[8 * c + 4 * h + 3]};
+    if (H8) *reinterpret_cast<f32x4_t*>(p + 512 * NV + 4 * lane) = f32x4_t{f[8 * NV], f[8 * NV + 1], f[8 * NV + 2], f[8 * NV + 3]};
+  }
+};
+
+// Round 3: the forward in the lane form of ln_bwd_lane_kernel below (columns as LaneCols deals them; gamma / beta in registers
+// instead of 6 KB of L2 reads per row; a workgroup's waves walk strided rows with the next row's load in flight).
 template <int NV, int H8>
 __global__ __launch_bounds__(256)
 void ln_fwd_lane_kernel(const LnArgs a) {
-  constexpr int EP = 8 * NV + 4 * H8, d = 512 * NV + 256 * H8;
+  using LC = LaneCols<NV, H8>;
+  constexpr int EP = LC::EP, d = LC::D;
   int pi = 0;
   while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
   const mmf_ln_problem& P = a.p[pi];
@@ -110,44 +169,18 @@ void ln_fwd_lane_kernel(const LnArgs a) {
   const int nblk = a.blk_start[pi + 1] - a.blk_start[pi];
   const float inv_d = 1.f / (float)d;
   float gam[EP], bet[EP];
-#pragma unroll
-  for (int c = 0; c < NV; ++c)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const f32x4_t g = *reinterpret_cast<const f32x4_t*>(P.gamma + 512 * c + 8 * lane + 4 * h);
-      const f32x4_t b = *reinterpret_cast<const f32x4_t*>(P.beta + 512 * c + 8 * lane + 4 * h);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { gam[8 * c + 4 * h + e] = g[e]; bet[8 * c + 4 * h + e] = b[e]; }
-    }
-  if (H8) {
-    const f32x4_t g = *reinterpret_cast<const f32x4_t*>(P.gamma + 512 * NV + 4 * lane);
-    const f32x4_t b = *reinterpret_cast<const f32x4_t*>(P.beta + 512 * NV + 4 * lane);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gam[8 * NV + e] = g[e]; bet[8 * NV + e] = b[e]; }
-  }
-  struct Row { u32x4_t x[NV > 0 ? NV : 1]; u32x2_t x8; };
-  auto fetch = [&](int row, Row& r) {
-    const unsigned short* x = static_cast<const unsigned short*>(P.x) + (size_t)row * d;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) r.x[c] = *reinterpret_cast<const u32x4_t*>(x + 512 * c + 8 * lane);
-    if (H8) r.x8 = *reinterpret_cast<const u32x2_t*>(x + 512 * NV + 4 * lane);
-  };
+  LC::load_f32(P.gamma, lane, gam);
+  LC::load_f32(P.beta, lane, bet);
+  auto fetch = [&](int row, typename LC::Bf16& r) { LC::load(static_cast<const unsigned short*>(P.x) + (size_t)row * d, lane, r); };
   const int step = nblk * ROWS_PER_BLOCK;
   int row = ((int)blockIdx.x - a.blk_start[pi]) * ROWS_PER_BLOCK + wave;
-  Row cur, nxt;
+  typename LC::Bf16 cur, nxt;
   if (row < P.rows) fetch(row, cur);
   for (; row < P.rows; row += step) {
     const bool more = row + step < P.rows;
     if (more) fetch(row + step, nxt);
     float v[EP];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      float t[8];
-      unpack8(cur.x[c], t);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[8 * c + e] = t[e];
-    }
-    if (H8) { v[8 * NV] = bf16lo(cur.x8[0]); v[8 * NV + 1] = bf16hi(cur.x8[0]); v[8 * NV + 2] = bf16lo(cur.x8[1]); v[8 * NV + 3] = bf16hi(cur.x8[1]); }
+    LC::unpack(cur, v);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < EP; ++e) s += v[e];
@@ -156,20 +189,10 @@ void ln_fwd_lane_kernel(const LnArgs a) {
 #pragma unroll
     for (int e = 0; e < EP; ++e) { v[e] -= mean; q += v[e] * v[e]; }
     const float rstd = rsqrtf(wave_sum(q) * inv_d + a.eps);
-    unsigned short* y = static_cast<unsigned short*>(P.y) + (size_t)row * d;
     float o[EP];
 #pragma unroll
     for (int e = 0; e < EP; ++e) o[e] = v[e] * rstd * gam[e] + bet[e];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      const u32x4_t w = {pack_bf16x2(o[8 * c], o[8 * c + 1]), pack_bf16x2(o[8 * c + 2], o[8 * c + 3]),
-                         pack_bf16x2(o[8 * c + 4], o[8 * c + 5]), pack_bf16x2(o[8 * c + 6], o[8 * c + 7])};
-      *reinterpret_cast<u32x4_t*>(y + 512 * c + 8 * lane) = w;
-    }
-    if (H8) {
-      const u32x2_t w = {pack_bf16x2(o[8 * NV], o[8 * NV + 1]), pack_bf16x2(o[8 * NV + 2], o[8 * NV + 3])};
-      *reinterpret_cast<u32x2_t*>(y + 512 * NV + 4 * lane) = w;
-    }
+    LC::store(static_cast<unsigned short*>(P.y) + (size_t)row * d, lane, o);
     if (lane == 0) { P.mean[row] = mean; P.rstd[row] = rstd; }
     if (more) cur = nxt;
   }
@@ -277,49 +300,29 @@ void ln_bwd_kernel(const LnArgs a) {
 // exists for lanes 0-31 (a quarter of the loads and of the arithmetic runs half empty), gamma is re-read from L2 for every
 // row (as many bytes as x and dy together), and a wave asks for a row only after it has reduced and stored the one before
 // (profiles/r03_layernorm.txt: 2.8 TB/s of algorithmic bytes for the three-problem launches, finalize included).  Here lane l
-// owns columns [8 l, 8 l + 8) of each 512-column block (16-byte loads) and [512 NV + 4 l, + 4) of the last 256 (8-byte
-// loads), gamma stays in registers, and the loads of the wave's next row are issued before the reductions of the current.
+// owns the columns LaneCols deals it, gamma stays in registers, and the loads of the wave's next row are issued before the
+// reductions of the current.
 template <int NV, int H8>
 __global__ __launch_bounds__(256)
 void ln_bwd_lane_kernel(const LnArgs a) {
-  constexpr int EP = 8 * NV + 4 * H8;                 // elements per lane
+  using LC = LaneCols<NV, H8>;
+  constexpr int EP = LC::EP, d = LC::D;               // elements per lane
   __shared__ float red[2][3][64 * EP];                // [dgamma|dbeta][waves 1..3][lane-major element]
   int pi = 0;
   while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
   const mmf_ln_problem& P = a.p[pi];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nblk = a.blk_start[pi + 1] - a.blk_start[pi];
-  constexpr int d = 512 * NV + 256 * H8;
   const float inv_d = 1.f / (float)d;
   float gam[EP], dg[EP], db[EP];
-#pragma unroll
-  for (int c = 0; c < NV; ++c) {
-    const f32x4_t g0 = *reinterpret_cast<const f32x4_t*>(P.gamma + 512 * c + 8 * lane);
-    const f32x4_t g1 = *reinterpret_cast<const f32x4_t*>(P.gamma + 512 * c + 8 * lane + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gam[8 * c + e] = g0[e]; gam[8 * c + 4 + e] = g1[e]; }
-  }
-  if (H8) {
-    const f32x4_t g0 = *reinterpret_cast<const f32x4_t*>(P.gamma + 512 * NV + 4 * lane);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) gam[8 * NV + e] = g0[e];
-  }
+  LC::load_f32(P.gamma, lane, gam);
 #pragma unroll
   for (int e = 0; e < EP; ++e) { dg[e] = 0.f; db[e] = 0.f; }
 
-  struct Row { u32x4_t x[NV > 0 ? NV : 1], y[NV > 0 ? NV : 1]; u32x2_t x8, y8; float mean, rstd; };
+  struct Row { typename LC::Bf16 x, dy; float mean, rstd; };
   auto fetch = [&](int row, Row& r) {
-    const unsigned short* x = static_cast<const unsigned short*>(P.x) + (size_t)row * d;
-    const unsigned short* dy = static_cast<const unsigned short*>(P.dy) + (size_t)row * d;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      r.x[c] = *reinterpret_cast<const u32x4_t*>(x + 512 * c + 8 * lane);
-      r.y[c] = *reinterpret_cast<const u32x4_t*>(dy + 512 * c + 8 * lane);
-    }
-    if (H8) {
-      r.x8 = *reinterpret_cast<const u32x2_t*>(x + 512 * NV + 4 * lane);
-      r.y8 = *reinterpret_cast<const u32x2_t*>(dy + 512 * NV + 4 * lane);
-    }
+    LC::load(static_cast<const unsigned short*>(P.x) + (size_t)row * d, lane, r.x);
+    LC::load(static_cast<const unsigned short*>(P.dy) + (size_t)row * d, lane, r.dy);
     r.mean = P.mean[row];
     r.rstd = P.rstd[row];
   };
@@ -331,20 +334,8 @@ void ln_bwd_lane_kernel(const LnArgs a) {
     const bool more = row + step < P.rows;
     if (more) fetch(row + step, nxt);                  // in flight under this row's reductions and store
     float xv[EP], dv[EP];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      float t[8];
-      unpack8(cur.x[c], t);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) xv[8 * c + e] = t[e];
-      unpack8(cur.y[c], t);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dv[8 * c + e] = t[e];
-    }
-    if (H8) {
-      xv[8 * NV + 0] = bf16lo(cur.x8[0]); xv[8 * NV + 1] = bf16hi(cur.x8[0]); xv[8 * NV + 2] = bf16lo(cur.x8[1]); xv[8 * NV + 3] = bf16hi(cur.x8[1]);
-      dv[8 * NV + 0] = bf16lo(cur.y8[0]); dv[8 * NV + 1] = bf16hi(cur.y8[0]); dv[8 * NV + 2] = bf16lo(cur.y8[1]); dv[8 * NV + 3] = bf16hi(cur.y8[1]);
-    }
+    LC::unpack(cur.x, xv);
+    LC::unpack(cur.dy, dv);
     const float mean = cur.mean, rstd = cur.rstd;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -358,20 +349,10 @@ void ln_bwd_lane_kernel(const LnArgs a) {
       dv[e] = g;
     }
     const float c1 = wave_sum(s1) * inv_d, c2 = wave_sum(s2) * inv_d;
-    unsigned short* dx = static_cast<unsigned short*>(P.dx) + (size_t)row * d;
     float o[EP];
 #pragma unroll
     for (int e = 0; e < EP; ++e) o[e] = rstd * (dv[e] - c1 - xv[e] * c2);
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      const u32x4_t w = {pack_bf16x2(o[8 * c], o[8 * c + 1]), pack_bf16x2(o[8 * c + 2], o[8 * c + 3]),
-                         pack_bf16x2(o[8 * c + 4], o[8 * c + 5]), pack_bf16x2(o[8 * c + 6], o[8 * c + 7])};
-      *reinterpret_cast<u32x4_t*>(dx + 512 * c + 8 * lane) = w;
-    }
-    if (H8) {
-      const u32x2_t w = {pack_bf16x2(o[8 * NV], o[8 * NV + 1]), pack_bf16x2(o[8 * NV + 2], o[8 * NV + 3])};
-      *reinterpret_cast<u32x2_t*>(dx + 512 * NV + 4 * lane) = w;
-    }
+    LC::store(static_cast<unsigned short*>(P.dx) + (size_t)row * d, lane, o);
     if (more) cur = nxt;
   }
   // combine the 4 waves' column sums; this workgroup's partials -> its workspace row (column order)
@@ -386,17 +367,8 @@ void ln_bwd_lane_kernel(const LnArgs a) {
     for (int e = 0; e < EP; ++e)
 #pragma unroll
       for (int w = 0; w < 3; ++w) { dg[e] += red[0][w][e * 64 + lane]; db[e] += red[1][w][e * 64 + lane]; }
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      *reinterpret_cast<f32x4_t*>(wsg + 512 * c + 8 * lane) = f32x4_t{dg[8 * c], dg[8 * c + 1], dg[8 * c + 2], dg[8 * c + 3]};
-      *reinterpret_cast<f32x4_t*>(wsg + 512 * c + 8 * lane + 4) = f32x4_t{dg[8 * c + 4], dg[8 * c + 5], dg[8 * c + 6], dg[8 * c + 7]};
-      *reinterpret_cast<f32x4_t*>(wsg + d + 512 * c + 8 * lane) = f32x4_t{db[8 * c], db[8 * c + 1], db[8 * c + 2], db[8 * c + 3]};
-      *reinterpret_cast<f32x4_t*>(wsg + d + 512 * c + 8 * lane + 4) = f32x4_t{db[8 * c + 4], db[8 * c + 5], db[8 * c + 6], db[8 * c + 7]};
-    }
-    if (H8) {
-      *reinterpret_cast<f32x4_t*>(wsg + 512 * NV + 4 * lane) = f32x4_t{dg[8 * NV], dg[8 * NV + 1], dg[8 * NV + 2], dg[8 * NV + 3]};
-      *reinterpret_cast<f32x4_t*>(wsg + d + 512 * NV + 4 * lane) = f32x4_t{db[8 * NV], db[8 * NV + 1], db[8 * NV + 2], db[8 * NV + 3]};
-    }
+    LC::store_f32(wsg, lane, dg);
+    LC::store_f32(wsg + d, lane, db);
   }
 }
 
@@ -436,12 +408,45 @@ void ln_bwd_finalize_kernel(const LnArgs a) {
 
 // the form and instantiation the calling thread's last forward / backward launch took (mmf_layernorm_last_form)
 thread_local int t_last_form = 0;
-constexpr int lane_form_id(int nv, int h8) { return 100 + 10 * nv + h8; }
+
+using LnKernel = void (*)(const LnArgs);
+// chunk form, by nch = ceil(d / 512); its form id is nch
+const LnKernel CHUNK_FWD[MAX_CH] = {ln_fwd_kernel<1>, ln_fwd_kernel<2>, ln_fwd_kernel<3>, ln_fwd_kernel<4>};
+const LnKernel CHUNK_BWD[MAX_CH] = {ln_bwd_kernel<1>, ln_bwd_kernel<2>, ln_bwd_kernel<3>, ln_bwd_kernel<4>};
+// lane form: the widths d = 512 NV + 256 H8 it is instantiated for
+struct LaneWidth { int d, form; LnKernel fwd, bwd; };   // form id: 100 + 10 NV + H8
+template <int NV, int H8>
+constexpr LaneWidth lane_width_of() {
+  return {LaneCols<NV, H8>::D, 100 + 10 * NV + H8, ln_fwd_lane_kernel<NV, H8>, ln_bwd_lane_kernel<NV, H8>};
+}
+const LaneWidth LANE_WIDTHS[] = {lane_width_of<0, 1>(), lane_width_of<1, 0>(), lane_width_of<1, 1>(), lane_width_of<2, 0>()};
+const LaneWidth* lane_width(int d) {                   // null: d is no lane width
+  for (const LaneWidth& w : LANE_WIDTHS) if (w.d == d) return &w;
+  return nullptr;
+}
 
 int check_common(const char* who, const mmf_ln_problem* p, int n, int d) {
   if (!p || n <= 0 || n > MMF_LN_MAX_PROBLEMS) MMF_FAIL(MMF_E_SHAPE, "%s: num_problems=%d out of range", who, n);
   if (d <= 0 || (d & 7) || d > MAX_CH * 512) MMF_FAIL(MMF_E_SHAPE, "%s: d=%d must be a multiple of 8, <= 2048", who, d);
   return MMF_OK;
+}
+
+int full_blocks(int rows) { return (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK; }
+
+// A budget of workgroups shared out over the problems in proportion to their rows: at least one each, at most one per
+// ROWS_PER_BLOCK rows (so at most budget + num_problems in all).  Fills a.blk_start and returns the total.
+int share_blocks(LnArgs& a, const mmf_ln_problem* problems, int num_problems, int budget) {
+  long long total_rows = 0;
+  for (int i = 0; i < num_problems; ++i) total_rows += problems[i].rows;
+  int total = 0;
+  for (int i = 0; i < num_problems; ++i) {
+    const int rows = problems[i].rows, full = full_blocks(rows);
+    const int nb = (int)(((long long)rows * budget + total_rows - 1) / total_rows);
+    a.blk_start[i] = total;
+    total += nb > full ? full : (nb < 1 ? 1 : nb);
+  }
+  a.blk_start[num_problems] = total;
+  return total;
 }
 
 }  // namespace
@@ -452,7 +457,8 @@ extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num
                                          float eps, void* stream) {
   if (int rc = check_common("mmf_layernorm_fwd_grouped", problems, num_problems, d)) return rc;
   LnArgs a; a.nprob = num_problems; a.d = d; a.eps = eps; a.ws = nullptr;
-  int total = 0;
+  int total = 0;                                       // one workgroup per ROWS_PER_BLOCK rows
+  long long total_rows = 0;
   for (int i = 0; i < num_problems; ++i) {
     const mmf_ln_problem& p = problems[i];
     if (p.rows <= 0 || !p.x || !p.y || !p.gamma || !p.beta || !p.mean || !p.rstd)
@@ -460,51 +466,32 @@ extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num
     if (!mmf_aligned16(p.x) || !mmf_aligned16(p.y) || !mmf_aligned16(p.gamma) || !mmf_aligned16(p.beta))
       MMF_FAIL(MMF_E_ALIGN, "mmf_layernorm_fwd_grouped[%d]: pointers must be 16-byte aligned", i);
     a.blk_start[i] = total;
-    total += (p.rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+    total += full_blocks(p.rows);
+    total_rows += p.rows;
     a.p[i] = p;
   }
   a.blk_start[num_problems] = total;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  static const int fwd_lane = [] { const char* e = getenv("MMF_LN_FWD_LANE"); return e ? atoi(e) : 1; }();
-  static const int fwd_blocks_env = [] { const char* e = getenv("MMF_LN_FWD_BLOCKS"); return e ? atoi(e) : 0; }();
-  long long total_rows = 0;
-  for (int i = 0; i < num_problems; ++i) total_rows += problems[i].rows;
-  // (round 3, same box, chunk form / lane form: three problems of 15,072 rows 13.0 / 9.6 us with 1024 workgroups; all six,
-  // 30,144 rows, 20.7 / 16.4 us with 2048 — profiles/r03_layernorm.txt)
-  const int fwd_blocks = fwd_blocks_env > 0 ? fwd_blocks_env : (total_rows > 20000 ? 2048 : 1024);
-  if (fwd_lane && (d == 768 || d == 512 || d == 256 || d == 1024) && total > fwd_blocks) {
-    // lane form: a bounded number of workgroups shared out over the problems in proportion to their rows
-    int t2 = 0;
-    for (int i = 0; i < num_problems; ++i) {
-      const int rows = problems[i].rows, full = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-      int nb = (int)(((long long)rows * fwd_blocks + total_rows - 1) / total_rows);
-      nb = nb > full ? full : (nb < 1 ? 1 : nb);
-      a.blk_start[i] = t2;
-      t2 += nb;
-    }
-    a.blk_start[num_problems] = t2;
-    if (d == 768)       hipLaunchKernelGGL((ln_fwd_lane_kernel<1, 1>), dim3(t2), dim3(256), 0, s, a);
-    else if (d == 512)  hipLaunchKernelGGL((ln_fwd_lane_kernel<1, 0>), dim3(t2), dim3(256), 0, s, a);
-    else if (d == 256)  hipLaunchKernelGGL((ln_fwd_lane_kernel<0, 1>), dim3(t2), dim3(256), 0, s, a);
-    else                hipLaunchKernelGGL((ln_fwd_lane_kernel<2, 0>), dim3(t2), dim3(256), 0, s, a);
-    t_last_form = lane_form_id(d / 512, (d / 256) & 1);
+  // lane form where one workgroup per ROWS_PER_BLOCK rows would be more than the budget: a bounded number of workgroups walking
+  // strided rows; else (any other width, or a small launch) the chunk form
+  const int budget = total_rows > FWD_LARGE_ROWS ? FWD_BLOCKS_LARGE : FWD_BLOCKS;
+  const LaneWidth* lw = lane_width(d);
+  if (lw && total > budget) {
+    total = share_blocks(a, problems, num_problems, budget);
+    hipLaunchKernelGGL(lw->fwd, dim3(total), dim3(256), 0, s, a);
+    t_last_form = lw->form;
     MMF_CHECK_LAUNCH("mmf_layernorm_fwd_grouped(lane)");
     return MMF_OK;
   }
   const int nch = (d + 511) / 512;
-  switch (nch) {
-    case 1: hipLaunchKernelGGL(ln_fwd_kernel<1>, dim3(total), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(ln_fwd_kernel<2>, dim3(total), dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(ln_fwd_kernel<3>, dim3(total), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(ln_fwd_kernel<4>, dim3(total), dim3(256), 0, s, a); break;
-  }
+  hipLaunchKernelGGL(CHUNK_FWD[nch - 1], dim3(total), dim3(256), 0, s, a);
   t_last_form = nch;
   MMF_CHECK_LAUNCH("mmf_layernorm_fwd_grouped");
   return MMF_OK;
 }
 
 extern "C" size_t mmf_layernorm_bwd_workspace_bytes(int d) {
-  return (size_t)(BWD_BLOCK_BUDGET + MMF_LN_MAX_PROBLEMS) * 2 * (size_t)(d > 0 ? d : 0) * sizeof(float);
+  return (size_t)(BWD_BLOCKS_CHUNK + MMF_LN_MAX_PROBLEMS) * 2 * (size_t)(d > 0 ? d : 0) * sizeof(float);
 }
 
 extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num_problems, int d,
@@ -514,8 +501,6 @@ extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num
     MMF_FAIL(MMF_E_SHAPE, "mmf_layernorm_bwd_grouped: workspace of %zu bytes (16-byte aligned) required",
              mmf_layernorm_bwd_workspace_bytes(d));
   LnArgs a; a.nprob = num_problems; a.d = d; a.eps = 0.f; a.ws = static_cast<float*>(workspace);
-  int total = 0;
-  long long total_rows = 0;
   for (int i = 0; i < num_problems; ++i) {
     const mmf_ln_problem& p = problems[i];
     if (p.rows <= 0 || !p.x || !p.dy || !p.dx || !p.gamma || !p.mean || !p.rstd || !p.dgamma || !p.dbeta)
@@ -523,45 +508,16 @@ extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num
     if (!mmf_aligned16(p.x) || !mmf_aligned16(p.dy) || !mmf_aligned16(p.dx) || !mmf_aligned16(p.gamma))
       MMF_FAIL(MMF_E_ALIGN, "mmf_layernorm_bwd_grouped[%d]: pointers must be 16-byte aligned", i);
     a.p[i] = p;
-    total_rows += p.rows;
   }
-  // Workgroups are shared out over the problems in proportion to their rows (~2 per CU in total);
-  // each leaves one row of column partials in the workspace (same-row float atomics would run ~14x
-  // below the streaming rate: MI355X_MICROARCH.md, Global float atomics), summed by the finalize pass.
-  static const int lane_form = [] { const char* e = getenv("MMF_LN_BWD_LANE"); return e ? atoi(e) : 1; }();
-  const bool use_lane = lane_form && (d == 768 || d == 512 || d == 256 || d == 1024);
-  const int budget = bwd_blocks(use_lane);
-  for (int i = 0; i < num_problems; ++i) {
-    const int rows = problems[i].rows;
-    int nb = (int)(((long long)rows * budget + total_rows - 1) / total_rows);
-    const int full = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    if (nb > full) nb = full;
-    if (nb < 1) nb = 1;
-    a.blk_start[i] = total;
-    total += nb;
-  }
-  a.blk_start[num_problems] = total;
+  // Each workgroup leaves one row of column partials in the workspace (same-row float atomics would run ~14x below the
+  // streaming rate: MI355X_MICROARCH.md, Global float atomics), summed by the finalize pass.
+  const LaneWidth* lw = lane_width(d);
+  const int total = share_blocks(a, problems, num_problems, lw ? BWD_BLOCKS_LANE : BWD_BLOCKS_CHUNK);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nch = (d + 511) / 512;
-  if (use_lane) {
-    if (d == 768)       hipLaunchKernelGGL((ln_bwd_lane_kernel<1, 1>), dim3(total), dim3(256), 0, s, a);
-    else if (d == 512)  hipLaunchKernelGGL((ln_bwd_lane_kernel<1, 0>), dim3(total), dim3(256), 0, s, a);
-    else if (d == 256)  hipLaunchKernelGGL((ln_bwd_lane_kernel<0, 1>), dim3(total), dim3(256), 0, s, a);
-    else                hipLaunchKernelGGL((ln_bwd_lane_kernel<2, 0>), dim3(total), dim3(256), 0, s, a);
-    t_last_form = lane_form_id(d / 512, (d / 256) & 1);
-    MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(lane)");
-    hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((d + 255) / 256, num_problems, FIN_SLICES), dim3(256), 0, s, a);
-    MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(finalize)");
-    return MMF_OK;
-  }
-  switch (nch) {
-    case 1: hipLaunchKernelGGL(ln_bwd_kernel<1>, dim3(total), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(ln_bwd_kernel<2>, dim3(total), dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(ln_bwd_kernel<3>, dim3(total), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(total), dim3(256), 0, s, a); break;
-  }
-  t_last_form = nch;
-  MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped");
+  hipLaunchKernelGGL(lw ? lw->bwd : CHUNK_BWD[nch - 1], dim3(total), dim3(256), 0, s, a);
+  t_last_form = lw ? lw->form : nch;
+  MMF_CHECK_LAUNCH(lw ? "mmf_layernorm_bwd_grouped(lane)" : "mmf_layernorm_bwd_grouped");
   hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((d + 255) / 256, num_problems, FIN_SLICES), dim3(256), 0, s, a);
   MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(finalize)");
   return MMF_OK;

@@ -11,31 +11,17 @@ namespace {
 
 constexpr int OPT_THREADS = 256;
 
-#ifndef MMF_OPT_UNROLL
-#define MMF_OPT_UNROLL 2          // 16-byte vectors per thread and stream in flight per iteration
-#endif
-#ifndef MMF_OPT_NT
-#define MMF_OPT_NT 1              // non-temporal loads / stores for what the step touches once (masters, moments, gradients)
-#endif
-template <typename T> __device__ __forceinline__ T ld_stream(const T* p) {
-#if MMF_OPT_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-template <typename T> __device__ __forceinline__ void st_stream(T* p, const T& v) {
-#if MMF_OPT_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+constexpr int OPT_UNROLL = 2;     // 16-byte vectors per thread and stream in flight per iteration
+constexpr int OPT_GRID = 2048;    // workgroups of the streaming kernels (8 per CU)
+
+// non-temporal loads / stores for what the step touches once (masters, moments, gradients)
+template <typename T> __device__ __forceinline__ T ld_stream(const T* p) { return __builtin_nontemporal_load(p); }
+template <typename T> __device__ __forceinline__ void st_stream(T* p, const T& v) { __builtin_nontemporal_store(v, p); }
 
 __global__ __launch_bounds__(OPT_THREADS)
 void sqnorm_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
   __shared__ float red[OPT_THREADS / 64];
-  constexpr int U = 2 * MMF_OPT_UNROLL;
+  constexpr int U = 2 * OPT_UNROLL;
   const int64_t nvec = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * OPT_THREADS;
   float s = 0.f;
@@ -85,7 +71,7 @@ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __r
       pp[e] = pp[e] * decay - step * mm[e] / (sqrtf(vv[e]) * rs2 + eps);
     }
   };
-  constexpr int U = MMF_OPT_UNROLL;
+  constexpr int U = OPT_UNROLL;
   int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x;
   for (; i + (U - 1) * stride < nvec; i += U * stride) {      // 4 U loads in flight per thread before the first use
     f32x4_t pp[U], gg[U], mm[U], vv[U];
@@ -167,12 +153,9 @@ __global__ void adamw_advance_kernel(long long* __restrict__ step, float* __rest
   hp[6] = (float)(1.0 - pow(b2, (double)t));
 }
 
-#ifndef MMF_OPT_GRID
-#define MMF_OPT_GRID 2048         // workgroups of the streaming kernels (8 per CU)
-#endif
 inline int opt_grid(int64_t n) {
   int64_t g = ((n >> 2) + OPT_THREADS - 1) / OPT_THREADS;
-  if (g > MMF_OPT_GRID) g = MMF_OPT_GRID;
+  if (g > OPT_GRID) g = OPT_GRID;
   return g < 1 ? 1 : (int)g;
 }
 

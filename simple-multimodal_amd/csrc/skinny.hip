@@ -13,7 +13,6 @@
 //                                                                 (ds_read_b64_tr_b16).
 // wgrad (dW = dy^T x, output-bound) stays on the grouped TN kernel via the deferred launch.
 #include "mmf_internal.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -375,9 +374,8 @@ thread_local int t_last_strip = 0;
 int launch_dgrad(SkinnyArgs& a, const mmf_skinny_problem* problems, int num_problems, int out_f32, void* stream) {
   int wide = 0;
   for (int i = 0; i < num_problems; ++i) wide += (problems[i].K + 63) / 64;
-  // strip width: 64 columns when that already gives the chip a workgroup per two CUs, else 32, else 16 (MMF_SKINNY_CT pins it)
-  static const int pin = [] { const char* e = getenv("MMF_SKINNY_CT"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 0; }();
-  const int ct = pin ? pin : wide >= 128 ? 4 : wide >= 48 ? 2 : 1;
+  // strip width: 64 columns when that already gives the chip a workgroup per two CUs, else 32, else 16
+  const int ct = wide >= 128 ? 4 : wide >= 48 ? 2 : 1;
   t_last_strip = ct;
   int total = 0;
   for (int i = 0; i < num_problems; ++i) { a.blk_start[i] = total; total += (problems[i].K + 16 * ct - 1) / (16 * ct); a.p[i] = problems[i]; }
