@@ -1,18 +1,13 @@
 // HBM-bound streaming helpers of the fusion path: casts, 3-way residual sum
 // (models/fusion_layers.py:156-158), mean over T (:166-168) and its backward, column sums (bias
-// gradients), relu backward.  All use 16-byte accesses per lane and grid-stride loops capped at
-// 2048 workgroups (guide: Guideline 11/13).
+// gradients), relu backward.  All use 16-byte accesses per lane and grid-stride loops on mmf_stream_grid's
+// grid (mmf_internal.h).  addn and the two meanpools keep the loop of the single and the grouped kernel in one
+// *_body function: the two kernels hand it their own operands and the workgroup's place (blk of nblk) in its launch or problem.
 #include "mmf_internal.h"
 
 namespace {
 
 constexpr int EW_THREADS = 256;
-inline int ew_grid(int64_t nvec) {
-  int64_t g = (nvec + EW_THREADS - 1) / EW_THREADS;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 // f32 -> bf16.  A lane converts 4 consecutive floats per access (16-B load, 8-B store): every load
 // wave-instruction covers 1 KiB contiguous (the first version gave each lane 8 consecutive floats = two 16-B loads
@@ -186,21 +181,22 @@ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, unsig
 }
 
 // mean over T: grid (B, ceil(d/128)); a workgroup owns 128 columns of one sample: 16 lanes x 8 columns
-// (one 256-byte segment per row), 16 row groups walk T, LDS combine.  B * d/128 workgroups (96 for
-// B=16, d=768) instead of B * d/512.
-__global__ __launch_bounds__(256)
-void meanpool_fwd_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
-                         int T, int d, int ldy) {
-  __shared__ float red[16][128 + 4];
+// (one 256-byte segment per row), RG row groups (16 RG threads) walk T, LDS combine.  B * d/128 workgroups (96 for
+// B=16, d=768) instead of B * d/512.  x is one (B, T, d) problem, y its first output column (row stride ldy).
+template <int RG>
+__device__ __forceinline__ void meanpool_fwd_body(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+                                                  int T, int d, int ldy) {
+  __shared__ float red[RG][128 + 4];
   const int b = blockIdx.x, cl = threadIdx.x & 15, rg = threadIdx.x >> 4;
   const int col = blockIdx.y * 128 + cl * 8;
   float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (col < d) {
     const unsigned short* p = x + (size_t)b * T * d + col;
-    for (int t = rg; t < T; t += 16) {
-      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(p + (size_t)t * d);
-      s[0] += bf16lo(w[0]); s[1] += bf16hi(w[0]); s[2] += bf16lo(w[1]); s[3] += bf16hi(w[1]);
-      s[4] += bf16lo(w[2]); s[5] += bf16hi(w[2]); s[6] += bf16lo(w[3]); s[7] += bf16hi(w[3]);
+    for (int t = rg; t < T; t += RG) {
+      float f[8];
+      unpack8(*reinterpret_cast<const u32x4_t*>(p + (size_t)t * d), f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] += f[e];
     }
   }
 #pragma unroll
@@ -211,20 +207,25 @@ void meanpool_fwd_kernel(const unsigned short* __restrict__ x, unsigned short* _
     if (c < d) {
       float t = 0.f;
 #pragma unroll
-      for (int g = 0; g < 16; ++g) t += red[g][threadIdx.x];
+      for (int g = 0; g < RG; ++g) t += red[g][threadIdx.x];
       y[(size_t)b * ldy + c] = f32_to_bf16_bits(t / (float)T);
     }
   }
 }
+__global__ __launch_bounds__(256)
+void meanpool_fwd_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+                         int T, int d, int ldy) {
+  meanpool_fwd_body<16>(x, y, T, d, ldy);
+}
 
-__global__ __launch_bounds__(EW_THREADS)
-void meanpool_bwd_kernel(const unsigned short* __restrict__ dy, unsigned short* __restrict__ dx,
-                         int B, int T, int d, int lddy) {
+// backward: dx[b][t][:] = dy[b][:] / T over workgroup blk's share; dy is the problem's first column (row stride lddy)
+__device__ __forceinline__ void meanpool_bwd_body(const unsigned short* __restrict__ dy, unsigned short* __restrict__ dx,
+                                                  int B, int T, int d, int lddy, int blk, int nblk) {
   const int dv = d >> 3;
   const int64_t nvec = (int64_t)B * T * dv;
   const float inv = 1.f / (float)T;
-  const int64_t stride = (int64_t)gridDim.x * EW_THREADS;
-  for (int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
+  const int64_t stride = (int64_t)nblk * EW_THREADS;
+  for (int64_t i = (int64_t)blk * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
     const int c = (int)(i % dv);
     const int b = (int)(i / ((int64_t)T * dv));
     const u32x4_t w = *reinterpret_cast<const u32x4_t*>(dy + (size_t)b * lddy + c * 8);
@@ -233,6 +234,11 @@ void meanpool_bwd_kernel(const unsigned short* __restrict__ dy, unsigned short* 
     for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(bf16lo(w[e]) * inv, bf16hi(w[e]) * inv);
     *reinterpret_cast<u32x4_t*>(dx + i * 8) = o;
   }
+}
+__global__ __launch_bounds__(EW_THREADS)
+void meanpool_bwd_kernel(const unsigned short* __restrict__ dy, unsigned short* __restrict__ dx,
+                         int B, int T, int d, int lddy) {
+  meanpool_bwd_body(dy, dx, B, T, d, lddy, blockIdx.x, gridDim.x);
 }
 
 // column sums (bias gradients), grouped: one launch covers several (x, out) problems.  A workgroup
@@ -248,8 +254,7 @@ struct ColsumArgs {
 __global__ __launch_bounds__(256)
 void colsum_kernel(const ColsumArgs a) {
   __shared__ float red[3][512];
-  int pi = 0;
-  while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
   const mmf_colsum_problem& P = a.p[pi];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ncc = (P.N + 511) / 512;
@@ -261,9 +266,10 @@ void colsum_kernel(const ColsumArgs a) {
   float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (col < P.N) {
     for (int r = r0 + wave; r < r1; r += 4) {
-      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(x + (size_t)r * P.ldx + col);
-      s[0] += bf16lo(w[0]); s[1] += bf16hi(w[0]); s[2] += bf16lo(w[1]); s[3] += bf16hi(w[1]);
-      s[4] += bf16lo(w[2]); s[5] += bf16hi(w[2]); s[6] += bf16lo(w[3]); s[7] += bf16hi(w[3]);
+      float f[8];
+      unpack8(*reinterpret_cast<const u32x4_t*>(x + (size_t)r * P.ldx + col), f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] += f[e];
     }
   }
   if (wave > 0) {
@@ -285,52 +291,14 @@ constexpr int POOL_THREADS = 1024, POOL_RG = POOL_THREADS / 16;   // 64 row grou
 // a MulT launch are one per CU, so the rows in flight per CU are what sets the rate (256 threads: 1.8 TB/s)
 __global__ __launch_bounds__(POOL_THREADS)
 void meanpool_cat_fwd_kernel(const PoolArgs a, unsigned short* __restrict__ y) {
-  __shared__ float red[POOL_RG][128 + 4];
-  const int i = blockIdx.z, T = a.T[i], d = a.d;
-  const int b = blockIdx.x, cl = threadIdx.x & 15, rg = threadIdx.x >> 4;
-  const int col = blockIdx.y * 128 + cl * 8;
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (col < d) {
-    const unsigned short* p = a.x[i] + (size_t)b * T * d + col;
-    for (int t = rg; t < T; t += POOL_RG) {
-      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(p + (size_t)t * d);
-      s[0] += bf16lo(w[0]); s[1] += bf16hi(w[0]); s[2] += bf16lo(w[1]); s[3] += bf16hi(w[1]);
-      s[4] += bf16lo(w[2]); s[5] += bf16hi(w[2]); s[6] += bf16lo(w[3]); s[7] += bf16hi(w[3]);
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[rg][cl * 8 + e] = s[e];
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int c = blockIdx.y * 128 + threadIdx.x;
-    if (c < d) {
-      float t = 0.f;
-#pragma unroll
-      for (int g = 0; g < POOL_RG; ++g) t += red[g][threadIdx.x];
-      y[(size_t)b * a.ld + i * d + c] = f32_to_bf16_bits(t / (float)T);
-    }
-  }
+  const int i = blockIdx.z;
+  meanpool_fwd_body<POOL_RG>(a.x[i], y + i * a.d, a.T[i], a.d, a.ld);
 }
 // backward: dx_i[b][t][:] = dy[b][i d : (i+1) d] / T_i
 __global__ __launch_bounds__(EW_THREADS)
 void meanpool_cat_bwd_kernel(const PoolArgs a, const unsigned short* __restrict__ dy) {
-  int i = 0;
-  while (i + 1 < a.n && (int)blockIdx.x >= a.blk_start[i + 1]) ++i;
-  const int T = a.T[i], d = a.d, dv = d >> 3;
-  const int64_t nvec = (int64_t)a.B * T * dv;
-  const float inv = 1.f / (float)T;
-  const int nb = a.blk_start[i + 1] - a.blk_start[i];
-  const int64_t stride = (int64_t)nb * EW_THREADS;
-  unsigned short* dx = a.g[i];
-  for (int64_t v = (int64_t)(blockIdx.x - a.blk_start[i]) * EW_THREADS + threadIdx.x; v < nvec; v += stride) {
-    const int c = (int)(v % dv);
-    const int b = (int)(v / ((int64_t)T * dv));
-    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(dy + (size_t)b * a.ld + i * d + c * 8);
-    u32x4_t o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(bf16lo(w[e]) * inv, bf16hi(w[e]) * inv);
-    *reinterpret_cast<u32x4_t*>(dx + v * 8) = o;
-  }
+  const int i = mmf_group_problem(a.blk_start, a.n, blockIdx.x);
+  meanpool_bwd_body(dy + i * a.d, a.g[i], a.B, a.T[i], a.d, a.ld, (int)blockIdx.x - a.blk_start[i], a.blk_start[i + 1] - a.blk_start[i]);
 }
 
 // row-strided f32 (rows x cols, ld_src floats between rows) -> contiguous bf16: the column blocks autograd hands back
@@ -374,7 +342,7 @@ void zero_ranges_kernel(const ZeroArgs a) {
 extern "C" int mmf_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
   if (n <= 0) return MMF_OK;
   EW_PTR_CHECK("mmf_cast_f32_to_bf16", src && dst && mmf_aligned16(src) && mmf_aligned16(dst));
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(ew_grid(n >> 4)), dim3(EW_THREADS), 0,
+  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(mmf_stream_grid(n >> 4, EW_THREADS)), dim3(EW_THREADS), 0,
                      static_cast<hipStream_t>(stream), src, static_cast<unsigned short*>(dst), n);
   MMF_CHECK_LAUNCH("mmf_cast_f32_to_bf16");
   return MMF_OK;
@@ -383,7 +351,7 @@ extern "C" int mmf_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void
 extern "C" int mmf_cast_bf16_to_f32_scaled(const void* src, float* dst, int64_t n, float scale, void* stream) {
   if (n <= 0) return MMF_OK;
   EW_PTR_CHECK("mmf_cast_bf16_to_f32", src && dst && mmf_aligned16(src) && mmf_aligned16(dst));
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(ew_grid(n >> 4)), dim3(EW_THREADS), 0,
+  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(mmf_stream_grid(n >> 4, EW_THREADS)), dim3(EW_THREADS), 0,
                      static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(src), dst, n, scale);
   MMF_CHECK_LAUNCH("mmf_cast_bf16_to_f32");
   return MMF_OK;
@@ -396,7 +364,7 @@ extern "C" int mmf_add3_bf16(const void* a, const void* b, const void* c, void* 
   if (n <= 0) return MMF_OK;
   EW_PTR_CHECK("mmf_add3_bf16", a && b && y && mmf_aligned16(a) && mmf_aligned16(b) && mmf_aligned16(y) &&
                (!c || mmf_aligned16(c)));
-  hipLaunchKernelGGL(add3_kernel, dim3(ew_grid(n >> 3)), dim3(EW_THREADS), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(add3_kernel, dim3(mmf_stream_grid(n >> 3, EW_THREADS)), dim3(EW_THREADS), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(b),
                      static_cast<const unsigned short*>(c), static_cast<unsigned short*>(y), n);
   MMF_CHECK_LAUNCH("mmf_add3_bf16");
@@ -415,7 +383,7 @@ extern "C" int mmf_add3_grouped(const mmf_add3_problem* problems, int num_proble
     EW_PTR_CHECK("mmf_add3_grouped", q.a && q.b && q.c && q.y && mmf_aligned16(q.a) && mmf_aligned16(q.b) &&
                  mmf_aligned16(q.c) && mmf_aligned16(q.y));
     a.blk_start[i] = total;
-    total += ew_grid(q.n >> 3);
+    total += mmf_stream_grid(q.n >> 3, EW_THREADS);
     a.p[i] = q;
   }
   a.blk_start[num_problems] = total;
@@ -427,22 +395,23 @@ extern "C" int mmf_add3_grouped(const mmf_add3_problem* problems, int num_proble
 // y = sum of n (2..MMF_ADDN_MAX) bf16 tensors, f32 accumulate, ONE pass: the gradient of a tensor used n times in
 // the forward (MulT's input rows feed two q-projections, two k/v-projections, two residuals and the three-way sum,
 // reference models/fusion_layers.py:146-158) instead of n - 1 pairwise adds.
-struct AddNArgs { int n; const unsigned short* x[MMF_ADDN_MAX]; };
+// The sum of the n bf16 tensors x[k] as bf16 (OUT_F32: f32) y, over workgroup blk's share of numel elements.
 template <bool OUT_F32>
-__global__ __launch_bounds__(EW_THREADS)
-void addn_kernel(const AddNArgs a, void* __restrict__ y, int64_t numel) {
+__device__ __forceinline__ void addn_body(const void* const (&x)[MMF_ADDN_MAX], int n, void* __restrict__ y, int64_t numel,
+                                          int blk, int nblk) {
   const int64_t nvec = numel >> 3;
-  const int64_t stride = (int64_t)gridDim.x * EW_THREADS;
-  for (int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
+  const int64_t stride = (int64_t)nblk * EW_THREADS;
+  for (int64_t i = (int64_t)blk * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 #pragma unroll
     for (int k = 0; k < MMF_ADDN_MAX; ++k) {
-      if (k < a.n) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(a.x[k] + i * 8);
+      if (k < n) {
+        float f[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(x[k]) + i * 8), f);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { acc[2 * e] += bf16lo(v[e]); acc[2 * e + 1] += bf16hi(v[e]); }
+        for (int e = 0; e < 8; ++e) acc[e] += f[e];
       }
     }
     if (OUT_F32) {
@@ -450,18 +419,23 @@ void addn_kernel(const AddNArgs a, void* __restrict__ y, int64_t numel) {
       *reinterpret_cast<f32x4_t*>(o) = f32x4_t{acc[0], acc[1], acc[2], acc[3]};
       *reinterpret_cast<f32x4_t*>(o + 4) = f32x4_t{acc[4], acc[5], acc[6], acc[7]};
     } else {
-      const u32x4_t o = {pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]), pack_bf16x2(acc[4], acc[5]), pack_bf16x2(acc[6], acc[7])};
-      *reinterpret_cast<u32x4_t*>(static_cast<unsigned short*>(y) + i * 8) = o;
+      *reinterpret_cast<u32x4_t*>(static_cast<unsigned short*>(y) + i * 8) = pack8(acc);
     }
   }
-  if (blockIdx.x == 0) {
+  if (blk == 0) {
     const int64_t t = (nvec << 3) + threadIdx.x;
     if (t < numel) {
       float s = 0.f;
-      for (int k = 0; k < a.n; ++k) s += bf16_bits_to_f32(a.x[k][t]);
+      for (int k = 0; k < n; ++k) s += bf16_bits_to_f32(static_cast<const unsigned short*>(x[k])[t]);
       if (OUT_F32) static_cast<float*>(y)[t] = s; else static_cast<unsigned short*>(y)[t] = f32_to_bf16_bits(s);
     }
   }
+}
+struct AddNArgs { int n; const void* x[MMF_ADDN_MAX]; };
+template <bool OUT_F32>
+__global__ __launch_bounds__(EW_THREADS)
+void addn_kernel(const AddNArgs a, void* __restrict__ y, int64_t numel) {
+  addn_body<OUT_F32>(a.x, a.n, y, numel, blockIdx.x, gridDim.x);
 }
 
 extern "C" int mmf_addn_bf16(const void* const* xs, int n, void* y, int64_t numel, int out_f32, void* stream) {
@@ -470,10 +444,10 @@ extern "C" int mmf_addn_bf16(const void* const* xs, int n, void* y, int64_t nume
   for (int k = 0; k < MMF_ADDN_MAX; ++k) a.x[k] = nullptr;
   for (int k = 0; k < n; ++k) {
     EW_PTR_CHECK("mmf_addn_bf16", xs[k] && mmf_aligned16(xs[k]));
-    a.x[k] = static_cast<const unsigned short*>(xs[k]);
+    a.x[k] = xs[k];
   }
   EW_PTR_CHECK("mmf_addn_bf16", mmf_aligned16(y));
-  const int grid = ew_grid(numel >> 3);
+  const int grid = mmf_stream_grid(numel >> 3, EW_THREADS);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (out_f32) hipLaunchKernelGGL(addn_kernel<true>, dim3(grid), dim3(EW_THREADS), 0, s, a, y, numel);
   else         hipLaunchKernelGGL(addn_kernel<false>, dim3(grid), dim3(EW_THREADS), 0, s, a, y, numel);
@@ -484,36 +458,9 @@ extern "C" int mmf_addn_bf16(const void* const* xs, int n, void* y, int64_t nume
 struct AddNGroupArgs { int nprob; int blk_start[MMF_ADDN_GROUP_MAX + 1]; mmf_addn_problem p[MMF_ADDN_GROUP_MAX]; };
 __global__ __launch_bounds__(EW_THREADS)
 void addn_grouped_kernel(const AddNGroupArgs a) {
-  int pi = 0;
-  while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
   const mmf_addn_problem& P = a.p[pi];
-  const int64_t nvec = P.numel >> 3;
-  const int blk = (int)blockIdx.x - a.blk_start[pi], nblk = a.blk_start[pi + 1] - a.blk_start[pi];
-  const int64_t stride = (int64_t)nblk * EW_THREADS;
-  unsigned short* y = static_cast<unsigned short*>(P.y);
-  for (int64_t i = (int64_t)blk * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int k = 0; k < MMF_ADDN_MAX; ++k) {
-      if (k < P.n) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(P.x[k]) + i * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { acc[2 * e] += bf16lo(v[e]); acc[2 * e + 1] += bf16hi(v[e]); }
-      }
-    }
-    const u32x4_t o = {pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]), pack_bf16x2(acc[4], acc[5]), pack_bf16x2(acc[6], acc[7])};
-    *reinterpret_cast<u32x4_t*>(y + i * 8) = o;
-  }
-  if (blk == 0) {
-    const int64_t t = (nvec << 3) + threadIdx.x;
-    if (t < P.numel) {
-      float s = 0.f;
-      for (int k = 0; k < P.n; ++k) s += bf16_bits_to_f32(static_cast<const unsigned short*>(P.x[k])[t]);
-      y[t] = f32_to_bf16_bits(s);
-    }
-  }
+  addn_body<false>(P.x, P.n, P.y, P.numel, (int)blockIdx.x - a.blk_start[pi], a.blk_start[pi + 1] - a.blk_start[pi]);
 }
 
 extern "C" int mmf_addn_grouped(const mmf_addn_problem* problems, int num_problems, void* stream) {
@@ -527,7 +474,7 @@ extern "C" int mmf_addn_grouped(const mmf_addn_problem* problems, int num_proble
     for (int k = 0; k < q.n; ++k) EW_PTR_CHECK("mmf_addn_grouped", q.x[k] && mmf_aligned16(q.x[k]));
     EW_PTR_CHECK("mmf_addn_grouped", q.y && mmf_aligned16(q.y));
     a.blk_start[i] = total;
-    total += ew_grid(q.numel >> 3);
+    total += mmf_stream_grid(q.numel >> 3, EW_THREADS);
     a.p[i] = q;
   }
   a.blk_start[num_problems] = total;
@@ -544,9 +491,9 @@ extern "C" int mmf_dropout(const void* x, void* y, int64_t n, int is_f32, float 
   const float scale = 1.f / (1.f - (float)thresh * (1.f / 4294967296.f));
   const unsigned long long* st = reinterpret_cast<const unsigned long long*>(rng_state);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (is_f32) hipLaunchKernelGGL(dropout_kernel<float>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, s,
+  if (is_f32) hipLaunchKernelGGL(dropout_kernel<float>, dim3(mmf_stream_grid(n, EW_THREADS)), dim3(EW_THREADS), 0, s,
                                  static_cast<const float*>(x), static_cast<float*>(y), n, thresh, scale, st, site);
-  else hipLaunchKernelGGL(dropout_kernel<unsigned short>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, s,
+  else hipLaunchKernelGGL(dropout_kernel<unsigned short>, dim3(mmf_stream_grid(n, EW_THREADS)), dim3(EW_THREADS), 0, s,
                           static_cast<const unsigned short*>(x), static_cast<unsigned short*>(y), n, thresh, scale, st, site);
   MMF_CHECK_LAUNCH("mmf_dropout");
   return MMF_OK;
@@ -572,7 +519,7 @@ extern "C" int mmf_relu_bwd_mixed(const void* dy, int dy_f32, const void* y, int
   if (!dy || !y || !dx) MMF_FAIL(MMF_E_SHAPE, "mmf_relu_bwd_mixed: null pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned short* o = static_cast<unsigned short*>(dx);
-  const dim3 grid(ew_grid(n)), block(EW_THREADS);
+  const dim3 grid(mmf_stream_grid(n, EW_THREADS)), block(EW_THREADS);
   if (dy_f32 && y_f32)       hipLaunchKernelGGL((relu_bwd_mixed_kernel<true, true>), grid, block, 0, s, dy, y, o, n);
   else if (dy_f32)           hipLaunchKernelGGL((relu_bwd_mixed_kernel<true, false>), grid, block, 0, s, dy, y, o, n);
   else if (y_f32)            hipLaunchKernelGGL((relu_bwd_mixed_kernel<false, true>), grid, block, 0, s, dy, y, o, n);
@@ -584,7 +531,7 @@ extern "C" int mmf_relu_bwd_mixed(const void* dy, int dy_f32, const void* y, int
 extern "C" int mmf_relu_bwd_bf16(const void* dy, const void* y, void* dx, int64_t n, void* stream) {
   if (n <= 0) return MMF_OK;
   if (!dy || !y || !dx) MMF_FAIL(MMF_E_SHAPE, "mmf_relu_bwd_bf16: null pointer");
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(n)), dim3(EW_THREADS), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(relu_bwd_kernel, dim3(mmf_stream_grid(n, EW_THREADS)), dim3(EW_THREADS), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(dy), static_cast<const unsigned short*>(y),
                      static_cast<unsigned short*>(dx), n);
   MMF_CHECK_LAUNCH("mmf_relu_bwd_bf16");
@@ -605,7 +552,7 @@ extern "C" int mmf_meanpool_bwd(const void* dy, void* dx, int B, int T, int d, i
   if (B <= 0 || T <= 0 || d <= 0 || (d & 7) || (lddy & 7) || lddy < d)
     MMF_FAIL(MMF_E_SHAPE, "mmf_meanpool_bwd: B=%d T=%d d=%d lddy=%d (d, lddy multiples of 8)", B, T, d, lddy);
   EW_PTR_CHECK("mmf_meanpool_bwd", dy && dx && mmf_aligned16(dy) && mmf_aligned16(dx));
-  hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(ew_grid((int64_t)B * T * (d >> 3))), dim3(EW_THREADS), 0,
+  hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(mmf_stream_grid((int64_t)B * T * (d >> 3), EW_THREADS)), dim3(EW_THREADS), 0,
                      static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(dy),
                      static_cast<unsigned short*>(dx), B, T, d, lddy);
   MMF_CHECK_LAUNCH("mmf_meanpool_bwd");
@@ -685,7 +632,7 @@ extern "C" int mmf_meanpool_cat_bwd(const void* dy, void* const* dxs, const int*
     if (!dxs[i] || Ts[i] <= 0 || !mmf_aligned16(dxs[i])) MMF_FAIL(MMF_E_SHAPE, "mmf_meanpool_cat_bwd[%d]: bad operand", i);
     a.g[i] = static_cast<unsigned short*>(dxs[i]); a.T[i] = Ts[i];
     a.blk_start[i] = total;
-    total += ew_grid((int64_t)B * Ts[i] * (d >> 3));
+    total += mmf_stream_grid((int64_t)B * Ts[i] * (d >> 3), EW_THREADS);
   }
   a.blk_start[n] = total;
   hipLaunchKernelGGL(meanpool_cat_bwd_kernel, dim3(total), dim3(EW_THREADS), 0, static_cast<hipStream_t>(stream), a,
@@ -698,7 +645,7 @@ extern "C" int mmf_cast_f32_to_bf16_2d(const float* src, void* dst, int rows, in
   if (rows <= 0 || cols <= 0) return MMF_OK;
   if (!src || !dst || (cols & 3) || (ld_src & 3) || ld_src < cols || !mmf_aligned16(src) || (reinterpret_cast<uintptr_t>(dst) & 7))
     MMF_FAIL(MMF_E_ALIGN, "mmf_cast_f32_to_bf16_2d: rows=%d cols=%d ld=%d (cols, ld multiples of 4; 16-byte aligned source)", rows, cols, ld_src);
-  hipLaunchKernelGGL(cast_f32_bf16_2d_kernel, dim3(ew_grid((int64_t)rows * (cols >> 2) / 4 + 1)), dim3(EW_THREADS), 0,
+  hipLaunchKernelGGL(cast_f32_bf16_2d_kernel, dim3(mmf_stream_grid((int64_t)rows * (cols >> 2) / 4 + 1, EW_THREADS)), dim3(EW_THREADS), 0,
                      static_cast<hipStream_t>(stream), src, static_cast<unsigned short*>(dst), rows, cols, ld_src);
   MMF_CHECK_LAUNCH("mmf_cast_f32_to_bf16_2d");
   return MMF_OK;

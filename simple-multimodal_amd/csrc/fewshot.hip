@@ -15,7 +15,6 @@ constexpr int FS_MAXWAY = 64;                  // one wave holds a query's n_way
 constexpr int FS_MAXSHOT = 64;
 constexpr int FS_MAXQ = 1024;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, const float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 sum3(const float4 t, const float4 a, const float4 v) {
   return make_float4((t.x + a.x) + v.x, (t.y + a.y) + v.y, (t.z + a.z) + v.z, (t.w + a.w) + v.w);   // the reference's order

@@ -28,20 +28,10 @@ struct LnArgs {
   mmf_ln_problem p[MMF_LN_MAX_PROBLEMS];
 };
 
-__device__ __forceinline__ void unpack8(const u32x4_t& w, float (&f)[8]) {
-  f[0] = bf16lo(w[0]); f[1] = bf16hi(w[0]); f[2] = bf16lo(w[1]); f[3] = bf16hi(w[1]);
-  f[4] = bf16lo(w[2]); f[5] = bf16hi(w[2]); f[6] = bf16lo(w[3]); f[7] = bf16hi(w[3]);
-}
-__device__ __forceinline__ u32x4_t pack8(const float (&f)[8]) {
-  return u32x4_t{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]),
-                 pack_bf16x2(f[6], f[7])};
-}
-
 template <int NCH>
 __global__ __launch_bounds__(256)
 void ln_fwd_kernel(const LnArgs a) {
-  int pi = 0;
-  while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
   const mmf_ln_problem& P = a.p[pi];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = ((int)blockIdx.x - a.blk_start[pi]) * ROWS_PER_BLOCK + wave;
@@ -162,8 +152,7 @@ __global__ __launch_bounds__(256)
 void ln_fwd_lane_kernel(const LnArgs a) {
   using LC = LaneCols<NV, H8>;
   constexpr int EP = LC::EP, d = LC::D;
-  int pi = 0;
-  while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
   const mmf_ln_problem& P = a.p[pi];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nblk = a.blk_start[pi + 1] - a.blk_start[pi];
@@ -205,8 +194,7 @@ template <int NCH>
 __global__ __launch_bounds__(256)
 void ln_bwd_kernel(const LnArgs a) {
   __shared__ float red[2][3][NCH * 512];          // [dgamma|dbeta][waves 1..3][column]
-  int pi = 0;
-  while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
   const mmf_ln_problem& P = a.p[pi];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nblk = a.blk_start[pi + 1] - a.blk_start[pi];
@@ -308,8 +296,7 @@ void ln_bwd_lane_kernel(const LnArgs a) {
   using LC = LaneCols<NV, H8>;
   constexpr int EP = LC::EP, d = LC::D;               // elements per lane
   __shared__ float red[2][3][64 * EP];                // [dgamma|dbeta][waves 1..3][lane-major element]
-  int pi = 0;
-  while (pi + 1 < a.nprob && (int)blockIdx.x >= a.blk_start[pi + 1]) ++pi;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
   const mmf_ln_problem& P = a.p[pi];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nblk = a.blk_start[pi + 1] - a.blk_start[pi];

@@ -275,16 +275,13 @@ void swap01_kernel(const void* __restrict__ in, void* __restrict__ out, int n0, 
       const f32x4_t b = *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(in) + src + 4);
       v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
     } else {
-      const u32x4_t x = *reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(in) + src);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo(x[e]); v[2 * e + 1] = bf16hi(x[e]); }
+      unpack8(*reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(in) + src), v);
     }
     if (OUT_F32) {
       *reinterpret_cast<f32x4_t*>(static_cast<float*>(out) + dst) = f32x4_t{v[0], v[1], v[2], v[3]};
       *reinterpret_cast<f32x4_t*>(static_cast<float*>(out) + dst + 4) = f32x4_t{v[4], v[5], v[6], v[7]};
     } else {
-      const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-      *reinterpret_cast<u32x4_t*>(static_cast<unsigned short*>(out) + dst) = o;
+      *reinterpret_cast<u32x4_t*>(static_cast<unsigned short*>(out) + dst) = pack8(v);
     }
   }
 }

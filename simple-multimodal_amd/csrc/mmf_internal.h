@@ -45,6 +45,40 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
+// eight bf16 (one 16-byte access) <-> eight f32: element 2 i is the low half of word i.  pack8 also takes the f32 side as two halves.
+__device__ __forceinline__ void unpack8(const u32x4_t& w, float (&f)[8]) {
+  f[0] = bf16lo(w[0]); f[1] = bf16hi(w[0]); f[2] = bf16lo(w[1]); f[3] = bf16hi(w[1]);
+  f[4] = bf16lo(w[2]); f[5] = bf16hi(w[2]); f[6] = bf16lo(w[3]); f[7] = bf16hi(w[3]);
+}
+__device__ __forceinline__ u32x4_t pack8(const float (&f)[8]) {
+  return u32x4_t{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]),
+                 pack_bf16x2(f[6], f[7])};
+}
+__device__ __forceinline__ u32x4_t pack8(const f32x4_t a, const f32x4_t b) {
+  return u32x4_t{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
+}
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }   // exact GELU
+
+// ---- streaming launches -----------------------------------------------------------------------
+// Grid of a grid-stride streaming kernel over nvec per-lane accesses: one workgroup per `threads` of them, 1 .. 2048
+// (cdna_hip_programming.md Guideline 11/13: enough workgroups to fill the chip, the loop takes the rest).
+static inline int mmf_stream_grid(int64_t nvec, int threads) {
+  int64_t g = (nvec + threads - 1) / threads;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+// Grouped launch: problem i owns workgroups [blk_start[i], blk_start[i + 1]) and blk_start[n] is the grid.  The problem
+// of workgroup `bid`, wave-uniform (n is a few dozen at most and blk_start sits in the kernel arguments: a scalar scan).
+template <int N>
+__device__ __forceinline__ int mmf_group_problem(const int (&blk_start)[N], int n, int bid) {
+  int pi = 0;
+  while (pi + 1 < n && bid >= blk_start[pi + 1]) ++pi;
+  return pi;
+}
+
 // ---- wave reductions ------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -684,7 +684,6 @@ struct RobustArgs {
   int B, d, C, avail;
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float dot4(const float4 x, const float4 w) { return x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w; }
 
 __global__ __launch_bounds__(SM_THREADS)

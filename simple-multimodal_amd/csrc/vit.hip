@@ -1,22 +1,12 @@
 // The pieces a ViT forward has and the fusion path did not (mmfusion/vit.py): patch extraction for the patch-embedding
 // GEMM, CLS / position tokens, exact (erf) GELU.  All three are HBM-bound streaming kernels: one 16-byte bf16 access
-// (8 elements) per lane on the bf16 side, two 16-byte accesses on the f32 side, grid-stride loops capped at 2048
-// workgroups per grid row like elementwise.hip's.
+// (8 elements) per lane on the bf16 side, two 16-byte accesses on the f32 side, grid-stride loops on mmf_stream_grid's
+// grid (mmf_internal.h) per grid row.
 #include "mmf_internal.h"
 
 namespace {
 
 constexpr int VIT_THREADS = 256;
-inline int vit_grid(int64_t nvec) {
-  int64_t g = (nvec + VIT_THREADS - 1) / VIT_THREADS;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-__device__ __forceinline__ u32x4_t pack8(const f32x4_t a, const f32x4_t b) {
-  return u32x4_t{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
-}
 
 // (N, C, H, W) f32 -> (N * gh * gw, C * P * P) bf16, column (c, py, px).  blockIdx.y = image; inside an image the lanes
 // walk the OUTPUT in order (every wave store covers 1 KiB contiguous); a lane's 8 output columns are 8 consecutive px of
@@ -67,8 +57,6 @@ void vit_embed_tokens_kernel(const unsigned short* __restrict__ pe, const float*
   }
 }
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
 // x <- gelu(x + bias) in place, rows x cols with row stride ld.  nvec = rows * cols / 8 < 2^31 (the host splits longer inputs).
 template <bool HAS_BIAS>
 __global__ __launch_bounds__(VIT_THREADS)
@@ -103,7 +91,7 @@ extern "C" int mmf_vit_patchify(const float* pixels, void* patches_bf16, int N, 
   const int64_t per_image = (int64_t)C * H * W / 8;                   // = gh * gw * C * P * P / 8 output vectors
   if (per_image >= (int64_t)1 << 31) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_patchify: image of %lld elements", (long long)per_image * 8);
   const unsigned kv = (unsigned)((int64_t)C * P * P / 8);
-  hipLaunchKernelGGL(vit_patchify_kernel, dim3(vit_grid(per_image), N), dim3(VIT_THREADS), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(vit_patchify_kernel, dim3(mmf_stream_grid(per_image, VIT_THREADS), N), dim3(VIT_THREADS), 0, static_cast<hipStream_t>(stream),
                      pixels, static_cast<unsigned short*>(patches_bf16), C, H, W, P, W / P, kv, (unsigned)per_image);
   MMF_CHECK_LAUNCH("mmf_vit_patchify");
   return MMF_OK;
@@ -118,7 +106,7 @@ extern "C" int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_embed_tokens: N=%d (at most 65535), T*d=%lld (below 2^31)", N, (long long)T * d);
   if (!mmf_aligned16(patch_emb_bf16) || !mmf_aligned16(cls) || !mmf_aligned16(pos) || !mmf_aligned16(tokens_bf16))
     MMF_FAIL(MMF_E_ALIGN, "mmf_vit_embed_tokens: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_embed_tokens_kernel, dim3(vit_grid((int64_t)T * d / 8), N), dim3(VIT_THREADS), 0,
+  hipLaunchKernelGGL(vit_embed_tokens_kernel, dim3(mmf_stream_grid((int64_t)T * d / 8, VIT_THREADS), N), dim3(VIT_THREADS), 0,
                      static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(patch_emb_bf16), cls, pos,
                      static_cast<unsigned short*>(tokens_bf16), T, d);
   MMF_CHECK_LAUNCH("mmf_vit_embed_tokens");
@@ -138,8 +126,8 @@ extern "C" int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows,
   for (int64_t r0 = 0; r0 < rows; r0 += max_rows) {
     const int64_t nr = rows - r0 < max_rows ? rows - r0 : max_rows;
     const unsigned nvec = (unsigned)(nr * cv);
-    if (bias) hipLaunchKernelGGL(bias_gelu_kernel<true>, dim3(vit_grid(nvec)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
-    else      hipLaunchKernelGGL(bias_gelu_kernel<false>, dim3(vit_grid(nvec)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
+    if (bias) hipLaunchKernelGGL(bias_gelu_kernel<true>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
+    else      hipLaunchKernelGGL(bias_gelu_kernel<false>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
     MMF_CHECK_LAUNCH("mmf_bias_gelu_bf16");
   }
   return MMF_OK;

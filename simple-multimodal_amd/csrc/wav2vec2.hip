@@ -12,18 +12,6 @@ namespace {
 constexpr int W2V_THREADS = 256;
 constexpr int W2V_SLOTS = MMF_W2V_STATS_SLOTS;      // frame lanes per clip in the statistics pass
 
-inline int w2v_grid(int64_t nvec) {
-  int64_t g = (nvec + W2V_THREADS - 1) / W2V_THREADS;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ u32x4_t pack8(const float* v) {
-  return u32x4_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-}
 
 // ---- layer 0 -------------------------------------------------------------------------------------------
 // A thread owns 8 consecutive channels (their K0 taps stay in registers) and walks frames; the C0 / 8 threads of one frame
@@ -149,8 +137,8 @@ void w2v_gelu_window_kernel(const unsigned short* __restrict__ x, unsigned short
   for (unsigned v = blockIdx.x * W2V_THREADS + threadIdx.x; v < nvec; v += stride) {
     const unsigned t = v / rowv, r = v - t * rowv;
     const unsigned j = r / cv, c = (r - j * cv) << 3;
-    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(src + ((size_t)t * s + j) * C + c);
-    float a[8] = {bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1]), bf16lo(w[2]), bf16hi(w[2]), bf16lo(w[3]), bf16hi(w[3])};
+    float a[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(src + ((size_t)t * s + j) * C + c), a);
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = gelu_erf(a[e]);
     *reinterpret_cast<u32x4_t*>(dst + (size_t)v * 8) = pack8(a);
@@ -287,7 +275,7 @@ extern "C" int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, in
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_w2v_gelu_window: C=%d (multiple of 8), N=%d (at most 65535), %lld output elements per clip (below 2^34), "
              "out must not be x", C, N, (long long)nvec * 8);
   if (!mmf_aligned16(x_bf16) || !mmf_aligned16(out_bf16)) MMF_FAIL(MMF_E_ALIGN, "mmf_w2v_gelu_window: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(w2v_gelu_window_kernel, dim3(w2v_grid(nvec), N), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(w2v_gelu_window_kernel, dim3(mmf_stream_grid(nvec, W2V_THREADS), N), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(x_bf16), static_cast<unsigned short*>(out_bf16), T_in, C, k, s, (unsigned)(C / 8), (unsigned)nvec);
   MMF_CHECK_LAUNCH("mmf_w2v_gelu_window");
   return MMF_OK;

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Streaming-kernel microbench: f32->bf16 cast of the MulT weight arena, LayerNorm fwd/bwd, add3, meanpool at the
-MulT shapes; prints achieved HBM GB/s of algorithmic bytes."""
-import os, sys
+MulT shapes, their grouped forms, the fan-out gradient sums and the bias-gradient column sums; prints achieved HBM GB/s of
+algorithmic bytes."""
+import ctypes as C, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "simple-multimodal_amd"))
 import torch
@@ -54,3 +55,33 @@ print(f"add3 8192x768: {us:7.1f} us  {4.0*8192*d*2/us/1e3:7.0f} GB/s")
 mp = [torch.randn(16, t, d, device="cuda").bfloat16() for t in (512, 400, 30)]
 us = timeit(lambda: ops.meanpool_cat(mp))
 print(f"meanpool_cat 16x(512,400,30)x768: {us:7.1f} us  {sum(m.numel() for m in mp)*2/us/1e3:7.0f} GB/s")
+trip = [tuple(torch.randn(r, d, device="cuda").bfloat16() for _ in range(3)) for r in (8192, 6400, 480)]
+us = timeit(lambda: ops.add3_group(trip))
+print(f"add3_group 8192/6400/480 x768: {us:7.1f} us  {4.0*15072*d*2/us/1e3:7.0f} GB/s")
+NG = 7                                                     # gradients per MulT input tensor (ops.fanout_group's backward)
+gr = [[torch.randn(r, d, device="cuda").bfloat16() for _ in range(NG)] for r in (8192, 6400, 480)]
+go = [torch.empty_like(g[0]) for g in gr]
+pr = (lib.AddNProblem * 3)()
+for q, g, o in zip(pr, gr, go):
+    for k, t in enumerate(g): q.x[k] = t.data_ptr()
+    q.y, q.numel, q.n = o.data_ptr(), o.numel(), NG
+us = timeit(lambda: lib.check(L.mmf_addn_grouped(pr, 3, lib.stream_ptr())))
+print(f"fanout_group bwd (addn_grouped) {NG} x 8192/6400/480 x768: {us:7.1f} us  {(NG+1.0)*15072*d*2/us/1e3:7.0f} GB/s")
+p1 = (C.c_void_p * NG)(*[t.data_ptr() for t in gr[0]])
+us = timeit(lambda: lib.check(L.mmf_addn_bf16(p1, NG, go[0].data_ptr(), go[0].numel(), 0, lib.stream_ptr())))
+print(f"fanout bwd (addn) {NG} x 8192x768: {us:7.1f} us  {(NG+1.0)*8192*d*2/us/1e3:7.0f} GB/s")
+cx = [torch.randn(m, n, device="cuda").bfloat16() for m, n in ((8192, 2304), (6400, 768), (480, 768))]
+co = [torch.zeros(x.shape[1], device="cuda") for x in cx]
+cp = [lib.ColsumProblem(x.data_ptr(), o.data_ptr(), x.shape[0], x.shape[1], x.shape[1]) for x, o in zip(cx, co)]
+us = timeit(lambda: lib.colsum_grouped(cp))
+print(f"colsum 8192x2304 + 6400x768 + 480x768: {us:7.1f} us  {sum(x.numel() for x in cx)*2/us/1e3:7.0f} GB/s")
+dyp = torch.randn(16, 3 * d, device="cuda").bfloat16()
+dxp = [torch.empty_like(m) for m in mp]
+pp, tp = (C.c_void_p * 3)(*[t.data_ptr() for t in dxp]), (C.c_int * 3)(512, 400, 30)
+us = timeit(lambda: lib.check(L.mmf_meanpool_cat_bwd(dyp.data_ptr(), pp, tp, 3, 16, d, 3 * d, lib.stream_ptr())))
+print(f"meanpool_cat bwd 16x(512,400,30)x768: {us:7.1f} us  {sum(m.numel() for m in mp)*2/us/1e3:7.0f} GB/s")
+y1 = torch.empty(16, d, device="cuda", dtype=torch.bfloat16)
+us = timeit(lambda: lib.check(L.mmf_meanpool_fwd(mp[0].data_ptr(), y1.data_ptr(), 16, 512, d, d, lib.stream_ptr())))
+print(f"meanpool fwd 16x512x768: {us:7.1f} us  {mp[0].numel()*2/us/1e3:7.0f} GB/s")
+us = timeit(lambda: lib.check(L.mmf_meanpool_bwd(y1.data_ptr(), dxp[0].data_ptr(), 16, 512, d, d, lib.stream_ptr())))
+print(f"meanpool bwd 16x512x768: {us:7.1f} us  {mp[0].numel()*2/us/1e3:7.0f} GB/s")
