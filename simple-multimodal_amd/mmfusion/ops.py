@@ -12,8 +12,11 @@ independent), which is what fills 256 CUs with these small per-block shapes.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
+import os
 from dataclasses import dataclass
+from itertools import accumulate
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -106,6 +109,32 @@ def _req(t: torch.Tensor, dtype) -> None:
         raise TypeError(f"expected {dtype}, got {t.dtype}")
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def _column_views(t: Optional[torch.Tensor], widths: Sequence[int]) -> list:
+    """t's adjacent column blocks of the given widths, from column 0 (a None per block for t = None)"""
+    offs = [0, *accumulate(widths)]
+    return [None if t is None else t[:, a:b] for a, b in zip(offs, offs[1:])]
+
+
+def _column_blocks(ts: Sequence[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The contiguous 2-D tensor that ``ts`` are views of and whose columns they tile — in order, from its first
+    element, without gap, overlap or rest (what ``_column_views`` returns); None for anything else.  Metadata only."""
+    base = ts[0]._base if len(ts) else None
+    if base is None or base.dim() != 2 or not base.is_contiguous():
+        return None
+    rows, width = base.shape
+    off = 0
+    for t in ts:
+        if (t._base is not base or t.dtype != base.dtype or t.dim() != 2 or t.shape[0] != rows
+                or t.stride() != (width, 1) or t.data_ptr() != base.data_ptr() + base.element_size() * off):
+            return None
+        off += t.shape[1]
+    return base if off == width else None
+
+
 # --------------------------------------------------------------------------------------------
 # raw (non-autograd) helpers
 # --------------------------------------------------------------------------------------------
@@ -132,6 +161,36 @@ def cast_to_f32(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _grad_bf16(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A bf16 or f32 gradient as contiguous bf16 (None stays None).  The cast comes first: it takes a row-strided f32
+    column block where it lies, in one launch, where ``.contiguous()`` ahead of it would add a copy."""
+    if g is None:
+        return None
+    return g.contiguous() if g.dtype == BF16 else cast_to_bf16(g)
+
+
+def _gemm_problems(layout: int, probs: Sequence[tuple], epilogue: int, dtype, c_dtype) -> List[GemmProblem]:
+    """One GemmProblem per (A, B, C, bias|None, aux|None): M, N from C, K from A.  A and B must be ``dtype``, every C
+    ``c_dtype``; the bias is f32, contiguous, [N] ([M] for the fused bias gradient); aux has C's shape."""
+    ps: List[GemmProblem] = []
+    for (A, Bm, Cm, bias, aux) in probs:
+        _req(A, dtype), _req(Bm, dtype)
+        M, N = Cm.shape
+        K = A.shape[0] if layout == GEMM_TN else A.shape[1]
+        a_shape, b_shape = (K, M) if layout == GEMM_TN else (M, K), (N, K) if layout == GEMM_NT else (K, N)
+        if A.shape != a_shape or Bm.shape != b_shape or Cm.dtype != c_dtype:
+            raise ValueError(f"gemm layout {layout}: A{tuple(A.shape)} B{tuple(Bm.shape)} C{tuple(Cm.shape)} {Cm.dtype}")
+        if aux is not None and tuple(aux.shape) != (M, N):
+            raise ValueError("aux must match C")
+        if bias is not None:
+            _req(bias, torch.float32)
+            if bias.numel() != (M if epilogue & EPI_COLSUM_A else N) or not bias.is_contiguous():
+                raise ValueError("bias must be contiguous [N] ([M] for the fused bias gradient)")
+        ps.append(GemmProblem(A.data_ptr(), Bm.data_ptr(), Cm.data_ptr(), _ptr(bias), _ptr(aux), M, N, K,
+                              _ld(A), _ld(Bm), _ld(Cm), _ld(aux) if aux is not None else 0))
+    return ps
+
+
 def gemm(layout: int, A: torch.Tensor, Bm: torch.Tensor, C: torch.Tensor, *, bias=None, aux=None,
          epilogue: int = 0) -> None:
     """Single-problem convenience over gemm_group (shapes are taken from C and the layout)."""
@@ -143,29 +202,7 @@ def gemm_group(layout: int, probs: Sequence[tuple], epilogue: int, alpha: float 
     """probs: (A, B, C, bias|None, aux|None) tensors; M,N from C; K from A.
     alpha scales the result after the mask step; dropout = (p, site) adds MMF_EPI_DROPOUT."""
     out_f32 = probs[0][2].dtype == torch.float32
-    ps: List[GemmProblem] = []
-    for (A, Bm, Cm, bias, aux) in probs:
-        _req(A, BF16), _req(Bm, BF16)
-        M, N = Cm.shape
-        K = A.shape[0] if layout == GEMM_TN else A.shape[1]
-        if layout == GEMM_NT:
-            ok = A.shape == (M, K) and Bm.shape == (N, K)
-        elif layout == GEMM_NN:
-            ok = A.shape == (M, K) and Bm.shape == (K, N)
-        else:
-            ok = A.shape == (K, M) and Bm.shape == (K, N)
-        if not ok or (Cm.dtype == torch.float32) != out_f32:
-            raise ValueError(f"gemm layout {layout}: A{tuple(A.shape)} B{tuple(Bm.shape)} C{tuple(Cm.shape)}")
-        if aux is not None and tuple(aux.shape) != (M, N):
-            raise ValueError("aux must match C")
-        if bias is not None:
-            _req(bias, torch.float32)
-            if bias.numel() != (M if epilogue & EPI_COLSUM_A else N) or not bias.is_contiguous():
-                raise ValueError("bias must be contiguous [N] ([M] for the fused bias gradient)")
-        ps.append(GemmProblem(A.data_ptr(), Bm.data_ptr(), Cm.data_ptr(),
-                              bias.data_ptr() if bias is not None else None,
-                              aux.data_ptr() if aux is not None else None,
-                              M, N, K, _ld(A), _ld(Bm), _ld(Cm), _ld(aux) if aux is not None else 0))
+    ps = _gemm_problems(layout, probs, epilogue, BF16, torch.float32 if out_f32 else BF16)
     if dropout is not None:
         if len(ps) > lib.GEMM_MAX_PROBLEMS:
             raise ValueError("a dropout GEMM group must fit one launch (the problem index keys the mask)")
@@ -274,8 +311,6 @@ def dropout(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
 #   automatic   issue everything on the current stream (what is left after the optional early launch, below);
 #   manual      park it for the caller (set_manual_wgrad_flush: bench.py's overlapped data-parallel step);
 #   round hook  hand it to a hook in rounds, the first ones during backward (set_wgrad_rounds: mmfusion.dp.BackwardExchange).
-import os as _os
-
 # Early flush (MMF_WGRAD_EARLY=1; measured +0.4 % and left OFF by default — with it the dominant kernel shares the chip with
 # the input-gradient sums, so its duration in a profile of the timed steps no longer equals its stand-alone duration, which
 # is what bench.py's roofline is built on): the number of weight-gradient problems a backward queues is the same every
@@ -287,7 +322,7 @@ import os as _os
 # A weight with requires_grad = False (few-shot training freezes everything but the adapters, the prompt and the prototype
 # network) queues nothing, its bias gradient included; the input gradient still flows through it.  Its arena gradient then
 # stays as zero_grad left it (lazy zeroing: ParamArena.finalize_grads clears it).
-_WGRAD_EARLY = _os.environ.get("MMF_WGRAD_EARLY", "0") == "1"
+_WGRAD_EARLY = os.environ.get("MMF_WGRAD_EARLY", "0") == "1"
 _pending_wgrad: List[tuple] = []
 _wgrad_stream: Optional[torch.cuda.Stream] = None
 
@@ -582,7 +617,6 @@ class LinearSpec:
     w: W
     b: Optional[W] = None          # bias parameter rows [r0, r1) (1-D parameter)
     relu: bool = False
-    has_residual: bool = False
 
 
 def _relu_mask(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -604,143 +638,117 @@ def _relu_mask(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return dz
 
 
+def _skinny(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, bias=None, aux=None) -> lib.SkinnyProblem:
+    """y (M, K or N) from x (M rows) and w (N, K): forward y = x w^T with x (M, K), input gradient y = x w with x (M, N)."""
+    return lib.SkinnyProblem(x.data_ptr(), w.data_ptr(), y.data_ptr(), _ptr(bias), _ptr(aux), x.shape[0], *w.shape,
+                             _ld(x), _ld(w), _ld(y), _ld(aux) if aux is not None else 0)
+
+
+def _flatten_items(items: Sequence[tuple], residual: bool = True) -> Tuple[list, list]:
+    """linear_group's (x, spec, residual|None) items -> (specs, [x_0, res_0|None, w_0.p, b_0.p|None, x_1, ...]) as the
+    Functions take them (without the residuals: three tensors per item)."""
+    specs, tensors = [], []
+    for x, spec, res in items:
+        specs.append(spec)
+        tensors += [x, *([res] if residual else []), spec.w.p, spec.b.p if spec.b is not None else None]
+    return specs, tensors
+
+
+def _one_epilogue(specs: Sequence[LinearSpec], ress: Sequence = ()) -> Tuple[bool, bool, bool]:
+    """(relu, has bias, has residual) of a linear group, which are one launch's epilogue and so the same for every problem"""
+    relu, has_bias, has_res = specs[0].relu, specs[0].b is not None, bool(ress) and ress[0] is not None
+    if (any(s.relu != relu or (s.b is not None) != has_bias for s in specs)
+            or any((r is not None) != has_res for r in ress)):
+        raise ValueError("a linear group must share one epilogue")
+    return relu, has_bias, has_res
+
+
+def _linear_outputs(xs: Sequence[torch.Tensor], ws: Sequence[torch.Tensor], dtype, cat: bool) -> Tuple[Optional[torch.Tensor], list]:
+    """(None, the (M_i, N_i) outputs of a linear group), or with ``cat`` (ONE (M, sum N_i) tensor, its column blocks as
+    the outputs): torch.cat / torch.stack of the outputs without a copy, and one gradient coming back instead of n slices."""
+    if not cat:
+        return None, [torch.empty((x.shape[0], w.shape[0]), dtype=dtype, device=x.device) for x, w in zip(xs, ws)]
+    if any(x.shape[0] != xs[0].shape[0] for x in xs):
+        raise ValueError("a concatenated linear group needs equal row counts")
+    widths = [w.shape[0] for w in ws]
+    base = torch.empty((xs[0].shape[0], sum(widths)), dtype=dtype, device=xs[0].device)
+    return base, _column_views(base, widths)
+
+
 class _GroupedLinear(torch.autograd.Function):
-    """tensors = [x_0, res_0|None, w_0.p, b_0.p|None, x_1, ...]; returns one output per spec."""
+    """tensors = [x_0, res_0|None, w_0.p, b_0.p|None, x_1, ...]; returns one output per spec, or with ``cat`` the one
+    tensor that holds them side by side (``_linear_outputs``)."""
 
     @staticmethod
-    def forward(ctx, specs: List[LinearSpec], out_f32, *tensors):
-        # out_f32 may be (out_f32, cat): with cat the outputs are the column blocks of ONE (M, sum N_i) tensor,
-        # which is returned instead of the list (torch.cat / torch.stack of the outputs without a copy, and one
-        # gradient tensor coming back instead of n slices)
-        cat = False
-        if isinstance(out_f32, tuple):
-            out_f32, cat = out_f32
-        n = len(specs)
-        relu = specs[0].relu
-        has_bias = specs[0].b is not None
-        has_res = specs[0].has_residual
-        if any(s.relu != relu or (s.b is not None) != has_bias or s.has_residual != has_res for s in specs):
-            raise ValueError("a linear group must share one epilogue")
-        xs, ress, outs, probs = [], [], [], []
-        base, off = None, 0
-        if cat:
-            M0 = tensors[0].shape[0]
-            if any(tensors[4 * i].shape[0] != M0 for i in range(n)):
-                raise ValueError("a concatenated linear group needs equal row counts")
-            base = torch.empty((M0, sum(s.w.w16.shape[0] for s in specs)), dtype=torch.float32 if out_f32 else BF16,
-                               device=tensors[0].device)
-        f32_in = []
-        for i, s in enumerate(specs):
-            x, res = tensors[4 * i], tensors[4 * i + 1]
-            # an f32 input (a module's f32 output fed on, e.g. MulT's pooled projections) is narrowed here and its
-            # gradient written as f32 by the dgrad kernel: no bf16 -> f32 cast node in the backward chain
-            f32_in.append(x.dtype == torch.float32)
-            if f32_in[-1]:
-                x = cast_to_bf16(x.contiguous())
+    def forward(ctx, specs: List[LinearSpec], out_f32: bool, cat: bool, *tensors):
+        relu, has_bias, has_res = _one_epilogue(specs, tensors[1::4])
+        xs, ress = tensors[0::4], tensors[1::4]
+        # an f32 input (a module's f32 output fed on, e.g. MulT's pooled projections) is narrowed here and its
+        # gradient written as f32 by the dgrad kernel: no bf16 -> f32 cast node in the backward chain
+        f32_in = xs[0].dtype == torch.float32
+        if any((x.dtype == torch.float32) != f32_in for x in xs):
+            raise ValueError("a linear group's inputs must share one dtype")
+        ws = [s.w.w16 for s in specs]
+        if f32_in:
+            xs = [cast_to_bf16(x.contiguous()) for x in xs]
+        for x in xs:
             _req(x, BF16)
-            w16 = s.w.w16
-            bias = s.b.master if has_bias else None
-            if cat:
-                y = base[:, off:off + w16.shape[0]]
-                off += w16.shape[0]
-            else:
-                y = torch.empty((x.shape[0], w16.shape[0]), dtype=torch.float32 if out_f32 else BF16, device=x.device)
-            probs.append((x, w16, y, bias, res))
-            xs.append(x), ress.append(res), outs.append(y)
+        base, outs = _linear_outputs(xs, ws, torch.float32 if out_f32 else BF16, cat)
+        probs = [(x, w, y, s.b.master if has_bias else None, res) for x, w, y, s, res in zip(xs, ws, outs, specs, ress)]
         epi = (EPI_BIAS if has_bias else 0) | (EPI_RELU if relu else 0) | (EPI_ADD_AUX if has_res else 0)
-        skinny = not has_res and all(x.shape[0] <= lib.SKINNY_MAX_M and x.shape[1] % 8 == 0 for x in xs)
-        if skinny:          # (B, d)-row problems: weight-streaming kernels instead of the 256-row tile
-            lib.skinny_fwd([lib.SkinnyProblem(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                              b.data_ptr() if b is not None else None, None,
-                                              x.shape[0], w.shape[0], x.shape[1], _ld(x), _ld(w), _ld(y), 0)
-                            for (x, w, y, b, _) in probs], epi, out_f32)
+        if not has_res and all(x.shape[0] <= lib.SKINNY_MAX_M and x.shape[1] % 8 == 0 for x in xs):
+            # (B, d)-row problems: weight-streaming kernels instead of the 256-row tile
+            lib.skinny_fwd([_skinny(x, w, y, b) for (x, w, y, b, _) in probs], epi, out_f32)
         else:
             gemm_group(GEMM_NT, probs, epi)
-        if any(f32_in) and not all(f32_in):
-            raise ValueError("a linear group's inputs must share one dtype")
-        ctx.f32_in = bool(f32_in and f32_in[0])
-        ctx.specs, ctx.out_f32, ctx.cat = specs, out_f32, cat
+        ctx.specs, ctx.cat, ctx.f32_in, ctx.has_res = specs, cat, f32_in, has_res
         ctx.save_for_backward(*xs, *(([base] if cat else outs) if relu else []))
-        ctx.x_needs = [tensors[4 * i].requires_grad for i in range(n)]
+        ctx.x_needs = [x.requires_grad for x in tensors[0::4]]
         return base if cat else tuple(outs)
 
     @staticmethod
     def backward(ctx, *gys):
         specs = ctx.specs
         n = len(specs)
-        saved = ctx.saved_tensors
-        xs = saved[:n]
-        ys = saved[n:] if specs[0].relu else None
-        L = lib.load()
-        st = lib.stream_ptr()
-        dys = []
+        relu, has_bias = specs[0].relu, specs[0].b is not None
+        xs = ctx.saved_tensors[:n]
+        ys = ctx.saved_tensors[n:] if relu else [None] * n
+        ws = [s.w.w16 for s in specs]
+
+        def narrow(g, y):                          # to bf16; behind a ReLU dz = dy * (y > 0) in the same kernel
+            return _relu_mask(g, y) if relu and g is not None else _grad_bf16(g)
         if ctx.cat:                                # one gradient for the concatenated output: slice it, no copies
-            g = gys[0]
-            if g is not None:
-                if specs[0].relu:
-                    g = _relu_mask(g, ys[0])
-                else:
-                    g = g.contiguous()
-                    if g.dtype != BF16:
-                        g = cast_to_bf16(g)
-            off = 0
-            for s in specs:
-                nout = s.w.w16.shape[0]
-                dys.append(None if g is None else g[:, off:off + nout])
-                off += nout
-            gys = dys
+            dys = _column_views(narrow(gys[0], ys[0]), [w.shape[0] for w in ws])
         else:
-          for i, g in enumerate(gys):
-            if g is None:
-                dys.append(None)
-                continue
-            if specs[0].relu:                      # dz = dy * (y > 0)
-                g = _relu_mask(g, ys[i])
-            else:
-                g = cast_to_bf16(g) if g.dtype != BF16 else g.contiguous()      # (the cast takes row-strided sources)
-            dys.append(g)
-        dgrad = []
-        has_bias = specs[0].b is not None
+            dys = [narrow(g, y) for g, y in zip(gys, ys)]
         grads: List[Optional[torch.Tensor]] = [None] * (4 * n)
         # inputs that are the adjacent column blocks of one contiguous tensor (small_ops.split3 of a pooled (B, 3d)
         # buffer) get their gradients as the same blocks of one buffer, so the split's backward has nothing to copy
-        dbase, col = None, 0
-        x0 = xs[0]
-        if (n > 1 and not ctx.f32_in and all(ctx.x_needs) and all(g is not None for g in dys) and x0._base is not None
-                and x0._base.is_contiguous() and x0._base.dim() == 2 and x0.data_ptr() == x0._base.data_ptr()
-                and x0._base.shape[1] == sum(x.shape[1] for x in xs) and x0._base.shape[0] == x0.shape[0]):
-            off, ok = 0, True
-            for x in xs:
-                ok = ok and x._base is x0._base and x.stride(0) == x0._base.shape[1] and \
-                    x.data_ptr() == x0._base.data_ptr() + 2 * off and x.shape[0] == x0.shape[0]
-                off += x.shape[1]
-            if ok:
-                dbase = torch.empty(x0._base.shape, dtype=BF16, device=x0.device)
+        dxs = []
+        if n > 1 and not ctx.f32_in and all(ctx.x_needs) and all(g is not None for g in dys):
+            xbase = _column_blocks(xs)
+            if xbase is not None:
+                dxs = _column_views(torch.empty_like(xbase), [x.shape[1] for x in xs])
+        dgrad = []
         for i, s in enumerate(specs):
             g = dys[i]
             if g is None:
                 continue
             if ctx.x_needs[i]:
-                if dbase is not None:
-                    dx = dbase[:, col:col + xs[i].shape[1]]
-                    col += xs[i].shape[1]
-                else:
-                    dx = torch.empty(xs[i].shape, dtype=torch.float32 if ctx.f32_in else BF16, device=g.device)
-                dgrad.append((g, s.w.w16, dx, None, None))
+                dx = dxs[i] if dxs else torch.empty(xs[i].shape, dtype=torch.float32 if ctx.f32_in else BF16, device=g.device)
+                dgrad.append((g, ws[i], dx, None, None))
                 grads[4 * i] = dx
             # wgrad; the bias gradient (column sums of dy) rides along in the same kernel (none for a frozen weight)
             if s.w.p.requires_grad:
                 queue_wgrad(g, xs[i], s.w.grad, s.b.grad if has_bias else None)
-            if s.has_residual:
+            if ctx.has_res:
                 grads[4 * i + 1] = g
         if dgrad:
             if all(g.shape[0] <= lib.SKINNY_MAX_M for (g, _, _, _, _) in dgrad):
-                lib.skinny_dgrad([lib.SkinnyProblem(g.data_ptr(), w.data_ptr(), dx.data_ptr(), None, None,
-                                                    g.shape[0], w.shape[0], w.shape[1], _ld(g), _ld(w), _ld(dx), 0)
-                                  for (g, w, dx, _, _) in dgrad], 0, 1.0, ctx.f32_in)
+                lib.skinny_dgrad([_skinny(g, w, dx) for (g, w, dx, _, _) in dgrad], 0, 1.0, ctx.f32_in)
             else:
                 gemm_group(GEMM_NN, dgrad, 0)
-        return (None, None, *grads)
+        return (None, None, None, *grads)
 
 
 def _rows2d(t: torch.Tensor) -> torch.Tensor:
@@ -768,9 +776,7 @@ class _RowLinear(torch.autograd.Function):
     def forward(ctx, specs: List[LinearSpec], opts, *tensors):
         out_f32, p, dual = opts
         n = len(specs)
-        relu, has_bias = specs[0].relu, specs[0].b is not None
-        if any(s.relu != relu or (s.b is not None) != has_bias or s.has_residual for s in specs):
-            raise ValueError("a row-linear group must share one epilogue and has no residual form")
+        relu, has_bias, _ = _one_epilogue(specs)
         xs = [_rows2d(tensors[3 * i]) for i in range(n)]
         f32_in = xs[0].dtype == torch.float32
         for x in xs:
@@ -788,9 +794,7 @@ class _RowLinear(torch.autograd.Function):
             x16 = torch.empty((M, K), dtype=BF16, device=x.device) if f32_in else x
             bias = s.b.master if has_bias else None
             probs.append(lib.SkinnyProblemEx(
-                lib.SkinnyProblem(x.data_ptr(), w16.data_ptr(), y.data_ptr(), bias.data_ptr() if bias is not None else None, None,
-                                  M, N, K, _ld(x), _ld(w16), _ld(y), 0),
-                y2.data_ptr() if y2 is not None else None, None, x16.data_ptr() if f32_in else None,
+                _skinny(x, w16, y, bias), _ptr(y2), None, x16.data_ptr() if f32_in else None,
                 _ld(y2) if y2 is not None else 0, 0, _ld(x16) if f32_in else 0, 0))
             outs.append(y), outs2.append(y2), x16s.append(x16)
         flags = (EPI_BIAS if has_bias else 0) | (EPI_RELU if relu else 0) | (EPI_DROPOUT if p > 0.0 else 0)
@@ -838,8 +842,7 @@ class _RowLinear(torch.autograd.Function):
                 dx = torch.empty((M, K), dtype=torch.float32 if ctx.f32_in else BF16, device=g.device)
                 y = ys[i]
                 probs.append(lib.SkinnyProblemEx(
-                    lib.SkinnyProblem(g.data_ptr(), w16.data_ptr(), dx.data_ptr(), None, None, M, N, K, _ld(g), _ld(w16), _ld(dx), 0),
-                    None, y.data_ptr() if y is not None else None, dz.data_ptr() if dz is not g else None,
+                    _skinny(g, w16, dx), None, _ptr(y), dz.data_ptr() if dz is not g else None,
                     0, _ld(y) if y is not None else 0, _ld(dz) if dz is not g else 0, 0))
                 dxs.append(dx)
                 if specs[i].w.p.requires_grad:               # a frozen weight: input gradient only
@@ -870,8 +873,8 @@ def row_linear_ok(items: Sequence[tuple]) -> bool:
 
 def linear_group(items: Sequence[tuple], out_f32: bool = False, cat: bool = False, dropout_p: float = 0.0, dual: bool = False):
     """items: (x_bf16 [M,K], LinearSpec, residual_bf16|None).  One NT launch for the group.  Returns the list of
-    outputs, or with ``cat`` ONE (M, sum N_i) tensor whose column blocks are the outputs (equal M required)."""
-    """``dropout_p``: nn.Dropout(p) on every output (training-mode probability: pass 0 in eval).  ``dual``: every output also as
+    outputs, or with ``cat`` ONE (M, sum N_i) tensor whose column blocks are the outputs (equal M required).
+    ``dropout_p``: nn.Dropout(p) on every output (training-mode probability: pass 0 in eval).  ``dual``: every output also as
     a second tensor in the OTHER dtype — the return value is then a list of (y, y_other) pairs.  Groups of (B, d)-row problems
     (``row_linear_ok``) run both inside the linear's own launch (``_RowLinear``); otherwise they are separate kernels."""
     if _PRECISION == "fp32":
@@ -880,25 +883,16 @@ def linear_group(items: Sequence[tuple], out_f32: bool = False, cat: bool = Fals
             raise RuntimeError("the fp32 parity mode runs without dropout (use p = 0 or eval())")
         return [(y, y) for y in ys] if dual else ys
     if not cat and row_linear_ok(items):
-        specs, tensors = [], []
-        for x, spec, res in items:
-            spec.has_residual = False
-            specs.append(spec)
-            tensors += [x, spec.w.p, spec.b.p if spec.b is not None else None]
+        specs, tensors = _flatten_items(items, residual=False)
         outs = _RowLinear.apply(specs, (bool(out_f32), float(dropout_p), bool(dual)), *tensors)
         n = len(specs)
         return [(outs[i], outs[n + i]) for i in range(n)] if dual else list(outs)
-    specs, tensors = [], []
-    for x, spec, res in items:
-        spec.has_residual = res is not None
-        specs.append(spec)
-        tensors += [x, res, spec.w.p, spec.b.p if spec.b is not None else None]
+    specs, tensors = _flatten_items(items)
     if cat:
-        ys = _GroupedLinear.apply(specs, (out_f32, True), *tensors)
         if dropout_p > 0.0 or dual:
             raise ValueError("a concatenated linear group has no dropout / dual form")
-        return ys
-    ys = [dropout(y, dropout_p, True) for y in _GroupedLinear.apply(specs, out_f32, *tensors)]
+        return _GroupedLinear.apply(specs, bool(out_f32), True, *tensors)
+    ys = [dropout(y, dropout_p, True) for y in _GroupedLinear.apply(specs, bool(out_f32), False, *tensors)]
     if dual:
         return [(y, (to_bf16(y) if out_f32 else to_f32(y))) for y in ys]
     return ys
@@ -1226,9 +1220,8 @@ class _Fanout(torch.autograd.Function):
             return None, None
         if len(live) == 1:
             return live[0], None
-        live = [g.contiguous() if g.dtype == BF16 else cast_to_bf16(g.contiguous()) for g in live]
+        live = [_grad_bf16(g) for g in live]
         out = torch.empty_like(live[0])
-        import ctypes as C
         for i in range(0, len(live), lib.ADDN_MAX - 1):            # chunks of <= 8 operands (running sum carried)
             chunk = live[i:i + lib.ADDN_MAX - 1] + ([out] if i > 0 else [])
             if len(chunk) == 1:
@@ -1269,7 +1262,7 @@ class _FanoutGroup(torch.autograd.Function):
             if len(live) == 1:
                 outs.append(live[0])
                 continue
-            live = [g.contiguous() if g.dtype == BF16 else cast_to_bf16(g.contiguous()) for g in live]
+            live = [_grad_bf16(g) for g in live]
             if len(live) > lib.ADDN_MAX or live[0].numel() % 8 or any(g.data_ptr() % 16 for g in live):
                 # a gradient the grouped kernel cannot take (a view at an odd offset, an over-wide fan-out): sum this tensor's
                 # gradients with stock adds in f32 rather than raising from inside backward
@@ -1315,7 +1308,6 @@ class _MeanPoolCat(torch.autograd.Function):
         for x in xs:
             _req(x, BF16)
         if n <= lib.POOL_MAX:                            # all modalities in one launch
-            import ctypes as C
             ptrs = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
             Ts = (C.c_int * n)(*[x.shape[1] for x in xs])
             lib.check(L.mmf_meanpool_cat_fwd(ptrs, Ts, n, y.data_ptr(), B, d, n * d, st))
@@ -1333,7 +1325,6 @@ class _MeanPoolCat(torch.autograd.Function):
         out = [torch.empty((B, T, d), dtype=BF16, device=g.device) for (B, T, d) in ctx.shapes]
         B, _, d = ctx.shapes[0]
         if n <= lib.POOL_MAX:
-            import ctypes as C
             ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in out])
             Ts = (C.c_int * n)(*[sh[1] for sh in ctx.shapes])
             lib.check(L.mmf_meanpool_cat_bwd(g.data_ptr(), ptrs, Ts, n, B, d, n * d, st))

@@ -17,41 +17,15 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import lib
-from .lib import (EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, EPI_MASK_AUX, EPI_RELU, GEMM_NN, GEMM_NT, GEMM_TN,
-                  GemmProblem)
+from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, EPI_MASK_AUX, EPI_RELU, GEMM_NN, GEMM_NT, GEMM_TN, GemmProblem
+from .ops import _column_views, _flatten_items, _gemm_problems, _linear_outputs, _one_epilogue, _req
 
 F32 = torch.float32
 
 
-def _ld(t: torch.Tensor) -> int:
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError(f"expected a 2-D row-major (possibly row-strided) tensor, got {tuple(t.shape)} strides {t.stride()}")
-    return t.stride(0)
-
-
-def _req(t: torch.Tensor) -> None:
-    if not t.is_cuda:
-        raise RuntimeError("mmfusion ops run on the GPU only (no CPU fallback)")
-    if t.dtype != F32:
-        raise TypeError(f"fp32 mode expects float32 tensors, got {t.dtype}")
-
-
 def gemm_group(layout: int, probs: Sequence[tuple], epilogue: int, alpha: float = 1.0) -> None:
     """probs: (A, B, C, bias|None, aux|None) f32 tensors; M, N from C; K from A."""
-    ps: List[GemmProblem] = []
-    for (A, Bm, Cm, bias, aux) in probs:
-        _req(A), _req(Bm), _req(Cm)
-        M, N = Cm.shape
-        K = A.shape[0] if layout == GEMM_TN else A.shape[1]
-        ok = {GEMM_NT: A.shape == (M, K) and Bm.shape == (N, K), GEMM_NN: A.shape == (M, K) and Bm.shape == (K, N),
-              GEMM_TN: A.shape == (K, M) and Bm.shape == (K, N)}[layout]
-        if not ok:
-            raise ValueError(f"f32 gemm layout {layout}: A{tuple(A.shape)} B{tuple(Bm.shape)} C{tuple(Cm.shape)}")
-        if aux is not None and tuple(aux.shape) != (M, N):
-            raise ValueError("aux must match C")
-        ps.append(GemmProblem(A.data_ptr(), Bm.data_ptr(), Cm.data_ptr(), bias.data_ptr() if bias is not None else None,
-                              aux.data_ptr() if aux is not None else None, M, N, K, _ld(A), _ld(Bm), _ld(Cm),
-                              _ld(aux) if aux is not None else 0))
+    ps = _gemm_problems(layout, probs, epilogue, F32, F32)
     for i in range(0, len(ps), lib.GEMM_MAX_PROBLEMS):
         chunk = ps[i:i + lib.GEMM_MAX_PROBLEMS]
         arr = (GemmProblem * len(chunk))(*chunk)
@@ -79,53 +53,34 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, specs, cat: bool, *tensors):
-        n = len(specs)
-        relu, has_bias, has_res = specs[0].relu, specs[0].b is not None, specs[0].has_residual
-        xs, outs, probs = [], [], []
-        base, off = None, 0
-        if cat:
-            base = torch.empty((tensors[0].shape[0], sum(s.w.master.shape[0] for s in specs)), dtype=F32, device=tensors[0].device)
-        for i, s in enumerate(specs):
-            x, res = tensors[4 * i].float(), tensors[4 * i + 1]
-            w = s.w.master
-            if cat:
-                y = base[:, off:off + w.shape[0]]
-                off += w.shape[0]
-            else:
-                y = torch.empty((x.shape[0], w.shape[0]), dtype=F32, device=x.device)
-            probs.append((x, w, y, s.b.master if has_bias else None, res))
-            xs.append(x), outs.append(y)
-        gemm_group(GEMM_NT, probs, (EPI_BIAS if has_bias else 0) | (EPI_RELU if relu else 0) | (EPI_ADD_AUX if has_res else 0))
-        ctx.specs, ctx.cat = specs, cat
+        relu, has_bias, has_res = _one_epilogue(specs, tensors[1::4])
+        xs, ws = [x.float() for x in tensors[0::4]], [s.w.master for s in specs]
+        base, outs = _linear_outputs(xs, ws, F32, cat)
+        gemm_group(GEMM_NT, [(x, w, y, s.b.master if has_bias else None, res)
+                             for x, w, y, s, res in zip(xs, ws, outs, specs, tensors[1::4])],
+                   (EPI_BIAS if has_bias else 0) | (EPI_RELU if relu else 0) | (EPI_ADD_AUX if has_res else 0))
+        ctx.specs, ctx.cat, ctx.has_res = specs, cat, has_res
         ctx.save_for_backward(*xs, *(([base] if cat else outs) if relu else []))
-        ctx.x_needs = [tensors[4 * i].requires_grad for i in range(n)]
+        ctx.x_needs = [x.requires_grad for x in tensors[0::4]]
         return base if cat else tuple(outs)
 
     @staticmethod
     def backward(ctx, *gys):
         specs = ctx.specs
         n = len(specs)
+        relu = specs[0].relu
         xs = ctx.saved_tensors[:n]
-        ys = ctx.saved_tensors[n:] if specs[0].relu else None
-        dys = []
+        ys = ctx.saved_tensors[n:] if relu else [None] * n
+
+        def widen(g, y):
+            if g is None:
+                return None
+            g = g.float().contiguous()
+            return g * (y > 0) if relu else g
         if ctx.cat:
-            g = gys[0]
-            if g is not None:
-                g = g.float().contiguous()
-                if specs[0].relu:
-                    g = g * (ys[0] > 0)
-            off = 0
-            for s in specs:
-                nout = s.w.master.shape[0]
-                dys.append(None if g is None else g[:, off:off + nout])
-                off += nout
+            dys = _column_views(widen(gys[0], ys[0]), [s.w.master.shape[0] for s in specs])
         else:
-            for i, g in enumerate(gys):
-                if g is None:
-                    dys.append(None)
-                    continue
-                g = g.float().contiguous()
-                dys.append(g * (ys[i] > 0) if specs[0].relu else g)
+            dys = [widen(g, y) for g, y in zip(gys, ys)]
         grads: List[Optional[torch.Tensor]] = [None] * (4 * n)
         dgrad = []
         for i, s in enumerate(specs):
@@ -137,7 +92,7 @@ class _Linear(torch.autograd.Function):
                 dgrad.append((g, s.w.master, dx, None, None))
                 grads[4 * i] = dx
             wgrad(g, xs[i], s.w.grad, s.b.grad if s.b is not None else None)
-            if s.has_residual:
+            if ctx.has_res:
                 grads[4 * i + 1] = g
         if dgrad:
             gemm_group(GEMM_NN, dgrad, 0)
@@ -145,11 +100,7 @@ class _Linear(torch.autograd.Function):
 
 
 def linear_group(items: Sequence[tuple], cat: bool = False):
-    specs, tensors = [], []
-    for x, spec, res in items:
-        spec.has_residual = res is not None
-        specs.append(spec)
-        tensors += [x, res, spec.w.p, spec.b.p if spec.b is not None else None]
+    specs, tensors = _flatten_items(items)
     out = _Linear.apply(specs, cat, *tensors)
     return out if cat else list(out)
 
@@ -206,7 +157,7 @@ def ffn_residual_group(items: Sequence[tuple]) -> List[torch.Tensor]:
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eps, x, gamma, beta):
-        _req(x)
+        _req(x, F32)
         x = x.contiguous()
         d = x.shape[-1]
         rows = x.numel() // d
@@ -255,7 +206,7 @@ class _Attention(torch.autograd.Function):
         B, Tq, Tk = spec.B, spec.Tq, spec.Tk
         qs, ks, vs = srcs[spec.q[0]], srcs[spec.k[0]], srcs[spec.v[0]]
         for t in (qs, ks, vs):
-            _req(t)
+            _req(t, F32)
         dev = qs.device
         P = torch.empty((B, H, Tq, Tk), dtype=F32, device=dev)
         o = torch.empty((B * Tq, d), dtype=F32, device=dev)

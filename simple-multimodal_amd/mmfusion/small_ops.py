@@ -11,7 +11,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import lib, ops
-from .ops import BF16, _req
+from .ops import BF16, _column_blocks, _grad_bf16, _ptr, _req
 
 F32 = torch.float32
 NCE_MAX_B = 64
@@ -25,22 +25,14 @@ def _grad_of(p: torch.nn.Parameter) -> torch.Tensor:
     return g
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 # --------------------------------------------------------------------------------------------
 # (B, 3d) "cat3" views: the three modality feature matrices side by side
 # --------------------------------------------------------------------------------------------
 def cat3(t: torch.Tensor, a: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """fp32 (B, 3d) = cat([t, a, v], -1).  When the three are the column thirds of one contiguous fp32 buffer
     (hier-seq: the pooled sequence means) that buffer itself is returned — no copy, gradients flow to it."""
-    B, d = t.shape
-    base = t._base
-    if (base is not None and a._base is base and v._base is base and base.dtype == F32 and base.is_contiguous()
-            and tuple(base.shape) == (B, 3 * d) and t.dtype == F32
-            and t.data_ptr() == base.data_ptr() and a.data_ptr() == base.data_ptr() + 4 * d
-            and v.data_ptr() == base.data_ptr() + 8 * d and t.stride(0) == a.stride(0) == v.stride(0) == 3 * d):
+    base = _column_blocks((t, a, v))
+    if base is not None and base.dtype == F32 and t.shape[1] == a.shape[1] == v.shape[1]:
         return base
     return torch.cat([t.float(), a.float(), v.float()], dim=-1)
 
@@ -64,11 +56,8 @@ class _Split3(torch.autograd.Function):
         # the producer (ops._GroupedLinear.backward) writes the three input gradients as the column thirds of one
         # buffer when its inputs were such thirds: that buffer is the gradient, no concatenation kernel
         if g0 is not None and g1 is not None and g2 is not None:
-            base, es = g0._base, g0.element_size()
-            if (base is not None and g1._base is base and g2._base is base and base.dtype == dtype and base.is_contiguous()
-                    and tuple(base.shape) == (B, 3 * d) and g0.data_ptr() == base.data_ptr()
-                    and g1.data_ptr() == base.data_ptr() + es * d and g2.data_ptr() == base.data_ptr() + 2 * es * d
-                    and g0.stride(0) == g1.stride(0) == g2.stride(0) == 3 * d):
+            base = _column_blocks((g0, g1, g2))
+            if base is not None and base.dtype == dtype and tuple(base.shape) == (B, 3 * d):
                 global split3_nocopy_hits
                 split3_nocopy_hits += 1
                 return base
@@ -143,12 +132,7 @@ class _Gat3(torch.autograd.Function):
         h, y, alpha, sdots = ctx.saved_tensors
         B, heads, C_, relu, drop = ctx.cfg
         att_src, att_dst, bias = ctx.params
-        dy = gs[0].contiguous() if gs[0] is not None else None
-        dpool = gs[1].contiguous() if ctx.pool and gs[1] is not None else None
-        if dy is not None and dy.dtype != BF16:
-            dy = ops.cast_to_bf16(dy)
-        if dpool is not None and dpool.dtype != BF16:
-            dpool = ops.cast_to_bf16(dpool)
+        dy, dpool = _grad_bf16(gs[0]), (_grad_bf16(gs[1]) if ctx.pool else None)
         if dy is None and dpool is None:
             return (None,) * 9
         dh = torch.empty_like(h)
@@ -254,10 +238,7 @@ class _AdaptiveCombine(torch.autograd.Function):
         hp, attended, aw = ctx.saved_tensors
         w2, b2 = ctx.params
         B, d = hp.shape
-        if dweighted is not None:
-            dweighted = dweighted.contiguous()
-            if dweighted.dtype != BF16:
-                dweighted = ops.cast_to_bf16(dweighted)
+        dweighted = _grad_bf16(dweighted)
         if daw is not None:
             daw = daw.contiguous().float()
         datt = torch.empty_like(attended)
@@ -342,11 +323,8 @@ def rowmask(x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------------------
 # ModalityDropout and the training-step loss as one launch each (round 4; csrc/loss.hip)
 # --------------------------------------------------------------------------------------------
-import ctypes as _C
-
-
 def _ptr3(ts):
-    return (_C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    return (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
 
 
 class _ModalityDropout(torch.autograd.Function):
@@ -438,8 +416,8 @@ class _LossTail(torch.autograd.Function):
             rc = L.mmf_distill_kl(*rows, t.data_ptr(), t.stride(0), B, Cn, temperature, *out)
         else:
             ex = [e.float().reshape(1) for e in extras]
-            ce = (*rows, targets.data_ptr(), B, Cn, smoothing, (_C.c_void_p * max(len(ex), 1))(*[e.data_ptr() for e in ex]),
-                  (_C.c_float * max(len(ex), 1))(*weights), len(ex))
+            ce = (*rows, targets.data_ptr(), B, Cn, smoothing, (C.c_void_p * max(len(ex), 1))(*[e.data_ptr() for e in ex]),
+                  (C.c_float * max(len(ex), 1))(*weights), len(ex))
             rc = (L.mmf_fusion_loss(*ce, *out) if teacher is None
                   else L.mmf_fusion_loss_kd(*ce, t.data_ptr(), t.stride(0), temperature, kd_weight, *out))
         lib.check(rc)
@@ -542,8 +520,8 @@ class _RobustHead(torch.autograd.Function):
         dfs = [torch.empty((B, d), dtype=F32, device=h.device) if need[i] else None for i in range(3)]
         # with a given mask only a direct gradient of the availability reaches the predictor
         dh = torch.empty((B, d), dtype=F32, device=h.device) if need[3] and (ctx.avail < 0 or ga is not None) else None
-        dP = (_C.c_void_p * 3)(*[_ptr(x) for x in dps])
-        dF = (_C.c_void_p * 3)(*[_ptr(x) for x in dfs])
+        dP = (C.c_void_p * 3)(*[_ptr(x) for x in dps])
+        dF = (C.c_void_p * 3)(*[_ptr(x) for x in dfs])
         lib.check(lib.load().mmf_robust_head_bwd(_ptr3((ft, fa, fv)), h.data_ptr(), w2.data_ptr(), _ptr3(wm), a.data_ptr(),
                                                  _ptr3((pt, pa, pv)), wn.data_ptr(), ctx.avail, g.data_ptr(), dP, _ptr(ga),
                                                  _ptr(gwn), dF, _ptr(dh), _grad_of(w2).data_ptr(), _grad_of(b2).data_ptr(),
