@@ -667,6 +667,38 @@ int mmf_deberta_attn_fwd(const void* qkv_bf16, const void* posq_bf16, const void
                          const void* mask, int mask_kind, void* out_bf16, int n, int H, int T, int S, int head_dim, float scale,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Input preparation (mmfusion/prep.py; the reference does this on the host per sample, data/dataset_loaders.py:95-261): what a
+ * decoder emits -> what the backbones read.  Every function validates first and launches nothing on an error; an optional
+ * per-frame / per-clip device array is NULL for "none".  DESIGN.md section 11 states the geometry, the filter and the RNG keying.
+ * ------------------------------------------------------------------------------------------ */
+/* frames (N, Hs, Ws, 3) u8 -> pixels (N, 3, H, W) f32.  Output pixel (c, y, x) is the bilinear interpolation (half-pixel centres,
+ * no antialiasing, edge replication: sx = (x + 0.5) Ws / W - 0.5 clamped below at 0, x0 = floor(sx), x1 = min(x0 + 1, Ws - 1),
+ * the same in y; coordinates in integer arithmetic) of byte (bgr ? 2 - c : c) of the source pixels, then
+ * clamp(v / 255 * brightness[n], 0, 1); with flip[n] column x takes the value of column W - 1 - x; a frame with live[n] == 0 is
+ * zeros.  live / flip u8 [N], brightness f32 [N].  W % 4 == 0 (else MMF_E_UNSUPPORTED), pixels 16-byte aligned (MMF_E_ALIGN),
+ * N <= 65535 and every side <= 16384. */
+int mmf_video_prepare(const uint8_t* frames, const uint8_t* live, const float* brightness, const uint8_t* flip, float* pixels,
+                      int N, int Hs, int Ws, int H, int W, int bgr, void* stream);
+/* The same pixels rounded to bf16 and stored as mmf_vit_patchify stores them: patches (N * (H/P) * (W/P), 3*P*P) bf16, bit-identical
+ * to mmf_vit_patchify of mmf_video_prepare's result, which is never written.  mmf_vit_patchify's constraints. */
+int mmf_video_prepare_patches(const uint8_t* frames, const uint8_t* live, const float* brightness, const uint8_t* flip,
+                              void* patches_bf16, int N, int Hs, int Ws, int H, int W, int P, int bgr, void* stream);
+/* wave (B, C, Ls) f32 -> out (B, L) f32 in one launch: mean over the C channels, resampling by new / orig (the rates divided by
+ * their gcd), zero padding / truncation to L.  Samples at or past len[b] (int32 [B], NULL: Ls) do not exist; outputs at or past
+ * ceil(new len / orig) are 0.  table: f32 (new, 2 width + orig), table[j][k] = g(((k - width) / orig - j / new) base) with
+ * base = 0.99 min(orig, new), width = ceil(6 orig / base), g(t) = cos^2(pi t / 12) sinc(pi t) base / orig inside |t| < 6 and 0
+ * outside; out[i new + j] = sum_k x[i orig + k - width] table[j][k].  table_elems must be new (2 width + orig) and width the value
+ * above (MMF_E_SHAPE).  orig == new takes a NULL table: mono mix and padding only.  B <= 65535, Ls and L below 2^30. */
+int mmf_audio_resample(const float* wave, const int* len, const float* table, int64_t table_elems, float* out, int B, int C,
+                       int64_t Ls, int64_t L, int orig, int new_, int width, void* stream);
+/* x (B, L) f32 -> out (B, L) f32, not in place.  xn[j] = x[j] + 0.01 z(b, j) where noise_on[b] (u8 [B]), z standard normal by
+ * Box-Muller from draws 2 j and 2 j + 1 of mmf_dropout's counter hash under the key of (*rng_state, site, b).  With
+ * n = stretch_len[b] (int32 [B]; NULL, L or a value below 1: off), out[i] for i < min(n, L) is xn resized L -> n by linear
+ * interpolation (half-sample centres, integer coordinates, edge replication) and 0 from there on. */
+int mmf_audio_augment(const float* x, float* out, const uint8_t* noise_on, const int* stretch_len, const uint64_t* rng_state,
+                      uint32_t site, int B, int64_t L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ SYMBOLS = (
     "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd",
+    "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
 )
 
 
@@ -211,6 +212,10 @@ def load() -> C.CDLL:
     lib.mmf_w2v_posconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_deberta_embed.argtypes = [vp, vp, vp, vp, vp, f32, vp, i32, vp, i64, i32, i32, vp]
     lib.mmf_deberta_attn_fwd.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
+    lib.mmf_video_prepare.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.mmf_video_prepare_patches.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.mmf_audio_resample.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, i64, i32, i32, i32, vp]
+    lib.mmf_audio_augment.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, i32, i64, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -502,3 +507,80 @@ def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S:
     with _Timed(f"deberta_attn_fwd_kernel<{head_dim}>", 12.0 * n * H * T * T * head_dim, [(T, T)]):
         check(load().mmf_deberta_attn_fwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
                                           out.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
+
+
+# ---- input preparation (csrc/prep.hip); tensors, not pointers: the shapes are checked here ------------------------
+def _prep_f32(who: str, *ts) -> None:
+    import torch
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{who}: expected a contiguous float32 tensor, got {tuple(t.shape)} {t.dtype}")
+
+
+def _prep_arg(t, who: str, dtype, numel: int, dev):
+    """-> the pointer of an optional per-frame / per-clip array (None: null), checked"""
+    if t is None:
+        return None
+    if t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{who} must be a contiguous {str(dtype).rpartition('.')[2]} tensor of {numel} values on {dev}, "
+                         f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t.data_ptr()
+
+
+def video_prepare(frames, out, H: int, W: int, P: Optional[int] = None, bgr: bool = False, live=None, brightness=None,
+                  flip=None) -> None:
+    """frames (N, Hs, Ws, 3) uint8 contiguous -> out: (N, 3, H, W) f32, or with ``P`` the (N * (H/P) * (W/P), 3*P*P) bf16 patch
+    matrix of ``vit_patchify``; live / flip uint8 (N,), brightness f32 (N,), all optional"""
+    import torch
+    if not frames.is_cuda or not out.is_cuda:
+        raise RuntimeError("video_prepare runs on the GPU only (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError(f"video_prepare: frames must be contiguous uint8 (N, Hs, Ws, 3), got {tuple(frames.shape)} {frames.dtype}")
+    N, Hs, Ws, _ = frames.shape
+    if out.dtype != (torch.float32 if P is None else torch.bfloat16) or out.numel() != N * 3 * H * W or not out.is_contiguous():
+        raise ValueError("video_prepare: out does not hold N x 3 x H x W contiguous f32 (pixels) / bf16 (patches) elements")
+    dev = frames.device
+    lp, fp = _prep_arg(live, "video_prepare: live", torch.uint8, N, dev), _prep_arg(flip, "video_prepare: flip", torch.uint8, N, dev)
+    bp = _prep_arg(brightness, "video_prepare: brightness", torch.float32, N, dev)
+    nbytes = N * (Hs * Ws * 3 + 3 * H * W * (4 if P is None else 2))
+    with _Timed("video_prepare_kernel<%s>" % ("false" if P is None else "true"), 0.0, [(N, nbytes // N)]):
+        if P is None:
+            check(load().mmf_video_prepare(frames.data_ptr(), lp, bp, fp, out.data_ptr(), N, Hs, Ws, H, W, int(bgr), stream_ptr()))
+        else:
+            check(load().mmf_video_prepare_patches(frames.data_ptr(), lp, bp, fp, out.data_ptr(), N, Hs, Ws, H, W, P, int(bgr),
+                                                   stream_ptr()))
+
+
+def audio_resample(wave, lengths, table, out, orig: int, new: int, width: int) -> None:
+    """wave (B, C, Ls) f32 -> out (B, L) f32: mono mean, resampling by new / orig against ``table`` (new, 2 width + orig) f32
+    (None when orig == new), zeros past each clip's resampled length; lengths int32 (B,) or None"""
+    import torch
+    _prep_f32("audio_resample", wave, out)
+    if wave.dim() != 3 or out.dim() != 2 or out.shape[0] != wave.shape[0]:
+        raise ValueError(f"audio_resample: wave must be (B, C, Ls) and out (B, L), got {tuple(wave.shape)} and {tuple(out.shape)}")
+    B, Cn, Ls = wave.shape
+    if table is not None:
+        _prep_f32("audio_resample", table)
+    lp = _prep_arg(lengths, "audio_resample: lengths", torch.int32, B, wave.device)
+    taps = 2 * width if table is not None else 1
+    # (two kernels behind one entry point: audio_resample_tile_kernel where the phases fit LDS, audio_resample_kernel otherwise)
+    with _Timed("audio_resample_kernels", 2.0 * out.numel() * taps, [(B, Cn * Ls * 4 + out.shape[1] * 4)]):
+        check(load().mmf_audio_resample(wave.data_ptr(), lp, table.data_ptr() if table is not None else None,
+                                        table.numel() if table is not None else 0, out.data_ptr(), B, Cn, Ls, out.shape[1], orig, new,
+                                        width, stream_ptr()))
+
+
+def audio_augment(x, out, noise_on, stretch_len, rng_state_ptr: Optional[int], site: int) -> None:
+    """x (B, L) f32 -> out (B, L) f32: additive noise where noise_on (uint8 (B,)), then the time stretch to stretch_len
+    (int32 (B,), L: off); either may be None"""
+    import torch
+    _prep_f32("audio_augment", x, out)
+    if x.dim() != 2 or out.shape != x.shape or out.data_ptr() == x.data_ptr():
+        raise ValueError("audio_augment: x and out must be two (B, L) tensors")
+    B, L = x.shape
+    np_ = _prep_arg(noise_on, "audio_augment: noise_on", torch.uint8, B, x.device)
+    sp = _prep_arg(stretch_len, "audio_augment: stretch_len", torch.int32, B, x.device)
+    with _Timed("audio_augment_kernel", 0.0, [(B, L * 8)]):
+        check(load().mmf_audio_augment(x.data_ptr(), out.data_ptr(), np_, sp, rng_state_ptr, site, B, L, stream_ptr()))

@@ -12,7 +12,9 @@ One pre-LN layer on a chunk of ``n`` images (rows = n * T tokens), in the blocks
     _ffn(ln, + y)                 ln -> h -> x
 
 In front of the layers: ``mmf_vit_patchify`` -> patch-embedding GEMM + bias -> ``mmf_vit_embed_tokens``; behind them the
-final LayerNorm and one widening cast into the f32 result.  ``cls_features`` runs the LAST layer for the CLS rows only:
+final LayerNorm and one widening cast into the f32 result.  Decoded uint8 ``(N, Hs, Ws, 3)`` frames are taken too: then
+``mmf_video_prepare_patches`` (mmfusion/prep.py) resizes them straight into the patch matrix, with the same bits as
+``mmf_vit_patchify`` of the prepared f32 frames, which are never written.  ``cls_features`` runs the LAST layer for the CLS rows only:
 K and V for every token, but Q, the out-projection, the MLP and the final LayerNorm for row 0 of each image (``Tq = 1``).
 
 Frames are processed in chunks of ``chunk`` images through one workspace allocated once, so memory does not grow with
@@ -22,7 +24,7 @@ from __future__ import annotations
 
 import re
 import types
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -30,6 +32,7 @@ from . import arena as _arena
 from . import lib, ops
 from .backbone import BackboneOutput, FrozenBackbone, WsTable
 from .lib import EPI_BIAS, GEMM_NT
+from .prep import VideoAug
 
 # images per pass through the workspace (tools/vit_bench.py --chunks; DESIGN.md section 8 has the numbers)
 DEFAULT_CHUNK = 160
@@ -69,7 +72,8 @@ class NativeViT(FrozenBackbone):
 
     ``forward(pixel_values)`` -> ``.last_hidden_state`` (N, T, hidden) f32 after the final LayerNorm;
     ``cls_features(pixel_values)`` -> (N, hidden) f32, row 0 of the same with the last layer run for those rows only.
-    ``pixel_values``: (N, C, H, W) f32 on the GPU.  ``state_dict()`` has the keys and shapes of transformers 5.x;
+    ``pixel_values``: (N, C, H, W) f32 on the GPU, or decoded frames (N, Hs, Ws, 3) uint8 of any size, which are resized to
+    the model's on the way into the patch matrix; ``aug`` (a ``prep.VideoAug``, uint8 input only) says how.  ``state_dict()`` has the keys and shapes of transformers 5.x;
     ``load_state_dict`` takes those and the 4.x names (``encoder.layer.N.attention.attention.query...``); Q/K/V are
     stored fused and split / merged on the way.  ``pooler.dense`` is kept as an unused parameter pair so that a round
     trip loses nothing."""
@@ -151,19 +155,32 @@ class NativeViT(FrozenBackbone):
         self._ln(ws, y, ln0, f"l{i}_ln2_w", f"l{i}_ln2_b")
         self._ffn(i, ws, ln0, y, self._rows(ws, "x", n, d))
 
-    def _embed(self, ws, pixels: torch.Tensor, n: int) -> None:
+    def _embed(self, ws, pixels: torch.Tensor, n: int, aug: Optional[VideoAug]) -> None:
         c, T, d, K, NP = self.config, self.T, self.config.hidden_size, self.patch_dim, self.num_patches
         patches = ws["h"][:n * NP * K].view(n * NP, K)
         off = self.chunk * NP * K
         pe = ws["h"][off:off + n * NP * d].view(n * NP, d)
-        lib.vit_patchify(pixels, patches, n, c.num_channels, c.image_size, c.image_size, c.patch_size)
+        if pixels.dtype == torch.uint8:
+            lib.video_prepare(pixels, patches, c.image_size, c.image_size, c.patch_size, aug.bgr, aug.live, aug.brightness, aug.flip)
+        else:
+            lib.vit_patchify(pixels, patches, n, c.num_channels, c.image_size, c.image_size, c.patch_size)
         ops.gemm(GEMM_NT, patches, self._w("patch_weight").view(d, K), pe, bias=self._f("patch_bias"), epilogue=EPI_BIAS)
         lib.vit_embed_tokens(pe, self._f("cls_token"), self._f("position_embeddings"), ws["x"], n, T, d)
 
-    def _run(self, pixel_values: torch.Tensor, cls_only: bool) -> torch.Tensor:
+    def _run(self, pixel_values: torch.Tensor, cls_only: bool, aug: Optional[VideoAug] = None) -> torch.Tensor:
         c = self.config
-        self._check_input(pixel_values, "pixel_values")
-        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (c.num_channels, c.image_size, c.image_size):
+        frames = isinstance(pixel_values, torch.Tensor) and pixel_values.dtype == torch.uint8
+        if frames:
+            self._check_input(pixel_values, "pixel_values", torch.uint8)
+            if pixel_values.dim() != 4 or pixel_values.shape[3] != 3 or c.num_channels != 3:
+                raise ValueError(f"NativeViT: uint8 pixel_values {tuple(pixel_values.shape)} is not (N, Hs, Ws, 3) decoded frames "
+                                 f"for a 3-channel model")
+            aug = aug if aug is not None else VideoAug()
+        else:
+            self._check_input(pixel_values, "pixel_values")
+            if aug is not None:
+                raise ValueError("NativeViT: aug goes with uint8 (N, Hs, Ws, 3) frames; f32 pixel_values are taken as prepared")
+        if not frames and (pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (c.num_channels, c.image_size, c.image_size)):
             raise ValueError(f"NativeViT: pixel_values {tuple(pixel_values.shape)} is not (N, {c.num_channels}, {c.image_size}, "
                              f"{c.image_size}) (position embeddings are not interpolated)")
         pixel_values = pixel_values.contiguous()
@@ -174,7 +191,7 @@ class NativeViT(FrozenBackbone):
         L = c.num_hidden_layers
         for n0 in range(0, N, self.chunk):
             n = min(self.chunk, N - n0)
-            self._embed(ws, pixel_values[n0:n0 + n], n)
+            self._embed(ws, pixel_values[n0:n0 + n], n, aug.rows(n0, n0 + n) if frames else None)
             for i in range(L - 1 if cls_only else L):
                 self._layer(i, ws, n)
             if cls_only:
@@ -185,8 +202,8 @@ class NativeViT(FrozenBackbone):
             self._widen(ln, out[n0:n0 + n])
         return out
 
-    def forward(self, pixel_values: torch.Tensor) -> BackboneOutput:
-        return BackboneOutput(self._run(pixel_values, cls_only=False))
+    def forward(self, pixel_values: torch.Tensor, aug: Optional[VideoAug] = None) -> BackboneOutput:
+        return BackboneOutput(self._run(pixel_values, cls_only=False, aug=aug))
 
-    def cls_features(self, pixel_values: torch.Tensor) -> torch.Tensor:
-        return self._run(pixel_values, cls_only=True)
+    def cls_features(self, pixel_values: torch.Tensor, aug: Optional[VideoAug] = None) -> torch.Tensor:
+        return self._run(pixel_values, cls_only=True, aug=aug)

@@ -21,6 +21,9 @@ models fetched by name.  All three have native, frozen, forward-only forms on th
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
+``VideoEncoder.forward`` also takes decoded frames, uint8 ``(B, frames, Hs, Ws, 3)`` of any size, with an optional
+``video_aug`` (``mmfusion.prep.VideoAug``): the native ViT resizes them straight into its patch matrix, any other backbone
+receives ``mmfusion.prep.prepare_video``'s f32 tensor at ``config.video_frame_size``, read as (height, width).
 The video BiLSTM (reference :183-190,233) runs on the HIP path too (``mmfusion.lstm_ops``: grouped MFMA GEMMs for the
 input projections, one persistent launch per layer for the 30 sequential steps of both directions); the
 ``torch.nn.LSTM`` module is only the parameter container (state_dict keys ``temporal_lstm.weight_ih_l0`` ...).
@@ -35,7 +38,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from mmfusion import ops
+from mmfusion import ops, prep
 from mmfusion.deberta import NativeDeberta
 from mmfusion.ops import AttnSpec, W
 from mmfusion.vit import NativeViT
@@ -219,10 +222,22 @@ class VideoEncoder(_FusionBase):
         self.projection = nn.Linear(self.hidden_size, config.fusion_hidden_size)
         self.dropout = nn.Dropout(config.fusion_dropout)
 
-    def forward(self, video_frames, use_adapter: bool = False) -> Dict[str, torch.Tensor]:
+    def forward(self, video_frames, use_adapter: bool = False, video_aug=None) -> Dict[str, torch.Tensor]:
         if self.vit is None:                         # feature mode: (B, frames, hidden) CLS features
             frame_features = video_frames
+        elif video_frames.dtype == torch.uint8:      # decoded frames (B, frames, Hs, Ws, 3): prepared on the device (mmfusion/prep.py)
+            B, n, hs, wsrc, c = video_frames.shape
+            flat, aug = video_frames.reshape(-1, hs, wsrc, c), video_aug if video_aug is not None else prep.VideoAug()
+            if self._cls_route:                      # straight into the ViT's patch matrix
+                cls = _run_backbone(self.vit.cls_features, True, flat, aug=aug)
+            else:
+                pixels = prep.prepare_video(flat, self.config.video_frame_size, bgr=aug.bgr, live=aug.live,
+                                            brightness=aug.brightness, flip=aug.flip)
+                cls = self.vit(pixel_values=pixels).last_hidden_state[:, 0]
+            frame_features = cls.view(B, n, -1)
         else:
+            if video_aug is not None:
+                raise ValueError("VideoEncoder: video_aug goes with uint8 (B, frames, Hs, Ws, 3) frames")
             B, n, c, h, w = video_frames.shape
             if self._cls_route:
                 cls = _run_backbone(self.vit.cls_features, True, video_frames.reshape(-1, c, h, w))
