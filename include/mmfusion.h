@@ -76,7 +76,22 @@ enum {
   /* mmf_gemm_grouped_ex only: after ReLU, zero each element with probability extra->dropout_p and scale
    * the kept ones by 1/(1-p) (nn.Dropout in training mode, reference models/fusion_layers.py:198);
    * the mask is a stateless hash of (*extra->rng_state, extra->site, problem index, m*N+n). */
-  MMF_EPI_DROPOUT = 64
+  MMF_EPI_DROPOUT = 64,
+  /* The ReLU / dropout keep-mask as one bit per element instead of the activation tensor (generation 7 only; ask
+   * mmf_gemm_relu_bits_available first: a launch that would go to generation 6 or 2 is refused with MMF_E_UNSUPPORTED).
+   * `aux` of each problem points to its bit buffer of mmf_gemm_relu_bits_bytes(M, N) bytes; ldaux is ignored.
+   *   MMF_EPI_RELU_BITS  with MMF_EPI_RELU (with or without MMF_EPI_BIAS / MMF_EPI_DROPOUT; bf16 output): the launch also
+   *                      WRITES the bits: a bit is 1 exactly when the bf16 value stored to C is > 0 (so 0 for a positive
+   *                      accumulator that rounds to zero, for a unit dropout zeroed, for NaN; 1 for +inf).
+   *   MMF_EPI_MASK_BITS  instead of MMF_EPI_MASK_AUX: v = bit ? v * alpha : 0, bit-equal to MMF_EPI_MASK_AUX on the
+   *                      activation tensor the bits were taken from.
+   * Layout, keyed by the problem's own 32 x 32 blocks and nothing of the launch (tile width, walk): the buffer is an array of
+   * uint16_t [ceil(M / 32)][ceil(N / 32)][64]; the word of block (bm, bn) at index 32 * h + r holds row 32 * bm + r, and its bit
+   * 2 * g + e / 2 + 8 * (e % 2) (g, e in 0..3) is column 32 * bn + 8 * g + 4 * h + e: even columns in the low byte, odd ones in the
+   * high byte.  In other words element (m, n) is bit 2 * ((n % 32) / 8) + (n % 4) / 2 + 8 * (n % 2) of word
+   * [m / 32][n / 32][32 * ((n / 4) % 2) + m % 32].  Bits of rows >= M or columns >= N of an edge block hold nothing. */
+  MMF_EPI_RELU_BITS = 128,
+  MMF_EPI_MASK_BITS = 256
 };
 
 typedef struct mmf_gemm_problem {
@@ -103,6 +118,13 @@ typedef struct mmf_gemm_extra {
 } mmf_gemm_extra;
 int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue,
                         int out_f32, const mmf_gemm_extra* extra, void* stream);
+/* bytes of the bit buffer of an M x N problem (MMF_EPI_RELU_BITS / MMF_EPI_MASK_BITS): rows and columns rounded up to 32 */
+size_t mmf_gemm_relu_bits_bytes(int M, int N);
+/* 1 when mmf_gemm_grouped_ex with exactly these arguments (epilogue holding MMF_EPI_RELU_BITS or MMF_EPI_MASK_BITS) would run on
+ * generation 7 under the current kernel selection, else 0; host only, launches nothing.  Callers decide per launch: where it is 0
+ * they launch the form without the bits (MMF_EPI_MASK_AUX on the activation tensor). */
+int mmf_gemm_relu_bits_available(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue,
+                                 int out_f32, const mmf_gemm_extra* extra);
 
 /* Tuning hook: which kernel mmf_gemm_grouped dispatches to.  0 = automatic [default]; 2 = LDS-DMA ring 256x128; 6 = 256x256 on
  * one wave per SIMD with 128x128 wave tiles [gemm6.hip: any K for TN, K % 32 == 0 for NT / NN, no aux epilogue with f32 output];
@@ -385,6 +407,35 @@ int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num_problems, 
  * target): 1-4 = the chunk form ln_*_kernel<NCH> (NCH 512-column chunks per row); 100 + 10 NV + H8 = the lane form
  * ln_*_lane_kernel<NV, H8> (d = 512 NV + 256 H8: 110 / 111 / 101 / 120 for d = 512 / 768 / 256 / 1024); 0 before any call. */
 int mmf_layernorm_last_form(void);
+
+/* norm2 of two blocks fused with the three-way sum that consumes them (models/fusion_layers.py:156-158 behind :209):
+ *   e = x + LN(pre_a; gamma_a, beta_a) + LN(pre_b; gamma_b, beta_b)
+ * in one pass over pre_a, pre_b and x.  Bit-equal to mmf_layernorm_fwd_grouped on (pre_a, pre_b) followed by mmf_add3_grouped on
+ * (x, y_a, y_b): each normalised value is rounded to bf16 where the stored tensor would have been, then the sum is formed in f32
+ * left to right and rounded once; the statistics are the ones the separate forward writes, and mmf_layernorm_bwd_grouped takes them.
+ * The kernel is the lane form (d = 256, 512, 768, 1024; any other d is MMF_E_SHAPE).  The separate forward reduces a row in another
+ * order in its chunk form, which it takes for small launches: mmf_layernorm2_add3_available(rows of each sum, num_problems, d) is 1
+ * exactly when d is a lane width AND mmf_layernorm_fwd_grouped over the 2 num_problems problems (pre_a, pre_b of every sum) would
+ * take the lane form, i.e. when this launch is bit-equal to the two it replaces; where it is 0 the caller composes the two launches.
+ * Does not change mmf_layernorm_last_form. */
+#define MMF_LN2_ADD3_MAX_PROBLEMS 4
+typedef struct mmf_ln2_add3_problem {
+  const void* x;          /* bf16 [rows][d] */
+  const void* pre_a;      /* bf16 [rows][d] */
+  const float* gamma_a;   /* f32 [d] */
+  const float* beta_a;
+  const void* pre_b;
+  const float* gamma_b;
+  const float* beta_b;
+  void* e;                /* bf16 [rows][d] out */
+  float* mean_a;          /* f32 [rows] out */
+  float* rstd_a;
+  float* mean_b;
+  float* rstd_b;
+  int32_t rows;
+} mmf_ln2_add3_problem;
+int mmf_layernorm2_add3_available(const int32_t* rows, int num_problems, int d);
+int mmf_layernorm2_add3_fwd_grouped(const mmf_ln2_add3_problem* problems, int num_problems, int d, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Streaming helpers (HBM-bound, 16-byte vector accesses)

@@ -56,6 +56,36 @@ extern "C" int mmf_gemm_select_impl(int impl) {
   return MMF_OK;
 }
 
+// the kernel generation a launch goes to: the pinned or automatic choice, falling back 7 -> 6 -> 2 to one that takes it
+static int select_impl(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue, int out_f32, const mmf_gemm_extra* extra) {
+  int impl = gemm_impl();
+  const bool pinned = impl != 0;
+  if (impl == 0) impl = auto_impl(problems, num_problems, layout);
+  const bool ok6 = mmf_gemm6_supports(problems, num_problems, layout) && mmf_gemm6_supports_epi(epilogue, out_f32);
+  if (impl == 6 && !pinned && mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 7;
+  if (impl == 7 && !mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 6;
+  if (impl == 6 && !ok6) impl = 2;
+  return impl;
+}
+
+constexpr int EPI_BITS = MMF_EPI_RELU_BITS | MMF_EPI_MASK_BITS;
+// the flag combinations the bit forms allow (whether generation 7 instantiates the set is mmf_gemm7_supports's answer)
+static bool bits_flags_ok(int epilogue) {
+  if ((epilogue & EPI_BITS) == EPI_BITS || (epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX))) return false;   // one owner of aux
+  return (epilogue & MMF_EPI_RELU_BITS) ? (epilogue & MMF_EPI_RELU) != 0 : true;
+}
+
+extern "C" size_t mmf_gemm_relu_bits_bytes(int M, int N) {
+  if (M <= 0 || N <= 0) return 0;
+  return (size_t)((M + 31) / 32) * (size_t)((N + 31) / 32) * 64 * sizeof(uint16_t);
+}
+
+extern "C" int mmf_gemm_relu_bits_available(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue,
+                                            int out_f32, const mmf_gemm_extra* extra) {
+  if (!problems || num_problems <= 0 || num_problems > MMF_GEMM_MAX_PROBLEMS || !(epilogue & EPI_BITS) || !bits_flags_ok(epilogue)) return 0;
+  return select_impl(problems, num_problems, layout, epilogue, out_f32, extra) == 7;
+}
+
 extern "C" int mmf_gemm_grouped(const mmf_gemm_problem* problems, int num_problems, int layout,
                                 int epilogue, int out_f32, void* stream) {
   return mmf_gemm_grouped_ex(problems, num_problems, layout, epilogue, out_f32, nullptr, stream);
@@ -74,17 +104,16 @@ extern "C" int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_pro
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: MASK_AUX and ADD_AUX are exclusive");
   if ((epilogue & MMF_EPI_COLSUM_A) && (layout != MMF_GEMM_TN || (epilogue & MMF_EPI_BIAS)))
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: COLSUM_A is a TN (wgrad) epilogue and excludes BIAS");
+  if ((epilogue & EPI_BITS) && !bits_flags_ok(epilogue))
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: RELU_BITS needs RELU; RELU_BITS, MASK_BITS, MASK_AUX and ADD_AUX are exclusive (one aux pointer)");
   if (epilogue & MMF_EPI_DROPOUT) {
     if (!extra || !extra->rng_state || !(extra->dropout_p >= 0.f) || extra->dropout_p >= 1.f)
       MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped_ex: MMF_EPI_DROPOUT needs rng_state and 0 <= p < 1");
   }
-  int impl = gemm_impl();
-  const bool pinned = impl != 0;
-  if (impl == 0) impl = auto_impl(problems, num_problems, layout);
-  const bool ok6 = mmf_gemm6_supports(problems, num_problems, layout) && mmf_gemm6_supports_epi(epilogue, out_f32);
-  if (impl == 6 && !pinned && mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 7;
-  if (impl == 7 && !mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra)) impl = 6;
-  if (impl == 6 && !ok6) impl = 2;
+  const int impl = select_impl(problems, num_problems, layout, epilogue, out_f32, extra);
+  if ((epilogue & EPI_BITS) && impl != 7)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: RELU_BITS / MASK_BITS exist in generation 7 only and this launch goes to generation %d "
+             "(mmf_gemm_relu_bits_available)", impl);
   t_last_impl = impl;
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[i];
@@ -92,7 +121,7 @@ extern "C" int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_pro
       MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: empty problem M=%d N=%d K=%d", i, p.M, p.N, p.K);
     if (!p.A || !p.B || !p.C) MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: null operand", i);
     if ((epilogue & (MMF_EPI_BIAS | MMF_EPI_COLSUM_A)) && !p.bias) MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: bias is null", i);
-    if ((epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX)) && !p.aux)
+    if ((epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX | EPI_BITS)) && !p.aux)
       MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: aux is null", i);
     // the contiguous extent of each operand must be a multiple of 8 elements (16-B vector loads)
     const int a_cols = (layout == MMF_GEMM_TN) ? p.M : p.K;

@@ -79,6 +79,20 @@ __device__ __forceinline__ void locate_tile(const GemmArgs& args, const int tota
   s.KT = P.K / BK;
 }
 
+// ---- the ReLU / dropout keep-mask as bits (drain_tile: MMF_EPI_RELU_BITS writes them, MMF_EPI_MASK_BITS applies them) ---------------
+// NOT (x > 0) of the two bf16 halves of w, 0 / 1 per half, in three packed 16-bit operations: as a bit pattern x > 0 is
+// 1 <= x <= 0x7f80 (+inf), that is x - 1 (wrapping: 0 -> 0xffff) < 0x7f80, that is bit 15 of the saturating (x - 1) + 0x80 clear.
+// Exact for every pattern (zeros, negatives and NaNs of either sign are not positive), as bf16lo(w) > 0.f is.
+__device__ __forceinline__ unsigned bf16x2_not_positive(unsigned w) {
+  typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+  const u16x2_t y = __builtin_bit_cast(u16x2_t, w) - (u16x2_t){1, 1};
+  const u16x2_t z = __builtin_elementwise_add_sat(y, (u16x2_t){0x80, 0x80});
+  return __builtin_bit_cast(unsigned, (u16x2_t)(z >> 15));
+}
+// bit of element e (0..3) of group g (0..3) in a lane's 16-bit word of a block: the low byte holds the even elements, the high byte
+// the odd ones (the halves of the packed words, gathered without unpacking them)
+__device__ __forceinline__ constexpr int keep_bit(int g, int e) { return 2 * g + (e >> 1) + 8 * (e & 1); }
+
 // ---- the tile's outputs through LDS -----------------------------------------------------------------------------------------------
 // The accumulator layout puts a ROW on each lane: stored from there, one 16-byte store instruction touches 32 rows x 32 B (32 cache
 // lines, a quarter of each), and the CU's store path takes ~64 cycles for it: 17.5 B/clk/CU, 7,500 cycles for the 128 KiB of a tile
@@ -95,15 +109,22 @@ __device__ __forceinline__ void locate_tile(const GemmArgs& args, const int tota
 // CT: the epilogue's flag set (compile time; alpha = 1, no dropout).  The bias is not added here: it is what the tile's accumulators
 // START from (bias_init below).  TN = 3: the wave tile is 96 columns, 12 of a row's 16 chunks; the lanes of chunks 12..15 get the
 // out-of-range offset (their aux loads read zeros into region chunks nobody reads back, their stores are dropped).
+// The keep-mask as bits (MMF_EPI_RELU_BITS / MMF_EPI_MASK_BITS, layout in mmfusion.h): a lane's sixteen values of a 32 x 32 block
+// (tm, tn) are sixteen bits of ONE 16-bit word, and the block's 64 words lie together, so a wave writes or reads a block's bits
+// with one 128-byte access straight from / into the accumulator layout: no aux tile, no LDS round trip.  The words are indexed by
+// the PROBLEM's blocks (mb, nb are multiples of 32 at either tile width).  Range-checked like the rest: blocks past
+// ceil(M / 32) rows fall behind the buffer, block columns past ceil(N / 32) get the out-of-range offset.
 template <int CT, int TN>
 __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, const mmf_gemm_problem& P, const int mb, const int nb,
                                            f32x16_t (&acc)[TN][4], char* region, const int lane) {
   constexpr bool AUX = (CT & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX)) != 0;
   constexpr bool DROP = (CT & MMF_EPI_DROPOUT) != 0;
+  constexpr bool EMIT_BITS = (CT & MMF_EPI_RELU_BITS) != 0, MASK_BITS = (CT & MMF_EPI_MASK_BITS) != 0;
+  static_assert(!(AUX && (EMIT_BITS || MASK_BITS)) && !(EMIT_BITS && MASK_BITS), "aux is one of: a bf16 tile, bits written, bits read");
   // dropout on the (activated) outputs, the mask of gemm6's epilogue: element m * N + n of the caller's problem `orig[pi]`
   const unsigned drop_key = DROP ? mmf_rng_key(*args.rng_state, args.site, (unsigned)args.orig[pi]) : 0u;
   const float drop_scale = DROP ? 1.f / (1.f - (float)args.drop_thresh * (1.f / 4294967296.f)) : 1.f;
-  const float alpha = (CT & MMF_EPI_MASK_AUX) ? args.alpha : 1.f;            // 1 / (1 - p) of a dropout backward rides on the ReLU mask
+  const float alpha = (CT & (MMF_EPI_MASK_AUX | MMF_EPI_MASK_BITS)) ? args.alpha : 1.f;            // 1 / (1 - p) of a dropout backward rides on the ReLU mask
   const int r = lane & 31, h = lane >> 5, q = lane >> 4, cq = lane & 15;
   // region offsets: accumulator layout (8 bytes at chunk c = 4 tn + g, half h, of row r), whole-row layout (16-byte chunk cq of row 4 it + q)
   const unsigned wr_base = (unsigned)(r * 256 + 8 * h + 16 * (r & 15));
@@ -119,6 +140,23 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
   const unsigned c_off0 = col_ok ? (unsigned)(((long)(mb + q) * P.ldc + nb + 8 * cq) * 2) : 0x80000000u;
   const unsigned a_off0 = col_ok ? (unsigned)(((long)(mb + q) * P.ldaux + nb + 8 * cq) * 2) : 0x80000000u;
   const unsigned c_row4 = (unsigned)(4 * P.ldc * 2), a_row4 = (unsigned)(4 * P.ldaux * 2);
+
+  // bits: 128 bytes per 32 x 32 block of the problem, row-major over its blocks; this lane's word of block (tm, tn) of the wave tile
+  const int nb32 = (P.N + 31) >> 5;
+  const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>((EMIT_BITS || MASK_BITS) ? P.aux : P.C), 0,
+      (EMIT_BITS || MASK_BITS) ? ((P.M + 31) >> 5) * nb32 * 128 : 0, 0x00020000);
+  auto bits_off = [&](int tm, int tn) {
+    const int bn = (nb >> 5) + tn;
+    return bn < nb32 ? (unsigned)((((mb >> 5) + tm) * nb32 + bn) * 128 + 2 * lane) : 0x80000000u;
+  };
+  unsigned keep[TN][4];                                       // MASK_BITS: the whole wave tile's words, loaded at the head of the drain
+  if constexpr (MASK_BITS) {
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+        keep[tn][tm] = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(brs, bits_off(tm, tn), 0, 0);
+  }
 
   u32x4_t auxr[2][8];
   auto load_aux = [&](int tm, int slot) {
@@ -148,6 +186,7 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
       // (the tile passes through an opaque statement HERE: its sixteen accumulator reads cannot be hoisted to the head of the drain,
       // where hipcc otherwise reads 160-250 accumulator registers into vector registers at once and spills the aux pieces in flight)
       asm volatile("" : "+a"(acc[tn][tm]));
+      unsigned npos = 0;                                       // EMIT_BITS: NOT (stored bf16 value > 0); bit 2 g + i of each half: word i of group g
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4_t v = {acc[tn][tm][4 * g], acc[tn][tm][4 * g + 1], acc[tn][tm][4 * g + 2], acc[tn][tm][4 * g + 3]};
@@ -170,8 +209,23 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
             v[0] += a0; v[1] += a1; v[2] += a2; v[3] += a3;
           }
         }
-        *reinterpret_cast<u32x2_t*>(acc_at(4 * tn + g)) = u32x2_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+        if constexpr (MASK_BITS) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {                         // bit ? v * alpha : +0, the bit spread over the word as a mask
+            // (as a statement the compiler cannot read: it turns every C form of this mask into and + compare + select, a
+            // third more vector instructions per element than the aux form it replaces)
+            int m;                                              // 0 / all ones
+            asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(keep[tn][tm]), "s"(keep_bit(g, e)));
+            v[e] = __uint_as_float(__float_as_uint(v[e] * alpha) & (unsigned)m);
+          }
+        }
+        const u32x2_t w = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+        if constexpr (EMIT_BITS) {                             // from the packed value: the predicate MASK_AUX applies to the stored tensor
+          npos |= bf16x2_not_positive(w[0]) << (2 * g) | bf16x2_not_positive(w[1]) << (2 * g + 1);
+        }
+        *reinterpret_cast<u32x2_t*>(acc_at(4 * tn + g)) = w;
       }
+      if constexpr (EMIT_BITS) __builtin_amdgcn_raw_buffer_store_b16((short)~((npos & 0xffu) | (npos >> 8)), brs, bits_off(tm, tn), 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
     u32x4_t w[8];
@@ -524,9 +578,16 @@ bool launch7_select(int layout, int eflags, const GemmArgs* a, int total, int gr
       if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s);
       return true;
     }
+    // the ReLU forms that also write the keep-mask as bits (FFN hidden layer of a forward that will be differentiated)
+    constexpr int RB = MMF_EPI_RELU | MMF_EPI_RELU_BITS;
+    if (eflags == RB)                                     { if (a) launch7<false, RB>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == (RB | MMF_EPI_BIAS))                    { if (a) launch7<false, RB | MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == (RB | MMF_EPI_DROPOUT))                 { if (a) launch7<false, RB | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == (RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT))  { if (a) launch7<false, RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s); return true; }
   } else if (layout == MMF_GEMM_NN) {
     if (eflags == 0)                                      { if (a) launch7<true, 0>(*a, total, grid, tile_n, s); return true; }
     if (eflags == MMF_EPI_MASK_AUX)                       { if (a) launch7<true, MMF_EPI_MASK_AUX>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == MMF_EPI_MASK_BITS)                      { if (a) launch7<true, MMF_EPI_MASK_BITS>(*a, total, grid, tile_n, s); return true; }
     if (eflags == MMF_EPI_ADD_AUX)                        { if (a) launch7<true, MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
   }
   return false;
@@ -617,11 +678,13 @@ extern "C" int mmf_gemm7_tile_n(const mmf_gemm_problem* problems, int num_proble
 // whether the persistent kernel can take this launch (gemm.hip asks before selecting it)
 bool mmf_gemm7_supports(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue, int out_f32, const mmf_gemm_extra* extra) {
   if (out_f32 || !launch7_select(layout, epilogue, nullptr, 0, 0, nullptr)) return false;
-  if (extra && extra->alpha != 1.f && !(layout == MMF_GEMM_NN && epilogue == MMF_EPI_MASK_AUX)) return false;   // alpha rides on the mask only
+  if (extra && extra->alpha != 1.f && !(layout == MMF_GEMM_NN && (epilogue == MMF_EPI_MASK_AUX || epilogue == MMF_EPI_MASK_BITS))) return false;   // alpha rides on the mask only
+  const bool bits = (epilogue & (MMF_EPI_RELU_BITS | MMF_EPI_MASK_BITS)) != 0;      // aux is a bit buffer: no ldaux
   if ((epilogue & MMF_EPI_DROPOUT) && !(extra && extra->rng_state)) return false;
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[i];
-    if (p.K % BK || p.K < (NS + 1) * BK || (p.N & 7) || (p.ldc & 7) || (p.aux && ((p.ldaux & 7) || !mmf_aligned16(p.aux)))) return false;
+    if (p.K % BK || p.K < (NS + 1) * BK || (p.N & 7) || (p.ldc & 7) || (p.aux && ((!bits && (p.ldaux & 7)) || !mmf_aligned16(p.aux)))) return false;
+    if (bits && !p.aux) return false;
   }
   return true;
 }
@@ -648,7 +711,8 @@ int mmf_gemm7_launch(const mmf_gemm_problem* problems, int num_problems, int lay
     const mmf_gemm_problem& p = problems[order[i]];
     const size_t a_bytes = (size_t)p.M * p.lda * 2;
     const size_t b_bytes = (size_t)(layout == MMF_GEMM_NT ? p.N : p.K) * p.ldb * 2;
-    const size_t c_bytes = (size_t)p.M * p.ldc * 2, x_bytes = p.aux ? (size_t)p.M * p.ldaux * 2 : 0;
+    const bool bits = (epilogue & (MMF_EPI_RELU_BITS | MMF_EPI_MASK_BITS)) != 0;
+    const size_t c_bytes = (size_t)p.M * p.ldc * 2, x_bytes = bits ? mmf_gemm_relu_bits_bytes(p.M, p.N) : p.aux ? (size_t)p.M * p.ldaux * 2 : 0;
     if (a_bytes >= 0x7fffffffull || b_bytes >= 0x7fffffffull || c_bytes >= 0x7fffffffull || x_bytes >= 0x7fffffffull)
       MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped[%d]: operand larger than 2 GiB", i);
     a.tile_start[i] = total;

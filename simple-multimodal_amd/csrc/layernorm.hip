@@ -145,6 +145,38 @@ struct LaneCols {
   }
 };
 
+// One row of the lane-form forward: a lane's share r of the row -> its normalised, scaled and shifted values o (f32, not yet
+// rounded) and the row's statistics.  ln_fwd_lane_kernel and ln2_add3_lane_kernel both normalise through this one routine and must
+// agree bit for bit, so which products are fused into the additions behind them is WRITTEN here and not left to the compiler
+// (contraction is off in this function): left alone it chose differently in the two kernels — the squares of the variance sum fused
+// in one and not in the other — and rstd differed in its last bit.  The choices are the ones the forward kernel was compiled to
+// before the routine was shared: squares rounded, then added; variance * (1 / d) + eps and gamma * (x hat) + beta as one fma each.
+template <class LC>
+__device__ __forceinline__ void ln_lane_row(const typename LC::Bf16& r, const float (&gam)[LC::EP], const float (&bet)[LC::EP],
+                                            const float inv_d, const float eps, float (&o)[LC::EP], float& mean, float& rstd) {
+#pragma clang fp contract(off)
+  constexpr int EP = LC::EP;
+  float v[EP];
+  LC::unpack(r, v);
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < EP; ++e) s += v[e];
+  mean = wave_sum(s) * inv_d;
+  float q = 0.f;
+#pragma unroll
+  for (int e = 0; e < EP; ++e) {
+    v[e] -= mean;
+    const float sq = v[e] * v[e];
+    q += sq;
+  }
+  rstd = rsqrtf(__builtin_fmaf(wave_sum(q), inv_d, eps));
+#pragma unroll
+  for (int e = 0; e < EP; ++e) {
+    const float xh = v[e] * rstd;
+    o[e] = __builtin_fmaf(gam[e], xh, bet[e]);
+  }
+}
+
 // Round 3: the forward in the lane form of ln_bwd_lane_kernel below (columns as LaneCols deals them; gamma / beta in registers
 // instead of 6 KB of L2 reads per row; a workgroup's waves walk strided rows with the next row's load in flight).
 template <int NV, int H8>
@@ -168,21 +200,73 @@ void ln_fwd_lane_kernel(const LnArgs a) {
   for (; row < P.rows; row += step) {
     const bool more = row + step < P.rows;
     if (more) fetch(row + step, nxt);
-    float v[EP];
-    LC::unpack(cur, v);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < EP; ++e) s += v[e];
-    const float mean = wave_sum(s) * inv_d;
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < EP; ++e) { v[e] -= mean; q += v[e] * v[e]; }
-    const float rstd = rsqrtf(wave_sum(q) * inv_d + a.eps);
-    float o[EP];
-#pragma unroll
-    for (int e = 0; e < EP; ++e) o[e] = v[e] * rstd * gam[e] + bet[e];
+    float o[EP], mean, rstd;
+    ln_lane_row<LC>(cur, gam, bet, inv_d, a.eps, o, mean, rstd);
     LC::store(static_cast<unsigned short*>(P.y) + (size_t)row * d, lane, o);
     if (lane == 0) { P.mean[row] = mean; P.rstd[row] = rstd; }
+    if (more) cur = nxt;
+  }
+}
+
+// norm2 of two cross-modal blocks and the three-way modality sum behind them in one pass: e = x + LN_a(pre_a) + LN_b(pre_b), the
+// rows of pre_a / pre_b normalised by ln_lane_row, each normalised value rounded to bf16 as the tensor ln_fwd_lane_kernel stores
+// would hold it, then summed as add3_grouped_kernel sums (x, y_a, y_b): f32, left to right, rounded once.  The two normalised
+// tensors (written, then read again by the sum: half the bytes of the two-kernel form) never reach memory; the statistics do, the
+// backward works from pre_a / pre_b and them.  Rows are walked as in ln_fwd_lane_kernel, with the next row's three loads in flight.
+struct Ln2Add3Args {
+  int nprob;
+  float eps;
+  int blk_start[MMF_LN2_ADD3_MAX_PROBLEMS + 1];
+  mmf_ln2_add3_problem p[MMF_LN2_ADD3_MAX_PROBLEMS];
+};
+
+template <int NV, int H8>
+__global__ __launch_bounds__(256)
+void ln2_add3_lane_kernel(const Ln2Add3Args a) {
+  using LC = LaneCols<NV, H8>;
+  constexpr int EP = LC::EP, d = LC::D;
+  const int pi = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
+  const mmf_ln2_add3_problem& P = a.p[pi];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nblk = a.blk_start[pi + 1] - a.blk_start[pi];
+  const float inv_d = 1.f / (float)d;
+  float gam_a[EP], bet_a[EP], gam_b[EP], bet_b[EP];
+  LC::load_f32(P.gamma_a, lane, gam_a);
+  LC::load_f32(P.beta_a, lane, bet_a);
+  LC::load_f32(P.gamma_b, lane, gam_b);
+  LC::load_f32(P.beta_b, lane, bet_b);
+  struct Row { typename LC::Bf16 x, pa, pb; };
+  auto fetch = [&](int row, Row& r) {
+    LC::load(static_cast<const unsigned short*>(P.pre_a) + (size_t)row * d, lane, r.pa);
+    LC::load(static_cast<const unsigned short*>(P.pre_b) + (size_t)row * d, lane, r.pb);
+    LC::load(static_cast<const unsigned short*>(P.x) + (size_t)row * d, lane, r.x);
+  };
+  // the bf16 the forward LayerNorm would have stored, as f32 (pairs as LaneCols::store packs them)
+  auto round_bf16 = [](float (&y)[EP]) {
+#pragma unroll
+    for (int e = 0; e < EP; e += 2) {
+      const unsigned w = pack_bf16x2(y[e], y[e + 1]);
+      y[e] = bf16lo(w);
+      y[e + 1] = bf16hi(w);
+    }
+  };
+  const int step = nblk * ROWS_PER_BLOCK;
+  int row = ((int)blockIdx.x - a.blk_start[pi]) * ROWS_PER_BLOCK + wave;
+  Row cur, nxt;
+  if (row < P.rows) fetch(row, cur);
+  for (; row < P.rows; row += step) {
+    const bool more = row + step < P.rows;
+    if (more) fetch(row + step, nxt);
+    float ya[EP], yb[EP], xv[EP], mean_a, rstd_a, mean_b, rstd_b;
+    ln_lane_row<LC>(cur.pa, gam_a, bet_a, inv_d, a.eps, ya, mean_a, rstd_a);
+    ln_lane_row<LC>(cur.pb, gam_b, bet_b, inv_d, a.eps, yb, mean_b, rstd_b);
+    round_bf16(ya);
+    round_bf16(yb);
+    LC::unpack(cur.x, xv);
+#pragma unroll
+    for (int e = 0; e < EP; ++e) xv[e] = xv[e] + ya[e] + yb[e];
+    LC::store(static_cast<unsigned short*>(P.e) + (size_t)row * d, lane, xv);
+    if (lane == 0) { P.mean_a[row] = mean_a; P.rstd_a[row] = rstd_a; P.mean_b[row] = mean_b; P.rstd_b[row] = rstd_b; }
     if (more) cur = nxt;
   }
 }
@@ -401,10 +485,11 @@ using LnKernel = void (*)(const LnArgs);
 const LnKernel CHUNK_FWD[MAX_CH] = {ln_fwd_kernel<1>, ln_fwd_kernel<2>, ln_fwd_kernel<3>, ln_fwd_kernel<4>};
 const LnKernel CHUNK_BWD[MAX_CH] = {ln_bwd_kernel<1>, ln_bwd_kernel<2>, ln_bwd_kernel<3>, ln_bwd_kernel<4>};
 // lane form: the widths d = 512 NV + 256 H8 it is instantiated for
-struct LaneWidth { int d, form; LnKernel fwd, bwd; };   // form id: 100 + 10 NV + H8
+using Ln2Add3Kernel = void (*)(const Ln2Add3Args);
+struct LaneWidth { int d, form; LnKernel fwd, bwd; Ln2Add3Kernel fwd2_add3; };   // form id: 100 + 10 NV + H8
 template <int NV, int H8>
 constexpr LaneWidth lane_width_of() {
-  return {LaneCols<NV, H8>::D, 100 + 10 * NV + H8, ln_fwd_lane_kernel<NV, H8>, ln_bwd_lane_kernel<NV, H8>};
+  return {LaneCols<NV, H8>::D, 100 + 10 * NV + H8, ln_fwd_lane_kernel<NV, H8>, ln_bwd_lane_kernel<NV, H8>, ln2_add3_lane_kernel<NV, H8>};
 }
 const LaneWidth LANE_WIDTHS[] = {lane_width_of<0, 1>(), lane_width_of<1, 0>(), lane_width_of<1, 1>(), lane_width_of<2, 0>()};
 const LaneWidth* lane_width(int d) {                   // null: d is no lane width
@@ -420,9 +505,17 @@ int check_common(const char* who, const mmf_ln_problem* p, int n, int d) {
 
 int full_blocks(int rows) { return (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK; }
 
+// The forward's choice of form for a launch of total_rows rows in `total` one-per-ROWS_PER_BLOCK workgroups: the lane form where
+// that would be more workgroups than the budget (a bounded number of them then walk strided rows); else (any other width, or a
+// small launch) the chunk form.  The two forms reduce a row in different orders, so what must match the forward bit for bit
+// (mmf_layernorm2_add3_available) asks here as well.
+int fwd_budget(long long total_rows) { return total_rows > FWD_LARGE_ROWS ? FWD_BLOCKS_LARGE : FWD_BLOCKS; }
+bool fwd_takes_lane_form(const LaneWidth* lw, int total, long long total_rows) { return lw && total > fwd_budget(total_rows); }
+
 // A budget of workgroups shared out over the problems in proportion to their rows: at least one each, at most one per
 // ROWS_PER_BLOCK rows (so at most budget + num_problems in all).  Fills a.blk_start and returns the total.
-int share_blocks(LnArgs& a, const mmf_ln_problem* problems, int num_problems, int budget) {
+template <class Args, class Problem>
+int share_blocks(Args& a, const Problem* problems, int num_problems, int budget) {
   long long total_rows = 0;
   for (int i = 0; i < num_problems; ++i) total_rows += problems[i].rows;
   int total = 0;
@@ -459,12 +552,9 @@ extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num
   }
   a.blk_start[num_problems] = total;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // lane form where one workgroup per ROWS_PER_BLOCK rows would be more than the budget: a bounded number of workgroups walking
-  // strided rows; else (any other width, or a small launch) the chunk form
-  const int budget = total_rows > FWD_LARGE_ROWS ? FWD_BLOCKS_LARGE : FWD_BLOCKS;
   const LaneWidth* lw = lane_width(d);
-  if (lw && total > budget) {
-    total = share_blocks(a, problems, num_problems, budget);
+  if (fwd_takes_lane_form(lw, total, total_rows)) {
+    total = share_blocks(a, problems, num_problems, fwd_budget(total_rows));
     hipLaunchKernelGGL(lw->fwd, dim3(total), dim3(256), 0, s, a);
     t_last_form = lw->form;
     MMF_CHECK_LAUNCH("mmf_layernorm_fwd_grouped(lane)");
@@ -474,6 +564,42 @@ extern "C" int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num
   hipLaunchKernelGGL(CHUNK_FWD[nch - 1], dim3(total), dim3(256), 0, s, a);
   t_last_form = nch;
   MMF_CHECK_LAUNCH("mmf_layernorm_fwd_grouped");
+  return MMF_OK;
+}
+
+extern "C" int mmf_layernorm2_add3_available(const int32_t* rows, int num_problems, int d) {
+  if (!rows || num_problems <= 0 || num_problems > MMF_LN2_ADD3_MAX_PROBLEMS) return 0;
+  int total = 0;                                        // the forward launch over pre_a and pre_b of every sum
+  long long total_rows = 0;
+  for (int i = 0; i < num_problems; ++i) {
+    if (rows[i] <= 0) return 0;
+    total += 2 * full_blocks(rows[i]);
+    total_rows += 2LL * rows[i];
+  }
+  return fwd_takes_lane_form(lane_width(d), total, total_rows);
+}
+
+extern "C" int mmf_layernorm2_add3_fwd_grouped(const mmf_ln2_add3_problem* problems, int num_problems, int d, float eps, void* stream) {
+  const char* who = "mmf_layernorm2_add3_fwd_grouped";
+  if (!problems || num_problems <= 0 || num_problems > MMF_LN2_ADD3_MAX_PROBLEMS)
+    MMF_FAIL(MMF_E_SHAPE, "%s: num_problems=%d out of range", who, num_problems);
+  const LaneWidth* lw = lane_width(d);
+  if (!lw) MMF_FAIL(MMF_E_SHAPE, "%s: d=%d is no lane width: compose the two launches", who, d);
+  Ln2Add3Args a; a.nprob = num_problems; a.eps = eps;
+  for (int i = 0; i < num_problems; ++i) {
+    const mmf_ln2_add3_problem& p = problems[i];
+    if (p.rows <= 0 || !p.x || !p.pre_a || !p.pre_b || !p.e || !p.gamma_a || !p.beta_a || !p.gamma_b || !p.beta_b || !p.mean_a ||
+        !p.rstd_a || !p.mean_b || !p.rstd_b)
+      MMF_FAIL(MMF_E_SHAPE, "%s[%d]: null operand or rows=%d", who, i, p.rows);
+    if (!mmf_aligned16(p.x) || !mmf_aligned16(p.pre_a) || !mmf_aligned16(p.pre_b) || !mmf_aligned16(p.e) || !mmf_aligned16(p.gamma_a) ||
+        !mmf_aligned16(p.beta_a) || !mmf_aligned16(p.gamma_b) || !mmf_aligned16(p.beta_b))
+      MMF_FAIL(MMF_E_ALIGN, "%s[%d]: pointers must be 16-byte aligned", who, i);
+    a.p[i] = p;
+  }
+  // a row of this launch is three rows read: the workgroup budget of a plain forward of as many rows keeps as many bytes in flight
+  const int total = share_blocks(a, problems, num_problems, FWD_BLOCKS);
+  hipLaunchKernelGGL(lw->fwd2_add3, dim3(total), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  MMF_CHECK_LAUNCH(who);
   return MMF_OK;
 }
 

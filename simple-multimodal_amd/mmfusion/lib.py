@@ -17,16 +17,18 @@ LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmfusion.so
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_BIAS, EPI_RELU, EPI_MASK_AUX, EPI_ADD_AUX, EPI_ACCUM, EPI_COLSUM_A, EPI_DROPOUT = 1, 2, 4, 8, 16, 32, 64
+EPI_RELU_BITS, EPI_MASK_BITS = 128, 256      # the ReLU / dropout keep-mask as bits: written by the forward, read by the dgrad (aux = the bit buffer)
 GEMM_MAX_PROBLEMS, ATTN_MAX_PROBLEMS, LN_MAX_PROBLEMS, COLSUM_MAX_PROBLEMS = 48, 12, 8, 24
+LN2_ADD3_MAX_PROBLEMS = 4
 EVAL_MAX_HEADS, EVAL_NSUMS = 4, 4
 
 # every symbol include/mmfusion.h declares (tests check the .so exports all of them)
 SYMBOLS = (
-    "mmf_version", "mmf_last_error", "mmf_device_cu_count", "mmf_gemm_grouped", "mmf_gemm_grouped_ex", "mmf_gemm_select_impl", "mmf_gemm_last_impl", "mmf_gemm_set_persistent_workgroups",
+    "mmf_version", "mmf_last_error", "mmf_device_cu_count", "mmf_gemm_grouped", "mmf_gemm_grouped_ex", "mmf_gemm_relu_bits_bytes", "mmf_gemm_relu_bits_available", "mmf_gemm_select_impl", "mmf_gemm_last_impl", "mmf_gemm_set_persistent_workgroups",
     "mmf_gemm7_set_tile_n", "mmf_gemm7_last_tile_n", "mmf_gemm7_tile_n",
     "mmf_attn_fwd_grouped_ex", "mmf_attn_bwd_grouped_ex", "mmf_dropout", "mmf_attn_select_impl",
     "mmf_attn_fwd_grouped", "mmf_attn_bwd_grouped", "mmf_layernorm_fwd_grouped",
-    "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
+    "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_layernorm2_add3_available", "mmf_layernorm2_add3_fwd_grouped", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
     "mmf_meanpool_fwd", "mmf_meanpool_bwd", "mmf_meanpool_cat_fwd", "mmf_meanpool_cat_bwd", "mmf_colsum_bf16", "mmf_colsum_grouped", "mmf_relu_bwd_bf16", "mmf_relu_bwd_mixed",
     "mmf_sqnorm_f32", "mmf_adamw_step", "mmf_adamw_advance", "mmf_skinny_linear_fwd", "mmf_skinny_linear_dgrad", "mmf_skinny_linear_fwd_ex", "mmf_skinny_linear_dgrad_ex", "mmf_skinny_last_strip",
     "mmf_gat3_dense_fwd", "mmf_gat3_dense_bwd", "mmf_infonce_fwd", "mmf_infonce_bwd", "mmf_adaptive_combine_fwd",
@@ -62,6 +64,13 @@ class LnProblem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
                 ("mean", C.c_void_p), ("rstd", C.c_void_p), ("dy", C.c_void_p), ("dx", C.c_void_p),
                 ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("rows", C.c_int32)]
+
+
+class Ln2Add3Problem(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("pre_a", C.c_void_p), ("gamma_a", C.c_void_p), ("beta_a", C.c_void_p),
+                ("pre_b", C.c_void_p), ("gamma_b", C.c_void_p), ("beta_b", C.c_void_p), ("e", C.c_void_p),
+                ("mean_a", C.c_void_p), ("rstd_a", C.c_void_p), ("mean_b", C.c_void_p), ("rstd_b", C.c_void_p),
+                ("rows", C.c_int32)]
 
 
 class GemmExtra(C.Structure):
@@ -137,6 +146,9 @@ def load() -> C.CDLL:
     vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
     lib.mmf_gemm_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, i32, vp]
     lib.mmf_gemm_grouped_ex.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, i32, C.POINTER(GemmExtra), vp]
+    lib.mmf_gemm_relu_bits_bytes.argtypes = [i32, i32]
+    lib.mmf_gemm_relu_bits_bytes.restype = C.c_size_t
+    lib.mmf_gemm_relu_bits_available.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, i32, C.POINTER(GemmExtra)]
     lib.mmf_gemm7_tile_n.argtypes = [C.POINTER(GemmProblem), i32, i32]
     lib.mmf_attn_fwd_grouped_ex.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, vp]
     lib.mmf_attn_bwd_grouped_ex.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, vp]
@@ -148,6 +160,8 @@ def load() -> C.CDLL:
     lib.mmf_layernorm_bwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
     lib.mmf_layernorm_bwd_workspace_bytes.argtypes = [i32]
     lib.mmf_layernorm_bwd_workspace_bytes.restype = C.c_size_t
+    lib.mmf_layernorm2_add3_available.argtypes = [C.POINTER(C.c_int32), i32, i32]
+    lib.mmf_layernorm2_add3_fwd_grouped.argtypes = [C.POINTER(Ln2Add3Problem), i32, i32, f32, vp]
     lib.mmf_cast_f32_to_bf16.argtypes = [vp, vp, i64, vp]
     lib.mmf_cast_bf16_to_f32.argtypes = [vp, vp, i64, vp]
     lib.mmf_cast_bf16_to_f32_scaled.argtypes = [vp, vp, i64, f32, vp]
@@ -284,6 +298,15 @@ def gemm_grouped(problems: Sequence[GemmProblem], layout: int, epilogue: int, ou
             tm.label = f"gemm{load().mmf_gemm_last_impl()}_grouped_kernel<{_LAYOUT_NAME[layout]},{'f32' if out_f32 else 'bf16'}>"
 
 
+def gemm_relu_bits_available(problems: Sequence[GemmProblem], layout: int, epilogue: int, alpha: float = 1.0,
+                             dropout_p: float = 0.0, rng_state_ptr: Optional[int] = None, site: int = 0) -> bool:
+    """Whether ``gemm_grouped`` with these arguments (a bf16-output launch whose epilogue holds EPI_RELU_BITS or
+    EPI_MASK_BITS) would run on the persistent kernel, the only one with the bit forms.  Host only."""
+    arr = (GemmProblem * len(problems))(*problems)
+    ex = GemmExtra(alpha, dropout_p, rng_state_ptr, site)
+    return bool(load().mmf_gemm_relu_bits_available(arr, len(problems), layout, epilogue, 0, C.byref(ex)))
+
+
 def attn_fwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: float, dropout_p: float = 0.0,
                      rng_state_ptr: Optional[int] = None, site: int = 0) -> None:
     arr = (AttnProblem * len(problems))(*problems)
@@ -306,6 +329,18 @@ def attn_bwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: floa
 def layernorm_fwd_grouped(problems: Sequence[LnProblem], d: int, eps: float) -> None:
     arr = (LnProblem * len(problems))(*problems)
     check(load().mmf_layernorm_fwd_grouped(arr, len(problems), d, eps, stream_ptr()))
+
+
+def layernorm2_add3_available(rows: Sequence[int], d: int) -> bool:
+    """Whether the fused norm2 + three-way sum applies to sums of these row counts: d is a lane width and the separate
+    LayerNorm forward over the same rows would take the lane form too (the launch is then bit-equal to the two it replaces)."""
+    arr = (C.c_int32 * len(rows))(*rows)
+    return bool(load().mmf_layernorm2_add3_available(arr, len(rows), d))
+
+
+def layernorm2_add3_fwd_grouped(problems: Sequence[Ln2Add3Problem], d: int, eps: float) -> None:
+    arr = (Ln2Add3Problem * len(problems))(*problems)
+    check(load().mmf_layernorm2_add3_fwd_grouped(arr, len(problems), d, eps, stream_ptr()))
 
 
 def layernorm_bwd_grouped(problems: Sequence[LnProblem], d: int, workspace) -> None:

@@ -23,7 +23,7 @@ import torch
 
 from . import lib
 from .lib import (AttnProblem, GemmProblem, LnProblem, EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A,
-                  EPI_DROPOUT, EPI_MASK_AUX, EPI_RELU, GEMM_NN, GEMM_NT, GEMM_TN)
+                  EPI_DROPOUT, EPI_MASK_AUX, EPI_MASK_BITS, EPI_RELU, EPI_RELU_BITS, GEMM_NN, GEMM_NT, GEMM_TN)
 
 BF16 = torch.bfloat16
 
@@ -171,8 +171,10 @@ def _grad_bf16(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 
 def _gemm_problems(layout: int, probs: Sequence[tuple], epilogue: int, dtype, c_dtype) -> List[GemmProblem]:
     """One GemmProblem per (A, B, C, bias|None, aux|None): M, N from C, K from A.  A and B must be ``dtype``, every C
-    ``c_dtype``; the bias is f32, contiguous, [N] ([M] for the fused bias gradient); aux has C's shape."""
+    ``c_dtype``; the bias is f32, contiguous, [N] ([M] for the fused bias gradient); aux has C's shape — or, with
+    EPI_RELU_BITS / EPI_MASK_BITS, is the problem's bit buffer (``relu_bits_buffer``)."""
     ps: List[GemmProblem] = []
+    bits = bool(epilogue & (EPI_RELU_BITS | EPI_MASK_BITS))
     for (A, Bm, Cm, bias, aux) in probs:
         _req(A, dtype), _req(Bm, dtype)
         M, N = Cm.shape
@@ -180,15 +182,36 @@ def _gemm_problems(layout: int, probs: Sequence[tuple], epilogue: int, dtype, c_
         a_shape, b_shape = (K, M) if layout == GEMM_TN else (M, K), (N, K) if layout == GEMM_NT else (K, N)
         if A.shape != a_shape or Bm.shape != b_shape or Cm.dtype != c_dtype:
             raise ValueError(f"gemm layout {layout}: A{tuple(A.shape)} B{tuple(Bm.shape)} C{tuple(Cm.shape)} {Cm.dtype}")
-        if aux is not None and tuple(aux.shape) != (M, N):
+        if bits:
+            if aux is None or aux.dtype != torch.uint8 or not aux.is_contiguous() or aux.numel() < lib.load().mmf_gemm_relu_bits_bytes(M, N):
+                raise ValueError("the bit forms take a contiguous uint8 buffer of mmf_gemm_relu_bits_bytes(M, N) bytes as aux")
+        elif aux is not None and tuple(aux.shape) != (M, N):
             raise ValueError("aux must match C")
         if bias is not None:
             _req(bias, torch.float32)
             if bias.numel() != (M if epilogue & EPI_COLSUM_A else N) or not bias.is_contiguous():
                 raise ValueError("bias must be contiguous [N] ([M] for the fused bias gradient)")
         ps.append(GemmProblem(A.data_ptr(), Bm.data_ptr(), Cm.data_ptr(), _ptr(bias), _ptr(aux), M, N, K,
-                              _ld(A), _ld(Bm), _ld(Cm), _ld(aux) if aux is not None else 0))
+                              _ld(A), _ld(Bm), _ld(Cm), _ld(aux) if aux is not None and not bits else 0))
     return ps
+
+
+def relu_bits_buffer(h: torch.Tensor) -> torch.Tensor:
+    """The buffer of the keep-mask bits of an activation tensor of h's shape (layout: include/mmfusion.h, MMF_EPI_RELU_BITS)."""
+    return torch.empty(lib.load().mmf_gemm_relu_bits_bytes(*h.shape), dtype=torch.uint8, device=h.device)
+
+
+def relu_bits_available(layout: int, probs: Sequence[tuple], epilogue: int, alpha: float = 1.0,
+                        dropout: Optional[tuple] = None) -> bool:
+    """Whether ``gemm_group`` with these arguments, the epilogue holding EPI_RELU_BITS or EPI_MASK_BITS, is a launch the
+    library has the bit form for (one launch on the persistent kernel); the caller decides per launch and keeps
+    EPI_MASK_AUX on the activation tensor where it is not."""
+    if len(probs) > lib.GEMM_MAX_PROBLEMS or probs[0][2].dtype != BF16:
+        return False
+    ps = _gemm_problems(layout, probs, epilogue, BF16, BF16)
+    if dropout is not None:
+        return lib.gemm_relu_bits_available(ps, layout, epilogue | EPI_DROPOUT, alpha, dropout[0], rng_state().data_ptr(), dropout[1])
+    return lib.gemm_relu_bits_available(ps, layout, epilogue, alpha)
 
 
 def gemm(layout: int, A: torch.Tensor, Bm: torch.Tensor, C: torch.Tensor, *, bias=None, aux=None,
@@ -909,40 +932,50 @@ def linear(x: torch.Tensor, w: W, b: Optional[W] = None, relu: bool = False,
 # apply the ReLU mask and the residual-gradient add in the dgrad GEMM epilogues:
 #   dH = (dY W2) * (h > 0)        NN GEMM, MASK_AUX epilogue (aux = h)
 #   dX = dH W1 + dY               NN GEMM, ADD_AUX epilogue  (aux = dY)
+# h is M x 4d and the mask is all that dH wants of it: where both launches have the bit form (relu_bits_available), the
+# forward GEMM also writes (h > 0) as one bit per element (RELU_BITS) and dH reads those (MASK_BITS) instead of h.
 # --------------------------------------------------------------------------------------------
 class _GroupedFFN(torch.autograd.Function):
     """tensors = [x_0, W1_0, b1_0, W2_0, b2_0, x_1, ...] (parameters passed so autograd runs backward)."""
 
     @staticmethod
-    def forward(ctx, layers, drop, *tensors):
+    def forward(ctx, layers, drop, want_bits, *tensors):
         n = len(layers)
         xs = [tensors[5 * i] for i in range(n)]
         for x in xs:
             _req(x, BF16)
         hs = [torch.empty((x.shape[0], l1.weight.shape[0]), dtype=BF16, device=x.device) for x, (l1, _) in zip(xs, layers)]
         # h = dropout(relu(x W1^T + b1)) in one epilogue; dropped units are exactly 0 in h
-        gemm_group(GEMM_NT, [(x, shadow(l1.weight), h, l1.bias.detach(), None)
-                             for x, h, (l1, _) in zip(xs, hs, layers)], EPI_BIAS | EPI_RELU, dropout=drop)
+        bits = [relu_bits_buffer(h) for h in hs] if want_bits else [None] * n
+        ffn1 = [(x, shadow(l1.weight), h, l1.bias.detach(), b) for x, h, b, (l1, _) in zip(xs, hs, bits, layers)]
+        if want_bits and relu_bits_available(GEMM_NT, ffn1, EPI_BIAS | EPI_RELU | EPI_RELU_BITS, dropout=drop):
+            gemm_group(GEMM_NT, ffn1, EPI_BIAS | EPI_RELU | EPI_RELU_BITS, dropout=drop)
+        else:
+            bits = []
+            gemm_group(GEMM_NT, [q[:4] + (None,) for q in ffn1], EPI_BIAS | EPI_RELU, dropout=drop)
         ctx.keep_scale = 1.0 / (1.0 - drop[0]) if drop is not None else 1.0
         ys = [torch.empty_like(x) for x in xs]
         gemm_group(GEMM_NT, [(h, shadow(l2.weight), y, l2.bias.detach(), x)
                              for x, h, y, (_, l2) in zip(xs, hs, ys, layers)], EPI_BIAS | EPI_ADD_AUX)
         ctx.layers = layers
-        ctx.save_for_backward(*xs, *hs)
+        ctx.save_for_backward(*xs, *hs, *bits)
         return tuple(ys)
 
     @staticmethod
     def backward(ctx, *gys):
         layers = ctx.layers
         n = len(layers)
-        xs, hs = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        xs, hs, bits = ctx.saved_tensors[:n], ctx.saved_tensors[n:2 * n], ctx.saved_tensors[2 * n:]
         idx = [i for i, g in enumerate(gys) if g is not None]
         dys = {i: gys[i].contiguous() for i in idx}
         dhs = {i: torch.empty_like(hs[i]) for i in idx}
         dxs = {i: torch.empty_like(xs[i]) for i in idx}
         # (h > 0) is ReLU mask AND dropout mask at once; only the 1/(1-p) factor is left to apply
-        gemm_group(GEMM_NN, [(dys[i], shadow(layers[i][1].weight), dhs[i], None, hs[i]) for i in idx], EPI_MASK_AUX,
-                   alpha=ctx.keep_scale)
+        dh = [(dys[i], shadow(layers[i][1].weight), dhs[i], None, bits[i] if bits else hs[i]) for i in idx]
+        if bits and relu_bits_available(GEMM_NN, dh, EPI_MASK_BITS, alpha=ctx.keep_scale):
+            gemm_group(GEMM_NN, dh, EPI_MASK_BITS, alpha=ctx.keep_scale)
+        else:
+            gemm_group(GEMM_NN, [q[:4] + (hs[i],) for q, i in zip(dh, idx)], EPI_MASK_AUX, alpha=ctx.keep_scale)
         gemm_group(GEMM_NN, [(dhs[i], shadow(layers[i][0].weight), dxs[i], None, dys[i]) for i in idx], EPI_ADD_AUX)
         for i in idx:
             for l, dy_, x_ in ((layers[i][1], dys[i], hs[i]), (layers[i][0], dhs[i], xs[i])):
@@ -951,7 +984,7 @@ class _GroupedFFN(torch.autograd.Function):
         grads: List[Optional[torch.Tensor]] = [None] * (5 * n)
         for i in idx:
             grads[5 * i] = dxs[i]
-        return (None, None, *grads)
+        return (None, None, None, *grads)
 
 
 def ffn_residual_group(items: Sequence[tuple], dropout_p: float = 0.0) -> List[torch.Tensor]:
@@ -969,7 +1002,8 @@ def ffn_residual_group(items: Sequence[tuple], dropout_p: float = 0.0) -> List[t
         layers.append((l1, l2))
         tensors += [x, l1.weight, l1.bias, l2.weight, l2.bias]
     drop = (float(dropout_p), next_site()) if dropout_p > 0.0 else None
-    return list(_GroupedFFN.apply(layers, drop, *tensors))
+    want_bits = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)       # only a forward that will be differentiated
+    return list(_GroupedFFN.apply(layers, drop, want_bits, *tensors))
 
 
 # --------------------------------------------------------------------------------------------
@@ -1038,6 +1072,80 @@ def layernorm_group(items: Sequence[tuple], eps: float = 1e-5) -> List[torch.Ten
     for x, g, b in items:
         flat += [x, g, b]
     return list(_GroupedLayerNorm.apply(eps, *flat))
+
+
+class _GroupedLn2Add3(torch.autograd.Function):
+    """tensors = [x_0, pre_a_0, gamma_a_0, beta_a_0, pre_b_0, gamma_b_0, beta_b_0, x_1, ...]:
+    e_i = x_i + LN(pre_a_i) + LN(pre_b_i) in ONE launch, bit-equal to _GroupedLayerNorm over (pre_a_0, pre_b_0, pre_a_1, ...)
+    followed by _Add3Group.  Saves what _GroupedLayerNorm saves; the backward is its backward with the two problems of a sum
+    sharing the sum's gradient, which is also the gradient of x."""
+
+    @staticmethod
+    def forward(ctx, eps: float, *tensors):
+        n = len(tensors) // 7
+        d = tensors[0].shape[-1]
+        outs, stats, probs, keep = [], [], [], []
+        for i in range(n):
+            x, pa, ga, ba, pb, gb, bb = tensors[7 * i:7 * i + 7]
+            _req(x, BF16), _req(pa, BF16), _req(pb, BF16)
+            if x.shape != pa.shape or x.shape != pb.shape:
+                raise ValueError("ln2_add3 group: operands of one sum must have one shape")
+            x, pa, pb = x.contiguous(), pa.contiguous(), pb.contiguous()
+            keep += [x, pa, pb]
+            rows = x.numel() // d
+            e = torch.empty_like(x)
+            st = torch.empty((4, rows), dtype=torch.float32, device=x.device)      # mean_a, rstd_a, mean_b, rstd_b
+            probs.append(lib.Ln2Add3Problem(x.data_ptr(), pa.data_ptr(), ga.data_ptr(), ba.data_ptr(), pb.data_ptr(), gb.data_ptr(),
+                                            bb.data_ptr(), e.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(),
+                                            st[3].data_ptr(), rows))
+            outs.append(e), stats.append(st)
+        lib.layernorm2_add3_fwd_grouped(probs, d, eps)
+        ctx.n, ctx.d = n, d
+        ctx.params = [tuple(tensors[7 * i + j] for j in (2, 3, 5, 6)) for i in range(n)]
+        ctx.save_for_backward(*[keep[3 * i + j] for i in range(n) for j in (1, 2)], *stats)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        n, d = ctx.n, ctx.d
+        pres, stats = ctx.saved_tensors[:2 * n], ctx.saved_tensors[2 * n:]
+        grads: List[Optional[torch.Tensor]] = [None] * (7 * n)
+        probs, keep = [], []
+        for i, g in enumerate(gs):
+            if g is None:
+                continue
+            g = g.contiguous()
+            keep.append(g)
+            grads[7 * i] = g
+            for j in (0, 1):                                  # the two norms of the sum: one dy
+                pre, gamma, beta = pres[2 * i + j], ctx.params[i][2 * j], ctx.params[i][2 * j + 1]
+                if gamma.grad is None or beta.grad is None:
+                    raise RuntimeError("LayerNorm parameters have no arena gradient")
+                dx = torch.empty_like(pre)
+                probs.append(LnProblem(pre.data_ptr(), None, gamma.data_ptr(), None, stats[i][2 * j].data_ptr(),
+                                       stats[i][2 * j + 1].data_ptr(), g.data_ptr(), dx.data_ptr(),
+                                       gamma.grad.data_ptr(), beta.grad.data_ptr(), pre.numel() // d))
+                grads[7 * i + 1 + 3 * j] = dx
+        if probs:
+            ws = torch.empty(lib.load().mmf_layernorm_bwd_workspace_bytes(d) // 4, dtype=torch.float32, device=pres[0].device)
+            keep.append(ws)
+            lib.layernorm_bwd_grouped(probs, d, ws)
+        return (None, *grads)
+
+
+def ln2_add3_group(items: Sequence[tuple], eps: float = 1e-5) -> List[torch.Tensor]:
+    """items: (x, pre_a, norm_a, pre_b, norm_b) with bf16 [rows, d] tensors and nn.LayerNorm modules: x + norm_a(pre_a) +
+    norm_b(pre_b) per item — MulT's three-way sum over the second LayerNorms of two cross-modal blocks.  One fused launch
+    where the library has it (lib.layernorm2_add3_available); else, and in fp32 mode, the two launches it stands for."""
+    rows = [x.numel() // x.shape[-1] for x, *_ in items]
+    if (_PRECISION == "fp32" or len(items) > lib.LN2_ADD3_MAX_PROBLEMS
+            or not lib.layernorm2_add3_available(rows, items[0][0].shape[-1])):
+        ys = layernorm_group([(pre, nm.weight, nm.bias) for _, pa, na, pb, nb in items for pre, nm in ((pa, na), (pb, nb))], eps)
+        return add3_group([(x, ys[2 * i], ys[2 * i + 1]) for i, (x, *_) in enumerate(items)])
+    flat = []
+    for x, pa, na, pb, nb in items:
+        flat += [x, pa, na.weight, na.bias, pb, nb.weight, nb.bias]
+    return list(_GroupedLn2Add3.apply(eps, *flat))
 
 
 # --------------------------------------------------------------------------------------------

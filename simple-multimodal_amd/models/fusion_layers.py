@@ -176,15 +176,16 @@ class _MHAParams(nn.Module):
 # ------------------------------------------------------------------------------------------------
 def _cross_blocks(blocks: Sequence["CrossModalTransformer"], qs: Sequence[torch.Tensor],
                   kvs: Sequence[torch.Tensor], B: int, Tqs: Sequence[int], Tks: Sequence[int],
-                  p: float = 0.0, ress: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+                  p: float = 0.0, ress: Optional[Sequence[torch.Tensor]] = None, norm2: bool = True) -> List[torch.Tensor]:
     """n independent CrossModalTransformer blocks (reference :202-211), one launch per stage.
     qs[i]: bf16 (B*Tq_i, d); kvs[i]: bf16 (B*Tk_i, d); ress[i] (default qs[i]): the query rows as the residual of
-    :205 — a separate handle when the caller fans its input out (ops.fanout) to sum the input gradients in one pass."""
+    :205 — a separate handle when the caller fans its input out (ops.fanout) to sum the input gradients in one pass.
+    norm2=False: the blocks' outputs BEFORE their second LayerNorm (:209), for a caller that fuses it into what follows."""
     proj = _cross_in_proj(blocks, qs, kvs)                           # [Q0, KV0, Q1, KV1, ...]
     _tick()
     att = _cross_attention(blocks, proj, B, Tqs, Tks, p)
     _tick()
-    return _cross_tail(blocks, att, qs if ress is None else ress, p)
+    return _cross_tail(blocks, att, qs if ress is None else ress, p, norm2)
 
 
 def _cross_in_proj(blocks, qs, kvs) -> List[torch.Tensor]:
@@ -203,7 +204,7 @@ def _cross_attention(blocks, proj, B, Tqs, Tks, p) -> List[torch.Tensor]:
     return ops.attention_group(specs, H, dh, proj, dropout_p=p)             # dropout(p) on the probabilities
 
 
-def _cross_tail(blocks, att, qs, p) -> List[torch.Tensor]:
+def _cross_tail(blocks, att, qs, p, norm2: bool = True) -> List[torch.Tensor]:
     pre1 = ops.linear_group([(att[i], _lin(blk.attention.out_proj), qs[i]) for i, blk in enumerate(blocks)])
     _tick()
     x = ops.layernorm_group([(pre1[i], blk.norm1.weight, blk.norm1.bias) for i, blk in enumerate(blocks)],
@@ -211,8 +212,17 @@ def _cross_tail(blocks, att, qs, p) -> List[torch.Tensor]:
     _tick()
     pre2 = ops.ffn_residual_group([(x[i], blk.ffn[0], blk.ffn[3]) for i, blk in enumerate(blocks)], dropout_p=p)
     _tick()
+    if not norm2:
+        return pre2
     return ops.layernorm_group([(pre2[i], blk.norm2.weight, blk.norm2.bias) for i, blk in enumerate(blocks)],
                                blocks[0].norm2.eps)
+
+
+def _norm2_sums(blocks, xs, pre2) -> List[torch.Tensor]:
+    """x_m + norm2(block 2m's output) + norm2(block 2m + 1's output) (reference :209 of both blocks, then :156-158) for
+    blocks given in pairs and their outputs before norm2: one launch, the normalised tensors never written."""
+    return ops.ln2_add3_group([(x, pre2[2 * i], blocks[2 * i].norm2, pre2[2 * i + 1], blocks[2 * i + 1].norm2)
+                               for i, x in enumerate(xs)], blocks[0].norm2.eps)
 
 
 def _self_attention_core(mhas: Sequence[_MHAParams], xs: Sequence[torch.Tensor], B: int, Ts: Sequence[int],
@@ -348,9 +358,9 @@ class MultimodalTransformer(_FusionBase):
 
             def chain(ms):          # query modalities ms: their two cross blocks each, the three-way sums, the self-attentions
                 g = [2 * m + j for m in ms for j in (0, 1)]
-                outs = _cross_blocks([blocks[i] for i in g], [qs[i] for i in g], [kvs[i] for i in g], B,
-                                     [Tqs[i] for i in g], [Tks[i] for i in g], p, [ress[i] for i in g])
-                es = ops.add3_group([(xs3[m], outs[2 * i], outs[2 * i + 1]) for i, m in enumerate(ms)])   # :156-158
+                pre2 = _cross_blocks([blocks[i] for i in g], [qs[i] for i in g], [kvs[i] for i in g], B,
+                                     [Tqs[i] for i in g], [Tks[i] for i in g], p, [ress[i] for i in g], norm2=False)
+                es = _norm2_sums([blocks[i] for i in g], [xs3[m] for m in ms], pre2)                      # :209, :156-158
                 return _self_attention_core([mhas[m] for m in ms], es, B, [Ts3[m] for m in ms], p)
             main = torch.cuda.current_stream()
             side = ops.branch_stream(1)                     # stream 0 belongs to HierarchicalFusion's small branches
@@ -362,8 +372,8 @@ class MultimodalTransformer(_FusionBase):
             for x in att_side:
                 x.record_stream(main)
         else:
-            t_a, t_v, a_t, a_v, v_t, v_a = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress)    # :146-153
-            et, ea, ev = ops.add3_group([(t, t_a, t_v), (a, a_t, a_v), (v, v_t, v_a)])         # :156-158, one launch
+            pre2 = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress, norm2=False)               # :146-153 up to norm2
+            et, ea, ev = _norm2_sums(blocks, [t, a, v], pre2)                                  # :209, :156-158, one launch
             att = _self_attention_core(mhas, [et, ea, ev], B, [Tt, Ta, Tv], p)
         # :161-168.  The self-attention outputs are only ever used through their mean over T, and the
         # out-projection is affine, so mean_t(out_proj(o_t)) == out_proj(mean_t o_t): pool the attention
