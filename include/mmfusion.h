@@ -663,6 +663,14 @@ int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls, const flo
 /* x <- gelu(x + bias) in place on a bf16 (rows, cols) block with row stride ld: the exact form 0.5 v (1 + erf(v / sqrt 2)) in
  * f32 (HuggingFace hidden_act = "gelu"), one rounding to bf16.  bias f32 [cols] or NULL.  cols % 8 == 0, ld % 8 == 0. */
 int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows, int cols, int ld, void* stream);
+/* The out-of-place form: g <- gelu(h + bias) with h kept (a backward reads it); the same kernel body, so g is bit-identical to
+ * what the in-place entry leaves in x.  h and g share the row stride ld; mmf_bias_gelu_bf16's constraints. */
+int mmf_bias_gelu_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, int64_t rows, int cols, int ld, void* stream);
+/* Its backward: dh <- dg * (Phi(v) + v phi(v)), v = h + bias in f32 (h = the stored linear output BEFORE its bias, Phi / phi the
+ * standard normal's distribution / density), one rounding to bf16.  dh may be dg.  All three blocks are (rows, cols) bf16 with
+ * row stride ld; mmf_bias_gelu_bf16's constraints. */
+int mmf_bias_gelu_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols, int ld,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frozen Wav2Vec2 backbone (mmfusion/wav2vec2.py; the reference runs HuggingFace's Wav2Vec2Model at models/encoders.py:116,144).
@@ -696,8 +704,9 @@ int mmf_w2v_posconv(const void* x_bf16, const void* w_bf16, const float* bias, v
 
 /* ------------------------------------------------------------------------------------------
  * Frozen DeBERTa-v3 backbone (mmfusion/deberta.py; the reference runs HuggingFace's DebertaV2Model at models/encoders.py:20).
- * The linears, the LayerNorms and the MLP of a layer are the grouped kernels above; these are the two pieces a DeBERTa has
- * beside them.  Both validate first and launch nothing on an error.  A mask is (n, T) as f32 (mask_kind 1, nonzero = keep) or
+ * The linears, the LayerNorms and the MLP of a layer are the grouped kernels above; these are the pieces a DeBERTa has
+ * beside them, forward and (with respect to the inputs only: prompt tuning through the frozen layers) backward.  All validate
+ * first and launch nothing on an error.  A mask is (n, T) as f32 (mask_kind 1, nonzero = keep) or
  * u8 (mask_kind 2), or NULL with mask_kind 0 for all ones.
  * ------------------------------------------------------------------------------------------ */
 /* rows of table[ids[row]] (ids int64 [rows], table f32 (vocab, d); an id outside the table reads its nearest row) or, with
@@ -717,6 +726,35 @@ int mmf_deberta_embed(const int64_t* ids, const float* embeds, const float* tabl
 int mmf_deberta_attn_fwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
                          const void* mask, int mask_kind, void* out_bf16, int n, int H, int T, int S, int head_dim, float scale,
                          void* stream);
+/* The same launch that also writes lse (n, H, T) f32: lse[item][h][i] = m + log(l) of query i's scaled, masked scores (natural
+ * log; m the row maximum, l the sum of exp(s - m) over the T keys).  out_bf16 is bit-identical to mmf_deberta_attn_fwd's.  A
+ * masked query row's scores are all the lowest finite f32, so its lse is that value again; mmf_deberta_attn_bwd does not use
+ * it.  lse 4-byte aligned. */
+int mmf_deberta_attn_fwd_lse(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                             const void* mask, int mask_kind, void* out_bf16, float* lse, int n, int H, int T, int S, int head_dim,
+                             float scale, void* stream);
+/* Backward of the above with respect to q, k, v (the position tables are frozen), c = 1 / scale:
+ *   P_ij  = exp(s_ij - lse_i) for a query with mask_i != 0, 1 / T for every key j < T of a masked query (the forward's uniform row)
+ *   dS_ij = c P_ij (dO_i.V_j - delta_i) on unmasked pairs, 0 on masked pairs;   delta_i = sum_d dO_i O_i
+ *   dV_j  = sum_i P_ij dO_i                                 (masked query rows contribute 1/T dO_i)
+ *   dQ_i  = sum_j dS_ij K_j + sum_r A_ir posK[r],   A_ir = sum of dS_ij over {j : idx(i-j) = r}
+ *   dK_j  = sum_i dS_ij Q_i + sum_r B_jr posQ[r],   B_jr = sum of dS_ij over {i : idx(i-j) = r}
+ * so dQ of a masked query row and dK of a masked key are exactly 0.  out_bf16 / lse: what mmf_deberta_attn_fwd_lse wrote for
+ * these operands; dout_bf16 (n*T, H 64) the gradient of out; delta_ws: n*H*T floats of scratch (holds delta afterwards);
+ * dqkv_bf16 (n*T, 3 H 64) in qkv's layout: every element of its n*T rows is written (the caller need not zero it), each by one
+ * lane in a fixed summation order: no atomics, bitwise repeatable.  Three launches: delta, the dQ pass (one workgroup per 64
+ * queries walking the keys), the dK/dV pass (one per 64 keys walking the queries); P and dS are rounded to bf16 as MFMA
+ * operands, accumulation is f32, one rounding of the results.  idx: mmf_deberta_attn_fwd's contract, clamped the same way.
+ * mmf_deberta_attn_fwd's limits; dout / dqkv 16-byte aligned, lse / delta_ws 4-byte aligned. */
+int mmf_deberta_attn_bwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                         const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                         float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, void* stream);
+/* Backward of mmf_deberta_embed on the embeds route: d_embeds (rows, d) f32 = mask[row] * the LayerNorm input gradient of
+ * dout_bf16 (rows, d), the gradient of the kernel's bf16 output.  The row statistics are recomputed in f32 from embeds as the
+ * forward computes them; rows with mask 0 are exactly 0.  mmf_deberta_embed's limits on d; embeds / gamma / d_embeds 16-byte
+ * aligned, dout 8-byte aligned. */
+int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, float eps, const void* mask, int mask_kind, const void* dout_bf16,
+                          float* d_embeds, int64_t rows, int d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Input preparation (mmfusion/prep.py; the reference does this on the host per sample, data/dataset_loaders.py:95-261): what a

@@ -2,7 +2,9 @@
 //   embed   word_embeddings[ids] (or f32 inputs_embeds rows) -> LayerNorm in f32 -> * mask -> bf16 rows, one pass
 //   attn    fused disentangled attention forward, head_dim 64:
 //             s[i][j] = (Q_i.K_j + Q_i.posK[idx(i-j)] + K_j.posQ[idx(i-j)]) / scale, masked softmax over j, @ V
-//           Scores, bias and probabilities live in registers and LDS only.
+//           Scores, bias and probabilities live in registers and LDS only.  With LSE it also writes the rows' log-sum-exp.
+//   backward with respect to the inputs (the weights are frozen; prompt tuning): the embedding LayerNorm's input gradient, and
+//           the attention backward: a delta pre-pass, a dQ pass and a dK/dV pass from one kernel body, without atomics.
 #include <float.h>
 #include "mmf_internal.h"
 
@@ -99,11 +101,12 @@ __device__ __forceinline__ int db_slot(int key) {            // key of a 32-key 
   return 8 * (k >> 2) + 4 * c + (k & 3);
 }
 
+template <bool LSE>                                          // LSE: also write lse[item][h][i] = m + log(l), what the backward reads
 __global__ __launch_bounds__(DB_THREADS)
 void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ posq,
                              const unsigned short* __restrict__ posk, int ld_pos, const int* __restrict__ idx,
                              const void* __restrict__ mask, int mask_kind, unsigned short* __restrict__ out,
-                             int H, int T, int S2 /* 2 S */, float inv_scale) {
+                             float* __restrict__ lse, int H, int T, int S2 /* 2 S */, float inv_scale) {
   __shared__ __attribute__((aligned(16))) unsigned short sK[DB_BK * DB_KLD];
   __shared__ __attribute__((aligned(16))) unsigned short sVt[DB_DH * DB_VLD];
   __shared__ float sC[4 * 16 * DB_CLD];
@@ -253,6 +256,343 @@ void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 #pragma unroll
     for (int t = 0; t < 4; ++t)
       *reinterpret_cast<u32x2_t*>(dst + t * 16) = u32x2_t{pack_bf16x2(o[t][0] * inv, o[t][1] * inv), pack_bf16x2(o[t][2] * inv, o[t][3] * inv)};
+    // a fully masked row: m = -FLT_MAX and l = T, so the sum is -FLT_MAX again in f32; the backward does not use it
+    if (LSE && q == 0) lse[((size_t)item * H + h) * T + iq] = m_run + logf(l_run);
+  }
+}
+
+// ---- backward with respect to the inputs (prompt tuning through the frozen layers) --------------------------------
+// embeddings: d_embeds = mask[row] * the LayerNorm input gradient of the bf16 gradient dy of deberta_embed_kernel's output
+// (inputs_embeds route).  The row statistics are recomputed as the forward computes them; one wave per row, same lane map.
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_embed_bwd_kernel(const float* __restrict__ embeds, const float* __restrict__ gamma, const void* __restrict__ mask,
+                              int mask_kind, const unsigned short* __restrict__ dy, float* __restrict__ dx, int rows, int d, float eps) {
+  const int row = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* __restrict__ src = embeds + (size_t)row * d;
+  const float m = db_mask(mask, mask_kind, (size_t)row);
+  f32x4_t v[4];
+  float sum = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 4 * lane + 256 * k;
+    v[k] = c < d ? *reinterpret_cast<const f32x4_t*>(src + c) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    sum += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+  }
+  const float mean = wave_sum(sum) / (float)d;
+  float sq = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (4 * lane + 256 * k < d) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float c = v[k][e] - mean; sq = fmaf(c, c, sq); }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+  // g = dy * mask * gamma (the gradient of the normalised value), xh the normalised value; s1 = sum g, s2 = sum g xh
+  f32x4_t g[4];
+  float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 4 * lane + 256 * k;
+    g[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    if (c < d) {
+      const u32x2_t w = *reinterpret_cast<const u32x2_t*>(dy + (size_t)row * d + c);
+      const f32x4_t gm = *reinterpret_cast<const f32x4_t*>(gamma + c);
+      g[k] = f32x4_t{bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])} * gm * m;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[k][e] = (v[k][e] - mean) * rstd;
+        s1 += g[k][e];
+        s2 = fmaf(g[k][e], v[k][e], s2);
+      }
+    }
+  }
+  s1 = wave_sum(s1) / (float)d;
+  s2 = wave_sum(s2) / (float)d;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 4 * lane + 256 * k;
+    if (c < d) {
+      f32x4_t o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = m != 0.0f ? rstd * (g[k][e] - s1 - v[k][e] * s2) : 0.0f;      // a masked row: exactly 0
+      *reinterpret_cast<f32x4_t*>(dx + (size_t)row * d + c) = o;
+    }
+  }
+}
+
+// delta[item][h][i] = sum_d dO_i O_i of one head: one lane per (token, head), eight 16-byte reads of each operand
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_attn_delta_kernel(const unsigned short* __restrict__ out, const unsigned short* __restrict__ dout, float* __restrict__ delta,
+                               int H, int T, unsigned total /* n T H */) {
+  const unsigned i = blockIdx.x * DB_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const unsigned row = i / (unsigned)H, h = i - row * (unsigned)H, item = row / (unsigned)T, t = row - item * (unsigned)T;
+  const size_t off = ((size_t)row * H + h) * DB_DH;
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < DB_DH / 8; ++k) {
+    float a[8], b[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(out + off + 8 * k), a);
+    unpack8(*reinterpret_cast<const u32x4_t*>(dout + off + 8 * k), b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc = fmaf(a[e], b[e], acc);
+  }
+  delta[((size_t)item * H + h) * T + t] = acc;
+}
+
+// The attention backward, both passes from one body.  The score is symmetric under (Q, posK, i) <-> (K, posQ, j):
+//   s_ij = Q_i.K_j + Q_i.posK[idx(i-j)] + K_j.posQ[idx(i-j)]
+// so with "own" = the 64 tokens a workgroup owns (a lane's column, as the forward's queries) and "other" = the tokens it
+// walks in tiles of 32, the dQ pass (KPASS false: own = queries, other = keys) and the dK/dV pass (KPASS true: own = keys,
+// other = queries, the delta negated) run the same products with the operands swapped:
+//   S^T    [other][own]     A = other rows (LDS)                  B = own fragment: Q | K (registers)
+//   T1^T   [pos row][own]   A = posK | posQ rows (global)         B = own fragment          -- the wave's 47-delta window
+//   T2^T   [pos row][other] A = posQ | posK rows (global)         B = other rows (LDS)      -- the block's 95-delta window
+//   dP^T   [other][own]     A = V | dO rows of the tile (LDS)     B = own dO | V fragment
+//   dOwn^T [dh][own]       += A = other^T (LDS, db_slot order)    B = dS^T, the lane's own D registers packed to bf16
+//   dOwn^T [dh][own]       += A = posK^T | posQ^T window (LDS)    B = the bucket sums of dS over the window rows
+//   dV^T   [dh][own key]   += A = dO^T (LDS, db_slot order)       B = P^T packed to bf16            (KPASS only)
+// P = exp(s - lse_i), or 1/T on a masked query row; dS = P (dP - delta_i) / scale on unmasked pairs, else 0.
+//
+// The position-gradient term.  For one own token the others of a tile that gather the same position row are a contiguous
+// run (idx is monotone in delta), so sFirst / sEnd hold, per window row, the run of the tile's 95 deltas that maps to it and
+// the lane that holds (own r, rows 8 q .. 8 q + 7 of a 32-row chunk) as its B operand sums that run of its own token's dS
+// row, parked in LDS as f32, in key order: no atomics, the same order every run.
+//
+// LDS: other rows 32 x 72 and their transpose 64 x 40 (9728 B), V | dO rows and (KPASS) dO^T (9728 B), T1 / dS 4 waves x 16 x 49
+// f32 (12544 B), T2 32 x 97 f32 (12416 B), the transposed position window 64 x 104 bf16 (13312 B), idx / run / per-row
+// values (1.5 KB): 59.3 KB, two workgroups per CU by LDS.
+constexpr int DB_TLD = 104, DB_TROWS = 96;
+
+template <bool KPASS>
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ posq,
+                             const unsigned short* __restrict__ posk, int ld_pos, const int* __restrict__ idx,
+                             const void* __restrict__ mask, int mask_kind, const float* __restrict__ lse,
+                             const unsigned short* __restrict__ dout, const float* __restrict__ delta,
+                             unsigned short* __restrict__ dqkv, int H, int T, int S2 /* 2 S */, float inv_scale) {
+  __shared__ __attribute__((aligned(16))) unsigned short sO[DB_BK * DB_KLD];          // other rows: K | Q
+  __shared__ __attribute__((aligned(16))) unsigned short sOt[DB_DH * DB_VLD];         // their transpose, db_slot order
+  __shared__ __attribute__((aligned(16))) unsigned short sO2[DB_BK * DB_KLD];         // V | dO rows of the other tokens
+  __shared__ __attribute__((aligned(16))) unsigned short sO2t[KPASS ? DB_DH * DB_VLD : 8];   // dO^T, db_slot order
+  __shared__ __attribute__((aligned(16))) unsigned short sT[DB_DH * DB_TLD];          // posK^T | posQ^T over the block's window
+  __shared__ float sC[4 * 16 * DB_CLD];
+  __shared__ float sP[DB_BK * DB_PLD];
+  __shared__ int sIdx[DB_NIDX + 1], sFirst[DB_TROWS], sEnd[DB_TROWS];
+  __shared__ float sOm[DB_BK], sLse[DB_BK], sDl[DB_BK];
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, r = lane & 15;
+  const int own0 = blockIdx.x * DB_BQ, h = blockIdx.y, item = blockIdx.z;
+  const int d = H * DB_DH, ld = 3 * d;
+  const unsigned short* __restrict__ base = qkv + (size_t)item * T * ld + h * DB_DH;
+  const unsigned short* __restrict__ dob = dout + (size_t)item * T * d + h * DB_DH;
+  const size_t mrow = (size_t)item * T, srow = ((size_t)item * H + h) * T;
+
+  // this lane's own token (column r of every product of this wave): its Q | K fragment and its dO | V fragment
+  const int ow = wave * 16 + r, io = own0 + ow, ioc = io < T ? io : T - 1;
+  const unsigned short* __restrict__ own = base + (size_t)ioc * ld + (KPASS ? d : 0);
+  const unsigned short* __restrict__ own2 = KPASS ? base + (size_t)ioc * ld + 2 * d : dob + (size_t)ioc * d;
+  bf16x8_t xf[2], yf[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    xf[ks] = *reinterpret_cast<const bf16x8_t*>(own + ks * 32 + q * 8);
+    yf[ks] = *reinterpret_cast<const bf16x8_t*>(own2 + ks * 32 + q * 8);
+  }
+  const bool own_on = db_mask(mask, mask_kind, mrow + ioc) != 0.0f;
+  const float lse_o = KPASS ? 0.0f : lse[srow + ioc], dl_o = KPASS ? 0.0f : delta[srow + ioc];
+  const float inv_T = 1.0f / (float)T;
+
+  f32x4_t acc[4], accv[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = accv[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float* __restrict__ cw = sC + wave * 16 * DB_CLD;
+  const unsigned short* __restrict__ tab1 = (KPASS ? posq : posk) + h * DB_DH;        // gathered with the own token's vector
+  const unsigned short* __restrict__ tab2 = (KPASS ? posk : posq) + h * DB_DH + q * 8;
+
+  for (int o0 = 0; o0 < T; o0 += DB_BK) {
+    __syncthreads();                                             // the previous tile's readers are done
+    {
+      // other rows as they are and transposed with their tokens in db_slot order.  Tokens past T read row T - 1: P and dS are 0 there.
+      const int key = tid >> 3, c8 = (tid & 7) * 8;
+      const int j = o0 + key < T ? o0 + key : T - 1;
+      const unsigned short* __restrict__ srcA = base + (size_t)j * ld + c8 + (KPASS ? 0 : d);
+      const unsigned short* __restrict__ srcB = KPASS ? dob + (size_t)j * d + c8 : base + (size_t)j * ld + c8 + 2 * d;
+      const u32x4_t va = *reinterpret_cast<const u32x4_t*>(srcA), vb = *reinterpret_cast<const u32x4_t*>(srcB);
+      *reinterpret_cast<u32x4_t*>(sO + key * DB_KLD + c8) = va;
+      *reinterpret_cast<u32x4_t*>(sO2 + key * DB_KLD + c8) = vb;
+      const int slot = db_slot(key);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sOt[(c8 + 2 * e) * DB_VLD + slot] = (unsigned short)(va[e] & 0xffffu);
+        sOt[(c8 + 2 * e + 1) * DB_VLD + slot] = (unsigned short)(va[e] >> 16);
+        if (KPASS) {
+          sO2t[(c8 + 2 * e) * DB_VLD + slot] = (unsigned short)(vb[e] & 0xffffu);
+          sO2t[(c8 + 2 * e + 1) * DB_VLD + slot] = (unsigned short)(vb[e] >> 16);
+        }
+      }
+      if (tid < DB_NIDX) {                                       // idx of the delta of (own ow, other k), ow - k + 31 = tid
+        int dl = own0 - o0 - (DB_BK - 1) + tid;
+        if (KPASS) dl = -dl;                                     // delta = query - key = other - own
+        dl = dl < -(T - 1) ? -(T - 1) : (dl > T - 1 ? T - 1 : dl);
+        int v = idx[dl + T - 1];
+        sIdx[tid] = v < 0 ? 0 : (v > S2 - 1 ? S2 - 1 : v);
+      }
+      if (tid < DB_TROWS) { sFirst[tid] = 0; sEnd[tid] = 0; }    // an empty run
+      if (tid < DB_BK) {
+        const int jj = o0 + tid < T ? o0 + tid : T - 1;
+        sOm[tid] = o0 + tid < T ? db_mask(mask, mask_kind, mrow + jj) : 0.0f;
+        if (KPASS) { sLse[tid] = lse[srow + jj]; sDl[tid] = delta[srow + jj]; }
+      }
+    }
+    __syncthreads();
+
+    // idx is monotone over the tile's deltas (non-decreasing, or non-increasing in the dK/dV pass): the windows' ends
+    const int e0 = sIdx[0], e1 = sIdx[DB_NIDX - 1], w0 = sIdx[16 * wave], w1 = sIdx[16 * wave + 46];
+    const int lo_p = e0 < e1 ? e0 : e1, hi_p = e0 < e1 ? e1 : e0;
+    const int lo_c = w0 < w1 ? w0 : w1, hi_c = w0 < w1 ? w1 : w0;
+    int npc = (hi_p - lo_p) / 16 + 1;
+    npc = npc < 1 ? 1 : (npc > DB_PROWS / 16 ? DB_PROWS / 16 : npc);
+    int ncc = (hi_c - lo_c) / 16 + 1;
+    ncc = ncc < 1 ? 1 : (ncc > DB_CROWS / 16 ? DB_CROWS / 16 : ncc);
+    const int nb32 = (npc + 1) >> 1;                             // 32-row chunks of the block's window
+
+    if (tid < DB_NIDX) {                                         // the run of deltas that gathers each window row
+      const int me = sIdx[tid];
+      int row = me - lo_p;
+      row = row < 0 ? 0 : (row > DB_TROWS - 1 ? DB_TROWS - 1 : row);
+      if (tid == 0 || sIdx[tid - 1] != me) sFirst[row] = tid;
+      if (tid == DB_NIDX - 1 || sIdx[tid + 1] != me) sEnd[row] = tid + 1;
+    }
+    for (int i = tid; i < nb32 * 32 * 8; i += DB_THREADS) {     // posK^T | posQ^T over the window, rows clamped to the table
+      const int row = i >> 3, c8 = (i & 7) * 8;
+      int prow = lo_p + row;
+      prow = prow > S2 - 1 ? S2 - 1 : prow;
+      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(tab1 + (size_t)prow * ld_pos + c8);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sT[(c8 + 2 * e) * DB_TLD + row] = (unsigned short)(w[e] & 0xffffu);
+        sT[(c8 + 2 * e + 1) * DB_TLD + row] = (unsigned short)(w[e] >> 16);
+      }
+    }
+
+    // the other rows' fragments: A of S^T and B of T2^T
+    bf16x8_t kf[2][2];
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) kf[kc][ks] = *reinterpret_cast<const bf16x8_t*>(sO + (kc * 16 + r) * DB_KLD + ks * 32 + q * 8);
+
+    // T2^T: this wave's share of the (row chunk, other chunk) tiles -> sP[other][pos row - lo_p]
+    for (int t = wave; t < npc * 2; t += 4) {
+      const int rc = t >> 1, kc = t & 1;
+      int prow = lo_p + rc * 16 + r;
+      prow = prow > S2 - 1 ? S2 - 1 : prow;
+      const unsigned short* __restrict__ a = tab2 + (size_t)prow * ld_pos;
+      f32x4_t c = {0.f, 0.f, 0.f, 0.f};
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), kc ? kf[1][0] : kf[0][0], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), kc ? kf[1][1] : kf[0][1], c, 0, 0, 0);
+      float* __restrict__ dst = sP + (kc * 16 + r) * DB_PLD + rc * 16 + q * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dst[e] = c[e];
+    }
+    // T1^T: this wave's own rows -> cw[own][pos row - lo_c]
+    for (int c16 = 0; c16 < ncc; ++c16) {
+      int prow = lo_c + c16 * 16 + r;
+      prow = prow > S2 - 1 ? S2 - 1 : prow;
+      const unsigned short* __restrict__ a = tab1 + (size_t)prow * ld_pos + q * 8;
+      f32x4_t c = {0.f, 0.f, 0.f, 0.f};
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), xf[0], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), xf[1], c, 0, 0, 0);
+      float* __restrict__ dst = cw + r * DB_CLD + c16 * 16 + q * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dst[e] = c[e];
+    }
+    // S^T and dP^T
+    f32x4_t s[2], dp[2];
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc) {
+      s[kc] = dp[kc] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        s[kc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kc][ks], xf[ks], s[kc], 0, 0, 0);
+        const bf16x8_t o2 = *reinterpret_cast<const bf16x8_t*>(sO2 + (kc * 16 + r) * DB_KLD + ks * 32 + q * 8);
+        dp[kc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o2, yf[ks], dp[kc], 0, 0, 0);
+      }
+    }
+    __syncthreads();                                             // sP, cw, sT and the runs are complete
+
+    // lane (q, r): others kc * 16 + 4 q + e of own token r.  The probabilities and dS of the tile stay in registers.
+    float p[2][4], ds[2][4];
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int key = kc * 16 + q * 4 + e;
+        const int ix = sIdx[ow - key + (DB_BK - 1)];
+        int oc = ix - lo_c, op = ix - lo_p;
+        oc = oc < 0 ? 0 : (oc > DB_CROWS - 1 ? DB_CROWS - 1 : oc);
+        op = op < 0 ? 0 : (op > DB_PROWS - 1 ? DB_PROWS - 1 : op);
+        const float v = (s[kc][e] + cw[r * DB_CLD + oc] + sP[key * DB_PLD + op]) * inv_scale;
+        const bool there = o0 + key < T;                         // the other token exists
+        const bool q_on = KPASS ? sOm[key] != 0.0f : own_on, k_on = KPASS ? own_on : sOm[key] != 0.0f;
+        const float l = KPASS ? sLse[key] : lse_o, dl = KPASS ? sDl[key] : dl_o;
+        const float pe = q_on ? (k_on ? __expf(v - l) : 0.0f) : inv_T;     // a masked query row is the uniform row; its lse is not used
+        p[kc][e] = there ? pe : 0.0f;
+        ds[kc][e] = (there && q_on && k_on) ? pe * (dp[kc][e] - dl) * inv_scale : 0.0f;
+      }
+    __syncthreads();                                             // every lane has gathered from cw: it becomes the dS rows
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) cw[r * DB_CLD + kc * 16 + q * 4 + e] = ds[kc][e];
+    __syncthreads();
+
+    const u32x4_t dw = {pack_bf16x2(ds[0][0], ds[0][1]), pack_bf16x2(ds[0][2], ds[0][3]), pack_bf16x2(ds[1][0], ds[1][1]), pack_bf16x2(ds[1][2], ds[1][3])};
+    const bf16x8_t df = __builtin_bit_cast(bf16x8_t, dw);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const bf16x8_t of = *reinterpret_cast<const bf16x8_t*>(sOt + (t * 16 + r) * DB_VLD + q * 8);
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of, df, acc[t], 0, 0, 0);
+    }
+    if (KPASS) {
+      const u32x4_t pw = {pack_bf16x2(p[0][0], p[0][1]), pack_bf16x2(p[0][2], p[0][3]), pack_bf16x2(p[1][0], p[1][1]), pack_bf16x2(p[1][2], p[1][3])};
+      const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pw);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const bf16x8_t of = *reinterpret_cast<const bf16x8_t*>(sO2t + (t * 16 + r) * DB_VLD + q * 8);
+        accv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of, pf, accv[t], 0, 0, 0);
+      }
+    }
+    // the bucket sums of this lane's own token over window rows c * 32 + 8 q + e, then (posK^T | posQ^T) . sums
+    for (int c = 0; c < nb32; ++c) {
+      float a[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int row = c * 32 + q * 8 + e;
+        int t0 = sFirst[row], t1 = sEnd[row];                    // deltas t0 .. t1 - 1; other = ow + 31 - t must lie in the tile
+        t0 = t0 < ow ? ow : t0;
+        t1 = t1 > ow + DB_BK ? ow + DB_BK : t1;
+        float sum = 0.0f;
+        for (int t = t0; t < t1; ++t) sum += cw[r * DB_CLD + (ow + (DB_BK - 1) - t)];
+        a[e] = sum;
+      }
+      const bf16x8_t af = __builtin_bit_cast(bf16x8_t, pack8(a));
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const bf16x8_t tf = *reinterpret_cast<const bf16x8_t*>(sT + (t * 16 + r) * DB_TLD + c * 32 + q * 8);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, af, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  if (io < T) {
+    unsigned short* __restrict__ dst = dqkv + ((size_t)item * T + io) * ld + (KPASS ? d : 0) + h * DB_DH + q * 4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      *reinterpret_cast<u32x2_t*>(dst + t * 16) = u32x2_t{pack_bf16x2(acc[t][0], acc[t][1]), pack_bf16x2(acc[t][2], acc[t][3])};
+      if (KPASS) *reinterpret_cast<u32x2_t*>(dst + d + t * 16) = u32x2_t{pack_bf16x2(accv[t][0], accv[t][1]), pack_bf16x2(accv[t][2], accv[t][3])};
+    }
   }
 }
 
@@ -285,23 +625,96 @@ extern "C" int mmf_deberta_embed(const int64_t* ids, const float* embeds, const 
   return MMF_OK;
 }
 
+namespace {
+
+// the checks the attention entries share; `out` is the forward's output (the backward reads it)
+int db_attn_check(const char* fn, const void* qkv, const void* posq, const void* posk, int ld_pos, const int* idx, const void* mask,
+                  int mask_kind, const void* out, int n, int H, int T, int S, int head_dim, float scale) {
+  if (!qkv || !posq || !posk || !idx || !out || n <= 0 || H <= 0 || T <= 0 || S <= 0 || head_dim <= 0 || !(scale > 0.0f))
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand or n=%d H=%d T=%d S=%d head_dim=%d scale=%g", fn, n, H, T, S, head_dim, (double)scale);
+  if (head_dim == DB_DH && ld_pos < H * DB_DH) MMF_FAIL(MMF_E_SHAPE, "%s: ld_pos=%d is less than H * 64 = %d", fn, ld_pos, H * DB_DH);
+  if (head_dim != DB_DH || T > 1024 || S > 256 || n > 65535 || H > 65535)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: head_dim=%d (64 only), T=%d (at most 1024), S=%d (at most 256), n=%d H=%d (at most 65535)",
+             fn, head_dim, T, S, n, H);
+  if (int rc = db_mask_check(fn, mask, mask_kind)) return rc;
+  if (!mmf_aligned16(qkv) || !mmf_aligned16(posq) || !mmf_aligned16(posk) || !mmf_aligned16(out) || (ld_pos & 7)
+      || (reinterpret_cast<uintptr_t>(idx) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: qkv / posq / posk / out must be 16-byte aligned, ld_pos a multiple of 8, idx 4-byte aligned", fn);
+  return MMF_OK;
+}
+
+template <bool LSE>
+void db_attn_fwd_launch(const void* qkv, const void* posq, const void* posk, int ld_pos, const int* idx, const void* mask, int mask_kind,
+                        void* out, float* lse, int n, int H, int T, int S, float scale, void* stream) {
+  hipLaunchKernelGGL(deberta_attn_fwd_kernel<LSE>, dim3((T + DB_BQ - 1) / DB_BQ, H, n), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(qkv), static_cast<const unsigned short*>(posq),
+                     static_cast<const unsigned short*>(posk), ld_pos, idx, mask, mask_kind, static_cast<unsigned short*>(out), lse,
+                     H, T, 2 * S, 1.0f / scale);
+}
+
+}  // namespace
+
 extern "C" int mmf_deberta_attn_fwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
                                     const void* mask, int mask_kind, void* out_bf16, int n, int H, int T, int S, int head_dim,
                                     float scale, void* stream) {
-  if (!qkv_bf16 || !posq_bf16 || !posk_bf16 || !idx || !out_bf16 || n <= 0 || H <= 0 || T <= 0 || S <= 0 || head_dim <= 0 || !(scale > 0.0f))
-    MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_attn_fwd: null operand or n=%d H=%d T=%d S=%d head_dim=%d scale=%g", n, H, T, S, head_dim, (double)scale);
-  if (head_dim == DB_DH && ld_pos < H * DB_DH) MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_attn_fwd: ld_pos=%d is less than H * 64 = %d", ld_pos, H * DB_DH);
-  if (head_dim != DB_DH || T > 1024 || S > 256 || n > 65535 || H > 65535)
-    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_deberta_attn_fwd: head_dim=%d (64 only), T=%d (at most 1024), S=%d (at most 256), n=%d H=%d (at most 65535)",
-             head_dim, T, S, n, H);
-  if (int rc = db_mask_check("mmf_deberta_attn_fwd", mask, mask_kind)) return rc;
-  if (!mmf_aligned16(qkv_bf16) || !mmf_aligned16(posq_bf16) || !mmf_aligned16(posk_bf16) || !mmf_aligned16(out_bf16) || (ld_pos & 7)
-      || (reinterpret_cast<uintptr_t>(idx) & 3u))
-    MMF_FAIL(MMF_E_ALIGN, "mmf_deberta_attn_fwd: qkv / posq / posk / out must be 16-byte aligned, ld_pos a multiple of 8, idx 4-byte aligned");
-  hipLaunchKernelGGL(deberta_attn_fwd_kernel, dim3((T + DB_BQ - 1) / DB_BQ, H, n), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const unsigned short*>(qkv_bf16), static_cast<const unsigned short*>(posq_bf16),
-                     static_cast<const unsigned short*>(posk_bf16), ld_pos, idx, mask, mask_kind, static_cast<unsigned short*>(out_bf16),
-                     H, T, 2 * S, 1.0f / scale);
+  if (int rc = db_attn_check("mmf_deberta_attn_fwd", qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, n, H, T, S, head_dim, scale))
+    return rc;
+  db_attn_fwd_launch<false>(qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, nullptr, n, H, T, S, scale, stream);
   MMF_CHECK_LAUNCH("mmf_deberta_attn_fwd");
+  return MMF_OK;
+}
+
+extern "C" int mmf_deberta_attn_fwd_lse(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                                        const void* mask, int mask_kind, void* out_bf16, float* lse, int n, int H, int T, int S,
+                                        int head_dim, float scale, void* stream) {
+  const char* fn = "mmf_deberta_attn_fwd_lse";
+  if (!lse) MMF_FAIL(MMF_E_SHAPE, "%s: null lse", fn);
+  if (int rc = db_attn_check(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, n, H, T, S, head_dim, scale)) return rc;
+  if (reinterpret_cast<uintptr_t>(lse) & 3u) MMF_FAIL(MMF_E_ALIGN, "%s: lse must be 4-byte aligned", fn);
+  db_attn_fwd_launch<true>(qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, n, H, T, S, scale, stream);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_deberta_attn_bwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                                    const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                                    float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, void* stream) {
+  const char* fn = "mmf_deberta_attn_bwd";
+  if (!lse || !dout_bf16 || !delta_ws || !dqkv_bf16) MMF_FAIL(MMF_E_SHAPE, "%s: null lse / dout / delta_ws / dqkv", fn);
+  if (int rc = db_attn_check(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, n, H, T, S, head_dim, scale)) return rc;
+  if (!mmf_aligned16(dout_bf16) || !mmf_aligned16(dqkv_bf16) || ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(delta_ws)) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: dout / dqkv must be 16-byte aligned, lse / delta_ws 4-byte aligned", fn);
+  if ((int64_t)n * T * H >= (int64_t)1 << 31) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: n * T * H = %lld (below 2^31)", fn, (long long)n * T * H);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned short *qkv = static_cast<const unsigned short*>(qkv_bf16), *pq = static_cast<const unsigned short*>(posq_bf16),
+                       *pk = static_cast<const unsigned short*>(posk_bf16), *dout = static_cast<const unsigned short*>(dout_bf16);
+  unsigned short* dqkv = static_cast<unsigned short*>(dqkv_bf16);
+  const unsigned total = (unsigned)((int64_t)n * T * H);
+  const dim3 grid((T + DB_BQ - 1) / DB_BQ, H, n);
+  hipLaunchKernelGGL(deberta_attn_delta_kernel, dim3((total + DB_THREADS - 1) / DB_THREADS), dim3(DB_THREADS), 0, s,
+                     static_cast<const unsigned short*>(out_bf16), dout, delta_ws, H, T, total);
+  MMF_CHECK_LAUNCH(fn);
+  hipLaunchKernelGGL(deberta_attn_bwd_kernel<false>, grid, dim3(DB_THREADS), 0, s, qkv, pq, pk, ld_pos, idx, mask, mask_kind, lse, dout,
+                     static_cast<const float*>(delta_ws), dqkv, H, T, 2 * S, 1.0f / scale);
+  MMF_CHECK_LAUNCH(fn);
+  hipLaunchKernelGGL(deberta_attn_bwd_kernel<true>, grid, dim3(DB_THREADS), 0, s, qkv, pq, pk, ld_pos, idx, mask, mask_kind, lse, dout,
+                     static_cast<const float*>(delta_ws), dqkv, H, T, 2 * S, 1.0f / scale);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, float eps, const void* mask, int mask_kind,
+                                     const void* dout_bf16, float* d_embeds, int64_t rows, int d, void* stream) {
+  const char* fn = "mmf_deberta_embed_bwd";
+  if (!embeds || !gamma || !dout_bf16 || !d_embeds || rows <= 0 || d <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: null operand or rows=%lld d=%d", fn, (long long)rows, d);
+  if ((d & 3) || d > 1024 || rows > ((int64_t)1 << 31) - 4)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: d=%d (multiple of 4, at most 1024), rows=%lld (below 2^31)", fn, d, (long long)rows);
+  if (int rc = db_mask_check(fn, mask, mask_kind)) return rc;
+  if (!mmf_aligned16(embeds) || !mmf_aligned16(gamma) || !mmf_aligned16(d_embeds) || (reinterpret_cast<uintptr_t>(dout_bf16) & 7u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: embeds / gamma / d_embeds must be 16-byte aligned, dout 8-byte aligned", fn);
+  const int per = DB_THREADS / MMF_WAVE;
+  hipLaunchKernelGGL(deberta_embed_bwd_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+                     embeds, gamma, mask, mask_kind, static_cast<const unsigned short*>(dout_bf16), d_embeds, (int)rows, d, eps);
+  MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }

@@ -1,6 +1,6 @@
 // The pieces a ViT forward has and the fusion path did not (mmfusion/vit.py): patch extraction for the patch-embedding
-// GEMM, CLS / position tokens, exact (erf) GELU.  All three are HBM-bound streaming kernels: one 16-byte bf16 access
-// (8 elements) per lane on the bf16 side, two 16-byte accesses on the f32 side, grid-stride loops on mmf_stream_grid's
+// GEMM, CLS / position tokens, exact (erf) GELU (and its backward, for the DeBERTa input gradient).  All are HBM-bound
+// streaming kernels: one 16-byte bf16 access (8 elements) per lane on the bf16 side, two 16-byte accesses on the f32 side, grid-stride loops on mmf_stream_grid's
 // grid (mmf_internal.h) per grid row.
 #include "mmf_internal.h"
 
@@ -57,15 +57,15 @@ void vit_embed_tokens_kernel(const unsigned short* __restrict__ pe, const float*
   }
 }
 
-// x <- gelu(x + bias) in place, rows x cols with row stride ld.  nvec = rows * cols / 8 < 2^31 (the host splits longer inputs).
+// y <- gelu(x + bias), rows x cols with row stride ld; y may be x (the in-place entry).  nvec = rows * cols / 8 < 2^31 (the host
+// splits longer inputs).
 template <bool HAS_BIAS>
 __global__ __launch_bounds__(VIT_THREADS)
-void bias_gelu_kernel(unsigned short* __restrict__ x, const float* __restrict__ bias, unsigned nvec, unsigned cv /* cols/8 */, int ld) {
+void bias_gelu_kernel(const unsigned short* x, unsigned short* y, const float* __restrict__ bias, unsigned nvec, unsigned cv /* cols/8 */, int ld) {
   const unsigned stride = gridDim.x * VIT_THREADS;
   for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
     const unsigned r = v / cv, j = (v - r * cv) << 3;
-    unsigned short* p = x + (size_t)r * ld + j;
-    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(p);
+    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(x + (size_t)r * ld + j);
     f32x4_t a = f32x4_t{bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
     f32x4_t b = f32x4_t{bf16lo(w[2]), bf16hi(w[2]), bf16lo(w[3]), bf16hi(w[3])};
     if (HAS_BIAS) {
@@ -74,8 +74,60 @@ void bias_gelu_kernel(unsigned short* __restrict__ x, const float* __restrict__ 
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) { a[e] = gelu_erf(a[e]); b[e] = gelu_erf(b[e]); }
-    *reinterpret_cast<u32x4_t*>(p) = pack8(a, b);
+    *reinterpret_cast<u32x4_t*>(y + (size_t)r * ld + j) = pack8(a, b);
   }
+}
+
+// dh <- dg * gelu'(h + bias), gelu'(v) = Phi(v) + v phi(v); dh may be dg.  Phi through erfc: 1 + erf(v / sqrt 2) loses every
+// digit of Phi in the left tail (v < -5), where v phi(v) is just as small and the derivative would be f32 noise.
+__device__ __forceinline__ float gelu_erf_grad(float v) {
+  return 0.5f * erfcf(v * -0.70710678118654752440f) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+}
+template <bool HAS_BIAS>
+__global__ __launch_bounds__(VIT_THREADS)
+void bias_gelu_bwd_kernel(const unsigned short* dg, const unsigned short* __restrict__ h, const float* __restrict__ bias, unsigned short* dh,
+                          unsigned nvec, unsigned cv /* cols/8 */, int ld) {
+  const unsigned stride = gridDim.x * VIT_THREADS;
+  for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const unsigned r = v / cv, j = (v - r * cv) << 3;
+    float x[8], g[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(h + (size_t)r * ld + j), x);
+    unpack8(*reinterpret_cast<const u32x4_t*>(dg + (size_t)r * ld + j), g);
+    if (HAS_BIAS) {
+      const f32x4_t b0 = *reinterpret_cast<const f32x4_t*>(bias + j), b1 = *reinterpret_cast<const f32x4_t*>(bias + j + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { x[e] += b0[e]; x[4 + e] += b1[e]; }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] *= gelu_erf_grad(x[e]);
+    *reinterpret_cast<u32x4_t*>(dh + (size_t)r * ld + j) = pack8(g);
+  }
+}
+
+// the checks and the row split the three GELU entries share; `launch(first row, vectors)` enqueues one piece
+template <typename Launch>
+int bias_gelu_run(const char* fn, const void* a, const void* b, const void* c, const float* bias, int64_t rows, int cols, int ld, Launch launch) {
+  if (!a || !b || !c || rows <= 0 || cols <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: null operand or rows=%lld cols=%d", fn, (long long)rows, cols);
+  if ((cols & 7) || (ld & 7) || ld < cols) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: cols=%d ld=%d (multiples of 8, ld >= cols)", fn, cols, ld);
+  if (!mmf_aligned16(a) || !mmf_aligned16(b) || !mmf_aligned16(c) || (bias && !mmf_aligned16(bias))) MMF_FAIL(MMF_E_ALIGN, "%s: pointers must be 16-byte aligned", fn);
+  const unsigned cv = (unsigned)cols >> 3;
+  const int64_t max_rows = (((int64_t)1 << 31) - 1) / cv;             // rows of one launch: 32-bit vector index
+  for (int64_t r0 = 0; r0 < rows; r0 += max_rows) {
+    const int64_t nr = rows - r0 < max_rows ? rows - r0 : max_rows;
+    launch(r0 * ld, (unsigned)(nr * cv), cv);
+    MMF_CHECK_LAUNCH(fn);
+  }
+  return MMF_OK;
+}
+
+int bias_gelu_fwd(const char* fn, const void* x_bf16, const float* bias, void* y_bf16, int64_t rows, int cols, int ld, void* stream) {
+  const unsigned short* x = static_cast<const unsigned short*>(x_bf16);
+  unsigned short* y = static_cast<unsigned short*>(y_bf16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return bias_gelu_run(fn, x, y, y, bias, rows, cols, ld, [&](int64_t off, unsigned nvec, unsigned cv) {
+    if (bias) hipLaunchKernelGGL(bias_gelu_kernel<true>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, x + off, y + off, bias, nvec, cv, ld);
+    else      hipLaunchKernelGGL(bias_gelu_kernel<false>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, x + off, y + off, bias, nvec, cv, ld);
+  });
 }
 
 }  // namespace
@@ -114,21 +166,20 @@ extern "C" int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls
 }
 
 extern "C" int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows, int cols, int ld, void* stream) {
-  if (!x_bf16 || rows <= 0 || cols <= 0) MMF_FAIL(MMF_E_SHAPE, "mmf_bias_gelu_bf16: null operand or rows=%lld cols=%d", (long long)rows, cols);
-  if ((cols & 7) || (ld & 7) || ld < cols)
-    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_bias_gelu_bf16: cols=%d ld=%d (multiples of 8, ld >= cols)", cols, ld);
-  if (!mmf_aligned16(x_bf16) || (bias && !mmf_aligned16(bias)))
-    MMF_FAIL(MMF_E_ALIGN, "mmf_bias_gelu_bf16: pointers must be 16-byte aligned");
-  const unsigned cv = (unsigned)cols >> 3;
-  const int64_t max_rows = (((int64_t)1 << 31) - 1) / cv;             // rows of one launch: 32-bit vector index
-  unsigned short* x = static_cast<unsigned short*>(x_bf16);
+  return bias_gelu_fwd("mmf_bias_gelu_bf16", x_bf16, bias, x_bf16, rows, cols, ld, stream);
+}
+
+extern "C" int mmf_bias_gelu_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, int64_t rows, int cols, int ld, void* stream) {
+  return bias_gelu_fwd("mmf_bias_gelu_bf16_to", h_bf16, bias, g_bf16, rows, cols, ld, stream);
+}
+
+extern "C" int mmf_bias_gelu_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols,
+                                      int ld, void* stream) {
+  const unsigned short *dg = static_cast<const unsigned short*>(dg_bf16), *h = static_cast<const unsigned short*>(h_bf16);
+  unsigned short* dh = static_cast<unsigned short*>(dh_bf16);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int64_t r0 = 0; r0 < rows; r0 += max_rows) {
-    const int64_t nr = rows - r0 < max_rows ? rows - r0 : max_rows;
-    const unsigned nvec = (unsigned)(nr * cv);
-    if (bias) hipLaunchKernelGGL(bias_gelu_kernel<true>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
-    else      hipLaunchKernelGGL(bias_gelu_kernel<false>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, x + r0 * ld, bias, nvec, cv, ld);
-    MMF_CHECK_LAUNCH("mmf_bias_gelu_bf16");
-  }
-  return MMF_OK;
+  return bias_gelu_run("mmf_bias_gelu_bwd_bf16", dg, h, dh, bias, rows, cols, ld, [&](int64_t off, unsigned nvec, unsigned cv) {
+    if (bias) hipLaunchKernelGGL(bias_gelu_bwd_kernel<true>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, dg + off, h + off, bias, dh + off, nvec, cv, ld);
+    else      hipLaunchKernelGGL(bias_gelu_bwd_kernel<false>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, dg + off, h + off, bias, dh + off, nvec, cv, ld);
+  });
 }

@@ -16,6 +16,7 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
       fc2 + bias + resid            mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> out
     _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
     _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
+    _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; NativeDeberta's backward)
 
 Parameters are stored as the kernels read them (Q/K/V fused, a subclass may store a weight with its last two dims swapped)
 and ``_hf`` maps every HuggingFace key to its view of them, in HuggingFace's order, so ``state_dict()`` and
@@ -24,7 +25,8 @@ names.  A subclass declares its workspace as a table of (name, elements per chun
 allocation and the bytes-per-item figure are both read from that table.  A forward pass writes no attribute of the module
 but that workspace and the ``_derived`` cache: what a launch needs beyond the buffers travels as arguments.
 
-Forward only and frozen: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  bf16
+Frozen: every parameter has ``requires_grad = False``.  Forward only, the outputs carrying no autograd graph, but for
+``NativeDeberta`` called with input embeddings that require a gradient (prompt tuning: mmfusion/deberta.py).  bf16
 storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
 Nothing synchronises with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.
 """
@@ -213,6 +215,18 @@ class FrozenBackbone(nn.Module):
                                                  ws["mean"].data_ptr(), ws["rstd"].data_ptr(), None, None, None, None, rows)],
                                       width, self.config.layer_norm_eps)
 
+    def _ln_bwd(self, scratch, src: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, gamma: str) -> None:
+        """dx = the LayerNorm input gradient of ``dy`` at the input ``src`` whose statistics are ``scratch["mean"]`` / ``["rstd"]``.
+        The kernel also sums the frozen gamma / beta's gradients: into ``scratch["dgb"]`` (2 width f32), zeroed here and discarded;
+        ``scratch["ln_ws"]``: its f32 workspace"""
+        rows, width = src.shape
+        dgb = scratch["dgb"]
+        dgb.zero_()
+        with lib._Timed("ln_bwd_kernel", 0.0, [(rows, width)]):
+            lib.layernorm_bwd_grouped([LnProblem(src.data_ptr(), None, self._f(gamma).data_ptr(), None, scratch["mean"].data_ptr(),
+                                                 scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgb.data_ptr(),
+                                                 dgb.data_ptr() + 4 * width, rows)], width, scratch["ln_ws"])
+
     def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
         """attention of ``Tq`` queries per item over its ``T`` keys, read from the fused ``qkv`` rows; ``Tq == 1`` takes the
         query of each item's first row"""
@@ -257,3 +271,8 @@ class FrozenBackbone(nn.Module):
     @staticmethod
     def _widen(src: torch.Tensor, dst: torch.Tensor) -> None:
         lib.check(lib.load().mmf_cast_bf16_to_f32(src.data_ptr(), dst.data_ptr(), src.numel(), lib.stream_ptr()))
+
+    @staticmethod
+    def _narrow(src: torch.Tensor, dst: torch.Tensor) -> None:
+        """contiguous f32 -> bf16, one rounding (an incoming gradient)"""
+        lib.check(lib.load().mmf_cast_f32_to_bf16(src.data_ptr(), dst.data_ptr(), src.numel(), lib.stream_ptr()))

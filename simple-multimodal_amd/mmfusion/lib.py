@@ -39,9 +39,9 @@ SYMBOLS = (
     "mmf_distill_kl", "mmf_fusion_loss_kd", "mmf_robust_head_fwd", "mmf_robust_head_bwd",
     "mmf_fewshot_proto_fwd", "mmf_fewshot_proto_bwd", "mmf_fewshot_dist_fwd", "mmf_fewshot_dist_bwd",
     "mmf_eval_accumulate",
-    "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16",
+    "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16", "mmf_bias_gelu_bf16_to", "mmf_bias_gelu_bwd_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
-    "mmf_deberta_embed", "mmf_deberta_attn_fwd",
+    "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
 )
 
@@ -220,12 +220,17 @@ def load() -> C.CDLL:
     lib.mmf_vit_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_vit_embed_tokens.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mmf_bias_gelu_bf16.argtypes = [vp, vp, i64, i32, i32, vp]
+    lib.mmf_bias_gelu_bf16_to.argtypes = [vp, vp, vp, i64, i32, i32, vp]
+    lib.mmf_bias_gelu_bwd_bf16.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp]
     lib.mmf_w2v_conv0_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_conv0_norm_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_w2v_gelu_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_posconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_deberta_embed.argtypes = [vp, vp, vp, vp, vp, f32, vp, i32, vp, i64, i32, i32, vp]
     lib.mmf_deberta_attn_fwd.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
+    lib.mmf_deberta_attn_fwd_lse.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    lib.mmf_deberta_attn_bwd.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    lib.mmf_deberta_embed_bwd.argtypes = [vp, vp, f32, vp, i32, vp, vp, i64, i32, vp]
     lib.mmf_video_prepare.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_video_prepare_patches.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_audio_resample.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, i64, i32, i32, i32, vp]
@@ -414,6 +419,30 @@ def bias_gelu(x, bias=None) -> None:
                                         x.stride(0), stream_ptr()))
 
 
+def _gelu_blocks(who: str, bias, *ts) -> None:
+    """2-D bf16 blocks of one shape and one row stride, contiguous rows; bias one f32 value per column or None"""
+    x = ts[0]
+    if any(t.dim() != 2 or t.stride(1) != 1 or t.shape != x.shape or t.stride(0) != x.stride(0) for t in ts) or (
+            bias is not None and (bias.numel() != x.shape[1] or not bias.is_contiguous())):
+        raise ValueError(f"{who}: 2-D blocks of one shape and row stride with contiguous rows, and bias one value per column")
+
+
+def bias_gelu_to(h, bias, g) -> None:
+    """g <- gelu(h + bias), h kept: the out-of-place form of ``bias_gelu``, bit-identical to it"""
+    _gelu_blocks("bias_gelu_to", bias, h, g)
+    with _Timed("bias_gelu_kernel", 0.0, [tuple(h.shape)]):
+        check(load().mmf_bias_gelu_bf16_to(h.data_ptr(), bias.data_ptr() if bias is not None else None, g.data_ptr(), h.shape[0],
+                                           h.shape[1], h.stride(0), stream_ptr()))
+
+
+def bias_gelu_bwd(dg, h, bias, dh) -> None:
+    """dh <- dg * gelu'(h + bias); ``h`` the stored linear output before its bias; ``dh`` may be ``dg``"""
+    _gelu_blocks("bias_gelu_bwd", bias, dg, h, dh)
+    with _Timed("bias_gelu_bwd_kernel", 0.0, [tuple(h.shape)]):
+        check(load().mmf_bias_gelu_bwd_bf16(dg.data_ptr(), h.data_ptr(), bias.data_ptr() if bias is not None else None, dh.data_ptr(),
+                                            h.shape[0], h.shape[1], h.stride(0), stream_ptr()))
+
+
 # ---- Wav2Vec2 kernels (csrc/wav2vec2.hip); tensors, not pointers: the shapes are checked here --------------
 W2V_STATS_SLOTS = 128            # MMF_W2V_STATS_SLOTS of include/mmfusion.h (tests/test_w2v_cpu.py compares the two)
 
@@ -527,21 +556,67 @@ def deberta_embed(out, table, gamma, beta, eps: float, ids=None, embeds=None, ma
                                        out.data_ptr(), rows, d, table.shape[0] if ids is not None else 0, stream_ptr()))
 
 
-def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S: int, scale: float, head_dim: int = 64) -> None:
-    """out (n T, H 64) bf16 = disentangled attention of the fused qkv rows (n T, 3 H 64); posq / posk (2S, H 64) bf16 views with a
-    common row stride; idx int32 (2T - 1,) (include/mmfusion.h states its contract); mask (n, T) or None"""
+def _deberta_attn_args(who: str, qkv, posq, posk, idx, out, n: int, H: int, T: int, S: int, head_dim: int) -> None:
     import torch
     _w2v_bf16(qkv, posq, posk, out)
     d = H * head_dim
     if not idx.is_cuda or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != 2 * T - 1:
-        raise ValueError("deberta_attn_fwd: idx must be a contiguous int32 GPU tensor of 2 T - 1 values")
+        raise ValueError(f"{who}: idx must be a contiguous int32 GPU tensor of 2 T - 1 values")
     if (qkv.numel() < n * T * 3 * d or out.numel() < n * T * d or not qkv.is_contiguous() or not out.is_contiguous()
             or tuple(posq.shape) != (2 * S, d) or tuple(posk.shape) != (2 * S, d) or posq.stride() != posk.stride() or posq.stride(1) != 1):
-        raise ValueError("deberta_attn_fwd: operand sizes do not match n, H, T, S")
+        raise ValueError(f"{who}: operand sizes do not match n, H, T, S")
+
+
+def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S: int, scale: float, head_dim: int = 64, lse=None) -> None:
+    """out (n T, H 64) bf16 = disentangled attention of the fused qkv rows (n T, 3 H 64); posq / posk (2S, H 64) bf16 views with a
+    common row stride; idx int32 (2T - 1,) (include/mmfusion.h states its contract); mask (n, T) or None.  With ``lse`` (f32, n H T
+    values) the launch also writes the rows' log-sum-exp for ``deberta_attn_bwd``; ``out`` is the same bits either way"""
+    _deberta_attn_args("deberta_attn_fwd", qkv, posq, posk, idx, out, n, H, T, S, head_dim)
+    if lse is not None:
+        _w2v_f32(lse)
+        if lse.numel() < n * H * T:
+            raise ValueError("deberta_attn_fwd: lse must hold n H T values")
     mp, kind = _deberta_mask(mask, n * T)
     with _Timed(f"deberta_attn_fwd_kernel<{head_dim}>", 12.0 * n * H * T * T * head_dim, [(T, T)]):
-        check(load().mmf_deberta_attn_fwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
-                                          out.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
+        if lse is None:
+            check(load().mmf_deberta_attn_fwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
+                                              out.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
+        else:
+            check(load().mmf_deberta_attn_fwd_lse(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
+                                                  out.data_ptr(), lse.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
+
+
+def deberta_attn_bwd(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv, n: int, H: int, T: int, S: int, scale: float,
+                     head_dim: int = 64) -> None:
+    """dqkv (n T, 3 H 64) bf16 <- the gradient of the fused qkv rows for the gradient ``dout`` (n T, H 64) of ``out``; ``out`` / ``lse``
+    as ``deberta_attn_fwd(..., lse=lse)`` wrote them; ``delta_ws`` f32 scratch of n H T values.  Every row of dqkv is written."""
+    _deberta_attn_args("deberta_attn_bwd", qkv, posq, posk, idx, out, n, H, T, S, head_dim)
+    _w2v_bf16(dout, dqkv)
+    _w2v_f32(lse, delta_ws)
+    d = H * head_dim
+    if (dout.numel() < n * T * d or dqkv.numel() < n * T * 3 * d or not dout.is_contiguous() or not dqkv.is_contiguous()
+            or lse.numel() < n * H * T or delta_ws.numel() < n * H * T):
+        raise ValueError("deberta_attn_bwd: operand sizes do not match n, H, T")
+    mp, kind = _deberta_mask(mask, n * T)
+    # the forward's three score products again, dP, and two products (content + position) for each of dQ and dK, and dV
+    with _Timed(f"deberta_attn_bwd_kernels<{head_dim}>", 22.0 * n * H * T * T * head_dim, [(T, T)]):
+        check(load().mmf_deberta_attn_bwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
+                                          out.data_ptr(), lse.data_ptr(), dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(),
+                                          n, H, T, S, head_dim, scale, stream_ptr()))
+
+
+def deberta_embed_bwd(embeds, gamma, eps: float, mask, dout, d_embeds) -> None:
+    """d_embeds (rows, d) f32 <- mask * the LayerNorm input gradient of ``dout`` (rows, d) bf16, the gradient of
+    ``deberta_embed(out, ..., embeds=embeds)``'s output"""
+    _w2v_f32(embeds, gamma, d_embeds)
+    _w2v_bf16(dout)
+    rows, d = dout.shape
+    if embeds.numel() != rows * d or d_embeds.numel() != rows * d or gamma.numel() != d or not dout.is_contiguous() or not d_embeds.is_contiguous():
+        raise ValueError("deberta_embed_bwd: embeds / d_embeds must hold (rows, d) values and gamma one value per column")
+    mp, kind = _deberta_mask(mask, rows)
+    with _Timed("deberta_embed_bwd_kernel", 0.0, [(rows, d)]):
+        check(load().mmf_deberta_embed_bwd(embeds.data_ptr(), gamma.data_ptr(), eps, mp, kind, dout.data_ptr(), d_embeds.data_ptr(), rows, d,
+                                           stream_ptr()))
 
 
 # ---- input preparation (csrc/prep.hip); tensors, not pointers: the shapes are checked here ------------------------

@@ -641,7 +641,9 @@ class FewShotTrainStep(FusionTrainStep):
     def reached_parameters(model: torch.nn.Module):
         """The trainable-by-name parameters a loss on ``predictions`` gives a gradient: the three encoders' adapters and
         ``prototype_network``, and ``prompt_embeddings`` only when the text encoder has a backbone (feature inputs bypass
-        the prompt, so torch leaves its ``.grad`` None).  ``support_encoder`` / ``query_encoder`` never run."""
+        the prompt, so torch leaves its ``.grad`` None).  That holds for the native text backbone too: ``NativeDeberta``
+        carries the gradient with respect to its input embeddings, so the prompt is moved by a real gradient there and
+        not by weight decay alone.  ``support_encoder`` / ``query_encoder`` never run."""
         text_backbone = getattr(model.base_model.text_encoder, "model", None) is not None
         out = []
         for n, p in model.named_parameters():

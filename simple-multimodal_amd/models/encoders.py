@@ -7,8 +7,9 @@ pool -> optional ``AdapterLayer`` -> ``projection`` Linear(hidden -> fusion_hidd
 self-attention heads run on the HIP kernels (``mmfusion.ops``).
 
 The HuggingFace backbones themselves (DeBERTa-v3 / Wav2Vec2 / ViT, reference :20,116,179) are third-party pretrained
-models fetched by name.  All three have native, frozen, forward-only forms on the HIP kernels that need no network
-(below).  The encoders take a ``backbone`` argument:
+models fetched by name.  All three have native, frozen forms on the HIP kernels that need no network (below): forward only,
+but for the text backbone's gradient with respect to its input embeddings, which is what prompt tuning needs.  The encoders
+take a ``backbone`` argument:
   * ``backbone=None`` (default) reproduces the reference: ``from_pretrained(config.*_model_name)``;
   * any ``nn.Module`` returning an object with ``.last_hidden_state`` is used as is;
   * ``config.video_backbone = "native"`` (dynamic attribute, ``VideoEncoder`` only) builds ``mmfusion.vit.NativeViT``: the
@@ -17,7 +18,9 @@ models fetched by name.  All three have native, frozen, forward-only forms on th
     the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers);
   * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
     same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
-    on the prompt route, from input embeddings;
+    on the prompt route, from input embeddings.  On that route, with grad mode on and ``prompt_embeddings.requires_grad``, the
+    backbone is called differentiably and ``prompt_embeddings`` trains through the frozen layers, as it does through
+    HuggingFace's model in the reference (:49-71);
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -87,9 +90,11 @@ def _backbone(config, kind: str, given: Optional[nn.Module]):
     return given, given.config.hidden_size, native
 
 
-def _run_backbone(fn, native: bool, *args, **kw):
-    """``fn(*args, **kw)``, under ``no_grad`` iff the backbone is the native one: that one is frozen"""
-    with torch.no_grad() if native else contextlib.nullcontext():
+def _run_backbone(fn, native: bool, *args, input_grad: bool = False, **kw):
+    """``fn(*args, **kw)``, under ``no_grad`` iff the backbone is the native one: that one is frozen.  ``input_grad``: the caller
+    wants the gradient with respect to the inputs it hands in (``NativeDeberta`` with ``inputs_embeds``: the prompt route),
+    so a native backbone is called in the caller's grad mode too"""
+    with torch.no_grad() if native and not input_grad else contextlib.nullcontext():
         return fn(*args, **kw)
 
 
@@ -162,7 +167,9 @@ class TextEncoder(_FusionBase):
             sequence_output = input_ids
         else:
             B = input_ids.size(0)
+            prompt_grad = False
             if use_prompt and self.prompt_embeddings is not None:        # reference :49-71
+                prompt_grad = torch.is_grad_enabled() and self.prompt_embeddings.requires_grad
                 pe = self.prompt_embeddings.unsqueeze(0).expand(B, -1, -1)
                 emb = self.model.embeddings.word_embeddings(input_ids)
                 pm = torch.ones(B, self.config.prompt_length, device=attention_mask.device, dtype=attention_mask.dtype)
@@ -170,7 +177,7 @@ class TextEncoder(_FusionBase):
                 kw = dict(inputs_embeds=torch.cat([pe, emb], dim=1), attention_mask=attention_mask)
             else:
                 kw = dict(input_ids=input_ids, attention_mask=attention_mask)
-            sequence_output = _run_backbone(self.model, self._native, **kw).last_hidden_state
+            sequence_output = _run_backbone(self.model, self._native, input_grad=prompt_grad, **kw).last_hidden_state
             cls_pool = "bert" in getattr(self.model.config, "model_type", "")     # reference :87
         if use_adapter and self.adapter is not None:
             sequence_output = self.adapter(sequence_output)

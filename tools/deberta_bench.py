@@ -6,10 +6,13 @@
     12 T^2 d per layer: QK^T, PV, and the two relative-position products at their bias-free size) of ``forward``, per chunk size;
   * the disentangled attention kernel alone beside ``mmf_attn_fwd_grouped`` on the same fused qkv rows: the bias-free, mask-free
     floor, and the ratio of the two (there is no pass mark: the new kernel forms two more products and gathers);
-  * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE).
+  * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE);
+  * with --grad, the prompt-tuning cost instead: for (items, tokens) = (16, 10 + 512) and (8, 10 + 128) on input embeddings, ms of
+    the inference forward, of the differentiable forward (it also keeps every layer's input) and of forward + backward, their
+    ratios to the inference forward, and the per-kernel table of one forward + backward.
 
-    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table]
-Prints one JSON line (the table, when asked for, on the lines before it)."""
+    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad]
+Prints one JSON line (the tables, when asked for, on the lines before it)."""
 import json
 import math
 
@@ -22,10 +25,39 @@ def gflop_per_item(cfg, T: int) -> float:
     return cfg.num_hidden_layers * (2.0 * T * (4 * d * d + 2 * d * I) + 12.0 * T * T * d) / 1e9
 
 
+def grad_mode(model, cfg, args) -> dict:
+    res = {"model": "deberta-v3-base, frozen, bf16 storage: gradient with respect to inputs_embeds", "chunk": model.chunk, "cases": []}
+    for N, T in ((16, 10 + 512), (8, 10 + 128)):
+        g = torch.Generator().manual_seed(2)
+        emb = torch.randn(N, T, cfg.hidden_size, generator=g).cuda()
+        leaf = emb.clone().requires_grad_(True)
+        dout = torch.randn(N, T, cfg.hidden_size, generator=g).cuda()
+        mask = torch.ones(N, T, dtype=torch.int64)
+        mask[1::2, T - 32:] = 0
+        mask = mask.cuda()
+
+        def infer():
+            with torch.no_grad():
+                model(inputs_embeds=emb, attention_mask=mask)
+        diff = lambda: model(inputs_embeds=leaf, attention_mask=mask)
+        both = lambda: torch.autograd.grad(model(inputs_embeds=leaf, attention_mask=mask).last_hidden_state, leaf, dout)
+        t_inf, t_diff, t_both = (time_eager(f, args.steps, args.warmup) for f in (infer, diff, both))
+        rows = kernel_table(both)
+        print(f"forward + backward, {N} items of {T} tokens")
+        print_table(rows)
+        res["cases"].append({"items": N, "tokens": T, "inference_forward_ms": round(t_inf, 3), "differentiable_forward_ms": round(t_diff, 3),
+                             "forward_backward_ms": round(t_both, 3), "differentiable_forward_ratio": round(t_diff / t_inf, 3),
+                             "forward_backward_ratio": round(t_both / t_inf, 3),
+                             "saved_inputs_mb": round(cfg.num_hidden_layers * N * T * cfg.hidden_size * 2 / 2 ** 20, 1),
+                             "grad_workspace_mb_per_item": round(model.grad_workspace_bytes_per_item(T) / 2 ** 20, 2), "kernels": rows})
+    return res
+
+
 def main():
     ap = parser(steps=5, warmup=2)
     ap.add_argument("--items", type=int, default=16)
     ap.add_argument("--tokens", type=int, default=512)
+    ap.add_argument("--grad", action="store_true")
     args = ap.parse_args()
     import deberta_ref
     from mmfusion import deberta, lib
@@ -34,6 +66,9 @@ def main():
     model = deberta.NativeDeberta(**deberta_ref.config_kwargs(cfg))
     model.load_state_dict(deberta_ref.seeded_weights(cfg, seed=0))
     model = model.cuda().eval()
+    if args.grad:
+        print(json.dumps(grad_mode(model, cfg, args)))
+        return
     N, T, d, H = args.items, args.tokens, cfg.hidden_size, cfg.num_attention_heads
     g = torch.Generator().manual_seed(1)
     ids = torch.randint(1, cfg.vocab_size, (N, T), generator=g).cuda()
