@@ -749,6 +749,23 @@ int mmf_deberta_attn_fwd_lse(const void* qkv_bf16, const void* posq_bf16, const 
 int mmf_deberta_attn_bwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
                          const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
                          float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, void* stream);
+/* mmf_deberta_attn_bwd plus the gradient of the position tables (fine-tuning: the layer's q / k weights also project the relative
+ * embeddings), summed over the n items of the call:
+ *   dposK[r] += sum_i A_ir Q_i        dposQ[r] += sum_j B_jr K_j        (A_ir / B_jr: the bucket sums of dS above)
+ * dqkv_bf16 is bit-identical to mmf_deberta_attn_bwd's for the same operands.  dposq / dposk: f32 (2S, H 64) with row stride ld_dpos
+ * (elements); the results are ADDED (the caller zeroes them once, calls accumulate); a row no (i, j) pair of the call maps to
+ * has 0 added.  The bucket sums are the bf16 values the position term of dQ / dK reads, contracted over a workgroup's 64 tokens by
+ * MFMA into that workgroup's own f32 partial table in `workspace`; a last launch sums the rows the partial tables hold in a fixed
+ * order: no floating-point atomics, bitwise repeatable.  workspace: mmf_deberta_attn_bwd_pos_workspace_bytes(n, H, T, S) bytes =
+ * 2 n ceil(T / 64) H (2S) 64 floats; it need not be initialised (a row is stored before it is added to or read) and holds
+ * nothing afterwards.  Four launches, no memset (a captured graph replays kernel nodes in order).  mmf_deberta_attn_bwd's limits and
+ * codes; null dposq / dposk / workspace, ld_dpos < H 64 or a workspace that is too small: MMF_E_SHAPE; dposq / dposk / workspace
+ * not 16-byte aligned or ld_dpos not a multiple of 4: MMF_E_ALIGN. */
+size_t mmf_deberta_attn_bwd_pos_workspace_bytes(int n, int H, int T, int S);
+int mmf_deberta_attn_bwd_pos(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                             const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                             float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale,
+                             float* dposq, float* dposk, int ld_dpos, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of mmf_deberta_embed on the embeds route: d_embeds (rows, d) f32 = mask[row] * the LayerNorm input gradient of
  * dout_bf16 (rows, d), the gradient of the kernel's bf16 output.  The row statistics are recomputed in f32 from embeds as the
  * forward computes them; rows with mask 0 are exactly 0.  mmf_deberta_embed's limits on d; embeds / gamma / d_embeds 16-byte

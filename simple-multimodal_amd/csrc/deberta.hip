@@ -5,6 +5,8 @@
 //           Scores, bias and probabilities live in registers and LDS only.  With LSE it also writes the rows' log-sum-exp.
 //   backward with respect to the inputs (the weights are frozen; prompt tuning): the embedding LayerNorm's input gradient, and
 //           the attention backward: a delta pre-pass, a dQ pass and a dK/dV pass from one kernel body, without atomics.
+//   the same backward with the gradient of the position tables posQ | posK (fine-tuning the layer's q / k weights, which also
+//           project the relative embeddings): a template flag of the two passes and a fixed-order reduction kernel.
 #include <float.h>
 #include "mmf_internal.h"
 
@@ -364,22 +366,40 @@ void deberta_attn_delta_kernel(const unsigned short* __restrict__ out, const uns
 // LDS: other rows 32 x 72 and their transpose 64 x 40 (9728 B), V | dO rows and (KPASS) dO^T (9728 B), T1 / dS 4 waves x 16 x 49
 // f32 (12544 B), T2 32 x 97 f32 (12416 B), the transposed position window 64 x 104 bf16 (13312 B), idx / run / per-row
 // values (1.5 KB): 59.3 KB, two workgroups per CU by LDS.
+//
+// The table gradients (POS; fine-tuning: the layer's q / k weights also project the relative embeddings).  The gradient of the
+// table a pass gathers with its own token's vector is "bucket sums x the own token's vector":
+//   dposK[r] += sum_i A_ir Q_i (dQ pass)      dposQ[r] += sum_j B_jr K_j (dK/dV pass)
+// i.e. the contraction over the block's 64 own tokens of the very bf16 sums the position term's B operand holds.  The sums go
+// through LDS (sA, in T2's buffer, which is free once the scores are gathered) to become the A operand, own tokens along k;
+// the B operand is the own tokens' vectors transposed, 16 head columns per wave, held in registers from the start:
+//   dTab [pos row][dh]      A = bucket sums [pos row][own] (LDS)  B = own^T [own][dh] (registers)
+// and the 16 x 16 results go to the workgroup's OWN (2S, 64) f32 partial table in global memory (`part`): no other workgroup
+// touches it, and the lanes of this one that meet at an address in successive tiles (the window moves with the tile) are
+// ordered by the tile's barriers.  The partial table is never cleared: idx is monotone, so the windows of successive tiles
+// overlap and move one way, a row outside the previous tile's window has not been written yet and is STORED, a row inside it
+// is added to; what a workgroup leaves behind is the rows idx(its smallest delta) .. idx(its largest delta), every one
+// written.  deberta_pos_reduce_kernel works that range out again and sums those rows of the partial tables in a fixed order.
+// Own tokens past T contribute zeros (their own^T entries are 0).
 constexpr int DB_TLD = 104, DB_TROWS = 96;
+constexpr int DB_ALD = 64;                                   // sA: 96 window rows x 64 own tokens bf16, 8-token groups XOR-swizzled by row
 
-template <bool KPASS>
+template <bool KPASS, bool POS>
 __global__ __launch_bounds__(DB_THREADS)
 void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ posq,
                              const unsigned short* __restrict__ posk, int ld_pos, const int* __restrict__ idx,
                              const void* __restrict__ mask, int mask_kind, const float* __restrict__ lse,
                              const unsigned short* __restrict__ dout, const float* __restrict__ delta,
-                             unsigned short* __restrict__ dqkv, int H, int T, int S2 /* 2 S */, float inv_scale) {
+                             unsigned short* __restrict__ dqkv, float* part /* POS: this pass's partial tables */,
+                             int H, int T, int S2 /* 2 S */, float inv_scale) {
+  static_assert(DB_TROWS * DB_ALD * 2 <= DB_BK * DB_PLD * 4, "sA must fit T2's buffer");
   __shared__ __attribute__((aligned(16))) unsigned short sO[DB_BK * DB_KLD];          // other rows: K | Q
   __shared__ __attribute__((aligned(16))) unsigned short sOt[DB_DH * DB_VLD];         // their transpose, db_slot order
   __shared__ __attribute__((aligned(16))) unsigned short sO2[DB_BK * DB_KLD];         // V | dO rows of the other tokens
   __shared__ __attribute__((aligned(16))) unsigned short sO2t[KPASS ? DB_DH * DB_VLD : 8];   // dO^T, db_slot order
   __shared__ __attribute__((aligned(16))) unsigned short sT[DB_DH * DB_TLD];          // posK^T | posQ^T over the block's window
   __shared__ float sC[4 * 16 * DB_CLD];
-  __shared__ float sP[DB_BK * DB_PLD];
+  __shared__ __attribute__((aligned(16))) float sP[DB_BK * DB_PLD];
   __shared__ int sIdx[DB_NIDX + 1], sFirst[DB_TROWS], sEnd[DB_TROWS];
   __shared__ float sOm[DB_BK], sLse[DB_BK], sDl[DB_BK];
 
@@ -411,6 +431,26 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
   const unsigned short* __restrict__ tab1 = (KPASS ? posq : posk) + h * DB_DH;        // gathered with the own token's vector
   const unsigned short* __restrict__ tab2 = (KPASS ? posk : posq) + h * DB_DH + q * 8;
 
+  // POS: own^T, B[k = own token ks * 32 + 8 q + e][col = head column 16 wave + r]; the partial table of this workgroup
+  bf16x8_t xt[2];
+  unsigned short* const sA = reinterpret_cast<unsigned short*>(sP);
+  float* const ptab = POS ? part + (((size_t)item * gridDim.x + blockIdx.x) * H + h) * ((size_t)S2 * DB_DH) + wave * 16 + r : nullptr;
+  if (POS) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      u32x4_t w;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int t0 = own0 + ks * 32 + q * 8 + 2 * e;
+        const unsigned lo = t0 < T ? base[(size_t)t0 * ld + (KPASS ? d : 0) + wave * 16 + r] : 0u;
+        const unsigned hi = t0 + 1 < T ? base[(size_t)(t0 + 1) * ld + (KPASS ? d : 0) + wave * 16 + r] : 0u;
+        w[e] = lo | (hi << 16);
+      }
+      xt[ks] = __builtin_bit_cast(bf16x8_t, w);
+    }
+  }
+
+  int plo = S2, phi = -1;                                        // POS: the previous tile's window (none yet)
   for (int o0 = 0; o0 < T; o0 += DB_BK) {
     __syncthreads();                                             // the previous tile's readers are done
     {
@@ -578,12 +618,42 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
         for (int t = t0; t < t1; ++t) sum += cw[r * DB_CLD + (ow + (DB_BK - 1) - t)];
         a[e] = sum;
       }
-      const bf16x8_t af = __builtin_bit_cast(bf16x8_t, pack8(a));
+      const u32x4_t aw = pack8(a);
+      const bf16x8_t af = __builtin_bit_cast(bf16x8_t, aw);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const bf16x8_t tf = *reinterpret_cast<const bf16x8_t*>(sT + (t * 16 + r) * DB_TLD + c * 32 + q * 8);
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, af, acc[t], 0, 0, 0);
       }
+      if (POS) {                                                 // the same bf16 sums -> sA[window row][own token]
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int row = c * 32 + q * 8 + e;
+          sA[row * DB_ALD + ((((ow >> 3) ^ (row & 7)) << 3) | (ow & 7))] = (unsigned short)((e & 1) ? aw[e >> 1] >> 16 : aw[e >> 1] & 0xffffu);
+        }
+      }
+    }
+    if (POS) {
+      __syncthreads();                                           // sA is complete
+      for (int rc = 0; rc < npc; ++rc) {
+        f32x4_t g = {0.f, 0.f, 0.f, 0.f};
+        const int row = rc * 16 + r;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const bf16x8_t sf = *reinterpret_cast<const bf16x8_t*>(sA + row * DB_ALD + (((ks * 4 + q) ^ (row & 7)) << 3));
+          g = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, xt[ks], g, 0, 0, 0);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int prow = lo_p + rc * 16 + q * 4 + e;           // hi_p <= 2 S - 1: never a row past the table
+          if (prow <= hi_p) {
+            float* dst = ptab + (size_t)prow * DB_DH;
+            *dst = (prow < plo || prow > phi) ? g[e] : *dst + g[e];      // first write of this row | a row of the previous window
+          }
+        }
+      }
+      plo = lo_p;
+      phi = hi_p;
     }
   }
   if (io < T) {
@@ -594,6 +664,39 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
       if (KPASS) *reinterpret_cast<u32x2_t*>(dst + d + t * 16) = u32x2_t{pack_bf16x2(accv[t][0], accv[t][1]), pack_bf16x2(accv[t][2], accv[t][3])};
     }
   }
+}
+
+// dposk | dposq (2S, H 64) f32 += the sum over the workgroups (item, block of 64 own tokens) of the dQ | dK/dV pass of the rows
+// their partial tables hold, block by block and item by item: one lane per element.  A workgroup of block b wrote the rows
+// idx(its smallest delta) .. idx(its largest delta), deltas and idx values clamped as the pass clamps them; the rest of its
+// table is not read.
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_pos_reduce_kernel(const float* __restrict__ part, const int* __restrict__ idx, float* __restrict__ dposq,
+                               float* __restrict__ dposk, int ld_dpos, int H, int T, int S2, int n, int nblk) {
+  const unsigned i = blockIdx.x * DB_THREADS + threadIdx.x;
+  const unsigned width = (unsigned)H * DB_DH;
+  if (i >= (unsigned)S2 * width) return;
+  const int row = (int)(i / width);
+  const unsigned col = i - (unsigned)row * width, h = col >> 6, dh = col & 63;
+  const bool kpass = blockIdx.y != 0;
+  const size_t stride = (size_t)H * S2 * DB_DH;
+  const float* __restrict__ src = part + (size_t)blockIdx.y * n * nblk * stride + ((size_t)h * S2 + row) * DB_DH + dh;
+  const int o_last = ((T - 1) / DB_BK) * DB_BK;
+  float sum = 0.0f;
+  for (int b = 0; b < nblk; ++b) {
+    int d0 = b * DB_BQ - o_last - (DB_BK - 1), d1 = b * DB_BQ + DB_BQ - 1;       // own - other over the block's tiles
+    if (kpass) { const int t = d0; d0 = -d1; d1 = -t; }                         // delta = other - own
+    d0 = d0 < -(T - 1) ? -(T - 1) : (d0 > T - 1 ? T - 1 : d0);
+    d1 = d1 < -(T - 1) ? -(T - 1) : (d1 > T - 1 ? T - 1 : d1);
+    int r0 = idx[d0 + T - 1], r1 = idx[d1 + T - 1];
+    r0 = r0 < 0 ? 0 : (r0 > S2 - 1 ? S2 - 1 : r0);
+    r1 = r1 < 0 ? 0 : (r1 > S2 - 1 ? S2 - 1 : r1);
+    if (row < (r0 < r1 ? r0 : r1) || row > (r0 < r1 ? r1 : r0)) continue;
+#pragma unroll 4
+    for (int item = 0; item < n; ++item) sum += src[((size_t)item * nblk + b) * stride];
+  }
+  float* __restrict__ dst = (kpass ? dposq : dposk) + (size_t)row * ld_dpos + col;
+  *dst += sum;
 }
 
 int db_mask_check(const char* fn, const void* mask, int mask_kind) {
@@ -676,14 +779,29 @@ extern "C" int mmf_deberta_attn_fwd_lse(const void* qkv_bf16, const void* posq_b
   return MMF_OK;
 }
 
-extern "C" int mmf_deberta_attn_bwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
-                                    const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
-                                    float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, void* stream) {
-  const char* fn = "mmf_deberta_attn_bwd";
+namespace {
+
+size_t db_pos_workspace_bytes(int n, int H, int T, int S) {      // two passes x (item, block of 64 tokens, head) x (2S, 64) f32
+  return (size_t)2 * n * ((T + DB_BQ - 1) / DB_BQ) * H * (2 * (size_t)S) * DB_DH * sizeof(float);
+}
+
+// both attention-backward entries: the checks they share, then delta, the dQ pass and the dK/dV pass; POS: the table gradients too
+template <bool POS>
+int db_attn_bwd(const char* fn, const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16, float* delta_ws,
+                void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, float* dposq, float* dposk, int ld_dpos,
+                void* workspace, size_t workspace_bytes, void* stream) {
   if (!lse || !dout_bf16 || !delta_ws || !dqkv_bf16) MMF_FAIL(MMF_E_SHAPE, "%s: null lse / dout / delta_ws / dqkv", fn);
+  if (POS && (!dposq || !dposk || !workspace)) MMF_FAIL(MMF_E_SHAPE, "%s: null dposq / dposk / workspace", fn);
   if (int rc = db_attn_check(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, n, H, T, S, head_dim, scale)) return rc;
+  if (POS && ld_dpos < H * DB_DH) MMF_FAIL(MMF_E_SHAPE, "%s: ld_dpos=%d is less than H * 64 = %d", fn, ld_dpos, H * DB_DH);
+  if (POS && workspace_bytes < db_pos_workspace_bytes(n, H, T, S))
+    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes, %zu needed (mmf_deberta_attn_bwd_pos_workspace_bytes)", fn, workspace_bytes,
+             db_pos_workspace_bytes(n, H, T, S));
   if (!mmf_aligned16(dout_bf16) || !mmf_aligned16(dqkv_bf16) || ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(delta_ws)) & 3u))
     MMF_FAIL(MMF_E_ALIGN, "%s: dout / dqkv must be 16-byte aligned, lse / delta_ws 4-byte aligned", fn);
+  if (POS && (!mmf_aligned16(dposq) || !mmf_aligned16(dposk) || !mmf_aligned16(workspace) || (ld_dpos & 3)))
+    MMF_FAIL(MMF_E_ALIGN, "%s: dposq / dposk / workspace must be 16-byte aligned, ld_dpos a multiple of 4", fn);
   if ((int64_t)n * T * H >= (int64_t)1 << 31) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: n * T * H = %lld (below 2^31)", fn, (long long)n * T * H);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned short *qkv = static_cast<const unsigned short*>(qkv_bf16), *pq = static_cast<const unsigned short*>(posq_bf16),
@@ -691,16 +809,45 @@ extern "C" int mmf_deberta_attn_bwd(const void* qkv_bf16, const void* posq_bf16,
   unsigned short* dqkv = static_cast<unsigned short*>(dqkv_bf16);
   const unsigned total = (unsigned)((int64_t)n * T * H);
   const dim3 grid((T + DB_BQ - 1) / DB_BQ, H, n);
+  float* part = static_cast<float*>(workspace);
+  const size_t pass_elems = POS ? db_pos_workspace_bytes(n, H, T, S) / (2 * sizeof(float)) : 0;
   hipLaunchKernelGGL(deberta_attn_delta_kernel, dim3((total + DB_THREADS - 1) / DB_THREADS), dim3(DB_THREADS), 0, s,
                      static_cast<const unsigned short*>(out_bf16), dout, delta_ws, H, T, total);
   MMF_CHECK_LAUNCH(fn);
-  hipLaunchKernelGGL(deberta_attn_bwd_kernel<false>, grid, dim3(DB_THREADS), 0, s, qkv, pq, pk, ld_pos, idx, mask, mask_kind, lse, dout,
-                     static_cast<const float*>(delta_ws), dqkv, H, T, 2 * S, 1.0f / scale);
+  hipLaunchKernelGGL((deberta_attn_bwd_kernel<false, POS>), grid, dim3(DB_THREADS), 0, s, qkv, pq, pk, ld_pos, idx, mask, mask_kind, lse, dout,
+                     static_cast<const float*>(delta_ws), dqkv, part, H, T, 2 * S, 1.0f / scale);
   MMF_CHECK_LAUNCH(fn);
-  hipLaunchKernelGGL(deberta_attn_bwd_kernel<true>, grid, dim3(DB_THREADS), 0, s, qkv, pq, pk, ld_pos, idx, mask, mask_kind, lse, dout,
-                     static_cast<const float*>(delta_ws), dqkv, H, T, 2 * S, 1.0f / scale);
+  hipLaunchKernelGGL((deberta_attn_bwd_kernel<true, POS>), grid, dim3(DB_THREADS), 0, s, qkv, pq, pk, ld_pos, idx, mask, mask_kind, lse, dout,
+                     static_cast<const float*>(delta_ws), dqkv, POS ? part + pass_elems : part, H, T, 2 * S, 1.0f / scale);
   MMF_CHECK_LAUNCH(fn);
+  if (POS) {
+    const unsigned elems = (unsigned)(2 * S) * H * DB_DH;
+    hipLaunchKernelGGL(deberta_pos_reduce_kernel, dim3((elems + DB_THREADS - 1) / DB_THREADS, 2), dim3(DB_THREADS), 0, s, part, idx, dposq, dposk,
+                       ld_dpos, H, T, 2 * S, n, (int)grid.x);
+    MMF_CHECK_LAUNCH(fn);
+  }
   return MMF_OK;
+}
+
+}  // namespace
+
+extern "C" int mmf_deberta_attn_bwd(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                                    const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                                    float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, void* stream) {
+  return db_attn_bwd<false>("mmf_deberta_attn_bwd", qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, dout_bf16,
+                            delta_ws, dqkv_bf16, n, H, T, S, head_dim, scale, nullptr, nullptr, 0, nullptr, 0, stream);
+}
+
+extern "C" size_t mmf_deberta_attn_bwd_pos_workspace_bytes(int n, int H, int T, int S) {
+  return n > 0 && H > 0 && T > 0 && S > 0 ? db_pos_workspace_bytes(n, H, T, S) : 0;
+}
+
+extern "C" int mmf_deberta_attn_bwd_pos(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                                        const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                                        float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale,
+                                        float* dposq, float* dposk, int ld_dpos, void* workspace, size_t workspace_bytes, void* stream) {
+  return db_attn_bwd<true>("mmf_deberta_attn_bwd_pos", qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, dout_bf16,
+                           delta_ws, dqkv_bf16, n, H, T, S, head_dim, scale, dposq, dposk, ld_dpos, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, float eps, const void* mask, int mask_kind,

@@ -26,7 +26,8 @@ allocation and the bytes-per-item figure are both read from that table.  A forwa
 but that workspace and the ``_derived`` cache: what a launch needs beyond the buffers travels as arguments.
 
 Frozen: every parameter has ``requires_grad = False``.  Forward only, the outputs carrying no autograd graph, but for
-``NativeDeberta`` called with input embeddings that require a gradient (prompt tuning: mmfusion/deberta.py).  bf16
+``NativeDeberta``: called with input embeddings that require a gradient (prompt tuning), or with its top layers marked
+trainable (``set_trainable_layers``: those layers' parameters then require a gradient), mmfusion/deberta.py.  bf16
 storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
 Nothing synchronises with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.
 """
@@ -215,17 +216,22 @@ class FrozenBackbone(nn.Module):
                                                  ws["mean"].data_ptr(), ws["rstd"].data_ptr(), None, None, None, None, rows)],
                                       width, self.config.layer_norm_eps)
 
-    def _ln_bwd(self, scratch, src: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, gamma: str) -> None:
+    def _ln_bwd(self, scratch, src: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, gamma: str, into=None) -> None:
         """dx = the LayerNorm input gradient of ``dy`` at the input ``src`` whose statistics are ``scratch["mean"]`` / ``["rstd"]``.
-        The kernel also sums the frozen gamma / beta's gradients: into ``scratch["dgb"]`` (2 width f32), zeroed here and discarded;
-        ``scratch["ln_ws"]``: its f32 workspace"""
+        The kernel also sums gamma / beta's gradients.  Frozen parameters (``into`` None): into ``scratch["dgb"]`` (2 width f32),
+        zeroed here and discarded.  Trainable ones: ``into`` = (dgamma, dbeta), the parameters' f32 gradients, which the kernel
+        adds to.  ``scratch["ln_ws"]``: its f32 workspace"""
         rows, width = src.shape
-        dgb = scratch["dgb"]
-        dgb.zero_()
+        if into is None:
+            dgb = scratch["dgb"]
+            dgb.zero_()
+            dgamma, dbeta = dgb.data_ptr(), dgb.data_ptr() + 4 * width
+        else:
+            dgamma, dbeta = into[0].data_ptr(), into[1].data_ptr()
         with lib._Timed("ln_bwd_kernel", 0.0, [(rows, width)]):
             lib.layernorm_bwd_grouped([LnProblem(src.data_ptr(), None, self._f(gamma).data_ptr(), None, scratch["mean"].data_ptr(),
-                                                 scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgb.data_ptr(),
-                                                 dgb.data_ptr() + 4 * width, rows)], width, scratch["ln_ws"])
+                                                 scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma, dbeta, rows)],
+                                      width, scratch["ln_ws"])
 
     def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
         """attention of ``Tq`` queries per item over its ``T`` keys, read from the fused ``qkv`` rows; ``Tq == 1`` takes the

@@ -1,5 +1,6 @@
-"""Frozen DeBERTa-v3 backbone on the HIP kernels: token ids (or input embeddings) + attention mask -> token states, with the
-gradient with respect to the input embeddings (prompt tuning); the weights never train.
+"""DeBERTa-v3 backbone on the HIP kernels: token ids (or input embeddings) + attention mask -> token states, with the gradient
+with respect to the input embeddings (prompt tuning) and, for the top layers marked trainable, to their weights (fine-tuning);
+frozen by default.
 
 The reference pushes every batch of token ids through HuggingFace's ``AutoModel`` for ``microsoft/deberta-v3-base`` (reference
 models/encoders.py:20,49-71).  ``NativeDeberta`` is ``DebertaV2Model`` rebuilt from its sizes alone (nothing is fetched), with
@@ -61,6 +62,23 @@ in the GEMM epilogue and rounded once); the incoming gradient of ``last_hidden_s
 one is f32.  The recomputation reuses the forward workspace; what the backward holds beside it (the second pre-LN sum, the GELU
 output beside ``h``, both LayerNorms' statistics, lse, the gradient buffers and scratch) is a table of its own
 (``_grad_table``), allocated on the first differentiable call.
+
+The top-K weight gradients.  ``set_trainable_layers(k)`` marks the parameters of layers ``L - k .. L - 1`` trainable; with grad
+mode on every call is then the differentiable one (the trainable parameters are inputs of the ``autograd.Function``, so the ids
+route carries a graph too), it keeps the inputs of the layers the backward will walk only (``>= L - k``, all when the
+embeddings need a gradient as well), and the backward of a trainable layer adds, in stream order where the operands stand,
+
+      dW_fc2 += dy2^T gel   dW_fc1 += dh^T ln   dW_o += dy1^T att   dW_qkv += dqkv^T x     mmf_gemm_grouped TN, COLSUM_A (the biases)
+      both LayerNorms' dgamma / dbeta                                                     mmf_layernorm_bwd_grouped, into .grad
+      d(posQ | posK) += ...                                                               mmf_deberta_attn_bwd_pos (4 launches)
+
+into the parameters' f32 ``.grad`` (the arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it), and stops after the lowest
+trainable layer's weight gradients when the embeddings need none.  The layer's q / k weights are used twice, on the tokens and on
+LayerNorm(rel_embeddings): the f32 (2S, 2d) gradient of posQ | posK is summed over the chunks, rounded to bf16 once (where the
+forward stores the tables) and two TN GEMMs against ``rel`` add ``dW_qkv[:2d] += dpos^T rel`` and ``db_q += colsum(dposQ)``
+(``colsum(dposK)`` is zero in exact arithmetic, the rows of dS summing to zero, so ``db_k`` takes none).
+A trainable layer's tables are computed in every call (the optimiser writes weights through raw pointers: no version counter
+moves).  ``rel_embeddings``, the encoder LayerNorm, the word embeddings and the embedding LayerNorm stay frozen.
 """
 from __future__ import annotations
 
@@ -73,7 +91,7 @@ import torch
 from . import arena as _arena
 from . import lib, ops
 from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
-from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NN, GEMM_NT
+from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, GEMM_NN, GEMM_NT, GEMM_TN
 
 # items per pass through the workspace.  NOT chosen by measurement yet: 16 items of 512 tokens give the layer GEMMs 8192 rows
 # at 0.14 GB of workspace; tools/deberta_bench.py --chunks is the sweep that should decide it
@@ -115,22 +133,34 @@ class _WordEmbeddings:
             return torch.nn.functional.embedding(input_ids, self.weight)
 
 
-class _InputGrad(torch.autograd.Function):
-    """``NativeDeberta._run`` on input embeddings, differentiable with respect to them"""
+class _Differentiable(torch.autograd.Function):
+    """``NativeDeberta._run``, differentiable with respect to ``inputs_embeds`` and to the parameters of the trainable layers.
+    ``params`` are those parameters: they are inputs so that the result carries a graph on the ids route too; their gradients
+    are not returned but added into their f32 ``.grad`` by the backward's own launches, as ``ops.queue_wgrad``'s are."""
 
     @staticmethod
-    def forward(ctx, model: "NativeDeberta", embeds: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
-        N, T, d = embeds.shape
-        keep = torch.empty((model.config.num_hidden_layers, N * T, d), dtype=BF16, device=embeds.device)
-        out = model._run(embeds, mask, False, keep)
-        ctx.model, ctx.mask = model, mask
-        ctx.save_for_backward(embeds, keep)
+    def forward(ctx, model: "NativeDeberta", src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, *params) -> torch.Tensor:
+        N, T = src.shape[:2]
+        L, d = model.config.num_hidden_layers, model.config.hidden_size
+        need_in = not by_ids and ctx.needs_input_grad[1]
+        first = 0 if need_in else L - model.trainable_layers          # the lowest layer the backward walks
+        keep = torch.empty((L - first, N * T, d), dtype=BF16, device=src.device)
+        _arena.ensure(model)
+        pos = model._pos_tables(src.device)
+        out = model._run(src, mask, by_ids, keep, first, pos)
+        ctx.model, ctx.mask, ctx.by_ids, ctx.first, ctx.pos, ctx.k = model, mask, by_ids, first, pos, model.trainable_layers
+        ctx.save_for_backward(src, keep)
         return out
 
     @staticmethod
     def backward(ctx, dout: torch.Tensor):
-        embeds, keep = ctx.saved_tensors
-        return None, ctx.model._input_grad(embeds, ctx.mask, keep, dout.contiguous()), None
+        src, keep = ctx.saved_tensors
+        need_in = not ctx.by_ids and ctx.needs_input_grad[1]
+        k = ctx.k if any(ctx.needs_input_grad[4:]) else 0         # (torch.autograd.grad for the embeddings alone: no weight gradients)
+        grad = None
+        if need_in or k:
+            grad = ctx.model._backward(src, ctx.by_ids, ctx.mask, keep, ctx.first, ctx.pos, dout.contiguous(), need_in, k)
+        return (None, grad, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
 
 
 class NativeDeberta(FrozenBackbone):
@@ -140,7 +170,8 @@ class NativeDeberta(FrozenBackbone):
     ``input_ids`` (N, T) int64 or ``inputs_embeds`` (N, T, hidden) f32, on the GPU, exactly one of them; ``attention_mask``
     (N, T) of any integer / bool / float dtype, or None for all ones.  Masked keys get probability exactly 0; a masked query
     row attends uniformly over all T keys, so padded rows of the result are HuggingFace's too.  With grad mode on and
-    ``inputs_embeds.requires_grad`` the result carries the gradient with respect to ``inputs_embeds``.
+    ``inputs_embeds.requires_grad`` the result carries the gradient with respect to ``inputs_embeds``; after
+    ``set_trainable_layers(k)``, ``k > 0``, every call in grad mode carries the top ``k`` layers' weight gradients.
     ``state_dict()`` has the keys, shapes and order of ``DebertaV2Model``; Q/K/V are stored fused and split on the way."""
 
     def __init__(self, vocab_size: int = 128100, hidden_size: int = 768, num_hidden_layers: int = 12, num_attention_heads: int = 12,
@@ -201,6 +232,31 @@ class NativeDeberta(FrozenBackbone):
         self.embeddings = types.SimpleNamespace(word_embeddings=_WordEmbeddings(self))
         self._idx: Dict[Tuple, torch.Tensor] = {}      # (T, S, max position, device) -> the int32 table on that device
         self._gws: Optional[dict] = None               # the backward's workspace (_grad_table), from the first differentiable call
+        self._trainable = 0                            # set_trainable_layers
+
+    # -- fine-tuning the top layers ----------------------------------------------------------------------
+    @staticmethod
+    def _layer_params(i: int) -> list:
+        return [f"l{i}_{r}_{s}" for r in ("qkv", "o", "ln1", "fc1", "fc2", "ln2") for s in "wb"]
+
+    @property
+    def trainable_layers(self) -> int:
+        return self._trainable
+
+    def set_trainable_layers(self, k: int) -> None:
+        """The parameters of the top ``k`` layers (``L - k .. L - 1``) get ``requires_grad = True``, every other parameter
+        ``False``; 0 freezes the backbone again.  With grad mode on and ``k > 0`` a call returns a result that carries a graph,
+        and its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops below
+        layer ``L - k`` unless ``inputs_embeds`` needs a gradient too.  Out of scope, frozen whatever ``k``: ``rel_embeddings``,
+        the encoder LayerNorm, the word embeddings and the embedding LayerNorm (their gradient would need every layer's
+        position path).  The backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
+        L = self.config.num_hidden_layers
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
+            raise ValueError(f"NativeDeberta: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
+        self._trainable = k
+        top = {n for i in range(L - k, L) for n in self._layer_params(i)}
+        for name, p in self.named_parameters(recurse=False):
+            p.requires_grad_(name in top)
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -240,6 +296,16 @@ class NativeDeberta(FrozenBackbone):
         self._gws = g
         return g
 
+    def _pos_workspace(self, g: dict, n: int, T: int) -> torch.Tensor:
+        """``mmf_deberta_attn_bwd_pos``'s workspace for chunks of up to ``n`` items of ``T`` tokens, kept beside the backward's
+        buffers and grown on demand"""
+        c = self.config
+        need = lib.deberta_attn_bwd_pos_workspace_bytes(n, c.num_attention_heads, T, c.position_buckets) // 4
+        w = g.get("pos_ws")
+        if w is None or w.numel() < need:
+            w = g["pos_ws"] = torch.empty(need, dtype=torch.float32, device=g["dev"])
+        return w
+
     def _index(self, T: int, dev) -> torch.Tensor:
         c = self.config
         key = (T, c.position_buckets, c.max_position_embeddings, dev)
@@ -255,23 +321,35 @@ class NativeDeberta(FrozenBackbone):
         return t
 
     # -- weights ----------------------------------------------------------------------------------------
-    def _pos_tables(self, dev) -> list:
-        """per layer (posQ, posK) = the layer's q / k projection (bias included) of LayerNorm(rel_embeddings): bf16 (2S, d) views
-        of one (2S, 2d) GEMM output, computed on the HIP kernels once per weight version"""
+    def _pos_cache(self, dev) -> tuple:
+        """(LayerNorm(rel_embeddings) as bf16 (2S, d), [(posQ, posK) of every FROZEN layer]): what depends on frozen weights only,
+        one mmf_deberta_embed launch on the relative table and one GEMM per frozen layer, once per weight version"""
         c = self.config
-        d, rows = c.hidden_size, 2 * c.position_buckets
+        frozen = c.num_hidden_layers - self._trainable
 
         def build():
-            rel = torch.empty((rows, d), dtype=BF16, device=dev)
+            rel = torch.empty((2 * c.position_buckets, c.hidden_size), dtype=BF16, device=dev)
             lib.deberta_embed(rel, None, self._f("enc_ln_w"), self._f("enc_ln_b"), c.layer_norm_eps, embeds=self._f("rel_emb"))
-            pos = []
-            for i in range(c.num_hidden_layers):
-                qk = torch.empty((rows, 2 * d), dtype=BF16, device=dev)
-                ops.gemm(GEMM_NT, rel, self._w(f"l{i}_qkv_w")[:2 * d], qk, bias=self._f(f"l{i}_qkv_b")[:2 * d], epilogue=EPI_BIAS)
-                pos.append((qk[:, :d], qk[:, d:]))
-            return pos
-        names = ["rel_emb", "enc_ln_w", "enc_ln_b"] + [f"l{i}_qkv_{s}" for i in range(c.num_hidden_layers) for s in "wb"]
+            return rel, [self._pos_of(i, rel) for i in range(frozen)]
+        names = ["rel_emb", "enc_ln_w", "enc_ln_b"] + [f"l{i}_qkv_{s}" for i in range(frozen) for s in "wb"]
         return self._derived("pos", names, build)
+
+    def _rel(self, dev) -> torch.Tensor:
+        return self._pos_cache(dev)[0]
+
+    def _pos_of(self, i: int, rel: torch.Tensor) -> tuple:
+        d = self.config.hidden_size
+        qk = torch.empty((rel.shape[0], 2 * d), dtype=BF16, device=rel.device)
+        ops.gemm(GEMM_NT, rel, self._w(f"l{i}_qkv_w")[:2 * d], qk, bias=self._f(f"l{i}_qkv_b")[:2 * d], epilogue=EPI_BIAS)
+        return qk[:, :d], qk[:, d:]
+
+    def _pos_tables(self, dev) -> list:
+        """per layer (posQ, posK) = the layer's q / k projection (bias included) of LayerNorm(rel_embeddings): bf16 (2S, d) views
+        of one (2S, 2d) GEMM output.  A frozen layer's are computed once per weight version.  A trainable layer's are computed in
+        every call, from the cached frozen ``rel``: the optimiser writes masters and shadows through raw pointers, which moves
+        no version counter, so nothing derived from a trainable weight may be cached"""
+        rel, pos = self._pos_cache(dev)
+        return list(pos) + [self._pos_of(i, rel) for i in range(len(pos), self.config.num_hidden_layers)]
 
     # -- launches ---------------------------------------------------------------------------------------
     def _layer(self, i: int, ws, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor]) -> None:
@@ -306,16 +384,20 @@ class NativeDeberta(FrozenBackbone):
                 raise ValueError(f"{who}: attention_mask {tuple(attention_mask.shape)} is not (N, T) = ({N}, {T}) on the inputs' device")
             mask = attention_mask if attention_mask.dtype in (torch.float32, torch.uint8, torch.bool) else attention_mask.to(torch.float32)
             mask = mask.contiguous()
-        if inputs_embeds is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
-            return BackboneOutput(_InputGrad.apply(self, src, mask))
+        if torch.is_grad_enabled() and (self._trainable > 0 or (inputs_embeds is not None and inputs_embeds.requires_grad)):
+            L = c.num_hidden_layers
+            params = [getattr(self, n) for i in range(L - self._trainable, L) for n in self._layer_params(i)]
+            return BackboneOutput(_Differentiable.apply(self, src, mask, input_ids is not None, *params))
         return BackboneOutput(self._run(src, mask, input_ids is not None))
 
-    def _run(self, src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """the launch list on checked inputs -> (N, T, d) f32; ``keep`` (layers, N T, d) bf16: also copy every layer's input there"""
+    def _run(self, src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, keep: Optional[torch.Tensor] = None,
+             first: int = 0, pos: Optional[list] = None) -> torch.Tensor:
+        """the launch list on checked inputs -> (N, T, d) f32; ``keep`` (layers - first, N T, d) bf16: also copy the input of every
+        layer from ``first`` up there; ``pos``: the layers' position tables where the caller has them already"""
         c, d, dev = self.config, self.config.hidden_size, src.device
         N, T = src.shape[:2]
         _arena.ensure(self)
-        pos, idx = self._pos_tables(dev), self._index(T, dev)
+        pos, idx = self._pos_tables(dev) if pos is None else pos, self._index(T, dev)
         ws = self._workspace(dev, T)
         out = torch.empty((N, T, d), dtype=torch.float32, device=dev)
         table, gamma, beta = self._f("word_emb"), self._f("emb_ln_w"), self._f("emb_ln_b")
@@ -328,23 +410,36 @@ class NativeDeberta(FrozenBackbone):
             else:
                 lib.deberta_embed(x, None, gamma, beta, c.layer_norm_eps, embeds=part, mask=m)
             for i in range(c.num_hidden_layers):
-                if keep is not None:
-                    keep[i, n0 * T:(n0 + n) * T].copy_(x)
+                if keep is not None and i >= first:
+                    keep[i - first, n0 * T:(n0 + n) * T].copy_(x)
                 self._layer(i, ws, n, T, pos[i], idx, m)
             self._widen(x, out[n0:n0 + n])
         return out
 
-    # -- the input gradient ---------------------------------------------------------------------------------
-    def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor]) -> None:
+    # -- the backward: input gradient and the trainable layers' weight gradients -------------------------------------
+    def _wgrad(self, dy: torch.Tensor, x: torch.Tensor, name: str) -> None:
+        """``l{i}_{role}``'s weight gradient += dy^T x and bias gradient += colsum(dy), now, in stream order (the operands are
+        workspace views the next launch overwrites).  The arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it: the first
+        write of a step into a lazily zeroed weight gradient overwrites, every later one accumulates"""
+        w, b = getattr(self, name + "_w").grad, getattr(self, name + "_b").grad
+        ar = _arena.arena_of(w)
+        overwrite = ar is not None and ar.take_first_touch(w)
+        ops.gemm_group(GEMM_TN, [(dy, x, w, b, None)], (0 if overwrite else EPI_ACCUM) | EPI_COLSUM_A)
+
+    def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor],
+                    dpos: Optional[torch.Tensor] = None, below: bool = True) -> None:
         """layer ``i`` again from its saved input ``xin``, then its backward: ``ga`` holds the gradient of the layer's output on
-        entry and of ``xin`` on return"""
+        entry and, with ``below``, of ``xin`` on return.  ``dpos`` (2S, 2d) f32, for a trainable layer: the layer's weight, bias
+        and LayerNorm gradients are added into the parameters' ``.grad`` and the gradient of posQ | posK into ``dpos``"""
         c, scale = self.config, math.sqrt(3.0 * self.head_dim)
         rows, d, H, S, I = n * T, c.hidden_size, c.num_attention_heads, c.position_buckets, c.intermediate_size
         R = self._rows
+        train = dpos is not None
         ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
         ln, h, qkv, att = R(ws, "ln", rows, d), R(ws, "h", rows, I), R(ws, "qkv", rows, 3 * d), R(ws, "att", rows, d)
         st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
         st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        lng = lambda r: (getattr(self, f"l{i}_{r}_w").grad, getattr(self, f"l{i}_{r}_b").grad) if train else None
 
         def attend(qkv_: torch.Tensor, att_: torch.Tensor) -> None:
             lib.deberta_attn_fwd(qkv_, pos[0], pos[1], idx, mask, att_, n, H, T, S, scale, self.head_dim, lse=g["lse"])
@@ -355,31 +450,62 @@ class NativeDeberta(FrozenBackbone):
         ops.gemm(GEMM_NT, gel, self._w(f"l{i}_fc2_w"), y2, bias=self._f(f"l{i}_fc2_b"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
         self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
 
-        self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w")                                  # gb = dy2
+        self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w", lng("ln2"))                      # gb = dy2
+        if train:
+            self._wgrad(gb, gel, f"l{i}_fc2")
         ops.gemm(GEMM_NN, gb, self._w(f"l{i}_fc2_w"), dh)                             # dg
         lib.bias_gelu_bwd(dh, h, self._f(f"l{i}_fc1_b"), dh)
+        if train:
+            self._wgrad(dh, ln, f"l{i}_fc1")
         ops.gemm(GEMM_NN, dh, self._w(f"l{i}_fc1_w"), ga, aux=gb, epilogue=EPI_ADD_AUX)          # ga = dln1: the MLP branch + the residual
-        self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w")                                  # gb = dy1
+        self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w", lng("ln1"))                      # gb = dy1
+        if train:
+            self._wgrad(gb, att, f"l{i}_o")
         ops.gemm(GEMM_NN, gb, self._w(f"l{i}_o_w"), ga)                               # ga = datt
-        lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], ga, g["delta"], dqkv, n, H, T, S, scale, self.head_dim)
-        ops.gemm(GEMM_NN, dqkv, self._w(f"l{i}_qkv_w"), ga, aux=gb, epilogue=EPI_ADD_AUX)        # ga = dx: the attention branch + the residual
+        if train:
+            lib.deberta_attn_bwd_pos(qkv, pos[0], pos[1], idx, mask, att, g["lse"], ga, g["delta"], dqkv, dpos[:, :d], dpos[:, d:],
+                                     self._pos_workspace(g, n, T), n, H, T, S, scale, self.head_dim)
+            self._wgrad(dqkv, xin, f"l{i}_qkv")
+        else:
+            lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], ga, g["delta"], dqkv, n, H, T, S, scale, self.head_dim)
+        if below:
+            ops.gemm(GEMM_NN, dqkv, self._w(f"l{i}_qkv_w"), ga, aux=gb, epilogue=EPI_ADD_AUX)    # ga = dx: the attention branch + the residual
 
-    def _input_grad(self, embeds: torch.Tensor, mask: Optional[torch.Tensor], keep: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
-        """d ``inputs_embeds`` (N, T, d) f32 for the gradient ``dout`` (N, T, d) f32 of the result; ``keep``: the layers' saved inputs"""
-        c, d, dev = self.config, self.config.hidden_size, embeds.device
-        N, T = embeds.shape[:2]
+    def _backward(self, src: torch.Tensor, by_ids: bool, mask: Optional[torch.Tensor], keep: torch.Tensor, first: int, pos: list,
+                  dout: torch.Tensor, need_in: bool, k: int) -> Optional[torch.Tensor]:
+        """for the gradient ``dout`` (N, T, d) f32 of the result: with ``need_in``, -> d ``inputs_embeds`` (N, T, d) f32; with
+        ``k > 0``, the gradients of the top ``k`` layers' parameters, added into their ``.grad``.  ``keep``: the saved inputs of
+        the layers from ``first`` up, ``pos``: the position tables the forward used.  Without ``need_in`` the walk ends with
+        layer ``first``'s weight gradients"""
+        c, d, dev = self.config, self.config.hidden_size, src.device
+        N, T = src.shape[:2]
+        L, S2 = c.num_hidden_layers, 2 * c.position_buckets
         if ops.fp32_mode():
             raise RuntimeError("NativeDeberta runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
-        pos, idx = self._pos_tables(dev), self._index(T, dev)
+        idx = self._index(T, dev)
         ws, g = self._workspace(dev, T), self._grad_workspace(dev, T)
-        grad = torch.empty((N, T, d), dtype=torch.float32, device=dev)
+        grad = torch.empty((N, T, d), dtype=torch.float32, device=dev) if need_in else None
+        # the gradient of posQ | posK of each trainable layer, summed over the chunks in f32
+        dpos = torch.zeros((k, S2, 2 * d), dtype=torch.float32, device=dev) if k else None
         for n0 in range(0, N, self.chunk):
             n = min(self.chunk, N - n0)
             rows = slice(n0 * T, (n0 + n) * T)
             m = None if mask is None else mask[n0:n0 + n]
             ga = self._rows(g, "ga", n * T, d)
             self._narrow(dout[n0:n0 + n], ga)
-            for i in reversed(range(c.num_hidden_layers)):
-                self._layer_grad(i, ws, g, keep[i, rows], n, T, pos[i], idx, m)
-            lib.deberta_embed_bwd(embeds[n0:n0 + n], self._f("emb_ln_w"), c.layer_norm_eps, m, ga, grad[n0:n0 + n])
+            for i in reversed(range(first, L)):
+                self._layer_grad(i, ws, g, keep[i - first, rows], n, T, pos[i], idx, m, dpos[i - (L - k)] if i >= L - k else None,
+                                 need_in or i > first)
+            if need_in:
+                lib.deberta_embed_bwd(src[n0:n0 + n], self._f("emb_ln_w"), c.layer_norm_eps, m, ga, grad[n0:n0 + n])
+        if k:
+            # the position path: posQ | posK = rel W_qk^T + b_qk is stored as bf16, so its gradient is rounded to bf16 there, once
+            rel, dp16 = self._rel(dev), ops.cast_to_bf16(dpos.view(k * S2, 2 * d)).view(k, S2, 2 * d)
+            # db_q += colsum(dposQ); db_k takes no column sum: sum_r dposK[r] = sum_i (sum_j dS_ij) Q_i, and a softmax backward's
+            # dS rows sum to zero, so the exact term is 0 and what the kernel's dposK sums to is rounding residue alone (delta
+            # comes from the bf16 O: each row of dS sums to dO_i . (O_i - bf16(O_i)), the residue colsum(dK) carries once already)
+            for i in range(L - k, L):
+                w, b, dp = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad, dp16[i - (L - k)]
+                ops.gemm_group(GEMM_TN, [(dp[:, :d], rel, w[:d], b[:d], None)], EPI_ACCUM | EPI_COLSUM_A)
+                ops.gemm_group(GEMM_TN, [(dp[:, d:], rel, w[d:2 * d], None, None)], EPI_ACCUM)
         return grad

@@ -42,6 +42,7 @@ SYMBOLS = (
     "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16", "mmf_bias_gelu_bf16_to", "mmf_bias_gelu_bwd_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
+    "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
 )
 
@@ -231,6 +232,10 @@ def load() -> C.CDLL:
     lib.mmf_deberta_attn_fwd_lse.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_deberta_attn_bwd.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_deberta_embed_bwd.argtypes = [vp, vp, f32, vp, i32, vp, vp, i64, i32, vp]
+    lib.mmf_deberta_attn_bwd_pos_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.mmf_deberta_attn_bwd_pos_workspace_bytes.restype = C.c_size_t
+    lib.mmf_deberta_attn_bwd_pos.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
+                                             vp, vp, i32, vp, C.c_size_t, vp]
     lib.mmf_video_prepare.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_video_prepare_patches.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_audio_resample.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, i64, i32, i32, i32, vp]
@@ -603,6 +608,36 @@ def deberta_attn_bwd(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv,
         check(load().mmf_deberta_attn_bwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
                                           out.data_ptr(), lse.data_ptr(), dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(),
                                           n, H, T, S, head_dim, scale, stream_ptr()))
+
+
+def deberta_attn_bwd_pos_workspace_bytes(n: int, H: int, T: int, S: int) -> int:
+    return int(load().mmf_deberta_attn_bwd_pos_workspace_bytes(n, H, T, S))
+
+
+def deberta_attn_bwd_pos(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv, dposq, dposk, workspace, n: int, H: int, T: int,
+                         S: int, scale: float, head_dim: int = 64) -> None:
+    """``deberta_attn_bwd`` (the same dqkv bits) that also ADDS the gradients of the position tables into ``dposq`` / ``dposk``: f32
+    (2S, H 64) views with a common row stride, zeroed by the caller before the first chunk; ``workspace``: a contiguous f32 / uint8
+    tensor of at least ``deberta_attn_bwd_pos_workspace_bytes(n, H, T, S)`` bytes (it need not be initialised)."""
+    _deberta_attn_args("deberta_attn_bwd_pos", qkv, posq, posk, idx, out, n, H, T, S, head_dim)
+    _w2v_bf16(dout, dqkv)
+    _w2v_f32(lse, delta_ws)
+    d = H * head_dim
+    if (dout.numel() < n * T * d or dqkv.numel() < n * T * 3 * d or not dout.is_contiguous() or not dqkv.is_contiguous()
+            or lse.numel() < n * H * T or delta_ws.numel() < n * H * T):
+        raise ValueError("deberta_attn_bwd_pos: operand sizes do not match n, H, T")
+    import torch
+    if (not dposq.is_cuda or not dposk.is_cuda or dposq.dtype != torch.float32 or dposk.dtype != torch.float32
+            or tuple(dposq.shape) != (2 * S, d) or tuple(dposk.shape) != (2 * S, d) or dposq.stride() != dposk.stride() or dposq.stride(1) != 1
+            or not workspace.is_cuda or not workspace.is_contiguous()):
+        raise ValueError("deberta_attn_bwd_pos: dposq / dposk must be (2S, H 64) f32 views with a common row stride, workspace contiguous")
+    mp, kind = _deberta_mask(mask, n * T)
+    # deberta_attn_bwd's products plus the two table contractions (2S x 64 x the tokens, per head)
+    with _Timed(f"deberta_attn_bwd_pos_kernels<{head_dim}>", 22.0 * n * H * T * T * head_dim, [(T, T)]):
+        check(load().mmf_deberta_attn_bwd_pos(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
+                                              out.data_ptr(), lse.data_ptr(), dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(),
+                                              n, H, T, S, head_dim, scale, dposq.data_ptr(), dposk.data_ptr(), dposq.stride(0),
+                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(), stream_ptr()))
 
 
 def deberta_embed_bwd(embeds, gamma, eps: float, mask, dout, d_embeds) -> None:

@@ -5,8 +5,13 @@ Reproduces the recipe of the reference's ``AdvancedTrainer`` for the part of the
 
   * loss (:139-166)      CrossEntropy(label_smoothing=0.1) on ``emotion_logits`` + 0.1 * sum of the
                          contrastive losses (+ 0.1 * aux, + 0.5 * distillation when present);
-  * optimiser (:85-94)   AdamW, weight_decay 1e-5; the reference's 0.1x LR group only holds HF-backbone
-                         parameters, which are outside this build, so all fusion parameters use ``lr``;
+  * optimiser (:85-94)   AdamW, weight_decay 1e-5, ONE learning rate for every parameter, the backbones' included.  The
+                         reference puts the HF-backbone parameters into a group with 0.1 x lr, but its own
+                         ``OneCycleLR(max_lr=<scalar>)`` (:102-110) then sets every group's ``initial_lr`` / ``max_lr`` from
+                         that one scalar, so the 0.1 x never takes effect: one schedule for all is the reference's
+                         behaviour.  The text backbone's top layers can train here (``NativeDeberta.set_trainable_layers``,
+                         ``config.text_backbone_trainable_layers``); ``finetune_optimizer`` builds the optimiser that steps
+                         exactly the parameters that require a gradient, as torch's AdamW skips the frozen ones;
   * schedule (:102-110)  OneCycleLR(max_lr, pct_start=0.1, cos) with torch's defaults, i.e. INCLUDING
                          ``cycle_momentum``: Adam's beta1 runs 0.95 -> 0.85 -> 0.95 against the learning rate;
   * clipping (:174,179)  ``clip_grad_norm_(1.0)``;
@@ -362,6 +367,18 @@ class FusedAdamW:
         self._dev_advanced = False
 
 
+def finetune_optimizer(module: torch.nn.Module, arena: Optional[ParamArena] = None, **kw) -> FusedAdamW:
+    """The fine-tuning recipe's optimiser, for ``FusionTrainStep(opt=...)``: ``FusedAdamW`` over the parameters of ``module``
+    that require a gradient (a model whose native text backbone trains its top layers holds frozen parameters in the same
+    arena: a whole-arena launch would apply weight decay to them, where torch's AdamW skips a parameter without a gradient).
+    ``arena``: the module's parameter arena, None: ``mmfusion.arena.ensure(module)``; ``kw``: ``FusedAdamW``'s arguments.
+    Call it after the trainable set is final (``set_trainable_layers``): the ranges are fixed here."""
+    if arena is None:
+        from .arena import ensure
+        arena = ensure(module)
+    return FusedAdamW(arena, params=[p for p in module.parameters() if p.requires_grad], **kw)
+
+
 def save_checkpoint(path: str, module: torch.nn.Module, optimizer: Optional["FusedAdamW"] = None, *, epoch: int = 0,
                     metrics: Optional[Dict] = None, config=None, scheduler_state: Optional[Dict] = None) -> None:
     """Write the reference's checkpoint layout (advanced_trainer.py:396-411): epoch, model_state_dict,
@@ -457,7 +474,8 @@ class FusionTrainStep:
         """exchange: "after" = one bucketed all-reduce of the gradient arena after backward; "backward" = the exchange
         runs inside backward in ``exchange_rounds`` reverse-autograd rounds (``dp.BackwardExchange``; replicated optimiser
         only).  opt: the optimiser over ``arena``; None builds the fusion recipe's (AdamW, OneCycleLR evaluated on the
-        device per step, clipping at ``max_grad_norm``)."""
+        device per step, clipping at ``max_grad_norm``).  A model with frozen parameters in the arena (a native text backbone
+        that trains its top layers only) hands in ``finetune_optimizer(model, arena, ...)``: the fine-tuning recipe."""
         self.model, self.head, self.arena = model, head, arena
         if opt is None:
             opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard_optimizer)

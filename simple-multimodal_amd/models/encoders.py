@@ -92,7 +92,7 @@ def _backbone(config, kind: str, given: Optional[nn.Module]):
 
 def _run_backbone(fn, native: bool, *args, input_grad: bool = False, **kw):
     """``fn(*args, **kw)``, under ``no_grad`` iff the backbone is the native one: that one is frozen.  ``input_grad``: the caller
-    wants the gradient with respect to the inputs it hands in (``NativeDeberta`` with ``inputs_embeds``: the prompt route),
+    wants a gradient through it (``NativeDeberta`` with ``inputs_embeds``: the prompt route; or with trainable top layers),
     so a native backbone is called in the caller's grad mode too"""
     with torch.no_grad() if native and not input_grad else contextlib.nullcontext():
         return fn(*args, **kw)
@@ -154,6 +154,8 @@ class TextEncoder(_FusionBase):
         super().__init__()
         self.config = config
         self.model, self.hidden_size, self._native = _backbone(config, "text", backbone)
+        if self._native:      # fine-tune the top layers of the native backbone (NativeDeberta.set_trainable_layers); 0: frozen
+            self.model.set_trainable_layers(int(getattr(config, "text_backbone_trainable_layers", 0)))
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.prompt_embeddings = nn.Parameter(torch.randn(config.prompt_length, self.hidden_size)) \
             if hasattr(config, "prompt_length") else None
@@ -177,7 +179,8 @@ class TextEncoder(_FusionBase):
                 kw = dict(inputs_embeds=torch.cat([pe, emb], dim=1), attention_mask=attention_mask)
             else:
                 kw = dict(input_ids=input_ids, attention_mask=attention_mask)
-            sequence_output = _run_backbone(self.model, self._native, input_grad=prompt_grad, **kw).last_hidden_state
+            tuned = self._native and self.model.trainable_layers > 0          # the backbone's own parameters train
+            sequence_output = _run_backbone(self.model, self._native, input_grad=prompt_grad or tuned, **kw).last_hidden_state
             cls_pool = "bert" in getattr(self.model.config, "model_type", "")     # reference :87
         if use_adapter and self.adapter is not None:
             sequence_output = self.adapter(sequence_output)

@@ -9,9 +9,13 @@
   * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE);
   * with --grad, the prompt-tuning cost instead: for (items, tokens) = (16, 10 + 512) and (8, 10 + 128) on input embeddings, ms of
     the inference forward, of the differentiable forward (it also keeps every layer's input) and of forward + backward, their
-    ratios to the inference forward, and the per-kernel table of one forward + backward.
+    ratios to the inference forward, and the per-kernel table of one forward + backward;
+  * with --finetune K, the cost of fine-tuning the top K layers instead (``set_trainable_layers(K)``): on token ids, for
+    (items, tokens) = (--items, --tokens) and (8, 128), the same three times and ratios (the backward stops below layer L - K and
+    adds the K layers' weight gradients into the arena), the per-kernel table, and ``mmf_deberta_attn_bwd_pos`` beside
+    ``mmf_deberta_attn_bwd`` on the same operands.
 
-    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad]
+    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad] [--finetune K]
 Prints one JSON line (the tables, when asked for, on the lines before it)."""
 import json
 import math
@@ -53,11 +57,56 @@ def grad_mode(model, cfg, args) -> dict:
     return res
 
 
+def finetune_mode(model, cfg, args) -> dict:
+    from mmfusion import lib
+    K, H, S, d = args.finetune, cfg.num_attention_heads, cfg.position_buckets, cfg.hidden_size
+    model.set_trainable_layers(K)
+    res = {"model": f"deberta-v3-base, bf16 storage: the top {K} layers trainable, token ids", "chunk": model.chunk, "cases": []}
+    for N, T in ((args.items, args.tokens), (8, 128)):
+        g = torch.Generator().manual_seed(2)
+        ids = torch.randint(1, cfg.vocab_size, (N, T), generator=g).cuda()
+        dout = torch.randn(N, T, d, generator=g).cuda()
+        mask = torch.ones(N, T, dtype=torch.int64)
+        mask[1::2, max(T - 32, 1):] = 0
+        mask = mask.cuda()
+
+        def infer():
+            with torch.no_grad():
+                model(input_ids=ids, attention_mask=mask)
+        diff = lambda: model(input_ids=ids, attention_mask=mask)
+        both = lambda: model(input_ids=ids, attention_mask=mask).last_hidden_state.backward(dout)     # (the gradients accumulate)
+        t_inf, t_diff, t_both = (time_eager(f, args.steps, args.warmup) for f in (infer, diff, both))
+        rows = kernel_table(both)
+        print(f"forward + backward, top {K} layers trainable, {N} items of {T} tokens")
+        print_table(rows)
+        # the attention backward with and without the table gradients, on one chunk's operands
+        n = min(N, model.chunk)
+        qkv, att, dat = (torch.randn(n * T, w, generator=g).to(torch.bfloat16).cuda() for w in (3 * d, d, d))
+        dqkv, lse, delta = torch.empty_like(qkv), torch.zeros(n * H * T, device="cuda"), torch.empty(n * H * T, device="cuda")
+        posq, posk = model._pos_tables(ids.device)[0]
+        idx, scale, m32 = model._index(T, ids.device), math.sqrt(3.0 * 64), mask[:n].float().contiguous()
+        lib.deberta_attn_fwd(qkv, posq, posk, idx, m32, att, n, H, T, S, scale, lse=lse)
+        dpos = torch.zeros(2 * S, 2 * d, device="cuda")
+        ws = torch.empty(lib.deberta_attn_bwd_pos_workspace_bytes(n, H, T, S) // 4, device="cuda")
+        plain = lambda: lib.deberta_attn_bwd(qkv, posq, posk, idx, m32, att, lse, dat, delta, dqkv, n, H, T, S, scale)
+        withpos = lambda: lib.deberta_attn_bwd_pos(qkv, posq, posk, idx, m32, att, lse, dat, delta, dqkv, dpos[:, :d], dpos[:, d:], ws,
+                                                   n, H, T, S, scale)
+        t_plain, t_pos = time_eager(plain, 20, 5), time_eager(withpos, 20, 5)
+        res["cases"].append({"items": N, "tokens": T, "trainable_layers": K, "inference_forward_ms": round(t_inf, 3),
+                             "differentiable_forward_ms": round(t_diff, 3), "forward_backward_ms": round(t_both, 3),
+                             "differentiable_forward_ratio": round(t_diff / t_inf, 3), "forward_backward_ratio": round(t_both / t_inf, 3),
+                             "saved_inputs_mb": round(K * N * T * d * 2 / 2 ** 20, 1),
+                             "attn_bwd_ms": round(t_plain, 4), "attn_bwd_pos_ms": round(t_pos, 4), "attn_bwd_pos_ratio": round(t_pos / t_plain, 3),
+                             "pos_workspace_mb": round(ws.numel() * 4 / 2 ** 20, 1), "kernels": rows})
+    return res
+
+
 def main():
     ap = parser(steps=5, warmup=2)
     ap.add_argument("--items", type=int, default=16)
     ap.add_argument("--tokens", type=int, default=512)
     ap.add_argument("--grad", action="store_true")
+    ap.add_argument("--finetune", type=int, default=0, metavar="K")
     args = ap.parse_args()
     import deberta_ref
     from mmfusion import deberta, lib
@@ -68,6 +117,9 @@ def main():
     model = model.cuda().eval()
     if args.grad:
         print(json.dumps(grad_mode(model, cfg, args)))
+        return
+    if args.finetune:
+        print(json.dumps(finetune_mode(model, cfg, args)))
         return
     N, T, d, H = args.items, args.tokens, cfg.hidden_size, cfg.num_attention_heads
     g = torch.Generator().manual_seed(1)
