@@ -7,6 +7,15 @@
 //           the attention backward: a delta pre-pass, a dQ pass and a dK/dV pass from one kernel body, without atomics.
 //   the same backward with the gradient of the position tables posQ | posK (fine-tuning the layer's q / k weights, which also
 //           project the relative embeddings): a template flag of the two passes and a fixed-order reduction kernel.
+// What the forward and the backward must agree on is stated once, as file-local __device__ functions that take operands and
+// never the name of their caller: the score tile (db_idx / db_fill_idx, db_chunks, db_pos_rows, db_frag, db_score; ahead of the
+// forward kernel) and the embedding LayerNorm's row statistics (db_row_stats).  The backward's P is the forward's P because both
+// call db_score on a tile staged by the same functions; the masking and softmax around it are each kernel's.  Bounds that are
+// constants of the file stay literals or template arguments inside the helpers: a clamp whose bounds arrive as function arguments
+// compiled to other device code in all six attention kernels.
+// Left unshared: the four "u32x4 of bf16 -> transposed LDS tile" loops (sVt; sOt with sO2t interleaved; sT).  One function for
+// them changed the device code of every attention kernel, whatever its signature, and the dK/dV pass's two tiles cannot interleave
+// through it; those four loops are the text they were, and the kernels compile to the instructions they had.
 #include <float.h>
 #include "mmf_internal.h"
 
@@ -21,24 +30,15 @@ __device__ __forceinline__ float db_mask(const void* __restrict__ mask, int kind
   return 1.0f;
 }
 
+__device__ __forceinline__ int db_clamp(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
 // ---- embeddings ---------------------------------------------------------------------------------------------
 // One wave per row; lane l owns columns 4 l + 256 k (k < 4, so d <= 1024), kept in registers between the two statistics
 // passes (mean, then the centred second moment: what torch's LayerNorm computes) and the store.
-__global__ __launch_bounds__(DB_THREADS)
-void deberta_embed_kernel(const long long* __restrict__ ids, const float* __restrict__ embeds, const float* __restrict__ table,
-                          const float* __restrict__ gamma, const float* __restrict__ beta, const void* __restrict__ mask,
-                          int mask_kind, unsigned short* __restrict__ out, int rows, int d, int vocab, float eps) {
-  const int row = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float* __restrict__ src;
-  if (ids) {
-    long long id = ids[row];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);              // an id outside the table reads its nearest row, never past it
-    src = table + (size_t)id * d;
-  } else {
-    src = embeds + (size_t)row * d;
-  }
-  f32x4_t v[4];
+struct DbRowStats { float mean, rstd; };
+
+// the lane's columns of row `src` -> v (zeros past d), and the row's statistics: the forward's and, again, the backward's
+__device__ __forceinline__ DbRowStats db_row_stats(const float* __restrict__ src, int lane, int d, float eps, f32x4_t (&v)[4]) {
   float sum = 0.0f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -55,7 +55,26 @@ void deberta_embed_kernel(const long long* __restrict__ ids, const float* __rest
       for (int e = 0; e < 4; ++e) { const float c = v[k][e] - mean; sq = fmaf(c, c, sq); }
     }
   }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+  return {mean, rsqrtf(wave_sum(sq) / (float)d + eps)};
+}
+
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_embed_kernel(const long long* __restrict__ ids, const float* __restrict__ embeds, const float* __restrict__ table,
+                          const float* __restrict__ gamma, const float* __restrict__ beta, const void* __restrict__ mask,
+                          int mask_kind, unsigned short* __restrict__ out, int rows, int d, int vocab, float eps) {
+  const int row = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* __restrict__ src;
+  if (ids) {
+    long long id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);              // an id outside the table reads its nearest row, never past it
+    src = table + (size_t)id * d;
+  } else {
+    src = embeds + (size_t)row * d;
+  }
+  f32x4_t v[4];
+  const DbRowStats st = db_row_stats(src, lane, d, eps, v);
+  const float mean = st.mean, rstd = st.rstd;
   const float m = db_mask(mask, mask_kind, (size_t)row);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -103,7 +122,57 @@ __device__ __forceinline__ int db_slot(int key) {            // key of a 32-key 
   return 8 * (k >> 2) + 4 * c + (k & 3);
 }
 
-template <bool LSE>                                          // LSE: also write lse[item][h][i] = m + log(l), what the backward reads
+// The score tile: the pieces the forward and both passes of the backward form s with.  "own" = the 64 tokens of the workgroup
+// (a lane's column; the forward's queries), "other" = the 32 tokens of the tile (the forward's keys).
+
+// idx(delta): the delta clamped to the table's +-(T - 1), the value to the rows 0 .. S2 - 1 of posQ | posK.  The only read of
+// idx in this file.
+__device__ __forceinline__ int db_idx(const int* __restrict__ idx, int delta, int T, int S2) {
+  return db_clamp(idx[db_clamp(delta, -(T - 1), T - 1) + T - 1], 0, S2 - 1);
+}
+
+// sIdx[t] = idx(d0 + step t) for the tile's 95 deltas; slot t belongs to the pairs with own - other + 31 = t
+__device__ __forceinline__ void db_fill_idx(int* __restrict__ sIdx, const int* __restrict__ idx, int tid, int d0, int step, int T, int S2) {
+  if (tid < DB_NIDX) sIdx[tid] = db_idx(idx, d0 + step * tid, T, S2);
+}
+
+// how many 16-row chunks from row lo reach row hi of a window (the idx values of its two end slots), within the ROWS its LDS
+// buffer holds
+template <int ROWS>
+__device__ __forceinline__ int db_chunks(int lo, int hi) {
+  const int n = (hi - lo) / 16 + 1;
+  return n < 1 ? 1 : (n > ROWS / 16 ? ROWS / 16 : n);
+}
+
+// 16 table rows (this lane: `row` >= 0, clamped to the table's last; tab points at its head's columns 8 q ..) x the two-fragment
+// B operand -> the lane's four f32 at dst
+__device__ __forceinline__ void db_pos_rows(const unsigned short* __restrict__ tab, int ld_pos, int row, int S2, bf16x8_t b0, bf16x8_t b1,
+                                            float* __restrict__ dst) {
+  const unsigned short* __restrict__ a = tab + (size_t)(row < S2 - 1 ? row : S2 - 1) * ld_pos;
+  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), b0, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), b1, acc, 0, 0, 0);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) dst[e] = acc[e];
+}
+
+// one MFMA fragment of the staged other rows: row `row`, columns 32 ks + 8 q ..
+__device__ __forceinline__ bf16x8_t db_frag(const unsigned short* rows, int row, int ks, int q) {
+  return *reinterpret_cast<const bf16x8_t*>(rows + row * DB_KLD + ks * 32 + q * 8);
+}
+
+// the score of (own token ow of the block = column r of its wave, other token `key` of the tile) from S^T's entry s and the
+// two parked position products, gathered at idx(delta) - lo of each window; the offsets clamped to the buffers
+__device__ __forceinline__ float db_score(float s, const int* __restrict__ sIdx, const float* __restrict__ cw, const float* __restrict__ sP,
+                                          int ow, int r, int key, int lo_c, int lo_p, float inv_scale) {
+  const int ix = sIdx[ow - key + (DB_BK - 1)];
+  int oc = ix - lo_c, op = ix - lo_p;
+  oc = oc < 0 ? 0 : (oc > DB_CROWS - 1 ? DB_CROWS - 1 : oc);
+  op = op < 0 ? 0 : (op > DB_PROWS - 1 ? DB_PROWS - 1 : op);
+  return (s + cw[r * DB_CLD + oc] + sP[key * DB_PLD + op]) * inv_scale;
+}
+
+template <bool LSE>                                         // LSE: also write lse[item][h][i] = m + log(l), what the backward reads
 __global__ __launch_bounds__(DB_THREADS)
 void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ posq,
                              const unsigned short* __restrict__ posk, int ld_pos, const int* __restrict__ idx,
@@ -152,55 +221,30 @@ void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsig
         sVt[(c8 + 2 * e) * DB_VLD + slot] = (unsigned short)(vv[e] & 0xffffu);
         sVt[(c8 + 2 * e + 1) * DB_VLD + slot] = (unsigned short)(vv[e] >> 16);
       }
-      if (tid < DB_NIDX) {                                       // idx of delta = dmin + tid, delta clamped to the table
-        int dl = i0 - j0 - (DB_BK - 1) + tid;
-        dl = dl < -(T - 1) ? -(T - 1) : (dl > T - 1 ? T - 1 : dl);
-        int v = idx[dl + T - 1];
-        sIdx[tid] = v < 0 ? 0 : (v > S2 - 1 ? S2 - 1 : v);
-      }
+      db_fill_idx(sIdx, idx, tid, i0 - j0 - (DB_BK - 1), 1, T, S2);          // delta = query - key
       if (tid < DB_BK) sKm[tid] = j0 + tid < T ? db_mask(mask, mask_kind, mrow + j0 + tid) : 0.0f;
     }
     __syncthreads();
 
     const int lo_p = sIdx[0], hi_p = sIdx[DB_NIDX - 1];
     const int lo_c = sIdx[16 * wave], hi_c = sIdx[16 * wave + 46];
-    int npc = (hi_p - lo_p) / 16 + 1;
-    npc = npc < 1 ? 1 : (npc > DB_PROWS / 16 ? DB_PROWS / 16 : npc);
-    int ncc = (hi_c - lo_c) / 16 + 1;
-    ncc = ncc < 1 ? 1 : (ncc > DB_CROWS / 16 ? DB_CROWS / 16 : ncc);
+    const int npc = db_chunks<DB_PROWS>(lo_p, hi_p), ncc = db_chunks<DB_CROWS>(lo_c, hi_c);
 
     // the K fragments of this tile: A of S^T and B of P2C^T
     bf16x8_t kf[2][2];
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) kf[kc][ks] = *reinterpret_cast<const bf16x8_t*>(sK + (kc * 16 + r) * DB_KLD + ks * 32 + q * 8);
+      for (int ks = 0; ks < 2; ++ks) kf[kc][ks] = db_frag(sK, kc * 16 + r, ks, q);
 
     // P2C^T: this wave's share of the (row chunk, key chunk) tiles -> sP[key][pos row - lo_p]
     for (int t = wave; t < npc * 2; t += 4) {
       const int rc = t >> 1, kc = t & 1;
-      int prow = lo_p + rc * 16 + r;
-      prow = prow > S2 - 1 ? S2 - 1 : prow;
-      const unsigned short* __restrict__ a = pq + (size_t)prow * ld_pos;
-      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), kc ? kf[1][0] : kf[0][0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), kc ? kf[1][1] : kf[0][1], acc, 0, 0, 0);
-      float* __restrict__ dst = sP + (kc * 16 + r) * DB_PLD + rc * 16 + q * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[e] = acc[e];
+      db_pos_rows(pq, ld_pos, lo_p + rc * 16 + r, S2, kc ? kf[1][0] : kf[0][0], kc ? kf[1][1] : kf[0][1],
+                  sP + (kc * 16 + r) * DB_PLD + rc * 16 + q * 4);
     }
     // C2P^T: this wave's own rows -> cw[query][pos row - lo_c]
-    for (int c = 0; c < ncc; ++c) {
-      int prow = lo_c + c * 16 + r;
-      prow = prow > S2 - 1 ? S2 - 1 : prow;
-      const unsigned short* __restrict__ a = pk + (size_t)prow * ld_pos;
-      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), qf[0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), qf[1], acc, 0, 0, 0);
-      float* __restrict__ dst = cw + r * DB_CLD + c * 16 + q * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[e] = acc[e];
-    }
+    for (int c = 0; c < ncc; ++c) db_pos_rows(pk, ld_pos, lo_c + c * 16 + r, S2, qf[0], qf[1], cw + r * DB_CLD + c * 16 + q * 4);
     // S^T
     f32x4_t s[2];
 #pragma unroll
@@ -218,11 +262,7 @@ void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int key = kc * 16 + q * 4 + e;
-        const int ix = sIdx[16 * wave + r - key + (DB_BK - 1)];
-        int oc = ix - lo_c, op = ix - lo_p;
-        oc = oc < 0 ? 0 : (oc > DB_CROWS - 1 ? DB_CROWS - 1 : oc);
-        op = op < 0 ? 0 : (op > DB_PROWS - 1 ? DB_PROWS - 1 : op);
-        float v = (s[kc][e] + cw[r * DB_CLD + oc] + sP[key * DB_PLD + op]) * inv_scale;
+        float v = db_score(s[kc][e], sIdx, cw, sP, 16 * wave + r, r, key, lo_c, lo_p, inv_scale);
         if (!(q_on && sKm[key] != 0.0f)) v = -FLT_MAX;          // a masked pair: HuggingFace's masked_fill(finfo.min)
         if (j0 + key >= T) v = -INFINITY;                        // no such key
         p[kc][e] = v;
@@ -265,7 +305,7 @@ void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 
 // ---- backward with respect to the inputs (prompt tuning through the frozen layers) --------------------------------
 // embeddings: d_embeds = mask[row] * the LayerNorm input gradient of the bf16 gradient dy of deberta_embed_kernel's output
-// (inputs_embeds route).  The row statistics are recomputed as the forward computes them; one wave per row, same lane map.
+// (inputs_embeds route).  The row statistics are the forward's (db_row_stats); one wave per row, same lane map.
 __global__ __launch_bounds__(DB_THREADS)
 void deberta_embed_bwd_kernel(const float* __restrict__ embeds, const float* __restrict__ gamma, const void* __restrict__ mask,
                               int mask_kind, const unsigned short* __restrict__ dy, float* __restrict__ dx, int rows, int d, float eps) {
@@ -274,23 +314,8 @@ void deberta_embed_bwd_kernel(const float* __restrict__ embeds, const float* __r
   const float* __restrict__ src = embeds + (size_t)row * d;
   const float m = db_mask(mask, mask_kind, (size_t)row);
   f32x4_t v[4];
-  float sum = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = 4 * lane + 256 * k;
-    v[k] = c < d ? *reinterpret_cast<const f32x4_t*>(src + c) : f32x4_t{0.f, 0.f, 0.f, 0.f};
-    sum += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-  }
-  const float mean = wave_sum(sum) / (float)d;
-  float sq = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (4 * lane + 256 * k < d) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float c = v[k][e] - mean; sq = fmaf(c, c, sq); }
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+  const DbRowStats st = db_row_stats(src, lane, d, eps, v);
+  const float mean = st.mean, rstd = st.rstd;
   // g = dy * mask * gamma (the gradient of the normalised value), xh the normalised value; s1 = sum g, s2 = sum g xh
   f32x4_t g[4];
   float s1 = 0.0f, s2 = 0.0f;
@@ -472,13 +497,9 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
           sO2t[(c8 + 2 * e + 1) * DB_VLD + slot] = (unsigned short)(vb[e] >> 16);
         }
       }
-      if (tid < DB_NIDX) {                                       // idx of the delta of (own ow, other k), ow - k + 31 = tid
-        int dl = own0 - o0 - (DB_BK - 1) + tid;
-        if (KPASS) dl = -dl;                                     // delta = query - key = other - own
-        dl = dl < -(T - 1) ? -(T - 1) : (dl > T - 1 ? T - 1 : dl);
-        int v = idx[dl + T - 1];
-        sIdx[tid] = v < 0 ? 0 : (v > S2 - 1 ? S2 - 1 : v);
-      }
+      // slot tid: the pairs with own - other + 31 = tid; delta = query - key is own - other, or other - own in the dK/dV pass
+      const int sgn = KPASS ? -1 : 1;
+      db_fill_idx(sIdx, idx, tid, sgn * (own0 - o0 - (DB_BK - 1)), sgn, T, S2);
       if (tid < DB_TROWS) { sFirst[tid] = 0; sEnd[tid] = 0; }    // an empty run
       if (tid < DB_BK) {
         const int jj = o0 + tid < T ? o0 + tid : T - 1;
@@ -492,16 +513,11 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
     const int e0 = sIdx[0], e1 = sIdx[DB_NIDX - 1], w0 = sIdx[16 * wave], w1 = sIdx[16 * wave + 46];
     const int lo_p = e0 < e1 ? e0 : e1, hi_p = e0 < e1 ? e1 : e0;
     const int lo_c = w0 < w1 ? w0 : w1, hi_c = w0 < w1 ? w1 : w0;
-    int npc = (hi_p - lo_p) / 16 + 1;
-    npc = npc < 1 ? 1 : (npc > DB_PROWS / 16 ? DB_PROWS / 16 : npc);
-    int ncc = (hi_c - lo_c) / 16 + 1;
-    ncc = ncc < 1 ? 1 : (ncc > DB_CROWS / 16 ? DB_CROWS / 16 : ncc);
-    const int nb32 = (npc + 1) >> 1;                             // 32-row chunks of the block's window
+    const int npc = db_chunks<DB_PROWS>(lo_p, hi_p), ncc = db_chunks<DB_CROWS>(lo_c, hi_c);
+    const int nb32 = (npc + 1) >> 1;                            // 32-row chunks of the block's window
 
     if (tid < DB_NIDX) {                                         // the run of deltas that gathers each window row
-      const int me = sIdx[tid];
-      int row = me - lo_p;
-      row = row < 0 ? 0 : (row > DB_TROWS - 1 ? DB_TROWS - 1 : row);
+      const int me = sIdx[tid], row = db_clamp(me - lo_p, 0, DB_TROWS - 1);
       if (tid == 0 || sIdx[tid - 1] != me) sFirst[row] = tid;
       if (tid == DB_NIDX - 1 || sIdx[tid + 1] != me) sEnd[row] = tid + 1;
     }
@@ -522,33 +538,16 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) kf[kc][ks] = *reinterpret_cast<const bf16x8_t*>(sO + (kc * 16 + r) * DB_KLD + ks * 32 + q * 8);
+      for (int ks = 0; ks < 2; ++ks) kf[kc][ks] = db_frag(sO, kc * 16 + r, ks, q);
 
     // T2^T: this wave's share of the (row chunk, other chunk) tiles -> sP[other][pos row - lo_p]
     for (int t = wave; t < npc * 2; t += 4) {
       const int rc = t >> 1, kc = t & 1;
-      int prow = lo_p + rc * 16 + r;
-      prow = prow > S2 - 1 ? S2 - 1 : prow;
-      const unsigned short* __restrict__ a = tab2 + (size_t)prow * ld_pos;
-      f32x4_t c = {0.f, 0.f, 0.f, 0.f};
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), kc ? kf[1][0] : kf[0][0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), kc ? kf[1][1] : kf[0][1], c, 0, 0, 0);
-      float* __restrict__ dst = sP + (kc * 16 + r) * DB_PLD + rc * 16 + q * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[e] = c[e];
+      db_pos_rows(tab2, ld_pos, lo_p + rc * 16 + r, S2, kc ? kf[1][0] : kf[0][0], kc ? kf[1][1] : kf[0][1],
+                  sP + (kc * 16 + r) * DB_PLD + rc * 16 + q * 4);
     }
     // T1^T: this wave's own rows -> cw[own][pos row - lo_c]
-    for (int c16 = 0; c16 < ncc; ++c16) {
-      int prow = lo_c + c16 * 16 + r;
-      prow = prow > S2 - 1 ? S2 - 1 : prow;
-      const unsigned short* __restrict__ a = tab1 + (size_t)prow * ld_pos + q * 8;
-      f32x4_t c = {0.f, 0.f, 0.f, 0.f};
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a), xf[0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(a + 32), xf[1], c, 0, 0, 0);
-      float* __restrict__ dst = cw + r * DB_CLD + c16 * 16 + q * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[e] = c[e];
-    }
+    for (int c = 0; c < ncc; ++c) db_pos_rows(tab1 + q * 8, ld_pos, lo_c + c * 16 + r, S2, xf[0], xf[1], cw + r * DB_CLD + c * 16 + q * 4);
     // S^T and dP^T
     f32x4_t s[2], dp[2];
 #pragma unroll
@@ -557,7 +556,7 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         s[kc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kc][ks], xf[ks], s[kc], 0, 0, 0);
-        const bf16x8_t o2 = *reinterpret_cast<const bf16x8_t*>(sO2 + (kc * 16 + r) * DB_KLD + ks * 32 + q * 8);
+        const bf16x8_t o2 = db_frag(sO2, kc * 16 + r, ks, q);
         dp[kc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o2, yf[ks], dp[kc], 0, 0, 0);
       }
     }
@@ -570,11 +569,7 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int key = kc * 16 + q * 4 + e;
-        const int ix = sIdx[ow - key + (DB_BK - 1)];
-        int oc = ix - lo_c, op = ix - lo_p;
-        oc = oc < 0 ? 0 : (oc > DB_CROWS - 1 ? DB_CROWS - 1 : oc);
-        op = op < 0 ? 0 : (op > DB_PROWS - 1 ? DB_PROWS - 1 : op);
-        const float v = (s[kc][e] + cw[r * DB_CLD + oc] + sP[key * DB_PLD + op]) * inv_scale;
+        const float v = db_score(s[kc][e], sIdx, cw, sP, ow, r, key, lo_c, lo_p, inv_scale);
         const bool there = o0 + key < T;                         // the other token exists
         const bool q_on = KPASS ? sOm[key] != 0.0f : own_on, k_on = KPASS ? own_on : sOm[key] != 0.0f;
         const float l = KPASS ? sLse[key] : lse_o, dl = KPASS ? sDl[key] : dl_o;
@@ -645,7 +640,7 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int prow = lo_p + rc * 16 + q * 4 + e;           // hi_p <= 2 S - 1: never a row past the table
+          const int prow = lo_p + rc * 16 + q * 4 + e;          // hi_p <= 2 S - 1: never a row past the table
           if (prow <= hi_p) {
             float* dst = ptab + (size_t)prow * DB_DH;
             *dst = (prow < plo || prow > phi) ? g[e] : *dst + g[e];      // first write of this row | a row of the previous window
@@ -668,8 +663,8 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 
 // dposk | dposq (2S, H 64) f32 += the sum over the workgroups (item, block of 64 own tokens) of the dQ | dK/dV pass of the rows
 // their partial tables hold, block by block and item by item: one lane per element.  A workgroup of block b wrote the rows
-// idx(its smallest delta) .. idx(its largest delta), deltas and idx values clamped as the pass clamps them; the rest of its
-// table is not read.
+// idx(its smallest delta) .. idx(its largest delta): db_idx again, the function the pass fills sIdx with, at those two deltas, so
+// the deltas and idx values are clamped as the pass clamps them by construction.  The rest of its table is not read.
 __global__ __launch_bounds__(DB_THREADS)
 void deberta_pos_reduce_kernel(const float* __restrict__ part, const int* __restrict__ idx, float* __restrict__ dposq,
                                float* __restrict__ dposk, int ld_dpos, int H, int T, int S2, int n, int nblk) {
@@ -684,13 +679,9 @@ void deberta_pos_reduce_kernel(const float* __restrict__ part, const int* __rest
   const int o_last = ((T - 1) / DB_BK) * DB_BK;
   float sum = 0.0f;
   for (int b = 0; b < nblk; ++b) {
-    int d0 = b * DB_BQ - o_last - (DB_BK - 1), d1 = b * DB_BQ + DB_BQ - 1;       // own - other over the block's tiles
-    if (kpass) { const int t = d0; d0 = -d1; d1 = -t; }                         // delta = other - own
-    d0 = d0 < -(T - 1) ? -(T - 1) : (d0 > T - 1 ? T - 1 : d0);
-    d1 = d1 < -(T - 1) ? -(T - 1) : (d1 > T - 1 ? T - 1 : d1);
-    int r0 = idx[d0 + T - 1], r1 = idx[d1 + T - 1];
-    r0 = r0 < 0 ? 0 : (r0 > S2 - 1 ? S2 - 1 : r0);
-    r1 = r1 < 0 ? 0 : (r1 > S2 - 1 ? S2 - 1 : r1);
+    // slot 0 of the block's last tile and slot 94 of its first: own - other at its smallest and largest, negated as the dK/dV pass does
+    const int sgn = kpass ? -1 : 1;
+    const int r0 = db_idx(idx, sgn * (b * DB_BQ - o_last - (DB_BK - 1)), T, S2), r1 = db_idx(idx, sgn * (b * DB_BQ + DB_BQ - 1), T, S2);
     if (row < (r0 < r1 ? r0 : r1) || row > (r0 < r1 ? r1 : r0)) continue;
 #pragma unroll 4
     for (int item = 0; item < n; ++item) sum += src[((size_t)item * nblk + b) * stride];
@@ -706,6 +697,16 @@ int db_mask_check(const char* fn, const void* mask, int mask_kind) {
   return MMF_OK;
 }
 
+// what the two embedding entries share: the limits of the one-wave-per-row kernels, the mask, and their grid
+int db_embed_rows(const char* fn, int64_t rows, int d, const void* mask, int mask_kind, dim3* grid) {
+  if ((d & 3) || d > 1024 || rows > ((int64_t)1 << 31) - 4)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: d=%d (multiple of 4, at most 1024), rows=%lld (below 2^31)", fn, d, (long long)rows);
+  if (int rc = db_mask_check(fn, mask, mask_kind)) return rc;
+  const int per = DB_THREADS / MMF_WAVE;
+  *grid = dim3((unsigned)((rows + per - 1) / per));
+  return MMF_OK;
+}
+
 }  // namespace
 
 extern "C" int mmf_deberta_embed(const int64_t* ids, const float* embeds, const float* table, const float* gamma, const float* beta,
@@ -714,14 +715,12 @@ extern "C" int mmf_deberta_embed(const int64_t* ids, const float* embeds, const 
   if ((ids == nullptr) == (embeds == nullptr)) MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_embed: exactly one of ids / embeds");
   if (!gamma || !beta || !out_bf16 || (ids && !table) || rows <= 0 || d <= 0 || (ids && vocab <= 0))
     MMF_FAIL(MMF_E_SHAPE, "mmf_deberta_embed: null operand or rows=%lld d=%d vocab=%d", (long long)rows, d, vocab);
-  if ((d & 3) || d > 1024 || rows > ((int64_t)1 << 31) - 4)
-    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_deberta_embed: d=%d (multiple of 4, at most 1024), rows=%lld (below 2^31)", d, (long long)rows);
-  if (int rc = db_mask_check("mmf_deberta_embed", mask, mask_kind)) return rc;
+  dim3 grid;
+  if (int rc = db_embed_rows("mmf_deberta_embed", rows, d, mask, mask_kind, &grid)) return rc;
   if (!mmf_aligned16(gamma) || !mmf_aligned16(beta) || !mmf_aligned16(out_bf16) || (ids && !mmf_aligned16(table)) || (embeds && !mmf_aligned16(embeds))
       || (reinterpret_cast<uintptr_t>(ids) & 7u))
     MMF_FAIL(MMF_E_ALIGN, "mmf_deberta_embed: table / embeds / gamma / beta / out must be 16-byte aligned, ids 8-byte aligned");
-  const int per = DB_THREADS / MMF_WAVE;
-  hipLaunchKernelGGL(deberta_embed_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(deberta_embed_kernel, grid, dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const long long*>(ids), embeds, table, gamma, beta, mask, mask_kind, static_cast<unsigned short*>(out_bf16),
                      (int)rows, d, vocab, eps);
   MMF_CHECK_LAUNCH("mmf_deberta_embed");
@@ -854,13 +853,11 @@ extern "C" int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, fl
                                      const void* dout_bf16, float* d_embeds, int64_t rows, int d, void* stream) {
   const char* fn = "mmf_deberta_embed_bwd";
   if (!embeds || !gamma || !dout_bf16 || !d_embeds || rows <= 0 || d <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: null operand or rows=%lld d=%d", fn, (long long)rows, d);
-  if ((d & 3) || d > 1024 || rows > ((int64_t)1 << 31) - 4)
-    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: d=%d (multiple of 4, at most 1024), rows=%lld (below 2^31)", fn, d, (long long)rows);
-  if (int rc = db_mask_check(fn, mask, mask_kind)) return rc;
+  dim3 grid;
+  if (int rc = db_embed_rows(fn, rows, d, mask, mask_kind, &grid)) return rc;
   if (!mmf_aligned16(embeds) || !mmf_aligned16(gamma) || !mmf_aligned16(d_embeds) || (reinterpret_cast<uintptr_t>(dout_bf16) & 7u))
     MMF_FAIL(MMF_E_ALIGN, "%s: embeds / gamma / d_embeds must be 16-byte aligned, dout 8-byte aligned", fn);
-  const int per = DB_THREADS / MMF_WAVE;
-  hipLaunchKernelGGL(deberta_embed_bwd_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(deberta_embed_bwd_kernel, grid, dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
                      embeds, gamma, mask, mask_kind, static_cast<const unsigned short*>(dout_bf16), d_embeds, (int)rows, d, eps);
   MMF_CHECK_LAUNCH(fn);
   return MMF_OK;

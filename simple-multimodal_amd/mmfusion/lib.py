@@ -591,17 +591,22 @@ def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S:
                                                   out.data_ptr(), lse.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
 
 
-def deberta_attn_bwd(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv, n: int, H: int, T: int, S: int, scale: float,
-                     head_dim: int = 64) -> None:
-    """dqkv (n T, 3 H 64) bf16 <- the gradient of the fused qkv rows for the gradient ``dout`` (n T, H 64) of ``out``; ``out`` / ``lse``
-    as ``deberta_attn_fwd(..., lse=lse)`` wrote them; ``delta_ws`` f32 scratch of n H T values.  Every row of dqkv is written."""
-    _deberta_attn_args("deberta_attn_bwd", qkv, posq, posk, idx, out, n, H, T, S, head_dim)
+def _deberta_attn_bwd_args(who: str, qkv, posq, posk, idx, out, lse, dout, delta_ws, dqkv, n: int, H: int, T: int, S: int, head_dim: int) -> None:
+    """the operand checks of ``deberta_attn_bwd`` and ``deberta_attn_bwd_pos`` (``who``: the one that was called)"""
+    _deberta_attn_args(who, qkv, posq, posk, idx, out, n, H, T, S, head_dim)
     _w2v_bf16(dout, dqkv)
     _w2v_f32(lse, delta_ws)
     d = H * head_dim
     if (dout.numel() < n * T * d or dqkv.numel() < n * T * 3 * d or not dout.is_contiguous() or not dqkv.is_contiguous()
             or lse.numel() < n * H * T or delta_ws.numel() < n * H * T):
-        raise ValueError("deberta_attn_bwd: operand sizes do not match n, H, T")
+        raise ValueError(f"{who}: operand sizes do not match n, H, T")
+
+
+def deberta_attn_bwd(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv, n: int, H: int, T: int, S: int, scale: float,
+                     head_dim: int = 64) -> None:
+    """dqkv (n T, 3 H 64) bf16 <- the gradient of the fused qkv rows for the gradient ``dout`` (n T, H 64) of ``out``; ``out`` / ``lse``
+    as ``deberta_attn_fwd(..., lse=lse)`` wrote them; ``delta_ws`` f32 scratch of n H T values.  Every row of dqkv is written."""
+    _deberta_attn_bwd_args("deberta_attn_bwd", qkv, posq, posk, idx, out, lse, dout, delta_ws, dqkv, n, H, T, S, head_dim)
     mp, kind = _deberta_mask(mask, n * T)
     # the forward's three score products again, dP, and two products (content + position) for each of dQ and dK, and dV
     with _Timed(f"deberta_attn_bwd_kernels<{head_dim}>", 22.0 * n * H * T * T * head_dim, [(T, T)]):
@@ -619,14 +624,9 @@ def deberta_attn_bwd_pos(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, d
     """``deberta_attn_bwd`` (the same dqkv bits) that also ADDS the gradients of the position tables into ``dposq`` / ``dposk``: f32
     (2S, H 64) views with a common row stride, zeroed by the caller before the first chunk; ``workspace``: a contiguous f32 / uint8
     tensor of at least ``deberta_attn_bwd_pos_workspace_bytes(n, H, T, S)`` bytes (it need not be initialised)."""
-    _deberta_attn_args("deberta_attn_bwd_pos", qkv, posq, posk, idx, out, n, H, T, S, head_dim)
-    _w2v_bf16(dout, dqkv)
-    _w2v_f32(lse, delta_ws)
-    d = H * head_dim
-    if (dout.numel() < n * T * d or dqkv.numel() < n * T * 3 * d or not dout.is_contiguous() or not dqkv.is_contiguous()
-            or lse.numel() < n * H * T or delta_ws.numel() < n * H * T):
-        raise ValueError("deberta_attn_bwd_pos: operand sizes do not match n, H, T")
     import torch
+    _deberta_attn_bwd_args("deberta_attn_bwd_pos", qkv, posq, posk, idx, out, lse, dout, delta_ws, dqkv, n, H, T, S, head_dim)
+    d = H * head_dim
     if (not dposq.is_cuda or not dposk.is_cuda or dposq.dtype != torch.float32 or dposk.dtype != torch.float32
             or tuple(dposq.shape) != (2 * S, d) or tuple(dposk.shape) != (2 * S, d) or dposq.stride() != dposk.stride() or dposq.stride(1) != 1
             or not workspace.is_cuda or not workspace.is_contiguous()):
