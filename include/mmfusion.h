@@ -403,6 +403,12 @@ int mmf_layernorm_fwd_grouped(const mmf_ln_problem* problems, int num_problems, 
 size_t mmf_layernorm_bwd_workspace_bytes(int d);
 int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num_problems, int d,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* The backward with a residual gradient folded in: dx = r + LNbwd(dy), r bf16 [rows][d] handed over in the problem's `y` field
+ * (which the plain backward does not read).  The add is in f32 in front of dx's one rounding; r may be dx itself (a pre-LN layer's
+ * residual gradient is overwritten by the gradient of the layer's input).  The same kernel bodies, workspace and constraints as
+ * mmf_layernorm_bwd_grouped; with r = 0 the results are its bits. */
+int mmf_layernorm_bwd_add_grouped(const mmf_ln_problem* problems, int num_problems, int d,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* the form the calling thread's last mmf_layernorm_fwd_grouped / _bwd_grouped call dispatched to (tests assert the form they
  * target): 1-4 = the chunk form ln_*_kernel<NCH> (NCH 512-column chunks per row); 100 + 10 NV + H8 = the lane form
  * ln_*_lane_kernel<NV, H8> (d = 512 NV + 256 H8: 110 / 111 / 101 / 120 for d = 512 / 768 / 256 / 1024); 0 before any call. */
@@ -503,6 +509,11 @@ int mmf_dropout(const void* x, void* y, int64_t n, int is_f32, float p, const ui
  * overwrite.  base 16-byte aligned; starts / ends are HOST arrays of element offsets. */
 #define MMF_ZERO_MAX_RANGES 48
 int mmf_zero_ranges_f32(float* base, const int64_t* starts, const int64_t* ends, int n, void* stream);
+/* out[i] = (accumulate ? out[i] : 0) + partial[0][i] + partial[1][i] + ... + partial[slabs - 1][i], summed in that order in f32:
+ * the K-slab partial products of a weight gradient (slab s at partial + s * n) into the gradient itself.  n % 4 == 0,
+ * 1 <= slabs <= MMF_SUM_SLABS_MAX, both pointers 16-byte aligned; no atomics, so two runs give the same bits. */
+#define MMF_SUM_SLABS_MAX 64
+int mmf_sum_slabs_f32(const float* partial, float* out, int64_t n, int slabs, int accumulate, void* stream);
 /* relu backward on bf16: dx = dy * (y > 0) */
 int mmf_relu_bwd_bf16(const void* dy, const void* y, void* dx, int64_t n, void* stream);
 /* same with dy and / or y in f32 (flags non-zero): narrows and masks in one pass; dx is bf16 */
@@ -659,6 +670,21 @@ int mmf_vit_patchify(const float* pixels, void* patches_bf16, int N, int C, int 
 /* tokens (N*T, d) bf16: row n*T = cls + pos[0], row n*T + 1 + p = patch_emb[n*(T-1) + p] + pos[1 + p]; cls f32 [d], pos f32
  * [T][d], patch_emb bf16 (N*(T-1), d); the add is f32 with one rounding to bf16.  d % 8 == 0, N <= 65535. */
 int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls, const float* pos, void* tokens_bf16, int N, int T, int d,
+                         void* stream);
+/* Its backward, for the gradient g (N*T, d) bf16 of the tokens: dcls[c] += sum_n g[n*T][c]; dpos[t][c] += sum_n g[n*T + t][c]
+ * (both f32, summed over n = 0 .. N-1 in that order by one thread per element: no atomics, two runs give the same bits; the sums
+ * are ADDED to what the buffers hold); dpatch_emb (N*(T-1), d) bf16 = the rows 1 .. T-1 of every image (the A operand of the patch
+ * projection's weight gradient).  mmf_vit_embed_tokens's constraints; validates first and launches nothing on an error. */
+int mmf_vit_embed_tokens_bwd(const void* dtokens_bf16, float* dcls, float* dpos, void* dpatch_emb_bf16, int N, int T, int d,
+                             void* stream);
+/* The attention backward of the CLS route's last layer: one query per image, row 0 of its T rows, on the fused rows q | k | v
+ * (N*T, 3 H head_dim) bf16; dout (N, H head_dim) bf16 = the gradient of that query's attention output.  dqkv, laid out as qkv:
+ * dq into the q columns of row 0 of each image (the q columns of the other rows are not written), dk | dv into the k | v columns
+ * of every row, each rounded to bf16 once.  The softmax is formed again in f32 from the scores and delta = sum_j p_j dp_j, so
+ * a row of dS sums to zero up to f32 rounding (mmf_attn_bwd_grouped's delta = dO . O carries the rounding of the bf16 O, which one
+ * query's dq and dk do not average out).  Fixed-order sums: two runs give the same bits.  head_dim 64 or 96, T <= 4096,
+ * N, H <= 65535; validates first and launches nothing on an error. */
+int mmf_vit_cls_attn_bwd(const void* qkv_bf16, const void* dout_bf16, void* dqkv_bf16, int N, int H, int T, int head_dim, float scale,
                          void* stream);
 /* x <- gelu(x + bias) in place on a bf16 (rows, cols) block with row stride ld: the exact form 0.5 v (1 + erf(v / sqrt 2)) in
  * f32 (HuggingFace hidden_act = "gelu"), one rounding to bf16.  bias f32 [cols] or NULL.  cols % 8 == 0, ld % 8 == 0. */

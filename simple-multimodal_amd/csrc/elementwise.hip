@@ -335,6 +335,28 @@ void zero_ranges_kernel(const ZeroArgs a) {
   }
 }
 
+// out = (ACCUM ? out : 0) + partial[0] + ... + partial[slabs - 1], 4 floats per lane per access, the slabs in order: one f32
+// chain per element (the K-slab partial products of a weight gradient; no atomics).  Four slabs' loads are in flight per lane.
+template <bool ACCUM>
+__global__ __launch_bounds__(EW_THREADS)
+void sum_slabs_kernel(const float* __restrict__ partial, float* __restrict__ out, int64_t nvec, int slabs) {
+  const int64_t stride = (int64_t)gridDim.x * EW_THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
+    f32x4_t s = ACCUM ? *reinterpret_cast<const f32x4_t*>(out + i * 4) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const float* p = partial + i * 4;
+    int k = 0;
+    for (; k + 4 <= slabs; k += 4) {
+      f32x4_t v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(p + (k + u) * nvec * 4);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s += v[u];
+    }
+    for (; k < slabs; ++k) s += *reinterpret_cast<const f32x4_t*>(p + k * nvec * 4);
+    *reinterpret_cast<f32x4_t*>(out + i * 4) = s;
+  }
+}
+
 }  // namespace
 
 #define EW_PTR_CHECK(name, cond) do { if (!(cond)) MMF_FAIL(MMF_E_ALIGN, name ": null or not 16-byte aligned pointer"); } while (0)
@@ -604,6 +626,19 @@ extern "C" int mmf_zero_ranges_f32(float* base, const int64_t* starts, const int
   a.blk_start[n] = total;
   hipLaunchKernelGGL(zero_ranges_kernel, dim3(total), dim3(EW_THREADS), 0, static_cast<hipStream_t>(stream), a);
   MMF_CHECK_LAUNCH("mmf_zero_ranges_f32");
+  return MMF_OK;
+}
+
+extern "C" int mmf_sum_slabs_f32(const float* partial, float* out, int64_t n, int slabs, int accumulate, void* stream) {
+  if (!partial || !out || n <= 0 || slabs < 1 || slabs > MMF_SUM_SLABS_MAX)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_sum_slabs_f32: null operand, n=%lld or slabs=%d outside [1,%d]", (long long)n, slabs, MMF_SUM_SLABS_MAX);
+  if ((n & 3) || !mmf_aligned16(partial) || !mmf_aligned16(out))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_sum_slabs_f32: n=%lld must be a multiple of 4 and the pointers 16-byte aligned", (long long)n);
+  const dim3 grid(mmf_stream_grid(n >> 2, EW_THREADS)), block(EW_THREADS);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (accumulate) hipLaunchKernelGGL(sum_slabs_kernel<true>, grid, block, 0, s, partial, out, n >> 2, slabs);
+  else            hipLaunchKernelGGL(sum_slabs_kernel<false>, grid, block, 0, s, partial, out, n >> 2, slabs);
+  MMF_CHECK_LAUNCH("mmf_sum_slabs_f32");
   return MMF_OK;
 }
 

@@ -2,11 +2,13 @@
 // HBM-bound: one wavefront owns one row (d <= 2048), 16-byte loads (8 bf16 per lane per chunk),
 // f32 statistics by wave butterfly reduction, no LDS in the forward.
 // Algorithmic bytes per row: forward 2 x 2d (x in, y out) + 8; backward 3 x 2d (x, dy in; dx out).
+#include <type_traits>
+
 #include "mmf_internal.h"
 
 namespace {
 
-constexpr int ROWS_PER_BLOCK = 4;      // 4 waves, one row each
+constexpr int ROWS_PER_BLOCK = 4;     // 4 waves, one row each
 constexpr int MAX_CH = 4;              // 4 chunks x 64 lanes x 8 elements = 2048 columns
 
 // Workgroups of a launch (round 3, same box, profiles/r03_layernorm.txt).  Forward, chunk form / lane form: three problems of
@@ -274,7 +276,9 @@ void ln2_add3_lane_kernel(const Ln2Add3Args a) {
 // Backward: a block owns a strided set of rows of ONE problem; each wave walks its rows, keeps the
 // dgamma/dbeta partial sums of its columns in registers, the 4 waves combine through LDS and the
 // block issues one f32 atomic per column (Guideline 12: reduce on chip, then one atomic per block).
-template <int NCH>
+// ADD (mmf_layernorm_bwd_add_grouped): dx = r + that, r = the bf16 rows behind the problem's `y`, added in f32 in front of the one
+// rounding; a lane reads its share of r's row right before it stores the same columns of dx, so r may be dx.
+template <int NCH, bool ADD>
 __global__ __launch_bounds__(256)
 void ln_bwd_kernel(const LnArgs a) {
   __shared__ float red[2][3][NCH * 512];          // [dgamma|dbeta][waves 1..3][column]
@@ -329,6 +333,12 @@ void ln_bwd_kernel(const LnArgs a) {
         float o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = rstd * (g[c][e] - c1 - xh[c][e] * c2);
+        if constexpr (ADD) {
+          float rv[8];
+          unpack8(*reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(P.y) + (size_t)row * d + col), rv);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] += rv[e];
+        }
         *reinterpret_cast<u32x4_t*>(dx + col) = pack8(o);
       }
     }
@@ -373,8 +383,9 @@ void ln_bwd_kernel(const LnArgs a) {
 // row (as many bytes as x and dy together), and a wave asks for a row only after it has reduced and stored the one before
 // (profiles/r03_layernorm.txt: 2.8 TB/s of algorithmic bytes for the three-problem launches, finalize included).  Here lane l
 // owns the columns LaneCols deals it, gamma stays in registers, and the loads of the wave's next row are issued before the
-// reductions of the current.
-template <int NV, int H8>
+// reductions of the current.  ADD: as in ln_bwd_kernel; r's row travels with x's and dy's, a wave reads a row of r before it
+// stores that row of dx and no other wave touches the row, so r may be dx.
+template <int NV, int H8, bool ADD>
 __global__ __launch_bounds__(256)
 void ln_bwd_lane_kernel(const LnArgs a) {
   using LC = LaneCols<NV, H8>;
@@ -390,10 +401,12 @@ void ln_bwd_lane_kernel(const LnArgs a) {
 #pragma unroll
   for (int e = 0; e < EP; ++e) { dg[e] = 0.f; db[e] = 0.f; }
 
-  struct Row { typename LC::Bf16 x, dy; float mean, rstd; };
+  struct NoRow {};
+  struct Row { typename LC::Bf16 x, dy; std::conditional_t<ADD, typename LC::Bf16, NoRow> r; float mean, rstd; };
   auto fetch = [&](int row, Row& r) {
     LC::load(static_cast<const unsigned short*>(P.x) + (size_t)row * d, lane, r.x);
     LC::load(static_cast<const unsigned short*>(P.dy) + (size_t)row * d, lane, r.dy);
+    if constexpr (ADD) LC::load(static_cast<const unsigned short*>(P.y) + (size_t)row * d, lane, r.r);
     r.mean = P.mean[row];
     r.rstd = P.rstd[row];
   };
@@ -423,6 +436,12 @@ void ln_bwd_lane_kernel(const LnArgs a) {
     float o[EP];
 #pragma unroll
     for (int e = 0; e < EP; ++e) o[e] = rstd * (dv[e] - c1 - xv[e] * c2);
+    if constexpr (ADD) {
+      float rv[EP];
+      LC::unpack(cur.r, rv);
+#pragma unroll
+      for (int e = 0; e < EP; ++e) o[e] += rv[e];
+    }
     LC::store(static_cast<unsigned short*>(P.dx) + (size_t)row * d, lane, o);
     if (more) cur = nxt;
   }
@@ -483,13 +502,15 @@ thread_local int t_last_form = 0;
 using LnKernel = void (*)(const LnArgs);
 // chunk form, by nch = ceil(d / 512); its form id is nch
 const LnKernel CHUNK_FWD[MAX_CH] = {ln_fwd_kernel<1>, ln_fwd_kernel<2>, ln_fwd_kernel<3>, ln_fwd_kernel<4>};
-const LnKernel CHUNK_BWD[MAX_CH] = {ln_bwd_kernel<1>, ln_bwd_kernel<2>, ln_bwd_kernel<3>, ln_bwd_kernel<4>};
+const LnKernel CHUNK_BWD[MAX_CH] = {ln_bwd_kernel<1, false>, ln_bwd_kernel<2, false>, ln_bwd_kernel<3, false>, ln_bwd_kernel<4, false>};
+const LnKernel CHUNK_BWD_ADD[MAX_CH] = {ln_bwd_kernel<1, true>, ln_bwd_kernel<2, true>, ln_bwd_kernel<3, true>, ln_bwd_kernel<4, true>};
 // lane form: the widths d = 512 NV + 256 H8 it is instantiated for
 using Ln2Add3Kernel = void (*)(const Ln2Add3Args);
-struct LaneWidth { int d, form; LnKernel fwd, bwd; Ln2Add3Kernel fwd2_add3; };   // form id: 100 + 10 NV + H8
+struct LaneWidth { int d, form; LnKernel fwd, bwd, bwd_add; Ln2Add3Kernel fwd2_add3; };   // form id: 100 + 10 NV + H8
 template <int NV, int H8>
 constexpr LaneWidth lane_width_of() {
-  return {LaneCols<NV, H8>::D, 100 + 10 * NV + H8, ln_fwd_lane_kernel<NV, H8>, ln_bwd_lane_kernel<NV, H8>, ln2_add3_lane_kernel<NV, H8>};
+  return {LaneCols<NV, H8>::D, 100 + 10 * NV + H8, ln_fwd_lane_kernel<NV, H8>, ln_bwd_lane_kernel<NV, H8, false>,
+          ln_bwd_lane_kernel<NV, H8, true>, ln2_add3_lane_kernel<NV, H8>};
 }
 const LaneWidth LANE_WIDTHS[] = {lane_width_of<0, 1>(), lane_width_of<1, 0>(), lane_width_of<1, 1>(), lane_width_of<2, 0>()};
 const LaneWidth* lane_width(int d) {                   // null: d is no lane width
@@ -607,19 +628,19 @@ extern "C" size_t mmf_layernorm_bwd_workspace_bytes(int d) {
   return (size_t)(BWD_BLOCKS_CHUNK + MMF_LN_MAX_PROBLEMS) * 2 * (size_t)(d > 0 ? d : 0) * sizeof(float);
 }
 
-extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num_problems, int d,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_common("mmf_layernorm_bwd_grouped", problems, num_problems, d)) return rc;
+// the two backward entries: `add` = the residual r behind every problem's `y` is added into dx
+static int ln_bwd_run(const char* who, const mmf_ln_problem* problems, int num_problems, int d, void* workspace, size_t workspace_bytes,
+                      void* stream, bool add) {
+  if (int rc = check_common(who, problems, num_problems, d)) return rc;
   if (!workspace || workspace_bytes < mmf_layernorm_bwd_workspace_bytes(d) || !mmf_aligned16(workspace))
-    MMF_FAIL(MMF_E_SHAPE, "mmf_layernorm_bwd_grouped: workspace of %zu bytes (16-byte aligned) required",
-             mmf_layernorm_bwd_workspace_bytes(d));
+    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes (16-byte aligned) required", who, mmf_layernorm_bwd_workspace_bytes(d));
   LnArgs a; a.nprob = num_problems; a.d = d; a.eps = 0.f; a.ws = static_cast<float*>(workspace);
   for (int i = 0; i < num_problems; ++i) {
     const mmf_ln_problem& p = problems[i];
-    if (p.rows <= 0 || !p.x || !p.dy || !p.dx || !p.gamma || !p.mean || !p.rstd || !p.dgamma || !p.dbeta)
-      MMF_FAIL(MMF_E_SHAPE, "mmf_layernorm_bwd_grouped[%d]: null operand or rows=%d", i, p.rows);
-    if (!mmf_aligned16(p.x) || !mmf_aligned16(p.dy) || !mmf_aligned16(p.dx) || !mmf_aligned16(p.gamma))
-      MMF_FAIL(MMF_E_ALIGN, "mmf_layernorm_bwd_grouped[%d]: pointers must be 16-byte aligned", i);
+    if (p.rows <= 0 || !p.x || !p.dy || !p.dx || !p.gamma || !p.mean || !p.rstd || !p.dgamma || !p.dbeta || (add && !p.y))
+      MMF_FAIL(MMF_E_SHAPE, "%s[%d]: null operand or rows=%d", who, i, p.rows);
+    if (!mmf_aligned16(p.x) || !mmf_aligned16(p.dy) || !mmf_aligned16(p.dx) || !mmf_aligned16(p.gamma) || (add && !mmf_aligned16(p.y)))
+      MMF_FAIL(MMF_E_ALIGN, "%s[%d]: pointers must be 16-byte aligned", who, i);
     a.p[i] = p;
   }
   // Each workgroup leaves one row of column partials in the workspace (same-row float atomics would run ~14x below the
@@ -628,10 +649,21 @@ extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num
   const int total = share_blocks(a, problems, num_problems, lw ? BWD_BLOCKS_LANE : BWD_BLOCKS_CHUNK);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nch = (d + 511) / 512;
-  hipLaunchKernelGGL(lw ? lw->bwd : CHUNK_BWD[nch - 1], dim3(total), dim3(256), 0, s, a);
+  const LnKernel kernel = lw ? (add ? lw->bwd_add : lw->bwd) : (add ? CHUNK_BWD_ADD : CHUNK_BWD)[nch - 1];
+  hipLaunchKernelGGL(kernel, dim3(total), dim3(256), 0, s, a);
   t_last_form = lw ? lw->form : nch;
-  MMF_CHECK_LAUNCH(lw ? "mmf_layernorm_bwd_grouped(lane)" : "mmf_layernorm_bwd_grouped");
+  MMF_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((d + 255) / 256, num_problems, FIN_SLICES), dim3(256), 0, s, a);
-  MMF_CHECK_LAUNCH("mmf_layernorm_bwd_grouped(finalize)");
+  MMF_CHECK_LAUNCH(who);
   return MMF_OK;
+}
+
+extern "C" int mmf_layernorm_bwd_grouped(const mmf_ln_problem* problems, int num_problems, int d,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return ln_bwd_run("mmf_layernorm_bwd_grouped", problems, num_problems, d, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int mmf_layernorm_bwd_add_grouped(const mmf_ln_problem* problems, int num_problems, int d,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return ln_bwd_run("mmf_layernorm_bwd_add_grouped", problems, num_problems, d, workspace, workspace_bytes, stream, true);
 }

@@ -57,6 +57,166 @@ void vit_embed_tokens_kernel(const unsigned short* __restrict__ pe, const float*
   }
 }
 
+// vit_embed_tokens_kernel's backward: a thread owns 8 columns of one token position t and walks the images in order, so
+// dpos[t] (and dcls, for t = 0) += sum_n g[n][t] is one f32 chain per element in a fixed order with no atomics, and the rows
+// t >= 1 are copied to the patch embedding's gradient on the way.  Four images' loads are in flight per thread (the rows of one
+// position lie T * d elements apart); a wave reads 1 KiB contiguous per image.
+__global__ __launch_bounds__(VIT_THREADS)
+void vit_embed_tokens_bwd_kernel(const unsigned short* __restrict__ g, float* __restrict__ dcls, float* __restrict__ dpos,
+                                 unsigned short* __restrict__ dpe, int N, int T, int d) {
+  const unsigned dv = (unsigned)d >> 3, nvec = (unsigned)T * dv;
+  const size_t img = (size_t)T * d, pimg = (size_t)(T - 1) * d;
+  const unsigned stride = gridDim.x * VIT_THREADS;
+  for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const unsigned short* __restrict__ src = g + (size_t)v * 8;
+    unsigned short* __restrict__ dst = v >= dv ? dpe + (size_t)(v - dv) * 8 : nullptr;
+    float s[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = 0.f;
+    int n = 0;
+    for (; n + 4 <= N; n += 4) {
+      u32x4_t w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = *reinterpret_cast<const u32x4_t*>(src + (size_t)(n + u) * img);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float f[8];
+        unpack8(w[u], f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] += f[e];
+        if (dst) *reinterpret_cast<u32x4_t*>(dst + (size_t)(n + u) * pimg) = w[u];
+      }
+    }
+    for (; n < N; ++n) {
+      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(src + (size_t)n * img);
+      float f[8];
+      unpack8(w, f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] += f[e];
+      if (dst) *reinterpret_cast<u32x4_t*>(dst + (size_t)n * pimg) = w;
+    }
+    float* out = dpos + (size_t)v * 8;
+    f32x4_t a = *reinterpret_cast<const f32x4_t*>(out), b = *reinterpret_cast<const f32x4_t*>(out + 4);
+    *reinterpret_cast<f32x4_t*>(out) = a + f32x4_t{s[0], s[1], s[2], s[3]};
+    *reinterpret_cast<f32x4_t*>(out + 4) = b + f32x4_t{s[4], s[5], s[6], s[7]};
+    if (v < dv) {
+      float* c = dcls + (size_t)v * 8;
+      a = *reinterpret_cast<const f32x4_t*>(c), b = *reinterpret_cast<const f32x4_t*>(c + 4);
+      *reinterpret_cast<f32x4_t*>(c) = a + f32x4_t{s[0], s[1], s[2], s[3]};
+      *reinterpret_cast<f32x4_t*>(c + 4) = b + f32x4_t{s[4], s[5], s[6], s[7]};
+    }
+  }
+}
+
+// The attention backward of the CLS route's last layer: ONE query per image (row 0) over its T keys, on the fused q | k | v rows.
+// A workgroup owns one (image, head): T dot products of DH each way, HBM-bound (k and v read twice, dk and dv written once), so it
+// is plain f32 arithmetic and not the MFMA backward.  What it is for: mmf_attn_bwd_grouped takes delta = dO . O from the bf16 O,
+// which leaves dO . (O - bf16(O)) as the sum of a row of dS; with one query that residue times the mean key is all of dq's error and
+// it exceeded the storage model's at ViT-base sizes.  Here the softmax is formed again in f32 from the scores and
+// delta = sum_j p_j dp_j, so a row of dS sums to zero up to f32 rounding.  LPK lanes share a key (8 columns each, the lanes past
+// DH / 8 idle); every sum is reduced in a fixed order (lanes by butterfly, waves through LDS): two runs give the same bits.
+constexpr int CLS_MAX_T = 4096;                                        // s and dp of every key live in LDS: 2 x 4 x T bytes
+template <int DH>
+__global__ __launch_bounds__(VIT_THREADS)
+void vit_cls_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ dout,
+                             unsigned short* __restrict__ dqkv, int T, int d, float scale) {
+  constexpr int LPK = DH == 64 ? 8 : 16, KPB = VIT_THREADS / LPK, NW = VIT_THREADS / 64;      // lanes per key, keys per pass, waves
+  __shared__ float s_sc[CLS_MAX_T], s_dp[CLS_MAX_T];
+  __shared__ float s_red[2][NW];
+  __shared__ float s_dq[NW][DH];
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid % LPK, grp = tid / LPK;
+  const bool live = sub * 8 < DH;
+  const int ld = 3 * d;
+  const size_t row0 = (size_t)b * T;
+  const unsigned short* __restrict__ kbase = qkv + row0 * ld + d + h * DH + sub * 8;
+  const unsigned short* __restrict__ vbase = kbase + d;
+  float q[8], go[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { q[e] = 0.f; go[e] = 0.f; }
+  if (live) {
+    unpack8(*reinterpret_cast<const u32x4_t*>(qkv + row0 * ld + h * DH + sub * 8), q);
+    unpack8(*reinterpret_cast<const u32x4_t*>(dout + (size_t)b * d + h * DH + sub * 8), go);
+  }
+  // pass 1: the scaled scores and dp_j = dO . v_j
+  for (int j = grp; j < T; j += KPB) {
+    float a = 0.f, c = 0.f;
+    if (live) {
+      float kv[8], vv[8];
+      unpack8(*reinterpret_cast<const u32x4_t*>(kbase + (size_t)j * ld), kv);
+      unpack8(*reinterpret_cast<const u32x4_t*>(vbase + (size_t)j * ld), vv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { a += q[e] * kv[e]; c += go[e] * vv[e]; }
+    }
+#pragma unroll
+    for (int o = LPK / 2; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
+    if (sub == 0) { s_sc[j] = a * scale; s_dp[j] = c; }
+  }
+  __syncthreads();
+  // the softmax over the T scores, and delta = sum_j p_j dp_j
+  float m = -INFINITY;
+  for (int j = tid; j < T; j += VIT_THREADS) m = fmaxf(m, s_sc[j]);
+  m = wave_max(m);
+  if ((tid & 63) == 0) s_red[0][tid >> 6] = m;
+  __syncthreads();
+  m = s_red[0][0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) m = fmaxf(m, s_red[0][w]);
+  __syncthreads();
+  float se = 0.f, sd = 0.f;
+  for (int j = tid; j < T; j += VIT_THREADS) {
+    const float e = expf(s_sc[j] - m);
+    s_sc[j] = e;
+    se += e;
+    sd += e * s_dp[j];
+  }
+  se = wave_sum(se);
+  sd = wave_sum(sd);
+  if ((tid & 63) == 0) { s_red[0][tid >> 6] = se; s_red[1][tid >> 6] = sd; }
+  __syncthreads();
+  se = s_red[0][0];
+  sd = s_red[1][0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) { se += s_red[0][w]; sd += s_red[1][w]; }
+  const float inv = 1.f / se, delta = sd * inv;
+  // pass 2: dS_j = p_j (dp_j - delta); dk_j = scale dS_j q, dv_j = p_j dO, dq = scale sum_j dS_j k_j
+  float dq[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) dq[e] = 0.f;
+  unsigned short* __restrict__ dkbase = dqkv + row0 * ld + d + h * DH + sub * 8;
+  for (int j = grp; j < T; j += KPB) {
+    if (live) {
+      const float p = s_sc[j] * inv, ds = p * (s_dp[j] - delta), dss = ds * scale;
+      float kv[8], ok[8], ov[8];
+      unpack8(*reinterpret_cast<const u32x4_t*>(kbase + (size_t)j * ld), kv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { dq[e] += ds * kv[e]; ok[e] = dss * q[e]; ov[e] = p * go[e]; }
+      *reinterpret_cast<u32x4_t*>(dkbase + (size_t)j * ld) = pack8(ok);
+      *reinterpret_cast<u32x4_t*>(dkbase + d + (size_t)j * ld) = pack8(ov);
+    }
+  }
+  // dq: the key groups of a wave by butterfly (lanes LPK apart own the same columns), the waves through LDS
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+#pragma unroll
+    for (int o = 32; o >= LPK; o >>= 1) dq[e] += __shfl_xor(dq[e], o, 64);
+  if ((tid & 63) < LPK && live) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_dq[tid >> 6][sub * 8 + e] = dq[e];
+  }
+  __syncthreads();
+  if (tid < LPK && live) {
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float t = s_dq[0][sub * 8 + e];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) t += s_dq[w][sub * 8 + e];
+      o[e] = t * scale;
+    }
+    *reinterpret_cast<u32x4_t*>(dqkv + row0 * ld + h * DH + sub * 8) = pack8(o);
+  }
+}
+
 // y <- gelu(x + bias), rows x cols with row stride ld; y may be x (the in-place entry).  nvec = rows * cols / 8 < 2^31 (the host
 // splits longer inputs).
 template <bool HAS_BIAS>
@@ -162,6 +322,40 @@ extern "C" int mmf_vit_embed_tokens(const void* patch_emb_bf16, const float* cls
                      static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(patch_emb_bf16), cls, pos,
                      static_cast<unsigned short*>(tokens_bf16), T, d);
   MMF_CHECK_LAUNCH("mmf_vit_embed_tokens");
+  return MMF_OK;
+}
+
+extern "C" int mmf_vit_embed_tokens_bwd(const void* dtokens_bf16, float* dcls, float* dpos, void* dpatch_emb_bf16, int N, int T, int d,
+                                        void* stream) {
+  if (!dtokens_bf16 || !dcls || !dpos || !dpatch_emb_bf16 || N <= 0 || T < 2 || d <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_vit_embed_tokens_bwd: null operand or N=%d T=%d d=%d", N, T, d);
+  if (d & 7) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_embed_tokens_bwd: d=%d must be a multiple of 8", d);
+  if (N > 65535 || (int64_t)T * d >= (int64_t)1 << 31)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_embed_tokens_bwd: N=%d (at most 65535), T*d=%lld (below 2^31)", N, (long long)T * d);
+  if (!mmf_aligned16(dtokens_bf16) || !mmf_aligned16(dcls) || !mmf_aligned16(dpos) || !mmf_aligned16(dpatch_emb_bf16))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_vit_embed_tokens_bwd: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(vit_embed_tokens_bwd_kernel, dim3(mmf_stream_grid((int64_t)T * d / 8, VIT_THREADS)), dim3(VIT_THREADS), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(dtokens_bf16), dcls, dpos,
+                     static_cast<unsigned short*>(dpatch_emb_bf16), N, T, d);
+  MMF_CHECK_LAUNCH("mmf_vit_embed_tokens_bwd");
+  return MMF_OK;
+}
+
+extern "C" int mmf_vit_cls_attn_bwd(const void* qkv_bf16, const void* dout_bf16, void* dqkv_bf16, int N, int H, int T, int head_dim,
+                                    float scale, void* stream) {
+  if (!qkv_bf16 || !dout_bf16 || !dqkv_bf16 || N <= 0 || H <= 0 || T <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_vit_cls_attn_bwd: null operand or N=%d H=%d T=%d", N, H, T);
+  if (head_dim != 64 && head_dim != 96) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_cls_attn_bwd: head_dim=%d (supported: 64, 96)", head_dim);
+  if (T > CLS_MAX_T || N > 65535 || H > 65535 || (int64_t)N * T * 3 * H * head_dim >= (int64_t)1 << 40)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_vit_cls_attn_bwd: T=%d (at most %d), N=%d, H=%d (at most 65535)", T, CLS_MAX_T, N, H);
+  if (!mmf_aligned16(qkv_bf16) || !mmf_aligned16(dout_bf16) || !mmf_aligned16(dqkv_bf16))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_vit_cls_attn_bwd: pointers must be 16-byte aligned");
+  const unsigned short *qkv = static_cast<const unsigned short*>(qkv_bf16), *dout = static_cast<const unsigned short*>(dout_bf16);
+  unsigned short* dqkv = static_cast<unsigned short*>(dqkv_bf16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (head_dim == 64) hipLaunchKernelGGL(vit_cls_attn_bwd_kernel<64>, dim3(H, N), dim3(VIT_THREADS), 0, s, qkv, dout, dqkv, T, H * head_dim, scale);
+  else                hipLaunchKernelGGL(vit_cls_attn_bwd_kernel<96>, dim3(H, N), dim3(VIT_THREADS), 0, s, qkv, dout, dqkv, T, H * head_dim, scale);
+  MMF_CHECK_LAUNCH("mmf_vit_cls_attn_bwd");
   return MMF_OK;
 }
 

@@ -16,7 +16,10 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
       fc2 + bias + resid            mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> out
     _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
     _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
-    _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; NativeDeberta's backward)
+    _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; the backward of NativeDeberta and NativeViT)
+    _ln_bwd_add(...)                mmf_layernorm_bwd_add_grouped        dy, r -> dx = r + that (a pre-LN layer's residual gradient)
+    _wgrad(dy, x, name, slabs)      mmf_gemm_grouped TN, COLSUM_A        dy, x -> a trainable layer's weight and bias gradients; in
+                                    (+ mmf_sum_slabs_f32)                ``slabs`` K-slabs where the output is a few tiles under many rows
 
 Parameters are stored as the kernels read them (Q/K/V fused, a subclass may store a weight with its last two dims swapped)
 and ``_hf`` maps every HuggingFace key to its view of them, in HuggingFace's order, so ``state_dict()`` and
@@ -25,9 +28,10 @@ names.  A subclass declares its workspace as a table of (name, elements per chun
 allocation and the bytes-per-item figure are both read from that table.  A forward pass writes no attribute of the module
 but that workspace and the ``_derived`` cache: what a launch needs beyond the buffers travels as arguments.
 
-Frozen: every parameter has ``requires_grad = False``.  Forward only, the outputs carrying no autograd graph, but for
-``NativeDeberta``: called with input embeddings that require a gradient (prompt tuning), or with its top layers marked
-trainable (``set_trainable_layers``: those layers' parameters then require a gradient), mmfusion/deberta.py.  bf16
+Frozen by default: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  Two backbones have a
+backward: ``NativeDeberta`` called with input embeddings that require a gradient (prompt tuning), and it and ``NativeViT`` with
+their top layers marked trainable (``set_trainable_layers``: those layers' parameters then require a gradient and a call in grad
+mode adds their gradients into the parameter arena), mmfusion/deberta.py and mmfusion/vit.py; ``NativeWav2Vec2`` is forward only.  bf16
 storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
 Nothing synchronises with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.
 """
@@ -38,8 +42,9 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
+from . import arena as _arena
 from . import lib, ops
-from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NT, AttnProblem, LnProblem
+from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, GEMM_NT, GEMM_TN, AttnProblem, LnProblem
 
 BF16 = torch.bfloat16
 LN_WIDTHS = (256, 512, 768, 1024)          # the lane forms of layernorm.hip
@@ -77,6 +82,18 @@ class FrozenBackbone(nn.Module):
         self._hf: Dict[str, Tuple[str, Optional[Tuple[int, int]], bool]] = {}
         self._ws: Optional[dict] = None
         self._cache: Dict[str, tuple] = {}             # _derived: slot -> (stamp of the parameters it was built from, value)
+        self._trainable = 0                            # a subclass's set_trainable_layers
+        self._gws: Optional[dict] = None               # a backward's workspace (the subclass's _grad_table), from the first differentiable call
+        self._slabs: Optional[torch.Tensor] = None     # _slab_buffer
+
+    # -- fine-tuning the top layers (NativeDeberta, NativeViT) -------------------------------------------
+    @staticmethod
+    def _layer_params(i: int) -> list:
+        return [f"l{i}_{r}_{s}" for r in ("qkv", "o", "ln1", "fc1", "fc2", "ln2") for s in "wb"]
+
+    @property
+    def trainable_layers(self) -> int:
+        return self._trainable
 
     # -- parameter table --------------------------------------------------------------------------------
     def _add(self, name: str, shape, key: Optional[str] = None, *, ones: bool = False, std: float = 0.02, swapped: bool = False):
@@ -232,6 +249,84 @@ class FrozenBackbone(nn.Module):
             lib.layernorm_bwd_grouped([LnProblem(src.data_ptr(), None, self._f(gamma).data_ptr(), None, scratch["mean"].data_ptr(),
                                                  scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma, dbeta, rows)],
                                       width, scratch["ln_ws"])
+
+    def _ln_bwd_add(self, scratch, src: torch.Tensor, dy: torch.Tensor, resid: torch.Tensor, dx: torch.Tensor, gamma: str, into=None) -> None:
+        """``_ln_bwd`` with the residual gradient folded in: dx = resid + the LayerNorm input gradient (a pre-LN layer: the
+        LayerNorm's input also feeds the residual add behind the block, so its gradient is the sum of the two); ``resid`` (bf16
+        rows like dx) may be dx"""
+        rows, width = src.shape
+        if into is None:
+            dgb = scratch["dgb"]
+            dgb.zero_()
+            dgamma, dbeta = dgb.data_ptr(), dgb.data_ptr() + 4 * width
+        else:
+            dgamma, dbeta = into[0].data_ptr(), into[1].data_ptr()
+        with lib._Timed("ln_bwd_kernel", 0.0, [(rows, width)]):
+            lib.layernorm_bwd_add_grouped([LnProblem(src.data_ptr(), resid.data_ptr(), self._f(gamma).data_ptr(), None, scratch["mean"].data_ptr(),
+                                                     scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma, dbeta, rows)],
+                                          width, scratch["ln_ws"])
+
+    # -- weight gradients of the trainable layers ----------------------------------------------------------
+    @staticmethod
+    def _first_touch(wgrad: torch.Tensor) -> bool:
+        """The arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it: whether the launch that is about to produce the
+        gradient ``wgrad`` (a parameter's ``.grad``) must overwrite it (the first write of a step into a lazily zeroed weight
+        gradient) or accumulate (every later one)"""
+        ar = _arena.arena_of(wgrad)
+        return ar is not None and ar.take_first_touch(wgrad)
+
+    @staticmethod
+    def _slab_bounds(rows: int, slabs: int) -> List[int]:
+        """the row range [0, rows) cut into at most ``slabs`` K-slabs whose lengths are multiples of 32 (the last one takes the
+        rest) and differ by at most 32 -> the slabs' first rows and ``rows``"""
+        units = (rows + 31) // 32
+        S = max(1, min(int(slabs), units))
+        cuts, at = [0], 0
+        for s in range(S):
+            at += units // S + (1 if s < units % S else 0)
+            cuts.append(min(rows, 32 * at))
+        return cuts
+
+    def _wgrad_launch(self, parts: Sequence[tuple], overwrite: bool, slabs: int = 1) -> None:
+        """One grouped TN launch, now, in stream order (the operands are workspace views the next launch overwrites), for
+        ``parts`` = (dy, x, wgrad, bgrad): wgrad (+)= dy^T x and bgrad += colsum(dy) (the GEMM's fused column sum, always added).
+        ``slabs`` > 1, the K-slab form for few tiles under many rows: the parts must share their row count and their wgrads tile
+        one contiguous block of a gradient in order; every part's rows are cut into ``slabs`` K-slabs (``_slab_bounds``) whose
+        products land in f32 partial buffers, all in the one launch, and ``mmf_sum_slabs_f32`` writes or adds their sum, slab 0
+        first, into the block.  The bias column sums go straight to bgrad in both forms"""
+        if slabs <= 1:
+            ops.gemm_group(GEMM_TN, [(dy, x, wg, bg, None) for dy, x, wg, bg in parts], (0 if overwrite else EPI_ACCUM) | EPI_COLSUM_A)
+            return
+        cuts = self._slab_bounds(parts[0][0].shape[0], slabs)
+        S, total = len(cuts) - 1, sum(wg.numel() for _, _, wg, _ in parts)
+        first = parts[0][2]
+        block = torch.as_strided(first, (total,), (1,))
+        if S > lib.SUM_SLABS_MAX or any(dy.shape[0] != cuts[-1] or not wg.is_contiguous() for dy, _, wg, _ in parts):
+            raise ValueError("_wgrad_launch: the K-slab form takes parts of one row count with contiguous gradients, at most "
+                             f"{lib.SUM_SLABS_MAX} slabs")
+        partial = self._slab_buffer(S * total, first.device).view(S, total)
+        probs, off = [], 0
+        for dy, x, wg, bg in parts:
+            if wg.data_ptr() != first.data_ptr() + 4 * off:
+                raise ValueError("_wgrad_launch: the parts' gradients must tile one contiguous block in order")
+            for s in range(S):
+                probs.append((dy[cuts[s]:cuts[s + 1]], x[cuts[s]:cuts[s + 1]], partial[s, off:off + wg.numel()].view(wg.shape), bg, None))
+            off += wg.numel()
+        ops.gemm_group(GEMM_TN, probs, EPI_COLSUM_A)
+        lib.sum_slabs(partial, block, not overwrite)
+
+    def _slab_buffer(self, numel: int, dev) -> torch.Tensor:
+        """the K-slab partial products' f32 buffer, kept beside the backward's workspace and grown on demand"""
+        buf = self._slabs
+        if buf is None or buf.numel() < numel or buf.device != dev:
+            buf = self._slabs = torch.empty(numel, dtype=torch.float32, device=dev)
+        return buf[:numel]
+
+    def _wgrad(self, dy: torch.Tensor, x: torch.Tensor, name: str, slabs: int = 1) -> None:
+        """``l{i}_{role}``'s weight gradient += dy^T x and bias gradient += colsum(dy) (``_wgrad_launch`` on the whole weight;
+        ``slabs`` = 1: one plain launch)"""
+        w, b = getattr(self, name + "_w").grad, getattr(self, name + "_b").grad
+        self._wgrad_launch([(dy, x, w, b)], self._first_touch(w), slabs)
 
     def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
         """attention of ``Tq`` queries per item over its ``T`` keys, read from the fused ``qkv`` rows; ``Tq == 1`` takes the

@@ -231,18 +231,8 @@ class NativeDeberta(FrozenBackbone):
         add("enc_ln_b", (d,), "encoder.LayerNorm.bias", std=0.0)
         self.embeddings = types.SimpleNamespace(word_embeddings=_WordEmbeddings(self))
         self._idx: Dict[Tuple, torch.Tensor] = {}      # (T, S, max position, device) -> the int32 table on that device
-        self._gws: Optional[dict] = None               # the backward's workspace (_grad_table), from the first differentiable call
-        self._trainable = 0                            # set_trainable_layers
 
     # -- fine-tuning the top layers ----------------------------------------------------------------------
-    @staticmethod
-    def _layer_params(i: int) -> list:
-        return [f"l{i}_{r}_{s}" for r in ("qkv", "o", "ln1", "fc1", "fc2", "ln2") for s in "wb"]
-
-    @property
-    def trainable_layers(self) -> int:
-        return self._trainable
-
     def set_trainable_layers(self, k: int) -> None:
         """The parameters of the top ``k`` layers (``L - k .. L - 1``) get ``requires_grad = True``, every other parameter
         ``False``; 0 freezes the backbone again.  With grad mode on and ``k > 0`` a call returns a result that carries a graph,
@@ -417,15 +407,6 @@ class NativeDeberta(FrozenBackbone):
         return out
 
     # -- the backward: input gradient and the trainable layers' weight gradients -------------------------------------
-    def _wgrad(self, dy: torch.Tensor, x: torch.Tensor, name: str) -> None:
-        """``l{i}_{role}``'s weight gradient += dy^T x and bias gradient += colsum(dy), now, in stream order (the operands are
-        workspace views the next launch overwrites).  The arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it: the first
-        write of a step into a lazily zeroed weight gradient overwrites, every later one accumulates"""
-        w, b = getattr(self, name + "_w").grad, getattr(self, name + "_b").grad
-        ar = _arena.arena_of(w)
-        overwrite = ar is not None and ar.take_first_touch(w)
-        ops.gemm_group(GEMM_TN, [(dy, x, w, b, None)], (0 if overwrite else EPI_ACCUM) | EPI_COLSUM_A)
-
     def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor],
                     dpos: Optional[torch.Tensor] = None, below: bool = True) -> None:
         """layer ``i`` again from its saved input ``xin``, then its backward: ``ga`` holds the gradient of the layer's output on

@@ -28,18 +28,18 @@ SYMBOLS = (
     "mmf_gemm7_set_tile_n", "mmf_gemm7_last_tile_n", "mmf_gemm7_tile_n",
     "mmf_attn_fwd_grouped_ex", "mmf_attn_bwd_grouped_ex", "mmf_dropout", "mmf_attn_select_impl",
     "mmf_attn_fwd_grouped", "mmf_attn_bwd_grouped", "mmf_layernorm_fwd_grouped",
-    "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_layernorm2_add3_available", "mmf_layernorm2_add3_fwd_grouped", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
+    "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_add_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_layernorm2_add3_available", "mmf_layernorm2_add3_fwd_grouped", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
     "mmf_meanpool_fwd", "mmf_meanpool_bwd", "mmf_meanpool_cat_fwd", "mmf_meanpool_cat_bwd", "mmf_colsum_bf16", "mmf_colsum_grouped", "mmf_relu_bwd_bf16", "mmf_relu_bwd_mixed",
     "mmf_sqnorm_f32", "mmf_adamw_step", "mmf_adamw_advance", "mmf_skinny_linear_fwd", "mmf_skinny_linear_dgrad", "mmf_skinny_linear_fwd_ex", "mmf_skinny_linear_dgrad_ex", "mmf_skinny_last_strip",
     "mmf_gat3_dense_fwd", "mmf_gat3_dense_bwd", "mmf_infonce_fwd", "mmf_infonce_bwd", "mmf_adaptive_combine_fwd",
     "mmf_adaptive_combine_bwd", "mmf_adaptive_attn_weights", "mmf_linear_narrow_fwd", "mmf_linear_narrow_bwd", "mmf_stack3_embed_fwd",
-    "mmf_stack3_embed_bwd", "mmf_rowmask_apply", "mmf_zero_ranges_f32", "mmf_fusion_loss", "mmf_modality_dropout",
+    "mmf_stack3_embed_bwd", "mmf_rowmask_apply", "mmf_zero_ranges_f32", "mmf_sum_slabs_f32", "mmf_fusion_loss", "mmf_modality_dropout",
     "mmf_attn_weights_mean", "mmf_gemm_f32_grouped", "mmf_gemm_f32_batched", "mmf_softmax_rows_f32", "mmf_softmax_bwd_rows_f32",
     "mmf_layernorm_f32_fwd", "mmf_layernorm_f32_bwd", "mmf_bilstm_workspace_bytes", "mmf_bilstm_layer_fwd", "mmf_bilstm_layer_bwd", "mmf_swap01",
     "mmf_distill_kl", "mmf_fusion_loss_kd", "mmf_robust_head_fwd", "mmf_robust_head_bwd",
     "mmf_fewshot_proto_fwd", "mmf_fewshot_proto_bwd", "mmf_fewshot_dist_fwd", "mmf_fewshot_dist_bwd",
     "mmf_eval_accumulate",
-    "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_bias_gelu_bf16", "mmf_bias_gelu_bf16_to", "mmf_bias_gelu_bwd_bf16",
+    "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_vit_embed_tokens_bwd", "mmf_vit_cls_attn_bwd", "mmf_bias_gelu_bf16", "mmf_bias_gelu_bf16_to", "mmf_bias_gelu_bwd_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
@@ -159,6 +159,7 @@ def load() -> C.CDLL:
     lib.mmf_attn_bwd_grouped.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
     lib.mmf_layernorm_fwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, f32, vp]
     lib.mmf_layernorm_bwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
+    lib.mmf_layernorm_bwd_add_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
     lib.mmf_layernorm_bwd_workspace_bytes.argtypes = [i32]
     lib.mmf_layernorm_bwd_workspace_bytes.restype = C.c_size_t
     lib.mmf_layernorm2_add3_available.argtypes = [C.POINTER(C.c_int32), i32, i32]
@@ -212,6 +213,7 @@ def load() -> C.CDLL:
     lib.mmf_stack3_embed_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mmf_rowmask_apply.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.mmf_zero_ranges_f32.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32, vp]
+    lib.mmf_sum_slabs_f32.argtypes = [vp, vp, i64, i32, i32, vp]
     lib.mmf_adamw_step.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
     lib.mmf_adamw_advance.argtypes = [vp, vp, vp, vp]
     lib.mmf_bilstm_workspace_bytes.restype = C.c_size_t
@@ -220,6 +222,8 @@ def load() -> C.CDLL:
     lib.mmf_swap01.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_vit_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_vit_embed_tokens.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_vit_embed_tokens_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.mmf_vit_cls_attn_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp]
     lib.mmf_bias_gelu_bf16.argtypes = [vp, vp, i64, i32, i32, vp]
     lib.mmf_bias_gelu_bf16_to.argtypes = [vp, vp, vp, i64, i32, i32, vp]
     lib.mmf_bias_gelu_bwd_bf16.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp]
@@ -360,6 +364,27 @@ def layernorm_bwd_grouped(problems: Sequence[LnProblem], d: int, workspace) -> N
                                            workspace.numel() * workspace.element_size(), stream_ptr()))
 
 
+def layernorm_bwd_add_grouped(problems: Sequence[LnProblem], d: int, workspace) -> None:
+    """``layernorm_bwd_grouped`` with dx = r + the input gradient, r the bf16 rows behind each problem's ``y`` (it may be dx)."""
+    arr = (LnProblem * len(problems))(*problems)
+    check(load().mmf_layernorm_bwd_add_grouped(arr, len(problems), d, workspace.data_ptr(),
+                                               workspace.numel() * workspace.element_size(), stream_ptr()))
+
+
+SUM_SLABS_MAX = 64               # MMF_SUM_SLABS_MAX of include/mmfusion.h
+
+
+def sum_slabs(partial, out, accumulate: bool) -> None:
+    """out (f32, contiguous) = (out if ``accumulate`` else 0) + partial[0] + ... + partial[S - 1] in that order; partial (S, numel of
+    out) f32 contiguous"""
+    import torch
+    if partial.dtype != torch.float32 or out.dtype != torch.float32 or not partial.is_contiguous() or not out.is_contiguous() \
+            or partial.dim() != 2 or partial.shape[1] != out.numel():
+        raise ValueError("sum_slabs: partial must be contiguous f32 (slabs, out.numel()) and out contiguous f32")
+    with _Timed("sum_slabs_kernel", 0.0, [(partial.shape[0], out.numel())]):
+        check(load().mmf_sum_slabs_f32(partial.data_ptr(), out.data_ptr(), out.numel(), partial.shape[0], int(bool(accumulate)), stream_ptr()))
+
+
 def colsum_grouped(problems: Sequence[ColsumProblem]) -> None:
     for i in range(0, len(problems), COLSUM_MAX_PROBLEMS):
         chunk = problems[i:i + COLSUM_MAX_PROBLEMS]
@@ -413,6 +438,28 @@ def vit_embed_tokens(patch_emb, cls, pos, tokens, N: int, T: int, d: int) -> Non
     with _Timed("vit_embed_tokens_kernel", 0.0, [(N * T, d)]):
         check(load().mmf_vit_embed_tokens(patch_emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), tokens.data_ptr(), N, T, d,
                                           stream_ptr()))
+
+
+def vit_embed_tokens_bwd(dtokens, dcls, dpos, dpatch_emb, N: int, T: int, d: int) -> None:
+    """dtokens (N T, d) bf16 -> dcls (d) f32 += its rows n T summed over n, dpos (T, d) f32 += its rows summed over n per position,
+    dpatch_emb (N (T - 1), d) bf16 = its rows 1 .. T - 1 of every image"""
+    if dtokens.numel() != N * T * d or not dtokens.is_contiguous() or dcls.numel() != d or dpos.numel() != T * d \
+            or dpatch_emb.numel() != N * (T - 1) * d or not dpatch_emb.is_contiguous() or not dcls.is_contiguous() or not dpos.is_contiguous():
+        raise ValueError("vit_embed_tokens_bwd: operand sizes do not match N, T, d")
+    with _Timed("vit_embed_tokens_bwd_kernel", 0.0, [(N * T, d)]):
+        check(load().mmf_vit_embed_tokens_bwd(dtokens.data_ptr(), dcls.data_ptr(), dpos.data_ptr(), dpatch_emb.data_ptr(), N, T, d,
+                                              stream_ptr()))
+
+
+def vit_cls_attn_bwd(qkv, dout, dqkv, N: int, H: int, T: int, head_dim: int, scale: float) -> None:
+    """qkv (N T, 3 H head_dim) bf16 fused rows, dout (N, H head_dim) bf16 -> dqkv laid out as qkv: the backward of the attention
+    of row 0 of each image over its T keys (dq on row 0, dk | dv on every row)"""
+    d = H * head_dim
+    if tuple(qkv.shape) != (N * T, 3 * d) or tuple(dqkv.shape) != (N * T, 3 * d) or tuple(dout.shape) != (N, d) \
+            or not (qkv.is_contiguous() and dqkv.is_contiguous() and dout.is_contiguous()):
+        raise ValueError("vit_cls_attn_bwd: operand shapes do not match N, H, T, head_dim")
+    with _Timed("vit_cls_attn_bwd_kernel", 0.0, [(N * T, 2 * d)]):
+        check(load().mmf_vit_cls_attn_bwd(qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), N, H, T, head_dim, scale, stream_ptr()))
 
 
 def bias_gelu(x, bias=None) -> None:

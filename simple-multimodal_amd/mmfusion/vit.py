@@ -1,4 +1,5 @@
-"""Frozen ViT backbone on the HIP kernels: video frames -> token states / CLS features, forward only.
+"""ViT backbone on the HIP kernels: video frames -> token states / CLS features; frozen by default, with the weight gradients of
+the top layers marked trainable (fine-tuning).
 
 The reference pushes ``B x 30`` frames through HuggingFace's ``ViTModel`` per step and keeps the CLS token of each
 (reference models/encoders.py:179,216-226).  ``NativeViT`` is that model rebuilt from its sizes alone (nothing is
@@ -18,7 +19,40 @@ final LayerNorm and one widening cast into the f32 result.  Decoded uint8 ``(N, 
 K and V for every token, but Q, the out-projection, the MLP and the final LayerNorm for row 0 of each image (``Tq = 1``).
 
 Frames are processed in chunks of ``chunk`` images through one workspace allocated once, so memory does not grow with
-``B x frames``.  Forward only, frozen, bf16 storage only, nothing synchronises with the host (mmfusion/backbone.py).
+``B x frames``.  Frozen by default, bf16 storage only, nothing synchronises with the host (mmfusion/backbone.py).
+
+The top-K weight gradients.  ``set_trainable_layers(k, embeddings=False)`` marks the parameters of layers ``L - k .. L - 1`` and the
+final LayerNorm trainable (with ``k == L`` and ``embeddings``: the CLS token, the position embeddings and the patch projection
+too).  With grad mode on every call is then one ``torch.autograd.Function`` around the launch list above (the trainable
+parameters are its inputs, so the result carries a graph; there is no gradient with respect to the pixels) plus one copy per
+walked layer: it keeps the bf16 input ``x`` of layers ``>= L - k`` and of the final LayerNorm.  The backward, per chunk: the final
+LayerNorm's backward, then per layer top down the layer's forward again from its saved ``x`` up to the GELU output (nothing
+behind fc2 is read by a pre-LN layer's backward) and
+
+      fc2 wgrad, dgrad              mmf_gemm_grouped TN (COLSUM_A) / NN      gx -> dg
+      GELU backward                 mmf_bias_gelu_bwd_bf16 (in place)        dg, h -> dh
+      fc1 wgrad, dgrad              TN / NN                                  dh -> dln2
+      LayerNorm backward + gx       mmf_layernorm_bwd_add_grouped            dln2, y (+ gx) -> dy
+      out-projection wgrad, dgrad   TN / NN                                  dy -> datt
+      attention backward            mmf_attn_bwd_grouped on the fused rows   datt -> dqkv
+      Q/K/V wgrad, dgrad            TN / NN                                  dqkv -> dln1
+      LayerNorm backward + dy       mmf_layernorm_bwd_add_grouped            dln1, x (+ dy) -> gx of the layer below
+
+The residual gradient of a pre-LN layer joins behind a LayerNorm backward, where no GEMM epilogue can add it: the LayerNorm
+backward takes it as one more operand (f32 add in front of dx's one rounding, in place).  The key bias gets no column sum: its
+exact gradient is zero (a shift of every key by one vector moves every score of a row equally), what a sum of dK would add is
+the bf16 residue of delta and dK.  A weight gradient over a chunk's rows is a few 256 x 256 output tiles under tens of
+thousands of rows; ``_slabs_for`` cuts the rows into K-slabs that one grouped launch multiplies and ``mmf_sum_slabs_f32`` sums
+(mmfusion/backbone.py ``_wgrad_launch``; DESIGN.md section 8 has the rule and its measurements).  On the ``cls_features`` route
+the last layer's backward has ``_layer_cls``'s form: MLP, out-projection and both LayerNorms on one row per image, the attention
+backward of that one query per image as ``mmf_vit_cls_attn_bwd`` (dQ for row 0, dK | dV for every row; plain f32 with
+delta = sum_j p_j dp_j: ``mmf_attn_bwd_grouped``'s delta = dO . O carries the rounding of the bf16 O, which a single query's dQ and
+dK do not average out), the Q rows of the weight gradient over those ``n`` rows and the
+K | V rows over all; dln1 is the K | V input gradient plus, on row 0, the Q one (through a zeroed buffer the K | V GEMM's epilogue
+adds), and the residual gradient reaches row 0 only (a zeroed buffer with those rows copied in).  With the embeddings trainable,
+``mmf_vit_embed_tokens_bwd`` sums the CLS / position gradients over the images and the patch matrix is built again for the patch
+projection's weight gradient.  Gradients are added into the parameters' f32 ``.grad`` (the arena's lazy-zero protocol as
+``ops.queue_wgrad`` keeps it) in stream order; what the backward holds beside the forward workspace is ``_grad_table``.
 """
 from __future__ import annotations
 
@@ -30,8 +64,8 @@ import torch
 
 from . import arena as _arena
 from . import lib, ops
-from .backbone import BackboneOutput, FrozenBackbone, WsTable
-from .lib import EPI_BIAS, GEMM_NT
+from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
+from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NN, GEMM_NT
 from .prep import VideoAug
 
 # images per pass through the workspace (tools/vit_bench.py --chunks; DESIGN.md section 8 has the numbers)
@@ -67,11 +101,37 @@ def hf_key_to_v4(key: str) -> str:
     return key
 
 
+class _Differentiable(torch.autograd.Function):
+    """``NativeViT._launches``, differentiable with respect to the trainable parameters (``params``; never to the pixels).  They
+    are inputs so that the result carries a graph; their gradients are not returned but added into their f32 ``.grad`` by the
+    backward's own launches, as ``ops.queue_wgrad``'s are."""
+
+    @staticmethod
+    def forward(ctx, model: "NativeViT", pixels: torch.Tensor, cls_only: bool, aug: Optional[VideoAug], *params) -> torch.Tensor:
+        N, T, d, L = pixels.shape[0], model.T, model.config.hidden_size, model.config.num_hidden_layers
+        first = L - model.trainable_layers                             # the lowest layer the backward walks
+        keep = torch.empty((L - first, N * T, d), dtype=BF16, device=pixels.device)
+        final = torch.empty((N if cls_only else N * T, d), dtype=BF16, device=pixels.device)
+        out = model._launches(pixels, cls_only, aug, keep, first, final)
+        ctx.model, ctx.cls_only, ctx.aug, ctx.first, ctx.embeddings = model, cls_only, aug, first, model.trainable_embeddings
+        ctx.save_for_backward(pixels, keep, final)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        pixels, keep, final = ctx.saved_tensors
+        if any(ctx.needs_input_grad[4:]):
+            ctx.model._backward(pixels, ctx.cls_only, ctx.aug, keep, final, ctx.first, ctx.embeddings, dout.contiguous())
+        return (None,) * len(ctx.needs_input_grad)
+
+
 class NativeViT(FrozenBackbone):
     """ViT encoder (HuggingFace ``ViTModel`` without the pooler's arithmetic), defaults = ViT-base/16 at 224 x 224.
 
     ``forward(pixel_values)`` -> ``.last_hidden_state`` (N, T, hidden) f32 after the final LayerNorm;
     ``cls_features(pixel_values)`` -> (N, hidden) f32, row 0 of the same with the last layer run for those rows only.
+    Frozen by default; after ``set_trainable_layers(k)``, ``k > 0``, both carry the top ``k`` layers' weight gradients when
+    called in grad mode (never a gradient with respect to ``pixel_values``).
     ``pixel_values``: (N, C, H, W) f32 on the GPU, or decoded frames (N, Hs, Ws, 3) uint8 of any size, which are resized to
     the model's on the way into the patch matrix; ``aug`` (a ``prep.VideoAug``, uint8 input only) says how.  ``state_dict()`` has the keys and shapes of transformers 5.x;
     ``load_state_dict`` takes those and the 4.x names (``encoder.layer.N.attention.attention.query...``); Q/K/V are
@@ -109,6 +169,40 @@ class NativeViT(FrozenBackbone):
         add("ln_b", (d,), "layernorm.bias", std=0.0)
         add("pooler_w", (d, d), "pooler.dense.weight")
         add("pooler_b", (d,), "pooler.dense.bias", std=0.0)
+        self._embeddings = False                       # set_trainable_layers(L, embeddings=True)
+
+    # -- fine-tuning --------------------------------------------------------------------------------------
+    _EMBEDDING_PARAMS = ("cls_token", "position_embeddings", "patch_weight", "patch_bias")
+
+    @property
+    def trainable_embeddings(self) -> bool:
+        return self._embeddings
+
+    def _trainable_names(self) -> list:
+        """the parameters that require a gradient, in the order the differentiable forward takes them"""
+        L, k = self.config.num_hidden_layers, self._trainable
+        names = list(self._EMBEDDING_PARAMS) if self._embeddings else []
+        names += [n for i in range(L - k, L) for n in self._layer_params(i)]
+        return names + (["ln_w", "ln_b"] if k else [])
+
+    def set_trainable_layers(self, k: int, embeddings: bool = False) -> None:
+        """The parameters of the top ``k`` layers (``L - k .. L - 1``) and, for ``k >= 1``, the final LayerNorm get
+        ``requires_grad = True``, every other parameter ``False``; 0 freezes the backbone again.  ``embeddings=True`` (with
+        ``k == L`` only: the gradient reaches them through every layer) also trains the CLS token, the position embeddings and
+        the patch projection.  With grad mode on and ``k > 0``, ``forward`` and ``cls_features`` return a result that carries a
+        graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops
+        below layer ``L - k``.  ``pooler.dense`` stays frozen whatever ``k`` (nothing reads it), there is no gradient with respect
+        to the pixels, the backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
+        L = self.config.num_hidden_layers
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
+            raise ValueError(f"NativeViT: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
+        if not isinstance(embeddings, bool) or (embeddings and k != L):
+            raise ValueError(f"NativeViT: set_trainable_layers({k!r}, embeddings={embeddings!r}): the embeddings train with all "
+                             f"{L} layers only (their gradient comes through every layer)")
+        self._trainable, self._embeddings = k, embeddings
+        names = set(self._trainable_names())
+        for name, p in self.named_parameters(recurse=False):
+            p.requires_grad_(name in names)
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _canonical_key(self, key: str) -> str:
@@ -142,32 +236,50 @@ class NativeViT(FrozenBackbone):
     def _layer_cls(self, i: int, ws, n: int) -> None:
         """The last layer for the CLS rows: K / V of every token, everything else on row 0 of each image.  Leaves the
         layer's output for those rows in the leading ``n`` rows of ``x``."""
-        T, d = self.T, self.config.hidden_size
-        rows = n * T
-        x, ln, qkv = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d), self._rows(ws, "qkv", rows, 3 * d)
-        att, y, ln0 = (self._rows(ws, k, n, d) for k in ("att", "y", "ln"))
-        self._ln(ws, x, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        w, b = self._w(f"l{i}_qkv_w"), self._f(f"l{i}_qkv_b")
-        row0 = lambda t, width: t.view(n, T * width)[:, :d]          # row 0 of each image, as an (n, d) row-strided view
-        ops.gemm_group(GEMM_NT, [(ln, w[d:], qkv[:, d:], b[d:], None), (row0(ln, d), w[:d], row0(qkv, 3 * d), b[:d], None)], EPI_BIAS)
-        self._attn(ws, qkv, att, n, 1, T)
-        self._out_proj(i, att, row0(x, d), y)
+        d = self.config.hidden_size
+        y, ln0 = self._cls_attention(i, ws, ws, self._rows(ws, "x", n * self.T, d), n), self._rows(ws, "ln", n, d)
         self._ln(ws, y, ln0, f"l{i}_ln2_w", f"l{i}_ln2_b")
         self._ffn(i, ws, ln0, y, self._rows(ws, "x", n, d))
 
-    def _embed(self, ws, pixels: torch.Tensor, n: int, aug: Optional[VideoAug]) -> None:
-        c, T, d, K, NP = self.config, self.T, self.config.hidden_size, self.patch_dim, self.num_patches
+    def _row0(self, t: torch.Tensor, n: int) -> torch.Tensor:
+        """row 0 of each image's leading ``hidden`` columns of a contiguous (n T, width) buffer, as an (n, hidden) row-strided view"""
+        return t.view(n, self.T * t.shape[1])[:, :self.config.hidden_size]
+
+    def _cls_attention(self, i: int, ws, st, x: torch.Tensor, n: int) -> torch.Tensor:
+        """the attention block of ``_layer_cls`` on the layer input ``x`` (n T rows) -> y (n rows) = row 0 of x + the
+        out-projection; ``ln`` keeps LayerNorm(x) of every row and ``st`` (``mean`` / ``rstd``) its statistics"""
+        T, d = self.T, self.config.hidden_size
+        rows = n * T
+        ln, qkv = self._rows(ws, "ln", rows, d), self._rows(ws, "qkv", rows, 3 * d)
+        att, y = self._rows(ws, "att", n, d), self._rows(ws, "y", n, d)
+        self._ln(st, x, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
+        w, b = self._w(f"l{i}_qkv_w"), self._f(f"l{i}_qkv_b")
+        ops.gemm_group(GEMM_NT, [(ln, w[d:], qkv[:, d:], b[d:], None), (self._row0(ln, n), w[:d], self._row0(qkv, n), b[:d], None)], EPI_BIAS)
+        self._attn(ws, qkv, att, n, 1, T)
+        self._out_proj(i, att, self._row0(x, n), y)
+        return y
+
+    def _patches(self, ws, pixels: torch.Tensor, n: int, aug: Optional[VideoAug]) -> torch.Tensor:
+        """the chunk's patch matrix (n patches, C P P) bf16, in the leading part of ``h``"""
+        c, K, NP = self.config, self.patch_dim, self.num_patches
         patches = ws["h"][:n * NP * K].view(n * NP, K)
-        off = self.chunk * NP * K
-        pe = ws["h"][off:off + n * NP * d].view(n * NP, d)
         if pixels.dtype == torch.uint8:
             lib.video_prepare(pixels, patches, c.image_size, c.image_size, c.patch_size, aug.bgr, aug.live, aug.brightness, aug.flip)
         else:
             lib.vit_patchify(pixels, patches, n, c.num_channels, c.image_size, c.image_size, c.patch_size)
+        return patches
+
+    def _embed(self, ws, pixels: torch.Tensor, n: int, aug: Optional[VideoAug]) -> None:
+        T, d, K, NP = self.T, self.config.hidden_size, self.patch_dim, self.num_patches
+        patches = self._patches(ws, pixels, n, aug)
+        off = self.chunk * NP * K
+        pe = ws["h"][off:off + n * NP * d].view(n * NP, d)
         ops.gemm(GEMM_NT, patches, self._w("patch_weight").view(d, K), pe, bias=self._f("patch_bias"), epilogue=EPI_BIAS)
         lib.vit_embed_tokens(pe, self._f("cls_token"), self._f("position_embeddings"), ws["x"], n, T, d)
 
-    def _run(self, pixel_values: torch.Tensor, cls_only: bool, aug: Optional[VideoAug] = None) -> torch.Tensor:
+
+    def _checked(self, pixel_values: torch.Tensor, aug: Optional[VideoAug]):
+        """-> (the contiguous input, its ``aug``: a ``VideoAug`` for uint8 frames, None for f32 pixels)"""
         c = self.config
         frames = isinstance(pixel_values, torch.Tensor) and pixel_values.dtype == torch.uint8
         if frames:
@@ -183,21 +295,38 @@ class NativeViT(FrozenBackbone):
         if not frames and (pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (c.num_channels, c.image_size, c.image_size)):
             raise ValueError(f"NativeViT: pixel_values {tuple(pixel_values.shape)} is not (N, {c.num_channels}, {c.image_size}, "
                              f"{c.image_size}) (position embeddings are not interpolated)")
-        pixel_values = pixel_values.contiguous()
+        return pixel_values.contiguous(), aug
+
+    def _run(self, pixel_values: torch.Tensor, cls_only: bool, aug: Optional[VideoAug] = None) -> torch.Tensor:
+        pixels, aug = self._checked(pixel_values, aug)
+        if torch.is_grad_enabled() and self._trainable > 0:
+            return _Differentiable.apply(self, pixels.detach(), cls_only, aug, *(getattr(self, n) for n in self._trainable_names()))
+        return self._launches(pixels, cls_only, aug)
+
+    def _launches(self, pixels: torch.Tensor, cls_only: bool, aug: Optional[VideoAug], keep: Optional[torch.Tensor] = None,
+                  first: int = 0, final: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the launch list on checked inputs -> (N, d) / (N, T, d) f32.  The differentiable call's: ``keep`` (layers - first, N T, d)
+        bf16 also takes a copy of the input of every layer from ``first`` up, ``final`` one of the final LayerNorm's input"""
+        c = self.config
         _arena.ensure(self)
-        N, T, d = pixel_values.shape[0], self.T, c.hidden_size
-        ws = self._workspace(pixel_values.device)
-        out = torch.empty((N, d) if cls_only else (N, T, d), dtype=torch.float32, device=pixel_values.device)
+        N, T, d = pixels.shape[0], self.T, c.hidden_size
+        ws = self._workspace(pixels.device)
+        out = torch.empty((N, d) if cls_only else (N, T, d), dtype=torch.float32, device=pixels.device)
         L = c.num_hidden_layers
         for n0 in range(0, N, self.chunk):
             n = min(self.chunk, N - n0)
-            self._embed(ws, pixel_values[n0:n0 + n], n, aug.rows(n0, n0 + n) if frames else None)
-            for i in range(L - 1 if cls_only else L):
-                self._layer(i, ws, n)
-            if cls_only:
-                self._layer_cls(L - 1, ws, n)
-            rows = n if cls_only else n * T
+            self._embed(ws, pixels[n0:n0 + n], n, aug.rows(n0, n0 + n) if aug is not None else None)
+            for i in range(L):
+                if keep is not None and i >= first:
+                    keep[i - first, n0 * T:(n0 + n) * T].copy_(self._rows(ws, "x", n * T, d))
+                if cls_only and i == L - 1:
+                    self._layer_cls(i, ws, n)
+                else:
+                    self._layer(i, ws, n)
+            rows, r0 = (n, n0) if cls_only else (n * T, n0 * T)
             x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
+            if final is not None:
+                final[r0:r0 + rows].copy_(x)
             self._ln(ws, x, ln, "ln_w", "ln_b")
             self._widen(ln, out[n0:n0 + n])
         return out
@@ -207,3 +336,153 @@ class NativeViT(FrozenBackbone):
 
     def cls_features(self, pixel_values: torch.Tensor, aug: Optional[VideoAug] = None) -> torch.Tensor:
         return self._run(pixel_values, cls_only=True, aug=aug)
+
+    # -- the backward: the trainable layers' weight gradients ------------------------------------------------------------
+    def _grad_table(self) -> WsTable:
+        """what the backward holds beside the forward workspace, per image: the second LayerNorm's output (``ln`` keeps the first's:
+        the Q/K/V weight gradient reads it), the GELU output (``h`` keeps the raw fc1 output), both LayerNorms' statistics, the
+        attention backward's delta, and the gradient buffers (``ga`` / ``gb`` alternate as the d-wide gradients, ``dh`` is dg then
+        dh).  lse is the forward workspace's"""
+        c, T = self.config, self.T
+        d, H, I, f32 = c.hidden_size, c.num_attention_heads, c.intermediate_size, torch.float32
+        return [("ln2", T * d, BF16), ("g", T * I, BF16), ("ga", T * d, BF16), ("gb", T * d, BF16), ("dh", T * I, BF16),
+                ("dqkv", T * 3 * d, BF16), ("mean1", T, f32), ("rstd1", T, f32), ("mean2", T, f32), ("rstd2", T, f32), ("delta", H * T, f32)]
+
+    def grad_workspace_bytes_per_image(self) -> int:
+        return self._bytes_per_item(self._grad_table())
+
+    def _grad_workspace(self, dev) -> dict:
+        g = self._gws
+        if g is not None and g["dev"] == dev and g["chunk"] == self.chunk:
+            return g
+        d = self.config.hidden_size
+        # beside the table: the LayerNorm backward's scratch, and where the key bias's column sum goes (it is not kept)
+        g = {"dev": dev, "chunk": self.chunk, "dgb": torch.empty(2 * d, dtype=torch.float32, device=dev),
+             "ln_ws": torch.empty(lib.load().mmf_layernorm_bwd_workspace_bytes(d) // 4, dtype=torch.float32, device=dev),
+             "junk": torch.empty(d, dtype=torch.float32, device=dev)}
+        for name, numel, dtype in self._grad_table():
+            g[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
+        self._gws = g
+        return g
+
+    @staticmethod
+    def _slabs_for(rows: int, tiles: int) -> int:
+        """The K-slab count of a weight-gradient launch of ``tiles`` 256 x 256 output tiles over ``rows`` rows (the host rule,
+        DESIGN.md section 8): as many slabs as fill one round of the CUs with tiles, each at least 1024 rows long; 1 (the plain
+        launch) where that would not reach half the CUs, below which the TN launch is the small-tile kernel's either way"""
+        cus = lib.load().mmf_device_cu_count()
+        cus = cus if cus > 0 else 256
+        S = min(cus // tiles, rows // 1024, lib.SUM_SLABS_MAX)
+        return S if S > 1 and S * tiles >= (cus + 1) // 2 else 1
+
+    @staticmethod
+    def _tiles(M: int, N: int) -> int:
+        """the 256 x 256 output tiles of an (M, N) weight gradient (what ``auto_impl`` of csrc/gemm.hip counts)"""
+        return ((M + 255) // 256) * ((N + 255) // 256)
+
+    def _attn_bwd(self, ws, g, qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor, n: int, Tq: int) -> None:
+        """``_attn``'s backward: dQ | dK | dV into the fused ``dqkv`` rows, laid out as ``qkv``.  ``Tq == 1`` (``mmf_vit_cls_attn_bwd``):
+        the query and ``datt`` rows are one per image, dQ lands in the leading columns of each image's row 0 and the dQ columns
+        of the other rows are not written"""
+        c, d, T = self.config, self.config.hidden_size, self.T
+        if Tq == 1:
+            lib.vit_cls_attn_bwd(qkv, datt, dqkv, n, c.num_attention_heads, T, self.head_dim, self.head_dim ** -0.5)
+            return
+        q, dq = qkv.data_ptr(), dqkv.data_ptr()
+        lib.attn_bwd_grouped([lib.AttnProblem(q, q + 2 * d, q + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), datt.data_ptr(),
+                                              g["delta"].data_ptr(), dq, dq + 2 * d, dq + 4 * d, n, c.num_attention_heads, Tq, T,
+                                              3 * d if Tq == T else T * 3 * d, 3 * d, 3 * d, d)], self.head_dim, self.head_dim ** -0.5)
+
+    def _qkv_wgrad(self, i: int, g, dqkv: torch.Tensor, ln: torch.Tensor, n: int, cls: bool) -> None:
+        """layer ``i``'s fused Q/K/V weight and bias gradients from ``dqkv`` and the first LayerNorm's output ``ln``.  The key bias
+        takes no column sum: its exact gradient is zero (a shift of every key by one vector moves every score of a row equally),
+        what a column sum would add is the bf16 residue of delta and dK; the GEMM's column sum of that part goes to ``junk``.
+        ``cls``: dQ is row 0 of each image only, so the Q rows of the weight are a launch of their own over those ``n`` rows"""
+        d = self.config.hidden_size
+        w, b = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad
+        over = self._first_touch(w)
+        part = lambda r, dy, x: (dy[:, r * d:(r + 1) * d], x, w[r * d:(r + 1) * d], g["junk"] if r == 1 else b[r * d:(r + 1) * d])
+        if cls:
+            self._wgrad_launch([(self._row0(dqkv, n), self._row0(ln, n), w[:d], b[:d])], over)
+        roles = (1, 2) if cls else (0, 1, 2)
+        self._wgrad_launch([part(r, dqkv, ln) for r in roles], over, self._slabs_for(ln.shape[0], len(roles) * self._tiles(d, d)))
+
+    def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, cls: bool) -> None:
+        """layer ``i`` again from its saved input ``xin`` up to the GELU output, then its backward with the weight, bias and
+        LayerNorm gradients added into the parameters' ``.grad``.  ``ga`` holds the gradient of the layer's output on entry and
+        of ``xin`` (n T rows) on return.  ``cls``: the layer in ``_layer_cls``'s form; on entry ``ga`` then is n rows, one per image"""
+        c, T = self.config, self.T
+        d, I, R, rows = c.hidden_size, c.intermediate_size, self._rows, n * T
+        m = n if cls else rows                                        # the rows behind the attention
+        ln1, qkv, dqkv = R(ws, "ln", rows, d), R(ws, "qkv", rows, 3 * d), R(g, "dqkv", rows, 3 * d)
+        att, h, ln2, gel, ga, gb, dh = R(ws, "att", m, d), R(ws, "h", m, I), R(g, "ln2", m, d), R(g, "g", m, I), R(g, "ga", m, d), R(g, "gb", m, d), R(g, "dh", m, I)
+        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        grads = lambda r: (getattr(self, f"l{i}_{r}_w").grad, getattr(self, f"l{i}_{r}_b").grad)
+        slabs = lambda M, N: self._slabs_for(m, self._tiles(M, N))
+        W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
+        # the forward again, up to the GELU output (nothing behind fc2 is read by a pre-LN layer's backward)
+        if cls:
+            y = self._cls_attention(i, ws, st1, xin, n)
+        else:
+            self._ln(st1, xin, ln1, f"l{i}_ln1_w", f"l{i}_ln1_b")
+            y = self._attention(i, ws, ln1, xin, n, T)
+        self._ln(st2, y, ln2, f"l{i}_ln2_w", f"l{i}_ln2_b")
+        ops.gemm(GEMM_NT, ln2, W("fc1"), h)
+        lib.bias_gelu_to(h, F("fc1"), gel)
+        # the MLP
+        self._wgrad(ga, gel, f"l{i}_fc2", slabs(d, I))
+        ops.gemm(GEMM_NN, ga, W("fc2"), dh)                                            # dg
+        lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
+        self._wgrad(dh, ln2, f"l{i}_fc1", slabs(I, d))
+        ops.gemm(GEMM_NN, dh, W("fc1"), gb)                                            # dln2
+        self._ln_bwd_add(st2, y, gb, ga, ga, f"l{i}_ln2_w", grads("ln2"))               # ga = dy: the MLP branch + the residual
+        # the attention
+        self._wgrad(ga, att, f"l{i}_o", slabs(d, d))
+        ops.gemm(GEMM_NN, ga, W("o"), gb)                                              # datt
+        self._attn_bwd(ws, g, qkv, att, gb, dqkv, n, 1 if cls else T)
+        self._qkv_wgrad(i, g, dqkv, ln1, n, cls)
+        gx, gl = R(g, "ga", rows, d), R(g, "gb", rows, d)
+        if not cls:
+            ops.gemm(GEMM_NN, dqkv, W("qkv"), gl)                                      # dln1
+            self._ln_bwd_add(st1, xin, gl, gx, gx, f"l{i}_ln1_w", grads("ln1"))        # ga = dx: the attention branch + the residual
+            return
+        # dln1 = the K | V input gradient of every row + the Q one on row 0 of each image: the latter goes into a zeroed buffer
+        # (``g``: the GELU output is done with) that the former's epilogue adds; the residual gradient reaches row 0 only, so it
+        # is a zeroed buffer too (``ln2``) with ``ga``'s n rows copied in
+        z, resid = R(g, "g", rows, d), R(g, "ln2", rows, d)
+        z.zero_()
+        ops.gemm(GEMM_NN, self._row0(dqkv, n), W("qkv")[:d], self._row0(z, n))
+        ops.gemm(GEMM_NN, dqkv[:, d:], W("qkv")[d:], gl, aux=z, epilogue=EPI_ADD_AUX)
+        resid.zero_()
+        self._row0(resid, n).copy_(ga)
+        self._ln_bwd_add(st1, xin, gl, resid, gx, f"l{i}_ln1_w", grads("ln1"))
+
+    def _backward(self, pixels: torch.Tensor, cls_only: bool, aug: Optional[VideoAug], keep: torch.Tensor, final: torch.Tensor,
+                  first: int, embeddings: bool, dout: torch.Tensor) -> None:
+        """for the gradient ``dout`` (N, d) / (N, T, d) f32 of the result: the gradients of the final LayerNorm, of layers
+        ``first`` .. L - 1 and, with ``embeddings``, of the CLS token, the position embeddings and the patch projection, added
+        into their ``.grad``.  ``keep``: the saved inputs of the layers from ``first`` up, ``final``: of the final LayerNorm"""
+        c, d, dev = self.config, self.config.hidden_size, pixels.device
+        if ops.fp32_mode():
+            raise RuntimeError("NativeViT runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        N, T, L, NP, K = pixels.shape[0], self.T, c.num_hidden_layers, self.num_patches, self.patch_dim
+        ws, g = self._workspace(dev), self._grad_workspace(dev)
+        st = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        dout = dout.view(N, -1)
+        for n0 in range(0, N, self.chunk):
+            n = min(self.chunk, N - n0)
+            rows, r0 = (n, n0) if cls_only else (n * T, n0 * T)
+            ga, gb, xf = self._rows(g, "ga", rows, d), self._rows(g, "gb", rows, d), final[r0:r0 + rows]
+            self._narrow(dout[n0:n0 + n], gb)
+            self._ln(st, xf, self._rows(ws, "ln", rows, d), "ln_w", "ln_b")            # for its statistics; the output is not read
+            self._ln_bwd(st, xf, gb, ga, "ln_w", (self.ln_w.grad, self.ln_b.grad))
+            for i in reversed(range(first, L)):
+                self._layer_grad(i, ws, g, keep[i - first, n0 * T:(n0 + n) * T], n, cls_only and i == L - 1)
+            if embeddings:
+                dtok, dpe = self._rows(g, "ga", n * T, d), self._rows(g, "gb", n * NP, d)
+                lib.vit_embed_tokens_bwd(dtok, self.cls_token.grad, self.position_embeddings.grad, dpe, n, T, d)
+                patches = self._patches(ws, pixels[n0:n0 + n], n, aug.rows(n0, n0 + n) if aug is not None else None)
+                wg = self.patch_weight.grad
+                self._wgrad_launch([(dpe, patches, wg.view(d, K), self.patch_bias.grad)], self._first_touch(wg),
+                                   self._slabs_for(n * NP, self._tiles(d, K)))

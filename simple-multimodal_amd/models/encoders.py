@@ -7,13 +7,16 @@ pool -> optional ``AdapterLayer`` -> ``projection`` Linear(hidden -> fusion_hidd
 self-attention heads run on the HIP kernels (``mmfusion.ops``).
 
 The HuggingFace backbones themselves (DeBERTa-v3 / Wav2Vec2 / ViT, reference :20,116,179) are third-party pretrained
-models fetched by name.  All three have native, frozen forms on the HIP kernels that need no network (below): forward only,
-but for the text backbone's gradient with respect to its input embeddings, which is what prompt tuning needs.  The encoders
-take a ``backbone`` argument:
+models fetched by name.  All three have native forms on the HIP kernels that need no network (below), frozen by default.  The
+text backbone has the gradient with respect to its input embeddings, which is what prompt tuning needs; the text and the video
+backbone can train their top layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trainable_layers``); the
+audio one is forward only.  The encoders take a ``backbone`` argument:
   * ``backbone=None`` (default) reproduces the reference: ``from_pretrained(config.*_model_name)``;
   * any ``nn.Module`` returning an object with ``.last_hidden_state`` is used as is;
   * ``config.video_backbone = "native"`` (dynamic attribute, ``VideoEncoder`` only) builds ``mmfusion.vit.NativeViT``: the
-    frozen, forward-only ViT on the HIP kernels, which takes HuggingFace ``state_dict``s and needs no network;
+    ViT on the HIP kernels, which takes HuggingFace ``state_dict``s and needs no network.  Frozen unless
+    ``config.video_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers and the final
+    LayerNorm then train, as the reference's optimiser trains ``video_encoder.vit``; ``"all"``: every layer and the embeddings;
   * ``config.audio_backbone = "native"`` (dynamic attribute, ``AudioEncoder`` only) builds ``mmfusion.wav2vec2.NativeWav2Vec2``
     the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers);
   * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
@@ -92,8 +95,8 @@ def _backbone(config, kind: str, given: Optional[nn.Module]):
 
 def _run_backbone(fn, native: bool, *args, input_grad: bool = False, **kw):
     """``fn(*args, **kw)``, under ``no_grad`` iff the backbone is the native one: that one is frozen.  ``input_grad``: the caller
-    wants a gradient through it (``NativeDeberta`` with ``inputs_embeds``: the prompt route; or with trainable top layers),
-    so a native backbone is called in the caller's grad mode too"""
+    wants a gradient through it (``NativeDeberta`` with ``inputs_embeds``: the prompt route; or it or ``NativeViT`` with trainable
+    top layers), so a native backbone is called in the caller's grad mode too"""
     with torch.no_grad() if native and not input_grad else contextlib.nullcontext():
         return fn(*args, **kw)
 
@@ -225,6 +228,12 @@ class VideoEncoder(_FusionBase):
         # the frozen route that runs the last layer for the CLS rows only.  Deliberately also for a NativeViT handed in as
         # ``backbone=`` (it always was): the one case where a given backbone is treated like the native one
         self._cls_route = native or isinstance(self.vit, NativeViT)
+        if native:            # fine-tune the native backbone (NativeViT.set_trainable_layers): the top k layers, "all": every layer
+            k = getattr(config, "video_backbone_trainable_layers", 0)          # and the embeddings; 0: frozen
+            if k == "all":
+                self.vit.set_trainable_layers(self.vit.config.num_hidden_layers, embeddings=True)
+            else:
+                self.vit.set_trainable_layers(k)
         self.temporal_lstm = nn.LSTM(self.hidden_size, self.hidden_size // 2, num_layers=2, batch_first=True,
                                      bidirectional=True, dropout=config.fusion_dropout)
         self.facial_attention = _MHAParams(self.hidden_size, 8)
@@ -239,7 +248,7 @@ class VideoEncoder(_FusionBase):
             B, n, hs, wsrc, c = video_frames.shape
             flat, aug = video_frames.reshape(-1, hs, wsrc, c), video_aug if video_aug is not None else prep.VideoAug()
             if self._cls_route:                      # straight into the ViT's patch matrix
-                cls = _run_backbone(self.vit.cls_features, True, flat, aug=aug)
+                cls = _run_backbone(self.vit.cls_features, True, flat, aug=aug, input_grad=self.vit.trainable_layers > 0)
             else:
                 pixels = prep.prepare_video(flat, self.config.video_frame_size, bgr=aug.bgr, live=aug.live,
                                             brightness=aug.brightness, flip=aug.flip)
@@ -250,7 +259,7 @@ class VideoEncoder(_FusionBase):
                 raise ValueError("VideoEncoder: video_aug goes with uint8 (B, frames, Hs, Ws, 3) frames")
             B, n, c, h, w = video_frames.shape
             if self._cls_route:
-                cls = _run_backbone(self.vit.cls_features, True, video_frames.reshape(-1, c, h, w))
+                cls = _run_backbone(self.vit.cls_features, True, video_frames.reshape(-1, c, h, w), input_grad=self.vit.trainable_layers > 0)
             else:
                 cls = self.vit(pixel_values=video_frames.view(-1, c, h, w)).last_hidden_state[:, 0]
             frame_features = cls.view(B, n, -1)
