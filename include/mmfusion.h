@@ -359,6 +359,13 @@ int mmf_attn_fwd_grouped(const mmf_attn_problem* problems, int num_problems, int
                          float scale, void* stream);
 int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_problems, int head_dim,
                          float scale, void* stream);
+/* The backward's delta by its definition, delta[b][h][i] = sum_j p_ij (dO_i . v_j) with p_ij = exp(scale q_i . k_j - LSE_i), in f32
+ * from the bf16 Q / K / V / dO and the forward's LSE (O is not read; dQ / dK / dV may be NULL), and mmf_attn_bwd_grouped with that
+ * delta as an INPUT.  mmf_attn_bwd_grouped forms delta = dO . O from the bf16 O, so a row of dS sums to dO . (O - bf16(O)) instead of
+ * zero; where dQ / dK are much smaller than |dO| |O| suggests (tokens that have grown alike) that residue is all they hold.  The
+ * pair costs one more pass over the keys on the vector units.  No dropout form; mmf_attn_bwd_grouped's validation and codes. */
+int mmf_attn_delta_f32(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream);
+int mmf_attn_bwd_grouped_delta(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream);
 /* With attention-probability dropout (nn.MultiheadAttention(dropout=p) in training mode): the
  * probabilities are dropped/rescaled before P.V, the softmax normaliser uses the undropped row sums;
  * the backward kernels regenerate the same mask from (*rng_state, site, problem, b, h, q, key): stream id
@@ -699,7 +706,7 @@ int mmf_bias_gelu_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float*
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Frozen Wav2Vec2 backbone (mmfusion/wav2vec2.py; the reference runs HuggingFace's Wav2Vec2Model at models/encoders.py:116,144).
+ * Wav2Vec2 backbone (mmfusion/wav2vec2.py; the reference runs HuggingFace's Wav2Vec2Model at models/encoders.py:116,144).
  * Activations are channel-last (time, channels) bf16.  The inner feature-extractor convolutions, the projection and the
  * transformer layers are the grouped kernels above; these are the pieces a Wav2Vec2 has beside them.  Every function
  * validates first and launches nothing on an error.
@@ -727,6 +734,32 @@ int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, int T_in, int
  * (127 cg + Kp) * 2 <= 65536 bytes of LDS, N and groups <= 65535, y must not be x. */
 int mmf_w2v_posconv(const void* x_bf16, const void* w_bf16, const float* bias, void* y_bf16, int N, int T, int C, int groups, int k,
                     void* stream);
+/* The backward of mmf_w2v_posconv (fine-tuning the front end, mmfusion/wav2vec2.py).  Shapes, the packed weight and the limits are
+ * the forward's; the refusals too (MMF_E_SHAPE for a null operand or a size out of range, MMF_E_UNSUPPORTED for a group width, a
+ * count or an LDS need beyond the kernel's forms, MMF_E_ALIGN for a pointer that is not 16-byte aligned), and nothing is launched.
+ *
+ * bwd_act: dz = dy * gelu'(conv(x) + bias), bf16, one rounding.  The pre-activation is computed again by the forward's MFMA loop,
+ * not read from memory.  dz must not be x; it may be dy. */
+int mmf_w2v_posconv_bwd_act(const void* x_bf16, const void* w_bf16, const float* bias, const void* dy_bf16, void* dz_bf16, int N, int T,
+                            int C, int groups, int k, void* stream);
+/* dgrad: dx = dy + conv^T(dz): dx[t][g*cg + ci] = dy[t][g*cg + ci] + sum_{j, co} wt[g][ci][j*cg + co] * dz[t + j - (k - 1 - k/2)][g*cg + co],
+ * the residual's gradient included.  wt_bf16 (groups, cg, Kp): the forward's weight with the taps reversed and co / ci swapped,
+ * wt[g][ci][j*cg + co] = the convolution weight [g*cg + co][ci][k - 1 - j].  The forward's kernel body with k - 1 - k/2 rows of
+ * padding in front (k/2 for an odd k).  dx must not be dz; it may be dy. */
+int mmf_w2v_posconv_dgrad(const void* dz_bf16, const void* wt_bf16, const void* dy_bf16, void* dx_bf16, int N, int T, int C, int groups,
+                          int k, void* stream);
+/* wgrad: dw[g*cg + co][j*cg + ci] (+)= sum over clips n and frames t of dz[n][t][g*cg + co] * x[n][t + j - k/2][g*cg + ci], rows
+ * outside [0, T) read as zero: f32 in the forward's packed (C, Kp) layout, the padding columns written as zeros.  An MFMA GEMM per
+ * (group, 8 taps) whose contraction runs over time; no atomics, the same bits on every run.  slabs == 1: dw (C, Kp) is written
+ * (accumulate == 0) or added to.  slabs > 1 (accumulate must be 0): the N * ceil(T / 128) (clip, time block) units are cut into
+ * `slabs` runs and dw is (slabs, C, Kp), one partial per run, for mmf_sum_slabs_f32.  slabs <= min(units, MMF_SUM_SLABS_MAX). */
+int mmf_w2v_posconv_wgrad(const void* dz_bf16, const void* x_bf16, float* dw, int N, int T, int C, int groups, int k, int slabs,
+                          int accumulate, void* stream);
+/* The weight norm's backward (weight_norm(dim = 2): w_eff[c][ci][j] = g[j] v[c][ci][j] / ||v[:, :, j]||): from dw (C, Kp) f32, the
+ * packed gradient of w_eff, dg[j] += sum dw u and dv (=, with overwrite_v, or +=) (g[j] / ||v_j||) (dw - u dg_j), u = v / ||v_j||.
+ * g / dg f32 [k], v / dv f32 (C, cg, k).  One workgroup per tap, f32, fixed reduction order.  C % cg == 0, C cg k < 2^31. */
+int mmf_w2v_weightnorm_bwd(const float* dw, const float* g, const float* v, float* dg, float* dv, int C, int cg, int k, int overwrite_v,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frozen DeBERTa-v3 backbone (mmfusion/deberta.py; the reference runs HuggingFace's DebertaV2Model at models/encoders.py:20).

@@ -45,7 +45,73 @@ int validate_dropout(const char* who, const mmf_attn_problem* p, int n, float dr
 int mmf_attn_fwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
                          const uint64_t* rng_state, uint32_t site, hipStream_t s);
 int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
-                         const uint64_t* rng_state, uint32_t site, hipStream_t s);
+                         const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta = false);
+
+namespace {
+
+// delta[b][h][i] = sum_j p_ij dp_ij in f32, p_ij = exp(scale q_i . k_j - LSE_i) and dp_ij = dO_i . v_j from the bf16 operands: the
+// softmax backward's row term as the definition has it.  (The backward kernels' own delta = dO . O reads the bf16 O, so a row of
+// dS sums to dO . (O - bf16(O)) instead of zero: an absolute residue that gradients much smaller than |dO| |O| do not cover.)
+// One thread per query row with q and dO in registers; the keys and values of 32 rows at a time in LDS, read as broadcasts.
+constexpr int DELTA_THREADS = 256, DELTA_KEYS = 32;
+template <int DH>
+__global__ __launch_bounds__(DELTA_THREADS)
+void attn_delta_kernel(const mmf_attn_problem P, float scale) {
+  __shared__ __attribute__((aligned(16))) unsigned short sk[DELTA_KEYS * DH], sv[DELTA_KEYS * DH];
+  const int h = blockIdx.y, b = blockIdx.z, i = blockIdx.x * DELTA_THREADS + threadIdx.x;
+  const int Tq = P.Tq, Tk = P.Tk;
+  const bool live = i < Tq;
+  const unsigned short* Q = static_cast<const unsigned short*>(P.Q) + ((size_t)b * Tq + (live ? i : 0)) * P.ldq + h * DH;
+  const unsigned short* dO = static_cast<const unsigned short*>(P.dO) + ((size_t)b * Tq + (live ? i : 0)) * P.ldo + h * DH;
+  const unsigned short* K = static_cast<const unsigned short*>(P.K) + (size_t)b * Tk * P.ldk + h * DH;
+  const unsigned short* V = static_cast<const unsigned short*>(P.V) + (size_t)b * Tk * P.ldv + h * DH;
+  float q[DH], g[DH];
+#pragma unroll
+  for (int c = 0; c < DH / 8; ++c) {
+    float t[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(Q + c * 8), t);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[c * 8 + e] = t[e] * scale;
+    unpack8(*reinterpret_cast<const u32x4_t*>(dO + c * 8), t);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[c * 8 + e] = t[e];
+  }
+  const size_t at = ((size_t)b * P.H + h) * Tq + (live ? i : 0);
+  const float lse = P.LSE[at];
+  float acc = 0.f;
+  for (int j0 = 0; j0 < Tk; j0 += DELTA_KEYS) {
+    __syncthreads();
+    for (int v = threadIdx.x; v < DELTA_KEYS * DH / 8; v += DELTA_THREADS) {
+      const int r = v / (DH / 8), c = v - r * (DH / 8);
+      u32x4_t kk = {0u, 0u, 0u, 0u}, vv = kk;
+      if (j0 + r < Tk) {
+        kk = *reinterpret_cast<const u32x4_t*>(K + (size_t)(j0 + r) * P.ldk + c * 8);
+        vv = *reinterpret_cast<const u32x4_t*>(V + (size_t)(j0 + r) * P.ldv + c * 8);
+      }
+      *reinterpret_cast<u32x4_t*>(sk + v * 8) = kk;
+      *reinterpret_cast<u32x4_t*>(sv + v * 8) = vv;
+    }
+    __syncthreads();
+    const int nk = Tk - j0 < DELTA_KEYS ? Tk - j0 : DELTA_KEYS;
+    for (int r = 0; r < nk; ++r) {
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int c = 0; c < DH / 8; ++c) {
+        float t[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(sk + r * DH + c * 8), t);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s = fmaf(q[c * 8 + e], t[e], s);
+        unpack8(*reinterpret_cast<const u32x4_t*>(sv + r * DH + c * 8), t);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dp = fmaf(g[c * 8 + e], t[e], dp);
+      }
+      acc = fmaf(expf(s - lse), dp, acc);
+    }
+  }
+  if (live) P.delta[at] = acc;
+}
+
+}  // namespace
 
 // Tuning hook kept for ABI stability: one kernel generation is left, so only 0 (automatic) and 2 are accepted.
 extern "C" int mmf_attn_select_impl(int impl) {
@@ -80,4 +146,28 @@ extern "C" int mmf_attn_fwd_grouped(const mmf_attn_problem* problems, int num_pr
 extern "C" int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_problems, int head_dim,
                                     float scale, void* stream) {
   return mmf_attn_bwd_grouped_ex(problems, num_problems, head_dim, scale, 0.f, nullptr, 0u, stream);
+}
+
+// mmf_attn_bwd_grouped with delta as an INPUT (f32 [B*H*Tq] per problem, e.g. mmf_attn_delta_f32's): the dQ kernel reads it
+// instead of forming dO . O, the dK/dV kernel reads it as it always does.  No dropout form.
+extern "C" int mmf_attn_bwd_grouped_delta(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream) {
+  if (int rc = validate("mmf_attn_bwd_grouped_delta", problems, num_problems, head_dim, true)) return rc;
+  return mmf_attn_bwd2_launch(problems, num_problems, head_dim, scale, 0.f, nullptr, 0u, static_cast<hipStream_t>(stream), true);
+}
+
+extern "C" int mmf_attn_delta_f32(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream) {
+  if (int rc = validate("mmf_attn_delta_f32", problems, num_problems, head_dim, false)) return rc;
+  for (int i = 0; i < num_problems; ++i) {
+    if (!problems[i].dO || !problems[i].delta) MMF_FAIL(MMF_E_SHAPE, "mmf_attn_delta_f32[%d]: null gradient operand", i);
+    if (!mmf_aligned16(problems[i].dO)) MMF_FAIL(MMF_E_ALIGN, "mmf_attn_delta_f32[%d]: gradient pointers must be 16-byte aligned", i);
+    if (problems[i].H > 65535 || problems[i].B > 65535) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_attn_delta_f32[%d]: B and H at most 65535", i);
+  }
+  for (int i = 0; i < num_problems; ++i) {
+    const mmf_attn_problem& p = problems[i];
+    const dim3 grid((p.Tq + DELTA_THREADS - 1) / DELTA_THREADS, p.H, p.B);
+    if (head_dim == 96) hipLaunchKernelGGL(attn_delta_kernel<96>, grid, dim3(DELTA_THREADS), 0, static_cast<hipStream_t>(stream), p, scale);
+    else                hipLaunchKernelGGL(attn_delta_kernel<64>, grid, dim3(DELTA_THREADS), 0, static_cast<hipStream_t>(stream), p, scale);
+    MMF_CHECK_LAUNCH("mmf_attn_delta_f32");
+  }
+  return MMF_OK;
 }

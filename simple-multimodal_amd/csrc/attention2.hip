@@ -197,7 +197,8 @@ void attn_fwd2n_kernel(const AttnArgs2 a) {
 // too — waves 0 and 1 sharing the 32 query rows of a x30 problem — and taken out again: at this kernel's 168-register budget
 // (three waves per SIMD) a third instantiation of the body spilled 31 registers instead of 6, a runtime selector 66, and the
 // spills land in the main path's loop.)
-template <int DH, bool DROP, bool ACTIVE>
+// GIVEN: delta is an input (mmf_attn_bwd_grouped_delta: the caller computed it in f32, mmf_attn_delta_f32); O is not read.
+template <int DH, bool DROP, bool ACTIVE, bool GIVEN = false>
 __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_problem& P, const int pidx, const int bh,
                                          const int qs, char* smem) {
   constexpr int KS = DH / 16, DT = DH / 32, TILE_B = img_tile_bytes<DH>(), STAGE_B = 2 * TILE_B;
@@ -225,6 +226,14 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
     auto rsrc = [&](const void* base, size_t off, int ld) {
       return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(base) + off), 0, Tq * ld * 2, 0x00020000);
     };
+    if constexpr (GIVEN) {
+      RowLoad<DH> rq, rdo;
+      rq.issue(rsrc(P.Q, qoff, P.ldq), P.ldq, qs, lane);
+      rdo.issue(rsrc(P.dO, ooff, P.ldo), P.ldo, qs, lane);
+      rq.commit(qf, lane, slice);
+      rdo.commit(dof, lane, slice);
+      delta = qrow < Tq ? P.delta[(size_t)bh * Tq + qrow] : 0.f;
+    } else {
     RowLoad<DH> rq, rdo, ro;                                  // 3 x 6 loads in flight, one wait (RowLoad, attn_helpers.h)
     rq.issue(rsrc(P.Q, qoff, P.ldq), P.ldq, qs, lane);
     rdo.issue(rsrc(P.dO, ooff, P.ldo), P.ldo, qs, lane);
@@ -241,6 +250,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
     }
     delta = half_sum(delta);
     if (half == 0 && qrow < Tq) P.delta[(size_t)bh * Tq + qrow] = delta;
+    }
     lse2 = (qrow < Tq ? P.LSE[(size_t)bh * Tq + qrow] : 0.f) * LOG2E;
   }
   const float c = a.scale * LOG2E;
@@ -310,7 +320,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
   }
 }
 
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool GIVEN = false>
 __global__ __launch_bounds__(NT, DQ_WAVES_PER_SIMD)
 void attn_bwd_dq2_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
@@ -322,8 +332,8 @@ void attn_bwd_dq2_kernel(const AttnArgs2 a) {
   const int bh = item / nchunk, q0 = (item % nchunk) * ROWS_PER_WG;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int qs = q0 + 32 * wave, pidx = a.orig[pi];
-  if (qs < P.Tq) dq2_wave<DH, DROP, true>(a, P, pidx, bh, qs, smem);
-  else           dq2_wave<DH, DROP, false>(a, P, pidx, bh, qs, smem);
+  if (qs < P.Tq) dq2_wave<DH, DROP, true, GIVEN>(a, P, pidx, bh, qs, smem);
+  else           dq2_wave<DH, DROP, false, GIVEN>(a, P, pidx, bh, qs, smem);
 }
 
 // Row statistics of the dK/dV kernel through the matrix pipe (round 3).  In S = Q.K^T the key is the lane and the query row
@@ -533,10 +543,15 @@ void launch4(int head_dim, bool dr, K96T k96t, K96F k96f, K64T k64t, K64F k64f, 
 }  // namespace
 
 int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
-                         const uint64_t* rng_state, uint32_t site, hipStream_t s) {
+                         const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta) {
   if (int rc = check_ranges("mmf_attn_bwd_grouped", problems, n)) return rc;
   AttnArgs2 a;
-  if (!(g_attn_stub & 2)) {
+  if (given_delta) {                                                                               // dQ from the caller's delta (no dropout form)
+    const int total = fill_args2(a, problems, n, scale, 0.f, nullptr, 0u, false, false);
+    if (head_dim == 96) hipLaunchKernelGGL((attn_bwd_dq2_kernel<96, false, true>), dim3(total), dim3(NT), 0, s, a);
+    else                hipLaunchKernelGGL((attn_bwd_dq2_kernel<64, false, true>), dim3(total), dim3(NT), 0, s, a);
+    MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_delta(dq, v2)");
+  } else if (!(g_attn_stub & 2)) {
     const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false);   // dQ (+ delta) first
     launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dq2_kernel<96, true>, attn_bwd_dq2_kernel<96, false>, attn_bwd_dq2_kernel<64, true>,
             attn_bwd_dq2_kernel<64, false>, total, a, s);

@@ -60,6 +60,11 @@ __device__ __forceinline__ u32x4_t pack8(const f32x4_t a, const f32x4_t b) {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }   // exact GELU
+// gelu'(v) = Phi(v) + v phi(v).  Phi through erfc: 1 + erf(v / sqrt 2) loses every digit of Phi in the left tail (v < -5), where
+// v phi(v) is just as small and the derivative would be f32 noise.
+__device__ __forceinline__ float gelu_erf_grad(float v) {
+  return 0.5f * erfcf(v * -0.70710678118654752440f) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+}
 
 // ---- streaming launches -----------------------------------------------------------------------
 // Grid of a grid-stride streaming kernel over nvec per-lane accesses: one workgroup per `threads` of them, 1 .. 2048

@@ -238,11 +238,7 @@ void bias_gelu_kernel(const unsigned short* x, unsigned short* y, const float* _
   }
 }
 
-// dh <- dg * gelu'(h + bias), gelu'(v) = Phi(v) + v phi(v); dh may be dg.  Phi through erfc: 1 + erf(v / sqrt 2) loses every
-// digit of Phi in the left tail (v < -5), where v phi(v) is just as small and the derivative would be f32 noise.
-__device__ __forceinline__ float gelu_erf_grad(float v) {
-  return 0.5f * erfcf(v * -0.70710678118654752440f) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
-}
+// dh <- dg * gelu'(h + bias) (gelu_erf_grad of mmf_internal.h); dh may be dg.
 template <bool HAS_BIAS>
 __global__ __launch_bounds__(VIT_THREADS)
 void bias_gelu_bwd_kernel(const unsigned short* dg, const unsigned short* __restrict__ h, const float* __restrict__ bias, unsigned short* dh,

@@ -4,7 +4,10 @@
 //   conv0_stats / conv0_norm_gelu   layer 0: Conv1d(1 -> C0, k0, s0) + GroupNorm(one group per channel) + GELU in two passes
 //                                   that both recompute the k0 MACs per output; no f32 intermediate is stored
 //   gelu_window                     GELU + the (T_out, k*C) window form the next conv layer's GEMM reads
-//   posconv                         the grouped positional convolution as one MFMA GEMM per (clip, group, 128 time rows)
+//   posconv                         the grouped positional convolution as one MFMA GEMM per (clip, group, 128 time rows); the same
+//                                   body with two more epilogues is its backward's dz = dy gelu'(z) and input gradient
+//   posconv_wgrad                   its weight gradient: an MFMA GEMM per (group, 8 taps) whose contraction runs over time
+//   weightnorm_bwd                  the effective weight's gradient -> the gradients of the weight norm's g and v
 #include "mmf_internal.h"
 
 namespace {
@@ -156,14 +159,21 @@ void w2v_gelu_window_kernel(const unsigned short* __restrict__ x, unsigned short
 // 16 slots start at 16 different multiples of 4 banks (24 r mod 64 takes 8 values, the two quarters of a group differ by 4):
 // conflict-free.  CG = 32 and 64 (row stride 16 / 32 banks) are 4-way conflicted; no shipped model has them.
 // D[row = co = 4 (lane >> 4) + reg][col = time = lane & 15]: a lane ends with 4 consecutive channels of one time row.
-template <int CT>
+// The backward runs the same body twice more (EPI): with ``aux`` (N, T, C) bf16 the operand its epilogue reads at the output's place,
+//   PC_FWD    y  = aux + gelu(acc + b)        aux = x: the forward
+//   PC_ACT    dz = aux * gelu'(acc + b)       aux = dy: z = b + conv(x) is computed again, not stored
+//   PC_DGRAD  dx = aux + acc                  aux = dy, x = dz, w = the weight with its taps reversed and co / ci swapped, and
+//                                             pad = k - 1 - k/2 rows in front instead of k/2 (they differ for an even k)
+enum { PC_FWD = 0, PC_ACT = 1, PC_DGRAD = 2 };
+template <int CT, int EPI>
 __global__ __launch_bounds__(W2V_THREADS)
 void w2v_posconv_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ wp, const float* __restrict__ bias,
-                        unsigned short* __restrict__ y, int T, int C, int k, int Kp) {
+                        const unsigned short* aux, unsigned short* y, int T, int C, int k, int Kp, int pad) {
   constexpr int CG = CT * 16, TT = 128;
   extern __shared__ __attribute__((aligned(16))) unsigned short sx[];
-  const int t0 = blockIdx.x * TT, g = blockIdx.y, pad = k >> 1;
+  const int t0 = blockIdx.x * TT, g = blockIdx.y;
   const unsigned short* __restrict__ xn = x + (size_t)blockIdx.z * T * C + g * CG;
+  const unsigned short* an = aux + (size_t)blockIdx.z * T * C + g * CG;
   const int nvec = ((TT - 1) * CG + Kp) >> 3, rows = TT + k - 1;
   for (int v = threadIdx.x; v < nvec; v += W2V_THREADS) {
     const int e = v << 3, rr = e / CG, cc = e - rr * CG, t = t0 - pad + rr;
@@ -198,13 +208,161 @@ void w2v_posconv_kernel(const unsigned short* __restrict__ x, const unsigned sho
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const int co = ct * 16 + q * 4;
-      const f32x4_t b = *reinterpret_cast<const f32x4_t*>(bias + g * CG + co);
-      const u32x2_t xr = *reinterpret_cast<const u32x2_t*>(xn + (size_t)t * C + co);
-      const f32x4_t a = acc[tt][ct] + b;
-      const u32x2_t o = {pack_bf16x2(bf16lo(xr[0]) + gelu_erf(a[0]), bf16hi(xr[0]) + gelu_erf(a[1])),
-                         pack_bf16x2(bf16lo(xr[1]) + gelu_erf(a[2]), bf16hi(xr[1]) + gelu_erf(a[3]))};
+      const u32x2_t xr = *reinterpret_cast<const u32x2_t*>(an + (size_t)t * C + co);
+      u32x2_t o;
+      if constexpr (EPI == PC_DGRAD) {
+        const f32x4_t a = acc[tt][ct];
+        o = u32x2_t{pack_bf16x2(bf16lo(xr[0]) + a[0], bf16hi(xr[0]) + a[1]), pack_bf16x2(bf16lo(xr[1]) + a[2], bf16hi(xr[1]) + a[3])};
+      } else {
+        const f32x4_t b = *reinterpret_cast<const f32x4_t*>(bias + g * CG + co);
+        const f32x4_t a = acc[tt][ct] + b;
+        if constexpr (EPI == PC_FWD)
+          o = u32x2_t{pack_bf16x2(bf16lo(xr[0]) + gelu_erf(a[0]), bf16hi(xr[0]) + gelu_erf(a[1])),
+                      pack_bf16x2(bf16lo(xr[1]) + gelu_erf(a[2]), bf16hi(xr[1]) + gelu_erf(a[3]))};
+        else
+          o = u32x2_t{pack_bf16x2(bf16lo(xr[0]) * gelu_erf_grad(a[0]), bf16hi(xr[0]) * gelu_erf_grad(a[1])),
+                      pack_bf16x2(bf16lo(xr[1]) * gelu_erf_grad(a[2]), bf16hi(xr[1]) * gelu_erf_grad(a[3]))};
+      }
       *reinterpret_cast<u32x2_t*>(y + ((size_t)blockIdx.z * T + t) * C + g * CG + co) = o;
     }
+  }
+}
+
+// ---- positional convolution: weight gradient ----------------------------------------------------------------
+// dW[g][co][j*CG + ci] (+)= sum_{n, t} dz[n][t][g*CG + co] * x[n][t + j - pad][g*CG + ci], rows outside [0, T) read as zero: per
+// tap a (CG x CG) GEMM whose contraction runs over time.  One workgroup = (WG_TAPS = 8 taps, group, row slab); wave w owns taps
+// 2w and 2w + 1 with all CT x CT output tiles in accumulators (2 * CT * CT * 4 f32 per lane) and the workgroup walks the slab's
+// (clip, 128-row time block) units: the group's channels of the block's dz rows and of the x rows [t0 + j0 - pad, + 128 + 7) are
+// staged as (rows, CG) images like the forward's, the next unit's rows are fetched into registers while this one is multiplied.
+// Both operands of v_mfma_f32_16x16x32_bf16 have time as their 32-index and are read with ds_read_b64_tr_b16: A[row = co][k = time]
+// from the dz image, B[k = time][col = ci] from the x image, where tap j is a row offset only (every row starts at a multiple of
+// 32 bytes, CG being a multiple of 16).  The MFMA's k index 8 (lane >> 4) + e is time row 4 (lane >> 4) + e for e < 4 and
+// 16 + 4 (lane >> 4) + e - 4 above, in both operands alike: the two 16-lane groups of a 32-lane half then read 8 CONSECUTIVE rows,
+// which at CG = 48 (row stride 24 banks) are 8 different multiples of 8 banks, conflict-free; CG = 16 likewise, CG = 32 is 2-way
+// and CG = 64 4-way conflicted (no shipped model has them).  EXEC is all ones at every transposed read: nothing around them
+// branches on a lane, rows past T and taps past k are zeros / computed and dropped (pad, don't mask).
+// D[row = co = 4 (lane >> 4) + reg][col = ci = lane & 15].  No atomics: with slabs > 1 slab s writes its own (C, Kp) partial.
+constexpr int WG_TT = 128, WG_TAPS = 8;
+
+template <int CT>
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_posconv_wgrad_kernel(const unsigned short* __restrict__ dz, const unsigned short* __restrict__ x, float* __restrict__ dw,
+                              int T, int C, int k, int Kp, int pad, int nblk, int units, int per_slab, int accumulate) {
+  constexpr int CG = CT * 16, XR = WG_TT + WG_TAPS - 1;
+  constexpr int NZ = WG_TT * CG / 8, NX = XR * CG / 8, NV = (NZ + NX + W2V_THREADS - 1) / W2V_THREADS;
+  __shared__ __attribute__((aligned(16))) unsigned short sz[WG_TT * CG];
+  __shared__ __attribute__((aligned(16))) unsigned short sxr[XR * CG];
+  const int j0 = blockIdx.x * WG_TAPS, g = blockIdx.y;
+  const int u0 = blockIdx.z * per_slab, u1 = min(units, u0 + per_slab);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, gq = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  float* __restrict__ out = dw + (size_t)blockIdx.z * C * Kp;                        // slab s writes partial s
+  u32x4_t pre[NV];
+  auto fetch = [&](int u) {
+    const int n = u / nblk, t0 = (u - n * nblk) * WG_TT;
+    const unsigned short* __restrict__ zn = dz + (size_t)n * T * C + g * CG;
+    const unsigned short* __restrict__ xn = x + (size_t)n * T * C + g * CG;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * W2V_THREADS;
+      u32x4_t val = {0u, 0u, 0u, 0u};
+      if (v < NZ) {
+        const int e = v << 3, rr = e / CG, cc = e - rr * CG, t = t0 + rr;
+        if (t < T) val = *reinterpret_cast<const u32x4_t*>(zn + (size_t)t * C + cc);
+      } else if (v < NZ + NX) {
+        const int e = (v - NZ) << 3, rr = e / CG, cc = e - rr * CG, t = t0 + j0 - pad + rr;
+        if (t >= 0 && t < T) val = *reinterpret_cast<const u32x4_t*>(xn + (size_t)t * C + cc);
+      }
+      pre[i] = val;
+    }
+  };
+  f32x4_t acc[2][CT][CT];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < CT; ++b)
+#pragma unroll
+      for (int c = 0; c < CT; ++c) acc[a][b][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  auto tr8 = [](const unsigned short* at) {                            // rows r .. r + 3 and r + 16 .. r + 19 of 16 columns
+    const s16x4_t lo = lds_read_tr16(at), hi = lds_read_tr16(at + 16 * CG);
+    const s16x8_t w = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8_t, w);
+  };
+  if (u0 < u1) fetch(u0);
+  for (int u = u0; u < u1; ++u) {
+    __syncthreads();                                                   // the previous unit's reads are done
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * W2V_THREADS;
+      if (v < NZ) *reinterpret_cast<u32x4_t*>(sz + (v << 3)) = pre[i];
+      else if (v < NZ + NX) *reinterpret_cast<u32x4_t*>(sxr + ((v - NZ) << 3)) = pre[i];
+    }
+    __syncthreads();
+    if (u + 1 < u1) fetch(u + 1);
+#pragma unroll
+    for (int ks = 0; ks < WG_TT / 32; ++ks) {
+      const int row = ks * 32 + 4 * gq + q;
+      bf16x8_t az[CT];
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) az[ct] = tr8(sz + row * CG + ct * 16 + 4 * p);
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int ci = 0; ci < CT; ++ci) {
+          const bf16x8_t b = tr8(sxr + (row + 2 * wave + a) * CG + ci * 16 + 4 * p);
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct) acc[a][ct][ci] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(az[ct], b, acc[a][ct][ci], 0, 0, 0);
+        }
+    }
+  }
+  const int r = lane & 15;
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    const int j = j0 + 2 * wave + a;
+    if (j > k) continue;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+      for (int ci = 0; ci < CT; ++ci)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int col = j * CG + ci * 16 + r;
+          if (col >= Kp) continue;                                     // tap k is the zero padding of the rows, where Kp has any
+          float* dst = out + (size_t)(g * CG + ct * 16 + 4 * gq + e) * Kp + col;
+          const float val = j < k ? acc[a][ct][ci][e] : 0.0f;
+          *dst = accumulate ? *dst + val : val;
+        }
+  }
+}
+
+// ---- weight norm: dW_eff -> dg, dv ------------------------------------------------------------------------------
+// w_eff[c][ci][j] = g[j] u, u = v[c][ci][j] / ||v[:, :, j]||: dg[j] = sum dW u, dv = (g / ||v||) (dW - u dg[j]).  One workgroup per tap j;
+// dw is the packed (C, Kp) gradient (column j*cg + ci), v / dv (C, cg, k) f32.  f32 throughout; a lane sums its elements in index
+// order, the wave sums by xor-shuffles and the four waves' sums are added in wave order: the same bits on every run.
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_weightnorm_bwd_kernel(const float* __restrict__ dw, const float* __restrict__ gain, const float* __restrict__ v,
+                               float* __restrict__ dg, float* __restrict__ dv, int n /* C*cg */, int cg, int k, int Kp, int overwrite_v) {
+  __shared__ float red[2][W2V_THREADS / 64];
+  const int j = blockIdx.x;
+  float svv = 0.0f, sdv = 0.0f;
+  for (int e = threadIdx.x; e < n; e += W2V_THREADS) {
+    const int c = e / cg, ci = e - c * cg;
+    const float vv = v[(size_t)e * k + j], d = dw[(size_t)c * Kp + j * cg + ci];
+    svv = fmaf(vv, vv, svv);
+    sdv = fmaf(d, vv, sdv);
+  }
+  svv = wave_sum(svv);
+  sdv = wave_sum(sdv);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = svv; red[1][threadIdx.x >> 6] = sdv; }
+  __syncthreads();
+  svv = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+  sdv = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+  const float inv = rsqrtf(svv), dgj = sdv * inv, scale = gain[j] * inv;
+  if (threadIdx.x == 0) dg[j] += dgj;
+  for (int e = threadIdx.x; e < n; e += W2V_THREADS) {
+    const int c = e / cg, ci = e - c * cg;
+    const size_t at = (size_t)e * k + j;
+    const float val = scale * (dw[(size_t)c * Kp + j * cg + ci] - v[at] * inv * dgj);
+    dv[at] = overwrite_v ? val : dv[at] + val;
   }
 }
 
@@ -281,30 +439,105 @@ extern "C" int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, in
   return MMF_OK;
 }
 
-extern "C" int mmf_w2v_posconv(const void* x_bf16, const void* w_bf16, const float* bias, void* y_bf16, int N, int T, int C,
-                               int groups, int k, void* stream) {
-  if (!x_bf16 || !w_bf16 || !bias || !y_bf16 || N <= 0 || T <= 0 || C <= 0 || groups <= 0 || k <= 0)
-    MMF_FAIL(MMF_E_SHAPE, "mmf_w2v_posconv: null operand or N=%d T=%d C=%d groups=%d k=%d", N, T, C, groups, k);
-  if (C % groups) MMF_FAIL(MMF_E_SHAPE, "mmf_w2v_posconv: C=%d is not a multiple of groups=%d", C, groups);
+namespace {
+
+// the three entry points of w2v_posconv_kernel: validation (``aux`` is x for the forward) and the launch of the EPI instantiation
+template <int EPI>
+int posconv_run(const char* fn, const void* x_bf16, const void* w_bf16, const float* bias, const void* aux_bf16, void* y_bf16, int N, int T,
+                int C, int groups, int k, int pad, void* stream) {
+  if (!x_bf16 || !w_bf16 || (EPI != PC_DGRAD && !bias) || !aux_bf16 || !y_bf16 || N <= 0 || T <= 0 || C <= 0 || groups <= 0 || k <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand or N=%d T=%d C=%d groups=%d k=%d", fn, N, T, C, groups, k);
+  if (C % groups) MMF_FAIL(MMF_E_SHAPE, "%s: C=%d is not a multiple of groups=%d", fn, C, groups);
   const int cg = C / groups;
   if ((cg & 15) || cg > 64 || N > 65535 || groups > 65535 || x_bf16 == y_bf16)
-    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_w2v_posconv: group width %d (16, 32, 48 or 64), N=%d groups=%d (at most 65535), y must not be x", cg, N, groups);
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: group width %d (16, 32, 48 or 64), N=%d groups=%d (at most 65535), %s", fn, cg, N, groups,
+             EPI == PC_FWD ? "y must not be x" : "the output must not be the convolution's input");
   const int Kp = (k * cg + 31) & ~31;
   const size_t lds = ((size_t)127 * cg + Kp) * 2;
-  if (lds > 65536) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_w2v_posconv: k=%d at group width %d needs %zu bytes of LDS (at most 65536)", k, cg, lds);
-  if (!mmf_aligned16(x_bf16) || !mmf_aligned16(w_bf16) || !mmf_aligned16(bias) || !mmf_aligned16(y_bf16))
-    MMF_FAIL(MMF_E_ALIGN, "mmf_w2v_posconv: pointers must be 16-byte aligned");
+  if (lds > 65536) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: k=%d at group width %d needs %zu bytes of LDS (at most 65536)", fn, k, cg, lds);
+  if (!mmf_aligned16(x_bf16) || !mmf_aligned16(w_bf16) || !mmf_aligned16(bias) || !mmf_aligned16(aux_bf16) || !mmf_aligned16(y_bf16))
+    MMF_FAIL(MMF_E_ALIGN, "%s: pointers must be 16-byte aligned", fn);
   const dim3 grid((T + 127) / 128, groups, N);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned short* x = static_cast<const unsigned short*>(x_bf16);
   const unsigned short* w = static_cast<const unsigned short*>(w_bf16);
+  const unsigned short* aux = static_cast<const unsigned short*>(aux_bf16);
   unsigned short* y = static_cast<unsigned short*>(y_bf16);
   switch (cg / 16) {
-    case 1: hipLaunchKernelGGL(w2v_posconv_kernel<1>, grid, dim3(W2V_THREADS), lds, s, x, w, bias, y, T, C, k, Kp); break;
-    case 2: hipLaunchKernelGGL(w2v_posconv_kernel<2>, grid, dim3(W2V_THREADS), lds, s, x, w, bias, y, T, C, k, Kp); break;
-    case 3: hipLaunchKernelGGL(w2v_posconv_kernel<3>, grid, dim3(W2V_THREADS), lds, s, x, w, bias, y, T, C, k, Kp); break;
-    default: hipLaunchKernelGGL(w2v_posconv_kernel<4>, grid, dim3(W2V_THREADS), lds, s, x, w, bias, y, T, C, k, Kp); break;
+    case 1: hipLaunchKernelGGL((w2v_posconv_kernel<1, EPI>), grid, dim3(W2V_THREADS), lds, s, x, w, bias, aux, y, T, C, k, Kp, pad); break;
+    case 2: hipLaunchKernelGGL((w2v_posconv_kernel<2, EPI>), grid, dim3(W2V_THREADS), lds, s, x, w, bias, aux, y, T, C, k, Kp, pad); break;
+    case 3: hipLaunchKernelGGL((w2v_posconv_kernel<3, EPI>), grid, dim3(W2V_THREADS), lds, s, x, w, bias, aux, y, T, C, k, Kp, pad); break;
+    default: hipLaunchKernelGGL((w2v_posconv_kernel<4, EPI>), grid, dim3(W2V_THREADS), lds, s, x, w, bias, aux, y, T, C, k, Kp, pad); break;
   }
-  MMF_CHECK_LAUNCH("mmf_w2v_posconv");
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+}  // namespace
+
+extern "C" int mmf_w2v_posconv(const void* x_bf16, const void* w_bf16, const float* bias, void* y_bf16, int N, int T, int C,
+                               int groups, int k, void* stream) {
+  return posconv_run<PC_FWD>("mmf_w2v_posconv", x_bf16, w_bf16, bias, x_bf16, y_bf16, N, T, C, groups, k, k >> 1, stream);
+}
+
+extern "C" int mmf_w2v_posconv_bwd_act(const void* x_bf16, const void* w_bf16, const float* bias, const void* dy_bf16, void* dz_bf16,
+                                       int N, int T, int C, int groups, int k, void* stream) {
+  return posconv_run<PC_ACT>("mmf_w2v_posconv_bwd_act", x_bf16, w_bf16, bias, dy_bf16, dz_bf16, N, T, C, groups, k, k >> 1, stream);
+}
+
+extern "C" int mmf_w2v_posconv_dgrad(const void* dz_bf16, const void* wt_bf16, const void* dy_bf16, void* dx_bf16, int N, int T, int C,
+                                     int groups, int k, void* stream) {
+  return posconv_run<PC_DGRAD>("mmf_w2v_posconv_dgrad", dz_bf16, wt_bf16, nullptr, dy_bf16, dx_bf16, N, T, C, groups, k, k - 1 - (k >> 1),
+                               stream);
+}
+
+extern "C" int mmf_w2v_posconv_wgrad(const void* dz_bf16, const void* x_bf16, float* dw, int N, int T, int C, int groups, int k,
+                                     int slabs, int accumulate, void* stream) {
+  const char* fn = "mmf_w2v_posconv_wgrad";
+  if (!dz_bf16 || !x_bf16 || !dw || N <= 0 || T <= 0 || C <= 0 || groups <= 0 || k <= 0 || slabs <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand or N=%d T=%d C=%d groups=%d k=%d slabs=%d", fn, N, T, C, groups, k, slabs);
+  if (C % groups) MMF_FAIL(MMF_E_SHAPE, "%s: C=%d is not a multiple of groups=%d", fn, C, groups);
+  const int cg = C / groups, nblk = (T + WG_TT - 1) / WG_TT;
+  const int64_t units = (int64_t)N * nblk;
+  if (slabs > units || slabs > MMF_SUM_SLABS_MAX || (slabs > 1 && accumulate))
+    MMF_FAIL(MMF_E_SHAPE, "%s: slabs=%d must be at most %d and the %lld (clip, 128-row block) units, and slab partials are written, "
+             "not added to (accumulate=%d)", fn, slabs, MMF_SUM_SLABS_MAX, (long long)units, accumulate);
+  if ((cg & 15) || cg > 64 || N > 65535 || groups > 65535 || units >= ((int64_t)1 << 30))
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: group width %d (16, 32, 48 or 64), N=%d groups=%d (at most 65535)", fn, cg, N, groups);
+  const int Kp = (k * cg + 31) & ~31;
+  if (((size_t)127 * cg + Kp) * 2 > 65536)                             // the forward's limit: what it cannot run has no gradient to take
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: k=%d at group width %d is beyond the forward's LDS limit", fn, k, cg);
+  if (!mmf_aligned16(dz_bf16) || !mmf_aligned16(x_bf16) || !mmf_aligned16(dw))
+    MMF_FAIL(MMF_E_ALIGN, "%s: pointers must be 16-byte aligned", fn);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned short* dz = static_cast<const unsigned short*>(dz_bf16);
+  const unsigned short* x = static_cast<const unsigned short*>(x_bf16);
+  const int per = (int)((units + slabs - 1) / slabs), pad = k >> 1;
+  const dim3 grid((k + WG_TAPS - 1) / WG_TAPS, groups, slabs);
+  const int nu = (int)units;
+  switch (cg / 16) {
+    case 1: hipLaunchKernelGGL(w2v_posconv_wgrad_kernel<1>, grid, dim3(W2V_THREADS), 0, s, dz, x, dw, T, C, k, Kp, pad, nblk, nu, per, accumulate); break;
+    case 2: hipLaunchKernelGGL(w2v_posconv_wgrad_kernel<2>, grid, dim3(W2V_THREADS), 0, s, dz, x, dw, T, C, k, Kp, pad, nblk, nu, per, accumulate); break;
+    case 3: hipLaunchKernelGGL(w2v_posconv_wgrad_kernel<3>, grid, dim3(W2V_THREADS), 0, s, dz, x, dw, T, C, k, Kp, pad, nblk, nu, per, accumulate); break;
+    default: hipLaunchKernelGGL(w2v_posconv_wgrad_kernel<4>, grid, dim3(W2V_THREADS), 0, s, dz, x, dw, T, C, k, Kp, pad, nblk, nu, per, accumulate); break;
+  }
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_w2v_weightnorm_bwd(const float* dw, const float* g, const float* v, float* dg, float* dv, int C, int cg, int k,
+                                      int overwrite_v, void* stream) {
+  const char* fn = "mmf_w2v_weightnorm_bwd";
+  if (!dw || !g || !v || !dg || !dv || C <= 0 || cg <= 0 || k <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: null operand or C=%d cg=%d k=%d", fn, C, cg, k);
+  if (C % cg) MMF_FAIL(MMF_E_SHAPE, "%s: C=%d is not a multiple of the group width %d", fn, C, cg);
+  if (k > 65535 || (int64_t)C * cg >= ((int64_t)1 << 31) / k)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: k=%d (at most 65535), C * cg * k = %lld (below 2^31)", fn, k, (long long)C * cg * k);
+  if (!mmf_aligned16(dw) || (reinterpret_cast<uintptr_t>(g) & 3u) || (reinterpret_cast<uintptr_t>(v) & 3u) || (reinterpret_cast<uintptr_t>(dg) & 3u)
+      || (reinterpret_cast<uintptr_t>(dv) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: dw must be 16-byte aligned, the other operands 4-byte aligned", fn);
+  const int Kp = (k * cg + 31) & ~31;
+  hipLaunchKernelGGL(w2v_weightnorm_bwd_kernel, dim3(k), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream), dw, g, v, dg, dv, C * cg, cg, k, Kp,
+                     overwrite_v);
+  MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }

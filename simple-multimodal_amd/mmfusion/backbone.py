@@ -16,7 +16,7 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
       fc2 + bias + resid            mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> out
     _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
     _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
-    _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; the backward of NativeDeberta and NativeViT)
+    _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; the backbones' backward)
     _ln_bwd_add(...)                mmf_layernorm_bwd_add_grouped        dy, r -> dx = r + that (a pre-LN layer's residual gradient)
     _wgrad(dy, x, name, slabs)      mmf_gemm_grouped TN, COLSUM_A        dy, x -> a trainable layer's weight and bias gradients; in
                                     (+ mmf_sum_slabs_f32)                ``slabs`` K-slabs where the output is a few tiles under many rows
@@ -28,10 +28,10 @@ names.  A subclass declares its workspace as a table of (name, elements per chun
 allocation and the bytes-per-item figure are both read from that table.  A forward pass writes no attribute of the module
 but that workspace and the ``_derived`` cache: what a launch needs beyond the buffers travels as arguments.
 
-Frozen by default: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  Two backbones have a
-backward: ``NativeDeberta`` called with input embeddings that require a gradient (prompt tuning), and it and ``NativeViT`` with
-their top layers marked trainable (``set_trainable_layers``: those layers' parameters then require a gradient and a call in grad
-mode adds their gradients into the parameter arena), mmfusion/deberta.py and mmfusion/vit.py; ``NativeWav2Vec2`` is forward only.  bf16
+Frozen by default: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  Every backbone has a
+backward: ``NativeDeberta`` called with input embeddings that require a gradient (prompt tuning), and all three with their top
+layers marked trainable (``set_trainable_layers``: those layers' parameters then require a gradient and a call in grad mode adds
+their gradients into the parameter arena), mmfusion/deberta.py, mmfusion/vit.py and mmfusion/wav2vec2.py.  bf16
 storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
 Nothing synchronises with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.
 """
@@ -86,7 +86,7 @@ class FrozenBackbone(nn.Module):
         self._gws: Optional[dict] = None               # a backward's workspace (the subclass's _grad_table), from the first differentiable call
         self._slabs: Optional[torch.Tensor] = None     # _slab_buffer
 
-    # -- fine-tuning the top layers (NativeDeberta, NativeViT) -------------------------------------------
+    # -- fine-tuning the top layers ----------------------------------------------------------------------
     @staticmethod
     def _layer_params(i: int) -> list:
         return [f"l{i}_{r}_{s}" for r in ("qkv", "o", "ln1", "fc1", "fc2", "ln2") for s in "wb"]
@@ -327,6 +327,34 @@ class FrozenBackbone(nn.Module):
         ``slabs`` = 1: one plain launch)"""
         w, b = getattr(self, name + "_w").grad, getattr(self, name + "_b").grad
         self._wgrad_launch([(dy, x, w, b)], self._first_touch(w), slabs)
+
+    @staticmethod
+    def _slabs_for(rows: int, tiles: int) -> int:
+        """The K-slab count of a weight-gradient launch of ``tiles`` 256 x 256 output tiles over ``rows`` rows (the host rule,
+        DESIGN.md section 8): as many slabs as fill one round of the CUs with tiles, each at least 1024 rows long; 1 (the plain
+        launch) where that would not reach half the CUs, below which the TN launch is the small-tile kernel's either way"""
+        cus = lib.load().mmf_device_cu_count()
+        cus = cus if cus > 0 else 256
+        S = min(cus // tiles, rows // 1024, lib.SUM_SLABS_MAX)
+        return S if S > 1 and S * tiles >= (cus + 1) // 2 else 1
+
+    @staticmethod
+    def _tiles(M: int, N: int) -> int:
+        """the 256 x 256 output tiles of an (M, N) weight gradient (what ``auto_impl`` of csrc/gemm.hip counts)"""
+        return ((M + 255) // 256) * ((N + 255) // 256)
+
+    def _qkv_wgrad_roles(self, i: int, junk: torch.Tensor, dqkv: torch.Tensor, x: torch.Tensor, roles: Sequence[int] = (0, 1, 2),
+                         overwrite: Optional[bool] = None) -> None:
+        """The rows ``roles`` (0 / 1 / 2 = q / k / v) of layer ``i``'s fused Q/K/V weight and bias gradients from ``dqkv`` and the
+        projection's input ``x``, one K-slab launch.  The key bias takes no column sum: its exact gradient is zero (a shift of
+        every key by one vector moves every score of a row equally), what a column sum would add is the bf16 residue of delta and
+        dK; the GEMM's column sum of that part goes to ``junk`` (hidden_size f32, not kept).  ``overwrite``: the weight's first
+        touch where the caller has taken it already"""
+        d = self.config.hidden_size
+        w, b = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad
+        over = self._first_touch(w) if overwrite is None else overwrite
+        part = lambda r: (dqkv[:, r * d:(r + 1) * d], x, w[r * d:(r + 1) * d], junk if r == 1 else b[r * d:(r + 1) * d])
+        self._wgrad_launch([part(r) for r in roles], over, self._slabs_for(x.shape[0], len(roles) * self._tiles(d, d)))
 
     def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
         """attention of ``Tq`` queries per item over its ``T`` keys, read from the fused ``qkv`` rows; ``Tq == 1`` takes the

@@ -27,7 +27,7 @@ SYMBOLS = (
     "mmf_version", "mmf_last_error", "mmf_device_cu_count", "mmf_gemm_grouped", "mmf_gemm_grouped_ex", "mmf_gemm_relu_bits_bytes", "mmf_gemm_relu_bits_available", "mmf_gemm_select_impl", "mmf_gemm_last_impl", "mmf_gemm_set_persistent_workgroups",
     "mmf_gemm7_set_tile_n", "mmf_gemm7_last_tile_n", "mmf_gemm7_tile_n",
     "mmf_attn_fwd_grouped_ex", "mmf_attn_bwd_grouped_ex", "mmf_dropout", "mmf_attn_select_impl",
-    "mmf_attn_fwd_grouped", "mmf_attn_bwd_grouped", "mmf_layernorm_fwd_grouped",
+    "mmf_attn_fwd_grouped", "mmf_attn_bwd_grouped", "mmf_attn_delta_f32", "mmf_attn_bwd_grouped_delta", "mmf_layernorm_fwd_grouped",
     "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_add_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_layernorm2_add3_available", "mmf_layernorm2_add3_fwd_grouped", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
     "mmf_meanpool_fwd", "mmf_meanpool_bwd", "mmf_meanpool_cat_fwd", "mmf_meanpool_cat_bwd", "mmf_colsum_bf16", "mmf_colsum_grouped", "mmf_relu_bwd_bf16", "mmf_relu_bwd_mixed",
     "mmf_sqnorm_f32", "mmf_adamw_step", "mmf_adamw_advance", "mmf_skinny_linear_fwd", "mmf_skinny_linear_dgrad", "mmf_skinny_linear_fwd_ex", "mmf_skinny_linear_dgrad_ex", "mmf_skinny_last_strip",
@@ -41,6 +41,7 @@ SYMBOLS = (
     "mmf_eval_accumulate",
     "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_vit_embed_tokens_bwd", "mmf_vit_cls_attn_bwd", "mmf_bias_gelu_bf16", "mmf_bias_gelu_bf16_to", "mmf_bias_gelu_bwd_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
+    "mmf_w2v_posconv_bwd_act", "mmf_w2v_posconv_dgrad", "mmf_w2v_posconv_wgrad", "mmf_w2v_weightnorm_bwd",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
@@ -157,6 +158,8 @@ def load() -> C.CDLL:
     lib.mmf_attn_fwd_grouped.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
     lib.mmf_attn_select_impl.argtypes = [i32]
     lib.mmf_attn_bwd_grouped.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
+    lib.mmf_attn_delta_f32.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
+    lib.mmf_attn_bwd_grouped_delta.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
     lib.mmf_layernorm_fwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, f32, vp]
     lib.mmf_layernorm_bwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
     lib.mmf_layernorm_bwd_add_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
@@ -231,6 +234,10 @@ def load() -> C.CDLL:
     lib.mmf_w2v_conv0_norm_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_w2v_gelu_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_posconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_posconv_bwd_act.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_posconv_dgrad.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_posconv_wgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_weightnorm_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.mmf_deberta_embed.argtypes = [vp, vp, vp, vp, vp, f32, vp, i32, vp, i64, i32, i32, vp]
     lib.mmf_deberta_attn_fwd.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_deberta_attn_fwd_lse.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp]
@@ -338,6 +345,18 @@ def attn_bwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: floa
     with _Timed(f"attn_bwd_kernels<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
         check(load().mmf_attn_bwd_grouped_ex(arr, len(problems), head_dim, scale, dropout_p, rng_state_ptr, site,
                                              stream_ptr()))
+
+
+def attn_bwd_grouped_exact_delta(problems: Sequence[AttnProblem], head_dim: int, scale: float) -> None:
+    """``attn_bwd_grouped`` (no dropout) with delta = sum_j p_ij dp_ij formed in f32 by ``mmf_attn_delta_f32`` instead of dO . O from
+    the bf16 O: one more pass over the keys, for gradients that the rounding of O would otherwise bury (include/mmfusion.h)"""
+    arr = (AttnProblem * len(problems))(*problems)
+    shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
+    flops = sum(p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
+    with _Timed(f"attn_delta_kernel<{head_dim}>", 4.0 * flops, shapes):
+        check(load().mmf_attn_delta_f32(arr, len(problems), head_dim, scale, stream_ptr()))
+    with _Timed(f"attn_bwd_kernels<{head_dim}>", 8.0 * flops, shapes):
+        check(load().mmf_attn_bwd_grouped_delta(arr, len(problems), head_dim, scale, stream_ptr()))
 
 
 def layernorm_fwd_grouped(problems: Sequence[LnProblem], d: int, eps: float) -> None:
@@ -566,6 +585,60 @@ def w2v_posconv(x, w, bias, y, N: int, T: int, C: int, groups: int, k: int) -> N
         raise ValueError("w2v_posconv: operand sizes do not match N, T, C, groups, k")
     with _Timed("w2v_posconv_kernel", 2.0 * N * T * C * cg * k, [(N * T, C, k * cg)]):
         check(load().mmf_w2v_posconv(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N, T, C, groups, k, stream_ptr()))
+
+
+def _w2v_posconv_sizes(what: str, acts, w, N: int, T: int, C: int, groups: int, k: int) -> int:
+    """the shared size check of the positional convolution's backward wrappers -> cg"""
+    cg = C // max(groups, 1)
+    Kp = (k * cg + 31) // 32 * 32
+    if any(t.numel() < N * T * C or not t.is_contiguous() for t in acts) or (w is not None and (w.numel() != C * Kp or not w.is_contiguous())):
+        raise ValueError(f"{what}: operand sizes do not match N, T, C, groups, k")
+    return cg
+
+
+def w2v_posconv_bwd_act(x, w, bias, dy, dz, N: int, T: int, C: int, groups: int, k: int) -> None:
+    """dz = dy * gelu'(grouped_conv(x) + bias) on (N, T, C) bf16: the pre-activation is computed again, as ``w2v_posconv`` does"""
+    _w2v_bf16(x, w, dy, dz)
+    _w2v_f32(bias)
+    cg = _w2v_posconv_sizes("w2v_posconv_bwd_act", (x, dy, dz), w, N, T, C, groups, k)
+    if bias.numel() != C:
+        raise ValueError("w2v_posconv_bwd_act: operand sizes do not match N, T, C, groups, k")
+    with _Timed("w2v_posconv_bwd_act_kernel", 2.0 * N * T * C * cg * k, [(N * T, C, k * cg)]):
+        check(load().mmf_w2v_posconv_bwd_act(x.data_ptr(), w.data_ptr(), bias.data_ptr(), dy.data_ptr(), dz.data_ptr(), N, T, C, groups, k,
+                                             stream_ptr()))
+
+
+def w2v_posconv_dgrad(dz, wt, dy, dx, N: int, T: int, C: int, groups: int, k: int) -> None:
+    """dx = dy + the convolution's input gradient of dz on (N, T, C) bf16; wt: the packed weight with the taps reversed and
+    co / ci swapped (include/mmfusion.h)"""
+    _w2v_bf16(dz, wt, dy, dx)
+    cg = _w2v_posconv_sizes("w2v_posconv_dgrad", (dz, dy, dx), wt, N, T, C, groups, k)
+    with _Timed("w2v_posconv_dgrad_kernel", 2.0 * N * T * C * cg * k, [(N * T, C, k * cg)]):
+        check(load().mmf_w2v_posconv_dgrad(dz.data_ptr(), wt.data_ptr(), dy.data_ptr(), dx.data_ptr(), N, T, C, groups, k, stream_ptr()))
+
+
+def w2v_posconv_wgrad(dz, x, dw, N: int, T: int, C: int, groups: int, k: int, slabs: int = 1, accumulate: bool = False) -> None:
+    """dw (C, Kp) f32, the packed layout of ``w2v_posconv``'s weight, (+)= the weight gradient over the N clips; ``slabs`` > 1:
+    dw is (slabs, C, Kp), one partial per run of (clip, 128-row block) units, written, for ``sum_slabs``"""
+    _w2v_bf16(dz, x)
+    _w2v_f32(dw)
+    cg = _w2v_posconv_sizes("w2v_posconv_wgrad", (dz, x), None, N, T, C, groups, k)
+    if dw.numel() != max(slabs, 1) * C * ((k * cg + 31) // 32 * 32):
+        raise ValueError("w2v_posconv_wgrad: dw is not (slabs, C, Kp)")
+    with _Timed("w2v_posconv_wgrad_kernel", 2.0 * N * T * C * cg * k, [(N * T, C, k * cg)]):
+        check(load().mmf_w2v_posconv_wgrad(dz.data_ptr(), x.data_ptr(), dw.data_ptr(), N, T, C, groups, k, slabs, int(bool(accumulate)),
+                                           stream_ptr()))
+
+
+def w2v_weightnorm_bwd(dw, g, v, dg, dv, overwrite_v: bool) -> None:
+    """dw (C, Kp) f32, the packed gradient of the effective weight g v / ||v|| -> dg (1, 1, k) += , dv (C, cg, k) = or +="""
+    _w2v_f32(dw, g, v, dg, dv)
+    C, cg, k = v.shape
+    if dw.numel() != C * ((k * cg + 31) // 32 * 32) or g.numel() != k or dg.numel() != k or dv.shape != v.shape:
+        raise ValueError("w2v_weightnorm_bwd: operand sizes do not match v (C, cg, k)")
+    with _Timed("w2v_weightnorm_bwd_kernel", 0.0, [(C * cg, k)]):
+        check(load().mmf_w2v_weightnorm_bwd(dw.data_ptr(), g.data_ptr(), v.data_ptr(), dg.data_ptr(), dv.data_ptr(), C, cg, k,
+                                            int(bool(overwrite_v)), stream_ptr()))
 
 
 # ---- DeBERTa kernels (csrc/deberta.hip) ------------------------------------------------------------------------

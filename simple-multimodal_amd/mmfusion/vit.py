@@ -365,21 +365,6 @@ class NativeViT(FrozenBackbone):
         self._gws = g
         return g
 
-    @staticmethod
-    def _slabs_for(rows: int, tiles: int) -> int:
-        """The K-slab count of a weight-gradient launch of ``tiles`` 256 x 256 output tiles over ``rows`` rows (the host rule,
-        DESIGN.md section 8): as many slabs as fill one round of the CUs with tiles, each at least 1024 rows long; 1 (the plain
-        launch) where that would not reach half the CUs, below which the TN launch is the small-tile kernel's either way"""
-        cus = lib.load().mmf_device_cu_count()
-        cus = cus if cus > 0 else 256
-        S = min(cus // tiles, rows // 1024, lib.SUM_SLABS_MAX)
-        return S if S > 1 and S * tiles >= (cus + 1) // 2 else 1
-
-    @staticmethod
-    def _tiles(M: int, N: int) -> int:
-        """the 256 x 256 output tiles of an (M, N) weight gradient (what ``auto_impl`` of csrc/gemm.hip counts)"""
-        return ((M + 255) // 256) * ((N + 255) // 256)
-
     def _attn_bwd(self, ws, g, qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor, n: int, Tq: int) -> None:
         """``_attn``'s backward: dQ | dK | dV into the fused ``dqkv`` rows, laid out as ``qkv``.  ``Tq == 1`` (``mmf_vit_cls_attn_bwd``):
         the query and ``datt`` rows are one per image, dQ lands in the leading columns of each image's row 0 and the dQ columns
@@ -394,18 +379,15 @@ class NativeViT(FrozenBackbone):
                                               3 * d if Tq == T else T * 3 * d, 3 * d, 3 * d, d)], self.head_dim, self.head_dim ** -0.5)
 
     def _qkv_wgrad(self, i: int, g, dqkv: torch.Tensor, ln: torch.Tensor, n: int, cls: bool) -> None:
-        """layer ``i``'s fused Q/K/V weight and bias gradients from ``dqkv`` and the first LayerNorm's output ``ln``.  The key bias
-        takes no column sum: its exact gradient is zero (a shift of every key by one vector moves every score of a row equally),
-        what a column sum would add is the bf16 residue of delta and dK; the GEMM's column sum of that part goes to ``junk``.
-        ``cls``: dQ is row 0 of each image only, so the Q rows of the weight are a launch of their own over those ``n`` rows"""
+        """layer ``i``'s fused Q/K/V weight and bias gradients from ``dqkv`` and the first LayerNorm's output ``ln``
+        (``FrozenBackbone._qkv_wgrad_roles``: the key bias takes no column sum).  ``cls``: dQ is row 0 of each image only, so the Q
+        rows of the weight are a launch of their own over those ``n`` rows"""
         d = self.config.hidden_size
         w, b = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad
         over = self._first_touch(w)
-        part = lambda r, dy, x: (dy[:, r * d:(r + 1) * d], x, w[r * d:(r + 1) * d], g["junk"] if r == 1 else b[r * d:(r + 1) * d])
         if cls:
             self._wgrad_launch([(self._row0(dqkv, n), self._row0(ln, n), w[:d], b[:d])], over)
-        roles = (1, 2) if cls else (0, 1, 2)
-        self._wgrad_launch([part(r, dqkv, ln) for r in roles], over, self._slabs_for(ln.shape[0], len(roles) * self._tiles(d, d)))
+        self._qkv_wgrad_roles(i, g["junk"], dqkv, ln, (1, 2) if cls else (0, 1, 2), over)
 
     def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, cls: bool) -> None:
         """layer ``i`` again from its saved input ``xin`` up to the GELU output, then its backward with the weight, bias and

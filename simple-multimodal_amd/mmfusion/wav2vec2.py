@@ -1,4 +1,5 @@
-"""Frozen Wav2Vec2 backbone on the HIP kernels: waveforms -> frame states, forward only.
+"""Wav2Vec2 backbone on the HIP kernels: waveforms -> frame states; frozen by default, with the weight gradients of the top layers
+and of the front end (everything above the convolutional feature extractor) where they are marked trainable.
 
 The reference pushes every clip through HuggingFace's ``Wav2Vec2Model`` per step (reference models/encoders.py:116,144).
 ``NativeWav2Vec2`` is that model rebuilt from its sizes alone (nothing is fetched), with HuggingFace's ``state_dict``
@@ -25,24 +26,62 @@ transformer needs no transpose.  Launch list for a chunk of ``n`` clips (the lay
     widening cast                 mmf_cast_bf16_to_f32                 x  -> result
 
 Clips are processed in chunks of ``chunk`` through one workspace sized by the chunk and the longest waveform seen so far
-(a longer one reallocates it once; shorter ones use its leading part).  Forward only, frozen, bf16 storage only, nothing
+(a longer one reallocates it once; shorter ones use its leading part).  Frozen by default, bf16 storage only, nothing
 synchronises with the host (mmfusion/backbone.py).
+
+Fine-tuning.  ``set_trainable_layers(k, front=False)`` marks the parameters of layers ``L - k .. L - 1`` trainable and, with
+``k == L`` and ``front``, everything between the feature extractor and layer 0 (HuggingFace's ``freeze_feature_encoder()`` regime).
+With grad mode on every call is then one ``torch.autograd.Function`` around the launch list above (the trainable parameters are
+its inputs, so the result carries a graph; there is no gradient with respect to the waveform) plus one copy per walked layer: it
+keeps the bf16 input of layers ``>= L - k`` and, with ``front``, ``feat``, the feature LayerNorm's input.  The backward, per chunk
+and per layer top down, runs the layer again from its saved input (both LayerNorms' statistics, the raw fc1 output beside the GELU
+output) and then
+
+      LayerNorm 2 backward          mmf_layernorm_bwd_grouped                gx -> dy2
+      fc2 wgrad, dgrad              mmf_gemm_grouped TN (COLSUM_A) / NN      dy2 -> dg
+      GELU backward                 mmf_bias_gelu_bwd_bf16 (in place)        dg, h -> dh
+      fc1 wgrad, dgrad + dy2        TN / NN, ADD_AUX                         dh -> dln1
+      LayerNorm 1 backward          mmf_layernorm_bwd_grouped                dln1 -> dy1
+      out-projection wgrad, dgrad   TN / NN                                  dy1 -> datt
+      attention backward            mmf_attn_delta_f32, then                 datt -> dqkv (delta = sum_j p_ij dp_ij in f32, not dO . O
+                                    mmf_attn_bwd_grouped_delta               from the bf16 O: see below)
+      Q/K/V wgrad, dgrad + dy1      TN / NN, ADD_AUX                         dqkv -> gx of the layer below
+
+(the dgrad of the lowest walked layer is not launched unless the front end trains).  The attention backward is the shared MFMA one
+with its delta as an input: its own delta = dO . O reads the bf16 O, so a row of dS sums to dO . (O - bf16(O)) instead of zero, an
+absolute residue; where the frames of a clip have grown alike (twelve layers deep they do) dS nearly vanishes and that residue was
+up to 18 times the q / k projections' exact gradients at base sizes (tests/test_w2v_finetune_gpu.py).  The d x d and d x I weight gradients take the
+K-slab form where ``_slabs_for`` says so, and the key bias gets no column sum (mmfusion/backbone.py).  The front end, per chunk:
+``LN(feat)``, the projection and the positional convolution are computed again (the conv stack never is), then
+
+      encoder LayerNorm backward    mmf_layernorm_bwd_grouped                gx -> dy
+      dz = dy gelu'(b + conv(x0))   mmf_w2v_posconv_bwd_act                  the forward's MFMA loop again; db += colsum(dz)
+      dW_eff += dz (*) x0           mmf_w2v_posconv_wgrad (+ mmf_sum_slabs)  f32, packed as the forward reads it, summed over the chunks
+      dx0 = dy + conv^T(dz)         mmf_w2v_posconv_dgrad                    the forward's kernel on the reversed, swapped weight
+      projection wgrad, dgrad       TN / NN                                  dx0 -> dfln
+      feature LayerNorm backward    mmf_layernorm_bwd_grouped                for its dgamma / dbeta; dx is not kept
+
+and once per backward ``mmf_w2v_weightnorm_bwd`` turns the summed dW_eff into the gradients of the weight norm's g and v (the
+forward rounds the effective weight to bf16; the gradient passes straight through that rounding).  Gradients are added into the
+parameters' f32 ``.grad`` (the arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it) in stream order.
 """
 from __future__ import annotations
 
 import types
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import arena as _arena
 from . import lib, ops
 from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
-from .lib import EPI_BIAS, GEMM_NT
+from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NN, GEMM_NT
 
-# clips per pass through the workspace.  NOT chosen by measurement yet: 8 clips keep the workspace at 0.57 GB for 10 s clips
-# and give the layer GEMMs 3992 rows; tools/w2v_bench.py --chunks is the sweep that should decide it (DESIGN.md section 9)
+# clips per pass through the workspace: 16 clips of 10 s give the layer GEMMs 7984 rows.  NOT chosen by measurement yet:
+# tools/w2v_bench.py --chunks is the sweep that should decide it (DESIGN.md section 9)
 DEFAULT_CHUNK = 16
+POS_WGRAD_BLOCK = 128                      # time rows per unit of mmf_w2v_posconv_wgrad (WG_TT of csrc/wav2vec2.hip)
+POS_WGRAD_TAPS = 8                         # taps per workgroup of it
 POS_GROUP_WIDTHS = (16, 32, 48, 64)        # the forms of mmf_w2v_posconv
 
 _WN = "encoder.pos_conv_embed.conv."
@@ -61,10 +100,38 @@ def feat_lengths(L: int, kernels: Sequence[int], strides: Sequence[int]) -> List
     return out
 
 
+class _Differentiable(torch.autograd.Function):
+    """``NativeWav2Vec2._launches``, differentiable with respect to the trainable parameters (``params``; never to the waveform).
+    They are inputs so that the result carries a graph; their gradients are not returned but added into their f32 ``.grad`` by the
+    backward's own launches, as ``ops.queue_wgrad``'s are."""
+
+    @staticmethod
+    def forward(ctx, model: "NativeWav2Vec2", wave: torch.Tensor, *params) -> torch.Tensor:
+        c = model.config
+        N, T, L = wave.shape[0], model.frames(wave.shape[1]), c.num_hidden_layers
+        first = L - model.trainable_layers                             # the lowest layer the backward walks
+        keep = torch.empty((L - first, N * T, c.hidden_size), dtype=BF16, device=wave.device)
+        feat = torch.empty((N * T, c.conv_dim[-1]), dtype=BF16, device=wave.device) if model.trainable_front else None
+        pos_w = model._pos_weight()
+        out = model._launches(wave, pos_w, keep, first, feat)
+        ctx.model, ctx.first, ctx.front, ctx.pos_w = model, first, model.trainable_front, pos_w
+        ctx.save_for_backward(*((wave, keep) if feat is None else (wave, keep, feat)))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        wave, keep, *feat = ctx.saved_tensors
+        if any(ctx.needs_input_grad[2:]):
+            ctx.model._backward(wave, keep, feat[0] if ctx.front else None, ctx.first, ctx.pos_w, dout.contiguous())
+        return (None,) * len(ctx.needs_input_grad)
+
+
 class NativeWav2Vec2(FrozenBackbone):
-    """HuggingFace ``Wav2Vec2Model`` (inference, no mask), defaults = wav2vec2-base.
+    """HuggingFace ``Wav2Vec2Model`` (no mask), defaults = wav2vec2-base.
 
     ``forward(input_values)`` -> ``.last_hidden_state`` (N, T, hidden) f32; ``input_values``: (N, L) f32 on the GPU.
+    Frozen by default; after ``set_trainable_layers(k)``, ``k > 0``, a call in grad mode carries the top ``k`` layers' weight
+    gradients (never a gradient with respect to ``input_values``).
     ``state_dict()`` has the keys, shapes and order of ``Wav2Vec2Model``; ``load_state_dict`` also takes the older weight-norm
     names (``weight_g`` / ``weight_v``).  Q/K/V are stored fused, the inner conv weights as ``(C_out, k, C_in)`` (the GEMM's
     operand), and split / permuted on the way.  ``masked_spec_embed`` is kept as an unused parameter."""
@@ -137,6 +204,40 @@ class NativeWav2Vec2(FrozenBackbone):
             self._add_layer(i, d, I, {"k": a + "attention.k_proj", "v": a + "attention.v_proj", "q": a + "attention.q_proj",
                                       "o": a + "attention.out_proj", "ln1": a + "layer_norm", "fc1": a + "feed_forward.intermediate_dense",
                                       "fc2": a + "feed_forward.output_dense", "ln2": a + "final_layer_norm"})
+        self._front = False                            # set_trainable_layers(L, front=True)
+
+    # -- fine-tuning --------------------------------------------------------------------------------------
+    _FRONT_PARAMS = ("fp_ln_w", "fp_ln_b", "fp_w", "fp_b", "pos_b", "pos_g", "pos_v", "enc_ln_w", "enc_ln_b")
+
+    @property
+    def trainable_front(self) -> bool:
+        return self._front
+
+    def _trainable_names(self) -> list:
+        """the parameters that require a gradient, in the order the differentiable forward takes them"""
+        L, k = self.config.num_hidden_layers, self._trainable
+        return (list(self._FRONT_PARAMS) if self._front else []) + [n for i in range(L - k, L) for n in self._layer_params(i)]
+
+    def set_trainable_layers(self, k: int, front: bool = False) -> None:
+        """The parameters of the top ``k`` layers (``L - k .. L - 1``) get ``requires_grad = True``, every other parameter
+        ``False``; 0 freezes the backbone again.  ``front=True`` (with ``k == L`` only: the gradient reaches the front end through
+        every layer) also trains ``feature_projection.layer_norm`` and ``.projection``, the positional convolution's ``bias`` and
+        its weight norm's ``g`` / ``v`` (``parametrizations.weight.original0`` / ``original1``) and ``encoder.layer_norm``.  The
+        feature-extractor convolutions, layer 0's GroupNorm and ``masked_spec_embed`` never train: this is the regime of
+        HuggingFace's ``freeze_feature_encoder()``.  With grad mode on and ``k > 0``, ``forward`` returns a result that carries a
+        graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops
+        below layer ``L - k``.  There is no gradient with respect to the waveform; SpecAugment masking, the backbone's dropout and
+        LayerDrop are not built; the fp32 parity mode is refused as everywhere in this class."""
+        L = self.config.num_hidden_layers
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
+            raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
+        if not isinstance(front, bool) or (front and k != L):
+            raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}, front={front!r}): the front end trains with all "
+                             f"{L} layers only (its gradient comes through every layer)")
+        self._trainable, self._front = k, front
+        names = set(self._trainable_names())
+        for name, p in self.named_parameters(recurse=False):
+            p.requires_grad_(name in names)
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _canonical_key(self, key: str) -> str:
@@ -173,17 +274,27 @@ class NativeWav2Vec2(FrozenBackbone):
         return self._bytes_per_item(self._ws_table(L))
 
     # -- weights ----------------------------------------------------------------------------------------
-    def _pos_weight(self) -> torch.Tensor:
+    def _pos_weight(self, transposed: bool = False) -> torch.Tensor:
         """The positional convolution's effective weight g v / ||v|| (norm over dims (0, 1) per tap, ``weight_norm(dim=2)``),
-        folded in f32, repacked to (groups, cg, Kp) column (tap, channel) and rounded to bf16 once per weight version."""
+        folded in f32, repacked to (groups, cg, Kp) column (tap, channel) and rounded to bf16.  ``transposed``: the operand of the
+        input gradient instead, taps reversed and co / ci swapped within each group: [g][ci][j * cg + co] = w[g cg + co][ci][k - 1 - j].
+        Once per weight version while the front end is frozen; in every call while it trains (the optimiser writes the masters
+        through raw pointers, which moves no version counter, so nothing derived from a trainable weight may be cached)"""
         def build():
             g, v = self._f("pos_g"), self._f("pos_v")
             w = g * v / v.norm(dim=(0, 1), keepdim=True)                                          # (C, cg, k)
             C, cg, k = w.shape
             packed = torch.zeros(C, self.pos_kp, dtype=BF16, device=w.device)
-            packed[:, :k * cg] = w.permute(0, 2, 1).reshape(C, k * cg).to(BF16)
+            if transposed:
+                w = w.view(C // cg, cg, cg, k).flip(3).permute(0, 2, 3, 1)                        # (groups, ci, reversed tap, co)
+            else:
+                w = w.permute(0, 2, 1)
+            packed[:, :k * cg] = w.reshape(C, k * cg).to(BF16)
             return packed
-        return self._derived("pos_w16", ("pos_g", "pos_v"), build)
+        if self._front:
+            with torch.no_grad():
+                return build()
+        return self._derived("pos_wt16" if transposed else "pos_w16", ("pos_g", "pos_v"), build)
 
     # -- launches ---------------------------------------------------------------------------------------
     def _features(self, ws, wave: torch.Tensor, n: int, Ts: List[int]) -> torch.Tensor:
@@ -206,33 +317,188 @@ class NativeWav2Vec2(FrozenBackbone):
         return raw
 
     def forward(self, input_values: torch.Tensor, attention_mask=None) -> BackboneOutput:
-        c = self.config
         if attention_mask is not None:
             raise NotImplementedError("NativeWav2Vec2: attention_mask is not implemented (the reference never passes one)")
         self._check_input(input_values, "input_values")
         if input_values.dim() != 2:
             raise ValueError(f"NativeWav2Vec2: input_values {tuple(input_values.shape)} is not (N, L)")
-        N, L = input_values.shape
-        Ts = feat_lengths(L, c.conv_kernel, c.conv_stride)
-        T, d = Ts[-1], c.hidden_size
-        if T < 1:
-            raise ValueError(f"NativeWav2Vec2: {L} samples are shorter than the feature extractor's receptive field")
+        if self.frames(input_values.shape[1]) < 1:
+            raise ValueError(f"NativeWav2Vec2: {input_values.shape[1]} samples are shorter than the feature extractor's receptive field")
         wave = input_values.contiguous()
         _arena.ensure(self)
-        pos_w = self._pos_weight()
+        if torch.is_grad_enabled() and self._trainable > 0:
+            return BackboneOutput(_Differentiable.apply(self, wave.detach(), *(getattr(self, n) for n in self._trainable_names())))
+        return BackboneOutput(self._launches(wave, self._pos_weight()))
+
+    def _front_end(self, ws, feat: torch.Tensor, pos_w: torch.Tensor, n: int, T: int, st=None) -> None:
+        """feat (n T, conv_dim[-1]) -> the feature LayerNorm (into ``win``; statistics into ``st``, None: the workspace's), the
+        projection (``x``) and the positional convolution (``y``)"""
+        c, d, rows = self.config, self.config.hidden_size, n * T
+        x, y, fln = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d), self._rows(ws, "win", rows, feat.shape[1])
+        self._ln(ws if st is None else st, feat, fln, "fp_ln_w", "fp_ln_b")
+        ops.gemm(GEMM_NT, fln, self._w("fp_w"), x, bias=self._f("fp_b"), epilogue=EPI_BIAS)
+        lib.w2v_posconv(x, pos_w, self._f("pos_b"), y, n, T, d, c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings)
+
+    def _launches(self, wave: torch.Tensor, pos_w: torch.Tensor, keep: Optional[torch.Tensor] = None, first: int = 0,
+                  feat_keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the launch list on checked inputs -> (N, T, d) f32.  The differentiable call's: ``keep`` (layers - first, N T, d) bf16
+        also takes a copy of the input of every layer from ``first`` up, ``feat_keep`` (N T, conv_dim[-1]) one of the feature
+        LayerNorm's input"""
+        c = self.config
+        N, L = wave.shape
+        Ts = feat_lengths(L, c.conv_kernel, c.conv_stride)
+        T, d = Ts[-1], c.hidden_size
         ws = self._workspace(wave.device, L)
         out = torch.empty((N, T, d), dtype=torch.float32, device=wave.device)
         for n0 in range(0, N, self.chunk):
             n = min(self.chunk, N - n0)
             rows = n * T
             feat = self._features(ws, wave[n0:n0 + n], n, Ts)
+            if feat_keep is not None:
+                feat_keep[n0 * T:n0 * T + rows].copy_(feat)
             x, y = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d)
-            fln = self._rows(ws, "win", rows, feat.shape[1])
-            self._ln(ws, feat, fln, "fp_ln_w", "fp_ln_b")
-            ops.gemm(GEMM_NT, fln, self._w("fp_w"), x, bias=self._f("fp_b"), epilogue=EPI_BIAS)
-            lib.w2v_posconv(x, pos_w, self._f("pos_b"), y, n, T, d, c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings)
+            self._front_end(ws, feat, pos_w, n, T)
             self._ln(ws, y, x, "enc_ln_w", "enc_ln_b")
             for i in range(c.num_hidden_layers):
+                if keep is not None and i >= first:
+                    keep[i - first, n0 * T:n0 * T + rows].copy_(x)
                 self._post_ln_layer(i, ws, n, T)
             self._widen(x, out[n0:n0 + n])
-        return BackboneOutput(out)
+        return out
+
+    # -- the backward: the trainable layers' and the front end's weight gradients ---------------------------------------
+    def _grad_table(self, L: int) -> WsTable:
+        """what the backward holds beside the forward workspace, per clip of ``L`` samples: the second pre-LN sum, the GELU output
+        (``h`` keeps the raw fc1 output), both LayerNorms' statistics, the attention backward's delta, the gradient buffers
+        (``ga`` / ``gb`` alternate as the d-wide gradients, ``dh`` is dg then dh; the front end's dz takes ``dqkv``'s place) and
+        the two conv_dim[-1]-wide gradients around the feature LayerNorm.  lse is the forward workspace's"""
+        c, T = self.config, self.frames(L)
+        d, H, I, cd, f32 = c.hidden_size, c.num_attention_heads, c.intermediate_size, c.conv_dim[-1], torch.float32
+        return [("y2", T * d, BF16), ("g", T * I, BF16), ("ga", T * d, BF16), ("gb", T * d, BF16), ("dh", T * I, BF16),
+                ("dqkv", T * 3 * d, BF16), ("dfln", T * cd, BF16), ("dfeat", T * cd, BF16), ("mean1", T, f32), ("rstd1", T, f32),
+                ("mean2", T, f32), ("rstd2", T, f32), ("delta", H * T, f32)]
+
+    def grad_workspace_bytes_per_clip(self, L: int) -> int:
+        return self._bytes_per_item(self._grad_table(L))
+
+    def _grad_workspace(self, dev, L: int) -> dict:
+        g = self._gws
+        if g is not None and g["dev"] == dev and g["chunk"] == self.chunk and g["size"] >= L:
+            return g
+        c = self.config
+        d, cd, nbytes = c.hidden_size, c.conv_dim[-1], lib.load().mmf_layernorm_bwd_workspace_bytes
+        # beside the table: the LayerNorm backward's scratch (at the wider of its two widths), where the key bias's column sum
+        # goes (it is not kept), and the positional weight's f32 gradient in the packed layout, summed over a backward's chunks
+        g = {"dev": dev, "chunk": self.chunk, "size": L, "dgb": torch.empty(2 * max(d, cd), dtype=torch.float32, device=dev),
+             "ln_ws": torch.empty(max(nbytes(d), nbytes(cd)) // 4, dtype=torch.float32, device=dev),
+             "junk": torch.empty(d, dtype=torch.float32, device=dev),
+             "dpos": torch.empty(d * self.pos_kp, dtype=torch.float32, device=dev)}
+        for name, numel, dtype in self._grad_table(L):
+            g[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
+        self._gws = g
+        return g
+
+    def _pos_wgrad_slabs(self, n: int, T: int) -> int:
+        """The slab count of ``mmf_w2v_posconv_wgrad`` on a chunk of ``n`` clips: its grid is (tap blocks, groups) workgroups of
+        256 threads, two of which fit a CU; where that leaves CUs idle the (clip, time block) units are cut into as many runs as
+        bring it to two rounds of the CUs, each at least 4 units long"""
+        c = self.config
+        cus = lib.load().mmf_device_cu_count()
+        cus = cus if cus > 0 else 256
+        wgs = c.num_conv_pos_embedding_groups * ((c.num_conv_pos_embeddings + POS_WGRAD_TAPS - 1) // POS_WGRAD_TAPS)
+        units = n * ((T + POS_WGRAD_BLOCK - 1) // POS_WGRAD_BLOCK)
+        return max(1, min(2 * cus // wgs, units // 4, lib.SUM_SLABS_MAX))
+
+    def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, below: bool) -> None:
+        """layer ``i`` again from its saved input ``xin``, then its backward with the weight, bias and LayerNorm gradients added
+        into the parameters' ``.grad``: ``ga`` holds the gradient of the layer's output on entry and, with ``below``, of ``xin``
+        on return"""
+        c = self.config
+        rows, d, I, R = n * T, c.hidden_size, c.intermediate_size, self._rows
+        ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
+        ln, h, qkv, att = R(ws, "ln", rows, d), R(ws, "h", rows, I), R(ws, "qkv", rows, 3 * d), R(ws, "att", rows, d)
+        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        grads = lambda r: (getattr(self, f"l{i}_{r}_w").grad, getattr(self, f"l{i}_{r}_b").grad)
+        slabs = lambda M, N: self._slabs_for(rows, self._tiles(M, N))
+        W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
+        # the forward again: both LayerNorms' statistics, the raw fc1 output and the GELU output side by side
+        y1 = self._attention(i, ws, xin, xin, n, T)
+        self._ln(st1, y1, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
+        ops.gemm(GEMM_NT, ln, W("fc1"), h)
+        lib.bias_gelu_to(h, F("fc1"), gel)
+        ops.gemm(GEMM_NT, gel, W("fc2"), y2, bias=F("fc2"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
+        # the MLP
+        self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w", grads("ln2"))                    # gb = dy2
+        self._wgrad(gb, gel, f"l{i}_fc2", slabs(d, I))
+        ops.gemm(GEMM_NN, gb, W("fc2"), dh)                                           # dg
+        lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
+        self._wgrad(dh, ln, f"l{i}_fc1", slabs(I, d))
+        ops.gemm(GEMM_NN, dh, W("fc1"), ga, aux=gb, epilogue=EPI_ADD_AUX)             # ga = dln1: the MLP branch + the residual
+        # the attention
+        self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w", grads("ln1"))                    # gb = dy1
+        self._wgrad(gb, att, f"l{i}_o", slabs(d, d))
+        ops.gemm(GEMM_NN, gb, W("o"), ga)                                             # ga = datt
+        q, dq = qkv.data_ptr(), dqkv.data_ptr()
+        lib.attn_bwd_grouped_exact_delta([lib.AttnProblem(q, q + 2 * d, q + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), ga.data_ptr(),
+                                              g["delta"].data_ptr(), dq, dq + 2 * d, dq + 4 * d, n, c.num_attention_heads, T, T,
+                                              3 * d, 3 * d, 3 * d, d)], self.head_dim, self.head_dim ** -0.5)
+        self._qkv_wgrad_roles(i, g["junk"], dqkv, xin)
+        if below:
+            ops.gemm(GEMM_NN, dqkv, W("qkv"), ga, aux=gb, epilogue=EPI_ADD_AUX)       # ga = dx: the attention branch + the residual
+
+    def _front_grad(self, ws, g, feat: torch.Tensor, pos_w: torch.Tensor, pos_wt: torch.Tensor, n: int, T: int) -> None:
+        """the front end again from the saved ``feat``, then its backward: ``ga`` holds the gradient of layer 0's input on entry.
+        The gradients of the encoder LayerNorm, the positional bias, the projection and the feature LayerNorm are added into
+        their ``.grad``; the positional weight's into ``g["dpos"]`` (f32, packed), which ``_backward`` finishes"""
+        c = self.config
+        rows, d, cd, R = n * T, c.hidden_size, c.conv_dim[-1], self._rows
+        G, k = c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
+        x0, y, fln = R(ws, "x", rows, d), R(ws, "y", rows, d), R(ws, "win", rows, cd)
+        ga, gb, dz, dfln, dfeat = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dqkv", rows, d), R(g, "dfln", rows, cd), R(g, "dfeat", rows, cd)
+        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        self._front_end(ws, feat, pos_w, n, T, st1)
+        self._ln(st2, y, R(ws, "ln", rows, d), "enc_ln_w", "enc_ln_b")               # for its statistics; the output is not read
+        self._ln_bwd(st2, y, ga, gb, "enc_ln_w", (self.enc_ln_w.grad, self.enc_ln_b.grad))          # gb = dy
+        lib.w2v_posconv_bwd_act(x0, pos_w, self._f("pos_b"), gb, dz, n, T, d, G, k)
+        lib.colsum_grouped([lib.ColsumProblem(dz.data_ptr(), self.pos_b.grad.data_ptr(), rows, d, d)])
+        S = self._pos_wgrad_slabs(n, T)
+        if S > 1:
+            partial = self._slab_buffer(S * g["dpos"].numel(), dz.device).view(S, -1)
+            lib.w2v_posconv_wgrad(dz, x0, partial, n, T, d, G, k, slabs=S)
+            lib.sum_slabs(partial, g["dpos"], True)
+        else:
+            lib.w2v_posconv_wgrad(dz, x0, g["dpos"], n, T, d, G, k, accumulate=True)
+        lib.w2v_posconv_dgrad(dz, pos_wt, gb, ga, n, T, d, G, k)                     # ga = dx0: the convolution + the residual
+        wg = self.fp_w.grad
+        self._wgrad_launch([(ga, fln, wg, self.fp_b.grad)], self._first_touch(wg), self._slabs_for(rows, self._tiles(d, cd)))
+        ops.gemm(GEMM_NN, ga, self._w("fp_w"), dfln)
+        self._ln_bwd(st1, feat, dfln, dfeat, "fp_ln_w", (self.fp_ln_w.grad, self.fp_ln_b.grad))    # dfeat is not kept: the conv stack is frozen
+
+    def _backward(self, wave: torch.Tensor, keep: torch.Tensor, feat: Optional[torch.Tensor], first: int, pos_w: torch.Tensor,
+                  dout: torch.Tensor) -> None:
+        """for the gradient ``dout`` (N, T, d) f32 of the result: the gradients of layers ``first`` .. L - 1 and, with ``feat`` (the
+        saved input of the feature LayerNorm: the front end trains), of the front end, added into their ``.grad``.  ``keep``: the
+        saved inputs of the layers from ``first`` up, ``pos_w``: the positional weight the forward used"""
+        c, d, dev = self.config, self.config.hidden_size, wave.device
+        if ops.fp32_mode():
+            raise RuntimeError("NativeWav2Vec2 runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        N, Lw = wave.shape
+        T, L, front = self.frames(Lw), c.num_hidden_layers, feat is not None
+        ws, g = self._workspace(dev, Lw), self._grad_workspace(dev, Lw)
+        if front:
+            pos_wt = self._pos_weight(transposed=True)
+            g["dpos"].zero_()
+        for n0 in range(0, N, self.chunk):
+            n = min(self.chunk, N - n0)
+            rows = slice(n0 * T, (n0 + n) * T)
+            self._narrow(dout[n0:n0 + n], self._rows(g, "ga", n * T, d))
+            for i in reversed(range(first, L)):
+                self._layer_grad(i, ws, g, keep[i - first, rows], n, T, front or i > first)
+            if front:
+                self._front_grad(ws, g, feat[rows], pos_w, pos_wt, n, T)
+        if front:
+            lib.w2v_weightnorm_bwd(g["dpos"], self._f("pos_g"), self._f("pos_v"), self.pos_g.grad, self.pos_v.grad,
+                                   self._first_touch(self.pos_v.grad))

@@ -8,9 +8,9 @@ self-attention heads run on the HIP kernels (``mmfusion.ops``).
 
 The HuggingFace backbones themselves (DeBERTa-v3 / Wav2Vec2 / ViT, reference :20,116,179) are third-party pretrained
 models fetched by name.  All three have native forms on the HIP kernels that need no network (below), frozen by default.  The
-text backbone has the gradient with respect to its input embeddings, which is what prompt tuning needs; the text and the video
-backbone can train their top layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trainable_layers``); the
-audio one is forward only.  The encoders take a ``backbone`` argument:
+text backbone has the gradient with respect to its input embeddings, which is what prompt tuning needs; all three can train their top
+layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trainable_layers`` /
+``config.audio_backbone_trainable_layers``).  The encoders take a ``backbone`` argument:
   * ``backbone=None`` (default) reproduces the reference: ``from_pretrained(config.*_model_name)``;
   * any ``nn.Module`` returning an object with ``.last_hidden_state`` is used as is;
   * ``config.video_backbone = "native"`` (dynamic attribute, ``VideoEncoder`` only) builds ``mmfusion.vit.NativeViT``: the
@@ -18,7 +18,10 @@ audio one is forward only.  The encoders take a ``backbone`` argument:
     ``config.video_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers and the final
     LayerNorm then train, as the reference's optimiser trains ``video_encoder.vit``; ``"all"``: every layer and the embeddings;
   * ``config.audio_backbone = "native"`` (dynamic attribute, ``AudioEncoder`` only) builds ``mmfusion.wav2vec2.NativeWav2Vec2``
-    the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers);
+    the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers).  Frozen
+    unless ``config.audio_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers then
+    train; ``"all"``: every layer and the front end above the feature-extractor convolutions (feature projection, positional
+    convolution, encoder LayerNorm), which stay frozen as under HuggingFace's ``freeze_feature_encoder()``;
   * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
     same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
     on the prompt route, from input embeddings.  On that route, with grad mode on and ``prompt_embeddings.requires_grad``, the
@@ -95,7 +98,7 @@ def _backbone(config, kind: str, given: Optional[nn.Module]):
 
 def _run_backbone(fn, native: bool, *args, input_grad: bool = False, **kw):
     """``fn(*args, **kw)``, under ``no_grad`` iff the backbone is the native one: that one is frozen.  ``input_grad``: the caller
-    wants a gradient through it (``NativeDeberta`` with ``inputs_embeds``: the prompt route; or it or ``NativeViT`` with trainable
+    wants a gradient through it (``NativeDeberta`` with ``inputs_embeds``: the prompt route; or any native backbone with trainable
     top layers), so a native backbone is called in the caller's grad mode too"""
     with torch.no_grad() if native and not input_grad else contextlib.nullcontext():
         return fn(*args, **kw)
@@ -202,6 +205,12 @@ class AudioEncoder(_FusionBase):
         super().__init__()
         self.config = config
         self.model, self.hidden_size, self._native = _backbone(config, "audio", backbone)
+        if self._native:      # fine-tune the native backbone (NativeWav2Vec2.set_trainable_layers): the top k layers, "all": every
+            k = getattr(config, "audio_backbone_trainable_layers", 0)          # layer and the front end; 0: frozen
+            if k == "all":
+                self.model.set_trainable_layers(self.model.config.num_hidden_layers, front=True)
+            else:
+                self.model.set_trainable_layers(k)
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.temporal_attention = _MHAParams(self.hidden_size, 8)
         self.projection = nn.Linear(self.hidden_size, config.fusion_hidden_size)
@@ -211,7 +220,8 @@ class AudioEncoder(_FusionBase):
         if self.model is None:                       # feature mode: waveform holds (B, T, hidden)
             seq = waveform
         else:
-            seq = _run_backbone(self.model, self._native, waveform).last_hidden_state
+            tuned = self._native and self.model.trainable_layers > 0          # the backbone's own parameters train
+            seq = _run_backbone(self.model, self._native, waveform, input_grad=tuned).last_hidden_state
         if use_adapter and self.adapter is not None:
             seq = self.adapter(seq)
         projected, attended, weights = _mha_mean_project(self.temporal_attention, self.projection, seq,

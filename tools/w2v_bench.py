@@ -9,7 +9,13 @@
   * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE): time, share,
     TFLOP/s where the wrapper counts operations.
 
+  * with --finetune K|all, instead: forward + backward of ``set_trainable_layers(K)`` (``all``: every layer and the front end)
+    against the frozen forward, the per-kernel table of one step, stock-torch bf16 autograd through the same restatement with the
+    same tensors as leaves, and (``all``) each kernel of the positional convolution's backward on one chunk beside the forward
+    ``mmf_w2v_posconv``, which does the same FLOPs.
+
     python tools/w2v_bench.py [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--no-torch]
+                              [--finetune K|all]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
 import json
 
@@ -28,10 +34,88 @@ def gflop_per_clip(cfg, L: int) -> dict:
             "total": round((conv + pos + layers) / 1e9, 2)}
 
 
+def posconv_kernels(model, n: int, T: int, steps: int, warmup: int) -> dict:
+    """each kernel of the positional convolution's backward on one chunk of ``n`` clips, ms and its ratio to the forward kernel"""
+    from mmfusion import lib
+    c = model.config
+    d, G, k = c.hidden_size, c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
+    g = torch.Generator().manual_seed(3)
+    x, dy = (torch.randn(n, T, d, generator=g).cuda().to(torch.bfloat16) for _ in range(2))
+    y, dz = torch.empty_like(x), torch.empty_like(x)
+    w, wt, b = model._pos_weight(), model._pos_weight(transposed=True), model._f("pos_b")
+    S = model._pos_wgrad_slabs(n, T)
+    dw = torch.zeros(d, model.pos_kp, device="cuda")
+    partial = torch.empty(S, d * model.pos_kp, device="cuda")
+
+    def wgrad():
+        if S > 1:
+            lib.w2v_posconv_wgrad(dz, x, partial, n, T, d, G, k, slabs=S)
+            lib.sum_slabs(partial, dw.view(-1), True)
+        else:
+            lib.w2v_posconv_wgrad(dz, x, dw, n, T, d, G, k, accumulate=True)
+    runs = {"posconv": lambda: lib.w2v_posconv(x, w, b, y, n, T, d, G, k),
+            "posconv_bwd_act": lambda: lib.w2v_posconv_bwd_act(x, w, b, dy, dz, n, T, d, G, k),
+            "posconv_dgrad": lambda: lib.w2v_posconv_dgrad(dz, wt, dy, y, n, T, d, G, k),
+            "posconv_wgrad": wgrad,
+            "weightnorm_bwd": lambda: lib.w2v_weightnorm_bwd(dw, model._f("pos_g"), model._f("pos_v"), torch.zeros_like(model.pos_g),
+                                                            torch.empty_like(model.pos_v), True)}
+    ms = {name: time_eager(fn, 4 * steps, warmup) for name, fn in runs.items()}
+    out = {name: {"ms": round(v, 4), "over_forward_kernel": round(v / ms["posconv"], 3)} for name, v in ms.items()}
+    out["wgrad_slabs"], out["gflop"] = S, round(2.0 * n * T * d * (d // G) * k / 1e9, 1)
+    return out
+
+
+def finetune(args, model, cfg, sd, x) -> dict:
+    import w2v_ref
+    from mmfusion import arena, wav2vec2
+    N, L, d = args.clips, cfg.num_hidden_layers, cfg.hidden_size
+    front = args.finetune == "all"
+    k = L if front else int(args.finetune)
+    T = model.frames(args.samples)
+    res = {"model": "wav2vec2-base, bf16 storage", "clips": N, "samples": args.samples, "frames": T, "chunk": model.chunk,
+           "trainable_layers": k, "front": front}
+    with torch.no_grad():
+        res["forward_ms"] = round(time_eager(lambda: model(x), args.steps, args.warmup), 3)
+    model.set_trainable_layers(k, front=front)
+    arena.ensure(model).zero_grad()
+    dout = torch.randn(N, T, d, generator=torch.Generator().manual_seed(2)).cuda()
+
+    def step():
+        model(x).last_hidden_state.backward(dout)
+    fwd = time_eager(lambda: model(x), args.steps, args.warmup)
+    both = time_eager(step, args.steps, args.warmup)
+    res["differentiable_forward_ms"], res["forward_backward_ms"] = round(fwd, 3), round(both, 3)
+    res["forward_backward_ratio"] = round(both / res["forward_ms"], 3)
+    res["saved_inputs_mb"] = round((k * d + (cfg.conv_dim[-1] if front else 0)) * N * T * 2 / 2 ** 20, 1)
+    res["grad_workspace_mb_per_clip"] = round(model.grad_workspace_bytes_per_clip(args.samples) / 2 ** 20, 2)
+    res["kernels"] = kernel_table(step)
+    print_table(res["kernels"])
+    if front:
+        res["posconv_kernels"] = posconv_kernels(model, min(model.chunk, N), T, args.steps, args.warmup)
+    if not args.no_torch:
+        model._ws = model._gws = model._slabs = None
+        torch.cuda.empty_cache()
+        keys = {n for n in sd if any(n.startswith(f"encoder.layers.{i}.") for i in range(L - k, L))
+                or (front and n.startswith(("feature_projection.", "encoder.pos_conv_embed.", "encoder.layer_norm.")))}
+        leaves = {n: v.cuda().to(torch.bfloat16).requires_grad_(n in keys) for n, v in sd.items()}
+        x16, d16, c = x.to(torch.bfloat16), dout.to(torch.bfloat16), wav2vec2.DEFAULT_CHUNK
+
+        def stock(backward):
+            for i in range(0, N, c):
+                out = w2v_ref.w2v_forward(leaves, x16[i:i + c], cfg, dtype=torch.bfloat16, sdpa=True)
+                if backward:
+                    out.backward(d16[i:i + c])
+        res["torch_bf16_forward_ms"] = round(time_eager(lambda: stock(False), args.steps, args.warmup), 3)
+        res["torch_bf16_forward_backward_ms"] = round(time_eager(lambda: stock(True), args.steps, args.warmup), 3)
+        res["speedup_forward_backward"] = round(res["torch_bf16_forward_backward_ms"] / both, 3)
+    return res
+
+
 def main():
     ap = parser(steps=5, warmup=2, torch_yardstick=True)
     ap.add_argument("--clips", type=int, default=16)
     ap.add_argument("--samples", type=int, default=160000)
+    ap.add_argument("--finetune", default=None, metavar="K|all")
     args = ap.parse_args()
     import w2v_ref
     from mmfusion import wav2vec2
@@ -42,6 +126,9 @@ def main():
     model = model.cuda().eval()
     N, L = args.clips, args.samples
     x = (0.5 * torch.randn(N, L, generator=torch.Generator().manual_seed(1))).cuda()
+    if args.finetune is not None:
+        print(json.dumps(finetune(args, model, cfg, sd, x)))
+        return
     gf = gflop_per_clip(cfg, L)
 
     def rate(ms: float) -> dict:
