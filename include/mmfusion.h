@@ -764,7 +764,8 @@ int mmf_w2v_weightnorm_bwd(const float* dw, const float* g, const float* v, floa
 /* ------------------------------------------------------------------------------------------
  * Frozen DeBERTa-v3 backbone (mmfusion/deberta.py; the reference runs HuggingFace's DebertaV2Model at models/encoders.py:20).
  * The linears, the LayerNorms and the MLP of a layer are the grouped kernels above; these are the pieces a DeBERTa has
- * beside them, forward and (with respect to the inputs only: prompt tuning through the frozen layers) backward.  All validate
+ * beside them, forward and backward (with respect to the inputs: prompt tuning through the frozen layers; to the position tables:
+ * fine-tuning the layers; to the embedding tables and their LayerNorms: full fine-tuning).  All validate
  * first and launch nothing on an error.  A mask is (n, T) as f32 (mask_kind 1, nonzero = keep) or
  * u8 (mask_kind 2), or NULL with mask_kind 0 for all ones.
  * ------------------------------------------------------------------------------------------ */
@@ -831,6 +832,31 @@ int mmf_deberta_attn_bwd_pos(const void* qkv_bf16, const void* posq_bf16, const 
  * aligned, dout 8-byte aligned. */
 int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, float eps, const void* mask, int mask_kind, const void* dout_bf16,
                           float* d_embeds, int64_t rows, int d, void* stream);
+/* Backward of mmf_deberta_embed on either route with the LayerNorm parameters' gradients (full fine-tuning).  The source row of
+ * row r is table[clamp(ids[r])] (ids given; the forward's clamp to [0, vocab)) or embeds[r] (embeds given); exactly one of the two.
+ *   d_rows (rows, d) f32  = (accumulate: +=) mask[r] * the LayerNorm input gradient of dout_bf16[r], as mmf_deberta_embed_bwd
+ *   dgamma [d] f32       += sum_r dout[r] * mask[r] * xhat[r]          dbeta [d] f32 += sum_r dout[r] * mask[r]
+ * On the embeds route without accumulate the d_rows bits are mmf_deberta_embed_bwd's for the same operands.  A row with mask 0
+ * is exactly 0 in d_rows (untouched with accumulate), adds nothing to dgamma / dbeta, and its source row is not read.  The column
+ * sums go through per-workgroup partial rows in `workspace` (mmf_deberta_embed_bwd_params_workspace_bytes(rows, d) bytes, f32; it
+ * need not be initialised and holds nothing afterwards) that a second launch adds in a fixed order: no floating-point atomics,
+ * bitwise repeatable.  Two launches.  mmf_deberta_embed's limits on d (else MMF_E_UNSUPPORTED); a null operand, both or neither
+ * of ids / embeds, or a workspace that is too small: MMF_E_SHAPE; table / embeds / gamma / d_rows / dgamma / dbeta / workspace not
+ * 16-byte aligned, dout or ids not 8-byte aligned: MMF_E_ALIGN.  Nothing is launched on an error. */
+size_t mmf_deberta_embed_bwd_params_workspace_bytes(int64_t rows, int d);
+int mmf_deberta_embed_bwd_params(const int64_t* ids, const float* embeds, const float* table, int vocab, const float* gamma, float eps,
+                                 const void* mask, int mask_kind, const void* dout_bf16, float* d_rows, int accumulate, float* dgamma,
+                                 float* dbeta, void* workspace, size_t workspace_bytes, int64_t rows, int d, void* stream);
+/* dtable[clamp(ids[r])] += d_rows[r] for the rows r with mask[r] != 0: ids int64 [rows] (mmf_deberta_embed's clamp), d_rows f32
+ * (rows, d), dtable f32 (vocab, d); a masked row is not read.  The first unmasked occurrence of a table row owns it: its wave adds
+ * the occurrences in ascending row order in registers and reads, adds to and writes the table row once, so every table element is
+ * written by one lane once per call, a table row no unmasked id names is not touched, and there are no floating-point atomics:
+ * bitwise repeatable.  Nothing is sorted and nothing synchronises with the host (the ids are read on the device only), so a
+ * captured graph replays correctly with other ids.  One wave sums all occurrences of an id: a very frequent id is the slow case.
+ * d % 4 == 0, d <= 1024, rows <= 2^30 (else MMF_E_UNSUPPORTED); a null operand: MMF_E_SHAPE; d_rows / dtable not 16-byte
+ * aligned or ids not 8-byte aligned: MMF_E_ALIGN. */
+int mmf_embedding_scatter_add_f32(const int64_t* ids, const void* mask, int mask_kind, const float* d_rows, float* dtable, int64_t rows,
+                                  int d, int vocab, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Input preparation (mmfusion/prep.py; the reference does this on the host per sample, data/dataset_loaders.py:95-261): what a

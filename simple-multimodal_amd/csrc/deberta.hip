@@ -7,6 +7,9 @@
 //           the attention backward: a delta pre-pass, a dQ pass and a dK/dV pass from one kernel body, without atomics.
 //   the same backward with the gradient of the position tables posQ | posK (fine-tuning the layer's q / k weights, which also
 //           project the relative embeddings): a template flag of the two passes and a fixed-order reduction kernel.
+//   full fine-tuning: the embedding backward with the LayerNorm parameters' gradients on either route (per-workgroup partial
+//           column sums added in a fixed order), and the scatter-add of gradient rows into the word-embedding table's gradient
+//           (the first occurrence of a table row owns it): no atomics in either.
 // What the forward and the backward must agree on is stated once, as file-local __device__ functions that take operands and
 // never the name of their caller: the score tile (db_idx / db_fill_idx, db_chunks, db_pos_rows, db_frag, db_score; ahead of the
 // forward kernel) and the embedding LayerNorm's row statistics (db_row_stats).  The backward's P is the forward's P because both
@@ -31,6 +34,9 @@ __device__ __forceinline__ float db_mask(const void* __restrict__ mask, int kind
 }
 
 __device__ __forceinline__ int db_clamp(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// the table row an id names: an id outside the table names its nearest row (the forward's gather, and what its gradient follows)
+__device__ __forceinline__ long long db_table_row(long long id, int vocab) { return id < 0 ? 0 : (id >= vocab ? vocab - 1 : id); }
 
 // ---- embeddings ---------------------------------------------------------------------------------------------
 // One wave per row; lane l owns columns 4 l + 256 k (k < 4, so d <= 1024), kept in registers between the two statistics
@@ -66,9 +72,7 @@ void deberta_embed_kernel(const long long* __restrict__ ids, const float* __rest
   if (row >= rows) return;
   const float* __restrict__ src;
   if (ids) {
-    long long id = ids[row];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);              // an id outside the table reads its nearest row, never past it
-    src = table + (size_t)id * d;
+    src = table + (size_t)db_table_row(ids[row], vocab) * d;       // an id outside the table reads its nearest row, never past it
   } else {
     src = embeds + (size_t)row * d;
   }
@@ -306,27 +310,24 @@ void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsig
 // ---- backward with respect to the inputs (prompt tuning through the frozen layers) --------------------------------
 // embeddings: d_embeds = mask[row] * the LayerNorm input gradient of the bf16 gradient dy of deberta_embed_kernel's output
 // (inputs_embeds route).  The row statistics are the forward's (db_row_stats); one wave per row, same lane map.
-__global__ __launch_bounds__(DB_THREADS)
-void deberta_embed_bwd_kernel(const float* __restrict__ embeds, const float* __restrict__ gamma, const void* __restrict__ mask,
-                              int mask_kind, const unsigned short* __restrict__ dy, float* __restrict__ dx, int rows, int d, float eps) {
-  const int row = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float* __restrict__ src = embeds + (size_t)row * d;
-  const float m = db_mask(mask, mask_kind, (size_t)row);
-  f32x4_t v[4];
-  const DbRowStats st = db_row_stats(src, lane, d, eps, v);
-  const float mean = st.mean, rstd = st.rstd;
-  // g = dy * mask * gamma (the gradient of the normalised value), xh the normalised value; s1 = sum g, s2 = sum g xh
-  f32x4_t g[4];
+// What the two embedding-backward kernels agree on, for one row: on entry v holds the lane's columns of the source row (what
+// db_row_stats left); on return v holds the normalised values xh, dyv the lane's columns of the bf16 gradient `dyrow`, g =
+// dy * gamma * mask (the gradient of the normalised value), and the result the row means s1 = mean g, s2 = mean g xh
+struct DbRowMeans { float s1, s2; };
+__device__ __forceinline__ DbRowMeans db_row_grad(const unsigned short* __restrict__ dyrow, const float* __restrict__ gamma, float m,
+                                                  float mean, float rstd, int lane, int d, f32x4_t (&v)[4], f32x4_t (&dyv)[4],
+                                                  f32x4_t (&g)[4]) {
   float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = 4 * lane + 256 * k;
     g[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    dyv[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     if (c < d) {
-      const u32x2_t w = *reinterpret_cast<const u32x2_t*>(dy + (size_t)row * d + c);
+      const u32x2_t w = *reinterpret_cast<const u32x2_t*>(dyrow + c);
       const f32x4_t gm = *reinterpret_cast<const f32x4_t*>(gamma + c);
-      g[k] = f32x4_t{bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])} * gm * m;
+      dyv[k] = f32x4_t{bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
+      g[k] = dyv[k] * gm * m;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         v[k][e] = (v[k][e] - mean) * rstd;
@@ -335,17 +336,172 @@ void deberta_embed_bwd_kernel(const float* __restrict__ embeds, const float* __r
       }
     }
   }
-  s1 = wave_sum(s1) / (float)d;
-  s2 = wave_sum(s2) / (float)d;
+  return {wave_sum(s1) / (float)d, wave_sum(s2) / (float)d};
+}
+
+// the lane's columns 4 lane + 256 k .. + 3 of the row's input gradient, rstd (g - s1 - xh s2); a masked row: exactly 0.  The fused
+// multiply-add is spelled out: left to the compiler's contraction, one kernel fused all four column groups and the other three and
+// a half of them, and the two kernels' bits must agree
+__device__ __forceinline__ f32x4_t db_row_dx(const f32x4_t& g, const f32x4_t& xh, float m, float rstd, DbRowMeans s) {
+  f32x4_t o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = m != 0.0f ? rstd * fmaf(-s.s2, xh[e], g[e] - s.s1) : 0.0f;
+  return o;
+}
+
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_embed_bwd_kernel(const float* __restrict__ embeds, const float* __restrict__ gamma, const void* __restrict__ mask,
+                              int mask_kind, const unsigned short* __restrict__ dy, float* __restrict__ dx, int rows, int d, float eps) {
+  const int row = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* __restrict__ src = embeds + (size_t)row * d;
+  const float m = db_mask(mask, mask_kind, (size_t)row);
+  f32x4_t v[4], dyv[4], g[4];
+  const DbRowStats st = db_row_stats(src, lane, d, eps, v);
+  const DbRowMeans s = db_row_grad(dy + (size_t)row * d, gamma, m, st.mean, st.rstd, lane, d, v, dyv, g);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = 4 * lane + 256 * k;
-    if (c < d) {
-      f32x4_t o;
+    if (c < d) *reinterpret_cast<f32x4_t*>(dx + (size_t)row * d + c) = db_row_dx(g[k], v[k], m, st.rstd, s);
+  }
+}
+
+// The same backward with the parameters' gradients (fine-tuning the embeddings), on either route of deberta_embed_kernel: the source
+// row is table[db_table_row(id)] or the row of embeds itself.  A workgroup's 4 waves walk the rows 4 b + wave, + 4 gridDim.x, ...,
+// one wave per row with the lane map above; d_rows (written, or added to with `accumulate`) has the bits of deberta_embed_bwd_kernel
+// for the same operands, by db_row_grad / db_row_dx.  Each lane keeps dgamma = sum dy mask xh and dbeta = sum dy mask of its
+// columns over the wave's rows in registers; the 4 waves combine through LDS in wave order and the workgroup leaves one row
+// [dgamma | dbeta] of partials in `part` (gridDim.x, 2 d): no atomics.  A row with mask 0 is not read: zeros (nothing with
+// `accumulate`) in d_rows and nothing in the sums.  deberta_embed_params_finalize_kernel adds the partial rows in order.
+constexpr int DB_PARAM_BLOCKS = 512;            // at most this many workgroups (= partial rows in the workspace)
+
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_embed_bwd_params_kernel(const long long* __restrict__ ids, const float* __restrict__ embeds, const float* __restrict__ table,
+                                     const float* __restrict__ gamma, const void* __restrict__ mask, int mask_kind,
+                                     const unsigned short* __restrict__ dy, float* __restrict__ dx, int accumulate,
+                                     float* __restrict__ part, int rows, int d, int vocab, float eps) {
+  __shared__ float red[2][3][1024];             // [dgamma | dbeta][waves 1 .. 3][column]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  f32x4_t dg[4], db[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = m != 0.0f ? rstd * (g[k][e] - s1 - v[k][e] * s2) : 0.0f;      // a masked row: exactly 0
-      *reinterpret_cast<f32x4_t*>(dx + (size_t)row * d + c) = o;
+  for (int k = 0; k < 4; ++k) { dg[k] = f32x4_t{0.f, 0.f, 0.f, 0.f}; db[k] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+  const long long step = (long long)gridDim.x * (DB_THREADS / MMF_WAVE);
+  for (long long row = (long long)blockIdx.x * (DB_THREADS / MMF_WAVE) + wave; row < rows; row += step) {
+    const float m = db_mask(mask, mask_kind, (size_t)row);
+    float* __restrict__ dst = dx + (size_t)row * d;
+    if (m == 0.0f) {
+      if (!accumulate) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int c = 4 * lane + 256 * k;
+          if (c < d) *reinterpret_cast<f32x4_t*>(dst + c) = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+      continue;
     }
+    const float* __restrict__ src = ids ? table + (size_t)db_table_row(ids[row], vocab) * d : embeds + (size_t)row * d;
+    f32x4_t v[4], dyv[4], g[4];
+    const DbRowStats st = db_row_stats(src, lane, d, eps, v);
+    const DbRowMeans s = db_row_grad(dy + (size_t)row * d, gamma, m, st.mean, st.rstd, lane, d, v, dyv, g);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = 4 * lane + 256 * k;
+      if (c < d) {
+        f32x4_t o = db_row_dx(g[k], v[k], m, st.rstd, s);
+        if (accumulate) o += *reinterpret_cast<const f32x4_t*>(dst + c);
+        *reinterpret_cast<f32x4_t*>(dst + c) = o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float dm = dyv[k][e] * m;
+          dg[k][e] = fmaf(dm, v[k][e], dg[k][e]);
+          db[k][e] += dm;
+        }
+      }
+    }
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = 4 * lane + 256 * k;
+      *reinterpret_cast<f32x4_t*>(&red[0][wave - 1][c]) = dg[k];
+      *reinterpret_cast<f32x4_t*>(&red[1][wave - 1][c]) = db[k];
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    float* __restrict__ out = part + (size_t)blockIdx.x * 2 * d;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = 4 * lane + 256 * k;
+      if (c < d) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+          dg[k] += *reinterpret_cast<const f32x4_t*>(&red[0][w][c]);
+          db[k] += *reinterpret_cast<const f32x4_t*>(&red[1][w][c]);
+        }
+        *reinterpret_cast<f32x4_t*>(out + c) = dg[k];
+        *reinterpret_cast<f32x4_t*>(out + d + c) = db[k];
+      }
+    }
+  }
+}
+
+// dgamma[c] += the sum over the `nblk` partial rows of column c, dbeta[c] += that of column d + c: one lane per column, the rows in
+// order through four running sums (independent loads in flight), combined in a fixed order
+__global__ __launch_bounds__(DB_THREADS)
+void deberta_embed_params_finalize_kernel(const float* __restrict__ part, float* __restrict__ dgamma, float* __restrict__ dbeta, int nblk, int d) {
+  const int col = blockIdx.x * DB_THREADS + threadIdx.x;
+  if (col >= 2 * d) return;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  int b = 0;
+  for (; b + 4 <= nblk; b += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] += part[(size_t)(b + u) * 2 * d + col];
+  }
+  for (; b < nblk; ++b) s[0] += part[(size_t)b * 2 * d + col];
+  float* __restrict__ dst = col < d ? dgamma + col : dbeta + (col - d);
+  *dst += (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// dtable[db_table_row(ids[r])] += d_rows[r] over the unmasked rows r, without atomics and without a sort: the first unmasked
+// occurrence of a table row owns it.  One wave per row p: it scans ids[0 .. p) 64 at a time (coalesced loads, one ballot per step) and
+// leaves if an earlier unmasked row names the same table row; otherwise it walks ids[p .. rows) the same way and adds the matching
+// unmasked rows to its registers in ascending row order (p itself first), then reads, adds to and writes the table row once.  Every
+// table element is written by one lane, once; a table row no unmasked id names is not touched; a masked row is never read.
+// The known cost is a very frequent id: one wave sums all its occurrences.
+__global__ __launch_bounds__(DB_THREADS)
+void embedding_scatter_add_kernel(const long long* __restrict__ ids, const void* __restrict__ mask, int mask_kind,
+                                  const float* __restrict__ d_rows, float* __restrict__ dtable, int rows, int d, int vocab) {
+  const int p = blockIdx.x * (DB_THREADS / MMF_WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (p >= rows) return;
+  if (db_mask(mask, mask_kind, (size_t)p) == 0.0f) return;
+  const long long own = db_table_row(ids[p], vocab);
+  auto names_own = [&](int q, int end) {
+    return q < end && db_mask(mask, mask_kind, (size_t)q) != 0.0f && db_table_row(ids[q], vocab) == own;
+  };
+  for (int q0 = 0; q0 < p; q0 += MMF_WAVE)
+    if (__ballot(names_own(q0 + lane, p))) return;             // (wave-uniform) an earlier row owns this table row
+  f32x4_t acc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  for (int q0 = p; q0 < rows; q0 += MMF_WAVE) {
+    unsigned long long hits = __ballot(names_own(q0 + lane, rows));
+    while (hits) {
+      const int j = __ffsll((long long)hits) - 1;
+      hits &= hits - 1;
+      const float* __restrict__ src = d_rows + (size_t)(q0 + j) * d;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = 4 * lane + 256 * k;
+        if (c < d) acc[k] += *reinterpret_cast<const f32x4_t*>(src + c);
+      }
+    }
+  }
+  float* __restrict__ dst = dtable + (size_t)own * d;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 4 * lane + 256 * k;
+    if (c < d) *reinterpret_cast<f32x4_t*>(dst + c) = *reinterpret_cast<const f32x4_t*>(dst + c) + acc[k];
   }
 }
 
@@ -859,6 +1015,65 @@ extern "C" int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, fl
     MMF_FAIL(MMF_E_ALIGN, "%s: embeds / gamma / d_embeds must be 16-byte aligned, dout 8-byte aligned", fn);
   hipLaunchKernelGGL(deberta_embed_bwd_kernel, grid, dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
                      embeds, gamma, mask, mask_kind, static_cast<const unsigned short*>(dout_bf16), d_embeds, (int)rows, d, eps);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+namespace {
+
+int db_param_blocks(int64_t rows) {
+  const int64_t per = DB_THREADS / MMF_WAVE, blocks = (rows + per - 1) / per;
+  return (int)(blocks < DB_PARAM_BLOCKS ? blocks : DB_PARAM_BLOCKS);
+}
+
+}  // namespace
+
+extern "C" size_t mmf_deberta_embed_bwd_params_workspace_bytes(int64_t rows, int d) {
+  return rows > 0 && d > 0 ? (size_t)db_param_blocks(rows) * 2 * (size_t)d * sizeof(float) : 0;
+}
+
+extern "C" int mmf_deberta_embed_bwd_params(const int64_t* ids, const float* embeds, const float* table, int vocab, const float* gamma,
+                                            float eps, const void* mask, int mask_kind, const void* dout_bf16, float* d_rows,
+                                            int accumulate, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                            int64_t rows, int d, void* stream) {
+  const char* fn = "mmf_deberta_embed_bwd_params";
+  if ((ids == nullptr) == (embeds == nullptr)) MMF_FAIL(MMF_E_SHAPE, "%s: exactly one of ids / embeds", fn);
+  if (!gamma || !dout_bf16 || !d_rows || !dgamma || !dbeta || !workspace || (ids && !table) || rows <= 0 || d <= 0 || (ids && vocab <= 0))
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand or rows=%lld d=%d vocab=%d", fn, (long long)rows, d, vocab);
+  dim3 grid;
+  if (int rc = db_embed_rows(fn, rows, d, mask, mask_kind, &grid)) return rc;
+  const size_t need = mmf_deberta_embed_bwd_params_workspace_bytes(rows, d);
+  if (workspace_bytes < need)
+    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes, %zu needed (mmf_deberta_embed_bwd_params_workspace_bytes)", fn, workspace_bytes, need);
+  if (!mmf_aligned16(gamma) || !mmf_aligned16(d_rows) || !mmf_aligned16(dgamma) || !mmf_aligned16(dbeta) || !mmf_aligned16(workspace)
+      || (ids && !mmf_aligned16(table)) || (embeds && !mmf_aligned16(embeds)) || (reinterpret_cast<uintptr_t>(dout_bf16) & 7u)
+      || (reinterpret_cast<uintptr_t>(ids) & 7u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: table / embeds / gamma / d_rows / dgamma / dbeta / workspace must be 16-byte aligned, dout and ids 8-byte aligned", fn);
+  const int nblk = db_param_blocks(rows);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(deberta_embed_bwd_params_kernel, dim3(nblk), dim3(DB_THREADS), 0, s, reinterpret_cast<const long long*>(ids), embeds, table,
+                     gamma, mask, mask_kind, static_cast<const unsigned short*>(dout_bf16), d_rows, accumulate ? 1 : 0, part, (int)rows, d,
+                     vocab, eps);
+  MMF_CHECK_LAUNCH(fn);
+  hipLaunchKernelGGL(deberta_embed_params_finalize_kernel, dim3((2 * d + DB_THREADS - 1) / DB_THREADS), dim3(DB_THREADS), 0, s,
+                     static_cast<const float*>(part), dgamma, dbeta, nblk, d);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_embedding_scatter_add_f32(const int64_t* ids, const void* mask, int mask_kind, const float* d_rows, float* dtable,
+                                             int64_t rows, int d, int vocab, void* stream) {
+  const char* fn = "mmf_embedding_scatter_add_f32";
+  if (!ids || !d_rows || !dtable || rows <= 0 || d <= 0 || vocab <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand or rows=%lld d=%d vocab=%d", fn, (long long)rows, d, vocab);
+  if (rows > ((int64_t)1 << 30)) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: rows=%lld (at most 2^30)", fn, (long long)rows);
+  dim3 grid;
+  if (int rc = db_embed_rows(fn, rows, d, mask, mask_kind, &grid)) return rc;
+  if (!mmf_aligned16(d_rows) || !mmf_aligned16(dtable) || (reinterpret_cast<uintptr_t>(ids) & 7u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: d_rows / dtable must be 16-byte aligned, ids 8-byte aligned", fn);
+  hipLaunchKernelGGL(embedding_scatter_add_kernel, grid, dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const long long*>(ids), mask, mask_kind, d_rows, dtable, (int)rows, d, vocab);
   MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }

@@ -78,7 +78,23 @@ LayerNorm(rel_embeddings): the f32 (2S, 2d) gradient of posQ | posK is summed ov
 forward stores the tables) and two TN GEMMs against ``rel`` add ``dW_qkv[:2d] += dpos^T rel`` and ``db_q += colsum(dposQ)``
 (``colsum(dposK)`` is zero in exact arithmetic, the rows of dS summing to zero, so ``db_k`` takes none).
 A trainable layer's tables are computed in every call (the optimiser writes weights through raw pointers: no version counter
-moves).  ``rel_embeddings``, the encoder LayerNorm, the word embeddings and the embedding LayerNorm stay frozen.
+moves).  ``rel_embeddings``, the encoder LayerNorm, the word embeddings and the embedding LayerNorm stay frozen in this mode.
+
+All weights.  ``set_trainable_layers(L, embeddings=True)`` trains those four as well (six tensors): every layer already runs the
+position path, and the walk goes down to layer 0 with its input gradient.  Per chunk, after layer 0,
+
+      ids route     mmf_deberta_embed_bwd_params (ids, table)    gx -> the gathered rows' f32 gradient; emb LN dgamma / dbeta += ...
+                    mmf_embedding_scatter_add_f32                those rows -> word_emb.grad (masked tokens skipped)
+      embeds route  mmf_deberta_embed_bwd_params (embeds)        gx -> d inputs_embeds (mmf_deberta_embed_bwd's bits); dgamma / dbeta
+
+and after the last chunk the position path continues below posQ | posK: d rel = sum over the layers of bf16(dpos_i) W_qk,i, one NN
+GEMM per layer adding into one f32 (2S, d) buffer in stream order; rounded to bf16 once (``rel`` is stored as bf16), then
+``mmf_deberta_embed_bwd_params`` on the relative table adds into ``rel_emb.grad`` and the encoder LayerNorm's gradients.  Neither
+kernel uses atomics: the column sums go through per-workgroup partials added in a fixed order, and the scatter's first occurrence
+of a table row owns it.  ``rel`` is then computed in every call too (nothing derived from a trainable tensor is cached).  The table
+gradients are plain accumulating regions of the arena (never first-touch managed: a scatter cannot overwrite the rows it does not
+visit), so ``zero_grad`` clears them by memset.  On the prompt route ``embeddings.word_embeddings(input_ids)`` carries a graph in
+this mode and its backward scatters the gradient of ``inputs_embeds`` into the table.
 """
 from __future__ import annotations
 
@@ -117,9 +133,29 @@ def bucket_index(T: int, S: int, max_position: int) -> torch.Tensor:
     return torch.clamp(log_bucket(delta, S, max_position) + S, 0, 2 * S - 1).to(torch.int32)
 
 
+class _Gather(torch.autograd.Function):
+    """``word_emb[ids]`` with the table as an input, so that the result carries a graph; the table's gradient is not returned
+    but added into its f32 ``.grad`` by ``mmf_embedding_scatter_add_f32`` (no mask: the reference's embedding has none)"""
+
+    @staticmethod
+    def forward(ctx, model: "NativeDeberta", ids: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+        _arena.ensure(model)
+        ctx.model = model
+        ctx.save_for_backward(ids)
+        return torch.nn.functional.embedding(ids, table.detach())
+
+    @staticmethod
+    def backward(ctx, grad: torch.Tensor):
+        (ids,) = ctx.saved_tensors
+        lib.embedding_scatter_add(ids.reshape(-1).contiguous(), grad.contiguous().view(-1, grad.shape[-1]), ctx.model.word_emb.grad)
+        return None, None, None
+
+
 class _WordEmbeddings:
-    """``model.embeddings.word_embeddings``: ids -> f32 embeddings without autograd (``TextEncoder``'s prompt route calls it
-    and hands the result back as ``inputs_embeds``).  Not an ``nn.Module``: the table is the backbone's own parameter."""
+    """``model.embeddings.word_embeddings``: ids -> f32 embeddings (``TextEncoder``'s prompt route calls it and hands the result
+    back as ``inputs_embeds``); without autograd unless the table trains (``set_trainable_layers(L, embeddings=True)``) and grad
+    mode is on: then the result carries a graph whose backward adds into ``word_emb.grad``.  Not an ``nn.Module``: the table is
+    the backbone's own parameter."""
 
     def __init__(self, owner: "NativeDeberta"):
         self._owner = [owner]                          # (a list: the backbone must not become a submodule of its own attribute)
@@ -129,26 +165,34 @@ class _WordEmbeddings:
         return self._owner[0].word_emb.detach()
 
     def __call__(self, input_ids: torch.Tensor) -> torch.Tensor:
+        owner = self._owner[0]
+        if torch.is_grad_enabled() and owner.word_emb.requires_grad:
+            if not input_ids.is_cuda or input_ids.dtype != torch.int64:
+                raise TypeError("NativeDeberta: the trainable word embeddings take int64 ids on the GPU (no CPU fallback)")
+            return _Gather.apply(owner, input_ids, owner.word_emb)
         with torch.no_grad():
             return torch.nn.functional.embedding(input_ids, self.weight)
 
 
 class _Differentiable(torch.autograd.Function):
-    """``NativeDeberta._run``, differentiable with respect to ``inputs_embeds`` and to the parameters of the trainable layers.
-    ``params`` are those parameters: they are inputs so that the result carries a graph on the ids route too; their gradients
-    are not returned but added into their f32 ``.grad`` by the backward's own launches, as ``ops.queue_wgrad``'s are."""
+    """``NativeDeberta._run``, differentiable with respect to ``inputs_embeds`` and to the parameters of the trainable layers
+    and, with them all, the embedding-side parameters.  ``params`` are those parameters: they are inputs so that the result
+    carries a graph on the ids route too; their gradients are not returned but added into their f32 ``.grad`` by the backward's
+    own launches, as ``ops.queue_wgrad``'s are."""
 
     @staticmethod
     def forward(ctx, model: "NativeDeberta", src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, *params) -> torch.Tensor:
         N, T = src.shape[:2]
         L, d = model.config.num_hidden_layers, model.config.hidden_size
         need_in = not by_ids and ctx.needs_input_grad[1]
-        first = 0 if need_in else L - model.trainable_layers          # the lowest layer the backward walks
+        emb = model.trainable_embeddings
+        first = 0 if need_in or emb else L - model.trainable_layers   # the lowest layer the backward walks
         keep = torch.empty((L - first, N * T, d), dtype=BF16, device=src.device)
         _arena.ensure(model)
-        pos = model._pos_tables(src.device)
+        rel, pos = model._pos_state(src.device)
         out = model._run(src, mask, by_ids, keep, first, pos)
         ctx.model, ctx.mask, ctx.by_ids, ctx.first, ctx.pos, ctx.k = model, mask, by_ids, first, pos, model.trainable_layers
+        ctx.rel, ctx.emb = rel, emb
         ctx.save_for_backward(src, keep)
         return out
 
@@ -159,7 +203,8 @@ class _Differentiable(torch.autograd.Function):
         k = ctx.k if any(ctx.needs_input_grad[4:]) else 0         # (torch.autograd.grad for the embeddings alone: no weight gradients)
         grad = None
         if need_in or k:
-            grad = ctx.model._backward(src, ctx.by_ids, ctx.mask, keep, ctx.first, ctx.pos, dout.contiguous(), need_in, k)
+            grad = ctx.model._backward(src, ctx.by_ids, ctx.mask, keep, ctx.first, ctx.pos, ctx.rel, dout.contiguous(), need_in, k,
+                                       ctx.emb and k > 0)
         return (None, grad, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
 
 
@@ -231,22 +276,36 @@ class NativeDeberta(FrozenBackbone):
         add("enc_ln_b", (d,), "encoder.LayerNorm.bias", std=0.0)
         self.embeddings = types.SimpleNamespace(word_embeddings=_WordEmbeddings(self))
         self._idx: Dict[Tuple, torch.Tensor] = {}      # (T, S, max position, device) -> the int32 table on that device
+        self._embeddings = False                       # set_trainable_layers(L, embeddings=True)
 
-    # -- fine-tuning the top layers ----------------------------------------------------------------------
-    def set_trainable_layers(self, k: int) -> None:
+    # -- fine-tuning -------------------------------------------------------------------------------------
+    _EMBEDDING_PARAMS = ("word_emb", "emb_ln_w", "emb_ln_b", "rel_emb", "enc_ln_w", "enc_ln_b")
+
+    @property
+    def trainable_embeddings(self) -> bool:
+        return self._embeddings
+
+    def set_trainable_layers(self, k: int, embeddings: bool = False) -> None:
         """The parameters of the top ``k`` layers (``L - k .. L - 1``) get ``requires_grad = True``, every other parameter
-        ``False``; 0 freezes the backbone again.  With grad mode on and ``k > 0`` a call returns a result that carries a graph,
-        and its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops below
-        layer ``L - k`` unless ``inputs_embeds`` needs a gradient too.  Out of scope, frozen whatever ``k``: ``rel_embeddings``,
-        the encoder LayerNorm, the word embeddings and the embedding LayerNorm (their gradient would need every layer's
-        position path).  The backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
+        ``False``; 0 freezes the backbone again.  ``embeddings=True`` (with ``k == L`` only: their gradient comes through every
+        layer, the relative embeddings' through every layer's position path) also trains the word embeddings, the embedding
+        LayerNorm, ``rel_embeddings`` and the encoder LayerNorm: every parameter, as the reference's optimiser trains the model.
+        With grad mode on and ``k > 0`` a call returns a result that carries a graph, and its backward adds those parameters'
+        gradients into their f32 ``.grad`` (the module's parameter arena) and stops below layer ``L - k`` unless ``inputs_embeds``
+        or the embeddings need a gradient too.  Without ``embeddings`` the six embedding-side tensors stay frozen whatever ``k``.
+        The backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
         L = self.config.num_hidden_layers
         if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
             raise ValueError(f"NativeDeberta: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
-        self._trainable = k
-        top = {n for i in range(L - k, L) for n in self._layer_params(i)}
+        if not isinstance(embeddings, bool) or (embeddings and k != L):
+            raise ValueError(f"NativeDeberta: set_trainable_layers({k!r}, embeddings={embeddings!r}): the embeddings train with all "
+                             f"{L} layers only (their gradient comes through every layer)")
+        if self._embeddings and not embeddings:        # (steps taken while ``rel_embeddings`` trained moved no version counter)
+            self._cache.pop("pos", None)
+        self._trainable, self._embeddings = k, embeddings
+        names = {n for i in range(L - k, L) for n in self._layer_params(i)} | set(self._EMBEDDING_PARAMS if embeddings else ())
         for name, p in self.named_parameters(recurse=False):
-            p.requires_grad_(name in top)
+            p.requires_grad_(name in names)
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -313,7 +372,8 @@ class NativeDeberta(FrozenBackbone):
     # -- weights ----------------------------------------------------------------------------------------
     def _pos_cache(self, dev) -> tuple:
         """(LayerNorm(rel_embeddings) as bf16 (2S, d), [(posQ, posK) of every FROZEN layer]): what depends on frozen weights only,
-        one mmf_deberta_embed launch on the relative table and one GEMM per frozen layer, once per weight version"""
+        one mmf_deberta_embed launch on the relative table and one GEMM per frozen layer, once per weight version.  With the
+        embeddings trainable ``rel`` itself is computed in every call and no layer is frozen: the rule ``_pos_tables`` states"""
         c = self.config
         frozen = c.num_hidden_layers - self._trainable
 
@@ -321,11 +381,11 @@ class NativeDeberta(FrozenBackbone):
             rel = torch.empty((2 * c.position_buckets, c.hidden_size), dtype=BF16, device=dev)
             lib.deberta_embed(rel, None, self._f("enc_ln_w"), self._f("enc_ln_b"), c.layer_norm_eps, embeds=self._f("rel_emb"))
             return rel, [self._pos_of(i, rel) for i in range(frozen)]
+        if self._embeddings:
+            with torch.no_grad():
+                return build()
         names = ["rel_emb", "enc_ln_w", "enc_ln_b"] + [f"l{i}_qkv_{s}" for i in range(frozen) for s in "wb"]
         return self._derived("pos", names, build)
-
-    def _rel(self, dev) -> torch.Tensor:
-        return self._pos_cache(dev)[0]
 
     def _pos_of(self, i: int, rel: torch.Tensor) -> tuple:
         d = self.config.hidden_size
@@ -336,10 +396,15 @@ class NativeDeberta(FrozenBackbone):
     def _pos_tables(self, dev) -> list:
         """per layer (posQ, posK) = the layer's q / k projection (bias included) of LayerNorm(rel_embeddings): bf16 (2S, d) views
         of one (2S, 2d) GEMM output.  A frozen layer's are computed once per weight version.  A trainable layer's are computed in
-        every call, from the cached frozen ``rel``: the optimiser writes masters and shadows through raw pointers, which moves
-        no version counter, so nothing derived from a trainable weight may be cached"""
+        every call, from ``rel`` (cached while ``rel_embeddings`` and the encoder LayerNorm are frozen): the optimiser writes
+        masters and shadows through raw pointers, which moves no version counter, so nothing derived from a trainable weight
+        may be cached"""
+        return self._pos_state(dev)[1]
+
+    def _pos_state(self, dev) -> tuple:
+        """(``rel`` = LayerNorm(rel_embeddings) as bf16 (2S, d), ``_pos_tables``' list computed from it)"""
         rel, pos = self._pos_cache(dev)
-        return list(pos) + [self._pos_of(i, rel) for i in range(len(pos), self.config.num_hidden_layers)]
+        return rel, list(pos) + [self._pos_of(i, rel) for i in range(len(pos), self.config.num_hidden_layers)]
 
     # -- launches ---------------------------------------------------------------------------------------
     def _layer(self, i: int, ws, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor]) -> None:
@@ -377,6 +442,8 @@ class NativeDeberta(FrozenBackbone):
         if torch.is_grad_enabled() and (self._trainable > 0 or (inputs_embeds is not None and inputs_embeds.requires_grad)):
             L = c.num_hidden_layers
             params = [getattr(self, n) for i in range(L - self._trainable, L) for n in self._layer_params(i)]
+            if self._embeddings:
+                params += [getattr(self, n) for n in self._EMBEDDING_PARAMS]
             return BackboneOutput(_Differentiable.apply(self, src, mask, input_ids is not None, *params))
         return BackboneOutput(self._run(src, mask, input_ids is not None))
 
@@ -452,12 +519,25 @@ class NativeDeberta(FrozenBackbone):
         if below:
             ops.gemm(GEMM_NN, dqkv, self._w(f"l{i}_qkv_w"), ga, aux=gb, epilogue=EPI_ADD_AUX)    # ga = dx: the attention branch + the residual
 
+    def _embed_workspace(self, g: dict, rows: int, d_rows: bool) -> tuple:
+        """(``mmf_deberta_embed_bwd_params``' workspace for up to ``rows`` rows, with ``d_rows`` an f32 (rows, d) buffer for the
+        rows' gradient where the caller has none), kept beside the backward's buffers and grown on demand"""
+        d = self.config.hidden_size
+        need = lib.deberta_embed_bwd_params_workspace_bytes(rows, d) // 4
+        w, r = g.get("emb_ws"), g.get("d_rows")
+        if w is None or w.numel() < need:
+            w = g["emb_ws"] = torch.empty(need, dtype=torch.float32, device=g["dev"])
+        if d_rows and (r is None or r.numel() < rows * d):
+            r = g["d_rows"] = torch.empty(rows * d, dtype=torch.float32, device=g["dev"])
+        return w, r[:rows * d].view(rows, d) if d_rows else None
+
     def _backward(self, src: torch.Tensor, by_ids: bool, mask: Optional[torch.Tensor], keep: torch.Tensor, first: int, pos: list,
-                  dout: torch.Tensor, need_in: bool, k: int) -> Optional[torch.Tensor]:
+                  rel: torch.Tensor, dout: torch.Tensor, need_in: bool, k: int, emb: bool = False) -> Optional[torch.Tensor]:
         """for the gradient ``dout`` (N, T, d) f32 of the result: with ``need_in``, -> d ``inputs_embeds`` (N, T, d) f32; with
-        ``k > 0``, the gradients of the top ``k`` layers' parameters, added into their ``.grad``.  ``keep``: the saved inputs of
-        the layers from ``first`` up, ``pos``: the position tables the forward used.  Without ``need_in`` the walk ends with
-        layer ``first``'s weight gradients"""
+        ``k > 0``, the gradients of the top ``k`` layers' parameters, added into their ``.grad``; with ``emb`` (``k == L``), also
+        those of the six embedding-side parameters.  ``keep``: the saved inputs of the layers from ``first`` up, ``pos`` / ``rel``:
+        the position tables the forward used and the normalised relative embeddings they were made from.  Without ``need_in``
+        and ``emb`` the walk ends with layer ``first``'s weight gradients"""
         c, d, dev = self.config, self.config.hidden_size, src.device
         N, T = src.shape[:2]
         L, S2 = c.num_hidden_layers, 2 * c.position_buckets
@@ -476,12 +556,24 @@ class NativeDeberta(FrozenBackbone):
             self._narrow(dout[n0:n0 + n], ga)
             for i in reversed(range(first, L)):
                 self._layer_grad(i, ws, g, keep[i - first, rows], n, T, pos[i], idx, m, dpos[i - (L - k)] if i >= L - k else None,
-                                 need_in or i > first)
-            if need_in:
+                                 need_in or emb or i > first)
+            if emb:
+                # the embedding LayerNorm's parameters, and the word embeddings: the gathered rows' gradient (a buffer of the
+                # backward's), scattered into the table's; on the embeds route the rows' gradient is d inputs_embeds itself
+                gamma, into = self._f("emb_ln_w"), (self.emb_ln_w.grad, self.emb_ln_b.grad)
+                wsp, d_rows = self._embed_workspace(g, n * T, by_ids or not need_in)
+                if by_ids:
+                    ids = src[n0:n0 + n].reshape(-1)
+                    lib.deberta_embed_bwd_params(gamma, c.layer_norm_eps, m, ga, d_rows, *into, wsp, ids=ids, table=self._f("word_emb"))
+                    lib.embedding_scatter_add(ids, d_rows, self.word_emb.grad, mask=m)
+                else:
+                    lib.deberta_embed_bwd_params(gamma, c.layer_norm_eps, m, ga, grad[n0:n0 + n].view(n * T, d) if need_in else d_rows,
+                                                 *into, wsp, embeds=src[n0:n0 + n])
+            elif need_in:
                 lib.deberta_embed_bwd(src[n0:n0 + n], self._f("emb_ln_w"), c.layer_norm_eps, m, ga, grad[n0:n0 + n])
         if k:
             # the position path: posQ | posK = rel W_qk^T + b_qk is stored as bf16, so its gradient is rounded to bf16 there, once
-            rel, dp16 = self._rel(dev), ops.cast_to_bf16(dpos.view(k * S2, 2 * d)).view(k, S2, 2 * d)
+            dp16 = ops.cast_to_bf16(dpos.view(k * S2, 2 * d)).view(k, S2, 2 * d)
             # db_q += colsum(dposQ); db_k takes no column sum: sum_r dposK[r] = sum_i (sum_j dS_ij) Q_i, and a softmax backward's
             # dS rows sum to zero, so the exact term is 0 and what the kernel's dposK sums to is rounding residue alone (delta
             # comes from the bf16 O: each row of dS sums to dO_i . (O_i - bf16(O_i)), the residue colsum(dK) carries once already)
@@ -489,4 +581,17 @@ class NativeDeberta(FrozenBackbone):
                 w, b, dp = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad, dp16[i - (L - k)]
                 ops.gemm_group(GEMM_TN, [(dp[:, :d], rel, w[:d], b[:d], None)], EPI_ACCUM | EPI_COLSUM_A)
                 ops.gemm_group(GEMM_TN, [(dp[:, d:], rel, w[d:2 * d], None, None)], EPI_ACCUM)
+            if emb:
+                # ... continued below posQ | posK: d rel = sum over the layers of dpos_i (2S, 2d) W_qk,i (2d, d), one NN launch per
+                # layer adding into one f32 (2S, d) buffer in stream order (layer 0 writes it).  In-stream accumulation keeps the sum
+                # in f32 in a fixed order with no partial buffer; a grouped launch into per-layer partials would hold L (2S, d) f32
+                # slabs and need the slab sum behind it, for products of 2S rows that fill a fraction of the CUs either way.
+                # rel is stored as bf16: d rel is rounded to bf16 there, once, and the relative table's LayerNorm backward adds
+                # straight into rel_emb.grad and the encoder LayerNorm's gradients
+                drel = torch.empty((S2, d), dtype=torch.float32, device=dev)
+                for i in range(L):
+                    ops.gemm(GEMM_NN, dp16[i], self._w(f"l{i}_qkv_w")[:2 * d], drel, epilogue=EPI_ACCUM if i else 0)
+                wsp, _ = self._embed_workspace(g, S2, False)
+                lib.deberta_embed_bwd_params(self._f("enc_ln_w"), c.layer_norm_eps, None, ops.cast_to_bf16(drel), self.rel_emb.grad,
+                                             self.enc_ln_w.grad, self.enc_ln_b.grad, wsp, embeds=self._f("rel_emb"), accumulate=True)
         return grad

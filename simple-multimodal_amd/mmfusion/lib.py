@@ -44,6 +44,7 @@ SYMBOLS = (
     "mmf_w2v_posconv_bwd_act", "mmf_w2v_posconv_dgrad", "mmf_w2v_posconv_wgrad", "mmf_w2v_weightnorm_bwd",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
+    "mmf_deberta_embed_bwd_params_workspace_bytes", "mmf_deberta_embed_bwd_params", "mmf_embedding_scatter_add_f32",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
 )
 
@@ -247,6 +248,10 @@ def load() -> C.CDLL:
     lib.mmf_deberta_attn_bwd_pos_workspace_bytes.restype = C.c_size_t
     lib.mmf_deberta_attn_bwd_pos.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
                                              vp, vp, i32, vp, C.c_size_t, vp]
+    lib.mmf_deberta_embed_bwd_params_workspace_bytes.argtypes = [i64, i32]
+    lib.mmf_deberta_embed_bwd_params_workspace_bytes.restype = C.c_size_t
+    lib.mmf_deberta_embed_bwd_params.argtypes = [vp, vp, vp, i32, vp, f32, vp, i32, vp, vp, i32, vp, vp, vp, C.c_size_t, i64, i32, vp]
+    lib.mmf_embedding_scatter_add_f32.argtypes = [vp, vp, i32, vp, vp, i64, i32, i32, vp]
     lib.mmf_video_prepare.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_video_prepare_patches.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_audio_resample.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, i64, i32, i32, i32, vp]
@@ -772,6 +777,65 @@ def deberta_embed_bwd(embeds, gamma, eps: float, mask, dout, d_embeds) -> None:
     with _Timed("deberta_embed_bwd_kernel", 0.0, [(rows, d)]):
         check(load().mmf_deberta_embed_bwd(embeds.data_ptr(), gamma.data_ptr(), eps, mp, kind, dout.data_ptr(), d_embeds.data_ptr(), rows, d,
                                            stream_ptr()))
+
+
+def _deberta_ids(who: str, ids, rows: int) -> None:
+    import torch
+    if not ids.is_cuda:
+        raise RuntimeError("deberta kernels run on the GPU only (no CPU fallback)")
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != rows:
+        raise ValueError(f"{who}: ids must be contiguous int64, one per row")
+
+
+def deberta_embed_bwd_params_workspace_bytes(rows: int, d: int) -> int:
+    return int(load().mmf_deberta_embed_bwd_params_workspace_bytes(rows, d))
+
+
+def deberta_embed_bwd_params(gamma, eps: float, mask, dout, d_rows, dgamma, dbeta, workspace, ids=None, table=None, embeds=None,
+                             accumulate: bool = False) -> None:
+    """The backward of ``deberta_embed`` on the route it took (``ids`` int64 (rows,) with ``table`` f32 (vocab, d), or ``embeds`` f32
+    (rows, d)) for the gradient ``dout`` (rows, d) bf16 of its output: d_rows (rows, d) f32 <- (``accumulate``: +=) the source
+    rows' gradient (``deberta_embed_bwd``'s bits on the embeds route), and the LayerNorm's dgamma / dbeta (d,) f32 += theirs.
+    ``workspace``: a contiguous f32 tensor of at least ``deberta_embed_bwd_params_workspace_bytes(rows, d)`` bytes (it need not be
+    initialised)."""
+    _w2v_f32(gamma, d_rows, dgamma, dbeta, workspace)
+    _w2v_bf16(dout)
+    if (ids is None) == (embeds is None):
+        raise ValueError("deberta_embed_bwd_params: exactly one of ids / embeds")
+    rows, d = dout.shape
+    if ids is not None:
+        _deberta_ids("deberta_embed_bwd_params", ids, rows)
+        _w2v_f32(table)
+        if table.dim() != 2 or table.shape[1] != d:
+            raise ValueError("deberta_embed_bwd_params: table must be (vocab, d)")
+    else:
+        _w2v_f32(embeds)
+        if embeds.numel() != rows * d:
+            raise ValueError("deberta_embed_bwd_params: embeds must hold (rows, d) values")
+    if (d_rows.numel() != rows * d or gamma.numel() != d or dgamma.numel() != d or dbeta.numel() != d or not dout.is_contiguous()
+            or not d_rows.is_contiguous() or not workspace.is_contiguous()):
+        raise ValueError("deberta_embed_bwd_params: d_rows must hold (rows, d) values, gamma / dgamma / dbeta one value per column")
+    mp, kind = _deberta_mask(mask, rows)
+    with _Timed("deberta_embed_bwd_params_kernels", 0.0, [(rows, d)]):
+        check(load().mmf_deberta_embed_bwd_params(ids.data_ptr() if ids is not None else None, embeds.data_ptr() if embeds is not None else None,
+                                                  table.data_ptr() if ids is not None else None, table.shape[0] if ids is not None else 0,
+                                                  gamma.data_ptr(), eps, mp, kind, dout.data_ptr(), d_rows.data_ptr(), int(bool(accumulate)),
+                                                  dgamma.data_ptr(), dbeta.data_ptr(), workspace.data_ptr(),
+                                                  workspace.numel() * workspace.element_size(), rows, d, stream_ptr()))
+
+
+def embedding_scatter_add(ids, d_rows, dtable, mask=None) -> None:
+    """dtable[clamp(ids[r])] += d_rows[r] over the rows whose ``mask`` is not 0: ids int64 (rows,), d_rows f32 (rows, d), dtable f32
+    (vocab, d); occurrences of an id are added in ascending row order, without atomics"""
+    _w2v_f32(d_rows, dtable)
+    if d_rows.dim() != 2 or dtable.dim() != 2 or dtable.shape[1] != d_rows.shape[1] or not d_rows.is_contiguous() or not dtable.is_contiguous():
+        raise ValueError("embedding_scatter_add: d_rows (rows, d) and dtable (vocab, d) must be contiguous with one width")
+    rows, d = d_rows.shape
+    _deberta_ids("embedding_scatter_add", ids, rows)
+    mp, kind = _deberta_mask(mask, rows)
+    with _Timed("embedding_scatter_add_kernel", 0.0, [(rows, d)]):
+        check(load().mmf_embedding_scatter_add_f32(ids.data_ptr(), mp, kind, d_rows.data_ptr(), dtable.data_ptr(), rows, d, dtable.shape[0],
+                                                   stream_ptr()))
 
 
 # ---- input preparation (csrc/prep.hip); tensors, not pointers: the shapes are checked here ------------------------

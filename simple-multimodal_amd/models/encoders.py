@@ -26,7 +26,10 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
     on the prompt route, from input embeddings.  On that route, with grad mode on and ``prompt_embeddings.requires_grad``, the
     backbone is called differentiably and ``prompt_embeddings`` trains through the frozen layers, as it does through
-    HuggingFace's model in the reference (:49-71);
+    HuggingFace's model in the reference (:49-71).  Frozen unless ``config.text_backbone_trainable_layers`` (dynamic attribute;
+    default 0) is ``k`` > 0: the top ``k`` layers then train; ``"all"``: every layer and the embedding side (word embeddings,
+    embedding LayerNorm, relative embeddings, encoder LayerNorm), which is every parameter the reference's optimiser steps; on
+    the prompt route the word embeddings then train through ``word_embeddings(input_ids)`` as well;
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -160,8 +163,12 @@ class TextEncoder(_FusionBase):
         super().__init__()
         self.config = config
         self.model, self.hidden_size, self._native = _backbone(config, "text", backbone)
-        if self._native:      # fine-tune the top layers of the native backbone (NativeDeberta.set_trainable_layers); 0: frozen
-            self.model.set_trainable_layers(int(getattr(config, "text_backbone_trainable_layers", 0)))
+        if self._native:      # fine-tune the native backbone (NativeDeberta.set_trainable_layers): the top k layers, "all": every
+            k = getattr(config, "text_backbone_trainable_layers", 0)           # layer and the embeddings; 0: frozen
+            if k == "all":
+                self.model.set_trainable_layers(self.model.config.num_hidden_layers, embeddings=True)
+            else:
+                self.model.set_trainable_layers(int(k))
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.prompt_embeddings = nn.Parameter(torch.randn(config.prompt_length, self.hidden_size)) \
             if hasattr(config, "prompt_length") else None

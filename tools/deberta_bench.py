@@ -13,9 +13,13 @@
   * with --finetune K, the cost of fine-tuning the top K layers instead (``set_trainable_layers(K)``): on token ids, for
     (items, tokens) = (--items, --tokens) and (8, 128), the same three times and ratios (the backward stops below layer L - K and
     adds the K layers' weight gradients into the arena), the per-kernel table, and ``mmf_deberta_attn_bwd_pos`` beside
-    ``mmf_deberta_attn_bwd`` on the same operands.
+    ``mmf_deberta_attn_bwd`` on the same operands.  ``--finetune all``: every layer and the embedding side
+    (``set_trainable_layers(L, embeddings=True)``); beside the above, on one chunk's operands: ``mmf_deberta_embed_bwd_params``,
+    ``mmf_embedding_scatter_add_f32`` on the batch's ids and on skewed ids (one id on a quarter of the tokens), the d rel GEMMs,
+    the recomputation of ``rel``, and the whole-table costs the real vocabulary adds to a step: the memset of the table's
+    gradient and the AdamW step over the trainable parameters (compare with ``--finetune 12``: the same tree, embeddings frozen).
 
-    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad] [--finetune K]
+    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad] [--finetune K|all]
 Prints one JSON line (the tables, when asked for, on the lines before it)."""
 import json
 import math
@@ -59,9 +63,13 @@ def grad_mode(model, cfg, args) -> dict:
 
 def finetune_mode(model, cfg, args) -> dict:
     from mmfusion import lib
-    K, H, S, d = args.finetune, cfg.num_attention_heads, cfg.position_buckets, cfg.hidden_size
-    model.set_trainable_layers(K)
-    res = {"model": f"deberta-v3-base, bf16 storage: the top {K} layers trainable, token ids", "chunk": model.chunk, "cases": []}
+    from mmfusion import arena, ops
+    from mmfusion.train import finetune_optimizer
+    full = args.finetune == "all"
+    K, H, S, d = cfg.num_hidden_layers if full else int(args.finetune), cfg.num_attention_heads, cfg.position_buckets, cfg.hidden_size
+    model.set_trainable_layers(K, embeddings=full)
+    res = {"model": f"deberta-v3-base, bf16 storage: the top {K} layers" + (" and the embeddings" if full else "") + " trainable, token ids",
+           "chunk": model.chunk, "cases": []}
     for N, T in ((args.items, args.tokens), (8, 128)):
         g = torch.Generator().manual_seed(2)
         ids = torch.randint(1, cfg.vocab_size, (N, T), generator=g).cuda()
@@ -77,7 +85,7 @@ def finetune_mode(model, cfg, args) -> dict:
         both = lambda: model(input_ids=ids, attention_mask=mask).last_hidden_state.backward(dout)     # (the gradients accumulate)
         t_inf, t_diff, t_both = (time_eager(f, args.steps, args.warmup) for f in (infer, diff, both))
         rows = kernel_table(both)
-        print(f"forward + backward, top {K} layers trainable, {N} items of {T} tokens")
+        print(f"forward + backward, top {K} layers" + (" and the embeddings" if full else "") + f" trainable, {N} items of {T} tokens")
         print_table(rows)
         # the attention backward with and without the table gradients, on one chunk's operands
         n = min(N, model.chunk)
@@ -92,7 +100,39 @@ def finetune_mode(model, cfg, args) -> dict:
         withpos = lambda: lib.deberta_attn_bwd_pos(qkv, posq, posk, idx, m32, att, lse, dat, delta, dqkv, dpos[:, :d], dpos[:, d:], ws,
                                                    n, H, T, S, scale)
         t_plain, t_pos = time_eager(plain, 20, 5), time_eager(withpos, 20, 5)
-        res["cases"].append({"items": N, "tokens": T, "trainable_layers": K, "inference_forward_ms": round(t_inf, 3),
+        extra = {}
+        if full:
+            # the embedding side's launches alone, on one chunk's operands
+            rows_, part = n * T, ids[:n].reshape(-1).contiguous()
+            gx = torch.randn(rows_, d, generator=g).to(torch.bfloat16).cuda()
+            d_rows, dgb = torch.empty(rows_, d, device="cuda"), torch.zeros(2, d, device="cuda")
+            ews = torch.empty(lib.deberta_embed_bwd_params_workspace_bytes(max(rows_, 2 * S), d) // 4, device="cuda")
+            table, dtable = model._f("word_emb"), model.word_emb.grad
+            skew = part.clone()
+            skew[::4] = 7
+            f_a = lambda: lib.deberta_embed_bwd_params(model._f("emb_ln_w"), cfg.layer_norm_eps, m32, gx, d_rows, dgb[0], dgb[1], ews,
+                                                       ids=part, table=table)
+            f_b = lambda: lib.embedding_scatter_add(part, d_rows, dtable, mask=m32)
+            f_skew = lambda: lib.embedding_scatter_add(skew, d_rows, dtable, mask=m32)
+            dp16, drel = torch.randn(K, 2 * S, 2 * d, generator=g).to(torch.bfloat16).cuda(), torch.empty(2 * S, d, device="cuda")
+
+            def f_drel():
+                for i in range(K):
+                    ops.gemm(lib.GEMM_NN, dp16[i], model._w(f"l{i}_qkv_w")[:2 * d], drel, epilogue=lib.EPI_ACCUM if i else 0)
+            f_rel = lambda: model._pos_cache(ids.device)
+            f_zero = lambda: dtable.zero_()
+            extra = {name + "_ms": round(time_eager(f, 20, 5), 4) for name, f in
+                     (("embed_bwd_params", f_a), ("scatter_add", f_b), ("scatter_add_skewed", f_skew), ("drel_gemms", f_drel),
+                      ("rel_recompute", f_rel), ("table_grad_memset", f_zero))}
+            extra["table_grad_mb"] = round(dtable.numel() * 4 / 2 ** 20, 1)
+        opt = finetune_optimizer(model, arena.ensure(model), lr=1e-5, weight_decay=0.01)
+
+        def step():
+            opt.advance()
+            opt.launch()
+        extra["adamw_step_ms"] = round(time_eager(step, 5, 2), 4)
+        extra["adamw_parameters_m"] = round(sum(p.numel() for p in model.parameters() if p.requires_grad) / 1e6, 1)
+        res["cases"].append({"items": N, "tokens": T, "trainable_layers": K, "embeddings": full, **extra, "inference_forward_ms": round(t_inf, 3),
                              "differentiable_forward_ms": round(t_diff, 3), "forward_backward_ms": round(t_both, 3),
                              "differentiable_forward_ratio": round(t_diff / t_inf, 3), "forward_backward_ratio": round(t_both / t_inf, 3),
                              "saved_inputs_mb": round(K * N * T * d * 2 / 2 ** 20, 1),
@@ -106,7 +146,7 @@ def main():
     ap.add_argument("--items", type=int, default=16)
     ap.add_argument("--tokens", type=int, default=512)
     ap.add_argument("--grad", action="store_true")
-    ap.add_argument("--finetune", type=int, default=0, metavar="K")
+    ap.add_argument("--finetune", type=lambda v: v if v == "all" else int(v), default=0, metavar="K|all")
     args = ap.parse_args()
     import deberta_ref
     from mmfusion import deberta, lib
