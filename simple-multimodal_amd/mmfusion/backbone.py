@@ -17,15 +17,38 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
     _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
     _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
     _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; the backbones' backward)
-    _ln_bwd_add(...)                mmf_layernorm_bwd_add_grouped        dy, r -> dx = r + that (a pre-LN layer's residual gradient)
+    _ln_bwd(..., resid=r)           mmf_layernorm_bwd_add_grouped        dy, r -> dx = r + that (a pre-LN layer's residual gradient)
     _wgrad(dy, x, name, slabs)      mmf_gemm_grouped TN, COLSUM_A        dy, x -> a trainable layer's weight and bias gradients; in
                                     (+ mmf_sum_slabs_f32)                ``slabs`` K-slabs where the output is a few tiles under many rows
+
+The backward of a post-LN layer is ``_post_ln_layer_grad`` (Wav2Vec2, DeBERTa; ViT's pre-LN one, with its CLS form, is its own
+``_layer_grad``): the layer again from its saved input ``xin``, then top down, on the backward's workspace (``_grad_workspace``;
+``ga`` holds the gradient of the layer's output on entry and of ``xin`` on return)
+
+      _attention(xin, + xin, attend)                                           xin -> qkv -> att -> y1 (the attention writes lse)
+      LayerNorm 1                   mmf_layernorm_fwd_grouped                  y1  -> ln   (mean1, rstd1)
+      fc1; + bias, GELU beside it   NT; mmf_bias_gelu_bf16_to                  ln  -> h (raw) -> g
+      fc2 + bias + ln               NT, BIAS | ADD_AUX                         g   -> y2
+      LayerNorm 2                   mmf_layernorm_fwd_grouped                  y2  -> (mean2, rstd2; the output is not read)
+      LayerNorm 2 backward          mmf_layernorm_bwd_grouped                  ga  -> gb = dy2
+      fc2 wgrad, dgrad              mmf_gemm_grouped TN (COLSUM_A) / NN        gb  -> dh = dg
+      GELU backward                 mmf_bias_gelu_bwd_bf16 (in place)          dh, h -> dh
+      fc1 wgrad, dgrad + dy2        TN / NN, ADD_AUX                           dh  -> ga = dln1
+      LayerNorm 1 backward          mmf_layernorm_bwd_grouped                  ga  -> gb = dy1
+      out-projection wgrad, dgrad   TN / NN                                    gb  -> ga = datt
+      attn_bwd(qkv, att, datt, dqkv)                                           ga  -> dqkv
+      qkv_wgrad(dqkv, xin)          TN                                         the fused Q/K/V weight and bias gradients
+      Q/K/V dgrad + dy1             NN, ADD_AUX                                dqkv -> ga = dxin (``below`` only)
+
+A model supplies four things: the attention forward, the attention backward, the Q/K/V weight gradient (None: the frozen walk,
+which forms no weight gradient at all and discards the LayerNorms' parameter sums) and the K-slab rule of the other weight
+gradients (None: plain launches).
 
 Parameters are stored as the kernels read them (Q/K/V fused, a subclass may store a weight with its last two dims swapped)
 and ``_hf`` maps every HuggingFace key to its view of them, in HuggingFace's order, so ``state_dict()`` and
 ``load_state_dict`` speak HuggingFace's names and shapes; ``_add_layer`` registers one layer from a table of HuggingFace's
-names.  A subclass declares its workspace as a table of (name, elements per chunk item, dtype), ``_ws_table(size)``; the
-allocation and the bytes-per-item figure are both read from that table.  A forward pass writes no attribute of the module
+names.  A subclass declares its workspace as a table of (name, elements per chunk item, dtype), ``_ws_table(size)``, and its
+backward's as ``_grad_table(size)``; the allocation and the bytes-per-item figure are both read from that table.  A forward pass writes no attribute of the module
 but that workspace and the ``_derived`` cache: what a launch needs beyond the buffers travels as arguments.
 
 Frozen by default: every parameter has ``requires_grad = False`` and the outputs carry no autograd graph.  Every backbone has a
@@ -44,12 +67,14 @@ import torch.nn as nn
 
 from . import arena as _arena
 from . import lib, ops
-from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, GEMM_NT, GEMM_TN, AttnProblem, LnProblem
+from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, GEMM_NN, GEMM_NT, GEMM_TN, AttnProblem, LnProblem
 
 BF16 = torch.bfloat16
 LN_WIDTHS = (256, 512, 768, 1024)          # the lane forms of layernorm.hip
 WsTable = List[Tuple[str, int, torch.dtype]]
 Attend = Callable[[torch.Tensor, torch.Tensor], None]          # (qkv rows, att rows): launches one chunk's attention
+AttnBwd = Callable[[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor], None]     # (qkv, att, datt, dqkv rows): its backward
+QkvWgrad = Callable[[torch.Tensor, torch.Tensor], None]        # (dqkv rows, the projection's input rows): the fused weight's gradient
 
 
 class BackboneOutput:
@@ -94,6 +119,30 @@ class FrozenBackbone(nn.Module):
     @property
     def trainable_layers(self) -> int:
         return self._trainable
+
+    def _check_trainable(self, k, flag: str, on, what: str, why: str) -> None:
+        """``set_trainable_layers(k, flag=on)``'s arguments: ``k`` in 0 .. L, and the model's extras (``what``: "the embeddings
+        train") with every layer only, since ``why``"""
+        who, L = type(self).__name__, self.config.num_hidden_layers
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
+            raise ValueError(f"{who}: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
+        if not isinstance(on, bool) or (on and k != L):
+            raise ValueError(f"{who}: set_trainable_layers({k!r}, {flag}={on!r}): {what} with all {L} layers only ({why})")
+
+    def _require_grad(self, names) -> None:
+        """``requires_grad`` for the parameters ``names`` and for no other"""
+        names = set(names)
+        for name, p in self.named_parameters(recurse=False):
+            p.requires_grad_(name in names)
+
+    def _grads(self, i: int, role: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """layer ``i``'s f32 (weight, bias) gradients of ``role`` (for a LayerNorm: dgamma, dbeta)"""
+        return getattr(self, f"l{i}_{role}_w").grad, getattr(self, f"l{i}_{role}_b").grad
+
+    def _keep(self, first: int, rows: int, dev) -> torch.Tensor:
+        """where a differentiable forward keeps the bf16 inputs of the layers ``first`` .. L - 1, ``rows`` rows each"""
+        c = self.config
+        return torch.empty((c.num_hidden_layers - first, rows, c.hidden_size), dtype=BF16, device=dev)
 
     # -- parameter table --------------------------------------------------------------------------------
     def _add(self, name: str, shape, key: Optional[str] = None, *, ones: bool = False, std: float = 0.02, swapped: bool = False):
@@ -182,14 +231,58 @@ class FrozenBackbone(nn.Module):
     def _workspace(self, dev, size=None) -> dict:
         """the workspace of ``self.chunk`` items of ``size`` (samples, tokens; None where the model fixes it).  Every buffer
         grows with ``size``, so a smaller item uses the leading part of what a larger one allocated"""
-        ws = self._ws
-        if ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk and (size is None or ws["size"] >= size):
-            return ws
+        if not self._fits(self._ws, dev, size):
+            self._ws = self._allocate(self._ws_table(size), dev, size)
+        return self._ws
+
+    def _fits(self, ws: Optional[dict], dev, size) -> bool:
+        """whether the workspace ``ws`` serves ``self.chunk`` items of ``size`` on ``dev``"""
+        return ws is not None and ws["dev"] == dev and ws["chunk"] == self.chunk and (size is None or ws["size"] >= size)
+
+    def _allocate(self, table: WsTable, dev, size) -> dict:
         ws = {"dev": dev, "chunk": self.chunk, "size": size}
-        for name, numel, dtype in self._ws_table(size):
+        for name, numel, dtype in table:
             ws[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
-        self._ws = ws
         return ws
+
+    def _grad_rows(self, T: int, second: str = "y2") -> WsTable:
+        """The layers' part of a backward's table (the subclass's ``_grad_table(size)``) for one item of ``T`` tokens, beside the
+        forward workspace: ``second`` (what the layer's backward keeps of its second block: a post-LN layer's pre-LN sum ``y2``,
+        ViT's ``ln2``), the GELU output ``g`` (``h`` keeps the raw fc1 output), the gradient buffers (``ga`` / ``gb`` alternate as
+        the d-wide gradients, ``dh`` is dg then dh), both LayerNorms' statistics and the attention backward's delta"""
+        c = self.config
+        d, H, I, f32 = c.hidden_size, c.num_attention_heads, c.intermediate_size, torch.float32
+        return [(second, T * d, BF16), ("g", T * I, BF16), ("ga", T * d, BF16), ("gb", T * d, BF16), ("dh", T * I, BF16),
+                ("dqkv", T * 3 * d, BF16), ("mean1", T, f32), ("rstd1", T, f32), ("mean2", T, f32), ("rstd2", T, f32), ("delta", H * T, f32)]
+
+    def _grad_scratch(self) -> Tuple[int, Dict[str, int]]:
+        """what a backward holds beside its table, whatever the chunk -> (the widest LayerNorm its backward goes through: the
+        width of ``dgb`` and ``ln_ws``, further f32 buffers: name -> elements).  ``junk``: where the key bias's column sum goes
+        (``_qkv_wgrad_roles``; it is not kept)"""
+        d = self.config.hidden_size
+        return d, {"junk": d}
+
+    def _grad_workspace(self, dev, size=None) -> dict:
+        """the backward's workspace of ``self.chunk`` items of ``size``: the subclass's ``_grad_table(size)`` and
+        ``_grad_scratch()``, kept and reused as ``_workspace`` is"""
+        if not self._fits(self._gws, dev, size):
+            width, extra = self._grad_scratch()
+            f32 = lambda numel: torch.empty(numel, dtype=torch.float32, device=dev)
+            g = self._allocate(self._grad_table(size), dev, size)
+            g.update(dgb=f32(2 * width), ln_ws=f32(lib.load().mmf_layernorm_bwd_workspace_bytes(width) // 4), **{k: f32(v) for k, v in extra.items()})
+            self._gws = g
+        return self._gws
+
+    @staticmethod
+    def _stats(g: dict, k: int) -> dict:
+        """the backward workspace as ``_ln`` / ``_ln_bwd`` read it for a layer's LayerNorm ``k`` (1 / 2): its statistics as
+        ``mean`` / ``rstd`` beside the LayerNorm backward's scratch"""
+        return {"mean": g[f"mean{k}"], "rstd": g[f"rstd{k}"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+
+    def _chunks(self, N: int):
+        """(first item, items) of each pass of ``N`` items through the workspace"""
+        for n0 in range(0, N, self.chunk):
+            yield n0, min(self.chunk, N - n0)
 
     @staticmethod
     def _rows(ws, name: str, rows: int, width: int) -> torch.Tensor:
@@ -208,10 +301,13 @@ class FrozenBackbone(nn.Module):
         return hit[1]
 
     # -- launches ---------------------------------------------------------------------------------------
+    def _refuse_fp32(self) -> None:
+        if ops.fp32_mode():
+            raise RuntimeError(f"{type(self).__name__} runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+
     def _check_input(self, x, name: str, dtype: torch.dtype = torch.float32, ndim: Optional[int] = None) -> None:
         who = type(self).__name__
-        if ops.fp32_mode():
-            raise RuntimeError(f"{who} runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        self._refuse_fp32()
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback)")
         want = str(dtype).rpartition(".")[2]
@@ -233,11 +329,14 @@ class FrozenBackbone(nn.Module):
                                                  ws["mean"].data_ptr(), ws["rstd"].data_ptr(), None, None, None, None, rows)],
                                       width, self.config.layer_norm_eps)
 
-    def _ln_bwd(self, scratch, src: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, gamma: str, into=None) -> None:
+    def _ln_bwd(self, scratch, src: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, gamma: str, into=None,
+                resid: Optional[torch.Tensor] = None) -> None:
         """dx = the LayerNorm input gradient of ``dy`` at the input ``src`` whose statistics are ``scratch["mean"]`` / ``["rstd"]``.
         The kernel also sums gamma / beta's gradients.  Frozen parameters (``into`` None): into ``scratch["dgb"]`` (2 width f32),
         zeroed here and discarded.  Trainable ones: ``into`` = (dgamma, dbeta), the parameters' f32 gradients, which the kernel
-        adds to.  ``scratch["ln_ws"]``: its f32 workspace"""
+        adds to.  ``scratch["ln_ws"]``: its f32 workspace.  With ``resid`` (bf16 rows like dx; it may be dx) the residual gradient
+        is folded in: dx = resid + the LayerNorm input gradient (a pre-LN layer: the LayerNorm's input also feeds the residual add
+        behind the block, so its gradient is the sum of the two)"""
         rows, width = src.shape
         if into is None:
             dgb = scratch["dgb"]
@@ -245,26 +344,11 @@ class FrozenBackbone(nn.Module):
             dgamma, dbeta = dgb.data_ptr(), dgb.data_ptr() + 4 * width
         else:
             dgamma, dbeta = into[0].data_ptr(), into[1].data_ptr()
+        launch = lib.layernorm_bwd_grouped if resid is None else lib.layernorm_bwd_add_grouped
         with lib._Timed("ln_bwd_kernel", 0.0, [(rows, width)]):
-            lib.layernorm_bwd_grouped([LnProblem(src.data_ptr(), None, self._f(gamma).data_ptr(), None, scratch["mean"].data_ptr(),
-                                                 scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma, dbeta, rows)],
-                                      width, scratch["ln_ws"])
-
-    def _ln_bwd_add(self, scratch, src: torch.Tensor, dy: torch.Tensor, resid: torch.Tensor, dx: torch.Tensor, gamma: str, into=None) -> None:
-        """``_ln_bwd`` with the residual gradient folded in: dx = resid + the LayerNorm input gradient (a pre-LN layer: the
-        LayerNorm's input also feeds the residual add behind the block, so its gradient is the sum of the two); ``resid`` (bf16
-        rows like dx) may be dx"""
-        rows, width = src.shape
-        if into is None:
-            dgb = scratch["dgb"]
-            dgb.zero_()
-            dgamma, dbeta = dgb.data_ptr(), dgb.data_ptr() + 4 * width
-        else:
-            dgamma, dbeta = into[0].data_ptr(), into[1].data_ptr()
-        with lib._Timed("ln_bwd_kernel", 0.0, [(rows, width)]):
-            lib.layernorm_bwd_add_grouped([LnProblem(src.data_ptr(), resid.data_ptr(), self._f(gamma).data_ptr(), None, scratch["mean"].data_ptr(),
-                                                     scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma, dbeta, rows)],
-                                          width, scratch["ln_ws"])
+            launch([LnProblem(src.data_ptr(), None if resid is None else resid.data_ptr(), self._f(gamma).data_ptr(), None,
+                              scratch["mean"].data_ptr(), scratch["rstd"].data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma, dbeta, rows)],
+                   width, scratch["ln_ws"])
 
     # -- weight gradients of the trainable layers ----------------------------------------------------------
     @staticmethod
@@ -351,19 +435,24 @@ class FrozenBackbone(nn.Module):
         dK; the GEMM's column sum of that part goes to ``junk`` (hidden_size f32, not kept).  ``overwrite``: the weight's first
         touch where the caller has taken it already"""
         d = self.config.hidden_size
-        w, b = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad
+        w, b = self._grads(i, "qkv")
         over = self._first_touch(w) if overwrite is None else overwrite
         part = lambda r: (dqkv[:, r * d:(r + 1) * d], x, w[r * d:(r + 1) * d], junk if r == 1 else b[r * d:(r + 1) * d])
         self._wgrad_launch([part(r) for r in roles], over, self._slabs_for(x.shape[0], len(roles) * self._tiles(d, d)))
 
-    def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
+    def _attn_problem(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int, datt: Optional[torch.Tensor] = None,
+                      delta: Optional[torch.Tensor] = None, dqkv: Optional[torch.Tensor] = None) -> AttnProblem:
         """attention of ``Tq`` queries per item over its ``T`` keys, read from the fused ``qkv`` rows; ``Tq == 1`` takes the
-        query of each item's first row"""
+        query of each item's first row.  lse is the forward workspace's; the backward adds ``datt``, ``delta`` and ``dqkv``, laid
+        out as ``qkv``"""
         c, d = self.config, self.config.hidden_size
-        base = qkv.data_ptr()
-        lib.attn_fwd_grouped([AttnProblem(base, base + 2 * d, base + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), None, None, None,
-                                          None, None, n, c.num_attention_heads, Tq, T, 3 * d if Tq == T else T * 3 * d, 3 * d, 3 * d, d)],
-                             self.head_dim, self.head_dim ** -0.5)
+        q, dq = qkv.data_ptr(), None if dqkv is None else dqkv.data_ptr()
+        return AttnProblem(q, q + 2 * d, q + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), None if datt is None else datt.data_ptr(),
+                           None if delta is None else delta.data_ptr(), dq, dq and dq + 2 * d, dq and dq + 4 * d, n,
+                           c.num_attention_heads, Tq, T, 3 * d if Tq == T else T * 3 * d, 3 * d, 3 * d, d)
+
+    def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
+        lib.attn_fwd_grouped([self._attn_problem(ws, qkv, att, n, Tq, T)], self.head_dim, self.head_dim ** -0.5)
 
     def _out_proj(self, i: int, att: torch.Tensor, resid: torch.Tensor, y: torch.Tensor) -> None:
         ops.gemm(GEMM_NT, att, self._w(f"l{i}_o_w"), y, bias=self._f(f"l{i}_o_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
@@ -396,6 +485,47 @@ class FrozenBackbone(nn.Module):
         self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
         self._ffn(i, ws, ln, ln, y)
         self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
+
+    def _post_ln_layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, attend: Optional[Attend], attn_bwd: AttnBwd,
+                            qkv_wgrad: Optional[QkvWgrad], below: bool = True, slabs: Optional[Callable[[int, int], int]] = None) -> None:
+        """``_post_ln_layer`` ``i`` again from its saved input ``xin``, then its backward (the module docstring has the rows):
+        ``ga`` holds the gradient of the layer's output on entry and, with ``below``, of ``xin`` on return.  ``attend`` as in
+        ``_attention``; it leaves the lse where ``attn_bwd(qkv, att, datt, dqkv)`` reads it.  With ``qkv_wgrad(dqkv, xin)`` the
+        layer trains: its weight, bias and LayerNorm gradients are added into the parameters' ``.grad``, the four plain weights'
+        in ``slabs(rows, tiles)`` K-slabs (``_slabs_for``; None: plain launches).  Without, no weight gradient is formed"""
+        c = self.config
+        rows, d, I, R, train = n * T, c.hidden_size, c.intermediate_size, self._rows, qkv_wgrad is not None
+        ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
+        ln, h, qkv, att = R(ws, "ln", rows, d), R(ws, "h", rows, I), R(ws, "qkv", rows, 3 * d), R(ws, "att", rows, d)
+        st1, st2 = self._stats(g, 1), self._stats(g, 2)
+        W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
+
+        def wgrad(dy: torch.Tensor, x: torch.Tensor, r: str, M: int, N: int) -> None:
+            if train:
+                self._wgrad(dy, x, f"l{i}_{r}", slabs(rows, self._tiles(M, N)) if slabs else 1)
+        # the forward again: both LayerNorms' statistics, the raw fc1 output and the GELU output side by side
+        y1 = self._attention(i, ws, xin, xin, n, T, attend)
+        self._ln(st1, y1, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
+        ops.gemm(GEMM_NT, ln, W("fc1"), h)
+        lib.bias_gelu_to(h, F("fc1"), gel)
+        ops.gemm(GEMM_NT, gel, W("fc2"), y2, bias=F("fc2"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
+        # the MLP
+        self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w", self._grads(i, "ln2") if train else None)          # gb = dy2
+        wgrad(gb, gel, "fc2", d, I)
+        ops.gemm(GEMM_NN, gb, W("fc2"), dh)                                           # dg
+        lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
+        wgrad(dh, ln, "fc1", I, d)
+        ops.gemm(GEMM_NN, dh, W("fc1"), ga, aux=gb, epilogue=EPI_ADD_AUX)             # ga = dln1: the MLP branch + the residual
+        # the attention
+        self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w", self._grads(i, "ln1") if train else None)          # gb = dy1
+        wgrad(gb, att, "o", d, d)
+        ops.gemm(GEMM_NN, gb, W("o"), ga)                                             # ga = datt
+        attn_bwd(qkv, att, ga, dqkv)
+        if train:
+            qkv_wgrad(dqkv, xin)
+        if below:
+            ops.gemm(GEMM_NN, dqkv, W("qkv"), ga, aux=gb, epilogue=EPI_ADD_AUX)       # ga = dx: the attention branch + the residual
 
     @staticmethod
     def _widen(src: torch.Tensor, dst: torch.Tensor) -> None:

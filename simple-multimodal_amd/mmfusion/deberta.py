@@ -42,19 +42,11 @@ The input gradient.  ``forward(inputs_embeds=...)`` with embeddings that require
 graph.  Prompt tuning needs no weight gradient, and posQ | posK depend on the frozen weights only, so the backward is the
 input-gradient pass through the frozen layers.  The differentiable forward is the launch list above plus one copy per layer:
 it keeps the bf16 input ``x`` of every layer (L N T d 2 bytes) and the backward, per chunk and per layer in reverse, runs the
-layer's forward again from that ``x`` and then its backward:
+layer's forward again from that ``x`` and then its backward, the post-LN layer's (``_post_ln_layer_grad``, mmfusion/backbone.py
+has its rows; the frozen walk: no weight gradient) with
 
-      the layer's forward again, with                                     x -> qkv, att, lse, y1, ln1 (mean1, rstd1), h, g, y2
-        mmf_deberta_attn_fwd_lse for the attention, mmf_bias_gelu_bf16_to for the GELU (h kept),
-        and the second LayerNorm for its statistics                       y2 -> (mean2, rstd2)
-      LayerNorm backward            mmf_layernorm_bwd_grouped            gx, y2 -> dy2
-      fc2 dgrad                     mmf_gemm_grouped NN                  dy2 -> dg
-      GELU backward                 mmf_bias_gelu_bwd_bf16 (in place)    dg, h -> dh
-      fc1 dgrad + dy2               mmf_gemm_grouped NN, ADD_AUX         dh  -> dln1
-      LayerNorm backward            mmf_layernorm_bwd_grouped            dln1, y1 -> dy1
-      out-projection dgrad          mmf_gemm_grouped NN                  dy1 -> datt
+      the attention again           mmf_deberta_attn_fwd_lse             qkv -> att, lse
       attention backward            mmf_deberta_attn_bwd (3 launches)    datt -> dqkv
-      Q/K/V dgrad + dy1             mmf_gemm_grouped NN, ADD_AUX         dqkv -> gx of the layer below
     embedding backward              mmf_deberta_embed_bwd                gx  -> d inputs_embeds (f32)
 
 Gradients are stored as bf16 exactly where the forward stores the activation they belong to (a residual join is summed in f32
@@ -107,7 +99,7 @@ import torch
 from . import arena as _arena
 from . import lib, ops
 from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
-from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, GEMM_NN, GEMM_NT, GEMM_TN
+from .lib import EPI_ACCUM, EPI_BIAS, EPI_COLSUM_A, GEMM_NN, GEMM_NT, GEMM_TN
 
 # items per pass through the workspace.  NOT chosen by measurement yet: 16 items of 512 tokens give the layer GEMMs 8192 rows
 # at 0.14 GB of workspace; tools/deberta_bench.py --chunks is the sweep that should decide it
@@ -183,11 +175,11 @@ class _Differentiable(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model: "NativeDeberta", src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, *params) -> torch.Tensor:
         N, T = src.shape[:2]
-        L, d = model.config.num_hidden_layers, model.config.hidden_size
+        L = model.config.num_hidden_layers
         need_in = not by_ids and ctx.needs_input_grad[1]
         emb = model.trainable_embeddings
         first = 0 if need_in or emb else L - model.trainable_layers   # the lowest layer the backward walks
-        keep = torch.empty((L - first, N * T, d), dtype=BF16, device=src.device)
+        keep = model._keep(first, N * T, src.device)
         _arena.ensure(model)
         rel, pos = model._pos_state(src.device)
         out = model._run(src, mask, by_ids, keep, first, pos)
@@ -295,17 +287,11 @@ class NativeDeberta(FrozenBackbone):
         or the embeddings need a gradient too.  Without ``embeddings`` the six embedding-side tensors stay frozen whatever ``k``.
         The backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
         L = self.config.num_hidden_layers
-        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
-            raise ValueError(f"NativeDeberta: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
-        if not isinstance(embeddings, bool) or (embeddings and k != L):
-            raise ValueError(f"NativeDeberta: set_trainable_layers({k!r}, embeddings={embeddings!r}): the embeddings train with all "
-                             f"{L} layers only (their gradient comes through every layer)")
+        self._check_trainable(k, "embeddings", embeddings, "the embeddings train", "their gradient comes through every layer")
         if self._embeddings and not embeddings:        # (steps taken while ``rel_embeddings`` trained moved no version counter)
             self._cache.pop("pos", None)
         self._trainable, self._embeddings = k, embeddings
-        names = {n for i in range(L - k, L) for n in self._layer_params(i)} | set(self._EMBEDDING_PARAMS if embeddings else ())
-        for name, p in self.named_parameters(recurse=False):
-            p.requires_grad_(name in names)
+        self._require_grad([n for i in range(L - k, L) for n in self._layer_params(i)] + list(self._EMBEDDING_PARAMS if embeddings else ()))
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -321,29 +307,15 @@ class NativeDeberta(FrozenBackbone):
         return self._bytes_per_item(self._ws_table(T))
 
     def _grad_table(self, T: int) -> WsTable:
-        """what the backward holds beside the forward workspace, per item of ``T`` tokens: the second pre-LN sum, the GELU output
-        (``h`` keeps the raw fc1 output), both LayerNorms' statistics, lse and delta, and the gradient buffers (``ga`` / ``gb``
-        alternate as the d-wide gradients, ``dh`` is dg then dh)"""
-        c = self.config
-        d, H, I, f32 = c.hidden_size, c.num_attention_heads, c.intermediate_size, torch.float32
-        return [("y2", T * d, BF16), ("g", T * I, BF16), ("ga", T * d, BF16), ("gb", T * d, BF16), ("dh", T * I, BF16),
-                ("dqkv", T * 3 * d, BF16), ("mean1", T, f32), ("rstd1", T, f32), ("mean2", T, f32), ("rstd2", T, f32),
-                ("lse", H * T, f32), ("delta", H * T, f32)]
+        """what the backward holds beside the forward workspace, per item of ``T`` tokens: the layers' part (``_grad_rows``) and
+        the lse of the attention it runs again (the forward workspace's is not written by ``mmf_deberta_attn_fwd``)"""
+        return self._grad_rows(T) + [("lse", self.config.num_attention_heads * T, torch.float32)]
 
     def grad_workspace_bytes_per_item(self, T: int) -> int:
         return self._bytes_per_item(self._grad_table(T))
 
-    def _grad_workspace(self, dev, T: int) -> dict:
-        g = self._gws
-        if g is not None and g["dev"] == dev and g["chunk"] == self.chunk and g["size"] >= T:
-            return g
-        d = self.config.hidden_size
-        g = {"dev": dev, "chunk": self.chunk, "size": T, "dgb": torch.empty(2 * d, dtype=torch.float32, device=dev),
-             "ln_ws": torch.empty(lib.load().mmf_layernorm_bwd_workspace_bytes(d) // 4, dtype=torch.float32, device=dev)}
-        for name, numel, dtype in self._grad_table(T):
-            g[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
-        self._gws = g
-        return g
+    def _grad_scratch(self) -> Tuple[int, Dict[str, int]]:
+        return self.config.hidden_size, {}             # (every bias takes its column sum here: nothing goes to ``junk``)
 
     def _pos_workspace(self, g: dict, n: int, T: int) -> torch.Tensor:
         """``mmf_deberta_attn_bwd_pos``'s workspace for chunks of up to ``n`` items of ``T`` tokens, kept beside the backward's
@@ -458,8 +430,7 @@ class NativeDeberta(FrozenBackbone):
         ws = self._workspace(dev, T)
         out = torch.empty((N, T, d), dtype=torch.float32, device=dev)
         table, gamma, beta = self._f("word_emb"), self._f("emb_ln_w"), self._f("emb_ln_b")
-        for n0 in range(0, N, self.chunk):
-            n = min(self.chunk, N - n0)
+        for n0, n in self._chunks(N):
             x = self._rows(ws, "x", n * T, d)
             part, m = src[n0:n0 + n], None if mask is None else mask[n0:n0 + n]
             if by_ids:
@@ -479,45 +450,22 @@ class NativeDeberta(FrozenBackbone):
         """layer ``i`` again from its saved input ``xin``, then its backward: ``ga`` holds the gradient of the layer's output on
         entry and, with ``below``, of ``xin`` on return.  ``dpos`` (2S, 2d) f32, for a trainable layer: the layer's weight, bias
         and LayerNorm gradients are added into the parameters' ``.grad`` and the gradient of posQ | posK into ``dpos``"""
-        c, scale = self.config, math.sqrt(3.0 * self.head_dim)
-        rows, d, H, S, I = n * T, c.hidden_size, c.num_attention_heads, c.position_buckets, c.intermediate_size
-        R = self._rows
+        c, d = self.config, self.config.hidden_size
+        dims = (n, c.num_attention_heads, T, c.position_buckets, math.sqrt(3.0 * self.head_dim), self.head_dim)
         train = dpos is not None
-        ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
-        ln, h, qkv, att = R(ws, "ln", rows, d), R(ws, "h", rows, I), R(ws, "qkv", rows, 3 * d), R(ws, "att", rows, d)
-        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        lng = lambda r: (getattr(self, f"l{i}_{r}_w").grad, getattr(self, f"l{i}_{r}_b").grad) if train else None
 
-        def attend(qkv_: torch.Tensor, att_: torch.Tensor) -> None:
-            lib.deberta_attn_fwd(qkv_, pos[0], pos[1], idx, mask, att_, n, H, T, S, scale, self.head_dim, lse=g["lse"])
-        y1 = self._attention(i, ws, xin, xin, n, T, attend)
-        self._ln(st1, y1, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        ops.gemm(GEMM_NT, ln, self._w(f"l{i}_fc1_w"), h)
-        lib.bias_gelu_to(h, self._f(f"l{i}_fc1_b"), gel)
-        ops.gemm(GEMM_NT, gel, self._w(f"l{i}_fc2_w"), y2, bias=self._f(f"l{i}_fc2_b"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
-        self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
+        def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
+            lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, *dims, lse=g["lse"])
 
-        self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w", lng("ln2"))                      # gb = dy2
-        if train:
-            self._wgrad(gb, gel, f"l{i}_fc2")
-        ops.gemm(GEMM_NN, gb, self._w(f"l{i}_fc2_w"), dh)                             # dg
-        lib.bias_gelu_bwd(dh, h, self._f(f"l{i}_fc1_b"), dh)
-        if train:
-            self._wgrad(dh, ln, f"l{i}_fc1")
-        ops.gemm(GEMM_NN, dh, self._w(f"l{i}_fc1_w"), ga, aux=gb, epilogue=EPI_ADD_AUX)          # ga = dln1: the MLP branch + the residual
-        self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w", lng("ln1"))                      # gb = dy1
-        if train:
-            self._wgrad(gb, att, f"l{i}_o")
-        ops.gemm(GEMM_NN, gb, self._w(f"l{i}_o_w"), ga)                               # ga = datt
-        if train:
-            lib.deberta_attn_bwd_pos(qkv, pos[0], pos[1], idx, mask, att, g["lse"], ga, g["delta"], dqkv, dpos[:, :d], dpos[:, d:],
-                                     self._pos_workspace(g, n, T), n, H, T, S, scale, self.head_dim)
-            self._wgrad(dqkv, xin, f"l{i}_qkv")
-        else:
-            lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], ga, g["delta"], dqkv, n, H, T, S, scale, self.head_dim)
-        if below:
-            ops.gemm(GEMM_NN, dqkv, self._w(f"l{i}_qkv_w"), ga, aux=gb, epilogue=EPI_ADD_AUX)    # ga = dx: the attention branch + the residual
+        def attn_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor) -> None:
+            if train:
+                lib.deberta_attn_bwd_pos(qkv, pos[0], pos[1], idx, mask, att, g["lse"], datt, g["delta"], dqkv, dpos[:, :d], dpos[:, d:],
+                                         self._pos_workspace(g, n, T), *dims)
+            else:
+                lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], datt, g["delta"], dqkv, *dims)
+        # the plain Q/K/V weight gradient, the key bias's column sum included: db_k has a real position-to-content term here
+        self._post_ln_layer_grad(i, ws, g, xin, n, T, attend, attn_bwd, (lambda dqkv, x: self._wgrad(dqkv, x, f"l{i}_qkv")) if train else None,
+                                 below)
 
     def _embed_workspace(self, g: dict, rows: int, d_rows: bool) -> tuple:
         """(``mmf_deberta_embed_bwd_params``' workspace for up to ``rows`` rows, with ``d_rows`` an f32 (rows, d) buffer for the
@@ -541,15 +489,13 @@ class NativeDeberta(FrozenBackbone):
         c, d, dev = self.config, self.config.hidden_size, src.device
         N, T = src.shape[:2]
         L, S2 = c.num_hidden_layers, 2 * c.position_buckets
-        if ops.fp32_mode():
-            raise RuntimeError("NativeDeberta runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        self._refuse_fp32()
         idx = self._index(T, dev)
         ws, g = self._workspace(dev, T), self._grad_workspace(dev, T)
         grad = torch.empty((N, T, d), dtype=torch.float32, device=dev) if need_in else None
         # the gradient of posQ | posK of each trainable layer, summed over the chunks in f32
         dpos = torch.zeros((k, S2, 2 * d), dtype=torch.float32, device=dev) if k else None
-        for n0 in range(0, N, self.chunk):
-            n = min(self.chunk, N - n0)
+        for n0, n in self._chunks(N):
             rows = slice(n0 * T, (n0 + n) * T)
             m = None if mask is None else mask[n0:n0 + n]
             ga = self._rows(g, "ga", n * T, d)

@@ -110,7 +110,7 @@ class _Differentiable(torch.autograd.Function):
     def forward(ctx, model: "NativeViT", pixels: torch.Tensor, cls_only: bool, aug: Optional[VideoAug], *params) -> torch.Tensor:
         N, T, d, L = pixels.shape[0], model.T, model.config.hidden_size, model.config.num_hidden_layers
         first = L - model.trainable_layers                             # the lowest layer the backward walks
-        keep = torch.empty((L - first, N * T, d), dtype=BF16, device=pixels.device)
+        keep = model._keep(first, N * T, pixels.device)
         final = torch.empty((N if cls_only else N * T, d), dtype=BF16, device=pixels.device)
         out = model._launches(pixels, cls_only, aug, keep, first, final)
         ctx.model, ctx.cls_only, ctx.aug, ctx.first, ctx.embeddings = model, cls_only, aug, first, model.trainable_embeddings
@@ -193,16 +193,9 @@ class NativeViT(FrozenBackbone):
         graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops
         below layer ``L - k``.  ``pooler.dense`` stays frozen whatever ``k`` (nothing reads it), there is no gradient with respect
         to the pixels, the backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
-        L = self.config.num_hidden_layers
-        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
-            raise ValueError(f"NativeViT: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
-        if not isinstance(embeddings, bool) or (embeddings and k != L):
-            raise ValueError(f"NativeViT: set_trainable_layers({k!r}, embeddings={embeddings!r}): the embeddings train with all "
-                             f"{L} layers only (their gradient comes through every layer)")
+        self._check_trainable(k, "embeddings", embeddings, "the embeddings train", "their gradient comes through every layer")
         self._trainable, self._embeddings = k, embeddings
-        names = set(self._trainable_names())
-        for name, p in self.named_parameters(recurse=False):
-            p.requires_grad_(name in names)
+        self._require_grad(self._trainable_names())
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _canonical_key(self, key: str) -> str:
@@ -313,8 +306,7 @@ class NativeViT(FrozenBackbone):
         ws = self._workspace(pixels.device)
         out = torch.empty((N, d) if cls_only else (N, T, d), dtype=torch.float32, device=pixels.device)
         L = c.num_hidden_layers
-        for n0 in range(0, N, self.chunk):
-            n = min(self.chunk, N - n0)
+        for n0, n in self._chunks(N):
             self._embed(ws, pixels[n0:n0 + n], n, aug.rows(n0, n0 + n) if aug is not None else None)
             for i in range(L):
                 if keep is not None and i >= first:
@@ -338,52 +330,29 @@ class NativeViT(FrozenBackbone):
         return self._run(pixel_values, cls_only=True, aug=aug)
 
     # -- the backward: the trainable layers' weight gradients ------------------------------------------------------------
-    def _grad_table(self) -> WsTable:
-        """what the backward holds beside the forward workspace, per image: the second LayerNorm's output (``ln`` keeps the first's:
-        the Q/K/V weight gradient reads it), the GELU output (``h`` keeps the raw fc1 output), both LayerNorms' statistics, the
-        attention backward's delta, and the gradient buffers (``ga`` / ``gb`` alternate as the d-wide gradients, ``dh`` is dg then
-        dh).  lse is the forward workspace's"""
-        c, T = self.config, self.T
-        d, H, I, f32 = c.hidden_size, c.num_attention_heads, c.intermediate_size, torch.float32
-        return [("ln2", T * d, BF16), ("g", T * I, BF16), ("ga", T * d, BF16), ("gb", T * d, BF16), ("dh", T * I, BF16),
-                ("dqkv", T * 3 * d, BF16), ("mean1", T, f32), ("rstd1", T, f32), ("mean2", T, f32), ("rstd2", T, f32), ("delta", H * T, f32)]
+    def _grad_table(self, size=None) -> WsTable:
+        """what the backward holds beside the forward workspace, per image: ``_grad_rows`` with the second LayerNorm's output
+        ``ln2`` (``ln`` keeps the first's: the Q/K/V weight gradient reads it).  lse is the forward workspace's"""
+        return self._grad_rows(self.T, "ln2")
 
     def grad_workspace_bytes_per_image(self) -> int:
         return self._bytes_per_item(self._grad_table())
-
-    def _grad_workspace(self, dev) -> dict:
-        g = self._gws
-        if g is not None and g["dev"] == dev and g["chunk"] == self.chunk:
-            return g
-        d = self.config.hidden_size
-        # beside the table: the LayerNorm backward's scratch, and where the key bias's column sum goes (it is not kept)
-        g = {"dev": dev, "chunk": self.chunk, "dgb": torch.empty(2 * d, dtype=torch.float32, device=dev),
-             "ln_ws": torch.empty(lib.load().mmf_layernorm_bwd_workspace_bytes(d) // 4, dtype=torch.float32, device=dev),
-             "junk": torch.empty(d, dtype=torch.float32, device=dev)}
-        for name, numel, dtype in self._grad_table():
-            g[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
-        self._gws = g
-        return g
 
     def _attn_bwd(self, ws, g, qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor, n: int, Tq: int) -> None:
         """``_attn``'s backward: dQ | dK | dV into the fused ``dqkv`` rows, laid out as ``qkv``.  ``Tq == 1`` (``mmf_vit_cls_attn_bwd``):
         the query and ``datt`` rows are one per image, dQ lands in the leading columns of each image's row 0 and the dQ columns
         of the other rows are not written"""
-        c, d, T = self.config, self.config.hidden_size, self.T
         if Tq == 1:
-            lib.vit_cls_attn_bwd(qkv, datt, dqkv, n, c.num_attention_heads, T, self.head_dim, self.head_dim ** -0.5)
+            lib.vit_cls_attn_bwd(qkv, datt, dqkv, n, self.config.num_attention_heads, self.T, self.head_dim, self.head_dim ** -0.5)
             return
-        q, dq = qkv.data_ptr(), dqkv.data_ptr()
-        lib.attn_bwd_grouped([lib.AttnProblem(q, q + 2 * d, q + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), datt.data_ptr(),
-                                              g["delta"].data_ptr(), dq, dq + 2 * d, dq + 4 * d, n, c.num_attention_heads, Tq, T,
-                                              3 * d if Tq == T else T * 3 * d, 3 * d, 3 * d, d)], self.head_dim, self.head_dim ** -0.5)
+        lib.attn_bwd_grouped([self._attn_problem(ws, qkv, att, n, Tq, self.T, datt, g["delta"], dqkv)], self.head_dim, self.head_dim ** -0.5)
 
     def _qkv_wgrad(self, i: int, g, dqkv: torch.Tensor, ln: torch.Tensor, n: int, cls: bool) -> None:
         """layer ``i``'s fused Q/K/V weight and bias gradients from ``dqkv`` and the first LayerNorm's output ``ln``
         (``FrozenBackbone._qkv_wgrad_roles``: the key bias takes no column sum).  ``cls``: dQ is row 0 of each image only, so the Q
         rows of the weight are a launch of their own over those ``n`` rows"""
         d = self.config.hidden_size
-        w, b = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad
+        w, b = self._grads(i, "qkv")
         over = self._first_touch(w)
         if cls:
             self._wgrad_launch([(self._row0(dqkv, n), self._row0(ln, n), w[:d], b[:d])], over)
@@ -398,9 +367,7 @@ class NativeViT(FrozenBackbone):
         m = n if cls else rows                                        # the rows behind the attention
         ln1, qkv, dqkv = R(ws, "ln", rows, d), R(ws, "qkv", rows, 3 * d), R(g, "dqkv", rows, 3 * d)
         att, h, ln2, gel, ga, gb, dh = R(ws, "att", m, d), R(ws, "h", m, I), R(g, "ln2", m, d), R(g, "g", m, I), R(g, "ga", m, d), R(g, "gb", m, d), R(g, "dh", m, I)
-        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        grads = lambda r: (getattr(self, f"l{i}_{r}_w").grad, getattr(self, f"l{i}_{r}_b").grad)
+        st1, st2 = self._stats(g, 1), self._stats(g, 2)
         slabs = lambda M, N: self._slabs_for(m, self._tiles(M, N))
         W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
         # the forward again, up to the GELU output (nothing behind fc2 is read by a pre-LN layer's backward)
@@ -418,7 +385,7 @@ class NativeViT(FrozenBackbone):
         lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
         self._wgrad(dh, ln2, f"l{i}_fc1", slabs(I, d))
         ops.gemm(GEMM_NN, dh, W("fc1"), gb)                                            # dln2
-        self._ln_bwd_add(st2, y, gb, ga, ga, f"l{i}_ln2_w", grads("ln2"))               # ga = dy: the MLP branch + the residual
+        self._ln_bwd(st2, y, gb, ga, f"l{i}_ln2_w", self._grads(i, "ln2"), resid=ga)   # ga = dy: the MLP branch + the residual
         # the attention
         self._wgrad(ga, att, f"l{i}_o", slabs(d, d))
         ops.gemm(GEMM_NN, ga, W("o"), gb)                                              # datt
@@ -427,7 +394,7 @@ class NativeViT(FrozenBackbone):
         gx, gl = R(g, "ga", rows, d), R(g, "gb", rows, d)
         if not cls:
             ops.gemm(GEMM_NN, dqkv, W("qkv"), gl)                                      # dln1
-            self._ln_bwd_add(st1, xin, gl, gx, gx, f"l{i}_ln1_w", grads("ln1"))        # ga = dx: the attention branch + the residual
+            self._ln_bwd(st1, xin, gl, gx, f"l{i}_ln1_w", self._grads(i, "ln1"), resid=gx)      # ga = dx: the attention branch + the residual
             return
         # dln1 = the K | V input gradient of every row + the Q one on row 0 of each image: the latter goes into a zeroed buffer
         # (``g``: the GELU output is done with) that the former's epilogue adds; the residual gradient reaches row 0 only, so it
@@ -438,7 +405,7 @@ class NativeViT(FrozenBackbone):
         ops.gemm(GEMM_NN, dqkv[:, d:], W("qkv")[d:], gl, aux=z, epilogue=EPI_ADD_AUX)
         resid.zero_()
         self._row0(resid, n).copy_(ga)
-        self._ln_bwd_add(st1, xin, gl, resid, gx, f"l{i}_ln1_w", grads("ln1"))
+        self._ln_bwd(st1, xin, gl, gx, f"l{i}_ln1_w", self._grads(i, "ln1"), resid=resid)
 
     def _backward(self, pixels: torch.Tensor, cls_only: bool, aug: Optional[VideoAug], keep: torch.Tensor, final: torch.Tensor,
                   first: int, embeddings: bool, dout: torch.Tensor) -> None:
@@ -446,14 +413,12 @@ class NativeViT(FrozenBackbone):
         ``first`` .. L - 1 and, with ``embeddings``, of the CLS token, the position embeddings and the patch projection, added
         into their ``.grad``.  ``keep``: the saved inputs of the layers from ``first`` up, ``final``: of the final LayerNorm"""
         c, d, dev = self.config, self.config.hidden_size, pixels.device
-        if ops.fp32_mode():
-            raise RuntimeError("NativeViT runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        self._refuse_fp32()
         N, T, L, NP, K = pixels.shape[0], self.T, c.num_hidden_layers, self.num_patches, self.patch_dim
         ws, g = self._workspace(dev), self._grad_workspace(dev)
-        st = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        st = self._stats(g, 1)
         dout = dout.view(N, -1)
-        for n0 in range(0, N, self.chunk):
-            n = min(self.chunk, N - n0)
+        for n0, n in self._chunks(N):
             rows, r0 = (n, n0) if cls_only else (n * T, n0 * T)
             ga, gb, xf = self._rows(g, "ga", rows, d), self._rows(g, "gb", rows, d), final[r0:r0 + rows]
             self._narrow(dout[n0:n0 + n], gb)

@@ -34,18 +34,10 @@ Fine-tuning.  ``set_trainable_layers(k, front=False)`` marks the parameters of l
 With grad mode on every call is then one ``torch.autograd.Function`` around the launch list above (the trainable parameters are
 its inputs, so the result carries a graph; there is no gradient with respect to the waveform) plus one copy per walked layer: it
 keeps the bf16 input of layers ``>= L - k`` and, with ``front``, ``feat``, the feature LayerNorm's input.  The backward, per chunk
-and per layer top down, runs the layer again from its saved input (both LayerNorms' statistics, the raw fc1 output beside the GELU
-output) and then
+and per layer top down, is the post-LN layer's (``_post_ln_layer_grad``, mmfusion/backbone.py has its rows) with
 
-      LayerNorm 2 backward          mmf_layernorm_bwd_grouped                gx -> dy2
-      fc2 wgrad, dgrad              mmf_gemm_grouped TN (COLSUM_A) / NN      dy2 -> dg
-      GELU backward                 mmf_bias_gelu_bwd_bf16 (in place)        dg, h -> dh
-      fc1 wgrad, dgrad + dy2        TN / NN, ADD_AUX                         dh -> dln1
-      LayerNorm 1 backward          mmf_layernorm_bwd_grouped                dln1 -> dy1
-      out-projection wgrad, dgrad   TN / NN                                  dy1 -> datt
       attention backward            mmf_attn_delta_f32, then                 datt -> dqkv (delta = sum_j p_ij dp_ij in f32, not dO . O
                                     mmf_attn_bwd_grouped_delta               from the bf16 O: see below)
-      Q/K/V wgrad, dgrad + dy1      TN / NN, ADD_AUX                         dqkv -> gx of the layer below
 
 (the dgrad of the lowest walked layer is not launched unless the front end trains).  The attention backward is the shared MFMA one
 with its delta as an input: its own delta = dO . O reads the bf16 O, so a row of dS sums to dO . (O - bf16(O)) instead of zero, an
@@ -75,7 +67,7 @@ import torch
 from . import arena as _arena
 from . import lib, ops
 from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
-from .lib import EPI_ADD_AUX, EPI_BIAS, GEMM_NN, GEMM_NT
+from .lib import EPI_BIAS, GEMM_NN, GEMM_NT
 
 # clips per pass through the workspace: 16 clips of 10 s give the layer GEMMs 7984 rows.  NOT chosen by measurement yet:
 # tools/w2v_bench.py --chunks is the sweep that should decide it
@@ -110,7 +102,7 @@ class _Differentiable(torch.autograd.Function):
         c = model.config
         N, T, L = wave.shape[0], model.frames(wave.shape[1]), c.num_hidden_layers
         first = L - model.trainable_layers                             # the lowest layer the backward walks
-        keep = torch.empty((L - first, N * T, c.hidden_size), dtype=BF16, device=wave.device)
+        keep = model._keep(first, N * T, wave.device)
         feat = torch.empty((N * T, c.conv_dim[-1]), dtype=BF16, device=wave.device) if model.trainable_front else None
         pos_w = model._pos_weight()
         out = model._launches(wave, pos_w, keep, first, feat)
@@ -228,16 +220,9 @@ class NativeWav2Vec2(FrozenBackbone):
         graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops
         below layer ``L - k``.  There is no gradient with respect to the waveform; SpecAugment masking, the backbone's dropout and
         LayerDrop are not built; the fp32 parity mode is refused as everywhere in this class."""
-        L = self.config.num_hidden_layers
-        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= L:
-            raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}): an integer in 0 .. {L} (num_hidden_layers)")
-        if not isinstance(front, bool) or (front and k != L):
-            raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}, front={front!r}): the front end trains with all "
-                             f"{L} layers only (its gradient comes through every layer)")
+        self._check_trainable(k, "front", front, "the front end trains", "its gradient comes through every layer")
         self._trainable, self._front = k, front
-        names = set(self._trainable_names())
-        for name, p in self.named_parameters(recurse=False):
-            p.requires_grad_(name in names)
+        self._require_grad(self._trainable_names())
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
     def _canonical_key(self, key: str) -> str:
@@ -350,8 +335,7 @@ class NativeWav2Vec2(FrozenBackbone):
         T, d = Ts[-1], c.hidden_size
         ws = self._workspace(wave.device, L)
         out = torch.empty((N, T, d), dtype=torch.float32, device=wave.device)
-        for n0 in range(0, N, self.chunk):
-            n = min(self.chunk, N - n0)
+        for n0, n in self._chunks(N):
             rows = n * T
             feat = self._features(ws, wave[n0:n0 + n], n, Ts)
             if feat_keep is not None:
@@ -368,35 +352,20 @@ class NativeWav2Vec2(FrozenBackbone):
 
     # -- the backward: the trainable layers' and the front end's weight gradients ---------------------------------------
     def _grad_table(self, L: int) -> WsTable:
-        """what the backward holds beside the forward workspace, per clip of ``L`` samples: the second pre-LN sum, the GELU output
-        (``h`` keeps the raw fc1 output), both LayerNorms' statistics, the attention backward's delta, the gradient buffers
-        (``ga`` / ``gb`` alternate as the d-wide gradients, ``dh`` is dg then dh; the front end's dz takes ``dqkv``'s place) and
-        the two conv_dim[-1]-wide gradients around the feature LayerNorm.  lse is the forward workspace's"""
-        c, T = self.config, self.frames(L)
-        d, H, I, cd, f32 = c.hidden_size, c.num_attention_heads, c.intermediate_size, c.conv_dim[-1], torch.float32
-        return [("y2", T * d, BF16), ("g", T * I, BF16), ("ga", T * d, BF16), ("gb", T * d, BF16), ("dh", T * I, BF16),
-                ("dqkv", T * 3 * d, BF16), ("dfln", T * cd, BF16), ("dfeat", T * cd, BF16), ("mean1", T, f32), ("rstd1", T, f32),
-                ("mean2", T, f32), ("rstd2", T, f32), ("delta", H * T, f32)]
+        """what the backward holds beside the forward workspace, per clip of ``L`` samples: the layers' part (``_grad_rows``; the
+        front end's dz takes ``dqkv``'s place) and the two conv_dim[-1]-wide gradients around the feature LayerNorm.  lse is the
+        forward workspace's"""
+        T, cd = self.frames(L), self.config.conv_dim[-1]
+        return self._grad_rows(T) + [("dfln", T * cd, BF16), ("dfeat", T * cd, BF16)]
 
     def grad_workspace_bytes_per_clip(self, L: int) -> int:
         return self._bytes_per_item(self._grad_table(L))
 
-    def _grad_workspace(self, dev, L: int) -> dict:
-        g = self._gws
-        if g is not None and g["dev"] == dev and g["chunk"] == self.chunk and g["size"] >= L:
-            return g
-        c = self.config
-        d, cd, nbytes = c.hidden_size, c.conv_dim[-1], lib.load().mmf_layernorm_bwd_workspace_bytes
-        # beside the table: the LayerNorm backward's scratch (at the wider of its two widths), where the key bias's column sum
-        # goes (it is not kept), and the positional weight's f32 gradient in the packed layout, summed over a backward's chunks
-        g = {"dev": dev, "chunk": self.chunk, "size": L, "dgb": torch.empty(2 * max(d, cd), dtype=torch.float32, device=dev),
-             "ln_ws": torch.empty(max(nbytes(d), nbytes(cd)) // 4, dtype=torch.float32, device=dev),
-             "junk": torch.empty(d, dtype=torch.float32, device=dev),
-             "dpos": torch.empty(d * self.pos_kp, dtype=torch.float32, device=dev)}
-        for name, numel, dtype in self._grad_table(L):
-            g[name] = torch.empty(self.chunk * numel, dtype=dtype, device=dev)
-        self._gws = g
-        return g
+    def _grad_scratch(self) -> Tuple[int, Dict[str, int]]:
+        """the LayerNorm backward's scratch at the wider of its two widths; ``dpos``: the positional weight's f32 gradient in the
+        packed layout, summed over a backward's chunks"""
+        d, extra = super()._grad_scratch()
+        return max(d, self.config.conv_dim[-1]), {**extra, "dpos": d * self.pos_kp}
 
     def _pos_wgrad_slabs(self, n: int, T: int) -> int:
         """The slab count of ``mmf_w2v_posconv_wgrad`` on a chunk of ``n`` clips: its grid is (tap blocks, groups) workgroups of
@@ -413,40 +382,11 @@ class NativeWav2Vec2(FrozenBackbone):
         """layer ``i`` again from its saved input ``xin``, then its backward with the weight, bias and LayerNorm gradients added
         into the parameters' ``.grad``: ``ga`` holds the gradient of the layer's output on entry and, with ``below``, of ``xin``
         on return"""
-        c = self.config
-        rows, d, I, R = n * T, c.hidden_size, c.intermediate_size, self._rows
-        ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
-        ln, h, qkv, att = R(ws, "ln", rows, d), R(ws, "h", rows, I), R(ws, "qkv", rows, 3 * d), R(ws, "att", rows, d)
-        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        grads = lambda r: (getattr(self, f"l{i}_{r}_w").grad, getattr(self, f"l{i}_{r}_b").grad)
-        slabs = lambda M, N: self._slabs_for(rows, self._tiles(M, N))
-        W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
-        # the forward again: both LayerNorms' statistics, the raw fc1 output and the GELU output side by side
-        y1 = self._attention(i, ws, xin, xin, n, T)
-        self._ln(st1, y1, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        ops.gemm(GEMM_NT, ln, W("fc1"), h)
-        lib.bias_gelu_to(h, F("fc1"), gel)
-        ops.gemm(GEMM_NT, gel, W("fc2"), y2, bias=F("fc2"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
-        self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
-        # the MLP
-        self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w", grads("ln2"))                    # gb = dy2
-        self._wgrad(gb, gel, f"l{i}_fc2", slabs(d, I))
-        ops.gemm(GEMM_NN, gb, W("fc2"), dh)                                           # dg
-        lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
-        self._wgrad(dh, ln, f"l{i}_fc1", slabs(I, d))
-        ops.gemm(GEMM_NN, dh, W("fc1"), ga, aux=gb, epilogue=EPI_ADD_AUX)             # ga = dln1: the MLP branch + the residual
-        # the attention
-        self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w", grads("ln1"))                    # gb = dy1
-        self._wgrad(gb, att, f"l{i}_o", slabs(d, d))
-        ops.gemm(GEMM_NN, gb, W("o"), ga)                                             # ga = datt
-        q, dq = qkv.data_ptr(), dqkv.data_ptr()
-        lib.attn_bwd_grouped_exact_delta([lib.AttnProblem(q, q + 2 * d, q + 4 * d, att.data_ptr(), ws["lse"].data_ptr(), ga.data_ptr(),
-                                              g["delta"].data_ptr(), dq, dq + 2 * d, dq + 4 * d, n, c.num_attention_heads, T, T,
-                                              3 * d, 3 * d, 3 * d, d)], self.head_dim, self.head_dim ** -0.5)
-        self._qkv_wgrad_roles(i, g["junk"], dqkv, xin)
-        if below:
-            ops.gemm(GEMM_NN, dqkv, W("qkv"), ga, aux=gb, epilogue=EPI_ADD_AUX)       # ga = dx: the attention branch + the residual
+        def attn_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor) -> None:
+            lib.attn_bwd_grouped_exact_delta([self._attn_problem(ws, qkv, att, n, T, T, datt, g["delta"], dqkv)], self.head_dim,
+                                             self.head_dim ** -0.5)
+        self._post_ln_layer_grad(i, ws, g, xin, n, T, None, attn_bwd, lambda dqkv, x: self._qkv_wgrad_roles(i, g["junk"], dqkv, x),
+                                 below, self._slabs_for)
 
     def _front_grad(self, ws, g, feat: torch.Tensor, pos_w: torch.Tensor, pos_wt: torch.Tensor, n: int, T: int) -> None:
         """the front end again from the saved ``feat``, then its backward: ``ga`` holds the gradient of layer 0's input on entry.
@@ -457,8 +397,7 @@ class NativeWav2Vec2(FrozenBackbone):
         G, k = c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
         x0, y, fln = R(ws, "x", rows, d), R(ws, "y", rows, d), R(ws, "win", rows, cd)
         ga, gb, dz, dfln, dfeat = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dqkv", rows, d), R(g, "dfln", rows, cd), R(g, "dfeat", rows, cd)
-        st1 = {"mean": g["mean1"], "rstd": g["rstd1"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
-        st2 = {"mean": g["mean2"], "rstd": g["rstd2"], "dgb": g["dgb"], "ln_ws": g["ln_ws"]}
+        st1, st2 = self._stats(g, 1), self._stats(g, 2)
         self._front_end(ws, feat, pos_w, n, T, st1)
         self._ln(st2, y, R(ws, "ln", rows, d), "enc_ln_w", "enc_ln_b")               # for its statistics; the output is not read
         self._ln_bwd(st2, y, ga, gb, "enc_ln_w", (self.enc_ln_w.grad, self.enc_ln_b.grad))          # gb = dy
@@ -483,16 +422,14 @@ class NativeWav2Vec2(FrozenBackbone):
         saved input of the feature LayerNorm: the front end trains), of the front end, added into their ``.grad``.  ``keep``: the
         saved inputs of the layers from ``first`` up, ``pos_w``: the positional weight the forward used"""
         c, d, dev = self.config, self.config.hidden_size, wave.device
-        if ops.fp32_mode():
-            raise RuntimeError("NativeWav2Vec2 runs with bf16 storage only: it has no form for the fp32 parity mode (and no eager fallback)")
+        self._refuse_fp32()
         N, Lw = wave.shape
         T, L, front = self.frames(Lw), c.num_hidden_layers, feat is not None
         ws, g = self._workspace(dev, Lw), self._grad_workspace(dev, Lw)
         if front:
             pos_wt = self._pos_weight(transposed=True)
             g["dpos"].zero_()
-        for n0 in range(0, N, self.chunk):
-            n = min(self.chunk, N - n0)
+        for n0, n in self._chunks(N):
             rows = slice(n0 * T, (n0 + n) * T)
             self._narrow(dout[n0:n0 + n], self._rows(g, "ga", n * T, d))
             for i in reversed(range(first, L)):
