@@ -826,6 +826,42 @@ int mmf_deberta_attn_bwd_pos(const void* qkv_bf16, const void* posq_bf16, const 
                              const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
                              float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale,
                              float* dposq, float* dposk, int ld_dpos, void* workspace, size_t workspace_bytes, void* stream);
+/* Training-mode dropout (mmfusion/deberta.py: HuggingFace's DebertaV2Model in train()).  Every mask is a stateless hash of
+ * (*rng_state, site, sub-stream, index) by mmf_dropout's counter hash, with p quantised to 2^-32 and c = 1 / (1 - p) as
+ * mmf_dropout forms them, and is keyed by the ELEMENT, never by the launch: `item0` is the index, in the whole batch, of the
+ * call's first item, so a batch cut into chunks draws what one call would, and a backward regenerates the forward's mask from
+ * the same (state, site, item0) instead of reading a stored one.  The codes these four add to the plain entry points': p outside
+ * [0, 1) (NaN included), item0 < 0, or a NULL rng_state with a non-zero threshold: MMF_E_SHAPE; rng_state not 8-byte aligned:
+ * MMF_E_ALIGN.  Nothing is launched on an error.
+ *
+ * mmf_deberta_attn_fwd with dropout of the probabilities (softmax -> dropout -> @ V): pair (query i, key j) of head h of item g is
+ * kept where the hash of sub-stream (item0 + g) H + h at index i T + j passes, out_i = sum_j keep_ij c P_ij V_j.  The softmax
+ * statistics run over the undropped probabilities: lse (NULL: not written) is bit-identical to mmf_deberta_attn_fwd_lse's.  A
+ * threshold of 0 (p = 0) runs mmf_deberta_attn_fwd / _lse's own kernels: their bits, and rng_state may be NULL. */
+int mmf_deberta_attn_fwd_drop(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                              const void* mask, int mask_kind, void* out_bf16, float* lse, int n, int H, int T, int S, int head_dim,
+                              float scale, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
+/* mmf_deberta_attn_bwd / mmf_deberta_attn_bwd_pos of that forward (out_bf16 / lse as it wrote them, the same p, state, site and
+ * item0): with w_ij = keep_ij c, dS_ij = c' P_ij (w_ij dO_i.V_j - delta_i) (c' = 1 / scale) and dV_j = sum_i w_ij P_ij dO_i; delta,
+ * dQ, dK and the table gradients follow from that dS unchanged.  Both passes regenerate the forward's bits.  The plain entry points'
+ * operands, launches, limits and codes; dqkv_bf16 of the _pos form is bit-identical to the other's; a threshold of 0 runs the plain
+ * kernels. */
+int mmf_deberta_attn_bwd_drop(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                              const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                              float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale, float p,
+                              const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
+int mmf_deberta_attn_bwd_pos_drop(const void* qkv_bf16, const void* posq_bf16, const void* posk_bf16, int ld_pos, const int* idx,
+                                  const void* mask, int mask_kind, const void* out_bf16, const float* lse, const void* dout_bf16,
+                                  float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale,
+                                  float* dposq, float* dposk, int ld_dpos, void* workspace, size_t workspace_bytes, float p,
+                                  const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
+/* Hidden dropout over `items` items of per_item elements each, one pass: element e of item g is kept where the hash of sub-stream
+ * item0 + g at index e passes.  bf16 (is_f32 0): out = bf16(fma(y, c, resid)) where kept, resid where dropped: one f32 multiply-add,
+ * one rounding; resid_bf16 NULL: 0 (the plain dropout and, on a gradient, its backward).  f32 (is_f32 1, resid_bf16 NULL): out =
+ * y c where kept, 0 where dropped.  out may be y or resid.  A threshold of 0 copies (c = 1, everything kept) and still needs
+ * rng_state.  per_item % 8 == 0, per_item <= 2^31, items < 2^31 (else MMF_E_UNSUPPORTED); y / resid / out 16-byte aligned. */
+int mmf_deberta_dropout(const void* y, const void* resid_bf16, void* out, int is_f32, int64_t items, int64_t per_item, float p,
+                        const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
 /* Backward of mmf_deberta_embed on the embeds route: d_embeds (rows, d) f32 = mask[row] * the LayerNorm input gradient of
  * dout_bf16 (rows, d), the gradient of the kernel's bf16 output.  The row statistics are recomputed in f32 from embeds as the
  * forward computes them; rows with mask 0 are exactly 0.  mmf_deberta_embed's limits on d; embeds / gamma / d_embeds 16-byte

@@ -14,6 +14,8 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
       fc1                           mmf_gemm_grouped NT                  src -> h (rows, intermediate)
       + bias, exact GELU            mmf_bias_gelu_bf16 (in place)        h
       fc2 + bias + resid            mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> out
+    (both blocks end in ``_closing``: with a model's ``join`` hook the closing launch is BIAS only and ``join(role, y, resid)`` makes
+     the sum; DeBERTa's training-mode dropout, mmfusion/deberta.py.  Without one, the rows above.)
     _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
     _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
     _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; the backbones' backward)
@@ -75,6 +77,11 @@ WsTable = List[Tuple[str, int, torch.dtype]]
 Attend = Callable[[torch.Tensor, torch.Tensor], None]          # (qkv rows, att rows): launches one chunk's attention
 AttnBwd = Callable[[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor], None]     # (qkv, att, datt, dqkv rows): its backward
 QkvWgrad = Callable[[torch.Tensor, torch.Tensor], None]        # (dqkv rows, the projection's input rows): the fused weight's gradient
+# What stands between a block's closing dense launch and its LayerNorm where a model has something there (DeBERTa's training-mode
+# dropout; absent: the residual add is the GEMM's epilogue).  Join(role, y, resid): role "o" / "fc2", y = dense + bias as bf16 -> the
+# pre-LN sum, in place.  JoinBwd(role, dy, out): the gradient dy of that sum -> out, the dense branch's share of it
+Join = Callable[[str, torch.Tensor, torch.Tensor], None]
+JoinBwd = Callable[[str, torch.Tensor, torch.Tensor], None]
 
 
 class BackboneOutput:
@@ -454,12 +461,23 @@ class FrozenBackbone(nn.Module):
     def _attn(self, ws, qkv: torch.Tensor, att: torch.Tensor, n: int, Tq: int, T: int) -> None:
         lib.attn_fwd_grouped([self._attn_problem(ws, qkv, att, n, Tq, T)], self.head_dim, self.head_dim ** -0.5)
 
-    def _out_proj(self, i: int, att: torch.Tensor, resid: torch.Tensor, y: torch.Tensor) -> None:
-        ops.gemm(GEMM_NT, att, self._w(f"l{i}_o_w"), y, bias=self._f(f"l{i}_o_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
+    def _closing(self, i: int, role: str, src: torch.Tensor, resid: torch.Tensor, y: torch.Tensor, join: Optional[Join]) -> None:
+        """y = resid + src W^T + b, the dense launch that closes a block (``role`` "o" / "fc2"): the residual add is its epilogue;
+        with ``join`` the launch writes src W^T + b and ``join(role, y, resid)`` makes the sum of it"""
+        w, b = self._w(f"l{i}_{role}_w"), self._f(f"l{i}_{role}_b")
+        if join is None:
+            ops.gemm(GEMM_NT, src, w, y, bias=b, aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        else:
+            ops.gemm(GEMM_NT, src, w, y, bias=b, epilogue=EPI_BIAS)
+            join(role, y, resid)
 
-    def _attention(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, n: int, T: int, attend: Optional[Attend] = None) -> torch.Tensor:
+    def _out_proj(self, i: int, att: torch.Tensor, resid: torch.Tensor, y: torch.Tensor, join: Optional[Join] = None) -> None:
+        self._closing(i, "o", att, resid, y, join)
+
+    def _attention(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, n: int, T: int, attend: Optional[Attend] = None,
+                   join: Optional[Join] = None) -> torch.Tensor:
         """-> y = resid + out_proj(attention(qkv(src))) on the ``n * T`` rows of a chunk; ``attend(qkv, att)`` launches the
-        attention, None: the fused one (``_attn``)"""
+        attention, None: the fused one (``_attn``); ``join``: ``_closing``'s"""
         rows, d = n * T, self.config.hidden_size
         qkv, att, y = self._rows(ws, "qkv", rows, 3 * d), self._rows(ws, "att", rows, d), self._rows(ws, "y", rows, d)
         ops.gemm(GEMM_NT, src, self._w(f"l{i}_qkv_w"), qkv, bias=self._f(f"l{i}_qkv_b"), epilogue=EPI_BIAS)
@@ -467,32 +485,37 @@ class FrozenBackbone(nn.Module):
             self._attn(ws, qkv, att, n, T, T)
         else:
             attend(qkv, att)
-        self._out_proj(i, att, resid, y)
+        self._out_proj(i, att, resid, y, join)
         return y
 
-    def _ffn(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, out: torch.Tensor) -> None:
-        """out = resid + fc2(gelu(fc1(src) + b1)) + b2 on the rows of ``src``"""
+    def _ffn(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, out: torch.Tensor, join: Optional[Join] = None) -> None:
+        """out = resid + fc2(gelu(fc1(src) + b1)) + b2 on the rows of ``src``; ``join``: ``_closing``'s"""
         h = self._rows(ws, "h", src.shape[0], self.config.intermediate_size)
         ops.gemm(GEMM_NT, src, self._w(f"l{i}_fc1_w"), h)
         lib.bias_gelu(h, self._f(f"l{i}_fc1_b"))
-        ops.gemm(GEMM_NT, h, self._w(f"l{i}_fc2_w"), out, bias=self._f(f"l{i}_fc2_b"), aux=resid, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        self._closing(i, "fc2", h, resid, out, join)
 
-    def _post_ln_layer(self, i: int, ws, n: int, T: int, attend: Optional[Attend] = None) -> None:
-        """x = LayerNorm(ln + ffn(ln)), ln = LayerNorm(x + attention(x)) on the ``n * T`` rows of ``x``"""
+    def _post_ln_layer(self, i: int, ws, n: int, T: int, attend: Optional[Attend] = None, join: Optional[Join] = None) -> None:
+        """x = LayerNorm(ln + ffn(ln)), ln = LayerNorm(x + attention(x)) on the ``n * T`` rows of ``x``; ``join``: ``_closing``'s"""
         rows, d = n * T, self.config.hidden_size
         x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
-        y = self._attention(i, ws, x, x, n, T, attend)
+        y = self._attention(i, ws, x, x, n, T, attend, join)
         self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        self._ffn(i, ws, ln, ln, y)
+        self._ffn(i, ws, ln, ln, y, join)
         self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
 
     def _post_ln_layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, attend: Optional[Attend], attn_bwd: AttnBwd,
-                            qkv_wgrad: Optional[QkvWgrad], below: bool = True, slabs: Optional[Callable[[int, int], int]] = None) -> None:
+                            qkv_wgrad: Optional[QkvWgrad], below: bool = True, slabs: Optional[Callable[[int, int], int]] = None,
+                            join: Optional[Join] = None, join_bwd: Optional[JoinBwd] = None) -> None:
         """``_post_ln_layer`` ``i`` again from its saved input ``xin``, then its backward (the module docstring has the rows):
         ``ga`` holds the gradient of the layer's output on entry and, with ``below``, of ``xin`` on return.  ``attend`` as in
         ``_attention``; it leaves the lse where ``attn_bwd(qkv, att, datt, dqkv)`` reads it.  With ``qkv_wgrad(dqkv, xin)`` the
         layer trains: its weight, bias and LayerNorm gradients are added into the parameters' ``.grad``, the four plain weights'
-        in ``slabs(rows, tiles)`` K-slabs (``_slabs_for``; None: plain launches).  Without, no weight gradient is formed"""
+        in ``slabs(rows, tiles)`` K-slabs (``_slabs_for``; None: plain launches).  Without, no weight gradient is formed.
+        ``join`` / ``join_bwd`` (both or neither): the forward's ``_closing`` hook and its gradient.  The gradient of a pre-LN sum
+        then reaches the residual branch as it is and the dense branch (the closing launch's weight and input gradients) as
+        ``join_bwd(role, dy, out)`` leaves it in ``out``: the second pre-LN sum's buffer, which is free once LayerNorm 2's backward
+        has read it"""
         c = self.config
         rows, d, I, R, train = n * T, c.hidden_size, c.intermediate_size, self._rows, qkv_wgrad is not None
         ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
@@ -504,23 +527,30 @@ class FrozenBackbone(nn.Module):
             if train:
                 self._wgrad(dy, x, f"l{i}_{r}", slabs(rows, self._tiles(M, N)) if slabs else 1)
         # the forward again: both LayerNorms' statistics, the raw fc1 output and the GELU output side by side
-        y1 = self._attention(i, ws, xin, xin, n, T, attend)
+        def dense_grad(role: str, dy: torch.Tensor) -> torch.Tensor:
+            if join_bwd is None:
+                return dy
+            join_bwd(role, dy, y2)
+            return y2
+        y1 = self._attention(i, ws, xin, xin, n, T, attend, join)
         self._ln(st1, y1, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
         ops.gemm(GEMM_NT, ln, W("fc1"), h)
         lib.bias_gelu_to(h, F("fc1"), gel)
-        ops.gemm(GEMM_NT, gel, W("fc2"), y2, bias=F("fc2"), aux=ln, epilogue=EPI_BIAS | EPI_ADD_AUX)
+        self._closing(i, "fc2", gel, ln, y2, join)
         self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
         # the MLP
         self._ln_bwd(st2, y2, ga, gb, f"l{i}_ln2_w", self._grads(i, "ln2") if train else None)          # gb = dy2
-        wgrad(gb, gel, "fc2", d, I)
-        ops.gemm(GEMM_NN, gb, W("fc2"), dh)                                           # dg
+        gd = dense_grad("fc2", gb)
+        wgrad(gd, gel, "fc2", d, I)
+        ops.gemm(GEMM_NN, gd, W("fc2"), dh)                                           # dg
         lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
         wgrad(dh, ln, "fc1", I, d)
         ops.gemm(GEMM_NN, dh, W("fc1"), ga, aux=gb, epilogue=EPI_ADD_AUX)             # ga = dln1: the MLP branch + the residual
         # the attention
         self._ln_bwd(st1, y1, ga, gb, f"l{i}_ln1_w", self._grads(i, "ln1") if train else None)          # gb = dy1
-        wgrad(gb, att, "o", d, d)
-        ops.gemm(GEMM_NN, gb, W("o"), ga)                                             # ga = datt
+        gd = dense_grad("o", gb)
+        wgrad(gd, att, "o", d, d)
+        ops.gemm(GEMM_NN, gd, W("o"), ga)                                             # ga = datt
         attn_bwd(qkv, att, ga, dqkv)
         if train:
             qkv_wgrad(dqkv, xin)

@@ -87,6 +87,26 @@ of a table row owns it.  ``rel`` is then computed in every call too (nothing der
 gradients are plain accumulating regions of the arena (never first-touch managed: a scatter cannot overwrite the rows it does not
 visit), so ``zero_grad`` clears them by memset.  On the prompt route ``embeddings.word_embeddings(input_ids)`` carries a graph in
 this mode and its backward scatters the gradient of ``inputs_embeds`` into the table.
+
+Dropout.  HuggingFace's model in ``train()`` drops at five sites, and the reference trains it that way; here they are opt-in
+(``hidden_dropout_prob`` / ``attention_probs_dropout_prob``, both 0 by default, or ``set_dropout``) and act only in a call that has
+``self.training``, a probability above 0 and the differentiable route; every other call is the launch lists above, bit for bit.
+
+    1  embeddings                 mmf_deberta_dropout (in place)       x = dropout(LayerNorm(..) * mask)
+    2  relative embeddings        mmf_deberta_dropout, once per layer  rel_i = dropout_i(rel); posQ_i | posK_i from rel_i, every call
+    3  attention probabilities    mmf_deberta_attn_fwd_drop            softmax -> dropout -> @ V, inside the kernel
+    4  attention output           NT, BIAS; mmf_deberta_dropout        y = bf16(fma(dense + bias, keep c, x))
+    5  MLP output                 NT, BIAS; mmf_deberta_dropout        y = bf16(fma(dense + bias, keep c, ln))
+
+Sites 1, 2, 4, 5 take ``hidden_dropout_prob``, site 3 ``attention_probs_dropout_prob``; a probability of 0 leaves its sites' launches
+as they are without dropout.  A call takes 1 + 4 L sites from ``ops.next_site()`` in that order (``_Drop``) and keeps them for its
+backward; masks are the counter hash of (``ops.rng_state()``, site, sub-stream, index) with sub-stream = the item's index in the
+batch (attention: that times H plus the head; ``rel_i``: 0) and index = the element's within the item, so no result depends on
+``chunk``, and the backward draws every mask again instead of storing it: the recomputed layer regenerates sites 3 - 5, the gradient
+of a pre-LN sum reaches the dense branch through ``mmf_deberta_dropout`` (the residual branch takes it as it is), the attention
+backward is ``mmf_deberta_attn_bwd_drop`` / ``_pos_drop``, ``dW_qkv[:2d] += bf16(dpos_i)^T rel_i`` with ``rel_i`` drawn again, and
+d rel = sum_i keep_i c (bf16(dpos_i) W_qk,i): one NN GEMM per layer into its own f32 slab, masked there, then ``mmf_sum_slabs_f32``.
+Called on its own (no root module's forward around it) such a call advances the RNG state itself, so successive calls draw new masks.
 """
 from __future__ import annotations
 
@@ -166,6 +186,25 @@ class _WordEmbeddings:
             return torch.nn.functional.embedding(input_ids, self.weight)
 
 
+class _Drop:
+    """The dropout of one differentiable training call: the two probabilities and the call's sites, taken from ``ops.next_site()``
+    in HuggingFace's order (the embeddings, then per layer the relative embeddings, the attention probabilities, the attention
+    output, the MLP output).  The state is read where a launch is made (``ops.rng_state()``, live: the backward draws the
+    forward's masks from the same state, as ``ops._Dropout.backward`` does)."""
+    REL, PROBS, OUT, MLP = range(4)
+
+    def __init__(self, p_h: float, p_a: float, layers: int):
+        self.p_h, self.p_a = p_h, p_a
+        self.emb = ops.next_site()
+        self.layers = [tuple(ops.next_site() for _ in range(4)) for _ in range(layers)]
+
+    def hidden(self, site: int, item0: int) -> tuple:
+        return self.p_h, ops.rng_state(), site, item0
+
+    def probs(self, i: int, item0: int) -> Optional[tuple]:
+        return (self.p_a, ops.rng_state(), self.layers[i][self.PROBS], item0) if self.p_a > 0.0 else None
+
+
 class _Differentiable(torch.autograd.Function):
     """``NativeDeberta._run``, differentiable with respect to ``inputs_embeds`` and to the parameters of the trainable layers
     and, with them all, the embedding-side parameters.  ``params`` are those parameters: they are inputs so that the result
@@ -173,7 +212,8 @@ class _Differentiable(torch.autograd.Function):
     own launches, as ``ops.queue_wgrad``'s are."""
 
     @staticmethod
-    def forward(ctx, model: "NativeDeberta", src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, *params) -> torch.Tensor:
+    def forward(ctx, model: "NativeDeberta", src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, drop: Optional[_Drop],
+                *params) -> torch.Tensor:
         N, T = src.shape[:2]
         L = model.config.num_hidden_layers
         need_in = not by_ids and ctx.needs_input_grad[1]
@@ -181,10 +221,10 @@ class _Differentiable(torch.autograd.Function):
         first = 0 if need_in or emb else L - model.trainable_layers   # the lowest layer the backward walks
         keep = model._keep(first, N * T, src.device)
         _arena.ensure(model)
-        rel, pos = model._pos_state(src.device)
-        out = model._run(src, mask, by_ids, keep, first, pos)
+        rel, pos = model._pos_state(src.device, drop)
+        out = model._run(src, mask, by_ids, keep, first, pos, drop)
         ctx.model, ctx.mask, ctx.by_ids, ctx.first, ctx.pos, ctx.k = model, mask, by_ids, first, pos, model.trainable_layers
-        ctx.rel, ctx.emb = rel, emb
+        ctx.rel, ctx.emb, ctx.drop = rel, emb, drop
         ctx.save_for_backward(src, keep)
         return out
 
@@ -192,12 +232,12 @@ class _Differentiable(torch.autograd.Function):
     def backward(ctx, dout: torch.Tensor):
         src, keep = ctx.saved_tensors
         need_in = not ctx.by_ids and ctx.needs_input_grad[1]
-        k = ctx.k if any(ctx.needs_input_grad[4:]) else 0         # (torch.autograd.grad for the embeddings alone: no weight gradients)
+        k = ctx.k if any(ctx.needs_input_grad[5:]) else 0         # (torch.autograd.grad for the embeddings alone: no weight gradients)
         grad = None
         if need_in or k:
             grad = ctx.model._backward(src, ctx.by_ids, ctx.mask, keep, ctx.first, ctx.pos, ctx.rel, dout.contiguous(), need_in, k,
-                                       ctx.emb and k > 0)
-        return (None, grad, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
+                                       ctx.emb and k > 0, ctx.drop)
+        return (None, grad, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 5)
 
 
 class NativeDeberta(FrozenBackbone):
@@ -216,7 +256,8 @@ class NativeDeberta(FrozenBackbone):
                  layer_norm_eps: float = 1e-7, relative_attention: bool = True, share_att_key: bool = True,
                  pos_att_type=("p2c", "c2p"), norm_rel_ebd: str = "layer_norm", position_biased_input: bool = False,
                  type_vocab_size: int = 0, conv_kernel_size: int = 0, max_relative_positions: int = -1, hidden_act: str = "gelu",
-                 embedding_size: Optional[int] = None, chunk: int = DEFAULT_CHUNK):
+                 embedding_size: Optional[int] = None, chunk: int = DEFAULT_CHUNK, hidden_dropout_prob: float = 0.0,
+                 attention_probs_dropout_prob: float = 0.0):
         d, H, I, S = int(hidden_size), int(num_attention_heads), int(intermediate_size), int(position_buckets)
         who = "NativeDeberta"
         pos = sorted(p.strip() for p in (pos_att_type.split("|") if isinstance(pos_att_type, str) else (pos_att_type or ())))
@@ -253,7 +294,8 @@ class NativeDeberta(FrozenBackbone):
             intermediate_size=I, max_position_embeddings=int(max_position_embeddings), position_buckets=S,
             layer_norm_eps=float(layer_norm_eps), relative_attention=True, share_att_key=True, pos_att_type=["p2c", "c2p"],
             norm_rel_ebd="layer_norm", position_biased_input=False, type_vocab_size=0, max_relative_positions=-1,
-            hidden_act="gelu", model_type="deberta-v2")
+            hidden_act="gelu", model_type="deberta-v2", hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+        self.set_dropout(hidden_dropout_prob, attention_probs_dropout_prob)
         add = self._add
         add("word_emb", (vocab_size, d), "embeddings.word_embeddings.weight")
         add("emb_ln_w", (d,), "embeddings.LayerNorm.weight", ones=True)
@@ -270,6 +312,29 @@ class NativeDeberta(FrozenBackbone):
         self._idx: Dict[Tuple, torch.Tensor] = {}      # (T, S, max position, device) -> the int32 table on that device
         self._embeddings = False                       # set_trainable_layers(L, embeddings=True)
 
+    # -- dropout -------------------------------------------------------------------------------------------
+    def set_dropout(self, hidden: float = 0.0, attention: float = 0.0) -> None:
+        """``config.hidden_dropout_prob`` (the embeddings, every layer's relative embeddings, attention output and MLP output) and
+        ``config.attention_probs_dropout_prob`` (the attention probabilities), each in [0, 1); HuggingFace's deberta-v3-base has 0.1
+        for both, the default here is 0 for both: off.  They act in training mode, on the differentiable route only (grad mode on
+        and something to train: ``set_trainable_layers`` or ``inputs_embeds.requires_grad``); ``eval()`` and ``no_grad`` calls are
+        the inference launches whatever the values."""
+        for name, p in (("hidden", hidden), ("attention", attention)):
+            if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p < 1.0:
+                raise ValueError(f"NativeDeberta: set_dropout({name}={p!r}): a probability in [0, 1)")
+        self.config.hidden_dropout_prob, self.config.attention_probs_dropout_prob = float(hidden), float(attention)
+
+    def _drop_of_call(self) -> Optional[_Drop]:
+        """the dropout of the differentiable call that is about to run: None unless the module trains with a probability above 0.
+        A call on its own starts a training forward itself (new masks, sites from 1); under a root module's forward it continues
+        that forward's site numbering"""
+        c = self.config
+        if not self.training or (c.hidden_dropout_prob <= 0.0 and c.attention_probs_dropout_prob <= 0.0):
+            return None
+        if not ops.inside_root():
+            ops.begin_training_forward()
+        return _Drop(c.hidden_dropout_prob, c.attention_probs_dropout_prob, c.num_hidden_layers)
+
     # -- fine-tuning -------------------------------------------------------------------------------------
     _EMBEDDING_PARAMS = ("word_emb", "emb_ln_w", "emb_ln_b", "rel_emb", "enc_ln_w", "enc_ln_b")
 
@@ -285,7 +350,7 @@ class NativeDeberta(FrozenBackbone):
         With grad mode on and ``k > 0`` a call returns a result that carries a graph, and its backward adds those parameters'
         gradients into their f32 ``.grad`` (the module's parameter arena) and stops below layer ``L - k`` unless ``inputs_embeds``
         or the embeddings need a gradient too.  Without ``embeddings`` the six embedding-side tensors stay frozen whatever ``k``.
-        The backbone's dropout is not built, and the fp32 parity mode is refused as everywhere in this class."""
+        Dropout is ``set_dropout``'s; the fp32 parity mode is refused as everywhere in this class."""
         L = self.config.num_hidden_layers
         self._check_trainable(k, "embeddings", embeddings, "the embeddings train", "their gradient comes through every layer")
         if self._embeddings and not embeddings:        # (steps taken while ``rel_embeddings`` trained moved no version counter)
@@ -373,20 +438,49 @@ class NativeDeberta(FrozenBackbone):
         may be cached"""
         return self._pos_state(dev)[1]
 
-    def _pos_state(self, dev) -> tuple:
-        """(``rel`` = LayerNorm(rel_embeddings) as bf16 (2S, d), ``_pos_tables``' list computed from it)"""
+    def _pos_state(self, dev, drop: Optional[_Drop] = None) -> tuple:
+        """(``rel`` = LayerNorm(rel_embeddings) as bf16 (2S, d), ``_pos_tables``' list computed from it).  With hidden dropout
+        every layer's tables come from its own ``rel_i`` = dropout_i(rel) and are computed in this call, a frozen layer's too
+        (the mask is the call's); ``rel`` itself is the cached one while frozen"""
         rel, pos = self._pos_cache(dev)
+        if drop is not None and drop.p_h > 0.0:
+            return rel, [self._pos_of(i, self._rel_of(i, rel, drop)) for i in range(self.config.num_hidden_layers)]
         return rel, list(pos) + [self._pos_of(i, rel) for i in range(len(pos), self.config.num_hidden_layers)]
 
+    @staticmethod
+    def _rel_of(i: int, rel: torch.Tensor, drop: _Drop) -> torch.Tensor:
+        """layer ``i``'s dropped relative embeddings (one item: sub-stream 0, index row * d + column), rounded once"""
+        rel_i = torch.empty_like(rel)
+        lib.deberta_dropout(rel, rel_i, 1, drop.hidden(drop.layers[i][_Drop.REL], 0))
+        return rel_i
+
     # -- launches ---------------------------------------------------------------------------------------
-    def _layer(self, i: int, ws, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor]) -> None:
+    def _layer(self, i: int, ws, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor], drop: Optional[_Drop] = None,
+               n0: int = 0) -> None:
         """a post-LN layer around the disentangled attention: ``pos`` = this layer's (posQ, posK), ``idx`` the index table,
-        ``mask`` the chunk's (n, T) mask or None"""
+        ``mask`` the chunk's (n, T) mask or None; ``drop``: the call's dropout, ``n0`` the chunk's first item in the batch"""
         c, scale = self.config, math.sqrt(3.0 * self.head_dim)
+        probs = drop.probs(i, n0) if drop is not None else None
 
         def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
-            lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, n, c.num_attention_heads, T, c.position_buckets, scale, self.head_dim)
-        self._post_ln_layer(i, ws, n, T, attend)
+            lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, n, c.num_attention_heads, T, c.position_buckets, scale, self.head_dim,
+                                 drop=probs)
+        self._post_ln_layer(i, ws, n, T, attend, self._joins(i, n, n0, drop)[0])
+
+    @staticmethod
+    def _joins(i: int, n: int, n0: int, drop: Optional[_Drop]) -> tuple:
+        """(join, join_bwd) of layer ``i`` on a chunk of ``n`` items from item ``n0`` (mmfusion/backbone.py: ``Join``): the
+        attention output's and the MLP output's dropout, fused with the residual add; (None, None) without hidden dropout"""
+        if drop is None or drop.p_h <= 0.0:
+            return None, None
+        sites = {"o": drop.layers[i][_Drop.OUT], "fc2": drop.layers[i][_Drop.MLP]}
+
+        def join(role: str, y: torch.Tensor, resid: torch.Tensor) -> None:
+            lib.deberta_dropout(y, y, n, drop.hidden(sites[role], n0), resid=resid)
+
+        def join_bwd(role: str, dy: torch.Tensor, out: torch.Tensor) -> None:
+            lib.deberta_dropout(dy, out, n, drop.hidden(sites[role], n0))
+        return join, join_bwd
 
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None) -> BackboneOutput:
         c, who = self.config, "NativeDeberta"
@@ -416,13 +510,14 @@ class NativeDeberta(FrozenBackbone):
             params = [getattr(self, n) for i in range(L - self._trainable, L) for n in self._layer_params(i)]
             if self._embeddings:
                 params += [getattr(self, n) for n in self._EMBEDDING_PARAMS]
-            return BackboneOutput(_Differentiable.apply(self, src, mask, input_ids is not None, *params))
+            return BackboneOutput(_Differentiable.apply(self, src, mask, input_ids is not None, self._drop_of_call(), *params))
         return BackboneOutput(self._run(src, mask, input_ids is not None))
 
     def _run(self, src: torch.Tensor, mask: Optional[torch.Tensor], by_ids: bool, keep: Optional[torch.Tensor] = None,
-             first: int = 0, pos: Optional[list] = None) -> torch.Tensor:
+             first: int = 0, pos: Optional[list] = None, drop: Optional[_Drop] = None) -> torch.Tensor:
         """the launch list on checked inputs -> (N, T, d) f32; ``keep`` (layers - first, N T, d) bf16: also copy the input of every
-        layer from ``first`` up there; ``pos``: the layers' position tables where the caller has them already"""
+        layer from ``first`` up there; ``pos``: the layers' position tables where the caller has them already; ``drop``: the
+        call's dropout (``pos`` is then ``_pos_state(dev, drop)``'s)"""
         c, d, dev = self.config, self.config.hidden_size, src.device
         N, T = src.shape[:2]
         _arena.ensure(self)
@@ -437,35 +532,40 @@ class NativeDeberta(FrozenBackbone):
                 lib.deberta_embed(x, table, gamma, beta, c.layer_norm_eps, ids=part.reshape(-1), mask=m)
             else:
                 lib.deberta_embed(x, None, gamma, beta, c.layer_norm_eps, embeds=part, mask=m)
+            if drop is not None and drop.p_h > 0.0:
+                lib.deberta_dropout(x, x, n, drop.hidden(drop.emb, n0))
             for i in range(c.num_hidden_layers):
                 if keep is not None and i >= first:
                     keep[i - first, n0 * T:(n0 + n) * T].copy_(x)
-                self._layer(i, ws, n, T, pos[i], idx, m)
+                self._layer(i, ws, n, T, pos[i], idx, m, drop, n0)
             self._widen(x, out[n0:n0 + n])
         return out
 
     # -- the backward: input gradient and the trainable layers' weight gradients -------------------------------------
     def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, pos, idx: torch.Tensor, mask: Optional[torch.Tensor],
-                    dpos: Optional[torch.Tensor] = None, below: bool = True) -> None:
+                    dpos: Optional[torch.Tensor] = None, below: bool = True, drop: Optional[_Drop] = None, n0: int = 0) -> None:
         """layer ``i`` again from its saved input ``xin``, then its backward: ``ga`` holds the gradient of the layer's output on
         entry and, with ``below``, of ``xin`` on return.  ``dpos`` (2S, 2d) f32, for a trainable layer: the layer's weight, bias
-        and LayerNorm gradients are added into the parameters' ``.grad`` and the gradient of posQ | posK into ``dpos``"""
+        and LayerNorm gradients are added into the parameters' ``.grad`` and the gradient of posQ | posK into ``dpos``.  ``drop``,
+        ``n0`` as in ``_layer``: the layer runs again under the forward's masks and its backward draws them once more"""
         c, d = self.config, self.config.hidden_size
         dims = (n, c.num_attention_heads, T, c.position_buckets, math.sqrt(3.0 * self.head_dim), self.head_dim)
         train = dpos is not None
+        probs = drop.probs(i, n0) if drop is not None else None
 
         def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
-            lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, *dims, lse=g["lse"])
+            lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, *dims, lse=g["lse"], drop=probs)
 
         def attn_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor) -> None:
             if train:
                 lib.deberta_attn_bwd_pos(qkv, pos[0], pos[1], idx, mask, att, g["lse"], datt, g["delta"], dqkv, dpos[:, :d], dpos[:, d:],
-                                         self._pos_workspace(g, n, T), *dims)
+                                         self._pos_workspace(g, n, T), *dims, drop=probs)
             else:
-                lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], datt, g["delta"], dqkv, *dims)
+                lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], datt, g["delta"], dqkv, *dims, drop=probs)
+        join, join_bwd = self._joins(i, n, n0, drop)
         # the plain Q/K/V weight gradient, the key bias's column sum included: db_k has a real position-to-content term here
         self._post_ln_layer_grad(i, ws, g, xin, n, T, attend, attn_bwd, (lambda dqkv, x: self._wgrad(dqkv, x, f"l{i}_qkv")) if train else None,
-                                 below)
+                                 below, join=join, join_bwd=join_bwd)
 
     def _embed_workspace(self, g: dict, rows: int, d_rows: bool) -> tuple:
         """(``mmf_deberta_embed_bwd_params``' workspace for up to ``rows`` rows, with ``d_rows`` an f32 (rows, d) buffer for the
@@ -480,15 +580,17 @@ class NativeDeberta(FrozenBackbone):
         return w, r[:rows * d].view(rows, d) if d_rows else None
 
     def _backward(self, src: torch.Tensor, by_ids: bool, mask: Optional[torch.Tensor], keep: torch.Tensor, first: int, pos: list,
-                  rel: torch.Tensor, dout: torch.Tensor, need_in: bool, k: int, emb: bool = False) -> Optional[torch.Tensor]:
+                  rel: torch.Tensor, dout: torch.Tensor, need_in: bool, k: int, emb: bool = False,
+                  drop: Optional[_Drop] = None) -> Optional[torch.Tensor]:
         """for the gradient ``dout`` (N, T, d) f32 of the result: with ``need_in``, -> d ``inputs_embeds`` (N, T, d) f32; with
         ``k > 0``, the gradients of the top ``k`` layers' parameters, added into their ``.grad``; with ``emb`` (``k == L``), also
         those of the six embedding-side parameters.  ``keep``: the saved inputs of the layers from ``first`` up, ``pos`` / ``rel``:
         the position tables the forward used and the normalised relative embeddings they were made from.  Without ``need_in``
-        and ``emb`` the walk ends with layer ``first``'s weight gradients"""
+        and ``emb`` the walk ends with layer ``first``'s weight gradients.  ``drop``: the forward's dropout, every mask drawn again"""
         c, d, dev = self.config, self.config.hidden_size, src.device
         N, T = src.shape[:2]
         L, S2 = c.num_hidden_layers, 2 * c.position_buckets
+        hidden = drop is not None and drop.p_h > 0.0
         self._refuse_fp32()
         idx = self._index(T, dev)
         ws, g = self._workspace(dev, T), self._grad_workspace(dev, T)
@@ -502,7 +604,9 @@ class NativeDeberta(FrozenBackbone):
             self._narrow(dout[n0:n0 + n], ga)
             for i in reversed(range(first, L)):
                 self._layer_grad(i, ws, g, keep[i - first, rows], n, T, pos[i], idx, m, dpos[i - (L - k)] if i >= L - k else None,
-                                 need_in or emb or i > first)
+                                 need_in or emb or i > first, drop, n0)
+            if hidden and (need_in or emb):
+                lib.deberta_dropout(ga, ga, n, drop.hidden(drop.emb, n0))      # through the embedding output's dropout
             if emb:
                 # the embedding LayerNorm's parameters, and the word embeddings: the gathered rows' gradient (a buffer of the
                 # backward's), scattered into the table's; on the embeds route the rows' gradient is d inputs_embeds itself
@@ -525,8 +629,9 @@ class NativeDeberta(FrozenBackbone):
             # comes from the bf16 O: each row of dS sums to dO_i . (O_i - bf16(O_i)), the residue colsum(dK) carries once already)
             for i in range(L - k, L):
                 w, b, dp = getattr(self, f"l{i}_qkv_w").grad, getattr(self, f"l{i}_qkv_b").grad, dp16[i - (L - k)]
-                ops.gemm_group(GEMM_TN, [(dp[:, :d], rel, w[:d], b[:d], None)], EPI_ACCUM | EPI_COLSUM_A)
-                ops.gemm_group(GEMM_TN, [(dp[:, d:], rel, w[d:2 * d], None, None)], EPI_ACCUM)
+                rel_i = self._rel_of(i, rel, drop) if hidden else rel              # what the layer's tables were projected from
+                ops.gemm_group(GEMM_TN, [(dp[:, :d], rel_i, w[:d], b[:d], None)], EPI_ACCUM | EPI_COLSUM_A)
+                ops.gemm_group(GEMM_TN, [(dp[:, d:], rel_i, w[d:2 * d], None, None)], EPI_ACCUM)
             if emb:
                 # ... continued below posQ | posK: d rel = sum over the layers of dpos_i (2S, 2d) W_qk,i (2d, d), one NN launch per
                 # layer adding into one f32 (2S, d) buffer in stream order (layer 0 writes it).  In-stream accumulation keeps the sum
@@ -534,9 +639,19 @@ class NativeDeberta(FrozenBackbone):
                 # slabs and need the slab sum behind it, for products of 2S rows that fill a fraction of the CUs either way.
                 # rel is stored as bf16: d rel is rounded to bf16 there, once, and the relative table's LayerNorm backward adds
                 # straight into rel_emb.grad and the encoder LayerNorm's gradients
+                # With hidden dropout each layer's term is the gradient of its own rel_i and goes through that layer's mask before
+                # the sum: one slab per layer, masked where it lies, then the slabs' sum in layer order
                 drel = torch.empty((S2, d), dtype=torch.float32, device=dev)
-                for i in range(L):
-                    ops.gemm(GEMM_NN, dp16[i], self._w(f"l{i}_qkv_w")[:2 * d], drel, epilogue=EPI_ACCUM if i else 0)
+                if hidden:
+                    slabs = torch.empty((L, S2 * d), dtype=torch.float32, device=dev)
+                    for i in range(L):
+                        ops.gemm(GEMM_NN, dp16[i], self._w(f"l{i}_qkv_w")[:2 * d], slabs[i].view(S2, d))
+                        lib.deberta_dropout(slabs[i], slabs[i], 1, drop.hidden(drop.layers[i][_Drop.REL], 0))
+                    for s0 in range(0, L, lib.SUM_SLABS_MAX):
+                        lib.sum_slabs(slabs[s0:s0 + lib.SUM_SLABS_MAX], drel, s0 > 0)
+                else:
+                    for i in range(L):
+                        ops.gemm(GEMM_NN, dp16[i], self._w(f"l{i}_qkv_w")[:2 * d], drel, epilogue=EPI_ACCUM if i else 0)
                 wsp, _ = self._embed_workspace(g, S2, False)
                 lib.deberta_embed_bwd_params(self._f("enc_ln_w"), c.layer_norm_eps, None, ops.cast_to_bf16(drel), self.rel_emb.grad,
                                              self.enc_ln_w.grad, self.enc_ln_b.grad, wsp, embeds=self._f("rel_emb"), accumulate=True)

@@ -45,6 +45,7 @@ SYMBOLS = (
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
     "mmf_deberta_embed_bwd_params_workspace_bytes", "mmf_deberta_embed_bwd_params", "mmf_embedding_scatter_add_f32",
+    "mmf_deberta_attn_fwd_drop", "mmf_deberta_attn_bwd_drop", "mmf_deberta_attn_bwd_pos_drop", "mmf_deberta_dropout",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
 )
 
@@ -248,6 +249,12 @@ def load() -> C.CDLL:
     lib.mmf_deberta_attn_bwd_pos_workspace_bytes.restype = C.c_size_t
     lib.mmf_deberta_attn_bwd_pos.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
                                              vp, vp, i32, vp, C.c_size_t, vp]
+    drop = [f32, vp, C.c_uint32, i64]                                  # p, rng_state, site, item0
+    lib.mmf_deberta_attn_fwd_drop.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32] + drop + [vp]
+    lib.mmf_deberta_attn_bwd_drop.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32] + drop + [vp]
+    lib.mmf_deberta_attn_bwd_pos_drop.argtypes = ([vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
+                                                   vp, vp, i32, vp, C.c_size_t] + drop + [vp])
+    lib.mmf_deberta_dropout.argtypes = [vp, vp, vp, i32, i64, i64] + drop + [vp]
     lib.mmf_deberta_embed_bwd_params_workspace_bytes.argtypes = [i64, i32]
     lib.mmf_deberta_embed_bwd_params_workspace_bytes.restype = C.c_size_t
     lib.mmf_deberta_embed_bwd_params.argtypes = [vp, vp, vp, i32, vp, f32, vp, i32, vp, vp, i32, vp, vp, vp, C.c_size_t, i64, i32, vp]
@@ -697,10 +704,23 @@ def _deberta_attn_args(who: str, qkv, posq, posk, idx, out, n: int, H: int, T: i
         raise ValueError(f"{who}: operand sizes do not match n, H, T, S")
 
 
-def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S: int, scale: float, head_dim: int = 64, lse=None) -> None:
+def _deberta_drop(who: str, drop) -> tuple:
+    """``drop`` = (p, state, site, item0) -> the four trailing arguments of the ``_drop`` entry points: ``state`` the device int64
+    [1] RNG state (``ops.rng_state()``), ``item0`` the index in the whole batch of the call's first item"""
+    import torch
+    p, state, site, item0 = drop
+    if state is not None and (not state.is_cuda or state.dtype != torch.int64 or state.numel() != 1):
+        raise ValueError(f"{who}: the dropout state must be one int64 on the GPU")
+    return float(p), None if state is None else state.data_ptr(), int(site), int(item0)
+
+
+def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S: int, scale: float, head_dim: int = 64, lse=None,
+                     drop=None) -> None:
     """out (n T, H 64) bf16 = disentangled attention of the fused qkv rows (n T, 3 H 64); posq / posk (2S, H 64) bf16 views with a
     common row stride; idx int32 (2T - 1,) (include/mmfusion.h states its contract); mask (n, T) or None.  With ``lse`` (f32, n H T
-    values) the launch also writes the rows' log-sum-exp for ``deberta_attn_bwd``; ``out`` is the same bits either way"""
+    values) the launch also writes the rows' log-sum-exp for ``deberta_attn_bwd``; ``out`` is the same bits either way.
+    ``drop`` = (p, state, site, item0): training-mode dropout of the probabilities (``mmf_deberta_attn_fwd_drop``); lse stays the
+    undropped one"""
     _deberta_attn_args("deberta_attn_fwd", qkv, posq, posk, idx, out, n, H, T, S, head_dim)
     if lse is not None:
         _w2v_f32(lse)
@@ -708,7 +728,11 @@ def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S:
             raise ValueError("deberta_attn_fwd: lse must hold n H T values")
     mp, kind = _deberta_mask(mask, n * T)
     with _Timed(f"deberta_attn_fwd_kernel<{head_dim}>", 12.0 * n * H * T * T * head_dim, [(T, T)]):
-        if lse is None:
+        if drop is not None:
+            check(load().mmf_deberta_attn_fwd_drop(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
+                                                   out.data_ptr(), None if lse is None else lse.data_ptr(), n, H, T, S, head_dim, scale,
+                                                   *_deberta_drop("deberta_attn_fwd", drop), stream_ptr()))
+        elif lse is None:
             check(load().mmf_deberta_attn_fwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
                                               out.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
         else:
@@ -728,16 +752,20 @@ def _deberta_attn_bwd_args(who: str, qkv, posq, posk, idx, out, lse, dout, delta
 
 
 def deberta_attn_bwd(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv, n: int, H: int, T: int, S: int, scale: float,
-                     head_dim: int = 64) -> None:
+                     head_dim: int = 64, drop=None) -> None:
     """dqkv (n T, 3 H 64) bf16 <- the gradient of the fused qkv rows for the gradient ``dout`` (n T, H 64) of ``out``; ``out`` / ``lse``
-    as ``deberta_attn_fwd(..., lse=lse)`` wrote them; ``delta_ws`` f32 scratch of n H T values.  Every row of dqkv is written."""
+    as ``deberta_attn_fwd(..., lse=lse)`` wrote them; ``delta_ws`` f32 scratch of n H T values.  Every row of dqkv is written.
+    ``drop``: the forward's (p, state, site, item0), the mask drawn again (``mmf_deberta_attn_bwd_drop``)."""
     _deberta_attn_bwd_args("deberta_attn_bwd", qkv, posq, posk, idx, out, lse, dout, delta_ws, dqkv, n, H, T, S, head_dim)
     mp, kind = _deberta_mask(mask, n * T)
     # the forward's three score products again, dP, and two products (content + position) for each of dQ and dK, and dV
     with _Timed(f"deberta_attn_bwd_kernels<{head_dim}>", 22.0 * n * H * T * T * head_dim, [(T, T)]):
-        check(load().mmf_deberta_attn_bwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
-                                          out.data_ptr(), lse.data_ptr(), dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(),
-                                          n, H, T, S, head_dim, scale, stream_ptr()))
+        args = (qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind, out.data_ptr(), lse.data_ptr(),
+                dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(), n, H, T, S, head_dim, scale)
+        if drop is not None:
+            check(load().mmf_deberta_attn_bwd_drop(*args, *_deberta_drop("deberta_attn_bwd", drop), stream_ptr()))
+        else:
+            check(load().mmf_deberta_attn_bwd(*args, stream_ptr()))
 
 
 def deberta_attn_bwd_pos_workspace_bytes(n: int, H: int, T: int, S: int) -> int:
@@ -745,10 +773,11 @@ def deberta_attn_bwd_pos_workspace_bytes(n: int, H: int, T: int, S: int) -> int:
 
 
 def deberta_attn_bwd_pos(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv, dposq, dposk, workspace, n: int, H: int, T: int,
-                         S: int, scale: float, head_dim: int = 64) -> None:
+                         S: int, scale: float, head_dim: int = 64, drop=None) -> None:
     """``deberta_attn_bwd`` (the same dqkv bits) that also ADDS the gradients of the position tables into ``dposq`` / ``dposk``: f32
     (2S, H 64) views with a common row stride, zeroed by the caller before the first chunk; ``workspace``: a contiguous f32 / uint8
-    tensor of at least ``deberta_attn_bwd_pos_workspace_bytes(n, H, T, S)`` bytes (it need not be initialised)."""
+    tensor of at least ``deberta_attn_bwd_pos_workspace_bytes(n, H, T, S)`` bytes (it need not be initialised).  ``drop`` as
+    ``deberta_attn_bwd``'s (``mmf_deberta_attn_bwd_pos_drop``)."""
     import torch
     _deberta_attn_bwd_args("deberta_attn_bwd_pos", qkv, posq, posk, idx, out, lse, dout, delta_ws, dqkv, n, H, T, S, head_dim)
     d = H * head_dim
@@ -759,10 +788,32 @@ def deberta_attn_bwd_pos(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, d
     mp, kind = _deberta_mask(mask, n * T)
     # deberta_attn_bwd's products plus the two table contractions (2S x 64 x the tokens, per head)
     with _Timed(f"deberta_attn_bwd_pos_kernels<{head_dim}>", 22.0 * n * H * T * T * head_dim, [(T, T)]):
-        check(load().mmf_deberta_attn_bwd_pos(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
-                                              out.data_ptr(), lse.data_ptr(), dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(),
-                                              n, H, T, S, head_dim, scale, dposq.data_ptr(), dposk.data_ptr(), dposq.stride(0),
-                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(), stream_ptr()))
+        args = (qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind, out.data_ptr(), lse.data_ptr(),
+                dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(), n, H, T, S, head_dim, scale, dposq.data_ptr(), dposk.data_ptr(),
+                dposq.stride(0), workspace.data_ptr(), workspace.numel() * workspace.element_size())
+        if drop is not None:
+            check(load().mmf_deberta_attn_bwd_pos_drop(*args, *_deberta_drop("deberta_attn_bwd_pos", drop), stream_ptr()))
+        else:
+            check(load().mmf_deberta_attn_bwd_pos(*args, stream_ptr()))
+
+
+def deberta_dropout(y, out, items: int, drop, resid=None) -> None:
+    """Hidden dropout of ``items`` items (``mmf_deberta_dropout``): out = keep ? y c : 0 (+ ``resid``), element e of item g keyed by
+    sub-stream item0 + g and index e of ``drop`` = (p, state, site, item0).  bf16: y, out and the optional ``resid`` are contiguous
+    bf16 of one size, one f32 multiply-add and one rounding.  f32: y and out contiguous f32, no ``resid``.  ``out`` may be ``y``."""
+    import torch
+    f32 = y.dtype == torch.float32
+    (_w2v_f32 if f32 else _w2v_bf16)(y, out)
+    if resid is not None:
+        if f32:
+            raise ValueError("deberta_dropout: the f32 form takes no residual")
+        _w2v_bf16(resid)
+    ts = [y, out] + ([resid] if resid is not None else [])
+    if items <= 0 or y.numel() % items or any(t.numel() != y.numel() or not t.is_contiguous() for t in ts):
+        raise ValueError("deberta_dropout: y, out and resid must be contiguous, of one size that the items divide")
+    with _Timed("deberta_dropout_kernel", 0.0, [(items, y.numel() // items)]):
+        check(load().mmf_deberta_dropout(y.data_ptr(), None if resid is None else resid.data_ptr(), out.data_ptr(), int(f32), items,
+                                         y.numel() // items, *_deberta_drop("deberta_dropout", drop), stream_ptr()))
 
 
 def deberta_embed_bwd(embeds, gamma, eps: float, mask, dout, d_embeds) -> None:

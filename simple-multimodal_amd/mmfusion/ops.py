@@ -271,6 +271,26 @@ def next_site() -> int:
     return _site
 
 
+_roots = 0
+
+
+def root_entered() -> None:
+    """A root module's forward (``models.fusion_layers._FusionBase``) is running: it has called ``begin_training_forward`` where
+    it trains, and what runs inside takes its sites from that numbering"""
+    global _roots
+    _roots += 1
+
+
+def root_left() -> None:
+    global _roots
+    _roots -= 1
+
+
+def inside_root() -> bool:
+    """False for a module called on its own: with dropout on, it must call ``begin_training_forward`` itself"""
+    return _roots > 0
+
+
 class dropout_state:
     """Within: dropout masks come from ``state`` (a device int64 [1]) with a site numbering of their own, and the outer
     state tensor and site counter are untouched — ``begin_training_forward`` advances ``state``, not the outer one.  For a

@@ -29,7 +29,10 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     HuggingFace's model in the reference (:49-71).  Frozen unless ``config.text_backbone_trainable_layers`` (dynamic attribute;
     default 0) is ``k`` > 0: the top ``k`` layers then train; ``"all"``: every layer and the embedding side (word embeddings,
     embedding LayerNorm, relative embeddings, encoder LayerNorm), which is every parameter the reference's optimiser steps; on
-    the prompt route the word embeddings then train through ``word_embeddings(input_ids)`` as well;
+    the prompt route the word embeddings then train through ``word_embeddings(input_ids)`` as well.
+    ``config.text_backbone_dropout`` (dynamic attribute; default 0: off) switches the backbone's training-mode dropout on:
+    ``True`` for HuggingFace's 0.1 / 0.1, which is what the reference trains under, or a pair (hidden, attention); it acts while
+    the encoder is in ``train()`` and the backbone has something to train, never under ``eval()``;
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -97,6 +100,19 @@ def _backbone(config, kind: str, given: Optional[nn.Module]):
     elif given is None:
         given = _load_backbone(kind, getattr(config, kind + "_model_name"))
     return given, given.config.hidden_size, native
+
+
+def _backbone_dropout(value) -> Tuple[float, float]:
+    """``config.text_backbone_dropout`` (dynamic attribute) -> (hidden, attention) probabilities of the native backbone's
+    training-mode dropout: absent, 0 or False: off; True: HuggingFace's 0.1 / 0.1 for deberta-v3-base, what the reference trains
+    with; a pair: those values (``NativeDeberta.set_dropout`` checks them)"""
+    if value is True:
+        return 0.1, 0.1
+    if value is False or value is None or (isinstance(value, (int, float)) and value == 0):
+        return 0.0, 0.0
+    if isinstance(value, (tuple, list)) and len(value) == 2:
+        return value[0], value[1]
+    raise ValueError(f"text_backbone_dropout={value!r}: 0 (off), True (0.1 / 0.1) or a pair (hidden, attention)")
 
 
 def _run_backbone(fn, native: bool, *args, input_grad: bool = False, **kw):
@@ -169,6 +185,7 @@ class TextEncoder(_FusionBase):
                 self.model.set_trainable_layers(self.model.config.num_hidden_layers, embeddings=True)
             else:
                 self.model.set_trainable_layers(int(k))
+            self.model.set_dropout(*_backbone_dropout(getattr(config, "text_backbone_dropout", 0)))
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.prompt_embeddings = nn.Parameter(torch.randn(config.prompt_length, self.hidden_size)) \
             if hasattr(config, "prompt_length") else None

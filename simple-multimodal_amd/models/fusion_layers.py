@@ -79,10 +79,12 @@ class _FusionBase(nn.Module):
             if self.training:
                 ops.begin_training_forward()        # new dropout masks for this step
         _depth += 1
+        ops.root_entered()
 
     def _exit(self):
         global _depth
         _depth -= 1
+        ops.root_left()
         if _depth == 0:
             ops.set_precision(getattr(self, "_saved_precision", "bf16"))
             _cat3_memo.clear()

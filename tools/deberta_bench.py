@@ -17,9 +17,13 @@
     (``set_trainable_layers(L, embeddings=True)``); beside the above, on one chunk's operands: ``mmf_deberta_embed_bwd_params``,
     ``mmf_embedding_scatter_add_f32`` on the batch's ids and on skewed ids (one id on a quarter of the tokens), the d rel GEMMs,
     the recomputation of ``rel``, and the whole-table costs the real vocabulary adds to a step: the memset of the table's
-    gradient and the AdamW step over the trainable parameters (compare with ``--finetune 12``: the same tree, embeddings frozen).
+    gradient and the AdamW step over the trainable parameters (compare with ``--finetune 12``: the same tree, embeddings frozen);
+  * with --dropout P_H,P_A (beside --grad or --finetune), the same training calls in ``train()`` with the backbone's dropout at
+    those probabilities (``set_dropout``; compare with the same command without it), and under --finetune the attention forward
+    (with lse) and backward (delta + dQ pass + dK/dV pass, and the form with the table gradients) alone with and without the mask.
 
-    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad] [--finetune K|all]
+    python tools/deberta_bench.py [--items 16] [--tokens 512] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--grad]
+                                  [--finetune K|all] [--dropout P_H,P_A]
 Prints one JSON line (the tables, when asked for, on the lines before it)."""
 import json
 import math
@@ -34,7 +38,8 @@ def gflop_per_item(cfg, T: int) -> float:
 
 
 def grad_mode(model, cfg, args) -> dict:
-    res = {"model": "deberta-v3-base, frozen, bf16 storage: gradient with respect to inputs_embeds", "chunk": model.chunk, "cases": []}
+    res = {"model": "deberta-v3-base, frozen, bf16 storage: gradient with respect to inputs_embeds", "chunk": model.chunk,
+           "dropout": args.dropout, "cases": []}
     for N, T in ((16, 10 + 512), (8, 10 + 128)):
         g = torch.Generator().manual_seed(2)
         emb = torch.randn(N, T, cfg.hidden_size, generator=g).cuda()
@@ -69,7 +74,7 @@ def finetune_mode(model, cfg, args) -> dict:
     K, H, S, d = cfg.num_hidden_layers if full else int(args.finetune), cfg.num_attention_heads, cfg.position_buckets, cfg.hidden_size
     model.set_trainable_layers(K, embeddings=full)
     res = {"model": f"deberta-v3-base, bf16 storage: the top {K} layers" + (" and the embeddings" if full else "") + " trainable, token ids",
-           "chunk": model.chunk, "cases": []}
+           "chunk": model.chunk, "dropout": args.dropout, "cases": []}
     for N, T in ((args.items, args.tokens), (8, 128)):
         g = torch.Generator().manual_seed(2)
         ids = torch.randint(1, cfg.vocab_size, (N, T), generator=g).cuda()
@@ -101,6 +106,17 @@ def finetune_mode(model, cfg, args) -> dict:
                                                    n, H, T, S, scale)
         t_plain, t_pos = time_eager(plain, 20, 5), time_eager(withpos, 20, 5)
         extra = {}
+        if args.dropout:
+            # the attention launches alone with and without the mask, on the same operands
+            drop = (args.dropout[1] or 0.1, ops.rng_state(), 3, 0)
+            fwd = lambda **kw: lib.deberta_attn_fwd(qkv, posq, posk, idx, m32, att, n, H, T, S, scale, lse=lse, **kw)
+            t_fwd, t_fwd_d = time_eager(fwd, 20, 5), time_eager(lambda: fwd(drop=drop), 20, 5)
+            t_plain_d = time_eager(lambda: lib.deberta_attn_bwd(qkv, posq, posk, idx, m32, att, lse, dat, delta, dqkv, n, H, T, S, scale, drop=drop), 20, 5)
+            t_pos_d = time_eager(lambda: lib.deberta_attn_bwd_pos(qkv, posq, posk, idx, m32, att, lse, dat, delta, dqkv, dpos[:, :d], dpos[:, d:], ws,
+                                                                  n, H, T, S, scale, drop=drop), 20, 5)
+            extra.update(attn_fwd_lse_ms=round(t_fwd, 4), attn_fwd_lse_drop_ms=round(t_fwd_d, 4), attn_fwd_drop_ratio=round(t_fwd_d / t_fwd, 3),
+                         attn_bwd_drop_ms=round(t_plain_d, 4), attn_bwd_drop_ratio=round(t_plain_d / t_plain, 3),
+                         attn_bwd_pos_drop_ms=round(t_pos_d, 4), attn_bwd_pos_drop_ratio=round(t_pos_d / t_pos, 3), attn_drop_p=drop[0])
         if full:
             # the embedding side's launches alone, on one chunk's operands
             rows_, part = n * T, ids[:n].reshape(-1).contiguous()
@@ -121,9 +137,9 @@ def finetune_mode(model, cfg, args) -> dict:
                     ops.gemm(lib.GEMM_NN, dp16[i], model._w(f"l{i}_qkv_w")[:2 * d], drel, epilogue=lib.EPI_ACCUM if i else 0)
             f_rel = lambda: model._pos_cache(ids.device)
             f_zero = lambda: dtable.zero_()
-            extra = {name + "_ms": round(time_eager(f, 20, 5), 4) for name, f in
-                     (("embed_bwd_params", f_a), ("scatter_add", f_b), ("scatter_add_skewed", f_skew), ("drel_gemms", f_drel),
-                      ("rel_recompute", f_rel), ("table_grad_memset", f_zero))}
+            extra.update({name + "_ms": round(time_eager(f, 20, 5), 4) for name, f in
+                          (("embed_bwd_params", f_a), ("scatter_add", f_b), ("scatter_add_skewed", f_skew), ("drel_gemms", f_drel),
+                           ("rel_recompute", f_rel), ("table_grad_memset", f_zero))})
             extra["table_grad_mb"] = round(dtable.numel() * 4 / 2 ** 20, 1)
         opt = finetune_optimizer(model, arena.ensure(model), lr=1e-5, weight_decay=0.01)
 
@@ -147,7 +163,10 @@ def main():
     ap.add_argument("--tokens", type=int, default=512)
     ap.add_argument("--grad", action="store_true")
     ap.add_argument("--finetune", type=lambda v: v if v == "all" else int(v), default=0, metavar="K|all")
+    ap.add_argument("--dropout", type=lambda v: tuple(float(p) for p in v.split(",")), default=None, metavar="P_H,P_A")
     args = ap.parse_args()
+    if args.dropout and (len(args.dropout) != 2 or not (args.grad or args.finetune)):
+        ap.error("--dropout takes P_H,P_A and goes with --grad or --finetune")
     import deberta_ref
     from mmfusion import deberta, lib
     from mmfusion.lib import AttnProblem
@@ -155,6 +174,9 @@ def main():
     model = deberta.NativeDeberta(**deberta_ref.config_kwargs(cfg))
     model.load_state_dict(deberta_ref.seeded_weights(cfg, seed=0))
     model = model.cuda().eval()
+    if args.dropout:
+        model.set_dropout(*args.dropout)
+        model.train()
     if args.grad:
         print(json.dumps(grad_mode(model, cfg, args)))
         return
