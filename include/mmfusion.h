@@ -363,9 +363,27 @@ int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_problems, int
  * from the bf16 Q / K / V / dO and the forward's LSE (O is not read; dQ / dK / dV may be NULL), and mmf_attn_bwd_grouped with that
  * delta as an INPUT.  mmf_attn_bwd_grouped forms delta = dO . O from the bf16 O, so a row of dS sums to dO . (O - bf16(O)) instead of
  * zero; where dQ / dK are much smaller than |dO| |O| suggests (tokens that have grown alike) that residue is all they hold.  The
- * pair costs one more pass over the keys on the vector units.  No dropout form; mmf_attn_bwd_grouped's validation and codes. */
+ * pair costs one more pass over the keys on the vector units.  These two have no dropout; the _keyed entries below do;
+ * mmf_attn_bwd_grouped's validation and codes. */
 int mmf_attn_delta_f32(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream);
 int mmf_attn_bwd_grouped_delta(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream);
+/* Attention-probability dropout with a caller-chosen base of the stream id: the mask of (problem, b, h, q, key) is
+ * the counter hash's keep of index q*Tk + key under the key of (*rng_state, site, sub-stream problem * 4096 + stream_base + b*H + h)
+ * (mmf_dropout's hash: csrc/mmf_internal.h has the two functions), so a one-problem launch of the
+ * items item0 .. of a batch with stream_base = item0 * H draws what a launch of the whole batch draws for them (a backbone's chunks);
+ * stream_base = 0 is mmf_attn_fwd_grouped_ex's rule.  One problem: stream_base + B*H <= 2^32; several: <= 4096 each.
+ *   _fwd_grouped_keyed        mmf_attn_fwd_grouped_ex's forward: O from the dropped, rescaled probabilities, LSE the undropped one.
+ *   _delta_f32_keyed          delta[b][h][i] = sum_j p_ij w_ij (dO_i . v_j), w = keep / (1 - p), p_ij from that LSE: the row term of
+ *                             the softmax backward under the mask, in f32 (mmf_attn_delta_f32's kernel with the mask drawn again).
+ *   _bwd_grouped_delta_keyed  mmf_attn_bwd_grouped_delta with the mask drawn again in both kernels: dS = p (w dp - delta), dV from w p.
+ * dropout_p in [0, 1), quantised to 2^-32 as mmf_dropout's; a threshold of 0 launches the plain kernels (rng_state may then be NULL).
+ * rng_state 8-byte aligned.  Validates first and launches nothing on an error. */
+int mmf_attn_fwd_grouped_keyed(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, float dropout_p,
+                               const uint64_t* rng_state, uint32_t site, uint32_t stream_base, void* stream);
+int mmf_attn_delta_f32_keyed(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, float dropout_p,
+                             const uint64_t* rng_state, uint32_t site, uint32_t stream_base, void* stream);
+int mmf_attn_bwd_grouped_delta_keyed(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, float dropout_p,
+                                     const uint64_t* rng_state, uint32_t site, uint32_t stream_base, void* stream);
 /* With attention-probability dropout (nn.MultiheadAttention(dropout=p) in training mode): the
  * probabilities are dropped/rescaled before P.V, the softmax normaliser uses the undropped row sums;
  * the backward kernels regenerate the same mask from (*rng_state, site, problem, b, h, q, key): stream id
@@ -704,6 +722,16 @@ int mmf_bias_gelu_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, i
  * row stride ld; mmf_bias_gelu_bf16's constraints. */
 int mmf_bias_gelu_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols, int ld,
                            void* stream);
+/* The two with dropout of the GELU's output (Wav2Vec2's activation_dropout).  The rows are `items` items of rows / items rows each;
+ * element (t, j) of item g is keyed as mmf_deberta_dropout keys it, sub-stream item0 + g and index t * cols + j, c = 1 / (1 - p):
+ *   _drop_bf16_to   g <- keep ? gelu(h + bias) c : 0 in f32, one rounding; h kept raw
+ *   _drop_bwd_bf16  dh <- keep ? dg c gelu'(h + bias) : 0, one rounding; dh may be dg
+ * bias is required; p in [0, 1) quantised as mmf_dropout's, a threshold of 0 runs the plain kernels (the same bits); rows % items == 0,
+ * an item at most 2^32 elements, rows * cols / 8 < 2^31; rng_state 8-byte aligned, the blocks as mmf_bias_gelu_bf16's.  Validates first. */
+int mmf_bias_gelu_drop_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, int64_t rows, int cols, int ld, int64_t items, float p,
+                               const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
+int mmf_bias_gelu_drop_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols, int ld,
+                                int64_t items, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Wav2Vec2 backbone (mmfusion/wav2vec2.py; the reference runs HuggingFace's Wav2Vec2Model at models/encoders.py:116,144).
@@ -760,6 +788,27 @@ int mmf_w2v_posconv_wgrad(const void* dz_bf16, const void* x_bf16, float* dw, in
  * g / dg f32 [k], v / dv f32 (C, cg, k).  One workgroup per tap, f32, fixed reduction order.  C % cg == 0, C cg k < 2^31. */
 int mmf_w2v_weightnorm_bwd(const float* dw, const float* g, const float* v, float* dg, float* dv, int C, int cg, int k, int overwrite_v,
                            void* stream);
+/* SpecAugment's time mask (HuggingFace _compute_mask_indices without an attention mask), one small launch: starts (N, S_max) int32 =
+ * each clip's span starts, -1 in unused slots.  Clip c draws from the hash key of (*rng_state, site, sub-stream item0 + c), draw n =
+ * mix32[key + n * 0x9E3779B9] (the keep hash before its threshold):  the count is n0 + (draw 0 >= up), n0 = floor(e), up = ceil((1 - frac(e)) 2^32), e = mask_prob T /
+ * length in double (the integer form of int(e + u), u uniform), raised to min_masks, T / length where count * length > T, at most
+ * T - (length - 1);  the starts are draws 1, 2, .. as (draw * (T - length + 1)) >> 32, a start already taken drawn again, at most 64
+ * draws per start, after which it is the next free value above the last draw, cyclically.  Spans may overlap.  1 <= length <= T,
+ * mask_prob in (0, 1], S_max at least the count of n0 + 1.  Validates first and launches nothing on an error. */
+int mmf_w2v_mask_spans(int* starts, int N, int S_max, int T, double mask_prob, int length, int min_masks, const uint64_t* rng_state,
+                       uint32_t site, int64_t item0, void* stream);
+/* Masking and feature-projection dropout in one pass over `items` clips of (T, d) bf16: a row t with starts[g][k] <= t < starts[g][k] +
+ * length for some k becomes bf16(embed) (embed f32 [d]; NULL: zeros, the gradient form: dproj = in_span ? 0 : dx0 keep c), any other
+ * row is keep ? x c : 0 with the mask of element (t, j) of clip g keyed as mmf_deberta_dropout's: sub-stream item0 + g, index t d + j.
+ * starts: the span rows of the call's first clip on, or NULL (dropout only); p = 0: masking only; out may be x.  d % 8 == 0,
+ * T d <= 2^32, x / out 16-byte aligned. */
+int mmf_w2v_mask_drop(const void* x_bf16, const float* embed, const int* starts, void* out_bf16, int64_t items, int T, int d, int S_max,
+                      int length, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
+/* The gradient of the mask embedding, first half: partial (slabs, d) f32, partial[s][j] = the sum of dx[r][j] over the rows r of
+ * slab s (ceil(rows / slabs) rows each, rows = items * T) that lie inside a span, added in row order.  mmf_sum_slabs_f32 adds the
+ * slabs in order: no atomics, the same bits on every run.  1 <= slabs <= min(rows, MMF_SUM_SLABS_MAX). */
+int mmf_w2v_mask_embed_grad(const void* dx_bf16, const int* starts, float* partial, int64_t items, int T, int d, int S_max, int length,
+                            int slabs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frozen DeBERTa-v3 backbone (mmfusion/deberta.py; the reference runs HuggingFace's DebertaV2Model at models/encoders.py:20).

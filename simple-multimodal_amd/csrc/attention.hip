@@ -43,20 +43,45 @@ int validate_dropout(const char* who, const mmf_attn_problem* p, int n, float dr
 }  // namespace
 
 int mmf_attn_fwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
-                         const uint64_t* rng_state, uint32_t site, hipStream_t s);
+                         const uint64_t* rng_state, uint32_t site, hipStream_t s, uint32_t stream_base = 0u);
 int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
-                         const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta = false);
+                         const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta = false, uint32_t stream_base = 0u);
 
 namespace {
+
+// The _keyed entries: the dropout stream id is problem * 4096 + stream_base + b*H + h.  One problem may take any base (its ids must
+// not wrap); several keep every id of a problem below its successor's first
+int validate_keyed(const char* who, const mmf_attn_problem* p, int n, float dropout_p, const uint64_t* rng_state, uint32_t stream_base) {
+  if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !rng_state))
+    MMF_FAIL(MMF_E_SHAPE, "%s: dropout needs 0 <= p < 1 and an rng_state", who);
+  if (reinterpret_cast<uintptr_t>(rng_state) & 7u) MMF_FAIL(MMF_E_ALIGN, "%s: rng_state must be 8-byte aligned", who);
+  for (int i = 0; dropout_p > 0.f && i < n; ++i) {
+    const long long last = (long long)stream_base + (long long)p[i].B * p[i].H;
+    if (n > 1 ? last > 4096 : last > 0xffffffffLL)
+      MMF_FAIL(MMF_E_SHAPE, "%s[%d]: stream_base=%u + B*H=%lld leaves the problem's stream ids (4096 per problem of a group, 2^32 alone)",
+               who, i, stream_base, (long long)p[i].B * p[i].H);
+  }
+  return MMF_OK;
+}
+
+// what the dropout form of the delta pre-pass takes beside the plain one's arguments
+struct DeltaDrop {
+  const unsigned long long* state;
+  unsigned site, thresh, stream_base;
+  float inv_keep;
+};
 
 // delta[b][h][i] = sum_j p_ij dp_ij in f32, p_ij = exp(scale q_i . k_j - LSE_i) and dp_ij = dO_i . v_j from the bf16 operands: the
 // softmax backward's row term as the definition has it.  (The backward kernels' own delta = dO . O reads the bf16 O, so a row of
 // dS sums to dO . (O - bf16(O)) instead of zero: an absolute residue that gradients much smaller than |dO| |O| do not cover.)
 // One thread per query row with q and dO in registers; the keys and values of 32 rows at a time in LDS, read as broadcasts.
+// Drop = one DeltaDrop (the dropout form: delta_i = sum_j p_ij w_ij dp_ij with w = keep c drawn as the forward drew it, stream
+// stream_base + b*H + h, index i Tk + j; p from the undropped LSE) or nothing: the plain instantiation keeps its argument block.
 constexpr int DELTA_THREADS = 256, DELTA_KEYS = 32;
-template <int DH>
+template <int DH, typename... Drop>
 __global__ __launch_bounds__(DELTA_THREADS)
-void attn_delta_kernel(const mmf_attn_problem P, float scale) {
+void attn_delta_kernel(const mmf_attn_problem P, float scale, const Drop... dr) {
+  constexpr bool DROP = sizeof...(Drop) != 0;
   __shared__ __attribute__((aligned(16))) unsigned short sk[DELTA_KEYS * DH], sv[DELTA_KEYS * DH];
   const int h = blockIdx.y, b = blockIdx.z, i = blockIdx.x * DELTA_THREADS + threadIdx.x;
   const int Tq = P.Tq, Tk = P.Tk;
@@ -79,6 +104,15 @@ void attn_delta_kernel(const mmf_attn_problem P, float scale) {
   const size_t at = ((size_t)b * P.H + h) * Tq + (live ? i : 0);
   const float lse = P.LSE[at];
   float acc = 0.f;
+  unsigned dkey = 0u, dthresh = 0u;
+  float dinv = 1.f;
+  if constexpr (DROP) {
+    const DeltaDrop d = (dr, ...);
+    dkey = mmf_rng_key(*d.state, d.site, d.stream_base + (unsigned)(b * P.H + h));
+    dthresh = d.thresh;
+    dinv = d.inv_keep;
+  }
+  const unsigned qidx = (unsigned)i * (unsigned)Tk;
   for (int j0 = 0; j0 < Tk; j0 += DELTA_KEYS) {
     __syncthreads();
     for (int v = threadIdx.x; v < DELTA_KEYS * DH / 8; v += DELTA_THREADS) {
@@ -105,6 +139,7 @@ void attn_delta_kernel(const mmf_attn_problem P, float scale) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) dp = fmaf(g[c * 8 + e], t[e], dp);
       }
+      if constexpr (DROP) dp = mmf_keep(dkey, qidx + (unsigned)(j0 + r), dthresh) ? dp * dinv : 0.f;       // dp through the forward's mask
       acc = fmaf(expf(s - lse), dp, acc);
     }
   }
@@ -149,25 +184,68 @@ extern "C" int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_pr
 }
 
 // mmf_attn_bwd_grouped with delta as an INPUT (f32 [B*H*Tq] per problem, e.g. mmf_attn_delta_f32's): the dQ kernel reads it
-// instead of forming dO . O, the dK/dV kernel reads it as it always does.  No dropout form.
+// instead of forming dO . O, the dK/dV kernel reads it as it always does.  The dropout form is mmf_attn_bwd_grouped_delta_keyed.
 extern "C" int mmf_attn_bwd_grouped_delta(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream) {
   if (int rc = validate("mmf_attn_bwd_grouped_delta", problems, num_problems, head_dim, true)) return rc;
   return mmf_attn_bwd2_launch(problems, num_problems, head_dim, scale, 0.f, nullptr, 0u, static_cast<hipStream_t>(stream), true);
 }
 
-extern "C" int mmf_attn_delta_f32(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream) {
-  if (int rc = validate("mmf_attn_delta_f32", problems, num_problems, head_dim, false)) return rc;
+namespace {
+int delta_launch(const char* fn, const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, const DeltaDrop* dr, void* stream) {
+  if (int rc = validate(fn, problems, num_problems, head_dim, false)) return rc;
   for (int i = 0; i < num_problems; ++i) {
-    if (!problems[i].dO || !problems[i].delta) MMF_FAIL(MMF_E_SHAPE, "mmf_attn_delta_f32[%d]: null gradient operand", i);
-    if (!mmf_aligned16(problems[i].dO)) MMF_FAIL(MMF_E_ALIGN, "mmf_attn_delta_f32[%d]: gradient pointers must be 16-byte aligned", i);
-    if (problems[i].H > 65535 || problems[i].B > 65535) MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_attn_delta_f32[%d]: B and H at most 65535", i);
+    if (!problems[i].dO || !problems[i].delta) MMF_FAIL(MMF_E_SHAPE, "%s[%d]: null gradient operand", fn, i);
+    if (!mmf_aligned16(problems[i].dO)) MMF_FAIL(MMF_E_ALIGN, "%s[%d]: gradient pointers must be 16-byte aligned", fn, i);
+    if (problems[i].H > 65535 || problems[i].B > 65535) MMF_FAIL(MMF_E_UNSUPPORTED, "%s[%d]: B and H at most 65535", fn, i);
   }
+  hipStream_t s = static_cast<hipStream_t>(stream);
   for (int i = 0; i < num_problems; ++i) {
     const mmf_attn_problem& p = problems[i];
     const dim3 grid((p.Tq + DELTA_THREADS - 1) / DELTA_THREADS, p.H, p.B);
-    if (head_dim == 96) hipLaunchKernelGGL(attn_delta_kernel<96>, grid, dim3(DELTA_THREADS), 0, static_cast<hipStream_t>(stream), p, scale);
-    else                hipLaunchKernelGGL(attn_delta_kernel<64>, grid, dim3(DELTA_THREADS), 0, static_cast<hipStream_t>(stream), p, scale);
-    MMF_CHECK_LAUNCH("mmf_attn_delta_f32");
+    if (dr) {
+      DeltaDrop d = *dr;
+      d.stream_base += (unsigned)i * 4096u;
+      if (head_dim == 96) hipLaunchKernelGGL((attn_delta_kernel<96, DeltaDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
+      else                hipLaunchKernelGGL((attn_delta_kernel<64, DeltaDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
+    } else {
+      if (head_dim == 96) hipLaunchKernelGGL(attn_delta_kernel<96>, grid, dim3(DELTA_THREADS), 0, s, p, scale);
+      else                hipLaunchKernelGGL(attn_delta_kernel<64>, grid, dim3(DELTA_THREADS), 0, s, p, scale);
+    }
+    MMF_CHECK_LAUNCH(fn);
   }
   return MMF_OK;
+}
+}  // namespace
+
+extern "C" int mmf_attn_delta_f32(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream) {
+  return delta_launch("mmf_attn_delta_f32", problems, num_problems, head_dim, scale, nullptr, stream);
+}
+
+// ---- the _keyed entries: dropout of the probabilities with a caller-chosen base of the stream id (include/mmfusion.h) ----------
+extern "C" int mmf_attn_fwd_grouped_keyed(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, float dropout_p,
+                                          const uint64_t* rng_state, uint32_t site, uint32_t stream_base, void* stream) {
+  const char* fn = "mmf_attn_fwd_grouped_keyed";
+  if (int rc = validate(fn, problems, num_problems, head_dim, false)) return rc;
+  if (int rc = validate_keyed(fn, problems, num_problems, dropout_p, rng_state, stream_base)) return rc;
+  return mmf_attn_fwd2_launch(problems, num_problems, head_dim, scale, dropout_p, rng_state, site, static_cast<hipStream_t>(stream), stream_base);
+}
+
+extern "C" int mmf_attn_delta_f32_keyed(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, float dropout_p,
+                                        const uint64_t* rng_state, uint32_t site, uint32_t stream_base, void* stream) {
+  const char* fn = "mmf_attn_delta_f32_keyed";
+  if (int rc = validate(fn, problems, num_problems, head_dim, false)) return rc;
+  if (int rc = validate_keyed(fn, problems, num_problems, dropout_p, rng_state, stream_base)) return rc;
+  const unsigned thresh = (dropout_p > 0.f && rng_state) ? mmf_drop_thresh(dropout_p) : 0u;
+  if (thresh == 0u) return delta_launch(fn, problems, num_problems, head_dim, scale, nullptr, stream);
+  const DeltaDrop d = {reinterpret_cast<const unsigned long long*>(rng_state), site, thresh, stream_base,
+                       1.f / (1.f - (float)thresh * (1.f / 4294967296.f))};
+  return delta_launch(fn, problems, num_problems, head_dim, scale, &d, stream);
+}
+
+extern "C" int mmf_attn_bwd_grouped_delta_keyed(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, float dropout_p,
+                                                const uint64_t* rng_state, uint32_t site, uint32_t stream_base, void* stream) {
+  const char* fn = "mmf_attn_bwd_grouped_delta_keyed";
+  if (int rc = validate(fn, problems, num_problems, head_dim, true)) return rc;
+  if (int rc = validate_keyed(fn, problems, num_problems, dropout_p, rng_state, stream_base)) return rc;
+  return mmf_attn_bwd2_launch(problems, num_problems, head_dim, scale, dropout_p, rng_state, site, static_cast<hipStream_t>(stream), true, stream_base);
 }

@@ -77,7 +77,7 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
   const float c = a.scale * LOG2E;
-  const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh)) : 0u;
+  const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh) + a.stream_base) : 0u;
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
@@ -198,6 +198,7 @@ void attn_fwd2n_kernel(const AttnArgs2 a) {
 // (three waves per SIMD) a third instantiation of the body spilled 31 registers instead of 6, a runtime selector 66, and the
 // spills land in the main path's loop.)
 // GIVEN: delta is an input (mmf_attn_bwd_grouped_delta: the caller computed it in f32, mmf_attn_delta_f32); O is not read.
+// GIVEN with DROP (mmf_attn_bwd_grouped_delta_keyed): that delta is the dropped one, sum_j p_ij w_ij dp_ij.
 template <int DH, bool DROP, bool ACTIVE, bool GIVEN = false>
 __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_problem& P, const int pidx, const int bh,
                                          const int qs, char* smem) {
@@ -254,7 +255,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
     lse2 = (qrow < Tq ? P.LSE[(size_t)bh * Tq + qrow] : 0.f) * LOG2E;
   }
   const float c = a.scale * LOG2E;
-  const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh)) : 0u;
+  const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh) + a.stream_base) : 0u;
   const unsigned qidx = (unsigned)qrow * (unsigned)Tk;
   f32x16_t dq[DT];
 #pragma unroll
@@ -400,7 +401,7 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
   const float c = a.scale * LOG2E;
-  const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh)) : 0u;
+  const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh) + a.stream_base) : 0u;
   const unsigned kcol = (unsigned)(k0 + (lane & 31));
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
@@ -543,22 +544,22 @@ void launch4(int head_dim, bool dr, K96T k96t, K96F k96f, K64T k64t, K64F k64f, 
 }  // namespace
 
 int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
-                         const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta) {
+                         const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta, uint32_t stream_base) {
   if (int rc = check_ranges("mmf_attn_bwd_grouped", problems, n)) return rc;
   AttnArgs2 a;
-  if (given_delta) {                                                                               // dQ from the caller's delta (no dropout form)
-    const int total = fill_args2(a, problems, n, scale, 0.f, nullptr, 0u, false, false);
-    if (head_dim == 96) hipLaunchKernelGGL((attn_bwd_dq2_kernel<96, false, true>), dim3(total), dim3(NT), 0, s, a);
-    else                hipLaunchKernelGGL((attn_bwd_dq2_kernel<64, false, true>), dim3(total), dim3(NT), 0, s, a);
+  if (given_delta) {                                                                               // dQ from the caller's delta
+    const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false, stream_base);
+    launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dq2_kernel<96, true, true>, attn_bwd_dq2_kernel<96, false, true>,
+            attn_bwd_dq2_kernel<64, true, true>, attn_bwd_dq2_kernel<64, false, true>, total, a, s);
     MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_delta(dq, v2)");
   } else if (!(g_attn_stub & 2)) {
-    const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false);   // dQ (+ delta) first
+    const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false, stream_base);   // dQ (+ delta) first
     launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dq2_kernel<96, true>, attn_bwd_dq2_kernel<96, false>, attn_bwd_dq2_kernel<64, true>,
             attn_bwd_dq2_kernel<64, false>, total, a, s);
     MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dq, v2)");
   }
   if (g_attn_stub & 4) return MMF_OK;
-  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, true, false);        // then dK/dV (reads delta)
+  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, true, false, stream_base);   // then dK/dV (reads delta)
   launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dkv2_kernel<96, true>, attn_bwd_dkv2_kernel<96, false>, attn_bwd_dkv2_kernel<64, true>,
           attn_bwd_dkv2_kernel<64, false>, total, a, s);
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dkv, v2)");
@@ -567,11 +568,11 @@ int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, 
 
 // Called by mmf_attn_fwd_grouped_ex (attention.hip) after validation.
 int mmf_attn_fwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
-                         const uint64_t* rng_state, uint32_t site, hipStream_t s) {
+                         const uint64_t* rng_state, uint32_t site, hipStream_t s, uint32_t stream_base) {
   if (int rc = check_ranges("mmf_attn_fwd_grouped", problems, n)) return rc;
   if (g_attn_stub & 1) return MMF_OK;
   AttnArgs2 a;
-  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, true);
+  const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, true, stream_base);
   launch4(head_dim, a.drop_thresh != 0u, attn_fwd2n_kernel<96, true>, attn_fwd2n_kernel<96, false>, attn_fwd2n_kernel<64, true>,
           attn_fwd2n_kernel<64, false>, total, a, s);
   MMF_CHECK_LAUNCH("mmf_attn_fwd_grouped");

@@ -23,7 +23,8 @@ struct AttnArgs2 {
   short rpc[MMF_ATTN_MAX_PROBLEMS];           // rows per chunk (multiple of 32, <= 256)
   short orig[MMF_ATTN_MAX_PROBLEMS];          // caller's problem index (dropout stream id)
   mmf_attn_problem p[MMF_ATTN_MAX_PROBLEMS];
-};
+  unsigned stream_base;                       // added to the dropout stream id (the _keyed entries; 0: problem * 4096 + b*H + h as ever).
+};                                            // Last, so that no other member moves and the plain kernels read what they read before
 
 // A workgroup's problem and its work item in it (item >= nwg[pi]: padding, nothing to do).  XCD x (= blockIdx % 8; blk_start is
 // a multiple of 8) walks a contiguous range of the problem's work items, so the chunks of one (b, h) and the heads of one batch
@@ -199,8 +200,8 @@ __device__ __forceinline__ void ring_handover(int j, int ntiles, const Issue& is
 // Work table: problems heaviest first; ROWS_PER_WG rows of the partitioned axis (queries, or keys for the dK/dV
 // kernel) per workgroup, with `balance` spread evenly over the chunks; workgroup ranges padded to multiples of 8 for the XCD map.
 int fill_args2(AttnArgs2& a, const mmf_attn_problem* problems, int n, float scale, float drop_p, const uint64_t* rng_state,
-               uint32_t site, bool by_keys, bool balance) {
-  a.nprob = n; a.scale = scale;
+               uint32_t site, bool by_keys, bool balance, uint32_t stream_base = 0u) {
+  a.nprob = n; a.scale = scale; a.stream_base = stream_base;
   a.drop_thresh = (drop_p > 0.f && rng_state) ? mmf_drop_thresh(drop_p) : 0u;
   a.inv_keep = a.drop_thresh ? 1.f / (1.f - (float)a.drop_thresh * (1.f / 4294967296.f)) : 1.f;
   a.site = site;

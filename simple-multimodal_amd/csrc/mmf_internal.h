@@ -138,6 +138,27 @@ static inline unsigned mmf_drop_thresh(float p) {          // host: p in [0, 1)
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
 }
+// What a streaming kernel with per-item keyed dropout takes (the Wav2Vec2 regularisers of vit.hip / wav2vec2.hip): element e of item g is
+// mmf_keep(mmf_rng_key(*state, site, item0 + g), e, thresh), kept values are multiplied by inv_keep = 1 / (1 - p), p quantised to 2^-32
+struct MmfItemDrop {
+  const unsigned long long* state;
+  unsigned site, thresh, item0;
+  float inv_keep;
+};
+// host: the checks those entries share -> dr.  thresh == 0 (p = 0 or below 2^-32): no dropout, state may be NULL
+static inline int mmf_item_drop_fill(const char* fn, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, MmfItemDrop* dr) {
+  if (!(p >= 0.0f) || p >= 1.0f) MMF_FAIL(MMF_E_SHAPE, "%s: p=%g outside [0, 1)", fn, (double)p);
+  if (item0 < 0) MMF_FAIL(MMF_E_SHAPE, "%s: item0=%lld is negative", fn, (long long)item0);
+  const unsigned thresh = mmf_drop_thresh(p);
+  if (thresh != 0u && !rng_state) MMF_FAIL(MMF_E_SHAPE, "%s: null rng_state with p=%g", fn, (double)p);
+  if (reinterpret_cast<uintptr_t>(rng_state) & 7u) MMF_FAIL(MMF_E_ALIGN, "%s: rng_state must be 8-byte aligned", fn);
+  dr->state = reinterpret_cast<const unsigned long long*>(rng_state);
+  dr->site = site;
+  dr->thresh = thresh;
+  dr->item0 = (unsigned)item0;
+  dr->inv_keep = thresh ? 1.0f / (1.0f - (float)thresh * (1.0f / 4294967296.0f)) : 1.0f;
+  return MMF_OK;
+}
 
 // transposed LDS read (ds_read_b64_tr_b16): per 16-lane group a 4-row x 16-column block of
 // 16-bit elements; lane 4q+p supplies the address of row q, columns 4p..4p+3; lane i receives

@@ -260,6 +260,34 @@ void bias_gelu_bwd_kernel(const unsigned short* dg, const unsigned short* __rest
   }
 }
 
+// GELU with activation dropout (Wav2Vec2's intermediate_dropout), both directions in one kernel.  The rows are `items` items of
+// `ipr` rows each; element (t, j) of item g is keyed by sub-stream item0 + g and index t * cols + j (MmfItemDrop, mmf_internal.h).
+//   BWD false: y <- keep ? gelu(x + bias) c : 0, one rounding (x is the raw fc1 output and is left as it is unless y is x)
+//   BWD true:  y <- keep ? dg c gelu'(x + bias) : 0, dg read from `dg` (y may be dg)
+template <bool BWD>
+__global__ __launch_bounds__(VIT_THREADS)
+void bias_gelu_drop_kernel(const unsigned short* dg, const unsigned short* x, const float* __restrict__ bias, unsigned short* y, unsigned nvec,
+                           unsigned cv /* cols/8 */, int ld, unsigned ipr, const MmfItemDrop dr) {
+  const unsigned stride = gridDim.x * VIT_THREADS;
+  const unsigned long long state = *dr.state;
+  for (unsigned v = blockIdx.x * VIT_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const unsigned r = v / cv, j = (v - r * cv) << 3, g = r / ipr, t = r - g * ipr;
+    const unsigned key = mmf_rng_key(state, dr.site, dr.item0 + g), idx = t * (cv << 3) + j;
+    float a[8], d[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(x + (size_t)r * ld + j), a);
+    if (BWD) unpack8(*reinterpret_cast<const u32x4_t*>(dg + (size_t)r * ld + j), d);
+    const f32x4_t b0 = *reinterpret_cast<const f32x4_t*>(bias + j), b1 = *reinterpret_cast<const f32x4_t*>(bias + j + 4);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xe = a[e] + (e < 4 ? b0[e] : b1[e - 4]);
+      const bool keep = mmf_keep(key, idx + (unsigned)e, dr.thresh);
+      const float val = BWD ? d[e] * dr.inv_keep * gelu_erf_grad(xe) : gelu_erf(xe) * dr.inv_keep;
+      a[e] = keep ? val : 0.0f;
+    }
+    *reinterpret_cast<u32x4_t*>(y + (size_t)r * ld + j) = pack8(a);
+  }
+}
+
 // the checks and the row split the three GELU entries share; `launch(first row, vectors)` enqueues one piece
 template <typename Launch>
 int bias_gelu_run(const char* fn, const void* a, const void* b, const void* c, const float* bias, int64_t rows, int cols, int ld, Launch launch) {
@@ -361,6 +389,41 @@ extern "C" int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows,
 
 extern "C" int mmf_bias_gelu_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, int64_t rows, int cols, int ld, void* stream) {
   return bias_gelu_fwd("mmf_bias_gelu_bf16_to", h_bf16, bias, g_bf16, rows, cols, ld, stream);
+}
+
+namespace {
+// the two dropout entries: the plain entry's checks plus the items' geometry; a threshold of 0 takes the plain kernels
+int bias_gelu_drop(const char* fn, bool bwd, const void* dg_bf16, const void* h_bf16, const float* bias, void* out_bf16, int64_t rows, int cols, int ld,
+                   int64_t items, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
+  MmfItemDrop dr;
+  if (int rc = mmf_item_drop_fill(fn, p, rng_state, site, item0, &dr)) return rc;
+  if (!bias) MMF_FAIL(MMF_E_SHAPE, "%s: null bias", fn);
+  if (items <= 0 || rows <= 0 || rows % items) MMF_FAIL(MMF_E_SHAPE, "%s: rows=%lld are not items=%lld times a row count", fn, (long long)rows, (long long)items);
+  if (cols <= 0 || (rows / items) * (int64_t)cols > ((int64_t)1 << 32) || rows * (int64_t)(cols >> 3) >= ((int64_t)1 << 31))
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: an item of %lld x %d elements (at most 2^32), %lld rows in all (rows * cols / 8 below 2^31)", fn,
+             (long long)(rows / items), cols, (long long)rows);
+  if (dr.thresh == 0u)
+    return bwd ? mmf_bias_gelu_bwd_bf16(dg_bf16, h_bf16, bias, out_bf16, rows, cols, ld, stream)
+               : mmf_bias_gelu_bf16_to(h_bf16, bias, out_bf16, rows, cols, ld, stream);
+  const unsigned short *dg = static_cast<const unsigned short*>(dg_bf16), *h = static_cast<const unsigned short*>(h_bf16);
+  unsigned short* out = static_cast<unsigned short*>(out_bf16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned ipr = (unsigned)(rows / items);
+  return bias_gelu_run(fn, bwd ? dg : h, h, out, bias, rows, cols, ld, [&](int64_t off, unsigned nvec, unsigned cv) {      // (one piece: rows * cols / 8 < 2^31)
+    if (bwd) hipLaunchKernelGGL(bias_gelu_drop_kernel<true>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, dg + off, h + off, bias, out + off, nvec, cv, ld, ipr, dr);
+    else     hipLaunchKernelGGL(bias_gelu_drop_kernel<false>, dim3(mmf_stream_grid(nvec, VIT_THREADS)), dim3(VIT_THREADS), 0, s, h + off, h + off, bias, out + off, nvec, cv, ld, ipr, dr);
+  });
+}
+}  // namespace
+
+extern "C" int mmf_bias_gelu_drop_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, int64_t rows, int cols, int ld, int64_t items,
+                                          float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
+  return bias_gelu_drop("mmf_bias_gelu_drop_bf16_to", false, nullptr, h_bf16, bias, g_bf16, rows, cols, ld, items, p, rng_state, site, item0, stream);
+}
+
+extern "C" int mmf_bias_gelu_drop_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols, int ld,
+                                           int64_t items, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
+  return bias_gelu_drop("mmf_bias_gelu_drop_bwd_bf16", true, dg_bf16, h_bf16, bias, dh_bf16, rows, cols, ld, items, p, rng_state, site, item0, stream);
 }
 
 extern "C" int mmf_bias_gelu_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols,

@@ -366,6 +366,111 @@ void w2v_weightnorm_bwd_kernel(const float* __restrict__ dw, const float* __rest
   }
 }
 
+// ---- training-mode regularisers: the time-mask draw, mask + feature-projection dropout -------------------------------------
+// The span count of HuggingFace's _compute_mask_indices for a drawn count `num` (no attention mask): raised to min_masks, T / length
+// where the spans would be longer than the clip, at most T - (length - 1).  Host and device; monotone in num.
+__host__ __device__ inline int w2v_span_count(long long num, int T, int length, int min_masks) {
+  if (num < min_masks) num = min_masks;
+  if (num * length > T) num = T / length;
+  const int room = T - (length - 1);
+  if (num > room) num = room > 0 ? room : 0;
+  return (int)num;
+}
+
+// One lane per clip: starts[clip][0 .. S_max) = the clip's span starts, -1 in the unused slots.  Draw n of clip c is
+// mmf_mix32(key + n * 0x9E3779B9) with key = mmf_rng_key(state, site, item0 + c) (mmf_keep's hash before its threshold):
+//   draw 0         the count: n0 + (draw >= up), the integer form of int(prob T / length + u), u = draw / 2^32 (the host forms
+//                  n0 = floor(e) and up = ceil((1 - frac(e)) 2^32) from e = prob T / length in double), then w2v_span_count
+//   draws 1, 2, .. the starts, uniform in 0 .. T - length as (draw * (T - length + 1)) >> 32; a start already taken is drawn again,
+//                  MASK_TRIES draws at most per start; after that the start is the next free value above the last draw, cyclically
+//                  (there is one: the count is at most T - length + 1).  Spans may overlap, as in HuggingFace.
+constexpr int MASK_TRIES = 64;
+__global__ __launch_bounds__(64)
+void w2v_mask_spans_kernel(int* __restrict__ starts, int N, int S_max, int T, int length, int n0, unsigned long long up, int min_masks,
+                           const unsigned long long* __restrict__ state, unsigned site, unsigned item0) {
+  const int clip = blockIdx.x * 64 + threadIdx.x;
+  if (clip >= N) return;
+  const unsigned key = mmf_rng_key(*state, site, item0 + (unsigned)clip);
+  unsigned n = 0u;
+  auto draw = [&]() { return mmf_mix32(key + (n++) * 0x9E3779B9u); };
+  const unsigned range = (unsigned)(T - length + 1);
+  int num = w2v_span_count((long long)n0 + ((unsigned long long)draw() >= up ? 1 : 0), T, length, min_masks);
+  num = num < S_max ? num : S_max;
+  int* row = starts + (size_t)clip * S_max;
+  auto taken = [&](int cand, int k) {
+    for (int i = 0; i < k; ++i)
+      if (row[i] == cand) return true;
+    return false;
+  };
+  for (int k = 0; k < num; ++k) {
+    int cand = 0;
+    bool free_ = false;
+    for (int a = 0; a < MASK_TRIES && !free_; ++a) {
+      cand = (int)(((unsigned long long)draw() * range) >> 32);
+      free_ = !taken(cand, k);
+    }
+    for (unsigned a = 0; a < range && !free_; ++a) {
+      cand = cand + 1 == (int)range ? 0 : cand + 1;
+      free_ = !taken(cand, k);
+    }
+    row[k] = cand;
+  }
+  for (int k = num; k < S_max; ++k) row[k] = -1;
+}
+
+__device__ __forceinline__ bool w2v_in_span(const int* __restrict__ row, int S_max, int length, int t) {
+  bool in = false;
+  for (int k = 0; k < S_max; ++k) {
+    const int s = row[k];
+    in |= s >= 0 && (unsigned)(t - s) < (unsigned)length;
+  }
+  return in;
+}
+
+// out = a row inside a span ? (EMBED: bf16(embed), else 0) : keep ? x c : 0, one pass over `items` clips of (T, d) bf16, eight elements per
+// lane; out may be x.  starts: the clips' rows of the span table or NULL (no masking); a threshold of 0 keeps everything (c = 1).  The mask of
+// element (t, j) of clip g is drawn from sub-stream item0 + g at index t d + j.  blockIdx.y walks the clips.
+template <bool EMBED>
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_mask_drop_kernel(const unsigned short* x, const float* __restrict__ embed, const int* __restrict__ starts, unsigned short* out,
+                          unsigned items, unsigned T, unsigned d8 /* d / 8 */, int S_max, int length, const MmfItemDrop dr) {
+  const unsigned long long state = dr.thresh ? *dr.state : 0ull;
+  const unsigned per8 = T * d8;
+  for (unsigned g = blockIdx.y; g < items; g += gridDim.y) {
+    const unsigned key = mmf_rng_key(state, dr.site, dr.item0 + g);
+    const int* row = starts ? starts + (size_t)g * S_max : nullptr;
+    for (unsigned v = blockIdx.x * W2V_THREADS + threadIdx.x; v < per8; v += gridDim.x * W2V_THREADS) {
+      const unsigned t = v / d8, j = (v - t * d8) << 3;
+      const size_t at = ((size_t)g * per8 + v) * 8;
+      float f[8];
+      if (row && w2v_in_span(row, S_max, length, (int)t)) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = EMBED ? embed[j + e] : 0.0f;
+      } else {
+        unpack8(*reinterpret_cast<const u32x4_t*>(x + at), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = mmf_keep(key, v * 8u + (unsigned)e, dr.thresh) ? f[e] * dr.inv_keep : 0.0f;
+      }
+      *reinterpret_cast<u32x4_t*>(out + at) = pack8(f);
+    }
+  }
+}
+
+// partial[slab][col] = the sum over the slab's rows that lie inside a span of dx[row][col], f32, rows in order: one lane per column,
+// blockIdx.y the slab of `per` rows.  mmf_sum_slabs_f32 adds the slabs in order, so the embedding's gradient has the same bits on every run.
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_mask_embed_grad_kernel(const unsigned short* __restrict__ dx, const int* __restrict__ starts, float* __restrict__ partial, int rows,
+                                int T, int d, int S_max, int length, int per) {
+  const int col = blockIdx.x * W2V_THREADS + threadIdx.x, r0 = blockIdx.y * per, r1 = r0 + per < rows ? r0 + per : rows;
+  if (col >= d) return;
+  float acc = 0.0f;
+  for (int r = r0; r < r1; ++r) {
+    const int g = r / T, t = r - g * T;
+    if (w2v_in_span(starts + (size_t)g * S_max, S_max, length, t)) acc += bf16_bits_to_f32(dx[(size_t)r * d + col]);
+  }
+  partial[(size_t)blockIdx.y * d + col] = acc;
+}
+
 struct Conv0Shape { int T0, T1, cgn, nfl, nblk; };
 
 // shared validation of the two layer-0 entry points; T1 is only meaningful with k1 > 0
@@ -538,6 +643,77 @@ extern "C" int mmf_w2v_weightnorm_bwd(const float* dw, const float* g, const flo
   const int Kp = (k * cg + 31) & ~31;
   hipLaunchKernelGGL(w2v_weightnorm_bwd_kernel, dim3(k), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream), dw, g, v, dg, dv, C * cg, cg, k, Kp,
                      overwrite_v);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+namespace {
+int mask_geometry(const char* fn, int64_t items, int T, int S_max, int length) {
+  if (items <= 0 || T <= 0 || S_max <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: items=%lld T=%d S_max=%d", fn, (long long)items, T, S_max);
+  if (length < 1 || length > T) MMF_FAIL(MMF_E_SHAPE, "%s: length=%d must be in 1 .. T=%d", fn, length, T);
+  if (items > ((int64_t)1 << 31) - 1 || items * (int64_t)S_max >= ((int64_t)1 << 31))
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: items=%lld x S_max=%d (below 2^31)", fn, (long long)items, S_max);
+  return MMF_OK;
+}
+}  // namespace
+
+extern "C" int mmf_w2v_mask_spans(int* starts, int N, int S_max, int T, double mask_prob, int length, int min_masks,
+                                  const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
+  const char* fn = "mmf_w2v_mask_spans";
+  if (!starts || !rng_state) MMF_FAIL(MMF_E_SHAPE, "%s: null operand", fn);
+  if (int rc = mask_geometry(fn, N, T, S_max, length)) return rc;
+  if (!(mask_prob > 0.0) || mask_prob > 1.0 || min_masks < 0 || item0 < 0)
+    MMF_FAIL(MMF_E_SHAPE, "%s: mask_prob=%g (in (0, 1]), min_masks=%d, item0=%lld", fn, mask_prob, min_masks, (long long)item0);
+  if ((reinterpret_cast<uintptr_t>(starts) & 3u) || (reinterpret_cast<uintptr_t>(rng_state) & 7u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: starts must be 4-byte aligned, rng_state 8-byte aligned", fn);
+  const double e = mask_prob * (double)T / (double)length;
+  const long long n0 = (long long)e;                                  // e >= 0: the floor
+  const double up = (1.0 - (e - (double)n0)) * 4294967296.0;
+  unsigned long long upi = (unsigned long long)up;
+  if ((double)upi < up) ++upi;                                        // the ceiling: 2^32 (never) where e is whole
+  if (w2v_span_count(n0 + 1, T, length, min_masks) > S_max)
+    MMF_FAIL(MMF_E_SHAPE, "%s: S_max=%d is below the %d spans a clip may draw", fn, S_max, w2v_span_count(n0 + 1, T, length, min_masks));
+  hipLaunchKernelGGL(w2v_mask_spans_kernel, dim3((N + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), starts, N, S_max, T, length,
+                     (int)(n0 > T ? T : n0), upi, min_masks, reinterpret_cast<const unsigned long long*>(rng_state), site, (unsigned)item0);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_w2v_mask_drop(const void* x_bf16, const float* embed, const int* starts, void* out_bf16, int64_t items, int T, int d,
+                                 int S_max, int length, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
+  const char* fn = "mmf_w2v_mask_drop";
+  MmfItemDrop dr;
+  if (int rc = mmf_item_drop_fill(fn, p, rng_state, site, item0, &dr)) return rc;
+  if (!x_bf16 || !out_bf16 || d <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: null operand or d=%d", fn, d);
+  if (int rc = mask_geometry(fn, items, T, starts ? S_max : 1, starts ? length : 1)) return rc;
+  if (!starts && dr.thresh == 0u) MMF_FAIL(MMF_E_SHAPE, "%s: neither spans nor dropout: nothing to do", fn);
+  if ((d & 7) || (int64_t)T * d > ((int64_t)1 << 32)) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: d=%d (a multiple of 8), T * d = %lld (at most 2^32)", fn, d, (long long)T * d);
+  if (!mmf_aligned16(x_bf16) || !mmf_aligned16(out_bf16) || (reinterpret_cast<uintptr_t>(embed) & 3u) || (reinterpret_cast<uintptr_t>(starts) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: x / out must be 16-byte aligned, embed / starts 4-byte aligned", fn);
+  const unsigned d8 = (unsigned)d >> 3;
+  const dim3 grid((unsigned)mmf_stream_grid((int64_t)T * d8, W2V_THREADS), (unsigned)(items < 65535 ? items : 65535));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned short* x = static_cast<const unsigned short*>(x_bf16);
+  unsigned short* out = static_cast<unsigned short*>(out_bf16);
+  if (embed) hipLaunchKernelGGL(w2v_mask_drop_kernel<true>, grid, dim3(W2V_THREADS), 0, s, x, embed, starts, out, (unsigned)items, (unsigned)T, d8, S_max, length, dr);
+  else       hipLaunchKernelGGL(w2v_mask_drop_kernel<false>, grid, dim3(W2V_THREADS), 0, s, x, embed, starts, out, (unsigned)items, (unsigned)T, d8, S_max, length, dr);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_w2v_mask_embed_grad(const void* dx_bf16, const int* starts, float* partial, int64_t items, int T, int d, int S_max, int length,
+                                       int slabs, void* stream) {
+  const char* fn = "mmf_w2v_mask_embed_grad";
+  if (!dx_bf16 || !starts || !partial || d <= 0) MMF_FAIL(MMF_E_SHAPE, "%s: null operand or d=%d", fn, d);
+  if (int rc = mask_geometry(fn, items, T, S_max, length)) return rc;
+  const int64_t rows = items * T;
+  if (rows >= ((int64_t)1 << 31) || slabs < 1 || slabs > MMF_SUM_SLABS_MAX || slabs > rows)
+    MMF_FAIL(MMF_E_SHAPE, "%s: rows=%lld (below 2^31), slabs=%d (1 .. %d, at most the rows)", fn, (long long)rows, slabs, MMF_SUM_SLABS_MAX);
+  if ((reinterpret_cast<uintptr_t>(dx_bf16) & 1u) || (reinterpret_cast<uintptr_t>(starts) & 3u) || (reinterpret_cast<uintptr_t>(partial) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: dx must be 2-byte aligned, starts / partial 4-byte aligned", fn);
+  const int per = (int)((rows + slabs - 1) / slabs);
+  hipLaunchKernelGGL(w2v_mask_embed_grad_kernel, dim3((d + W2V_THREADS - 1) / W2V_THREADS, slabs), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(dx_bf16), starts, partial, (int)rows, T, d, S_max, length, per);
   MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }

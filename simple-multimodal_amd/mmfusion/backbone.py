@@ -82,6 +82,9 @@ QkvWgrad = Callable[[torch.Tensor, torch.Tensor], None]        # (dqkv rows, the
 # pre-LN sum, in place.  JoinBwd(role, dy, out): the gradient dy of that sum -> out, the dense branch's share of it
 Join = Callable[[str, torch.Tensor, torch.Tensor], None]
 JoinBwd = Callable[[str, torch.Tensor, torch.Tensor], None]
+# A model's own activation launches, (forward(h, bias, g), backward(dg, h, bias, dh)) with ``lib.bias_gelu_to`` / ``bias_gelu_bwd``'s
+# arguments (Wav2Vec2's training-mode activation dropout; absent: those two)
+Act = Tuple[Callable[[torch.Tensor, torch.Tensor, torch.Tensor], None], Callable[[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor], None]]
 
 
 class BackboneOutput:
@@ -488,25 +491,32 @@ class FrozenBackbone(nn.Module):
         self._out_proj(i, att, resid, y, join)
         return y
 
-    def _ffn(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, out: torch.Tensor, join: Optional[Join] = None) -> None:
-        """out = resid + fc2(gelu(fc1(src) + b1)) + b2 on the rows of ``src``; ``join``: ``_closing``'s"""
+    def _ffn(self, i: int, ws, src: torch.Tensor, resid: torch.Tensor, out: torch.Tensor, join: Optional[Join] = None,
+             act: Optional[Act] = None) -> None:
+        """out = resid + fc2(gelu(fc1(src) + b1)) + b2 on the rows of ``src``; ``join``: ``_closing``'s; ``act``: the model's own
+        activation launch (in place here)"""
         h = self._rows(ws, "h", src.shape[0], self.config.intermediate_size)
         ops.gemm(GEMM_NT, src, self._w(f"l{i}_fc1_w"), h)
-        lib.bias_gelu(h, self._f(f"l{i}_fc1_b"))
+        if act is None:
+            lib.bias_gelu(h, self._f(f"l{i}_fc1_b"))
+        else:
+            act[0](h, self._f(f"l{i}_fc1_b"), h)
         self._closing(i, "fc2", h, resid, out, join)
 
-    def _post_ln_layer(self, i: int, ws, n: int, T: int, attend: Optional[Attend] = None, join: Optional[Join] = None) -> None:
-        """x = LayerNorm(ln + ffn(ln)), ln = LayerNorm(x + attention(x)) on the ``n * T`` rows of ``x``; ``join``: ``_closing``'s"""
+    def _post_ln_layer(self, i: int, ws, n: int, T: int, attend: Optional[Attend] = None, join: Optional[Join] = None,
+                       act: Optional[Act] = None) -> None:
+        """x = LayerNorm(ln + ffn(ln)), ln = LayerNorm(x + attention(x)) on the ``n * T`` rows of ``x``; ``join``: ``_closing``'s,
+        ``act``: ``_ffn``'s"""
         rows, d = n * T, self.config.hidden_size
         x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
         y = self._attention(i, ws, x, x, n, T, attend, join)
         self._ln(ws, y, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        self._ffn(i, ws, ln, ln, y, join)
+        self._ffn(i, ws, ln, ln, y, join, act)
         self._ln(ws, y, x, f"l{i}_ln2_w", f"l{i}_ln2_b")
 
     def _post_ln_layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, attend: Optional[Attend], attn_bwd: AttnBwd,
                             qkv_wgrad: Optional[QkvWgrad], below: bool = True, slabs: Optional[Callable[[int, int], int]] = None,
-                            join: Optional[Join] = None, join_bwd: Optional[JoinBwd] = None) -> None:
+                            join: Optional[Join] = None, join_bwd: Optional[JoinBwd] = None, act: Optional[Act] = None) -> None:
         """``_post_ln_layer`` ``i`` again from its saved input ``xin``, then its backward (the module docstring has the rows):
         ``ga`` holds the gradient of the layer's output on entry and, with ``below``, of ``xin`` on return.  ``attend`` as in
         ``_attention``; it leaves the lse where ``attn_bwd(qkv, att, datt, dqkv)`` reads it.  With ``qkv_wgrad(dqkv, xin)`` the
@@ -515,8 +525,10 @@ class FrozenBackbone(nn.Module):
         ``join`` / ``join_bwd`` (both or neither): the forward's ``_closing`` hook and its gradient.  The gradient of a pre-LN sum
         then reaches the residual branch as it is and the dense branch (the closing launch's weight and input gradients) as
         ``join_bwd(role, dy, out)`` leaves it in ``out``: the second pre-LN sum's buffer, which is free once LayerNorm 2's backward
-        has read it"""
+        has read it.  ``act`` = (forward, backward): the model's own activation launches in place of ``bias_gelu_to`` /
+        ``bias_gelu_bwd``, with their arguments (Wav2Vec2's activation dropout); None: those two"""
         c = self.config
+        gelu_to, gelu_bwd = (lib.bias_gelu_to, lib.bias_gelu_bwd) if act is None else act
         rows, d, I, R, train = n * T, c.hidden_size, c.intermediate_size, self._rows, qkv_wgrad is not None
         ga, gb, dh, dqkv, y2, gel = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I), R(g, "dqkv", rows, 3 * d), R(g, "y2", rows, d), R(g, "g", rows, I)
         ln, h, qkv, att = R(ws, "ln", rows, d), R(ws, "h", rows, I), R(ws, "qkv", rows, 3 * d), R(ws, "att", rows, d)
@@ -535,7 +547,7 @@ class FrozenBackbone(nn.Module):
         y1 = self._attention(i, ws, xin, xin, n, T, attend, join)
         self._ln(st1, y1, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
         ops.gemm(GEMM_NT, ln, W("fc1"), h)
-        lib.bias_gelu_to(h, F("fc1"), gel)
+        gelu_to(h, F("fc1"), gel)
         self._closing(i, "fc2", gel, ln, y2, join)
         self._ln(st2, y2, R(ws, "x", rows, d), f"l{i}_ln2_w", f"l{i}_ln2_b")          # for its statistics; the output is not read
         # the MLP
@@ -543,7 +555,7 @@ class FrozenBackbone(nn.Module):
         gd = dense_grad("fc2", gb)
         wgrad(gd, gel, "fc2", d, I)
         ops.gemm(GEMM_NN, gd, W("fc2"), dh)                                           # dg
-        lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
+        gelu_bwd(dh, h, F("fc1"), dh)
         wgrad(dh, ln, "fc1", I, d)
         ops.gemm(GEMM_NN, dh, W("fc1"), ga, aux=gb, epilogue=EPI_ADD_AUX)             # ga = dln1: the MLP branch + the residual
         # the attention

@@ -47,6 +47,8 @@ SYMBOLS = (
     "mmf_deberta_embed_bwd_params_workspace_bytes", "mmf_deberta_embed_bwd_params", "mmf_embedding_scatter_add_f32",
     "mmf_deberta_attn_fwd_drop", "mmf_deberta_attn_bwd_drop", "mmf_deberta_attn_bwd_pos_drop", "mmf_deberta_dropout",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
+    "mmf_attn_fwd_grouped_keyed", "mmf_attn_delta_f32_keyed", "mmf_attn_bwd_grouped_delta_keyed", "mmf_bias_gelu_drop_bf16_to",
+    "mmf_bias_gelu_drop_bwd_bf16", "mmf_w2v_mask_spans", "mmf_w2v_mask_drop", "mmf_w2v_mask_embed_grad",
 )
 
 
@@ -255,6 +257,15 @@ def load() -> C.CDLL:
     lib.mmf_deberta_attn_bwd_pos_drop.argtypes = ([vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
                                                    vp, vp, i32, vp, C.c_size_t] + drop + [vp])
     lib.mmf_deberta_dropout.argtypes = [vp, vp, vp, i32, i64, i64] + drop + [vp]
+    keyed = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, C.c_uint32, vp]       # .., scale, p, rng_state, site, stream_base
+    lib.mmf_attn_fwd_grouped_keyed.argtypes = keyed
+    lib.mmf_attn_delta_f32_keyed.argtypes = keyed
+    lib.mmf_attn_bwd_grouped_delta_keyed.argtypes = keyed
+    lib.mmf_bias_gelu_drop_bf16_to.argtypes = [vp, vp, vp, i64, i32, i32, i64] + drop + [vp]
+    lib.mmf_bias_gelu_drop_bwd_bf16.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64] + drop + [vp]
+    lib.mmf_w2v_mask_spans.argtypes = [vp, i32, i32, i32, C.c_double, i32, i32, vp, C.c_uint32, i64, vp]
+    lib.mmf_w2v_mask_drop.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32] + drop + [vp]
+    lib.mmf_w2v_mask_embed_grad.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]
     lib.mmf_deberta_embed_bwd_params_workspace_bytes.argtypes = [i64, i32]
     lib.mmf_deberta_embed_bwd_params_workspace_bytes.restype = C.c_size_t
     lib.mmf_deberta_embed_bwd_params.argtypes = [vp, vp, vp, i32, vp, f32, vp, i32, vp, vp, i32, vp, vp, vp, C.c_size_t, i64, i32, vp]
@@ -369,6 +380,49 @@ def attn_bwd_grouped_exact_delta(problems: Sequence[AttnProblem], head_dim: int,
         check(load().mmf_attn_delta_f32(arr, len(problems), head_dim, scale, stream_ptr()))
     with _Timed(f"attn_bwd_kernels<{head_dim}>", 8.0 * flops, shapes):
         check(load().mmf_attn_bwd_grouped_delta(arr, len(problems), head_dim, scale, stream_ptr()))
+
+
+def _keyed(who: str, drop) -> tuple:
+    """``drop`` = (p, state, site, stream_base) -> the trailing arguments of the ``_keyed`` attention entries (``state``: the device
+    int64 [1] RNG state)"""
+    import torch
+    p, state, site, base = drop
+    if state is not None and (not state.is_cuda or state.dtype != torch.int64 or state.numel() != 1):
+        raise ValueError(f"{who}: the dropout state must be one int64 on the GPU")
+    return float(p), None if state is None else state.data_ptr(), int(site), int(base)
+
+
+def attn_fwd_grouped_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
+    """``attn_fwd_grouped`` with dropout of the probabilities, ``drop`` = (p, state, site, stream_base): the stream id of (problem, b,
+    h) is problem * 4096 + stream_base + b H + h (``mmf_attn_fwd_grouped_keyed``); lse stays the undropped one"""
+    arr = (AttnProblem * len(problems))(*problems)
+    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
+    with _Timed(f"attn_fwd_kernel<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
+        check(load().mmf_attn_fwd_grouped_keyed(arr, len(problems), head_dim, scale, *_keyed("attn_fwd_grouped_keyed", drop), stream_ptr()))
+
+
+def attn_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
+    """delta = sum_j p_ij w_ij dp_ij in f32 under the mask of ``drop`` (``mmf_attn_delta_f32_keyed``)"""
+    arr = (AttnProblem * len(problems))(*problems)
+    shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
+    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
+    with _Timed(f"attn_delta_kernel<{head_dim}>", flops, shapes):
+        check(load().mmf_attn_delta_f32_keyed(arr, len(problems), head_dim, scale, *_keyed("attn_delta_keyed", drop), stream_ptr()))
+
+
+def attn_bwd_grouped_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
+    """the backward from a given delta under the mask of ``drop`` (``mmf_attn_bwd_grouped_delta_keyed``)"""
+    arr = (AttnProblem * len(problems))(*problems)
+    shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
+    flops = sum(8.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
+    with _Timed(f"attn_bwd_kernels<{head_dim}>", flops, shapes):
+        check(load().mmf_attn_bwd_grouped_delta_keyed(arr, len(problems), head_dim, scale, *_keyed("attn_bwd_grouped_delta_keyed", drop), stream_ptr()))
+
+
+def attn_bwd_grouped_exact_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
+    """``attn_bwd_grouped_exact_delta`` with the forward's dropout mask drawn again in all three kernels"""
+    attn_delta_keyed(problems, head_dim, scale, drop)
+    attn_bwd_grouped_delta_keyed(problems, head_dim, scale, drop)
 
 
 def layernorm_fwd_grouped(problems: Sequence[LnProblem], d: int, eps: float) -> None:
@@ -814,6 +868,80 @@ def deberta_dropout(y, out, items: int, drop, resid=None) -> None:
     with _Timed("deberta_dropout_kernel", 0.0, [(items, y.numel() // items)]):
         check(load().mmf_deberta_dropout(y.data_ptr(), None if resid is None else resid.data_ptr(), out.data_ptr(), int(f32), items,
                                          y.numel() // items, *_deberta_drop("deberta_dropout", drop), stream_ptr()))
+
+
+hidden_dropout = deberta_dropout          # the kernel is no model's own: Wav2Vec2's hidden-dropout sites reach it under this name
+
+
+def bias_gelu_drop_to(h, bias, g, items: int, drop) -> None:
+    """g <- keep ? gelu(h + bias) c : 0 (``mmf_bias_gelu_drop_bf16_to``): ``bias_gelu_to`` with dropout of the GELU's output; the rows
+    are ``items`` items, element (t, j) of item i keyed by sub-stream item0 + i and index t cols + j of ``drop`` = (p, state, site,
+    item0).  ``g`` may be ``h``"""
+    _w2v_bf16(h, g)
+    _w2v_f32(bias)
+    _gelu_blocks("bias_gelu_drop_to", bias, h, g)
+    with _Timed("bias_gelu_drop_kernel", 0.0, [tuple(h.shape)]):
+        check(load().mmf_bias_gelu_drop_bf16_to(h.data_ptr(), None if bias is None else bias.data_ptr(), g.data_ptr(), h.shape[0], h.shape[1],
+                                                h.stride(0), int(items), *_deberta_drop("bias_gelu_drop_to", drop), stream_ptr()))
+
+
+def bias_gelu_drop_bwd(dg, h, bias, dh, items: int, drop) -> None:
+    """dh <- keep ? dg c gelu'(h + bias) : 0 (``mmf_bias_gelu_drop_bwd_bf16``), the mask of ``bias_gelu_drop_to`` drawn again"""
+    _w2v_bf16(dg, h, dh)
+    _w2v_f32(bias)
+    _gelu_blocks("bias_gelu_drop_bwd", bias, dg, h, dh)
+    with _Timed("bias_gelu_drop_bwd_kernel", 0.0, [tuple(h.shape)]):
+        check(load().mmf_bias_gelu_drop_bwd_bf16(dg.data_ptr(), h.data_ptr(), None if bias is None else bias.data_ptr(), dh.data_ptr(), h.shape[0],
+                                                 h.shape[1], h.stride(0), int(items), *_deberta_drop("bias_gelu_drop_bwd", drop), stream_ptr()))
+
+
+def _w2v_starts(who: str, starts, items: int) -> int:
+    import torch
+    if not starts.is_cuda or starts.dtype != torch.int32 or starts.dim() != 2 or not starts.is_contiguous() or starts.shape[0] < items:
+        raise ValueError(f"{who}: starts must be a contiguous int32 GPU tensor (clips, slots) of at least {items} clips")
+    return starts.shape[1]
+
+
+def w2v_mask_spans(starts, T: int, mask_prob: float, length: int, min_masks: int, state, site: int, item0: int = 0) -> None:
+    """starts (N, S_max) int32 <- every clip's span starts of SpecAugment's time mask, -1 in unused slots (``mmf_w2v_mask_spans``;
+    include/mmfusion.h states the draw)"""
+    S = _w2v_starts("w2v_mask_spans", starts, 1)
+    _, sp, site, item0 = _deberta_drop("w2v_mask_spans", (0.0, state, site, item0))
+    with _Timed("w2v_mask_spans_kernel", 0.0, [tuple(starts.shape)]):
+        check(load().mmf_w2v_mask_spans(starts.data_ptr(), starts.shape[0], S, int(T), float(mask_prob), int(length), int(min_masks), sp, site,
+                                        item0, stream_ptr()))
+
+
+def w2v_mask_drop(x, out, items: int, T: int, length: int, drop, starts=None, embed=None) -> None:
+    """out <- rows inside a span of ``starts`` (the rows of the ``items`` clips; None: no masking) = bf16(``embed``) (f32 (d,); None:
+    zeros, the gradient form), every other row keep ? x c : 0 under ``drop`` = (p, state, site, item0) (``mmf_w2v_mask_drop``).
+    x, out: contiguous bf16 (items T, d); ``out`` may be ``x``"""
+    _w2v_bf16(x, out)
+    if x.dim() != 2 or x.shape != out.shape or x.shape[0] != items * T or not x.is_contiguous() or not out.is_contiguous():
+        raise ValueError("w2v_mask_drop: x and out must be contiguous (items T, d)")
+    S = _w2v_starts("w2v_mask_drop", starts, items) if starts is not None else 0
+    if embed is not None:
+        _w2v_f32(embed)
+        if embed.numel() != x.shape[1] or not embed.is_contiguous():
+            raise ValueError("w2v_mask_drop: embed must be contiguous f32 (d,)")
+    with _Timed("w2v_mask_drop_kernel", 0.0, [tuple(x.shape)]):
+        check(load().mmf_w2v_mask_drop(x.data_ptr(), None if embed is None else embed.data_ptr(), None if starts is None else starts.data_ptr(),
+                                       out.data_ptr(), int(items), int(T), x.shape[1], S, int(length), *_deberta_drop("w2v_mask_drop", drop),
+                                       stream_ptr()))
+
+
+def w2v_mask_embed_grad(dx, starts, partial, items: int, T: int, length: int) -> None:
+    """partial (slabs, d) f32 <- per slab of rows the sum of the rows of ``dx`` (items T, d) bf16 that lie inside a span
+    (``mmf_w2v_mask_embed_grad``); ``sum_slabs`` finishes the mask embedding's gradient"""
+    _w2v_bf16(dx)
+    _w2v_f32(partial)
+    S = _w2v_starts("w2v_mask_embed_grad", starts, items)
+    if dx.dim() != 2 or dx.shape[0] != items * T or not dx.is_contiguous() or partial.dim() != 2 or partial.shape[1] != dx.shape[1] \
+            or not partial.is_contiguous():
+        raise ValueError("w2v_mask_embed_grad: dx must be contiguous (items T, d) and partial contiguous f32 (slabs, d)")
+    with _Timed("w2v_mask_embed_grad_kernel", 0.0, [tuple(dx.shape)]):
+        check(load().mmf_w2v_mask_embed_grad(dx.data_ptr(), starts.data_ptr(), partial.data_ptr(), int(items), int(T), dx.shape[1], S, int(length),
+                                             partial.shape[0], stream_ptr()))
 
 
 def deberta_embed_bwd(embeds, gamma, eps: float, mask, dout, d_embeds) -> None:

@@ -56,6 +56,21 @@ K-slab form where ``_slabs_for`` says so, and the key bias gets no column sum (m
 and once per backward ``mmf_w2v_weightnorm_bwd`` turns the summed dW_eff into the gradients of the weight norm's g and v (the
 forward rounds the effective weight to bf16; the gradient passes straight through that rounding).  Gradients are added into the
 parameters' f32 ``.grad`` (the arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it) in stream order.
+
+Regularisers.  HuggingFace's model in ``train()`` masks time spans with ``masked_spec_embed``, drops at seven kinds of place and
+skips layers, and the reference trains it that way; here they are opt-in (``set_regularisation``, all off by default) and act only in a
+differentiable call in ``train()`` mode.  Such a call takes 3 + 4 L sites from ``ops.next_site()`` (``_Reg``) in HuggingFace's order:
+
+    1  feature-projection dropout   mmf_w2v_mask_drop (in place, with 2)   x = in_span ? bf16(masked_spec_embed) : keep ? proj c : 0
+    2  the time mask's spans        mmf_w2v_mask_spans, once per call      (N, slots) int32 span starts for the whole batch
+    3  after encoder.layer_norm     mmf_deberta_dropout (in place)         x = dropout(LayerNorm(y))
+    per layer: attention probabilities (mmf_attn_fwd_grouped_keyed), attention output and MLP output (NT, BIAS then
+    mmf_deberta_dropout with the residual: ``_closing``'s ``join``), GELU output (mmf_bias_gelu_drop_bf16_to: ``_ffn``'s ``act``)
+
+Masks are the counter hash keyed by (state, site, clip [* H + head], element), so results do not depend on ``chunk``, and the backward
+draws them again: ``mmf_attn_delta_f32_keyed`` + ``mmf_attn_bwd_grouped_delta_keyed``, ``mmf_bias_gelu_drop_bwd_bf16``, the gradient
+forms of the two streaming kernels, and ``mmf_w2v_mask_embed_grad`` + ``mmf_sum_slabs_f32`` for ``masked_spec_embed``'s gradient (a
+fixed-order sum).  LayerDrop is a host draw per layer and call; a skipped layer launches nothing ("Regularisers").
 """
 from __future__ import annotations
 
@@ -92,48 +107,114 @@ def feat_lengths(L: int, kernels: Sequence[int], strides: Sequence[int]) -> List
     return out
 
 
+REG_NAMES = ("hidden_dropout", "attention_dropout", "activation_dropout", "feat_proj_dropout", "layerdrop", "mask_time_prob",
+             "mask_time_length", "mask_time_min_masks")
+# wav2vec2-base-960h's training regime
+REG_960H = dict(hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1, feat_proj_dropout=0.1, layerdrop=0.1,
+                mask_time_prob=0.05, mask_time_length=10, mask_time_min_masks=2)
+
+
+def span_count(num: int, T: int, length: int, min_masks: int) -> int:
+    """the spans of a clip of ``T`` frames for a drawn count ``num``: HuggingFace's ``_compute_mask_indices`` without an attention
+    mask (``w2v_span_count`` of csrc/wav2vec2.hip)"""
+    num = max(num, min_masks)
+    if num * length > T:
+        num = T // length
+    return max(min(num, T - (length - 1)), 0)
+
+
+def span_slots(T: int, prob: float, length: int, min_masks: int) -> int:
+    """the slots per clip of the span table: the most spans ``mmf_w2v_mask_spans`` can draw, int(prob T / length) + 1 finished"""
+    return max(1, span_count(int(prob * T / length) + 1, T, length, min_masks))
+
+
+class _Reg:
+    """The regularisers of one differentiable training call.  Its 3 + 4 L sites come from ``ops.next_site()`` in HuggingFace's
+    call order: the feature projection's dropout, the time-mask draw, the dropout after ``encoder.layer_norm``, then per layer the
+    attention probabilities, the attention output, the GELU output and the MLP output, whether or not LayerDrop skips the layer.  The
+    state is read where a launch is made (``ops.rng_state()``, live: the backward draws the forward's masks again from the same state).
+    What the call keeps: ``starts`` (N, slots) int32, the time mask's span starts (drawn here, once, for the whole batch), and
+    ``skip``, LayerDrop's decision per layer (drawn by the host before the chunk loop, so every chunk agrees)."""
+    PROBS, OUT, ACT, MLP = range(4)
+
+    def __init__(self, c, N: int, T: int, dev, skip: List[bool]):
+        self.p_h, self.p_a, self.p_act, self.p_fp = c.hidden_dropout, c.attention_dropout, c.activation_dropout, c.feat_proj_dropout
+        self.H, self.length, self.skip = c.num_attention_heads, c.mask_time_length, skip
+        self.fp, self.mask, self.enc = ops.next_site(), ops.next_site(), ops.next_site()
+        self.layers = [tuple(ops.next_site() for _ in range(4)) for _ in range(c.num_hidden_layers)]
+        self.starts = None
+        if c.mask_time_prob > 0.0:
+            self.starts = torch.empty((N, span_slots(T, c.mask_time_prob, c.mask_time_length, c.mask_time_min_masks)), dtype=torch.int32,
+                                      device=dev)
+            lib.w2v_mask_spans(self.starts, T, c.mask_time_prob, c.mask_time_length, c.mask_time_min_masks, ops.rng_state(), self.mask, 0)
+
+    @property
+    def front(self) -> bool:
+        """whether the projection's output is masked or dropped"""
+        return self.starts is not None or self.p_fp > 0.0
+
+    def spans(self, n0: int, n: int) -> Optional[torch.Tensor]:
+        return None if self.starts is None else self.starts[n0:n0 + n]
+
+    def hidden(self, site: int, item0: int) -> tuple:
+        return self.p_h, ops.rng_state(), site, item0
+
+    def feat_proj(self, item0: int) -> tuple:
+        return self.p_fp, ops.rng_state(), self.fp, item0
+
+    def probs(self, i: int, item0: int) -> Optional[tuple]:
+        """the attention's (p, state, site, stream base): stream id = clip * H + head over the whole batch"""
+        return (self.p_a, ops.rng_state(), self.layers[i][self.PROBS], item0 * self.H) if self.p_a > 0.0 else None
+
+    def act(self, i: int, item0: int) -> Optional[tuple]:
+        return (self.p_act, ops.rng_state(), self.layers[i][self.ACT], item0) if self.p_act > 0.0 else None
+
+
 class _Differentiable(torch.autograd.Function):
     """``NativeWav2Vec2._launches``, differentiable with respect to the trainable parameters (``params``; never to the waveform).
     They are inputs so that the result carries a graph; their gradients are not returned but added into their f32 ``.grad`` by the
-    backward's own launches, as ``ops.queue_wgrad``'s are."""
+    backward's own launches, as ``ops.queue_wgrad``'s are.  ``reg``: the call's regularisers or None."""
 
     @staticmethod
-    def forward(ctx, model: "NativeWav2Vec2", wave: torch.Tensor, *params) -> torch.Tensor:
+    def forward(ctx, model: "NativeWav2Vec2", wave: torch.Tensor, reg: Optional[_Reg], *params) -> torch.Tensor:
         c = model.config
         N, T, L = wave.shape[0], model.frames(wave.shape[1]), c.num_hidden_layers
         first = L - model.trainable_layers                             # the lowest layer the backward walks
         keep = model._keep(first, N * T, wave.device)
         feat = torch.empty((N * T, c.conv_dim[-1]), dtype=BF16, device=wave.device) if model.trainable_front else None
         pos_w = model._pos_weight()
-        out = model._launches(wave, pos_w, keep, first, feat)
-        ctx.model, ctx.first, ctx.front, ctx.pos_w = model, first, model.trainable_front, pos_w
+        out = model._launches(wave, pos_w, keep, first, feat, reg)
+        ctx.model, ctx.first, ctx.front, ctx.pos_w, ctx.reg = model, first, model.trainable_front, pos_w, reg
         ctx.save_for_backward(*((wave, keep) if feat is None else (wave, keep, feat)))
         return out
 
     @staticmethod
     def backward(ctx, dout: torch.Tensor):
         wave, keep, *feat = ctx.saved_tensors
-        if any(ctx.needs_input_grad[2:]):
-            ctx.model._backward(wave, keep, feat[0] if ctx.front else None, ctx.first, ctx.pos_w, dout.contiguous())
+        if any(ctx.needs_input_grad[3:]):
+            ctx.model._backward(wave, keep, feat[0] if ctx.front else None, ctx.first, ctx.pos_w, dout.contiguous(), ctx.reg)
         return (None,) * len(ctx.needs_input_grad)
 
 
 class NativeWav2Vec2(FrozenBackbone):
-    """HuggingFace ``Wav2Vec2Model`` (no mask), defaults = wav2vec2-base.
+    """HuggingFace ``Wav2Vec2Model`` (no attention mask), defaults = wav2vec2-base.
 
     ``forward(input_values)`` -> ``.last_hidden_state`` (N, T, hidden) f32; ``input_values``: (N, L) f32 on the GPU.
     Frozen by default; after ``set_trainable_layers(k)``, ``k > 0``, a call in grad mode carries the top ``k`` layers' weight
     gradients (never a gradient with respect to ``input_values``).
     ``state_dict()`` has the keys, shapes and order of ``Wav2Vec2Model``; ``load_state_dict`` also takes the older weight-norm
     names (``weight_g`` / ``weight_v``).  Q/K/V are stored fused, the inner conv weights as ``(C_out, k, C_in)`` (the GEMM's
-    operand), and split / permuted on the way.  ``masked_spec_embed`` is kept as an unused parameter."""
+    operand), and split / permuted on the way.  ``masked_spec_embed`` is read only where SpecAugment's time mask is on
+    (``set_regularisation``; the training-mode regularisers are off by default)."""
 
     def __init__(self, hidden_size: int = 768, num_hidden_layers: int = 12, num_attention_heads: int = 12,
                  intermediate_size: int = 3072, conv_dim: Sequence[int] = (512,) * 7,
                  conv_kernel: Sequence[int] = (10, 3, 3, 3, 3, 2, 2), conv_stride: Sequence[int] = (5, 2, 2, 2, 2, 2, 2),
                  conv_bias: bool = False, num_conv_pos_embeddings: int = 128, num_conv_pos_embedding_groups: int = 16,
                  layer_norm_eps: float = 1e-5, feat_extract_norm: str = "group", do_stable_layer_norm: bool = False,
-                 in_channels: int = 1, chunk: int = DEFAULT_CHUNK):
+                 in_channels: int = 1, chunk: int = DEFAULT_CHUNK, hidden_dropout: float = 0.0, attention_dropout: float = 0.0,
+                 activation_dropout: float = 0.0, feat_proj_dropout: float = 0.0, layerdrop: float = 0.0, mask_time_prob: float = 0.0,
+                 mask_time_length: int = 10, mask_time_min_masks: int = 2, mask_feature_prob: float = 0.0):
         d, H, I = int(hidden_size), int(num_attention_heads), int(intermediate_size)
         dims, ks, ss = tuple(int(v) for v in conv_dim), tuple(int(v) for v in conv_kernel), tuple(int(v) for v in conv_stride)
         pk, pg = int(num_conv_pos_embeddings), int(num_conv_pos_embedding_groups)
@@ -197,6 +278,14 @@ class NativeWav2Vec2(FrozenBackbone):
                                       "o": a + "attention.out_proj", "ln1": a + "layer_norm", "fc1": a + "feed_forward.intermediate_dense",
                                       "fc2": a + "feed_forward.output_dense", "ln2": a + "final_layer_norm"})
         self._front = False                            # set_trainable_layers(L, front=True)
+        self.layerdrop_generator = torch.Generator()   # LayerDrop's host draws (CPU; seed it to fix the skip pattern)
+        if mask_feature_prob != 0:
+            raise ValueError(f"{who}: mask_feature_prob={mask_feature_prob!r}: masking along the feature axis is not built (no released "
+                             "base checkpoint sets it)")
+        self.config.mask_feature_prob = 0.0
+        self.set_regularisation(hidden_dropout=hidden_dropout, attention_dropout=attention_dropout, activation_dropout=activation_dropout,
+                                feat_proj_dropout=feat_proj_dropout, layerdrop=layerdrop, mask_time_prob=mask_time_prob,
+                                mask_time_length=mask_time_length, mask_time_min_masks=mask_time_min_masks)
 
     # -- fine-tuning --------------------------------------------------------------------------------------
     _FRONT_PARAMS = ("fp_ln_w", "fp_ln_b", "fp_w", "fp_b", "pos_b", "pos_g", "pos_v", "enc_ln_w", "enc_ln_b")
@@ -208,18 +297,76 @@ class NativeWav2Vec2(FrozenBackbone):
     def _trainable_names(self) -> list:
         """the parameters that require a gradient, in the order the differentiable forward takes them"""
         L, k = self.config.num_hidden_layers, self._trainable
-        return (list(self._FRONT_PARAMS) if self._front else []) + [n for i in range(L - k, L) for n in self._layer_params(i)]
+        front = list(self._FRONT_PARAMS) + (["masked_spec_embed"] if self.config.mask_time_prob > 0.0 else []) if self._front else []
+        return front + [n for i in range(L - k, L) for n in self._layer_params(i)]
+
+    # -- training-mode regularisers ------------------------------------------------------------------------
+    def set_regularisation(self, **settings) -> None:
+        """HuggingFace's training-mode regularisers, under its names (``REG_NAMES``; the ones not given keep their values, all 0 /
+        off at construction): ``hidden_dropout`` (after ``encoder.layer_norm`` and on every layer's attention and MLP outputs),
+        ``attention_dropout`` (the attention probabilities), ``activation_dropout`` (the GELU output), ``feat_proj_dropout`` (the
+        feature projection's output), each a probability in [0, 1); ``layerdrop``, the probability in [0, 1) of skipping a layer;
+        SpecAugment's time mask ``mask_time_prob`` in [0, 1] with ``mask_time_length`` >= 1 and ``mask_time_min_masks`` >= 0
+        (``config.apply_spec_augment`` says whether it is on).  ``REG_960H`` holds wav2vec2-base-960h's values.  They act only in
+        a call of the differentiable route (``trainable_layers > 0``, grad mode on) in ``train()`` mode; every other call is the plain
+        launch list.  Masking along the feature axis (``mask_feature_prob``) is not built.  ``masked_spec_embed`` trains exactly
+        when the front end does and ``mask_time_prob`` is above 0."""
+        who, c = "NativeWav2Vec2.set_regularisation", self.config
+        unknown = sorted(set(settings) - set(REG_NAMES))
+        if "mask_feature_prob" in unknown and settings["mask_feature_prob"] == 0:
+            unknown.remove("mask_feature_prob")
+        if unknown:
+            raise ValueError(f"{who}: {unknown} not built or not known (the settings are {', '.join(REG_NAMES)})")
+        new = {n: settings.get(n, getattr(c, n, 10 if n == "mask_time_length" else 2 if n == "mask_time_min_masks" else 0.0)) for n in REG_NAMES}
+        for n in REG_NAMES[:5]:
+            p = new[n]
+            if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p < 1.0:
+                raise ValueError(f"{who}({n}={p!r}): a probability in [0, 1)")
+        p = new["mask_time_prob"]
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError(f"{who}(mask_time_prob={p!r}): a probability in [0, 1]")
+        for n, low in (("mask_time_length", 1), ("mask_time_min_masks", 0)):
+            v = new[n]
+            if isinstance(v, bool) or not isinstance(v, int) or v < low:
+                raise ValueError(f"{who}({n}={v!r}): an integer of at least {low}")
+        for n in REG_NAMES:
+            setattr(c, n, float(new[n]) if n not in ("mask_time_length", "mask_time_min_masks") else new[n])
+        c.apply_spec_augment = c.mask_time_prob > 0.0
+        self._require_grad(self._trainable_names())
+
+    def _reg_of_call(self, N: int, T: int, dev) -> Optional[_Reg]:
+        """the regularisers of the differentiable call that is about to run: None unless the module trains with a setting above 0.
+        A call on its own starts a training forward itself (new masks, sites from 1); under a root module's forward it continues
+        that forward's site numbering.  LayerDrop is HuggingFace's ``torch.rand([]) < layerdrop`` per layer, drawn on the host from
+        ``layerdrop_generator``: no device synchronisation, but a graph capture would freeze the pattern, so it is refused there"""
+        c = self.config
+        if not self.training or not any(getattr(c, n) > 0.0 for n in REG_NAMES[:6]):
+            return None
+        if c.mask_time_prob > 0.0 and c.mask_time_length > T:             # (HuggingFace's _compute_mask_indices raises as well)
+            raise ValueError(f"NativeWav2Vec2: mask_time_length {c.mask_time_length} is longer than the clip's {T} frames")
+        L = c.num_hidden_layers
+        skip = [False] * L
+        if c.layerdrop > 0.0:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("NativeWav2Vec2: layerdrop > 0 draws its skip pattern on the host, which a graph capture would freeze "
+                                   "into every replay; capture with layerdrop = 0 (the other regularisers draw new masks on every replay)")
+            skip = [bool(torch.rand([], generator=self.layerdrop_generator).item() < c.layerdrop) for _ in range(L)]
+        if not ops.inside_root():
+            ops.begin_training_forward()
+        return _Reg(c, N, T, dev, skip)
 
     def set_trainable_layers(self, k: int, front: bool = False) -> None:
         """The parameters of the top ``k`` layers (``L - k .. L - 1``) get ``requires_grad = True``, every other parameter
         ``False``; 0 freezes the backbone again.  ``front=True`` (with ``k == L`` only: the gradient reaches the front end through
         every layer) also trains ``feature_projection.layer_norm`` and ``.projection``, the positional convolution's ``bias`` and
         its weight norm's ``g`` / ``v`` (``parametrizations.weight.original0`` / ``original1``) and ``encoder.layer_norm``.  The
-        feature-extractor convolutions, layer 0's GroupNorm and ``masked_spec_embed`` never train: this is the regime of
-        HuggingFace's ``freeze_feature_encoder()``.  With grad mode on and ``k > 0``, ``forward`` returns a result that carries a
-        graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's parameter arena) and stops
-        below layer ``L - k``.  There is no gradient with respect to the waveform; SpecAugment masking, the backbone's dropout and
-        LayerDrop are not built; the fp32 parity mode is refused as everywhere in this class."""
+        feature-extractor convolutions and layer 0's GroupNorm never train: this is the regime of HuggingFace's
+        ``freeze_feature_encoder()``.  ``masked_spec_embed`` trains with the front end where the time mask is on
+        (``mask_time_prob > 0``, ``set_regularisation``) and is frozen otherwise.  With grad mode on and ``k > 0``, ``forward``
+        returns a result that carries a graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's
+        parameter arena) and stops below layer ``L - k``.  There is no gradient with respect to the waveform; SpecAugment's time
+        mask, the backbone's dropout and LayerDrop are ``set_regularisation``'s (off by default); the fp32 parity mode is refused as
+        everywhere in this class."""
         self._check_trainable(k, "front", front, "the front end trains", "its gradient comes through every layer")
         self._trainable, self._front = k, front
         self._require_grad(self._trainable_names())
@@ -312,23 +459,51 @@ class NativeWav2Vec2(FrozenBackbone):
         wave = input_values.contiguous()
         _arena.ensure(self)
         if torch.is_grad_enabled() and self._trainable > 0:
-            return BackboneOutput(_Differentiable.apply(self, wave.detach(), *(getattr(self, n) for n in self._trainable_names())))
+            reg = self._reg_of_call(wave.shape[0], self.frames(wave.shape[1]), wave.device)
+            return BackboneOutput(_Differentiable.apply(self, wave.detach(), reg, *(getattr(self, n) for n in self._trainable_names())))
         return BackboneOutput(self._launches(wave, self._pos_weight()))
 
-    def _front_end(self, ws, feat: torch.Tensor, pos_w: torch.Tensor, n: int, T: int, st=None) -> None:
+    def _front_end(self, ws, feat: torch.Tensor, pos_w: torch.Tensor, n: int, T: int, st=None, reg: Optional[_Reg] = None,
+                   n0: int = 0) -> None:
         """feat (n T, conv_dim[-1]) -> the feature LayerNorm (into ``win``; statistics into ``st``, None: the workspace's), the
-        projection (``x``) and the positional convolution (``y``)"""
+        projection (``x``) and the positional convolution (``y``).  With ``reg`` (``n0``: the chunk's first clip in the batch) the
+        projection's output is dropped and the time mask's rows set to ``masked_spec_embed``, in place, in front of the convolution"""
         c, d, rows = self.config, self.config.hidden_size, n * T
         x, y, fln = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d), self._rows(ws, "win", rows, feat.shape[1])
         self._ln(ws if st is None else st, feat, fln, "fp_ln_w", "fp_ln_b")
         ops.gemm(GEMM_NT, fln, self._w("fp_w"), x, bias=self._f("fp_b"), epilogue=EPI_BIAS)
+        if reg is not None and reg.front:
+            lib.w2v_mask_drop(x, x, n, T, reg.length, reg.feat_proj(n0), reg.spans(n0, n), self._f("masked_spec_embed"))
         lib.w2v_posconv(x, pos_w, self._f("pos_b"), y, n, T, d, c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings)
 
+    def _hooks(self, i: int, ws, n: int, T: int, n0: int, reg: Optional[_Reg]) -> tuple:
+        """layer ``i``'s (attend, join, join_bwd, act) for a chunk of ``n`` clips from clip ``n0`` under ``reg``: the attention with
+        dropped probabilities, hidden dropout fused with the residual add and its gradient form, the GELU with activation dropout
+        and its backward; None where the setting is 0 (the plain launch)"""
+        if reg is None:
+            return None, None, None, None
+        attend = join = join_bwd = act = None
+        probs, drop = reg.probs(i, n0), reg.act(i, n0)
+        if probs is not None:
+            def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
+                lib.attn_fwd_grouped_keyed([self._attn_problem(ws, qkv, att, n, T, T)], self.head_dim, self.head_dim ** -0.5, probs)
+        if reg.p_h > 0.0:
+            sites = {"o": reg.layers[i][_Reg.OUT], "fc2": reg.layers[i][_Reg.MLP]}
+
+            def join(role: str, y: torch.Tensor, resid: torch.Tensor) -> None:
+                lib.hidden_dropout(y, y, n, reg.hidden(sites[role], n0), resid=resid)
+
+            def join_bwd(role: str, dy: torch.Tensor, out: torch.Tensor) -> None:
+                lib.hidden_dropout(dy, out, n, reg.hidden(sites[role], n0))
+        if drop is not None:
+            act = (lambda h, b, g: lib.bias_gelu_drop_to(h, b, g, n, drop), lambda dg, h, b, dh: lib.bias_gelu_drop_bwd(dg, h, b, dh, n, drop))
+        return attend, join, join_bwd, act
+
     def _launches(self, wave: torch.Tensor, pos_w: torch.Tensor, keep: Optional[torch.Tensor] = None, first: int = 0,
-                  feat_keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  feat_keep: Optional[torch.Tensor] = None, reg: Optional[_Reg] = None) -> torch.Tensor:
         """the launch list on checked inputs -> (N, T, d) f32.  The differentiable call's: ``keep`` (layers - first, N T, d) bf16
         also takes a copy of the input of every layer from ``first`` up, ``feat_keep`` (N T, conv_dim[-1]) one of the feature
-        LayerNorm's input"""
+        LayerNorm's input; ``reg``: the call's regularisers (a layer LayerDrop skips launches nothing and keeps nothing)"""
         c = self.config
         N, L = wave.shape
         Ts = feat_lengths(L, c.conv_kernel, c.conv_stride)
@@ -341,12 +516,17 @@ class NativeWav2Vec2(FrozenBackbone):
             if feat_keep is not None:
                 feat_keep[n0 * T:n0 * T + rows].copy_(feat)
             x, y = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d)
-            self._front_end(ws, feat, pos_w, n, T)
+            self._front_end(ws, feat, pos_w, n, T, None, reg, n0)
             self._ln(ws, y, x, "enc_ln_w", "enc_ln_b")
+            if reg is not None and reg.p_h > 0.0:
+                lib.hidden_dropout(x, x, n, reg.hidden(reg.enc, n0))
             for i in range(c.num_hidden_layers):
+                if reg is not None and reg.skip[i]:
+                    continue
                 if keep is not None and i >= first:
                     keep[i - first, n0 * T:n0 * T + rows].copy_(x)
-                self._post_ln_layer(i, ws, n, T)
+                attend, join, _, act = self._hooks(i, ws, n, T, n0, reg)
+                self._post_ln_layer(i, ws, n, T, attend, join, act)
             self._widen(x, out[n0:n0 + n])
         return out
 
@@ -378,28 +558,40 @@ class NativeWav2Vec2(FrozenBackbone):
         units = n * ((T + POS_WGRAD_BLOCK - 1) // POS_WGRAD_BLOCK)
         return max(1, min(2 * cus // wgs, units // 4, lib.SUM_SLABS_MAX))
 
-    def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, below: bool) -> None:
+    def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, below: bool, reg: Optional[_Reg] = None, n0: int = 0) -> None:
         """layer ``i`` again from its saved input ``xin``, then its backward with the weight, bias and LayerNorm gradients added
         into the parameters' ``.grad``: ``ga`` holds the gradient of the layer's output on entry and, with ``below``, of ``xin``
-        on return"""
-        def attn_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor) -> None:
-            lib.attn_bwd_grouped_exact_delta([self._attn_problem(ws, qkv, att, n, T, T, datt, g["delta"], dqkv)], self.head_dim,
-                                             self.head_dim ** -0.5)
-        self._post_ln_layer_grad(i, ws, g, xin, n, T, None, attn_bwd, lambda dqkv, x: self._qkv_wgrad_roles(i, g["junk"], dqkv, x),
-                                 below, self._slabs_for)
+        on return.  ``reg`` / ``n0``: the forward's regularisers and the chunk's first clip; every mask is drawn again"""
+        probs = reg.probs(i, n0) if reg is not None else None
 
-    def _front_grad(self, ws, g, feat: torch.Tensor, pos_w: torch.Tensor, pos_wt: torch.Tensor, n: int, T: int) -> None:
+        def attn_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor) -> None:
+            problem = [self._attn_problem(ws, qkv, att, n, T, T, datt, g["delta"], dqkv)]
+            if probs is None:
+                lib.attn_bwd_grouped_exact_delta(problem, self.head_dim, self.head_dim ** -0.5)
+            else:
+                lib.attn_bwd_grouped_exact_delta_keyed(problem, self.head_dim, self.head_dim ** -0.5, probs)
+        attend, join, join_bwd, act = self._hooks(i, ws, n, T, n0, reg)
+        self._post_ln_layer_grad(i, ws, g, xin, n, T, attend, attn_bwd, lambda dqkv, x: self._qkv_wgrad_roles(i, g["junk"], dqkv, x),
+                                 below, self._slabs_for, join, join_bwd, act)
+
+    def _front_grad(self, ws, g, feat: torch.Tensor, pos_w: torch.Tensor, pos_wt: torch.Tensor, n: int, T: int,
+                    reg: Optional[_Reg] = None, n0: int = 0) -> None:
         """the front end again from the saved ``feat``, then its backward: ``ga`` holds the gradient of layer 0's input on entry.
         The gradients of the encoder LayerNorm, the positional bias, the projection and the feature LayerNorm are added into
-        their ``.grad``; the positional weight's into ``g["dpos"]`` (f32, packed), which ``_backward`` finishes"""
+        their ``.grad``; the positional weight's into ``g["dpos"]`` (f32, packed), which ``_backward`` finishes.  With ``reg``
+        the front end is computed under the forward's masks again (``x0`` is the masked, dropped projection), the gradient first
+        passes the encoder dropout, the rows of dx0 inside a span are summed into ``masked_spec_embed``'s gradient where it trains
+        (per-slab partials, ``mmf_sum_slabs_f32``: a fixed order), and the projection's gradients take dproj = in_span ? 0 : dx0 keep c"""
         c = self.config
         rows, d, cd, R = n * T, c.hidden_size, c.conv_dim[-1], self._rows
         G, k = c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
         x0, y, fln = R(ws, "x", rows, d), R(ws, "y", rows, d), R(ws, "win", rows, cd)
         ga, gb, dz, dfln, dfeat = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dqkv", rows, d), R(g, "dfln", rows, cd), R(g, "dfeat", rows, cd)
         st1, st2 = self._stats(g, 1), self._stats(g, 2)
-        self._front_end(ws, feat, pos_w, n, T, st1)
+        self._front_end(ws, feat, pos_w, n, T, st1, reg, n0)
         self._ln(st2, y, R(ws, "ln", rows, d), "enc_ln_w", "enc_ln_b")               # for its statistics; the output is not read
+        if reg is not None and reg.p_h > 0.0:
+            lib.hidden_dropout(ga, ga, n, reg.hidden(reg.enc, n0))                     # through the dropout behind the encoder LayerNorm
         self._ln_bwd(st2, y, ga, gb, "enc_ln_w", (self.enc_ln_w.grad, self.enc_ln_b.grad))          # gb = dy
         lib.w2v_posconv_bwd_act(x0, pos_w, self._f("pos_b"), gb, dz, n, T, d, G, k)
         lib.colsum_grouped([lib.ColsumProblem(dz.data_ptr(), self.pos_b.grad.data_ptr(), rows, d, d)])
@@ -411,16 +603,25 @@ class NativeWav2Vec2(FrozenBackbone):
         else:
             lib.w2v_posconv_wgrad(dz, x0, g["dpos"], n, T, d, G, k, accumulate=True)
         lib.w2v_posconv_dgrad(dz, pos_wt, gb, ga, n, T, d, G, k)                     # ga = dx0: the convolution + the residual
+        if reg is not None and reg.front:
+            spans = reg.spans(n0, n)
+            if spans is not None and self.masked_spec_embed.requires_grad:
+                S = max(1, min(lib.SUM_SLABS_MAX, rows // 64))
+                partial = self._slab_buffer(S * d, ga.device).view(S, d)
+                lib.w2v_mask_embed_grad(ga, spans, partial, n, T, reg.length)
+                lib.sum_slabs(partial, self.masked_spec_embed.grad, True)            # (a vector: zeroed with the biases, never lazily)
+            lib.w2v_mask_drop(ga, ga, n, T, reg.length, reg.feat_proj(n0), spans)       # ga = dproj
         wg = self.fp_w.grad
         self._wgrad_launch([(ga, fln, wg, self.fp_b.grad)], self._first_touch(wg), self._slabs_for(rows, self._tiles(d, cd)))
         ops.gemm(GEMM_NN, ga, self._w("fp_w"), dfln)
         self._ln_bwd(st1, feat, dfln, dfeat, "fp_ln_w", (self.fp_ln_w.grad, self.fp_ln_b.grad))    # dfeat is not kept: the conv stack is frozen
 
     def _backward(self, wave: torch.Tensor, keep: torch.Tensor, feat: Optional[torch.Tensor], first: int, pos_w: torch.Tensor,
-                  dout: torch.Tensor) -> None:
+                  dout: torch.Tensor, reg: Optional[_Reg] = None) -> None:
         """for the gradient ``dout`` (N, T, d) f32 of the result: the gradients of layers ``first`` .. L - 1 and, with ``feat`` (the
         saved input of the feature LayerNorm: the front end trains), of the front end, added into their ``.grad``.  ``keep``: the
-        saved inputs of the layers from ``first`` up, ``pos_w``: the positional weight the forward used"""
+        saved inputs of the layers from ``first`` up, ``pos_w``: the positional weight the forward used, ``reg``: its regularisers
+        (a layer LayerDrop skipped is the identity: ``ga`` passes through and its parameters receive nothing)"""
         c, d, dev = self.config, self.config.hidden_size, wave.device
         self._refuse_fp32()
         N, Lw = wave.shape
@@ -433,9 +634,10 @@ class NativeWav2Vec2(FrozenBackbone):
             rows = slice(n0 * T, (n0 + n) * T)
             self._narrow(dout[n0:n0 + n], self._rows(g, "ga", n * T, d))
             for i in reversed(range(first, L)):
-                self._layer_grad(i, ws, g, keep[i - first, rows], n, T, front or i > first)
+                if reg is None or not reg.skip[i]:
+                    self._layer_grad(i, ws, g, keep[i - first, rows], n, T, front or i > first, reg, n0)
             if front:
-                self._front_grad(ws, g, feat[rows], pos_w, pos_wt, n, T)
+                self._front_grad(ws, g, feat[rows], pos_w, pos_wt, n, T, reg, n0)
         if front:
             lib.w2v_weightnorm_bwd(g["dpos"], self._f("pos_g"), self._f("pos_v"), self.pos_g.grad, self.pos_v.grad,
                                    self._first_touch(self.pos_v.grad))

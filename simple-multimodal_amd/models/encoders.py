@@ -21,7 +21,10 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers).  Frozen
     unless ``config.audio_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers then
     train; ``"all"``: every layer and the front end above the feature-extractor convolutions (feature projection, positional
-    convolution, encoder LayerNorm), which stay frozen as under HuggingFace's ``freeze_feature_encoder()``;
+    convolution, encoder LayerNorm), which stay frozen as under HuggingFace's ``freeze_feature_encoder()``.
+    ``config.audio_backbone_regularisation`` (dynamic attribute; default 0: off) switches HuggingFace's training-mode regularisers
+    on: ``True`` for wav2vec2-base-960h's dropouts, LayerDrop and SpecAugment time mask, which is what the reference trains under, or
+    a dict of ``NativeWav2Vec2.set_regularisation``'s names; they act in ``train()`` while the backbone has something to train;
   * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
     same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
     on the prompt route, from input embeddings.  On that route, with grad mode on and ``prompt_embeddings.requires_grad``, the
@@ -113,6 +116,23 @@ def _backbone_dropout(value) -> Tuple[float, float]:
     if isinstance(value, (tuple, list)) and len(value) == 2:
         return value[0], value[1]
     raise ValueError(f"text_backbone_dropout={value!r}: 0 (off), True (0.1 / 0.1) or a pair (hidden, attention)")
+
+
+def _audio_regularisation(value) -> dict:
+    """``config.audio_backbone_regularisation`` (dynamic attribute) -> the settings of ``NativeWav2Vec2.set_regularisation``: absent,
+    0 or False: all off; True: wav2vec2-base-960h's training regime (``mmfusion.wav2vec2.REG_960H``: the four dropouts and layerdrop
+    0.1, mask_time_prob 0.05 / length 10 / min 2), what the reference trains with; a dict of those names: its values over all-off
+    (``set_regularisation`` checks them)"""
+    from mmfusion.wav2vec2 import REG_960H, REG_NAMES
+    off = {**{n: 0.0 for n in REG_NAMES}, "mask_time_length": 10, "mask_time_min_masks": 2}
+    if value is True:
+        return dict(REG_960H)
+    if value is None or value is False or (isinstance(value, (int, float)) and value == 0):
+        return off
+    if isinstance(value, dict) and value and all(isinstance(k, str) for k in value):
+        return {**off, **value}
+    raise ValueError(f"audio_backbone_regularisation={value!r}: 0 (off), True (wav2vec2-base-960h's values) or a dict of "
+                     f"{', '.join(REG_NAMES)}")
 
 
 def _run_backbone(fn, native: bool, *args, input_grad: bool = False, **kw):
@@ -235,6 +255,7 @@ class AudioEncoder(_FusionBase):
                 self.model.set_trainable_layers(self.model.config.num_hidden_layers, front=True)
             else:
                 self.model.set_trainable_layers(k)
+            self.model.set_regularisation(**_audio_regularisation(getattr(config, "audio_backbone_regularisation", 0)))
         self.adapter = AdapterLayer(self.hidden_size, config.adapter_size) if hasattr(config, "adapter_size") else None
         self.temporal_attention = _MHAParams(self.hidden_size, 8)
         self.projection = nn.Linear(self.hidden_size, config.fusion_hidden_size)

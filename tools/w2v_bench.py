@@ -12,10 +12,11 @@
   * with --finetune K|all, instead: forward + backward of ``set_trainable_layers(K)`` (``all``: every layer and the front end)
     against the frozen forward, the per-kernel table of one step, stock-torch bf16 autograd through the same restatement with the
     same tensors as leaves, and (``all``) each kernel of the positional convolution's backward on one chunk beside the forward
-    ``mmf_w2v_posconv``, which does the same FLOPs.
+    ``mmf_w2v_posconv``, which does the same FLOPs.  With --regularise as well: the same step in ``train()`` under
+    wav2vec2-base-960h's regularisers (``mmfusion.wav2vec2.REG_960H``), with and without LayerDrop, and its per-kernel table.
 
     python tools/w2v_bench.py [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--no-torch]
-                              [--finetune K|all]
+                              [--finetune K|all [--regularise]]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
 import json
 
@@ -90,6 +91,19 @@ def finetune(args, model, cfg, sd, x) -> dict:
     res["grad_workspace_mb_per_clip"] = round(model.grad_workspace_bytes_per_clip(args.samples) / 2 ** 20, 2)
     res["kernels"] = kernel_table(step)
     print_table(res["kernels"])
+    if args.regularise:
+        # the same step under wav2vec2-base-960h's training regime (train() mode; LayerDrop skips a tenth of the layers, so the figure
+        # with it is an average over the steps' skip patterns, and the one without it is given beside it)
+        model.train()
+        for name, settings in (("regularised", wav2vec2.REG_960H), ("regularised_no_layerdrop", dict(wav2vec2.REG_960H, layerdrop=0.0))):
+            model.set_regularisation(**settings)
+            model.layerdrop_generator.manual_seed(0)
+            ms = time_eager(step, args.steps, args.warmup)
+            res[name + "_forward_backward_ms"], res[name + "_over_plain"] = round(ms, 3), round(ms / both, 4)
+        res["regularised_kernels"] = kernel_table(step)               # (no LayerDrop: every layer's launches)
+        print_table(res["regularised_kernels"])
+        model.set_regularisation(**{n: 0.0 for n in wav2vec2.REG_NAMES[:6]})
+        model.eval()
     if front:
         res["posconv_kernels"] = posconv_kernels(model, min(model.chunk, N), T, args.steps, args.warmup)
     if not args.no_torch:
@@ -116,6 +130,7 @@ def main():
     ap.add_argument("--clips", type=int, default=16)
     ap.add_argument("--samples", type=int, default=160000)
     ap.add_argument("--finetune", default=None, metavar="K|all")
+    ap.add_argument("--regularise", action="store_true", help="with --finetune: also time the step under wav2vec2-base-960h's regularisers")
     args = ap.parse_args()
     import w2v_ref
     from mmfusion import wav2vec2
