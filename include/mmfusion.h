@@ -367,6 +367,30 @@ int mmf_attn_bwd_grouped(const mmf_attn_problem* problems, int num_problems, int
  * mmf_attn_bwd_grouped's validation and codes. */
 int mmf_attn_delta_f32(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream);
 int mmf_attn_bwd_grouped_delta(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, void* stream);
+/* The backward of an attention whose output is consumed only through its mean over the queries (MulT's self-attentions,
+ * models/fusion_layers.py:161-168): every query row of batch row b then has the same output gradient u[b].  Here dO points at
+ * that (B, ldo) bf16 matrix, ONE row per batch row (head h at columns [h*head_dim, (h+1)*head_dim), row stride ldo as O's),
+ * already divided by Tq and rounded to bf16 as mmf_meanpool_cat_bwd rounds it; every other member as in mmf_attn_bwd_grouped.
+ * With u_h the head's columns:  c[k] = V[k,:] . u_h,  delta[q] = O[q,:] . u_h,  dS[q][k] = p[q][k] (c[k] - delta[q]),
+ * dQ = scale dS K,  dK = scale dS^T Q,  dV[k,:] = (sum_q p[q][k]) u_h: a streaming kernel writes c into the workspace (f32, f32
+ * accumulation, V read once), then a dQ kernel (which forms and writes delta from its O rows, f32) and a dK/dV kernel run without
+ * the dO.V^T and P^T.dO products of the general backward.  The results are those of mmf_attn_bwd_grouped given the materialised
+ * (B*Tq, ldo) dO, up to rounding.
+ * workspace: _workspace_bytes(problems, num_problems) bytes = 4 * sum B*H*Tk, 4-byte aligned, need not be initialised.
+ * _available answers 0 — and the caller materialises dO for mmf_attn_bwd_grouped_ex — for a head_dim other than 64 / 96 and for
+ * dropout_p != 0 (under dropout dP is no longer the same for every query).  Validation and codes of mmf_attn_bwd_grouped;
+ * MMF_E_SHAPE for a missing or short workspace. */
+int mmf_attn_bwd_grouped_uniform_available(int head_dim, float dropout_p);
+size_t mmf_attn_bwd_grouped_uniform_workspace_bytes(const mmf_attn_problem* problems, int num_problems);
+int mmf_attn_bwd_grouped_uniform(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* The same with dO made on the way, for the caller that holds the gradient of the POOLED output: dys[i] (HOST array of device
+ * pointers) is problem i's (B, lddy) bf16 gradient of mean_q O (16-byte aligned, lddy a multiple of 8 and >= H*head_dim; column
+ * blocks of one wider tensor are fine); the streaming kernel writes dO[b][:] = bf16(dys[i][b][:] / Tq) into the problem's
+ * (B, ldo) dO buffer — the one row mmf_meanpool_cat_bwd would write Tq times — and uses it; no launch of its own.  MMF_E_ALIGN
+ * for a bad dys / lddy; otherwise as above. */
+int mmf_attn_bwd_grouped_pooled(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
+                                const void* const* dys, int lddy, void* workspace, size_t workspace_bytes, void* stream);
 /* Attention-probability dropout with a caller-chosen base of the stream id: the mask of (problem, b, h, q, key) is
  * the counter hash's keep of index q*Tk + key under the key of (*rng_state, site, sub-stream problem * 4096 + stream_base + b*H + h)
  * (mmf_dropout's hash: csrc/mmf_internal.h has the two functions), so a one-problem launch of the

@@ -190,6 +190,47 @@ extern "C" int mmf_attn_bwd_grouped_delta(const mmf_attn_problem* problems, int 
   return mmf_attn_bwd2_launch(problems, num_problems, head_dim, scale, 0.f, nullptr, 0u, static_cast<hipStream_t>(stream), true);
 }
 
+// ---- the uniform backward: one output-gradient row per batch row (include/mmfusion.h; kernels in attention2.hip) ---------------
+int mmf_attn_bwd2u_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float* cws, hipStream_t s,
+                          const void* const* dys = nullptr, int lddy = 0);
+
+extern "C" int mmf_attn_bwd_grouped_uniform_available(int head_dim, float dropout_p) {
+  return (head_dim == 64 || head_dim == 96) && dropout_p == 0.f;
+}
+
+extern "C" size_t mmf_attn_bwd_grouped_uniform_workspace_bytes(const mmf_attn_problem* problems, int num_problems) {
+  size_t n = 0;
+  for (int i = 0; problems && i < num_problems; ++i)
+    if (problems[i].B > 0 && problems[i].H > 0 && problems[i].Tk > 0) n += (size_t)problems[i].B * problems[i].H * problems[i].Tk;
+  return n * sizeof(float);
+}
+
+extern "C" int mmf_attn_bwd_grouped_uniform(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "mmf_attn_bwd_grouped_uniform";
+  if (int rc = validate(fn, problems, num_problems, head_dim, true)) return rc;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u) || workspace_bytes < mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems))
+    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes (4-byte aligned) required", fn, mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems));
+  return mmf_attn_bwd2u_launch(problems, num_problems, head_dim, scale, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// ... with dO made on the way: dys[i] is problem i's (B, lddy) bf16 gradient of the POOLED output (the mean over Tq); the call writes
+// dO[b][:] = bf16(dys[i][b][:] / Tq) into the problem's (B, ldo) dO buffer — what mmf_meanpool_cat_bwd writes Tq times — and goes on
+// as mmf_attn_bwd_grouped_uniform.
+extern "C" int mmf_attn_bwd_grouped_pooled(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
+                                           const void* const* dys, int lddy, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "mmf_attn_bwd_grouped_pooled";
+  if (int rc = validate(fn, problems, num_problems, head_dim, true)) return rc;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u) || workspace_bytes < mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems))
+    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes (4-byte aligned) required", fn, mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems));
+  if (!dys || (lddy & 7)) MMF_FAIL(MMF_E_ALIGN, "%s: lddy=%d (a multiple of 8) and the gradient pointers are required", fn, lddy);
+  for (int i = 0; i < num_problems; ++i) {
+    if (!dys[i] || !mmf_aligned16(dys[i]) || lddy < problems[i].H * head_dim)
+      MMF_FAIL(MMF_E_ALIGN, "%s[%d]: the pooled gradient must be 16-byte aligned with lddy >= H*head_dim", fn, i);
+  }
+  return mmf_attn_bwd2u_launch(problems, num_problems, head_dim, scale, static_cast<float*>(workspace), static_cast<hipStream_t>(stream), dys, lddy);
+}
+
 namespace {
 int delta_launch(const char* fn, const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, const DeltaDrop* dr, void* stream) {
   if (int rc = validate(fn, problems, num_problems, head_dim, false)) return rc;

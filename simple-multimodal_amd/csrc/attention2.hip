@@ -519,6 +519,341 @@ void attn_bwd_dkv2_kernel(const AttnArgs2 a) {
   else     dkv2_wave<DH, DROP, false>(a, P, pidx, bh, k0, smem, split, -1);
 }
 
+// ================================================================================================
+// Uniform backward (mmf_attn_bwd_grouped_uniform): every query row of a batch row has the SAME output gradient u[b] — the
+// attention output is consumed only through its mean over T.  With u_h the head's columns of u[b]:
+//     c[k]     = V[k,:] . u_h           dP[q][k] = c[k] for every q: one dot product per KEY instead of a Tq x Tk product
+//     delta[q] = O[q,:] . u_h
+//     dS[q][k] = P[q][k] (c[k] - delta[q])
+//     dQ = scale dS K      dK = scale dS^T Q      dV[k,:] = (sum_q P[q][k]) u_h           (rank one)
+// Three launches: a streaming kernel for c (V read once), then the dQ kernel, which forms delta from its own O rows as dq2_wave
+// does (a first form took delta from the streaming kernel too: 22.6 us for that launch; one stream runs the launches in turn anyway),
+// then the dK/dV kernel.  Against dq2_wave / dkv2_wave: no dP chain in either, no dV chain, the ring carries ONE tile per stage
+// (K; Q), and the prologue loads Q and O; K.  The bodies are separate functions: the general ones are at their register budgets.
+// LDS: the two one-tile stages first, then the four wave-private slices of the prologue / epilogue (nothing of the ring is reused).
+// ================================================================================================
+struct UniArgs {
+  AttnArgs2 a;
+  const float* c[MMF_ATTN_MAX_PROBLEMS];      // c of a.p[i], f32 [B*H*Tk]
+};
+
+// dK^T += Q^T . dS for the 32 query rows of block QS of the Q tile: the one chain DkvStepD keeps here is PvStepD's sequence
+// (fragment n = k-substep n / DT, d-tile n % DT) with the Q tile as the transposed operand.
+template <int DH, int QS, int D, int N> using DkStepD = PvStepD<DH, QS, D, N>;
+constexpr int UNI_TRDEPTH = 2;
+
+// c of problem i: c[(b*H + h)*Tk + k] = V[b*Tk + k][h*DH ..] . u[b][h*DH ..] in f32.  A workgroup takes STAT_CHUNKS consecutive 16-byte
+// chunks of the matrix' (row, chunk) grid, one chunk per lane and pass (fully coalesced), leaves each chunk's partial sum in LDS and
+// adds the DH/8 partial sums of a (row, head): STAT_CHUNKS is a multiple of DH/8 as a row's chunk count is, so no head straddles.
+constexpr int STAT_THREADS = 256, STAT_PASSES = 6, STAT_CHUNKS = STAT_THREADS * STAT_PASSES;
+struct StatArgs {
+  int nprob;
+  int blk_start[MMF_ATTN_MAX_PROBLEMS + 1];
+  // g != nullptr (mmf_attn_bwd_grouped_pooled): u is not given but made here, u[b][:] = bf16(g[b][:] * inv) (meanpool_bwd_body's
+  // rounding), used, and written by the lanes that hold row t = 0 of a batch row
+  struct Job { const unsigned short* x; const unsigned short* u; float* out; int B, H, T, ldx, ldu; const unsigned short* g; int ldg; float inv; } j[MMF_ATTN_MAX_PROBLEMS];
+};
+template <int DH>
+__global__ __launch_bounds__(STAT_THREADS)
+void attn_uniform_stats_kernel(const StatArgs a) {
+  constexpr int CPH = DH / 8, NG = STAT_CHUNKS / CPH;
+  static_assert(STAT_CHUNKS % CPH == 0, "a head's chunks must not straddle two workgroups");
+  __shared__ float part[STAT_CHUNKS];
+  const int ji = mmf_group_problem(a.blk_start, a.nprob, blockIdx.x);
+  const StatArgs::Job& J = a.j[ji];
+  const unsigned blk = (unsigned)((int)blockIdx.x - a.blk_start[ji]);
+  const unsigned cpr = (unsigned)(J.H * CPH), nchunks = (unsigned)(J.B * J.T) * cpr;      // (the host checked the range)
+  u32x4_t x[STAT_PASSES], u[STAT_PASSES];
+#pragma unroll
+  for (int i = 0; i < STAT_PASSES; ++i) {
+    const unsigned idx = blk * STAT_CHUNKS + threadIdx.x + STAT_THREADS * i;
+    x[i] = u[i] = u32x4_t{0u, 0u, 0u, 0u};
+    if (idx < nchunks) {
+      const unsigned row = idx / cpr, ch = idx - row * cpr, b = row / (unsigned)J.T;
+      x[i] = *reinterpret_cast<const u32x4_t*>(J.x + (size_t)row * J.ldx + ch * 8);
+      if (J.g) {
+        const u32x4_t w = *reinterpret_cast<const u32x4_t*>(J.g + (size_t)b * J.ldg + ch * 8);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) u[i][e] = pack_bf16x2(bf16lo(w[e]) * J.inv, bf16hi(w[e]) * J.inv);
+        if (row == b * (unsigned)J.T) *reinterpret_cast<u32x4_t*>(const_cast<unsigned short*>(J.u) + (size_t)b * J.ldu + ch * 8) = u[i];
+      } else {
+        u[i] = *reinterpret_cast<const u32x4_t*>(J.u + (size_t)b * J.ldu + ch * 8);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < STAT_PASSES; ++i) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += bf16lo(x[i][e]) * bf16lo(u[i][e]) + bf16hi(x[i][e]) * bf16hi(u[i][e]);
+    part[threadIdx.x + STAT_THREADS * i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NG) {
+    const unsigned g = blk * NG + threadIdx.x;                // (row, head) pair
+    if (g < (unsigned)(J.B * J.T * J.H)) {
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < CPH; ++e) s += part[threadIdx.x * CPH + e];
+      const unsigned row = g / (unsigned)J.H, h = g - row * J.H, b = row / (unsigned)J.T, t = row - b * J.T;
+      J.out[((size_t)b * J.H + h) * J.T + t] = s;
+    }
+  }
+}
+
+// One wave of the uniform dQ kernel: dq2_wave<.., GIVEN> without the dP chain, the V tile and the dO rows.  dP^T[key][q] = c[key]
+// reaches the accumulator layout (key on the register, query on the lane) the way the dK/dV kernel spreads its row statistics: one
+// outer-product MFMA of the exact three-way split of this lane's c[k0 + (lane & 31)] with a ones fragment; the two values of a tile
+// are requested one tile ahead (they land behind the next hand-over's wait).
+template <int DH, bool ACTIVE>
+__device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_problem& P, const float* cst, const int bh,
+                                          const int qs, char* smem) {
+  constexpr int KS = DH / 16, DT = DH / 32, TILE_B = img_tile_bytes<DH>();
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int Tq = P.Tq, Tk = P.Tk, H = P.H;
+  const int b = bh / H, h = bh % H;
+  const unsigned short* Kg = static_cast<const unsigned short*>(P.K) + (size_t)b * Tk * P.ldk + h * DH;
+  const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cst) + (size_t)bh * Tk, 0, Tk * 4, 0x00020000);
+  TileDma<DH> dma;
+  dma.init(P.ldk, P.ldk, wave, lane);
+  auto issue = [&](int j) { dma.issue_x(Kg + (size_t)64 * j * P.ldk, P.ldk, Tk - 64 * j, smem + (j & 1) * TILE_B, wave); };
+  float ck[2];                                               // c of this lane's key of the two blocks of tile j (keys past Tk read as 0)
+  auto cstat = [&](int j) {
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+      ck[kt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsC, (unsigned)(64 * j + 32 * kt + (lane & 31)) * 4u, 0, 0));
+  };
+  const int ntiles = (Tk + 63) / 64;
+  issue(0);
+  if constexpr (ACTIVE) cstat(0);
+
+  const int qrow = qs + (lane & 31);
+  const size_t qoff = (size_t)b * Tq * P.ldq + h * DH;
+  char* slice = smem + 2 * TILE_B + wave * img_slice_bytes<DH>();
+  bf16x8_t qf[KS];
+  float delta = 0.f, lse2 = 0.f;
+  if constexpr (ACTIVE) {
+    const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(P.Q) + qoff), 0, Tq * P.ldq * 2, 0x00020000);
+    const size_t ooff = (size_t)b * Tq * P.ldo + h * DH;
+    const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short*>(P.O) + ooff, 0, Tq * P.ldo * 2, 0x00020000);
+    RowLoad<DH> rq, ro;                                       // 2 x 6 loads in flight, one wait (RowLoad, attn_helpers.h)
+    rq.issue(rsQ, P.ldq, qs, lane);
+    ro.issue(rsO, P.ldo, qs, lane);
+    rq.commit(qf, lane, slice);
+    bf16x8_t of[KS];
+    ro.commit(of, lane, slice);
+    // delta = O . u_h as dq2_wave forms O . dO, against the one row; written for the dK/dV kernel behind this one
+    const unsigned short* ug = static_cast<const unsigned short*>(P.dO) + (size_t)b * P.ldo + h * DH + 8 * half;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const u32x4_t x = __builtin_bit_cast(u32x4_t, of[ks]), y = *reinterpret_cast<const u32x4_t*>(ug + 16 * ks);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) delta += bf16lo(x[e]) * bf16lo(y[e]) + bf16hi(x[e]) * bf16hi(y[e]);
+    }
+    delta = half_sum(delta);
+    if (half == 0 && qrow < Tq) P.delta[(size_t)bh * Tq + qrow] = delta;
+    lse2 = (qrow < Tq ? P.LSE[(size_t)bh * Tq + qrow] : 0.f) * LOG2E;
+  }
+  const float c = a.scale * LOG2E;
+  f32x16_t dq[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+  const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
+  const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+
+  for (int j = 0; j < ntiles; ++j) {
+    ring_handover(j, ntiles, issue, [](int) {});
+    if constexpr (ACTIVE) {
+      const char* sK = smem + (j & 1) * TILE_B;
+      const TrBase vaK = tr_base(smem_lds + (j & 1) * TILE_B, tlo, thi);
+      const float cc[2] = {ck[0], ck[1]};
+      const bf16x8_t one3 = ones3_frag(half == 0);
+      if (j + 1 < ntiles) cstat(j + 1);
+      auto block = [&](auto KTc) {
+        constexpr int KT = decltype(KTc)::value;
+        const int k0 = j * 64 + 32 * KT;
+        if (k0 >= Tk) return;
+        f32x16_t s, dp;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cc[KT], half == 0), one3, s, 0, 0, 0);   // c[key] in every query column
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sK, 32 * KT, ks, lane), qf[ks], s, 0, 0, 0);
+        constexpr int TD = UNI_TRDEPTH;
+        s16x4_t lo[2 * DT], hi[2 * DT];
+        DkStepD<DH, KT, TD, 0>::prime(vaK, lo, hi);         // the first K^T fragments land under the dS arithmetic
+        const bool ragged = k0 + 32 > Tk;
+        f32x16_t ds;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float p = fast_exp2(__builtin_fmaf(s[r], c, -lse2));
+          const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          if (ragged) p = key < Tk ? p : 0.f;
+          ds[r] = p * (dp[r] - delta);                      // dS^T (scale applied at the store)
+        }
+        bf16x8_t pf;
+        DkStepD<DH, KT, TD, 0>::run(vaK, lo, hi, ds, pf, dq);
+      };
+      block(std::integral_constant<int, 0>{});
+      block(std::integral_constant<int, 1>{});
+    }
+  }
+  if constexpr (ACTIVE) {
+    int lane_e;                                            // (the lane id read again behind the sweep: see dq2_wave)
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    store_rows_lds<DH>(dq, a.scale, static_cast<unsigned short*>(P.dQ) + qoff, P.ldq, qs, Tq, lane_e, slice);
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(NT, DQ_WAVES_PER_SIMD)
+void attn_bwd_dq2u_kernel(const UniArgs u) {
+  __shared__ __attribute__((aligned(1024))) char smem[4 * img_tile_bytes<DH>()];
+  const AttnArgs2& a = u.a;
+  const auto [pi, item] = work_item(a);
+  if (item >= a.nwg[pi]) return;
+  const mmf_attn_problem& P = a.p[pi];
+  const int nchunk = a.nchunk[pi];
+  const int bh = item / nchunk, q0 = (item % nchunk) * ROWS_PER_WG;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int qs = q0 + 32 * wave;
+  if (qs < P.Tq) dq2u_wave<DH, true>(a, P, u.c[pi], bh, qs, smem);
+  else           dq2u_wave<DH, false>(a, P, u.c[pi], bh, qs, smem);
+}
+
+// One wave of the uniform dK/dV kernel: dkv2_wave without the dP and dV^T chains, the dO tile and the V rows.  dS = p (c_k - delta[q])
+// with c_k this lane's key's scalar; w = sum_q p[q][key] is summed per lane over the sweep (the two halves of a wave hold the same key
+// for different query rows) and dV[key,:] = w u_h is written as rows.  Query rows past Tq take LSE = +big, so that their p is 0
+// (the general kernel lets p = 1 meet dO = 0).  No sweep split: a self-attention with <= 32 keys has one tile to sweep.
+template <int DH, bool ACTIVE>
+__device__ __forceinline__ void dkv2u_wave(const AttnArgs2& a, const mmf_attn_problem& P, const float* cst, const int bh,
+                                           const int k0, char* smem) {
+  constexpr int KS = DH / 16, DT = DH / 32, TILE_B = img_tile_bytes<DH>();
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int Tq = P.Tq, Tk = P.Tk, H = P.H;
+  const int b = bh / H, h = bh % H;
+  const unsigned short* Qg = static_cast<const unsigned short*>(P.Q) + (size_t)b * Tq * P.ldq + h * DH;
+  const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc(P.LSE + (size_t)bh * Tq, 0, Tq * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(P.delta + (size_t)bh * Tq, 0, Tq * 4, 0x00020000);
+  TileDma<DH> dma;
+  dma.init(P.ldq, P.ldq, wave, lane);
+  auto issue = [&](int j) { dma.issue_x(Qg + (size_t)64 * j * P.ldq, P.ldq, Tq - 64 * j, smem + (j & 1) * TILE_B, wave); };
+  float st_l[2], st_d[2];                                    // LSE, delta of this lane's row of the two blocks of tile j (dkv2_wave)
+  auto stats = [&](int j) {
+#pragma unroll
+    for (int qs_ = 0; qs_ < 2; ++qs_) {
+      const int row = 64 * j + 32 * qs_ + (lane & 31);
+      const float l = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsL, (unsigned)row * 4u, 0, 0));
+      st_l[qs_] = row < Tq ? l : -NEG_BIG;
+      st_d[qs_] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsD, (unsigned)row * 4u, 0, 0));
+    }
+  };
+  const int ntiles = (Tq + 63) / 64;
+  issue(0);
+  if constexpr (ACTIVE) stats(0);
+
+  const size_t koff = (size_t)b * Tk * P.ldk + h * DH, voff = (size_t)b * Tk * P.ldv + h * DH;
+  char* slice = smem + 2 * TILE_B + wave * img_slice_bytes<DH>();
+  bf16x8_t kf[KS];
+  float ckey = 0.f;
+  if constexpr (ACTIVE) {
+    const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(P.K) + koff), 0, Tk * P.ldk * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cst) + (size_t)bh * Tk, 0, Tk * 4, 0x00020000);
+    RowLoad<DH> rk;
+    rk.issue(rsK, P.ldk, k0, lane);
+    ckey = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsC, (unsigned)(k0 + (lane & 31)) * 4u, 0, 0));
+    rk.commit(kf, lane, slice);
+  }
+  f32x16_t dk[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dk[dt][r] = 0.f;
+  float w = 0.f;
+  const float c = a.scale * LOG2E;
+  const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
+  const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+
+  for (int j = 0; j < ntiles; ++j) {
+    ring_handover(j, ntiles, issue, [](int) {});
+    if constexpr (ACTIVE) {
+      const char* sQ = smem + (j & 1) * TILE_B;
+      // this tile's row statistics as MFMA operands; the next tile's are requested now and land under this tile's work
+      const float nls = -1.f / a.scale;
+      const float cl[2] = {st_l[0] * nls, st_l[1] * nls}, cd[2] = {-st_d[0], -st_d[1]};
+      const bf16x8_t one3 = ones3_frag(half == 0);
+      if (j + 1 < ntiles) stats(j + 1);
+      const TrBase vaQ = tr_base(smem_lds + (j & 1) * TILE_B, tlo, thi);
+      auto block = [&](auto QSc) {
+        constexpr int QS = decltype(QSc)::value;
+        const int q0 = j * 64 + 32 * QS;
+        if (q0 >= Tq) return;
+        f32x16_t s, dm, z;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) z[r] = 0.f;
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cl[QS], half == 0), one3, z, 0, 0, 0);    // S' starts at -LSE / scale
+        dm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cd[QS], half == 0), one3, z, 0, 0, 0);   // -delta[q] in every key column
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sQ, 32 * QS, ks, lane), kf[ks], s, 0, 0, 0);
+        constexpr int TD = UNI_TRDEPTH;
+        s16x4_t lo[2 * DT], hi[2 * DT];
+        DkStepD<DH, QS, TD, 0>::prime(vaQ, lo, hi);         // the first Q^T fragments land under the P / dS arithmetic
+        f32x16_t ds;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = fast_exp2(s[r] * c);
+          w += p;
+          ds[r] = p * (dm[r] + ckey);
+        }
+        bf16x8_t dsf;
+        DkStepD<DH, QS, TD, 0>::run(vaQ, lo, hi, ds, dsf, dk);
+      };
+      block(std::integral_constant<int, 0>{});
+      block(std::integral_constant<int, 1>{});
+    }
+  }
+  if constexpr (ACTIVE) {
+    int lane_e;                                            // (the lane id read again behind the sweep: see dq2_wave)
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    store_rows_lds<DH>(dk, a.scale, static_cast<unsigned short*>(P.dK) + koff, P.ldk, k0, Tk, lane_e, slice);
+    // dV[key,:] = w u_h in the accumulator layout store_rows_lds takes: register 4g+i of tile dt is column 32 dt + 8 g + 4 half + i
+    const float wt = half_sum(w);
+    const unsigned short* ug = static_cast<const unsigned short*>(P.dO) + (size_t)b * P.ldo + h * DH + 4 * (lane_e >> 5);
+    f32x16_t dv[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const u32x2_t uu = *reinterpret_cast<const u32x2_t*>(ug + 32 * dt + 8 * g);
+        dv[dt][4 * g + 0] = wt * bf16lo(uu[0]); dv[dt][4 * g + 1] = wt * bf16hi(uu[0]);
+        dv[dt][4 * g + 2] = wt * bf16lo(uu[1]); dv[dt][4 * g + 3] = wt * bf16hi(uu[1]);
+      }
+    store_rows_lds<DH>(dv, 1.f, static_cast<unsigned short*>(P.dV) + voff, P.ldv, k0, Tk, lane_e, slice);
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(NT, 3)      // dK^T and the K fragments are 72 registers: three waves per SIMD, as the dQ kernels
+void attn_bwd_dkv2u_kernel(const UniArgs u) {
+  __shared__ __attribute__((aligned(1024))) char smem[4 * img_tile_bytes<DH>()];
+  const AttnArgs2& a = u.a;
+  const auto [pi, item] = work_item(a);
+  if (item >= a.nwg[pi]) return;
+  const mmf_attn_problem& P = a.p[pi];
+  const int nchunk = a.nchunk[pi];
+  const int bh = item / nchunk, kc0 = (item % nchunk) * ROWS_PER_WG;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int k0 = kc0 + 32 * wave;
+  if (k0 < P.Tk) dkv2u_wave<DH, true>(a, P, u.c[pi], bh, k0, smem);
+  else           dkv2u_wave<DH, false>(a, P, u.c[pi], bh, k0, smem);
+}
+
 }  // namespace
 
 #ifdef MMF_ATTN_STAMPS
@@ -563,6 +898,49 @@ int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, 
   launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dkv2_kernel<96, true>, attn_bwd_dkv2_kernel<96, false>, attn_bwd_dkv2_kernel<64, true>,
           attn_bwd_dkv2_kernel<64, false>, total, a, s);
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dkv, v2)");
+  return MMF_OK;
+}
+
+// Called by mmf_attn_bwd_grouped_uniform (attention.hip) after validation.  cws: the c arrays, problem i's B*H*Tk floats behind
+// problem i - 1's (mmf_attn_bwd_grouped_uniform_workspace_bytes).
+// dys (may be null): per problem the (B, lddy) pooled gradient the statistics kernel makes dO from (mmf_attn_bwd_grouped_pooled).
+int mmf_attn_bwd2u_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float* cws, hipStream_t s,
+                          const void* const* dys, int lddy) {
+  if (int rc = check_ranges("mmf_attn_bwd_grouped_uniform", problems, n)) return rc;
+  float* cst[MMF_ATTN_MAX_PROBLEMS];
+  StatArgs sa;
+  sa.nprob = n;
+  int sblocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const mmf_attn_problem& q = problems[i];
+    cst[i] = cws;
+    cws += (size_t)q.B * q.H * q.Tk;
+    sa.j[i] = {static_cast<const unsigned short*>(q.V), static_cast<const unsigned short*>(q.dO), cst[i], q.B, q.H, q.Tk, q.ldv, q.ldo,
+               dys ? static_cast<const unsigned short*>(dys[i]) : nullptr, lddy, 1.f / (float)q.Tq};
+    sa.blk_start[i] = sblocks;
+    const long long chunks = (long long)q.B * q.Tk * q.H * (head_dim / 8);
+    if (chunks > 0x7fffffffLL || (chunks + STAT_CHUNKS - 1) / STAT_CHUNKS + sblocks > 0x7fffffffLL)
+      MMF_FAIL(MMF_E_SHAPE, "mmf_attn_bwd_grouped_uniform[%d]: B*Tk*H*head_dim exceeds the statistics launch", i);
+    sblocks += (int)((chunks + STAT_CHUNKS - 1) / STAT_CHUNKS);
+  }
+  sa.blk_start[n] = sblocks;
+  if (head_dim == 96) hipLaunchKernelGGL(attn_uniform_stats_kernel<96>, dim3(sblocks), dim3(STAT_THREADS), 0, s, sa);
+  else                hipLaunchKernelGGL(attn_uniform_stats_kernel<64>, dim3(sblocks), dim3(STAT_THREADS), 0, s, sa);
+  MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_uniform(stats)");
+  UniArgs ua;
+  auto fill = [&](bool by_keys) {
+    const int total = fill_args2(ua.a, problems, n, scale, 0.f, nullptr, 0u, by_keys, false);
+    for (int k = 0; k < n; ++k) ua.c[k] = cst[ua.a.orig[k]];
+    return total;
+  };
+  int total = fill(false);
+  if (head_dim == 96) hipLaunchKernelGGL(attn_bwd_dq2u_kernel<96>, dim3(total), dim3(NT), 0, s, ua);
+  else                hipLaunchKernelGGL(attn_bwd_dq2u_kernel<64>, dim3(total), dim3(NT), 0, s, ua);
+  MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_uniform(dq)");
+  total = fill(true);
+  if (head_dim == 96) hipLaunchKernelGGL(attn_bwd_dkv2u_kernel<96>, dim3(total), dim3(NT), 0, s, ua);
+  else                hipLaunchKernelGGL(attn_bwd_dkv2u_kernel<64>, dim3(total), dim3(NT), 0, s, ua);
+  MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_uniform(dkv)");
   return MMF_OK;
 }
 

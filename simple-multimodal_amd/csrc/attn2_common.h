@@ -182,6 +182,13 @@ struct TileDma {
       else                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsY, (lds_void_t*)dst, 16, voff[i], 0, 0, 0);
     }
   }
+  // The X pieces alone: a one-tile stage at st (the uniform backward kernels of attention2.hip sweep one matrix)
+  __device__ __forceinline__ void issue_x(const unsigned short* Xj, int ldx, int rows_left, char* st, int wave) const {
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Xj), 0, rows_left * ldx * 2, 0x00020000);
+#pragma unroll
+    for (int i = 0; 4 * i < PIECES; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void_t*)(st + (wave + 4 * i) * 1024), 16, voff[i], 0, 0, 0);
+  }
 };
 
 // Ring hand-over at the top of tile j's iteration: this wave's pieces of tile j have landed (vmcnt), after the barrier everyone's

@@ -49,6 +49,8 @@ SYMBOLS = (
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
     "mmf_attn_fwd_grouped_keyed", "mmf_attn_delta_f32_keyed", "mmf_attn_bwd_grouped_delta_keyed", "mmf_bias_gelu_drop_bf16_to",
     "mmf_bias_gelu_drop_bwd_bf16", "mmf_w2v_mask_spans", "mmf_w2v_mask_drop", "mmf_w2v_mask_embed_grad",
+    "mmf_attn_bwd_grouped_uniform_available", "mmf_attn_bwd_grouped_uniform_workspace_bytes", "mmf_attn_bwd_grouped_uniform",
+    "mmf_attn_bwd_grouped_pooled",
 )
 
 
@@ -164,6 +166,11 @@ def load() -> C.CDLL:
     lib.mmf_attn_bwd_grouped.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
     lib.mmf_attn_delta_f32.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
     lib.mmf_attn_bwd_grouped_delta.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp]
+    lib.mmf_attn_bwd_grouped_uniform_available.argtypes = [i32, f32]
+    lib.mmf_attn_bwd_grouped_uniform_workspace_bytes.argtypes = [C.POINTER(AttnProblem), i32]
+    lib.mmf_attn_bwd_grouped_uniform_workspace_bytes.restype = C.c_size_t
+    lib.mmf_attn_bwd_grouped_uniform.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, vp, C.c_size_t, vp]
+    lib.mmf_attn_bwd_grouped_pooled.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, C.POINTER(C.c_void_p), i32, vp, C.c_size_t, vp]
     lib.mmf_layernorm_fwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, f32, vp]
     lib.mmf_layernorm_bwd_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
     lib.mmf_layernorm_bwd_add_grouped.argtypes = [C.POINTER(LnProblem), i32, i32, vp, C.c_size_t, vp]
@@ -368,6 +375,34 @@ def attn_bwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: floa
     with _Timed(f"attn_bwd_kernels<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
         check(load().mmf_attn_bwd_grouped_ex(arr, len(problems), head_dim, scale, dropout_p, rng_state_ptr, site,
                                              stream_ptr()))
+
+
+def attn_bwd_uniform_available(head_dim: int, dropout_p: float) -> bool:
+    """whether ``attn_bwd_grouped_uniform`` has kernels for this head_dim and dropout (``mmf_attn_bwd_grouped_uniform_available``)"""
+    return bool(load().mmf_attn_bwd_grouped_uniform_available(head_dim, dropout_p))
+
+
+def attn_bwd_uniform_workspace_bytes(problems: Sequence[AttnProblem]) -> int:
+    arr = (AttnProblem * len(problems))(*problems)
+    return int(load().mmf_attn_bwd_grouped_uniform_workspace_bytes(arr, len(problems)))
+
+
+def attn_bwd_grouped_uniform(problems: Sequence[AttnProblem], head_dim: int, scale: float, workspace, pooled=None) -> None:
+    """the backward of attentions consumed through their mean over the queries: ``dO`` of every problem is the (B, ldo) matrix of
+    one gradient row per batch row (include/mmfusion.h).  ``workspace``: a contiguous f32 tensor of at least
+    ``attn_bwd_uniform_workspace_bytes(problems)`` bytes (it need not be initialised).  ``pooled`` = (pointers, lddy): per problem
+    the (B, lddy) gradient of the pooled output, from which the launch itself writes those rows (``mmf_attn_bwd_grouped_pooled``)."""
+    arr = (AttnProblem * len(problems))(*problems)
+    # algorithmic work left: dQ and dK, 2 products of 2*Tq*Tk*dh; the recomputed S is not credited
+    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
+    nbytes = workspace.numel() * workspace.element_size()
+    with _Timed(f"attn_bwd_uniform_kernels<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
+        if pooled is None:
+            check(load().mmf_attn_bwd_grouped_uniform(arr, len(problems), head_dim, scale, workspace.data_ptr(), nbytes, stream_ptr()))
+        else:
+            dys = (C.c_void_p * len(problems))(*pooled[0])
+            check(load().mmf_attn_bwd_grouped_pooled(arr, len(problems), head_dim, scale, dys, pooled[1], workspace.data_ptr(), nbytes,
+                                                     stream_ptr()))
 
 
 def attn_bwd_grouped_exact_delta(problems: Sequence[AttnProblem], head_dim: int, scale: float) -> None:

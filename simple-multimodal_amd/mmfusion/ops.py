@@ -1183,31 +1183,70 @@ class AttnSpec:
     v: Tuple[int, int]
 
 
+def _attn_forward(specs: List[AttnSpec], H: int, dh: int, drop, srcs) -> Tuple[list, list]:
+    """the grouped forward launch(es): per problem the (B*Tq, d) bf16 output and the f32 LSE"""
+    scale = 1.0 / math.sqrt(dh)
+    d = H * dh
+    outs, lses, probs = [], [], []
+    for s in specs:
+        for (si, col), T in ((s.q, s.Tq), (s.k, s.Tk), (s.v, s.Tk)):
+            t = srcs[si]
+            _req(t, BF16)
+            if t.dim() != 2 or not t.is_contiguous() or t.shape[0] != s.B * T or col + d > t.shape[1]:
+                raise ValueError(f"attention source {si}: shape {tuple(t.shape)} does not hold B*T={s.B * T} rows x {d} columns at {col}")
+        dev = srcs[0].device
+        o = torch.empty((s.B * s.Tq, d), dtype=BF16, device=dev)
+        lse = torch.empty((s.B * H * s.Tq,), dtype=torch.float32, device=dev)
+        qs, ks, vs = srcs[s.q[0]], srcs[s.k[0]], srcs[s.v[0]]
+        probs.append(AttnProblem(qs.data_ptr() + 2 * s.q[1], ks.data_ptr() + 2 * s.k[1], vs.data_ptr() + 2 * s.v[1],
+                                 o.data_ptr(), lse.data_ptr(), None, None, None, None, None,
+                                 s.B, H, s.Tq, s.Tk, qs.shape[1], ks.shape[1], vs.shape[1], d))
+        outs.append(o), lses.append(lse)
+    if drop is not None and len(probs) > lib.ATTN_MAX_PROBLEMS:
+        raise ValueError("an attention group with dropout must fit one launch (the problem index keys the mask)")
+    dp_, st_, site_ = (drop[0], rng_state().data_ptr(), drop[1]) if drop is not None else (0.0, None, 0)
+    for i in range(0, len(probs), lib.ATTN_MAX_PROBLEMS):
+        lib.attn_fwd_grouped(probs[i:i + lib.ATTN_MAX_PROBLEMS], dh, scale, dp_, st_, site_)
+    return outs, lses
+
+
+def _attn_backward_problems(specs: List[AttnSpec], H: int, dh: int, srcs, outs, lses, gos) -> Tuple[list, list, list]:
+    """The backward's problem table for output gradients ``gos`` (contiguous bf16; a None skips its problem): the problems, one
+    gradient buffer per source (None where nothing flows) and the temporaries the table points into."""
+    d = H * dh
+    # one gradient buffer per source; zero-filled only when some column range is not covered
+    covered = [set() for _ in srcs]
+    for s, g in zip(specs, gos):
+        if g is None:
+            continue
+        for si, col in (s.q, s.k, s.v):
+            covered[si].add(col)
+    gsrc: List[Optional[torch.Tensor]] = []
+    for si, t in enumerate(srcs):
+        if not covered[si]:
+            gsrc.append(None)
+            continue
+        full = len(covered[si]) * d == t.shape[1]
+        gsrc.append(torch.empty_like(t) if full else torch.zeros_like(t))
+    probs, keep = [], []          # `keep`: every temporary whose pointer sits in a problem table must
+    for i, (s, g) in enumerate(zip(specs, gos)):      # outlive the launch, or the caching allocator
+        if g is None:                                 # hands its block to the next problem
+            continue
+        delta = torch.empty_like(lses[i])
+        keep += [g, delta]
+        qs, ks, vs = srcs[s.q[0]], srcs[s.k[0]], srcs[s.v[0]]
+        probs.append(AttnProblem(qs.data_ptr() + 2 * s.q[1], ks.data_ptr() + 2 * s.k[1], vs.data_ptr() + 2 * s.v[1],
+                                 outs[i].data_ptr(), lses[i].data_ptr(), g.data_ptr(), delta.data_ptr(),
+                                 gsrc[s.q[0]].data_ptr() + 2 * s.q[1], gsrc[s.k[0]].data_ptr() + 2 * s.k[1],
+                                 gsrc[s.v[0]].data_ptr() + 2 * s.v[1],
+                                 s.B, H, s.Tq, s.Tk, qs.shape[1], ks.shape[1], vs.shape[1], d))
+    return probs, gsrc, keep
+
+
 class _GroupedAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, specs: List[AttnSpec], H: int, dh: int, drop, *srcs):
-        scale = 1.0 / math.sqrt(dh)
-        d = H * dh
-        outs, lses, probs = [], [], []
-        for s in specs:
-            for (si, col), T in ((s.q, s.Tq), (s.k, s.Tk), (s.v, s.Tk)):
-                t = srcs[si]
-                _req(t, BF16)
-                if t.dim() != 2 or not t.is_contiguous() or t.shape[0] != s.B * T or col + d > t.shape[1]:
-                    raise ValueError(f"attention source {si}: shape {tuple(t.shape)} does not hold B*T={s.B * T} rows x {d} columns at {col}")
-            dev = srcs[0].device
-            o = torch.empty((s.B * s.Tq, d), dtype=BF16, device=dev)
-            lse = torch.empty((s.B * H * s.Tq,), dtype=torch.float32, device=dev)
-            qs, ks, vs = srcs[s.q[0]], srcs[s.k[0]], srcs[s.v[0]]
-            probs.append(AttnProblem(qs.data_ptr() + 2 * s.q[1], ks.data_ptr() + 2 * s.k[1], vs.data_ptr() + 2 * s.v[1],
-                                     o.data_ptr(), lse.data_ptr(), None, None, None, None, None,
-                                     s.B, H, s.Tq, s.Tk, qs.shape[1], ks.shape[1], vs.shape[1], d))
-            outs.append(o), lses.append(lse)
-        if drop is not None and len(probs) > lib.ATTN_MAX_PROBLEMS:
-            raise ValueError("an attention group with dropout must fit one launch (the problem index keys the mask)")
-        dp_, st_, site_ = (drop[0], rng_state().data_ptr(), drop[1]) if drop is not None else (0.0, None, 0)
-        for i in range(0, len(probs), lib.ATTN_MAX_PROBLEMS):
-            lib.attn_fwd_grouped(probs[i:i + lib.ATTN_MAX_PROBLEMS], dh, scale, dp_, st_, site_)
+        outs, lses = _attn_forward(specs, H, dh, drop, srcs)
         ctx.specs, ctx.H, ctx.dh, ctx.nsrc, ctx.drop = specs, H, dh, len(srcs), drop
         ctx.save_for_backward(*srcs, *outs, *lses)
         return tuple(outs)
@@ -1216,37 +1255,11 @@ class _GroupedAttention(torch.autograd.Function):
     def backward(ctx, *gos):
         specs, H, dh, ns = ctx.specs, ctx.H, ctx.dh, ctx.nsrc
         n = len(specs)
-        d = H * dh
         srcs = ctx.saved_tensors[:ns]
         outs = ctx.saved_tensors[ns:ns + n]
         lses = ctx.saved_tensors[ns + n:]
-        # one gradient buffer per source; zero-filled only when some column range is not covered
-        covered = [set() for _ in range(ns)]
-        for s, g in zip(specs, gos):
-            if g is None:
-                continue
-            for si, col in (s.q, s.k, s.v):
-                covered[si].add(col)
-        gsrc: List[Optional[torch.Tensor]] = []
-        for si, t in enumerate(srcs):
-            if not covered[si]:
-                gsrc.append(None)
-                continue
-            full = len(covered[si]) * d == t.shape[1]
-            gsrc.append(torch.empty_like(t) if full else torch.zeros_like(t))
-        probs, keep = [], []          # `keep`: every temporary whose pointer sits in a problem table must
-        for i, (s, g) in enumerate(zip(specs, gos)):      # outlive the launch, or the caching allocator
-            if g is None:                                 # hands its block to the next problem
-                continue
-            g = g.contiguous()
-            delta = torch.empty_like(lses[i])
-            keep += [g, delta]
-            qs, ks, vs = srcs[s.q[0]], srcs[s.k[0]], srcs[s.v[0]]
-            probs.append(AttnProblem(qs.data_ptr() + 2 * s.q[1], ks.data_ptr() + 2 * s.k[1], vs.data_ptr() + 2 * s.v[1],
-                                     outs[i].data_ptr(), lses[i].data_ptr(), g.data_ptr(), delta.data_ptr(),
-                                     gsrc[s.q[0]].data_ptr() + 2 * s.q[1], gsrc[s.k[0]].data_ptr() + 2 * s.k[1],
-                                     gsrc[s.v[0]].data_ptr() + 2 * s.v[1],
-                                     s.B, H, s.Tq, s.Tk, qs.shape[1], ks.shape[1], vs.shape[1], d))
+        probs, gsrc, keep = _attn_backward_problems(specs, H, dh, srcs, outs, lses,
+                                                    [None if g is None else g.contiguous() for g in gos])
         drop = ctx.drop
         if drop is not None and len(probs) != len(specs):
             raise RuntimeError("attention dropout backward needs the gradient of every problem of the group")
@@ -1267,6 +1280,53 @@ def attention_group(specs: List[AttnSpec], H: int, dh: int, srcs: Sequence[torch
         return _f32().attention_group(specs, H, dh, srcs)
     drop = (float(dropout_p), next_site()) if dropout_p > 0.0 else None
     return list(_GroupedAttention.apply(specs, H, dh, drop, *srcs))
+
+
+class _AttentionMeanPool(torch.autograd.Function):
+    """``meanpool_cat`` of ``attention_group``'s outputs as one node: the forward is those two steps' launches; the backward never
+    writes the (B*T, d) output gradients — every row of a batch row's is the same u[b] = bf16(g[b] / T) — and hands the (B, d)
+    rows to the uniform attention backward (include/mmfusion.h: mmf_attn_bwd_grouped_uniform)."""
+
+    @staticmethod
+    def forward(ctx, specs: List[AttnSpec], H: int, dh: int, *srcs):
+        outs, lses = _attn_forward(specs, H, dh, None, srcs)
+        n, B, d = len(specs), specs[0].B, H * dh
+        y = torch.empty((B, n * d), dtype=BF16, device=srcs[0].device)
+        ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        Ts = (C.c_int * n)(*[s.Tq for s in specs])
+        lib.check(lib.load().mmf_meanpool_cat_fwd(ptrs, Ts, n, y.data_ptr(), B, d, n * d, lib.stream_ptr()))
+        ctx.specs, ctx.H, ctx.dh, ctx.nsrc = specs, H, dh, len(srcs)
+        ctx.save_for_backward(*srcs, *outs, *lses)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        specs, H, dh, ns = ctx.specs, ctx.H, ctx.dh, ctx.nsrc
+        n, B, d = len(specs), specs[0].B, H * dh
+        srcs = ctx.saved_tensors[:ns]
+        outs = ctx.saved_tensors[ns:ns + n]
+        lses = ctx.saved_tensors[ns + n:]
+        if g.dtype != BF16 or g.stride(1) != 1 or g.stride(0) % 8 or g.data_ptr() % 16:
+            g = g.contiguous()
+        u = torch.empty((n, B, d), dtype=BF16, device=g.device)                 # one gradient row per batch row, written by the launch
+        probs, gsrc, keep = _attn_backward_problems(specs, H, dh, srcs, outs, lses, [u[i] for i in range(n)])
+        ws = torch.empty((lib.attn_bwd_uniform_workspace_bytes(probs) // 4,), dtype=torch.float32, device=g.device)
+        lib.attn_bwd_grouped_uniform(probs, dh, 1.0 / math.sqrt(dh), ws,
+                                     pooled=([g.data_ptr() + 2 * i * d for i in range(n)], g.stride(0)))
+        return (None, None, None, *gsrc)
+
+
+def attention_meanpool_group(specs: List[AttnSpec], H: int, dh: int, srcs: Sequence[torch.Tensor],
+                             dropout_p: float = 0.0) -> torch.Tensor:
+    """``meanpool_cat`` of ``attention_group``'s outputs, (B, n*d) bf16, for attentions that are consumed through their mean over
+    the queries only (MulT's self-attentions).  Forward: those two steps' launches.  Backward: the uniform attention backward
+    where the library has it for this head_dim and dropout (``lib.attn_bwd_uniform_available``); else, and in fp32 mode, the
+    two steps as they are."""
+    if (_PRECISION == "fp32" or not 0 < len(specs) <= min(lib.POOL_MAX, lib.ATTN_MAX_PROBLEMS) or any(s.B != specs[0].B for s in specs)
+            or not lib.attn_bwd_uniform_available(dh, float(dropout_p))):
+        att = attention_group(specs, H, dh, srcs, dropout_p=dropout_p)
+        return meanpool_cat([o.view(s.B, s.Tq, H * dh) for o, s in zip(att, specs)])
+    return _AttentionMeanPool.apply(specs, H, dh, *srcs)
 
 
 # --------------------------------------------------------------------------------------------

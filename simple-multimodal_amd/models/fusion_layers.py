@@ -228,12 +228,15 @@ def _norm2_sums(blocks, xs, pre2) -> List[torch.Tensor]:
 
 
 def _self_attention_core(mhas: Sequence[_MHAParams], xs: Sequence[torch.Tensor], B: int, Ts: Sequence[int],
-                         p: float = 0.0) -> List[torch.Tensor]:
+                         p: float = 0.0, pooled: bool = False):
     """packed QKV projection + fused attention of n independent self-attention MHAs; the
-    out-projection is left to the caller."""
+    out-projection is left to the caller.  ``pooled``: the outputs' means over T instead, side by side as one (B, n*d)
+    tensor (``ops.attention_meanpool_group``: the backward then needs no (B*T, d) output gradient)."""
     d, H, dh = mhas[0].embed_dim, mhas[0].num_heads, mhas[0].head_dim
     qkv = ops.linear_group([(x, m.qkv_spec(), None) for m, x in zip(mhas, xs)])
     specs = [AttnSpec(B, Ts[i], Ts[i], q=(i, 0), k=(i, d), v=(i, 2 * d)) for i in range(len(mhas))]
+    if pooled:
+        return ops.attention_meanpool_group(specs, H, dh, qkv, dropout_p=p)
     return ops.attention_group(specs, H, dh, qkv, dropout_p=p)
 
 
@@ -363,25 +366,25 @@ class MultimodalTransformer(_FusionBase):
                 pre2 = _cross_blocks([blocks[i] for i in g], [qs[i] for i in g], [kvs[i] for i in g], B,
                                      [Tqs[i] for i in g], [Tks[i] for i in g], p, [ress[i] for i in g], norm2=False)
                 es = _norm2_sums([blocks[i] for i in g], [xs3[m] for m in ms], pre2)                      # :209, :156-158
-                return _self_attention_core([mhas[m] for m in ms], es, B, [Ts3[m] for m in ms], p)
+                return _self_attention_core([mhas[m] for m in ms], es, B, [Ts3[m] for m in ms], p, pooled=True)
             main = torch.cuda.current_stream()
             side = ops.branch_stream(1)                     # stream 0 belongs to HierarchicalFusion's small branches
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                att_side = chain([1, 2])
-            att = [*chain([0]), *att_side]
+                pooled_side = chain([1, 2])
+            pooled_main = chain([0])
             main.wait_stream(side)
-            for x in att_side:
-                x.record_stream(main)
+            pooled_side.record_stream(main)
+            pooled_att = torch.cat([pooled_main, pooled_side], dim=1)     # (its backward hands each chain its column block as a view)
         else:
             pre2 = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress, norm2=False)               # :146-153 up to norm2
             et, ea, ev = _norm2_sums(blocks, [t, a, v], pre2)                                  # :209, :156-158, one launch
-            att = _self_attention_core(mhas, [et, ea, ev], B, [Tt, Ta, Tv], p)
+            pooled_att = _self_attention_core(mhas, [et, ea, ev], B, [Tt, Ta, Tv], p, pooled=True)
         # :161-168.  The self-attention outputs are only ever used through their mean over T, and the
-        # out-projection is affine, so mean_t(out_proj(o_t)) == out_proj(mean_t o_t): pool the attention
-        # output first and run the three out-projections on (B, d) instead of (B*T, d) rows — the same
+        # out-projection is affine, so mean_t(out_proj(o_t)) == out_proj(mean_t o_t): the attention output is pooled
+        # first (above, in one node with the attention, so that the backward works from the pooled gradient) and the three
+        # out-projections run on (B, d) instead of (B*T, d) rows — the same
         # arithmetic up to fp reassociation, minus 2*(Tt+Ta+Tv)*d^2 FLOP/sample forward and twice that backward.
-        pooled_att = ops.meanpool_cat([att[0].view(B, Tt, d), att[1].view(B, Ta, d), att[2].view(B, Tv, d)])
         pf = ops.linear_group([(x, _lin(m.out_proj), None) for x, m in zip(sops.split3(pooled_att), mhas)],
                               out_f32=True, cat=True)                           # :171 (B, 3d) f32, written in place
         fused = ops.linear(pf, *_wb(self.final_fusion[0]), relu=True, out_f32=True, dropout_p=p)      # :172
