@@ -32,6 +32,7 @@ import torch.nn.functional as F
 
 from . import dp, lib
 from .arena import ALIGN as ARENA_ALIGN, ParamArena
+from .backbone import FrozenBackbone
 
 
 def coalesce_ranges(spans: Iterable[Tuple[int, int]], align: int = ARENA_ALIGN) -> List[Tuple[int, int]]:
@@ -474,11 +475,18 @@ class FusionTrainStep:
         """exchange: "after" = one bucketed all-reduce of the gradient arena after backward; "backward" = the exchange
         runs inside backward in ``exchange_rounds`` reverse-autograd rounds (``dp.BackwardExchange``; replicated optimiser
         only).  opt: the optimiser over ``arena``; None builds the fusion recipe's (AdamW, OneCycleLR evaluated on the
-        device per step, clipping at ``max_grad_norm``).  A model with frozen parameters in the arena (a native text backbone
-        that trains its top layers only) hands in ``finetune_optimizer(model, arena, ...)``: the fine-tuning recipe."""
+        device per step, clipping at ``max_grad_norm``) over the arena's parameters that require a gradient: the whole arena in
+        one launch when all of them do, else their coalesced ranges (a native backbone registers its frozen weights as
+        parameters of the same arena, and a whole-arena launch would apply weight decay to them where torch's AdamW skips a
+        parameter without a gradient).  ``finetune_optimizer(model, arena, ...)`` builds the same selection for a caller that
+        wants other hyper-parameters."""
         self.model, self.head, self.arena = model, head, arena
         if opt is None:
-            opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard_optimizer)
+            # the whole arena in one launch unless it holds frozen parameters (a native backbone's): then the subset form over
+            # the parameters that require a gradient, as ``finetune_optimizer`` builds it (not with ``shard_optimizer``)
+            live = [p for p in arena.params if p.requires_grad]
+            opt = FusedAdamW(arena, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, shard=shard_optimizer,
+                             params=None if len(live) == len(arena.params) else live)
             opt.set_schedule(lr, total_steps)
         self.opt = opt
         self.max_lr, self.total_steps, self.contrastive, self.allreduce = lr, total_steps, contrastive, allreduce
@@ -533,7 +541,9 @@ class DistillTrainStep(FusionTrainStep):
          d/d(student logits);
       5. ``backward_from``; 6. the gradient exchange of ``FusionTrainStep`` at world size > 1;
       7. ``FusedAdamW`` over the STUDENT's arena only: the teacher's weights are in an arena of their own that no optimiser
-         touches (no weight decay on frozen weights).
+         touches (no weight decay on frozen weights).  A student on native backbones holds their frozen weights in its arena:
+         the step then covers the student's parameters that require a gradient only (``FusionTrainStep``'s selection; the
+         whole-arena launch when every one does).
 
     Everything after the constructor is graph-capturable (capture single-stream, ``bench.single_stream``)."""
 
@@ -579,7 +589,8 @@ class RobustTrainStep(FusionTrainStep):
       6. ``FusedAdamW`` at a constant lr = ``lr / 25`` with betas (0.95, 0.999) — what ``OneCycleLR``'s constructor
          leaves on the optimiser (initial_lr = max_lr / div_factor, beta1 = max_momentum); the loop never steps the
          scheduler — without clipping (the loop never clips), over the parameters the loss reaches only
-         (``reached_parameters``): torch's AdamW skips the ones whose ``.grad`` is None, weight decay included.
+         (``reached_parameters``): torch's AdamW skips the ones whose ``.grad`` is None, weight decay included.  A frozen
+         parameter (``requires_grad = False``: a native backbone's below its trainable layers) is never among them.
 
     ``missing_modalities`` is fixed per captured graph, like every other host-side argument: everything after the constructor
     is graph-capturable for one scenario (capture single-stream, ``bench.single_stream``)."""
@@ -603,9 +614,13 @@ class RobustTrainStep(FusionTrainStep):
         """The parameters a loss on ``robust_prediction`` gives a gradient: the encoders without their adapters and prompt
         embeddings (the forward runs with ``use_adapter = use_prompt = False``), the modality-only classifiers and the
         availability predictor.  The fusion layer, the ``EmotionClassifier`` and the valence / arousal / uncertainty heads
-        run (their outputs are returned) but do not reach the loss."""
+        run (their outputs are returned) but do not reach the loss.  The selection is by name, then by ``requires_grad``: a
+        native backbone keeps its frozen weights as parameters under ``base_model.<kind>_encoder`` and only its trainable
+        layers' are reached (a HuggingFace backbone's parameters all require a gradient, as the reference trains them)."""
         out = []
         for n, p in model.named_parameters():
+            if not p.requires_grad:
+                continue
             if n.startswith("base_model."):
                 parts = n.split(".")
                 if parts[1] not in ("text_encoder", "audio_encoder", "video_encoder"):
@@ -631,7 +646,10 @@ class FewShotTrainStep(FusionTrainStep):
 
       1. the constructor sets ``requires_grad`` by name, as the reference trainer does: True for a parameter whose name
          contains ``adapter``, ``prompt_embeddings`` or ``prototype_network``, False for every other one — the backward
-         then queues no weight gradient for a frozen weight (mmfusion.ops: the deferred wgrad queue);
+         then queues no weight gradient for a frozen weight (mmfusion.ops: the deferred wgrad queue).  No backbone parameter
+         has such a name, so a native backbone built with trainable layers is frozen by that rule: the constructor also calls
+         its ``set_trainable_layers(0)``, so that ``trainable_layers`` and the parameters' ``requires_grad`` agree and its
+         forward takes the frozen route (the prompt route keeps ``NativeDeberta``'s input gradient);
       2. zero the gradient arena (lazily); forward of the wrapper in training mode (dropout, ``ModalityDropout``);
       3. ``nn.CrossEntropyLoss()`` on ``predictions`` — probabilities already, the reference's double softmax — as ONE
          ``small_ops.fusion_loss`` launch without label smoothing;
@@ -647,6 +665,9 @@ class FewShotTrainStep(FusionTrainStep):
         from . import arena as arena_mod
         for name, p in model.named_parameters():
             p.requires_grad_(any(k in name for k in FEWSHOT_TRAINABLE))
+        for m in model.modules():                        # frozen by name above: frozen in the backbone's own book-keeping too
+            if isinstance(m, FrozenBackbone) and m.trainable_layers > 0:
+                m.set_trainable_layers(0)
         arena = arena_mod.ensure(model)
         self.n_way, self.n_shot = int(n_way), int(n_shot)
         self.reached = self.reached_parameters(model)
@@ -665,6 +686,8 @@ class FewShotTrainStep(FusionTrainStep):
         text_backbone = getattr(model.base_model.text_encoder, "model", None) is not None
         out = []
         for n, p in model.named_parameters():
+            if not p.requires_grad:
+                continue
             if n.startswith("prototype_network.") or ".adapter." in n:
                 out.append(p)
             elif n.endswith("prompt_embeddings") and text_backbone:

@@ -137,6 +137,7 @@ def _run_queue(monkeypatch):
     from mmfusion import arena as arena_mod, ops
     calls = []
     monkeypatch.setattr(ops, "gemm_group", lambda layout, probs, epi, *a, **k: calls.append((layout, list(probs), epi)))
+    monkeypatch.setattr(ops, "_branch_streams", [])      # (a GPU test earlier in the same process leaves its branch streams behind)
     ar = _FirstTouchArena(256)
     monkeypatch.setattr(arena_mod, "_ARENAS", {ar})
     W1, W2, W3, W4 = (ar.grads[0:32].view(4, 8), ar.grads[64:112].view(6, 8), ar.grads[128:160].view(4, 8),
