@@ -747,7 +747,7 @@ int mmf_bias_gelu_bf16_to(const void* h_bf16, const float* bias, void* g_bf16, i
 int mmf_bias_gelu_bwd_bf16(const void* dg_bf16, const void* h_bf16, const float* bias, void* dh_bf16, int64_t rows, int cols, int ld,
                            void* stream);
 /* The two with dropout of the GELU's output (Wav2Vec2's activation_dropout).  The rows are `items` items of rows / items rows each;
- * element (t, j) of item g is keyed as mmf_deberta_dropout keys it, sub-stream item0 + g and index t * cols + j, c = 1 / (1 - p):
+ * element (t, j) of item g is keyed as mmf_hidden_dropout keys it, sub-stream item0 + g and index t * cols + j, c = 1 / (1 - p):
  *   _drop_bf16_to   g <- keep ? gelu(h + bias) c : 0 in f32, one rounding; h kept raw
  *   _drop_bwd_bf16  dh <- keep ? dg c gelu'(h + bias) : 0, one rounding; dh may be dg
  * bias is required; p in [0, 1) quantised as mmf_dropout's, a threshold of 0 runs the plain kernels (the same bits); rows % items == 0,
@@ -823,7 +823,7 @@ int mmf_w2v_mask_spans(int* starts, int N, int S_max, int T, double mask_prob, i
                        uint32_t site, int64_t item0, void* stream);
 /* Masking and feature-projection dropout in one pass over `items` clips of (T, d) bf16: a row t with starts[g][k] <= t < starts[g][k] +
  * length for some k becomes bf16(embed) (embed f32 [d]; NULL: zeros, the gradient form: dproj = in_span ? 0 : dx0 keep c), any other
- * row is keep ? x c : 0 with the mask of element (t, j) of clip g keyed as mmf_deberta_dropout's: sub-stream item0 + g, index t d + j.
+ * row is keep ? x c : 0 with the mask of element (t, j) of clip g keyed as mmf_hidden_dropout's: sub-stream item0 + g, index t d + j.
  * starts: the span rows of the call's first clip on, or NULL (dropout only); p = 0: masking only; out may be x.  d % 8 == 0,
  * T d <= 2^32, x / out 16-byte aligned. */
 int mmf_w2v_mask_drop(const void* x_bf16, const float* embed, const int* starts, void* out_bf16, int64_t items, int T, int d, int S_max,
@@ -928,13 +928,13 @@ int mmf_deberta_attn_bwd_pos_drop(const void* qkv_bf16, const void* posq_bf16, c
                                   float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale,
                                   float* dposq, float* dposk, int ld_dpos, void* workspace, size_t workspace_bytes, float p,
                                   const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
-/* Hidden dropout over `items` items of per_item elements each, one pass: element e of item g is kept where the hash of sub-stream
- * item0 + g at index e passes.  bf16 (is_f32 0): out = bf16(fma(y, c, resid)) where kept, resid where dropped: one f32 multiply-add,
+/* Hidden dropout over `items` items of per_item elements each, one pass (csrc/elementwise.hip; no model's own: Wav2Vec2's hidden
+ * sites take it too, mmfusion/wav2vec2.py): element e of item g is kept where the hash of sub-stream item0 + g at index e passes.  bf16 (is_f32 0): out = bf16(fma(y, c, resid)) where kept, resid where dropped: one f32 multiply-add,
  * one rounding; resid_bf16 NULL: 0 (the plain dropout and, on a gradient, its backward).  f32 (is_f32 1, resid_bf16 NULL): out =
  * y c where kept, 0 where dropped.  out may be y or resid.  A threshold of 0 copies (c = 1, everything kept) and still needs
  * rng_state.  per_item % 8 == 0, per_item <= 2^31, items < 2^31 (else MMF_E_UNSUPPORTED); y / resid / out 16-byte aligned. */
-int mmf_deberta_dropout(const void* y, const void* resid_bf16, void* out, int is_f32, int64_t items, int64_t per_item, float p,
-                        const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
+int mmf_hidden_dropout(const void* y, const void* resid_bf16, void* out, int is_f32, int64_t items, int64_t per_item, float p,
+                       const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream);
 /* Backward of mmf_deberta_embed on the embeds route: d_embeds (rows, d) f32 = mask[row] * the LayerNorm input gradient of
  * dout_bf16 (rows, d), the gradient of the kernel's bf16 output.  The row statistics are recomputed in f32 from embeds as the
  * forward computes them; rows with mask 0 are exactly 0.  mmf_deberta_embed's limits on d; embeds / gamma / d_embeds 16-byte

@@ -64,19 +64,12 @@ int validate_keyed(const char* who, const mmf_attn_problem* p, int n, float drop
   return MMF_OK;
 }
 
-// what the dropout form of the delta pre-pass takes beside the plain one's arguments
-struct DeltaDrop {
-  const unsigned long long* state;
-  unsigned site, thresh, stream_base;
-  float inv_keep;
-};
-
 // delta[b][h][i] = sum_j p_ij dp_ij in f32, p_ij = exp(scale q_i . k_j - LSE_i) and dp_ij = dO_i . v_j from the bf16 operands: the
 // softmax backward's row term as the definition has it.  (The backward kernels' own delta = dO . O reads the bf16 O, so a row of
 // dS sums to dO . (O - bf16(O)) instead of zero: an absolute residue that gradients much smaller than |dO| |O| do not cover.)
 // One thread per query row with q and dO in registers; the keys and values of 32 rows at a time in LDS, read as broadcasts.
-// Drop = one DeltaDrop (the dropout form: delta_i = sum_j p_ij w_ij dp_ij with w = keep c drawn as the forward drew it, stream
-// stream_base + b*H + h, index i Tk + j; p from the undropped LSE) or nothing: the plain instantiation keeps its argument block.
+// Drop = one MmfItemDrop, item0 carrying the stream base (the dropout form: delta_i = sum_j p_ij w_ij dp_ij with w = keep c drawn as the forward drew it, stream
+// item0 + b*H + h, index i Tk + j; p from the undropped LSE) or nothing: the plain instantiation keeps its argument block.
 constexpr int DELTA_THREADS = 256, DELTA_KEYS = 32;
 template <int DH, typename... Drop>
 __global__ __launch_bounds__(DELTA_THREADS)
@@ -107,8 +100,8 @@ void attn_delta_kernel(const mmf_attn_problem P, float scale, const Drop... dr) 
   unsigned dkey = 0u, dthresh = 0u;
   float dinv = 1.f;
   if constexpr (DROP) {
-    const DeltaDrop d = (dr, ...);
-    dkey = mmf_rng_key(*d.state, d.site, d.stream_base + (unsigned)(b * P.H + h));
+    const MmfItemDrop d = (dr, ...);
+    dkey = mmf_rng_key(*d.state, d.site, d.item0 + (unsigned)(b * P.H + h));
     dthresh = d.thresh;
     dinv = d.inv_keep;
   }
@@ -232,7 +225,7 @@ extern "C" int mmf_attn_bwd_grouped_pooled(const mmf_attn_problem* problems, int
 }
 
 namespace {
-int delta_launch(const char* fn, const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, const DeltaDrop* dr, void* stream) {
+int delta_launch(const char* fn, const mmf_attn_problem* problems, int num_problems, int head_dim, float scale, const MmfItemDrop* dr, void* stream) {
   if (int rc = validate(fn, problems, num_problems, head_dim, false)) return rc;
   for (int i = 0; i < num_problems; ++i) {
     if (!problems[i].dO || !problems[i].delta) MMF_FAIL(MMF_E_SHAPE, "%s[%d]: null gradient operand", fn, i);
@@ -244,10 +237,10 @@ int delta_launch(const char* fn, const mmf_attn_problem* problems, int num_probl
     const mmf_attn_problem& p = problems[i];
     const dim3 grid((p.Tq + DELTA_THREADS - 1) / DELTA_THREADS, p.H, p.B);
     if (dr) {
-      DeltaDrop d = *dr;
-      d.stream_base += (unsigned)i * 4096u;
-      if (head_dim == 96) hipLaunchKernelGGL((attn_delta_kernel<96, DeltaDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
-      else                hipLaunchKernelGGL((attn_delta_kernel<64, DeltaDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
+      MmfItemDrop d = *dr;
+      d.item0 += (unsigned)i * 4096u;
+      if (head_dim == 96) hipLaunchKernelGGL((attn_delta_kernel<96, MmfItemDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
+      else                hipLaunchKernelGGL((attn_delta_kernel<64, MmfItemDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
     } else {
       if (head_dim == 96) hipLaunchKernelGGL(attn_delta_kernel<96>, grid, dim3(DELTA_THREADS), 0, s, p, scale);
       else                hipLaunchKernelGGL(attn_delta_kernel<64>, grid, dim3(DELTA_THREADS), 0, s, p, scale);
@@ -278,8 +271,7 @@ extern "C" int mmf_attn_delta_f32_keyed(const mmf_attn_problem* problems, int nu
   if (int rc = validate_keyed(fn, problems, num_problems, dropout_p, rng_state, stream_base)) return rc;
   const unsigned thresh = (dropout_p > 0.f && rng_state) ? mmf_drop_thresh(dropout_p) : 0u;
   if (thresh == 0u) return delta_launch(fn, problems, num_problems, head_dim, scale, nullptr, stream);
-  const DeltaDrop d = {reinterpret_cast<const unsigned long long*>(rng_state), site, thresh, stream_base,
-                       1.f / (1.f - (float)thresh * (1.f / 4294967296.f))};
+  const MmfItemDrop d = {reinterpret_cast<const unsigned long long*>(rng_state), site, thresh, stream_base, mmf_inv_keep(thresh)};
   return delta_launch(fn, problems, num_problems, head_dim, scale, &d, stream);
 }
 

@@ -210,7 +210,7 @@ int fill_args2(AttnArgs2& a, const mmf_attn_problem* problems, int n, float scal
                uint32_t site, bool by_keys, bool balance, uint32_t stream_base = 0u) {
   a.nprob = n; a.scale = scale; a.stream_base = stream_base;
   a.drop_thresh = (drop_p > 0.f && rng_state) ? mmf_drop_thresh(drop_p) : 0u;
-  a.inv_keep = a.drop_thresh ? 1.f / (1.f - (float)a.drop_thresh * (1.f / 4294967296.f)) : 1.f;
+  a.inv_keep = mmf_inv_keep(a.drop_thresh);
   a.site = site;
   a.rng_state = reinterpret_cast<const unsigned long long*>(rng_state);
   int order[MMF_ATTN_MAX_PROBLEMS];

@@ -11,8 +11,8 @@
 //           column sums added in a fixed order), and the scatter-add of gradient rows into the word-embedding table's gradient
 //           (the first occurrence of a table row owns it): no atomics in either.
 //   training-mode dropout (HuggingFace's model in train()): a DROP template flag of the attention forward and of both backward passes
-//           (the probabilities are dropped in front of the product with V; the mask is drawn again, never stored), and one
-//           streaming kernel for the hidden sites: dropout (+ residual) in one pass.  DbDrop, ahead of the forward kernel.
+//           (the probabilities are dropped in front of the product with V; the mask is drawn again, never stored): db_drop_key /
+//           db_drop_w, ahead of the forward kernel.  The hidden sites' streaming kernel is mmf_hidden_dropout (elementwise.hip).
 // What the forward and the backward must agree on is stated once, as file-local __device__ functions that take operands and
 // never the name of their caller: the score tile (db_idx / db_fill_idx, db_chunks, db_pos_rows, db_frag, db_score; ahead of the
 // forward kernel) and the embedding LayerNorm's row statistics (db_row_stats).  The backward's P is the forward's P because both
@@ -182,24 +182,20 @@ __device__ __forceinline__ float db_score(float s, const int* __restrict__ sIdx,
 // Training-mode dropout of the probabilities (HuggingFace: softmax -> dropout -> @ V).  The mask is a function of the element and
 // never of the launch: sub-stream (item0 + item) H + h of (state, site), element i T + j for query i and key j (below 2^20), so a
 // chunk that starts at item0 draws what the whole batch would, and the backward's two passes, whichever token is "own", draw the
-// forward's bit again.  thresh != 0 in every DROP instantiation (the entry points take the plain kernels otherwise).
-struct DbDrop {
-  const unsigned long long* state;                             // the device-resident 64-bit RNG state
-  unsigned site, thresh, item0;
-  float inv_keep;                                              // c = 1 / (1 - p), p quantised to 2^-32
-};
+// forward's bit again.  thresh != 0 in every DROP instantiation (the entry points take the plain kernels otherwise).  The arguments
+// are one MmfItemDrop (mmf_internal.h), filled and checked by mmf_item_drop_fill.
 
-// A DROP kernel takes one DbDrop behind its other arguments and a plain one takes nothing there (an empty pack), so the plain
+// A DROP kernel takes one MmfItemDrop behind its other arguments and a plain one takes nothing there (an empty pack), so the plain
 // instantiations keep the argument block, and with it the device code, they had before there was a DROP form
-__device__ __forceinline__ DbDrop db_drop_of() { return DbDrop{nullptr, 0u, 0u, 0u, 1.0f}; }
-__device__ __forceinline__ DbDrop db_drop_of(const DbDrop& dr) { return dr; }
+__device__ __forceinline__ MmfItemDrop db_drop_of() { return MmfItemDrop{nullptr, 0u, 0u, 0u, 1.0f}; }
+__device__ __forceinline__ MmfItemDrop db_drop_of(const MmfItemDrop& dr) { return dr; }
 
-__device__ __forceinline__ unsigned db_drop_key(const DbDrop& dr, int item, int H, int h) {
+__device__ __forceinline__ unsigned db_drop_key(const MmfItemDrop& dr, int item, int H, int h) {
   return mmf_rng_key(*dr.state, dr.site, (dr.item0 + (unsigned)item) * (unsigned)H + (unsigned)h);
 }
 
 // the factor of pair (query i, key j): c where it is kept, 0 where it is dropped
-__device__ __forceinline__ float db_drop_w(const DbDrop& dr, unsigned key, int i, int j, int T) {
+__device__ __forceinline__ float db_drop_w(const MmfItemDrop& dr, unsigned key, int i, int j, int T) {
   return mmf_keep(key, (unsigned)i * (unsigned)T + (unsigned)j, dr.thresh) ? dr.inv_keep : 0.0f;
 }
 
@@ -211,8 +207,8 @@ void deberta_attn_fwd_kernel(const unsigned short* __restrict__ qkv, const unsig
                              const unsigned short* __restrict__ posk, int ld_pos, const int* __restrict__ idx,
                              const void* __restrict__ mask, int mask_kind, unsigned short* __restrict__ out,
                              float* __restrict__ lse, int H, int T, int S2 /* 2 S */, float inv_scale, const Drop... drop) {
-  static_assert(sizeof...(Drop) == (DROP ? 1 : 0), "a DROP kernel takes one DbDrop, a plain one none");
-  const DbDrop dr = db_drop_of(drop...);
+  static_assert(sizeof...(Drop) == (DROP ? 1 : 0), "a DROP kernel takes one MmfItemDrop, a plain one none");
+  const MmfItemDrop dr = db_drop_of(drop...);
   __shared__ __attribute__((aligned(16))) unsigned short sK[DB_BK * DB_KLD];
   __shared__ __attribute__((aligned(16))) unsigned short sVt[DB_DH * DB_VLD];
   __shared__ float sC[4 * 16 * DB_CLD];
@@ -605,7 +601,7 @@ constexpr int DB_TLD = 104, DB_TROWS = 96;
 constexpr int DB_ALD = 64;                                   // sA: 96 window rows x 64 own tokens bf16, 8-token groups XOR-swizzled by row
 
 //
-// DROP (the forward dropped the probabilities, DbDrop above): with w_ij = keep_ij c, dP_ij = w_ij (dO_i . V_j) and the dV product
+// DROP (the forward dropped the probabilities, db_drop_w above): with w_ij = keep_ij c, dP_ij = w_ij (dO_i . V_j) and the dV product
 // takes w_ij P_ij; dS = P (dP - delta) / scale as without, delta_i = dO_i . O_i still being the row sum of P dP because O is the
 // dropped product.  The bucket sums and the table gradients come from this dS with no further change.
 template <bool KPASS, bool POS, bool DROP, typename... Drop>
@@ -616,8 +612,8 @@ void deberta_attn_bwd_kernel(const unsigned short* __restrict__ qkv, const unsig
                              const unsigned short* __restrict__ dout, const float* __restrict__ delta,
                              unsigned short* __restrict__ dqkv, float* part /* POS: this pass's partial tables */,
                              int H, int T, int S2 /* 2 S */, float inv_scale, const Drop... drop) {
-  static_assert(sizeof...(Drop) == (DROP ? 1 : 0), "a DROP kernel takes one DbDrop, a plain one none");
-  const DbDrop dr = db_drop_of(drop...);
+  static_assert(sizeof...(Drop) == (DROP ? 1 : 0), "a DROP kernel takes one MmfItemDrop, a plain one none");
+  const MmfItemDrop dr = db_drop_of(drop...);
   static_assert(DB_TROWS * DB_ALD * 2 <= DB_BK * DB_PLD * 4, "sA must fit T2's buffer");
   __shared__ __attribute__((aligned(16))) unsigned short sO[DB_BK * DB_KLD];          // other rows: K | Q
   __shared__ __attribute__((aligned(16))) unsigned short sOt[DB_DH * DB_VLD];         // their transpose, db_slot order
@@ -899,66 +895,6 @@ void deberta_pos_reduce_kernel(const float* __restrict__ part, const int* __rest
   *dst += sum;
 }
 
-// ---- hidden dropout ---------------------------------------------------------------------------------------------
-// out = keep ? y c : 0 (+ resid) over `items` items of `per` elements each, one pass: the mask of element e of item g is drawn from
-// sub-stream item0 + g of (state, site) at index e, so it does not depend on how the items are cut into launches.  bf16 (F32 false):
-// eight elements per lane and access, the sum formed as one f32 multiply-add and rounded once; resid may be NULL.  f32 (F32 true,
-// the gradient of an f32 buffer): the product alone.  blockIdx.y walks the items, blockIdx.x the item's 8-element groups.
-template <bool F32>
-__global__ __launch_bounds__(DB_THREADS)
-void deberta_dropout_kernel(const void* y_, const unsigned short* resid, void* out_ /* may be y_ or resid */, unsigned items,
-                            unsigned per8 /* per / 8 */, const DbDrop dr) {
-  const unsigned long long state = *dr.state;
-  for (unsigned g = blockIdx.y; g < items; g += gridDim.y) {
-    const unsigned key = mmf_rng_key(state, dr.site, dr.item0 + g);
-    for (unsigned v = blockIdx.x * DB_THREADS + threadIdx.x; v < per8; v += gridDim.x * DB_THREADS) {
-      const size_t at = ((size_t)g * per8 + v) * 8;
-      bool keep[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) keep[e] = mmf_keep(key, v * 8u + (unsigned)e, dr.thresh);
-      const float c = dr.inv_keep;
-      if (F32) {
-        const float* y = static_cast<const float*>(y_) + at;
-        float* out = static_cast<float*>(out_) + at;
-        const f32x4_t a = *reinterpret_cast<const f32x4_t*>(y), b = *reinterpret_cast<const f32x4_t*>(y + 4);
-        f32x4_t oa, ob;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { oa[e] = keep[e] ? a[e] * c : 0.0f; ob[e] = keep[4 + e] ? b[e] * c : 0.0f; }
-        *reinterpret_cast<f32x4_t*>(out) = oa;
-        *reinterpret_cast<f32x4_t*>(out + 4) = ob;
-      } else {
-        float f[8], r[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(y_) + at), f);
-        if (resid) {
-          unpack8(*reinterpret_cast<const u32x4_t*>(resid + at), r);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) r[e] = 0.0f;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = keep[e] ? __fmaf_rn(f[e], c, r[e]) : r[e];
-        *reinterpret_cast<u32x4_t*>(static_cast<unsigned short*>(out_) + at) = pack8(f);
-      }
-    }
-  }
-}
-
-// the dropout arguments the new entries share -> dr.  p in [0, 1), quantised as mmf_dropout quantises it; a threshold of 0 (p = 0, or
-// below 2^-32) leaves dr->thresh 0: the caller then takes its plain kernels, and state may be NULL
-int db_drop_check(const char* fn, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, DbDrop* dr) {
-  if (!(p >= 0.0f) || p >= 1.0f) MMF_FAIL(MMF_E_SHAPE, "%s: p=%g outside [0, 1)", fn, (double)p);
-  if (item0 < 0) MMF_FAIL(MMF_E_SHAPE, "%s: item0=%lld is negative", fn, (long long)item0);
-  const unsigned thresh = mmf_drop_thresh(p);
-  if (thresh != 0u && !rng_state) MMF_FAIL(MMF_E_SHAPE, "%s: null rng_state with p=%g", fn, (double)p);
-  if (reinterpret_cast<uintptr_t>(rng_state) & 7u) MMF_FAIL(MMF_E_ALIGN, "%s: rng_state must be 8-byte aligned", fn);
-  dr->state = reinterpret_cast<const unsigned long long*>(rng_state);
-  dr->site = site;
-  dr->thresh = thresh;
-  dr->item0 = (unsigned)item0;                                   // the sub-stream is a 32-bit value: item0 + item wraps as the hash's input does
-  dr->inv_keep = thresh ? 1.0f / (1.0f - (float)thresh * (1.0f / 4294967296.0f)) : 1.0f;
-  return MMF_OK;
-}
-
 int db_mask_check(const char* fn, const void* mask, int mask_kind) {
   if (mask_kind < 0 || mask_kind > 2 || (mask_kind == 0) != (mask == nullptr))
     MMF_FAIL(MMF_E_SHAPE, "%s: mask_kind=%d (0 none, 1 f32, 2 u8) does not match the mask pointer", fn, mask_kind);
@@ -1052,8 +988,8 @@ extern "C" int mmf_deberta_attn_fwd_drop(const void* qkv_bf16, const void* posq_
                                          int head_dim, float scale, float p, const uint64_t* rng_state, uint32_t site, int64_t item0,
                                          void* stream) {
   const char* fn = "mmf_deberta_attn_fwd_drop";
-  DbDrop dr;
-  if (int rc = db_drop_check(fn, p, rng_state, site, item0, &dr)) return rc;
+  MmfItemDrop dr;
+  if (int rc = mmf_item_drop_fill(fn, p, rng_state, site, item0, &dr)) return rc;
   if (int rc = db_attn_check(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, n, H, T, S, head_dim, scale)) return rc;
   if (reinterpret_cast<uintptr_t>(lse) & 3u) MMF_FAIL(MMF_E_ALIGN, "%s: lse must be 4-byte aligned", fn);
 #define DB_FWD(LSE, DROP, ...) db_attn_fwd_launch<LSE, DROP>(qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, n, H, T, S, \
@@ -1141,8 +1077,8 @@ extern "C" int mmf_deberta_attn_bwd_drop(const void* qkv_bf16, const void* posq_
                                          float* delta_ws, void* dqkv_bf16, int n, int H, int T, int S, int head_dim, float scale,
                                          float p, const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
   const char* fn = "mmf_deberta_attn_bwd_drop";
-  DbDrop dr;
-  if (int rc = db_drop_check(fn, p, rng_state, site, item0, &dr)) return rc;
+  MmfItemDrop dr;
+  if (int rc = mmf_item_drop_fill(fn, p, rng_state, site, item0, &dr)) return rc;
   if (dr.thresh == 0u)
     return db_attn_bwd<false, false>(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, dout_bf16, delta_ws, dqkv_bf16,
                                      n, H, T, S, head_dim, scale, nullptr, nullptr, 0, nullptr, 0, stream);
@@ -1156,34 +1092,13 @@ extern "C" int mmf_deberta_attn_bwd_pos_drop(const void* qkv_bf16, const void* p
                                              float* dposq, float* dposk, int ld_dpos, void* workspace, size_t workspace_bytes, float p,
                                              const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
   const char* fn = "mmf_deberta_attn_bwd_pos_drop";
-  DbDrop dr;
-  if (int rc = db_drop_check(fn, p, rng_state, site, item0, &dr)) return rc;
+  MmfItemDrop dr;
+  if (int rc = mmf_item_drop_fill(fn, p, rng_state, site, item0, &dr)) return rc;
   if (dr.thresh == 0u)
     return db_attn_bwd<true, false>(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, dout_bf16, delta_ws, dqkv_bf16,
                                     n, H, T, S, head_dim, scale, dposq, dposk, ld_dpos, workspace, workspace_bytes, stream);
   return db_attn_bwd<true, true>(fn, qkv_bf16, posq_bf16, posk_bf16, ld_pos, idx, mask, mask_kind, out_bf16, lse, dout_bf16, delta_ws, dqkv_bf16,
                                  n, H, T, S, head_dim, scale, dposq, dposk, ld_dpos, workspace, workspace_bytes, stream, dr);
-}
-
-extern "C" int mmf_deberta_dropout(const void* y, const void* resid_bf16, void* out, int is_f32, int64_t items, int64_t per_item, float p,
-                                   const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
-  const char* fn = "mmf_deberta_dropout";
-  DbDrop dr;
-  if (int rc = db_drop_check(fn, p, rng_state, site, item0, &dr)) return rc;
-  if (!y || !out || items <= 0 || per_item <= 0 || (is_f32 && resid_bf16))
-    MMF_FAIL(MMF_E_SHAPE, "%s: null operand, items=%lld per_item=%lld, or a residual with f32 values", fn, (long long)items, (long long)per_item);
-  if (!rng_state) MMF_FAIL(MMF_E_SHAPE, "%s: null rng_state", fn);
-  if ((per_item & 7) || per_item > ((int64_t)1 << 31) || items > ((int64_t)1 << 31) - 1)
-    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: per_item=%lld (a multiple of 8, at most 2^31), items=%lld (below 2^31)", fn, (long long)per_item, (long long)items);
-  if (!mmf_aligned16(y) || !mmf_aligned16(out) || !mmf_aligned16(resid_bf16)) MMF_FAIL(MMF_E_ALIGN, "%s: y / resid / out must be 16-byte aligned", fn);
-  const unsigned per8 = (unsigned)(per_item >> 3);
-  const dim3 grid((unsigned)mmf_stream_grid(per8, DB_THREADS), (unsigned)(items < 65535 ? items : 65535));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (is_f32) hipLaunchKernelGGL(deberta_dropout_kernel<true>, grid, dim3(DB_THREADS), 0, s, y, nullptr, out, (unsigned)items, per8, dr);
-  else hipLaunchKernelGGL(deberta_dropout_kernel<false>, grid, dim3(DB_THREADS), 0, s, y, static_cast<const unsigned short*>(resid_bf16), out,
-                          (unsigned)items, per8, dr);
-  MMF_CHECK_LAUNCH(fn);
-  return MMF_OK;
 }
 
 extern "C" int mmf_deberta_embed_bwd(const float* embeds, const float* gamma, float eps, const void* mask, int mask_kind,

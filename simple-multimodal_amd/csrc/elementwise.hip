@@ -1,6 +1,6 @@
 // HBM-bound streaming helpers of the fusion path: casts, 3-way residual sum
 // (models/fusion_layers.py:156-158), mean over T (:166-168) and its backward, column sums (bias
-// gradients), relu backward.  All use 16-byte accesses per lane and grid-stride loops on mmf_stream_grid's
+// gradients), relu backward, dropout (mmf_dropout, and the backbones' keyed mmf_hidden_dropout).  All use 16-byte accesses per lane and grid-stride loops on mmf_stream_grid's
 // grid (mmf_internal.h).  addn and the two meanpools keep the loop of the single and the grouped kernel in one
 // *_body function: the two kernels hand it their own operands and the workgroup's place (blk of nblk) in its launch or problem.
 #include "mmf_internal.h"
@@ -176,6 +176,50 @@ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, unsig
     } else {
       const float v = bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(x)[i]);
       reinterpret_cast<unsigned short*>(y)[i] = keep ? f32_to_bf16_bits(v * scale) : (unsigned short)0;
+    }
+  }
+}
+
+// ---- hidden dropout (the backbones' training mode: DeBERTa's hidden sites, Wav2Vec2's) --------------------------------
+// out = keep ? y c : 0 (+ resid) over `items` items of `per` elements each, one pass: the mask of element e of item g is drawn from
+// sub-stream item0 + g of (state, site) at index e, so it does not depend on how the items are cut into launches.  bf16 (F32 false):
+// eight elements per lane and access, the sum formed as one f32 multiply-add and rounded once; resid may be NULL.  f32 (F32 true,
+// the gradient of an f32 buffer): the product alone.  blockIdx.y walks the items, blockIdx.x the item's 8-element groups.
+template <bool F32>
+__global__ __launch_bounds__(EW_THREADS)
+void hidden_dropout_kernel(const void* y_, const unsigned short* resid, void* out_ /* may be y_ or resid */, unsigned items,
+                           unsigned per8 /* per / 8 */, const MmfItemDrop dr) {
+  const unsigned long long state = *dr.state;
+  for (unsigned g = blockIdx.y; g < items; g += gridDim.y) {
+    const unsigned key = mmf_rng_key(state, dr.site, dr.item0 + g);
+    for (unsigned v = blockIdx.x * EW_THREADS + threadIdx.x; v < per8; v += gridDim.x * EW_THREADS) {
+      const size_t at = ((size_t)g * per8 + v) * 8;
+      bool keep[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) keep[e] = mmf_keep(key, v * 8u + (unsigned)e, dr.thresh);
+      const float c = dr.inv_keep;
+      if (F32) {
+        const float* y = static_cast<const float*>(y_) + at;
+        float* out = static_cast<float*>(out_) + at;
+        const f32x4_t a = *reinterpret_cast<const f32x4_t*>(y), b = *reinterpret_cast<const f32x4_t*>(y + 4);
+        f32x4_t oa, ob;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { oa[e] = keep[e] ? a[e] * c : 0.0f; ob[e] = keep[4 + e] ? b[e] * c : 0.0f; }
+        *reinterpret_cast<f32x4_t*>(out) = oa;
+        *reinterpret_cast<f32x4_t*>(out + 4) = ob;
+      } else {
+        float f[8], r[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(static_cast<const unsigned short*>(y_) + at), f);
+        if (resid) {
+          unpack8(*reinterpret_cast<const u32x4_t*>(resid + at), r);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) r[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = keep[e] ? __fmaf_rn(f[e], c, r[e]) : r[e];
+        *reinterpret_cast<u32x4_t*>(static_cast<unsigned short*>(out_) + at) = pack8(f);
+      }
     }
   }
 }
@@ -510,7 +554,7 @@ extern "C" int mmf_dropout(const void* x, void* y, int64_t n, int is_f32, float 
   if (n <= 0) return MMF_OK;
   if (!x || !y || !rng_state || !(p >= 0.f) || p >= 1.f) MMF_FAIL(MMF_E_SHAPE, "mmf_dropout: null pointer or p outside [0,1)");
   const unsigned thresh = mmf_drop_thresh(p);
-  const float scale = 1.f / (1.f - (float)thresh * (1.f / 4294967296.f));
+  const float scale = mmf_inv_keep(thresh);
   const unsigned long long* st = reinterpret_cast<const unsigned long long*>(rng_state);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (is_f32) hipLaunchKernelGGL(dropout_kernel<float>, dim3(mmf_stream_grid(n, EW_THREADS)), dim3(EW_THREADS), 0, s,
@@ -518,6 +562,27 @@ extern "C" int mmf_dropout(const void* x, void* y, int64_t n, int is_f32, float 
   else hipLaunchKernelGGL(dropout_kernel<unsigned short>, dim3(mmf_stream_grid(n, EW_THREADS)), dim3(EW_THREADS), 0, s,
                           static_cast<const unsigned short*>(x), static_cast<unsigned short*>(y), n, thresh, scale, st, site);
   MMF_CHECK_LAUNCH("mmf_dropout");
+  return MMF_OK;
+}
+
+extern "C" int mmf_hidden_dropout(const void* y, const void* resid_bf16, void* out, int is_f32, int64_t items, int64_t per_item, float p,
+                                  const uint64_t* rng_state, uint32_t site, int64_t item0, void* stream) {
+  const char* fn = "mmf_hidden_dropout";
+  MmfItemDrop dr;
+  if (int rc = mmf_item_drop_fill(fn, p, rng_state, site, item0, &dr)) return rc;
+  if (!y || !out || items <= 0 || per_item <= 0 || (is_f32 && resid_bf16))
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand, items=%lld per_item=%lld, or a residual with f32 values", fn, (long long)items, (long long)per_item);
+  if (!rng_state) MMF_FAIL(MMF_E_SHAPE, "%s: null rng_state", fn);
+  if ((per_item & 7) || per_item > ((int64_t)1 << 31) || items > ((int64_t)1 << 31) - 1)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: per_item=%lld (a multiple of 8, at most 2^31), items=%lld (below 2^31)", fn, (long long)per_item, (long long)items);
+  if (!mmf_aligned16(y) || !mmf_aligned16(out) || !mmf_aligned16(resid_bf16)) MMF_FAIL(MMF_E_ALIGN, "%s: y / resid / out must be 16-byte aligned", fn);
+  const unsigned per8 = (unsigned)(per_item >> 3);
+  const dim3 grid((unsigned)mmf_stream_grid(per8, EW_THREADS), (unsigned)(items < 65535 ? items : 65535));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (is_f32) hipLaunchKernelGGL(hidden_dropout_kernel<true>, grid, dim3(EW_THREADS), 0, s, y, nullptr, out, (unsigned)items, per8, dr);
+  else hipLaunchKernelGGL(hidden_dropout_kernel<false>, grid, dim3(EW_THREADS), 0, s, y, static_cast<const unsigned short*>(resid_bf16), out,
+                          (unsigned)items, per8, dr);
+  MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }
 

@@ -259,7 +259,7 @@ void gemm2_grouped_kernel(const GemmArgs args, const int total_tiles) {
   const unsigned short* __restrict__ aux = static_cast<const unsigned short*>(P.aux);
   const bool do_drop = epi & MMF_EPI_DROPOUT;
   const unsigned drop_key = do_drop ? mmf_rng_key(*args.rng_state, args.site, (unsigned)pi) : 0u;
-  const float drop_scale = do_drop ? 1.f / (1.f - (float)args.drop_thresh * (1.f / 4294967296.f)) : 1.f;
+  const float drop_scale = do_drop ? mmf_inv_keep(args.drop_thresh) : 1.f;
   const float alpha = args.alpha;
   auto finish = [&](f32x4_t v, int m, int n) -> f32x4_t {  // bias -> relu -> dropout -> mask -> alpha -> residual
     if (epi & MMF_EPI_BIAS) v += *reinterpret_cast<const f32x4_t*>(P.bias + n);

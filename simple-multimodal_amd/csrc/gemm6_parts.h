@@ -181,7 +181,7 @@ __device__ __forceinline__ void tile_epilogue_mode(const GemmArgs& args, const m
   const unsigned short* __restrict__ aux = static_cast<const unsigned short*>(P.aux);
   const bool do_drop = MODE == 3 && (epi & MMF_EPI_DROPOUT);
   const unsigned drop_key = do_drop ? mmf_rng_key(*args.rng_state, args.site, (unsigned)pi) : 0u;
-  const float drop_scale = do_drop ? 1.f / (1.f - (float)args.drop_thresh * (1.f / 4294967296.f)) : 1.f;
+  const float drop_scale = do_drop ? mmf_inv_keep(args.drop_thresh) : 1.f;
   const float alpha = MODE == 3 ? args.alpha : 1.f;
   const bool use_aux = epi & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX);
   const bool use_old = OUT_F32 && (epi & MMF_EPI_ACCUM);

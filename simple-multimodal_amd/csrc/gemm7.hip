@@ -123,7 +123,7 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
   static_assert(!(AUX && (EMIT_BITS || MASK_BITS)) && !(EMIT_BITS && MASK_BITS), "aux is one of: a bf16 tile, bits written, bits read");
   // dropout on the (activated) outputs, the mask of gemm6's epilogue: element m * N + n of the caller's problem `orig[pi]`
   const unsigned drop_key = DROP ? mmf_rng_key(*args.rng_state, args.site, (unsigned)args.orig[pi]) : 0u;
-  const float drop_scale = DROP ? 1.f / (1.f - (float)args.drop_thresh * (1.f / 4294967296.f)) : 1.f;
+  const float drop_scale = DROP ? mmf_inv_keep(args.drop_thresh) : 1.f;
   const float alpha = (CT & (MMF_EPI_MASK_AUX | MMF_EPI_MASK_BITS)) ? args.alpha : 1.f;            // 1 / (1 - p) of a dropout backward rides on the ReLU mask
   const int r = lane & 31, h = lane >> 5, q = lane >> 4, cq = lane & 15;
   // region offsets: accumulator layout (8 bytes at chunk c = 4 tn + g, half h, of row r), whole-row layout (16-byte chunk cq of row 4 it + q)

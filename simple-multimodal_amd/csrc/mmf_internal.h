@@ -138,14 +138,23 @@ static inline unsigned mmf_drop_thresh(float p) {          // host: p in [0, 1)
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
 }
-// What a streaming kernel with per-item keyed dropout takes (the Wav2Vec2 regularisers of vit.hip / wav2vec2.hip): element e of item g is
-// mmf_keep(mmf_rng_key(*state, site, item0 + g), e, thresh), kept values are multiplied by inv_keep = 1 / (1 - p), p quantised to 2^-32
+// what a kept value is multiplied by: 1 / (1 - p) with p as mmf_drop_thresh quantised it.  thresh == 0 (no dropout) gives 1.f by the
+// arithmetic itself (1 / (1 - 0)), so there is no branch on it: the GEMM epilogues call this under their own DROP guard and keep
+// the instructions they had.  The host restatements (tests/attn_ref.py: inv_keep_of) form the same f32 operations in this order
+__host__ __device__ __forceinline__ float mmf_inv_keep(unsigned thresh) {
+  return 1.f / (1.f - (float)thresh * (1.f / 4294967296.f));
+}
+// What a kernel with keyed dropout takes by value (hidden dropout in elementwise.hip, the Wav2Vec2 regularisers of vit.hip / wav2vec2.hip,
+// DeBERTa's attention in deberta.hip, the delta pre-pass of attention.hip): element e of item g is
+// mmf_keep(mmf_rng_key(*state, site, item0 + g), e, thresh), kept values are multiplied by inv_keep.  The attention kernels key a (item,
+// head) pair: DeBERTa's sub-stream is (item0 + item) H + h, the delta pre-pass takes its stream base in item0 (sub-stream item0 + b H + h)
 struct MmfItemDrop {
-  const unsigned long long* state;
-  unsigned site, thresh, item0;
-  float inv_keep;
+  const unsigned long long* state;                             // the device-resident 64-bit RNG state
+  unsigned site, thresh, item0;                                // the sub-stream is a 32-bit value: item0 + item wraps as the hash's input does
+  float inv_keep;                                              // mmf_inv_keep(thresh)
 };
-// host: the checks those entries share -> dr.  thresh == 0 (p = 0 or below 2^-32): no dropout, state may be NULL
+// host: the checks the entries with (p, rng_state, site, item0) share -> dr.  thresh == 0 (p = 0 or below 2^-32): no dropout, state may
+// be NULL (an entry with a plain kernel form then takes it)
 static inline int mmf_item_drop_fill(const char* fn, float p, const uint64_t* rng_state, uint32_t site, int64_t item0, MmfItemDrop* dr) {
   if (!(p >= 0.0f) || p >= 1.0f) MMF_FAIL(MMF_E_SHAPE, "%s: p=%g outside [0, 1)", fn, (double)p);
   if (item0 < 0) MMF_FAIL(MMF_E_SHAPE, "%s: item0=%lld is negative", fn, (long long)item0);
@@ -156,7 +165,7 @@ static inline int mmf_item_drop_fill(const char* fn, float p, const uint64_t* rn
   dr->site = site;
   dr->thresh = thresh;
   dr->item0 = (unsigned)item0;
-  dr->inv_keep = thresh ? 1.0f / (1.0f - (float)thresh * (1.0f / 4294967296.0f)) : 1.0f;
+  dr->inv_keep = mmf_inv_keep(thresh);
   return MMF_OK;
 }
 

@@ -338,7 +338,7 @@ int fill_ex(const char* who, SkinnyArgs& a, const mmf_skinny_problem_ex* px, int
     if (!ex || !ex->rng_state || !(ex->dropout_p >= 0.f) || ex->dropout_p >= 1.f)
       MMF_FAIL(MMF_E_SHAPE, "%s: MMF_EPI_DROPOUT needs rng_state and 0 <= p < 1", who);
     a.drop_thresh = mmf_drop_thresh(ex->dropout_p);
-    a.drop_scale = 1.f / (1.f - (float)a.drop_thresh * (1.f / 4294967296.f));
+    a.drop_scale = mmf_inv_keep(a.drop_thresh);
   }
   for (int i = 0; i < n; ++i) {
     a.y2[i] = px ? px[i].Y2 : nullptr; a.ldy2[i] = px ? px[i].ldy2 : 0;

@@ -655,7 +655,7 @@ int fill_gat(Gat3Args& a, const mmf_gat3_params* p) {
     MMF_FAIL(MMF_E_SHAPE, "mmf_gat3_dense: dropout needs 0 <= p < 1 and an rng_state");
   a.B = p->B; a.H = p->heads; a.C = p->C; a.relu = p->relu; a.slope = p->negative_slope;
   a.drop_thresh = p->dropout_p > 0.f ? mmf_drop_thresh(p->dropout_p) : 0u;
-  a.inv_keep = a.drop_thresh ? 1.f / (1.f - (float)a.drop_thresh * (1.f / 4294967296.f)) : 1.f;
+  a.inv_keep = mmf_inv_keep(a.drop_thresh);
   a.site = p->site;
   a.rng_state = reinterpret_cast<const unsigned long long*>(p->rng_state);
   return MMF_OK;

@@ -15,7 +15,7 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
       + bias, exact GELU            mmf_bias_gelu_bf16 (in place)        h
       fc2 + bias + resid            mmf_gemm_grouped NT, BIAS | ADD_AUX  h   -> out
     (both blocks end in ``_closing``: with a model's ``join`` hook the closing launch is BIAS only and ``join(role, y, resid)`` makes
-     the sum; DeBERTa's training-mode dropout, mmfusion/deberta.py.  Without one, the rows above.)
+     the sum; training-mode hidden dropout, ``_hidden_joins``.  Without one, the rows above.)
     _ln(src, dst)                   mmf_layernorm_fwd_grouped            src -> dst
     _widen(src, dst)                mmf_cast_bf16_to_f32                 src -> the f32 result
     _ln_bwd(...)                    mmf_layernorm_bwd_grouped            dy  -> dx (the input gradient; the backbones' backward)
@@ -59,6 +59,18 @@ layers marked trainable (``set_trainable_layers``: those layers' parameters then
 their gradients into the parameter arena), mmfusion/deberta.py, mmfusion/vit.py and mmfusion/wav2vec2.py.  bf16
 storage only: in the fp32 parity mode (``ops.fp32_mode()``) the forward raises instead of computing something else.
 Nothing synchronises with the host: a fixed-shape call can be captured by ``torch.cuda.graph``.
+
+Training-mode dropout (DeBERTa's dropout, Wav2Vec2's regularisers; each model's docstring has its table of sites).  A differentiable
+call in ``train()`` mode with a probability above 0 owns one ``_CallDropout``: it takes its sites from ``ops.next_site()`` in
+HuggingFace's call order, a model's leading sites and then four per layer, and keeps them for its backward.  Every mask is the counter
+hash of (``ops.rng_state()``, site, sub-stream, index) with sub-stream = the item's index in the WHOLE batch (attention: that times
+H plus the head) and index = the element's place within the item, never a function of the launch: a chunk that starts at item
+``n0`` passes ``n0`` as ``item0`` and draws what the whole batch would, so no result depends on ``chunk``.  Nothing is stored: the
+state is read where a launch is made (live, as ``ops._Dropout.backward`` does), the recomputed layer regenerates its masks and the
+backward's own kernels draw them again from the same (state, site, item0).  The hidden sites of a layer are ``_closing``'s ``join``
+hook (``_hidden_joins``: the closing launch is BIAS only, ``mmf_hidden_dropout`` forms bf16(fma(dense + bias, keep c, resid)); the
+gradient of a pre-LN sum reaches the dense branch through the same kernel and the residual branch as it is).  A call on its own (no
+root module's forward around it) starts a training forward itself, so successive calls draw new masks (``_own_training_forward``).
 """
 from __future__ import annotations
 
@@ -77,7 +89,7 @@ WsTable = List[Tuple[str, int, torch.dtype]]
 Attend = Callable[[torch.Tensor, torch.Tensor], None]          # (qkv rows, att rows): launches one chunk's attention
 AttnBwd = Callable[[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor], None]     # (qkv, att, datt, dqkv rows): its backward
 QkvWgrad = Callable[[torch.Tensor, torch.Tensor], None]        # (dqkv rows, the projection's input rows): the fused weight's gradient
-# What stands between a block's closing dense launch and its LayerNorm where a model has something there (DeBERTa's training-mode
+# What stands between a block's closing dense launch and its LayerNorm where a model has something there (training-mode hidden
 # dropout; absent: the residual add is the GEMM's epilogue).  Join(role, y, resid): role "o" / "fc2", y = dense + bias as bf16 -> the
 # pre-LN sum, in place.  JoinBwd(role, dy, out): the gradient dy of that sum -> out, the dense branch's share of it
 Join = Callable[[str, torch.Tensor, torch.Tensor], None]
@@ -85,6 +97,37 @@ JoinBwd = Callable[[str, torch.Tensor, torch.Tensor], None]
 # A model's own activation launches, (forward(h, bias, g), backward(dg, h, bias, dh)) with ``lib.bias_gelu_to`` / ``bias_gelu_bwd``'s
 # arguments (Wav2Vec2's training-mode activation dropout; absent: those two)
 Act = Tuple[Callable[[torch.Tensor, torch.Tensor, torch.Tensor], None], Callable[[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor], None]]
+
+
+def _check_probability(who: str, name: str, p, closed: bool = False) -> None:
+    """``p`` must be a number (no bool) in [0, 1), with ``closed`` in [0, 1]; the error names the call as ``who(name=p)``"""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= p <= 1.0 if closed else 0.0 <= p < 1.0):
+        raise ValueError(f"{who}({name}={p!r}): a probability in [0, 1{']' if closed else ')'}")
+
+
+class _CallDropout:
+    """The dropout of one differentiable training call (the module docstring has the keying): the hidden and the attention
+    probability and the call's sites, ``lead`` leading ones and then four per layer, taken from ``ops.next_site()`` in that order.  A
+    model's subclass names them in HuggingFace's call order and adds what else its call keeps."""
+
+    def __init__(self, p_h: float, p_a: float, lead: int, layers: int):
+        self.p_h, self.p_a = p_h, p_a
+        self.lead = tuple(ops.next_site() for _ in range(lead))
+        self.layers = [tuple(ops.next_site() for _ in range(4)) for _ in range(layers)]
+
+    @staticmethod
+    def key(p: float, site: int, item0: int) -> tuple:
+        """what a launch with keyed dropout takes (``lib._drop_args``); the state is read here, live: the backward draws the
+        forward's masks from the same state"""
+        return p, ops.rng_state(), site, item0
+
+    def hidden(self, site: int, item0: int) -> tuple:
+        return self.key(self.p_h, site, item0)
+
+    def join_sites(self, i: int) -> Tuple[int, int]:
+        """layer ``i``'s hidden sites behind its two closing launches (``FrozenBackbone._hidden_joins``); ``OUT`` / ``MLP``: the
+        subclass's places of them among the layer's four"""
+        return self.layers[i][self.OUT], self.layers[i][self.MLP]
 
 
 class BackboneOutput:
@@ -120,6 +163,30 @@ class FrozenBackbone(nn.Module):
         self._trainable = 0                            # a subclass's set_trainable_layers
         self._gws: Optional[dict] = None               # a backward's workspace (the subclass's _grad_table), from the first differentiable call
         self._slabs: Optional[torch.Tensor] = None     # _slab_buffer
+
+    # -- training-mode dropout ---------------------------------------------------------------------------
+    @staticmethod
+    def _own_training_forward() -> None:
+        """A differentiable training call that is about to take its sites: on its own it starts a training forward itself (new
+        masks, sites from 1); under a root module's forward it continues that forward's site numbering"""
+        if not ops.inside_root():
+            ops.begin_training_forward()
+
+    @staticmethod
+    def _hidden_joins(drop: Optional[_CallDropout], sites: Tuple[int, int], n: int, n0: int) -> tuple:
+        """(join, join_bwd) of a layer on a chunk of ``n`` items from item ``n0`` (``Join`` / ``JoinBwd`` above): hidden dropout at
+        ``sites`` = (the attention output's, the MLP output's), fused with the residual add, and its gradient form; (None, None)
+        without hidden dropout"""
+        if drop is None or drop.p_h <= 0.0:
+            return None, None
+        site = dict(zip(("o", "fc2"), sites))
+
+        def join(role: str, y: torch.Tensor, resid: torch.Tensor) -> None:
+            lib.hidden_dropout(y, y, n, drop.hidden(site[role], n0), resid=resid)
+
+        def join_bwd(role: str, dy: torch.Tensor, out: torch.Tensor) -> None:
+            lib.hidden_dropout(dy, out, n, drop.hidden(site[role], n0))
+        return join, join_bwd
 
     # -- fine-tuning the top layers ----------------------------------------------------------------------
     @staticmethod

@@ -92,21 +92,18 @@ Dropout.  HuggingFace's model in ``train()`` drops at five sites, and the refere
 (``hidden_dropout_prob`` / ``attention_probs_dropout_prob``, both 0 by default, or ``set_dropout``) and act only in a call that has
 ``self.training``, a probability above 0 and the differentiable route; every other call is the launch lists above, bit for bit.
 
-    1  embeddings                 mmf_deberta_dropout (in place)       x = dropout(LayerNorm(..) * mask)
-    2  relative embeddings        mmf_deberta_dropout, once per layer  rel_i = dropout_i(rel); posQ_i | posK_i from rel_i, every call
+    1  embeddings                 mmf_hidden_dropout (in place)        x = dropout(LayerNorm(..) * mask)
+    2  relative embeddings        mmf_hidden_dropout, once per layer   rel_i = dropout_i(rel); posQ_i | posK_i from rel_i, every call
     3  attention probabilities    mmf_deberta_attn_fwd_drop            softmax -> dropout -> @ V, inside the kernel
-    4  attention output           NT, BIAS; mmf_deberta_dropout        y = bf16(fma(dense + bias, keep c, x))
-    5  MLP output                 NT, BIAS; mmf_deberta_dropout        y = bf16(fma(dense + bias, keep c, ln))
+    4  attention output           NT, BIAS; mmf_hidden_dropout         y = bf16(fma(dense + bias, keep c, x))
+    5  MLP output                 NT, BIAS; mmf_hidden_dropout         y = bf16(fma(dense + bias, keep c, ln))
 
 Sites 1, 2, 4, 5 take ``hidden_dropout_prob``, site 3 ``attention_probs_dropout_prob``; a probability of 0 leaves its sites' launches
 as they are without dropout.  A call takes 1 + 4 L sites from ``ops.next_site()`` in that order (``_Drop``) and keeps them for its
-backward; masks are the counter hash of (``ops.rng_state()``, site, sub-stream, index) with sub-stream = the item's index in the
-batch (attention: that times H plus the head; ``rel_i``: 0) and index = the element's within the item, so no result depends on
-``chunk``, and the backward draws every mask again instead of storing it: the recomputed layer regenerates sites 3 - 5, the gradient
-of a pre-LN sum reaches the dense branch through ``mmf_deberta_dropout`` (the residual branch takes it as it is), the attention
+backward; the keying, and why no result depends on ``chunk``, is mmfusion/backbone.py's ("Training-mode dropout"; ``rel_i`` is one
+item, sub-stream 0).  The backward draws every mask again: the recomputed layer regenerates sites 3 - 5, the attention
 backward is ``mmf_deberta_attn_bwd_drop`` / ``_pos_drop``, ``dW_qkv[:2d] += bf16(dpos_i)^T rel_i`` with ``rel_i`` drawn again, and
 d rel = sum_i keep_i c (bf16(dpos_i) W_qk,i): one NN GEMM per layer into its own f32 slab, masked there, then ``mmf_sum_slabs_f32``.
-Called on its own (no root module's forward around it) such a call advances the RNG state itself, so successive calls draw new masks.
 """
 from __future__ import annotations
 
@@ -118,7 +115,7 @@ import torch
 
 from . import arena as _arena
 from . import lib, ops
-from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
+from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable, _CallDropout, _check_probability
 from .lib import EPI_ACCUM, EPI_BIAS, EPI_COLSUM_A, GEMM_NN, GEMM_NT, GEMM_TN
 
 # items per pass through the workspace.  NOT chosen by measurement yet: 16 items of 512 tokens give the layer GEMMs 8192 rows
@@ -186,23 +183,18 @@ class _WordEmbeddings:
             return torch.nn.functional.embedding(input_ids, self.weight)
 
 
-class _Drop:
-    """The dropout of one differentiable training call: the two probabilities and the call's sites, taken from ``ops.next_site()``
-    in HuggingFace's order (the embeddings, then per layer the relative embeddings, the attention probabilities, the attention
-    output, the MLP output).  The state is read where a launch is made (``ops.rng_state()``, live: the backward draws the
-    forward's masks from the same state, as ``ops._Dropout.backward`` does)."""
+class _Drop(_CallDropout):
+    """The dropout of one differentiable training call (mmfusion/backbone.py), its 1 + 4 L sites in HuggingFace's order: the
+    embeddings, then per layer the relative embeddings, the attention probabilities, the attention output, the MLP output."""
     REL, PROBS, OUT, MLP = range(4)
 
     def __init__(self, p_h: float, p_a: float, layers: int):
-        self.p_h, self.p_a = p_h, p_a
-        self.emb = ops.next_site()
-        self.layers = [tuple(ops.next_site() for _ in range(4)) for _ in range(layers)]
-
-    def hidden(self, site: int, item0: int) -> tuple:
-        return self.p_h, ops.rng_state(), site, item0
+        super().__init__(p_h, p_a, 1, layers)
+        (self.emb,) = self.lead
 
     def probs(self, i: int, item0: int) -> Optional[tuple]:
-        return (self.p_a, ops.rng_state(), self.layers[i][self.PROBS], item0) if self.p_a > 0.0 else None
+        """the attention's (p, state, site, item base): the kernel forms the stream id (item0 + item) H + head itself"""
+        return self.key(self.p_a, self.layers[i][self.PROBS], item0) if self.p_a > 0.0 else None
 
 
 class _Differentiable(torch.autograd.Function):
@@ -320,19 +312,15 @@ class NativeDeberta(FrozenBackbone):
         and something to train: ``set_trainable_layers`` or ``inputs_embeds.requires_grad``); ``eval()`` and ``no_grad`` calls are
         the inference launches whatever the values."""
         for name, p in (("hidden", hidden), ("attention", attention)):
-            if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p < 1.0:
-                raise ValueError(f"NativeDeberta: set_dropout({name}={p!r}): a probability in [0, 1)")
+            _check_probability("NativeDeberta: set_dropout", name, p)
         self.config.hidden_dropout_prob, self.config.attention_probs_dropout_prob = float(hidden), float(attention)
 
     def _drop_of_call(self) -> Optional[_Drop]:
-        """the dropout of the differentiable call that is about to run: None unless the module trains with a probability above 0.
-        A call on its own starts a training forward itself (new masks, sites from 1); under a root module's forward it continues
-        that forward's site numbering"""
+        """the dropout of the differentiable call that is about to run: None unless the module trains with a probability above 0"""
         c = self.config
         if not self.training or (c.hidden_dropout_prob <= 0.0 and c.attention_probs_dropout_prob <= 0.0):
             return None
-        if not ops.inside_root():
-            ops.begin_training_forward()
+        self._own_training_forward()
         return _Drop(c.hidden_dropout_prob, c.attention_probs_dropout_prob, c.num_hidden_layers)
 
     # -- fine-tuning -------------------------------------------------------------------------------------
@@ -451,7 +439,7 @@ class NativeDeberta(FrozenBackbone):
     def _rel_of(i: int, rel: torch.Tensor, drop: _Drop) -> torch.Tensor:
         """layer ``i``'s dropped relative embeddings (one item: sub-stream 0, index row * d + column), rounded once"""
         rel_i = torch.empty_like(rel)
-        lib.deberta_dropout(rel, rel_i, 1, drop.hidden(drop.layers[i][_Drop.REL], 0))
+        lib.hidden_dropout(rel, rel_i, 1, drop.hidden(drop.layers[i][_Drop.REL], 0))
         return rel_i
 
     # -- launches ---------------------------------------------------------------------------------------
@@ -465,22 +453,7 @@ class NativeDeberta(FrozenBackbone):
         def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
             lib.deberta_attn_fwd(qkv, pos[0], pos[1], idx, mask, att, n, c.num_attention_heads, T, c.position_buckets, scale, self.head_dim,
                                  drop=probs)
-        self._post_ln_layer(i, ws, n, T, attend, self._joins(i, n, n0, drop)[0])
-
-    @staticmethod
-    def _joins(i: int, n: int, n0: int, drop: Optional[_Drop]) -> tuple:
-        """(join, join_bwd) of layer ``i`` on a chunk of ``n`` items from item ``n0`` (mmfusion/backbone.py: ``Join``): the
-        attention output's and the MLP output's dropout, fused with the residual add; (None, None) without hidden dropout"""
-        if drop is None or drop.p_h <= 0.0:
-            return None, None
-        sites = {"o": drop.layers[i][_Drop.OUT], "fc2": drop.layers[i][_Drop.MLP]}
-
-        def join(role: str, y: torch.Tensor, resid: torch.Tensor) -> None:
-            lib.deberta_dropout(y, y, n, drop.hidden(sites[role], n0), resid=resid)
-
-        def join_bwd(role: str, dy: torch.Tensor, out: torch.Tensor) -> None:
-            lib.deberta_dropout(dy, out, n, drop.hidden(sites[role], n0))
-        return join, join_bwd
+        self._post_ln_layer(i, ws, n, T, attend, self._hidden_joins(drop, drop and drop.join_sites(i), n, n0)[0])
 
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None) -> BackboneOutput:
         c, who = self.config, "NativeDeberta"
@@ -533,7 +506,7 @@ class NativeDeberta(FrozenBackbone):
             else:
                 lib.deberta_embed(x, None, gamma, beta, c.layer_norm_eps, embeds=part, mask=m)
             if drop is not None and drop.p_h > 0.0:
-                lib.deberta_dropout(x, x, n, drop.hidden(drop.emb, n0))
+                lib.hidden_dropout(x, x, n, drop.hidden(drop.emb, n0))
             for i in range(c.num_hidden_layers):
                 if keep is not None and i >= first:
                     keep[i - first, n0 * T:(n0 + n) * T].copy_(x)
@@ -562,7 +535,7 @@ class NativeDeberta(FrozenBackbone):
                                          self._pos_workspace(g, n, T), *dims, drop=probs)
             else:
                 lib.deberta_attn_bwd(qkv, pos[0], pos[1], idx, mask, att, g["lse"], datt, g["delta"], dqkv, *dims, drop=probs)
-        join, join_bwd = self._joins(i, n, n0, drop)
+        join, join_bwd = self._hidden_joins(drop, drop and drop.join_sites(i), n, n0)
         # the plain Q/K/V weight gradient, the key bias's column sum included: db_k has a real position-to-content term here
         self._post_ln_layer_grad(i, ws, g, xin, n, T, attend, attn_bwd, (lambda dqkv, x: self._wgrad(dqkv, x, f"l{i}_qkv")) if train else None,
                                  below, join=join, join_bwd=join_bwd)
@@ -606,7 +579,7 @@ class NativeDeberta(FrozenBackbone):
                 self._layer_grad(i, ws, g, keep[i - first, rows], n, T, pos[i], idx, m, dpos[i - (L - k)] if i >= L - k else None,
                                  need_in or emb or i > first, drop, n0)
             if hidden and (need_in or emb):
-                lib.deberta_dropout(ga, ga, n, drop.hidden(drop.emb, n0))      # through the embedding output's dropout
+                lib.hidden_dropout(ga, ga, n, drop.hidden(drop.emb, n0))      # through the embedding output's dropout
             if emb:
                 # the embedding LayerNorm's parameters, and the word embeddings: the gathered rows' gradient (a buffer of the
                 # backward's), scattered into the table's; on the embeds route the rows' gradient is d inputs_embeds itself
@@ -646,7 +619,7 @@ class NativeDeberta(FrozenBackbone):
                     slabs = torch.empty((L, S2 * d), dtype=torch.float32, device=dev)
                     for i in range(L):
                         ops.gemm(GEMM_NN, dp16[i], self._w(f"l{i}_qkv_w")[:2 * d], slabs[i].view(S2, d))
-                        lib.deberta_dropout(slabs[i], slabs[i], 1, drop.hidden(drop.layers[i][_Drop.REL], 0))
+                        lib.hidden_dropout(slabs[i], slabs[i], 1, drop.hidden(drop.layers[i][_Drop.REL], 0))
                     for s0 in range(0, L, lib.SUM_SLABS_MAX):
                         lib.sum_slabs(slabs[s0:s0 + lib.SUM_SLABS_MAX], drel, s0 > 0)
                 else:

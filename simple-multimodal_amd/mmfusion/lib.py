@@ -45,7 +45,7 @@ SYMBOLS = (
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
     "mmf_deberta_embed_bwd_params_workspace_bytes", "mmf_deberta_embed_bwd_params", "mmf_embedding_scatter_add_f32",
-    "mmf_deberta_attn_fwd_drop", "mmf_deberta_attn_bwd_drop", "mmf_deberta_attn_bwd_pos_drop", "mmf_deberta_dropout",
+    "mmf_deberta_attn_fwd_drop", "mmf_deberta_attn_bwd_drop", "mmf_deberta_attn_bwd_pos_drop", "mmf_hidden_dropout",
     "mmf_video_prepare", "mmf_video_prepare_patches", "mmf_audio_resample", "mmf_audio_augment",
     "mmf_attn_fwd_grouped_keyed", "mmf_attn_delta_f32_keyed", "mmf_attn_bwd_grouped_delta_keyed", "mmf_bias_gelu_drop_bf16_to",
     "mmf_bias_gelu_drop_bwd_bf16", "mmf_w2v_mask_spans", "mmf_w2v_mask_drop", "mmf_w2v_mask_embed_grad",
@@ -263,7 +263,7 @@ def load() -> C.CDLL:
     lib.mmf_deberta_attn_bwd_drop.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32] + drop + [vp]
     lib.mmf_deberta_attn_bwd_pos_drop.argtypes = ([vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
                                                    vp, vp, i32, vp, C.c_size_t] + drop + [vp])
-    lib.mmf_deberta_dropout.argtypes = [vp, vp, vp, i32, i64, i64] + drop + [vp]
+    lib.mmf_hidden_dropout.argtypes = [vp, vp, vp, i32, i64, i64] + drop + [vp]
     keyed = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, C.c_uint32, vp]       # .., scale, p, rng_state, site, stream_base
     lib.mmf_attn_fwd_grouped_keyed.argtypes = keyed
     lib.mmf_attn_delta_f32_keyed.argtypes = keyed
@@ -417,9 +417,11 @@ def attn_bwd_grouped_exact_delta(problems: Sequence[AttnProblem], head_dim: int,
         check(load().mmf_attn_bwd_grouped_delta(arr, len(problems), head_dim, scale, stream_ptr()))
 
 
-def _keyed(who: str, drop) -> tuple:
-    """``drop`` = (p, state, site, stream_base) -> the trailing arguments of the ``_keyed`` attention entries (``state``: the device
-    int64 [1] RNG state)"""
+def _drop_args(who: str, drop) -> tuple:
+    """``drop`` = (p, state, site, base) -> the four trailing arguments of every entry point with keyed dropout: ``state`` the device
+    int64 [1] RNG state (``ops.rng_state()``).  The one difference between callers is ``base``: for the per-item kernels it is the
+    index in the whole batch of the call's first item (``item0``); for the grouped attention's ``_keyed`` entries it is the stream
+    base, in (item, head) pairs (Wav2Vec2 passes ``item0 * H`` there)"""
     import torch
     p, state, site, base = drop
     if state is not None and (not state.is_cuda or state.dtype != torch.int64 or state.numel() != 1):
@@ -433,7 +435,7 @@ def attn_fwd_grouped_keyed(problems: Sequence[AttnProblem], head_dim: int, scale
     arr = (AttnProblem * len(problems))(*problems)
     flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
     with _Timed(f"attn_fwd_kernel<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
-        check(load().mmf_attn_fwd_grouped_keyed(arr, len(problems), head_dim, scale, *_keyed("attn_fwd_grouped_keyed", drop), stream_ptr()))
+        check(load().mmf_attn_fwd_grouped_keyed(arr, len(problems), head_dim, scale, *_drop_args("attn_fwd_grouped_keyed", drop), stream_ptr()))
 
 
 def attn_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
@@ -442,7 +444,7 @@ def attn_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: floa
     shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
     flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
     with _Timed(f"attn_delta_kernel<{head_dim}>", flops, shapes):
-        check(load().mmf_attn_delta_f32_keyed(arr, len(problems), head_dim, scale, *_keyed("attn_delta_keyed", drop), stream_ptr()))
+        check(load().mmf_attn_delta_f32_keyed(arr, len(problems), head_dim, scale, *_drop_args("attn_delta_keyed", drop), stream_ptr()))
 
 
 def attn_bwd_grouped_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
@@ -451,7 +453,7 @@ def attn_bwd_grouped_delta_keyed(problems: Sequence[AttnProblem], head_dim: int,
     shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
     flops = sum(8.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
     with _Timed(f"attn_bwd_kernels<{head_dim}>", flops, shapes):
-        check(load().mmf_attn_bwd_grouped_delta_keyed(arr, len(problems), head_dim, scale, *_keyed("attn_bwd_grouped_delta_keyed", drop), stream_ptr()))
+        check(load().mmf_attn_bwd_grouped_delta_keyed(arr, len(problems), head_dim, scale, *_drop_args("attn_bwd_grouped_delta_keyed", drop), stream_ptr()))
 
 
 def attn_bwd_grouped_exact_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
@@ -793,16 +795,6 @@ def _deberta_attn_args(who: str, qkv, posq, posk, idx, out, n: int, H: int, T: i
         raise ValueError(f"{who}: operand sizes do not match n, H, T, S")
 
 
-def _deberta_drop(who: str, drop) -> tuple:
-    """``drop`` = (p, state, site, item0) -> the four trailing arguments of the ``_drop`` entry points: ``state`` the device int64
-    [1] RNG state (``ops.rng_state()``), ``item0`` the index in the whole batch of the call's first item"""
-    import torch
-    p, state, site, item0 = drop
-    if state is not None and (not state.is_cuda or state.dtype != torch.int64 or state.numel() != 1):
-        raise ValueError(f"{who}: the dropout state must be one int64 on the GPU")
-    return float(p), None if state is None else state.data_ptr(), int(site), int(item0)
-
-
 def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S: int, scale: float, head_dim: int = 64, lse=None,
                      drop=None) -> None:
     """out (n T, H 64) bf16 = disentangled attention of the fused qkv rows (n T, 3 H 64); posq / posk (2S, H 64) bf16 views with a
@@ -820,7 +812,7 @@ def deberta_attn_fwd(qkv, posq, posk, idx, mask, out, n: int, H: int, T: int, S:
         if drop is not None:
             check(load().mmf_deberta_attn_fwd_drop(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
                                                    out.data_ptr(), None if lse is None else lse.data_ptr(), n, H, T, S, head_dim, scale,
-                                                   *_deberta_drop("deberta_attn_fwd", drop), stream_ptr()))
+                                                   *_drop_args("deberta_attn_fwd", drop), stream_ptr()))
         elif lse is None:
             check(load().mmf_deberta_attn_fwd(qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind,
                                               out.data_ptr(), n, H, T, S, head_dim, scale, stream_ptr()))
@@ -852,7 +844,7 @@ def deberta_attn_bwd(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, dqkv,
         args = (qkv.data_ptr(), posq.data_ptr(), posk.data_ptr(), posq.stride(0), idx.data_ptr(), mp, kind, out.data_ptr(), lse.data_ptr(),
                 dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(), n, H, T, S, head_dim, scale)
         if drop is not None:
-            check(load().mmf_deberta_attn_bwd_drop(*args, *_deberta_drop("deberta_attn_bwd", drop), stream_ptr()))
+            check(load().mmf_deberta_attn_bwd_drop(*args, *_drop_args("deberta_attn_bwd", drop), stream_ptr()))
         else:
             check(load().mmf_deberta_attn_bwd(*args, stream_ptr()))
 
@@ -881,13 +873,13 @@ def deberta_attn_bwd_pos(qkv, posq, posk, idx, mask, out, lse, dout, delta_ws, d
                 dout.data_ptr(), delta_ws.data_ptr(), dqkv.data_ptr(), n, H, T, S, head_dim, scale, dposq.data_ptr(), dposk.data_ptr(),
                 dposq.stride(0), workspace.data_ptr(), workspace.numel() * workspace.element_size())
         if drop is not None:
-            check(load().mmf_deberta_attn_bwd_pos_drop(*args, *_deberta_drop("deberta_attn_bwd_pos", drop), stream_ptr()))
+            check(load().mmf_deberta_attn_bwd_pos_drop(*args, *_drop_args("deberta_attn_bwd_pos", drop), stream_ptr()))
         else:
             check(load().mmf_deberta_attn_bwd_pos(*args, stream_ptr()))
 
 
-def deberta_dropout(y, out, items: int, drop, resid=None) -> None:
-    """Hidden dropout of ``items`` items (``mmf_deberta_dropout``): out = keep ? y c : 0 (+ ``resid``), element e of item g keyed by
+def hidden_dropout(y, out, items: int, drop, resid=None) -> None:
+    """Hidden dropout of ``items`` items (``mmf_hidden_dropout``; DeBERTa's and Wav2Vec2's hidden sites): out = keep ? y c : 0 (+ ``resid``), element e of item g keyed by
     sub-stream item0 + g and index e of ``drop`` = (p, state, site, item0).  bf16: y, out and the optional ``resid`` are contiguous
     bf16 of one size, one f32 multiply-add and one rounding.  f32: y and out contiguous f32, no ``resid``.  ``out`` may be ``y``."""
     import torch
@@ -895,17 +887,14 @@ def deberta_dropout(y, out, items: int, drop, resid=None) -> None:
     (_w2v_f32 if f32 else _w2v_bf16)(y, out)
     if resid is not None:
         if f32:
-            raise ValueError("deberta_dropout: the f32 form takes no residual")
+            raise ValueError("hidden_dropout: the f32 form takes no residual")
         _w2v_bf16(resid)
     ts = [y, out] + ([resid] if resid is not None else [])
     if items <= 0 or y.numel() % items or any(t.numel() != y.numel() or not t.is_contiguous() for t in ts):
-        raise ValueError("deberta_dropout: y, out and resid must be contiguous, of one size that the items divide")
-    with _Timed("deberta_dropout_kernel", 0.0, [(items, y.numel() // items)]):
-        check(load().mmf_deberta_dropout(y.data_ptr(), None if resid is None else resid.data_ptr(), out.data_ptr(), int(f32), items,
-                                         y.numel() // items, *_deberta_drop("deberta_dropout", drop), stream_ptr()))
-
-
-hidden_dropout = deberta_dropout          # the kernel is no model's own: Wav2Vec2's hidden-dropout sites reach it under this name
+        raise ValueError("hidden_dropout: y, out and resid must be contiguous, of one size that the items divide")
+    with _Timed("hidden_dropout_kernel", 0.0, [(items, y.numel() // items)]):
+        check(load().mmf_hidden_dropout(y.data_ptr(), None if resid is None else resid.data_ptr(), out.data_ptr(), int(f32), items,
+                                        y.numel() // items, *_drop_args("hidden_dropout", drop), stream_ptr()))
 
 
 def bias_gelu_drop_to(h, bias, g, items: int, drop) -> None:
@@ -917,7 +906,7 @@ def bias_gelu_drop_to(h, bias, g, items: int, drop) -> None:
     _gelu_blocks("bias_gelu_drop_to", bias, h, g)
     with _Timed("bias_gelu_drop_kernel", 0.0, [tuple(h.shape)]):
         check(load().mmf_bias_gelu_drop_bf16_to(h.data_ptr(), None if bias is None else bias.data_ptr(), g.data_ptr(), h.shape[0], h.shape[1],
-                                                h.stride(0), int(items), *_deberta_drop("bias_gelu_drop_to", drop), stream_ptr()))
+                                                h.stride(0), int(items), *_drop_args("bias_gelu_drop_to", drop), stream_ptr()))
 
 
 def bias_gelu_drop_bwd(dg, h, bias, dh, items: int, drop) -> None:
@@ -927,7 +916,7 @@ def bias_gelu_drop_bwd(dg, h, bias, dh, items: int, drop) -> None:
     _gelu_blocks("bias_gelu_drop_bwd", bias, dg, h, dh)
     with _Timed("bias_gelu_drop_bwd_kernel", 0.0, [tuple(h.shape)]):
         check(load().mmf_bias_gelu_drop_bwd_bf16(dg.data_ptr(), h.data_ptr(), None if bias is None else bias.data_ptr(), dh.data_ptr(), h.shape[0],
-                                                 h.shape[1], h.stride(0), int(items), *_deberta_drop("bias_gelu_drop_bwd", drop), stream_ptr()))
+                                                 h.shape[1], h.stride(0), int(items), *_drop_args("bias_gelu_drop_bwd", drop), stream_ptr()))
 
 
 def _w2v_starts(who: str, starts, items: int) -> int:
@@ -941,7 +930,7 @@ def w2v_mask_spans(starts, T: int, mask_prob: float, length: int, min_masks: int
     """starts (N, S_max) int32 <- every clip's span starts of SpecAugment's time mask, -1 in unused slots (``mmf_w2v_mask_spans``;
     include/mmfusion.h states the draw)"""
     S = _w2v_starts("w2v_mask_spans", starts, 1)
-    _, sp, site, item0 = _deberta_drop("w2v_mask_spans", (0.0, state, site, item0))
+    _, sp, site, item0 = _drop_args("w2v_mask_spans", (0.0, state, site, item0))
     with _Timed("w2v_mask_spans_kernel", 0.0, [tuple(starts.shape)]):
         check(load().mmf_w2v_mask_spans(starts.data_ptr(), starts.shape[0], S, int(T), float(mask_prob), int(length), int(min_masks), sp, site,
                                         item0, stream_ptr()))
@@ -961,7 +950,7 @@ def w2v_mask_drop(x, out, items: int, T: int, length: int, drop, starts=None, em
             raise ValueError("w2v_mask_drop: embed must be contiguous f32 (d,)")
     with _Timed("w2v_mask_drop_kernel", 0.0, [tuple(x.shape)]):
         check(load().mmf_w2v_mask_drop(x.data_ptr(), None if embed is None else embed.data_ptr(), None if starts is None else starts.data_ptr(),
-                                       out.data_ptr(), int(items), int(T), x.shape[1], S, int(length), *_deberta_drop("w2v_mask_drop", drop),
+                                       out.data_ptr(), int(items), int(T), x.shape[1], S, int(length), *_drop_args("w2v_mask_drop", drop),
                                        stream_ptr()))
 
 

@@ -63,12 +63,12 @@ differentiable call in ``train()`` mode.  Such a call takes 3 + 4 L sites from `
 
     1  feature-projection dropout   mmf_w2v_mask_drop (in place, with 2)   x = in_span ? bf16(masked_spec_embed) : keep ? proj c : 0
     2  the time mask's spans        mmf_w2v_mask_spans, once per call      (N, slots) int32 span starts for the whole batch
-    3  after encoder.layer_norm     mmf_deberta_dropout (in place)         x = dropout(LayerNorm(y))
+    3  after encoder.layer_norm     mmf_hidden_dropout (in place)          x = dropout(LayerNorm(y))
     per layer: attention probabilities (mmf_attn_fwd_grouped_keyed), attention output and MLP output (NT, BIAS then
-    mmf_deberta_dropout with the residual: ``_closing``'s ``join``), GELU output (mmf_bias_gelu_drop_bf16_to: ``_ffn``'s ``act``)
+    mmf_hidden_dropout with the residual: ``_closing``'s ``join``), GELU output (mmf_bias_gelu_drop_bf16_to: ``_ffn``'s ``act``)
 
-Masks are the counter hash keyed by (state, site, clip [* H + head], element), so results do not depend on ``chunk``, and the backward
-draws them again: ``mmf_attn_delta_f32_keyed`` + ``mmf_attn_bwd_grouped_delta_keyed``, ``mmf_bias_gelu_drop_bwd_bf16``, the gradient
+The keying (state, site, clip [* H + head], element), and why results do not depend on ``chunk``, is mmfusion/backbone.py's
+("Training-mode dropout").  The backward draws the masks again: ``mmf_attn_delta_f32_keyed`` + ``mmf_attn_bwd_grouped_delta_keyed``, ``mmf_bias_gelu_drop_bwd_bf16``, the gradient
 forms of the two streaming kernels, and ``mmf_w2v_mask_embed_grad`` + ``mmf_sum_slabs_f32`` for ``masked_spec_embed``'s gradient (a
 fixed-order sum).  LayerDrop is a host draw per layer and call; a skipped layer launches nothing ("Regularisers").
 """
@@ -81,7 +81,7 @@ import torch
 
 from . import arena as _arena
 from . import lib, ops
-from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable
+from .backbone import BF16, BackboneOutput, FrozenBackbone, WsTable, _CallDropout, _check_probability
 from .lib import EPI_BIAS, GEMM_NN, GEMM_NT
 
 # clips per pass through the workspace: 16 clips of 10 s give the layer GEMMs 7984 rows.  NOT chosen by measurement yet:
@@ -128,20 +128,19 @@ def span_slots(T: int, prob: float, length: int, min_masks: int) -> int:
     return max(1, span_count(int(prob * T / length) + 1, T, length, min_masks))
 
 
-class _Reg:
-    """The regularisers of one differentiable training call.  Its 3 + 4 L sites come from ``ops.next_site()`` in HuggingFace's
-    call order: the feature projection's dropout, the time-mask draw, the dropout after ``encoder.layer_norm``, then per layer the
-    attention probabilities, the attention output, the GELU output and the MLP output, whether or not LayerDrop skips the layer.  The
-    state is read where a launch is made (``ops.rng_state()``, live: the backward draws the forward's masks again from the same state).
-    What the call keeps: ``starts`` (N, slots) int32, the time mask's span starts (drawn here, once, for the whole batch), and
-    ``skip``, LayerDrop's decision per layer (drawn by the host before the chunk loop, so every chunk agrees)."""
+class _Reg(_CallDropout):
+    """The regularisers of one differentiable training call (mmfusion/backbone.py).  Its 3 + 4 L sites in HuggingFace's call order:
+    the feature projection's dropout, the time-mask draw, the dropout after ``encoder.layer_norm``, then per layer the attention
+    probabilities, the attention output, the GELU output and the MLP output, whether or not LayerDrop skips the layer.
+    What the call keeps beside them: ``starts`` (N, slots) int32, the time mask's span starts (drawn here, once, for the whole batch),
+    and ``skip``, LayerDrop's decision per layer (drawn by the host before the chunk loop, so every chunk agrees)."""
     PROBS, OUT, ACT, MLP = range(4)
 
     def __init__(self, c, N: int, T: int, dev, skip: List[bool]):
-        self.p_h, self.p_a, self.p_act, self.p_fp = c.hidden_dropout, c.attention_dropout, c.activation_dropout, c.feat_proj_dropout
+        super().__init__(c.hidden_dropout, c.attention_dropout, 3, c.num_hidden_layers)
+        self.p_act, self.p_fp = c.activation_dropout, c.feat_proj_dropout
         self.H, self.length, self.skip = c.num_attention_heads, c.mask_time_length, skip
-        self.fp, self.mask, self.enc = ops.next_site(), ops.next_site(), ops.next_site()
-        self.layers = [tuple(ops.next_site() for _ in range(4)) for _ in range(c.num_hidden_layers)]
+        self.fp, self.mask, self.enc = self.lead
         self.starts = None
         if c.mask_time_prob > 0.0:
             self.starts = torch.empty((N, span_slots(T, c.mask_time_prob, c.mask_time_length, c.mask_time_min_masks)), dtype=torch.int32,
@@ -156,18 +155,15 @@ class _Reg:
     def spans(self, n0: int, n: int) -> Optional[torch.Tensor]:
         return None if self.starts is None else self.starts[n0:n0 + n]
 
-    def hidden(self, site: int, item0: int) -> tuple:
-        return self.p_h, ops.rng_state(), site, item0
-
     def feat_proj(self, item0: int) -> tuple:
-        return self.p_fp, ops.rng_state(), self.fp, item0
+        return self.key(self.p_fp, self.fp, item0)
 
     def probs(self, i: int, item0: int) -> Optional[tuple]:
         """the attention's (p, state, site, stream base): stream id = clip * H + head over the whole batch"""
-        return (self.p_a, ops.rng_state(), self.layers[i][self.PROBS], item0 * self.H) if self.p_a > 0.0 else None
+        return self.key(self.p_a, self.layers[i][self.PROBS], item0 * self.H) if self.p_a > 0.0 else None
 
     def act(self, i: int, item0: int) -> Optional[tuple]:
-        return (self.p_act, ops.rng_state(), self.layers[i][self.ACT], item0) if self.p_act > 0.0 else None
+        return self.key(self.p_act, self.layers[i][self.ACT], item0) if self.p_act > 0.0 else None
 
 
 class _Differentiable(torch.autograd.Function):
@@ -319,12 +315,8 @@ class NativeWav2Vec2(FrozenBackbone):
             raise ValueError(f"{who}: {unknown} not built or not known (the settings are {', '.join(REG_NAMES)})")
         new = {n: settings.get(n, getattr(c, n, 10 if n == "mask_time_length" else 2 if n == "mask_time_min_masks" else 0.0)) for n in REG_NAMES}
         for n in REG_NAMES[:5]:
-            p = new[n]
-            if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p < 1.0:
-                raise ValueError(f"{who}({n}={p!r}): a probability in [0, 1)")
-        p = new["mask_time_prob"]
-        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
-            raise ValueError(f"{who}(mask_time_prob={p!r}): a probability in [0, 1]")
+            _check_probability(who, n, new[n])
+        _check_probability(who, "mask_time_prob", new["mask_time_prob"], closed=True)
         for n, low in (("mask_time_length", 1), ("mask_time_min_masks", 0)):
             v = new[n]
             if isinstance(v, bool) or not isinstance(v, int) or v < low:
@@ -336,8 +328,7 @@ class NativeWav2Vec2(FrozenBackbone):
 
     def _reg_of_call(self, N: int, T: int, dev) -> Optional[_Reg]:
         """the regularisers of the differentiable call that is about to run: None unless the module trains with a setting above 0.
-        A call on its own starts a training forward itself (new masks, sites from 1); under a root module's forward it continues
-        that forward's site numbering.  LayerDrop is HuggingFace's ``torch.rand([]) < layerdrop`` per layer, drawn on the host from
+        LayerDrop is HuggingFace's ``torch.rand([]) < layerdrop`` per layer, drawn on the host from
         ``layerdrop_generator``: no device synchronisation, but a graph capture would freeze the pattern, so it is refused there"""
         c = self.config
         if not self.training or not any(getattr(c, n) > 0.0 for n in REG_NAMES[:6]):
@@ -351,8 +342,7 @@ class NativeWav2Vec2(FrozenBackbone):
                 raise RuntimeError("NativeWav2Vec2: layerdrop > 0 draws its skip pattern on the host, which a graph capture would freeze "
                                    "into every replay; capture with layerdrop = 0 (the other regularisers draw new masks on every replay)")
             skip = [bool(torch.rand([], generator=self.layerdrop_generator).item() < c.layerdrop) for _ in range(L)]
-        if not ops.inside_root():
-            ops.begin_training_forward()
+        self._own_training_forward()
         return _Reg(c, N, T, dev, skip)
 
     def set_trainable_layers(self, k: int, front: bool = False) -> None:
@@ -479,22 +469,15 @@ class NativeWav2Vec2(FrozenBackbone):
     def _hooks(self, i: int, ws, n: int, T: int, n0: int, reg: Optional[_Reg]) -> tuple:
         """layer ``i``'s (attend, join, join_bwd, act) for a chunk of ``n`` clips from clip ``n0`` under ``reg``: the attention with
         dropped probabilities, hidden dropout fused with the residual add and its gradient form, the GELU with activation dropout
-        and its backward; None where the setting is 0 (the plain launch)"""
+        and its backward; None where the setting is 0 (the plain launch).  join / join_bwd: ``_hidden_joins``"""
         if reg is None:
             return None, None, None, None
-        attend = join = join_bwd = act = None
+        attend = act = None
         probs, drop = reg.probs(i, n0), reg.act(i, n0)
         if probs is not None:
             def attend(qkv: torch.Tensor, att: torch.Tensor) -> None:
                 lib.attn_fwd_grouped_keyed([self._attn_problem(ws, qkv, att, n, T, T)], self.head_dim, self.head_dim ** -0.5, probs)
-        if reg.p_h > 0.0:
-            sites = {"o": reg.layers[i][_Reg.OUT], "fc2": reg.layers[i][_Reg.MLP]}
-
-            def join(role: str, y: torch.Tensor, resid: torch.Tensor) -> None:
-                lib.hidden_dropout(y, y, n, reg.hidden(sites[role], n0), resid=resid)
-
-            def join_bwd(role: str, dy: torch.Tensor, out: torch.Tensor) -> None:
-                lib.hidden_dropout(dy, out, n, reg.hidden(sites[role], n0))
+        join, join_bwd = self._hidden_joins(reg, reg.join_sites(i), n, n0)
         if drop is not None:
             act = (lambda h, b, g: lib.bias_gelu_drop_to(h, b, g, n, drop), lambda dg, h, b, dh: lib.bias_gelu_drop_bwd(dg, h, b, dh, n, drop))
         return attend, join, join_bwd, act

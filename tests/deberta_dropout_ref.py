@@ -16,7 +16,7 @@ A mask is a bool tensor (True = kept) and the kept values are multiplied by ``c`
 dropout, dropout + residual is rounded once, the dropped embedding output and every ``rel_i`` are rounded once more; probabilities
 are never stored.
 
-Keying (csrc/deberta.hip).  Every mask is ``mmf_keep(mmf_rng_key(state, site, sub), index, thresh)`` of tests/attn_ref.py:
+Keying (csrc/deberta.hip, csrc/elementwise.hip).  Every mask is ``mmf_keep(mmf_rng_key(state, site, sub), index, thresh)`` of tests/attn_ref.py:
   hidden sites    sub = the item's index in the whole batch, index = t * d + column      (``hidden_keep``)
   rel[i]          one item: sub = 0, index = row * d + column
   probs[i]        sub = item * H + head, index = i * T + j for query i and key j         (``probs_keep``)

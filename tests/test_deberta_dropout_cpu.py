@@ -193,4 +193,4 @@ def test_wrapper_refuses_cpu_tensors():
     from mmfusion import lib
     x = torch.zeros(2, 64, dtype=torch.bfloat16)
     with pytest.raises(RuntimeError, match="GPU only"):
-        lib.deberta_dropout(x, x, 2, (0.1, None, 1, 0))
+        lib.hidden_dropout(x, x, 2, (0.1, None, 1, 0))

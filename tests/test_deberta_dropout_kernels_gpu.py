@@ -1,6 +1,6 @@
-"""GPU: the dropout kernels of csrc/deberta.hip against float64 under the masks tests/deberta_dropout_ref.py restates on the host:
+"""GPU: the dropout kernels of csrc/deberta.hip and csrc/elementwise.hip against float64 under the masks tests/deberta_dropout_ref.py restates on the host:
 the attention forward and backward with dropped probabilities (``mmf_deberta_attn_fwd_drop`` / ``_bwd_drop`` / ``_bwd_pos_drop``) and
-the streaming hidden dropout (``mmf_deberta_dropout``).
+the streaming hidden dropout (``mmf_hidden_dropout``).
 
 The mask is held to the restatement EXACTLY (one-hot V rows turn the forward's output into the mask; the streaming kernel's zeros
 are the mask), values to the bounds of tests/test_deberta_grad_gpu.py: the forward's O within BOUND_A relative L2 of float64, its
@@ -245,28 +245,28 @@ def test_streaming_dropout_is_the_restated_mask_and_exact(items, per, p):
     yd, rd = y.cuda(), resid.cuda()
     # without a residual: zeros exactly where the restatement drops (y is never 0), bf16(y c) elsewhere; the gradient form
     out = torch.full_like(yd, float("nan"))
-    lib.deberta_dropout(yd, out, items, _drop(p))
+    lib.hidden_dropout(yd, out, items, _drop(p))
     got = out.cpu()
     assert torch.equal(got.float() != 0, keep), "the kept set is not the restated one"
     assert torch.equal(_bits(got), _bits(torch.where(keep, _fma_bf16(y, cf, torch.zeros_like(y)), torch.zeros_like(y))))
     # with the residual: one multiply-add, one rounding; a dropped element is the residual itself
     out2 = torch.full_like(yd, float("nan"))
-    lib.deberta_dropout(yd, out2, items, _drop(p), resid=rd)
+    lib.hidden_dropout(yd, out2, items, _drop(p), resid=rd)
     assert torch.equal(_bits(out2.cpu()), _bits(torch.where(keep, _fma_bf16(y, cf, resid), resid)))
     inplace = yd.clone()
-    lib.deberta_dropout(inplace, inplace, items, _drop(p), resid=rd)
+    lib.hidden_dropout(inplace, inplace, items, _drop(p), resid=rd)
     assert torch.equal(_bits(inplace), _bits(out2)) and torch.equal(_bits(yd), _bits(y)) and torch.equal(_bits(rd), _bits(resid))
     # f32 (the gradient of an f32 buffer): the same mask, y c in f32
     y32 = y.float() * 1.2345
     out3 = torch.full((items, per), float("nan"), device="cuda")
-    lib.deberta_dropout(y32.cuda(), out3, items, _drop(p))
+    lib.hidden_dropout(y32.cuda(), out3, items, _drop(p))
     assert torch.equal(_bits(out3.cpu()), _bits(torch.where(keep, (y32.double() * cf).float(), torch.zeros_like(y32))))
     # another first item: another mask, and the batch's rows when it is a chunk of it
     if items > 1:
         out4 = torch.full_like(yd[1:], float("nan"))
-        lib.deberta_dropout(yd[1:].contiguous(), out4, items - 1, _drop(p, item0=ITEM0 + 1))
+        lib.hidden_dropout(yd[1:].contiguous(), out4, items - 1, _drop(p, item0=ITEM0 + 1))
         assert torch.equal(_bits(out4), _bits(out[1:]))
-        lib.deberta_dropout(yd[1:].contiguous(), out4, items - 1, _drop(p, item0=ITEM0))
+        lib.hidden_dropout(yd[1:].contiguous(), out4, items - 1, _drop(p, item0=ITEM0))
         assert not torch.equal(_bits(out4), _bits(out[1:]))
     torch.cuda.synchronize()
 
@@ -291,9 +291,9 @@ def test_refusals_return_the_documented_codes_and_launch_nothing():
     bwd_pos = lambda prob, state, ws_bytes=1 << 18, ld=128: L.mmf_deberta_attn_bwd_pos_drop(
         p(b), p(b), p(b), 128, p(idx), None, 0, p(b), p(f), p(b), p(nan32), p(nan16), 1, 2, 16, 8, 64, SCALE, p(nan32), p(nan32, 4096 * 4), ld,
         p(nan32, 8192 * 4), ws_bytes, prob, state, 3, 0, s)
-    drop = lambda prob, state, y="b", resid=None, out=None, f32=0, items=4, per=64, item0=0: L.mmf_deberta_dropout(
+    drop = lambda prob, state, y="b", resid=None, out=None, f32=0, items=4, per=64, item0=0: L.mmf_hidden_dropout(
         p(b) if y == "b" else y, resid, p(nan16) if out is None else out, f32, items, per, prob, state, 3, item0, s)
-    A, B_, C_, D_ = "mmf_deberta_attn_fwd_drop", "mmf_deberta_attn_bwd_drop", "mmf_deberta_attn_bwd_pos_drop", "mmf_deberta_dropout"
+    A, B_, C_, D_ = "mmf_deberta_attn_fwd_drop", "mmf_deberta_attn_bwd_drop", "mmf_deberta_attn_bwd_pos_drop", "mmf_hidden_dropout"
     cases = [
         (A, lambda: fwd(1.0, p(st)), E_SHAPE), (A, lambda: fwd(-0.1, p(st)), E_SHAPE), (A, lambda: fwd(float("nan"), p(st)), E_SHAPE),
         (A, lambda: fwd(0.1, None), E_SHAPE), (A, lambda: fwd(0.1, p(st), item0=-1), E_SHAPE), (A, lambda: fwd(0.1, p(st, 4)), E_ALIGN),

@@ -18,7 +18,7 @@ rounding points to ``w2v_ref``'s: the dropped projection is rounded once (a mask
 rounded before its dropout and dropout + residual once, as in tests/deberta_dropout_ref.py; the dropped GELU output is rounded once;
 the dropped encoder LayerNorm output once more; probabilities are never stored.
 
-Keying (csrc/wav2vec2.hip, csrc/vit.hip, csrc/attention2.hip).  Every mask is ``mmf_keep(mmf_rng_key(state, site, sub), index, thresh)``:
+Keying (csrc/wav2vec2.hip, csrc/vit.hip, csrc/attention2.hip, csrc/elementwise.hip).  Every mask is ``mmf_keep(mmf_rng_key(state, site, sub), index, thresh)``:
   hidden-type sites   sub = the clip's index in the whole batch, index = t * width + column, width d (I at act[i])
   probs[i]            sub = clip * H + head, index = i * T + j
 and the span draw of clip c uses draws n = 0, 1, .. of ``mmf_mix32(key + n * 0x9E3779B9)``, key = mmf_rng_key(state, site, c): draw 0

@@ -10,7 +10,13 @@ the host side.  Each subcommand is one process, so every tree gets a fresh one (
                                                              and every backward: the top two layers trainable (ViT on both routes), and at
                                                              tiny sizes every layer with the embeddings / the front end (DeBERTa from ids
                                                              and through inputs_embeds with its gradient): every parameter .grad after one
-                                                             backward for a seeded dout, and the launches mmfusion.lib.PROFILE recorded
+                                                             backward for a seeded dout, and the launches mmfusion.lib.PROFILE recorded.
+                                                             Training mode, tiny sizes only, every layer trainable: DeBERTa in train() with
+                                                             set_dropout(0.1, 0.1) and the embeddings, from ids with the padded tail;
+                                                             Wav2Vec2 in train() with set_regularisation(**REG_960H) and the front end on
+                                                             4000 samples, layerdrop_generator seeded; ops.seed_dropout(25) before each
+                                                             call: the result, every parameter .grad and the launches.  A launch label
+                                                             in RENAMED_LABELS is recorded under its new name, whichever tree is saved
     python tools/backbone_compare.py equal A.pt B.pt REPORT [A2.pt ...]
                                                              torch.equal per case (== for a launch list) -> REPORT; exit 1 unless all are
                                                              equal.  A2.pt ...: further saves of A's tree; a 1-d parameter .grad (a bias or
@@ -20,8 +26,9 @@ the host side.  Each subcommand is one process, so every tree gets a fresh one (
     python tools/backbone_compare.py speed RUNS REPORT       RUNS: lines "== TOOL [ARGUMENTS] TAG" (TAG = parent | new) each followed by the
                                                              JSON line that tools/TOOL printed from that tree, the trees alternated.
                                                              -> REPORT: every ``*_chunk*``, ``differentiable_forward_ms`` and
-                                                             ``forward_backward_ms`` figure of every run, both medians, the parent's min-max
-                                                             spread; exit 1 unless every new median <= parent median + spread
+                                                             ``[regularised_[no_layerdrop_]]forward_backward_ms`` figure of every run, both
+                                                             medians, the parent's min-max spread; exit 1 unless every new median <= parent
+                                                             median + spread
 """
 import json
 import os
@@ -30,6 +37,9 @@ import sys
 
 
 PARAM_GRAD = "grad_param_"      # in a case's name: a parameter's .grad, the only cases `equal` may find unreproducible in one tree
+# launch labels (mmfusion.lib._Timed) renamed since the parent commit, old -> new: `save` records the new one for either tree, so
+# that the launch lists compare; nothing else is normalised
+RENAMED_LABELS = {"deberta_dropout_kernel": "hidden_dropout_kernel"}
 
 
 def save(tree, out):
@@ -41,7 +51,7 @@ def save(tree, out):
     import deberta_ref
     import vit_ref
     import w2v_ref
-    from mmfusion import arena, backbone, deberta, lib, vit, wav2vec2
+    from mmfusion import arena, backbone, deberta, lib, ops, vit, wav2vec2
     assert os.path.dirname(os.path.abspath(backbone.__file__)) == os.path.join(tree, "simple-multimodal_amd", "mmfusion"), backbone.__file__
 
     def model(cls, ref, cfg, kw):
@@ -51,19 +61,25 @@ def save(tree, out):
 
     res = {}
 
-    def backward(case, m, run, leaf=None):
+    def backward(case, m, run, leaf=None, training=False):
         """one differentiable ``run()`` and its backward for a seeded dout, the gradients zeroed before it -> the case's every
-        parameter .grad (and ``leaf``'s), and the launches ``lib.PROFILE`` recorded from the call to the end of the backward"""
+        parameter .grad (and ``leaf``'s), and the launches ``lib.PROFILE`` recorded from the call to the end of the backward.
+        ``training``: a training-mode call: the dropout state is seeded before it and the result is recorded too"""
         arena.ensure(m).zero_grad()
+        if training:
+            ops.seed_dropout(25)
         torch.cuda.synchronize()
         lib.PROFILE = []
         try:
             out = run()
             out.backward(torch.randn(out.shape, generator=torch.Generator().manual_seed(23)).cuda())
             torch.cuda.synchronize()
-            res[f"{case}_launches"] = [(label, tuple(tuple(int(v) for v in d) for d in detail)) for label, _, _, _, detail in lib.PROFILE]
+            res[f"{case}_launches"] = [(RENAMED_LABELS.get(label, label), tuple(tuple(int(v) for v in d) for d in detail))
+                                       for label, _, _, _, detail in lib.PROFILE]
         finally:
             lib.PROFILE = None
+        if training:
+            res[f"{case}_result"] = out.detach().cpu().clone()
         if leaf is not None:
             res[f"{case}_grad_input"] = leaf.grad.cpu().clone()
         res.update({f"{case}_{PARAM_GRAD}{n}": p.grad.cpu().clone() for n, p in m.named_parameters() if p.requires_grad})
@@ -88,6 +104,11 @@ def save(tree, out):
         for tag, args in (("top2", (2,)), ("all", (cfg.num_hidden_layers, True)))[:2 if size == "tiny" else 1]:
             m.set_trainable_layers(*args)
             backward(f"w2v_{size}_{tag}_4000", m, lambda: m(wave).last_hidden_state)
+        if size == "tiny":             # training mode: every regulariser of wav2vec2-base-960h, every layer and the front end
+            m.train()
+            m.set_regularisation(**wav2vec2.REG_960H)
+            m.layerdrop_generator.manual_seed(24)
+            backward("w2v_tiny_train_960h_4000", m, lambda: m(wave).last_hidden_state, training=True)
         cfg = getattr(deberta_ref, size + "_config")()
         T, pad = (70, 50) if size == "tiny" else (128, 100)
         m = model(deberta.NativeDeberta, deberta_ref, cfg, kw)
@@ -113,6 +134,9 @@ def save(tree, out):
             with torch.no_grad():
                 leaf = m.embeddings.word_embeddings(i).clone().requires_grad_(True)
             backward("deberta_tiny_all_inputs_embeds", m, lambda: m(inputs_embeds=leaf, attention_mask=k).last_hidden_state, leaf)
+            m.train()                  # training mode: HuggingFace's 0.1 / 0.1 at the five sites, every layer and the embeddings
+            m.set_dropout(0.1, 0.1)
+            backward("deberta_tiny_train_dropout_ids", m, lambda: m(input_ids=i, attention_mask=k).last_hidden_state, training=True)
         del m
         torch.cuda.empty_cache()
     assert all(bool(torch.isfinite(v).all()) for v in res.values() if isinstance(v, torch.Tensor))
@@ -126,7 +150,8 @@ def equal(path_a, path_b, report, *more_a):
     again = [torch.load(p) for p in more_a]
     lines = ["Bit identity of the three backbones between two checkouts (tools/backbone_compare.py save, once per tree in a process of its",
              "own, then equal): torch.equal on the f32 results and gradients, == on the recorded launch lists.  seeded_weights(seed=21),",
-             f"seeded inputs; tiny_config: N=3 chunk=2, base_config: N=2 default chunk.  {1 + len(again)} saves of the first tree.", ""]
+             f"seeded inputs; tiny_config: N=3 chunk=2, base_config: N=2 default chunk.  {1 + len(again)} saves of the first tree.",
+             "Launch labels recorded under their new names for either tree: " + ", ".join(f"{o} -> {n}" for o, n in RENAMED_LABELS.items()), ""]
     ok, loose = set(a) == set(b) and all(set(a) == set(x) for x in again), 0
     tensor = lambda v: isinstance(v, torch.Tensor)
     equal_ = lambda x, y: (x.shape == y.shape and torch.equal(x, y)) if tensor(x) and tensor(y) else (not tensor(x) and not tensor(y) and x == y)
@@ -155,7 +180,7 @@ def equal(path_a, path_b, report, *more_a):
 
 def speed(runs_path, report):
     runs, raw, tool, tag = {}, [], None, None
-    timed = ("differentiable_forward_ms", "forward_backward_ms")
+    timed = ("differentiable_forward_ms", "forward_backward_ms", "regularised_forward_backward_ms", "regularised_no_layerdrop_forward_backward_ms")
 
     def take(res, prefix=""):
         """the frozen forwards' ``*_chunk*`` entries, a fine-tuning run's two timings, and those of each of its ``cases``"""
@@ -175,7 +200,8 @@ def speed(runs_path, report):
         elif line.startswith("{"):
             res = json.loads(line)
             for case in [res] + res.get("cases", []):
-                case.pop("kernels", None)                # (the per-kernel table of a fine-tuning run: not compared, not kept)
+                case.pop("kernels", None)                # (the per-kernel tables of a fine-tuning run: not compared, not kept)
+                case.pop("regularised_kernels", None)
             raw.append(f"{tool} {tag}: {json.dumps(res)}")
             take(res)
     lines = ["Host-side speed of the three backbones, parent commit against this one: tools/{vit,w2v,deberta}_bench.py (default chunk,",
