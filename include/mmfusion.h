@@ -55,9 +55,13 @@ int mmf_device_cu_count(void);
  *   layout MMF_GEMM_NN:  C[m][n] = sum_k A[m][k]  * B[k][n]    (dx = dy W, dgrad)
  *   layout MMF_GEMM_TN:  C[m][n] = sum_k A[k][m]  * B[k][n]    (dW = dy^T x, wgrad)
  *
- * Epilogue, applied in this order on the f32 accumulator:
- *   + bias[n] (MMF_EPI_BIAS) -> relu (MMF_EPI_RELU) -> * (aux[m][n] > 0) (MMF_EPI_MASK_AUX)
- *   -> + aux[m][n] (MMF_EPI_ADD_AUX) -> + C_old[m][n] (MMF_EPI_ACCUM, f32 output only)
+ * Epilogue, applied in this order on the f32 accumulator (dropout and alpha: mmf_gemm_grouped_ex):
+ *   + bias[n] (MMF_EPI_BIAS) -> relu (MMF_EPI_RELU) -> keep ? v / (1 - p) : 0 (MMF_EPI_DROPOUT)
+ *   -> * (aux[m][n] > 0) (MMF_EPI_MASK_AUX) -> * alpha -> + aux[m][n] (MMF_EPI_ADD_AUX)
+ *   -> + C_old[m][n] (MMF_EPI_ACCUM, f32 output only)
+ * so a residual (ADD_AUX) and an accumulated old C are neither dropped nor scaled.  The dropout mask of element (m, n) of the
+ * caller's problem i is the counter hash's keep of index m * N + n (N, not ldc; mod 2^32) in sub-stream i of (*rng_state, site),
+ * whichever kernel generation runs the launch and in whatever order it walks the problems (tests/keyed_dropout_ref.py restates it).
  * aux is bf16 with leading dimension ldaux.  Output is bf16 or f32 (out_f32 != 0).
  * One launch covers all problems (<= MMF_GEMM_MAX_PROBLEMS); problems must not alias outputs.
  * ------------------------------------------------------------------------------------------ */
