@@ -162,6 +162,37 @@ int mmf_gemm7_last_tile_n(void);
  * would get); host only, launches nothing */
 int mmf_gemm7_tile_n(const mmf_gemm_problem* problems, int num_problems, int workgroups);
 
+/* K-segment chains (generation 7): C[m][n] = sum over the chain's segments s of sum_k A_s[m][k] B_s[k][n] — ONE GEMM over
+ * K = sum K_s whose operand pieces live in different buffers (the input gradient of a tensor that several linears read: A_s the
+ * output gradients, B_s the weights).  A tile's segments are consecutive entries of the persistent walk; at a segment boundary the
+ * fetch side switches operands as it does between tiles, the accumulators are kept and nothing is stored.  Every output element's
+ * MFMA chain is: bias start, then the k-substeps of segment 0, 1, .. in order — bit-identical to mmf_gemm_grouped on one problem
+ * whose A is the segments' A side by side and whose B is the segments' B stacked.  No atomics, no K split.
+ * Takes: layout MMF_GEMM_NN, bf16 output, epilogue 0, MMF_EPI_BIAS or MMF_EPI_ADD_AUX (the drain's one aux operand), 1..12
+ * chains of 1..4 segments, every K_s a multiple of 32 and >= 160, N and every leading dimension a multiple of 8 (lda >= K_s,
+ * ldb / ldc / ldaux >= N), 16-byte aligned pointers, a generation-7 selection (mmf_gemm_select_impl 0 or 7).
+ * mmf_gemm_chain_available: 1 when mmf_gemm_grouped_chain takes exactly these arguments, else 0; host only, launches nothing
+ * (`stream` is ignored).  mmf_gemm_grouped_chain returns MMF_E_SHAPE for everything else.  The tile width is chosen as for a launch
+ * of one problem of K = sum K_s per chain; mmf_gemm7_chain_tile_n is mmf_gemm7_tile_n for chains (host only). */
+#define MMF_GEMM_CHAIN_MAX_SEGMENTS 4
+#define MMF_GEMM_MAX_CHAINS 12
+typedef struct mmf_gemm_segment {
+  const void* A;      /* bf16 [M][lda], K columns */
+  const void* B;      /* bf16 [K][ldb], N columns */
+  int32_t K, lda, ldb, reserved;
+} mmf_gemm_segment;
+typedef struct mmf_gemm_chain {
+  void* C;            /* bf16 [M][ldc] */
+  const float* bias;  /* f32 [N] (MMF_EPI_BIAS) or NULL */
+  const void* aux;    /* bf16 [M][ldaux] (MMF_EPI_ADD_AUX) or NULL */
+  int32_t M, N, ldc, ldaux;
+  int32_t num_segments, reserved;
+  mmf_gemm_segment seg[MMF_GEMM_CHAIN_MAX_SEGMENTS];
+} mmf_gemm_chain;
+int mmf_gemm_grouped_chain(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, void* stream);
+int mmf_gemm_chain_available(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, void* stream);
+int mmf_gemm7_chain_tile_n(const mmf_gemm_chain* chains, int num_chains, int workgroups);
+
 /* ------------------------------------------------------------------------------------------
  * Skinny-M linear layers (1 <= M <= 64 rows): the (B, d) MLPs of the Early / Contrastive / Adaptive /
  * Graph / meta branches (models/fusion_layers.py:21-28, 304-327, 395-412, 471-476) and MulT's pooled

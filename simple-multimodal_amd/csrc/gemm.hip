@@ -143,3 +143,21 @@ extern "C" int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_pro
   if (impl == 7) return mmf_gemm7_launch(problems, num_problems, layout, epilogue, out_f32, extra, s);
   MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: kernel generation %d is not built (2, 6, 7)", impl);
 }
+
+// ---- K-segment chains: C = sum over a chain's segments of A_s B_s, one accumulator chain per output tile (gemm7.hip) -----------------
+bool mmf_gemm7_chain_supports(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue);
+int mmf_gemm7_chain_launch(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, hipStream_t s);
+
+// generation 7 only: a pinned generation 2 or 6 (mmf_gemm_select_impl) has no chain form
+extern "C" int mmf_gemm_chain_available(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, void* /*stream*/) {
+  return (gemm_impl() == 0 || gemm_impl() == 7) && mmf_gemm7_chain_supports(chains, num_chains, layout, epilogue);
+}
+
+extern "C" int mmf_gemm_grouped_chain(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, void* stream) {
+  if (!mmf_gemm_chain_available(chains, num_chains, layout, epilogue, stream))
+    MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped_chain: %d chains, layout %d, epilogue %d: not a launch of the chain form (NN, bf16 output, flags none / "
+             "MMF_EPI_BIAS / MMF_EPI_ADD_AUX, 1..%d segments of K %% 32 == 0 and K >= 160, generation 7 selectable; mmf_gemm_chain_available)",
+             num_chains, layout, epilogue, MMF_GEMM_CHAIN_MAX_SEGMENTS);
+  t_last_impl = 7;
+  return mmf_gemm7_chain_launch(chains, num_chains, layout, epilogue, static_cast<hipStream_t>(stream));
+}

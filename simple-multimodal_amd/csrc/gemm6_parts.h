@@ -22,7 +22,10 @@ struct GemmArgs {
   unsigned drop_thresh, site;        // MMF_EPI_DROPOUT
   const unsigned long long* rng_state;
   int tile_start[MMF_GEMM_MAX_PROBLEMS + 1];
-  short orig[MMF_GEMM_MAX_PROBLEMS];   // gemm7: the caller's index of problem i (its problems are sorted by K; the dropout stream id is the caller's)
+  // gemm7: the caller's index of problem i (its problems are sorted by K; the dropout stream id is the caller's).  A chain launch
+  // (gemm7.hip, CHAIN: no dropout) keeps here where chain i's segments start in p[]: chain i owns p[orig[i]] .. p[orig[i + 1] - 1],
+  // nprob counts the chains and tile_start[] is per chain.
+  short orig[MMF_GEMM_MAX_PROBLEMS];
   mmf_gemm_problem p[MMF_GEMM_MAX_PROBLEMS];
 };
 

@@ -41,9 +41,10 @@ struct TileSrc {
   const unsigned short* Bb;
   int recA, recB, stepB, KT;
 };
-// what the compute / store side needs
+// what the compute / store side needs (last: a chain launch's entry is its tile's last K segment, the one that is drained)
 struct TileDst {
   int pi, m0, n0;
+  bool last;
 };
 
 // A wave-uniform value the vector ALU produced (integer division has no scalar form), handed to the scalar side.  As an inline-asm
@@ -59,14 +60,22 @@ __device__ __forceinline__ int to_sgpr(int x) {
   return r;
 }
 
-template <bool B_KR, int TN>
-__device__ __forceinline__ void locate_tile(const GemmArgs& args, const int total_tiles, const int orig, TileSrc& s, TileDst& d, int& lda, int& ldb) {
+// CHAIN: the launch's units are chains of K segments (GemmArgs::orig); the entry is segment `seg` of tile `orig` of the chains'
+// tile order.  A chain's segments are problems of one M, N and C, so the tile's origin and its output side are any segment's.
+template <bool B_KR, int TN, bool CHAIN>
+__device__ __forceinline__ void locate_tile(const GemmArgs& args, const int total_tiles, const int orig, const int seg, TileSrc& s, TileDst& d, int& lda, int& ldb) {
   const int bid = to_sgpr(mmf_xcd_tile(orig, total_tiles, args.xcd_granule));
   int pi = 0;
   while (pi + 1 < args.nprob && bid >= args.tile_start[pi + 1]) ++pi;
+  const int t = bid - args.tile_start[pi];
+  d.last = true;
+  if constexpr (CHAIN) {
+    d.last = args.orig[pi] + seg + 1 == args.orig[pi + 1];
+    pi = args.orig[pi] + seg;
+  }
   const mmf_gemm_problem& P = args.p[pi];
   int m0, n0;
-  tile_origin<Form<TN>::BNT>(P, bid - args.tile_start[pi], m0, n0);
+  tile_origin<Form<TN>::BNT>(P, t, m0, n0);
   m0 = to_sgpr(m0);
   n0 = to_sgpr(n0);
   d.pi = pi; d.m0 = m0; d.n0 = n0;
@@ -249,7 +258,12 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
 //     the instruction stream (and in the hand-overs' counts) but touch no memory — the range check answers them with zeros;
 //   * the ring fill fetches NS - 1 stages and the late half of the NS-th, so the very first stage already finds its early pieces
 //     to issue.
-template <bool B_KR, int CT, int TN>
+//
+// CHAIN (K-segment chains, mmf_gemm_grouped_chain): an output tile's reduction runs over 1..4 segments whose operands live in different
+// buffers.  A tile's segments are consecutive entries of the workgroup's walk, and a segment boundary is the tile hand-over above with
+// two differences: the accumulators are kept (no bias_init) and nothing is drained.  The k-loop, the ring and the drain are the same
+// code; every output element's MFMA chain is the bias start, then the k-substeps of segment 0, 1, .. in order.
+template <bool B_KR, int CT, int TN, bool CHAIN>
 __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total_tiles, char* smem) {
   constexpr bool A_KR = false;
   using F = Form<TN>;
@@ -267,12 +281,10 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   // to workgroups 0 .. 16, four of which already held long tiles: 96 k-steps where 48 suffice (93 us in the step, 382 TF).
   const int wid = blockIdx.x;
   auto walk = [&](int round) { return round * nwg + ((round & 1) ? nwg - 1 - wid : wid); };
-  int round = 0;
-  int orig = walk(0);
   TileSrc ns;
   TileDst cd, nd;
   int KT, lda, ldb;
-  locate_tile<B_KR, TN>(args, total_tiles, orig, ns, cd, lda, ldb);
+  locate_tile<B_KR, TN, CHAIN>(args, total_tiles, walk(0), 0, ns, cd, lda, ldb);
   KT = ns.KT;
 
   // ---- LDS-DMA: this wave's PPW pieces of a stage (PPO of the m-operand, TN of the n-operand), per-lane source offsets for the tile
@@ -336,17 +348,29 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     }
   }
 
-  bool has_next = walk(1) < total_tiles;
+  // The entry behind the one in (ns, nd) — the same tile's next segment (CHAIN), else the first segment of the workgroup's next
+  // tile — becomes what the fetch side switches to; false: the walk has ended, the refills get an empty range.
+  int nround = 0, nseg = 0;
   nd = cd;
-  if (has_next) {
-    int la, lb;
-    locate_tile<B_KR, TN>(args, total_tiles, walk(1), ns, nd, la, lb);
-    set_voff(voffn, la, lb);
-  } else {
-    ns.recA = 0; ns.recB = 0; ns.stepB = 0;
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) voffn[i] = voff[i];
-  }
+  for (int i = 0; i < PPW; ++i) voffn[i] = voff[i];
+  auto locate_next = [&]() {
+    if (CHAIN && !nd.last) {
+      ++nseg;
+    } else {
+      ++nround;
+      nseg = 0;
+      if (walk(nround) >= total_tiles) {
+        ns.recA = 0; ns.recB = 0; ns.stepB = 0;
+        return false;
+      }
+    }
+    int la, lb;
+    locate_tile<B_KR, TN, CHAIN>(args, total_tiles, walk(nround), nseg, ns, nd, la, lb);
+    set_voff(voffn, la, lb);
+    return true;
+  };
+  bool has_next = locate_next();
 
   // ---- fragment addressing (tile-independent) ----------------------------------------------------------------------------------------
   unsigned la0, la1, lb0, lb1;
@@ -524,8 +548,14 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   unsigned g = 0;
   for (;;) {
     bias_init(bcur);
-    const int ksw = KT - NS;                                   // >= 1 (host)
-    for (int kt = 0; kt < KT; ++kt, ++g) stage(g, kt, ksw);
+    for (;;) {
+      const int ksw = KT - NS;                                 // >= 1 (host)
+      for (int kt = 0; kt < KT; ++kt, ++g) stage(g, kt, ksw);
+      if (!CHAIN || cd.last) break;
+      cd = nd;                                                 // the tile's next segment: the hand-over of stage ksw switched the fetch side to it
+      KT = ns.KT;
+      has_next = locate_next();
+    }
     // ---- the tile's outputs ----------------------------------------------------------------------------------------------------------
     const mmf_gemm_problem& P = args.p[cd.pi];
     const int mb = cd.m0 + 128 * wm, nb = cd.n0 + 32 * TN * wn;
@@ -536,28 +566,19 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
     if (lane == 0 && mb == -1) static_cast<volatile unsigned short*>(P.C)[0] = (unsigned short)acc[0][0][0];   // (ablation: the tile is not stored)
 #endif
     if (!has_next) break;
-    ++round;
-    orig = walk(round);
     cd = nd;
     KT = ns.KT;
-    has_next = walk(round + 1) < total_tiles;
-    if (has_next) {
-      int la, lb;
-      locate_tile<B_KR, TN>(args, total_tiles, walk(round + 1), ns, nd, la, lb);
-      set_voff(voffn, la, lb);
-    } else {
-      ns.recA = 0; ns.recB = 0; ns.stepB = 0;
-    }
+    has_next = locate_next();
   }
   vm_wait<0>();                       // the zero-range refills behind the last tile
 }
 
-template <bool B_KR, int CT, int TN>
+template <bool B_KR, int CT, int TN, bool CHAIN = false>
 __global__ __launch_bounds__(NTHREADS, 1)
 void gemm7_persistent_kernel(const GemmArgs args, const int total_tiles) {
   // the ring and, behind it, one 8-KiB output staging region per wave: all 160 KiB of the CU at TN = 4, 144 KiB at TN = 3
   __shared__ __attribute__((aligned(1024))) char smem[Form<TN>::LDS];
-  gemm7_body<B_KR, CT, TN>(args, total_tiles, smem);
+  gemm7_body<B_KR, CT, TN, CHAIN>(args, total_tiles, smem);
 }
 
 // the (layout, flag set) pairs of the fusion step's NT / NN launches: in-projections (NT, bias), FFN1 (NT, bias + ReLU), out-projection
@@ -586,10 +607,24 @@ bool launch7_select(int layout, int eflags, const GemmArgs* a, int total, int gr
     if (eflags == (RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT))  { if (a) launch7<false, RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s); return true; }
   } else if (layout == MMF_GEMM_NN) {
     if (eflags == 0)                                      { if (a) launch7<true, 0>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == MMF_EPI_MASK_AUX)                       { if (a) launch7<true, MMF_EPI_MASK_AUX>(*a, total, grid, tile_n, s); return true; }
+    if (eflags == MMF_EPI_BIAS)                           { if (a) launch7<true, MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }   // (the chain form's twin)
+    if (eflags == MMF_EPI_MASK_AUX)                      { if (a) launch7<true, MMF_EPI_MASK_AUX>(*a, total, grid, tile_n, s); return true; }
     if (eflags == MMF_EPI_MASK_BITS)                      { if (a) launch7<true, MMF_EPI_MASK_BITS>(*a, total, grid, tile_n, s); return true; }
     if (eflags == MMF_EPI_ADD_AUX)                        { if (a) launch7<true, MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
   }
+  return false;
+}
+// the chain form's flag sets (NN: the input gradient summed over the linears that read one input); a == nullptr: only ask
+template <int CT>
+void launch7_chain(const GemmArgs& a, int total, int grid, int tile_n, hipStream_t s) {
+  if (tile_n == 192) hipLaunchKernelGGL((gemm7_persistent_kernel<true, CT, 3, true>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
+  else               hipLaunchKernelGGL((gemm7_persistent_kernel<true, CT, 4, true>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
+}
+bool launch7_chain_select(int layout, int eflags, const GemmArgs* a, int total, int grid, hipStream_t s, int tile_n = 256) {
+  if (layout != MMF_GEMM_NN) return false;
+  if (eflags == 0)               { if (a) launch7_chain<0>(*a, total, grid, tile_n, s); return true; }
+  if (eflags == MMF_EPI_BIAS)    { if (a) launch7_chain<MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }
+  if (eflags == MMF_EPI_ADD_AUX) { if (a) launch7_chain<MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
   return false;
 }
 }  // namespace
@@ -725,5 +760,90 @@ int mmf_gemm7_launch(const mmf_gemm_problem* problems, int num_problems, int lay
   t_last_tile_n = tile_n;
   launch7_select(layout, epilogue, &a, total, grid, s, tile_n);
   MMF_CHECK_LAUNCH("mmf_gemm_grouped(v7)");
+  return MMF_OK;
+}
+
+// ---- K-segment chains (mmf_gemm_grouped_chain) ------------------------------------------------------------------------------------------
+namespace {
+static_assert(MMF_GEMM_MAX_CHAINS * MMF_GEMM_CHAIN_MAX_SEGMENTS <= MMF_GEMM_MAX_PROBLEMS, "a launch's segments fill GemmArgs::p at most");
+// the chains as the walk and pick_tile_n see them: one problem of K = the sum of the segments' K each
+void chains_as_problems(const mmf_gemm_chain* chains, int n, mmf_gemm_problem* out) {
+  for (int i = 0; i < n; ++i) {
+    out[i] = mmf_gemm_problem{};
+    out[i].M = chains[i].M;
+    out[i].N = chains[i].N;
+    for (int j = 0; j < chains[i].num_segments; ++j) out[i].K += chains[i].seg[j].K;
+  }
+}
+bool chain_shapes_ok(const mmf_gemm_chain* chains, int n, int epilogue) {
+  if (!chains || n < 1 || n > MMF_GEMM_MAX_CHAINS) return false;
+  for (int i = 0; i < n; ++i) {
+    const mmf_gemm_chain& c = chains[i];
+    if (c.num_segments < 1 || c.num_segments > MMF_GEMM_CHAIN_MAX_SEGMENTS || c.M <= 0 || c.N <= 0) return false;
+    if (!c.C || !mmf_aligned16(c.C) || (c.N & 7) || (c.ldc & 7) || c.ldc < c.N || (size_t)c.M * c.ldc * 2 >= 0x7fffffffull) return false;
+    if ((epilogue & MMF_EPI_BIAS) && (!c.bias || !mmf_aligned16(c.bias))) return false;
+    if ((epilogue & MMF_EPI_ADD_AUX) &&
+        (!c.aux || !mmf_aligned16(c.aux) || (c.ldaux & 7) || c.ldaux < c.N || (size_t)c.M * c.ldaux * 2 >= 0x7fffffffull)) return false;
+    for (int j = 0; j < c.num_segments; ++j) {
+      const mmf_gemm_segment& g = c.seg[j];
+      if (!g.A || !g.B || !mmf_aligned16(g.A) || !mmf_aligned16(g.B)) return false;
+      if (g.K % BK || g.K < (NS + 1) * BK || (g.lda & 7) || (g.ldb & 7) || g.lda < g.K || g.ldb < c.N) return false;
+      if ((size_t)c.M * g.lda * 2 >= 0x7fffffffull || (size_t)g.K * g.ldb * 2 >= 0x7fffffffull) return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int mmf_gemm7_chain_tile_n(const mmf_gemm_chain* chains, int num_chains, int workgroups) {
+  if (!chain_shapes_ok(chains, num_chains, 0) || workgroups < 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_gemm7_chain_tile_n: %d chains, %d workgroups, or a chain the chain form does not take", num_chains, workgroups);
+  mmf_gemm_problem sums[MMF_GEMM_MAX_CHAINS];
+  chains_as_problems(chains, num_chains, sums);
+  return mmf_gemm7_tile_n(sums, num_chains, workgroups);
+}
+
+// whether the persistent kernel's chain form takes this launch: NN, the flag sets none / bias / residual, every segment's K a multiple
+// of 32 and >= (NS + 1) * 32, and the alignment rules of mmf_gemm7_supports
+bool mmf_gemm7_chain_supports(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue) {
+  return launch7_chain_select(layout, epilogue, nullptr, 0, 0, nullptr) && chain_shapes_ok(chains, num_chains, epilogue);
+}
+
+int mmf_gemm7_chain_launch(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, hipStream_t s) {
+  if (!mmf_gemm7_chain_supports(chains, num_chains, layout, epilogue))
+    MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped_chain: takes 1..%d NN chains of 1..%d segments with bf16 output, the flag sets none / MMF_EPI_BIAS / "
+             "MMF_EPI_ADD_AUX, every segment's K %% 32 == 0 and >= %d, N and the leading dimensions multiples of 8, 16-byte aligned operands "
+             "(mmf_gemm_chain_available)", MMF_GEMM_MAX_CHAINS, MMF_GEMM_CHAIN_MAX_SEGMENTS, (NS + 1) * BK);
+  mmf_gemm_problem sums[MMF_GEMM_MAX_CHAINS];
+  chains_as_problems(chains, num_chains, sums);
+  int order[MMF_GEMM_MAX_CHAINS];
+  sort_by_k(sums, num_chains, order);                          // longest total reduction first
+  const int cap = persistent_grid_cap();
+  const int tile_n = g_tile_n ? g_tile_n : pick_tile_n(sums, order, num_chains, cap);
+  GemmArgs a;
+  a.nprob = num_chains;
+  a.epi = epilogue;
+  a.xcd_granule = mmf_xcd_granule();
+  a.alpha = 1.f;
+  a.drop_thresh = 0u;
+  a.site = 0u;
+  a.rng_state = nullptr;
+  int total = 0, nseg = 0;
+  for (int i = 0; i < num_chains; ++i) {
+    const mmf_gemm_chain& c = chains[order[i]];
+    a.tile_start[i] = total;
+    total += tiles_of(sums[order[i]], tile_n);
+    a.orig[i] = (short)nseg;
+    for (int j = 0; j < c.num_segments; ++j) {
+      const mmf_gemm_segment& g = c.seg[j];
+      a.p[nseg++] = mmf_gemm_problem{g.A, g.B, c.C, c.bias, (epilogue & MMF_EPI_ADD_AUX) ? c.aux : nullptr, c.M, c.N, g.K, g.lda, g.ldb, c.ldc, c.ldaux};
+    }
+  }
+  a.tile_start[num_chains] = total;
+  a.orig[num_chains] = (short)nseg;
+  const int grid = total < cap ? total : cap;
+  t_last_tile_n = tile_n;
+  launch7_chain_select(layout, epilogue, &a, total, grid, s, tile_n);
+  MMF_CHECK_LAUNCH("mmf_gemm_grouped_chain(v7)");
   return MMF_OK;
 }

@@ -26,6 +26,7 @@ EVAL_MAX_HEADS, EVAL_NSUMS = 4, 4
 SYMBOLS = (
     "mmf_version", "mmf_last_error", "mmf_device_cu_count", "mmf_gemm_grouped", "mmf_gemm_grouped_ex", "mmf_gemm_relu_bits_bytes", "mmf_gemm_relu_bits_available", "mmf_gemm_select_impl", "mmf_gemm_last_impl", "mmf_gemm_set_persistent_workgroups",
     "mmf_gemm7_set_tile_n", "mmf_gemm7_last_tile_n", "mmf_gemm7_tile_n",
+    "mmf_gemm_grouped_chain", "mmf_gemm_chain_available", "mmf_gemm7_chain_tile_n",
     "mmf_attn_fwd_grouped_ex", "mmf_attn_bwd_grouped_ex", "mmf_dropout", "mmf_attn_select_impl",
     "mmf_attn_fwd_grouped", "mmf_attn_bwd_grouped", "mmf_attn_delta_f32", "mmf_attn_bwd_grouped_delta", "mmf_layernorm_fwd_grouped",
     "mmf_layernorm_bwd_grouped", "mmf_layernorm_bwd_add_grouped", "mmf_layernorm_bwd_workspace_bytes", "mmf_layernorm_last_form", "mmf_layernorm2_add3_available", "mmf_layernorm2_add3_fwd_grouped", "mmf_cast_f32_to_bf16", "mmf_cast_bf16_to_f32", "mmf_cast_bf16_to_f32_scaled", "mmf_cast_f32_to_bf16_2d", "mmf_add3_bf16", "mmf_add3_grouped", "mmf_addn_bf16", "mmf_addn_grouped",
@@ -58,6 +59,20 @@ class GemmProblem(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("bias", C.c_void_p),
                 ("aux", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
                 ("lda", C.c_int32), ("ldb", C.c_int32), ("ldc", C.c_int32), ("ldaux", C.c_int32)]
+
+
+GEMM_CHAIN_MAX_SEGMENTS, GEMM_MAX_CHAINS = 4, 12
+
+
+class GemmSegment(C.Structure):
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("K", C.c_int32), ("lda", C.c_int32), ("ldb", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GemmChain(C.Structure):
+    _fields_ = [("C", C.c_void_p), ("bias", C.c_void_p), ("aux", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32),
+                ("ldc", C.c_int32), ("ldaux", C.c_int32), ("num_segments", C.c_int32), ("reserved", C.c_int32),
+                ("seg", GemmSegment * GEMM_CHAIN_MAX_SEGMENTS)]
 
 
 class AttnProblem(C.Structure):
@@ -158,6 +173,9 @@ def load() -> C.CDLL:
     lib.mmf_gemm_relu_bits_bytes.restype = C.c_size_t
     lib.mmf_gemm_relu_bits_available.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, i32, C.POINTER(GemmExtra)]
     lib.mmf_gemm7_tile_n.argtypes = [C.POINTER(GemmProblem), i32, i32]
+    lib.mmf_gemm_grouped_chain.argtypes = [C.POINTER(GemmChain), i32, i32, i32, vp]
+    lib.mmf_gemm_chain_available.argtypes = [C.POINTER(GemmChain), i32, i32, i32, vp]
+    lib.mmf_gemm7_chain_tile_n.argtypes = [C.POINTER(GemmChain), i32, i32]
     lib.mmf_attn_fwd_grouped_ex.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, vp]
     lib.mmf_attn_bwd_grouped_ex.argtypes = [C.POINTER(AttnProblem), i32, i32, f32, f32, vp, C.c_uint32, vp]
     lib.mmf_dropout.argtypes = [vp, vp, i64, i32, f32, vp, C.c_uint32, vp]
@@ -356,6 +374,24 @@ def gemm_relu_bits_available(problems: Sequence[GemmProblem], layout: int, epilo
     arr = (GemmProblem * len(problems))(*problems)
     ex = GemmExtra(alpha, dropout_p, rng_state_ptr, site)
     return bool(load().mmf_gemm_relu_bits_available(arr, len(problems), layout, epilogue, 0, C.byref(ex)))
+
+
+def gemm_chain_available(chains: Sequence[GemmChain], layout: int, epilogue: int) -> bool:
+    """Whether ``gemm_grouped_chain`` takes exactly this launch (``mmf_gemm_chain_available``).  Host only."""
+    if not 0 < len(chains) <= GEMM_MAX_CHAINS:
+        return False
+    arr = (GemmChain * len(chains))(*chains)
+    return bool(load().mmf_gemm_chain_available(arr, len(chains), layout, epilogue, None))
+
+
+def gemm_grouped_chain(chains: Sequence[GemmChain], layout: int, epilogue: int) -> None:
+    """One launch of K-segment chains: every chain's output is the sum of its segments' products, accumulated in one
+    MFMA chain per output tile and stored once (``mmf_gemm_grouped_chain``)."""
+    arr = (GemmChain * len(chains))(*chains)
+    flops = sum(2.0 * c.M * c.N * c.seg[j].K for c in chains for j in range(c.num_segments)) if PROFILE is not None else 0.0
+    detail = [(c.M, c.N, sum(c.seg[j].K for j in range(c.num_segments))) for c in chains] if PROFILE is not None else None
+    with _Timed(f"gemm7_chain_kernel<{_LAYOUT_NAME[layout]},bf16>", flops, detail):
+        check(load().mmf_gemm_grouped_chain(arr, len(chains), layout, epilogue, stream_ptr()))
 
 
 def attn_fwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: float, dropout_p: float = 0.0,

@@ -236,6 +236,42 @@ def gemm_group(layout: int, probs: Sequence[tuple], epilogue: int, alpha: float 
         lib.gemm_grouped(ps[i:i + lib.GEMM_MAX_PROBLEMS], layout, epilogue, out_f32, alpha)
 
 
+def _gemm_chains(chains: Sequence[tuple]) -> List[lib.GemmChain]:
+    """One lib.GemmChain per (C, bias|None, aux|None, [(A_0, B_0), (A_1, B_1), ...]) of bf16 row matrices (NN: A_s is
+    (M, K_s), B_s is (K_s, N)): C = sum_s A_s B_s in one accumulator chain."""
+    cs: List[lib.GemmChain] = []
+    for (Cm, bias, aux, segs) in chains:
+        _req(Cm, BF16)
+        M, N = Cm.shape
+        if not 0 < len(segs) <= lib.GEMM_CHAIN_MAX_SEGMENTS:
+            raise ValueError(f"a chain has 1..{lib.GEMM_CHAIN_MAX_SEGMENTS} segments, got {len(segs)}")
+        if aux is not None and (aux.dtype != BF16 or tuple(aux.shape) != (M, N)):
+            raise ValueError("aux must match C")
+        if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+            raise ValueError("bias must be contiguous f32 [N]")
+        c = lib.GemmChain()
+        c.C, c.bias, c.aux, c.M, c.N, c.ldc, c.num_segments = Cm.data_ptr(), _ptr(bias), _ptr(aux), M, N, _ld(Cm), len(segs)
+        c.ldaux = _ld(aux) if aux is not None else 0
+        for k, (A, Bm) in enumerate(segs):
+            _req(A, BF16), _req(Bm, BF16)
+            if A.dim() != 2 or Bm.dim() != 2 or A.shape[0] != M or Bm.shape != (A.shape[1], N):
+                raise ValueError(f"chain segment {k}: A{tuple(A.shape)} B{tuple(Bm.shape)} C{tuple(Cm.shape)}")
+            c.seg[k].A, c.seg[k].B, c.seg[k].K, c.seg[k].lda, c.seg[k].ldb = A.data_ptr(), Bm.data_ptr(), A.shape[1], _ld(A), _ld(Bm)
+        cs.append(c)
+    return cs
+
+
+def gemm_chain_available(chains: Sequence[tuple], epilogue: int) -> bool:
+    """whether ``gemm_chain_group`` has its launch for these chains (``lib.gemm_chain_available``); host only"""
+    return lib.gemm_chain_available(_gemm_chains(chains), GEMM_NN, epilogue)
+
+
+def gemm_chain_group(chains: Sequence[tuple], epilogue: int) -> None:
+    """chains: (C, bias|None, aux|None, [(A_s, B_s), ...]); C = sum_s A_s B_s (+ bias | + aux) for every chain in ONE launch,
+    each output tile accumulated over its chain's segments and stored once (``mmf_gemm_grouped_chain``: NN, bf16)."""
+    lib.gemm_grouped_chain(_gemm_chains(chains), GEMM_NN, epilogue)
+
+
 # --------------------------------------------------------------------------------------------
 # dropout: device-resident RNG state + per-call-site ids
 # --------------------------------------------------------------------------------------------
@@ -1440,38 +1476,44 @@ class _FanoutGroup(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gs):
         n, m = ctx.n, ctx.m
-        outs: List[Optional[torch.Tensor]] = []
-        probs, keep = [], []
-        for i in range(m):
-            live = [g for g in gs[i * n:(i + 1) * n] if g is not None]
-            if not live:
-                outs.append(None)
-                continue
-            if len(live) == 1:
-                outs.append(live[0])
-                continue
-            live = [_grad_bf16(g) for g in live]
-            if len(live) > lib.ADDN_MAX or live[0].numel() % 8 or any(g.data_ptr() % 16 for g in live):
-                # a gradient the grouped kernel cannot take (a view at an odd offset, an over-wide fan-out): sum this tensor's
-                # gradients with stock adds in f32 rather than raising from inside backward
-                acc = live[0].float()
-                for g in live[1:]:
-                    acc = acc + g.float()
-                outs.append(acc.to(BF16))
-                continue
-            out = torch.empty_like(live[0])
-            q = lib.AddNProblem()
-            for k, g in enumerate(live):
-                q.x[k] = g.data_ptr()
-            q.y, q.numel, q.n = out.data_ptr(), out.numel(), len(live)
-            probs.append(q)
-            keep += live
-            outs.append(out)
-        for i in range(0, len(probs), lib.ADDN_GROUP_MAX):
-            chunk = probs[i:i + lib.ADDN_GROUP_MAX]
-            arr = (lib.AddNProblem * len(chunk))(*chunk)
-            lib.check(lib.load().mmf_addn_grouped(arr, len(chunk), lib.stream_ptr()))
-        return (None, *outs)
+        return (None, *_sum_gradient_groups([gs[i * n:(i + 1) * n] for i in range(m)]))
+
+
+def _sum_gradient_groups(groups: Sequence[Sequence[Optional[torch.Tensor]]]) -> List[Optional[torch.Tensor]]:
+    """One bf16 sum per group of gradients (None entries skipped; an empty group gives None), all groups in ONE grouped launch
+    (mmf_addn_grouped, f32 accumulate)."""
+    outs: List[Optional[torch.Tensor]] = []
+    probs, keep = [], []
+    for grads in groups:
+        live = [g for g in grads if g is not None]
+        if not live:
+            outs.append(None)
+            continue
+        if len(live) == 1:
+            outs.append(live[0])
+            continue
+        live = [_grad_bf16(g) for g in live]
+        if len(live) > lib.ADDN_MAX or live[0].numel() % 8 or any(g.data_ptr() % 16 for g in live):
+            # a gradient the grouped kernel cannot take (a view at an odd offset, an over-wide fan-out): sum this tensor's
+            # gradients with stock adds in f32 rather than raising from inside backward (ADVICE r3)
+            acc = live[0].float()
+            for g in live[1:]:
+                acc = acc + g.float()
+            outs.append(acc.to(BF16))
+            continue
+        out = torch.empty_like(live[0])
+        q = lib.AddNProblem()
+        for k, g in enumerate(live):
+            q.x[k] = g.data_ptr()
+        q.y, q.numel, q.n = out.data_ptr(), out.numel(), len(live)
+        probs.append(q)
+        keep += live
+        outs.append(out)
+    for i in range(0, len(probs), lib.ADDN_GROUP_MAX):
+        chunk = probs[i:i + lib.ADDN_GROUP_MAX]
+        arr = (lib.AddNProblem * len(chunk))(*chunk)
+        lib.check(lib.load().mmf_addn_grouped(arr, len(chunk), lib.stream_ptr()))
+    return outs
 
 
 def fanout_group(xs: Sequence[torch.Tensor], n: int) -> List[List[torch.Tensor]]:
@@ -1481,6 +1523,101 @@ def fanout_group(xs: Sequence[torch.Tensor], n: int) -> List[List[torch.Tensor]]
         return [fanout(x, n) for x in xs]
     flat = _FanoutGroup.apply(n, *xs)
     return [list(flat[i * n:(i + 1) * n]) for i in range(len(xs))]
+
+
+# --------------------------------------------------------------------------------------------
+# the linears that read one input, with that input's pass-through uses, as ONE node: its backward forms each input's
+# gradient in one accumulator chain per output tile (lib.gemm_grouped_chain) instead of one dgrad per linear plus a sum
+# --------------------------------------------------------------------------------------------
+class _FanoutLinear(torch.autograd.Function):
+    """tensors = [x_0 .. x_{m-1}, w_0.p, b_0.p, w_1.p, ...]; ``src[i]``: the input linear i reads; ``npass`` further handles
+    on every input.  Returns the linears' outputs, then the m * npass handles.  The forward is the launch ``linear_group``
+    makes of the same items.  The backward receives every gradient of an input at once:
+        dx_j = sum over the linears i that read x_j of dy_i W_i  +  the sum of the npass handle gradients
+    as one chain per input (the handle gradients summed first, left to right, by ``mmf_add3_grouped`` and added in the
+    chain's drain) where the library takes it, else as the dgrad launch and the grouped sum ``_GroupedLinear`` and
+    ``_FanoutGroup`` make.  Weight gradients are queued as ``_GroupedLinear`` queues them."""
+
+    @staticmethod
+    def forward(ctx, specs: List[LinearSpec], src: List[int], npass: int, m: int, *tensors):
+        xs = tensors[:m]
+        for x in xs:
+            _req(x, BF16)
+        _one_epilogue(specs)
+        has_bias = specs[0].b is not None
+        ws = [s.w.w16 for s in specs]
+        ins = [xs[j] for j in src]
+        _, outs = _linear_outputs(ins, ws, BF16, False)
+        gemm_group(GEMM_NT, [(x, w, y, s.b.master if has_bias else None, None) for x, w, y, s in zip(ins, ws, outs, specs)],
+                   EPI_BIAS if has_bias else 0)
+        ctx.specs, ctx.src, ctx.npass, ctx.m = specs, src, npass, m
+        ctx.save_for_backward(*xs)
+        return (*outs, *(x.view_as(x) for x in xs for _ in range(npass)))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        specs, src, npass, m = ctx.specs, ctx.src, ctx.npass, ctx.m
+        xs = ctx.saved_tensors
+        n = len(specs)
+        has_bias = specs[0].b is not None
+        ws = [s.w.w16 for s in specs]
+        dys = [_grad_bf16(g) for g in gs[:n]]
+        passes = [[_grad_bf16(g) for g in gs[n + j * npass:n + (j + 1) * npass]] for j in range(m)]
+        for i, s in enumerate(specs):               # the weight gradients: the operands _GroupedLinear queues, in its order
+            if dys[i] is not None and s.w.p.requires_grad:
+                queue_wgrad(dys[i], xs[src[i]], s.w.grad, s.b.grad if has_bias else None)
+        dxs = _chained_input_grads(xs, src, ws, dys, passes)
+        if dxs is None:                             # the launches of the separate nodes
+            parts = [torch.empty_like(xs[src[i]]) if dys[i] is not None else None for i in range(n)]
+            dgrad = [(dys[i], ws[i], parts[i], None, None) for i in range(n) if dys[i] is not None]
+            if dgrad:
+                gemm_group(GEMM_NN, dgrad, 0)
+            # (operand order of fanout_group's sum in MulT: the linears, then the handles with the first one last)
+            dxs = _sum_gradient_groups([[parts[i] for i in range(n) if src[i] == j] + passes[j][1:] + passes[j][:1] for j in range(m)])
+        return (None, None, None, None, *dxs, *([None] * (2 * n)))
+
+
+def _chained_input_grads(xs, src, ws, dys, passes) -> Optional[List[torch.Tensor]]:
+    """``_FanoutLinear``'s input gradients by one chained launch, or None where that launch does not exist: a gradient is
+    missing, an input has more linears than a chain has segments or other than three handles, or the library refuses the
+    shapes (``lib.gemm_chain_available``)."""
+    m = len(xs)
+    if any(g is None for g in dys) or any(len(p) != 3 or any(g is None for g in p) for p in passes):
+        return None
+    chains, sums, dxs = [], [], []
+    for j in range(m):
+        mine = [i for i in range(len(src)) if src[i] == j]
+        if not 0 < len(mine) <= lib.GEMM_CHAIN_MAX_SEGMENTS or any(g.shape != xs[j].shape for g in passes[j]):
+            return None
+        if any(dys[i].shape != (xs[j].shape[0], ws[i].shape[0]) or dys[i].stride(1) != 1 or ws[i].stride(1) != 1 for i in mine):
+            return None
+        s, dx = torch.empty_like(passes[j][0]), torch.empty_like(passes[j][0])
+        chains.append((dx, None, s, [(dys[i], ws[i]) for i in mine]))
+        sums.append(lib.Add3Problem(*(g.data_ptr() for g in passes[j]), s.data_ptr(), s.numel()))
+        dxs.append(dx)
+    if m > lib.ADD3_MAX or m > lib.GEMM_MAX_CHAINS or not gemm_chain_available(chains, EPI_ADD_AUX):
+        return None
+    lib.check(lib.load().mmf_add3_grouped((lib.Add3Problem * m)(*sums), m, lib.stream_ptr()))
+    gemm_chain_group(chains, EPI_ADD_AUX)
+    return dxs
+
+
+def fanout_linear_ok(xs: Sequence[torch.Tensor], items: Sequence[tuple]) -> bool:
+    """whether ``fanout_linear_group`` has its node for these inputs and (input index, LinearSpec) items: bf16 mode, every
+    input a bf16 row matrix that needs a gradient, one launch, no ReLU"""
+    return (_PRECISION != "fp32" and 0 < len(items) <= lib.GEMM_MAX_PROBLEMS
+            and all(x.is_cuda and x.dtype == BF16 and x.requires_grad and x.dim() == 2 for x in xs)
+            and not any(spec.relu for _, spec in items))
+
+
+def fanout_linear_group(xs: Sequence[torch.Tensor], items: Sequence[tuple], npass: int) -> Tuple[List[torch.Tensor], List[List[torch.Tensor]]]:
+    """(``linear_group([(xs[j], spec, None) for j, spec in items])``, ``npass`` further handles on every x) as one node
+    (``_FanoutLinear``); call where ``fanout_linear_ok``."""
+    specs, src = [spec for _, spec in items], [j for j, _ in items]
+    params = [t for s in specs for t in (s.w.p, s.b.p if s.b is not None else None)]
+    flat = _FanoutLinear.apply(specs, src, int(npass), len(xs), *xs, *params)
+    n = len(specs)
+    return list(flat[:n]), [list(flat[n + j * npass:n + (j + 1) * npass]) for j in range(len(xs))]
 
 
 class _MeanPoolCat(torch.autograd.Function):

@@ -178,12 +178,15 @@ class _MHAParams(nn.Module):
 # ------------------------------------------------------------------------------------------------
 def _cross_blocks(blocks: Sequence["CrossModalTransformer"], qs: Sequence[torch.Tensor],
                   kvs: Sequence[torch.Tensor], B: int, Tqs: Sequence[int], Tks: Sequence[int],
-                  p: float = 0.0, ress: Optional[Sequence[torch.Tensor]] = None, norm2: bool = True) -> List[torch.Tensor]:
+                  p: float = 0.0, ress: Optional[Sequence[torch.Tensor]] = None, norm2: bool = True,
+                  proj: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
     """n independent CrossModalTransformer blocks (reference :202-211), one launch per stage.
     qs[i]: bf16 (B*Tq_i, d); kvs[i]: bf16 (B*Tk_i, d); ress[i] (default qs[i]): the query rows as the residual of
     :205 — a separate handle when the caller fans its input out (ops.fanout) to sum the input gradients in one pass.
-    norm2=False: the blocks' outputs BEFORE their second LayerNorm (:209), for a caller that fuses it into what follows."""
-    proj = _cross_in_proj(blocks, qs, kvs)                           # [Q0, KV0, Q1, KV1, ...]
+    norm2=False: the blocks' outputs BEFORE their second LayerNorm (:209), for a caller that fuses it into what follows.
+    proj: the in-projections [Q0, KV0, Q1, KV1, ...] of a caller that made them itself (qs, kvs are then unused; ress is required)."""
+    if proj is None:
+        proj = _cross_in_proj(blocks, qs, kvs)                       # [Q0, KV0, Q1, KV1, ...]
     _tick()
     att = _cross_attention(blocks, proj, B, Tqs, Tks, p)
     _tick()
@@ -345,15 +348,27 @@ class MultimodalTransformer(_FusionBase):
         t, a, v = _as_rows(text_features), _as_rows(audio_features), _as_rows(video_features)
         blocks = [self.text_to_audio, self.text_to_video, self.audio_to_text, self.audio_to_video,
                   self.video_to_text, self.video_to_audio]
-        # every modality's rows are used seven times (2 queries + their residuals, 2 key/value sources, the three-way sum
-        # :156-158): fan them out so that the seven input-gradient contributions are summed by ONE kernel in backward
-        tf, af, vf = ops.fanout_group([t, a, v], 7)
-        qs, kvs = [tf[0], tf[1], af[0], af[1], vf[0], vf[1]], [af[2], vf[2], tf[2], vf[3], tf[3], af[3]]
-        ress = [tf[4], tf[5], af[4], af[5], vf[4], vf[5]]
         Tqs, Tks = [Tt, Tt, Ta, Ta, Tv, Tv], [Ta, Tv, Tt, Tv, Tt, Ta]
-        t, a, v = tf[6], af[6], vf[6]
         mhas = [self.text_self_attn, self.audio_self_attn, self.video_self_attn]
         streams = _MULT_STREAMS > 1 and _depth == 1 and t.is_cuda and not ops.fp32_mode()
+        # every modality's rows are used seven times (2 queries + their residuals, 2 key/value sources, the three-way sum
+        # :156-158).  On one stream the twelve in-projections and the three other handles of each modality are ONE node
+        # (ops.fanout_linear_group): its backward forms each input gradient as one GEMM over the four projections' stacked K
+        # with the pass-through gradients added in its drain.  Otherwise (two chains, fp32 mode, inputs without a gradient) the
+        # rows are fanned out so that the seven input-gradient contributions are summed by ONE kernel in backward.
+        src_q, src_kv = [0, 0, 1, 1, 2, 2], [1, 2, 0, 2, 0, 1]
+        in_items = [it for i, blk in enumerate(blocks)
+                    for it in ((src_q[i], blk.attention.q_spec()), (src_kv[i], blk.attention.kv_spec()))]
+        proj = qs = kvs = None
+        if not streams and ops.fanout_linear_ok([t, a, v], in_items):
+            proj, (tf, af, vf) = ops.fanout_linear_group([t, a, v], in_items, 3)
+            ress = [tf[1], tf[2], af[1], af[2], vf[1], vf[2]]
+            t, a, v = tf[0], af[0], vf[0]
+        else:
+            tf, af, vf = ops.fanout_group([t, a, v], 7)
+            qs, kvs = [tf[0], tf[1], af[0], af[1], vf[0], vf[1]], [af[2], vf[2], tf[2], vf[3], tf[3], af[3]]
+            ress = [tf[4], tf[5], af[4], af[5], vf[4], vf[5]]
+            t, a, v = tf[6], af[6], vf[6]
         # (as the root module only: nested in HierarchicalFusion the branch stream already fills the holes, and the cut
         # there measured slower: hier-seq 2.90 -> 3.24 ms)
         if streams:
@@ -377,7 +392,7 @@ class MultimodalTransformer(_FusionBase):
             pooled_side.record_stream(main)
             pooled_att = torch.cat([pooled_main, pooled_side], dim=1)     # (its backward hands each chain its column block as a view)
         else:
-            pre2 = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress, norm2=False)               # :146-153 up to norm2
+            pre2 = _cross_blocks(blocks, qs, kvs, B, Tqs, Tks, p, ress, norm2=False, proj=proj)    # :146-153 up to norm2
             et, ea, ev = _norm2_sums(blocks, [t, a, v], pre2)                                  # :209, :156-158, one launch
             pooled_att = _self_attention_core(mhas, [et, ea, ev], B, [Tt, Ta, Tv], p, pooled=True)
         # :161-168.  The self-attention outputs are only ever used through their mean over T, and the
