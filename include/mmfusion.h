@@ -145,7 +145,8 @@ int mmf_gemm_last_impl(void);
 /* Generation 7 (gemm7.hip): generation 6's tile on PERSISTENT workgroups — one per CU, each walking the tiles w, w + grid, ... of
  * the launch with its LDS ring running on across tile boundaries (no ring fill and no idle matrix pipe between tiles).  NT / NN
  * with bf16 output, K % 32 == 0, K >= 160, N and the leading dimensions of C / aux multiples of 8, a 16-byte aligned aux, and the
- * flag sets of the fusion step.  Without a bias bit-identical to generation 6; with one the accumulators start from the bias, so
+ * flag sets of the fusion step (alpha != 1 only on the NN ReLU mask, MMF_EPI_MASK_AUX / MMF_EPI_MASK_BITS alone); every other launch
+ * falls back to generation 6, then 2.  Without a bias bit-identical to generation 6; with one the accumulators start from the bias, so
  * outputs may differ from generation 6 by one bf16 ulp on a small fraction of the elements.
  * Tile width: 256 x 256 or 256 x 192, per launch.  Automatic: 192 exactly when the launch's makespan — the longest workgroup's
  * sum of K x width over the tiles the persistent walk gives it — is strictly shorter at 192 than at 256.  Both widths give every

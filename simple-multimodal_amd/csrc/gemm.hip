@@ -8,10 +8,12 @@
 //
 // Kernels (three): gemm2.hip (LDS-DMA ring, 256 x 128 tile, eight waves: the general kernel — any K, small launches),
 // gemm6.hip (256 x 256 tile, one wave per SIMD with 128 x 128 wave tiles, a 32-deep x 4-stage LDS ring, one tile per workgroup: wgrad,
-// and every NT / NN launch the persistent form refuses — f32 output, a flag set it does not instantiate, K < 160, N or a leading
-// dimension of C / aux no multiple of 8) and gemm7.hip (gemm6's tile and ring walked by persistent workgroups, outputs through LDS: the NT / NN
-// launches of the fusion step); gemm6_parts.h holds what the last two share.  Earlier generations — the register-staged 128 x 128
-// kernel and gemm3 (rounds 1-2), gemm4 (256 x 256 ring, eight waves; stream-K) and gemm5 (32-deep ring, two workgroups per CU)
+// and every NT / NN launch the persistent form refuses — f32 output, a flag set it does not instantiate, alpha != 1 anywhere but on the
+// NN ReLU mask, K < 160, N or a leading dimension of C / aux no multiple of 8, an aux that is not 16-byte aligned) and gemm7.hip (gemm6's
+// tile and ring walked by persistent workgroups, outputs through LDS: every NT / NN launch it takes once the automatic choice below has given
+// the launch generation 6); gemm6_parts.h holds what the last two share, gemm_common.h what all three do (epilogue arithmetic, tile order,
+// table fill).  Without a bias generation 7 is bit-identical to generation 6; with one a small fraction of the outputs differ by one bf16 ulp.
+// Earlier generations — the register-staged 128 x 128 kernel and gemm3 (rounds 1-2), gemm4 (256 x 256 ring, eight waves; stream-K) and gemm5 (32-deep ring, two workgroups per CU)
 // (rounds 2-3) — are in git history with their measurements in DESIGN.md section 5; the last two left in round 4, when a same-box
 // A/B of the selection rule without them came out level or ahead on all four workloads (MulT 2.116 -> 2.088 ms, hierarchical
 // 2.75 = 2.75, training step 3.33 -> 3.34, MELD-shaped 1.076 -> 1.070).
@@ -75,6 +77,30 @@ static bool bits_flags_ok(int epilogue) {
   return (epilogue & MMF_EPI_RELU_BITS) ? (epilogue & MMF_EPI_RELU) != 0 : true;
 }
 
+// What the entry points ask of ONE problem, whichever generation takes the launch -> MMF_OK, or the code with the reason in `why`
+// (nullptr: only ask).  mmf_gemm_grouped_ex asks it per problem, the chain form (gemm7.hip) per segment.
+int mmf_gemm_problem_fault(const mmf_gemm_problem& p, int layout, int epilogue, char* why, size_t why_bytes) {
+#define MMF_FAULT(code, ...) do { if (why) snprintf(why, why_bytes, __VA_ARGS__); return (code); } while (0)
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0) MMF_FAULT(MMF_E_SHAPE, "empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+  if (!p.A || !p.B || !p.C) MMF_FAULT(MMF_E_SHAPE, "null operand");
+  if ((epilogue & (MMF_EPI_BIAS | MMF_EPI_COLSUM_A)) && !p.bias) MMF_FAULT(MMF_E_SHAPE, "bias is null");
+  if ((epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX | EPI_BITS)) && !p.aux) MMF_FAULT(MMF_E_SHAPE, "aux is null");
+  // the contiguous extent of each operand must be a multiple of 8 elements (16-B vector loads)
+  const int a_cols = (layout == MMF_GEMM_TN) ? p.M : p.K;
+  const int b_cols = (layout == MMF_GEMM_NT) ? p.K : p.N;
+  if ((a_cols & 7) || (b_cols & 7) || (p.lda & 7) || (p.ldb & 7) || (p.N & 3) || (p.ldc & 3) ||
+      ((epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX)) && (p.ldaux & 3)))
+    MMF_FAULT(MMF_E_ALIGN, "M=%d N=%d K=%d lda=%d ldb=%d ldc=%d ldaux=%d violate the 8-element (operands) / 4-element (output) granularity",
+              p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldaux);
+  if (p.lda < a_cols || p.ldb < b_cols || p.ldc < p.N) MMF_FAULT(MMF_E_SHAPE, "leading dimension smaller than the row");
+  // (aux at 8 bytes: generations 2 and 6 read it in 8-byte pieces; generation 7 asks for 16, mmf_gemm7_supports)
+  if (!mmf_aligned16(p.A) || !mmf_aligned16(p.B) || !mmf_aligned16(p.C) ||
+      (p.bias && !mmf_aligned16(p.bias)) || (p.aux && (reinterpret_cast<uintptr_t>(p.aux) & 7)))
+    MMF_FAULT(MMF_E_ALIGN, "operand pointers must be 16-byte aligned");
+#undef MMF_FAULT
+  return MMF_OK;
+}
+
 extern "C" size_t mmf_gemm_relu_bits_bytes(int M, int N) {
   if (M <= 0 || N <= 0) return 0;
   return (size_t)((M + 31) / 32) * (size_t)((N + 31) / 32) * 64 * sizeof(uint16_t);
@@ -115,28 +141,9 @@ extern "C" int mmf_gemm_grouped_ex(const mmf_gemm_problem* problems, int num_pro
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: RELU_BITS / MASK_BITS exist in generation 7 only and this launch goes to generation %d "
              "(mmf_gemm_relu_bits_available)", impl);
   t_last_impl = impl;
-  for (int i = 0; i < num_problems; ++i) {
-    const mmf_gemm_problem& p = problems[i];
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0)
-      MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: empty problem M=%d N=%d K=%d", i, p.M, p.N, p.K);
-    if (!p.A || !p.B || !p.C) MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: null operand", i);
-    if ((epilogue & (MMF_EPI_BIAS | MMF_EPI_COLSUM_A)) && !p.bias) MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: bias is null", i);
-    if ((epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX | EPI_BITS)) && !p.aux)
-      MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: aux is null", i);
-    // the contiguous extent of each operand must be a multiple of 8 elements (16-B vector loads)
-    const int a_cols = (layout == MMF_GEMM_TN) ? p.M : p.K;
-    const int b_cols = (layout == MMF_GEMM_NT) ? p.K : p.N;
-    if ((a_cols & 7) || (b_cols & 7) || (p.lda & 7) || (p.ldb & 7) || (p.N & 3) || (p.ldc & 3) ||
-        ((epilogue & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX)) && (p.ldaux & 3)))
-      MMF_FAIL(MMF_E_ALIGN, "mmf_gemm_grouped[%d]: M=%d N=%d K=%d lda=%d ldb=%d ldc=%d ldaux=%d violate "
-               "the 8-element (operands) / 4-element (output) granularity", i, p.M, p.N, p.K, p.lda,
-               p.ldb, p.ldc, p.ldaux);
-    if (p.lda < a_cols || p.ldb < b_cols || p.ldc < p.N)
-      MMF_FAIL(MMF_E_SHAPE, "mmf_gemm_grouped[%d]: leading dimension smaller than the row", i);
-    if (!mmf_aligned16(p.A) || !mmf_aligned16(p.B) || !mmf_aligned16(p.C) ||
-        (p.bias && !mmf_aligned16(p.bias)) || (p.aux && (reinterpret_cast<uintptr_t>(p.aux) & 7)))
-      MMF_FAIL(MMF_E_ALIGN, "mmf_gemm_grouped[%d]: operand pointers must be 16-byte aligned", i);
-  }
+  char why[256];
+  for (int i = 0; i < num_problems; ++i)
+    if (const int e = mmf_gemm_problem_fault(problems[i], layout, epilogue, why, sizeof why)) MMF_FAIL(e, "mmf_gemm_grouped[%d]: %s", i, why);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (impl == 2) return mmf_gemm2_launch(problems, num_problems, layout, epilogue, out_f32, extra, s);
   if (impl == 6) return mmf_gemm6_launch(problems, num_problems, layout, epilogue, out_f32, extra, s);

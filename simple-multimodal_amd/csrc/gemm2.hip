@@ -18,7 +18,7 @@
 //             share A/B panels in that XCD's L2 and every XCD gets the same mix of long and short tiles;
 //   db        wgrad's fused bias gradient is one extra MFMA per (k-substep, m-tile) against an
 //             all-ones fragment — no extra LDS or HBM traffic.
-#include "mmf_internal.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -41,6 +41,9 @@ struct GemmArgs {
   int tile_start[MMF_GEMM_MAX_PROBLEMS + 1];
   mmf_gemm_problem p[MMF_GEMM_MAX_PROBLEMS];
 };
+// the kernels read these at fixed kernel-argument offsets (the head of gemm6_parts.h's table; no orig[])
+static_assert(offsetof(GemmArgs, alpha) == 12 && offsetof(GemmArgs, rng_state) == 24 && offsetof(GemmArgs, tile_start) == 32 &&
+              offsetof(GemmArgs, p) == 232 && sizeof(GemmArgs) == 232 + sizeof(mmf_gemm_problem) * MMF_GEMM_MAX_PROBLEMS, "GemmArgs layout (generation 2)");
 
 __device__ __forceinline__ int kc_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 __device__ __forceinline__ int kr_swz(int krow) { return ((krow & 3) << 2) | ((krow >> 2) & 3); }
@@ -114,18 +117,8 @@ void gemm2_grouped_kernel(const GemmArgs args, const int total_tiles) {
   while (pi + 1 < args.nprob && bid >= args.tile_start[pi + 1]) ++pi;
   const mmf_gemm_problem& P = args.p[pi];
   const int M = P.M, N = P.N, K = P.K;
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int t = bid - args.tile_start[pi];
-  // Super-rows of GROUP_M m-tiles, n fastest across a super-row: the ~32 tiles an XCD runs at the same
-  // time then form a GROUP_M x 4 block of the output and share A and B panels in that XCD's L2; with a
-  // plain m-fastest order they would be 32 different m-tiles of one n-tile (no A reuse: every A slice
-  // would stream from the Infinity Cache at ~1/2 the L2 rate).
-  constexpr int GROUP_M = 8;
-  const int grp = t / (GROUP_M * tiles_n), rem = t % (GROUP_M * tiles_n);
-  const int gm = min(GROUP_M, tiles_m - grp * GROUP_M);
-  const int m0 = (grp * GROUP_M + rem % gm) * BM;
-  const int n0 = (rem / gm) * BN;
-  (void)tiles_n;
+  int m0, n0;
+  tile_origin<BM, BN>(P, bid - args.tile_start[pi], m0, n0);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -261,7 +254,9 @@ void gemm2_grouped_kernel(const GemmArgs args, const int total_tiles) {
   const unsigned drop_key = do_drop ? mmf_rng_key(*args.rng_state, args.site, (unsigned)pi) : 0u;
   const float drop_scale = do_drop ? mmf_inv_keep(args.drop_thresh) : 1.f;
   const float alpha = args.alpha;
-  auto finish = [&](f32x4_t v, int m, int n) -> f32x4_t {  // bias -> relu -> dropout -> mask -> alpha -> residual
+  // bias, then gemm_common.h's statement (MMF_EPI_QUAD_RT) in this kernel's own text: the aux pair is loaded under the aux flags' branch, which holds the
+  // mask, alpha and residual steps.  Through the shared text all six kernels became other code, 235 to 513 lines shorter (profiles/gemm_shared_parts.txt).
+  auto finish = [&](f32x4_t v, int m, int n) -> f32x4_t {
     if (epi & MMF_EPI_BIAS) v += *reinterpret_cast<const f32x4_t*>(P.bias + n);
     if (epi & MMF_EPI_RELU) {
 #pragma unroll
@@ -357,26 +352,12 @@ void launch(const GemmArgs& a, int total, int out_f32, hipStream_t s) {
 int mmf_gemm2_launch(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue,
                      int out_f32, const mmf_gemm_extra* extra, hipStream_t s) {
   GemmArgs a;
-  a.nprob = num_problems;
-  a.epi = epilogue;
-  a.xcd_granule = mmf_xcd_granule();
-  a.alpha = extra ? extra->alpha : 1.f;
-  a.drop_thresh = extra ? mmf_drop_thresh(extra->dropout_p) : 0u;
-  a.site = extra ? extra->site : 0u;
-  a.rng_state = extra ? reinterpret_cast<const unsigned long long*>(extra->rng_state) : nullptr;
-  int total = 0;
+  mmf_gemm_table_begin(a, epilogue, extra);
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[i];
-    // 32-bit byte offsets inside the buffer descriptors
-    const size_t a_bytes = (size_t)(layout == MMF_GEMM_TN ? p.K : p.M) * p.lda * 2;
-    const size_t b_bytes = (size_t)(layout == MMF_GEMM_NT ? p.N : p.K) * p.ldb * 2;
-    if (a_bytes >= 0x7fffffffull || b_bytes >= 0x7fffffffull)
-      MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped[%d]: operand larger than 2 GiB", i);
-    a.tile_start[i] = total;
-    total += ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    a.p[i] = p;
+    if (const int e = mmf_gemm_table_add(a, p, ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN), i, layout, false)) return e;
   }
-  a.tile_start[num_problems] = total;
+  const int total = a.tile_start[num_problems];
   switch (layout) {
     case MMF_GEMM_NT: launch<false, false>(a, total, out_f32, s); break;
     case MMF_GEMM_NN: launch<false, true>(a, total, out_f32, s); break;

@@ -40,7 +40,7 @@ __device__ __forceinline__ void gemm6_body(const GemmArgs& args, const int total
   while (pi + 1 < args.nprob && bid >= args.tile_start[pi + 1]) ++pi;
   const mmf_gemm_problem& P = args.p[pi];
   int m0, n0;
-  tile_origin(P, bid - args.tile_start[pi], m0, n0);
+  tile_origin<BM, BN>(P, bid - args.tile_start[pi], m0, n0);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -281,25 +281,12 @@ int mmf_gemm6_launch(const mmf_gemm_problem* problems, int num_problems, int lay
   if (!mmf_gemm6_supports_epi(epilogue, out_f32))
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: the one-wave-per-SIMD kernel has no aux epilogue with f32 output");
   GemmArgs a;
-  a.nprob = num_problems;
-  a.epi = epilogue;
-  a.xcd_granule = mmf_xcd_granule();
-  a.alpha = extra ? extra->alpha : 1.f;
-  a.drop_thresh = extra ? mmf_drop_thresh(extra->dropout_p) : 0u;
-  a.site = extra ? extra->site : 0u;
-  a.rng_state = extra ? reinterpret_cast<const unsigned long long*>(extra->rng_state) : nullptr;
-  int total = 0;
+  mmf_gemm_table_begin(a, epilogue, extra);
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[i];
-    const size_t a_bytes = (size_t)(layout == MMF_GEMM_TN ? p.K : p.M) * p.lda * 2;
-    const size_t b_bytes = (size_t)(layout == MMF_GEMM_NT ? p.N : p.K) * p.ldb * 2;
-    if (a_bytes >= 0x7fffffffull || b_bytes >= 0x7fffffffull)
-      MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped[%d]: operand larger than 2 GiB", i);
-    a.tile_start[i] = total;
-    total += ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    a.p[i] = p;
+    if (const int e = mmf_gemm_table_add(a, p, ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN), i, layout, false)) return e;
   }
-  a.tile_start[num_problems] = total;
+  const int total = a.tile_start[num_problems];
   switch (layout) {
     case MMF_GEMM_NT: launch<false, false>(a, total, out_f32, s); break;
     case MMF_GEMM_NN: launch<false, true>(a, total, out_f32, s); break;

@@ -1,7 +1,8 @@
 // Parts shared by the one-wave-per-SIMD GEMM kernels (gemm6.hip: one tile per workgroup; gemm7.hip: persistent workgroups):
-// the kernel-argument table, fragment reads and their LDS addressing, the LDS-DMA source map, tile order and the epilogue.
+// the kernel-argument table, fragment reads and their LDS addressing, the LDS-DMA source map and the tile's epilogue loop.  The element
+// arithmetic of the epilogue, the tile order and the table's fill are gemm_common.h's (shared with gemm2.hip).
 #pragma once
-#include "mmf_internal.h"
+#include "gemm_common.h"
 #include "lds_image.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -28,6 +29,9 @@ struct GemmArgs {
   short orig[MMF_GEMM_MAX_PROBLEMS];
   mmf_gemm_problem p[MMF_GEMM_MAX_PROBLEMS];
 };
+// the kernels read these at fixed kernel-argument offsets (the head of gemm2.hip's table, then orig[])
+static_assert(offsetof(GemmArgs, alpha) == 12 && offsetof(GemmArgs, rng_state) == 24 && offsetof(GemmArgs, tile_start) == 32 && offsetof(GemmArgs, orig) == 228 &&
+              offsetof(GemmArgs, p) == 328 && sizeof(GemmArgs) == 328 + sizeof(mmf_gemm_problem) * MMF_GEMM_MAX_PROBLEMS, "GemmArgs layout (generations 6, 7)");
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef int i32x4_t __attribute__((ext_vector_type(4)));      // a buffer descriptor as the "s" operand of an LDS-DMA statement
@@ -152,20 +156,6 @@ __device__ __forceinline__ unsigned piece_voff(int p, int ld, int lane) {
   return (unsigned)(row * ld * 2 + ch * 16);
 }
 
-// tile t of problem P -> (m0, n0): super-rows of GROUP_M m-tiles, n fastest across a super-row.  TBN: the tile width (gemm7:
-// 256 or 192)
-template <int TBN = BN>
-__device__ __forceinline__ void tile_origin(const mmf_gemm_problem& P, const int t, int& m0, int& n0) {
-  const int tiles_m = (P.M + BM - 1) / BM, tiles_n = (P.N + TBN - 1) / TBN;
-  // super-rows of 8 m-tiles.  (Round 4 tried the height that makes an XCD's 32 concurrent tiles touch the fewest operand panels — 32 / tiles_n
-  // for narrow outputs, 11 x 3 instead of 8 x 3 + 8 x 1 at N = 768: the step got SLOWER, 2.027 -> 2.052 ms same box.)
-  constexpr int GROUP_M = 8;
-  const int grp = t / (GROUP_M * tiles_n), rem = t % (GROUP_M * tiles_n);
-  const int gm = min(GROUP_M, tiles_m - grp * GROUP_M);
-  m0 = (grp * GROUP_M + rem % gm) * BM;
-  n0 = (rem / gm) * TBN;
-}
-
 // epilogue: lane owns C[m][n .. n+3] for m = m_base + 32 tm + (l & 31), n = n_base + 32 tn + 8 g + 4 (l >> 5).
 // A wave that owns its SIMD has nobody to cover a load's round trip, and the compiler may not move a load above an earlier store
 // to C: the first form of this epilogue (gemm4's: bias / aux / old-C loads next to each use) spent ~35 us per tile in 64 exposed
@@ -199,41 +189,14 @@ __device__ __forceinline__ void tile_epilogue_mode(const GemmArgs& args, const m
       bv[tn][g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
       if ((epi & MMF_EPI_BIAS) && ncol(tn, g) < N) bv[tn][g] = *reinterpret_cast<const f32x4_t*>(P.bias + ncol(tn, g));
     }
-  auto finish = [&](f32x4_t v, const f32x4_t& b, const u32x2_t& a, int m, int n) -> f32x4_t {  // bias -> relu -> dropout -> mask -> alpha -> residual
-    if constexpr (CT >= 0) {                                // compile-time flag set: bias -> relu -> mask -> residual
+  auto finish = [&](f32x4_t v, const f32x4_t& b, const u32x2_t& a, int m, int n) -> f32x4_t {  // bias, then the shared statement
+    if constexpr (CT >= 0) {                                // compile-time flag set: no dropout, alpha = 1
       if constexpr (CT & MMF_EPI_BIAS) v += b;
-      if constexpr (CT & MMF_EPI_RELU) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      if constexpr (CT & (MMF_EPI_MASK_AUX | MMF_EPI_ADD_AUX)) {
-        const float a0 = bf16lo(a[0]), a1 = bf16hi(a[0]), a2 = bf16lo(a[1]), a3 = bf16hi(a[1]);
-        if constexpr (CT & MMF_EPI_MASK_AUX) {
-          v[0] = a0 > 0.f ? v[0] : 0.f; v[1] = a1 > 0.f ? v[1] : 0.f;
-          v[2] = a2 > 0.f ? v[2] : 0.f; v[3] = a3 > 0.f ? v[3] : 0.f;
-        } else {
-          v[0] += a0; v[1] += a1; v[2] += a2; v[3] += a3;
-        }
-      }
+      MMF_EPI_QUAD_CT(CT, v, a, (unsigned)m * (unsigned)N + (unsigned)n, drop_key, args.drop_thresh, drop_scale, alpha);
       return v;
     }
     v += b;
-    if (epi & MMF_EPI_RELU) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    if (do_drop) {
-      const unsigned idx = (unsigned)m * (unsigned)N + (unsigned)n;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = mmf_keep(drop_key, idx + e, args.drop_thresh) ? v[e] * drop_scale : 0.f;
-    }
-    const float a0 = bf16lo(a[0]), a1 = bf16hi(a[0]), a2 = bf16lo(a[1]), a3 = bf16hi(a[1]);
-    if (epi & MMF_EPI_MASK_AUX) {
-      v[0] = a0 > 0.f ? v[0] : 0.f; v[1] = a1 > 0.f ? v[1] : 0.f;
-      v[2] = a2 > 0.f ? v[2] : 0.f; v[3] = a3 > 0.f ? v[3] : 0.f;
-    }
-    v *= alpha;
-    if (epi & MMF_EPI_ADD_AUX) { v[0] += a0; v[1] += a1; v[2] += a2; v[3] += a3; }
+    MMF_EPI_QUAD_RT(epi, do_drop, v, a, (unsigned)m * (unsigned)N + (unsigned)n, drop_key, args.drop_thresh, drop_scale, alpha);
     return v;
   };
   const bool wide = (N & 7) == 0 && (P.ldc & 7) == 0;

@@ -75,7 +75,7 @@ __device__ __forceinline__ void locate_tile(const GemmArgs& args, const int tota
   }
   const mmf_gemm_problem& P = args.p[pi];
   int m0, n0;
-  tile_origin<Form<TN>::BNT>(P, t, m0, n0);
+  tile_origin<BM, Form<TN>::BNT>(P, t, m0, n0);
   m0 = to_sgpr(m0);
   n0 = to_sgpr(n0);
   d.pi = pi; d.m0 = m0; d.n0 = n0;
@@ -199,25 +199,9 @@ __device__ __forceinline__ void drain_tile(const GemmArgs& args, const int pi, c
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4_t v = {acc[tn][tm][4 * g], acc[tn][tm][4 * g + 1], acc[tn][tm][4 * g + 2], acc[tn][tm][4 * g + 3]};
-        if constexpr (CT & MMF_EPI_RELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if constexpr (DROP) {
-          const unsigned idx = (unsigned)(mb + 32 * tm + r) * (unsigned)P.N + (unsigned)(nb + 32 * tn + 8 * g + 4 * h);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = mmf_keep(drop_key, idx + e, args.drop_thresh) ? v[e] * drop_scale : 0.f;
-        }
-        if constexpr (AUX) {
-          const u32x2_t a = axv[tn][g];
-          const float a0 = bf16lo(a[0]), a1 = bf16hi(a[0]), a2 = bf16lo(a[1]), a3 = bf16hi(a[1]);
-          if constexpr (CT & MMF_EPI_MASK_AUX) {
-            v[0] = a0 > 0.f ? v[0] * alpha : 0.f; v[1] = a1 > 0.f ? v[1] * alpha : 0.f;
-            v[2] = a2 > 0.f ? v[2] * alpha : 0.f; v[3] = a3 > 0.f ? v[3] * alpha : 0.f;
-          } else {
-            v[0] += a0; v[1] += a1; v[2] += a2; v[3] += a3;
-          }
-        }
+        // (the bit forms are not part of the shared statement: MMF_EPI_MASK_BITS applies its mask below, where MMF_EPI_MASK_AUX does inside)
+        MMF_EPI_QUAD_CT(CT, v, axv[tn][g], (unsigned)(mb + 32 * tm + r) * (unsigned)P.N + (unsigned)(nb + 32 * tn + 8 * g + 4 * h),
+                        drop_key, args.drop_thresh, drop_scale, alpha);
         if constexpr (MASK_BITS) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {                         // bit ? v * alpha : +0, the bit spread over the word as a mask
@@ -573,7 +557,7 @@ __device__ __forceinline__ void gemm7_body(const GemmArgs& args, const int total
   vm_wait<0>();                       // the zero-range refills behind the last tile
 }
 
-template <bool B_KR, int CT, int TN, bool CHAIN = false>
+template <bool B_KR, int CT, int TN, bool CHAIN>
 __global__ __launch_bounds__(NTHREADS, 1)
 void gemm7_persistent_kernel(const GemmArgs args, const int total_tiles) {
   // the ring and, behind it, one 8-KiB output staging region per wave: all 160 KiB of the CU at TN = 4, 144 KiB at TN = 3
@@ -581,52 +565,40 @@ void gemm7_persistent_kernel(const GemmArgs args, const int total_tiles) {
   gemm7_body<B_KR, CT, TN, CHAIN>(args, total_tiles, smem);
 }
 
-// the (layout, flag set) pairs of the fusion step's NT / NN launches: in-projections (NT, bias), FFN1 (NT, bias + ReLU), out-projection
-// and FFN2 (NT, bias + residual), plain NT, dgrads (NN, none), dH (NN, ReLU mask), dX (NN, residual gradient)
-template <bool B_KR, int CT>
+// The instantiated forms, one line each: the (layout, flag set) pairs of the fusion step's NT / NN launches and of the chain form (NN:
+// the input gradient summed over the linears that read one input).  A line answers "is there such a form" and, given a table (a), launches it.
+template <bool B_KR, int CT, bool CHAIN>
 void launch7(const GemmArgs& a, int total, int grid, int tile_n, hipStream_t s) {
-  if (tile_n == 192) hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT, 3>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
-  else               hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT, 4>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
+  if (tile_n == 192) hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT, 3, CHAIN>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
+  else               hipLaunchKernelGGL((gemm7_persistent_kernel<B_KR, CT, 4, CHAIN>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
 }
-// a == nullptr: only ask
-bool launch7_select(int layout, int eflags, const GemmArgs* a, int total, int grid, hipStream_t s, int tile_n = 256) {
-  if (layout == MMF_GEMM_NT) {
-    if (eflags == 0)                                      { if (a) launch7<false, 0>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == MMF_EPI_BIAS)                           { if (a) launch7<false, MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == (MMF_EPI_BIAS | MMF_EPI_RELU))          { if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == (MMF_EPI_BIAS | MMF_EPI_ADD_AUX))       { if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == (MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT)) {       // FFN hidden layer in training mode
-      if (a) launch7<false, MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s);
-      return true;
-    }
-    // the ReLU forms that also write the keep-mask as bits (FFN hidden layer of a forward that will be differentiated)
-    constexpr int RB = MMF_EPI_RELU | MMF_EPI_RELU_BITS;
-    if (eflags == RB)                                     { if (a) launch7<false, RB>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == (RB | MMF_EPI_BIAS))                    { if (a) launch7<false, RB | MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == (RB | MMF_EPI_DROPOUT))                 { if (a) launch7<false, RB | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == (RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT))  { if (a) launch7<false, RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT>(*a, total, grid, tile_n, s); return true; }
-  } else if (layout == MMF_GEMM_NN) {
-    if (eflags == 0)                                      { if (a) launch7<true, 0>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == MMF_EPI_BIAS)                           { if (a) launch7<true, MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }   // (the chain form's twin)
-    if (eflags == MMF_EPI_MASK_AUX)                      { if (a) launch7<true, MMF_EPI_MASK_AUX>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == MMF_EPI_MASK_BITS)                      { if (a) launch7<true, MMF_EPI_MASK_BITS>(*a, total, grid, tile_n, s); return true; }
-    if (eflags == MMF_EPI_ADD_AUX)                        { if (a) launch7<true, MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
+#define MMF_G7_FORM(LAYOUT, CHAIN, FLAGS)                                                        \
+  if (layout == (LAYOUT) && chain == (CHAIN) && eflags == (FLAGS)) {                             \
+    if (a) launch7<(LAYOUT) == MMF_GEMM_NN, (FLAGS), CHAIN>(*a, total, grid, tile_n, s);         \
+    return true;                                                                                 \
   }
+constexpr int RB = MMF_EPI_RELU | MMF_EPI_RELU_BITS;           // the ReLU forms that also write the keep-mask as bits
+bool launch7_select(int layout, int eflags, bool chain, const GemmArgs* a = nullptr, int total = 0, int grid = 0, hipStream_t s = nullptr, int tile_n = 256) {
+  MMF_G7_FORM(MMF_GEMM_NT, false, 0)                                                        // plain NT
+  MMF_G7_FORM(MMF_GEMM_NT, false, MMF_EPI_BIAS)                                             // in-projections
+  MMF_G7_FORM(MMF_GEMM_NT, false, MMF_EPI_BIAS | MMF_EPI_RELU)                              // FFN1
+  MMF_G7_FORM(MMF_GEMM_NT, false, MMF_EPI_BIAS | MMF_EPI_ADD_AUX)                           // out-projection and FFN2 (residual)
+  MMF_G7_FORM(MMF_GEMM_NT, false, MMF_EPI_BIAS | MMF_EPI_RELU | MMF_EPI_DROPOUT)            // FFN hidden layer in training mode
+  MMF_G7_FORM(MMF_GEMM_NT, false, RB)                                                       // FFN hidden layer of a forward that will be
+  MMF_G7_FORM(MMF_GEMM_NT, false, RB | MMF_EPI_BIAS)                                        // differentiated
+  MMF_G7_FORM(MMF_GEMM_NT, false, RB | MMF_EPI_DROPOUT)
+  MMF_G7_FORM(MMF_GEMM_NT, false, RB | MMF_EPI_BIAS | MMF_EPI_DROPOUT)
+  MMF_G7_FORM(MMF_GEMM_NN, false, 0)                                                        // dgrads
+  MMF_G7_FORM(MMF_GEMM_NN, false, MMF_EPI_BIAS)                                             // (the chain form's twin)
+  MMF_G7_FORM(MMF_GEMM_NN, false, MMF_EPI_MASK_AUX)                                         // dH (ReLU mask)
+  MMF_G7_FORM(MMF_GEMM_NN, false, MMF_EPI_MASK_BITS)
+  MMF_G7_FORM(MMF_GEMM_NN, false, MMF_EPI_ADD_AUX)                                          // dX (residual gradient)
+  MMF_G7_FORM(MMF_GEMM_NN, true, 0)
+  MMF_G7_FORM(MMF_GEMM_NN, true, MMF_EPI_BIAS)
+  MMF_G7_FORM(MMF_GEMM_NN, true, MMF_EPI_ADD_AUX)
   return false;
 }
-// the chain form's flag sets (NN: the input gradient summed over the linears that read one input); a == nullptr: only ask
-template <int CT>
-void launch7_chain(const GemmArgs& a, int total, int grid, int tile_n, hipStream_t s) {
-  if (tile_n == 192) hipLaunchKernelGGL((gemm7_persistent_kernel<true, CT, 3, true>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
-  else               hipLaunchKernelGGL((gemm7_persistent_kernel<true, CT, 4, true>), dim3(grid), dim3(NTHREADS), 0, s, a, total);
-}
-bool launch7_chain_select(int layout, int eflags, const GemmArgs* a, int total, int grid, hipStream_t s, int tile_n = 256) {
-  if (layout != MMF_GEMM_NN) return false;
-  if (eflags == 0)               { if (a) launch7_chain<0>(*a, total, grid, tile_n, s); return true; }
-  if (eflags == MMF_EPI_BIAS)    { if (a) launch7_chain<MMF_EPI_BIAS>(*a, total, grid, tile_n, s); return true; }
-  if (eflags == MMF_EPI_ADD_AUX) { if (a) launch7_chain<MMF_EPI_ADD_AUX>(*a, total, grid, tile_n, s); return true; }
-  return false;
-}
+#undef MMF_G7_FORM
 }  // namespace
 
 static int g_persistent_wgs = [] { const char* e = getenv("MMF_GEMM7_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
@@ -710,17 +682,21 @@ extern "C" int mmf_gemm7_tile_n(const mmf_gemm_problem* problems, int num_proble
   return pick_tile_n(problems, order, num_problems, workgroups > 0 ? workgroups : persistent_grid_cap());
 }
 
+// What generation 7 takes of ONE problem (mmf_gemm7_supports asks it per problem, the chain form per segment): the ring's K, outputs and
+// aux rows in 8-column granularity, a 16-byte aligned aux; with the bit forms aux is the bit buffer (no ldaux) and has to be there.
+static bool gemm7_takes(const mmf_gemm_problem& p, int epilogue) {
+  const bool bits = (epilogue & (MMF_EPI_RELU_BITS | MMF_EPI_MASK_BITS)) != 0;
+  if (p.K % BK || p.K < (NS + 1) * BK || (p.N & 7) || (p.ldc & 7)) return false;
+  if (p.aux && ((!bits && (p.ldaux & 7)) || !mmf_aligned16(p.aux))) return false;
+  return !bits || p.aux;
+}
 // whether the persistent kernel can take this launch (gemm.hip asks before selecting it)
 bool mmf_gemm7_supports(const mmf_gemm_problem* problems, int num_problems, int layout, int epilogue, int out_f32, const mmf_gemm_extra* extra) {
-  if (out_f32 || !launch7_select(layout, epilogue, nullptr, 0, 0, nullptr)) return false;
+  if (out_f32 || !launch7_select(layout, epilogue, false)) return false;
   if (extra && extra->alpha != 1.f && !(layout == MMF_GEMM_NN && (epilogue == MMF_EPI_MASK_AUX || epilogue == MMF_EPI_MASK_BITS))) return false;   // alpha rides on the mask only
-  const bool bits = (epilogue & (MMF_EPI_RELU_BITS | MMF_EPI_MASK_BITS)) != 0;      // aux is a bit buffer: no ldaux
   if ((epilogue & MMF_EPI_DROPOUT) && !(extra && extra->rng_state)) return false;
-  for (int i = 0; i < num_problems; ++i) {
-    const mmf_gemm_problem& p = problems[i];
-    if (p.K % BK || p.K < (NS + 1) * BK || (p.N & 7) || (p.ldc & 7) || (p.aux && ((!bits && (p.ldaux & 7)) || !mmf_aligned16(p.aux)))) return false;
-    if (bits && !p.aux) return false;
-  }
+  for (int i = 0; i < num_problems; ++i)
+    if (!gemm7_takes(problems[i], epilogue)) return false;
   return true;
 }
 
@@ -729,41 +705,27 @@ int mmf_gemm7_launch(const mmf_gemm_problem* problems, int num_problems, int lay
   if (!mmf_gemm7_supports(problems, num_problems, layout, epilogue, out_f32, extra))
     MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped: the persistent kernel takes NT / NN launches with bf16 output, K %% 32 == 0, K >= %d, N and the "
              "leading dimensions of C / aux multiples of 8, and the flag sets of the fusion step (alpha only with the NN ReLU mask)", (NS + 1) * BK);
-  GemmArgs a;
-  a.nprob = num_problems;
-  a.epi = epilogue;
-  a.xcd_granule = mmf_xcd_granule();
-  a.alpha = extra ? extra->alpha : 1.f;
-  a.drop_thresh = (extra && (epilogue & MMF_EPI_DROPOUT)) ? mmf_drop_thresh(extra->dropout_p) : 0u;
-  a.site = extra ? extra->site : 0u;
-  a.rng_state = extra ? reinterpret_cast<const unsigned long long*>(extra->rng_state) : nullptr;
-  int total = 0;
   int order[MMF_GEMM_MAX_PROBLEMS];
   sort_by_k(problems, num_problems, order);
   const int cap = persistent_grid_cap();
   const int tile_n = g_tile_n ? g_tile_n : pick_tile_n(problems, order, num_problems, cap);
+  GemmArgs a;
+  mmf_gemm_table_begin(a, epilogue, extra);
   for (int i = 0; i < num_problems; ++i) {
     const mmf_gemm_problem& p = problems[order[i]];
-    const size_t a_bytes = (size_t)p.M * p.lda * 2;
-    const size_t b_bytes = (size_t)(layout == MMF_GEMM_NT ? p.N : p.K) * p.ldb * 2;
-    const bool bits = (epilogue & (MMF_EPI_RELU_BITS | MMF_EPI_MASK_BITS)) != 0;
-    const size_t c_bytes = (size_t)p.M * p.ldc * 2, x_bytes = bits ? mmf_gemm_relu_bits_bytes(p.M, p.N) : p.aux ? (size_t)p.M * p.ldaux * 2 : 0;
-    if (a_bytes >= 0x7fffffffull || b_bytes >= 0x7fffffffull || c_bytes >= 0x7fffffffull || x_bytes >= 0x7fffffffull)
-      MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_gemm_grouped[%d]: operand larger than 2 GiB", i);
-    a.tile_start[i] = total;
-    total += tiles_of(p, tile_n);
-    a.p[i] = p;
+    if (const int e = mmf_gemm_table_add(a, p, tiles_of(p, tile_n), order[i], layout, true)) return e;
     a.orig[i] = (short)order[i];
   }
-  a.tile_start[num_problems] = total;
-  const int grid = total < cap ? total : cap;
+  const int total = a.tile_start[num_problems], grid = total < cap ? total : cap;
   t_last_tile_n = tile_n;
-  launch7_select(layout, epilogue, &a, total, grid, s, tile_n);
+  launch7_select(layout, epilogue, false, &a, total, grid, s, tile_n);
   MMF_CHECK_LAUNCH("mmf_gemm_grouped(v7)");
   return MMF_OK;
 }
 
 // ---- K-segment chains (mmf_gemm_grouped_chain) ------------------------------------------------------------------------------------------
+int mmf_gemm_problem_fault(const mmf_gemm_problem& p, int layout, int epilogue, char* why, size_t why_bytes);   // gemm.hip: the entry points' rules
+
 namespace {
 static_assert(MMF_GEMM_MAX_CHAINS * MMF_GEMM_CHAIN_MAX_SEGMENTS <= MMF_GEMM_MAX_PROBLEMS, "a launch's segments fill GemmArgs::p at most");
 // the chains as the walk and pick_tile_n see them: one problem of K = the sum of the segments' K each
@@ -775,21 +737,29 @@ void chains_as_problems(const mmf_gemm_chain* chains, int n, mmf_gemm_problem* o
     for (int j = 0; j < chains[i].num_segments; ++j) out[i].K += chains[i].seg[j].K;
   }
 }
+// a chain's segments as the problems the kernel walks -> their number.  bias and aux only under their flags: what the launch does not read is not looked at
+int chain_segments(const mmf_gemm_chain& c, int epilogue, mmf_gemm_problem* out) {
+  for (int j = 0; j < c.num_segments; ++j) {
+    const mmf_gemm_segment& g = c.seg[j];
+    out[j] = mmf_gemm_problem{g.A, g.B, c.C, (epilogue & MMF_EPI_BIAS) ? c.bias : nullptr, (epilogue & MMF_EPI_ADD_AUX) ? c.aux : nullptr,
+                              c.M, c.N, g.K, g.lda, g.ldb, c.ldc, c.ldaux};
+  }
+  return c.num_segments;
+}
+// What is about chains: their number, a chain's number of segments, a residual of the output's shape.  Every segment is a problem
+// the entry points' rules hold for, that generation 7 takes, and whose A, B, C and aux fit the drain's and the ring's descriptors.
 bool chain_shapes_ok(const mmf_gemm_chain* chains, int n, int epilogue) {
   if (!chains || n < 1 || n > MMF_GEMM_MAX_CHAINS) return false;
   for (int i = 0; i < n; ++i) {
     const mmf_gemm_chain& c = chains[i];
-    if (c.num_segments < 1 || c.num_segments > MMF_GEMM_CHAIN_MAX_SEGMENTS || c.M <= 0 || c.N <= 0) return false;
-    if (!c.C || !mmf_aligned16(c.C) || (c.N & 7) || (c.ldc & 7) || c.ldc < c.N || (size_t)c.M * c.ldc * 2 >= 0x7fffffffull) return false;
-    if ((epilogue & MMF_EPI_BIAS) && (!c.bias || !mmf_aligned16(c.bias))) return false;
-    if ((epilogue & MMF_EPI_ADD_AUX) &&
-        (!c.aux || !mmf_aligned16(c.aux) || (c.ldaux & 7) || c.ldaux < c.N || (size_t)c.M * c.ldaux * 2 >= 0x7fffffffull)) return false;
-    for (int j = 0; j < c.num_segments; ++j) {
-      const mmf_gemm_segment& g = c.seg[j];
-      if (!g.A || !g.B || !mmf_aligned16(g.A) || !mmf_aligned16(g.B)) return false;
-      if (g.K % BK || g.K < (NS + 1) * BK || (g.lda & 7) || (g.ldb & 7) || g.lda < g.K || g.ldb < c.N) return false;
-      if ((size_t)c.M * g.lda * 2 >= 0x7fffffffull || (size_t)g.K * g.ldb * 2 >= 0x7fffffffull) return false;
-    }
+    if (c.num_segments < 1 || c.num_segments > MMF_GEMM_CHAIN_MAX_SEGMENTS) return false;
+    if ((epilogue & MMF_EPI_ADD_AUX) && c.ldaux < c.N) return false;
+    mmf_gemm_problem seg[MMF_GEMM_CHAIN_MAX_SEGMENTS];
+    chain_segments(c, epilogue, seg);
+    for (int j = 0; j < c.num_segments; ++j)
+      if (mmf_gemm_problem_fault(seg[j], MMF_GEMM_NN, epilogue, nullptr, 0) != MMF_OK || !gemm7_takes(seg[j], epilogue) ||
+          !mmf_gemm_descriptors_fit(seg[j], MMF_GEMM_NN, epilogue, true))
+        return false;
   }
   return true;
 }
@@ -803,10 +773,9 @@ extern "C" int mmf_gemm7_chain_tile_n(const mmf_gemm_chain* chains, int num_chai
   return mmf_gemm7_tile_n(sums, num_chains, workgroups);
 }
 
-// whether the persistent kernel's chain form takes this launch: NN, the flag sets none / bias / residual, every segment's K a multiple
-// of 32 and >= (NS + 1) * 32, and the alignment rules of mmf_gemm7_supports
+// whether the persistent kernel's chain form takes this launch: an instantiated form, every segment a problem generation 7 takes
 bool mmf_gemm7_chain_supports(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue) {
-  return launch7_chain_select(layout, epilogue, nullptr, 0, 0, nullptr) && chain_shapes_ok(chains, num_chains, epilogue);
+  return launch7_select(layout, epilogue, true) && chain_shapes_ok(chains, num_chains, epilogue);
 }
 
 int mmf_gemm7_chain_launch(const mmf_gemm_chain* chains, int num_chains, int layout, int epilogue, hipStream_t s) {
@@ -820,30 +789,18 @@ int mmf_gemm7_chain_launch(const mmf_gemm_chain* chains, int num_chains, int lay
   sort_by_k(sums, num_chains, order);                          // longest total reduction first
   const int cap = persistent_grid_cap();
   const int tile_n = g_tile_n ? g_tile_n : pick_tile_n(sums, order, num_chains, cap);
+  // a unit of the table is a chain: orig[i] is where chain i's segments start in p[] (gemm6_parts.h)
   GemmArgs a;
-  a.nprob = num_chains;
-  a.epi = epilogue;
-  a.xcd_granule = mmf_xcd_granule();
-  a.alpha = 1.f;
-  a.drop_thresh = 0u;
-  a.site = 0u;
-  a.rng_state = nullptr;
-  int total = 0, nseg = 0;
+  mmf_gemm_table_begin(a, epilogue, nullptr);
+  int nseg = 0;
   for (int i = 0; i < num_chains; ++i) {
-    const mmf_gemm_chain& c = chains[order[i]];
-    a.tile_start[i] = total;
-    total += tiles_of(sums[order[i]], tile_n);
-    a.orig[i] = (short)nseg;
-    for (int j = 0; j < c.num_segments; ++j) {
-      const mmf_gemm_segment& g = c.seg[j];
-      a.p[nseg++] = mmf_gemm_problem{g.A, g.B, c.C, c.bias, (epilogue & MMF_EPI_ADD_AUX) ? c.aux : nullptr, c.M, c.N, g.K, g.lda, g.ldb, c.ldc, c.ldaux};
-    }
+    a.orig[mmf_gemm_table_unit(a, tiles_of(sums[order[i]], tile_n))] = (short)nseg;
+    nseg += chain_segments(chains[order[i]], epilogue, a.p + nseg);
   }
-  a.tile_start[num_chains] = total;
   a.orig[num_chains] = (short)nseg;
-  const int grid = total < cap ? total : cap;
+  const int total = a.tile_start[num_chains], grid = total < cap ? total : cap;
   t_last_tile_n = tile_n;
-  launch7_chain_select(layout, epilogue, &a, total, grid, s, tile_n);
+  launch7_select(layout, epilogue, true, &a, total, grid, s, tile_n);
   MMF_CHECK_LAUNCH("mmf_gemm_grouped_chain(v7)");
   return MMF_OK;
 }
