@@ -4,7 +4,7 @@
 // a MulT stage (6 cross or 3 self, unequal Tq/Tk) go out as ONE launch.  Rounds 1-2 kept superseded kernel generations here
 // and in attention3.hip / attention4.hip behind mmf_attn_select_impl; round 3 removed them (git history has them,
 // DESIGN.md section 5 their measurements).
-#include "mmf_internal.h"
+#include "attn_helpers.h"
 #include <stdlib.h>
 
 namespace {
@@ -30,10 +30,16 @@ int validate(const char* who, const mmf_attn_problem* p, int n, int head_dim, bo
   return MMF_OK;
 }
 
-// the dropout stream id is problem * 4096 + b*H + h: past 4096 (b, h) pairs a problem would draw its successor's masks
-int validate_dropout(const char* who, const mmf_attn_problem* p, int n, float dropout_p, const uint64_t* rng_state) {
+// the probability rule of every entry with dropout
+int validate_prob(const char* who, float dropout_p, const uint64_t* rng_state) {
   if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !rng_state))
     MMF_FAIL(MMF_E_SHAPE, "%s: dropout needs 0 <= p < 1 and an rng_state", who);
+  return MMF_OK;
+}
+
+// the dropout stream id is problem * 4096 + b*H + h: past 4096 (b, h) pairs a problem would draw its successor's masks
+int validate_dropout(const char* who, const mmf_attn_problem* p, int n, float dropout_p, const uint64_t* rng_state) {
+  if (int rc = validate_prob(who, dropout_p, rng_state)) return rc;
   for (int i = 0; dropout_p > 0.f && i < n; ++i)
     if ((long long)p[i].B * p[i].H > 4096)
       MMF_FAIL(MMF_E_SHAPE, "%s[%d]: dropout needs B*H <= 4096 (B=%d H=%d)", who, i, p[i].B, p[i].H);
@@ -52,8 +58,7 @@ namespace {
 // The _keyed entries: the dropout stream id is problem * 4096 + stream_base + b*H + h.  One problem may take any base (its ids must
 // not wrap); several keep every id of a problem below its successor's first
 int validate_keyed(const char* who, const mmf_attn_problem* p, int n, float dropout_p, const uint64_t* rng_state, uint32_t stream_base) {
-  if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !rng_state))
-    MMF_FAIL(MMF_E_SHAPE, "%s: dropout needs 0 <= p < 1 and an rng_state", who);
+  if (int rc = validate_prob(who, dropout_p, rng_state)) return rc;
   if (reinterpret_cast<uintptr_t>(rng_state) & 7u) MMF_FAIL(MMF_E_ALIGN, "%s: rng_state must be 8-byte aligned", who);
   for (int i = 0; dropout_p > 0.f && i < n; ++i) {
     const long long last = (long long)stream_base + (long long)p[i].B * p[i].H;
@@ -61,6 +66,15 @@ int validate_keyed(const char* who, const mmf_attn_problem* p, int n, float drop
       MMF_FAIL(MMF_E_SHAPE, "%s[%d]: stream_base=%u + B*H=%lld leaves the problem's stream ids (4096 per problem of a group, 2^32 alone)",
                who, i, stream_base, (long long)p[i].B * p[i].H);
   }
+  return MMF_OK;
+}
+
+// what mmf_attn_bwd_grouped_uniform and _pooled check alike: the operands, then the workspace
+int validate_uniform(const char* fn, const mmf_attn_problem* problems, int num_problems, int head_dim, const void* workspace, size_t workspace_bytes) {
+  if (int rc = validate(fn, problems, num_problems, head_dim, true)) return rc;
+  const size_t need = mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems);
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u) || workspace_bytes < need)
+    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes (4-byte aligned) required", fn, need);
   return MMF_OK;
 }
 
@@ -200,10 +214,7 @@ extern "C" size_t mmf_attn_bwd_grouped_uniform_workspace_bytes(const mmf_attn_pr
 
 extern "C" int mmf_attn_bwd_grouped_uniform(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
                                             void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "mmf_attn_bwd_grouped_uniform";
-  if (int rc = validate(fn, problems, num_problems, head_dim, true)) return rc;
-  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u) || workspace_bytes < mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems))
-    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes (4-byte aligned) required", fn, mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems));
+  if (int rc = validate_uniform("mmf_attn_bwd_grouped_uniform", problems, num_problems, head_dim, workspace, workspace_bytes)) return rc;
   return mmf_attn_bwd2u_launch(problems, num_problems, head_dim, scale, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
 
@@ -213,9 +224,7 @@ extern "C" int mmf_attn_bwd_grouped_uniform(const mmf_attn_problem* problems, in
 extern "C" int mmf_attn_bwd_grouped_pooled(const mmf_attn_problem* problems, int num_problems, int head_dim, float scale,
                                            const void* const* dys, int lddy, void* workspace, size_t workspace_bytes, void* stream) {
   const char* fn = "mmf_attn_bwd_grouped_pooled";
-  if (int rc = validate(fn, problems, num_problems, head_dim, true)) return rc;
-  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u) || workspace_bytes < mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems))
-    MMF_FAIL(MMF_E_SHAPE, "%s: workspace of %zu bytes (4-byte aligned) required", fn, mmf_attn_bwd_grouped_uniform_workspace_bytes(problems, num_problems));
+  if (int rc = validate_uniform(fn, problems, num_problems, head_dim, workspace, workspace_bytes)) return rc;
   if (!dys || (lddy & 7)) MMF_FAIL(MMF_E_ALIGN, "%s: lddy=%d (a multiple of 8) and the gradient pointers are required", fn, lddy);
   for (int i = 0; i < num_problems; ++i) {
     if (!dys[i] || !mmf_aligned16(dys[i]) || lddy < problems[i].H * head_dim)
@@ -239,11 +248,9 @@ int delta_launch(const char* fn, const mmf_attn_problem* problems, int num_probl
     if (dr) {
       MmfItemDrop d = *dr;
       d.item0 += (unsigned)i * 4096u;
-      if (head_dim == 96) hipLaunchKernelGGL((attn_delta_kernel<96, MmfItemDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
-      else                hipLaunchKernelGGL((attn_delta_kernel<64, MmfItemDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d);
+      attn_select(head_dim, true, [&](auto dh, auto) { hipLaunchKernelGGL((attn_delta_kernel<dh(), MmfItemDrop>), grid, dim3(DELTA_THREADS), 0, s, p, scale, d); });
     } else {
-      if (head_dim == 96) hipLaunchKernelGGL(attn_delta_kernel<96>, grid, dim3(DELTA_THREADS), 0, s, p, scale);
-      else                hipLaunchKernelGGL(attn_delta_kernel<64>, grid, dim3(DELTA_THREADS), 0, s, p, scale);
+      attn_select(head_dim, false, [&](auto dh, auto) { hipLaunchKernelGGL(attn_delta_kernel<dh()>, grid, dim3(DELTA_THREADS), 0, s, p, scale); });
     }
     MMF_CHECK_LAUNCH(fn);
   }

@@ -49,6 +49,8 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
   const int Tq = P.Tq, Tk = P.Tk, H = P.H;
   const int b = bh / H, h = bh % H;
 
+  // (the (b, h) origin b * T * ld + h * DH is spelled out at each use on purpose: formed by a function, with any parameter passing,
+  // the leading dimension is loaded ahead of the product and 20 of the 22 kernels come out in another instruction order)
   const unsigned short* Kg = static_cast<const unsigned short*>(P.K) + (size_t)b * Tk * P.ldk + h * DH;
   const unsigned short* Vg = static_cast<const unsigned short*>(P.V) + (size_t)b * Tk * P.ldv + h * DH;
   TileDma<DH> dma;
@@ -64,20 +66,18 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
   bf16x8_t qf[KS];
   if constexpr (ACTIVE) {
     const unsigned short* Qg = static_cast<const unsigned short*>(P.Q) + (size_t)b * Tq * P.ldq + h * DH;
-    const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Qg), 0, Tq * P.ldq * 2, 0x00020000);
     RowLoad<DH> rl;
-    rl.issue(rsQ, P.ldq, qs, lane);
+    rl.issue(rows_rsrc(Qg, 0, Tq, P.ldq), P.ldq, qs, lane);
     rl.commit(qf, lane, slice);
   }
 
   f32x16_t o[DT];
   float m = NEG_BIG, l = 0.f;
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+  for (int dt = 0; dt < DT; ++dt) o[dt] = zero16();
   const float c = a.scale * LOG2E;
   const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh) + a.stream_base) : 0u;
+  // (these three are repeated in every body on purpose: held in a struct that hands out tr_base, 20 kernels change)
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
@@ -157,8 +157,7 @@ __device__ __forceinline__ void fwd2_wave(const AttnArgs2& a, const mmf_attn_pro
     char* oslice = smem + (ntiles & 1) * STAGE_B + wave * img_slice_bytes<DH>();
     unsigned short* Og = static_cast<unsigned short*>(P.O) + (size_t)b * Tq * P.ldo + h * DH;
     const float lt = half_sum(l);
-    int lane_e;                                            // (the lane id read again behind the sweep: see dq2_wave)
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    const int lane_e = lane_again();
     store_rows_lds<DH>(o, 1.f / lt, Og, P.ldo, qs, Tq, lane_e, oslice);
     const int qrow = qs + (lane & 31);
     if (half == 0 && qrow < Tq) P.LSE[(size_t)bh * Tq + qrow] = m * LN2 + __logf(lt);
@@ -173,14 +172,11 @@ __global__ __launch_bounds__(NT, 3)
 void attn_fwd2n_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_B];
-  const auto [pi, item] = work_item(a);
-  if (item >= a.nwg[pi]) return;
-  const mmf_attn_problem& P = a.p[pi];
-  const int nchunk = a.nchunk[pi], rpc = a.rpc[pi];         // rpc <= 128 here
-  const int bh = item / nchunk, q0 = (item % nchunk) * rpc;
+  MMF_ATTN_WG_DECODE(a, a.rpc[pi], q0);                     // rpc <= 128 here
   const int nb = (min(P.Tq, q0 + rpc) - q0 + 31) >> 5;      // 32-row query blocks in this chunk (1..4)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int qs = q0 + 32 * wave, pidx = a.orig[pi];
+  // (the two instantiations are named in every kernel on purpose: chosen through a generic lambda, the head_dim 96 kernels change)
   if (wave < nb) fwd2_wave<DH, DROP, true>(a, P, pidx, bh, qs, smem);
   else           fwd2_wave<DH, DROP, false>(a, P, pidx, bh, qs, smem);
 }
@@ -224,9 +220,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
   bf16x8_t qf[KS], dof[KS];
   float delta = 0.f, lse2 = 0.f;
   if constexpr (ACTIVE) {
-    auto rsrc = [&](const void* base, size_t off, int ld) {
-      return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(base) + off), 0, Tq * ld * 2, 0x00020000);
-    };
+    auto rsrc = [&](const void* base, size_t off, int ld) { return rows_rsrc(base, off, Tq, ld); };
     if constexpr (GIVEN) {
       RowLoad<DH> rq, rdo;
       rq.issue(rsrc(P.Q, qoff, P.ldq), P.ldq, qs, lane);
@@ -244,11 +238,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
     bf16x8_t of[KS];
     ro.commit(of, lane, slice);
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const u32x4_t x = __builtin_bit_cast(u32x4_t, of[ks]), y = __builtin_bit_cast(u32x4_t, dof[ks]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) delta += bf16lo(x[e]) * bf16lo(y[e]) + bf16hi(x[e]) * bf16hi(y[e]);
-    }
+    for (int ks = 0; ks < KS; ++ks) delta = dot8(delta, __builtin_bit_cast(u32x4_t, of[ks]), __builtin_bit_cast(u32x4_t, dof[ks]));
     delta = half_sum(delta);
     if (half == 0 && qrow < Tq) P.delta[(size_t)bh * Tq + qrow] = delta;
     }
@@ -259,9 +249,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
   const unsigned qidx = (unsigned)qrow * (unsigned)Tk;
   f32x16_t dq[DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+  for (int dt = 0; dt < DT; ++dt) dq[dt] = zero16();
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
@@ -311,10 +299,7 @@ __device__ __forceinline__ void dq2_wave(const AttnArgs2& a, const mmf_attn_prob
   }
   if constexpr (ACTIVE) {
     char* oslice = smem + (ntiles & 1) * STAGE_B + wave * img_slice_bytes<DH>();
-    // the store's per-lane LDS / global offsets depend on the lane only: formed at kernel entry they are carried (spilled) around the
-    // sweep, so the lane id is read again here (guide: "recompute per block (v_mbcnt)")
-    int lane_e;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    const int lane_e = lane_again();
     store_rows_lds<DH>(dq, a.scale, static_cast<unsigned short*>(P.dQ) + qoff, P.ldq, qs, Tq, lane_e, oslice);
     BSTAMP(7);
     BSTAMP_STORE(0);
@@ -326,11 +311,7 @@ __global__ __launch_bounds__(NT, DQ_WAVES_PER_SIMD)
 void attn_bwd_dq2_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_B];
-  const auto [pi, item] = work_item(a);
-  if (item >= a.nwg[pi]) return;
-  const mmf_attn_problem& P = a.p[pi];
-  const int nchunk = a.nchunk[pi];
-  const int bh = item / nchunk, q0 = (item % nchunk) * ROWS_PER_WG;
+  MMF_ATTN_WG_DECODE(a, ROWS_PER_WG, q0);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int qs = q0 + 32 * wave, pidx = a.orig[pi];
   if (qs < P.Tq) dq2_wave<DH, DROP, true, GIVEN>(a, P, pidx, bh, qs, smem);
@@ -360,24 +341,14 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
   const int b = bh / H, h = bh % H;
   const unsigned short* Qg = static_cast<const unsigned short*>(P.Q) + (size_t)b * Tq * P.ldq + h * DH;
   const unsigned short* dOg = static_cast<const unsigned short*>(P.dO) + (size_t)b * Tq * P.ldo + h * DH;
-  const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc(P.LSE + (size_t)bh * Tq, 0, Tq * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(P.delta + (size_t)bh * Tq, 0, Tq * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsL = f32_rsrc(P.LSE + (size_t)bh * Tq, Tq), rsD = f32_rsrc(P.delta + (size_t)bh * Tq, Tq);
   TileDma<DH> dma;
   dma.init(P.ldq, P.ldo, wave, lane);
   auto issue = [&](int j) {
     dma.issue(Qg + (size_t)64 * j * P.ldq, dOg + (size_t)64 * j * P.ldo, P.ldq, P.ldo, Tq - 64 * j, smem + (j & 1) * STAGE_B, wave);
   };
-  // LSE and delta of this lane's row (lane & 31) of the two 32-row blocks of tile j (rows past Tq read as 0, which is
-  // harmless: their Q and dO rows are zeros, so P = 1 meets dO = 0 and dS = 1 * (0 - 0))
-  float st_l[2], st_d[2];
-  auto stats = [&](int j) {
-#pragma unroll
-    for (int qs_ = 0; qs_ < 2; ++qs_) {
-      const unsigned off = (unsigned)(64 * j + 32 * qs_ + (lane & 31)) * 4u;
-      st_l[qs_] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsL, off, 0, 0));
-      st_d[qs_] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsD, off, 0, 0));
-    }
-  };
+  float st_l[2], st_d[2];                                    // LSE, delta of this lane's row of the two blocks of tile j (row_stats)
+  auto stats = [&](int j) { row_stats<false>(rsL, rsD, j, lane, Tq, st_l, st_d); };
   const int ntiles = (Tq + 63) / 64;
   BSTAMP_DECL;
   issue(0);
@@ -387,8 +358,7 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
   char* slice = smem + STAGE_B + wave * img_slice_bytes<DH>();
   bf16x8_t kf[KS], vf[KS];
   if constexpr (ACTIVE) {
-    const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(P.K) + koff), 0, Tk * P.ldk * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(P.V) + voff), 0, Tk * P.ldv * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsK = rows_rsrc(P.K, koff, Tk, P.ldk), rsV = rows_rsrc(P.V, voff, Tk, P.ldv);
     RowLoad<DH> rk, rv;                                       // 2 x 6 loads in flight, one wait (RowLoad, attn_helpers.h)
     rk.issue(rsK, P.ldk, k0, lane);
     rv.issue(rsV, P.ldv, k0, lane);
@@ -397,9 +367,7 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
   }
   f32x16_t dk[DT], dv[DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+  for (int dt = 0; dt < DT; ++dt) { dk[dt] = zero16(); dv[dt] = zero16(); }
   const float c = a.scale * LOG2E;
   const unsigned dkey = DROP ? mmf_rng_key(*a.rng_state, a.site, (unsigned)(pidx * 4096 + bh) + a.stream_base) : 0u;
   const unsigned kcol = (unsigned)(k0 + (lane & 31));
@@ -427,9 +395,9 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
         f32x16_t s, dp, z;
 #pragma unroll
         for (int r = 0; r < 16; ++r) z[r] = 0.f;
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cl[QS], half == 0), one3, z, 0, 0, 0);   // S' starts at -LSE / scale
+        s = spread_rows(cl[QS], half == 0, one3, z);   // S' starts at -LSE / scale
         f32x16_t dm;                                                                      // -delta[q] in every key column
-        dm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cd[QS], half == 0), one3, z, 0, 0, 0);
+        dm = spread_rows(cd[QS], half == 0, one3, z);
         if constexpr (DROP) dp = z; else dp = dm;                                         // dP' starts at -delta (no dropout)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -492,8 +460,7 @@ __device__ __forceinline__ void dkv2_wave(const AttnArgs2& a, const mmf_attn_pro
   if constexpr (ACTIVE) {
     if (sel > 0) return;
     char* oslice = smem + (ntiles & 1) * STAGE_B + wave * img_slice_bytes<DH>();
-    int lane_e;                                            // (the lane id read again behind the sweep: see dq2_wave)
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    const int lane_e = lane_again();
     store_rows_lds<DH>(dk, a.scale, static_cast<unsigned short*>(P.dK) + koff, P.ldk, k0, Tk, lane_e, oslice);
     store_rows_lds<DH>(dv, 1.f, static_cast<unsigned short*>(P.dV) + voff, P.ldv, k0, Tk, lane_e, oslice);
     BSTAMP(7);
@@ -506,11 +473,7 @@ __global__ __launch_bounds__(NT, 2)      // dK^T, dV^T, K and V fragments alone 
 void attn_bwd_dkv2_kernel(const AttnArgs2 a) {
   constexpr int STAGE_B = 2 * img_tile_bytes<DH>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_B];
-  const auto [pi, item] = work_item(a);
-  if (item >= a.nwg[pi]) return;
-  const mmf_attn_problem& P = a.p[pi];
-  const int nchunk = a.nchunk[pi];
-  const int bh = item / nchunk, kc0 = (item % nchunk) * ROWS_PER_WG;
+  MMF_ATTN_WG_DECODE(a, ROWS_PER_WG, kc0);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int k0 = kc0 + 32 * wave, pidx = a.orig[pi];
   const bool split = P.Tk <= 32;                            // workgroup-uniform: the sweep split (dkv2_wave)
@@ -583,7 +546,7 @@ void attn_uniform_stats_kernel(const StatArgs a) {
   }
 #pragma unroll
   for (int i = 0; i < STAT_PASSES; ++i) {
-    float s = 0.f;
+    float s = 0.f;                                            // (dot8's text on purpose: through the function this kernel changes)
 #pragma unroll
     for (int e = 0; e < 4; ++e) s += bf16lo(x[i][e]) * bf16lo(u[i][e]) + bf16hi(x[i][e]) * bf16hi(u[i][e]);
     part[threadIdx.x + STAT_THREADS * i] = s;
@@ -614,7 +577,7 @@ __device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_pro
   const int Tq = P.Tq, Tk = P.Tk, H = P.H;
   const int b = bh / H, h = bh % H;
   const unsigned short* Kg = static_cast<const unsigned short*>(P.K) + (size_t)b * Tk * P.ldk + h * DH;
-  const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cst) + (size_t)bh * Tk, 0, Tk * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsC = f32_rsrc(cst + (size_t)bh * Tk, Tk);
   TileDma<DH> dma;
   dma.init(P.ldk, P.ldk, wave, lane);
   auto issue = [&](int j) { dma.issue_x(Kg + (size_t)64 * j * P.ldk, P.ldk, Tk - 64 * j, smem + (j & 1) * TILE_B, wave); };
@@ -634,9 +597,9 @@ __device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_pro
   bf16x8_t qf[KS];
   float delta = 0.f, lse2 = 0.f;
   if constexpr (ACTIVE) {
-    const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(P.Q) + qoff), 0, Tq * P.ldq * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsQ = rows_rsrc(P.Q, qoff, Tq, P.ldq);
     const size_t ooff = (size_t)b * Tq * P.ldo + h * DH;
-    const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short*>(P.O) + ooff, 0, Tq * P.ldo * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsO = rows_rsrc(P.O, ooff, Tq, P.ldo);
     RowLoad<DH> rq, ro;                                       // 2 x 6 loads in flight, one wait (RowLoad, attn_helpers.h)
     rq.issue(rsQ, P.ldq, qs, lane);
     ro.issue(rsO, P.ldo, qs, lane);
@@ -646,11 +609,7 @@ __device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_pro
     // delta = O . u_h as dq2_wave forms O . dO, against the one row; written for the dK/dV kernel behind this one
     const unsigned short* ug = static_cast<const unsigned short*>(P.dO) + (size_t)b * P.ldo + h * DH + 8 * half;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const u32x4_t x = __builtin_bit_cast(u32x4_t, of[ks]), y = *reinterpret_cast<const u32x4_t*>(ug + 16 * ks);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) delta += bf16lo(x[e]) * bf16lo(y[e]) + bf16hi(x[e]) * bf16hi(y[e]);
-    }
+    for (int ks = 0; ks < KS; ++ks) delta = dot8(delta, __builtin_bit_cast(u32x4_t, of[ks]), *reinterpret_cast<const u32x4_t*>(ug + 16 * ks));
     delta = half_sum(delta);
     if (half == 0 && qrow < Tq) P.delta[(size_t)bh * Tq + qrow] = delta;
     lse2 = (qrow < Tq ? P.LSE[(size_t)bh * Tq + qrow] : 0.f) * LOG2E;
@@ -658,9 +617,7 @@ __device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_pro
   const float c = a.scale * LOG2E;
   f32x16_t dq[DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+  for (int dt = 0; dt < DT; ++dt) dq[dt] = zero16();
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
@@ -679,7 +636,7 @@ __device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_pro
         f32x16_t s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cc[KT], half == 0), one3, s, 0, 0, 0);   // c[key] in every query column
+        dp = spread_rows(cc[KT], half == 0, one3, s);   // c[key] in every query column
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sK, 32 * KT, ks, lane), qf[ks], s, 0, 0, 0);
@@ -703,8 +660,7 @@ __device__ __forceinline__ void dq2u_wave(const AttnArgs2& a, const mmf_attn_pro
     }
   }
   if constexpr (ACTIVE) {
-    int lane_e;                                            // (the lane id read again behind the sweep: see dq2_wave)
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    const int lane_e = lane_again();
     store_rows_lds<DH>(dq, a.scale, static_cast<unsigned short*>(P.dQ) + qoff, P.ldq, qs, Tq, lane_e, slice);
   }
 }
@@ -714,11 +670,7 @@ __global__ __launch_bounds__(NT, DQ_WAVES_PER_SIMD)
 void attn_bwd_dq2u_kernel(const UniArgs u) {
   __shared__ __attribute__((aligned(1024))) char smem[4 * img_tile_bytes<DH>()];
   const AttnArgs2& a = u.a;
-  const auto [pi, item] = work_item(a);
-  if (item >= a.nwg[pi]) return;
-  const mmf_attn_problem& P = a.p[pi];
-  const int nchunk = a.nchunk[pi];
-  const int bh = item / nchunk, q0 = (item % nchunk) * ROWS_PER_WG;
+  MMF_ATTN_WG_DECODE(a, ROWS_PER_WG, q0);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int qs = q0 + 32 * wave;
   if (qs < P.Tq) dq2u_wave<DH, true>(a, P, u.c[pi], bh, qs, smem);
@@ -738,21 +690,12 @@ __device__ __forceinline__ void dkv2u_wave(const AttnArgs2& a, const mmf_attn_pr
   const int Tq = P.Tq, Tk = P.Tk, H = P.H;
   const int b = bh / H, h = bh % H;
   const unsigned short* Qg = static_cast<const unsigned short*>(P.Q) + (size_t)b * Tq * P.ldq + h * DH;
-  const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc(P.LSE + (size_t)bh * Tq, 0, Tq * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(P.delta + (size_t)bh * Tq, 0, Tq * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsL = f32_rsrc(P.LSE + (size_t)bh * Tq, Tq), rsD = f32_rsrc(P.delta + (size_t)bh * Tq, Tq);
   TileDma<DH> dma;
   dma.init(P.ldq, P.ldq, wave, lane);
   auto issue = [&](int j) { dma.issue_x(Qg + (size_t)64 * j * P.ldq, P.ldq, Tq - 64 * j, smem + (j & 1) * TILE_B, wave); };
-  float st_l[2], st_d[2];                                    // LSE, delta of this lane's row of the two blocks of tile j (dkv2_wave)
-  auto stats = [&](int j) {
-#pragma unroll
-    for (int qs_ = 0; qs_ < 2; ++qs_) {
-      const int row = 64 * j + 32 * qs_ + (lane & 31);
-      const float l = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsL, (unsigned)row * 4u, 0, 0));
-      st_l[qs_] = row < Tq ? l : -NEG_BIG;
-      st_d[qs_] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsD, (unsigned)row * 4u, 0, 0));
-    }
-  };
+  float st_l[2], st_d[2];                                    // ... with LSE = +big for the rows past Tq
+  auto stats = [&](int j) { row_stats<true>(rsL, rsD, j, lane, Tq, st_l, st_d); };
   const int ntiles = (Tq + 63) / 64;
   issue(0);
   if constexpr (ACTIVE) stats(0);
@@ -762,18 +705,15 @@ __device__ __forceinline__ void dkv2u_wave(const AttnArgs2& a, const mmf_attn_pr
   bf16x8_t kf[KS];
   float ckey = 0.f;
   if constexpr (ACTIVE) {
-    const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(P.K) + koff), 0, Tk * P.ldk * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cst) + (size_t)bh * Tk, 0, Tk * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsC = f32_rsrc(cst + (size_t)bh * Tk, Tk);
     RowLoad<DH> rk;
-    rk.issue(rsK, P.ldk, k0, lane);
+    rk.issue(rows_rsrc(P.K, koff, Tk, P.ldk), P.ldk, k0, lane);
     ckey = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsC, (unsigned)(k0 + (lane & 31)) * 4u, 0, 0));
     rk.commit(kf, lane, slice);
   }
   f32x16_t dk[DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dk[dt][r] = 0.f;
+  for (int dt = 0; dt < DT; ++dt) dk[dt] = zero16();
   float w = 0.f;
   const float c = a.scale * LOG2E;
   const unsigned tlo = tr_lane_lo(lane), thi = tr_lane_hi(lane);
@@ -796,8 +736,8 @@ __device__ __forceinline__ void dkv2u_wave(const AttnArgs2& a, const mmf_attn_pr
         f32x16_t s, dm, z;
 #pragma unroll
         for (int r = 0; r < 16; ++r) z[r] = 0.f;
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cl[QS], half == 0), one3, z, 0, 0, 0);    // S' starts at -LSE / scale
-        dm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(cd[QS], half == 0), one3, z, 0, 0, 0);   // -delta[q] in every key column
+        s = spread_rows(cl[QS], half == 0, one3, z);    // S' starts at -LSE / scale
+        dm = spread_rows(cd[QS], half == 0, one3, z);   // -delta[q] in every key column
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<DH>(sQ, 32 * QS, ks, lane), kf[ks], s, 0, 0, 0);
@@ -819,8 +759,7 @@ __device__ __forceinline__ void dkv2u_wave(const AttnArgs2& a, const mmf_attn_pr
     }
   }
   if constexpr (ACTIVE) {
-    int lane_e;                                            // (the lane id read again behind the sweep: see dq2_wave)
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+    const int lane_e = lane_again();
     store_rows_lds<DH>(dk, a.scale, static_cast<unsigned short*>(P.dK) + koff, P.ldk, k0, Tk, lane_e, slice);
     // dV[key,:] = w u_h in the accumulator layout store_rows_lds takes: register 4g+i of tile dt is column 32 dt + 8 g + 4 half + i
     const float wt = half_sum(w);
@@ -843,11 +782,7 @@ __global__ __launch_bounds__(NT, 3)      // dK^T and the K fragments are 72 regi
 void attn_bwd_dkv2u_kernel(const UniArgs u) {
   __shared__ __attribute__((aligned(1024))) char smem[4 * img_tile_bytes<DH>()];
   const AttnArgs2& a = u.a;
-  const auto [pi, item] = work_item(a);
-  if (item >= a.nwg[pi]) return;
-  const mmf_attn_problem& P = a.p[pi];
-  const int nchunk = a.nchunk[pi];
-  const int bh = item / nchunk, kc0 = (item % nchunk) * ROWS_PER_WG;
+  MMF_ATTN_WG_DECODE(a, ROWS_PER_WG, kc0);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int k0 = kc0 + 32 * wave;
   if (k0 < P.Tk) dkv2u_wave<DH, true>(a, P, u.c[pi], bh, k0, smem);
@@ -871,32 +806,24 @@ constexpr int g_attn_stub = 0;
 #endif
 
 namespace {
-template <typename K96T, typename K96F, typename K64T, typename K64F>
-void launch4(int head_dim, bool dr, K96T k96t, K96F k96f, K64T k64t, K64F k64f, int total, const AttnArgs2& a, hipStream_t s) {
-  if (head_dim == 96) { if (dr) hipLaunchKernelGGL(k96t, dim3(total), dim3(NT), 0, s, a); else hipLaunchKernelGGL(k96f, dim3(total), dim3(NT), 0, s, a); }
-  else                { if (dr) hipLaunchKernelGGL(k64t, dim3(total), dim3(NT), 0, s, a); else hipLaunchKernelGGL(k64f, dim3(total), dim3(NT), 0, s, a); }
-}
+// one launch of `total` NT-thread workgroups; the instantiation comes from attn_select (attn_helpers.h)
+template <typename K, typename Args>
+void launch(K kernel, int total, hipStream_t s, const Args& args) { hipLaunchKernelGGL(kernel, dim3(total), dim3(NT), 0, s, args); }
 }  // namespace
 
 int mmf_attn_bwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, float scale, float drop_p,
                          const uint64_t* rng_state, uint32_t site, hipStream_t s, bool given_delta, uint32_t stream_base) {
   if (int rc = check_ranges("mmf_attn_bwd_grouped", problems, n)) return rc;
   AttnArgs2 a;
-  if (given_delta) {                                                                               // dQ from the caller's delta
+  if (given_delta || !(g_attn_stub & 2)) {                  // dQ first: from the caller's delta, or writing delta on its way
     const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false, stream_base);
-    launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dq2_kernel<96, true, true>, attn_bwd_dq2_kernel<96, false, true>,
-            attn_bwd_dq2_kernel<64, true, true>, attn_bwd_dq2_kernel<64, false, true>, total, a, s);
-    MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_delta(dq, v2)");
-  } else if (!(g_attn_stub & 2)) {
-    const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, false, stream_base);   // dQ (+ delta) first
-    launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dq2_kernel<96, true>, attn_bwd_dq2_kernel<96, false>, attn_bwd_dq2_kernel<64, true>,
-            attn_bwd_dq2_kernel<64, false>, total, a, s);
-    MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dq, v2)");
+    if (given_delta) attn_select(head_dim, a.drop_thresh != 0u, [&](auto dh, auto dr) { launch(attn_bwd_dq2_kernel<dh(), dr(), true>, total, s, a); });
+    else             attn_select(head_dim, a.drop_thresh != 0u, [&](auto dh, auto dr) { launch(attn_bwd_dq2_kernel<dh(), dr(), false>, total, s, a); });
+    MMF_CHECK_LAUNCH(given_delta ? "mmf_attn_bwd_grouped_delta(dq, v2)" : "mmf_attn_bwd_grouped(dq, v2)");
   }
   if (g_attn_stub & 4) return MMF_OK;
   const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, true, false, stream_base);   // then dK/dV (reads delta)
-  launch4(head_dim, a.drop_thresh != 0u, attn_bwd_dkv2_kernel<96, true>, attn_bwd_dkv2_kernel<96, false>, attn_bwd_dkv2_kernel<64, true>,
-          attn_bwd_dkv2_kernel<64, false>, total, a, s);
+  attn_select(head_dim, a.drop_thresh != 0u, [&](auto dh, auto dr) { launch(attn_bwd_dkv2_kernel<dh(), dr()>, total, s, a); });
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped(dkv, v2)");
   return MMF_OK;
 }
@@ -924,8 +851,9 @@ int mmf_attn_bwd2u_launch(const mmf_attn_problem* problems, int n, int head_dim,
     sblocks += (int)((chunks + STAT_CHUNKS - 1) / STAT_CHUNKS);
   }
   sa.blk_start[n] = sblocks;
-  if (head_dim == 96) hipLaunchKernelGGL(attn_uniform_stats_kernel<96>, dim3(sblocks), dim3(STAT_THREADS), 0, s, sa);
-  else                hipLaunchKernelGGL(attn_uniform_stats_kernel<64>, dim3(sblocks), dim3(STAT_THREADS), 0, s, sa);
+  attn_select(head_dim, false, [&](auto dh, auto) {
+    hipLaunchKernelGGL(attn_uniform_stats_kernel<dh()>, dim3(sblocks), dim3(STAT_THREADS), 0, s, sa);
+  });
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_uniform(stats)");
   UniArgs ua;
   auto fill = [&](bool by_keys) {
@@ -934,12 +862,10 @@ int mmf_attn_bwd2u_launch(const mmf_attn_problem* problems, int n, int head_dim,
     return total;
   };
   int total = fill(false);
-  if (head_dim == 96) hipLaunchKernelGGL(attn_bwd_dq2u_kernel<96>, dim3(total), dim3(NT), 0, s, ua);
-  else                hipLaunchKernelGGL(attn_bwd_dq2u_kernel<64>, dim3(total), dim3(NT), 0, s, ua);
+  attn_select(head_dim, false, [&](auto dh, auto) { launch(attn_bwd_dq2u_kernel<dh()>, total, s, ua); });
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_uniform(dq)");
   total = fill(true);
-  if (head_dim == 96) hipLaunchKernelGGL(attn_bwd_dkv2u_kernel<96>, dim3(total), dim3(NT), 0, s, ua);
-  else                hipLaunchKernelGGL(attn_bwd_dkv2u_kernel<64>, dim3(total), dim3(NT), 0, s, ua);
+  attn_select(head_dim, false, [&](auto dh, auto) { launch(attn_bwd_dkv2u_kernel<dh()>, total, s, ua); });
   MMF_CHECK_LAUNCH("mmf_attn_bwd_grouped_uniform(dkv)");
   return MMF_OK;
 }
@@ -951,8 +877,7 @@ int mmf_attn_fwd2_launch(const mmf_attn_problem* problems, int n, int head_dim, 
   if (g_attn_stub & 1) return MMF_OK;
   AttnArgs2 a;
   const int total = fill_args2(a, problems, n, scale, drop_p, rng_state, site, false, true, stream_base);
-  launch4(head_dim, a.drop_thresh != 0u, attn_fwd2n_kernel<96, true>, attn_fwd2n_kernel<96, false>, attn_fwd2n_kernel<64, true>,
-          attn_fwd2n_kernel<64, false>, total, a, s);
+  attn_select(head_dim, a.drop_thresh != 0u, [&](auto dh, auto dr) { launch(attn_fwd2n_kernel<dh(), dr()>, total, s, a); });
   MMF_CHECK_LAUNCH("mmf_attn_fwd_grouped");
   return MMF_OK;
 }

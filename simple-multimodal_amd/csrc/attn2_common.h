@@ -1,5 +1,7 @@
-// Shared pieces of the attention kernels (attention2.hip): the work table, LDS-DMA staging of tile pairs in the dual-use
-// LDS image of attn_helpers.h, asm transposed reads with counted waits, and the host-side table fill.
+// Shared pieces of the attention kernels (attention2.hip): the work table and the kernel wrappers' decode of it, buffer descriptors,
+// LDS-DMA staging of tile pairs in the dual-use LDS image of attn_helpers.h, asm transposed reads with counted waits, the row
+// statistics of the dK/dV kernels, and the host-side table fill.  What is shared as a function, what as text and what not at all was
+// decided by the generated code (profiles/attention_shared_parts.txt): these kernels keep the parent's instructions only in some forms.
 #pragma once
 #include "mmf_internal.h"
 #include <algorithm>
@@ -36,6 +38,26 @@ __device__ __forceinline__ WorkItem work_item(const AttnArgs2& a) {
   while (pi + 1 < a.nprob && bid >= a.blk_start[pi + 1]) ++pi;
   const int loc = bid - a.blk_start[pi], n8 = (a.blk_start[pi + 1] - a.blk_start[pi]) >> 3;
   return {pi, (loc & 7) * n8 + (loc >> 3)};
+}
+
+// The kernel wrappers' decode of a workgroup, one statement for the five kernels.  It declares the workgroup's problem P (pi in the
+// table; a padding workgroup returns), its (b, h) pair bh, rpc = RPC rows of the partitioned axis per chunk and the chunk's first row
+// under the caller's name for it.  (A macro: as a function, in every form tried, all kernels come out in another instruction order.)
+#define MMF_ATTN_WG_DECODE(a, RPC, row0)                                  \
+  const auto [pi, item] = work_item(a);                                   \
+  if (item >= (a).nwg[pi]) return;                                        \
+  const mmf_attn_problem& P = (a).p[pi];                                  \
+  const int nchunk = (a).nchunk[pi], rpc = (RPC);                         \
+  const int bh = item / nchunk, row0 = (item % nchunk) * rpc
+
+// Buffer descriptors of the kernels' raw buffer loads and LDS-DMA: whatever lies past the range reads as zeros.  rows_rsrc: the T
+// rows of a (T, ld) bf16 matrix that starts `off` elements behind `base` (a (b, h) origin, or a tile's first row with the rows
+// left); f32_rsrc: n floats.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const void* base, size_t off, int T, int ld) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(static_cast<const unsigned short*>(base) + off), 0, T * ld * 2, 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t f32_rsrc(const float* p, int n) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, n * 4, 0x00020000);
 }
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -148,6 +170,26 @@ __device__ __forceinline__ bf16x8_t ones3_frag(bool low_half) {
   return __builtin_bit_cast(bf16x8_t, w);
 }
 
+// ... the statistics' prefetch in the dK/dV kernels: LSE and delta of this lane's row (lane & 31) of the two 32-row blocks of tile j.
+// Rows past Tq read as 0 from the range check.  The general kernel leaves that (their Q and dO rows are zeros, so P = 1 meets dO = 0
+// and dS = 1 * (0 - 0)); PAST_BIG (the uniform kernel, whose dS has no dO factor) gives them LSE = +big, so that their p is 0.
+template <bool PAST_BIG>
+__device__ __forceinline__ void row_stats(__amdgpu_buffer_rsrc_t rsL, __amdgpu_buffer_rsrc_t rsD, int j, int lane, int Tq,
+                                          float (&st_l)[2], float (&st_d)[2]) {
+#pragma unroll
+  for (int qs_ = 0; qs_ < 2; ++qs_) {
+    const int row = 64 * j + 32 * qs_ + (lane & 31);
+    const float l = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsL, (unsigned)row * 4u, 0, 0));
+    if constexpr (PAST_BIG) st_l[qs_] = row < Tq ? l : -NEG_BIG; else st_l[qs_] = l;
+    st_d[qs_] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsD, (unsigned)row * 4u, 0, 0));
+  }
+}
+
+// ... the outer product itself: x of this lane's row (lane & 31) in every column of a 32 x 32 accumulator, added to z
+__device__ __forceinline__ f32x16_t spread_rows(float x, bool low_half, const bf16x8_t& one3, const f32x16_t& z) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(split3_frag(x, low_half), one3, z, 0, 0, 0);
+}
+
 // One wave's share of the LDS-DMA of a stage = the image (attn_helpers.h) of two 64-row tiles X (at st) and Y (at st +
 // tile bytes) of two (T, ld) matrices.  A tile is DH/8 one-KiB pieces; the stage's pieces are dealt to the 4 waves, piece
 // p = wave + 4 i, so whether piece i of a wave belongs to X or Y is a compile-time fact (DH/8 is a multiple of 4).  LDS-DMA
@@ -173,6 +215,7 @@ struct TileDma {
   // Xj / Yj: the matrices' (b, h) origins advanced to row 64 j; rows_left = T - 64 j
   __device__ __forceinline__ void issue(const unsigned short* Xj, const unsigned short* Yj, int ldx, int ldy, int rows_left,
                                         char* st, int wave) const {
+    // (rows_rsrc's text, twice on purpose: through the function the five general kernels come out in another instruction order)
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Xj), 0, rows_left * ldx * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Yj), 0, rows_left * ldy * 2, 0x00020000);
 #pragma unroll
@@ -184,7 +227,7 @@ struct TileDma {
   }
   // The X pieces alone: a one-tile stage at st (the uniform backward kernels of attention2.hip sweep one matrix)
   __device__ __forceinline__ void issue_x(const unsigned short* Xj, int ldx, int rows_left, char* st, int wave) const {
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Xj), 0, rows_left * ldx * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = rows_rsrc(Xj, 0, rows_left, ldx);
 #pragma unroll
     for (int i = 0; 4 * i < PIECES; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void_t*)(st + (wave + 4 * i) * 1024), 16, voff[i], 0, 0, 0);

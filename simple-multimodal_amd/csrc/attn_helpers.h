@@ -1,5 +1,6 @@
 // Shared device helpers of the attention kernels (attention2.hip): MFMA v_mfma_f32_32x32x16_bf16 fragment layouts and
-// the ONE LDS image every tile uses (round 3).
+// the ONE LDS image every tile uses (round 3); and attn_select, by which every attention launch (attention.hip's delta kernel
+// included) picks its instantiation.
 //
 // LDS image of a [rows][DH] bf16 tile (rows a multiple of 8): 8-row x 32-column subtiles of 512 B, guide T10 image (a),
 //     off(row, ch) = (DH/32)*512*(row >> 3) + 512*(ch >> 2) + 64*(row & 7) + 16*((ch & 3) ^ ((row >> 2) & 3))
@@ -13,6 +14,7 @@
 // LDS-DMA pieces exactly, and a wave-private 32-row slice (prologue loads, epilogue stores) is a quarter of a stage.
 #pragma once
 #include "mmf_internal.h"
+#include <type_traits>
 #include "lds_image.h"
 
 namespace {
@@ -23,6 +25,30 @@ constexpr float LN2 = 0.6931471805599453f;
 constexpr float NEG_BIG = -1.0e30f;
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// a zeroed 32 x 32 accumulator (one vector at a time: zeroing a whole array through a function moves the kernels' instructions)
+__device__ __forceinline__ f32x16_t zero16() {
+  f32x16_t z;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) z[r] = 0.f;
+  return z;
+}
+
+// acc + x . y over the eight bf16 of two 16-byte chunks, in the order the dQ kernels sum delta = O . dO
+__device__ __forceinline__ float dot8(float acc, const u32x4_t& x, const u32x4_t& y) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc += bf16lo(x[e]) * bf16lo(y[e]) + bf16hi(x[e]) * bf16hi(y[e]);
+  return acc;
+}
+
+// Host: the one place a launch picks its kernel instantiation.  f(dh, drop) is called with std::integral_constant<int, 64 | 96> for
+// head_dim (validated by the entry points of attention.hip) and std::bool_constant for `drop`; a kernel without a dropout parameter
+// ignores the second.
+template <typename F>
+void attn_select(int head_dim, bool drop, const F& f) {
+  auto with_dh = [&](auto dh) { if (drop) f(dh, std::true_type{}); else f(dh, std::false_type{}); };
+  if (head_dim == 96) with_dh(std::integral_constant<int, 96>{}); else with_dh(std::integral_constant<int, 64>{});
+}
 
 // Combine a value with its partner in the other half-wave (lane i <-> lane i + 32) without the LDS round trip of
 // ds_bpermute: v_permlane32_swap exchanges lanes 32-63 of its first operand with lanes 0-31 of its second, so with
@@ -110,6 +136,15 @@ struct RowLoad {
     for (int ks = 0; ks < DH / 16; ++ks) f[ks] = row_frag<DH>(slice, 0, ks, lane);
   }
 };
+
+// The lane id read again behind a kernel's sweep, for store_rows_lds: the store's per-lane LDS / global offsets depend on the lane
+// only, so formed from the lane id of the kernel's entry they are carried (spilled) around the sweep (guide: "recompute per block
+// (v_mbcnt)")
+__device__ __forceinline__ int lane_again() {
+  int lane;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  return lane;
+}
 
 // store a [d][q or key] accumulator set as rows of a (T, ld) bf16 matrix: lane owns row (row0 + (l&31)),
 // register 4g+i of tile dt is column 32 dt + 8 g + 4 (l>>5) + i.

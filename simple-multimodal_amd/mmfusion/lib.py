@@ -394,23 +394,24 @@ def gemm_grouped_chain(chains: Sequence[GemmChain], layout: int, epilogue: int) 
         check(load().mmf_gemm_grouped_chain(arr, len(chains), layout, epilogue, stream_ptr()))
 
 
+def _attn_call(label: str, factor: float, problems: Sequence[AttnProblem], head_dim: int, entry: str, *args) -> None:
+    """One grouped-attention call ``entry(problems, n, head_dim, *args, stream)`` inside its ``_Timed`` bracket ``label<head_dim>``.
+    ``factor``: the pass's algorithmic FLOPs per B*H*Tq*Tk*head_dim — 4 for the forward (S, P.V), 8 for the backward (dV, dP, dQ,
+    dK), 4 for the uniform backward (dQ, dK) and for delta (S, dP); the recomputed S of a backward is not credited."""
+    arr = (AttnProblem * len(problems))(*problems)
+    flops = sum(factor * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
+    with _Timed(f"{label}<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
+        check(getattr(load(), entry)(arr, len(problems), head_dim, *args, stream_ptr()))
+
+
 def attn_fwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: float, dropout_p: float = 0.0,
                      rng_state_ptr: Optional[int] = None, site: int = 0) -> None:
-    arr = (AttnProblem * len(problems))(*problems)
-    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    with _Timed(f"attn_fwd_kernel<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
-        check(load().mmf_attn_fwd_grouped_ex(arr, len(problems), head_dim, scale, dropout_p, rng_state_ptr, site,
-                                             stream_ptr()))
+    _attn_call("attn_fwd_kernel", 4.0, problems, head_dim, "mmf_attn_fwd_grouped_ex", scale, dropout_p, rng_state_ptr, site)
 
 
 def attn_bwd_grouped(problems: Sequence[AttnProblem], head_dim: int, scale: float, dropout_p: float = 0.0,
                      rng_state_ptr: Optional[int] = None, site: int = 0) -> None:
-    arr = (AttnProblem * len(problems))(*problems)
-    # algorithmic backward work: 4 products of 2*Tq*Tk*dh (dV, dP, dQ, dK); the recomputed S is not credited
-    flops = sum(8.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    with _Timed(f"attn_bwd_kernels<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
-        check(load().mmf_attn_bwd_grouped_ex(arr, len(problems), head_dim, scale, dropout_p, rng_state_ptr, site,
-                                             stream_ptr()))
+    _attn_call("attn_bwd_kernels", 8.0, problems, head_dim, "mmf_attn_bwd_grouped_ex", scale, dropout_p, rng_state_ptr, site)
 
 
 def attn_bwd_uniform_available(head_dim: int, dropout_p: float) -> bool:
@@ -428,29 +429,19 @@ def attn_bwd_grouped_uniform(problems: Sequence[AttnProblem], head_dim: int, sca
     one gradient row per batch row (include/mmfusion.h).  ``workspace``: a contiguous f32 tensor of at least
     ``attn_bwd_uniform_workspace_bytes(problems)`` bytes (it need not be initialised).  ``pooled`` = (pointers, lddy): per problem
     the (B, lddy) gradient of the pooled output, from which the launch itself writes those rows (``mmf_attn_bwd_grouped_pooled``)."""
-    arr = (AttnProblem * len(problems))(*problems)
-    # algorithmic work left: dQ and dK, 2 products of 2*Tq*Tk*dh; the recomputed S is not credited
-    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    nbytes = workspace.numel() * workspace.element_size()
-    with _Timed(f"attn_bwd_uniform_kernels<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
-        if pooled is None:
-            check(load().mmf_attn_bwd_grouped_uniform(arr, len(problems), head_dim, scale, workspace.data_ptr(), nbytes, stream_ptr()))
-        else:
-            dys = (C.c_void_p * len(problems))(*pooled[0])
-            check(load().mmf_attn_bwd_grouped_pooled(arr, len(problems), head_dim, scale, dys, pooled[1], workspace.data_ptr(), nbytes,
-                                                     stream_ptr()))
+    ws = (workspace.data_ptr(), workspace.numel() * workspace.element_size())
+    if pooled is None:
+        _attn_call("attn_bwd_uniform_kernels", 4.0, problems, head_dim, "mmf_attn_bwd_grouped_uniform", scale, *ws)
+    else:
+        dys = (C.c_void_p * len(problems))(*pooled[0])
+        _attn_call("attn_bwd_uniform_kernels", 4.0, problems, head_dim, "mmf_attn_bwd_grouped_pooled", scale, dys, pooled[1], *ws)
 
 
 def attn_bwd_grouped_exact_delta(problems: Sequence[AttnProblem], head_dim: int, scale: float) -> None:
     """``attn_bwd_grouped`` (no dropout) with delta = sum_j p_ij dp_ij formed in f32 by ``mmf_attn_delta_f32`` instead of dO . O from
     the bf16 O: one more pass over the keys, for gradients that the rounding of O would otherwise bury (include/mmfusion.h)"""
-    arr = (AttnProblem * len(problems))(*problems)
-    shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
-    flops = sum(p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    with _Timed(f"attn_delta_kernel<{head_dim}>", 4.0 * flops, shapes):
-        check(load().mmf_attn_delta_f32(arr, len(problems), head_dim, scale, stream_ptr()))
-    with _Timed(f"attn_bwd_kernels<{head_dim}>", 8.0 * flops, shapes):
-        check(load().mmf_attn_bwd_grouped_delta(arr, len(problems), head_dim, scale, stream_ptr()))
+    _attn_call("attn_delta_kernel", 4.0, problems, head_dim, "mmf_attn_delta_f32", scale)
+    _attn_call("attn_bwd_kernels", 8.0, problems, head_dim, "mmf_attn_bwd_grouped_delta", scale)
 
 
 def _drop_args(who: str, drop) -> tuple:
@@ -468,28 +459,18 @@ def _drop_args(who: str, drop) -> tuple:
 def attn_fwd_grouped_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
     """``attn_fwd_grouped`` with dropout of the probabilities, ``drop`` = (p, state, site, stream_base): the stream id of (problem, b,
     h) is problem * 4096 + stream_base + b H + h (``mmf_attn_fwd_grouped_keyed``); lse stays the undropped one"""
-    arr = (AttnProblem * len(problems))(*problems)
-    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    with _Timed(f"attn_fwd_kernel<{head_dim}>", flops, [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None):
-        check(load().mmf_attn_fwd_grouped_keyed(arr, len(problems), head_dim, scale, *_drop_args("attn_fwd_grouped_keyed", drop), stream_ptr()))
+    _attn_call("attn_fwd_kernel", 4.0, problems, head_dim, "mmf_attn_fwd_grouped_keyed", scale, *_drop_args("attn_fwd_grouped_keyed", drop))
 
 
 def attn_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
     """delta = sum_j p_ij w_ij dp_ij in f32 under the mask of ``drop`` (``mmf_attn_delta_f32_keyed``)"""
-    arr = (AttnProblem * len(problems))(*problems)
-    shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
-    flops = sum(4.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    with _Timed(f"attn_delta_kernel<{head_dim}>", flops, shapes):
-        check(load().mmf_attn_delta_f32_keyed(arr, len(problems), head_dim, scale, *_drop_args("attn_delta_keyed", drop), stream_ptr()))
+    _attn_call("attn_delta_kernel", 4.0, problems, head_dim, "mmf_attn_delta_f32_keyed", scale, *_drop_args("attn_delta_keyed", drop))
 
 
 def attn_bwd_grouped_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
     """the backward from a given delta under the mask of ``drop`` (``mmf_attn_bwd_grouped_delta_keyed``)"""
-    arr = (AttnProblem * len(problems))(*problems)
-    shapes = [(p.Tq, p.Tk) for p in problems] if PROFILE is not None else None
-    flops = sum(8.0 * p.B * p.H * p.Tq * p.Tk * head_dim for p in problems) if PROFILE is not None else 0.0
-    with _Timed(f"attn_bwd_kernels<{head_dim}>", flops, shapes):
-        check(load().mmf_attn_bwd_grouped_delta_keyed(arr, len(problems), head_dim, scale, *_drop_args("attn_bwd_grouped_delta_keyed", drop), stream_ptr()))
+    _attn_call("attn_bwd_kernels", 8.0, problems, head_dim, "mmf_attn_bwd_grouped_delta_keyed", scale,
+               *_drop_args("attn_bwd_grouped_delta_keyed", drop))
 
 
 def attn_bwd_grouped_exact_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:
