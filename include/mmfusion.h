@@ -815,6 +815,30 @@ int mmf_w2v_conv0_norm_gelu(const float* wave, const float* weight, const float*
  * form, f32, one rounding), T_out = (T_in - k) / s + 1: the A operand of the next conv layer as ONE NT GEMM against its weight
  * repacked to (C_out, k*C), column (j, c).  C % 8 == 0, N <= 65535, out must not be x. */
 int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, int T_in, int C, int k, int s, void* stream);
+/* Its mirror, the backward of GELU + window form: dwin (N, T_out, k*C) bf16, the gradient of the window form, and the raw x
+ * (N, T_in, C) bf16 -> dx (N, T_in, C) bf16,
+ *   dx[n][f][c] = gelu'(x[n][f][c]) * sum_{j < k, (f - j) % s == 0, 0 <= (f - j) / s < T_out} dwin[n][(f - j) / s][j*C + c],
+ * a gather (each lane owns 8 channels of one frame of dx), the sum in f32 in tap order, one rounding.  Frames no window reads
+ * (past s*(T_out - 1) + k - 1) are written as zeros.  C % 8 == 0, k >= s >= 1, N <= 65535; dx may be x, dwin neither. */
+int mmf_w2v_window_fold_gelu_bwd(const void* dwin_bf16, const void* x_bf16, void* dx_bf16, int N, int T_in, int C, int k, int s,
+                                 void* stream);
+/* Layer 0's backward, two passes that recompute c = conv0(wave) as the forward's do and fold dwin1 (N, T1, k1*C0) bf16, the
+ * gradient of mmf_w2v_conv0_norm_gelu's output, themselves: with xhat = (c - mean) rstd, y = gamma xhat + beta (stats: the
+ * forward's), da0 = the fold of dwin1 (zero on the frames layer 1 never reads) and dy = da0 gelu'(y), all f32:
+ *   _bwd_stats  sums (N, 2, C0) f32 = S1 = sum_t dy | S2 = sum_t dy xhat per (clip, channel), summed per frame lane and merged in
+ *               slot order; then dbeta (+)= sum_n S1 and dgamma (+)= sum_n S2 in clip order (f32 [C0]).
+ *               partial: N * MMF_W2V_STATS_SLOTS * 2 * C0 floats of scratch.
+ *   _bwd_wgrad  dc = gamma rstd (dy - S1 / T0 - xhat S2 / T0) on ALL T0 frames (one that layer 1 never reads has dy = 0 but took
+ *               part in the statistics); dweight (C0, k0) f32 (+)= sum_{n, t} dc[n][t][ch] wave[n][s0 t + j], through per-lane
+ *               partials (clip-major, then slot) added in a fixed tree.  partial: N * MMF_W2V_STATS_SLOTS * C0 * k0 floats of scratch.
+ * accumulate != 0 adds to the outputs, 0 overwrites them.  No atomics: the same bits on every run.  The limits of
+ * mmf_w2v_conv0_norm_gelu; stats / sums / partial 16-byte aligned. */
+int mmf_w2v_conv0_bwd_stats(const float* wave, const float* weight, const float* stats, const float* gamma, const float* beta,
+                            const void* dwin1_bf16, float* sums, float* partial, float* dgamma, float* dbeta, int N, int L, int C0,
+                            int k0, int s0, int k1, int s1, float eps, int accumulate, void* stream);
+int mmf_w2v_conv0_bwd_wgrad(const float* wave, const float* weight, const float* stats, const float* gamma, const float* beta,
+                            const void* dwin1_bf16, const float* sums, float* partial, float* dweight, int N, int L, int C0, int k0,
+                            int s0, int k1, int s1, float eps, int accumulate, void* stream);
 /* The positional convolution with its residual: y = x + gelu(conv(x) + bias), x / y (N, T, C) bf16, Conv1d(C -> C, kernel k,
  * padding k/2, `groups` groups; for an even k the extra last frame is dropped) on the MFMA units with f32 accumulation.
  * w_bf16: (groups, cg, Kp) with cg = C / groups, Kp = k*cg rounded up to a multiple of 32, w[g][co][j*cg + ci] = the

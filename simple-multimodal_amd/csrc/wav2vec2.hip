@@ -4,6 +4,8 @@
 //   conv0_stats / conv0_norm_gelu   layer 0: Conv1d(1 -> C0, k0, s0) + GroupNorm(one group per channel) + GELU in two passes
 //                                   that both recompute the k0 MACs per output; no f32 intermediate is stored
 //   gelu_window                     GELU + the (T_out, k*C) window form the next conv layer's GEMM reads
+//   window_fold_gelu_bwd            its mirror: the gradient of the window form gathered back to the raw output's, times gelu'
+//   conv0_bwd_stats / _bwd_wgrad    layer 0's backward: GroupNorm's two sums per channel, then dW0, recomputing as the forward does
 //   posconv                         the grouped positional convolution as one MFMA GEMM per (clip, group, 128 time rows); the same
 //                                   body with two more epilogues is its backward's dz = dy gelu'(z) and input gradient
 //   posconv_wgrad                   its weight gradient: an MFMA GEMM per (group, 8 taps) whose contraction runs over time
@@ -145,6 +147,213 @@ void w2v_gelu_window_kernel(const unsigned short* __restrict__ x, unsigned short
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = gelu_erf(a[e]);
     *reinterpret_cast<u32x4_t*>(dst + (size_t)v * 8) = pack8(a);
+  }
+}
+
+// ---- backward of the window form ---------------------------------------------------------------------------
+// The fold of a window-form gradient dwin (T_out, k*C) of one clip at input frame f, channels c .. c + 7: the rows t and taps j with
+// s t + j == f, j ascending (j = f % s, f % s + s, ...), added in f32 in that order.  Returns whether any window reads the frame.
+__device__ __forceinline__ bool w2v_fold8(const unsigned short* __restrict__ dwin, int f, int c, int C, int k, int s, int T_out,
+                                          float (&acc)[8]) {
+  bool any = false;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+  for (int j = f % s; j < k && j <= f; j += s) {
+    const int t = (f - j) / s;
+    if (t >= T_out) continue;
+    float a[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(dwin + ((size_t)t * k + j) * C + c), a);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += a[e];
+    any = true;
+  }
+  return any;
+}
+
+// The mirror of w2v_gelu_window_kernel: dx[f][c] = gelu'(x[f][c]) * fold(dwin)[f][c].  The lanes walk dx in order, 8 channels each
+// (a gather: no lane writes what another one does).  A frame no window reads is written as zeros.  dx may be x: a lane reads its
+// own 16 bytes of x before it writes them.
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_window_fold_gelu_bwd_kernel(const unsigned short* __restrict__ dwin, const unsigned short* x, unsigned short* dx, int T_in,
+                                     int T_out, int C, int k, int s, unsigned cv /* C/8 */, unsigned nvec /* T_in*C/8 */) {
+  const unsigned short* __restrict__ g = dwin + (size_t)blockIdx.y * T_out * k * C;
+  const size_t base = (size_t)blockIdx.y * nvec * 8;
+  const unsigned stride = gridDim.x * W2V_THREADS;
+  for (unsigned v = blockIdx.x * W2V_THREADS + threadIdx.x; v < nvec; v += stride) {
+    const unsigned f = v / cv, c = (v - f * cv) << 3;
+    float acc[8], a[8];
+    const bool any = w2v_fold8(g, (int)f, (int)c, C, k, s, T_out, acc);
+    unpack8(*reinterpret_cast<const u32x4_t*>(x + base + (size_t)v * 8), a);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = any ? acc[e] * gelu_erf_grad(a[e]) : 0.0f;
+    *reinterpret_cast<u32x4_t*>(dx + base + (size_t)v * 8) = pack8(acc);
+  }
+}
+
+// ---- layer 0: backward ---------------------------------------------------------------------------------------
+// With c = conv0(wave), xhat = (c - mean) rstd, y = gamma xhat + beta: da0 = the fold of dwin_1 (zero on the frames layer 1 never
+// reads), dy = da0 gelu'(y).  Both passes recompute c on the Conv0 body and fold dwin_1 themselves; nothing (T0, C0)-sized is stored.
+template <int K0>
+struct Conv0Bwd {
+  Conv0<K0> cv;
+  float mean[8], rstd[8], scale[8], shift[8];
+  __device__ __forceinline__ void load(const float* __restrict__ wt, const float* __restrict__ st, const float* __restrict__ gamma,
+                                       const float* __restrict__ beta, int c, int C0, int k0, float eps) {
+    cv.load(wt, c, k0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      mean[e] = st[e];
+      rstd[e] = rsqrtf(st[C0 + e] + eps);
+      scale[e] = gamma[c + e] * rstd[e];                   // y exactly as the forward forms it
+      shift[e] = beta[c + e] - st[e] * scale[e];
+    }
+  }
+  // frame f of the clip at xs: xhat, and dy (zero where `read` is false: past the last frame layer 1 reads)
+  __device__ __forceinline__ void frame(const float* __restrict__ xs, float* x, const unsigned short* __restrict__ dwin, int f, int c,
+                                        int C0, int k0, int s0, int k1, int s1, int T1, bool read, float* xhat, float* dy) const {
+#pragma unroll
+    for (int j = 0; j < K0; ++j) x[j] = j < k0 ? xs[(size_t)f * s0 + j] : 0.0f;
+    float v[8], da[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float a = 0.0f;
+#pragma unroll
+      for (int j = 0; j < K0; ++j) a = fmaf(cv.w[e][j], x[j], a);
+      v[e] = a;
+      xhat[e] = (a - mean[e]) * rstd[e];
+      dy[e] = 0.0f;
+    }
+    if (read && w2v_fold8(dwin, f, c, C0, k1, s1, T1, da)) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dy[e] = da[e] * gelu_erf_grad(fmaf(v[e], scale[e], shift[e]));
+    }
+  }
+};
+
+// pass 1a: S1 = sum dy, S2 = sum dy xhat over this thread's frames f = slot, slot + nslots, ... -> partial[clip][slot][S1 | S2][C0]
+template <int K0>
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_conv0_bwd_partial_kernel(const float* __restrict__ wave, const float* __restrict__ wt, const float* __restrict__ stats,
+                                  const float* __restrict__ gamma, const float* __restrict__ beta, const unsigned short* __restrict__ dwin,
+                                  float* __restrict__ partial, int L, int C0, int k0, int s0, int k1, int s1, int T1, float eps,
+                                  int nfl, int cgn) {
+  const int cgi = threadIdx.x % cgn, fl = threadIdx.x / cgn;
+  if (fl >= nfl) return;
+  const int slot = blockIdx.x * nfl + fl, nslots = gridDim.x * nfl, c = cgi * 8;
+  Conv0Bwd<K0> b;
+  b.load(wt, stats + (size_t)blockIdx.y * 2 * C0 + c, gamma, beta, c, C0, k0, eps);
+  const float* __restrict__ xs = wave + (size_t)blockIdx.y * L;
+  const unsigned short* __restrict__ g = dwin + (size_t)blockIdx.y * T1 * k1 * C0;
+  const int last = s1 * (T1 - 1) + k1 - 1;                 // the last frame layer 1 reads: dy is zero past it
+  float s1v[8], s2v[8], x[K0], xhat[8], dy[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s1v[e] = s2v[e] = 0.0f;
+  for (int f = slot; f <= last; f += nslots) {
+    b.frame(xs, x, g, f, c, C0, k0, s0, k1, s1, T1, true, xhat, dy);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      s1v[e] += dy[e];
+      s2v[e] = fmaf(dy[e], xhat[e], s2v[e]);
+    }
+  }
+  float* __restrict__ p = partial + (((size_t)blockIdx.y * W2V_SLOTS + slot) * 2) * C0 + c;
+  *reinterpret_cast<f32x4_t*>(p) = f32x4_t{s1v[0], s1v[1], s1v[2], s1v[3]};
+  *reinterpret_cast<f32x4_t*>(p + 4) = f32x4_t{s1v[4], s1v[5], s1v[6], s1v[7]};
+  *reinterpret_cast<f32x4_t*>(p + C0) = f32x4_t{s2v[0], s2v[1], s2v[2], s2v[3]};
+  *reinterpret_cast<f32x4_t*>(p + C0 + 4) = f32x4_t{s2v[4], s2v[5], s2v[6], s2v[7]};
+}
+
+// pass 1b: the slots of one (clip, channel) added in slot order -> sums[clip][S1 | S2][C0]
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_conv0_bwd_merge_kernel(const float* __restrict__ partial, float* __restrict__ sums, int C0, int nslots) {
+  const int c = blockIdx.x * W2V_THREADS + threadIdx.x;
+  if (c >= C0) return;
+  const float* __restrict__ p = partial + (size_t)blockIdx.y * W2V_SLOTS * 2 * C0 + c;
+  float a = 0.0f, b = 0.0f;
+  for (int s = 0; s < nslots; ++s) {
+    a += p[(size_t)s * 2 * C0];
+    b += p[(size_t)s * 2 * C0 + C0];
+  }
+  sums[(size_t)blockIdx.y * 2 * C0 + c] = a;
+  sums[(size_t)blockIdx.y * 2 * C0 + C0 + c] = b;
+}
+
+// pass 1c: dbeta (+)= sum_n S1, dgamma (+)= sum_n S2, the clips in order
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_conv0_bwd_affine_kernel(const float* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int C0,
+                                 int accumulate) {
+  const int c = blockIdx.x * W2V_THREADS + threadIdx.x;
+  if (c >= C0) return;
+  float a = accumulate ? dbeta[c] : 0.0f, b = accumulate ? dgamma[c] : 0.0f;
+  for (int n = 0; n < N; ++n) {
+    a += sums[(size_t)n * 2 * C0 + c];
+    b += sums[(size_t)n * 2 * C0 + C0 + c];
+  }
+  dbeta[c] = a;
+  dgamma[c] = b;
+}
+
+// pass 2a: dc = gamma rstd (dy - S1 / T0 - xhat S2 / T0) on ALL T0 frames (a frame layer 1 never reads has dy = 0 but took part in
+// the statistics), dW0[ch][j] partial = sum over this thread's frames of dc[ch] wave[s0 f + j] -> partial[clip * nslots + slot][C0][k0]
+template <int K0>
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_conv0_bwd_wgrad_kernel(const float* __restrict__ wave, const float* __restrict__ wt, const float* __restrict__ stats,
+                                const float* __restrict__ gamma, const float* __restrict__ beta, const unsigned short* __restrict__ dwin,
+                                const float* __restrict__ sums, float* __restrict__ partial, int L, int T0, int C0, int k0, int s0,
+                                int k1, int s1, int T1, float eps, int nfl, int cgn) {
+  const int cgi = threadIdx.x % cgn, fl = threadIdx.x / cgn;
+  if (fl >= nfl) return;
+  const int slot = blockIdx.x * nfl + fl, nslots = gridDim.x * nfl, c = cgi * 8;
+  Conv0Bwd<K0> b;
+  b.load(wt, stats + (size_t)blockIdx.y * 2 * C0 + c, gamma, beta, c, C0, k0, eps);
+  const float* __restrict__ xs = wave + (size_t)blockIdx.y * L;
+  const unsigned short* __restrict__ g = dwin + (size_t)blockIdx.y * T1 * k1 * C0;
+  const float* __restrict__ sm = sums + (size_t)blockIdx.y * 2 * C0 + c;
+  const int last = s1 * (T1 - 1) + k1 - 1;
+  const float inv = 1.0f / (float)T0;
+  float m1[8], m2[8], acc[8][K0], x[K0], xhat[8], dy[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    m1[e] = sm[e] * inv;
+    m2[e] = sm[C0 + e] * inv;
+#pragma unroll
+    for (int j = 0; j < K0; ++j) acc[e][j] = 0.0f;
+  }
+  for (int f = slot; f < T0; f += nslots) {
+    b.frame(xs, x, g, f, c, C0, k0, s0, k1, s1, T1, f <= last, xhat, dy);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float dc = b.scale[e] * (dy[e] - m1[e] - xhat[e] * m2[e]);
+#pragma unroll
+      for (int j = 0; j < K0; ++j) acc[e][j] = fmaf(dc, x[j], acc[e][j]);
+    }
+  }
+  float* __restrict__ p = partial + ((size_t)blockIdx.y * nslots + slot) * C0 * k0 + (size_t)c * k0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+#pragma unroll
+    for (int j = 0; j < K0; ++j)
+      if (j < k0) p[e * k0 + j] = acc[e][j];
+}
+
+// pass 2b: dW0 (+)= the sum of the rows of partial (clip-major, then slot).  A workgroup owns WM_COLS output elements; its WM_RUNS
+// thread rows each add one contiguous run of partial rows in order, and the runs' sums are added in run order: a fixed tree
+constexpr int WM_COLS = 32, WM_RUNS = W2V_THREADS / WM_COLS;
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_conv0_bwd_wgrad_merge_kernel(const float* __restrict__ partial, float* __restrict__ dw, int numel, int rows, int accumulate) {
+  __shared__ float part[WM_RUNS][WM_COLS];
+  const int col = threadIdx.x % WM_COLS, run = threadIdx.x / WM_COLS, i = blockIdx.x * WM_COLS + col;
+  const int per = (rows + WM_RUNS - 1) / WM_RUNS, r0 = run * per, r1 = min(rows, r0 + per);
+  float a = 0.0f;
+  if (i < numel)
+    for (int r = r0; r < r1; ++r) a += partial[(size_t)r * numel + i];
+  part[run][col] = a;
+  __syncthreads();
+  if (run == 0 && i < numel) {
+    float s = accumulate ? dw[i] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < WM_RUNS; ++g) s += part[g][col];
+    dw[i] = s;
   }
 }
 
@@ -541,6 +750,91 @@ extern "C" int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, in
   hipLaunchKernelGGL(w2v_gelu_window_kernel, dim3(mmf_stream_grid(nvec, W2V_THREADS), N), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(x_bf16), static_cast<unsigned short*>(out_bf16), T_in, C, k, s, (unsigned)(C / 8), (unsigned)nvec);
   MMF_CHECK_LAUNCH("mmf_w2v_gelu_window");
+  return MMF_OK;
+}
+
+extern "C" int mmf_w2v_window_fold_gelu_bwd(const void* dwin_bf16, const void* x_bf16, void* dx_bf16, int N, int T_in, int C, int k, int s,
+                                            void* stream) {
+  if (!dwin_bf16 || !x_bf16 || !dx_bf16 || N <= 0 || T_in <= 0 || C <= 0 || k <= 0 || s <= 0)
+    MMF_FAIL(MMF_E_SHAPE, "mmf_w2v_window_fold_gelu_bwd: null operand or N=%d T_in=%d C=%d k=%d s=%d", N, T_in, C, k, s);
+  if (T_in < k) MMF_FAIL(MMF_E_SHAPE, "mmf_w2v_window_fold_gelu_bwd: T_in=%d is shorter than the kernel k=%d", T_in, k);
+  const int64_t T_out = (T_in - k) / s + 1, wvec = T_out * k * (C / 8), nvec = (int64_t)T_in * (C / 8);
+  if ((C & 7) || k < s || N > 65535 || wvec >= (int64_t)1 << 31 || nvec >= (int64_t)1 << 31 || dwin_bf16 == x_bf16 || dwin_bf16 == dx_bf16)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "mmf_w2v_window_fold_gelu_bwd: C=%d (multiple of 8), k=%d >= s=%d, N=%d (at most 65535), %lld window "
+             "elements per clip (below 2^34), dwin must be neither x nor dx", C, k, s, N, (long long)wvec * 8);
+  if (!mmf_aligned16(dwin_bf16) || !mmf_aligned16(x_bf16) || !mmf_aligned16(dx_bf16))
+    MMF_FAIL(MMF_E_ALIGN, "mmf_w2v_window_fold_gelu_bwd: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(w2v_window_fold_gelu_bwd_kernel, dim3(mmf_stream_grid(nvec, W2V_THREADS), N), dim3(W2V_THREADS), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(dwin_bf16), static_cast<const unsigned short*>(x_bf16),
+                     static_cast<unsigned short*>(dx_bf16), T_in, (int)T_out, C, k, s, (unsigned)(C / 8), (unsigned)nvec);
+  MMF_CHECK_LAUNCH("mmf_w2v_window_fold_gelu_bwd");
+  return MMF_OK;
+}
+
+namespace {
+
+// shared validation of layer 0's two backward entry points -> the launch shape of mmf_w2v_conv0_stats (nblk workgroups of nfl frame lanes)
+int conv0_bwd_check(const char* fn, const void* const* f32s, int nf32, const void* dwin, int N, int L, int C0, int k0, int s0, int k1,
+                    int s1, Conv0Shape* sh, int* nblk) {
+  for (int i = 0; i < nf32; ++i)
+    if (!f32s[i]) MMF_FAIL(MMF_E_SHAPE, "%s: null operand", fn);
+  if (!dwin) MMF_FAIL(MMF_E_SHAPE, "%s: null operand", fn);
+  if (int rc = conv0_check(fn, N, L, C0, k0, s0, sh)) return rc;
+  if (k1 <= 0 || s1 <= 0 || sh->T0 < k1) MMF_FAIL(MMF_E_SHAPE, "%s: k1=%d s1=%d against T0=%d frames", fn, k1, s1, sh->T0);
+  sh->T1 = (sh->T0 - k1) / s1 + 1;
+  if ((int64_t)sh->T1 * k1 * (C0 / 8) >= (int64_t)1 << 31)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: %lld window elements per clip (below 2^34)", fn, (long long)sh->T1 * k1 * C0);
+  if (!mmf_aligned16(dwin)) MMF_FAIL(MMF_E_ALIGN, "%s: dwin_1 must be 16-byte aligned", fn);
+  for (int i = 0; i < nf32; ++i)
+    if (reinterpret_cast<uintptr_t>(f32s[i]) & 3u) MMF_FAIL(MMF_E_ALIGN, "%s: the f32 operands must be 4-byte aligned", fn);
+  *nblk = sh->nblk;
+  if ((int64_t)*nblk * sh->nfl > sh->T0) *nblk = (sh->T0 + sh->nfl - 1) / sh->nfl;
+  return MMF_OK;
+}
+
+}  // namespace
+
+extern "C" int mmf_w2v_conv0_bwd_stats(const float* wave, const float* weight, const float* stats, const float* gamma, const float* beta,
+                                       const void* dwin1_bf16, float* sums, float* partial, float* dgamma, float* dbeta, int N, int L,
+                                       int C0, int k0, int s0, int k1, int s1, float eps, int accumulate, void* stream) {
+  const char* fn = "mmf_w2v_conv0_bwd_stats";
+  const void* f32s[] = {wave, weight, stats, gamma, beta, sums, partial, dgamma, dbeta};
+  Conv0Shape sh;
+  int nblk;
+  if (int rc = conv0_bwd_check(fn, f32s, 9, dwin1_bf16, N, L, C0, k0, s0, k1, s1, &sh, &nblk)) return rc;
+  if (!mmf_aligned16(stats) || !mmf_aligned16(sums) || !mmf_aligned16(partial))
+    MMF_FAIL(MMF_E_ALIGN, "%s: stats / sums / partial must be 16-byte aligned", fn);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned short* dwin = static_cast<const unsigned short*>(dwin1_bf16);
+  const int nslots = nblk * sh.nfl;                                       // <= MMF_W2V_STATS_SLOTS
+  if (k0 <= 10) hipLaunchKernelGGL(w2v_conv0_bwd_partial_kernel<10>, dim3(nblk, N), dim3(W2V_THREADS), 0, s, wave, weight, stats, gamma, beta, dwin, partial, L, C0, k0, s0, k1, s1, sh.T1, eps, sh.nfl, sh.cgn);
+  else          hipLaunchKernelGGL(w2v_conv0_bwd_partial_kernel<16>, dim3(nblk, N), dim3(W2V_THREADS), 0, s, wave, weight, stats, gamma, beta, dwin, partial, L, C0, k0, s0, k1, s1, sh.T1, eps, sh.nfl, sh.cgn);
+  MMF_CHECK_LAUNCH(fn);
+  const int cblk = (C0 + W2V_THREADS - 1) / W2V_THREADS;
+  hipLaunchKernelGGL(w2v_conv0_bwd_merge_kernel, dim3(cblk, N), dim3(W2V_THREADS), 0, s, partial, sums, C0, nslots);
+  MMF_CHECK_LAUNCH(fn);
+  hipLaunchKernelGGL(w2v_conv0_bwd_affine_kernel, dim3(cblk), dim3(W2V_THREADS), 0, s, sums, dgamma, dbeta, N, C0, accumulate);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_w2v_conv0_bwd_wgrad(const float* wave, const float* weight, const float* stats, const float* gamma, const float* beta,
+                                       const void* dwin1_bf16, const float* sums, float* partial, float* dweight, int N, int L, int C0,
+                                       int k0, int s0, int k1, int s1, float eps, int accumulate, void* stream) {
+  const char* fn = "mmf_w2v_conv0_bwd_wgrad";
+  const void* f32s[] = {wave, weight, stats, gamma, beta, sums, partial, dweight};
+  Conv0Shape sh;
+  int nblk;
+  if (int rc = conv0_bwd_check(fn, f32s, 8, dwin1_bf16, N, L, C0, k0, s0, k1, s1, &sh, &nblk)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned short* dwin = static_cast<const unsigned short*>(dwin1_bf16);
+  const int nslots = nblk * sh.nfl;
+  if (k0 <= 10) hipLaunchKernelGGL(w2v_conv0_bwd_wgrad_kernel<10>, dim3(nblk, N), dim3(W2V_THREADS), 0, s, wave, weight, stats, gamma, beta, dwin, sums, partial, L, sh.T0, C0, k0, s0, k1, s1, sh.T1, eps, sh.nfl, sh.cgn);
+  else          hipLaunchKernelGGL(w2v_conv0_bwd_wgrad_kernel<16>, dim3(nblk, N), dim3(W2V_THREADS), 0, s, wave, weight, stats, gamma, beta, dwin, sums, partial, L, sh.T0, C0, k0, s0, k1, s1, sh.T1, eps, sh.nfl, sh.cgn);
+  MMF_CHECK_LAUNCH(fn);
+  const int numel = C0 * k0;
+  hipLaunchKernelGGL(w2v_conv0_bwd_wgrad_merge_kernel, dim3((numel + WM_COLS - 1) / WM_COLS), dim3(W2V_THREADS), 0, s, partial, dweight, numel, N * nslots, accumulate);
+  MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }
 

@@ -43,6 +43,7 @@ SYMBOLS = (
     "mmf_vit_patchify", "mmf_vit_embed_tokens", "mmf_vit_embed_tokens_bwd", "mmf_vit_cls_attn_bwd", "mmf_bias_gelu_bf16", "mmf_bias_gelu_bf16_to", "mmf_bias_gelu_bwd_bf16",
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
     "mmf_w2v_posconv_bwd_act", "mmf_w2v_posconv_dgrad", "mmf_w2v_posconv_wgrad", "mmf_w2v_weightnorm_bwd",
+    "mmf_w2v_window_fold_gelu_bwd", "mmf_w2v_conv0_bwd_stats", "mmf_w2v_conv0_bwd_wgrad",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
     "mmf_deberta_embed_bwd_params_workspace_bytes", "mmf_deberta_embed_bwd_params", "mmf_embedding_scatter_add_f32",
@@ -262,6 +263,9 @@ def load() -> C.CDLL:
     lib.mmf_w2v_conv0_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_conv0_norm_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_w2v_gelu_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_window_fold_gelu_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_conv0_bwd_stats.argtypes = [vp] * 10 + [i32] * 7 + [f32, i32, vp]
+    lib.mmf_w2v_conv0_bwd_wgrad.argtypes = [vp] * 9 + [i32] * 7 + [f32, i32, vp]
     lib.mmf_w2v_posconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_posconv_bwd_act.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_posconv_dgrad.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -692,6 +696,60 @@ def w2v_gelu_window(x, out, N: int, T_in: int, C: int, k: int, s: int) -> None:
         raise ValueError("w2v_gelu_window: operand sizes do not match N, T_in, C, k, s")
     with _Timed("w2v_gelu_window_kernel", 0.0, [(N * T_out, k * C)]):
         check(load().mmf_w2v_gelu_window(x.data_ptr(), out.data_ptr(), N, T_in, C, k, s, stream_ptr()))
+
+
+def w2v_window_fold_gelu_bwd(dwin, x, dx, N: int, T_in: int, C: int, k: int, s: int) -> None:
+    """dwin (N, T_out, k * C) bf16, the gradient of ``w2v_gelu_window``'s output, and its raw input x (N, T_in, C) bf16 -> dx like x:
+    gelu'(x) times the fold of dwin, zeros on the frames no window reads; dx may be x"""
+    _w2v_bf16(dwin, x, dx)
+    T_out = (T_in - k) // s + 1
+    if T_out < 1 or dwin.numel() < N * T_out * k * C or x.numel() < N * T_in * C or dx.numel() < N * T_in * C \
+            or not (dwin.is_contiguous() and x.is_contiguous() and dx.is_contiguous()):
+        raise ValueError("w2v_window_fold_gelu_bwd: operand sizes do not match N, T_in, C, k, s")
+    with _Timed("w2v_window_fold_gelu_bwd_kernel", 0.0, [(N * T_in, C)]):
+        check(load().mmf_w2v_window_fold_gelu_bwd(dwin.data_ptr(), x.data_ptr(), dx.data_ptr(), N, T_in, C, k, s, stream_ptr()))
+
+
+def _w2v_conv0_bwd_sizes(who: str, wave, weight, stats, gamma, beta, dwin1, sums, k0: int, s0: int, k1: int, s1: int) -> tuple:
+    _w2v_f32(wave, weight, stats, gamma, beta, sums)
+    _w2v_bf16(dwin1)
+    N, L = wave.shape
+    C0 = weight.shape[0]
+    T0 = (L - k0) // s0 + 1
+    T1 = (T0 - k1) // s1 + 1
+    if weight.numel() != C0 * k0 or stats.numel() < N * 2 * C0 or sums.numel() < N * 2 * C0 or gamma.numel() != C0 or beta.numel() != C0 \
+            or T1 < 1 or dwin1.numel() < N * T1 * k1 * C0 or not dwin1.is_contiguous():
+        raise ValueError(f"{who}: operand sizes do not match N, L, C0 and the two kernels")
+    return N, L, C0, T0
+
+
+def w2v_conv0_bwd_stats(wave, weight, stats, gamma, beta, dwin1, sums, partial, dgamma, dbeta, k0: int, s0: int, k1: int, s1: int,
+                        eps: float, accumulate: bool = True) -> None:
+    """layer 0's backward, pass 1 (``mmf_w2v_conv0_bwd_stats``): dwin1 (N, T1, k1 * C0) bf16, the gradient of
+    ``w2v_conv0_norm_gelu``'s output -> sums (N, 2, C0) f32 = sum_t dy | sum_t dy xhat, and dgamma / dbeta (C0) f32 (+)= their sums
+    over the clips; partial: N * W2V_STATS_SLOTS * 2 * C0 floats of scratch"""
+    N, L, C0, _ = _w2v_conv0_bwd_sizes("w2v_conv0_bwd_stats", wave, weight, stats, gamma, beta, dwin1, sums, k0, s0, k1, s1)
+    _w2v_f32(partial, dgamma, dbeta)
+    if partial.numel() < N * W2V_STATS_SLOTS * 2 * C0 or dgamma.numel() != C0 or dbeta.numel() != C0:
+        raise ValueError("w2v_conv0_bwd_stats: partial / dgamma / dbeta do not match N, C0")
+    with _Timed("w2v_conv0_bwd_stats_kernels", 2.0 * N * ((L - k0) // s0 + 1) * C0 * k0, [(N, L)]):
+        check(load().mmf_w2v_conv0_bwd_stats(wave.data_ptr(), weight.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                             dwin1.data_ptr(), sums.data_ptr(), partial.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                             N, L, C0, k0, s0, k1, s1, eps, int(bool(accumulate)), stream_ptr()))
+
+
+def w2v_conv0_bwd_wgrad(wave, weight, stats, gamma, beta, dwin1, sums, partial, dweight, k0: int, s0: int, k1: int, s1: int, eps: float,
+                        accumulate: bool = True) -> None:
+    """layer 0's backward, pass 2 (``mmf_w2v_conv0_bwd_wgrad``): dweight (C0, 1, k0) f32 (+)= the convolution's weight gradient over
+    all T0 frames of the N clips, from pass 1's ``sums``; partial: N * W2V_STATS_SLOTS * C0 * k0 floats of scratch"""
+    N, L, C0, T0 = _w2v_conv0_bwd_sizes("w2v_conv0_bwd_wgrad", wave, weight, stats, gamma, beta, dwin1, sums, k0, s0, k1, s1)
+    _w2v_f32(partial, dweight)
+    if partial.numel() < N * W2V_STATS_SLOTS * C0 * k0 or dweight.numel() != C0 * k0:
+        raise ValueError("w2v_conv0_bwd_wgrad: partial / dweight do not match N, C0, k0")
+    with _Timed("w2v_conv0_bwd_wgrad_kernels", 4.0 * N * T0 * C0 * k0, [(N, L)]):
+        check(load().mmf_w2v_conv0_bwd_wgrad(wave.data_ptr(), weight.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                             dwin1.data_ptr(), sums.data_ptr(), partial.data_ptr(), dweight.data_ptr(), N, L, C0, k0, s0,
+                                             k1, s1, eps, int(bool(accumulate)), stream_ptr()))
 
 
 def w2v_posconv(x, w, bias, y, N: int, T: int, C: int, groups: int, k: int) -> None:

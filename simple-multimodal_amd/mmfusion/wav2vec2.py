@@ -1,5 +1,6 @@
 """Wav2Vec2 backbone on the HIP kernels: waveforms -> frame states; frozen by default, with the weight gradients of the top layers
-and of the front end (everything above the convolutional feature extractor) where they are marked trainable.
+and of the front end (everything above the convolutional feature extractor) where they are marked trainable, and those of the
+feature extractor itself where it is.
 
 The reference pushes every clip through HuggingFace's ``Wav2Vec2Model`` per step (reference models/encoders.py:116,144).
 ``NativeWav2Vec2`` is that model rebuilt from its sizes alone (nothing is fetched), with HuggingFace's ``state_dict``
@@ -44,7 +45,8 @@ with its delta as an input: its own delta = dO . O reads the bf16 O, so a row of
 absolute residue; where the frames of a clip have grown alike (twelve layers deep they do) dS nearly vanishes and that residue was
 up to 18 times the q / k projections' exact gradients at base sizes (tests/test_w2v_finetune_gpu.py).  The d x d and d x I weight gradients take the
 K-slab form where ``_slabs_for`` says so, and the key bias gets no column sum (mmfusion/backbone.py).  The front end, per chunk:
-``LN(feat)``, the projection and the positional convolution are computed again (the conv stack never is), then
+``LN(feat)``, the projection and the positional convolution are computed again (the conv stack is not, unless it trains: "The
+feature encoder" below), then
 
       encoder LayerNorm backward    mmf_layernorm_bwd_grouped                gx -> dy
       dz = dy gelu'(b + conv(x0))   mmf_w2v_posconv_bwd_act                  the forward's MFMA loop again; db += colsum(dz)
@@ -56,6 +58,23 @@ K-slab form where ``_slabs_for`` says so, and the key bias gets no column sum (m
 and once per backward ``mmf_w2v_weightnorm_bwd`` turns the summed dW_eff into the gradients of the weight norm's g and v (the
 forward rounds the effective weight to bf16; the gradient passes straight through that rounding).  Gradients are added into the
 parameters' f32 ``.grad`` (the arena's lazy-zero protocol as ``ops.queue_wgrad`` keeps it) in stream order.
+
+The feature encoder.  ``set_trainable_layers(L, front=True, feature_encoder=True)`` also trains the seven convolutions and layer 0's
+GroupNorm, as a ``Wav2Vec2Model`` nobody froze does.  The forward keeps nothing more (the waveform is saved already).  Per chunk,
+after the front end's backward has left ``dfeat``, ``_conv_grad`` runs the conv stack again with every layer's raw output kept side
+by side and walks it top down (dr_i: the gradient of layer i's raw output; it takes the place of the raw output it is formed from):
+
+      dr_last = dfeat gelu'(r_last)  mmf_bias_gelu_bwd_bf16 (no bias)         in place on dfeat
+      per layer i = last .. 1:
+        win_i again                 mmf_w2v_gelu_window                      r_{i-1} -> win (i = 1: mmf_w2v_conv0_norm_gelu; i = last: still there)
+        dW_i (+)= dr_i^T win_i      TN, K-slabs where _slabs_for says so     straight into the (C_out, k, C_in) parameter's .grad
+        dwin_i = dr_i W_i           NN
+        dr_{i-1}                    mmf_w2v_window_fold_gelu_bwd             gelu'(r_{i-1}) x the fold of dwin_i, zeros on unread frames
+      layer 0                       mmf_w2v_conv0_bwd_stats                  dwin_1 -> S1 = sum dy, S2 = sum dy xhat; dgamma, dbeta
+                                    mmf_w2v_conv0_bwd_wgrad                  dW0 over ALL frames (an unread one has dy = 0, not dc = 0)
+
+No host synchronisation and no floating-point atomics in any of these; the inner conv weights' bf16 shadows are the arena's, which
+the optimiser writes with the masters (tests/test_w2v_feature_encoder_gpu.py steps it and checks the next forward).
 
 Regularisers.  HuggingFace's model in ``train()`` masks time spans with ``masked_spec_embed``, drops at seven kinds of place and
 skips layers, and the reference trains it that way; here they are opt-in (``set_regularisation``, all off by default) and act only in a
@@ -181,6 +200,7 @@ class _Differentiable(torch.autograd.Function):
         pos_w = model._pos_weight()
         out = model._launches(wave, pos_w, keep, first, feat, reg)
         ctx.model, ctx.first, ctx.front, ctx.pos_w, ctx.reg = model, first, model.trainable_front, pos_w, reg
+        ctx.feature_encoder = model.trainable_feature_encoder
         ctx.save_for_backward(*((wave, keep) if feat is None else (wave, keep, feat)))
         return out
 
@@ -188,7 +208,8 @@ class _Differentiable(torch.autograd.Function):
     def backward(ctx, dout: torch.Tensor):
         wave, keep, *feat = ctx.saved_tensors
         if any(ctx.needs_input_grad[3:]):
-            ctx.model._backward(wave, keep, feat[0] if ctx.front else None, ctx.first, ctx.pos_w, dout.contiguous(), ctx.reg)
+            ctx.model._backward(wave, keep, feat[0] if ctx.front else None, ctx.first, ctx.pos_w, dout.contiguous(), ctx.reg,
+                                ctx.feature_encoder)
         return (None,) * len(ctx.needs_input_grad)
 
 
@@ -274,6 +295,7 @@ class NativeWav2Vec2(FrozenBackbone):
                                       "o": a + "attention.out_proj", "ln1": a + "layer_norm", "fc1": a + "feed_forward.intermediate_dense",
                                       "fc2": a + "feed_forward.output_dense", "ln2": a + "final_layer_norm"})
         self._front = False                            # set_trainable_layers(L, front=True)
+        self._feature_encoder = False                  # set_trainable_layers(L, front=True, feature_encoder=True)
         self.layerdrop_generator = torch.Generator()   # LayerDrop's host draws (CPU; seed it to fix the skip pattern)
         if mask_feature_prob != 0:
             raise ValueError(f"{who}: mask_feature_prob={mask_feature_prob!r}: masking along the feature axis is not built (no released "
@@ -290,11 +312,19 @@ class NativeWav2Vec2(FrozenBackbone):
     def trainable_front(self) -> bool:
         return self._front
 
+    @property
+    def trainable_feature_encoder(self) -> bool:
+        return self._feature_encoder
+
+    def _feature_params(self) -> list:
+        """the feature extractor's parameters: layer 0's convolution and GroupNorm, then the inner convolutions"""
+        return ["conv0_w", "conv0_gn_w", "conv0_gn_b"] + [f"conv{i}_w" for i in range(1, len(self.config.conv_dim))]
+
     def _trainable_names(self) -> list:
         """the parameters that require a gradient, in the order the differentiable forward takes them"""
         L, k = self.config.num_hidden_layers, self._trainable
         front = list(self._FRONT_PARAMS) + (["masked_spec_embed"] if self.config.mask_time_prob > 0.0 else []) if self._front else []
-        return front + [n for i in range(L - k, L) for n in self._layer_params(i)]
+        return (self._feature_params() if self._feature_encoder else []) + front + [n for i in range(L - k, L) for n in self._layer_params(i)]
 
     # -- training-mode regularisers ------------------------------------------------------------------------
     def set_regularisation(self, **settings) -> None:
@@ -345,20 +375,28 @@ class NativeWav2Vec2(FrozenBackbone):
         self._own_training_forward()
         return _Reg(c, N, T, dev, skip)
 
-    def set_trainable_layers(self, k: int, front: bool = False) -> None:
+    def set_trainable_layers(self, k: int, front: bool = False, feature_encoder: bool = False) -> None:
         """The parameters of the top ``k`` layers (``L - k .. L - 1``) get ``requires_grad = True``, every other parameter
         ``False``; 0 freezes the backbone again.  ``front=True`` (with ``k == L`` only: the gradient reaches the front end through
         every layer) also trains ``feature_projection.layer_norm`` and ``.projection``, the positional convolution's ``bias`` and
-        its weight norm's ``g`` / ``v`` (``parametrizations.weight.original0`` / ``original1``) and ``encoder.layer_norm``.  The
-        feature-extractor convolutions and layer 0's GroupNorm never train: this is the regime of HuggingFace's
-        ``freeze_feature_encoder()``.  ``masked_spec_embed`` trains with the front end where the time mask is on
+        its weight norm's ``g`` / ``v`` (``parametrizations.weight.original0`` / ``original1``) and ``encoder.layer_norm``: the
+        regime of HuggingFace's ``freeze_feature_encoder()``.  ``feature_encoder=True`` (with ``k == L`` and ``front`` only: the
+        gradient reaches the convolutions through the front end) also trains the feature extractor, ``conv0_w``, layer 0's
+        GroupNorm and every inner convolution: the regime of a ``Wav2Vec2Model`` nobody froze (the reference's).
+        ``masked_spec_embed`` trains with the front end where the time mask is on
         (``mask_time_prob > 0``, ``set_regularisation``) and is frozen otherwise.  With grad mode on and ``k > 0``, ``forward``
         returns a result that carries a graph; its backward adds those parameters' gradients into their f32 ``.grad`` (the module's
         parameter arena) and stops below layer ``L - k``.  There is no gradient with respect to the waveform; SpecAugment's time
         mask, the backbone's dropout and LayerDrop are ``set_regularisation``'s (off by default); the fp32 parity mode is refused as
         everywhere in this class."""
         self._check_trainable(k, "front", front, "the front end trains", "its gradient comes through every layer")
-        self._trainable, self._front = k, front
+        self._check_trainable(k, "feature_encoder", feature_encoder, "the feature encoder trains", "its gradient comes through every layer")
+        if feature_encoder and not front:
+            raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}, front={front!r}, feature_encoder={feature_encoder!r}): the "
+                             "feature encoder trains with the front end only (its gradient comes through the front end)")
+        if feature_encoder != self._feature_encoder:
+            self._gws = None                                              # the backward's table changes (``_grad_table``)
+        self._trainable, self._front, self._feature_encoder = k, front, feature_encoder
         self._require_grad(self._trainable_names())
 
     # -- HuggingFace state_dict surface ----------------------------------------------------------------
@@ -419,8 +457,10 @@ class NativeWav2Vec2(FrozenBackbone):
         return self._derived("pos_wt16" if transposed else "pos_w16", ("pos_g", "pos_v"), build)
 
     # -- launches ---------------------------------------------------------------------------------------
-    def _features(self, ws, wave: torch.Tensor, n: int, Ts: List[int]) -> torch.Tensor:
-        """the feature extractor: wave (n, L) f32 -> (n * T, conv_dim[-1]) bf16 after the last layer's GELU"""
+    def _features(self, ws, wave: torch.Tensor, n: int, Ts: List[int], raws: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+        """the feature extractor: wave (n, L) f32 -> (n * T, conv_dim[-1]) bf16 after the last layer's GELU.  With ``raws`` (the
+        backward's recompute; ``raws[i]``: (n T_i, conv_dim[i]) bf16) every layer's raw output goes to its own buffer and stays
+        there: the last layer's GELU is not applied, and ``win`` is left holding the last layer's window form"""
         c = self.config
         dims, ks, ss = c.conv_dim, c.conv_kernel, c.conv_stride
         w0 = self._f("conv0_w")
@@ -430,11 +470,11 @@ class NativeWav2Vec2(FrozenBackbone):
         last = len(dims) - 1
         for i in range(1, last + 1):
             rows, K = n * Ts[i], ks[i] * dims[i - 1]
-            win, raw = self._rows(ws, "win", rows, K), self._rows(ws, "raw", rows, dims[i])
+            win, raw = self._rows(ws, "win", rows, K), self._rows(ws, "raw", rows, dims[i]) if raws is None else raws[i]
             ops.gemm(GEMM_NT, win, self._w(f"conv{i}_w").view(dims[i], K), raw)
             if i < last:
-                lib.w2v_gelu_window(ws["raw"], ws["win"], n, Ts[i], dims[i], ks[i + 1], ss[i + 1])
-            else:
+                lib.w2v_gelu_window(raw, ws["win"], n, Ts[i], dims[i], ks[i + 1], ss[i + 1])
+            elif raws is None:
                 lib.bias_gelu(raw)
         return raw
 
@@ -517,18 +557,29 @@ class NativeWav2Vec2(FrozenBackbone):
     def _grad_table(self, L: int) -> WsTable:
         """what the backward holds beside the forward workspace, per clip of ``L`` samples: the layers' part (``_grad_rows``; the
         front end's dz takes ``dqkv``'s place) and the two conv_dim[-1]-wide gradients around the feature LayerNorm.  lse is the
-        forward workspace's"""
-        T, cd = self.frames(L), self.config.conv_dim[-1]
-        return self._grad_rows(T) + [("dfln", T * cd, BF16), ("dfeat", T * cd, BF16)]
+        forward workspace's.  While the feature encoder trains, also every inner conv layer's raw output side by side (``raws``; a
+        layer's gradient takes its raw output's place once that has been read), one window-form gradient (``dwin``) and layer
+        0's two sums per channel (``bsums``)"""
+        c = self.config
+        T, cd = self.frames(L), c.conv_dim[-1]
+        table = self._grad_rows(T) + [("dfln", T * cd, BF16), ("dfeat", T * cd, BF16)]
+        if self._feature_encoder:
+            Ts = feat_lengths(L, c.conv_kernel, c.conv_stride)
+            inner = range(1, len(Ts))
+            table += [("raws", sum(Ts[i] * c.conv_dim[i] for i in inner), BF16),
+                      ("dwin", max(Ts[i] * c.conv_kernel[i] * c.conv_dim[i - 1] for i in inner), BF16),
+                      ("bsums", 2 * c.conv_dim[0], torch.float32)]
+        return table
 
     def grad_workspace_bytes_per_clip(self, L: int) -> int:
         return self._bytes_per_item(self._grad_table(L))
 
     def _grad_scratch(self) -> Tuple[int, Dict[str, int]]:
         """the LayerNorm backward's scratch at the wider of its two widths; ``dpos``: the positional weight's f32 gradient in the
-        packed layout, summed over a backward's chunks"""
+        packed layout, summed over a backward's chunks; ``junk`` also takes the column sums of the conv layers' weight-gradient
+        launches (they have no bias), so it is as wide as the widest of them"""
         d, extra = super()._grad_scratch()
-        return max(d, self.config.conv_dim[-1]), {**extra, "dpos": d * self.pos_kp}
+        return max(d, self.config.conv_dim[-1]), {**extra, "junk": max(d, *self.config.conv_dim), "dpos": d * self.pos_kp}
 
     def _pos_wgrad_slabs(self, n: int, T: int) -> int:
         """The slab count of ``mmf_w2v_posconv_wgrad`` on a chunk of ``n`` clips: its grid is (tap blocks, groups) workgroups of
@@ -597,14 +648,52 @@ class NativeWav2Vec2(FrozenBackbone):
         wg = self.fp_w.grad
         self._wgrad_launch([(ga, fln, wg, self.fp_b.grad)], self._first_touch(wg), self._slabs_for(rows, self._tiles(d, cd)))
         ops.gemm(GEMM_NN, ga, self._w("fp_w"), dfln)
-        self._ln_bwd(st1, feat, dfln, dfeat, "fp_ln_w", (self.fp_ln_w.grad, self.fp_ln_b.grad))    # dfeat is not kept: the conv stack is frozen
+        self._ln_bwd(st1, feat, dfln, dfeat, "fp_ln_w", (self.fp_ln_w.grad, self.fp_ln_b.grad))    # dfeat: what _conv_grad starts from where the conv stack trains
+
+    def _conv_grad(self, ws, g, wave: torch.Tensor, n: int, Ts: List[int]) -> None:
+        """the feature extractor's backward on a chunk of ``n`` clips: ``dfeat`` holds the gradient of the last layer's GELU output
+        on entry.  The conv stack is computed again with every raw output kept (``_features`` with ``raws``), then walked top down:
+        dr_i = the gradient of layer i's raw output, win_i rebuilt from the raw output below, dW_i (+)= dr_i^T win_i straight into
+        the parameter's ``.grad`` (stored (C_out, k, C_in): the GEMM's (C_out, k C_in)), dwin_i = dr_i W_i, folded back to dr_{i-1}
+        in the place of the raw output it is formed from; layer 0 takes dwin_1 itself (two passes, csrc/wav2vec2.hip)"""
+        c = self.config
+        dims, ks, ss, last = c.conv_dim, c.conv_kernel, c.conv_stride, len(c.conv_dim) - 1
+        raws, at = [None], 0
+        for i in range(1, last + 1):
+            raws.append(g["raws"][at:at + n * Ts[i] * dims[i]].view(n * Ts[i], dims[i]))
+            at += n * Ts[i] * dims[i]
+        self._features(ws, wave, n, Ts, raws)
+        w0, gn_w, gn_b = self._f("conv0_w"), self._f("conv0_gn_w"), self._f("conv0_gn_b")
+        dr = self._rows(g, "dfeat", n * Ts[last], dims[last])
+        lib.bias_gelu_bwd(dr, raws[last], None, dr)                                 # dr_last, in place
+        for i in range(last, 0, -1):
+            rows, K = n * Ts[i], ks[i] * dims[i - 1]
+            win, dwin = self._rows(ws, "win", rows, K), self._rows(g, "dwin", rows, K)
+            if i == 1:
+                lib.w2v_conv0_norm_gelu(wave, w0, ws["stats"], gn_w, gn_b, ws["win"], ks[0], ss[0], ks[1], ss[1], 1e-5)
+            elif i < last:                                                          # (the recompute left win_last in place)
+                lib.w2v_gelu_window(raws[i - 1], ws["win"], n, Ts[i - 1], dims[i - 1], ks[i], ss[i])
+            wg = getattr(self, f"conv{i}_w").grad.view(dims[i], K)
+            self._wgrad_launch([(dr, win, wg, g["junk"][:dims[i]])], self._first_touch(wg),
+                               self._slabs_for(rows, self._tiles(dims[i], K)))
+            ops.gemm(GEMM_NN, dr, self._w(f"conv{i}_w").view(dims[i], K), dwin)
+            if i > 1:
+                dr = raws[i - 1]
+                lib.w2v_window_fold_gelu_bwd(g["dwin"], dr, dr, n, Ts[i - 1], dims[i - 1], ks[i], ss[i])
+        w0g = self.conv0_w.grad
+        lib.w2v_conv0_bwd_stats(wave, w0, ws["stats"], gn_w, gn_b, g["dwin"], g["bsums"], ws["partial"], self.conv0_gn_w.grad,
+                                self.conv0_gn_b.grad, ks[0], ss[0], ks[1], ss[1], 1e-5)     # (vectors: zeroed with the biases, never lazily)
+        partial = self._slab_buffer(n * lib.W2V_STATS_SLOTS * dims[0] * ks[0], wave.device)
+        lib.w2v_conv0_bwd_wgrad(wave, w0, ws["stats"], gn_w, gn_b, g["dwin"], g["bsums"], partial, w0g, ks[0], ss[0], ks[1], ss[1], 1e-5,
+                                accumulate=not self._first_touch(w0g))
 
     def _backward(self, wave: torch.Tensor, keep: torch.Tensor, feat: Optional[torch.Tensor], first: int, pos_w: torch.Tensor,
-                  dout: torch.Tensor, reg: Optional[_Reg] = None) -> None:
+                  dout: torch.Tensor, reg: Optional[_Reg] = None, feature_encoder: bool = False) -> None:
         """for the gradient ``dout`` (N, T, d) f32 of the result: the gradients of layers ``first`` .. L - 1 and, with ``feat`` (the
         saved input of the feature LayerNorm: the front end trains), of the front end, added into their ``.grad``.  ``keep``: the
         saved inputs of the layers from ``first`` up, ``pos_w``: the positional weight the forward used, ``reg``: its regularisers
-        (a layer LayerDrop skipped is the identity: ``ga`` passes through and its parameters receive nothing)"""
+        (a layer LayerDrop skipped is the identity: ``ga`` passes through and its parameters receive nothing); ``feature_encoder``:
+        the conv stack trains too (``_conv_grad`` takes each chunk's ``dfeat`` from ``_front_grad``)"""
         c, d, dev = self.config, self.config.hidden_size, wave.device
         self._refuse_fp32()
         N, Lw = wave.shape
@@ -621,6 +710,8 @@ class NativeWav2Vec2(FrozenBackbone):
                     self._layer_grad(i, ws, g, keep[i - first, rows], n, T, front or i > first, reg, n0)
             if front:
                 self._front_grad(ws, g, feat[rows], pos_w, pos_wt, n, T, reg, n0)
+            if feature_encoder:
+                self._conv_grad(ws, g, wave[n0:n0 + n], n, feat_lengths(Lw, c.conv_kernel, c.conv_stride))
         if front:
             lib.w2v_weightnorm_bwd(g["dpos"], self._f("pos_g"), self._f("pos_v"), self.pos_g.grad, self.pos_v.grad,
                                    self._first_touch(self.pos_v.grad))

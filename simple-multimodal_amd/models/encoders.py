@@ -21,7 +21,8 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers).  Frozen
     unless ``config.audio_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers then
     train; ``"all"``: every layer and the front end above the feature-extractor convolutions (feature projection, positional
-    convolution, encoder LayerNorm), which stay frozen as under HuggingFace's ``freeze_feature_encoder()``.
+    convolution, encoder LayerNorm), which stay frozen as under HuggingFace's ``freeze_feature_encoder()``; ``"full"``: the
+    feature-extractor convolutions and layer 0's GroupNorm as well, every parameter the reference's optimiser trains.
     ``config.audio_backbone_regularisation`` (dynamic attribute; default 0: off) switches HuggingFace's training-mode regularisers
     on: ``True`` for wav2vec2-base-960h's dropouts, LayerDrop and SpecAugment time mask, which is what the reference trains under, or
     a dict of ``NativeWav2Vec2.set_regularisation``'s names; they act in ``train()`` while the backbone has something to train;
@@ -250,9 +251,9 @@ class AudioEncoder(_FusionBase):
         self.config = config
         self.model, self.hidden_size, self._native = _backbone(config, "audio", backbone)
         if self._native:      # fine-tune the native backbone (NativeWav2Vec2.set_trainable_layers): the top k layers, "all": every
-            k = getattr(config, "audio_backbone_trainable_layers", 0)          # layer and the front end; 0: frozen
-            if k == "all":
-                self.model.set_trainable_layers(self.model.config.num_hidden_layers, front=True)
+            k = getattr(config, "audio_backbone_trainable_layers", 0)          # layer and the front end; "full": the feature
+            if k in ("all", "full"):                                           # extractor as well; 0: frozen
+                self.model.set_trainable_layers(self.model.config.num_hidden_layers, front=True, feature_encoder=k == "full")
             else:
                 self.model.set_trainable_layers(k)
             self.model.set_regularisation(**_audio_regularisation(getattr(config, "audio_backbone_regularisation", 0)))

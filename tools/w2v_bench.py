@@ -9,14 +9,14 @@
   * with --table, a per-kernel table of one batch from HIP events around every launch (mmfusion.lib.PROFILE): time, share,
     TFLOP/s where the wrapper counts operations.
 
-  * with --finetune K|all, instead: forward + backward of ``set_trainable_layers(K)`` (``all``: every layer and the front end)
-    against the frozen forward, the per-kernel table of one step, stock-torch bf16 autograd through the same restatement with the
-    same tensors as leaves, and (``all``) each kernel of the positional convolution's backward on one chunk beside the forward
+  * with --finetune K|all|full, instead: forward + backward of ``set_trainable_layers(K)`` (``all``: every layer and the front end;
+    ``full``: the feature extractor as well, its tensors leaves of the yardstick too) against the frozen forward, the per-kernel table of one step, stock-torch bf16 autograd through the same restatement with the
+    same tensors as leaves, and (``all`` / ``full``) each kernel of the positional convolution's backward on one chunk beside the forward
     ``mmf_w2v_posconv``, which does the same FLOPs.  With --regularise as well: the same step in ``train()`` under
     wav2vec2-base-960h's regularisers (``mmfusion.wav2vec2.REG_960H``), with and without LayerDrop, and its per-kernel table.
 
     python tools/w2v_bench.py [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--no-torch]
-                              [--finetune K|all [--regularise]]
+                              [--finetune K|all|full [--regularise]]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
 import json
 
@@ -70,14 +70,15 @@ def finetune(args, model, cfg, sd, x) -> dict:
     import w2v_ref
     from mmfusion import arena, wav2vec2
     N, L, d = args.clips, cfg.num_hidden_layers, cfg.hidden_size
-    front = args.finetune == "all"
+    full = args.finetune == "full"
+    front = full or args.finetune == "all"
     k = L if front else int(args.finetune)
     T = model.frames(args.samples)
     res = {"model": "wav2vec2-base, bf16 storage", "clips": N, "samples": args.samples, "frames": T, "chunk": model.chunk,
-           "trainable_layers": k, "front": front}
+           "trainable_layers": k, "front": front, "feature_encoder": full}
     with torch.no_grad():
         res["forward_ms"] = round(time_eager(lambda: model(x), args.steps, args.warmup), 3)
-    model.set_trainable_layers(k, front=front)
+    model.set_trainable_layers(k, front=front, feature_encoder=full)
     arena.ensure(model).zero_grad()
     dout = torch.randn(N, T, d, generator=torch.Generator().manual_seed(2)).cuda()
 
@@ -110,7 +111,8 @@ def finetune(args, model, cfg, sd, x) -> dict:
         model._ws = model._gws = model._slabs = None
         torch.cuda.empty_cache()
         keys = {n for n in sd if any(n.startswith(f"encoder.layers.{i}.") for i in range(L - k, L))
-                or (front and n.startswith(("feature_projection.", "encoder.pos_conv_embed.", "encoder.layer_norm.")))}
+                or (front and n.startswith(("feature_projection.", "encoder.pos_conv_embed.", "encoder.layer_norm.")))
+                or (full and n.startswith("feature_extractor."))}
         leaves = {n: v.cuda().to(torch.bfloat16).requires_grad_(n in keys) for n, v in sd.items()}
         x16, d16, c = x.to(torch.bfloat16), dout.to(torch.bfloat16), wav2vec2.DEFAULT_CHUNK
 
@@ -129,7 +131,7 @@ def main():
     ap = parser(steps=5, warmup=2, torch_yardstick=True)
     ap.add_argument("--clips", type=int, default=16)
     ap.add_argument("--samples", type=int, default=160000)
-    ap.add_argument("--finetune", default=None, metavar="K|all")
+    ap.add_argument("--finetune", default=None, metavar="K|all|full")
     ap.add_argument("--regularise", action="store_true", help="with --finetune: also time the step under wav2vec2-base-960h's regularisers")
     args = ap.parse_args()
     import w2v_ref
