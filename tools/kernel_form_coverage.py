@@ -11,6 +11,9 @@ For a trace of tests/test_streaming_small_gpu.py (the kernels of elementwise.hip
 For a trace of tests/test_attention_paths_gpu.py (the twelve instantiations of attention2.hip: forward, dQ and dK/dV, each at
 head_dim 64 and 96, each with and without dropout; profiles/attention_form_coverage.txt):
     --only '^attn_(fwd|bwd)'    (attn_weights_mean_kernel of small.hip belongs to the streaming file's list above)
+For a trace of tests/test_deberta_attention_paths_gpu.py (the forward's four and the backward's eight instantiations of deberta.hip, and the
+delta pre-pass; profiles/deberta_attention_form_coverage.txt):
+    --only 'deberta_attn'
 Exit status 1 if an instantiation was never launched.
 """
 import argparse
