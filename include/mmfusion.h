@@ -815,6 +815,25 @@ int mmf_w2v_conv0_norm_gelu(const float* wave, const float* weight, const float*
  * form, f32, one rounding), T_out = (T_in - k) / s + 1: the A operand of the next conv layer as ONE NT GEMM against its weight
  * repacked to (C_out, k*C), column (j, c).  C % 8 == 0, N <= 65535, out must not be x. */
 int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, int T_in, int C, int k, int s, void* stream);
+/* The layer-norm family (feat_extract_norm "layer": large-lv60, XLS-R), whose conv layers are Conv1d(bias) -> LayerNorm over the
+ * channels of every frame (gamma, beta f32 [C], eps) -> GELU.  The C / 8 lanes that own a frame reduce its statistics among
+ * themselves in f32: the mean, then the squared deviations from it over the values held in registers (never E[x^2] - mean^2);
+ * through LDS where a frame spans more than one wave (C > 512).  C / 8 must be a power of two up to 256 (8 .. 2048 channels);
+ * no atomics, the same bits on every run.
+ *   mmf_w2v_conv0_ln_gelu   layer 0 in one pass: conv0(wave) + bias (NULL: none), LayerNorm, GELU, one rounding, stored in the
+ *                           window form of the next layer exactly as mmf_w2v_conv0_norm_gelu stores it.  No statistics pass and
+ *                           no stored intermediate.  Its limits (k0 <= 16, N <= 65535) and k1 >= s1; out 16-byte aligned.
+ *   mmf_w2v_ln_gelu_window  x (N, T_in, C) bf16, a raw convolution output with its bias added ->
+ *                           out[n][t][j*C + c] = bf16(gelu(LN(x[n][s*t + j])[c])), (N, T_out, k*C).  It walks the INPUT rows: a row is
+ *                           normalised once and stored to every (t, j) that reads it; rows no window reads are skipped.
+ *                           k == 0: the last layer's form, out (N, T_in, C), which may be x.  k >= s otherwise, and out must not be
+ *                           x; N <= 65535; x / out 16-byte aligned.
+ * MMF_E_SHAPE for null / non-positive / too short operands, MMF_E_UNSUPPORTED for a channel count, k < s or aliasing outside the
+ * above, MMF_E_ALIGN for alignment; nothing is launched on an error. */
+int mmf_w2v_conv0_ln_gelu(const float* wave, const float* weight, const float* bias, const float* gamma, const float* beta,
+                          void* out_bf16, int N, int L, int C0, int k0, int s0, int k1, int s1, float eps, void* stream);
+int mmf_w2v_ln_gelu_window(const void* x_bf16, const float* gamma, const float* beta, void* out_bf16, int N, int T_in, int C, int k,
+                           int s, float eps, void* stream);
 /* Its mirror, the backward of GELU + window form: dwin (N, T_out, k*C) bf16, the gradient of the window form, and the raw x
  * (N, T_in, C) bf16 -> dx (N, T_in, C) bf16,
  *   dx[n][f][c] = gelu'(x[n][f][c]) * sum_{j < k, (f - j) % s == 0, 0 <= (f - j) / s < T_out} dwin[n][(f - j) / s][j*C + c],

@@ -4,6 +4,8 @@
 //   conv0_stats / conv0_norm_gelu   layer 0: Conv1d(1 -> C0, k0, s0) + GroupNorm(one group per channel) + GELU in two passes
 //                                   that both recompute the k0 MACs per output; no f32 intermediate is stored
 //   gelu_window                     GELU + the (T_out, k*C) window form the next conv layer's GEMM reads
+//   conv0_ln_gelu / ln_gelu_window  the layer-norm family's forms of the two: LayerNorm over the channels of every frame (with conv
+//                                   biases) in front of the GELU, the frame's statistics reduced across the C / 8 lanes that own it
 //   window_fold_gelu_bwd            its mirror: the gradient of the window form gathered back to the raw output's, times gelu'
 //   conv0_bwd_stats / _bwd_wgrad    layer 0's backward: GroupNorm's two sums per channel, then dW0, recomputing as the forward does
 //   posconv                         the grouped positional convolution as one MFMA GEMM per (clip, group, 128 time rows); the same
@@ -147,6 +149,139 @@ void w2v_gelu_window_kernel(const unsigned short* __restrict__ x, unsigned short
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = gelu_erf(a[e]);
     *reinterpret_cast<u32x4_t*>(dst + (size_t)v * 8) = pack8(a);
+  }
+}
+
+// ---- the layer-norm family: LayerNorm over the channels of a frame ------------------------------------------------
+// The C / 8 lanes that own a frame sit next to each other (cgn = C / 8, a power of two up to 256).  row_sum adds one value per lane
+// over them: xor-shuffles inside a wave (cgn <= 64: the partners of a lane are the lanes of its own frame), and for a frame that
+// spans 2 or 4 waves the waves' sums go through `red` (one row of W2V_THREADS / 64 floats per call site, so that two reductions
+// of one loop pass need one barrier each) and are added in wave order.  Every lane of the workgroup must call it: the callers'
+// loops have workgroup-uniform trip counts and predicate their stores instead of branching around it.
+__device__ __forceinline__ float w2v_row_sum(float v, int cgn, float* red) {
+  if (cgn <= 64) {
+    for (int o = cgn >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  }
+  v = wave_sum(v);
+  const int wave = threadIdx.x >> 6, wpr = cgn >> 6, w0 = wave / wpr * wpr;
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+  float a = red[w0];
+  for (int w = 1; w < wpr; ++w) a += red[w0 + w];
+  return a;
+}
+
+// The exact GELU through erfc, gelu(x) = x Phi(x) with Phi(x) = erfc(|x| / sqrt 2) / 2 for x < 0 and 1 - that otherwise:
+// 1 + erf(x / sqrt 2) rounds away every digit of Phi in the left tail, and a LayerNorm's output reaches it (x = -5: 20 bf16 ulps of
+// the result), so these kernels' outputs would not be within a bf16 ulp of the exact value.  erfc(z), z >= 0, is the Chebyshev fit
+// t exp(-z^2 + P(t)), t = 1 / (1 + z / 2) (Numerical Recipes' erfcc: a RELATIVE error near 1e-7 for every z; in f32 with v_rcp and
+// v_exp the GELU stays within 2e-5 of its value out to |x| = 12), a third of erfcf's instructions: the two kernels are near their
+// ALU bound beside the memory one.
+__device__ __forceinline__ float w2v_gelu_erfc(float x) {
+  const float z = fabsf(x) * 0.70710678118654752440f, t = __builtin_amdgcn_rcpf(fmaf(0.5f, z, 1.0f));
+  float p = 0.17087277f;
+  p = fmaf(p, t, -0.82215223f);
+  p = fmaf(p, t, 1.48851587f);
+  p = fmaf(p, t, -1.13520398f);
+  p = fmaf(p, t, 0.27886807f);
+  p = fmaf(p, t, -0.18628806f);
+  p = fmaf(p, t, 0.09678418f);
+  p = fmaf(p, t, 0.37409196f);
+  p = fmaf(p, t, 1.00002368f);
+  p = fmaf(p, t, -1.26551223f);
+  const float h = 0.5f * t * __expf(fmaf(-z, z, p));                  // Phi(-|x|)
+  return x * (x < 0.0f ? h : 1.0f - h);
+}
+
+// v[8] (one lane's channels of a frame of C = 8 cgn channels) -> gelu(gamma xhat + beta), the mean and then the squared deviations
+// from it summed over the values in registers (two passes: no E[x^2] - mean^2)
+__device__ __forceinline__ void w2v_ln_gelu8(float (&v)[8], const float (&gamma)[8], const float (&beta)[8], int cgn, float eps,
+                                             float (*red)[W2V_THREADS / 64]) {
+  const float inv = 1.0f / (float)(cgn * 8);
+  float a = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+  const float mean = w2v_row_sum(a, cgn, red[0]) * inv;
+  float q = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    v[e] -= mean;
+    q = fmaf(v[e], v[e], q);
+  }
+  const float rstd = rsqrtf(w2v_row_sum(q, cgn, red[1]) * inv + eps);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = w2v_gelu_erfc(fmaf(v[e] * rstd, gamma[e], beta[e]));
+}
+
+// frame f, 8 channels as pk, to every (row t, tap j) of the window form with s t + j == f: dst[(t k + j) C] (dst: the clip's window
+// form at this lane's channel)
+__device__ __forceinline__ void w2v_scatter8(unsigned short* __restrict__ dst, const u32x4_t pk, int f, int C, int k, int s, int T_out) {
+  for (int j = 0; j < k && j <= f; ++j) {
+    const int t = (f - j) / s;
+    if (t * s == f - j && t < T_out) *reinterpret_cast<u32x4_t*>(dst + ((size_t)t * k + j) * C) = pk;
+  }
+}
+
+// Layer 0 in one pass: conv + bias, LayerNorm over the C0 channels of the frame, GELU, one rounding, the window form of layer 1
+// (w2v_conv0_norm_gelu_kernel's scatter).  nfl = W2V_THREADS / cgn frames per workgroup pass; a lane past the last frame layer 1
+// reads computes that last frame again and stores nothing.
+template <int K0>
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_conv0_ln_gelu_kernel(const float* __restrict__ wave, const float* __restrict__ wt, const float* __restrict__ bias,
+                              const float* __restrict__ gamma, const float* __restrict__ beta, unsigned short* __restrict__ out,
+                              int L, int C0, int k0, int s0, int k1, int s1, int T1, float eps, int nfl, int cgn) {
+  __shared__ float red[2][W2V_THREADS / 64];
+  const int cgi = threadIdx.x % cgn, fl = threadIdx.x / cgn, c = cgi * 8;
+  Conv0<K0> cv;
+  cv.load(wt, c, k0);
+  float b[8], ga[8], be[8], v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    b[e] = bias ? bias[c + e] : 0.0f;
+    ga[e] = gamma[c + e];
+    be[e] = beta[c + e];
+  }
+  const float* __restrict__ xs = wave + (size_t)blockIdx.y * L;
+  unsigned short* __restrict__ dst = out + (size_t)blockIdx.y * T1 * k1 * C0 + c;
+  const int last = s1 * (T1 - 1) + k1 - 1;                 // the last frame the next layer reads
+  for (int f0 = blockIdx.x * nfl; f0 <= last; f0 += gridDim.x * nfl) {
+    const int f = f0 + fl;
+    const bool live = f <= last;
+    cv.frame(xs + (size_t)(live ? f : last) * s0, k0, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += b[e];
+    w2v_ln_gelu8(v, ga, be, cgn, eps, red);
+    if (live) w2v_scatter8(dst, pack8(v), f, C0, k1, s1, T1);
+  }
+}
+
+// The inner layers: x (T_in, C) raw conv output (bias added) per clip -> out[t][j*C + c] = gelu(LN(x[s t + j])[c]).  The lanes walk
+// the INPUT rows, rpb = W2V_THREADS / cgn of them per workgroup pass: a row is normalised once and stored to every slot that reads
+// it.  k = 0: out is (T_in, C) and may be x (a row's lanes have all read it, and been through a reduction, before one of them writes;
+// a lane past the end reads nothing and normalises zeros).  T_read: the rows some window reads (all of them for k = 0); the rest are skipped.
+__global__ __launch_bounds__(W2V_THREADS)
+void w2v_ln_gelu_window_kernel(const unsigned short* x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                               unsigned short* out, int T_in, int T_read, int T_out, int C, int k, int s, float eps, int rpb, int cgn) {
+  __shared__ float red[2][W2V_THREADS / 64];
+  const int cgi = threadIdx.x % cgn, rl = threadIdx.x / cgn, c = cgi * 8;
+  float ga[8], be[8], v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    ga[e] = gamma[c + e];
+    be[e] = beta[c + e];
+  }
+  const unsigned short* src = x + (size_t)blockIdx.y * T_in * C + c;
+  unsigned short* dst = out + (size_t)blockIdx.y * (k ? (size_t)T_out * k : (size_t)T_in) * C + c;
+  for (int f0 = blockIdx.x * rpb; f0 < T_read; f0 += gridDim.x * rpb) {
+    const int f = f0 + rl;
+    const bool live = f < T_read;
+    u32x4_t in = {0u, 0u, 0u, 0u};
+    if (live) in = *reinterpret_cast<const u32x4_t*>(src + (size_t)f * C);
+    unpack8(in, v);
+    w2v_ln_gelu8(v, ga, be, cgn, eps, red);
+    if (!live) continue;
+    const u32x4_t pk = pack8(v);
+    if (k == 0) *reinterpret_cast<u32x4_t*>(dst + (size_t)f * C) = pk;
+    else w2v_scatter8(dst, pk, f, C, k, s, T_out);
   }
 }
 
@@ -750,6 +885,64 @@ extern "C" int mmf_w2v_gelu_window(const void* x_bf16, void* out_bf16, int N, in
   hipLaunchKernelGGL(w2v_gelu_window_kernel, dim3(mmf_stream_grid(nvec, W2V_THREADS), N), dim3(W2V_THREADS), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(x_bf16), static_cast<unsigned short*>(out_bf16), T_in, C, k, s, (unsigned)(C / 8), (unsigned)nvec);
   MMF_CHECK_LAUNCH("mmf_w2v_gelu_window");
+  return MMF_OK;
+}
+
+namespace {
+// the channel counts the layer-norm kernels reduce over: C / 8 lanes, a power of two up to 256 (8 .. 2048 channels)
+bool w2v_ln_channels(int C) { return C >= 8 && C <= 2048 && (C & 7) == 0 && ((C >> 3) & ((C >> 3) - 1)) == 0; }
+}  // namespace
+
+extern "C" int mmf_w2v_conv0_ln_gelu(const float* wave, const float* weight, const float* bias, const float* gamma, const float* beta,
+                                     void* out_bf16, int N, int L, int C0, int k0, int s0, int k1, int s1, float eps, void* stream) {
+  const char* fn = "mmf_w2v_conv0_ln_gelu";
+  if (!wave || !weight || !gamma || !beta || !out_bf16) MMF_FAIL(MMF_E_SHAPE, "%s: null operand", fn);
+  Conv0Shape sh;
+  if (int rc = conv0_check(fn, N, L, C0, k0, s0, &sh)) return rc;
+  if (!w2v_ln_channels(C0)) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: C0=%d: C0 / 8 must be a power of two up to 256", fn, C0);
+  if (k1 <= 0 || s1 <= 0 || sh.T0 < k1) MMF_FAIL(MMF_E_SHAPE, "%s: k1=%d s1=%d against T0=%d frames", fn, k1, s1, sh.T0);
+  const int T1 = (sh.T0 - k1) / s1 + 1;
+  if (k1 < s1 || (int64_t)T1 * k1 * (C0 / 8) >= (int64_t)1 << 31)
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: k1=%d >= s1=%d, %lld window elements per clip (below 2^34)", fn, k1, s1, (long long)T1 * k1 * C0);
+  if (!mmf_aligned16(out_bf16) || (reinterpret_cast<uintptr_t>(wave) & 3u) || (reinterpret_cast<uintptr_t>(weight) & 3u)
+      || (reinterpret_cast<uintptr_t>(bias) & 3u) || (reinterpret_cast<uintptr_t>(gamma) & 3u) || (reinterpret_cast<uintptr_t>(beta) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: out must be 16-byte aligned, the f32 operands 4-byte aligned", fn);
+  const int cgn = C0 / 8, nfl = W2V_THREADS / cgn;
+  int64_t blocks = ((int64_t)s1 * (T1 - 1) + k1 + nfl - 1) / nfl;
+  if (blocks > 1024) blocks = 1024;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned short* out = static_cast<unsigned short*>(out_bf16);
+  if (k0 <= 10) hipLaunchKernelGGL(w2v_conv0_ln_gelu_kernel<10>, dim3((int)blocks, N), dim3(W2V_THREADS), 0, s, wave, weight, bias, gamma, beta, out, L, C0, k0, s0, k1, s1, T1, eps, nfl, cgn);
+  else          hipLaunchKernelGGL(w2v_conv0_ln_gelu_kernel<16>, dim3((int)blocks, N), dim3(W2V_THREADS), 0, s, wave, weight, bias, gamma, beta, out, L, C0, k0, s0, k1, s1, T1, eps, nfl, cgn);
+  MMF_CHECK_LAUNCH(fn);
+  return MMF_OK;
+}
+
+extern "C" int mmf_w2v_ln_gelu_window(const void* x_bf16, const float* gamma, const float* beta, void* out_bf16, int N, int T_in, int C,
+                                      int k, int s, float eps, void* stream) {
+  const char* fn = "mmf_w2v_ln_gelu_window";
+  if (!x_bf16 || !gamma || !beta || !out_bf16 || N <= 0 || T_in <= 0 || C <= 0 || k < 0 || (k > 0 && s <= 0))
+    MMF_FAIL(MMF_E_SHAPE, "%s: null operand or N=%d T_in=%d C=%d k=%d s=%d", fn, N, T_in, C, k, s);
+  if (T_in < k) MMF_FAIL(MMF_E_SHAPE, "%s: T_in=%d is shorter than the kernel k=%d", fn, T_in, k);
+  if (!w2v_ln_channels(C)) MMF_FAIL(MMF_E_UNSUPPORTED, "%s: C=%d: C / 8 must be a power of two up to 256", fn, C);
+  const int64_t T_out = k ? (T_in - k) / s + 1 : T_in, T_read = k ? (int64_t)s * (T_out - 1) + k : T_in;
+  const int64_t nvec = T_out * (k ? k : 1) * (C / 8);
+  if ((k > 0 && k < s) || N > 65535 || nvec >= (int64_t)1 << 31 || (k > 0 && x_bf16 == out_bf16))
+    MMF_FAIL(MMF_E_UNSUPPORTED, "%s: k=%d >= s=%d (or k = 0), N=%d (at most 65535), %lld output elements per clip (below 2^34), out may "
+             "be x for k = 0 only", fn, k, s, N, (long long)nvec * 8);
+  if (!mmf_aligned16(x_bf16) || !mmf_aligned16(out_bf16) || (reinterpret_cast<uintptr_t>(gamma) & 3u) || (reinterpret_cast<uintptr_t>(beta) & 3u))
+    MMF_FAIL(MMF_E_ALIGN, "%s: x / out must be 16-byte aligned, gamma / beta 4-byte aligned", fn);
+  const int cgn = C / 8, rpb = W2V_THREADS / cgn;
+  // up to 8 passes per workgroup where that still leaves 2048 workgroups: a lane's gamma / beta (64 bytes) are then loaded once for
+  // 8 rows' 16 bytes each
+  const int64_t row_blocks = (T_read + rpb - 1) / rpb;
+  int64_t passes = (int64_t)N * row_blocks / 2048;
+  if (passes > 8) passes = 8;
+  if (passes < 1) passes = 1;
+  hipLaunchKernelGGL(w2v_ln_gelu_window_kernel, dim3(mmf_stream_grid((row_blocks + passes - 1) / passes, 1), N), dim3(W2V_THREADS), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned short*>(x_bf16), gamma, beta, static_cast<unsigned short*>(out_bf16),
+                     T_in, (int)T_read, (int)T_out, C, k, s, eps, rpb, cgn);
+  MMF_CHECK_LAUNCH(fn);
   return MMF_OK;
 }
 

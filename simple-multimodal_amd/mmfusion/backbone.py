@@ -3,7 +3,7 @@ share: the table of frozen parameters behind HuggingFace's ``state_dict`` surfac
 the weights once per weight version, and the launches of a transformer layer.
 
 A layer is two blocks on ``rows = n * T`` tokens of a chunk of ``n`` items (bf16 residual stream like MulT's).  Where the
-LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subclass's own ``_layer`` (ViT, pre-LN):
+LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2's base family, DeBERTa) or ``_pre_ln_layer`` (ViT, Wav2Vec2's layer-norm family):
 
     _attention(src, resid, attend):
       fused Q/K/V linear + bias     mmf_gemm_grouped NT, BIAS            src -> qkv (rows, 3 d)
@@ -23,8 +23,9 @@ LayerNorms go around them is ``_post_ln_layer`` (Wav2Vec2, DeBERTa) or the subcl
     _wgrad(dy, x, name, slabs)      mmf_gemm_grouped TN, COLSUM_A        dy, x -> a trainable layer's weight and bias gradients; in
                                     (+ mmf_sum_slabs_f32)                ``slabs`` K-slabs where the output is a few tiles under many rows
 
-The backward of a post-LN layer is ``_post_ln_layer_grad`` (Wav2Vec2, DeBERTa; ViT's pre-LN one, with its CLS form, is its own
-``_layer_grad``): the layer again from its saved input ``xin``, then top down, on the backward's workspace (``_grad_workspace``;
+The backward of a post-LN layer is ``_post_ln_layer_grad`` (Wav2Vec2's base family, DeBERTa; a pre-LN layer's is
+``_pre_ln_layer_grad``, which ViT and Wav2Vec2's layer-norm family share; ViT's CLS form is its own ``_layer_grad``): the layer
+again from its saved input ``xin``, then top down, on the backward's workspace (``_grad_workspace``;
 ``ga`` holds the gradient of the layer's output on entry and of ``xin`` on return)
 
       _attention(xin, + xin, attend)                                           xin -> qkv -> att -> y1 (the attention writes lse)
@@ -635,6 +636,51 @@ class FrozenBackbone(nn.Module):
             qkv_wgrad(dqkv, xin)
         if below:
             ops.gemm(GEMM_NN, dqkv, W("qkv"), ga, aux=gb, epilogue=EPI_ADD_AUX)       # ga = dx: the attention branch + the residual
+
+    def _pre_ln_layer(self, i: int, ws, n: int, T: int) -> None:
+        """x = y + ffn(LayerNorm(y)), y = x + attention(LayerNorm(x)) on the ``n * T`` rows of ``x`` (ViT; Wav2Vec2's layer-norm
+        family)"""
+        rows, d = n * T, self.config.hidden_size
+        x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
+        self._ln(ws, x, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
+        y = self._attention(i, ws, ln, x, n, T)
+        self._ln(ws, y, ln, f"l{i}_ln2_w", f"l{i}_ln2_b")
+        self._ffn(i, ws, ln, y, x)
+
+    def _pre_ln_layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int, attn_bwd: AttnBwd, qkv_wgrad: QkvWgrad,
+                           slabs: Callable[[int, int], int]) -> None:
+        """``_pre_ln_layer`` ``i`` again from its saved input ``xin`` up to the GELU output (nothing behind fc2 is read by a pre-LN
+        layer's backward), then its backward with the weight, bias and LayerNorm gradients added into the parameters' ``.grad``, on
+        a ``_grad_rows(T, "ln2")`` workspace: ``ga`` holds the gradient of the layer's output on entry and of ``xin`` on return.
+        ``attn_bwd(qkv, att, datt, dqkv)`` and ``qkv_wgrad(dqkv, ln1)`` are the model's; the four plain weights' gradients take
+        ``slabs(rows, tiles)`` K-slabs.  The Q/K/V input gradient is always formed: the first LayerNorm's own parameter gradients
+        come out of its backward, whether or not anything below the layer trains"""
+        c = self.config
+        d, I, R, rows = c.hidden_size, c.intermediate_size, self._rows, n * T
+        ln1, qkv, dqkv = R(ws, "ln", rows, d), R(ws, "qkv", rows, 3 * d), R(g, "dqkv", rows, 3 * d)
+        att, h, ln2, gel, ga, gb, dh = R(ws, "att", rows, d), R(ws, "h", rows, I), R(g, "ln2", rows, d), R(g, "g", rows, I), R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dh", rows, I)
+        st1, st2 = self._stats(g, 1), self._stats(g, 2)
+        S = lambda M, N: slabs(rows, self._tiles(M, N))
+        W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
+        self._ln(st1, xin, ln1, f"l{i}_ln1_w", f"l{i}_ln1_b")
+        y = self._attention(i, ws, ln1, xin, n, T)
+        self._ln(st2, y, ln2, f"l{i}_ln2_w", f"l{i}_ln2_b")
+        ops.gemm(GEMM_NT, ln2, W("fc1"), h)
+        lib.bias_gelu_to(h, F("fc1"), gel)
+        # the MLP
+        self._wgrad(ga, gel, f"l{i}_fc2", S(d, I))
+        ops.gemm(GEMM_NN, ga, W("fc2"), dh)                                            # dg
+        lib.bias_gelu_bwd(dh, h, F("fc1"), dh)
+        self._wgrad(dh, ln2, f"l{i}_fc1", S(I, d))
+        ops.gemm(GEMM_NN, dh, W("fc1"), gb)                                            # dln2
+        self._ln_bwd(st2, y, gb, ga, f"l{i}_ln2_w", self._grads(i, "ln2"), resid=ga)   # ga = dy: the MLP branch + the residual
+        # the attention
+        self._wgrad(ga, att, f"l{i}_o", S(d, d))
+        ops.gemm(GEMM_NN, ga, W("o"), gb)                                              # datt
+        attn_bwd(qkv, att, gb, dqkv)
+        qkv_wgrad(dqkv, ln1)
+        ops.gemm(GEMM_NN, dqkv, W("qkv"), gb)                                          # dln1
+        self._ln_bwd(st1, xin, gb, ga, f"l{i}_ln1_w", self._grads(i, "ln1"), resid=ga)  # ga = dx: the attention branch + the residual
 
     @staticmethod
     def _widen(src: torch.Tensor, dst: torch.Tensor) -> None:

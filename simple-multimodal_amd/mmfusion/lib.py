@@ -44,6 +44,7 @@ SYMBOLS = (
     "mmf_w2v_conv0_stats", "mmf_w2v_conv0_norm_gelu", "mmf_w2v_gelu_window", "mmf_w2v_posconv",
     "mmf_w2v_posconv_bwd_act", "mmf_w2v_posconv_dgrad", "mmf_w2v_posconv_wgrad", "mmf_w2v_weightnorm_bwd",
     "mmf_w2v_window_fold_gelu_bwd", "mmf_w2v_conv0_bwd_stats", "mmf_w2v_conv0_bwd_wgrad",
+    "mmf_w2v_conv0_ln_gelu", "mmf_w2v_ln_gelu_window",
     "mmf_deberta_embed", "mmf_deberta_attn_fwd", "mmf_deberta_attn_fwd_lse", "mmf_deberta_attn_bwd", "mmf_deberta_embed_bwd",
     "mmf_deberta_attn_bwd_pos_workspace_bytes", "mmf_deberta_attn_bwd_pos",
     "mmf_deberta_embed_bwd_params_workspace_bytes", "mmf_deberta_embed_bwd_params", "mmf_embedding_scatter_add_f32",
@@ -263,6 +264,8 @@ def load() -> C.CDLL:
     lib.mmf_w2v_conv0_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_conv0_norm_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_w2v_gelu_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mmf_w2v_conv0_ln_gelu.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.mmf_w2v_ln_gelu_window.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
     lib.mmf_w2v_window_fold_gelu_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mmf_w2v_conv0_bwd_stats.argtypes = [vp] * 10 + [i32] * 7 + [f32, i32, vp]
     lib.mmf_w2v_conv0_bwd_wgrad.argtypes = [vp] * 9 + [i32] * 7 + [f32, i32, vp]
@@ -696,6 +699,35 @@ def w2v_gelu_window(x, out, N: int, T_in: int, C: int, k: int, s: int) -> None:
         raise ValueError("w2v_gelu_window: operand sizes do not match N, T_in, C, k, s")
     with _Timed("w2v_gelu_window_kernel", 0.0, [(N * T_out, k * C)]):
         check(load().mmf_w2v_gelu_window(x.data_ptr(), out.data_ptr(), N, T_in, C, k, s, stream_ptr()))
+
+
+def w2v_conv0_ln_gelu(wave, weight, bias, gamma, beta, out, k0: int, s0: int, k1: int, s1: int, eps: float) -> None:
+    """-> out (N, T1, k1 * C0) bf16: gelu(layernorm over channels(conv0(wave) + bias)) in the window form of the next conv layer, one
+    pass (``mmf_w2v_conv0_ln_gelu``); ``bias`` None: none"""
+    _w2v_f32(wave, weight, gamma, beta, *(() if bias is None else (bias,)))
+    _w2v_bf16(out)
+    N, L = wave.shape
+    C0 = weight.shape[0]
+    T1 = (((L - k0) // s0 + 1) - k1) // s1 + 1
+    if weight.numel() != C0 * k0 or gamma.numel() != C0 or beta.numel() != C0 or (bias is not None and bias.numel() != C0) \
+            or T1 < 1 or out.numel() < N * T1 * k1 * C0 or not out.is_contiguous():
+        raise ValueError("w2v_conv0_ln_gelu: operand sizes do not match N, L, C0 and the two kernels")
+    with _Timed("w2v_conv0_ln_gelu_kernel", 2.0 * N * ((L - k0) // s0 + 1) * C0 * k0, [(N, L)]):
+        check(load().mmf_w2v_conv0_ln_gelu(wave.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), gamma.data_ptr(),
+                                           beta.data_ptr(), out.data_ptr(), N, L, C0, k0, s0, k1, s1, eps, stream_ptr()))
+
+
+def w2v_ln_gelu_window(x, gamma, beta, out, N: int, T_in: int, C: int, k: int, s: int, eps: float) -> None:
+    """x (N, T_in, C) bf16 -> out (N, T_out, k * C) bf16, out[n][t][j*C + c] = gelu(LN(x[n][s*t + j])[c]), LayerNorm over the channels
+    of a row (``mmf_w2v_ln_gelu_window``); ``k == 0``: out (N, T_in, C), which may be x"""
+    _w2v_bf16(x, out)
+    _w2v_f32(gamma, beta)
+    rows = ((T_in - k) // s + 1) * k if k else T_in
+    if x.numel() < N * T_in * C or not x.is_contiguous() or rows < 1 or out.numel() < N * rows * C or not out.is_contiguous() \
+            or gamma.numel() != C or beta.numel() != C:
+        raise ValueError("w2v_ln_gelu_window: operand sizes do not match N, T_in, C, k, s")
+    with _Timed("w2v_ln_gelu_window_kernel", 0.0, [(N * rows, C)]):
+        check(load().mmf_w2v_ln_gelu_window(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), N, T_in, C, k, s, eps, stream_ptr()))
 
 
 def w2v_window_fold_gelu_bwd(dwin, x, dx, N: int, T_in: int, C: int, k: int, s: int) -> None:

@@ -218,14 +218,6 @@ class NativeViT(FrozenBackbone):
         return self._bytes_per_item(self._ws_table())
 
     # -- launches ---------------------------------------------------------------------------------------
-    def _layer(self, i: int, ws, n: int) -> None:
-        rows, d = n * self.T, self.config.hidden_size
-        x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
-        self._ln(ws, x, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")
-        y = self._attention(i, ws, ln, x, n, self.T)
-        self._ln(ws, y, ln, f"l{i}_ln2_w", f"l{i}_ln2_b")
-        self._ffn(i, ws, ln, y, x)
-
     def _layer_cls(self, i: int, ws, n: int) -> None:
         """The last layer for the CLS rows: K / V of every token, everything else on row 0 of each image.  Leaves the
         layer's output for those rows in the leading ``n`` rows of ``x``."""
@@ -314,7 +306,7 @@ class NativeViT(FrozenBackbone):
                 if cls_only and i == L - 1:
                     self._layer_cls(i, ws, n)
                 else:
-                    self._layer(i, ws, n)
+                    self._pre_ln_layer(i, ws, n, T)
             rows, r0 = (n, n0) if cls_only else (n * T, n0 * T)
             x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
             if final is not None:
@@ -361,21 +353,21 @@ class NativeViT(FrozenBackbone):
     def _layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, cls: bool) -> None:
         """layer ``i`` again from its saved input ``xin`` up to the GELU output, then its backward with the weight, bias and
         LayerNorm gradients added into the parameters' ``.grad``.  ``ga`` holds the gradient of the layer's output on entry and
-        of ``xin`` (n T rows) on return.  ``cls``: the layer in ``_layer_cls``'s form; on entry ``ga`` then is n rows, one per image"""
+        of ``xin`` (n T rows) on return.  Every row: ``_pre_ln_layer_grad`` (mmfusion/backbone.py).  ``cls``: the layer in
+        ``_layer_cls``'s form, below; on entry ``ga`` then is n rows, one per image"""
+        if not cls:
+            self._pre_ln_layer_grad(i, ws, g, xin, n, self.T, lambda qkv, att, datt, dqkv: self._attn_bwd(ws, g, qkv, att, datt, dqkv, n, self.T),
+                                    lambda dqkv, ln1: self._qkv_wgrad(i, g, dqkv, ln1, n, False), self._slabs_for)
+            return
         c, T = self.config, self.T
         d, I, R, rows = c.hidden_size, c.intermediate_size, self._rows, n * T
-        m = n if cls else rows                                        # the rows behind the attention
         ln1, qkv, dqkv = R(ws, "ln", rows, d), R(ws, "qkv", rows, 3 * d), R(g, "dqkv", rows, 3 * d)
-        att, h, ln2, gel, ga, gb, dh = R(ws, "att", m, d), R(ws, "h", m, I), R(g, "ln2", m, d), R(g, "g", m, I), R(g, "ga", m, d), R(g, "gb", m, d), R(g, "dh", m, I)
+        att, h, ln2, gel, ga, gb, dh = R(ws, "att", n, d), R(ws, "h", n, I), R(g, "ln2", n, d), R(g, "g", n, I), R(g, "ga", n, d), R(g, "gb", n, d), R(g, "dh", n, I)
         st1, st2 = self._stats(g, 1), self._stats(g, 2)
-        slabs = lambda M, N: self._slabs_for(m, self._tiles(M, N))
+        slabs = lambda M, N: self._slabs_for(n, self._tiles(M, N))
         W, F = lambda r: self._w(f"l{i}_{r}_w"), lambda r: self._f(f"l{i}_{r}_b")
         # the forward again, up to the GELU output (nothing behind fc2 is read by a pre-LN layer's backward)
-        if cls:
-            y = self._cls_attention(i, ws, st1, xin, n)
-        else:
-            self._ln(st1, xin, ln1, f"l{i}_ln1_w", f"l{i}_ln1_b")
-            y = self._attention(i, ws, ln1, xin, n, T)
+        y = self._cls_attention(i, ws, st1, xin, n)
         self._ln(st2, y, ln2, f"l{i}_ln2_w", f"l{i}_ln2_b")
         ops.gemm(GEMM_NT, ln2, W("fc1"), h)
         lib.bias_gelu_to(h, F("fc1"), gel)
@@ -389,13 +381,9 @@ class NativeViT(FrozenBackbone):
         # the attention
         self._wgrad(ga, att, f"l{i}_o", slabs(d, d))
         ops.gemm(GEMM_NN, ga, W("o"), gb)                                              # datt
-        self._attn_bwd(ws, g, qkv, att, gb, dqkv, n, 1 if cls else T)
-        self._qkv_wgrad(i, g, dqkv, ln1, n, cls)
+        self._attn_bwd(ws, g, qkv, att, gb, dqkv, n, 1)
+        self._qkv_wgrad(i, g, dqkv, ln1, n, True)
         gx, gl = R(g, "ga", rows, d), R(g, "gb", rows, d)
-        if not cls:
-            ops.gemm(GEMM_NN, dqkv, W("qkv"), gl)                                      # dln1
-            self._ln_bwd(st1, xin, gl, gx, f"l{i}_ln1_w", self._grads(i, "ln1"), resid=gx)      # ga = dx: the attention branch + the residual
-            return
         # dln1 = the K | V input gradient of every row + the Q one on row 0 of each image: the latter goes into a zeroed buffer
         # (``g``: the GELU output is done with) that the former's epilogue adds; the residual gradient reaches row 0 only, so it
         # is a zeroed buffer too (``ln2``) with ``ga``'s n rows copied in

@@ -4,8 +4,10 @@ feature extractor itself where it is.
 
 The reference pushes every clip through HuggingFace's ``Wav2Vec2Model`` per step (reference models/encoders.py:116,144).
 ``NativeWav2Vec2`` is that model rebuilt from its sizes alone (nothing is fetched), with HuggingFace's ``state_dict``
-surface, so published checkpoints and the reference's ``.pth`` files load.  Only the base family is built: group-norm
-feature extractor without conv biases, post-LN encoder.
+surface, so published checkpoints and the reference's ``.pth`` files load.  Two families are built, by one switch with three
+spellings: the base family (group-norm feature extractor without conv biases, post-LN encoder; the launch list below) and the
+layer-norm family (``feat_extract_norm="layer"``, ``conv_bias=True``, ``do_stable_layer_norm=True``: "The layer-norm family"
+below).  ``FAMILIES`` holds the released sizes as constructor kwargs.
 
 Activations are channel-last ``(time, channels)`` bf16, so a convolution over time is one GEMM over a window form and the
 transformer needs no transpose.  Launch list for a chunk of ``n`` clips (the layer's two blocks: mmfusion/backbone.py):
@@ -76,6 +78,33 @@ by side and walks it top down (dr_i: the gradient of layer i's raw output; it ta
 No host synchronisation and no floating-point atomics in any of these; the inner conv weights' bf16 shadows are the arena's, which
 the optimiser writes with the masters (tests/test_w2v_feature_encoder_gpu.py steps it and checks the next forward).
 
+The layer-norm family (wav2vec2-large-lv60, large-960h-lv60-self, large-robust, xlsr-53, XLS-R).  Every conv layer is Conv1d(bias) ->
+LayerNorm over the channels of a frame (eps 1e-5, affine) -> GELU, and the encoder is HuggingFace's ``Wav2Vec2EncoderStableLayerNorm``:
+nothing behind the positional convolution, pre-LN layers, ``encoder.layer_norm`` on top.  Launch list for a chunk:
+
+    conv 0 + bias + LN + GELU     mmf_w2v_conv0_ln_gelu                wave -> window form of layer 1, one pass, no statistics
+    conv layer i >= 1             mmf_gemm_grouped NT, BIAS            window -> raw (n T_i, C_i)
+    LN + GELU + next window       mmf_w2v_ln_gelu_window               raw -> window form of layer i + 1 (k = 0 behind the last layer: in place)
+    LayerNorm(conv_dim), projection + bias                             as above; the projection lands in ``y``
+    x + gelu(pos_conv(x) + b)     mmf_w2v_posconv                      y -> x, layer 0's input
+    per pre-LN layer (``_pre_ln_layer``, mmfusion/backbone.py: ViT's):
+      LayerNorm                                                        x  -> ln
+      _attention(ln, + x)                                              ln -> qkv -> att -> y
+      LayerNorm                                                        y  -> ln
+      _ffn(ln, + y)                                                    ln -> h -> x
+    encoder.layer_norm, widening cast                                  x  -> y -> result
+
+bf16 is stored where the table has an arrow: layer 0 after its GELU, each raw conv output after the bias, each LN + GELU output, then
+as the base family.  The C_i / 8 lanes that own a frame reduce its statistics among themselves (csrc/wav2vec2.hip), so C_i / 8 must
+be a power of two up to 256.  Fine-tuning is HuggingFace's ``freeze_feature_encoder()`` regime: ``set_trainable_layers(k)`` trains
+the top ``k`` layers and, from ``k = 1`` on, ``encoder.layer_norm`` above them; ``front=True`` (``k == L``) adds the feature
+projection, its LayerNorm and the positional convolution.  The forward also keeps the input of ``encoder.layer_norm``; the backward
+starts with that LayerNorm's, walks ``_pre_ln_layer_grad`` (ViT's layer backward, with this class's exact-delta attention backward,
+K-slab weight gradients and no column sum for the key bias; a pre-LN layer's Q/K/V input gradient is always formed, since its first
+LayerNorm's own gradients come out of it) and ends in the front end's backward above without the encoder LayerNorm.  Refused on this
+family, each with a ``ValueError``: ``feature_encoder=True`` (the backward of the LayerNorm over channels is not built), any
+regulariser above 0, and every mixed setting of the three switches (no released checkpoint has one).
+
 Regularisers.  HuggingFace's model in ``train()`` masks time spans with ``masked_spec_embed``, drops at seven kinds of place and
 skips layers, and the reference trains it that way; here they are opt-in (``set_regularisation``, all off by default) and act only in a
 differentiable call in ``train()`` mode.  Such a call takes 3 + 4 L sites from ``ops.next_site()`` (``_Reg``) in HuggingFace's order:
@@ -109,6 +138,15 @@ DEFAULT_CHUNK = 16
 POS_WGRAD_BLOCK = 128                      # time rows per unit of mmf_w2v_posconv_wgrad (WG_TT of csrc/wav2vec2.hip)
 POS_WGRAD_TAPS = 8                         # taps per workgroup of it
 POS_GROUP_WIDTHS = (16, 32, 48, 64)        # the forms of mmf_w2v_posconv
+
+# constructor kwargs of the released families.  "large-lv60" is the layer-norm family (wav2vec2-large-lv60, large-960h-lv60-self,
+# large-robust, xlsr-53, the XLS-R models): ``config.audio_backbone_kwargs = FAMILIES["large-lv60"]``
+_LARGE = dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096)
+FAMILIES = {
+    "base": dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072),
+    "large": dict(_LARGE),
+    "large-lv60": dict(_LARGE, feat_extract_norm="layer", conv_bias=True, do_stable_layer_norm=True),
+}
 
 _WN = "encoder.pos_conv_embed.conv."
 _WN_NEW = (_WN + "parametrizations.weight.original0", _WN + "parametrizations.weight.original1")
@@ -197,24 +235,27 @@ class _Differentiable(torch.autograd.Function):
         first = L - model.trainable_layers                             # the lowest layer the backward walks
         keep = model._keep(first, N * T, wave.device)
         feat = torch.empty((N * T, c.conv_dim[-1]), dtype=BF16, device=wave.device) if model.trainable_front else None
+        final = torch.empty((N * T, c.hidden_size), dtype=BF16, device=wave.device) if model._ln_family else None
         pos_w = model._pos_weight()
-        out = model._launches(wave, pos_w, keep, first, feat, reg)
+        out = model._launches(wave, pos_w, keep, first, feat, reg, final)
         ctx.model, ctx.first, ctx.front, ctx.pos_w, ctx.reg = model, first, model.trainable_front, pos_w, reg
         ctx.feature_encoder = model.trainable_feature_encoder
-        ctx.save_for_backward(*((wave, keep) if feat is None else (wave, keep, feat)))
+        ctx.save_for_backward(wave, keep, *(t for t in (feat, final) if t is not None))
         return out
 
     @staticmethod
     def backward(ctx, dout: torch.Tensor):
-        wave, keep, *feat = ctx.saved_tensors
+        wave, keep, *rest = ctx.saved_tensors
         if any(ctx.needs_input_grad[3:]):
-            ctx.model._backward(wave, keep, feat[0] if ctx.front else None, ctx.first, ctx.pos_w, dout.contiguous(), ctx.reg,
-                                ctx.feature_encoder)
+            feat = rest.pop(0) if ctx.front else None
+            ctx.model._backward(wave, keep, feat, ctx.first, ctx.pos_w, dout.contiguous(), ctx.reg, ctx.feature_encoder,
+                                rest[0] if rest else None)
         return (None,) * len(ctx.needs_input_grad)
 
 
 class NativeWav2Vec2(FrozenBackbone):
-    """HuggingFace ``Wav2Vec2Model`` (no attention mask), defaults = wav2vec2-base.
+    """HuggingFace ``Wav2Vec2Model`` (no attention mask), defaults = wav2vec2-base; ``feat_extract_norm="layer"``, ``conv_bias=True`` and
+    ``do_stable_layer_norm=True`` together: the layer-norm family (``FAMILIES["large-lv60"]``).
 
     ``forward(input_values)`` -> ``.last_hidden_state`` (N, T, hidden) f32; ``input_values``: (N, L) f32 on the GPU.
     Frozen by default; after ``set_trainable_layers(k)``, ``k > 0``, a call in grad mode carries the top ``k`` layers' weight
@@ -236,12 +277,14 @@ class NativeWav2Vec2(FrozenBackbone):
         dims, ks, ss = tuple(int(v) for v in conv_dim), tuple(int(v) for v in conv_kernel), tuple(int(v) for v in conv_stride)
         pk, pg = int(num_conv_pos_embeddings), int(num_conv_pos_embedding_groups)
         who = "NativeWav2Vec2"
-        if feat_extract_norm != "group":
-            raise ValueError(f"{who}: feat_extract_norm={feat_extract_norm!r}: only the 'group' (base) family is built")
-        if do_stable_layer_norm:
-            raise ValueError(f"{who}: do_stable_layer_norm=True (the large-lv60 family) is not built")
-        if conv_bias:
-            raise ValueError(f"{who}: conv_bias=True is not built (the base family has no conv biases)")
+        if feat_extract_norm not in ("group", "layer"):
+            raise ValueError(f"{who}: feat_extract_norm={feat_extract_norm!r}: 'group' (the base family) or 'layer'")
+        switches = (feat_extract_norm == "layer", bool(do_stable_layer_norm), bool(conv_bias))
+        if any(switches) != all(switches):
+            raise ValueError(f"{who}: feat_extract_norm={feat_extract_norm!r}, do_stable_layer_norm={do_stable_layer_norm!r}, "
+                             f"conv_bias={conv_bias!r}: the layer-norm family (large-lv60, XLS-R) sets all three ('layer', True, "
+                             "True) and the base family none; no mixed setting is built (no released checkpoint has one)")
+        ln_family = all(switches)
         if not (len(dims) == len(ks) == len(ss)) or len(dims) < 2 or min(dims + ks + ss) < 1:
             raise ValueError(f"{who}: conv_dim, conv_kernel and conv_stride must be positive and of one length of at least 2")
         super().__init__(d, H, chunk, ln_widths={"conv_dim[-1]": dims[-1]})
@@ -258,6 +301,9 @@ class NativeWav2Vec2(FrozenBackbone):
         cg = d // pg
         if any(c % 8 for c in dims) or I % 8 or cg % 8:
             raise ValueError(f"{who}: conv_dim {dims}, intermediate_size {I} and the positional group width {cg} must be multiples of 8")
+        if ln_family and any(c > 2048 or (c // 8) & (c // 8 - 1) for c in dims):
+            raise ValueError(f"{who}: conv_dim {dims}: the layer-norm family's LayerNorm over channels takes 8 times a power of two, "
+                             "8 .. 2048 channels")
         kp = (pk * cg + 31) // 32 * 32
         if cg not in POS_GROUP_WIDTHS or pk < 1 or (127 * cg + kp) * 2 > 65536:
             raise ValueError(f"{who}: positional convolution with group width {cg} (one of {POS_GROUP_WIDTHS}) and kernel {pk} has no "
@@ -266,18 +312,25 @@ class NativeWav2Vec2(FrozenBackbone):
             raise ValueError(f"{who}: layers and chunk at least 1")
         self.config = types.SimpleNamespace(
             hidden_size=d, num_hidden_layers=int(num_hidden_layers), num_attention_heads=H, intermediate_size=I, conv_dim=dims,
-            conv_kernel=ks, conv_stride=ss, conv_bias=False, num_conv_pos_embeddings=pk, num_conv_pos_embedding_groups=pg,
-            layer_norm_eps=float(layer_norm_eps), feat_extract_norm="group", do_stable_layer_norm=False, hidden_act="gelu",
+            conv_kernel=ks, conv_stride=ss, conv_bias=ln_family, num_conv_pos_embeddings=pk, num_conv_pos_embedding_groups=pg,
+            layer_norm_eps=float(layer_norm_eps), feat_extract_norm="layer" if ln_family else "group", do_stable_layer_norm=ln_family, hidden_act="gelu",
             feat_extract_activation="gelu", num_feat_extract_layers=len(dims), model_type="wav2vec2")
         self.pos_cg, self.pos_kp = cg, kp
+        self._ln_family = ln_family
         add = self._add
         add("masked_spec_embed", (d,), "masked_spec_embed", std=1.0)
         fe = "feature_extractor.conv_layers."
         add("conv0_w", (dims[0], 1, ks[0]), fe + "0.conv.weight", std=0.3)
-        add("conv0_gn_w", (dims[0],), fe + "0.layer_norm.weight", ones=True)
+        if ln_family:
+            add("conv0_b", (dims[0],), fe + "0.conv.bias", std=0.0)
+        add("conv0_gn_w", (dims[0],), fe + "0.layer_norm.weight", ones=True)       # (the layer-norm family's LayerNorm of layer 0 as well)
         add("conv0_gn_b", (dims[0],), fe + "0.layer_norm.bias", std=0.0)
         for i in range(1, len(dims)):
             add(f"conv{i}_w", (dims[i], ks[i], dims[i - 1]), f"{fe}{i}.conv.weight", std=(dims[i - 1] * ks[i]) ** -0.5, swapped=True)
+            if ln_family:
+                add(f"conv{i}_b", (dims[i],), f"{fe}{i}.conv.bias", std=0.0)
+                add(f"conv{i}_ln_w", (dims[i],), f"{fe}{i}.layer_norm.weight", ones=True)
+                add(f"conv{i}_ln_b", (dims[i],), f"{fe}{i}.layer_norm.bias", std=0.0)
         add("fp_ln_w", (dims[-1],), "feature_projection.layer_norm.weight", ones=True)
         add("fp_ln_b", (dims[-1],), "feature_projection.layer_norm.bias", std=0.0)
         add("fp_w", (d, dims[-1]), "feature_projection.projection.weight")
@@ -324,7 +377,11 @@ class NativeWav2Vec2(FrozenBackbone):
         """the parameters that require a gradient, in the order the differentiable forward takes them"""
         L, k = self.config.num_hidden_layers, self._trainable
         front = list(self._FRONT_PARAMS) + (["masked_spec_embed"] if self.config.mask_time_prob > 0.0 else []) if self._front else []
-        return (self._feature_params() if self._feature_encoder else []) + front + [n for i in range(L - k, L) for n in self._layer_params(i)]
+        layers = [n for i in range(L - k, L) for n in self._layer_params(i)]
+        if self._ln_family:                    # encoder.layer_norm sits on top of the layers: it trains with the first of them
+            top = ("enc_ln_w", "enc_ln_b")
+            return [n for n in front if n not in top] + layers + (list(top) if k else [])
+        return (self._feature_params() if self._feature_encoder else []) + front + layers
 
     # -- training-mode regularisers ------------------------------------------------------------------------
     def set_regularisation(self, **settings) -> None:
@@ -351,6 +408,10 @@ class NativeWav2Vec2(FrozenBackbone):
             v = new[n]
             if isinstance(v, bool) or not isinstance(v, int) or v < low:
                 raise ValueError(f"{who}({n}={v!r}): an integer of at least {low}")
+        on = [n for n in REG_NAMES[:6] if new[n] > 0.0]
+        if self._ln_family and on:
+            raise ValueError(f"{who}({', '.join(f'{n}={new[n]!r}' for n in on)}): the training-mode regularisers are not built for the "
+                             "layer-norm family (feat_extract_norm='layer'); they stay at 0 there")
         for n in REG_NAMES:
             setattr(c, n, float(new[n]) if n not in ("mask_time_length", "mask_time_min_masks") else new[n])
         c.apply_spec_augment = c.mask_time_prob > 0.0
@@ -394,6 +455,10 @@ class NativeWav2Vec2(FrozenBackbone):
         if feature_encoder and not front:
             raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}, front={front!r}, feature_encoder={feature_encoder!r}): the "
                              "feature encoder trains with the front end only (its gradient comes through the front end)")
+        if feature_encoder and self._ln_family:
+            raise ValueError(f"NativeWav2Vec2: set_trainable_layers({k!r}, front={front!r}, feature_encoder=True): the layer-norm family's "
+                             "feature encoder does not train (the backward of its LayerNorm over channels is not built); "
+                             "HuggingFace's freeze_feature_encoder() regime, front=True, is")
         if feature_encoder != self._feature_encoder:
             self._gws = None                                              # the backward's table changes (``_grad_table``)
         self._trainable, self._front, self._feature_encoder = k, front, feature_encoder
@@ -427,8 +492,10 @@ class NativeWav2Vec2(FrozenBackbone):
         """per clip of ``L`` samples"""
         c, T = self.config, self.frames(L)
         win, raw = self._conv_elements(L)
-        return [("win", win, BF16), ("raw", raw, BF16)] + self._token_table(T, T * c.intermediate_size) \
-            + [("stats", 2 * c.conv_dim[0], torch.float32), ("partial", lib.W2V_STATS_SLOTS * 2 * c.conv_dim[0], torch.float32)]
+        table = [("win", win, BF16), ("raw", raw, BF16)] + self._token_table(T, T * c.intermediate_size)
+        if self._ln_family:                    # layer 0 is one pass: no statistics
+            return table
+        return table + [("stats", 2 * c.conv_dim[0], torch.float32), ("partial", lib.W2V_STATS_SLOTS * 2 * c.conv_dim[0], torch.float32)]
 
     def workspace_bytes_per_clip(self, L: int) -> int:
         return self._bytes_per_item(self._ws_table(L))
@@ -463,6 +530,8 @@ class NativeWav2Vec2(FrozenBackbone):
         there: the last layer's GELU is not applied, and ``win`` is left holding the last layer's window form"""
         c = self.config
         dims, ks, ss = c.conv_dim, c.conv_kernel, c.conv_stride
+        if self._ln_family:
+            return self._features_ln(ws, wave, n, Ts)
         w0 = self._f("conv0_w")
         lib.w2v_conv0_stats(wave, w0, ws["stats"], ws["partial"], ks[0], ss[0])
         lib.w2v_conv0_norm_gelu(wave, w0, ws["stats"], self._f("conv0_gn_w"), self._f("conv0_gn_b"), ws["win"], ks[0], ss[0],
@@ -476,6 +545,22 @@ class NativeWav2Vec2(FrozenBackbone):
                 lib.w2v_gelu_window(raw, ws["win"], n, Ts[i], dims[i], ks[i + 1], ss[i + 1])
             elif raws is None:
                 lib.bias_gelu(raw)
+        return raw
+
+    def _features_ln(self, ws, wave: torch.Tensor, n: int, Ts: List[int]) -> torch.Tensor:
+        """``_features`` of the layer-norm family: every layer is conv + bias -> LayerNorm over channels -> GELU (nn.LayerNorm's
+        own eps, 1e-5, not layer_norm_eps).  Layer 0 in one pass, an inner layer's bias in its GEMM's epilogue and its LayerNorm
+        and GELU on the way into the next window form; behind the last layer in place"""
+        c = self.config
+        dims, ks, ss, last = c.conv_dim, c.conv_kernel, c.conv_stride, len(c.conv_dim) - 1
+        lib.w2v_conv0_ln_gelu(wave, self._f("conv0_w"), self._f("conv0_b"), self._f("conv0_gn_w"), self._f("conv0_gn_b"), ws["win"],
+                              ks[0], ss[0], ks[1], ss[1], 1e-5)
+        for i in range(1, last + 1):
+            rows, K = n * Ts[i], ks[i] * dims[i - 1]
+            win, raw = self._rows(ws, "win", rows, K), self._rows(ws, "raw", rows, dims[i])
+            ops.gemm(GEMM_NT, win, self._w(f"conv{i}_w").view(dims[i], K), raw, bias=self._f(f"conv{i}_b"), epilogue=EPI_BIAS)
+            k, s = (ks[i + 1], ss[i + 1]) if i < last else (0, 1)
+            lib.w2v_ln_gelu_window(raw, self._f(f"conv{i}_ln_w"), self._f(f"conv{i}_ln_b"), ws["win"] if k else raw, n, Ts[i], dims[i], k, s, 1e-5)
         return raw
 
     def forward(self, input_values: torch.Tensor, attention_mask=None) -> BackboneOutput:
@@ -496,10 +581,12 @@ class NativeWav2Vec2(FrozenBackbone):
     def _front_end(self, ws, feat: torch.Tensor, pos_w: torch.Tensor, n: int, T: int, st=None, reg: Optional[_Reg] = None,
                    n0: int = 0) -> None:
         """feat (n T, conv_dim[-1]) -> the feature LayerNorm (into ``win``; statistics into ``st``, None: the workspace's), the
-        projection (``x``) and the positional convolution (``y``).  With ``reg`` (``n0``: the chunk's first clip in the batch) the
+        projection (``x``) and the positional convolution (``y``; the layer-norm family: the other way round).  With ``reg`` (``n0``: the chunk's first clip in the batch) the
         projection's output is dropped and the time mask's rows set to ``masked_spec_embed``, in place, in front of the convolution"""
         c, d, rows = self.config, self.config.hidden_size, n * T
         x, y, fln = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d), self._rows(ws, "win", rows, feat.shape[1])
+        if self._ln_family:                    # no LayerNorm behind the convolution: its output is layer 0's input, ``x``
+            x, y = y, x
         self._ln(ws if st is None else st, feat, fln, "fp_ln_w", "fp_ln_b")
         ops.gemm(GEMM_NT, fln, self._w("fp_w"), x, bias=self._f("fp_b"), epilogue=EPI_BIAS)
         if reg is not None and reg.front:
@@ -523,10 +610,11 @@ class NativeWav2Vec2(FrozenBackbone):
         return attend, join, join_bwd, act
 
     def _launches(self, wave: torch.Tensor, pos_w: torch.Tensor, keep: Optional[torch.Tensor] = None, first: int = 0,
-                  feat_keep: Optional[torch.Tensor] = None, reg: Optional[_Reg] = None) -> torch.Tensor:
+                  feat_keep: Optional[torch.Tensor] = None, reg: Optional[_Reg] = None, final: Optional[torch.Tensor] = None) -> torch.Tensor:
         """the launch list on checked inputs -> (N, T, d) f32.  The differentiable call's: ``keep`` (layers - first, N T, d) bf16
         also takes a copy of the input of every layer from ``first`` up, ``feat_keep`` (N T, conv_dim[-1]) one of the feature
-        LayerNorm's input; ``reg``: the call's regularisers (a layer LayerDrop skips launches nothing and keeps nothing)"""
+        LayerNorm's input; ``reg``: the call's regularisers (a layer LayerDrop skips launches nothing and keeps nothing); ``final``
+        (N T, d), the layer-norm family: one of the input of ``encoder.layer_norm``, which sits behind the last layer there"""
         c = self.config
         N, L = wave.shape
         Ts = feat_lengths(L, c.conv_kernel, c.conv_stride)
@@ -540,7 +628,8 @@ class NativeWav2Vec2(FrozenBackbone):
                 feat_keep[n0 * T:n0 * T + rows].copy_(feat)
             x, y = self._rows(ws, "x", rows, d), self._rows(ws, "y", rows, d)
             self._front_end(ws, feat, pos_w, n, T, None, reg, n0)
-            self._ln(ws, y, x, "enc_ln_w", "enc_ln_b")
+            if not self._ln_family:
+                self._ln(ws, y, x, "enc_ln_w", "enc_ln_b")
             if reg is not None and reg.p_h > 0.0:
                 lib.hidden_dropout(x, x, n, reg.hidden(reg.enc, n0))
             for i in range(c.num_hidden_layers):
@@ -548,8 +637,16 @@ class NativeWav2Vec2(FrozenBackbone):
                     continue
                 if keep is not None and i >= first:
                     keep[i - first, n0 * T:n0 * T + rows].copy_(x)
+                if self._ln_family:
+                    self._pre_ln_layer(i, ws, n, T)
+                    continue
                 attend, join, _, act = self._hooks(i, ws, n, T, n0, reg)
                 self._post_ln_layer(i, ws, n, T, attend, join, act)
+            if self._ln_family:
+                if final is not None:
+                    final[n0 * T:n0 * T + rows].copy_(x)
+                self._ln(ws, x, y, "enc_ln_w", "enc_ln_b")
+                x = y
             self._widen(x, out[n0:n0 + n])
         return out
 
@@ -562,7 +659,7 @@ class NativeWav2Vec2(FrozenBackbone):
         0's two sums per channel (``bsums``)"""
         c = self.config
         T, cd = self.frames(L), c.conv_dim[-1]
-        table = self._grad_rows(T) + [("dfln", T * cd, BF16), ("dfeat", T * cd, BF16)]
+        table = self._grad_rows(T, "ln2" if self._ln_family else "y2") + [("dfln", T * cd, BF16), ("dfeat", T * cd, BF16)]
         if self._feature_encoder:
             Ts = feat_lengths(L, c.conv_kernel, c.conv_stride)
             inner = range(1, len(Ts))
@@ -608,6 +705,16 @@ class NativeWav2Vec2(FrozenBackbone):
         self._post_ln_layer_grad(i, ws, g, xin, n, T, attend, attn_bwd, lambda dqkv, x: self._qkv_wgrad_roles(i, g["junk"], dqkv, x),
                                  below, self._slabs_for, join, join_bwd, act)
 
+    def _ln_family_layer_grad(self, i: int, ws, g, xin: torch.Tensor, n: int, T: int) -> None:
+        """the layer-norm family's ``_layer_grad``: ``_pre_ln_layer_grad`` (mmfusion/backbone.py) with this class's attention backward
+        (the exact-delta route) and Q/K/V weight gradient (no column sum for the key bias).  ``ga`` holds the gradient of ``xin`` on
+        return whatever lies below: a pre-LN layer's first LayerNorm is its own parameter and its backward takes that gradient in"""
+        def attn_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, dqkv: torch.Tensor) -> None:
+            lib.attn_bwd_grouped_exact_delta([self._attn_problem(ws, qkv, att, n, T, T, datt, g["delta"], dqkv)], self.head_dim,
+                                             self.head_dim ** -0.5)
+        self._pre_ln_layer_grad(i, ws, g, xin, n, T, attn_bwd, lambda dqkv, ln1: self._qkv_wgrad_roles(i, g["junk"], dqkv, ln1),
+                                self._slabs_for)
+
     def _front_grad(self, ws, g, feat: torch.Tensor, pos_w: torch.Tensor, pos_wt: torch.Tensor, n: int, T: int,
                     reg: Optional[_Reg] = None, n0: int = 0) -> None:
         """the front end again from the saved ``feat``, then its backward: ``ga`` holds the gradient of layer 0's input on entry.
@@ -615,7 +722,8 @@ class NativeWav2Vec2(FrozenBackbone):
         their ``.grad``; the positional weight's into ``g["dpos"]`` (f32, packed), which ``_backward`` finishes.  With ``reg``
         the front end is computed under the forward's masks again (``x0`` is the masked, dropped projection), the gradient first
         passes the encoder dropout, the rows of dx0 inside a span are summed into ``masked_spec_embed``'s gradient where it trains
-        (per-slab partials, ``mmf_sum_slabs_f32``: a fixed order), and the projection's gradients take dproj = in_span ? 0 : dx0 keep c"""
+        (per-slab partials, ``mmf_sum_slabs_f32``: a fixed order), and the projection's gradients take dproj = in_span ? 0 : dx0 keep c.
+        The layer-norm family has no encoder LayerNorm here (it sits on top of the layers: ``_backward``); ``ga`` / ``gb`` swap roles"""
         c = self.config
         rows, d, cd, R = n * T, c.hidden_size, c.conv_dim[-1], self._rows
         G, k = c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
@@ -623,10 +731,13 @@ class NativeWav2Vec2(FrozenBackbone):
         ga, gb, dz, dfln, dfeat = R(g, "ga", rows, d), R(g, "gb", rows, d), R(g, "dqkv", rows, d), R(g, "dfln", rows, cd), R(g, "dfeat", rows, cd)
         st1, st2 = self._stats(g, 1), self._stats(g, 2)
         self._front_end(ws, feat, pos_w, n, T, st1, reg, n0)
-        self._ln(st2, y, R(ws, "ln", rows, d), "enc_ln_w", "enc_ln_b")               # for its statistics; the output is not read
-        if reg is not None and reg.p_h > 0.0:
-            lib.hidden_dropout(ga, ga, n, reg.hidden(reg.enc, n0))                     # through the dropout behind the encoder LayerNorm
-        self._ln_bwd(st2, y, ga, gb, "enc_ln_w", (self.enc_ln_w.grad, self.enc_ln_b.grad))          # gb = dy
+        if self._ln_family:                    # layer 0 reads the convolution's output itself: the gradient on entry is dy already
+            x0, ga, gb = y, gb, ga
+        else:
+            self._ln(st2, y, R(ws, "ln", rows, d), "enc_ln_w", "enc_ln_b")           # for its statistics; the output is not read
+            if reg is not None and reg.p_h > 0.0:
+                lib.hidden_dropout(ga, ga, n, reg.hidden(reg.enc, n0))                 # through the dropout behind the encoder LayerNorm
+            self._ln_bwd(st2, y, ga, gb, "enc_ln_w", (self.enc_ln_w.grad, self.enc_ln_b.grad))      # gb = dy
         lib.w2v_posconv_bwd_act(x0, pos_w, self._f("pos_b"), gb, dz, n, T, d, G, k)
         lib.colsum_grouped([lib.ColsumProblem(dz.data_ptr(), self.pos_b.grad.data_ptr(), rows, d, d)])
         S = self._pos_wgrad_slabs(n, T)
@@ -688,12 +799,14 @@ class NativeWav2Vec2(FrozenBackbone):
                                 accumulate=not self._first_touch(w0g))
 
     def _backward(self, wave: torch.Tensor, keep: torch.Tensor, feat: Optional[torch.Tensor], first: int, pos_w: torch.Tensor,
-                  dout: torch.Tensor, reg: Optional[_Reg] = None, feature_encoder: bool = False) -> None:
+                  dout: torch.Tensor, reg: Optional[_Reg] = None, feature_encoder: bool = False,
+                  final: Optional[torch.Tensor] = None) -> None:
         """for the gradient ``dout`` (N, T, d) f32 of the result: the gradients of layers ``first`` .. L - 1 and, with ``feat`` (the
         saved input of the feature LayerNorm: the front end trains), of the front end, added into their ``.grad``.  ``keep``: the
         saved inputs of the layers from ``first`` up, ``pos_w``: the positional weight the forward used, ``reg``: its regularisers
         (a layer LayerDrop skipped is the identity: ``ga`` passes through and its parameters receive nothing); ``feature_encoder``:
-        the conv stack trains too (``_conv_grad`` takes each chunk's ``dfeat`` from ``_front_grad``)"""
+        the conv stack trains too (``_conv_grad`` takes each chunk's ``dfeat`` from ``_front_grad``); ``final``, the layer-norm
+        family: the saved input of ``encoder.layer_norm``, whose backward comes first there"""
         c, d, dev = self.config, self.config.hidden_size, wave.device
         self._refuse_fp32()
         N, Lw = wave.shape
@@ -704,9 +817,18 @@ class NativeWav2Vec2(FrozenBackbone):
             g["dpos"].zero_()
         for n0, n in self._chunks(N):
             rows = slice(n0 * T, (n0 + n) * T)
-            self._narrow(dout[n0:n0 + n], self._rows(g, "ga", n * T, d))
+            ga = self._rows(g, "ga", n * T, d)
+            if final is None:
+                self._narrow(dout[n0:n0 + n], ga)
+            else:
+                gb, st = self._rows(g, "gb", n * T, d), self._stats(g, 1)
+                self._narrow(dout[n0:n0 + n], gb)
+                self._ln(st, final[rows], self._rows(ws, "ln", n * T, d), "enc_ln_w", "enc_ln_b")     # for its statistics; the output is not read
+                self._ln_bwd(st, final[rows], gb, ga, "enc_ln_w", (self.enc_ln_w.grad, self.enc_ln_b.grad))
             for i in reversed(range(first, L)):
-                if reg is None or not reg.skip[i]:
+                if self._ln_family:
+                    self._ln_family_layer_grad(i, ws, g, keep[i - first, rows], n, T)
+                elif reg is None or not reg.skip[i]:
                     self._layer_grad(i, ws, g, keep[i - first, rows], n, T, front or i > first, reg, n0)
             if front:
                 self._front_grad(ws, g, feat[rows], pos_w, pos_wt, n, T, reg, n0)

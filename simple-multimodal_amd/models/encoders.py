@@ -18,7 +18,9 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     ``config.video_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers and the final
     LayerNorm then train, as the reference's optimiser trains ``video_encoder.vit``; ``"all"``: every layer and the embeddings;
   * ``config.audio_backbone = "native"`` (dynamic attribute, ``AudioEncoder`` only) builds ``mmfusion.wav2vec2.NativeWav2Vec2``
-    the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers).  Frozen
+    the same way: the base-family Wav2Vec2 (feature-extractor convolutions, positional convolution, post-LN layers) or, with
+    ``config.audio_backbone_kwargs = mmfusion.wav2vec2.FAMILIES["large-lv60"]``'s three switches, the layer-norm family (at widths
+    512 / 768 here: the temporal attention's 8 heads have no form for the head_dim 128 of a 1024-wide backbone yet).  Frozen
     unless ``config.audio_backbone_trainable_layers`` (dynamic attribute; default 0) is ``k`` > 0: the top ``k`` layers then
     train; ``"all"``: every layer and the front end above the feature-extractor convolutions (feature projection, positional
     convolution, encoder LayerNorm), which stay frozen as under HuggingFace's ``freeze_feature_encoder()``; ``"full"``: the

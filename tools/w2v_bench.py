@@ -15,8 +15,13 @@
     ``mmf_w2v_posconv``, which does the same FLOPs.  With --regularise as well: the same step in ``train()`` under
     wav2vec2-base-960h's regularisers (``mmfusion.wav2vec2.REG_960H``), with and without LayerDrop, and its per-kernel table.
 
-    python tools/w2v_bench.py [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table] [--no-torch]
-                              [--finetune K|all|full [--regularise]]
+  * --family NAME: a key of ``mmfusion.wav2vec2.FAMILIES`` instead of wav2vec2-base (seeded weights at its sizes).  On the
+    layer-norm family (``large-lv60``) the yardstick is tests/w2v_ln_ref.py the same way, and --ln-kernels times, instead, the
+    family's two kernels against the base family's on the family's own conv shapes and on the same buffers:
+    ``mmf_w2v_ln_gelu_window`` against ``mmf_w2v_gelu_window`` and ``mmf_w2v_conv0_ln_gelu`` against ``mmf_w2v_conv0_norm_gelu``.
+
+    python tools/w2v_bench.py [--family base] [--clips 16] [--samples 160000] [--chunks 4,8,16] [--steps 5] [--warmup 2] [--table]
+                              [--no-torch] [--finetune K|all|full [--regularise]] [--ln-kernels]
 Prints one JSON line (the table, when asked for, on the lines before it)."""
 import json
 
@@ -66,15 +71,46 @@ def posconv_kernels(model, n: int, T: int, steps: int, warmup: int) -> dict:
     return out
 
 
-def finetune(args, model, cfg, sd, x) -> dict:
-    import w2v_ref
+def ln_kernels(model, n: int, samples: int, steps: int, warmup: int) -> dict:
+    """the layer-norm family's two kernels against the base family's two, which move the same bytes, on one chunk of ``n`` clips at
+    the model's conv shapes: ms (the inner layers' summed) and the ratios"""
+    from mmfusion import lib
+    from mmfusion.wav2vec2 import feat_lengths
+    c = model.config
+    dims, ks, ss = c.conv_dim, c.conv_kernel, c.conv_stride
+    Ts = feat_lengths(samples, ks, ss)
+    g = torch.Generator().manual_seed(4)
+    wave = (0.5 * torch.randn(n, samples, generator=g)).cuda()
+    w0, b0, gamma, beta = model._f("conv0_w"), model._f("conv0_b"), model._f("conv0_gn_w"), model._f("conv0_gn_b")
+    stats = torch.empty(n * 2 * dims[0], device="cuda")
+    partial = torch.empty(n * lib.W2V_STATS_SLOTS * 2 * dims[0], device="cuda")
+    win = torch.empty(n * max(Ts[i] * ks[i] * dims[i - 1] for i in range(1, len(dims))), dtype=torch.bfloat16, device="cuda")
+    lib.w2v_conv0_stats(wave, w0, stats, partial, ks[0], ss[0])
+    ms = {"conv0_norm_gelu": time_eager(lambda: lib.w2v_conv0_norm_gelu(wave, w0, stats, gamma, beta, win, ks[0], ss[0], ks[1], ss[1], 1e-5), 4 * steps, warmup),
+          "conv0_ln_gelu": time_eager(lambda: lib.w2v_conv0_ln_gelu(wave, w0, b0, gamma, beta, win, ks[0], ss[0], ks[1], ss[1], 1e-5), 4 * steps, warmup),
+          "gelu_window": 0.0, "ln_gelu_window": 0.0}
+    layers = []
+    for i in range(1, len(dims) - 1):
+        raw = torch.randn(n, Ts[i], dims[i], generator=g).cuda().to(torch.bfloat16)
+        lw, lb, k, s = model._f(f"conv{i}_ln_w"), model._f(f"conv{i}_ln_b"), ks[i + 1], ss[i + 1]
+        a = time_eager(lambda: lib.w2v_gelu_window(raw, win, n, Ts[i], dims[i], k, s), 4 * steps, warmup)
+        b = time_eager(lambda: lib.w2v_ln_gelu_window(raw, lw, lb, win, n, Ts[i], dims[i], k, s, 1e-5), 4 * steps, warmup)
+        ms["gelu_window"], ms["ln_gelu_window"] = ms["gelu_window"] + a, ms["ln_gelu_window"] + b
+        layers.append({"layer": i, "T_in": Ts[i], "C": dims[i], "k": k, "s": s, "gelu_window_ms": round(a, 4), "ln_gelu_window_ms": round(b, 4),
+                       "ratio": round(b / a, 3)})
+    return {"clips": n, "samples": samples, "ms": {k: round(v, 4) for k, v in ms.items()}, "layers": layers,
+            "ln_gelu_window_over_gelu_window": round(ms["ln_gelu_window"] / ms["gelu_window"], 3),
+            "conv0_ln_gelu_over_conv0_norm_gelu": round(ms["conv0_ln_gelu"] / ms["conv0_norm_gelu"], 3)}
+
+
+def finetune(args, model, cfg, sd, x, w2v_ref) -> dict:
     from mmfusion import arena, wav2vec2
     N, L, d = args.clips, cfg.num_hidden_layers, cfg.hidden_size
     full = args.finetune == "full"
     front = full or args.finetune == "all"
     k = L if front else int(args.finetune)
     T = model.frames(args.samples)
-    res = {"model": "wav2vec2-base, bf16 storage", "clips": N, "samples": args.samples, "frames": T, "chunk": model.chunk,
+    res = {"model": f"wav2vec2-{args.family}, bf16 storage", "clips": N, "samples": args.samples, "frames": T, "chunk": model.chunk,
            "trainable_layers": k, "front": front, "feature_encoder": full}
     with torch.no_grad():
         res["forward_ms"] = round(time_eager(lambda: model(x), args.steps, args.warmup), 3)
@@ -88,7 +124,7 @@ def finetune(args, model, cfg, sd, x) -> dict:
     both = time_eager(step, args.steps, args.warmup)
     res["differentiable_forward_ms"], res["forward_backward_ms"] = round(fwd, 3), round(both, 3)
     res["forward_backward_ratio"] = round(both / res["forward_ms"], 3)
-    res["saved_inputs_mb"] = round((k * d + (cfg.conv_dim[-1] if front else 0)) * N * T * 2 / 2 ** 20, 1)
+    res["saved_inputs_mb"] = round((k * d + (cfg.conv_dim[-1] if front else 0) + (d if cfg.do_stable_layer_norm else 0)) * N * T * 2 / 2 ** 20, 1)
     res["grad_workspace_mb_per_clip"] = round(model.grad_workspace_bytes_per_clip(args.samples) / 2 ** 20, 2)
     res["kernels"] = kernel_table(step)
     print_table(res["kernels"])
@@ -112,6 +148,7 @@ def finetune(args, model, cfg, sd, x) -> dict:
         torch.cuda.empty_cache()
         keys = {n for n in sd if any(n.startswith(f"encoder.layers.{i}.") for i in range(L - k, L))
                 or (front and n.startswith(("feature_projection.", "encoder.pos_conv_embed.", "encoder.layer_norm.")))
+                or (cfg.do_stable_layer_norm and n.startswith("encoder.layer_norm."))
                 or (full and n.startswith("feature_extractor."))}
         leaves = {n: v.cuda().to(torch.bfloat16).requires_grad_(n in keys) for n, v in sd.items()}
         x16, d16, c = x.to(torch.bfloat16), dout.to(torch.bfloat16), wav2vec2.DEFAULT_CHUNK
@@ -133,25 +170,37 @@ def main():
     ap.add_argument("--samples", type=int, default=160000)
     ap.add_argument("--finetune", default=None, metavar="K|all|full")
     ap.add_argument("--regularise", action="store_true", help="with --finetune: also time the step under wav2vec2-base-960h's regularisers")
+    ap.add_argument("--family", default="base", help="a key of mmfusion.wav2vec2.FAMILIES")
+    ap.add_argument("--ln-kernels", action="store_true", help="the layer-norm family's two kernels against the base family's (large-lv60)")
     args = ap.parse_args()
-    import w2v_ref
     from mmfusion import wav2vec2
-    cfg = w2v_ref.base_config()
+    if args.family not in wav2vec2.FAMILIES:
+        ap.error(f"--family {args.family}: one of {', '.join(wav2vec2.FAMILIES)}")
+    model = wav2vec2.NativeWav2Vec2(**wav2vec2.FAMILIES[args.family])
+    cfg = model.config                                            # (the restatements read the sizes and the three switches from it)
+    if cfg.do_stable_layer_norm:
+        import w2v_ln_ref as w2v_ref
+    else:
+        import w2v_ref
     sd = w2v_ref.seeded_weights(cfg, seed=0)
-    model = wav2vec2.NativeWav2Vec2(**w2v_ref.config_kwargs(cfg))
     model.load_state_dict(sd)
     model = model.cuda().eval()
     N, L = args.clips, args.samples
+    if args.ln_kernels:
+        if not cfg.do_stable_layer_norm:
+            ap.error("--ln-kernels goes with a layer-norm family (--family large-lv60)")
+        print(json.dumps(ln_kernels(model, min(model.chunk, N), L, args.steps, args.warmup)))
+        return
     x = (0.5 * torch.randn(N, L, generator=torch.Generator().manual_seed(1))).cuda()
     if args.finetune is not None:
-        print(json.dumps(finetune(args, model, cfg, sd, x)))
+        print(json.dumps(finetune(args, model, cfg, sd, x, w2v_ref)))
         return
     gf = gflop_per_clip(cfg, L)
 
     def rate(ms: float) -> dict:
         return {"ms": round(ms, 3), "clips_per_s": round(N / ms * 1e3, 1), "tflops": round(gf["total"] * N / ms, 1)}
 
-    res = {"model": "wav2vec2-base, frozen, bf16 storage", "clips": N, "samples": L, "frames": model.frames(L), "gflop_per_clip": gf,
+    res = {"model": f"wav2vec2-{args.family}, frozen, bf16 storage", "clips": N, "samples": L, "frames": model.frames(L), "gflop_per_clip": gf,
            "default_chunk": wav2vec2.DEFAULT_CHUNK, "workspace_mb_per_clip": round(model.workspace_bytes_per_clip(L) / 2 ** 20, 2)}
 
     def measure(c):
