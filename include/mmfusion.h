@@ -1078,6 +1078,27 @@ int mmf_audio_resample(const float* wave, const int* len, const float* table, in
 int mmf_audio_augment(const float* x, float* out, const uint8_t* noise_on, const int* stretch_len, const uint64_t* rng_state,
                       uint32_t site, int B, int64_t L, void* stream);
 
+/* ---- WavLM's gated relative position bias (csrc/wavlm.hip) ----------------------------------------------------------------
+ * mmf_wavlm_gate: x (n*T, ldx) bf16, the layer's INPUT rows (H heads of head_dim columns each) -> gate (n, H, T) f32,
+ *     gate[b][h][t] = sigmoid(a) (sigmoid(b) head_const[h] - 1) + 2,
+ *     a = sum_{o<4} y[o], b = sum_{4<=o<8} y[o], y = lin_w x[b T + t][h head_dim ..] + lin_b
+ * with lin_w (8, head_dim) f32 and lin_b (8) f32 shared by all heads (HuggingFace's gru_rel_pos_linear / gru_rel_pos_const).
+ * f32 throughout in a fixed summation order: the same bits on every run.  head_dim 64 / 96 (else MMF_E_UNSUPPORTED); a null
+ * operand or a non-positive size: MMF_E_SHAPE; x / lin_w not 16-byte aligned, ldx < H head_dim or not a multiple of 8, lin_b /
+ * head_const / gate not 4-byte aligned: MMF_E_ALIGN.  Nothing is launched on an error.
+ *
+ * mmf_attn_fwd_relbias: mmf_attn_fwd_grouped for ONE self-attention problem (Tq == Tk = T, else MMF_E_SHAPE) with
+ *     score[b][h][i][j] = scale q_i . k_j + gate[b][h][i] * table[h][j - i + T - 1]
+ * gate (B, H, T) f32 as mmf_wavlm_gate writes it, table (H, 2T - 1) f32.  Writes O (bf16) and LSE (f32 (B, H, T), the
+ * log-sum-exp of the biased scores).  The (T, T) bias is never formed.  mmf_attn_fwd_grouped's constraints and codes: head_dim
+ * 64 / 96 (MMF_E_UNSUPPORTED), null problem / Q / K / V / O / LSE / gate / table (MMF_E_SHAPE), Q / K / V / O 16-byte aligned
+ * with row strides >= H head_dim and multiples of 8, LSE / gate / table 4-byte aligned (MMF_E_ALIGN); nothing is launched on
+ * an error. */
+int mmf_wavlm_gate(const void* x_bf16, int ldx, const float* lin_w, const float* lin_b, const float* head_const, float* gate,
+                   int n, int T, int H, int head_dim, void* stream);
+int mmf_attn_fwd_relbias(const mmf_attn_problem* problem, int head_dim, float scale, const float* gate, const float* table,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

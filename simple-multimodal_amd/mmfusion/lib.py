@@ -54,6 +54,7 @@ SYMBOLS = (
     "mmf_bias_gelu_drop_bwd_bf16", "mmf_w2v_mask_spans", "mmf_w2v_mask_drop", "mmf_w2v_mask_embed_grad",
     "mmf_attn_bwd_grouped_uniform_available", "mmf_attn_bwd_grouped_uniform_workspace_bytes", "mmf_attn_bwd_grouped_uniform",
     "mmf_attn_bwd_grouped_pooled",
+    "mmf_wavlm_gate", "mmf_attn_fwd_relbias",
 )
 
 
@@ -306,6 +307,8 @@ def load() -> C.CDLL:
     lib.mmf_video_prepare_patches.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mmf_audio_resample.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, i64, i32, i32, i32, vp]
     lib.mmf_audio_augment.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, i32, i64, vp]
+    lib.mmf_wavlm_gate.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.mmf_attn_fwd_relbias.argtypes = [C.POINTER(AttnProblem), i32, f32, vp, vp, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -467,6 +470,32 @@ def attn_fwd_grouped_keyed(problems: Sequence[AttnProblem], head_dim: int, scale
     """``attn_fwd_grouped`` with dropout of the probabilities, ``drop`` = (p, state, site, stream_base): the stream id of (problem, b,
     h) is problem * 4096 + stream_base + b H + h (``mmf_attn_fwd_grouped_keyed``); lse stays the undropped one"""
     _attn_call("attn_fwd_kernel", 4.0, problems, head_dim, "mmf_attn_fwd_grouped_keyed", scale, *_drop_args("attn_fwd_grouped_keyed", drop))
+
+
+def wavlm_gate(x, lin_w, lin_b, head_const, gate, n: int, T: int, H: int, head_dim: int) -> None:
+    """WavLM's gate of the relative position bias (``mmf_wavlm_gate``): x (n T, H head_dim) bf16 rows, the layer's input ->
+    gate (n, H, T) f32; lin_w (8, head_dim), lin_b (8), head_const (H) f32"""
+    import torch
+    if (x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1 or x.shape[0] != n * T or x.shape[1] != H * head_dim
+            or lin_w.numel() != 8 * head_dim or lin_b.numel() != 8 or head_const.numel() != H or gate.numel() < n * H * T
+            or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (lin_w, lin_b, head_const, gate))):
+        raise ValueError("wavlm_gate: operand sizes do not match n, T, H, head_dim")
+    with _Timed("wavlm_gate_kernel", 16.0 * n * T * H * head_dim, [(n * T, H * head_dim)]):
+        check(load().mmf_wavlm_gate(x.data_ptr(), x.stride(0), lin_w.data_ptr(), lin_b.data_ptr(), head_const.data_ptr(),
+                                    gate.data_ptr(), n, T, H, head_dim, stream_ptr()))
+
+
+def attn_fwd_relbias(problem: AttnProblem, head_dim: int, scale: float, gate, table) -> None:
+    """the fused self-attention forward with WavLM's gated relative position bias (``mmf_attn_fwd_relbias``): score = scale q . k +
+    gate[b][h][i] table[h][j - i + T - 1]; gate (B, H, T) f32, table (H, 2T - 1) f32, both contiguous on the GPU"""
+    import torch
+    T = problem.Tq
+    if (gate.dtype != torch.float32 or table.dtype != torch.float32 or not gate.is_contiguous() or not table.is_contiguous()
+            or gate.numel() < problem.B * problem.H * T or table.numel() != problem.H * (2 * T - 1)):
+        raise ValueError("attn_fwd_relbias: gate must hold (B, H, T) and table (H, 2T - 1) contiguous f32")
+    flops = 4.0 * problem.B * problem.H * T * T * head_dim if PROFILE is not None else 0.0
+    with _Timed(f"attn_fwd_relbias_kernel<{head_dim}>", flops, [(T, T)] if PROFILE is not None else None):
+        check(load().mmf_attn_fwd_relbias(C.byref(problem), head_dim, scale, gate.data_ptr(), table.data_ptr(), stream_ptr()))
 
 
 def attn_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:

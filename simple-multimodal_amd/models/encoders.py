@@ -28,6 +28,10 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     ``config.audio_backbone_regularisation`` (dynamic attribute; default 0: off) switches HuggingFace's training-mode regularisers
     on: ``True`` for wav2vec2-base-960h's dropouts, LayerDrop and SpecAugment time mask, which is what the reference trains under, or
     a dict of ``NativeWav2Vec2.set_regularisation``'s names; they act in ``train()`` while the backbone has something to train;
+  * ``config.audio_backbone = "native-wavlm"`` builds ``mmfusion.wavlm.NativeWavLM`` the same way (sizes and
+    ``audio_backbone_kwargs`` as for ``"native"``): WavLM-base / base-plus, whose attention adds a gated relative position bias, on
+    a fused HIP kernel.  A frozen forward: ``audio_backbone_trainable_layers`` > 0 or ``audio_backbone_regularisation`` on raise
+    that class's refusal at construction;
   * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
     same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
     on the prompt route, from input embeddings.  On that route, with grad mode on and ``prompt_embeddings.requires_grad``, the
@@ -64,6 +68,7 @@ from mmfusion.deberta import NativeDeberta
 from mmfusion.ops import AttnSpec, W
 from mmfusion.vit import NativeViT
 from mmfusion.wav2vec2 import NativeWav2Vec2
+from mmfusion.wavlm import NativeWavLM
 from .fusion_layers import _FusionBase, _MHAParams, _as_rows, _p, _wb
 
 
@@ -92,6 +97,10 @@ _NATIVE = {
     "audio": (NativeWav2Vec2, lambda c: dict(hidden_size=c.audio_hidden_size)),
     "video": (NativeViT, lambda c: dict(hidden_size=c.video_hidden_size, image_size=_square(c.video_frame_size))),
 }
+# (kind, ``config.<kind>_backbone``) -> the same pair for a kind's further native models, handled as "native" is
+_NATIVE_OTHER = {
+    ("audio", "native-wavlm"): (NativeWavLM, lambda c: dict(hidden_size=c.audio_hidden_size)),
+}
 
 
 def _backbone(config, kind: str, given: Optional[nn.Module]):
@@ -99,9 +108,10 @@ def _backbone(config, kind: str, given: Optional[nn.Module]):
     the config switch and is never ``native``; then ``config.<kind>_backbone == "native"``; else the reference's ``from_pretrained``."""
     if _feature_mode(config):
         return None, getattr(config, kind + "_hidden_size"), False
-    native = given is None and getattr(config, kind + "_backbone", None) == "native"
+    choice = getattr(config, kind + "_backbone", None)
+    native = given is None and (choice == "native" or (kind, choice) in _NATIVE_OTHER)
     if native:
-        cls, sizes = _NATIVE[kind]
+        cls, sizes = _NATIVE[kind] if choice == "native" else _NATIVE_OTHER[(kind, choice)]
         given = cls(**{**sizes(config), **(getattr(config, kind + "_backbone_kwargs", None) or {})})
     elif given is None:
         given = _load_backbone(kind, getattr(config, kind + "_model_name"))
