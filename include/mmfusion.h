@@ -1099,6 +1099,33 @@ int mmf_wavlm_gate(const void* x_bf16, int ldx, const float* lin_w, const float*
 int mmf_attn_fwd_relbias(const mmf_attn_problem* problem, int head_dim, float scale, const float* gate, const float* table,
                          void* stream);
 
+/* ---- The BERT family: embedding row, packed key mask, key-masked attention forward (csrc/bert.hip) ---------------------------
+ * mmf_bert_embed: out (rows, d) bf16 = LayerNorm((word[ids[r]] | embeds[r]) + type[token_type_ids[r]] + pos[p(r)]), rows =
+ * n * T tokens of n items; the rows, gamma and beta are f32, the sum and the LayerNorm are carried in f64 and rounded once.  Exactly one of ids (int64) / embeds (f32 (rows, d)); token_type_ids (int64) may be NULL: row 0.
+ * position_rule 0 (BERT): p = t, the token's place in its item.  1 (RoBERTa): on the ids route p = pad + #{ids != pad among the
+ * item's tokens 0 .. t} where ids[r] != pad, else pad (HuggingFace's create_position_ids_from_input_ids, counted on the device);
+ * on the embeds route p = pad + 1 + t.  Ids, type ids and positions are clamped into their tables (vocab, ntype, npos rows): no
+ * input reads outside a table.  d a multiple of 4, at most 1024, rows below 2^31 (MMF_E_UNSUPPORTED); a null operand, both or
+ * neither of ids / embeds, rows not a multiple of T, an unknown rule: MMF_E_SHAPE; tables / embeds / gamma / beta / out 16-byte
+ * aligned, ids / type ids 8-byte aligned (MMF_E_ALIGN).
+ *
+ * mmf_mask_pack: an (n, T) mask (mask_kind 0: none, mask NULL; 1: f32; 2: u8; an element is valid when non-zero) -> packed, n rows
+ * of mmf_mask_pack_words(T) = 2 + 2 ceil(T / 64) uint32: [0] one past the last valid key (0: none), [1] the count of valid keys,
+ * [2 + w] bit k set = key 32 w + k is valid (keys past T: 0).  One launch, nothing on the host.  packed 8-byte aligned.
+ *
+ * mmf_attn_fwd_keymask: mmf_attn_fwd_grouped for ONE self-attention problem (Tq == Tk = T, else MMF_E_SHAPE) whose keys are
+ * masked per item by packed_mask (B rows as mmf_mask_pack writes them): a masked key has probability exactly 0, every query row
+ * is computed, an item without a valid key attends uniformly over all T keys (O = the mean of its value rows, LSE = ln T).  Blocks
+ * of 32 masked keys are skipped and tiles past an item's last valid key are not read.  Writes O (bf16) and LSE (f32 (B, H, T), over
+ * the valid keys).  No atomics: the same bits on every run.  mmf_attn_fwd_relbias's constraints and codes, with packed_mask 8-byte
+ * aligned; nothing is launched on an error. */
+int mmf_bert_embed(const int64_t* ids, const float* embeds, const int64_t* token_type_ids, const float* word, const float* pos,
+                   const float* type, const float* gamma, const float* beta, float eps, int position_rule, int64_t pad,
+                   void* out_bf16, int64_t rows, int T, int d, int vocab, int npos, int ntype, void* stream);
+int mmf_mask_pack_words(int T);
+int mmf_mask_pack(const void* mask, int mask_kind, uint32_t* packed, int n, int T, void* stream);
+int mmf_attn_fwd_keymask(const mmf_attn_problem* problem, int head_dim, float scale, const uint32_t* packed_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

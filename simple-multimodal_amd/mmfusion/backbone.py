@@ -1,5 +1,5 @@
 """What the frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2`` and its subclass
-``mmfusion.wavlm.NativeWavLM``, ``mmfusion.deberta.NativeDeberta``) share: the table of frozen parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, what is derived from
+``mmfusion.wavlm.NativeWavLM``, ``mmfusion.deberta.NativeDeberta``, ``mmfusion.bert.NativeBert`` / ``NativeRoberta``) share: the table of frozen parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, what is derived from
 the weights once per weight version, and the launches of a transformer layer.
 
 A layer is two blocks on ``rows = n * T`` tokens of a chunk of ``n`` items (bf16 residual stream like MulT's).  Where the

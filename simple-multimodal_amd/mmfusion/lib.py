@@ -55,6 +55,7 @@ SYMBOLS = (
     "mmf_attn_bwd_grouped_uniform_available", "mmf_attn_bwd_grouped_uniform_workspace_bytes", "mmf_attn_bwd_grouped_uniform",
     "mmf_attn_bwd_grouped_pooled",
     "mmf_wavlm_gate", "mmf_attn_fwd_relbias",
+    "mmf_bert_embed", "mmf_mask_pack_words", "mmf_mask_pack", "mmf_attn_fwd_keymask",
 )
 
 
@@ -309,6 +310,10 @@ def load() -> C.CDLL:
     lib.mmf_audio_augment.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, i32, i64, vp]
     lib.mmf_wavlm_gate.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.mmf_attn_fwd_relbias.argtypes = [C.POINTER(AttnProblem), i32, f32, vp, vp, vp]
+    lib.mmf_bert_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, i64, vp, i64, i32, i32, i32, i32, i32, vp]
+    lib.mmf_mask_pack_words.argtypes = [i32]
+    lib.mmf_mask_pack.argtypes = [vp, i32, vp, i32, i32, vp]
+    lib.mmf_attn_fwd_keymask.argtypes = [C.POINTER(AttnProblem), i32, f32, vp, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -496,6 +501,88 @@ def attn_fwd_relbias(problem: AttnProblem, head_dim: int, scale: float, gate, ta
     flops = 4.0 * problem.B * problem.H * T * T * head_dim if PROFILE is not None else 0.0
     with _Timed(f"attn_fwd_relbias_kernel<{head_dim}>", flops, [(T, T)] if PROFILE is not None else None):
         check(load().mmf_attn_fwd_relbias(C.byref(problem), head_dim, scale, gate.data_ptr(), table.data_ptr(), stream_ptr()))
+
+
+# ---- the BERT family's kernels (csrc/bert.hip) ---------------------------------------------------------------------
+BERT_POSITIONS = {"bert": 0, "roberta": 1}            # mmf_bert_embed's position_rule
+
+
+def mask_pack_words(T: int) -> int:
+    """uint32 words of one item's row of ``mask_pack``'s output (``mmf_mask_pack_words``): one past the last valid key, the count
+    of valid keys, then one bit per key in whole 64-key tiles"""
+    return 2 + 2 * ((T + 63) // 64)
+
+
+def mask_pack(mask, packed, n: int, T: int) -> None:
+    """``mask`` (n, T) contiguous float32 / uint8 / bool on the GPU, or None for all ones -> ``packed``: int32, at least
+    n * ``mask_pack_words(T)`` elements, as ``attn_fwd_keymask`` reads it (``mmf_mask_pack``; one launch, no host step)"""
+    import torch
+    if not packed.is_cuda or (mask is not None and not mask.is_cuda):
+        raise RuntimeError("mask_pack runs on the GPU only (no CPU fallback)")
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < n * mask_pack_words(T) or n < 1 or T < 1:
+        raise ValueError("mask_pack: packed must be contiguous int32 with n * mask_pack_words(T) elements")
+    mp, kind = None, 0
+    if mask is not None:
+        if mask.dtype not in (torch.float32, torch.uint8, torch.bool) or not mask.is_contiguous() or mask.numel() != n * T:
+            raise ValueError("mask_pack: the mask must be a contiguous float32 / uint8 / bool tensor of n * T elements")
+        mp, kind = mask.data_ptr(), 1 if mask.dtype == torch.float32 else 2
+    with _Timed("mask_pack_kernel", 0.0, [(n, T)]):
+        check(load().mmf_mask_pack(mp, kind, packed.data_ptr(), n, T, stream_ptr()))
+
+
+def attn_fwd_keymask(problem: AttnProblem, head_dim: int, scale: float, packed) -> None:
+    """the fused self-attention forward with a key padding mask (``mmf_attn_fwd_keymask``): ``packed`` holds the B items' rows as
+    ``mask_pack`` writes them"""
+    import torch
+    T = problem.Tq
+    if not packed.is_cuda:
+        raise RuntimeError("attn_fwd_keymask runs on the GPU only (no CPU fallback)")
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < problem.B * mask_pack_words(T):
+        raise ValueError("attn_fwd_keymask: packed must be contiguous int32 with B * mask_pack_words(T) elements")
+    flops = 4.0 * problem.B * problem.H * T * T * head_dim if PROFILE is not None else 0.0
+    with _Timed(f"attn_fwd_keymask_kernel<{head_dim}>", flops, [(T, T)] if PROFILE is not None else None):
+        check(load().mmf_attn_fwd_keymask(C.byref(problem), head_dim, scale, packed.data_ptr(), stream_ptr()))
+
+
+def bert_embed(out, word, pos, type_table, gamma, beta, eps: float, T: int, rule: str, pad: int = 0, ids=None, embeds=None,
+               token_type_ids=None) -> None:
+    """out (rows, d) bf16 = LayerNorm((word[ids] | embeds) + type_table[token_type_ids] + pos[p]), rows = n * T (``mmf_bert_embed``).
+    ``rule``: "bert" (p = the token's place) or "roberta" (from the ids and ``pad``; on the embeds route pad + 1 + place); ids /
+    token_type_ids int64 (rows,), the latter optional (row 0); the tables f32 (vocab | positions | types, d)"""
+    import torch
+    _w2v_bf16(out)
+    _w2v_f32(pos, type_table, gamma, beta)
+    if (ids is None) == (embeds is None):
+        raise ValueError("bert_embed: exactly one of ids / embeds")
+    if rule not in BERT_POSITIONS:
+        raise ValueError(f"bert_embed: rule {rule!r} is not one of {sorted(BERT_POSITIONS)}")
+    if out.dim() != 2 or not out.is_contiguous():
+        raise ValueError("bert_embed: out must be a contiguous (rows, d) matrix")
+    rows, d = out.shape
+    if T < 1 or rows % T or any(t.dim() != 2 or t.shape[1] != d for t in (pos, type_table)) or gamma.numel() != d or beta.numel() != d:
+        raise ValueError("bert_embed: rows must be a multiple of T, the tables (.., d) and gamma / beta one value per column")
+    for name, t in (("ids", ids), ("token_type_ids", token_type_ids)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("bert_embed runs on the GPU only (no CPU fallback)")
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != rows:
+            raise ValueError(f"bert_embed: {name} must be contiguous int64, one per output row")
+    vocab = 0
+    if ids is not None:
+        _w2v_f32(word)
+        if word.dim() != 2 or word.shape[1] != d:
+            raise ValueError("bert_embed: word must be (vocab, d)")
+        vocab = word.shape[0]
+    else:
+        _w2v_f32(embeds)
+        if embeds.numel() != rows * d:
+            raise ValueError("bert_embed: embeds must hold (rows, d) values")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with _Timed("bert_embed_kernel", 0.0, [(rows, d)]):
+        check(load().mmf_bert_embed(ptr(ids), ptr(embeds), ptr(token_type_ids), ptr(word) if ids is not None else None, pos.data_ptr(),
+                                    type_table.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, BERT_POSITIONS[rule], int(pad),
+                                    out.data_ptr(), rows, T, d, vocab, pos.shape[0], type_table.shape[0], stream_ptr()))
 
 
 def attn_delta_keyed(problems: Sequence[AttnProblem], head_dim: int, scale: float, drop) -> None:

@@ -43,6 +43,11 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     ``config.text_backbone_dropout`` (dynamic attribute; default 0: off) switches the backbone's training-mode dropout on:
     ``True`` for HuggingFace's 0.1 / 0.1, which is what the reference trains under, or a pair (hidden, attention); it acts while
     the encoder is in ``train()`` and the backbone has something to train, never under ``eval()``;
+  * ``config.text_backbone = "native-bert"`` / ``"native-roberta"`` builds ``mmfusion.bert.NativeBert`` / ``NativeRoberta`` the same
+    way (sizes and ``text_backbone_kwargs`` as for ``"native"``): the BERT family with absolute positions, whose attention honours
+    the key padding mask on a fused HIP kernel; ``model_type`` contains "bert", so the CLS row is pooled as in the reference (:87).
+    A frozen forward: ``text_backbone_trainable_layers`` > 0, ``text_backbone_dropout`` on, or prompt embeddings that require a
+    gradient in grad mode raise that class's refusal;
   * ``config.feature_inputs = True`` (dynamic attribute) builds no backbone at all: the ``forward``
     inputs are then precomputed backbone features ``(B, T, hidden)`` — the synthetic-feature route
     of BASELINE.json's configs.
@@ -64,6 +69,7 @@ import torch
 import torch.nn as nn
 
 from mmfusion import ops, prep
+from mmfusion.bert import NativeBert, NativeRoberta
 from mmfusion.deberta import NativeDeberta
 from mmfusion.ops import AttnSpec, W
 from mmfusion.vit import NativeViT
@@ -100,6 +106,8 @@ _NATIVE = {
 # (kind, ``config.<kind>_backbone``) -> the same pair for a kind's further native models, handled as "native" is
 _NATIVE_OTHER = {
     ("audio", "native-wavlm"): (NativeWavLM, lambda c: dict(hidden_size=c.audio_hidden_size)),
+    ("text", "native-bert"): (NativeBert, lambda c: dict(hidden_size=c.text_hidden_size)),
+    ("text", "native-roberta"): (NativeRoberta, lambda c: dict(hidden_size=c.text_hidden_size)),
 }
 
 
