@@ -1126,6 +1126,49 @@ int mmf_mask_pack_words(int T);
 int mmf_mask_pack(const void* mask, int mask_kind, uint32_t* packed, int n, int T, void* stream);
 int mmf_attn_fwd_keymask(const mmf_attn_problem* problem, int head_dim, float scale, const uint32_t* packed_mask, void* stream);
 
+/* ---- Whisper's front end: log-mel features and the padded convolution stem (csrc/whisper.hip) ---------------------------------
+ * mmf_whisper_logmel: wave (N, L) f32 at 16 kHz, row stride ld -> HuggingFace WhisperFeatureExtractor's input_features
+ * (_np_extract_fbank_features): the clip zero-padded to n_samples, reflect-padded by 200 on both sides, frames of 400 at hop 160
+ * times window (f32 [400], the periodic Hann), |DFT|^2 over 201 bins, times mel_fb (201, n_mels) f32, log10(max(., 1e-10)), the
+ * last frame dropped (Tm = n_samples / 160 frames), max(x, the clip's own maximum - 8), (x + 4) / 4.  dft is the host's table,
+ * f32 (400, 2 MMF_WHISPER_DFT_COLS): dft[k][b] = cos(2 pi b k / 400) and dft[k][MMF_WHISPER_DFT_COLS + b] = sin(2 pi b k / 400) for
+ * b < 201, zero columns behind; the product runs on the f32-input MFMA (an f32 fmaf chain in k order) and no sine or cosine is
+ * evaluated on the device.  The mel product walks each filter's run of non-zero bins.
+ *   features  (N, n_mels, Tm) f32, HuggingFace's layout; may be NULL
+ *   window    (N, Tm, Kw) bf16, the first convolution's A operand (kernel 3, padding 1): window[n][t][j n_mels + c] =
+ *             bf16(features[n][c][t + j - 1]), zero outside 0 .. Tm - 1 and in columns 3 n_mels .. Kw - 1; may be NULL (not both)
+ *   scratch   mmf_whisper_logmel_scratch_bytes(N, n_samples, n_mels) bytes: the raw log spectrum (N, Tm, n_mels) f32 and one maximum
+ *             per pass-1 workgroup (the per-clip maximum is the pass boundary)
+ * Two launches, no atomics, no host synchronisation: the same bits on every run, graph-capturable.  A null operand, N < 1, L
+ * outside 1 .. n_samples, n_samples not a positive multiple of 320, ld < L, Kw < 3 n_mels or not a multiple of 8, a scratch that
+ * is too small: MMF_E_SHAPE; n_mels outside {80, 128}, N > 65535: MMF_E_UNSUPPORTED; f32 operands not 4-byte aligned, window /
+ * scratch not 16-byte aligned: MMF_E_ALIGN.  Nothing is launched on an error.
+ *
+ * mmf_whisper_feature_window: features (N, n_mels, Tm) f32 as above -> window, with mmf_whisper_logmel's bits for the same features
+ * and its codes.
+ *
+ * mmf_whisper_gelu_window: x (N, T_in, C) bf16, a raw convolution output, bias f32 [C] -> out (N, T_out, k C) bf16,
+ * out[n][t][j C + c] = bf16(gelu(x[n][s t + j - pad][c] + bias[c])) (exact GELU, f32, one rounding), zero where the frame is outside
+ * 0 .. T_in - 1; T_out = (T_in + 2 pad - k) / s + 1.  mmf_w2v_gelu_window with a bias and zero padding: the A operand of the next
+ * convolution as ONE NT GEMM against its weight repacked to (C_out, k C), column (j, c).  A null operand, a non-positive size,
+ * pad < 0, pad >= k, T_in + 2 pad < k: MMF_E_SHAPE; C % 8 != 0, N > 65535, out == x: MMF_E_UNSUPPORTED; x / bias / out not 16-byte
+ * aligned: MMF_E_ALIGN.  Nothing is launched on an error.
+ *
+ * mmf_whisper_stem_out: x (rows, d) bf16, the second convolution's raw output for rows = n T frames, bias f32 [d], pos f32 (T, d) ->
+ * out[r][c] = bf16(gelu(x[r][c] + bias[c]) + pos[r % T][c]), the residual stream's first value; out may be x.  A null operand, a
+ * non-positive size, rows not a multiple of T: MMF_E_SHAPE; d % 8 != 0: MMF_E_UNSUPPORTED; a pointer not 16-byte aligned:
+ * MMF_E_ALIGN.  Nothing is launched on an error. */
+#define MMF_WHISPER_DFT_COLS 224
+size_t mmf_whisper_logmel_scratch_bytes(int N, int n_samples, int n_mels);
+int mmf_whisper_logmel(const float* wave, int64_t ld, const float* window, const float* dft, const float* mel_fb, float* features,
+                       void* window_bf16, void* scratch, size_t scratch_bytes, int N, int L, int n_samples, int n_mels, int Kw,
+                       void* stream);
+int mmf_whisper_feature_window(const float* features, void* window_bf16, int N, int n_mels, int Tm, int Kw, void* stream);
+int mmf_whisper_gelu_window(const void* x_bf16, const float* bias, void* out_bf16, int N, int T_in, int C, int k, int s, int pad,
+                            void* stream);
+int mmf_whisper_stem_out(const void* x_bf16, const float* bias, const float* pos, void* out_bf16, int64_t rows, int T, int d,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 """What the frozen backbones (``mmfusion.vit.NativeViT``, ``mmfusion.wav2vec2.NativeWav2Vec2`` and its subclass
-``mmfusion.wavlm.NativeWavLM``, ``mmfusion.deberta.NativeDeberta``, ``mmfusion.bert.NativeBert`` / ``NativeRoberta``) share: the table of frozen parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, what is derived from
+``mmfusion.wavlm.NativeWavLM``, ``mmfusion.deberta.NativeDeberta``, ``mmfusion.bert.NativeBert`` / ``NativeRoberta``,
+``mmfusion.whisper.NativeWhisperEncoder``) share: the table of frozen parameters behind HuggingFace's ``state_dict`` surface, the chunk workspace, what is derived from
 the weights once per weight version, and the launches of a transformer layer.
 
 A layer is two blocks on ``rows = n * T`` tokens of a chunk of ``n`` items (bf16 residual stream like MulT's).  Where the
@@ -86,6 +87,7 @@ from .lib import EPI_ACCUM, EPI_ADD_AUX, EPI_BIAS, EPI_COLSUM_A, GEMM_NN, GEMM_N
 
 BF16 = torch.bfloat16
 LN_WIDTHS = (256, 512, 768, 1024)          # the lane forms of layernorm.hip
+LN_MAX_WIDTH = 2048                        # its chunk form: every multiple of 8 up to this (forward; a frozen model needs no more)
 WsTable = List[Tuple[str, int, torch.dtype]]
 Attend = Callable[[torch.Tensor, torch.Tensor], None]          # (qkv rows, att rows): launches one chunk's attention
 AttnBwd = Callable[[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor], None]     # (qkv, att, datt, dqkv rows): its backward
@@ -141,19 +143,22 @@ class BackboneOutput:
 
 class FrozenBackbone(nn.Module):
     """Base of the native backbones.  A subclass declares its limits to ``__init__`` (``head_dims``: the head widths its
-    attention has a form for; ``ln_widths``: further named sizes that go through the LayerNorm kernel), sets ``self.config``
+    attention has a form for; ``ln_widths``: further named sizes that go through the LayerNorm kernel; ``ln_any_width``: the model
+    runs the LayerNorm forward only, whose chunk form takes every multiple of 8 up to 2048 where no lane form does), sets ``self.config``
     (``hidden_size``, ``num_attention_heads``, ``intermediate_size``, ``layer_norm_eps``), registers its parameters with ``_add``
     / ``_add_layer`` in HuggingFace's order, and defines ``_ws_table(size)``."""
 
     def __init__(self, hidden_size: int, num_attention_heads: int, chunk: int, head_dims: Sequence[int] = (64, 96),
-                 ln_widths: Optional[Dict[str, int]] = None):
+                 ln_widths: Optional[Dict[str, int]] = None, ln_any_width: bool = False):
         super().__init__()
         d, H, who = hidden_size, num_attention_heads, type(self).__name__
         if H <= 0 or d % H or d // H not in head_dims:
             raise ValueError(f"{who}: hidden_size {d} / num_attention_heads {H} must give a head_dim of "
                              f"{' or '.join(str(v) for v in head_dims)} (its attention kernel's forms)")
         for name, width in {"hidden_size": d, **(ln_widths or {})}.items():
-            if width not in LN_WIDTHS:
+            if ln_any_width and (width <= 0 or width % 8 or width > LN_MAX_WIDTH):
+                raise ValueError(f"{who}: {name} {width} is not a multiple of 8 up to {LN_MAX_WIDTH} (the LayerNorm forward's chunk form)")
+            if not ln_any_width and width not in LN_WIDTHS:
                 raise ValueError(f"{who}: {name} {width} is not one of the LayerNorm kernel's widths {LN_WIDTHS}")
         self.chunk = int(chunk)
         self.head_dim = d // H
@@ -639,7 +644,7 @@ class FrozenBackbone(nn.Module):
 
     def _pre_ln_layer(self, i: int, ws, n: int, T: int) -> None:
         """x = y + ffn(LayerNorm(y)), y = x + attention(LayerNorm(x)) on the ``n * T`` rows of ``x`` (ViT; Wav2Vec2's layer-norm
-        family)"""
+        family; Whisper's encoder)"""
         rows, d = n * T, self.config.hidden_size
         x, ln = self._rows(ws, "x", rows, d), self._rows(ws, "ln", rows, d)
         self._ln(ws, x, ln, f"l{i}_ln1_w", f"l{i}_ln1_b")

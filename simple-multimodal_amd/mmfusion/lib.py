@@ -56,6 +56,7 @@ SYMBOLS = (
     "mmf_attn_bwd_grouped_pooled",
     "mmf_wavlm_gate", "mmf_attn_fwd_relbias",
     "mmf_bert_embed", "mmf_mask_pack_words", "mmf_mask_pack", "mmf_attn_fwd_keymask",
+    "mmf_whisper_logmel_scratch_bytes", "mmf_whisper_logmel", "mmf_whisper_feature_window", "mmf_whisper_gelu_window", "mmf_whisper_stem_out",
 )
 
 
@@ -314,6 +315,12 @@ def load() -> C.CDLL:
     lib.mmf_mask_pack_words.argtypes = [i32]
     lib.mmf_mask_pack.argtypes = [vp, i32, vp, i32, i32, vp]
     lib.mmf_attn_fwd_keymask.argtypes = [C.POINTER(AttnProblem), i32, f32, vp, vp]
+    lib.mmf_whisper_logmel_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.mmf_whisper_logmel_scratch_bytes.restype = C.c_size_t
+    lib.mmf_whisper_logmel.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, vp]
+    lib.mmf_whisper_feature_window.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    lib.mmf_whisper_gelu_window.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.mmf_whisper_stem_out.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp]
     S2 = C.c_int64 * 2
     lib.mmf_gemm_f32_grouped.argtypes = [C.POINTER(GemmProblem), i32, i32, i32, f32, vp]
     lib.mmf_gemm_f32_batched.argtypes = [C.POINTER(GemmProblem), i32, i32, f32, i32, i32, S2, S2, S2, vp]
@@ -1339,3 +1346,86 @@ def audio_augment(x, out, noise_on, stretch_len, rng_state_ptr: Optional[int], s
     sp = _prep_arg(stretch_len, "audio_augment: stretch_len", torch.int32, B, x.device)
     with _Timed("audio_augment_kernel", 0.0, [(B, L * 8)]):
         check(load().mmf_audio_augment(x.data_ptr(), out.data_ptr(), np_, sp, rng_state_ptr, site, B, L, stream_ptr()))
+
+
+# ---- Whisper's front end (csrc/whisper.hip) -------------------------------------------------------------------------------
+WHISPER_DFT_COLS = 224           # MMF_WHISPER_DFT_COLS of include/mmfusion.h: the bins' columns of each half of the DFT table
+
+
+def whisper_logmel_scratch_bytes(N: int, n_samples: int, n_mels: int) -> int:
+    return int(load().mmf_whisper_logmel_scratch_bytes(N, n_samples, n_mels))
+
+
+def whisper_logmel(wave, window, dft, mel_fb, scratch, n_samples: int, features=None, out_window=None) -> None:
+    """wave (N, L) f32 (rows may be strided) -> ``features`` (N, n_mels, Tm) f32 and / or ``out_window`` (N, Tm, Kw) bf16
+    (``mmf_whisper_logmel``); ``window`` [400], ``dft`` (400, 2 WHISPER_DFT_COLS) and ``mel_fb`` (201, n_mels) are the host's f32
+    tables, ``scratch`` any contiguous buffer of ``whisper_logmel_scratch_bytes`` bytes"""
+    import torch
+    for t in (wave, window, dft, mel_fb, scratch, features, out_window):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("whisper_logmel runs on the GPU only (no CPU fallback)")
+    if wave.dim() != 2 or wave.dtype != torch.float32 or wave.stride(1) != 1:
+        raise ValueError(f"whisper_logmel: wave must be (N, L) f32 with contiguous rows, got {tuple(wave.shape)} {wave.dtype}")
+    N, L = wave.shape
+    Tm = n_samples // 160
+    if mel_fb.dim() != 2 or mel_fb.shape[0] != 201 or window.numel() != 400 or dft.numel() != 400 * 2 * WHISPER_DFT_COLS or any(
+            t.dtype != torch.float32 or not t.is_contiguous() for t in (window, dft, mel_fb)):
+        raise ValueError("whisper_logmel: window [400], dft (400, 448) and mel_fb (201, n_mels) must be contiguous f32")
+    n_mels, Kw = mel_fb.shape[1], 0
+    if features is not None and (features.dtype != torch.float32 or tuple(features.shape) != (N, n_mels, Tm) or not features.is_contiguous()):
+        raise ValueError(f"whisper_logmel: features must be contiguous f32 {(N, n_mels, Tm)}")
+    if out_window is not None:
+        if out_window.dtype != torch.bfloat16 or out_window.dim() != 3 or tuple(out_window.shape[:2]) != (N, Tm) or not out_window.is_contiguous():
+            raise ValueError(f"whisper_logmel: out_window must be contiguous bf16 ({N}, {Tm}, Kw)")
+        Kw = out_window.shape[2]
+    if not scratch.is_contiguous():
+        raise ValueError("whisper_logmel: scratch must be contiguous")
+    with _Timed("whisper_logmel_kernels", 2.0 * N * Tm * 400 * 402, [(N, L)]):
+        check(load().mmf_whisper_logmel(wave.data_ptr(), wave.stride(0) if N > 1 else L, window.data_ptr(), dft.data_ptr(), mel_fb.data_ptr(),
+                                        None if features is None else features.data_ptr(),
+                                        None if out_window is None else out_window.data_ptr(), scratch.data_ptr(),
+                                        scratch.numel() * scratch.element_size(), N, L, n_samples, n_mels, Kw, stream_ptr()))
+
+
+def whisper_feature_window(features, out_window) -> None:
+    """features (N, n_mels, Tm) f32 -> out_window (N, Tm, Kw) bf16, ``whisper_logmel``'s window form of the same features"""
+    import torch
+    if not features.is_cuda or not out_window.is_cuda:
+        raise RuntimeError("whisper_feature_window runs on the GPU only (no CPU fallback)")
+    if features.dim() != 3 or features.dtype != torch.float32 or not features.is_contiguous():
+        raise ValueError("whisper_feature_window: features must be contiguous f32 (N, n_mels, Tm)")
+    N, n_mels, Tm = features.shape
+    if out_window.dtype != torch.bfloat16 or out_window.dim() != 3 or tuple(out_window.shape[:2]) != (N, Tm) or not out_window.is_contiguous():
+        raise ValueError(f"whisper_feature_window: out_window must be contiguous bf16 ({N}, {Tm}, Kw)")
+    with _Timed("whisper_feature_window_kernel", 0.0, [(N * Tm, out_window.shape[2])]):
+        check(load().mmf_whisper_feature_window(features.data_ptr(), out_window.data_ptr(), N, n_mels, Tm, out_window.shape[2], stream_ptr()))
+
+
+def whisper_gelu_window(x, bias, out, N: int, T_in: int, C: int, k: int, s: int, pad: int) -> None:
+    """x (N, T_in, C) bf16 raw convolution output, bias f32 [C] -> out (N, T_out, k * C) bf16: bias, exact GELU and the window form
+    of a convolution with ``pad`` zero frames on both sides (``mmf_whisper_gelu_window``)"""
+    _bf16_pair("whisper_gelu_window", x, out)
+    T_out = (T_in + 2 * pad - k) // s + 1
+    if x.numel() != N * T_in * C or out.numel() != N * T_out * k * C or bias.numel() != C:
+        raise ValueError("whisper_gelu_window: operand sizes do not match N, T_in, C, k, s, pad")
+    with _Timed("whisper_gelu_window_kernel", 0.0, [(N * T_out, k * C)]):
+        check(load().mmf_whisper_gelu_window(x.data_ptr(), bias.data_ptr(), out.data_ptr(), N, T_in, C, k, s, pad, stream_ptr()))
+
+
+def whisper_stem_out(x, bias, pos, out, T: int) -> None:
+    """x (rows, d) bf16 raw convolution output of rows = n * T frames, bias f32 [d], pos f32 (T, d) -> out = bf16(gelu(x + bias) +
+    pos[t]); out may be x (``mmf_whisper_stem_out``)"""
+    _bf16_pair("whisper_stem_out", x, out)
+    rows, d = x.shape
+    if tuple(out.shape) != (rows, d) or bias.numel() != d or tuple(pos.shape) != (T, d) or not pos.is_contiguous():
+        raise ValueError("whisper_stem_out: operand sizes do not match rows, T, d")
+    with _Timed("whisper_stem_out_kernel", 0.0, [(rows, d)]):
+        check(load().mmf_whisper_stem_out(x.data_ptr(), bias.data_ptr(), pos.data_ptr(), out.data_ptr(), rows, T, d, stream_ptr()))
+
+
+def _bf16_pair(who: str, x, out) -> None:
+    import torch
+    if not x.is_cuda or not out.is_cuda:
+        raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback)")
+    if x.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or not x.is_contiguous() or not out.is_contiguous():
+        raise ValueError(f"{who}: x and out must be contiguous bf16")

@@ -32,6 +32,10 @@ layers (``config.text_backbone_trainable_layers`` / ``config.video_backbone_trai
     ``audio_backbone_kwargs`` as for ``"native"``): WavLM-base / base-plus, whose attention adds a gated relative position bias, on
     a fused HIP kernel.  A frozen forward: ``audio_backbone_trainable_layers`` > 0 or ``audio_backbone_regularisation`` on raise
     that class's refusal at construction;
+  * ``config.audio_backbone = "native-whisper"`` builds ``mmfusion.whisper.NativeWhisperEncoder`` (``d_model`` =
+    ``audio_hidden_size``, the rest from ``audio_backbone_kwargs`` in ``WhisperConfig``'s names): Whisper's encoder, which takes the
+    same 16 kHz waveform and makes its log-mel features on the device.  Widths 512 (base) and 768 (small): the temporal attention's
+    8 heads have no form for the other families' head_dim.  Frozen, as ``"native-wavlm"`` is, with the same refusals;
   * ``config.text_backbone = "native"`` (dynamic attribute, ``TextEncoder`` only) builds ``mmfusion.deberta.NativeDeberta`` the
     same way: the DeBERTa-v3 family (disentangled relative-position attention with a padding mask), from raw token ids or,
     on the prompt route, from input embeddings.  On that route, with grad mode on and ``prompt_embeddings.requires_grad``, the
@@ -75,6 +79,7 @@ from mmfusion.ops import AttnSpec, W
 from mmfusion.vit import NativeViT
 from mmfusion.wav2vec2 import NativeWav2Vec2
 from mmfusion.wavlm import NativeWavLM
+from mmfusion.whisper import NativeWhisperEncoder
 from .fusion_layers import _FusionBase, _MHAParams, _as_rows, _p, _wb
 
 
@@ -106,6 +111,7 @@ _NATIVE = {
 # (kind, ``config.<kind>_backbone``) -> the same pair for a kind's further native models, handled as "native" is
 _NATIVE_OTHER = {
     ("audio", "native-wavlm"): (NativeWavLM, lambda c: dict(hidden_size=c.audio_hidden_size)),
+    ("audio", "native-whisper"): (NativeWhisperEncoder, lambda c: dict(d_model=c.audio_hidden_size)),
     ("text", "native-bert"): (NativeBert, lambda c: dict(hidden_size=c.text_hidden_size)),
     ("text", "native-roberta"): (NativeRoberta, lambda c: dict(hidden_size=c.text_hidden_size)),
 }
