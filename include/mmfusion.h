@@ -771,8 +771,8 @@ int mmf_vit_embed_tokens_bwd(const void* dtokens_bf16, float* dcls, float* dpos,
  * N, H <= 65535; validates first and launches nothing on an error. */
 int mmf_vit_cls_attn_bwd(const void* qkv_bf16, const void* dout_bf16, void* dqkv_bf16, int N, int H, int T, int head_dim, float scale,
                          void* stream);
-/* x <- gelu(x + bias) in place on a bf16 (rows, cols) block with row stride ld: the exact form 0.5 v (1 + erf(v / sqrt 2)) in
- * f32 (HuggingFace hidden_act = "gelu"), one rounding to bf16.  bias f32 [cols] or NULL.  cols % 8 == 0, ld % 8 == 0. */
+/* x <- gelu(x + bias) in place on a bf16 (rows, cols) block with row stride ld: the exact form v Phi(v) in f32
+ * (HuggingFace hidden_act = "gelu"; Phi through erfc, so the left tail keeps its digits), one rounding to bf16.  bias f32 [cols] or NULL.  cols % 8 == 0, ld % 8 == 0. */
 int mmf_bias_gelu_bf16(void* x_bf16, const float* bias, int64_t rows, int cols, int ld, void* stream);
 /* The out-of-place form: g <- gelu(h + bias) with h kept (a backward reads it); the same kernel body, so g is bit-identical to
  * what the in-place entry leaves in x.  h and g share the row stride ld; mmf_bias_gelu_bf16's constraints. */

@@ -59,7 +59,28 @@ __device__ __forceinline__ u32x4_t pack8(const f32x4_t a, const f32x4_t b) {
 }
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }   // exact GELU
+// The exact GELU, the project's only forward: gelu(x) = x Phi(x) with Phi(x) = erfc(|x| / sqrt 2) / 2 for x < 0 and 1 - that otherwise.
+// 1 + erf(x / sqrt 2) rounds away every digit of Phi in the left tail (x = -5: 20 bf16 ulps of the result, an exact -0 from x = -5.44
+// down), and FFN pre-activations and a normalisation's output both reach it, so the kernels' outputs would not be within a bf16 ulp of
+// the exact value.  erfc(z), z >= 0, is the Chebyshev fit t exp(-z^2 + P(t)), t = 1 / (1 + z / 2) (Numerical Recipes' erfcc: a RELATIVE
+// error near 1e-7 for every z; in f32 with v_rcp and v_exp the GELU stays within 2e-5 of its value until Phi itself falls under the
+// smallest normal f32 near x = -13), a third of erfcf's instructions: the layer-norm family's two kernels are near their ALU bound beside
+// the memory one.  tests/gelu_domain.py holds every site to float64 over all finite bf16 inputs.
+__device__ __forceinline__ float gelu_erf(float x) {
+  const float z = fabsf(x) * 0.70710678118654752440f, t = __builtin_amdgcn_rcpf(fmaf(0.5f, z, 1.0f));
+  float p = 0.17087277f;
+  p = fmaf(p, t, -0.82215223f);
+  p = fmaf(p, t, 1.48851587f);
+  p = fmaf(p, t, -1.13520398f);
+  p = fmaf(p, t, 0.27886807f);
+  p = fmaf(p, t, -0.18628806f);
+  p = fmaf(p, t, 0.09678418f);
+  p = fmaf(p, t, 0.37409196f);
+  p = fmaf(p, t, 1.00002368f);
+  p = fmaf(p, t, -1.26551223f);
+  const float h = 0.5f * t * __expf(fmaf(-z, z, p));                  // Phi(-|x|)
+  return x * (x < 0.0f ? h : 1.0f - h);
+}
 // gelu'(v) = Phi(v) + v phi(v).  Phi through erfc: 1 + erf(v / sqrt 2) loses every digit of Phi in the left tail (v < -5), where
 // v phi(v) is just as small and the derivative would be f32 noise.
 __device__ __forceinline__ float gelu_erf_grad(float v) {

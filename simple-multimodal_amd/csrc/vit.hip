@@ -1,5 +1,5 @@
 // The pieces a ViT forward has and the fusion path did not (mmfusion/vit.py): patch extraction for the patch-embedding
-// GEMM, CLS / position tokens, exact (erf) GELU (and its backward, for the DeBERTa input gradient).  All are HBM-bound
+// GEMM, CLS / position tokens, exact GELU (gelu_erf of mmf_internal.h; and its backward, for the DeBERTa input gradient).  All are HBM-bound
 // streaming kernels: one 16-byte bf16 access (8 elements) per lane on the bf16 side, two 16-byte accesses on the f32 side, grid-stride loops on mmf_stream_grid's
 // grid (mmf_internal.h) per grid row.
 #include "mmf_internal.h"

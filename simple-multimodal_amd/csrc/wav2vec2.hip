@@ -19,30 +19,6 @@ namespace {
 constexpr int W2V_THREADS = 256;
 constexpr int W2V_SLOTS = MMF_W2V_STATS_SLOTS;      // frame lanes per clip in the statistics pass
 
-
-// The exact GELU through erfc, gelu(x) = x Phi(x) with Phi(x) = erfc(|x| / sqrt 2) / 2 for x < 0 and 1 - that otherwise:
-// 1 + erf(x / sqrt 2) rounds away every digit of Phi in the left tail, and a normalisation's output reaches it (x = -5: 20 bf16 ulps of
-// the result), so the kernels' outputs would not be within a bf16 ulp of the exact value.  erfc(z), z >= 0, is the Chebyshev fit
-// t exp(-z^2 + P(t)), t = 1 / (1 + z / 2) (Numerical Recipes' erfcc: a RELATIVE error near 1e-7 for every z; in f32 with v_rcp and
-// v_exp the GELU stays within 2e-5 of its value out to |x| = 12), a third of erfcf's instructions: the layer-norm family's two kernels are
-// near their ALU bound beside the memory one.  Layer 0's GroupNorm form uses it for the same reason: its pre-activations reach x = -6.
-__device__ __forceinline__ float w2v_gelu_erfc(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f, t = __builtin_amdgcn_rcpf(fmaf(0.5f, z, 1.0f));
-  float p = 0.17087277f;
-  p = fmaf(p, t, -0.82215223f);
-  p = fmaf(p, t, 1.48851587f);
-  p = fmaf(p, t, -1.13520398f);
-  p = fmaf(p, t, 0.27886807f);
-  p = fmaf(p, t, -0.18628806f);
-  p = fmaf(p, t, 0.09678418f);
-  p = fmaf(p, t, 0.37409196f);
-  p = fmaf(p, t, 1.00002368f);
-  p = fmaf(p, t, -1.26551223f);
-  const float h = 0.5f * t * __expf(fmaf(-z, z, p));                  // Phi(-|x|)
-  return x * (x < 0.0f ? h : 1.0f - h);
-}
-
-
 // ---- layer 0 -------------------------------------------------------------------------------------------
 // A thread owns 8 consecutive channels (their K0 taps stay in registers) and walks frames; the C0 / 8 threads of one frame
 // sit next to each other, so every store of a frame row is contiguous and the waveform loads are broadcasts.
@@ -146,7 +122,7 @@ void w2v_conv0_norm_gelu_kernel(const float* __restrict__ wave, const float* __r
   for (int f = blockIdx.x * nfl + fl; f <= last; f += gridDim.x * nfl) {
     cv.frame(xs + (size_t)f * s0, k0, v);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = w2v_gelu_erfc(fmaf(v[e], scale[e], shift[e]));
+    for (int e = 0; e < 8; ++e) v[e] = gelu_erf(fmaf(v[e], scale[e], shift[e]));
     const u32x4_t pk = pack8(v);
     for (int j = 0; j < k1 && j <= f; ++j) {
       const int t1 = (f - j) / s1;
@@ -210,7 +186,7 @@ __device__ __forceinline__ void w2v_ln_gelu8(float (&v)[8], const float (&gamma)
   }
   const float rstd = rsqrtf(w2v_row_sum(q, cgn, red[1]) * inv + eps);
 #pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = w2v_gelu_erfc(fmaf(v[e] * rstd, gamma[e], beta[e]));
+  for (int e = 0; e < 8; ++e) v[e] = gelu_erf(fmaf(v[e] * rstd, gamma[e], beta[e]));
 }
 
 // frame f, 8 channels as pk, to every (row t, tap j) of the window form with s t + j == f: dst[(t k + j) C] (dst: the clip's window

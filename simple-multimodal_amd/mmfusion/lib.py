@@ -732,7 +732,7 @@ def vit_cls_attn_bwd(qkv, dout, dqkv, N: int, H: int, T: int, head_dim: int, sca
 
 
 def bias_gelu(x, bias=None) -> None:
-    """x (rows, cols) bf16, row-strided allowed, in place: gelu(x + bias), exact (erf) form"""
+    """x (rows, cols) bf16, row-strided allowed, in place: gelu(x + bias), the exact form v Phi(v) with Phi through erfc"""
     if x.dim() != 2 or x.stride(1) != 1 or (bias is not None and (bias.numel() != x.shape[1] or not bias.is_contiguous())):
         raise ValueError("bias_gelu: x must be 2-D with contiguous rows and bias one value per column")
     with _Timed("bias_gelu_kernel", 0.0, [tuple(x.shape)]):

@@ -21,4 +21,5 @@ def layer_norm(x, gamma, beta, eps):
 
 
 def gelu_erf(x):
-    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+    """x Phi(x), Phi through erfc: 1 + erf keeps no digit of Phi in the left tail, in float64 from x = -8.3 down"""
+    return x * (0.5 * torch.erfc(x * (-1.0 / math.sqrt(2.0))))

@@ -12,7 +12,7 @@ included (where gelu's condition number is y^2: 25 x 2^-20 terms / |y| is still 
 fails.  Inside the set the error is capped in size, ulp + 0.51 x F32_TERMS x terms (gelu' is within 0.5 +- 0.01 there), and the set
 in count: y is spread over about terms / 4 or more, so |y| < 2^-12 terms takes about 2^-9 of the outputs; the cap is 2^-8 of them
 (at least 8 for the tiny cases).  A further case puts every pre-activation into the left tail (y in about -6 .. -4, beta = -5),
-where nothing cancels and the bare rule holds throughout: a GELU formed as 1 + erf misses it there by 20 ulps.  Module: tests/test_w2v_gpu.py's two,
+where nothing cancels and the bare rule holds throughout: a GELU formed as 1 + erf would miss it there by 20 ulps.  Module: tests/test_w2v_gpu.py's two,
 (a) <= BOUND_A against the restatement with bf16 storage, (b) <= 2 x the bf16-storage restatement's own error against the exact one."""
 import pytest
 import torch
