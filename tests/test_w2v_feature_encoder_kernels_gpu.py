@@ -29,20 +29,26 @@ FOLD_IDS = [f"k{k}-s{s}-T{T}-C{C}" for k, s, T, C in FOLD_CASES]
 _fold, _l0 = {}, {}
 
 
-def _fold_case(k, s, T_in, C):
-    """bf16 x and dwin, and on them in float64: dx = d/dx <dwin, window(gelu(x))> and sum |terms| (the same with |dwin|, in absolute value)"""
-    key = (k, s, T_in, C)
+def _fold_case(k, s, T_in, C, n=N):
+    """bf16 x and dwin of ``n`` clips, and on them in float64: dx = d/dx <dwin, window(gelu(x))> and sum |terms| (the same with |dwin|, in
+    absolute value)"""
+    key = (k, s, T_in, C) if n == N else (k, s, T_in, C, n)
     if key not in _fold:
         g = torch.Generator().manual_seed(1000 * k + 100 * s + T_in + C)
         T_out = (T_in - k) // s + 1
-        x = (1.5 * torch.randn(N, T_in, C, generator=g)).to(BF16)
-        dwin = torch.randn(N, T_out, k * C, generator=g).to(BF16)
+        x = (1.5 * torch.randn(n, T_in, C, generator=g)).to(BF16)
+        dwin = torch.randn(n, T_out, k * C, generator=g).to(BF16)
         xd = x.double().requires_grad_(True)
         out = w2v_ref.window(w2v_ref.gelu_erf(xd), k, s)
         (dx,) = torch.autograd.grad(out, xd, dwin.double(), retain_graph=True)
         (terms,) = torch.autograd.grad(out, xd, dwin.double().abs())
         _fold[key] = dict(x=x, dwin=dwin, dx=dx, terms=terms.abs(), T_out=T_out, last=s * (T_out - 1) + k - 1)
     return _fold[key]
+
+
+def fold_bound(c):
+    """the module docstring's bound of the fold, per element of dx"""
+    return 2.0 ** -8 * c["dx"].abs() + 1e-6 * c["terms"]
 
 
 def _run_fold(c, k, s, T_in, C, in_place=False):
@@ -60,7 +66,7 @@ def test_window_fold_against_float64(k, s, T_in, C):
     got = _run_fold(c, k, s, T_in, C)
     assert bool(torch.isfinite(got).all()), "a row of dx was skipped (the output was prefilled with NaN)"
     err = (got.double() - c["dx"]).abs()
-    bound = 2.0 ** -8 * c["dx"].abs() + 1e-6 * c["terms"]
+    bound = fold_bound(c)
     worst = float((err / bound.clamp_min(1e-300)).max())
     print(f"window_fold_gelu_bwd k={k} s={s} T_in={T_in} C={C}: worst |got - exact| / bound {worst:.3f}, rel L2 {l2_rel(got, c['dx']):.3e}, "
           f"{T_in - 1 - c['last']} unread frame(s)")

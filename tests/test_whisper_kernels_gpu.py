@@ -223,6 +223,12 @@ def test_gelu_window_within_one_bf16_ulp_of_float64(C, T_in, k, s, pad):
     assert torch.equal(again.t.view(torch.int16), out.t.view(torch.int16))
 
 
+def stem_out_allowance(v, act, want):
+    """the module docstring's allowance of ``mmf_whisper_stem_out``: the GELU's (tests/gelu_domain.py) with its store term moved to
+    the sum ``want`` = act + position, and 2^-24 of the sum for the f32 add of the position"""
+    return 0.5 * _bf16_ulp(want) + 2.0 ** -24 * want.abs() + (gelu_domain.allow_fwd(v, act) - 0.5 * _bf16_ulp(act))
+
+
 @pytest.mark.parametrize("d,T", [(d, T) for d in (128, 384) for T in (1, 37, 40)])
 def test_stem_out_within_one_bf16_ulp_of_float64(d, T):
     n = 2
@@ -231,7 +237,7 @@ def test_stem_out_within_one_bf16_ulp_of_float64(d, T):
     v = x.float() + bias                                              # the f32 sum the kernel forms, exactly
     act = gelu_domain.gelu64(v)
     want = act + pos.double().repeat(n, 1)
-    tol = 0.5 * _bf16_ulp(want) + 2.0 ** -24 * want.abs() + (gelu_domain.allow_fwd(v, act) - 0.5 * _bf16_ulp(act))
+    tol = stem_out_allowance(v, act, want)
     xd, bd, pd = x.to(DEV), bias.to(DEV), pos.to(DEV)
     keep = xd.clone()
     out = Guarded((n * T, d), BF16)
